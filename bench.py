@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- Mblocks/s of the hot path (MF::calcMotionBlockMatching) on MI355X.
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one whole pyramid (search + regulariser of every level + dense expansion) over one
@@ -9,6 +9,11 @@ synthetic 4K frame pair per GPU (BASELINE.json configs[2]; configs[4] for N > 1:
 GPU, dense .flo fields gathered to rank 0 over RCCL).  Frames are resident in HBM before the
 timed region; the pyramid build (the reference's constructor, outside its own timed region,
 main_class.cpp:45-55) is not part of a step.  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`).
+`--full` adds every other leg: sequences, host boundary, per-kernel and roofline figures, EPE,
+the Jacobi regulariser, the other workloads and the CPU baseline with its parity check.
+`--dump-outputs DIR` writes the field of the last timed step as DIR/*.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -127,10 +132,15 @@ def epe_on_ground_truth(bbme, device, jacobi=False):
     levels, block 32, search 64, every 4th pixel / 4; main_class.cpp:19-21,32-33,58-70) against Middlebury
     ground truth.  The Middlebury frames are not in the reference (only its GT .flo files are), so the pair
     is a texture warped by the Venus ground truth, which makes that file the true flow of the pair."""
-    gt_path = os.path.join(ROOT, "tests", "golden", "gt_Venus_flow10.flo")
-    if not os.path.exists(gt_path):
+    import gzip
+    gz_path = os.path.join(ROOT, "tests", "golden", "gt_Venus_flow10.flo.gz")
+    if not os.path.exists(gz_path):
         return None
-    gt = bbme.Flow().ReadFlowFile(gt_path)
+    with tempfile.TemporaryDirectory(prefix="bbme_gt_") as tmp:
+        gt_path = os.path.join(tmp, "gt_Venus_flow10.flo")
+        with gzip.open(gz_path, "rb") as src, open(gt_path, "wb") as dst:
+            dst.write(src.read())
+        gt = bbme.Flow().ReadFlowFile(gt_path)
     h, w = gt.shape[:2]
     f1, f2 = bbme.warp_pair_from_flow(gt)
     u1, u2 = bbme.resize_x4(f1), bbme.resize_x4(f2)
@@ -142,6 +152,22 @@ def epe_on_ground_truth(bbme, device, jacobi=False):
     return {"value": round(bbme.Flow().CalculateMSE(gt, sub), 6), "unit": "px",
             "data": "texture warped by Middlebury Venus flow10.flo (420x380); reference pipeline: x4 bilinear, "
                     "4 levels, 32x32 blocks, search 64"}
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(out_dir, fields):
+    """The dense fields the timed path handed out in its last step ({name: (H, W, 2) float32}), as out_dir/<name>.npy.  The
+    field is constant on 2x2 cells (k_expand writes it from the cell grid), so every second row and column holds all of it
+    (16.7 MB at 4K); with several fields (N > 1) the stride doubles until they fit in DUMP_BYTES_MAX together."""
+    os.makedirs(out_dir, exist_ok=True)
+    stride = 2
+    while sum(f[::stride, ::stride].nbytes for f in fields.values()) > DUMP_BYTES_MAX:
+        stride *= 2
+    for name, f in fields.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(f[::stride, ::stride], dtype=np.float32))
+    return stride
 
 
 def cgroup_cpu_quota():
@@ -327,6 +353,13 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="cfg3", choices=HEADLINE_WORKLOADS)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the dense field(s) of the last timed step as DIR/flow.npy (N > 1: DIR/flow_rank<r>.npy, rank 0), "
+                         "float32, every second row and column (the field is constant on 2x2 cells)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: sequence and host-boundary legs, per-kernel / roofline figures, EPE, the Jacobi "
+                         "regulariser, the other workloads and the CPU baseline with the parity check (the options below "
+                         "only shape these legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--profile-iters", type=int, default=5)
     ap.add_argument("--no-other-workloads", action="store_true", help="skip the `other_workloads` legs (cfg2, cfg4, cfg1, ref, ref2)")
@@ -435,8 +468,15 @@ def main():
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
 
-    result_flow = mf.get_flow() if rank == 0 else None
-    if use_dist and rank == 0:
+    result_flow = mf.get_flow() if rank == 0 and (args.full or args.dump_outputs) else None
+    if rank == 0 and args.dump_outputs:
+        if use_dist:
+            gathered = gather.flows.cpu().numpy()
+            dump_outputs(args.dump_outputs, {"flow_rank%d" % r: gathered[r] for r in range(world)})
+            del gathered
+        else:
+            dump_outputs(args.dump_outputs, {"flow": result_flow})
+    if use_dist and rank == 0 and args.full:
         # the field rank 0 expanded from its own gathered cells must be the field its context holds
         assert np.array_equal(gather.flows[0].cpu().numpy(), result_flow), "gathered + expanded field differs"
 
@@ -444,7 +484,7 @@ def main():
     # One pair leaves most of the chip idle while the regulariser walks its dependency chains, so
     # pairs of a sequence overlap well.  Reported as `sequence`, beside the single-pair `value`.
     sequence = sequence_deep = None
-    if rank == 0 and not use_dist and args.in_flight > 1:
+    if args.full and rank == 0 and not use_dist and args.in_flight > 1:
         # Pairs that share a GPU go into BATCHED contexts (bbme_create_batch: every kernel works on all pairs of the context
         # at once): the device dispatches the dependent kernels of many streams no faster than one per ~4 us chip-wide, so
         # one context per pair is dispatch-bound (69 launches per pair); `--seq-batch` pairs per context, in_flight / batch
@@ -501,7 +541,7 @@ def main():
     # the boundary with host buffers (never `value`): frames in (pinned) host memory -> upload (2 x 8.3 MB at 4K), padding +
     # pyramid on the GPU, estimate, download of the dense field (66.8 MB) or of the compact 2x2-cell grid (4.2 MB)
     host_boundary = None
-    if rank == 0 and not use_dist and not args.no_host_boundary:
+    if args.full and rank == 0 and not use_dist and not args.no_host_boundary:
         p1, p2 = torch.from_numpy(f1).pin_memory(), torch.from_numpy(f2).pin_memory()
         reps = 9
 
@@ -582,7 +622,7 @@ def main():
 
     # per-kernel timing with HIP events on the ctx stream (eager launches, same kernels and data)
     prof = None
-    if rank == 0:
+    if args.full and rank == 0:
         mf.set_profiling(True)
         acc = {}
         for _ in range(args.profile_iters):
@@ -592,9 +632,26 @@ def main():
         mf.set_profiling(False)
         prof = {k: val / args.profile_iters for k, val in acc.items()}
 
+    R = (search - block) >> 1
+    units = blocks[0] * world
     if rank == 0:
-        R = (search - block) >> 1
-        units = blocks[0] * world
+        value = units * args.steps / elapsed / 1e6
+        out = {
+            "metric": "Mblocks/s (16x16, +-32 full search)", "value": round(value, 4), "unit": "Mblocks/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "config": {"workload": desc, "pairs_per_step": world, "frame": [w, h], "padded": [pw, ph],
+                       "block": block, "search_range": R, "levels": levels,
+                       "blocks_level0": blocks[0], "blocks_all_levels": sum(blocks),
+                       "multi_gpu": ("one pair per GPU; int16 cell grids gathered on rank 0 over RCCL and expanded there to "
+                                     "the dense .flo fields (" + dist_mode_text + "; ms per step measured before the timed "
+                                     "region: " + ", ".join("%.3f %s" % (t, "speculative" if sp else "plain/overlapped")
+                                                            for t, _, sp, _ in dist_calibration) + ")")
+                                    if use_dist else "single GPU"},
+        }
+
+    if args.full and rank == 0:
         # the binding ceiling is the issue rate of the SAD instructions; measure it on this device
         import ctypes as C
         from blockbasedmotionestimation_amd import _capi
@@ -604,7 +661,6 @@ def main():
         sad_peak = rates[1] * 64 * 4 / 1e3            # T abs-diff/s through v_sad_u8
         loops = (C.c_double * 2)()
         _capi.check(_capi.lib().bbme_probe_search_loops(local_rank, loops))
-        value = units * args.steps / elapsed / 1e6
         # dominant kernel (by arithmetic): k_search_fast<B, W>, one launch per level.  Algorithmic bytes per block
         # = B^2 + (B+2R)^2 + 8; "per launch" = mean over the `levels` launches of a pyramid.
         bytes_per_block = block * block + (block + 2 * R) ** 2 + 8
@@ -620,19 +676,7 @@ def main():
         ms_step = elapsed / args.steps * 1e3
         step_absdiff = sum(blocks) * (2 * R + 1) ** 2 * block * block * world      # the searches of one step, all levels
         step_tabs = step_absdiff / (ms_step * 1e-3) / 1e12
-        out = {
-            "metric": "Mblocks/s (16x16, +-32 full search)", "value": round(value, 4), "unit": "Mblocks/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-            "config": {"workload": desc, "pairs_per_step": world, "frame": [w, h], "padded": [pw, ph],
-                       "block": block, "search_range": R, "levels": levels,
-                       "blocks_level0": blocks[0], "blocks_all_levels": sum(blocks),
-                       "multi_gpu": ("one pair per GPU; int16 cell grids gathered on rank 0 over RCCL and expanded there to "
-                                     "the dense .flo fields (" + dist_mode_text + "; ms per step measured before the timed "
-                                     "region: " + ", ".join("%.3f %s" % (t, "speculative" if sp else "plain/overlapped")
-                                                            for t, _, sp, _ in dist_calibration) + ")")
-                                    if use_dist else "single GPU"},
+        out.update({
             # contract fields (achieved / peak / unit / frac / traffic) are the HBM figures; what BINDS the kernel is the issue
             # rate of the integer SAD instructions, priced in `binding` against the chip's spec rate
             "roofline": {"bound": "valu", "kernel": "k_search_fast<%d, W> (mean of the %d per-level launches; W = 2 waves per macroblock on levels of "
@@ -668,7 +712,7 @@ def main():
                              "achieved": round(step_tabs, 3), "peak": VALU_SAD_PEAK_T, "frac": round(step_tabs / VALU_SAD_PEAK_T, 5),
                              "note": "search abs-diffs of every level / the timed step (search + regulariser + expand); "
                                      "roofline.binding prices the search launches alone"},
-        }
+        })
         # the regulariser takes most of the step although it is 2 % of the arithmetic: every sweep is a
         # chain of dependent block updates.  Algorithmic bytes of a sweep at block size b: per b x b block
         # its own pixels, nine candidate blocks (10 b^2) and nine MVs in, one out (40).
@@ -730,6 +774,8 @@ def main():
                                                          "(calcLevelBM), regulariser sweeps sequential"},
                                    "host": {"cpu_model": model, "nproc": nproc, "usable_cores": usable, "cgroup_quota": quota_text}}
             out["parity_vs_oracle"] = bool(par1 and parn)
+
+    if rank == 0:
         if saved_stdout is not None:
             sys.stdout.flush()
             os.dup2(saved_stdout, 1)

@@ -9,7 +9,7 @@ TMP=$(mktemp -d)
 for i in $(seq $N); do
   for j in "${!CFG[@]}"; do
     c="${CFG[$j]}"; [ "$c" = "-" ] && c="BBME_DUMMY=1"
-    env $c timeout -k 10 120 python3 bench.py --workload $WL --steps 60 --warmup 5 --no-cpu-baseline --no-other-workloads --no-host-boundary --in-flight 0 --profile-iters 2 2>/dev/null |
+    env $c timeout -k 10 120 python3 bench.py --full --workload $WL --steps 60 --warmup 5 --no-cpu-baseline --no-other-workloads --no-host-boundary --in-flight 0 --profile-iters 2 2>/dev/null |
       python3 -c "import sys,json; d=json.loads(sys.stdin.read()); print(d['ms_per_step'], d['device_ms']['regularize_ms'])" >> $TMP/$j.txt
   done
 done

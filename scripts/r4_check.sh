@@ -6,7 +6,7 @@ mkdir -p $OUT
 cd $REPO
 timeout -k 10 500 python3 -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1 || { tail -30 $OUT/pytest.log; exit 1; }
 echo "tests done"; tail -2 $OUT/pytest.log
-timeout -k 10 300 python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --in-flight 8 --in-flight-deep 24 --no-host-boundary "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
+timeout -k 10 300 python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --in-flight 8 --in-flight-deep 24 --no-host-boundary "$@" > $OUT/bench.json 2> $OUT/bench.err || { tail $OUT/bench.err; exit 1; }
 python3 - <<PY
 import json
 d=json.loads(open("$OUT/bench.json").readline())

@@ -10,7 +10,7 @@ echo "tests done"; tail -2 $OUT/pytest.log
 for cfg in "BBME_MEMO=0" "BBME_MEMO=1 BBME_MEMO_FORWARD=0" "BBME_MEMO=1 BBME_MEMO_FORWARD=1"; do
   tag=$(echo $cfg | tr ' =' '__')
   env $cfg timeout -k 10 200 python3 scripts/sweep_timeline.py > $OUT/sweeps_$tag.txt 2>&1 || { tail $OUT/sweeps_$tag.txt; exit 1; }
-  env $cfg timeout -k 10 200 python3 bench.py --steps 40 --warmup 5 --no-cpu-baseline --in-flight 8 --in-flight-deep 24 --no-other-workloads --no-host-boundary > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err || { tail $OUT/bench_$tag.err; exit 1; }
+  env $cfg timeout -k 10 200 python3 bench.py --full --steps 40 --warmup 5 --no-cpu-baseline --in-flight 8 --in-flight-deep 24 --no-other-workloads --no-host-boundary > $OUT/bench_$tag.json 2> $OUT/bench_$tag.err || { tail $OUT/bench_$tag.err; exit 1; }
   python3 - <<PY
 import json
 d=json.loads(open("$OUT/bench_$tag.json").readline())

@@ -10,7 +10,7 @@ i=0
 for setting in "$@"; do
   i=$((i+1))
   [ "$setting" = "-" ] || export $setting
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s$i -- python3 $REPO/bench.py --steps 30 --warmup 3 --no-cpu-baseline --in-flight 0 --no-other-workloads --no-host-boundary --profile-iters 1 > $OUT/s$i.log 2>&1 || exit 1
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/s$i -- python3 $REPO/bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --in-flight 0 --no-other-workloads --no-host-boundary --profile-iters 1 > $OUT/s$i.log 2>&1 || exit 1
   [ "$setting" = "-" ] || for kv in $setting; do unset ${kv%%=*}; done
   find $OUT/s$i -name "*kernel_trace.csv" -delete; find $OUT/s$i -name "*.db" -delete
   echo "== $setting"; python3 - $OUT/s$i <<'PY'

@@ -2,7 +2,7 @@
 """One graph replay of the pyramid from a rocprofv3 kernel trace (speculative search on): start, end, duration in us of every
 search launch, with the regulariser launches between them folded into one line per group.
 
-    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 8 --warmup 2 --no-cpu-baseline --profile-iters 1 --in-flight 0 --no-host-boundary
+    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --profile-iters 1 --in-flight 0 --no-host-boundary
     python scripts/spec_timeline.py OUT"""
 import csv, glob, os, sys
 f = max(glob.glob(sys.argv[1] + '/**/*kernel_trace.csv', recursive=True), key=os.path.getmtime)

@@ -2,7 +2,7 @@
 """Per-sweep kernel durations (us) of the graph-replayed pyramids in a rocprofv3 kernel trace, averaged over the
 pyramids of the timed loop (the asynchronous solver's schedule differs from replay to replay):
 
-    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --profile-iters 1
+    rocprofv3 --kernel-trace --output-format csv -d OUT -- python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --profile-iters 1
     python scripts/trace_table.py OUT
 
 One line per level: the search, then per sweep  pass1+[relaxation]+solve."""

@@ -1,3 +1,4 @@
+import gzip
 import os
 import sys
 
@@ -44,3 +45,13 @@ def bbme():
 
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+@pytest.fixture(scope="session")
+def venus_flo(tmp_path_factory):
+    """Path of the Venus ground-truth .flo, unpacked from tests/golden/gt_Venus_flow10.flo.gz (the .flo itself is larger
+    than a committed file may be)."""
+    path = tmp_path_factory.mktemp("golden") / "gt_Venus_flow10.flo"
+    with gzip.open(os.path.join(GOLDEN, "gt_Venus_flow10.flo.gz"), "rb") as f:
+        path.write_bytes(f.read())
+    return str(path)

@@ -11,20 +11,28 @@
 2. flo_ramp_ref.flo -- a 7x5 .flo written by the REFERENCE's own Middlebury code
    (middlebury/flow-code/flowIO.cpp, compiled into oracle/_ref/flo_ref): pins the codec.
 3. gt_stats.json -- known answers computed with the reference's own reader on the 8 ground-truth
-   files it ships (size, unknown-pixel count, sums, sha256), plus gt_Venus_flow10.flo copied as
-   data (smallest GT file) so the GPU box can run the known-answer test without /root/reference.
+   files it ships (size, unknown-pixel count, sums, sha256), plus the Venus file (the smallest) as
+   data, gzipped (gt_Venus_flow10.flo.gz; the .flo itself is larger than a committed file may be),
+   so that the known-answer tests need no copy of the reference.
 4. color_ref.npz -- colour coding made by the REFERENCE's own vendored colour-wheel code
    (middlebury/flow-code/colorcode.cpp computeColor, compiled into oracle/_ref/flo_ref, called by
    oracle/ref_flo_driver.cpp): Venus ground truth with the automatic radius and with maxmotion 3.5
    (exercises the out-of-range branch), and a synthetic wheel field (all angles, radii 0..1.5,
    some unknown pixels).  gt_stats.json also gets the sha256 of that output for all 8 GT files.
+5. gt_samples.npz -- every GT_STRIDE-th row and column of each of the 8 GT files (the whole files are
+   too large to commit), written by the oracle and read + rewritten by the REFERENCE's flowIO.cpp
+   (flo_ref roundtrip; the bytes must come back unchanged), with the reference's stats of the sample
+   and its colour coding (flo_ref color, automatic radius).  `python tests/golden/make_golden.py
+   gt_samples` rewrites this file alone.
 """
+import gzip
 import hashlib
 import json
 import os
 import shutil
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 
@@ -99,6 +107,30 @@ def wheel_field():
     return f
 
 
+GT_STRIDE = 8
+
+
+def make_gt_samples(flo_ref, gt_dir):
+    data = {}
+    tmp = tempfile.mkdtemp(prefix="bbme_gt_")
+    mine, ref = os.path.join(tmp, "sample.flo"), os.path.join(tmp, "sample_ref.flo")
+    for seq in sorted(os.listdir(gt_dir)):
+        sample = O.flo_read(os.path.join(gt_dir, seq, "flow10.flo"))[::GT_STRIDE, ::GT_STRIDE]
+        O.flo_write(mine, sample)
+        subprocess.check_call([flo_ref, "roundtrip", mine, ref])
+        raw = open(ref, "rb").read()
+        assert raw == open(mine, "rb").read(), seq
+        w, h, unk, su, sv = subprocess.check_output([flo_ref, "stats", ref]).decode().split()
+        assert (int(h), int(w)) == sample.shape[:2]
+        data[seq + "_flo"] = np.frombuffer(raw, np.uint8)
+        data[seq + "_unknown"] = np.array(int(unk), np.int64)
+        data[seq + "_sums"] = np.array([float(su), float(sv)], np.float64)
+        data[seq + "_color"] = color_by_reference(flo_ref, ref, sample.shape[:2])
+    shutil.rmtree(tmp)
+    np.savez_compressed(os.path.join(HERE, "gt_samples.npz"), stride=np.array(GT_STRIDE, np.int64), **data)
+    print("gt samples:", {k[:-4]: v.shape for k, v in data.items() if k.endswith("_flo")})
+
+
 def color_by_reference(flo_ref, flo_path, shape, maxmotion=None):
     out = os.path.join("/tmp", "bbme_color_ref.bgr")
     cmd = [flo_ref, "color", flo_path, out] + ([repr(maxmotion)] if maxmotion else [])
@@ -111,6 +143,10 @@ def main():
     if sys.argv[1:] == ["variants"]:
         for name, cfg in VARIANTS.items():
             make_hotpath(name, *cfg)
+        return
+    if sys.argv[1:] == ["gt_samples"]:
+        assert os.path.exists(O.FLO_REF), "oracle/_ref/flo_ref missing (needs the reference)"
+        make_gt_samples(O.FLO_REF, os.path.join(REF, "middlebury", "gt-flow"))
         return
     if len(sys.argv) == 3 and sys.argv[1] == "only":          # one hot-path case; the other files are not rewritten
         make_hotpath(sys.argv[2], *{**CASES, **VARIANTS}[sys.argv[2]])
@@ -141,8 +177,10 @@ def main():
                         wheel_flow=wheel,
                         wheel_auto=color_by_reference(flo_ref, wheel_path, wheel.shape),
                         wheel_max40=color_by_reference(flo_ref, wheel_path, wheel.shape, 40.0))
-    shutil.copyfile(os.path.join(gt_dir, "Venus", "flow10.flo"), os.path.join(HERE, "gt_Venus_flow10.flo"))
-    os.chmod(os.path.join(HERE, "gt_Venus_flow10.flo"), 0o644)
+    with open(venus, "rb") as src, open(os.path.join(HERE, "gt_Venus_flow10.flo.gz"), "wb") as raw:
+        with gzip.GzipFile(filename="", mode="wb", fileobj=raw, compresslevel=9, mtime=0) as dst:
+            shutil.copyfileobj(src, dst)
+    make_gt_samples(flo_ref, gt_dir)
     print("gt stats:", {k: (v["width"], v["height"], v["unknown"]) for k, v in stats.items()})
 
 

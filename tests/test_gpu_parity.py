@@ -497,15 +497,13 @@ def test_cli_reproduces_reference_driver_sequence(bbme, oracle, tmp_path):
     assert ("max motion: %.4f  motion range: u = %.3f .. %.3f;  v = %.3f .. %.3f" % rng) in r.stdout
 
 
-def test_epe_against_middlebury_ground_truth_warped_pair(bbme, oracle):
+def test_epe_against_middlebury_ground_truth_warped_pair(bbme, oracle, venus_flo):
     """BASELINE configs[0] asks for EPE against Middlebury ground truth.  The Middlebury frames are
     not in the reference (only the GT .flo files are), so the pair is synthetic: frame2 is a texture
     and frame1(x) = frame2(x + gt(x)) by bilinear sampling, which makes the Venus GT file the true
     flow of the pair.  The reference's own pipeline and literals (4x up-sampling, 4 levels, block 32,
     search 64) must then give the same EPE on the HIP path and on the oracle, and a small one."""
-    import os
-    from conftest import GOLDEN
-    gt = bbme.Flow().ReadFlowFile(os.path.join(GOLDEN, "gt_Venus_flow10.flo"))
+    gt = bbme.Flow().ReadFlowFile(venus_flo)
     h, w = gt.shape[:2]
     frame1, frame2 = bbme.warp_pair_from_flow(gt)
     search, block = [64] * 4, [32] * 4

@@ -104,7 +104,7 @@ def test_pad_pyrdown_resize_match_oracle(bbme, oracle):
     assert np.all(bbme.pyr_down(c) == 201) and np.all(bbme.resize_x4(c) == 201)
 
 
-def test_flow_class_codec_and_epe(bbme, oracle, tmp_path):
+def test_flow_class_codec_and_epe(bbme, oracle, tmp_path, venus_flo):
     flow = bbme.Flow()
     ref_file = os.path.join(GOLDEN, "flo_ramp_ref.flo")
     f = flow.ReadFlowFile(ref_file)
@@ -112,7 +112,7 @@ def test_flow_class_codec_and_epe(bbme, oracle, tmp_path):
     out = tmp_path / "w.flo"
     flow.WriteFlowFile(f, str(out))
     assert out.read_bytes() == open(ref_file, "rb").read()
-    venus = flow.ReadFlowFile(os.path.join(GOLDEN, "gt_Venus_flow10.flo"))
+    venus = flow.ReadFlowFile(venus_flo)
     assert venus.shape == (380, 420, 2)
     rng = np.random.default_rng(9)
     est = venus + rng.normal(0, 1.5, venus.shape).astype(np.float32)
@@ -126,13 +126,13 @@ def test_flow_class_codec_and_epe(bbme, oracle, tmp_path):
     assert np.array_equal(sub, oracle.subsample_div4(np.arange(64 * 48 * 2, dtype=np.float32).reshape(48, 64, 2), 4, 8, 14, 8))
 
 
-def test_motion_to_color_equals_oracle(bbme, oracle, tmp_path, capsys):
+def test_motion_to_color_equals_oracle(bbme, oracle, tmp_path, capsys, venus_flo):
     """Flow::MotionToColor / ShowImage of the product against the oracle (bit-exact) and against the image the
     reference's vendored colorcode.cpp made (tests/golden/color_ref.npz; one level in a handful of channels,
     see test_colour_coding_pinned_by_reference_colorcode)."""
     flow = bbme.Flow()
     ref = np.load(os.path.join(GOLDEN, "color_ref.npz"), allow_pickle=False)
-    venus = flow.ReadFlowFile(os.path.join(GOLDEN, "gt_Venus_flow10.flo"))
+    venus = flow.ReadFlowFile(venus_flo)
     rng = np.random.default_rng(21)
     noisy = (rng.normal(0, 6, (97, 131, 2))).astype(np.float32)
     noisy[3, 4] = np.nan

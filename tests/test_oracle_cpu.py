@@ -4,16 +4,12 @@ restatement against an independently structured numpy restatement and the commit
 import hashlib
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from conftest import GOLDEN
 from helpers import oracle_schedule
-
-REF_GT = "/root/reference/middlebury/gt-flow"
-
 
 def load_golden(name):
     return np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
@@ -153,11 +149,11 @@ def test_flo_writer_is_byte_identical_to_reference(oracle, tmp_path):
     assert ref[:4] == b"PIEH" and len(ref) == 12 + 7 * 5 * 8
 
 
-def test_gt_known_answers(oracle):
+def test_gt_known_answers(oracle, venus_flo):
     """Venus ground truth (a data file of the reference) against numbers computed with the
     reference's own reader (tests/golden/gt_stats.json, made by make_golden.py)."""
     stats = json.load(open(os.path.join(GOLDEN, "gt_stats.json")))["Venus"]
-    p = os.path.join(GOLDEN, "gt_Venus_flow10.flo")
+    p = venus_flo
     assert hashlib.sha256(open(p, "rb").read()).hexdigest() == stats["sha256"]
     f = oracle.flo_read(p)
     assert f.shape == (stats["height"], stats["width"], 2)
@@ -172,14 +168,14 @@ def test_gt_known_answers(oracle):
     assert oracle.calculate_mse(f, g) == pytest.approx(5.0, abs=1e-5)
 
 
-def test_colour_coding_pinned_by_reference_colorcode(oracle):
+def test_colour_coding_pinned_by_reference_colorcode(oracle, venus_flo):
     """Flow::MotionToColor.  tests/golden/color_ref.npz was made by the reference's own vendored colour-wheel
     code (middlebury/flow-code/colorcode.cpp, compiled into oracle/_ref).  The oracle's `vendored` flavour
     (that file's double sub-expressions) must reproduce it bit for bit; the rw_flow.cpp flavour (float
     sub-expressions, rw_flow.cpp:258,264-265 -- the one the product follows) may differ from it by one level
     in a handful of channel values and nowhere else."""
     ref = np.load(os.path.join(GOLDEN, "color_ref.npz"), allow_pickle=False)
-    venus = oracle.flo_read(os.path.join(GOLDEN, "gt_Venus_flow10.flo"))
+    venus = oracle.flo_read(venus_flo)
     cases = [(venus, -1.0, "venus_auto"), (venus, 3.5, "venus_max3p5"),
              (ref["wheel_flow"], -1.0, "wheel_auto"), (ref["wheel_flow"], 40.0, "wheel_max40")]
     for flow, maxmotion, key in cases:
@@ -204,35 +200,55 @@ def test_colour_coding_pinned_by_reference_colorcode(oracle):
     assert zr[0] == 0.0 and (zero == 255).all()                # maxrad 0 -> 1, every pixel white
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GT), reason="reference data only exists in the build container")
-def test_colour_coding_of_all_gt_files_equals_reference(oracle, tmp_path):
+def gt_samples(tmp_path):
+    """{sequence: (path of its sample .flo, fixture arrays)} of tests/golden/gt_samples.npz: every `stride`-th row and column
+    of each of the reference's 8 ground-truth files, as bytes written by the reference's WriteFlowFile, with the reference's
+    stats and colour coding of the sample (make_golden.py)."""
+    g = np.load(os.path.join(GOLDEN, "gt_samples.npz"), allow_pickle=False)
     stats = json.load(open(os.path.join(GOLDEN, "gt_stats.json")))
+    assert sorted(k[:-len("_flo")] for k in g.files if k.endswith("_flo")) == sorted(stats)
+    stride = int(g["stride"])
+    out = {}
     for seq, st in stats.items():
-        p = os.path.join(REF_GT, seq, "flow10.flo")
+        p = tmp_path / (seq + "_sample.flo")
+        p.write_bytes(g[seq + "_flo"].tobytes())
+        out[seq] = (str(p), {"width": -(-st["width"] // stride), "height": -(-st["height"] // stride),
+                             "unknown": int(g[seq + "_unknown"]), "sums": g[seq + "_sums"], "color": g[seq + "_color"]})
+    return out
+
+
+def test_colour_coding_of_all_gt_files_equals_reference(oracle, tmp_path, venus_flo):
+    """The oracle's vendored colour coding of a sample of every GT file against the reference's colorcode.cpp on it, and of
+    the whole Venus file against the digest of the reference's (gt_stats.json)."""
+    got, _ = oracle.motion_to_color(oracle.flo_read(venus_flo), vendored=True)
+    stats = json.load(open(os.path.join(GOLDEN, "gt_stats.json")))
+    assert hashlib.sha256(got.tobytes()).hexdigest() == stats["Venus"]["color_sha256"]
+    for seq, (p, ref) in gt_samples(tmp_path).items():
         got, _ = oracle.motion_to_color(oracle.flo_read(p), vendored=True)
-        assert hashlib.sha256(got.tobytes()).hexdigest() == st["color_sha256"], seq
-        out = tmp_path / (seq + ".bgr")
-        subprocess.check_call([oracle.FLO_REF, "color", p, str(out)])
-        assert out.read_bytes() == got.tobytes()
+        assert got.shape == (ref["height"], ref["width"], 3), seq
+        assert np.array_equal(got, ref["color"]), seq
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_GT), reason="reference data only exists in the build container")
-def test_all_gt_files_roundtrip_through_reference_and_oracle(oracle, tmp_path):
-    stats = json.load(open(os.path.join(GOLDEN, "gt_stats.json")))
-    for seq, st in stats.items():
-        p = os.path.join(REF_GT, seq, "flow10.flo")
+def test_all_gt_files_roundtrip_through_reference_and_oracle(oracle, tmp_path, venus_flo):
+    """A sample of every GT file: the reference read the oracle's file and wrote these bytes back unchanged; the oracle must
+    read them as the reference did (unknown pixels, sums) and write them back byte for byte.  The whole Venus file too."""
+    raw = open(venus_flo, "rb").read()
+    out = tmp_path / "venus.flo"
+    oracle.flo_write(str(out), oracle.flo_read(venus_flo))
+    assert out.read_bytes() == raw
+    for seq, (p, ref) in gt_samples(tmp_path).items():
         raw = open(p, "rb").read()
-        assert len(raw) == st["bytes"] == 12 + 8 * st["width"] * st["height"]
-        assert hashlib.sha256(raw).hexdigest() == st["sha256"]
+        assert len(raw) == 12 + 8 * ref["width"] * ref["height"]
         f = oracle.flo_read(p)
+        assert f.shape == (ref["height"], ref["width"], 2)
         out = tmp_path / (seq + ".flo")
         oracle.flo_write(str(out), f)
-        assert out.read_bytes() == raw
-        ref_out = tmp_path / (seq + "_ref.flo")
-        subprocess.check_call([oracle.FLO_REF, "roundtrip", str(out), str(ref_out)])
-        assert ref_out.read_bytes() == raw
-        unk = int(((np.abs(f) > 1e9).any(-1)).sum())
-        assert unk == st["unknown"]
+        assert out.read_bytes() == raw, seq
+        unknown = (np.abs(f) > 1e9).any(-1)
+        assert int(unknown.sum()) == ref["unknown"], seq
+        known = f[~unknown].astype(np.float64)
+        assert known[:, 0].sum() == pytest.approx(ref["sums"][0], rel=1e-12, abs=1e-9), seq
+        assert known[:, 1].sum() == pytest.approx(ref["sums"][1], rel=1e-12, abs=1e-9), seq
 
 
 def test_flo_read_rejects_what_the_reference_rejects(oracle, tmp_path):
