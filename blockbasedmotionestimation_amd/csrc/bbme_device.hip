@@ -7,6 +7,8 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
+#include <mutex>
 #include <vector>
 
 #include "bbme_internal.hpp"
@@ -106,6 +108,9 @@ struct bbme_ctx {
     bool solve_share = true;                      // k_reg_solve: idle waves of a workgroup take a sibling's surplus; BBME_SOLVE_SHARE=0
     int solve_wgs = 256;                          // most workgroups of k_reg_solve (4 independent waves each); r04: 256 measured 1.5 % ahead of 128 (one wave per SIMD)
     int xcd_remap = 1;                            // XCD-aware block order in k_search_fast; BBME_XCD_REMAP
+    bool loose_plan = false;                      // the round-2 search plan without rim rounds; BBME_LOOSE_PLAN
+    long long relax_min_blocks = 300000;          // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (launch_sweep)
+    int relax_max_b = 2, relax_s1 = 1, relax_s2 = 0;
     bool jacobi = false;                          // opt-in, not bit-exact: Jacobi sweeps (pass 1 only); bbme_set_regularizer_mode
     bool raster_search = false;                   // MF::find_min_block (:246-294) instead of the spiral search; bbme_set_search_mode
     bool force_generic_search = false;            // BBME_GENERIC_SEARCH=1: use k_search_generic everywhere
@@ -185,6 +190,42 @@ int check_converged(bbme_ctx *c)
 }
 
 // ---- launches ---------------------------------------------------------------------------
+
+// hipFuncAttributeMaxDynamicSharedMemorySize belongs to a kernel, not to a context: every context of the process that launches
+// the kernel on the device depends on it.  So it is only ever raised, to the most any context has asked of it there; a context
+// created later with a smaller window must not lower it under one that is still alive.
+int raise_lds_limit(int device, const void *kernel, size_t bytes)
+{
+    if (bytes <= 48 * 1024) return BBME_OK;                 // what every kernel may use without the attribute
+    static std::mutex mu;
+    static std::map<std::pair<int, const void *>, size_t> granted;
+    std::lock_guard<std::mutex> lock(mu);
+    size_t &cur = granted[{device, kernel}];
+    if (bytes <= cur) return BBME_OK;
+    const hipError_t err = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (err != hipSuccess) return bbme::fail(BBME_ERR_HIP, "%zu bytes of LDS for a search kernel: %s", bytes, hipGetErrorString(err));
+    cur = bytes;
+    return BBME_OK;
+}
+
+const void *search_generic_kernel(int block)
+{
+    switch (block) {
+    case 2:  return reinterpret_cast<const void *>(&k_search_generic<2>);
+    case 4:  return reinterpret_cast<const void *>(&k_search_generic<4>);
+    case 8:  return reinterpret_cast<const void *>(&k_search_generic<8>);
+    case 16: return reinterpret_cast<const void *>(&k_search_generic<16>);
+    case 32: return reinterpret_cast<const void *>(&k_search_generic<32>);
+    default: return reinterpret_cast<const void *>(&k_search_generic<64>);
+    }
+}
+
+const void *search_fast_kernel(int block)
+{
+    if (block == 16) return reinterpret_cast<const void *>(&k_search_fast<16, 1>);
+    if (block == 32) return reinterpret_cast<const void *>(&k_search_fast<32, 1>);
+    return reinterpret_cast<const void *>(&k_search_fast<8, 1>);
+}
 
 template <int B>
 void launch_search_t(const SearchArgs &a, int nblocks, int batch, size_t lds, hipStream_t s)
@@ -458,20 +499,13 @@ int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false)
     const long long nblk = (long long)a.rows * a.cols;
     int steps = c->relax_steps;
     if (steps < 0) {
-        // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (tuning knob)
+        // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (tuning knob, read by bbme_create_batch)
         // (r03: no relaxation launch in front of the second sweep at a block size -- it changes little, and the launch cost more
         // than it took off the solver: 1.760 -> 1.735 ms per cfg3 pair; r04: nor at 4 x 4 -- with the memo-less solver of this
         // round the chain form takes those sweeps' first generations faster than a 40 us launch does: cfg3 1.566 -> 1.547 ms,
         // cfg4 1.605 -> 1.585 ms, interleaved medians of 5 / 4 runs; and, once the solver's waves shared their queues, only on
         // grids of >= 300 000 blocks: cfg3 1.523 -> 1.496, cfg2 0.699 -> 0.680, cfg4 1.611 -> 1.603, reference literals 1.336 -> 1.331)
-        static long long min_blocks = 300000;
-        static int max_b = 2, s1 = 1, s2 = 0;
-        static const bool parsed = [] {
-            if (const char *e = getenv("BBME_RELAX_RULE")) sscanf(e, "%lld,%d,%d,%d", &min_blocks, &max_b, &s1, &s2);
-            return true;
-        }();
-        (void)parsed;
-        steps = (c->relax && nblk >= min_blocks && b <= max_b) ? (mult == 1 ? s1 : s2) : 0;
+        steps = (c->relax && nblk >= c->relax_min_blocks && b <= c->relax_max_b) ? (mult == 1 ? c->relax_s1 : c->relax_s2) : 0;
     }
     switch (b) {
     case 2:  launch_sweep_t<2>(a, c->flags, steps, c->solve_wgs, c->solve_waves, c->jacobi, c->pass1_lanes_max, c->scan_fine_max, c->pass1_strip, c->pass1_lazy, (unsigned)c->batch, c->stream); break;
@@ -672,6 +706,8 @@ int bbme_create_batch(const bbme_params *params, int width, int height, int devi
     if (const char *e = getenv("BBME_MEMO_FORWARD")) c->memo_forward = atoi(e) != 0;
     if (const char *e = getenv("BBME_MEMO_MIN_B")) c->memo_min_block = std::max(8, atoi(e));
     if (const char *e = getenv("BBME_XCD_REMAP")) c->xcd_remap = atoi(e) != 0;
+    c->loose_plan = getenv("BBME_LOOSE_PLAN") != nullptr;
+    if (const char *e = getenv("BBME_RELAX_RULE")) sscanf(e, "%lld,%d,%d,%d", &c->relax_min_blocks, &c->relax_max_b, &c->relax_s1, &c->relax_s2);
     c->lv.resize(nl);
     auto cleanup_fail = [&](int rc) { bbme_destroy(c); return rc; };
     hipError_t err = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
@@ -715,34 +751,27 @@ int bbme_create_batch(const bbme_params *params, int width, int height, int devi
             (err = hipMemset(L.img1, 0, P * plane)) != hipSuccess || (err = hipMemset(L.img2, 0, P * plane)) != hipSuccess ||
             (err = hipMemcpy(L.spiral, packed.data(), packed.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
             return cleanup_fail(bbme::fail(BBME_ERR_HIP, "allocating level %d: %s", l, hipGetErrorString(err)));
+        // the speculative search of this level pads its workgroups to this much LDS (launch_search's lds_floor)
+        const size_t spec_floor = l + 1 < nl ? c->spec_lds_for(params->block_size[l + 1], l) : 0;
         if (!((L.block == 8 || L.block == 16 || L.block == 32) && L.range <= 63)) {
             // the generic kernel (block 4 / 64, or a range beyond the strip kernel's packed keys): its window may need more LDS
-            // than a kernel gets by default
-            if (L.lds_bytes > 48 * 1024) {
-                if (L.lds_bytes > 160 * 1024)
-                    return cleanup_fail(bbme::fail(BBME_ERR_UNSUPPORTED, "level %d: a %dx%d block with range %d needs %zu bytes of LDS", l,
-                                                   L.block, L.block, L.range, L.lds_bytes));
-                const int bytes = (int)L.lds_bytes;
-                switch (L.block) {
-                case 2:  err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_generic<2>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); break;
-                case 4:  err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_generic<4>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); break;
-                case 8:  err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_generic<8>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); break;
-                case 16: err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_generic<16>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); break;
-                case 32: err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_generic<32>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); break;
-                default: err = hipFuncSetAttribute(reinterpret_cast<const void *>(&k_search_generic<64>), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); break;
-                }
-                if (err != hipSuccess)
-                    return cleanup_fail(bbme::fail(BBME_ERR_HIP, "level %d: %zu bytes of LDS for the search window: %s", l, L.lds_bytes, hipGetErrorString(err)));
-            }
+            // than a kernel gets by default (raise_lds_limit below)
+            if (L.lds_bytes > 160 * 1024)
+                return cleanup_fail(bbme::fail(BBME_ERR_UNSUPPORTED, "level %d: a %dx%d block with range %d needs %zu bytes of LDS", l,
+                                               L.block, L.block, L.range, L.lds_bytes));
         } else {
             // the strip kernel reads rank rows dy0 .. dy0+S-1 as 4 x u16 per column group
-            SearchPlan plan = plan_search(L.range, L.block, L.block == 32 ? 8 : 16);
+            SearchPlan plan = plan_search(L.range, L.block, L.block == 32 ? 8 : 16, 64, c->loose_plan);
             L.fast = true;
             L.rank_pitch = sp.rank_pitch;
             L.nrounds = (int)plan.rounds.size();
             L.fast_pitch_dw = plan.pitch_dw;
             // the window (+ for B <= 16 a copy of the block, 16-byte aligned, for the rim rounds of the tight plan)
             L.fast_lds_bytes = (((size_t)(L.block + 2 * L.range) * plan.pitch_dw + 3) & ~(size_t)3) * 4 + (size_t)L.block * L.block;
+            // only the speculative launch adds a floor, and it is the one-wave k_search_fast (launch_search_fast); the others stay
+            // at fast_lds_bytes (< 26 KB)
+            if (int rc = raise_lds_limit(device, search_fast_kernel(L.block), std::max(L.fast_lds_bytes, spec_floor)))
+                return cleanup_fail(rc);
             // the device copy of a plan's round codes carries, for strip rounds, where the round's rank entries start in
             // lane_ranks (<< 16, in rows of T entries); lane_ranks itself: per strip round and lane the S entries of 4 ranks
             auto upload_plan = [&](const SearchPlan &p, int T, uint32_t **d_tasks, uint32_t **d_rounds, uint2 **d_ranks) -> int {
@@ -786,7 +815,7 @@ int bbme_create_batch(const bbme_params *params, int width, int height, int devi
                 return cleanup_fail(bbme::fail(BBME_ERR_HIP, "allocating search plan of level %d: %s", l, hipGetErrorString(err)));
             if (int rc = upload_plan(plan, 64, &L.tasks, &L.rounds, &L.lane_ranks)) return cleanup_fail(rc);
             // shorter strips, so that the 128 lanes of two waves have a full round of them
-            SearchPlan plan2 = plan_search(L.range, L.block, 8, 128);
+            SearchPlan plan2 = plan_search(L.range, L.block, 8, 128, c->loose_plan);
             L.nrounds2 = (int)plan2.rounds.size();
             // a round of strips of S rows walks S + B - 1 window rows: the split only pays where it shortens a wave's walk
             // (+-32 at B <= 16: 0.6x; +-16: the square is too small to fill 128 lanes with tall strips, 0.94-1.0x -- measured slower)
@@ -799,6 +828,8 @@ int bbme_create_batch(const bbme_params *params, int width, int height, int devi
             if (plan2.pitch_dw != plan.pitch_dw) return cleanup_fail(bbme::fail(BBME_ERR_STATE, "search plans disagree on the window pitch"));
             if (int rc = upload_plan(plan2, 128, &L.tasks2, &L.rounds2, &L.lane_ranks2)) return cleanup_fail(rc);
         }
+        // k_search_generic serves the levels above, and every level in raster mode or under BBME_GENERIC_SEARCH
+        if (int rc = raise_lds_limit(device, search_generic_kernel(L.block), std::max(L.lds_bytes, spec_floor))) return cleanup_fail(rc);
     }
     // pitch = 33 (mod 64) words: consecutive blocks land 132 bytes (mod 256) apart
     c->own_pitch = (uint32_t)(((max_blocks + 31) / 32 + 63) / 64 * 64 + 33);
@@ -1233,6 +1264,7 @@ int bbme_stage_search(bbme_ctx *c, int level)
     if (int rc = check_level(c, level)) return rc;
     if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "no frames set");
     HIP_TRY(hipSetDevice(c->device));
+    c->memo_block = 0;             // a stage sequence at a level starts here: the planes may have been refilled in place since
     return launch_search(c, level);
 }
 
@@ -1284,6 +1316,7 @@ int bbme_stage_set_mvs(bbme_ctx *c, int level, int block, const int16_t *mvs)
     for (size_t i = 0; i < n; ++i) host[i] = ((uint32_t)(uint16_t)mvs[2 * i]) | ((uint32_t)(uint16_t)mvs[2 * i + 1] << 16);
     L.cur_grid = block == L.block ? L.small[0] : L.big[0];
     L.cur_block = block;
+    c->memo_block = 0;             // as bbme_stage_search: the planes may have been refilled in place since
     HIP_TRY(hipMemcpyAsync(L.cur_grid, host.data(), n * sizeof(mv_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BBME_OK;

@@ -232,7 +232,7 @@ SpiralTable build_spiral(int search_size, int block_size)
 // full: take the tallest strip height that still has 64 strips available; what is left (< 64
 // single rows) goes into one last round of height 1.
 // ---------------------------------------------------------------------------------------
-SearchPlan plan_search(int range, int block_size, int max_strip, int lanes)
+SearchPlan plan_search(int range, int block_size, int max_strip, int lanes, bool loose)
 {
     SearchPlan p;
     const int n = 2 * range + 1;
@@ -244,7 +244,6 @@ SearchPlan plan_search(int range, int block_size, int max_strip, int lanes)
     // search_aligned_column): kind 1, candidate row n - 1 of the G' full groups, four lanes per (group, row), a quarter of
     // the block's rows each; kind 2, candidate column n - 1 (dx = +R, dword aligned in the staged window: R is even),
     // one candidate per lane, v_sad_u8.  rounds[] = S | kind << 8.
-    static const bool loose = getenv("BBME_LOOSE_PLAN") != nullptr;   // read once: every context of a process plans alike
     const bool tight = n % 4 == 1 && n >= 9 && block_size <= 16 && !loose;
     const int groups_main = tight ? p.groups - 1 : p.groups, rows_main = tight ? n - 1 : n;
     std::vector<int> next(groups_main, 0);                   // first uncovered candidate row per column group
@@ -571,7 +570,8 @@ int bbme_search_plan_host_waves(int range, int block_size, int waves, uint32_t *
     if (!nrounds || range < 0 || range > 63 || (block_size != 8 && block_size != 16 && block_size != 32) || waves < 1 || waves > 2)
         return bbme::fail(BBME_ERR_INVALID, "bbme_search_plan_host: bad arguments");
     const int lanes = 64 * waves;
-    const bbme::SearchPlan p = bbme::plan_search(range, block_size, waves == 2 || block_size == 32 ? 8 : 16, lanes);
+    const bbme::SearchPlan p = bbme::plan_search(range, block_size, waves == 2 || block_size == 32 ? 8 : 16, lanes,
+                                                 getenv("BBME_LOOSE_PLAN") != nullptr);
     *nrounds = (int)p.rounds.size();
     if (groups) *groups = p.groups;
     if (pitch_dw) *pitch_dw = p.pitch_dw;

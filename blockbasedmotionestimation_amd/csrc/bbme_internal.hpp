@@ -44,7 +44,8 @@ struct SearchPlan {
     int pitch_dw = 0;                      // LDS window pitch in dwords (odd, >= groups + B/4)
 };
 // lanes = 64 x the waves that share one macroblock: a round is `lanes` tasks, wave w takes tasks [64 w, 64 w + 64)
-SearchPlan plan_search(int range, int block_size, int max_strip, int lanes = 64);
+// loose: the round-2 plan without rim rounds (BBME_LOOSE_PLAN, read by the caller: per context, or per call of the host entry)
+SearchPlan plan_search(int range, int block_size, int max_strip, int lanes = 64, bool loose = false);
 
 // ---- Flow (rw_flow.cpp) ---------------------------------------------------------------
 int flo_read(const char *filename, int *width, int *height, float **data);

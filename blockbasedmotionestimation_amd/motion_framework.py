@@ -133,6 +133,14 @@ class MF:
         assert image1.shape == (h, w) and image2.shape == (h, w)
         _capi.check(self._lib.bbme_set_level_planes_host(self._ctx, level, image1.ctypes.data, image2.ctypes.data))
 
+    def level_planes_device(self, level):
+        """Device pointers of the level's two padded planes (pitch = level width) for filling or inspecting them in place
+        (bbme_level_planes_device).  After an in-place refill the next stage call at the level must be stage_search or
+        stage_set_mvs; estimate() needs nothing."""
+        d1, d2 = C.c_void_p(), C.c_void_p()
+        _capi.check(self._lib.bbme_level_planes_device(self._ctx, level, C.byref(d1), C.byref(d2)))
+        return d1.value, d2.value
+
     def get_level_planes(self, level):
         w, h, _, _ = self.level_geometry(level)
         a = np.empty((h, w), np.uint8)
@@ -247,7 +255,9 @@ class MFBatch(MF):
     """Several independent frame pairs of one size behind ONE launch sequence (bbme_create_batch): the pairs of a sequence
     that share a GPU.  Every kernel of the estimate works on all pairs at once; each pair's field is bit for bit what an MF
     of its own returns.  `pairs` = [(image1, image2), ...] host arrays, or torch uint8 CUDA tensors with
-    frames_on_device=True.  Methods inherited from MF without a pair index address pair 0."""
+    frames_on_device=True.  Of the methods inherited from MF, set_frames, set_frames_device, get_flow, get_cells and the
+    device-pointer getters address pair 0; the single-pair calls (stage_*, the level planes, last_sweep_passes, sweep_stats,
+    calculate_mse_device) raise BbmeError (ERR_UNSUPPORTED) on a batch of more than one pair."""
 
     def __init__(self, pairs, search_size, block_size, num_levels=None, device=0, frames_on_device=False):
         if num_levels is None:

@@ -7,6 +7,7 @@ Errors the reference reports with a message and exit(1) raise BbmeError instead.
 """
 import ctypes as C
 import os
+import threading
 
 import numpy as np
 
@@ -80,16 +81,22 @@ class FlowWriter:
     """Flow::WriteFlowFile on a worker thread (bbme_flo_writer_*): submit() returns at once, the file is written while
     the next pair is being estimated.  The array handed to submit() must stay alive and untouched until a wait covers it.
     workers > 1: a pool, one file per worker at a time (files then finish in any order); submit*() return the job's ticket
-    and wait(ticket) returns once every job up to it is on disk."""
+    and wait(ticket) returns once every job up to it is on disk.  A writer may be shared by Python threads: each submit gets
+    its own job's ticket."""
 
     def __init__(self, workers=1):
         self._w = C.c_void_p()
         _capi.check(_capi.lib().bbme_flo_writer_create_pool(int(workers), C.byref(self._w)))
-        self._keep = []
+        self._keep = []                 # (ticket, array) of every job no wait has covered yet, in ticket order
+        self._lock = threading.Lock()   # a job's submit and the read of its ticket are one step for Python threads
 
-    def _ticket(self):
+    def _submit(self, array, submit):
+        """submit() queues the job; its ticket is the last one handed out, read before another thread can submit."""
         t = C.c_ulonglong()
-        _capi.check(_capi.lib().bbme_flo_writer_ticket(self._w, C.byref(t)))
+        with self._lock:
+            _capi.check(submit())
+            _capi.check(_capi.lib().bbme_flo_writer_ticket(self._w, C.byref(t)))
+            self._keep.append((t.value, array))
         return t.value
 
     def submit(self, flow_padded, filename, pad_x=0, pad_y=0, width=None, height=None):
@@ -101,10 +108,9 @@ class FlowWriter:
         height = f.shape[0] - pad_y if height is None else height
         if pad_x < 0 or pad_y < 0 or pad_x + width > f.shape[1] or pad_y + height > f.shape[0]:
             raise _capi.BbmeError(_capi.ERR_INVALID, "FlowWriter.submit: window outside the field")
-        self._keep.append(f)
         ptr = f.ctypes.data + 8 * (pad_y * f.shape[1] + pad_x)
-        _capi.check(_capi.lib().bbme_flo_writer_submit(self._w, os.fsencode(filename), width, height, C.c_void_p(ptr), f.shape[1]))
-        return self._ticket()
+        return self._submit(f, lambda: _capi.lib().bbme_flo_writer_submit(self._w, os.fsencode(filename), width, height,
+                                                                           C.c_void_p(ptr), f.shape[1]))
 
     def submit_cells(self, cells, filename, pad_x=0, pad_y=0, width=None, height=None):
         """The same file from the compact result of MF.get_cells (int16 (rows, cols, 2), one (dx, dy) per 2x2 pixels of the
@@ -114,20 +120,23 @@ class FlowWriter:
             raise _capi.BbmeError(_capi.ERR_INVALID, "FlowWriter.submit_cells: C-contiguous int16 (rows, cols, 2) grid expected")
         width = 2 * c.shape[1] - pad_x if width is None else width
         height = 2 * c.shape[0] - pad_y if height is None else height
-        self._keep.append(c)
-        _capi.check(_capi.lib().bbme_flo_writer_submit_cells(self._w, os.fsencode(filename), width, height,
-                                                             C.c_void_p(c.ctypes.data), c.shape[0], c.shape[1], pad_x, pad_y))
-        return self._ticket()
+        return self._submit(c, lambda: _capi.lib().bbme_flo_writer_submit_cells(self._w, os.fsencode(filename), width, height,
+                                                                                 C.c_void_p(c.ctypes.data), c.shape[0], c.shape[1],
+                                                                                 pad_x, pad_y))
 
     def wait(self, ticket=None):
-        """Every job submitted so far, or (ticket) every job up to that one; the arrays of later jobs stay referenced."""
+        """Every job submitted so far, or (ticket) every job up to that one.  The arrays of the jobs a successful wait covers
+        are released; those of later jobs stay referenced."""
         if ticket is not None:
             _capi.check(_capi.lib().bbme_flo_writer_wait_ticket(self._w, int(ticket)))
+            with self._lock:
+                self._keep = [(t, a) for t, a in self._keep if t > ticket]
             return
         try:
             _capi.check(_capi.lib().bbme_flo_writer_wait(self._w))
         finally:
-            self._keep.clear()
+            with self._lock:
+                self._keep.clear()
 
     def close(self):
         if self._w:

@@ -206,6 +206,10 @@ int bbme_set_relaxation(bbme_ctx *ctx, int enabled);
 int bbme_wait_for_stream(bbme_ctx *ctx, void *producer_stream);
 /* Direct access to the ctx-owned padded planes of a level (device pointers, pitch ==
  * level width) so a caller can fill or inspect them in place.
+ * IN-PLACE REFILL RULE.  The library is not told when planes change behind these pointers, and the regulariser's SAD memo
+ * holds sums taken from the planes it last saw.  After a refill, the next stage call at the level must be bbme_stage_search
+ * or bbme_stage_set_mvs (both start the memo afresh); bbme_estimate always does.  Running bbme_stage_regularize straight
+ * after a refill is not supported.
  * SINGLE-PAIR ENTRY POINTS.  The three plane calls below, bbme_calculate_mse_device, every bbme_stage_* call,
  * bbme_sweep_stats, bbme_last_sweep_passes and bbme_gather_cells (bbme_rccl.h) address one pair: on a batched context
  * (bbme_create_batch with pairs > 1) they return BBME_ERR_UNSUPPORTED instead of quietly working on pair 0.  A batch

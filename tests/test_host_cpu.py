@@ -225,6 +225,56 @@ def test_flow_writer_pool_and_tickets(bbme, tmp_path):
         bbme.FlowWriter(workers=0)
 
 
+def test_flow_writer_ticket_waits_release_arrays_and_threads_get_their_own_tickets(bbme, oracle, tmp_path):
+    """FlowWriter keeps every submitted array alive until a wait covers its job.  wait(ticket) must then let go of the arrays of
+    the jobs up to that ticket -- a round pipeline that only waits on tickets would otherwise hold every 66 MB 4K field until
+    close() -- and keep the later ones.  Two Python threads submitting at once must each get their own job's ticket, and
+    wait(ticket) must find that job's file complete: byte for byte the oracle's Flow::WriteFlowFile of the same field."""
+    import gc
+    import threading
+    import weakref
+    rng = np.random.default_rng(11)
+    w = bbme.FlowWriter(workers=2)
+    fields = [rng.standard_normal((48, 64, 2)).astype(np.float32) for _ in range(6)]
+    refs = [weakref.ref(f) for f in fields]
+    tickets = [w.submit(f, str(tmp_path / ("k%d.flo" % i))) for i, f in enumerate(fields)]
+    del fields
+    gc.collect()
+    assert all(r() is not None for r in refs), "submitted arrays must stay referenced until a wait covers them"
+    w.wait(tickets[2])
+    gc.collect()
+    assert [r() is None for r in refs] == [True] * 3 + [False] * 3, "wait(ticket) must release exactly the jobs up to it"
+    w.wait()
+    gc.collect()
+    assert all(r() is None for r in refs)
+
+    n = 40
+    per_thread = {k: [rng.standard_normal((24 + 8 * k, 40, 2)).astype(np.float32) for _ in range(n)] for k in range(2)}
+    got = {0: [], 1: []}
+    start = threading.Barrier(2)
+
+    def producer(k):
+        start.wait()
+        for i, f in enumerate(per_thread[k]):
+            got[k].append(w.submit(f, str(tmp_path / ("t%d_%02d.flo" % (k, i)))))
+
+    threads = [threading.Thread(target=producer, args=(k,)) for k in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    all_tickets = got[0] + got[1]
+    assert len(set(all_tickets)) == 2 * n, "two threads received the same ticket"
+    assert sorted(all_tickets) == list(range(tickets[-1] + 1, tickets[-1] + 1 + 2 * n))
+    for k in range(2):
+        assert got[k] == sorted(got[k])
+        for i in (0, n // 2, n - 1):
+            w.wait(got[k][i])
+            oracle.flo_write(str(tmp_path / "expect.flo"), per_thread[k][i])
+            assert (tmp_path / ("t%d_%02d.flo" % (k, i))).read_bytes() == (tmp_path / "expect.flo").read_bytes(), (k, i)
+    w.close()
+
+
 @pytest.mark.parametrize("pads", [(0, 0), (4, 6), (3, 5), (1, 0)])
 @pytest.mark.parametrize("threads", ["1", "3"])
 def test_async_flow_writer_from_cells(bbme, tmp_path, monkeypatch, pads, threads):
@@ -392,3 +442,23 @@ def test_search_plan_covers_every_candidate_once(bbme, rng, block, waves):
     assert cost <= -(-n * groups.value // lanes) + 2
     if n % 4 == 1 and n >= 9 and block <= 16:
         assert cost <= n * n / 4.0 / lanes + 1.6
+
+
+def test_loose_plan_knob_is_read_per_call(bbme, monkeypatch):
+    """BBME_LOOSE_PLAN is read when a plan is made (per context; per call of bbme_search_plan_host), not once per process: in one
+    process the tight plan of an even range at B <= 16 (rim rounds, kinds 1 and 2) and the loose plan (strips only) alternate
+    with the variable, and the tight plan comes back once it is gone."""
+    from blockbasedmotionestimation_amd import _capi
+    cap = 256
+
+    def kinds():
+        rounds, tasks, nr = np.zeros(cap, np.uint32), np.zeros((cap, 64), np.uint32), C.c_int()
+        _capi.check(_capi.lib().bbme_search_plan_host(32, 16, rounds.ctypes.data, cap, C.byref(nr), tasks.ctypes.data, None, None))
+        return sorted({int(r) >> 8 for r in rounds[:nr.value]})
+
+    monkeypatch.delenv("BBME_LOOSE_PLAN", raising=False)
+    assert kinds() == [0, 1, 2]
+    monkeypatch.setenv("BBME_LOOSE_PLAN", "1")
+    assert kinds() == [0]
+    monkeypatch.delenv("BBME_LOOSE_PLAN")
+    assert kinds() == [0, 1, 2]
