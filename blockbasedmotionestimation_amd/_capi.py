@@ -83,6 +83,11 @@ SIGNATURES = {
     "bbme_set_frames_host_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "bbme_set_frames_host_async": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "bbme_set_frames_device_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bbme_set_frames_host_x4": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bbme_set_frames_host_x4_async": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bbme_set_frames_device_x4": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bbme_subsampled_flow_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_get_subsampled_flow_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
     "bbme_flow_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),
     "bbme_get_flow_host_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p]),
     "bbme_cells_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),

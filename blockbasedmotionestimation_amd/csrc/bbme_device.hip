@@ -135,6 +135,9 @@ struct bbme_ctx {
     bool profiling = false;
     float t_total = 0, t_search = 0, t_reg = 0, t_expand = 0, t_search0 = 0;
     uint8_t *raw[2] = {nullptr, nullptr};         // bbme_set_frames_host: the unpadded frames in HBM (allocated on first use)
+    float *sub = nullptr;                         // bbme_get_subsampled_flow_host: the packed field before its download
+    size_t sub_bytes = 0;                         // (allocated on first use, grown to the largest asked for)
+    hipEvent_t ev_sub = nullptr;                  // bbme_subsampled_flow_device: orders the caller's stream behind the ctx stream
 };
 
 namespace {
@@ -881,6 +884,8 @@ int bbme_destroy(bbme_ctx *c)
     (void)hipFree(c->flow);
     (void)hipFree(c->epe_scratch);
     (void)hipFree(c->raw[0]); (void)hipFree(c->raw[1]);
+    (void)hipFree(c->sub);
+    if (c->ev_sub) (void)hipEventDestroy(c->ev_sub);
     (void)hipFree(c->list[0]); (void)hipFree(c->list[1]);
     (void)hipFree(c->own);
     (void)hipFree(c->flags[0]); (void)hipFree(c->flags[1]);
@@ -1012,6 +1017,21 @@ int bbme_set_frames_host_pair(bbme_ctx *c, int pair, const uint8_t *image1, cons
     return BBME_OK;
 }
 
+// Enqueues the upload of a pair's two (width x height, rows `pitch` bytes apart) host frames into raw[], packed (pitch = width).
+// raw[] has room for the context's frame size; the x4 setters upload frames of a sixteenth of that.
+static int upload_raw(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int width, int height, int pitch)
+{
+    const Geometry &g = c->geom;
+    const size_t bytes = (size_t)g.width * g.height;
+    c->raw_stride = (bytes + 64 + 255) / 256 * 256;
+    const uint8_t *src[2] = {image1, image2};
+    for (int i = 0; i < 2; ++i) {
+        if (!c->raw[i]) HIP_TRY(hipMalloc(&c->raw[i], c->raw_stride * c->batch));
+        HIP_TRY(hipMemcpy2DAsync(c->raw[i] + pair * c->raw_stride, width, src[i], pitch, width, height, hipMemcpyHostToDevice, c->stream));
+    }
+    return BBME_OK;
+}
+
 int bbme_set_frames_host_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
 {
     if (int rc = check_ctx(c)) return rc;
@@ -1021,13 +1041,7 @@ int bbme_set_frames_host_async(bbme_ctx *c, int pair, const uint8_t *image1, con
     // the frames as they are go to HBM; zero border and pyrDown cascade run there (bbme_set_frames_device) -- the same
     // integers as bbme_pad_zero_host / bbme_pyr_down_host produce, without 18 ms of single-threaded host filtering at 4K
     const Geometry &g = c->geom;
-    const size_t bytes = (size_t)g.width * g.height;
-    c->raw_stride = (bytes + 64 + 255) / 256 * 256;
-    const uint8_t *src[2] = {image1, image2};
-    for (int i = 0; i < 2; ++i) {
-        if (!c->raw[i]) HIP_TRY(hipMalloc(&c->raw[i], c->raw_stride * c->batch));
-        HIP_TRY(hipMemcpy2DAsync(c->raw[i] + pair * c->raw_stride, g.width, src[i], pitch, g.width, g.height, hipMemcpyHostToDevice, c->stream));
-    }
+    if (int rc = upload_raw(c, pair, image1, image2, g.width, g.height, pitch)) return rc;
     // no host wait: with pinned source buffers the upload, the border, the pyramid and an estimate behind them overlap whatever
     // the host does next; the buffers must stay untouched until the context's stream has passed this point
     return bbme_set_frames_device_pair(c, pair, c->raw[0] + pair * c->raw_stride, c->raw[1] + pair * c->raw_stride, g.width);
@@ -1037,6 +1051,8 @@ int bbme_set_frames_device(bbme_ctx *c, const uint8_t *d_image1, const uint8_t *
 {
     return bbme_set_frames_device_pair(c, 0, d_image1, d_image2, pitch);
 }
+
+static int enqueue_cascade(bbme_ctx *c, int pair);
 
 int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
 {
@@ -1052,6 +1068,14 @@ int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, 
     const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
     hipLaunchKernelGGL(k_pad_zero, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
                        pp, g.width, g.height, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    return enqueue_cascade(c, pair);
+}
+
+// MF::MF's pyrDown cascade (motion_framework.cpp:86-106) of one pair from its level-0 planes, and the bookkeeping every frame
+// setter shares: the pair has frames, and what the SAD memo holds is no longer true
+static int enqueue_cascade(bbme_ctx *c, int pair)
+{
+    const size_t pp_ = (size_t)pair;
     for (size_t l = 1; l < c->lv.size(); ++l) {
         Level &P = c->lv[l - 1], &L = c->lv[l];
         PlanePair q{{P.img1 + pp_ * P.plane_stride, P.img2 + pp_ * P.plane_stride}, {L.img1 + pp_ * L.plane_stride, L.img2 + pp_ * L.plane_stride}};
@@ -1066,6 +1090,52 @@ int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, 
     HIP_TRY(hipGetLastError());
     c->frames_mask |= 1ull << pair;
     c->memo_block = 0;                                  // new planes: what the SAD memo holds is no longer true
+    return BBME_OK;
+}
+
+// ---- x4 up-sampling on the device (main_class.cpp:32-33): frames of (width / 4) x (height / 4) ------------------------
+
+static int check_x4(const bbme_ctx *c, int pair, const void *image1, const void *image2, int pitch, const char *what)
+{
+    if (int rc = check_ctx(c)) return rc;
+    const Geometry &g = c->geom;
+    if (g.width % 4 || g.height % 4)
+        return bbme::fail(BBME_ERR_INVALID, "%s: the context's frame (%dx%d) is not a multiple of 4 in both dimensions", what,
+                          g.width, g.height);
+    if (!image1 || !image2 || pitch < g.width / 4 || pair < 0 || pair >= c->batch)
+        return bbme::fail(BBME_ERR_INVALID, "%s: bad arguments (pitch %d, source width %d, pair %d of %d)", what, pitch,
+                          g.width / 4, pair, c->batch);
+    return BBME_OK;
+}
+
+int bbme_set_frames_device_x4(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
+{
+    if (int rc = check_x4(c, pair, d_image1, d_image2, pitch, "bbme_set_frames_device_x4")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const Geometry &g = c->geom;
+    const size_t pp_ = (size_t)pair;
+    // both frames per launch: up-sampling and zero border into the level-0 planes (every byte), then the pyrDown cascade
+    Level &L0 = c->lv[0];
+    PlanePair pp{{d_image1, d_image2}, {L0.img1 + pp_ * L0.plane_stride, L0.img2 + pp_ * L0.plane_stride}};
+    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
+    hipLaunchKernelGGL(k_resize_x4_pad, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
+                       pp, g.width / 4, g.height / 4, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    return enqueue_cascade(c, pair);
+}
+
+int bbme_set_frames_host_x4_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    if (int rc = check_x4(c, pair, image1, image2, pitch, "bbme_set_frames_host_x4")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int sw = c->geom.width / 4, sh = c->geom.height / 4;
+    if (int rc = upload_raw(c, pair, image1, image2, sw, sh, pitch)) return rc;
+    return bbme_set_frames_device_x4(c, pair, c->raw[0] + pair * c->raw_stride, c->raw[1] + pair * c->raw_stride, sw);
+}
+
+int bbme_set_frames_host_x4(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    if (int rc = bbme_set_frames_host_x4_async(c, pair, image1, image2, pitch)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
     return BBME_OK;
 }
 
@@ -1256,6 +1326,58 @@ int bbme_calculate_mse_device(bbme_ctx *c, const float *d_gtruth, int gt_width, 
     for (int i = 0; i < groups; ++i) { error += h_sum[i]; count += h_cnt[i]; }
     *out = error / (double)count;                     // 0/0 = NaN when no pixel is known, as in the reference (:330)
     return BBME_OK;
+}
+
+// main_class.cpp:58-70 from the cell grid: the ceil(W/s) x ceil(H/s) field at every s-th pixel of the unpadded frame, / s
+static int enqueue_subsample(bbme_ctx *c, int pair, int scale, float *d_out, int out_pitch, hipStream_t stream, const char *what)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!d_out || scale < 1) return bbme::fail(BBME_ERR_INVALID, "%s: null output or scale %d < 1", what, scale);
+    const int ow = (c->geom.width + scale - 1) / scale, oh = (c->geom.height + scale - 1) / scale;
+    if (out_pitch < ow) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < width %d", what, out_pitch, ow);
+    const Level &L = c->lv[0];
+    if (L.cur_block != 2) return bbme::fail(BBME_ERR_STATE, "%s: level 0 has not been regularised down to 2x2 blocks", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (stream != c->stream) {
+        if (!c->ev_sub) HIP_TRY(hipEventCreateWithFlags(&c->ev_sub, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->ev_sub, c->stream));
+        HIP_TRY(hipStreamWaitEvent(stream, c->ev_sub, 0));
+    }
+    const long long n = (long long)ow * oh;
+    hipLaunchKernelGGL(k_subsample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                       L.cur_grid + (size_t)pair * L.grid_stride(L.cur_grid), L.width / 2, c->geom.pad_x, c->geom.pad_y, scale,
+                       d_out, ow, oh, out_pitch, 0u, (size_t)0);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+int bbme_subsampled_flow_device(bbme_ctx *c, int pair, int scale, float *d_out, int out_pitch_pixels, void *hip_stream)
+{
+    if (int rc = check_ctx(c)) return rc;
+    return enqueue_subsample(c, pair, scale, d_out, out_pitch_pixels,
+                             hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream, "bbme_subsampled_flow_device");
+}
+
+int bbme_get_subsampled_flow_host(bbme_ctx *c, int pair, int scale, float *out)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!out || scale < 1) return bbme::fail(BBME_ERR_INVALID, "bbme_get_subsampled_flow_host: null output or scale %d < 1", scale);
+    if (c->lv[0].cur_block != 2)
+        return bbme::fail(BBME_ERR_STATE, "bbme_get_subsampled_flow_host: level 0 has not been regularised down to 2x2 blocks");
+    const int ow = (c->geom.width + scale - 1) / scale, oh = (c->geom.height + scale - 1) / scale;
+    const size_t bytes = (size_t)ow * oh * 2 * sizeof(float);
+    if (bytes > c->sub_bytes) {
+        HIP_TRY(hipSetDevice(c->device));
+        HIP_TRY(hipStreamSynchronize(c->stream));     // the old buffer may still be being read
+        (void)hipFree(c->sub);
+        c->sub = nullptr;
+        c->sub_bytes = 0;
+        HIP_TRY(hipMalloc(&c->sub, bytes));
+        c->sub_bytes = bytes;
+    }
+    if (int rc = enqueue_subsample(c, pair, scale, c->sub, ow, c->stream, "bbme_get_subsampled_flow_host")) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->sub, bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
 }
 
 int bbme_stage_search(bbme_ctx *c, int level)

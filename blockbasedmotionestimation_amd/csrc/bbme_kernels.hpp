@@ -2140,6 +2140,26 @@ __global__ __launch_bounds__(256) void k_epe(const mv_t *cells, int cell_cols, i
 }
 
 // =======================================================================================
+// The driver's subsampling (main_class.cpp:58-70) straight from the 2x2-cell grid, with k_epe's indexing:
+// out(y, x) = cell((pad_y + s y) >> 1, (pad_x + s x) >> 1) / s for the ceil(W/s) x ceil(H/s) field of the unpadded
+// W x H frame; rows out_pitch float2 apart.  s = 4: what bbme_subsample_div4 makes of the dense field; s = 1: the
+// unpadded window.  One output pixel per thread; batch as k_expand (blockIdx.y = pair).
+// =======================================================================================
+__global__ __launch_bounds__(256) void k_subsample(const mv_t *cells, int cell_cols, int pad_x, int pad_y, int scale,
+                                                   float *out, int out_width, int out_height, int out_pitch,
+                                                   uint32_t s_cells, size_t s_out)
+{
+    cells += (size_t)blockIdx.y * s_cells;
+    out += (size_t)blockIdx.y * s_out;
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)out_width * out_height) return;
+    const int x = (int)(t % out_width), y = (int)(t / out_width);
+    const mv_t m = cells[(size_t)((pad_y + scale * y) >> 1) * cell_cols + ((pad_x + scale * x) >> 1)];
+    const float s = (float)scale;
+    *reinterpret_cast<float2 *>(out + 2 * ((size_t)y * out_pitch + x)) = make_float2((float)mv_x(m) / s, (float)mv_y(m) / s);
+}
+
+// =======================================================================================
 // MF::MF on the GPU (motion_framework.cpp:57-61, 86-106): zero border and pyrDown cascade.  Both frames of the pair
 // in one launch (blockIdx.y).  Bandwidth-bound byte work: 16 bytes per thread for the border copy, four output pixels
 // per thread for pyrDown (dword loads, the 5-tap rows as v_dot4_u32_u8 on re-aligned dwords).
@@ -2178,6 +2198,73 @@ __global__ __launch_bounds__(256) void k_pad_zero(PlanePair p, int width, int he
 #pragma unroll
         for (int q = 0; q < 4; ++q)
             if (x0 + 4 * q < pw) out[q] = w[q];
+    }
+}
+
+// =======================================================================================
+// cv::resize(..., 4, 4, INTER_LINEAR) of main_class.cpp:32-33 fused with the zero border (motion_framework.cpp:57-61):
+// pixel (X, Y) of the padded plane is resize_x4(src)(X - pad_x, Y - pad_y) inside the frame, 0 outside.  Bit for bit
+// bbme::resize_x4 (bbme_host.cpp), whose coefficients repeat with period 4: phase p of an output coordinate d = 4k + p
+// samples source k - 1 (p = 0, 1) or k (p = 2, 3) with weights (768, 1280), (256, 1792), (1792, 256), (1280, 768).
+// Horizontally a first column outside the source resets them to (2048, 0) (output columns 0, 1, 4W-2, 4W-1);
+// vertically only the row index is clamped.  Both frames per launch (blockIdx.y), 16 output bytes per thread, the
+// source bytes a thread needs (at most 7 per row) held in one 64-bit word per row.  sw, sh: source size; pw, ph: plane.
+// =======================================================================================
+__device__ __forceinline__ int resize_x4_w0(int phase)      // weight of the first tap; the second is 2048 minus it
+{
+    return phase == 0 ? 768 : phase == 1 ? 256 : phase == 2 ? 1792 : 1280;
+}
+
+__global__ __launch_bounds__(256) void k_resize_x4_pad(PlanePair p, int sw, int sh, int pitch,
+                                                       int pad_x, int pad_y, int pw, int ph)
+{
+    const uint8_t *src = p.src[blockIdx.y];
+    uint8_t *dst = p.dst[blockIdx.y];
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int per_row = (pw + 15) / 16;
+    if (t >= (long long)per_row * ph) return;
+    const int y = (int)(t / per_row), x0 = (int)(t % per_row) * 16;
+    const int dw = 4 * sw, dy = y - pad_y, dx0 = x0 - pad_x;
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (dy >= 0 && dy < 4 * sh) {
+        const int py = dy & 3, sy = (dy >> 2) - (py < 2 ? 1 : 0);
+        const int y0 = min(max(sy, 0), sh - 1), y1 = min(max(sy + 1, 0), sh - 1);
+        const int b0 = resize_x4_w0(py), b1 = 2048 - b0;
+        const int kbase = (dx0 >> 2) - 1;                             // first source column any of the 16 bytes reads
+        uint64_t r0 = 0, r1 = 0;
+        const uint8_t *s0 = src + (size_t)y0 * pitch, *s1 = src + (size_t)y1 * pitch;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int sx = kbase + j;
+            if (sx >= 0 && sx < sw) { r0 |= (uint64_t)s0[sx] << (8 * j); r1 |= (uint64_t)s1[sx] << (8 * j); }
+        }
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            const int dx = dx0 + b;
+            if (dx < 0 || dx >= dw) continue;
+            const int px = dx & 3;
+            int sx = (dx >> 2) - (px < 2 ? 1 : 0), a0 = resize_x4_w0(px);
+            if (sx < 0 || sx >= sw - 1) { sx = min(max(sx, 0), sw - 1); a0 = 2048; }
+            const int a1 = 2048 - a0;
+            const int i = 8 * (sx - kbase);                           // sx + 1 - kbase <= 7: inside the word
+            const int h0 = (int)((r0 >> i) & 0xffu) * a0 + (int)((r0 >> (i + 8)) & 0xffu) * a1;
+            const int h1 = (int)((r1 >> i) & 0xffu) * a0 + (int)((r1 >> (i + 8)) & 0xffu) * a1;
+            const int v = (((b0 * (h0 >> 4)) >> 16) + ((b1 * (h1 >> 4)) >> 16) + 2) >> 2;
+            w[b >> 2] |= (uint32_t)v << (8 * (b & 3));
+        }
+    }
+    uint8_t *o = dst + (size_t)y * pw + x0;
+    if (x0 + 16 <= pw && (((uintptr_t)o) & 15u) == 0) {
+        *reinterpret_cast<uint4 *>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {                                                          // the row's last chunk, or rows not 16-byte aligned
+        uint32_t *out = reinterpret_cast<uint32_t *>(o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (x0 + 4 * q + 4 <= pw) out[q] = w[q];
+            else
+                for (int b = 4 * q; b < 4 * q + 4; ++b)               // nothing past the row: it is the next row's
+                    if (x0 + b < pw) o[b] = (uint8_t)(w[q] >> (8 * (b & 3)));
+        }
     }
 }
 

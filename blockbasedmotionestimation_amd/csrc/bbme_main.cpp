@@ -4,9 +4,10 @@
 //            [--block B] [--search S] [--no-upsample] [--device D]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
-// libpng), 4x bilinear up-sampling (:32-33), MF::MF (:45), timed calcMotionBlockMatching (:47-55),
-// strip the padding + every 4th pixel / 4 (:58-70), write the field (the reference only ever
-// colour-codes it; here Flow::WriteFlowFile is actually called), EPE against ground truth (:78-82).
+// libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
+// timed calcMotionBlockMatching (:47-55) with the padding strip + every 4th pixel / 4 (:58-70) on
+// the GPU, write the field (the reference only ever colour-codes it; here Flow::WriteFlowFile is
+// actually called), EPE against ground truth (:78-82).
 // Defaults are the reference's literals (:19-21): 4 levels, block 32, search 64.
 #include <chrono>
 #include <cstdio>
@@ -73,29 +74,15 @@ int main(int argc, char **argv)
             fprintf(stderr, "Could not open one of the images\n");                    // main_class.cpp:40
             return 1;
         }
-        const int orig_height = image1.rows, orig_width = image1.cols;
         const int scale = upsample ? 4 : 1;
-        if (upsample) { image1 = bbme::resize_x4(image1); image2 = bbme::resize_x4(image2); }
         std::vector<int> search_size(levels, search), block_size(levels, block);
-        MF motion_pair(image1, image2, search_size.data(), block_size.data(), levels, device);
+        // the x4 up-sampling (:32-33) runs on the GPU from the original frames; the padding strip and the every-4th-pixel / 4
+        // subsampling (:58-70) too, so only the original-sized field comes back
+        MF motion_pair(image1, image2, search_size.data(), block_size.data(), levels, device, scale);
         const auto t1 = std::chrono::steady_clock::now();
-        bbme::ImageFlow flow_res = motion_pair.calcMotionBlockMatching();
+        bbme::ImageFlow subpix = motion_pair.calcMotionBlockMatchingSubsampled(scale);
         const auto t2 = std::chrono::steady_clock::now();
         printf("Seconds: %g\n", std::chrono::duration<double>(t2 - t1).count());
-        bbme::ImageFlow subpix(orig_height, orig_width);
-        if (upsample) {
-            bbme::check(bbme_subsample_div4(flow_res.data.data(), motion_pair.padded_width, motion_pair.padded_height,
-                                            motion_pair.padding_x, motion_pair.padding_y, subpix.data.data(),
-                                            orig_width, orig_height));
-        } else {
-            for (int y = 0; y < orig_height; ++y)
-                for (int x = 0; x < orig_width; ++x) {
-                    const float *s = flow_res.at(y + motion_pair.padding_y, x + motion_pair.padding_x);
-                    subpix.at(y, x)[0] = s[0];
-                    subpix.at(y, x)[1] = s[1];
-                }
-        }
-        (void)scale;
         Flow file;
         if (color) {                                   // main_class.cpp:73-75 (flow.png there)
             bbme::ImageBGR flow_img;

@@ -79,9 +79,14 @@ inline Image8 resize_x4(const Image8 &src)
 
 class MF {
 public:
+    // upsample = 4: image1 / image2 are the ORIGINAL frames of the reference's pipeline; the context is created at their
+    // x4 size (what the reference's MF sees after main_class.cpp:32-33) and the up-sampling runs on the GPU
+    // (bbme_set_frames_host_x4).  padded_* / padding_* then describe the up-sampled frame.
     MF(const bbme::Image8 &image1, const bbme::Image8 &image2, const int search_size[], const int block_size[],
-       const int num_levels, int device = 0)
+       const int num_levels, int device = 0, int upsample = 1)
+        : upsample(upsample)
     {
+        if (upsample != 1 && upsample != 4) throw bbme::Error(BBME_ERR_INVALID, "upsample must be 1 or 4");
         if (num_levels <= 0) throw bbme::Error(BBME_ERR_INVALID, "num_levels must be > 0");                       // assert :7
         if (image1.rows != image2.rows || image1.cols != image2.cols)
             throw bbme::Error(BBME_ERR_INVALID, "image1.size() != image2.size()");                                 // assert :8
@@ -91,9 +96,10 @@ public:
             p.block_size[i] = block_size[i];
             p.search_size[i] = search_size[i];
         }
-        bbme::check(bbme_create(&p, image1.cols, image1.rows, device, &ctx_));
+        bbme::check(bbme_create(&p, image1.cols * upsample, image1.rows * upsample, device, &ctx_));
         bbme::check(bbme_get_geometry(ctx_, &padded_width, &padded_height, &padding_x, &padding_y));
-        int rc = bbme_set_frames_host(ctx_, image1.data.data(), image2.data.data(), image1.cols);
+        int rc = upsample == 4 ? bbme_set_frames_host_x4(ctx_, 0, image1.data.data(), image2.data.data(), image1.cols)
+                               : bbme_set_frames_host(ctx_, image1.data.data(), image2.data.data(), image1.cols);
         if (rc != BBME_OK) { bbme_destroy(ctx_); ctx_ = nullptr; bbme::check(rc); }
     }
 #ifdef BBME_WITH_OPENCV
@@ -122,7 +128,24 @@ public:
         return flow;
     }
 #endif
+    // calcMotionBlockMatching() followed by the driver's subsampling (main_class.cpp:58-70) on the GPU: the
+    // ceil(W / scale) x ceil(H / scale) field of the unpadded frame at every scale-th pixel, divided by scale (scale 0 =
+    // upsample, i.e. the original frame's size for an x4 MF).  Only that field is downloaded.
+    bbme::ImageFlow calcMotionBlockMatchingSubsampled(int scale = 0)
+    {
+        if (scale == 0) scale = upsample;
+        bbme::check(bbme_estimate(ctx_));
+        int w = 0, h = 0;
+        bbme::check(bbme_level_geometry(ctx_, 0, &w, &h, nullptr, nullptr));
+        w -= 2 * padding_x;
+        h -= 2 * padding_y;
+        bbme::ImageFlow flow(scale > 0 ? (h + scale - 1) / scale : 0, scale > 0 ? (w + scale - 1) / scale : 0);
+        bbme::check(bbme_get_subsampled_flow_host(ctx_, 0, scale, flow.data.data()));
+        return flow;
+    }
     bbme_ctx *context() { return ctx_; }
+
+    const int upsample = 1;       // 4: constructed from the original frames of the reference's x4 pipeline
 
     int padded_height = 0;        // motion_framework.h:16-19
     int padded_width = 0;

@@ -4,6 +4,9 @@
     flow = mf.calcMotionBlockMatching()                             # :113-219 -> (H_pad, W_pad, 2) float32
     mf.padded_height, mf.padded_width, mf.padding_x, mf.padding_y   # public fields :16-19
 
+    mf = MF(image1, image2, search_size, block_size, upsample=4)   # the original frames of main_class.cpp:32-33
+    sub = mf.calcMotionBlockMatchingSubsampled()                    # :58-70 on the GPU -> (h, w, 2) float32
+
 Argument meaning and order follow the reference: arrays are indexed [0] = finest level,
 search_size is the window side length.  Errors the reference reports with assert / exit(1)
 raise BbmeError here.  All arithmetic runs in the HIP kernels of libbbme.so.
@@ -15,9 +18,22 @@ import numpy as np
 from . import _capi
 
 
+def _check_upsample(upsample):
+    if upsample not in (1, 4):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "upsample must be 1 or 4, not %r" % (upsample,))
+    return upsample
+
+
 class MF:
+    """upsample=4: image1 / image2 are the original frames of the reference's pipeline, which up-samples them x4 before
+    MF::MF (main_class.cpp:32-33).  The context is created at the up-sampled size (orig_width / orig_height keep meaning
+    "the frame MF sees", source_width / source_height are the frames passed in) and the up-sampling runs on the GPU
+    (bbme_set_frames_host_x4 / bbme_set_frames_device_x4): the planes are byte for byte those of MF(resize_x4(image1),
+    resize_x4(image2), ...).  set_frames / set_frames_device then take frames of the source size too."""
+
     def __init__(self, image1, image2, search_size, block_size, num_levels=None, device=0,
-                 frames_on_device=False):
+                 frames_on_device=False, upsample=1):
+        self.upsample = _check_upsample(upsample)
         if num_levels is None:
             num_levels = len(block_size)
         if num_levels <= 0:
@@ -39,9 +55,10 @@ class MF:
             if image1.ndim != 2 or image1.shape != image2.shape:                        # assert :8
                 raise _capi.BbmeError(_capi.ERR_INVALID, "image1.size() != image2.size()")
             h, w = image1.shape
-        self.orig_height, self.orig_width = h, w
+        self.source_height, self.source_width = h, w
+        self.orig_height, self.orig_width = h * upsample, w * upsample
         self.params = _capi.make_params(search_size, block_size)
-        _capi.check(self._lib.bbme_create(C.byref(self.params), w, h, device, C.byref(self._ctx)))
+        _capi.check(self._lib.bbme_create(C.byref(self.params), self.orig_width, self.orig_height, device, C.byref(self._ctx)))
         pw, ph, px, py = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         _capi.check(self._lib.bbme_get_geometry(self._ctx, C.byref(pw), C.byref(ph), C.byref(px), C.byref(py)))
         self.padded_width, self.padded_height = pw.value, ph.value
@@ -50,7 +67,7 @@ class MF:
         if frames_on_device:
             self.set_frames_device(image1, image2)
         else:
-            _capi.check(self._lib.bbme_set_frames_host(self._ctx, image1.ctypes.data, image2.ctypes.data, w))
+            self.set_frames(image1, image2)
 
     # -- lifetime -------------------------------------------------------------------------
     def close(self):
@@ -71,35 +88,51 @@ class MF:
         self.close()
 
     # -- inputs ---------------------------------------------------------------------------
+    def _host_frames(self, image1, image2):
+        image1 = np.ascontiguousarray(image1, dtype=np.uint8)
+        image2 = np.ascontiguousarray(image2, dtype=np.uint8)
+        if image1.shape != (self.source_height, self.source_width) or image2.shape != image1.shape:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "frames must keep the size the context was created for")
+        return image1, image2
+
+    def _set_host_pair(self, pair, image1, image2):
+        image1, image2 = self._host_frames(image1, image2)
+        if self.upsample == 4:
+            _capi.check(self._lib.bbme_set_frames_host_x4(self._ctx, pair, image1.ctypes.data, image2.ctypes.data,
+                                                          self.source_width))
+        else:
+            _capi.check(self._lib.bbme_set_frames_host_pair(self._ctx, pair, image1.ctypes.data, image2.ctypes.data,
+                                                            self.source_width))
+
+    def _set_device_pair(self, pair, image1, image2):
+        self._check_device_frames(image1, image2)
+        # the tensors may still be being written by work on torch's current stream: order the context's stream behind it
+        import torch
+        _capi.check(self._lib.bbme_wait_for_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(image1.device).cuda_stream)))
+        setter = self._lib.bbme_set_frames_device_x4 if self.upsample == 4 else self._lib.bbme_set_frames_device_pair
+        _capi.check(setter(self._ctx, pair, image1.data_ptr(), image2.data_ptr(), image1.stride(0)))
+
     def set_frames(self, image1, image2):
         """A new pair of the same size into this context (host arrays): what a second MF::MF would do,
         without re-allocating the level state or re-capturing the launch graph."""
-        image1 = np.ascontiguousarray(image1, dtype=np.uint8)
-        image2 = np.ascontiguousarray(image2, dtype=np.uint8)
-        if image1.shape != (self.orig_height, self.orig_width) or image2.shape != image1.shape:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "frames must keep the size the context was created for")
-        _capi.check(self._lib.bbme_set_frames_host(self._ctx, image1.ctypes.data, image2.ctypes.data, self.orig_width))
+        self._set_host_pair(0, image1, image2)
 
     def _check_device_frames(self, image1, image2):
-        """The padding kernel reads orig_height x pitch bytes behind each pointer: a tensor of any other shape must be
+        """The padding kernel reads source_height x pitch bytes behind each pointer: a tensor of any other shape must be
         refused here (the C-ABI sees only a pointer and a pitch)."""
         import torch
         for t in (image1, image2):
-            if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and tuple(t.shape) == (self.orig_height, self.orig_width)):
+            if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and tuple(t.shape) == (self.source_height, self.source_width)):
                 raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must be 2-D uint8 CUDA tensors of %d x %d (the size the "
-                                      "context was created for)" % (self.orig_height, self.orig_width))
+                                      "context was created for)" % (self.source_height, self.source_width))
         if image1.stride(1) != 1 or image2.stride(1) != 1 or image1.stride(0) != image2.stride(0):
             raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must have unit column stride and a common row pitch")
 
     def set_frames_device(self, image1, image2):
-        """Frames already in HBM (torch uint8 CUDA tensors, H x W): padding + pyramid on the GPU."""
-        self._check_device_frames(image1, image2)
+        """Frames already in HBM (torch uint8 CUDA tensors, H x W of the source size): (x4 up-sampling,) padding and
+        pyramid on the GPU."""
+        self._set_device_pair(0, image1, image2)
         self._torch_frames = (image1, image2)
-        # the tensors may still be being written by work on torch's current stream: order the context's stream behind it
-        import torch
-        _capi.check(self._lib.bbme_wait_for_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(image1.device).cuda_stream)))
-        _capi.check(self._lib.bbme_set_frames_device(self._ctx, image1.data_ptr(), image2.data_ptr(),
-                                                     image1.stride(0)))
 
     def set_search_mode(self, raster):
         """False: find_min_block_spiral (the reference's live search); True: the raster find_min_block (:246-294)."""
@@ -166,6 +199,50 @@ class MF:
             raise _capi.BbmeError(_capi.ERR_INVALID, "get_flow: out must be a C-contiguous float32 array of shape %s" % (shape,))
         _capi.check(self._lib.bbme_get_flow_host(self._ctx, out.ctypes.data))
         return out
+
+    def subsampled_shape(self, scale=None):
+        """(rows, cols, 2) of the subsampled field: ceil(orig / scale); scale defaults to upsample."""
+        scale = self.upsample if scale is None else int(scale)
+        if scale < 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "scale must be >= 1")
+        return (-(-self.orig_height // scale), -(-self.orig_width // scale), 2)
+
+    def _get_subsampled(self, pair, scale, out, what):
+        shape = self.subsampled_shape(scale)
+        scale = self.upsample if scale is None else int(scale)
+        if out is None:
+            out = np.empty(shape, np.float32)
+        elif out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous float32 array of shape %s" % (what, shape))
+        _capi.check(self._lib.bbme_get_subsampled_flow_host(self._ctx, pair, scale, out.ctypes.data))
+        return out
+
+    def get_subsampled_flow(self, scale=None, out=None):
+        """The driver's subsampling (main_class.cpp:58-70) on the GPU: the field of the unpadded frame at every `scale`-th
+        pixel, divided by `scale` (default: upsample, i.e. the source frame's size) -> (rows, cols, 2) float32.  scale 4
+        equals subsample_div4(get_flow(), ...), scale 1 the unpadded window of get_flow(); only that field is downloaded."""
+        return self._get_subsampled(0, scale, out, "get_subsampled_flow")
+
+    def subsampled_flow_device(self, out, scale=None, hip_stream_handle=None, pair=0):
+        """The same into a float32 CUDA tensor of shape (rows, >= cols, 2) whose rows may be further apart than cols
+        (a column slice of a wider tensor), on the given HIP stream (default: the context's), ordered behind the
+        context's stream; no host wait."""
+        scale = self.upsample if scale is None else int(scale)
+        rows, cols, _ = self.subsampled_shape(scale)
+        import torch
+        if not (out.is_cuda and out.dtype == torch.float32 and out.dim() == 3 and out.shape[0] == rows and out.shape[1] == cols
+                and out.shape[2] == 2 and out.stride(2) == 1 and out.stride(1) == 2 and out.stride(0) % 2 == 0
+                and out.stride(0) >= 2 * cols):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "subsampled_flow_device: out must be a float32 CUDA tensor of shape "
+                                  "(%d, %d, 2) with unit pixel stride" % (rows, cols))
+        _capi.check(self._lib.bbme_subsampled_flow_device(self._ctx, pair, scale, C.c_void_p(out.data_ptr()),
+                                                          out.stride(0) // 2, C.c_void_p(hip_stream_handle or 0)))
+        return out
+
+    def calcMotionBlockMatchingSubsampled(self, scale=None):
+        """calcMotionBlockMatching followed by get_subsampled_flow: nothing dense crosses PCIe."""
+        self.estimate_async()
+        return self.get_subsampled_flow(scale)
 
     def get_cells(self, out=None):
         shape = (self.padded_height // 2, self.padded_width // 2, 2)
@@ -255,11 +332,13 @@ class MFBatch(MF):
     """Several independent frame pairs of one size behind ONE launch sequence (bbme_create_batch): the pairs of a sequence
     that share a GPU.  Every kernel of the estimate works on all pairs at once; each pair's field is bit for bit what an MF
     of its own returns.  `pairs` = [(image1, image2), ...] host arrays, or torch uint8 CUDA tensors with
-    frames_on_device=True.  Of the methods inherited from MF, set_frames, set_frames_device, get_flow, get_cells and the
-    device-pointer getters address pair 0; the single-pair calls (stage_*, the level planes, last_sweep_passes, sweep_stats,
-    calculate_mse_device) raise BbmeError (ERR_UNSUPPORTED) on a batch of more than one pair."""
+    frames_on_device=True.  Of the methods inherited from MF, set_frames, set_frames_device, get_flow, get_cells,
+    get_subsampled_flow and the device-pointer getters address pair 0; the single-pair calls (stage_*, the level planes,
+    last_sweep_passes, sweep_stats, calculate_mse_device) raise BbmeError (ERR_UNSUPPORTED) on a batch of more than one pair.
+    upsample=4: the pairs are original frames, up-sampled x4 on the GPU, as MF(..., upsample=4)."""
 
-    def __init__(self, pairs, search_size, block_size, num_levels=None, device=0, frames_on_device=False):
+    def __init__(self, pairs, search_size, block_size, num_levels=None, device=0, frames_on_device=False, upsample=1):
+        self.upsample = _check_upsample(upsample)
         if num_levels is None:
             num_levels = len(block_size)
         if num_levels <= 0 or not pairs:
@@ -270,9 +349,11 @@ class MFBatch(MF):
         self.batch = len(pairs)
         self._torch_frames = [None] * self.batch
         h, w = pairs[0][0].shape
-        self.orig_height, self.orig_width = h, w
+        self.source_height, self.source_width = h, w
+        self.orig_height, self.orig_width = h * upsample, w * upsample
         self.params = _capi.make_params(list(search_size)[:num_levels], list(block_size)[:num_levels])
-        _capi.check(self._lib.bbme_create_batch(C.byref(self.params), w, h, device, self.batch, C.byref(self._ctx)))
+        _capi.check(self._lib.bbme_create_batch(C.byref(self.params), self.orig_width, self.orig_height, device, self.batch,
+                                                C.byref(self._ctx)))
         pw, ph, px, py = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         _capi.check(self._lib.bbme_get_geometry(self._ctx, C.byref(pw), C.byref(ph), C.byref(px), C.byref(py)))
         self.padded_width, self.padded_height = pw.value, ph.value
@@ -285,11 +366,7 @@ class MFBatch(MF):
                 self.set_pair(p, image1, image2)
 
     def set_pair(self, pair, image1, image2):
-        image1 = np.ascontiguousarray(image1, dtype=np.uint8)
-        image2 = np.ascontiguousarray(image2, dtype=np.uint8)
-        if image1.shape != (self.orig_height, self.orig_width) or image2.shape != image1.shape:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "frames must keep the size the context was created for")
-        _capi.check(self._lib.bbme_set_frames_host_pair(self._ctx, pair, image1.ctypes.data, image2.ctypes.data, self.orig_width))
+        self._set_host_pair(pair, image1, image2)
 
     def set_frames(self, image1, image2):
         """Pair 0 (the inherited entry point without a pair index)."""
@@ -302,11 +379,8 @@ class MFBatch(MF):
     def set_pair_device(self, pair, image1, image2):
         if not 0 <= pair < self.batch:
             raise _capi.BbmeError(_capi.ERR_INVALID, "pair %d of a batch of %d" % (pair, self.batch))
-        self._check_device_frames(image1, image2)
+        self._set_device_pair(pair, image1, image2)
         self._torch_frames[pair] = (image1, image2)
-        import torch
-        _capi.check(self._lib.bbme_wait_for_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(image1.device).cuda_stream)))
-        _capi.check(self._lib.bbme_set_frames_device_pair(self._ctx, pair, image1.data_ptr(), image2.data_ptr(), image1.stride(0)))
 
     def get_pair_flow(self, pair, out=None):
         shape = (self.padded_height, self.padded_width, 2)
@@ -325,6 +399,10 @@ class MFBatch(MF):
             raise _capi.BbmeError(_capi.ERR_INVALID, "get_pair_cells: out must be a C-contiguous int16 array of shape %s" % (shape,))
         _capi.check(self._lib.bbme_get_cells_host_pair(self._ctx, pair, out.ctypes.data))
         return out
+
+    def get_pair_subsampled_flow(self, pair, scale=None, out=None):
+        """MF.get_subsampled_flow of one pair."""
+        return self._get_subsampled(pair, scale, out, "get_pair_subsampled_flow")
 
     def calcMotionBlockMatching(self):
         """Every pair's dense padded field, in order."""

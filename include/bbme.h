@@ -174,6 +174,17 @@ int bbme_set_frames_host_async(bbme_ctx *ctx, int pair, const uint8_t *image1, c
  * zero padding and the whole pyrDown cascade run as HIP kernels on the ctx stream. */
 int bbme_set_frames_device(bbme_ctx *ctx, const uint8_t *d_image1, const uint8_t *d_image2, int pitch);
 int bbme_set_frames_device_pair(bbme_ctx *ctx, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch);
+/* The reference's pipeline up-samples both frames x4 before MF::MF (main_class.cpp:32-33, cv::resize INTER_LINEAR).  These
+ * setters take the ORIGINAL frames, (width / 4) x (height / 4) for a context created at the up-sampled width x height,
+ * rows `pitch` bytes apart, and run the up-sampling fused with the zero border as one HIP kernel that writes every byte of
+ * the level-0 planes, then the pyrDown cascade: planes byte for byte those of bbme_set_frames_host on
+ * bbme_resize_x4_host's output, with a sixteenth of the bytes crossing PCIe.  BBME_ERR_INVALID when the context's width or
+ * height is not a multiple of 4 or pitch < width / 4.  Otherwise as their plain counterparts: the host setter returns once
+ * the upload has completed, the _async one only enqueues it (same buffer rules as bbme_set_frames_host_async), the device
+ * setter reads HBM on the ctx stream. */
+int bbme_set_frames_host_x4(bbme_ctx *ctx, int pair, const uint8_t *image1, const uint8_t *image2, int pitch);
+int bbme_set_frames_host_x4_async(bbme_ctx *ctx, int pair, const uint8_t *image1, const uint8_t *image2, int pitch);
+int bbme_set_frames_device_x4(bbme_ctx *ctx, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch);
 /* Which of the reference's two block searches MF::calcLevelBM calls (motion_framework.cpp:235-236): the spiral full
  * search find_min_block_spiral (:296-422, the live one: ties go to the candidate visited first on the spiral; a
  * prediction outside the image gives a zero MV) or the raster full search find_min_block (:246-294, commented out in the
@@ -244,6 +255,16 @@ int bbme_expand_cells_device(bbme_ctx *ctx, const int16_t *d_cells, float *d_flo
 int bbme_expand_cells_device_on(bbme_ctx *ctx, const int16_t *d_cells, float *d_flow, void *hip_stream);
 int bbme_get_cells_host(bbme_ctx *ctx, int16_t *cells);
 int bbme_get_cells_host_pair(bbme_ctx *ctx, int pair, int16_t *cells);
+/* The driver's subsampling (main_class.cpp:58-70: strip the padding, every `scale`-th pixel, divide by `scale`) straight
+ * from the 2x2-cell grid: a ceil(width / scale) x ceil(height / scale) float2 (u, v) field of the unpadded frame, pixel
+ * (x, y) = cell((pad_y + scale y) / 2, (pad_x + scale x) / 2) / scale.  scale 4 is bit for bit bbme_subsample_div4 of the
+ * dense field, scale 1 its unpadded window; nothing dense is written or downloaded.  BBME_ERR_INVALID for scale < 1,
+ * BBME_ERR_STATE before level 0 has reached 2x2 blocks (as bbme_calculate_mse_device).
+ * bbme_subsampled_flow_device: into d_out (rows out_pitch_pixels float2 apart) on hip_stream (NULL = the ctx stream; another
+ * stream is first ordered behind the ctx stream); no host wait.
+ * bbme_get_subsampled_flow_host: synchronises, then packed rows into `out`. */
+int bbme_subsampled_flow_device(bbme_ctx *ctx, int pair, int scale, float *d_out, int out_pitch_pixels, void *hip_stream);
+int bbme_get_subsampled_flow_host(bbme_ctx *ctx, int pair, int scale, float *out);
 /* Flow::CalculateMSE (rw_flow.cpp:309-332) on the device, fused with the driver's subsampling
  * (main_class.cpp:58-70): mean end-point error between a ground-truth field in HBM (gt_width x gt_height,
  * u,v interleaved) and the context's current result taken at every `scale`-th pixel of the unpadded frame and
