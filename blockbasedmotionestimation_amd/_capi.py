@@ -88,6 +88,12 @@ SIGNATURES = {
     "bbme_set_frames_device_x4": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
     "bbme_subsampled_flow_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "bbme_get_subsampled_flow_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_motion_compensate_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_get_motion_compensated_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_compensation_error": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_motion_compensate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_pgm_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_flow_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),
     "bbme_get_flow_host_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p]),
     "bbme_cells_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),

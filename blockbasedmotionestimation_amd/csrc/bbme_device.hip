@@ -137,7 +137,11 @@ struct bbme_ctx {
     uint8_t *raw[2] = {nullptr, nullptr};         // bbme_set_frames_host: the unpadded frames in HBM (allocated on first use)
     float *sub = nullptr;                         // bbme_get_subsampled_flow_host: the packed field before its download
     size_t sub_bytes = 0;                         // (allocated on first use, grown to the largest asked for)
-    hipEvent_t ev_sub = nullptr;                  // bbme_subsampled_flow_device: orders the caller's stream behind the ctx stream
+    hipEvent_t ev_sub = nullptr;                  // bbme_subsampled_flow_device, bbme_motion_compensate_device: orders the caller's
+                                                  // stream behind the ctx stream
+    uint8_t *mc_plane = nullptr;                  // bbme_get_motion_compensated_host: a level-0-sized plane before its download
+    unsigned long long *mc_stats = nullptr;       // bbme_compensation_error: 4 words per pair, then the partials of k_motion_compensate
+                                                  // (both allocated on first use)
 };
 
 namespace {
@@ -885,6 +889,8 @@ int bbme_destroy(bbme_ctx *c)
     (void)hipFree(c->epe_scratch);
     (void)hipFree(c->raw[0]); (void)hipFree(c->raw[1]);
     (void)hipFree(c->sub);
+    (void)hipFree(c->mc_plane);
+    (void)hipFree(c->mc_stats);
     if (c->ev_sub) (void)hipEventDestroy(c->ev_sub);
     (void)hipFree(c->list[0]); (void)hipFree(c->list[1]);
     (void)hipFree(c->own);
@@ -1377,6 +1383,116 @@ int bbme_get_subsampled_flow_host(bbme_ctx *c, int pair, int scale, float *out)
     }
     if (int rc = enqueue_subsample(c, pair, scale, c->sub, ow, c->stream, "bbme_get_subsampled_flow_host")) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->sub, bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+// ---- motion compensation: MF::draw_MVimage (motion_framework.cpp:887-905) and its residual statistics ---------------------
+
+// The arguments every motion-compensation entry point shares (include/bbme.h): level, block size, fill and window are valid,
+// and the level has a grid.  Touches no device.
+static int check_mc(const bbme_ctx *c, int level, int block, int fill, const int *window, const char *what)
+{
+    if (int rc = check_level(c, level)) return rc;
+    const Level &L = c->lv[level];
+    if (block < 1 || block > L.block || (block & (block - 1)))
+        return bbme::fail(BBME_ERR_INVALID, "%s: block %d is not a power of two in 1..%d", what, block, L.block);
+    if (fill < 0 || fill > 255) return bbme::fail(BBME_ERR_INVALID, "%s: fill %d outside 0..255", what, fill);
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > L.width || (long long)window[1] + window[3] > L.height))
+        return bbme::fail(BBME_ERR_INVALID, "%s: window (%d, %d, %d, %d) is not inside the %dx%d plane of level %d", what,
+                          window[0], window[1], window[2], window[3], L.width, L.height, level);
+    return BBME_OK;
+}
+
+static int check_mc_state(const bbme_ctx *c, int level, const char *what)
+{
+    if (c->lv[level].cur_block == 0) return bbme::fail(BBME_ERR_STATE, "%s: level %d has no MV grid yet", what, level);
+    return BBME_OK;
+}
+
+static long long mc_groups(const Level &L)
+{
+    return ((long long)(L.width + 3) / 4 * L.height + 256 * kMcRunsPerLane - 1) / (256 * kMcRunsPerLane);
+}
+
+// k_motion_compensate over `pairs` pairs from `pair0` on: the frame into d_out (one pair only) and/or, with d_stats, the
+// statistics (k_mc_reduce adds the partials, kept behind the 4 words per pair of c->mc_stats, into d_stats[4 p ..])
+static int enqueue_mc(bbme_ctx *c, int pair0, int pairs, int level, int block, int fill, const int *window, uint8_t *d_out,
+                      int out_pitch, unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[level];
+    McArgs a{};
+    a.plane_stride = L.plane_stride;
+    a.grid_stride = L.grid_stride(L.cur_grid);
+    a.img1 = L.img1 + (size_t)pair0 * a.plane_stride;
+    a.img2 = L.img2 + (size_t)pair0 * a.plane_stride;
+    a.grid = L.cur_grid + (size_t)pair0 * a.grid_stride;
+    a.out = d_out;
+    a.partial = d_stats ? c->mc_stats + (size_t)4 * BBME_MAX_BATCH : nullptr;
+    a.width = L.width; a.height = L.height;
+    a.gcols = L.width / L.cur_block;
+    a.lcb = __builtin_ctz((unsigned)L.cur_block);
+    a.lb = __builtin_ctz((unsigned)block);
+    a.fill = fill; a.out_pitch = out_pitch;
+    a.wx0 = window ? window[0] : 0; a.wy0 = window ? window[1] : 0;
+    a.wx1 = window ? window[0] + window[2] : L.width; a.wy1 = window ? window[1] + window[3] : L.height;
+    a.runs_per_row = (L.width + 3) / 4;
+    a.runs = (long long)a.runs_per_row * L.height;
+    const long long groups = mc_groups(L);
+    hipLaunchKernelGGL(k_motion_compensate, dim3((unsigned)groups, (unsigned)pairs), dim3(256), 0, stream, a);
+    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)pairs), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+int bbme_motion_compensate_device(bbme_ctx *c, int pair, int level, int block, int fill, uint8_t *d_out, int out_pitch,
+                                  void *hip_stream)
+{
+    const char *what = "bbme_motion_compensate_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_mc(c, level, block, fill, nullptr, what)) return rc;
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (out_pitch < c->lv[level].width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < level width %d", what, out_pitch, c->lv[level].width);
+    if (int rc = check_mc_state(c, level, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (stream != c->stream) {
+        if (!c->ev_sub) HIP_TRY(hipEventCreateWithFlags(&c->ev_sub, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->ev_sub, c->stream));
+        HIP_TRY(hipStreamWaitEvent(stream, c->ev_sub, 0));
+    }
+    return enqueue_mc(c, pair, 1, level, block, fill, nullptr, d_out, out_pitch, nullptr, stream);
+}
+
+int bbme_get_motion_compensated_host(bbme_ctx *c, int pair, int level, int block, int fill, uint8_t *out)
+{
+    const char *what = "bbme_get_motion_compensated_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_mc(c, level, block, fill, nullptr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_mc_state(c, level, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[level];
+    if (!c->mc_plane) HIP_TRY(hipMalloc(&c->mc_plane, (size_t)c->lv[0].width * c->lv[0].height));   // level 0 is the largest
+    if (int rc = enqueue_mc(c, pair, 1, level, block, fill, nullptr, c->mc_plane, L.width, nullptr, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->mc_plane, (size_t)L.width * L.height, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_compensation_error(bbme_ctx *c, int level, int block, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_compensation_error";
+    if (int rc = check_mc(c, level, block, 0, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_mc_state(c, level, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)4 * sizeof(unsigned long long) * c->batch;
+    // the result words of every pair, then one partial per pair and workgroup of level 0 (the largest plane)
+    if (!c->mc_stats)
+        HIP_TRY(hipMalloc(&c->mc_stats, (size_t)4 * sizeof(unsigned long long) * (BBME_MAX_BATCH + mc_groups(c->lv[0]) * c->batch)));
+    if (int rc = enqueue_mc(c, 0, c->batch, level, block, 0, window, nullptr, 0, c->mc_stats, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(stats, c->mc_stats, bytes, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
 }
 

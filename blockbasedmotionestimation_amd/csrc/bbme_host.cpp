@@ -462,6 +462,34 @@ void subsample_div4(const float *flow_padded, int padded_width, int padded_heigh
         }
 }
 
+// MF::draw_MVimage (motion_framework.cpp:887-905) as include/bbme.h states it, block by block, with the residual statistics
+void motion_compensate(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *grid, int grid_block,
+                       int block, int fill, const int window[4], uint8_t *out, unsigned long long stats[4])
+{
+    const int gcols = (width + grid_block - 1) / grid_block;
+    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
+    const int wx1 = window ? window[0] + window[2] : width, wy1 = window ? window[1] + window[3] : height;
+    unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
+    for (int Y = 0; Y < height; Y += block)
+        for (int X = 0; X < width; X += block) {
+            const int16_t *mv = grid + 2 * ((size_t)(Y / grid_block) * gcols + X / grid_block);
+            const int sx = X + mv[0], sy = Y + mv[1];
+            const bool ok = sx >= 0 && sx <= width - block && sy >= 0 && sy <= height - block;
+            for (int i = 0; i < block && Y + i < height; ++i)
+                for (int j = 0; j < block && X + j < width; ++j) {
+                    const int v = ok ? image2[(size_t)(sy + i) * width + sx + j] : fill;
+                    if (out) out[(size_t)(Y + i) * width + X + j] = (uint8_t)v;
+                    if (!stats || Y + i < wy0 || Y + i >= wy1 || X + j < wx0 || X + j >= wx1) continue;
+                    if (!ok) { ++skipped; continue; }
+                    const int d = v - image1[(size_t)(Y + i) * width + X + j];
+                    sse += (unsigned long long)(d * d);
+                    sad += (unsigned long long)(d < 0 ? -d : d);
+                    ++pixels;
+                }
+        }
+    if (stats) { stats[0] = sse; stats[1] = sad; stats[2] = pixels; stats[3] = skipped; }
+}
+
 }  // namespace bbme
 
 // ---------------------------------------------------------------------------------------
@@ -540,6 +568,33 @@ int bbme_ppm_write_bgr(const char *filename, int width, int height, const uint8_
     if (!filename || !bgr || width < 1 || height < 1)
         return bbme::fail(BBME_ERR_INVALID, "bbme_ppm_write_bgr: bad arguments");
     return bbme::ppm_write_bgr(filename, width, height, bgr);
+}
+
+int bbme_pgm_write(const char *filename, int width, int height, int pitch, const uint8_t *gray)
+{
+    if (!filename || !gray || width < 1 || height < 1 || pitch < width)
+        return bbme::fail(BBME_ERR_INVALID, "bbme_pgm_write: bad arguments");
+    FILE *f = fopen(filename, "wb");
+    if (!f) return bbme::fail(BBME_ERR_IO, "pgm_write: could not open %s", filename);
+    bool ok = fprintf(f, "P5\n%d %d\n255\n", width, height) > 0;
+    for (int y = 0; y < height && ok; ++y) ok = fwrite(gray + (size_t)y * pitch, 1, (size_t)width, f) == (size_t)width;
+    if (fclose(f) != 0) ok = false;
+    return ok ? BBME_OK : bbme::fail(BBME_ERR_IO, "pgm_write: problem writing %s", filename);
+}
+
+int bbme_motion_compensate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *grid,
+                                int grid_block, int block, int fill, const int *window, uint8_t *out, unsigned long long *stats4)
+{
+    if (!image2 || !grid || (!out && !stats4) || (stats4 && !image1))
+        return bbme::fail(BBME_ERR_INVALID, "bbme_motion_compensate_host: null pointer");
+    if (width < 1 || height < 1 || grid_block < 1 || block < 1 || (block & (block - 1)) || fill < 0 || fill > 255)
+        return bbme::fail(BBME_ERR_INVALID, "bbme_motion_compensate_host: bad arguments (%dx%d, grid block %d, block %d, fill %d)",
+                          width, height, grid_block, block, fill);
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > width || (long long)window[1] + window[3] > height))
+        return bbme::fail(BBME_ERR_INVALID, "bbme_motion_compensate_host: window not inside the %dx%d plane", width, height);
+    bbme::motion_compensate(image1, image2, width, height, grid, grid_block, block, fill, window, out, stats4);
+    return BBME_OK;
 }
 
 int bbme_subsample_div4(const float *flow_padded, int padded_width, int padded_height,

@@ -2554,4 +2554,144 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
     sad16_out[i] = __builtin_amdgcn_sad_u16(a[i], b[i], c[i] & 0xffffu);
 }
 
+// =======================================================================================
+// MF::draw_MVimage (motion_framework.cpp:887-905) fused with the residual statistics of the compensated frame against
+// image1.  b-block (X, Y) = (bx b, by b) takes its MV from grid[Y >> lcb][X >> lcb] (the current grid, cur_block =
+// 1 << lcb >= 2) and copies the b x b block of image2 at (X + dx, Y + dy) when that lies inside the plane; a skipped
+// block's pixels get `fill`.  A lane takes a run of 4 pixels along x: with b >= 4 the run lies in one block (one grid
+// read, one unaligned dword of image2); with b = 2 each half of the run is one block (an unaligned u16 each); with b = 1
+// both pixels of a half share a grid cell.  image1 is read (as a dword) only when statistics are asked for.
+// Statistics over the window [wx0, wx1) x [wy0, wy1): sse, sad and pixels over compensated pixels, skipped over the
+// others.  A lane sums at most kMcRunsPerLane runs in 32 bits and a wave's sum stays below 2^32
+// (64 * 4 * 4 * 255^2); every workgroup stores its four 64-bit sums as a partial (pair p, workgroup g at word
+// 4 (p gridDim.x + g)) and k_mc_reduce adds them up.  (64-bit atomics into the pair's four words instead: the 2040
+// workgroups of a 4K plane queue on that one cache line, 34 us against 11 us for the same pass writing the frame.)
+// Batch: blockIdx.y = pair (planes plane_stride bytes, grids grid_stride words apart); `out` only with one pair per launch.
+// =======================================================================================
+struct McArgs {
+    const uint8_t *img1, *img2;           // the level's padded planes, pitch = width
+    const mv_t *grid;                     // current grid: gcols entries per row
+    uint8_t *out;                         // compensated plane (rows out_pitch bytes apart), or null
+    unsigned long long *partial;          // per pair and workgroup {sse, sad, pixels, skipped}; or null (no statistics)
+    uint32_t plane_stride, grid_stride;
+    int width, height, gcols, lcb, lb, fill, out_pitch;
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(width / 4)
+    long long runs;                       // runs_per_row * height
+};
+
+constexpr int kMcRunsPerLane = 4;
+
+struct __attribute__((packed, aligned(1))) ua_u16 { uint16_t v; };
+
+__global__ __launch_bounds__(256) void k_motion_compensate(McArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const uint8_t *img1 = a.img1 + pair * a.plane_stride, *img2 = a.img2 + pair * a.plane_stride;
+    const mv_t *grid = a.grid + pair * a.grid_stride;
+    const int W = a.width, H = a.height, b = 1 << a.lb;
+    uint32_t sse = 0, sad = 0, npix = 0, nskip = 0;
+#pragma unroll
+    for (int k = 0; k < kMcRunsPerLane; ++k) {
+        const long long i = ((long long)blockIdx.x * kMcRunsPerLane + k) * 256 + threadIdx.x;
+        if (i >= a.runs) break;
+        const int y = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
+        const int Y = y & ~(b - 1), grow = (Y >> a.lcb) * a.gcols, iy = y - Y;
+        const int n = min(4, W - x0);                         // pixels of the run inside the row
+        uint32_t mc = 0, ok = 0;                              // gathered bytes; bit j: pixel x0 + j was compensated
+        if (b >= 4 && n == 4) {
+            const int X = x0 & ~(b - 1);
+            const mv_t m = grid[grow + (X >> a.lcb)];
+            const int sx = X + mv_x(m), sy = Y + mv_y(m);
+            if (sx >= 0 && sx <= W - b && sy >= 0 && sy <= H - b) {
+                mc = reinterpret_cast<const ua_u32 *>(img2 + (size_t)(sy + iy) * W + sx + (x0 - X))->v;
+                ok = 0xfu;
+            }
+        } else {
+            for (int h = 0; h < 2; ++h) {
+                const int xh = x0 + 2 * h;
+                if (xh >= W) break;
+                const mv_t m = grid[grow + ((xh & ~(b - 1)) >> a.lcb)];
+                const int dx = mv_x(m), sy = Y + mv_y(m);
+                if (sy < 0 || sy > H - b) continue;
+                const uint8_t *row = img2 + (size_t)(sy + iy) * W;
+                if (b == 2 && xh + 2 <= W) {
+                    const int sx = xh + dx;
+                    if (sx >= 0 && sx <= W - 2) {
+                        mc |= (uint32_t)reinterpret_cast<const ua_u16 *>(row + sx)->v << (16 * h);
+                        ok |= 3u << (2 * h);
+                    }
+                } else {
+                    for (int j = 2 * h; j < 2 * h + 2 && j < n; ++j) {
+                        const int X = (x0 + j) & ~(b - 1), sx = X + dx;
+                        if (sx >= 0 && sx <= W - b) { mc |= (uint32_t)row[sx + (x0 + j - X)] << (8 * j); ok |= 1u << j; }
+                    }
+                }
+            }
+        }
+        if (a.out) {
+            uint32_t keep = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) keep |= ((ok >> j) & 1u) ? 0xffu << (8 * j) : 0u;
+            const uint32_t v = (mc & keep) | ((uint32_t)a.fill * 0x01010101u & ~keep);
+            uint8_t *o = a.out + (size_t)y * a.out_pitch + x0;
+            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = v;
+            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(v >> (8 * j));
+        }
+        if (a.partial && y >= a.wy0 && y < a.wy1) {
+            const uint8_t *r1 = img1 + (size_t)y * W + x0;
+            uint32_t ref = 0;
+            if (n == 4) ref = reinterpret_cast<const ua_u32 *>(r1)->v;
+            else for (int j = 0; j < n; ++j) ref |= (uint32_t)r1[j] << (8 * j);
+            for (int j = 0; j < n; ++j) {
+                if (x0 + j < a.wx0 || x0 + j >= a.wx1) continue;
+                if ((ok >> j) & 1u) {
+                    const int d = (int)((mc >> (8 * j)) & 0xffu) - (int)((ref >> (8 * j)) & 0xffu);
+                    sse += (uint32_t)(d * d);
+                    sad += (uint32_t)abs(d);
+                    ++npix;
+                } else {
+                    ++nskip;
+                }
+            }
+        }
+    }
+    if (!a.partial) return;
+    for (int o = 32; o > 0; o >>= 1) {
+        sse += __shfl_xor(sse, o);
+        sad += __shfl_xor(sad, o);
+        npix += __shfl_xor(npix, o);
+        nskip += __shfl_xor(nskip, o);
+    }
+    __shared__ uint32_t part[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        uint32_t *w = part[threadIdx.x >> 6];
+        w[0] = sse; w[1] = sad; w[2] = npix; w[3] = nskip;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        a.partial[4 * (pair * gridDim.x + blockIdx.x) + threadIdx.x] =
+            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+// One workgroup per pair (blockIdx.x): the `groups` partials of k_motion_compensate into the pair's four words of `out`.
+__global__ __launch_bounds__(256) void k_mc_reduce(const unsigned long long *partial, int groups, unsigned long long *out)
+{
+    const ulonglong2 *p = reinterpret_cast<const ulonglong2 *>(partial + (size_t)4 * groups * blockIdx.x);
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int g = threadIdx.x; g < groups; g += 256) {
+        const ulonglong2 lo = p[2 * g], hi = p[2 * g + 1];
+        s[0] += lo.x; s[1] += lo.y; s[2] += hi.x; s[3] += hi.y;
+    }
+    __shared__ unsigned long long red[4][256];
+    for (int k = 0; k < 4; ++k) red[k][threadIdx.x] = s[k];
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o)
+            for (int k = 0; k < 4; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x < 4) out[4 * blockIdx.x + threadIdx.x] = red[threadIdx.x][0];
+}
+
 }  // namespace bbme

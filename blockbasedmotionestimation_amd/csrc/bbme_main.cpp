@@ -1,13 +1,15 @@
 // bbme_main.cpp -- the reference's driver (main_class.cpp:6-85) as a real command line.
 //
 //   bbme_cli frame10.pgm frame11.pgm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
-//            [--block B] [--search S] [--no-upsample] [--device D]
+//            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
 // timed calcMotionBlockMatching (:47-55) with the padding strip + every 4th pixel / 4 (:58-70) on
 // the GPU, write the field (the reference only ever colour-codes it; here Flow::WriteFlowFile is
-// actually called), EPE against ground truth (:78-82).
+// actually called), EPE against ground truth (:78-82).  --mc writes the motion-compensated frame of draw_MVimage
+// (motion_framework.cpp:887-905) with 2x2 blocks at level 0, the reference's "MC_imageL1" (:213-216), over the unpadded frame
+// MF sees, and prints its PSNR against frame 1.
 // Defaults are the reference's literals (:19-21): 4 levels, block 32, search 64.
 #include <chrono>
 #include <cstdio>
@@ -45,7 +47,7 @@ static bool read_pgm(const char *path, bbme::Image8 &img)
 
 int main(int argc, char **argv)
 {
-    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr;
+    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
     for (int i = 1; i < argc; ++i) {
@@ -54,6 +56,7 @@ int main(int argc, char **argv)
         if (a == "--gt") gt = next();
         else if (a == "--out") out = next();
         else if (a == "--color") color = next();
+        else if (a == "--mc") mc = next();
         else if (a == "--levels") levels = atoi(next());
         else if (a == "--block") block = atoi(next());
         else if (a == "--search") search = atoi(next());
@@ -65,7 +68,7 @@ int main(int argc, char **argv)
     }
     if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS) {
         fprintf(stderr, "usage: bbme_cli frame1.pgm frame2.pgm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
-                        "[--levels N] [--block B] [--search S] [--no-upsample] [--device D]\n");
+                        "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm]\n");
         return 2;
     }
     try {
@@ -94,6 +97,13 @@ int main(int argc, char **argv)
             bbme::ImageFlow gtruth;
             file.ReadFlowFile(gtruth, gt);
             printf("Calculated MSE is %.9g\n", file.CalculateMSE(gtruth, subpix));       // :82
+        }
+        if (mc) {
+            const bbme::Image8 img = motion_pair.drawMVimage(0, 2, 0);
+            const int px = motion_pair.padding_x, py = motion_pair.padding_y;
+            bbme::check(bbme_pgm_write(mc, img.cols - 2 * px, img.rows - 2 * py, img.cols, img.data.data() + (size_t)py * img.cols + px));
+            const bbme::CompensationError e = motion_pair.compensationError(0, 2);
+            printf("MC PSNR is %.9g dB over %llu pixels (%llu skipped)\n", e.psnr(), e.pixels, e.skipped);
         }
     } catch (const bbme::Error &e) {
         fprintf(stderr, "%s\n", e.what());

@@ -13,7 +13,9 @@
 // instance may run calcMotionBlockMatching() any number of times (it is not one-shot).
 #pragma once
 
+#include <cmath>
 #include <cstdint>
+#include <limits>
 #include <stdexcept>
 #include <string>
 #include <utility>
@@ -65,6 +67,19 @@ struct ImageBGR {
     ImageBGR(int r, int c) : rows(r), cols(c), data((size_t)r * c * 3) {}
     uint8_t *at(int y, int x) { return &data[3 * ((size_t)y * cols + x)]; }
     const uint8_t *at(int y, int x) const { return &data[3 * ((size_t)y * cols + x)]; }
+};
+
+// residual statistics of a motion-compensated frame (bbme_compensation_error)
+struct CompensationError {
+    unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
+    double mse() const { return pixels ? (double)sse / (double)pixels : std::numeric_limits<double>::quiet_NaN(); }
+    // 10 log10(255^2 pixels / sse); infinite for a perfect prediction, NaN when no pixel was compensated
+    double psnr() const
+    {
+        if (!pixels) return std::numeric_limits<double>::quiet_NaN();
+        if (!sse) return std::numeric_limits<double>::infinity();
+        return 10.0 * std::log10(255.0 * 255.0 * (double)pixels / (double)sse);
+    }
 };
 
 // cv::resize(img, img, cv::Size(), 4, 4, cv::INTER_LINEAR) of main_class.cpp:32-33
@@ -142,6 +157,31 @@ public:
         bbme::ImageFlow flow(scale > 0 ? (h + scale - 1) / scale : 0, scale > 0 ? (w + scale - 1) / scale : 0);
         bbme::check(bbme_get_subsampled_flow_host(ctx_, 0, scale, flow.data.data()));
         return flow;
+    }
+    // MF::draw_MVimage (motion_framework.cpp:887-905) from the level's current MV grid with b x b blocks (include/bbme.h):
+    // the padded W_l x H_l plane, skipped blocks set to `fill`.  (level 0, block 2) after calcMotionBlockMatching is the
+    // reference's "MC_imageL1" (:213-216).
+    bbme::Image8 drawMVimage(int level = 0, int block = 2, int fill = 0)
+    {
+        int w = 0, h = 0;
+        bbme::check(bbme_level_geometry(ctx_, level, &w, &h, nullptr, nullptr));
+        bbme::Image8 img(h, w);
+        bbme::check(bbme_get_motion_compensated_host(ctx_, 0, level, block, fill, img.data.data()));
+        return img;
+    }
+    // The residual statistics of that frame against image1 over window {x0, y0, w, h} of the level plane; nullptr = the
+    // unpadded frame at level 0, the whole plane at other levels.
+    bbme::CompensationError compensationError(int level = 0, int block = 2, const int *window = nullptr)
+    {
+        int w = 0, h = 0;
+        bbme::check(bbme_level_geometry(ctx_, level, &w, &h, nullptr, nullptr));
+        const int unpadded[4] = {padding_x, padding_y, w - 2 * padding_x, h - 2 * padding_y};
+        if (!window && level == 0) window = unpadded;
+        unsigned long long s[4] = {0, 0, 0, 0};
+        bbme::check(bbme_compensation_error(ctx_, level, block, window, s));
+        bbme::CompensationError e;
+        e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3];
+        return e;
     }
     bbme_ctx *context() { return ctx_; }
 

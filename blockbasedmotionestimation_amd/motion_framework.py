@@ -6,12 +6,15 @@
 
     mf = MF(image1, image2, search_size, block_size, upsample=4)   # the original frames of main_class.cpp:32-33
     sub = mf.calcMotionBlockMatchingSubsampled()                    # :58-70 on the GPU -> (h, w, 2) float32
+    mc = mf.draw_MVimage(level=0, block=2)                          # :887-905 on the GPU -> (H_pad, W_pad) uint8
+    err = mf.compensation_error()                                   # its sse / sad / pixels / skipped / mse / psnr
 
 Argument meaning and order follow the reference: arrays are indexed [0] = finest level,
 search_size is the window side length.  Errors the reference reports with assert / exit(1)
 raise BbmeError here.  All arithmetic runs in the HIP kernels of libbbme.so.
 """
 import ctypes as C
+import math
 
 import numpy as np
 
@@ -239,6 +242,58 @@ class MF:
                                                           out.stride(0) // 2, C.c_void_p(hip_stream_handle or 0)))
         return out
 
+    # -- motion compensation (MF::draw_MVimage, motion_framework.cpp:887-905; rule in include/bbme.h) -----------------
+    def _get_motion_compensated(self, pair, level, block, fill, out, what):
+        w, h, _, _ = self.level_geometry(level)
+        if out is None:
+            out = np.empty((h, w), np.uint8)
+        elif out.shape != (h, w) or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, (h, w)))
+        _capi.check(self._lib.bbme_get_motion_compensated_host(self._ctx, pair, level, block, fill, out.ctypes.data))
+        return out
+
+    def draw_MVimage(self, level=0, block=2, fill=0, out=None):
+        """MF::draw_MVimage from the level's current MV grid with block x block blocks: the padded (H_l, W_l) uint8 plane,
+        every block a copy of image2 where its MV points, blocks whose source leaves the plane set to `fill`.  Level 0 with
+        block 2 after calcMotionBlockMatching is the reference's "MC_imageL1" (:213-216)."""
+        return self._get_motion_compensated(0, level, block, fill, out, "draw_MVimage")
+
+    def motion_compensated_device(self, out, level=0, block=2, fill=0, hip_stream_handle=None, pair=0):
+        """draw_MVimage into a uint8 CUDA tensor of shape (H_l, W_l) whose rows may be further apart than W_l (a column
+        slice of a wider tensor), on the given HIP stream (default: the context's), ordered behind the context's stream;
+        no host wait."""
+        w, h, _, _ = self.level_geometry(level)
+        import torch
+        if not (out.is_cuda and out.dtype == torch.uint8 and out.dim() == 2 and tuple(out.shape) == (h, w)
+                and out.stride(1) == 1 and out.stride(0) >= w):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "motion_compensated_device: out must be a uint8 CUDA tensor of shape "
+                                  "(%d, %d) with unit column stride" % (h, w))
+        _capi.check(self._lib.bbme_motion_compensate_device(self._ctx, pair, level, block, fill, C.c_void_p(out.data_ptr()),
+                                                            out.stride(0), C.c_void_p(hip_stream_handle or 0)))
+        return out
+
+    def _compensation_stats(self, level, block, window):
+        if window is None and level == 0:
+            window = (self.padding_x, self.padding_y, self.orig_width, self.orig_height)
+        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+        pairs = getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_compensation_error(self._ctx, level, block, win, s))
+        out = []
+        for p in range(pairs):
+            sse, sad, pixels, skipped = s[4 * p:4 * p + 4]
+            mse = sse / pixels if pixels else math.nan
+            psnr = math.nan if not pixels else math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * pixels / sse)
+            out.append(dict(sse=sse, sad=sad, pixels=pixels, skipped=skipped, mse=mse, psnr=psnr))
+        return out
+
+    def compensation_error(self, level=0, block=2, window=None):
+        """Residual statistics of draw_MVimage(level, block) against image1 over window (x0, y0, w, h) of the level plane:
+        dict(sse, sad, pixels, skipped, mse, psnr).  Skipped blocks count in neither sum; mse = sse / pixels and
+        psnr = 10 log10(255^2 pixels / sse) (inf for sse = 0, nan when no pixel was compensated).  Default window: the
+        unpadded frame at level 0, the whole plane at other levels."""
+        return self._compensation_stats(level, block, window)[0]
+
     def calcMotionBlockMatchingSubsampled(self, scale=None):
         """calcMotionBlockMatching followed by get_subsampled_flow: nothing dense crosses PCIe."""
         self.estimate_async()
@@ -333,7 +388,7 @@ class MFBatch(MF):
     that share a GPU.  Every kernel of the estimate works on all pairs at once; each pair's field is bit for bit what an MF
     of its own returns.  `pairs` = [(image1, image2), ...] host arrays, or torch uint8 CUDA tensors with
     frames_on_device=True.  Of the methods inherited from MF, set_frames, set_frames_device, get_flow, get_cells,
-    get_subsampled_flow and the device-pointer getters address pair 0; the single-pair calls (stage_*, the level planes,
+    get_subsampled_flow, draw_MVimage, compensation_error and the device-pointer getters address pair 0; the single-pair calls (stage_*, the level planes,
     last_sweep_passes, sweep_stats, calculate_mse_device) raise BbmeError (ERR_UNSUPPORTED) on a batch of more than one pair.
     upsample=4: the pairs are original frames, up-sampled x4 on the GPU, as MF(..., upsample=4)."""
 
@@ -403,6 +458,14 @@ class MFBatch(MF):
     def get_pair_subsampled_flow(self, pair, scale=None, out=None):
         """MF.get_subsampled_flow of one pair."""
         return self._get_subsampled(pair, scale, out, "get_pair_subsampled_flow")
+
+    def get_pair_motion_compensated(self, pair, level=0, block=2, fill=0, out=None):
+        """MF.draw_MVimage of one pair."""
+        return self._get_motion_compensated(pair, level, block, fill, out, "get_pair_motion_compensated")
+
+    def compensation_errors(self, level=0, block=2, window=None):
+        """MF.compensation_error of every pair, in order, from one launch."""
+        return self._compensation_stats(level, block, window)
 
     def calcMotionBlockMatching(self):
         """Every pair's dense padded field, in order."""

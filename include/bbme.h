@@ -113,6 +113,9 @@ int bbme_calculate_mse(const float *gtruth, const float *flow, int width, int he
 int bbme_motion_to_color(const float *flow, int width, int height, float maxmotion, uint8_t *bgr, float *range);
 /* What Flow::ShowImage (rw_flow.cpp:334-340) keeps on disk, as binary PPM (no PNG codec, no GUI here). */
 int bbme_ppm_write_bgr(const char *filename, int width, int height, const uint8_t *bgr);
+/* Binary PGM (P5, maxval 255), the grey sibling of bbme_ppm_write_bgr: "P5\n<width> <height>\n255\n", then `height` rows of
+ * `width` bytes, consecutive rows `pitch` (>= width) bytes apart in `gray`. */
+int bbme_pgm_write(const char *filename, int width, int height, int pitch, const uint8_t *gray);
 /* main_class.cpp:58-70: strip padding, every 4th pixel, divide by 4. */
 int bbme_subsample_div4(const float *flow_padded, int padded_width, int padded_height,
                         int pad_x, int pad_y, float *out, int out_width, int out_height);
@@ -272,6 +275,41 @@ int bbme_get_subsampled_flow_host(bbme_ctx *ctx, int pair, int scale, float *out
  * float expression; the double sum is taken in a different order, so it agrees with bbme_calculate_mse to
  * about 1e-12 relative, not bit for bit.  Synchronises the ctx stream. */
 int bbme_calculate_mse_device(bbme_ctx *ctx, const float *d_gtruth, int gt_width, int gt_height, int scale, double *out);
+
+/* Motion compensation: MF::draw_MVimage (motion_framework.cpp:887-905), which the reference calls -- commented out -- on the
+ * coarsest level with that level's block size ("MC_imageL3", :160-163) and on level 0 with 2x2 blocks after the whole
+ * pyramid ("MC_imageL1", :205, 213-216), and the residual statistics of its frame against image1.
+ * For pair p, level l and block size b, the compensated plane MC is W_l x H_l (bbme_level_geometry) and is built from the
+ * level's CURRENT MV grid (block size cur_block): after bbme_estimate every level holds its final 2x2 grid; after stage calls,
+ * whatever they left.  b is a power of two in 1..B_l.  The b-block with origin (X, Y) = (bx b, by b) takes the MV (dx, dy)
+ * of the grid entry that covers pixel (X, Y), grid[Y / cur_block][X / cur_block].  Its source is (sx, sy) = (X + dx, Y + dy):
+ * if 0 <= sx <= W_l - b and 0 <= sy <= H_l - b, MC[Y + i][X + j] = image2_l[sy + i][sx + j] for 0 <= i, j < b; otherwise
+ * the block is skipped and its pixels get `fill` (0..255; the reference leaves them uninitialised).
+ * This is the reference's draw_MVimage wherever its level_flow holds MVs at the b-block origins: after a level's last
+ * divide_blocks (every level after bbme_estimate) for any b, b = 1 being a dense backward warp of image2; after
+ * bbme_stage_search(l) for b = B_l; after the sweeps at b' for b' <= b <= B_l.
+ * Residual statistics over a window {x0, y0, w, h} of the level plane (NULL = the whole plane) against image1_l, four
+ * words per pair: sse = sum (MC - image1)^2, sad = sum |MC - image1|, pixels = window pixels whose block was compensated,
+ * skipped = window pixels whose block was skipped.  Skipped pixels count in neither sum, so nothing depends on `fill`;
+ * all four are exact integers.
+ * Errors: BBME_ERR_INVALID for a null context or pointer, a pair or level out of range, a block that is not a power of two
+ * in 1..B_l, a fill outside 0..255, a window not inside the plane, out_pitch < W_l; BBME_ERR_STATE when the level has no
+ * grid yet.  These calls work on batched contexts and change no context state (grids, SAD memo, flow, cells).
+ * bbme_motion_compensate_device: MC of `pair` into d_out (rows out_pitch bytes apart) on hip_stream (NULL = the ctx stream;
+ * another stream is first ordered behind the ctx stream, as in bbme_subsampled_flow_device); no host wait.
+ * bbme_get_motion_compensated_host: synchronises, then the packed W_l x H_l plane into `out`.
+ * bbme_compensation_error: the statistics of EVERY pair in one launch, stats[4 p + {0, 1, 2, 3}] = sse, sad, pixels,
+ * skipped; synchronises (like bbme_calculate_mse_device). */
+int bbme_motion_compensate_device(bbme_ctx *ctx, int pair, int level, int block, int fill, uint8_t *d_out, int out_pitch,
+                                  void *hip_stream);
+int bbme_get_motion_compensated_host(bbme_ctx *ctx, int pair, int level, int block, int fill, uint8_t *out);
+int bbme_compensation_error(bbme_ctx *ctx, int level, int block, const int *window, unsigned long long *stats);
+/* The same rule on the CPU, no GPU: `grid` holds int16 (dx, dy) pairs, ceil(height / grid_block) rows of
+ * ceil(width / grid_block); planes and `out` are packed width x height.  image1 may be NULL (no statistics), out may be NULL
+ * (statistics only); stats4 = {sse, sad, pixels, skipped} or NULL.  Blocks cut by the plane's edge keep the rule. */
+int bbme_motion_compensate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *grid,
+                                int grid_block, int block, int fill, const int *window, uint8_t *out,
+                                unsigned long long *stats4);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
