@@ -79,3 +79,406 @@ def compare_stagewise(bbme, oracle, f1, f2, search, block, use_planes=True, rast
     mf.close()
     omf.close()
     return gflow, oflow
+
+
+# ---- content at the limits of the kernels' packed sums and keys (tests/test_limits_cpu.py proves what it does, ----
+# ---- tests/test_gpu_limits.py runs the kernels on it) ------------------------------------------------------------
+def limit_pair(family, h, w, rng):
+    """One (image1, image2) pair of h x w whose block SADs sit at the ceiling 255 * B * B of any block size B.
+    dark_on_bright: image1 = 0, image2 = 255 - U{0..3}: every SAD lies within 3 B^2 of the ceiling, neighbouring candidates
+    differ by little and the arg-min is a real one (the variation has to be in image2: with a constant image2 all candidates tie).
+    bright_on_dark: its mirror.  inverse_binary: image1 in {0, 255}, image2 = 255 - image1: the zero vector sums to exactly the
+    ceiling, everything else to about half of it.  ceiling: image1 = 0, image2 = 255 (the base of dent_planes)."""
+    if family == "dark_on_bright":
+        return np.zeros((h, w), np.uint8), (255 - rng.integers(0, 4, (h, w))).astype(np.uint8)
+    if family == "bright_on_dark":
+        return np.full((h, w), 255, np.uint8), rng.integers(0, 4, (h, w)).astype(np.uint8)
+    if family == "inverse_binary":
+        a = (rng.integers(0, 2, (h, w)) * 255).astype(np.uint8)
+        return a, (255 - a).astype(np.uint8)
+    if family == "ceiling":
+        return np.zeros((h, w), np.uint8), np.full((h, w), 255, np.uint8)
+    raise ValueError(family)
+
+
+def limit_planes(family, w, h, levels, seed):
+    """Per-level planes (planes1, planes2), level l being (h >> l) x (w >> l) and generated on its own: a pyrDown of such
+    planes would wash the structure out, so coarse levels are injected as extreme as level 0."""
+    rng = np.random.default_rng(seed)
+    pairs = [limit_pair(family, h >> l, w >> l, rng) for l in range(levels)]
+    return [p[0] for p in pairs], [p[1] for p in pairs]
+
+
+def dent_planes(w, h, block, rng_r, dents):
+    """image1 = 0, image2 = 255 except pixels of 254 ("dents"), one level.  dents = [(block_row, block_col, sx, sy)] with
+    sx, sy in {-1, 0, 1}: for sx, sy != 0 ONE pixel at the far corner of that block's search area, which of the block's
+    candidates only (sx R, sy R) contains; for (1, 0) / (0, 1) a line of B pixels along the far edge of the search area, which
+    only candidate (R, 0) / (0, R) contains whole.  Every other candidate of the block sums to exactly (or, on the lines,
+    nearer to) 255 B^2, so the dented block's winner is a candidate of the highest spiral ranks."""
+    (p1,), (p2,) = limit_planes("ceiling", w, h, 1, 0)
+    B, R = block, rng_r
+    for br, bc, sx, sy in dents:
+        x0, y0 = bc * B, br * B
+        xs = [x0 + R + B - 1] if sx > 0 else [x0 - R] if sx < 0 else list(range(x0, x0 + B))
+        ys = [y0 + R + B - 1] if sy > 0 else [y0 - R] if sy < 0 else list(range(y0, y0 + B))
+        for y in ys:
+            for x in xs:
+                assert 0 <= x < w and 0 <= y < h, "dent outside the plane"
+                p2[y, x] = 254
+    return [p1], [p2]
+
+
+def oracle_stages_from_planes(oracle, planes1, planes2, search, block, raster=False):
+    """The oracle's schedule on injected per-level planes: ([(stage, level, block, mvs)], dense flow, final 2x2 grid per level)."""
+    L = len(block)
+    omf = oracle.OracleMF(search_size=search, block_size=block, planes1=planes1, planes2=planes2)
+    if raster:
+        omf.set_raster_search(True)
+    exp = []
+    flow = oracle_schedule(omf, L, lambda *a: exp.append(a))
+    finals = [omf.block_mvs(lvl, 2).copy() for lvl in range(L)]
+    omf.close()
+    return exp, flow, finals
+
+
+def make_mf_from_planes(bbme, planes1, planes2, search, block, raster=False):
+    """A product context on the same injected planes (create it under the environment knobs of the form to be tested)."""
+    L = len(block)
+    mf = bbme.MF(planes1[0], planes2[0], search, block, L)
+    assert (mf.padded_height, mf.padded_width) == planes1[0].shape, "the limit geometries need no padding"
+    if raster:
+        mf.set_search_mode(True)
+    for lvl in range(L):
+        mf.set_level_planes(lvl, planes1[lvl], planes2[lvl])
+    return mf
+
+
+def assert_stages_equal(exp, got, what=""):
+    assert len(exp) == len(got)
+    for (en, el, eb, ev), (gn, gl, gb, gv) in zip(exp, got):
+        assert (en, el, eb) == (gn, gl, gb)
+        bad = np.argwhere((ev != gv).any(-1))
+        assert bad.size == 0, "%s: stage %s level %d block %d: %d of %d MVs differ, first at %s: oracle %s gpu %s" % (
+            what, en, el, eb, len(bad), ev.shape[0] * ev.shape[1], bad[0], ev[tuple(bad[0])], gv[tuple(bad[0])])
+
+
+def gpu_stages_match(bbme, planes1, planes2, search, block, expected, raster=False, what="", probe=None):
+    """The product's schedule on the injected planes, stage by stage against oracle_stages_from_planes' result.
+    probe(mf, stage, level, block) runs after every stage (e.g. to read bbme_sweep_stats)."""
+    exp, oflow, _ = expected
+    mf = make_mf_from_planes(bbme, planes1, planes2, search, block, raster)
+    got = []
+
+    def on_stage(*a):
+        got.append(a)
+        if probe:
+            probe(mf, *a[:3])
+    gflow = gpu_schedule(mf, len(block), block, on_stage)
+    mf.close()
+    assert_stages_equal(exp, got, what)
+    assert np.array_equal(oflow, gflow), what
+
+
+def box_sums(img, b):
+    """Sum of every b x b window of img, int64 (rows - b + 1, cols - b + 1).  With image1 = 0 the SAD of the candidate whose
+    window starts at (y, x) is box_sums(image2, b)[y, x]; with image1 = 255 it is 255 b^2 minus that."""
+    s = np.zeros((img.shape[0] + 1, img.shape[1] + 1), np.int64)
+    s[1:, 1:] = img.astype(np.int64).cumsum(0).cumsum(1)
+    return s[b:, b:] - s[:-b, b:] - s[b:, :-b] + s[:-b, :-b]
+
+
+def _content(family, w, h, search, block, seed=0, raster=False, dents=None):
+    return dict(family=family, w=w, h=h, search=list(search), block=list(block), seed=seed, raster=raster, dents=dents)
+
+
+# Contents of the limit tests, by name: geometry (no padding needed), search / block per level, family.  R = (search - block) / 2.
+LIMIT_CONTENTS = {
+    # dark-on-bright: every SAD within 3 B^2 of the ceiling; one level so that the search is the only producer of the first grid
+    "dark_b16_r16": _content("dark_on_bright", 256, 192, [48], [16], 11),          # tight plan (n = 33), rim rounds
+    "dark_b8_r16": _content("dark_on_bright", 192, 128, [40], [8], 12),
+    "dark_b32_r32": _content("dark_on_bright", 384, 256, [96], [32], 13),          # WIDE: u16 sums flushed every 8 rows
+    "dark_b16_odd": _content("dark_on_bright", 256, 192, [49], [16], 14),          # odd shift
+    "dark_b8_odd": _content("dark_on_bright", 192, 128, [41], [8], 15),
+    "dark_b32_odd": _content("dark_on_bright", 384, 256, [97], [32], 16),
+    "dark_b16_r15": _content("dark_on_bright", 256, 192, [46], [16], 17),          # odd range: no rim rounds
+    "dark_b16_r63": _content("dark_on_bright", 384, 256, [142], [16], 18),         # 16 129 candidates, ranks up to 16 128
+    "dark_b8_r63": _content("dark_on_bright", 192, 128, [134], [8], 19),
+    "dark_b32_r63": _content("dark_on_bright", 384, 256, [158], [32], 20),
+    "dark_b2": _content("dark_on_bright", 128, 96, [10], [2], 21),                 # the generic kernel's block sizes ...
+    "dark_b4": _content("dark_on_bright", 128, 96, [12], [4], 22),
+    "dark_b64": _content("dark_on_bright", 512, 384, [80], [64], 23),
+    "dark_b16_r64": _content("dark_on_bright", 256, 192, [16 + 2 * 64], [16], 24),  # ... and its ranges
+    "dark_b16_r127": _content("dark_on_bright", 256, 192, [16 + 2 * 127], [16], 25),
+    "dark_b16_raster": _content("dark_on_bright", 256, 192, [48], [16], 26, raster=True),
+    "bright_b16_r16": _content("bright_on_dark", 256, 192, [48], [16], 31),
+    "bright_b8_r16": _content("bright_on_dark", 192, 128, [40], [8], 32),
+    "bright_b32_r32": _content("bright_on_dark", 384, 256, [96], [32], 33),
+    "inverse_b16_r16": _content("inverse_binary", 256, 192, [48], [16], 41),
+    "inverse_b8_r16": _content("inverse_binary", 192, 128, [40], [8], 42),
+    "inverse_b32_r32": _content("inverse_binary", 384, 256, [96], [32], 43),
+    "inverse_b64": _content("inverse_binary", 512, 384, [80], [64], 44),
+    # the ceiling next to the border: windows leave the plane on every level (R = 32 on 512 x 384, 256 x 192, 128 x 96), so
+    # valid 0xFFxx sums and the 0xFFFF mark of an out-of-range column meet in one accumulator
+    "border_b16_r32": _content("dark_on_bright", 512, 384, [80, 80, 80], [16, 16, 16], 51),
+    "border_b8_r32": _content("dark_on_bright", 256, 256, [72, 72], [8, 8], 52),
+    "border_b32_r32": _content("bright_on_dark", 512, 512, [96, 96], [32, 32], 53),
+    # multi-level cases for the speculative search and its list (fix-up) kernel
+    "spec_b16": _content("dark_on_bright", 512, 384, [48, 48, 48], [16, 16, 16], 61),
+    "spec_b8": _content("inverse_binary", 256, 256, [40, 40], [8, 8], 62),
+    "spec_b32": _content("dark_on_bright", 512, 512, [96, 96], [32, 32], 63),
+    # the exact ceiling with dents: chosen interior blocks whose only candidate below 255 B^2 is (+-R, +-R), (+R, 0) or (0, +R)
+    "dent_b16_r16": _content("dent", 256, 192, [48], [16],
+                             dents=[(5, 7, 1, 1), (5, 3, -1, -1), (2, 10, 1, -1), (2, 3, -1, 1), (8, 5, 1, 0), (8, 11, 0, 1)]),
+    "dent_b8_r16": _content("dent", 192, 128, [40], [8],
+                            dents=[(2, 2, 1, 1), (2, 20, -1, -1), (12, 3, 1, -1), (9, 12, -1, 1), (12, 20, 1, 0), (8, 17, 0, 1)]),
+    "dent_b32_r32": _content("dent", 512, 384, [96], [32],
+                             dents=[(5, 7, 1, 1), (5, 3, -1, -1), (2, 10, 1, -1), (2, 3, -1, 1), (8, 5, 1, 0), (8, 11, 0, 1)]),
+    # ... at the highest spiral rank there is, 16 128 = (+63, -63), and the first of the last ring's last side, (-63, -63)
+    "dent_b16_r63": _content("dent", 384, 256, [142], [16], dents=[(10, 5, 1, -1), (10, 17, -1, -1)]),
+    "dent_b32_r63": _content("dent", 512, 384, [158], [32], dents=[(8, 3, 1, -1), (8, 12, -1, -1)]),
+}
+
+
+def limit_content_planes(name):
+    c = LIMIT_CONTENTS[name]
+    if c["family"] == "dent":
+        return dent_planes(c["w"], c["h"], c["block"][0], (c["search"][0] - c["block"][0]) // 2, c["dents"])
+    return limit_planes(c["family"], c["w"], c["h"], len(c["block"]), c["seed"])
+
+
+_SPLIT_OFF = {"BBME_SEARCH_SPLIT_BLOCKS": "0"}                 # k_search_fast<B, 1>
+_SPLIT_ON = {"BBME_SEARCH_SPLIT_BLOCKS": "100000000"}          # k_search_fast<B, 2>: two waves per macroblock
+# (content, environment of the context) of the search tests: every stage against the oracle
+LIMIT_SEARCH_CASES = (
+    [(n, _SPLIT_OFF) for n in LIMIT_CONTENTS if not n.startswith("spec_")] +
+    [(n, _SPLIT_ON) for n in ("dark_b16_r16", "dark_b8_r16", "dark_b32_r32", "dark_b16_r63", "dark_b8_r63", "dark_b32_r63",
+                              "inverse_b16_r16", "inverse_b32_r32", "bright_b8_r16", "border_b16_r32", "border_b32_r32",
+                              "dent_b16_r16", "dent_b8_r16", "dent_b32_r32", "dent_b16_r63", "dent_b32_r63")] +
+    [(n, dict(_SPLIT_OFF, BBME_LOOSE_PLAN="1")) for n in ("dark_b16_r16", "dark_b8_r16", "dent_b16_r16", "dent_b8_r16",
+                                                            "inverse_b16_r16", "border_b16_r32")] +
+    [(n, {"BBME_GENERIC_SEARCH": "1"}) for n in ("dark_b16_r16", "dent_b16_r16", "dent_b32_r63", "inverse_b32_r32")])
+
+# the regulariser's forms, each over all block sizes from B down to 2 (environment of the context; "memo": the SAD memo must
+# have been looked up during the sweeps)
+LIMIT_REG_CONTENTS = ("dark_b16_r16", "dark_b32_r32", "inverse_b16_r16", "bright_b8_r16", "dark_b64", "border_b16_r32")
+LIMIT_REG_FORMS = {
+    "pass1_strip": {"BBME_PASS1_STRIP": "1", "BBME_PASS1_LANES_MAX": "0"},
+    "pass1_lanes_low": {"BBME_PASS1_LANES_MAX": "0"},
+    "pass1_lanes_high": {"BBME_PASS1_LANES_MAX": "100000000"},
+    "solve_waves_1": {"BBME_SOLVE_WAVES": "1"},
+    "solve_one_wave": {"BBME_SOLVE_WGS": "1", "BBME_SOLVE_WAVES": "1"},       # (a single wave walks every chain)
+    "relax_rule": {"BBME_RELAX_RULE": "1,64,2,1"},
+    "memo_off": {"BBME_MEMO": "0"},
+    "memo_b8": {"BBME_MEMO": "1", "BBME_MEMO_MIN_B": "8", "BBME_MEMO_FORWARD": "0"},
+    "memo_b8_forward": {"BBME_MEMO": "1", "BBME_MEMO_MIN_B": "8", "BBME_MEMO_FORWARD": "1"},
+}
+
+
+# ---- grids injected with stage_set_mvs: energies beyond 2^24, the SAD memo's 8192 guard, vectors at int16's bounds ----
+def inside_field(rows, cols, b, w, h, rng):
+    """A (rows, cols, 2) int16 grid of uniformly random vectors that keep every block's own candidate inside the w x h plane."""
+    ys, xs = np.mgrid[0:rows, 0:cols] * b
+    u = rng.integers(-xs, w - b - xs + 1)
+    v = rng.integers(-ys, h - b - ys + 1)
+    return np.stack([u, v], -1).astype(np.int16)
+
+
+def energy_field(rows, cols, b, w, h, rng, huge=0.35):
+    """Large vectors, mostly inside the plane; a fraction `huge` of the blocks carries vectors of up to +-12 000 instead (they
+    point outside and score FLT_MAX, but they enter every neighbour's smoothness): lambda * mult * S then exceeds 2^24 while
+    the SADs stay in the thousands."""
+    f = inside_field(rows, cols, b, w, h, rng)
+    big = rng.random((rows, cols)) < huge
+    f[big] = rng.integers(-12000, 12001, (int(big.sum()), 2))
+    return f
+
+
+def smoothness_terms(field, lam_mult):
+    """float32 lambda * mult * S of every interior block's OWN candidate against its eight neighbours (calculate_smoothness,
+    motion_framework.cpp:623-644, restated in numpy int64) and whether that candidate lies inside a w x h plane is left to the
+    caller: returns the (rows - 2, cols - 2) float32 terms."""
+    f = field.astype(np.int64)
+    c = f[1:-1, 1:-1]
+    s = np.zeros(c.shape[:2], np.int64)
+    for dy in (0, 1, 2):
+        for dx in (0, 1, 2):
+            if (dy, dx) != (1, 1):
+                s += np.abs(f[dy:dy + c.shape[0], dx:dx + c.shape[1]] - c).sum(-1)
+    return np.float32(lam_mult) * s.astype(np.float32)
+
+
+def level_lambda(B, b):
+    """lambda of the sweeps at b under a level of B x B blocks: B / 2 at b = B, doubled at every halving (:134-151)."""
+    return float(B // 2) * (B // b)
+
+
+def oracle_sweeps_from_grid(oracle, omf, level, B, b, field, mults=(1, 2)):
+    """Sweeps at block size b on the oracle, from an injected grid, one per lambda multiplier in mults: the grid after each (int32)."""
+    omf.flow(level)[...] = 0
+    omf.flow(level)[::b, ::b, :] = field
+    omf.set_block_size(level, b)
+    omf.set_lambda(level, level_lambda(B, b))
+    out = []
+    for mult in mults:
+        omf.regularize_mvs(level, mult)
+        out.append(omf.block_mvs(level, b).copy())
+    omf.set_block_size(level, B)
+    return out
+
+
+ENERGY_LEVEL = dict(w=1024, h=1024, search=[72], block=[64], seed=71)     # one 1024 x 1024 level of 64 x 64 blocks
+ENERGY_BLOCKS = (2, 4, 8)
+ENERGY_RUNS = ((1, 2), (2,))       # both sweeps in the schedule's order, and the doubled lambda straight on the injected grid
+
+
+ENERGY_FIELDS = ("random", "ties")
+# "ties": every block carries A, B (both inside, at the same L1 distance from C) or C (far outside).  A block whose neighbourhood
+# holds as many A as B has S_A = S_B, so the energies of A and B differ by their SADs alone -- less than one ulp of the float32
+# sum once lambda * mult * S is beyond 2^24: float32 rounds them to a tie (the first candidate wins) or even flips them, where
+# exact arithmetic would take the smaller SAD.
+TIE_VECTORS = ((5, -3), (-4, 6), (12000, 12000))
+
+
+def energy_case(b, kind="random"):
+    g = ENERGY_LEVEL
+    rng = np.random.default_rng(g["seed"] + b)
+    p1 = rng.integers(0, 256, (g["h"], g["w"]), dtype=np.uint8)
+    p2 = rng.integers(0, 256, (g["h"], g["w"]), dtype=np.uint8)
+    rows, cols = g["h"] // b, g["w"] // b
+    if kind == "ties":
+        field = np.array(TIE_VECTORS, np.int16)[rng.choice(3, (rows, cols), p=[0.35, 0.35, 0.3])]
+    else:
+        field = energy_field(rows, cols, b, g["w"], g["h"], rng)
+    return [p1], [p2], field
+
+
+# the SAD memo packs a vector into 2 x 14 bits; the host allows it on levels of at most 8192 x 8192 only
+GUARD_CASES = {"wide_8192": (8192, 64, True), "wide_8448": (8448, 64, False),
+               "tall_8192": (64, 8192, True), "tall_8448": (64, 8448, False)}
+GUARD_BLOCK, GUARD_SEARCH = 16, 24
+
+
+def guard_case(name):
+    """(planes1, planes2, grid at b = 16): vectors of up to +-(size - 16) that keep every candidate's own block inside."""
+    w, h, _ = GUARD_CASES[name]
+    rng = np.random.default_rng(80 + (w * 3 + h) % 97)
+    p1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    p2 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    b = GUARD_BLOCK
+    f = inside_field(h // b, w // b, b, w, h, rng)
+    if w > h:
+        f[:, 0, 0], f[:, -1, 0] = w - b, -(w - b)
+    else:
+        f[0, :, 1], f[-1, :, 1] = h - b, -(h - b)
+    return [p1], [p2], f
+
+
+INT16_LEVELS = dict(w=256, h=192, search=[32, 32], block=[16, 16], seed=91)
+INT16_SPECIALS = [(32767, 5), (-32767, -32767), (16384, -16384), (-16384, 0), (-32768, -32768), (-32768, 32767), (3, -32768),
+                  (32767, 32767)]
+
+
+def int16_case(b):
+    """Two levels of noise planes and a level-1 grid at block size b: small vectors, with INT16_SPECIALS sprinkled in."""
+    g = INT16_LEVELS
+    rng = np.random.default_rng(g["seed"])
+    planes = [(rng.integers(0, 256, (g["h"] >> l, g["w"] >> l), dtype=np.uint8),
+               rng.integers(0, 256, (g["h"] >> l, g["w"] >> l), dtype=np.uint8)) for l in range(2)]
+    rows, cols = (g["h"] >> 1) // b, (g["w"] >> 1) // b
+    f = rng.integers(-3, 4, (rows, cols, 2)).astype(np.int16)
+    n = max(len(INT16_SPECIALS), rows * cols // 6)
+    for k, i in enumerate(rng.choice(rows * cols, n, replace=False)):
+        f[i // cols, i % cols] = INT16_SPECIALS[k % len(INT16_SPECIALS)]
+    return [p[0] for p in planes], [p[1] for p in planes], f
+
+
+def oracle_search_from_coarse(omf, field2, B1, B0):
+    """copyMVs + calcLevelBM of level 0 on the oracle from a level-1 grid given at 2 x 2 cells: level 0's grid at B0 (int32)."""
+    omf.flow(1)[...] = 0
+    omf.flow(1)[::2, ::2, :] = field2
+    omf.set_block_size(1, B1)
+    omf.copy_mvs(0)
+    omf.calc_level_bm(0)
+    return omf.block_mvs(0, B0).copy()
+
+
+def epe_reference(gt, cells, pad_x, pad_y, scale):
+    """Flow::CalculateMSE (rw_flow.cpp:309-332) on the field the 2 x 2-cell grid holds at every scale-th pixel of the unpadded
+    frame, divided by scale: the float32 per-pixel expression sqrtf(du * du + dv * dv), every operation rounded to float32 on
+    its own (numpy fuses nothing), summed in float64; unknown ground truth (|u| or |v| > 1e9, NaN) is skipped; NaN when nothing
+    is known."""
+    gt = np.asarray(gt, np.float32)
+    gh, gw = gt.shape[:2]
+    ys = (pad_y + scale * np.arange(gh)) >> 1
+    xs = (pad_x + scale * np.arange(gw)) >> 1
+    est = cells[np.ix_(ys, xs)].astype(np.float32) / np.float32(scale)
+    with np.errstate(invalid="ignore", over="ignore"):
+        known = ~((np.abs(gt[..., 0]) > np.float32(1e9)) | (np.abs(gt[..., 1]) > np.float32(1e9)) |
+                  np.isnan(gt[..., 0]) | np.isnan(gt[..., 1]))
+        du = (gt[..., 0] - est[..., 0]).astype(np.float32)
+        dv = (gt[..., 1] - est[..., 1]).astype(np.float32)
+        sq = ((du * du).astype(np.float32) + (dv * dv).astype(np.float32)).astype(np.float32)
+        e = np.sqrt(sq).astype(np.float32)
+    n = int(known.sum())
+    return float(e[known].astype(np.float64).sum()) / n if n else float("nan")
+
+
+def epe_ground_truth(gh, gw, kind, rng):
+    """A float32 (gh, gw, 2) ground-truth field: plain: finite values; holes: with +-inf, NaN and values just below, at and just
+    above the 1e9 threshold of "unknown"; unknown: nothing known."""
+    gt = (rng.random((gh, gw, 2)) * 40 - 20).astype(np.float32)
+    if kind == "unknown":
+        gt[..., 0] = np.where(rng.random((gh, gw)) < 0.5, np.float32(np.nan), np.float32(2e9))
+        return gt
+    if kind == "holes":
+        big = np.float32(1e9)
+        vals = [np.inf, -np.inf, np.nan, np.nextafter(big, np.float32(0)), big, np.nextafter(big, np.float32(np.inf)),
+                -np.nextafter(big, np.float32(0)), -np.nextafter(big, np.float32(np.inf))]
+        flat = gt.reshape(-1)
+        idx = rng.choice(flat.size, min(flat.size // 2, 8 * max(1, flat.size // 200)), replace=False)
+        for k, i in enumerate(idx):
+            flat[i] = vals[k % len(vals)]
+    return gt
+
+
+# one batched context of four pairs, one level, the families mixed pair by pair (whole frames: the level-0 planes of a frame
+# that needs no padding are the frame itself)
+LIMIT_BATCH_CONTENTS = ("dark_b16_r16", "bright_b16_r16", "inverse_b16_r16", "dent_b16_r16")
+# bbme_estimate with the speculative search and its list kernel forced onto every level
+LIMIT_SPEC_CONTENTS = ("spec_b16", "spec_b8", "spec_b32")
+
+
+def block_sads_of_vector(p1, p2, b, vec):
+    """int64 SAD of every b x b block of p1 against p2 displaced by vec, and whether the displaced block lies inside the plane."""
+    dx, dy = vec
+    h, w = p1.shape
+    moved, valid = np.zeros((h, w), np.int64), np.zeros((h, w), bool)
+    ys, xs = slice(max(0, -dy), min(h, h - dy)), slice(max(0, -dx), min(w, w - dx))
+    moved[ys, xs] = p2[ys.start + dy:ys.stop + dy, xs.start + dx:xs.stop + dx]
+    valid[ys, xs] = True
+    sad = np.abs(p1.astype(np.int64) - moved).reshape(h // b, b, w // b, b).sum((1, 3))
+    return sad, valid.reshape(h // b, b, w // b, b).all((1, 3))
+
+
+def tie_field_float_vs_exact(p1, p2, b, field, lam_mult):
+    """On a "ties" grid: the interior blocks whose neighbourhood holds as many A as B (>= 1) and at least one C, whose common term
+    lambda * mult * S is beyond 2^24 and whose A and B candidates are inside; and, of them, those where the order of the float32
+    energies of A and B is not the order of the exact sums.  Returns (blocks, blocks where float32 and exact disagree)."""
+    A, B, C = TIE_VECTORS
+
+    def count(mask):
+        m = mask.astype(np.int64)
+        r, c = m.shape
+        return sum(m[dy:dy + r - 2, dx:dx + c - 2] for dy in range(3) for dx in range(3))
+    na, nb, nc = (count((field == v).all(-1)) for v in TIE_VECTORS)
+    d_ab = abs(A[0] - B[0]) + abs(A[1] - B[1])
+    d_c = abs(C[0] - A[0]) + abs(C[1] - A[1])
+    assert d_c == abs(C[0] - B[0]) + abs(C[1] - B[1])
+    t = np.float32(lam_mult) * (nb * d_ab + nc * d_c).astype(np.float32)            # S_A = S_B where na == nb
+    sad_a, in_a = block_sads_of_vector(p1, p2, b, A)
+    sad_b, in_b = block_sads_of_vector(p1, p2, b, B)
+    sad_a, sad_b = sad_a[1:-1, 1:-1], sad_b[1:-1, 1:-1]
+    ok = (na == nb) & (na >= 1) & (nc >= 1) & (t > 2.0 ** 24) & in_a[1:-1, 1:-1] & in_b[1:-1, 1:-1]
+    e_a, e_b = sad_a.astype(np.float32) + t, sad_b.astype(np.float32) + t           # float32 sums, as :607
+    differs = np.sign(sad_a - sad_b) != np.sign(e_a.astype(np.float64) - e_b.astype(np.float64))
+    return int(ok.sum()), int((ok & differs).sum())
