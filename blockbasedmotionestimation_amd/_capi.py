@@ -73,6 +73,12 @@ SIGNATURES = {
     "bbme_create": (C.c_int, [_P(Params), C.c_int, C.c_int, C.c_int, _P(_ctx)]),
     "bbme_create_batch": (C.c_int, [_P(Params), C.c_int, C.c_int, C.c_int, C.c_int, _P(_ctx)]),
     "bbme_batch_size": (C.c_int, [_ctx, _P(C.c_int)]),
+    "bbme_create_chain": (C.c_int, [_P(Params), C.c_int, C.c_int, C.c_int, C.c_int, _P(_ctx)]),
+    "bbme_chain_frames": (C.c_int, [_ctx, _P(C.c_int)]),
+    "bbme_set_chain_frames_host": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int, C.c_int]),
+    "bbme_set_chain_frames_host_async": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int, C.c_int]),
+    "bbme_set_chain_frames_device": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int, C.c_int]),
+    "bbme_chain_advance": (C.c_int, [_ctx]),
     "bbme_destroy": (C.c_int, [_ctx]),
     "bbme_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "bbme_get_stream": (C.c_int, [_ctx, _P(C.c_void_p)]),

@@ -100,7 +100,17 @@ struct bbme_ctx {
     int memo_min_block = 16;                      // sweeps at smaller blocks run without it (8: measured slower); BBME_MEMO_MIN_B
     bool memo_forward = false;                    // BBME_MEMO_FORWARD (measured slower: off)
     uint64_t frames_mask = 0;                     // bit p: pair p has frames (bbme_estimate needs every pair's)
-    bool frames_set() const { return frames_mask == (batch >= 64 ? ~0ull : (1ull << batch) - 1ull); }
+    // chain context (bbme_create_chain): batch + 1 frame SLOTS in one allocation per level (Level::img1; img2 = img1 + one plane
+    // stride, so pair p reads slots p and p + 1).  frames_mask then has one bit per slot 0 .. 63, last_slot is slot 64.
+    bool chain = false;
+    bool last_slot = false;
+    void mark_slot(int s) { if (s < 64) frames_mask |= 1ull << s; else last_slot = true; }
+    void mark_pair0() { if (chain) { mark_slot(0); mark_slot(1); } else frames_mask |= 1ull; }
+    bool frames_set() const
+    {
+        const int n = chain ? batch + 1 : batch;
+        return frames_mask == (n >= 64 ? ~0ull : (1ull << n) - 1ull) && (n <= 64 || last_slot);
+    }
     double *epe_scratch = nullptr;                // partial sums + counts of bbme_calculate_mse_device (allocated on first use)
     int local_rounds = 8;                         // k_reg_iter: heavy rounds of a tile per launch; BBME_LOCAL_ROUNDS
     int wide_threshold = 16;                      // solver: queue length above which a round takes the throughput form; BBME_WIDE_THRESHOLD
@@ -159,6 +169,31 @@ int single_pair_only(const bbme_ctx *c, const char *what)
     if (int rc = check_ctx(c)) return rc;
     if (c->batch > 1)
         return bbme::fail(BBME_ERR_UNSUPPORTED, "%s addresses one pair: not available on a batched context (%d pairs)", what, c->batch);
+    return BBME_OK;
+}
+
+// The pair setters write both planes of a pair; in a chain context a plane belongs to two pairs and is set by slot.
+int pair_context_only(const bbme_ctx *c, const char *what)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (c->chain)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "%s sets the two frames of a pair: a chain context (%d pairs over %d frame slots) "
+                                                "is fed with bbme_set_chain_frames_*", what, c->batch, c->batch + 1);
+    return BBME_OK;
+}
+
+int chain_context_only(const bbme_ctx *c, const char *what)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->chain) return bbme::fail(BBME_ERR_UNSUPPORTED, "%s needs a chain context (bbme_create_chain)", what);
+    return BBME_OK;
+}
+
+// Calls that read planes on a chain context between bbme_chain_advance and the setting of the last slot
+int chain_slots_ready(const bbme_ctx *c, const char *what)
+{
+    if (c->chain && !c->frames_set())
+        return bbme::fail(BBME_ERR_STATE, "%s: not every frame slot of the chain context is set", what);
     return BBME_OK;
 }
 
@@ -643,7 +678,19 @@ int bbme_create(const bbme_params *params, int width, int height, int device, bb
     return bbme_create_batch(params, width, height, device, 1, out);
 }
 
+static int create_context(const bbme_params *params, int width, int height, int device, int pairs, bool chain, bbme_ctx **out);
+
 int bbme_create_batch(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out)
+{
+    return create_context(params, width, height, device, pairs, false, out);
+}
+
+int bbme_create_chain(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out)
+{
+    return create_context(params, width, height, device, pairs, true, out);
+}
+
+static int create_context(const bbme_params *params, int width, int height, int device, int pairs, bool chain, bbme_ctx **out)
 {
     if (!params || !out) return bbme::fail(BBME_ERR_INVALID, "bbme_create: null argument");
     *out = nullptr;
@@ -676,6 +723,7 @@ int bbme_create_batch(const bbme_params *params, int width, int height, int devi
     bbme_ctx *c = new bbme_ctx();
     c->params = *params; c->geom = g; c->device = device;
     c->batch = pairs;
+    c->chain = chain;
     const size_t P = (size_t)pairs;
     auto round64 = [](size_t n) { return (n + 63) / 64 * 64; };
     if (const char *e = getenv("BBME_SOLVE_SHARE")) c->solve_share = atoi(e) != 0;
@@ -745,7 +793,10 @@ int bbme_create_batch(const bbme_params *params, int width, int height, int devi
         std::vector<uint32_t> packed(sp.dx.size());
         for (size_t i = 0; i < sp.dx.size(); ++i)
             packed[i] = ((uint32_t)(uint16_t)sp.dx[i]) | ((uint32_t)(uint16_t)sp.dy[i] << 16);
-        if ((err = hipMalloc(&L.img1, P * plane)) != hipSuccess || (err = hipMalloc(&L.img2, P * plane)) != hipSuccess ||
+        // a chain context: the P + 1 frame slots of the level in ONE allocation, image 2 of pair p = image 1 of pair p + 1
+        const size_t img1_bytes = (chain ? P + 1 : P) * plane;
+        if ((err = hipMalloc(&L.img1, img1_bytes)) != hipSuccess ||
+            (chain ? (L.img2 = L.img1 + plane, err = hipSuccess) : (err = hipMalloc(&L.img2, P * plane))) != hipSuccess ||
             (err = hipMalloc(&L.small[0], P * own_blocks * sizeof(mv_t))) != hipSuccess ||
             (err = hipMalloc(&L.small[1], P * own_blocks * sizeof(mv_t))) != hipSuccess ||
             (err = hipMalloc(&L.pred, P * own_blocks * sizeof(mv_t))) != hipSuccess ||
@@ -755,7 +806,7 @@ int bbme_create_batch(const bbme_params *params, int width, int height, int devi
             (err = hipMalloc(&L.big[0], P * cells * sizeof(mv_t))) != hipSuccess ||
             (err = hipMalloc(&L.big[1], P * cells * sizeof(mv_t))) != hipSuccess ||
             (err = hipMalloc(&L.spiral, packed.size() * 4)) != hipSuccess ||
-            (err = hipMemset(L.img1, 0, P * plane)) != hipSuccess || (err = hipMemset(L.img2, 0, P * plane)) != hipSuccess ||
+            (err = hipMemset(L.img1, 0, img1_bytes)) != hipSuccess || (!chain && (err = hipMemset(L.img2, 0, P * plane)) != hipSuccess) ||
             (err = hipMemcpy(L.spiral, packed.data(), packed.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
             return cleanup_fail(bbme::fail(BBME_ERR_HIP, "allocating level %d: %s", l, hipGetErrorString(err)));
         // the speculative search of this level pads its workgroups to this much LDS (launch_search's lds_floor)
@@ -878,7 +929,8 @@ int bbme_destroy(bbme_ctx *c)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     drop_graph(c);
     for (Level &L : c->lv) {
-        (void)hipFree(L.img1); (void)hipFree(L.img2);
+        (void)hipFree(L.img1);
+        if (!c->chain) (void)hipFree(L.img2);
         (void)hipFree(L.small[0]); (void)hipFree(L.small[1]); (void)hipFree(L.pred);
         (void)hipFree(L.fix_list); (void)hipFree(L.fix_count);
         (void)hipFree(L.big[0]); (void)hipFree(L.big[1]); (void)hipFree(L.spiral);
@@ -1040,7 +1092,7 @@ static int upload_raw(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_
 
 int bbme_set_frames_host_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
 {
-    if (int rc = check_ctx(c)) return rc;
+    if (int rc = pair_context_only(c, "bbme_set_frames_host")) return rc;
     if (!image1 || !image2 || pitch < c->geom.width || pair < 0 || pair >= c->batch)
         return bbme::fail(BBME_ERR_INVALID, "bbme_set_frames_host: bad arguments");
     HIP_TRY(hipSetDevice(c->device));
@@ -1062,7 +1114,7 @@ static int enqueue_cascade(bbme_ctx *c, int pair);
 
 int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
 {
-    if (int rc = check_ctx(c)) return rc;
+    if (int rc = pair_context_only(c, "bbme_set_frames_device")) return rc;
     if (!d_image1 || !d_image2 || pitch < c->geom.width || pair < 0 || pair >= c->batch)
         return bbme::fail(BBME_ERR_INVALID, "bbme_set_frames_device: bad arguments");
     HIP_TRY(hipSetDevice(c->device));
@@ -1103,7 +1155,7 @@ static int enqueue_cascade(bbme_ctx *c, int pair)
 
 static int check_x4(const bbme_ctx *c, int pair, const void *image1, const void *image2, int pitch, const char *what)
 {
-    if (int rc = check_ctx(c)) return rc;
+    if (int rc = pair_context_only(c, what)) return rc;
     const Geometry &g = c->geom;
     if (g.width % 4 || g.height % 4)
         return bbme::fail(BBME_ERR_INVALID, "%s: the context's frame (%dx%d) is not a multiple of 4 in both dimensions", what,
@@ -1145,13 +1197,133 @@ int bbme_set_frames_host_x4(bbme_ctx *c, int pair, const uint8_t *image1, const 
     return BBME_OK;
 }
 
+// ---- chain contexts: frames by slot, rolled forward through a video ----------------------------------------------------
+
+int bbme_chain_frames(const bbme_ctx *c, int *frames)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (!frames) return bbme::fail(BBME_ERR_INVALID, "null output");
+    *frames = c->chain ? c->batch + 1 : 0;
+    return BBME_OK;
+}
+
+static int check_chain_run(const bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale, const char *what)
+{
+    if (int rc = chain_context_only(c, what)) return rc;
+    const Geometry &g = c->geom;
+    if (scale != 1 && scale != 4) return bbme::fail(BBME_ERR_INVALID, "%s: scale %d (1 or 4)", what, scale);
+    if (scale == 4 && (g.width % 4 || g.height % 4))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the context's frame (%dx%d) is not a multiple of 4 in both dimensions", what,
+                          g.width, g.height);
+    if (first < 0 || count < 1 || first > c->batch || count > c->batch + 1 - first)
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d of %d", what, first, first + count - 1, c->batch + 1);
+    if (!frames) return bbme::fail(BBME_ERR_INVALID, "%s: null frame table", what);
+    for (int i = 0; i < count; ++i)
+        if (!frames[i]) return bbme::fail(BBME_ERR_INVALID, "%s: frame %d of the run is null", what, i);
+    if (pitch < g.width / scale) return bbme::fail(BBME_ERR_INVALID, "%s: pitch %d < frame width %d", what, pitch, g.width / scale);
+    return BBME_OK;
+}
+
+// `count` frames in HBM into slots first .. : border (or x4 up-sampling + border) as one launch, then one pyrDown launch per
+// level, all frames of the run in each (blockIdx.y); and the bookkeeping every frame setter shares (enqueue_cascade)
+static int enqueue_chain_run(bbme_ctx *c, int first, int count, const FrameRun &run, int pitch, int scale)
+{
+    const Geometry &g = c->geom;
+    Level &L0 = c->lv[0];
+    uint8_t *dst0 = L0.img1 + (size_t)first * L0.plane_stride;
+    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
+    const dim3 grid0((unsigned)((chunks + 255) / 256), (unsigned)count);
+    if (scale == 4)
+        hipLaunchKernelGGL(k_resize_x4_pad_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width / 4, g.height / 4,
+                           pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    else
+        hipLaunchKernelGGL(k_pad_zero_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width, g.height, pitch,
+                           g.pad_x, g.pad_y, L0.width, L0.height);
+    for (size_t l = 1; l < c->lv.size(); ++l) {
+        Level &P = c->lv[l - 1], &L = c->lv[l];
+        const uint8_t *src = P.img1 + (size_t)first * P.plane_stride;
+        uint8_t *dst = L.img1 + (size_t)first * L.plane_stride;
+        if (P.width % 8 == 0) {
+            const long long n = (long long)(L.width / 4) * L.height;
+            hipLaunchKernelGGL(k_pyr_down4_run, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, c->stream,
+                               src, P.plane_stride, dst, L.plane_stride, P.width, P.height);
+        } else {
+            const long long n = (long long)L.width * L.height;
+            hipLaunchKernelGGL(k_pyr_down_run, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, c->stream,
+                               src, P.plane_stride, dst, L.plane_stride, P.width, P.height);
+        }
+    }
+    HIP_TRY(hipGetLastError());
+    for (int i = 0; i < count; ++i) c->mark_slot(first + i);
+    c->memo_block = 0;                                  // new planes: what the SAD memo holds is no longer true
+    return BBME_OK;
+}
+
+int bbme_set_chain_frames_device(bbme_ctx *c, int first, int count, const uint8_t *const *d_frames, int pitch, int scale)
+{
+    if (int rc = check_chain_run(c, first, count, d_frames, pitch, scale, "bbme_set_chain_frames_device")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    FrameRun run{};
+    for (int i = 0; i < count; ++i) run.src[i] = d_frames[i];
+    return enqueue_chain_run(c, first, count, run, pitch, scale);
+}
+
+int bbme_set_chain_frames_host_async(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale)
+{
+    if (int rc = check_chain_run(c, first, count, frames, pitch, scale, "bbme_set_chain_frames_host")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // every frame crosses PCIe once, packed, into its slot of ONE upload buffer (as upload_raw: room for the context's frame size)
+    const Geometry &g = c->geom;
+    const int sw = g.width / scale, sh = g.height / scale;
+    c->raw_stride = ((size_t)g.width * g.height + 64 + 255) / 256 * 256;
+    if (!c->raw[0]) HIP_TRY(hipMalloc(&c->raw[0], c->raw_stride * (size_t)(c->batch + 1)));
+    FrameRun run{};
+    for (int i = 0; i < count; ++i) {
+        uint8_t *d = c->raw[0] + (size_t)(first + i) * c->raw_stride;
+        HIP_TRY(hipMemcpy2DAsync(d, sw, frames[i], pitch, sw, sh, hipMemcpyHostToDevice, c->stream));
+        run.src[i] = d;
+    }
+    return enqueue_chain_run(c, first, count, run, sw, scale);
+}
+
+int bbme_set_chain_frames_host(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale)
+{
+    if (int rc = bbme_set_chain_frames_host_async(c, first, count, frames, pitch, scale)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
+    return BBME_OK;
+}
+
+int bbme_chain_advance(bbme_ctx *c)
+{
+    if (int rc = chain_context_only(c, "bbme_chain_advance")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    // the planes of the last slot, all levels, become slot 0: one copy launch behind whatever still reads the slots
+    ChainRoll r{};
+    uint32_t most = 0;
+    for (size_t l = 0; l < c->lv.size(); ++l) {
+        Level &L = c->lv[l];
+        r.src[l] = reinterpret_cast<const uint4 *>(L.img1 + (size_t)c->batch * L.plane_stride);
+        r.dst[l] = reinterpret_cast<uint4 *>(L.img1);
+        r.n16[l] = L.plane_stride / 16;
+        most = std::max(most, r.n16[l]);
+    }
+    const unsigned wgs = std::max(1u, std::min(2048u, (most + 255u) / 256u));
+    hipLaunchKernelGGL(k_chain_roll, dim3(wgs, (unsigned)c->lv.size()), dim3(256), 0, c->stream, r);
+    HIP_TRY(hipGetLastError());
+    const bool had_last = c->batch < 64 ? (c->frames_mask >> c->batch) & 1ull : c->last_slot;
+    c->frames_mask = had_last ? 1ull : 0ull;         // slot 0 is as set as the slot it came from
+    c->last_slot = false;
+    c->memo_block = 0;
+    return BBME_OK;
+}
+
 int bbme_level_planes_device(bbme_ctx *c, int level, uint8_t **d1, uint8_t **d2)
 {
     if (int rc = single_pair_only(c, "bbme_level_planes_device")) return rc;
     if (int rc = check_level(c, level)) return rc;
     if (d1) *d1 = c->lv[level].img1;
     if (d2) *d2 = c->lv[level].img2;
-    c->frames_mask |= 1ull;        // the caller fills them in place (pair 0)
+    c->mark_pair0();               // the caller fills them in place (pair 0; a chain of one pair: slots 0 and 1)
     c->memo_block = 0;
     return BBME_OK;
 }
@@ -1166,7 +1338,7 @@ int bbme_set_level_planes_host(bbme_ctx *c, int level, const uint8_t *image1, co
     HIP_TRY(hipMemcpyAsync(L.img1, image1, (size_t)L.width * L.height, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(L.img2, image2, (size_t)L.width * L.height, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->frames_mask |= 1ull;
+    c->mark_pair0();
     c->memo_block = 0;
     return BBME_OK;
 }
@@ -1406,6 +1578,7 @@ static int check_mc(const bbme_ctx *c, int level, int block, int fill, const int
 
 static int check_mc_state(const bbme_ctx *c, int level, const char *what)
 {
+    if (int rc = chain_slots_ready(c, what)) return rc;
     if (c->lv[level].cur_block == 0) return bbme::fail(BBME_ERR_STATE, "%s: level %d has no MV grid yet", what, level);
     return BBME_OK;
 }

@@ -2166,11 +2166,11 @@ __global__ __launch_bounds__(256) void k_subsample(const mv_t *cells, int cell_c
 // =======================================================================================
 struct PlanePair { const uint8_t *src[2]; uint8_t *dst[2]; };
 
-__global__ __launch_bounds__(256) void k_pad_zero(PlanePair p, int width, int height, int pitch,
-                                                  int pad_x, int pad_y, int pw, int ph)
+// (the bodies are __device__ functions of one plane: k_pad_zero & co. take the two frames of a pair, the *_run kernels
+//  further down the frames of a run -- the same integers either way)
+__device__ __forceinline__ void pad_zero_plane(const uint8_t *src, uint8_t *dst, int width, int height, int pitch,
+                                               int pad_x, int pad_y, int pw, int ph)
 {
-    const uint8_t *src = p.src[blockIdx.y];
-    uint8_t *dst = p.dst[blockIdx.y];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;    // 16 output bytes (pw is a multiple of 4)
     const int per_row = (pw + 15) / 16;
     if (t >= (long long)per_row * ph) return;
@@ -2201,6 +2201,12 @@ __global__ __launch_bounds__(256) void k_pad_zero(PlanePair p, int width, int he
     }
 }
 
+__global__ __launch_bounds__(256) void k_pad_zero(PlanePair p, int width, int height, int pitch,
+                                                  int pad_x, int pad_y, int pw, int ph)
+{
+    pad_zero_plane(p.src[blockIdx.y], p.dst[blockIdx.y], width, height, pitch, pad_x, pad_y, pw, ph);
+}
+
 // =======================================================================================
 // cv::resize(..., 4, 4, INTER_LINEAR) of main_class.cpp:32-33 fused with the zero border (motion_framework.cpp:57-61):
 // pixel (X, Y) of the padded plane is resize_x4(src)(X - pad_x, Y - pad_y) inside the frame, 0 outside.  Bit for bit
@@ -2215,11 +2221,9 @@ __device__ __forceinline__ int resize_x4_w0(int phase)      // weight of the fir
     return phase == 0 ? 768 : phase == 1 ? 256 : phase == 2 ? 1792 : 1280;
 }
 
-__global__ __launch_bounds__(256) void k_resize_x4_pad(PlanePair p, int sw, int sh, int pitch,
-                                                       int pad_x, int pad_y, int pw, int ph)
+__device__ __forceinline__ void resize_x4_pad_plane(const uint8_t *src, uint8_t *dst, int sw, int sh, int pitch,
+                                                    int pad_x, int pad_y, int pw, int ph)
 {
-    const uint8_t *src = p.src[blockIdx.y];
-    uint8_t *dst = p.dst[blockIdx.y];
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     const int per_row = (pw + 15) / 16;
     if (t >= (long long)per_row * ph) return;
@@ -2268,6 +2272,12 @@ __global__ __launch_bounds__(256) void k_resize_x4_pad(PlanePair p, int sw, int 
     }
 }
 
+__global__ __launch_bounds__(256) void k_resize_x4_pad(PlanePair p, int sw, int sh, int pitch,
+                                                       int pad_x, int pad_y, int pw, int ph)
+{
+    resize_x4_pad_plane(p.src[blockIdx.y], p.dst[blockIdx.y], sw, sh, pitch, pad_x, pad_y, pw, ph);
+}
+
 __device__ __forceinline__ int mirror101(int p, int n)
 {
     if (n == 1) return 0;
@@ -2276,10 +2286,8 @@ __device__ __forceinline__ int mirror101(int p, int n)
 }
 
 // one output pixel per thread: planes whose half width is not a multiple of 4
-__global__ __launch_bounds__(256) void k_pyr_down(PlanePair p, int sw, int sh)
+__device__ __forceinline__ void pyr_down_plane(const uint8_t *src, uint8_t *dst, int sw, int sh)
 {
-    const uint8_t *src = p.src[blockIdx.y];
-    uint8_t *dst = p.dst[blockIdx.y];
     const int dw = sw / 2, dh = sh / 2;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long long)dw * dh) return;
@@ -2300,14 +2308,17 @@ __global__ __launch_bounds__(256) void k_pyr_down(PlanePair p, int sw, int sh)
     dst[(size_t)y * dw + x] = (uint8_t)((acc + 128) >> 8);
 }
 
+__global__ __launch_bounds__(256) void k_pyr_down(PlanePair p, int sw, int sh)
+{
+    pyr_down_plane(p.src[blockIdx.y], p.dst[blockIdx.y], sw, sh);
+}
+
 // four output pixels per thread (sw a multiple of 8): output x = 4k + c reads input bytes 8k + 2c - 2 .. 8k + 2c + 2, all
 // inside the four dwords at 8k - 4 .. 8k + 11.  h = [1 4 6 4] . bytes[o .. o+3] (v_dot4_u32_u8 on a re-aligned dword)
 // + byte[o + 4]; out = (h0 + 4 h1 + 6 h2 + 4 h3 + h4 + 128) >> 8 over the five (mirrored) rows -- the same integers as
 // the separable host form, no rounding in between.
-__global__ __launch_bounds__(256) void k_pyr_down4(PlanePair p, int sw, int sh)
+__device__ __forceinline__ void pyr_down4_plane(const uint8_t *src, uint8_t *dst, int sw, int sh)
 {
-    const uint8_t *src = p.src[blockIdx.y];
-    uint8_t *dst = p.dst[blockIdx.y];
     const int dw = sw / 2, dh = sh / 2, per_row = dw / 4;
     const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
     if (t >= (long long)per_row * dh) return;
@@ -2340,6 +2351,55 @@ __global__ __launch_bounds__(256) void k_pyr_down4(PlanePair p, int sw, int sh)
     }
     const uint32_t out = (acc[0] >> 8) | (acc[1] >> 8) << 8 | (acc[2] >> 8) << 16 | (acc[3] >> 8) << 24;
     *reinterpret_cast<uint32_t *>(dst + (size_t)y * dw + 4 * k) = out;
+}
+
+__global__ __launch_bounds__(256) void k_pyr_down4(PlanePair p, int sw, int sh)
+{
+    pyr_down4_plane(p.src[blockIdx.y], p.dst[blockIdx.y], sw, sh);
+}
+
+// =======================================================================================
+// Frame preparation of a chain context (bbme_create_chain): the frames of a RUN in one launch per step, blockIdx.y = frame
+// of the run.  Level 0: frame f is read from run.src[f] (a kernel-argument table: the frames of a video lie anywhere) and
+// written to dst + f * s_dst, the slots of the context lying one plane stride apart; the cascade reads and writes slots
+// (src + f * s_src -> dst + f * s_dst).  So a round costs num_levels launches whatever the number of frames.  Per plane the
+// bodies above, unchanged.
+// =======================================================================================
+constexpr int kMaxChainFrames = 65;                    // BBME_MAX_BATCH pairs are one frame more
+struct FrameRun { const uint8_t *src[kMaxChainFrames]; };
+
+__global__ __launch_bounds__(256) void k_pad_zero_run(FrameRun run, uint8_t *dst, uint32_t s_dst, int width, int height, int pitch,
+                                                      int pad_x, int pad_y, int pw, int ph)
+{
+    pad_zero_plane(run.src[blockIdx.y], dst + (size_t)blockIdx.y * s_dst, width, height, pitch, pad_x, pad_y, pw, ph);
+}
+
+__global__ __launch_bounds__(256) void k_resize_x4_pad_run(FrameRun run, uint8_t *dst, uint32_t s_dst, int sw, int sh, int pitch,
+                                                           int pad_x, int pad_y, int pw, int ph)
+{
+    resize_x4_pad_plane(run.src[blockIdx.y], dst + (size_t)blockIdx.y * s_dst, sw, sh, pitch, pad_x, pad_y, pw, ph);
+}
+
+__global__ __launch_bounds__(256) void k_pyr_down_run(const uint8_t *src, uint32_t s_src, uint8_t *dst, uint32_t s_dst, int sw, int sh)
+{
+    pyr_down_plane(src + (size_t)blockIdx.y * s_src, dst + (size_t)blockIdx.y * s_dst, sw, sh);
+}
+
+__global__ __launch_bounds__(256) void k_pyr_down4_run(const uint8_t *src, uint32_t s_src, uint8_t *dst, uint32_t s_dst, int sw, int sh)
+{
+    pyr_down4_plane(src + (size_t)blockIdx.y * s_src, dst + (size_t)blockIdx.y * s_dst, sw, sh);
+}
+
+// bbme_chain_advance: the last slot of every level becomes slot 0, all levels in one launch (blockIdx.y = level).  Whole
+// plane strides (multiples of 64 bytes; the slack behind a plane is zero in every slot), 16 bytes per thread and step.
+struct ChainRoll { const uint4 *src[8]; uint4 *dst[8]; uint32_t n16[8]; };
+
+__global__ __launch_bounds__(256) void k_chain_roll(ChainRoll r)
+{
+    const uint4 *src = r.src[blockIdx.y];
+    uint4 *dst = r.dst[blockIdx.y];
+    const uint32_t n = r.n16[blockIdx.y];
+    for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) dst[i] = src[i];
 }
 
 // =======================================================================================

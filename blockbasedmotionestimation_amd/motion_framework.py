@@ -473,6 +473,98 @@ class MFBatch(MF):
         return [self.get_pair_flow(p) for p in range(self.batch)]
 
 
+class MFChain(MFBatch):
+    """The CONSECUTIVE pairs of a video behind one launch sequence (bbme_create_chain): `frames` = [f0, f1, ..., fP] are P + 1
+    frame slots and pair p = (f_p, f_p+1), so batch = len(frames) - 1 and every frame is uploaded, padded (or up-sampled) and
+    run through the pyramid ONCE -- an MFBatch fed the same pairs does all of that twice for every inner frame.  Each pair's
+    field is bit for bit what MF(f_p, f_p+1, ...) returns.  Frames are host arrays, or torch uint8 CUDA tensors with
+    frames_on_device=True; upsample=4: original frames, up-sampled x4 on the GPU.
+
+        chain = MFChain(video[0:P + 1], search, block)       # pairs 0 .. P-1
+        chain.estimate_async(); cells = [chain.get_pair_cells(p) for p in range(P)]
+        chain.advance(video[P + 1:2 * P + 1])                 # slot P -> slot 0 on the GPU, then P new frames: pairs P .. 2P-1
+
+    The get_pair_* getters, compensation_errors, estimate_async and the switches are MFBatch's.  The pair setters (set_pair,
+    set_frames, ...) raise BbmeError (ERR_UNSUPPORTED): a plane here belongs to two pairs and is set by slot."""
+
+    def __init__(self, frames, search_size, block_size, num_levels=None, device=0, frames_on_device=False, upsample=1):
+        self.upsample = _check_upsample(upsample)
+        if num_levels is None:
+            num_levels = len(block_size)
+        frames = list(frames)
+        if num_levels <= 0 or len(frames) < 2:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "num_levels must be > 0 and a chain needs at least two frames")
+        self._ctx = C.c_void_p()
+        self._lib = _capi.lib()
+        self.device = device
+        self.batch = len(frames) - 1
+        self.frames_on_device = bool(frames_on_device)
+        self._torch_frames = [None] * len(frames)
+        h, w = frames[0].shape
+        self.source_height, self.source_width = h, w
+        self.orig_height, self.orig_width = h * upsample, w * upsample
+        self.params = _capi.make_params(list(search_size)[:num_levels], list(block_size)[:num_levels])
+        _capi.check(self._lib.bbme_create_chain(C.byref(self.params), self.orig_width, self.orig_height, device, self.batch,
+                                                C.byref(self._ctx)))
+        pw, ph, px, py = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        _capi.check(self._lib.bbme_get_geometry(self._ctx, C.byref(pw), C.byref(ph), C.byref(px), C.byref(py)))
+        self.padded_width, self.padded_height = pw.value, ph.value
+        self.padding_x, self.padding_y = px.value, py.value
+        self.num_levels = num_levels
+        self.set_frame_run(0, frames)
+
+    @property
+    def slots(self):
+        n = C.c_int()
+        _capi.check(self._lib.bbme_chain_frames(self._ctx, C.byref(n)))
+        return n.value
+
+    def set_frame_run(self, first, frames, wait=True):
+        """Slots first .. first + len(frames) - 1 from `frames`: host arrays (wait=False only enqueues the uploads: the arrays,
+        pinned for a truly asynchronous copy, must stay untouched until the context's stream has passed them), or torch uint8
+        CUDA tensors on a context made with frames_on_device=True (ordered behind torch's current stream, kept referenced)."""
+        frames = list(frames)
+        n = len(frames)
+        if n < 1 or first < 0 or first + n > self.batch + 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "slots %d .. %d of a chain of %d" % (first, first + n - 1, self.batch + 1))
+        table = (C.c_void_p * n)()
+        if self.frames_on_device:
+            import torch
+            self._check_device_run(frames)
+            for i, t in enumerate(frames):
+                table[i] = t.data_ptr()
+            _capi.check(self._lib.bbme_wait_for_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(frames[0].device).cuda_stream)))
+            _capi.check(self._lib.bbme_set_chain_frames_device(self._ctx, first, n, table, frames[0].stride(0), self.upsample))
+            self._torch_frames[first:first + n] = frames
+            return
+        frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
+        for i, f in enumerate(frames):
+            if f.shape != (self.source_height, self.source_width):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "frames must keep the size the context was created for")
+            table[i] = f.ctypes.data
+        setter = self._lib.bbme_set_chain_frames_host if wait else self._lib.bbme_set_chain_frames_host_async
+        _capi.check(setter(self._ctx, first, n, table, self.source_width, self.upsample))
+        if not wait:
+            self._host_frames_in_flight = frames          # keeps converted copies alive until the next run replaces them
+
+    def _check_device_run(self, frames):
+        import torch
+        for t in frames:
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and tuple(t.shape) == (self.source_height, self.source_width)
+                    and t.stride(1) == 1 and t.stride(0) == frames[0].stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must be 2-D uint8 CUDA tensors of %d x %d with unit column "
+                                      "stride and a common row pitch" % (self.source_height, self.source_width))
+
+    def advance(self, new_frames, wait=True):
+        """The next round of the video: the last slot becomes slot 0 on the GPU (bbme_chain_advance: one copy launch, nothing
+        re-uploaded or re-computed), then `new_frames` go into slots 1 .. (all `batch` of them before the next estimate)."""
+        _capi.check(self._lib.bbme_chain_advance(self._ctx))
+        self._torch_frames = [self._torch_frames[-1]] + [None] * self.batch
+        new_frames = list(new_frames)
+        if new_frames:
+            self.set_frame_run(1, new_frames, wait=wait)
+
+
 def plan_padding(width, height, search_size, block_size):
     """padded_width, padded_height, padding_x, padding_y of MF::MF (motion_framework.cpp:14-54)."""
     p = _capi.make_params(search_size, block_size)

@@ -10,6 +10,9 @@ motion_framework.h:37-46; nothing is carried from pair to pair), so they shard w
   estimate.  (`csrc/seq_schedule.hpp` + `bbme_seq` is the same pipeline in C++ over RCCL, without torch.)
 * within a GPU -- `estimate_pairs_pipelined`: the pairs that share a GPU go into BATCHED contexts (`MFBatch`,
   bbme_create_batch: every kernel works on all pairs of a context at once), a few contexts side by side on their own streams.
+* a video -- frames f0, f1, ... whose pairs (f0, f1), (f1, f2), ... share every inner frame: `estimate_frames_pipelined` on
+  chain contexts (`MFChain`, bbme_create_chain), dealt in contiguous segments (`plan_frame_segments`, `shard_frames`), sets
+  every frame once where the pair form sets it twice.
 * `estimate_sequence` is the convenience form on top of any `compute` callable and any torch.distributed backend ("nccl" is
   RCCL over xGMI on ROCm; "gloo" in the CPU tests): it gathers the finished dense fields round by round and optionally writes
   the .flo files.  It is not the timed path.
@@ -205,6 +208,103 @@ def estimate_pairs_pipelined(pairs, search_size, block_size, device=None, in_fli
     finally:
         for mf in slots:
             mf.close()
+    return out
+
+
+def plan_frame_segments(n_pairs, slots, batch):
+    """The rounds, in issue order, of the `n_pairs` consecutive pairs of a video (pair p = frames p, p + 1) on `slots` chain
+    contexts (MFChain) of at most `batch` pairs: [(slot, first_pair, count, carry), ...].
+
+    The pairs are cut into `slots` CONTIGUOUS segments whose lengths differ by at most one (empty ones dropped), one per
+    context, and every context walks its segment `batch` pairs a round; rounds are issued round-robin over the contexts.
+    `carry` is true when the context's previous round ended at first_pair: frame first_pair is then already on the GPU (its
+    last slot, rolled to slot 0 by MFChain.advance) and the round sets `count` frames; a context's first round sets count + 1.
+    So the frames set in total are n_pairs + (number of segments) against 2 * n_pairs for independent pairs.
+    Dealing the PAIRS round-robin, as estimate_pairs_pipelined does, would hand a context frames 0..2, then 8..10: nothing to
+    carry.  Contiguous segments are what make the roll pay, and they are also how the frames of a video have to be dealt to
+    GPUs (shard_frames)."""
+    if n_pairs < 0 or slots < 1 or batch < 1:
+        raise ValueError("plan_frame_segments: n_pairs >= 0, slots >= 1 and batch >= 1")
+    base, extra = divmod(n_pairs, slots)
+    segments, start = [], 0
+    for s in range(slots):
+        n = base + (1 if s < extra else 0)
+        if n:
+            segments.append((start, start + n))
+        start += n
+    rounds, done = [], [seg[0] for seg in segments]
+    while any(done[s] < segments[s][1] for s in range(len(segments))):
+        for s, (lo, hi) in enumerate(segments):
+            if done[s] < hi:
+                count = min(batch, hi - done[s])
+                rounds.append((s, done[s], count, done[s] != lo))
+                done[s] += count
+    return rounds
+
+
+def shard_frames(n_frames, rank, world_size):
+    """(first_frame, last_frame) of the contiguous run of a video's frames rank `rank` takes -- it computes the pairs
+    first_frame .. last_frame - 1 -- or None when it takes none.  The video counterpart of shard_pairs: the n_frames - 1 pairs
+    in `world_size` contiguous segments (plan_frame_segments with one round per rank), so that ranks share only their boundary
+    frames; shard_pairs' round-robin would give every rank both frames of every pair it owns."""
+    n_pairs = max(n_frames - 1, 0)
+    base, extra = divmod(n_pairs, world_size)
+    first = rank * base + min(rank, extra)
+    count = base + (1 if rank < extra else 0)
+    return (first, first + count) if count else None
+
+
+def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_flight=4, batch=2, upsample=1):
+    """The len(frames) - 1 consecutive pairs of a video on ONE GPU: the unpadded (H, W, 2) float32 fields in order, the same
+    as estimate_pairs_pipelined(list(zip(frames, frames[1:])), ...), but on chain contexts (MFChain) that follow
+    plan_frame_segments: in_flight // batch contexts, each walking a contiguous segment of the video; a context's first round
+    sets count + 1 frames, every later round rolls its last frame to slot 0 and sets `count`.  A short last round is padded by
+    repeating its last frame (the padded pairs are not read).  upsample=4: original frames, fields of the up-sampled size."""
+    from .motion_framework import MFChain
+    frames = list(frames)
+    n_pairs = len(frames) - 1
+    if n_pairs < 1:
+        return []
+    if device is None:
+        device = local_device()
+    per = max(1, min(batch, in_flight, n_pairs))
+    n_slots = max(1, in_flight // per)
+    rounds = plan_frame_segments(n_pairs, n_slots, per)
+    n_ctx = 1 + max(r[0] for r in rounds)
+    chains = [None] * n_ctx
+    out = [None] * n_pairs
+    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
+
+    def collect(slot):
+        first, count = pending[slot]
+        pending[slot] = None
+        mf = chains[slot]
+        h, w = mf.orig_height, mf.orig_width
+        for p in range(count):
+            flow = mf.get_pair_flow(p)                     # waits for this context's stream only
+            out[first + p] = np.ascontiguousarray(flow[mf.padding_y:mf.padding_y + h, mf.padding_x:mf.padding_x + w])
+
+    try:
+        for slot, first, count, carry in rounds:
+            run = frames[first + 1:first + count + 1]
+            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
+            if not carry:
+                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device,
+                                       upsample=upsample)
+                if n_ctx * per > 1:
+                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
+            else:
+                collect(slot)
+                chains[slot].advance(run)
+            chains[slot].estimate_async()
+            pending[slot] = (first, count)
+        for slot in range(n_ctx):
+            if pending[slot]:
+                collect(slot)
+    finally:
+        for mf in chains:
+            if mf is not None:
+                mf.close()
     return out
 
 

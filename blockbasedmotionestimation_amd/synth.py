@@ -3,7 +3,7 @@
 frame1 = band-limited noise (uniform 0..255 -> three 5x5 box blurs -> rescaled to 0..255);
 frame2 = frame1 translated by a piecewise-constant integer motion field (tiles x tiles motions
 drawn from [-max_motion, max_motion]^2) plus +-2 uniform noise.  Pure numpy, deterministic
-for a given (width, height, seed).
+for a given (width, height, seed).  synth_video: a whole video by the same rule, frame after frame.
 """
 import numpy as np
 
@@ -45,6 +45,38 @@ def synth_pair(width, height, seed, max_motion=24, tiles=4, noise=2):
         frame2 = frame2 + rng2.integers(-noise, noise + 1, size=frame2.shape)
     frame2 = np.clip(frame2, 0, 255).astype(np.uint8)
     return frame1, frame2, motion
+
+
+def synth_video(width, height, n_frames, seed, max_motion=8, tiles=4, noise=2):
+    """n_frames uint8 (H, W) frames of a seeded video: one band-limited base texture (synth_pair's), frame 0 its window,
+    frame k + 1 the texture as frame k shows it moved by a fresh piecewise-constant integer field (tiles x tiles motions from
+    [-max_motion, max_motion]^2, synth_pair's rule) plus +-noise of its own.  Each tile's displacement accumulates from frame
+    to frame (the noise does not), so consecutive frames differ by at most max_motion per axis whatever n_frames is.
+    Deterministic for a given (width, height, n_frames, seed)."""
+    if n_frames < 1:
+        raise ValueError("n_frames must be >= 1")
+    rng = np.random.default_rng(seed)
+    margin = max_motion * max(n_frames - 1, 1)
+    base = rng.integers(0, 256, size=(height + 2 * margin, width + 2 * margin)).astype(np.float64)
+    for _ in range(3):
+        base = _box5(base)
+    base -= base.min()
+    base *= 255.0 / max(base.max(), 1e-9)
+    base = np.rint(base).astype(np.uint8)
+    ty = np.minimum(np.arange(height) * tiles // height, tiles - 1)
+    tx = np.minimum(np.arange(width) * tiles // width, tiles - 1)
+    ys, xs = np.mgrid[0:height, 0:width]
+    total = np.zeros((height, width, 2), np.int64)                   # (dx, dy) of every pixel's content since frame 0
+    frames = [base[margin:margin + height, margin:margin + width].copy()]
+    rng2 = np.random.default_rng(seed + 1)
+    for _ in range(1, n_frames):
+        mv = rng2.integers(-max_motion, max_motion + 1, size=(tiles, tiles, 2))
+        total = total + mv[ty[:, None], tx[None, :]]
+        frame = base[ys - total[..., 1] + margin, xs - total[..., 0] + margin].astype(np.int16)
+        if noise:
+            frame = frame + rng2.integers(-noise, noise + 1, size=frame.shape)
+        frames.append(np.clip(frame, 0, 255).astype(np.uint8))
+    return frames
 
 
 def warp_pair_from_flow(flow, seed=4711):

@@ -188,6 +188,37 @@ int bbme_set_frames_device_pair(bbme_ctx *ctx, int pair, const uint8_t *d_image1
 int bbme_set_frames_host_x4(bbme_ctx *ctx, int pair, const uint8_t *image1, const uint8_t *image2, int pitch);
 int bbme_set_frames_host_x4_async(bbme_ctx *ctx, int pair, const uint8_t *image1, const uint8_t *image2, int pitch);
 int bbme_set_frames_device_x4(bbme_ctx *ctx, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch);
+/* A CHAIN context: `pairs` (1..BBME_MAX_BATCH) CONSECUTIVE pairs of a video over pairs + 1 frame slots, pair p = (slot p,
+ * slot p + 1).  A video f0, f1, ... has the pairs (f0, f1), (f1, f2), ...: every inner frame is image 2 of one pair and image 1
+ * of the next, and a batched context uploads it, pads it and runs it through the pyrDown cascade twice.  Here every level holds
+ * its pairs + 1 planes one plane stride apart in ONE allocation, image1 = its start and image2 = one stride further, so a frame
+ * is set once and pair p reads slots p and p + 1 -- the kernels of bbme_estimate address pairs by that stride anyway and are
+ * untouched.  Validation, errors and everything not named below (streams, modes, speculation / relaxation switches, *_pair
+ * getters, bbme_subsampled_flow_device, bbme_compensation_error, the knobs) as bbme_create_batch with `pairs` pairs;
+ * bbme_batch_size reports `pairs`.  A chain of one pair counts as a single-pair context (bbme_level_planes_device returns slot 0
+ * and slot 1).  bbme_chain_frames: pairs + 1 for a chain context, 0 for any other.
+ * bbme_set_chain_frames_*: slots first .. first + count - 1 from `count` frames, frames[i] (a HOST array of pointers in every
+ * variant) pointing to host memory (_host, _host_async) or HBM (_device), rows `pitch` bytes apart.  scale 1: frames of the
+ * context's size; scale 4: original frames of a quarter of the size, up-sampled as bbme_set_frames_*_x4 do.  A slot's planes are
+ * byte for byte what bbme_set_frames_* / bbme_set_frames_*_x4 make of that frame.  The whole run is prepared by one launch per
+ * level (border or up-sampling, then one pyrDown per level, the frame being a grid dimension) whatever `count` is.  _host
+ * returns once the uploads have completed, _host_async only enqueues (buffer rules of bbme_set_frames_host_async), _device reads
+ * HBM on the ctx stream (bbme_wait_for_stream orders it behind a producer).
+ * bbme_chain_advance: enqueues, on the ctx stream and without a host wait, the copy of slot `pairs` (all levels, one launch) to
+ * slot 0 -- the roll from one round of a video to the next; nothing is re-computed or re-uploaded.  Afterwards slot 0 is as set
+ * as slot `pairs` was (set, in any sensible sequence) and slots 1 .. pairs are unset.  Results of the last estimate (flow,
+ * cells, grids) stay readable.
+ * State: while any slot is unset, every call that reads planes -- bbme_estimate, bbme_stage_search, bbme_stage_regularize, the
+ * motion-compensation calls -- returns BBME_ERR_STATE.  Every frame setter and the roll reset the SAD memo.  The pair setters
+ * (bbme_set_frames_*) return BBME_ERR_UNSUPPORTED on a chain context, the chain calls BBME_ERR_UNSUPPORTED on any other;
+ * BBME_ERR_INVALID for first / count outside the slots, a null table or entry, pitch < width / scale, scale not 1 or 4, or
+ * scale 4 on a context whose width or height is not a multiple of 4. */
+int bbme_create_chain(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out);
+int bbme_chain_frames(const bbme_ctx *ctx, int *frames);
+int bbme_set_chain_frames_host(bbme_ctx *ctx, int first, int count, const uint8_t *const *frames, int pitch, int scale);
+int bbme_set_chain_frames_host_async(bbme_ctx *ctx, int first, int count, const uint8_t *const *frames, int pitch, int scale);
+int bbme_set_chain_frames_device(bbme_ctx *ctx, int first, int count, const uint8_t *const *d_frames, int pitch, int scale);
+int bbme_chain_advance(bbme_ctx *ctx);
 /* Which of the reference's two block searches MF::calcLevelBM calls (motion_framework.cpp:235-236): the spiral full
  * search find_min_block_spiral (:296-422, the live one: ties go to the candidate visited first on the spiral; a
  * prediction outside the image gives a zero MV) or the raster full search find_min_block (:246-294, commented out in the
