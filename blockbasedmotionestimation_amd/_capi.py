@@ -99,6 +99,16 @@ SIGNATURES = {
     "bbme_compensation_error": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_motion_compensate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                               C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_set_direction": (C.c_int, [_ctx, C.c_int]),
+    "bbme_get_direction": (C.c_int, [_ctx, _P(C.c_int)]),
+    "bbme_estimate_bidirectional": (C.c_int, [_ctx]),
+    "bbme_backward_cells_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),
+    "bbme_get_backward_cells_host_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p]),
+    "bbme_cells_consistency_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                                C.c_void_p]),
+    "bbme_get_consistency_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_consistency_stats": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_cells_consistency_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bbme_pgm_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_flow_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),
     "bbme_get_flow_host_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p]),

@@ -141,7 +141,26 @@ struct bbme_ctx {
         return ((size_t)(160 - 40) * 1024 / per_cu) / 256 * 256;
     }
     double spec_min_absdiffs = 8e9;               // levels with less search work are not speculated; BBME_SPEC_MIN_GABS
-    hipGraphExec_t graph_exec = nullptr;
+    hipGraphExec_t graph_exec[2] = {nullptr, nullptr};   // the captured launch sequence of each direction, captured on first use
+    // bbme_set_direction: BBME_DIR_BACKWARD exchanges the two plane bases in the arguments of every kernel that reads planes for
+    // an estimate or a result (plane1 / plane2 below); setters, the chain roll and the plane accessors stay physical
+    int direction = 0;
+    // A context keeps ONE graph with the speculative search's forked branch: a second forked graph on the same context replays
+    // 0.9 ms slower at 4K whichever direction it is (2.4 ms against 1.43-1.47; 1.57 unforked; profiles/r08_bidirectional.txt).
+    // FORWARD's graph always speculates; BACKWARD's only while the context has no FORWARD graph, and capturing FORWARD drops a
+    // forked BACKWARD graph (captured again, unforked, on its next use).  BBME_SPECULATE_BOTH_GRAPHS=1: both forked (measurements).
+    bool graph_forked[2] = {false, false};
+    bool fork_both = false;
+    const uint8_t *plane1(const Level &L) const { return direction ? L.img2 : L.img1; }
+    const uint8_t *plane2(const Level &L) const { return direction ? L.img1 : L.img2; }
+    // bbme_estimate_bidirectional: level 0's final grid of the backward half, every pair (bwd_stride words apart), and whether
+    // it and the forward grid still describe the frames the context holds
+    mv_t *bwd_cells = nullptr;
+    uint32_t bwd_stride = 0;
+    bool fields_valid = false;
+    uint8_t *fb_mask = nullptr;                   // bbme_get_consistency_host: a packed CH x CW mask before its download
+    unsigned long long *fb_stats = nullptr;       // consistency statistics: 4 words per pair, then the partials of k_fb_consistency of
+                                                  // bbme_consistency_stats (every pair) and of bbme_cells_consistency_device (one pair)
     bool profiling = false;
     float t_total = 0, t_search = 0, t_reg = 0, t_expand = 0, t_search0 = 0;
     uint8_t *raw[2] = {nullptr, nullptr};         // bbme_set_frames_host: the unpadded frames in HBM (allocated on first use)
@@ -207,7 +226,9 @@ int check_level(const bbme_ctx *c, int level)
 
 void drop_graph(bbme_ctx *c)
 {
-    if (c->graph_exec) { (void)hipGraphExecDestroy(c->graph_exec); c->graph_exec = nullptr; }
+    for (hipGraphExec_t &g : c->graph_exec)
+        if (g) { (void)hipGraphExecDestroy(g); g = nullptr; }
+    c->graph_forked[0] = c->graph_forked[1] = false;
 }
 
 // The regulariser's waves leave at a round cap instead of spinning for ever (RegArgs::round_cap); a sweep that hit
@@ -312,7 +333,7 @@ int launch_search_fast(bbme_ctx *c, int level, int mode, hipStream_t stream, siz
 {
     Level &L = c->lv[level];
     FastSearchArgs a{};
-    a.image1 = L.img1; a.image2 = L.img2;
+    a.image1 = c->plane1(L); a.image2 = c->plane2(L);
     a.width = L.width; a.height = L.height;
     a.range = L.range; a.spiral = L.spiral;
     a.rank_of = L.rank_of; a.rank_pitch = L.rank_pitch;
@@ -389,7 +410,7 @@ int launch_search(bbme_ctx *c, int level, int mode = kSearchPlain, hipStream_t s
         rc = launch_search_fast(c, level, mode, stream, lds_floor);
     } else {
         SearchArgs a{};
-        a.image1 = L.img1; a.image2 = L.img2;
+        a.image1 = c->plane1(L); a.image2 = c->plane2(L);
         a.width = L.width; a.height = L.height;
         a.range = L.range; a.ncand = L.ncand; a.spiral = L.spiral;
         a.raster = c->raster_search ? 1 : 0;
@@ -498,7 +519,7 @@ int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false)
     else if (L.cur_block == 2 * b) a.old_shift = 1;
     else return bbme::fail(BBME_ERR_STATE, "level %d grid is at block size %d, cannot sweep at %d",
                            level, L.cur_block, b);
-    a.image1 = L.img1; a.image2 = L.img2;
+    a.image1 = c->plane1(L); a.image2 = c->plane2(L);
     a.width = L.width; a.height = L.height;
     a.rows = L.height / b; a.cols = L.width / b;
     a.old_grid = L.cur_grid;
@@ -742,6 +763,7 @@ static int create_context(const bbme_params *params, int width, int height, int 
     if (const char *e = getenv("BBME_SEARCH_SPLIT_BLOCKS")) { c->split_blocks = std::max(0, atoi(e)); c->split_forced = true; }
     if (const char *e = getenv("BBME_NO_GRAPH")) c->use_graph = atoi(e) == 0;
     if (const char *e = getenv("BBME_SPECULATE")) c->speculate = atoi(e) != 0;
+    if (const char *e = getenv("BBME_SPECULATE_BOTH_GRAPHS")) c->fork_both = atoi(e) != 0;
     {
         // a speculative search may keep at most this many of its (one-wave) workgroups on a CU: the rest of the CU's wave
         // slots, registers and LDS (40 KB) stay free for the regulariser kernels it runs beside
@@ -943,6 +965,9 @@ int bbme_destroy(bbme_ctx *c)
     (void)hipFree(c->sub);
     (void)hipFree(c->mc_plane);
     (void)hipFree(c->mc_stats);
+    (void)hipFree(c->bwd_cells);
+    (void)hipFree(c->fb_mask);
+    (void)hipFree(c->fb_stats);
     if (c->ev_sub) (void)hipEventDestroy(c->ev_sub);
     (void)hipFree(c->list[0]); (void)hipFree(c->list[1]);
     (void)hipFree(c->own);
@@ -1148,6 +1173,7 @@ static int enqueue_cascade(bbme_ctx *c, int pair)
     HIP_TRY(hipGetLastError());
     c->frames_mask |= 1ull << pair;
     c->memo_block = 0;                                  // new planes: what the SAD memo holds is no longer true
+    c->fields_valid = false;
     return BBME_OK;
 }
 
@@ -1256,6 +1282,7 @@ static int enqueue_chain_run(bbme_ctx *c, int first, int count, const FrameRun &
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < count; ++i) c->mark_slot(first + i);
     c->memo_block = 0;                                  // new planes: what the SAD memo holds is no longer true
+    c->fields_valid = false;
     return BBME_OK;
 }
 
@@ -1314,6 +1341,7 @@ int bbme_chain_advance(bbme_ctx *c)
     c->frames_mask = had_last ? 1ull : 0ull;         // slot 0 is as set as the slot it came from
     c->last_slot = false;
     c->memo_block = 0;
+    c->fields_valid = false;
     return BBME_OK;
 }
 
@@ -1340,6 +1368,7 @@ int bbme_set_level_planes_host(bbme_ctx *c, int level, const uint8_t *image1, co
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mark_pair0();
     c->memo_block = 0;
+    c->fields_valid = false;
     return BBME_OK;
 }
 
@@ -1355,31 +1384,102 @@ int bbme_get_level_planes_host(bbme_ctx *c, int level, uint8_t *image1, uint8_t 
     return BBME_OK;
 }
 
+// bbme_estimate in the context's current direction (one captured graph per direction)
+static int run_pyramid(bbme_ctx *c)
+{
+    if (c->profiling) { const int rc = profiled_pyramid(c); c->memo_block = 0; return rc; }
+    if (!c->use_graph) { const int rc = enqueue_pyramid(c, c->speculate); c->memo_block = 0; return rc; }
+    hipGraphExec_t &exec = c->graph_exec[c->direction];
+    if (!exec) {
+        // the launch sequence is fixed (no host decisions inside), so capture it once
+        hipGraph_t graph = nullptr;
+        bool fork = c->speculate;                      // (see bbme_ctx::graph_forked)
+        if (!c->fork_both) {
+            if (c->direction == BBME_DIR_BACKWARD && c->graph_exec[BBME_DIR_FORWARD]) fork = false;
+            if (c->direction == BBME_DIR_FORWARD && c->graph_exec[BBME_DIR_BACKWARD] && c->graph_forked[BBME_DIR_BACKWARD]) {
+                HIP_TRY(hipStreamSynchronize(c->stream));          // once per context: the graph may still be running
+                (void)hipGraphExecDestroy(c->graph_exec[BBME_DIR_BACKWARD]);
+                c->graph_exec[BBME_DIR_BACKWARD] = nullptr;
+                c->graph_forked[BBME_DIR_BACKWARD] = false;
+            }
+        }
+        c->graph_forked[c->direction] = fork;
+        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
+        int rc = enqueue_pyramid(c, fork);
+        hipError_t e = hipStreamEndCapture(c->stream, &graph);
+        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
+        if (e != hipSuccess) return bbme::fail(BBME_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
+        e = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0);
+        (void)hipGraphDestroy(graph);
+        if (e != hipSuccess) { exec = nullptr; return bbme::fail(BBME_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
+    } else {
+        // keep the host-side grid bookkeeping in step with what the graph replays
+        for (Level &L : c->lv) { L.cur_grid = L.final_grid(); L.cur_block = 2; }
+    }
+    HIP_TRY(hipGraphLaunch(exec, c->stream));
+    // after a pyramid the memo describes level 0 at its last memoised block size; a later stage call starts afresh
+    c->memo_block = 0;
+    return BBME_OK;
+}
+
 int bbme_estimate(bbme_ctx *c)
 {
     if (int rc = check_ctx(c)) return rc;
     if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "bbme_estimate: no frames set (every pair of a batch needs its frames)");
     HIP_TRY(hipSetDevice(c->device));
-    if (c->profiling) { const int rc = profiled_pyramid(c); c->memo_block = 0; return rc; }
-    if (!c->use_graph) { const int rc = enqueue_pyramid(c, c->speculate); c->memo_block = 0; return rc; }
-    if (!c->graph_exec) {
-        // the launch sequence is fixed (no host decisions inside), so capture it once
-        hipGraph_t graph = nullptr;
-        HIP_TRY(hipStreamBeginCapture(c->stream, hipStreamCaptureModeThreadLocal));
-        int rc = enqueue_pyramid(c, c->speculate);
-        hipError_t e = hipStreamEndCapture(c->stream, &graph);
-        if (rc) { if (graph) (void)hipGraphDestroy(graph); return rc; }
-        if (e != hipSuccess) return bbme::fail(BBME_ERR_HIP, "hipStreamEndCapture: %s", hipGetErrorString(e));
-        e = hipGraphInstantiate(&c->graph_exec, graph, nullptr, nullptr, 0);
-        (void)hipGraphDestroy(graph);
-        if (e != hipSuccess) { c->graph_exec = nullptr; return bbme::fail(BBME_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(e)); }
-    } else {
-        // keep the host-side grid bookkeeping in step with what the graph replays
-        for (Level &L : c->lv) { L.cur_grid = L.final_grid(); L.cur_block = 2; }
-    }
-    HIP_TRY(hipGraphLaunch(c->graph_exec, c->stream));
-    // after a pyramid the memo describes level 0 at its last memoised block size; a later stage call starts afresh
+    c->fields_valid = false;
+    return run_pyramid(c);
+}
+
+// The grids and the SAD memo describe one direction's problem: the other direction starts as after bbme_create.
+static void switch_direction(bbme_ctx *c, int dir)
+{
+    if (c->direction == dir) return;
+    c->direction = dir;
+    for (Level &L : c->lv) { L.cur_grid = nullptr; L.cur_block = 0; }
     c->memo_block = 0;
+    c->fields_valid = false;
+}
+
+int bbme_set_direction(bbme_ctx *c, int dir)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (dir != BBME_DIR_FORWARD && dir != BBME_DIR_BACKWARD) return bbme::fail(BBME_ERR_INVALID, "direction %d (0 or 1)", dir);
+    switch_direction(c, dir);
+    return BBME_OK;
+}
+
+int bbme_get_direction(const bbme_ctx *c, int *dir)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (!dir) return bbme::fail(BBME_ERR_INVALID, "null output");
+    *dir = c->direction;
+    return BBME_OK;
+}
+
+int bbme_estimate_bidirectional(bbme_ctx *c)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (!c->frames_set())
+        return bbme::fail(BBME_ERR_STATE, "bbme_estimate_bidirectional: no frames set (every pair of a batch needs its frames)");
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L0 = c->lv[0];
+    const uint32_t stride = L0.grid_stride(L0.final_grid());
+    if (!c->bwd_cells) {
+        HIP_TRY(hipMalloc(&c->bwd_cells, (size_t)stride * c->batch * sizeof(mv_t)));
+        c->bwd_stride = stride;
+    }
+    // backward pyramid, its final grid of every pair into the backward cells, forward pyramid: all on the ctx stream, in order
+    switch_direction(c, BBME_DIR_BACKWARD);
+    int rc = run_pyramid(c);
+    if (rc == BBME_OK) {
+        hipError_t e = hipMemcpyAsync(c->bwd_cells, L0.final_grid(), (size_t)stride * c->batch * sizeof(mv_t), hipMemcpyDeviceToDevice, c->stream);
+        if (e != hipSuccess) rc = bbme::fail(BBME_ERR_HIP, "copying the backward cells: %s", hipGetErrorString(e));
+    }
+    switch_direction(c, BBME_DIR_FORWARD);
+    if (rc) return rc;
+    if ((rc = run_pyramid(c))) return rc;
+    c->fields_valid = true;
     return BBME_OK;
 }
 
@@ -1597,8 +1697,8 @@ static int enqueue_mc(bbme_ctx *c, int pair0, int pairs, int level, int block, i
     McArgs a{};
     a.plane_stride = L.plane_stride;
     a.grid_stride = L.grid_stride(L.cur_grid);
-    a.img1 = L.img1 + (size_t)pair0 * a.plane_stride;
-    a.img2 = L.img2 + (size_t)pair0 * a.plane_stride;
+    a.img1 = c->plane1(L) + (size_t)pair0 * a.plane_stride;
+    a.img2 = c->plane2(L) + (size_t)pair0 * a.plane_stride;
     a.grid = L.cur_grid + (size_t)pair0 * a.grid_stride;
     a.out = d_out;
     a.partial = d_stats ? c->mc_stats + (size_t)4 * BBME_MAX_BATCH : nullptr;
@@ -1669,6 +1769,141 @@ int bbme_compensation_error(bbme_ctx *c, int level, int block, const int *window
     return check_converged(c);
 }
 
+// ---- forward-backward consistency of two cell grids (the rule of include/bbme.h; k_fb_consistency) -----------------------------
+
+int bbme_backward_cells_device_pair(bbme_ctx *c, int pair, const int16_t **d_cells)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!d_cells) return bbme::fail(BBME_ERR_INVALID, "null output");
+    if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "bbme_backward_cells_device_pair: no valid bidirectional estimate");
+    *d_cells = reinterpret_cast<const int16_t *>(c->bwd_cells + (size_t)pair * c->bwd_stride);
+    return BBME_OK;
+}
+
+int bbme_get_backward_cells_host_pair(bbme_ctx *c, int pair, int16_t *cells)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!cells) return bbme::fail(BBME_ERR_INVALID, "null output");
+    if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "bbme_get_backward_cells_host_pair: no valid bidirectional estimate");
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[0];
+    const size_t n = (size_t)(L.width / 2) * (L.height / 2);
+    HIP_TRY(hipMemcpyAsync(cells, c->bwd_cells + (size_t)pair * c->bwd_stride, n * sizeof(mv_t), hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+// tolerance and window {cx0, cy0, cw, ch} in cells of a cells_w x cells_h grid.  Touches no device.
+static int check_fb(int cells_w, int cells_h, int tol, const int *window, const char *what)
+{
+    if (tol < 0) return bbme::fail(BBME_ERR_INVALID, "%s: tolerance %d < 0", what, tol);
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > cells_w || (long long)window[1] + window[3] > cells_h))
+        return bbme::fail(BBME_ERR_INVALID, "%s: window (%d, %d, %d, %d) is not inside the %dx%d cells", what, window[0], window[1],
+                          window[2], window[3], cells_w, cells_h);
+    return BBME_OK;
+}
+
+static long long fb_groups(const Level &L0)
+{
+    return ((long long)(L0.width / 2 + 3) / 4 * (L0.height / 2) + 256 * kFbRunsPerLane - 1) / (256 * kFbRunsPerLane);
+}
+
+// the result words of every pair, then the partials of a launch over every pair, then those of a one-pair launch
+static int fb_scratch(bbme_ctx *c)
+{
+    if (!c->fb_stats)
+        HIP_TRY(hipMalloc(&c->fb_stats, (size_t)4 * sizeof(unsigned long long) * (BBME_MAX_BATCH + fb_groups(c->lv[0]) * (c->batch + 1))));
+    return BBME_OK;
+}
+
+// k_fb_consistency over `pairs` pairs: the mask (rows mask_pitch, pairs s_mask bytes apart) and / or, with d_stats, the statistics
+// (k_mc_reduce adds the partials at `partial` into d_stats[4 p ..])
+static int enqueue_fb(bbme_ctx *c, const mv_t *d_a, uint32_t s_a, const mv_t *d_b, uint32_t s_b, int pairs, int tol, const int *window,
+                      uint8_t *d_mask, int mask_pitch, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    FbArgs a{};
+    a.a = d_a; a.b = d_b; a.s_a = s_a; a.s_b = s_b;
+    a.mask = d_mask; a.mask_pitch = mask_pitch; a.s_mask = 0;
+    a.partial = d_stats ? partial : nullptr;
+    a.cw = L.width / 2; a.ch = L.height / 2; a.tol = tol;
+    a.wx0 = window ? window[0] : 0; a.wy0 = window ? window[1] : 0;
+    a.wx1 = window ? window[0] + window[2] : a.cw; a.wy1 = window ? window[1] + window[3] : a.ch;
+    a.runs_per_row = (a.cw + 3) / 4;
+    a.runs = (long long)a.runs_per_row * a.ch;
+    const long long groups = fb_groups(L);
+    hipLaunchKernelGGL(k_fb_consistency, dim3((unsigned)groups, (unsigned)pairs), dim3(256), 0, stream, a);
+    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)pairs), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+int bbme_cells_consistency_device(bbme_ctx *c, const int16_t *d_a, const int16_t *d_b, int tol, const int *window, uint8_t *d_mask,
+                                  int mask_pitch, unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_consistency_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_a || !d_b || (!d_mask && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_fb(L.width / 2, L.height / 2, tol, window, what)) return rc;
+    if (d_mask && mask_pitch < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: mask pitch %d < %d cells per row", what, mask_pitch, L.width / 2);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = fb_scratch(c)) return rc;
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (stream != c->stream) {
+        if (!c->ev_sub) HIP_TRY(hipEventCreateWithFlags(&c->ev_sub, hipEventDisableTiming));
+        HIP_TRY(hipEventRecord(c->ev_sub, c->stream));
+        HIP_TRY(hipStreamWaitEvent(stream, c->ev_sub, 0));
+    }
+    unsigned long long *partial = d_stats4 ? c->fb_stats + (size_t)4 * (BBME_MAX_BATCH + fb_groups(L) * c->batch) : nullptr;
+    return enqueue_fb(c, reinterpret_cast<const mv_t *>(d_a), 0, reinterpret_cast<const mv_t *>(d_b), 0, 1, tol, window, d_mask,
+                      mask_pitch, partial, d_stats4, stream);
+}
+
+// A = the forward cells, B = the backward cells of `which` = BBME_DIR_FORWARD, the other way round for BBME_DIR_BACKWARD
+static int check_fb_ctx(const bbme_ctx *c, int which, int tol, const int *window, const char *what)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (which != BBME_DIR_FORWARD && which != BBME_DIR_BACKWARD) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    return check_fb(c->lv[0].width / 2, c->lv[0].height / 2, tol, window, what);
+}
+
+int bbme_get_consistency_host(bbme_ctx *c, int pair, int which, int tol, uint8_t *mask)
+{
+    const char *what = "bbme_get_consistency_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_fb_ctx(c, which, tol, nullptr, what)) return rc;
+    if (!mask) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[0];
+    const int cw = L.width / 2, ch = L.height / 2;
+    if (!c->fb_mask) HIP_TRY(hipMalloc(&c->fb_mask, (size_t)cw * ch));
+    const uint32_t s_f = L.grid_stride(L.final_grid());
+    const mv_t *f = L.final_grid() + (size_t)pair * s_f, *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
+    if (int rc = enqueue_fb(c, which ? b : f, 0, which ? f : b, 0, 1, tol, nullptr, c->fb_mask, cw, nullptr, nullptr, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(mask, c->fb_mask, (size_t)cw * ch, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_consistency_stats(bbme_ctx *c, int which, int tol, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_consistency_stats";
+    if (int rc = check_fb_ctx(c, which, tol, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = fb_scratch(c)) return rc;
+    const Level &L = c->lv[0];
+    const uint32_t s_f = L.grid_stride(L.final_grid()), s_b = c->bwd_stride;
+    const mv_t *f = L.final_grid(), *b = c->bwd_cells;
+    if (int rc = enqueue_fb(c, which ? b : f, which ? s_b : s_f, which ? f : b, which ? s_f : s_b, c->batch, tol, window, nullptr, 0,
+                            c->fb_stats + (size_t)4 * BBME_MAX_BATCH, c->fb_stats, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(stats, c->fb_stats, (size_t)4 * sizeof(unsigned long long) * c->batch, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
 int bbme_stage_search(bbme_ctx *c, int level)
 {
     if (int rc = single_pair_only(c, "bbme_stage_search")) return rc;
@@ -1676,6 +1911,7 @@ int bbme_stage_search(bbme_ctx *c, int level)
     if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "no frames set");
     HIP_TRY(hipSetDevice(c->device));
     c->memo_block = 0;             // a stage sequence at a level starts here: the planes may have been refilled in place since
+    c->fields_valid = false;
     return launch_search(c, level);
 }
 
@@ -1685,6 +1921,7 @@ int bbme_stage_regularize(bbme_ctx *c, int level, int block, int mult)
     if (int rc = check_level(c, level)) return rc;
     if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "no frames set");
     HIP_TRY(hipSetDevice(c->device));
+    c->fields_valid = false;
     return launch_sweep(c, level, block, mult, true);       // with the solver's counters (bbme_sweep_stats)
 }
 
@@ -1728,6 +1965,7 @@ int bbme_stage_set_mvs(bbme_ctx *c, int level, int block, const int16_t *mvs)
     L.cur_grid = block == L.block ? L.small[0] : L.big[0];
     L.cur_block = block;
     c->memo_block = 0;             // as bbme_stage_search: the planes may have been refilled in place since
+    c->fields_valid = false;
     HIP_TRY(hipMemcpyAsync(L.cur_grid, host.data(), n * sizeof(mv_t), hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return BBME_OK;

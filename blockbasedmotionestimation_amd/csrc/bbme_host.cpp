@@ -597,6 +597,37 @@ int bbme_motion_compensate_host(const uint8_t *image1, const uint8_t *image2, in
     return BBME_OK;
 }
 
+int bbme_cells_consistency_host(const int16_t *a, const int16_t *b, int cells_w, int cells_h, int tol, const int *window,
+                                uint8_t *mask, unsigned long long *stats4)
+{
+    if (!a || !b || (!mask && !stats4)) return bbme::fail(BBME_ERR_INVALID, "bbme_cells_consistency_host: null pointer");
+    if (cells_w < 1 || cells_h < 1 || tol < 0)
+        return bbme::fail(BBME_ERR_INVALID, "bbme_cells_consistency_host: bad arguments (%dx%d cells, tolerance %d)", cells_w, cells_h, tol);
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > cells_w || (long long)window[1] + window[3] > cells_h))
+        return bbme::fail(BBME_ERR_INVALID, "bbme_cells_consistency_host: window not inside the %dx%d cells", cells_w, cells_h);
+    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
+    const int wx1 = window ? window[0] + window[2] : cells_w, wy1 = window ? window[1] + window[3] : cells_h;
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < cells_h; ++cy)
+        for (int cx = 0; cx < cells_w; ++cx) {
+            const size_t i = (size_t)cy * cells_w + cx;
+            const int dx = a[2 * i], dy = a[2 * i + 1];
+            const int tx = 2 * cx + dx, ty = 2 * cy + dy;
+            int cls = BBME_FB_OUTSIDE;
+            unsigned d = 0;
+            if (tx >= 0 && ty >= 0 && tx < 2 * cells_w && ty < 2 * cells_h) {
+                const size_t j = (size_t)(ty >> 1) * cells_w + (tx >> 1);
+                d = (unsigned)(abs(dx + b[2 * j]) + abs(dy + b[2 * j + 1]));
+                cls = d <= (unsigned)tol ? BBME_FB_CONSISTENT : BBME_FB_INCONSISTENT;
+            }
+            if (mask) mask[i] = (uint8_t)cls;
+            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) { ++s[cls]; s[3] += d; }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 int bbme_subsample_div4(const float *flow_padded, int padded_width, int padded_height,
                         int pad_x, int pad_y, float *out, int out_width, int out_height)
 {

@@ -2754,4 +2754,95 @@ __global__ __launch_bounds__(256) void k_mc_reduce(const unsigned long long *par
     if (threadIdx.x < 4) out[4 * blockIdx.x + threadIdx.x] = red[threadIdx.x][0];
 }
 
+// =======================================================================================
+// Forward-backward consistency of two 2x2-cell grids (the rule of include/bbme.h): cell (cx, cy) of A with (dx, dy) looks
+// at pixel (tx, ty) = (2 cx + dx, 2 cy + dy); outside the 2 CW x 2 CH plane it is class 2, otherwise (ex, ey) =
+// B[ty >> 1][tx >> 1], d = |dx + ex| + |dy + ey| and the class is d > tol.  A memory-bound gather: a lane takes a run of 4
+// consecutive cells of one row, so that A arrives as one 16-byte load and the mask leaves as one dword (the last run of a
+// row holds 2 cells when CW is not a multiple of 4; a caller's mask rows need not be dword-aligned); the four reads of B
+// are 4-byte gathers near the lane's own position (fields are piecewise smooth) and are left to L2.
+// Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells of class 0, 1, 2 and the sum of d over classes 0 and
+// 1.  A lane holds at most 4 kFbRunsPerLane = 16 cells, so a wave's 32-bit sum of d stays below 16 * 64 * 131 070 < 2^27;
+// every workgroup stores its four 64-bit sums as a partial in k_motion_compensate's layout and k_mc_reduce adds them up
+// (no atomics onto one line, see McArgs).  blockIdx.y = pair; mask and partial are each optional.
+// =======================================================================================
+struct FbArgs {
+    const mv_t *a, *b;                    // cw entries per row, ch rows
+    uint8_t *mask;                        // one class byte per cell, rows mask_pitch bytes apart; or null
+    unsigned long long *partial;          // per pair and workgroup {consistent, inconsistent, outside, discrepancy}; or null
+    uint32_t s_a, s_b;                    // words from pair to pair
+    size_t s_mask;                        // bytes from pair to pair
+    int cw, ch, tol, mask_pitch;
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kFbRunsPerLane = 4;
+
+__global__ __launch_bounds__(256) void k_fb_consistency(FbArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const mv_t *A = a.a + pair * a.s_a, *B = a.b + pair * a.s_b;
+    const int CW = a.cw, PW = 2 * a.cw, PH = 2 * a.ch;
+    uint32_t n0 = 0, n1 = 0, n2 = 0, dsum = 0;
+#pragma unroll
+    for (int k = 0; k < kFbRunsPerLane; ++k) {
+        const long long i = ((long long)blockIdx.x * kFbRunsPerLane + k) * 256 + threadIdx.x;
+        if (i >= a.runs) break;
+        const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
+        const int n = min(4, CW - x0);                        // cells of the run inside the row (4, or 2 at the row's end)
+        const mv_t *src = A + (size_t)cy * CW + x0;
+        uint32_t m[4] = {0, 0, 0, 0};
+        if (n == 4) {
+            const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(src);
+            m[0] = v.v[0]; m[1] = v.v[1]; m[2] = v.v[2]; m[3] = v.v[3];
+        } else {
+            m[0] = src[0];
+            if (n > 1) m[1] = src[1];
+            if (n > 2) m[2] = src[2];
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint32_t cls = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int dx = mv_x(m[j]), dy = mv_y(m[j]);
+            const int tx = 2 * (x0 + j) + dx, ty = 2 * cy + dy;
+            uint32_t c = 2u, d = 0;
+            if (tx >= 0 && ty >= 0 && tx < PW && ty < PH) {
+                const mv_t e = B[(size_t)(ty >> 1) * CW + (tx >> 1)];
+                d = (uint32_t)(abs(dx + mv_x(e)) + abs(dy + mv_y(e)));
+                c = d > (uint32_t)a.tol ? 1u : 0u;
+            }
+            cls |= c << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                n0 += c == 0u; n1 += c == 1u; n2 += c == 2u;
+                dsum += d;
+            }
+        }
+        if (a.mask) {
+            uint8_t *o = a.mask + pair * a.s_mask + (size_t)cy * a.mask_pitch + x0;
+            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = cls;
+            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(cls >> (8 * j));
+        }
+    }
+    if (!a.partial) return;
+    for (int o = 32; o > 0; o >>= 1) {
+        n0 += __shfl_xor(n0, o);
+        n1 += __shfl_xor(n1, o);
+        n2 += __shfl_xor(n2, o);
+        dsum += __shfl_xor(dsum, o);
+    }
+    __shared__ uint32_t part[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        uint32_t *w = part[threadIdx.x >> 6];
+        w[0] = n0; w[1] = n1; w[2] = n2; w[3] = dsum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        a.partial[4 * (pair * gridDim.x + blockIdx.x) + threadIdx.x] =
+            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
 }  // namespace bbme

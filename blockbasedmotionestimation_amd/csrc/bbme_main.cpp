@@ -1,7 +1,7 @@
 // bbme_main.cpp -- the reference's driver (main_class.cpp:6-85) as a real command line.
 //
 //   bbme_cli frame10.pgm frame11.pgm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
-//            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm]
+//            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -9,7 +9,10 @@
 // the GPU, write the field (the reference only ever colour-codes it; here Flow::WriteFlowFile is
 // actually called), EPE against ground truth (:78-82).  --mc writes the motion-compensated frame of draw_MVimage
 // (motion_framework.cpp:887-905) with 2x2 blocks at level 0, the reference's "MC_imageL1" (:213-216), over the unpadded frame
-// MF sees, and prints its PSNR against frame 1.
+// MF sees, and prints its PSNR against frame 1.  --backward writes the field from frame 2 to frame 1 (the context's direction
+// BACKWARD, include/bbme.h) through the same subsampling and writer as --out; --occlusion writes the forward-backward consistency
+// mask on frame 1 at tolerance 1, one byte per 2x2 cell whose top-left pixel lies in the unpadded frame MF sees (0 consistent,
+// 128 inconsistent, 255 target outside the plane), and prints the three counts.
 // Defaults are the reference's literals (:19-21): 4 levels, block 32, search 64.
 #include <chrono>
 #include <cstdio>
@@ -47,7 +50,7 @@ static bool read_pgm(const char *path, bbme::Image8 &img)
 
 int main(int argc, char **argv)
 {
-    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr;
+    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
     for (int i = 1; i < argc; ++i) {
@@ -57,6 +60,8 @@ int main(int argc, char **argv)
         else if (a == "--out") out = next();
         else if (a == "--color") color = next();
         else if (a == "--mc") mc = next();
+        else if (a == "--backward") backward = next();
+        else if (a == "--occlusion") occlusion = next();
         else if (a == "--levels") levels = atoi(next());
         else if (a == "--block") block = atoi(next());
         else if (a == "--search") search = atoi(next());
@@ -68,7 +73,8 @@ int main(int argc, char **argv)
     }
     if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS) {
         fprintf(stderr, "usage: bbme_cli frame1.pgm frame2.pgm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
-                        "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm]\n");
+                        "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
+                        "[--occlusion occ.pgm]\n");
         return 2;
     }
     try {
@@ -104,6 +110,22 @@ int main(int argc, char **argv)
             bbme::check(bbme_pgm_write(mc, img.cols - 2 * px, img.rows - 2 * py, img.cols, img.data.data() + (size_t)py * img.cols + px));
             const bbme::CompensationError e = motion_pair.compensationError(0, 2);
             printf("MC PSNR is %.9g dB over %llu pixels (%llu skipped)\n", e.psnr(), e.pixels, e.skipped);
+        }
+        if (backward) {
+            // the subsampled getter reads the context's current field: estimate in direction BACKWARD, then back to FORWARD
+            motion_pair.setDirection(true);
+            file.WriteFlowFile(motion_pair.calcMotionBlockMatchingSubsampled(scale), backward);
+            motion_pair.setDirection(false);
+        }
+        if (occlusion) {
+            motion_pair.estimateBidirectional();
+            bbme::Image8 mask = motion_pair.consistency(false, 1);
+            for (uint8_t &v : mask.data) v = v == BBME_FB_CONSISTENT ? 0 : v == BBME_FB_INCONSISTENT ? 128 : 255;
+            int win[4];
+            motion_pair.unpaddedCells(win);
+            bbme::check(bbme_pgm_write(occlusion, win[2], win[3], mask.cols, mask.data.data() + (size_t)win[1] * mask.cols + win[0]));
+            const bbme::ConsistencyStats st = motion_pair.consistencyStats(false, 1);
+            printf("consistent %llu inconsistent %llu outside %llu\n", st.consistent, st.inconsistent, st.outside);
         }
     } catch (const bbme::Error &e) {
         fprintf(stderr, "%s\n", e.what());

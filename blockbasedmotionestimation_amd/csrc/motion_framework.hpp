@@ -82,6 +82,11 @@ struct CompensationError {
     }
 };
 
+// statistics of a forward-backward consistency mask (bbme_consistency_stats)
+struct ConsistencyStats {
+    unsigned long long consistent = 0, inconsistent = 0, outside = 0, discrepancy = 0;
+};
+
 // cv::resize(img, img, cv::Size(), 4, 4, cv::INTER_LINEAR) of main_class.cpp:32-33
 inline Image8 resize_x4(const Image8 &src)
 {
@@ -181,6 +186,57 @@ public:
         bbme::check(bbme_compensation_error(ctx_, level, block, window, s));
         bbme::CompensationError e;
         e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3];
+        return e;
+    }
+    // Direction of the context (include/bbme.h): backward = every estimate and result as if image1 and image2 were exchanged.
+    void setDirection(bool backward) { bbme::check(bbme_set_direction(ctx_, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD)); }
+    bool direction() const
+    {
+        int d = 0;
+        bbme::check(bbme_get_direction(ctx_, &d));
+        return d == BBME_DIR_BACKWARD;
+    }
+    // Backward and forward estimate of the pair from the planes the context holds; no host wait.  Leaves the direction forward.
+    void estimateBidirectional() { bbme::check(bbme_estimate_bidirectional(ctx_)); }
+    // The 2x2-cell grid of the forward (bbme_get_cells_host) / backward field: (padded_height / 2) x (padded_width / 2) (dx, dy) pairs.
+    std::vector<int16_t> getCells()
+    {
+        std::vector<int16_t> cells((size_t)(padded_height / 2) * (padded_width / 2) * 2);
+        bbme::check(bbme_get_cells_host(ctx_, cells.data()));
+        return cells;
+    }
+    std::vector<int16_t> getBackwardCells()
+    {
+        std::vector<int16_t> cells((size_t)(padded_height / 2) * (padded_width / 2) * 2);
+        bbme::check(bbme_get_backward_cells_host_pair(ctx_, 0, cells.data()));
+        return cells;
+    }
+    // The consistency mask after estimateBidirectional(): one class byte (BBME_FB_*) per cell, on frame 1 (backward = false)
+    // or on frame 2 (backward = true).
+    bbme::Image8 consistency(bool backward = false, int tol = 1)
+    {
+        bbme::Image8 mask(padded_height / 2, padded_width / 2);
+        bbme::check(bbme_get_consistency_host(ctx_, 0, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD, tol, mask.data.data()));
+        return mask;
+    }
+    // The cells whose top-left pixel lies in the unpadded frame, {cx0, cy0, cw, ch}: the default window of consistencyStats.
+    void unpaddedCells(int window[4]) const
+    {
+        const int w = padded_width - 2 * padding_x, h = padded_height - 2 * padding_y;
+        window[0] = (padding_x + 1) / 2;
+        window[1] = (padding_y + 1) / 2;
+        window[2] = (padding_x + w + 1) / 2 - window[0];
+        window[3] = (padding_y + h + 1) / 2 - window[1];
+    }
+    // Its statistics over window {cx0, cy0, cw, ch} in cells; nullptr = unpaddedCells.
+    bbme::ConsistencyStats consistencyStats(bool backward = false, int tol = 1, const int *window = nullptr)
+    {
+        int unpadded[4];
+        unpaddedCells(unpadded);
+        unsigned long long s[4] = {0, 0, 0, 0};
+        bbme::check(bbme_consistency_stats(ctx_, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD, tol, window ? window : unpadded, s));
+        bbme::ConsistencyStats e;
+        e.consistent = s[0]; e.inconsistent = s[1]; e.outside = s[2]; e.discrepancy = s[3];
         return e;
     }
     bbme_ctx *context() { return ctx_; }

@@ -21,6 +21,10 @@ import numpy as np
 from . import _capi
 
 
+DIR_FORWARD, DIR_BACKWARD = 0, 1                           # bbme_set_direction, `which` of the consistency calls
+FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2      # classes of a consistency mask
+
+
 def _check_upsample(upsample):
     if upsample not in (1, 4):
         raise _capi.BbmeError(_capi.ERR_INVALID, "upsample must be 1 or 4, not %r" % (upsample,))
@@ -294,6 +298,106 @@ class MF:
         unpadded frame at level 0, the whole plane at other levels."""
         return self._compensation_stats(level, block, window)[0]
 
+    # -- direction, bidirectional estimate, forward-backward consistency (rules in include/bbme.h) ---------------------
+    def set_direction(self, backward):
+        """True: every estimate and result of this context as if image1 and image2 of every pair were exchanged (no plane is
+        touched; the level grids become "nothing yet" until the next estimate).  False: forward, the default."""
+        _capi.check(self._lib.bbme_set_direction(self._ctx, 1 if backward else 0))
+
+    @property
+    def direction(self):
+        """DIR_FORWARD (0) or DIR_BACKWARD (1)."""
+        d = C.c_int()
+        _capi.check(self._lib.bbme_get_direction(self._ctx, C.byref(d)))
+        return d.value
+
+    def estimate_bidirectional_async(self):
+        """Enqueue the backward estimate of every pair (its cells kept as the backward cells), then the forward estimate; no
+        host wait.  Afterwards every getter is as after estimate_async() in direction forward."""
+        _capi.check(self._lib.bbme_estimate_bidirectional(self._ctx))
+
+    @property
+    def cells_shape(self):
+        return (self.padded_height // 2, self.padded_width // 2)
+
+    def _get_backward_cells(self, pair, out, what):
+        shape = self.cells_shape + (2,)
+        if out is None:
+            out = np.empty(shape, np.int16)
+        elif out.shape != shape or out.dtype != np.int16 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous int16 array of shape %s" % (what, shape))
+        _capi.check(self._lib.bbme_get_backward_cells_host_pair(self._ctx, pair, out.ctypes.data))
+        return out
+
+    def get_backward_cells(self, out=None):
+        """The 2x2-cell grid of the backward field after estimate_bidirectional_async() -> (CH, CW, 2) int16."""
+        return self._get_backward_cells(0, out, "get_backward_cells")
+
+    def backward_cells_device_ptr(self, pair=0):
+        p = C.c_void_p()
+        _capi.check(self._lib.bbme_backward_cells_device_pair(self._ctx, pair, C.byref(p)))
+        return p.value
+
+    def consistency(self, which="forward", tol=1, pair=0, out=None):
+        """The forward-backward consistency mask of the context's two fields -> (CH, CW) uint8: 0 consistent, 1 inconsistent,
+        2 target outside the plane.  which="forward": the mask on frame 1 (forward vector followed, backward vector read
+        there); "backward": on frame 2."""
+        shape = self.cells_shape
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "consistency: out must be a C-contiguous uint8 array of shape %s" % (shape,))
+        _capi.check(self._lib.bbme_get_consistency_host(self._ctx, pair, _which(which), int(tol), out.ctypes.data))
+        return out
+
+    def default_cell_window(self):
+        """(cx0, cy0, cw, ch): the cells whose top-left pixel lies in the unpadded frame."""
+        x0, y0 = -(-self.padding_x // 2), -(-self.padding_y // 2)
+        x1, y1 = -(-(self.padding_x + self.orig_width) // 2), -(-(self.padding_y + self.orig_height) // 2)
+        return (x0, y0, x1 - x0, y1 - y0)
+
+    def _consistency_stats(self, which, tol, window):
+        if window is None:
+            window = self.default_cell_window()
+        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
+        pairs = getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_consistency_stats(self._ctx, _which(which), int(tol), win, s))
+        return [dict(zip(("consistent", "inconsistent", "outside", "discrepancy"), s[4 * p:4 * p + 4])) for p in range(pairs)]
+
+    def consistency_stats(self, which="forward", tol=1, window=None):
+        """dict(consistent, inconsistent, outside, discrepancy) of that mask over window (cx0, cy0, cw, ch) in cells:
+        cells per class and the sum of the discrepancy |dx + ex| + |dy + ey| over the cells of the first two.  Default
+        window: default_cell_window(); "all": every cell of the padded grid."""
+        return self._consistency_stats(which, tol, window)[0]
+
+    def cells_consistency_device(self, a, b, tol=1, mask=None, stats=None, window=None, hip_stream_handle=None):
+        """The consistency rule on any two cell grids in HBM: a, b contiguous int16 CUDA tensors (CH, CW, 2); mask a uint8
+        CUDA tensor (CH, CW) whose rows may be further apart than CW (a column slice of a wider tensor); stats an int64 or
+        uint64 CUDA tensor of 4 (consistent, inconsistent, outside, discrepancy) over window (cx0, cy0, cw, ch) in cells
+        (None = all cells).  On the given HIP stream (default: the context's), ordered behind the context's stream; no host
+        wait.  Needs no estimate."""
+        import torch
+        ch, cw = self.cells_shape
+        for t in (a, b):
+            if not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_consistency_device: grids must be contiguous int16 CUDA tensors "
+                                      "of shape (%d, %d, 2)" % (ch, cw))
+        if mask is not None and not (mask.is_cuda and mask.dtype == torch.uint8 and tuple(mask.shape) == (ch, cw)
+                                     and mask.stride(1) == 1 and mask.stride(0) >= cw):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_consistency_device: mask must be a uint8 CUDA tensor of shape "
+                                  "(%d, %d) with unit column stride" % (ch, cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_consistency_device: stats must be a contiguous int64 or uint64 CUDA "
+                                  "tensor of 4")
+        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+        _capi.check(self._lib.bbme_cells_consistency_device(
+            self._ctx, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), int(tol), win,
+            C.c_void_p(mask.data_ptr() if mask is not None else 0), mask.stride(0) if mask is not None else 0,
+            C.c_void_p(stats.data_ptr() if stats is not None else 0), C.c_void_p(hip_stream_handle or 0)))
+        return mask, stats
+
     def calcMotionBlockMatchingSubsampled(self, scale=None):
         """calcMotionBlockMatching followed by get_subsampled_flow: nothing dense crosses PCIe."""
         self.estimate_async()
@@ -463,6 +567,14 @@ class MFBatch(MF):
         """MF.draw_MVimage of one pair."""
         return self._get_motion_compensated(pair, level, block, fill, out, "get_pair_motion_compensated")
 
+    def get_pair_backward_cells(self, pair, out=None):
+        """MF.get_backward_cells of one pair."""
+        return self._get_backward_cells(pair, out, "get_pair_backward_cells")
+
+    def consistency_stats_all(self, which="forward", tol=1, window=None):
+        """MF.consistency_stats of every pair, in order, from one launch."""
+        return self._consistency_stats(which, tol, window)
+
     def compensation_errors(self, level=0, block=2, window=None):
         """MF.compensation_error of every pair, in order, from one launch."""
         return self._compensation_stats(level, block, window)
@@ -563,6 +675,30 @@ class MFChain(MFBatch):
         new_frames = list(new_frames)
         if new_frames:
             self.set_frame_run(1, new_frames, wait=wait)
+
+
+def _which(which):
+    if which in ("forward", 0, False):
+        return 0
+    if which in ("backward", 1, True):
+        return 1
+    raise _capi.BbmeError(_capi.ERR_INVALID, "which must be 'forward' or 'backward', not %r" % (which,))
+
+
+def cells_consistency(a, b, tol=1, window=None):
+    """The forward-backward consistency rule of include/bbme.h on the CPU (bbme_cells_consistency_host): a, b int16
+    (CH, CW, 2) cell grids -> (mask (CH, CW) uint8, dict(consistent, inconsistent, outside, discrepancy) over window
+    (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    a = np.ascontiguousarray(a, np.int16)
+    b = np.ascontiguousarray(b, np.int16)
+    if a.ndim != 3 or a.shape[2] != 2 or a.shape != b.shape:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "cells_consistency: two int16 grids of one shape (CH, CW, 2)")
+    ch, cw = a.shape[:2]
+    mask = np.empty((ch, cw), np.uint8)
+    s = (C.c_ulonglong * 4)()
+    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+    _capi.check(_capi.lib().bbme_cells_consistency_host(a.ctypes.data, b.ctypes.data, cw, ch, int(tol), win, mask.ctypes.data, s))
+    return mask, dict(zip(("consistent", "inconsistent", "outside", "discrepancy"), list(s)))
 
 
 def plan_padding(width, height, search_size, block_size):

@@ -308,6 +308,65 @@ def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_f
     return out
 
 
+def estimate_frames_bidirectional(frames, search_size, block_size, device=None, in_flight=4, batch=2, upsample=1, tol=1):
+    """Both fields of the len(frames) - 1 consecutive pairs of a video on ONE GPU, and their forward-backward consistency, on
+    the chain plan of estimate_frames_pipelined (same contexts, rounds and padding of a short round): every frame is still
+    set once, and MFChain.estimate_bidirectional_async estimates pair p = (f_p, f_p+1) and (f_p+1, f_p) from the same planes.
+    Returns one tuple per pair: (forward (H, W, 2) float32, backward (H, W, 2) float32 -- the unpadded fields, the backward
+    one expanded on the host from its cells --, forward mask, backward mask -- uint8 consistency classes at tolerance `tol`
+    over the cells whose top-left pixel lies in the unpadded frame, MF.default_cell_window)."""
+    from .motion_framework import MFChain
+    frames = list(frames)
+    n_pairs = len(frames) - 1
+    if n_pairs < 1:
+        return []
+    if device is None:
+        device = local_device()
+    per = max(1, min(batch, in_flight, n_pairs))
+    n_slots = max(1, in_flight // per)
+    rounds = plan_frame_segments(n_pairs, n_slots, per)
+    n_ctx = 1 + max(r[0] for r in rounds)
+    chains = [None] * n_ctx
+    out = [None] * n_pairs
+    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
+
+    def collect(slot):
+        first, count = pending[slot]
+        pending[slot] = None
+        mf = chains[slot]
+        h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
+        cx0, cy0, cw, ch = mf.default_cell_window()
+        for p in range(count):
+            fwd = mf.get_pair_flow(p)                      # waits for this context's stream only
+            bwd = expand_cells_host(mf.get_pair_backward_cells(p).view(np.int32)[..., 0])
+            masks = [mf.consistency(which, tol, pair=p)[cy0:cy0 + ch, cx0:cx0 + cw].copy() for which in ("forward", "backward")]
+            out[first + p] = (np.ascontiguousarray(fwd[py:py + h, px:px + w]), np.ascontiguousarray(bwd[py:py + h, px:px + w]),
+                              masks[0], masks[1])
+
+    try:
+        for slot, first, count, carry in rounds:
+            run = frames[first + 1:first + count + 1]
+            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
+            if not carry:
+                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device,
+                                       upsample=upsample)
+                if n_ctx * per > 1:
+                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
+            else:
+                collect(slot)
+                chains[slot].advance(run)
+            chains[slot].estimate_bidirectional_async()
+            pending[slot] = (first, count)
+        for slot in range(n_ctx):
+            if pending[slot]:
+                collect(slot)
+    finally:
+        for mf in chains:
+            if mf is not None:
+                mf.close()
+    return out
+
+
 def _gpu_compute(search_size, block_size, device):
     from .motion_framework import MF
 

@@ -342,6 +342,75 @@ int bbme_motion_compensate_host(const uint8_t *image1, const uint8_t *image2, in
                                 int grid_block, int block, int fill, const int *window, uint8_t *out,
                                 unsigned long long *stats4);
 
+/* ---- direction, bidirectional estimate and forward-backward consistency ---------------------------------------------- */
+
+/* DIRECTION.  A context has a direction, BBME_DIR_FORWARD (default) or BBME_DIR_BACKWARD.  In direction BACKWARD every call that
+ * reads planes or produces or reads results -- bbme_estimate, the bbme_stage_* calls, the flow / cells / subsampled getters,
+ * bbme_calculate_mse_device, the three motion-compensation calls -- behaves bit for bit as it would on a context of the same kind
+ * in which every pair had been set with image 1 and image 2 exchanged.  (The reference's MF is one-way, MF::MF(image1, image2,
+ * ...): the backward field is the reference's field of the exchanged pair.)  Setters and the plane accessors (bbme_set_frames_*,
+ * bbme_set_chain_frames_*, bbme_chain_advance, bbme_level_planes_device, bbme_set/get_level_planes_host) keep their physical
+ * meaning in both directions: "image1" is what was set as image 1.  Changing the direction moves no byte of any plane -- the
+ * kernels get the two plane bases exchanged; on a chain context pair p then reads slot p + 1 as its image 1 and slot p as its
+ * image 2.  It does make every level's grid "nothing yet" (as after bbme_create: the cells / subsampled getters and the
+ * motion-compensation calls return BBME_ERR_STATE until the next estimate or stage call) and restarts the SAD memo, because the
+ * grids and the memo describe the other problem; setting the direction it already has changes nothing.  Each direction keeps a
+ * captured launch graph of its own, so alternating directions does not capture again.  Of the two, one carries the forked branch
+ * of the speculative search (bbme_set_speculation): FORWARD's, or BACKWARD's while the context has no FORWARD graph -- the first
+ * FORWARD estimate after BACKWARD-only use waits once for the stream and has BACKWARD captured again without the branch.  Scheduling
+ * only; every field is the same.  (A second forked graph on one context replays 0.9 ms slower at 4K than the first, whichever
+ * direction it is; BBME_SPECULATE_BOTH_GRAPHS=1 forks both.)  BBME_ERR_INVALID for another value. */
+enum { BBME_DIR_FORWARD = 0, BBME_DIR_BACKWARD = 1 };
+int bbme_set_direction(bbme_ctx *ctx, int dir);
+int bbme_get_direction(const bbme_ctx *ctx, int *dir);
+/* BIDIRECTIONAL ESTIMATE.  Enqueues, on the ctx stream and without a host wait, the backward estimate of every pair, a copy of
+ * its final 2x2-cell grid into a buffer of the context's own (the BACKWARD CELLS: shape and type of bbme_cells_device_pair, one
+ * grid per pair), then the forward estimate (on first use the two graphs are captured, see above: a context without a FORWARD
+ * graph waits once for the stream in that call).  Leaves the direction FORWARD whatever it was.  Afterwards every existing getter
+ * returns exactly what it returns after bbme_estimate in direction FORWARD, and the backward cells are readable
+ * (bbme_expand_cells_device makes a dense field of them).  No frame is uploaded, padded, up-sampled or pyramided again for the
+ * backward half, on a chain context either.  BBME_ERR_STATE without frames / with an unset chain slot, as bbme_estimate.
+ * The pair of fields is VALID from this call until the next call that can change either of them: any frame setter,
+ * bbme_chain_advance, bbme_set_level_planes_host, bbme_estimate, bbme_stage_search / _regularize / _set_mvs, or
+ * bbme_set_direction to another direction.  While it is not valid, bbme_backward_cells_device_pair,
+ * bbme_get_backward_cells_host_pair, bbme_get_consistency_host and bbme_consistency_stats return BBME_ERR_STATE.  The sticky
+ * "sweep did not converge" flag (bbme_synchronize) covers both halves. */
+int bbme_estimate_bidirectional(bbme_ctx *ctx);
+int bbme_backward_cells_device_pair(bbme_ctx *ctx, int pair, const int16_t **d_cells);
+/* Synchronises, then downloads; reports non-convergence like bbme_get_cells_host. */
+int bbme_get_backward_cells_host_pair(bbme_ctx *ctx, int pair, int16_t *cells);
+/* CONSISTENCY RULE (this project's own; the reference has no such check).  Inputs: two cell grids A and B of CH x CW int16
+ * (dx, dy) pairs (CH = H0 / 2, CW = W0 / 2 of the padded level-0 plane), a tolerance tol >= 0.  For cell (cx, cy) with
+ * (dx, dy) = A[cy][cx]:
+ *   target pixel (tx, ty) = (2 cx + dx, 2 cy + dy), in 32-bit integers;
+ *   tx < 0, ty < 0, tx >= 2 CW or ty >= 2 CH: class BBME_FB_OUTSIDE, discrepancy not defined;
+ *   otherwise (ex, ey) = B[ty >> 1][tx >> 1], d = |dx + ex| + |dy + ey| (up to 131 070), and the class is BBME_FB_CONSISTENT
+ *   if d <= tol, else BBME_FB_INCONSISTENT.
+ * The mask is one byte per cell holding the class.  The statistics over a window {cx0, cy0, cw, ch} IN CELLS (NULL = all
+ * cells) are four exact 64-bit integers: cells of class 0, of class 1, of class 2, and the sum of d over the window's cells of
+ * class 0 or 1.  which = BBME_DIR_FORWARD: A = forward cells, B = backward cells (the mask lives on frame 1: where it is 1,
+ * frame 1's content has no agreeing partner in frame 2); which = BBME_DIR_BACKWARD the other way round (mask on frame 2).
+ * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, tol < 0, a window
+ * with a negative origin, an empty side or reaching outside CW x CH, mask_pitch < CW; BBME_ERR_STATE for the context-level calls
+ * without a valid pair of fields.  None of these calls changes context state (grids, memo, flow, cells, backward cells); their
+ * scratch buffers are independent of the other getters'.  All work on single, batched and chain contexts.
+ * bbme_cells_consistency_device: the rule on ANY two cell grids in HBM of this context's cell geometry (bbme_cells_device_pair
+ * and bbme_backward_cells_device_pair, or grids gathered from another GPU); d_mask (rows mask_pitch bytes apart) and d_stats4
+ * each may be null, not both; on hip_stream (NULL = the ctx stream; another stream is first ordered behind it, as
+ * bbme_motion_compensate_device); no host wait; needs no valid pair of fields.  Launches with d_stats4 share one scratch buffer
+ * per context: the caller orders those it issues on different streams.
+ * bbme_get_consistency_host: the context's own two fields of `pair`; synchronises; packed CH x CW bytes.
+ * bbme_consistency_stats: EVERY pair in one launch, stats[4 p + k]; synchronises (like bbme_compensation_error).
+ * bbme_cells_consistency_host: the same rule on the CPU, no GPU, on packed cells_h x cells_w grids; mask (packed) and stats4
+ * each may be NULL, not both. */
+enum { BBME_FB_CONSISTENT = 0, BBME_FB_INCONSISTENT = 1, BBME_FB_OUTSIDE = 2 };
+int bbme_cells_consistency_device(bbme_ctx *ctx, const int16_t *d_a, const int16_t *d_b, int tol, const int *window,
+                                  uint8_t *d_mask, int mask_pitch, unsigned long long *d_stats4, void *hip_stream);
+int bbme_get_consistency_host(bbme_ctx *ctx, int pair, int which, int tol, uint8_t *mask);
+int bbme_consistency_stats(bbme_ctx *ctx, int which, int tol, const int *window, unsigned long long *stats);
+int bbme_cells_consistency_host(const int16_t *a, const int16_t *b, int cells_w, int cells_h, int tol, const int *window,
+                                uint8_t *mask, unsigned long long *stats4);
+
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
 /* copyMVs (:828-843) + calcLevelBM (:226-244) of one level.  Leaves that level's MV
