@@ -9,7 +9,8 @@ C oracle's structure, so that agreement between the two means something:
   * energies are exact Python integers instead of float32 (:607);
   * MVs live in compact per-block integer grids instead of a dense float field, and
     divide_blocks / copyMVs / copy_to_all_pixels are index arithmetic.
-PARITY UNPINNED with respect to the reference binary (see oracle/bbme_oracle.h).
+It agrees with the C oracle, which is pinned to the reference's compiled core (see oracle/bbme_oracle.h and
+tests/test_reference_core_cpu.py).
 """
 import numpy as np
 

@@ -6,8 +6,8 @@
  * Arithmetic types follow the reference: motion vectors and energies are
  * float32, SADs are int, the padding search runs in double.
  *
- * Hot path (search / regulariser / driver): PARITY UNPINNED -- the reference
- * holds no golden vectors for it and cannot be built here (needs OpenCV).
+ * Hot path (search / regulariser / driver), raster search and padding plan: pinned, bit for bit and stage by stage,
+ * against the reference's own compiled core (oracle/_ref/mf_ref) by tests/test_reference_core_cpu.py.
  * Build with -ffp-contract=off so float expressions round as written.
  */
 #include "bbme_oracle.h"

@@ -11,18 +11,20 @@
  *   .flo codec + EPE : pinned.  Checked against the reference's own vendored
  *       Middlebury flowIO.cpp (compiled into oracle/_ref/ by oracle/Makefile)
  *       and against the 8 ground-truth flow10.flo files the reference ships.
- *   search / regulariser / level driver : PARITY UNPINNED.  The reference has
- *       no tests, no golden vectors and no input frames for this path, and its
- *       core (motion_framework.cpp) needs OpenCV 2.4.9/3.0.0, which is absent
- *       here, so it cannot be built.  These functions follow the reference
- *       source line by line (citations on every function) and are
- *       cross-checked by an independent numpy restatement (oracle/bbme_numpy.py).
- *   raster search find_min_block (:246-294, dead code in the reference; raster_search = 1) : PARITY UNPINNED, same
- *       grounds; additionally checked against a direct numpy statement of its rules (tests/test_oracle_cpu.py).
+ *   search / regulariser / level driver / padding plan / draw_MVimage / MotionToColor / CalculateMSE : pinned.
+ *       oracle/Makefile compiles the reference's own core (motion_framework.cpp, parallel.h, rw_flow.cpp) in
+ *       place, against the stand-in headers of oracle/cvshim/ (OpenCV itself is absent; none of this arithmetic
+ *       is inside it), into oracle/_ref/mf_ref.  tests/test_reference_core_cpu.py compares every stage and the
+ *       dense field bit for bit.  These functions follow the reference source line by line (citations on every
+ *       function) and are also cross-checked by an independent numpy restatement (oracle/bbme_numpy.py).
+ *   raster search find_min_block (:246-294, dead code in the reference; raster_search = 1) : pinned the same way
+ *       (mf_ref stages --raster); additionally checked against a direct numpy statement of its rules
+ *       (tests/test_oracle_cpu.py).
  *   jacobi_regularizer = 1 : NOT a reference function -- the written-down definition of the product's opt-in fast
  *       mode, so that that mode can be tested bit for bit and its distance from the reference's field measured.
- *   padding / pyrDown / 4x bilinear resize : PARITY UNPINNED.  Restated from
- *       OpenCV's published 8-bit algorithms; outside the hot path (host prep).
+ *   pyrDown / 4x bilinear resize : PARITY UNPINNED.  Restated from OpenCV's published 8-bit algorithms; they are
+ *       OpenCV's, the reference tree does not contain them and a stand-in cannot pin them; outside the hot path
+ *       (host prep).  Zero padding (copyMakeBorder with a constant) is plain copying.
  *
  * All file:line citations are relative to the reference repository root.
  */

@@ -2,18 +2,23 @@
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and the
 cpu_baseline leg of bench.py, never by the product package.  Parity status of
-each piece is stated in oracle/bbme_oracle.h (hot path: PARITY UNPINNED; .flo
-codec and EPE: pinned by the reference's vendored flowIO.cpp and GT files).
+each piece is stated in oracle/bbme_oracle.h (hot path, raster search, padding
+plan, draw_MVimage, MotionToColor and CalculateMSE: pinned against the reference's
+own compiled core, oracle/_ref/mf_ref, by tests/test_reference_core_cpu.py; .flo
+codec: pinned by the reference's vendored flowIO.cpp and GT files; pyrDown and the
+x4 resize are OpenCV's and stay unpinned).
 """
 import ctypes as C
 import os
 import subprocess
+import tempfile
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB_PATH = os.path.join(_HERE, "_build", "libbbme_oracle.so")
 FLO_REF = os.path.join(_HERE, "_ref", "flo_ref")
+MF_REF = os.path.join(_HERE, "_ref", "mf_ref")     # the reference's own core behind oracle/ref_mf_driver.cpp
 
 
 class _Level(C.Structure):
@@ -33,8 +38,10 @@ class _MF(C.Structure):
 
 
 def build(force=False):
-    """Compile the oracle (and oracle/_ref when /root/reference is present)."""
-    if force or not os.path.exists(_LIB_PATH) or \
+    """Compile the oracle (and oracle/_ref when the reference directory is present)."""
+    # a missing reference binary: let make decide (its `ref` target builds them only where the reference directory exists)
+    ref_missing = not (os.path.exists(MF_REF) and os.path.exists(FLO_REF))
+    if force or ref_missing or not os.path.exists(_LIB_PATH) or \
             os.path.getmtime(_LIB_PATH) < os.path.getmtime(os.path.join(_HERE, "bbme_oracle.c")):
         subprocess.check_call(["make", "-s", "-C", _HERE, "all"])
     return _LIB_PATH
@@ -297,3 +304,133 @@ def subsample_div4(flow_padded, pad_x, pad_y, out_width, out_height):
     lib().orc_subsample_div4(f.ctypes.data, f.shape[1], f.shape[0], pad_x, pad_y,
                              out.ctypes.data, out_width, out_height)
     return out
+
+
+# ---- the reference's own compiled core (oracle/_ref/mf_ref, see oracle/ref_mf_driver.cpp): arrays in, arrays out ----
+class RefAbort(RuntimeError):
+    """mf_ref ended otherwise than with status 0: .status (negative: signal) and .stderr (the stand-in's bounds message)."""
+
+    def __init__(self, status, stderr):
+        RuntimeError.__init__(self, "mf_ref: status %d: %s" % (status, stderr.strip()))
+        self.status, self.stderr = status, stderr
+
+
+def have_mf_ref():
+    return os.path.exists(MF_REF)
+
+
+def _mf_ref(args, parts):
+    """Runs mf_ref <args> in out with the concatenated bytes of parts as the input file; returns the output file's bytes."""
+    with tempfile.TemporaryDirectory(prefix="bbme_mf_ref_") as tmp:
+        src, dst = os.path.join(tmp, "in.bin"), os.path.join(tmp, "out.bin")
+        with open(src, "wb") as f:
+            for p in parts:
+                f.write(p if isinstance(p, bytes) else np.ascontiguousarray(p).tobytes())
+        r = subprocess.run([MF_REF] + list(args) + [src, dst], stdin=subprocess.DEVNULL, stdout=subprocess.DEVNULL,
+                           stderr=subprocess.PIPE)
+        if r.returncode != 0:
+            raise RefAbort(r.returncode, r.stderr.decode(errors="replace"))
+        with open(dst, "rb") as f:
+            return f.read()
+
+
+def _i32(*v):
+    return np.array(v, np.int32).tobytes()
+
+
+def _u8(a):
+    return np.ascontiguousarray(a, np.uint8)
+
+
+def _grid(a):
+    return np.ascontiguousarray(a, np.float32)
+
+
+def stage_list(block):
+    """(name, level, block size) of every grid the schedule :115-206 produces, in order."""
+    out = []
+    for lvl in range(len(block) - 1, -1, -1):
+        out.append(("search", lvl, block[lvl]))
+        b = block[lvl]
+        while b > 1:
+            out += [("sweep1", lvl, b), ("sweep2", lvl, b)]
+            b >>= 1
+    return out
+
+
+def ref_plan(block, w0, w1, h0, h1):
+    """MF::MF's padding plan on every size of the ranges: {(w, h): (status, padded_w, padded_h, pad_x, pad_y)}; status 1 is
+    the reference's own exit ("Could not find any multiples ...", :21-26)."""
+    with tempfile.TemporaryDirectory(prefix="bbme_mf_ref_") as tmp:
+        dst = os.path.join(tmp, "plan.txt")
+        subprocess.check_call([MF_REF, "plan", dst, str(len(block))] + [str(b) for b in block] +
+                              [str(v) for v in (w0, w1, h0, h1)], stdin=subprocess.DEVNULL, stdout=subprocess.DEVNULL)
+        rows = [[int(t) for t in line.split()] for line in open(dst)]
+    return {(r[0], r[1]): tuple(r[2:]) for r in rows}
+
+
+def ref_stages(f1, f2, search, block, planes=None, mode=None):
+    """The reference's schedule call by call (mode None / "raster" / "parallel", see ref_mf_driver.cpp).  Returns a dict:
+    geometry (padded_w, padded_h, pad_x, pad_y), planes [(plane1, plane2)], stages [(name, level, block, float32 grid)],
+    flow (dense, of the staged run), whole (dense, calcMotionBlockMatching() on an untouched MF; None unless mode is None)."""
+    f1, f2 = _u8(f1), _u8(f2)
+    L = len(block)
+    parts = [_i32(L, f1.shape[1], f1.shape[0], 1 if planes else 0), _i32(*search), _i32(*block), f1, f2]
+    if planes:
+        for lvl in range(L):
+            parts += [_u8(planes[0][lvl]), _u8(planes[1][lvl])]
+    raw = _mf_ref(["stages"] + (["--" + mode] if mode else []), parts)
+    pw, ph, px, py, has_whole = (int(v) for v in np.frombuffer(raw[:20], np.int32))
+    off = [20]
+
+    def take(shape, dtype):
+        n = int(np.prod(shape)) * np.dtype(dtype).itemsize
+        a = np.frombuffer(raw[off[0]:off[0] + n], dtype).reshape(shape)
+        off[0] += n
+        return a
+    out = {"geometry": (pw, ph, px, py), "planes": [], "stages": []}
+    for lvl in range(L):
+        out["planes"].append((take((ph >> lvl, pw >> lvl), np.uint8), take((ph >> lvl, pw >> lvl), np.uint8)))
+    for name, lvl, b in stage_list(block):
+        out["stages"].append((name, lvl, b, take(((ph >> lvl) // b, (pw >> lvl) // b, 2), np.float32)))
+    out["flow"] = take((ph, pw, 2), np.float32)
+    out["whole"] = take((ph, pw, 2), np.float32) if has_whole else None
+    assert off[0] == len(raw), "mf_ref stages: unexpected output size"
+    return out
+
+
+def ref_sweeps(plane1, plane2, search, B, b, field, mults=(1, 2)):
+    """regularize_MVs at block size b from an injected grid, one sweep per multiplier: the float32 grid after each."""
+    p1, p2 = _u8(plane1), _u8(plane2)
+    h, w = p1.shape
+    raw = _mf_ref(["sweeps"], [_i32(w, h, B, b, search, len(mults)), _i32(*mults), p1, p2, _grid(field)])
+    return list(np.frombuffer(raw, np.float32).reshape(len(mults), h // b, w // b, 2))
+
+
+def ref_search_from_coarse(planes1, planes2, search, block, field2):
+    """copyMVs + calcLevelBM of level 0 from a level-1 grid given at 2 x 2 cells: level 0's float32 grid at block[0]."""
+    h, w = planes1[0].shape
+    raw = _mf_ref(["search-from-coarse"], [_i32(w, h), _i32(*search), _i32(*block), _u8(planes1[0]), _u8(planes2[0]),
+                                           _u8(planes1[1]), _u8(planes2[1]), _grid(field2)])
+    return np.frombuffer(raw, np.float32).reshape(h // block[0], w // block[0], 2)
+
+
+def ref_mc(plane2, b, field, fill):
+    """MF::draw_MVimage (:887-905) of a level whose image2 is plane2, at block size b, into an image of `fill`."""
+    p2 = _u8(plane2)
+    h, w = p2.shape
+    return np.frombuffer(_mf_ref(["mc"], [_i32(w, h, b, fill), p2, _grid(field)]), np.uint8).reshape(h, w)
+
+
+def ref_motion_to_color(flow, maxmotion=-1.0):
+    """Flow::MotionToColor (rw_flow.cpp:202-249) itself: (H, W, 3) uint8 B,G,R."""
+    f = _grid(flow)
+    raw = _mf_ref(["color"], [_i32(f.shape[1], f.shape[0]), np.array([maxmotion], np.float32).tobytes(), f])
+    return np.frombuffer(raw, np.uint8).reshape(f.shape[0], f.shape[1], 3)
+
+
+def ref_calculate_mse(gtruth, flow):
+    """Flow::CalculateMSE (rw_flow.cpp:309-332) itself."""
+    g, f = _grid(gtruth), _grid(flow)
+    assert g.shape == f.shape
+    return float(np.frombuffer(_mf_ref(["mse"], [_i32(g.shape[1], g.shape[0]), g, f]), np.float64)[0])

@@ -5,9 +5,9 @@
 
 1. hotpath_*.npz -- inputs (level planes AFTER padding + pyramid) and expected outputs of the hot
    path (MV grid after the search of every level and after every regulariser sweep, final dense
-   flow) for small seeded cases.  Produced by the CPU oracle (oracle/bbme_oracle.c), because the
-   reference's core cannot be built here (needs OpenCV) and holds no vectors of its own:
-   regression vectors, PARITY UNPINNED with respect to the reference binary.
+   flow) for small seeded cases.  Written by the CPU oracle (oracle/bbme_oracle.c) and PINNED: step 6
+   has the reference's own compiled core compute every stage of them again (variant_jacobi_* is not a
+   reference function and stays the oracle's).
 2. flo_ramp_ref.flo -- a 7x5 .flo written by the REFERENCE's own Middlebury code
    (middlebury/flow-code/flowIO.cpp, compiled into oracle/_ref/flo_ref): pins the codec.
 3. gt_stats.json -- known answers computed with the reference's own reader on the 8 ground-truth
@@ -24,6 +24,11 @@
    (flo_ref roundtrip; the bytes must come back unchanged), with the reference's stats of the sample
    and its colour coding (flo_ref color, automatic radius).  `python tests/golden/make_golden.py
    gt_samples` rewrites this file alone.
+6. reference_digests.json -- sha256 of what the REFERENCE's own core (motion_framework.cpp compiled in place
+   into oracle/_ref/mf_ref, see oracle/Makefile) computes: every stage and the dense field of the hotpath_* /
+   variant_raster_* files above (the step fails if a file differs from the reference), and the inputs, stages,
+   sweeps, fields and motion-compensated frames of the cases of tests/test_gpu_reference.py (tests/helpers.py:
+   REF_*).  `python tests/golden/make_golden.py reference_digests` rewrites this file alone.
 """
 import gzip
 import hashlib
@@ -43,6 +48,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 from oracle import bbme_oracle as O                                     # noqa: E402
 from blockbasedmotionestimation_amd.synth import synth_pair             # noqa: E402
+import helpers as H                                                     # noqa: E402
 from helpers import oracle_schedule                                     # noqa: E402
 
 REF = "/root/reference"
@@ -138,8 +144,87 @@ def color_by_reference(flo_ref, flo_path, shape, maxmotion=None):
     return np.fromfile(out, np.uint8).reshape(shape[0], shape[1], 3)
 
 
+def grid_digest(grid):
+    """sha256 of a float32 grid of the reference as int16 (what bbme_stage_get_mvs hands out)."""
+    assert np.array_equal(grid, np.round(grid)) and grid.min() >= -32768 and grid.max() <= 32767, "not an int16 grid"
+    return H.sha256_of(grid.astype(np.int16))
+
+
+def stage_record(planes1, planes2, search, block, raster=False):
+    ref = O.ref_stages(planes1[0], planes2[0], search, block, planes=(planes1, planes2), mode="raster" if raster else None)
+    whole = ref["flow"] if raster else ref["whole"]
+    assert whole.tobytes() == ref["flow"].tobytes()
+    rec = {"inputs": H.sha256_of(np.array(search + block, np.int32), *(list(planes1) + list(planes2))),
+           "stages": [[H.stage_key(n, l, b), grid_digest(g)] for n, l, b, g in ref["stages"]],
+           "flow": H.sha256_of(whole.astype(np.float32))}
+    return rec, ref
+
+
+def make_reference_digests():
+    assert O.have_mf_ref(), "oracle/_ref/mf_ref missing (needs the reference)"
+    out = {"golden": {}, "stages": {}, "spec": {}, "random": {}, "sweeps": {}, "coarse": {}, "mc": {}}
+    for name in sorted(list(CASES) + [v for v in VARIANTS if "raster" in v]):
+        g = np.load(os.path.join(HERE, name + ".npz"), allow_pickle=False)
+        L = len(g["block_size"])
+        p1, p2 = [g["plane1_l%d" % l] for l in range(L)], [g["plane2_l%d" % l] for l in range(L)]
+        ref = O.ref_stages(g["frame1"], g["frame2"], g["search_size"].tolist(), g["block_size"].tolist(), planes=(p1, p2),
+                           mode="raster" if "raster" in name else None)
+        keys = [str(k) for k in g["stages"]]
+        assert len(keys) == len(ref["stages"]) and list(ref["geometry"]) == g["geometry"].tolist(), name
+        for key, (_, _, _, grid) in zip(keys, ref["stages"]):
+            assert np.array_equal(grid, g[key].astype(np.float32)), "%s %s: the reference disagrees with the file" % (name, key)
+        whole = ref["flow"] if ref["whole"] is None else ref["whole"]
+        assert whole.tobytes() == g["flow"].tobytes() == ref["flow"].tobytes(), name
+        out["golden"][name] = {"inputs": H.sha256_of(np.concatenate([p.reshape(-1) for p in p1 + p2])),
+                               "stages": [[k, grid_digest(r[3])] for k, r in zip(keys, ref["stages"])],
+                               "flow": H.sha256_of(whole.astype(np.float32))}
+    for name in H.REF_STAGE_CASES:
+        p1, p2, search, block, raster = H.ref_stage_case(O, name)
+        out["stages"][name], ref = stage_record(p1, p2, search, block, raster)
+        if name == H.REF_MC_CASE:
+            finals = {l: g for n, l, b, g in ref["stages"] if (n, b) == ("sweep2", 2)}
+            for lvl in range(len(block)):
+                for b in sorted({2, 8, block[lvl]}):
+                    grid = finals[lvl][::b // 2, ::b // 2]
+                    frames = [O.ref_mc(p2[lvl], b, grid, fill) for fill in H.REF_MC_FILLS]
+                    out["mc"]["l%d_b%d" % (lvl, b)] = {"frames": [H.sha256_of(f) for f in frames],
+                                                       "stats": H.mc_stats(p1[lvl], frames[0], frames[1])}
+    for name in H.REF_SPEC_CASES:
+        c = H.LIMIT_CONTENTS[name]
+        p1, p2 = H.limit_content_planes(name)
+        out["spec"][name], _ = stage_record(p1, p2, c["search"], c["block"])
+    for seed in H.REF_RANDOM_SEEDS:
+        p1, p2, search, block = H.ref_random_case(O, seed)
+        out["random"][str(seed)], _ = stage_record(p1, p2, search, block)
+    g = H.ENERGY_LEVEL
+    for b in H.ENERGY_BLOCKS:
+        for kind in H.ENERGY_FIELDS:
+            p1, p2, field = H.energy_case(b, kind)
+            for run, mults in enumerate(H.ENERGY_RUNS):
+                sweeps = O.ref_sweeps(p1[0], p2[0], g["search"][0], g["block"][0], b, field, mults)
+                out["sweeps"]["energy_b%d_%s_run%d" % (b, kind, run)] = {"inputs": H.sha256_of(p1[0], p2[0], field),
+                                                                        "sweeps": [grid_digest(s) for s in sweeps]}
+    g = H.INT16_LEVELS
+    for b in (16, 8, 2):
+        p1, p2, field = H.int16_case(b)
+        sweeps = O.ref_sweeps(p1[1], p2[1], g["search"][1], g["block"][1], b, field)
+        out["sweeps"]["int16_b%d" % b] = {"inputs": H.sha256_of(p1[0], p2[0], p1[1], p2[1], field),
+                                          "sweeps": [grid_digest(s) for s in sweeps]}
+        if b == 2:
+            for k, grid in enumerate((field, sweeps[1].astype(np.int16))):
+                out["coarse"]["int16_from_%s" % ("field", "sweeps")[k]] = grid_digest(
+                    O.ref_search_from_coarse(p1, p2, g["search"], g["block"], grid))
+    with open(os.path.join(HERE, "reference_digests.json"), "w") as f:
+        json.dump(out, f, indent=1, sort_keys=True)
+        f.write("\n")
+    print("reference digests:", {k: len(v) for k, v in out.items()})
+
+
 def main():
     O.build(force=True)
+    if sys.argv[1:] == ["reference_digests"]:
+        make_reference_digests()
+        return
     if sys.argv[1:] == ["variants"]:
         for name, cfg in VARIANTS.items():
             make_hotpath(name, *cfg)
@@ -181,6 +266,7 @@ def main():
         with gzip.GzipFile(filename="", mode="wb", fileobj=raw, compresslevel=9, mtime=0) as dst:
             shutil.copyfileobj(src, dst)
     make_gt_samples(flo_ref, gt_dir)
+    make_reference_digests()
     print("gt stats:", {k: (v["width"], v["height"], v["unknown"]) for k, v in stats.items()})
 
 

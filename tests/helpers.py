@@ -61,8 +61,8 @@ def compare_stagewise(bbme, oracle, f1, f2, search, block, use_planes=True, rast
     assert (mf.padded_width, mf.padded_height, mf.padding_x, mf.padding_y) == \
            (omf.padded_width, omf.padded_height, omf.padding_x, omf.padding_y)
     if use_planes:
-        # hand the oracle's planes to the kernels so that pyramid construction (host prep,
-        # parity unpinned) cannot leak into hot-path parity
+        # hand the oracle's planes to the kernels so that pyramid construction (host prep; pyrDown is
+        # OpenCV's and not pinned) cannot leak into hot-path parity
         for lvl in range(L):
             mf.set_level_planes(lvl, omf.image(lvl, 1), omf.image(lvl, 2))
     exp = []
@@ -405,7 +405,7 @@ def oracle_search_from_coarse(omf, field2, B1, B0):
 def epe_reference(gt, cells, pad_x, pad_y, scale):
     """Flow::CalculateMSE (rw_flow.cpp:309-332) on the field the 2 x 2-cell grid holds at every scale-th pixel of the unpadded
     frame, divided by scale: the float32 per-pixel expression sqrtf(du * du + dv * dv), every operation rounded to float32 on
-    its own (numpy fuses nothing), summed in float64; unknown ground truth (|u| or |v| > 1e9, NaN) is skipped; NaN when nothing
+    its own (numpy fuses nothing), summed in float64 in row order; unknown ground truth (|u| or |v| > 1e9, NaN) is skipped; NaN when nothing
     is known."""
     gt = np.asarray(gt, np.float32)
     gh, gw = gt.shape[:2]
@@ -420,7 +420,9 @@ def epe_reference(gt, cells, pad_x, pad_y, scale):
         sq = ((du * du).astype(np.float32) + (dv * dv).astype(np.float32)).astype(np.float32)
         e = np.sqrt(sq).astype(np.float32)
     n = int(known.sum())
-    return float(e[known].astype(np.float64).sum()) / n if n else float("nan")
+    # summed one by one in row order, as the reference's loop does (cumsum adds sequentially; sum() would add pairwise and may
+    # leave the reference's double in its last bit)
+    return float(np.cumsum(e[known].astype(np.float64))[-1]) / n if n else float("nan")
 
 
 def epe_ground_truth(gh, gw, kind, rng):
@@ -482,3 +484,232 @@ def tie_field_float_vs_exact(p1, p2, b, field, lam_mult):
     e_a, e_b = sad_a.astype(np.float32) + t, sad_b.astype(np.float32) + t           # float32 sums, as :607
     differs = np.sign(sad_a - sad_b) != np.sign(e_a.astype(np.float64) - e_b.astype(np.float64))
     return int(ok.sum()), int((ok & differs).sum())
+
+
+# ---- the case lists of the parity tests (tests/test_gpu_parity.py: kernels against the oracle; ----
+# ---- tests/test_reference_core_cpu.py: the oracle against the reference's compiled core) -----------
+CASES = [
+    # (width, height, search_size[], block_size[], seed, max_motion)
+    (320, 208, [30, 30, 30], [16, 16, 16], 1001, 12),          # cfg1-like: B=16, R=7, 3 levels
+    (256, 192, [48], [16], 1002, 14),                           # single level, R=16
+    (384, 256, [48, 48, 48], [16, 16, 16], 1003, 24),           # cfg2-like, 3 levels
+    (512, 384, [80, 80, 80], [16, 16, 16], 1004, 40),           # R=32 (cfg3's search), windows leave the image
+    (256, 256, [72, 72], [8, 8], 1005, 20),                     # cfg4-like: B=8, R=32
+    (512, 512, [64, 64, 64], [32, 32, 32], 1006, 30),           # the reference's own literals: B=32, search 64
+    (320, 256, [24, 40, 30], [8, 16, 8], 1007, 10),             # different block / search per level
+    (200, 120, [30, 30], [16, 16], 1008, 6),                    # needs padding in both dimensions
+    (256, 128, [17, 21], [16, 16], 1009, 3),                    # odd shift (search-block odd), tiny ranges
+    (128, 128, [16], [16], 1010, 0),                            # search_size == block_size: centre only
+    (256, 192, [12, 12], [4, 4], 1011, 5),                      # B=4
+    (512, 512, [80, 80], [64, 64], 1012, 10),                   # B=64 (generic search, 64-lane regulariser groups)
+    (640, 512, [20, 20, 20, 24, 24], [4, 4, 4, 8, 8], 1013, 30),  # five levels, large coarse-to-fine motion
+    (256, 128, [8, 12], [16, 16], 1014, 2),                     # search_size < block_size: centre candidate only
+    (250, 130, [30], [16], 1015, 5),                            # odd-looking size, padded both ways (256 x 144)
+    (1024, 64, [48, 48], [16, 16], 1016, 12),                   # two block rows at the coarse level, very wide
+    (64, 1024, [48, 48], [16, 16], 1017, 12),                   # two block columns, very tall
+    # wide ranges: the fast kernel's packed (SAD, rank) keys at their limits (B=32: ranks up to 16128 need 14 bits)
+    (512, 384, [120], [32], 1018, 40),                          # B=32, R=44
+    (512, 384, [122], [32], 1019, 44),                          # B=32, R=45: 8281 candidates > 2^13
+    (512, 384, [123], [32], 1020, 44),                          # B=32, odd shift, R=45
+    (384, 384, [158], [32], 1021, 60),                          # B=32, R=63 (largest supported)
+    (384, 256, [134], [8], 1022, 60),                           # B=8, R=63
+    (384, 256, [142], [16], 1023, 60),                          # B=16, R=63
+    # ranges beyond the strip kernel's packed keys (R > 63) take the generic kernel, whose window then needs more LDS than a kernel
+    # gets by default (r04; the reference takes any search size, motion_framework.cpp:296-422)
+    (384, 256, [16 + 2 * 64], [16], 1025, 60),                  # B=16, R=64: the first range past the strip kernel
+    (320, 256, [8 + 2 * 100, 8 + 2 * 70], [8, 8], 1026, 70),    # B=8, R=100 over R=70
+    (384, 384, [32 + 2 * 127], [32], 1027, 100),                # B=32, R=127 (largest supported): 286-row window, 87 KB of LDS
+    # 2 x 2 blocks as a level's own block size (r04; the generic search kernel with the block in one dword): alone, under 4 x 4, and
+    # between two levels of larger blocks (copyMVs from a level that is already at 2 x 2 cells when its search ends)
+    (128, 96, [10], [2], 1028, 3),
+    (160, 128, [12, 20], [2, 4], 1029, 4),
+    (192, 128, [14, 10, 24], [4, 2, 8], 1030, 5),
+    # the author's second literal set (main_class.cpp:15-17, commented out there) on the 584 x 388 Middlebury geometry:
+    # 32 x 32 blocks over 16 x 16 ones (search_prediction's mixed-size path) and an odd shift, 42 - 32 = 10 -> R = 5
+    (584, 388, [32, 32, 42], [16, 16, 32], 1024, 10),
+]
+
+
+RASTER_CASES = [
+    (320, 208, [30, 30, 30], [16, 16, 16], 2001, 12),           # B=16, R=7, 3 levels
+    (384, 256, [48, 48], [16, 16], 2002, 24),                   # R=16
+    (256, 256, [72, 72], [8, 8], 2003, 20),                     # B=8, R=32: windows and predictions leave the image
+    (512, 512, [64, 64, 64], [32, 32, 32], 2004, 30),           # the reference's literals
+    (256, 192, [12, 12], [4, 4], 2005, 5),                      # B=4
+    (256, 128, [17, 21], [16, 16], 2006, 3),                    # odd search - block
+]
+
+
+def _random_case(rng):
+    """A random legal configuration and frame pair (small enough for the oracle to take milliseconds)."""
+    levels = int(rng.integers(1, 4))
+    blocks = [int(rng.choice([2, 4, 4, 8, 8, 16, 16, 32])) for _ in range(levels)]
+    # sizes that need no padding keep the search for a legal size trivial; padding is tested elsewhere; every level's width a
+    # multiple of four (the kernels move rows as dwords: only 2 x 2 blocks can ask for less)
+    m = int(np.lcm.reduce([b << i for i, b in enumerate(blocks)] + [4 << (levels - 1)]))
+    w = m * int(rng.integers(max(2, -(-2 * (blocks[-1] << (levels - 1)) // m)), 6))
+    h = m * int(rng.integers(max(2, -(-2 * (blocks[-1] << (levels - 1)) // m)), 5))
+    w, h = min(w, 768), min(h, 512)
+    w, h = max(m * 2, w // m * m), max(m * 2, h // m * m)
+    search = [b + 2 * int(rng.integers(0, 20)) + int(rng.integers(0, 2)) for b in blocks]
+    kind = int(rng.integers(0, 5))
+    if kind == 0:                       # smooth texture + piecewise motion (the bench's recipe)
+        from blockbasedmotionestimation_amd.synth import synth_pair
+        f1, f2, _ = synth_pair(w, h, int(rng.integers(1 << 30)), max_motion=int(rng.integers(0, 12)))
+    elif kind == 1:                     # white noise, shifted
+        f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        f2 = np.roll(f1, (int(rng.integers(-9, 10)), int(rng.integers(-9, 10))), axis=(0, 1))
+    elif kind == 2:                     # few grey levels: ties everywhere
+        f1 = (rng.integers(0, 3, (h, w)) * 100).astype(np.uint8)
+        f2 = (rng.integers(0, 3, (h, w)) * 100).astype(np.uint8)
+    elif kind == 3:                     # flat regions next to texture
+        f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        f1[: h // 2, : w // 2] = 50
+        f2 = np.roll(f1, 3, axis=1)
+        f2[h // 3:, w // 3:] = 200
+    else:                               # unrelated frames
+        f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        f2 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    return f1, f2, search, blocks
+
+
+def content_pairs():
+    """The tie / flat / periodic / noise / large-motion contents of tests/test_gpu_parity.py: (name, f1, f2, search, block, raster)."""
+    from blockbasedmotionestimation_amd.synth import synth_pair
+    out = []
+    z = np.zeros((128, 192), np.uint8)
+    c = np.full((128, 192), 77, np.uint8)
+    t1, t2, _ = synth_pair(192, 128, 5, max_motion=8)
+    out += [("zeros", z, z, [48, 48], [16, 16], False), ("flat", c, c, [30, 30], [16, 16], False),
+            ("flat_vs_texture", c, t2, [30, 30], [16, 16], False), ("texture_vs_flat", t1, c, [30, 30], [16, 16], False)]
+    y, x = np.mgrid[0:192, 0:256]
+    stripes = ((x // 4) % 2 * 200).astype(np.uint8)
+    checker = (((x // 8) + (y // 8)) % 2 * 255).astype(np.uint8)
+    out += [("stripes", stripes, np.roll(stripes, 3, axis=1), [48, 48], [16, 16], False),
+            ("checker", checker, np.roll(checker, (5, -2), axis=(0, 1)), [48, 48], [16, 16], False)]
+    rng = np.random.default_rng(7)
+    f1 = rng.integers(0, 256, (256, 320), dtype=np.uint8)
+    out.append(("large_motion", f1, np.roll(f1, (37, -45), axis=(0, 1)), [80, 80, 80], [16, 16, 16], False))
+    rng = np.random.default_rng(12)
+    n1 = rng.integers(0, 256, (160, 224), dtype=np.uint8)
+    n2 = rng.integers(0, 256, (160, 224), dtype=np.uint8)
+    out.append(("noise_b8", n1, n2, [40, 40], [8, 8], False))
+    rng = np.random.default_rng(13)
+    n1 = rng.integers(0, 256, (128, 192), dtype=np.uint8)
+    n2 = rng.integers(0, 256, (128, 192), dtype=np.uint8)
+    out.append(("noise_b4", n1, n2, [24, 24], [4, 4], False))
+    rng = np.random.default_rng(14)
+    g1 = (rng.integers(0, 3, (128, 192)) * 100).astype(np.uint8)
+    g2 = (rng.integers(0, 3, (128, 192)) * 100).astype(np.uint8)
+    out.append(("three_grey_levels", g1, g2, [30, 30], [8, 8], False))
+    # raster mode where its rules differ from the spiral's (test_raster_search_ties_and_outside_predictions)
+    z90 = np.full((128, 192), 90, np.uint8)
+    rng = np.random.default_rng(17)
+    r1 = rng.integers(0, 256, (256, 320), dtype=np.uint8)
+    out += [("raster_flat", z90, z90, [48, 48], [16, 16], True),
+            ("raster_stripes", stripes, np.roll(stripes, 3, axis=1), [48, 48], [16, 16], True),
+            ("raster_large_motion", r1, np.roll(r1, (37, -45), axis=(0, 1)), [80, 80, 80], [16, 16, 16], True),
+            ("raster_three_grey_levels", g1, g2, [30, 30], [8, 8], True)]
+    return out
+
+
+CONTENT_NAMES = ["zeros", "flat", "flat_vs_texture", "texture_vs_flat", "stripes", "checker", "large_motion", "noise_b8",
+                 "noise_b4", "three_grey_levels", "raster_flat", "raster_stripes", "raster_large_motion",
+                 "raster_three_grey_levels"]
+
+
+# ---- the cases of tests/test_gpu_reference.py: the kernels against what the reference's compiled core (oracle/_ref/mf_ref) ----
+# ---- wrote.  tests/golden/make_golden.py runs mf_ref on these inputs and records sha256 digests of the inputs, of every -------
+# ---- stage's grid (as int16) and of the dense field (float32) in tests/golden/reference_digests.json -------------------------
+def sha256_of(*arrays):
+    import hashlib
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a).tobytes())
+    return h.hexdigest()
+
+
+def pyramid_planes(oracle, f1, f2, block):
+    """The level planes MF::MF makes of a frame pair (zero padding by the plan :14-54, then pyrDown per level), by the oracle's
+    host functions: inputs of the comparisons, covered by the recorded input digest."""
+    rc, pw, ph, px, py = oracle.plan_padding(f1.shape[1], f1.shape[0], block)
+    assert rc == 0, "no padding plan for %s with %s" % (f1.shape, block)
+    p1, p2 = [oracle.pad_zero(f1, px, py)], [oracle.pad_zero(f2, px, py)]
+    for _ in block[1:]:
+        p1.append(oracle.pyr_down(p1[-1]))
+        p2.append(oracle.pyr_down(p2[-1]))
+    return p1, p2
+
+
+# name: (source, key): "case" / "raster" index CASES / RASTER_CASES, "content" a CONTENT_NAMES entry.  Every search kernel and
+# regulariser form is touched: the strip kernels for B = 8, 16, 32, the generic kernel for 2 x 2, 4 x 4 and 64 x 64 blocks and
+# for R = 64 (its first range), the widest strip range R = 63, mixed block sizes between levels, raster mode, ties, predictions
+# that leave the image
+REF_STAGE_CASES = {
+    "cfg1_like": ("case", 0), "cfg4_like_b8_r32": ("case", 4), "literals_b32_s64": ("case", 5), "mixed": ("case", 6),
+    "ref2_literals": ("case", 29), "padded": ("case", 7), "odd_shift": ("case", 8), "block2": ("case", 26),
+    "block2_under_4": ("case", 27), "block2_between": ("case", 28), "block4": ("case", 10), "b64": ("case", 11), "b16_r63": ("case", 22), "b16_r64": ("case", 23),
+    "raster_b16_r7": ("raster", 0), "raster_b8_r32": ("raster", 2), "raster_odd_shift": ("raster", 5),
+    "zeros": ("content", "zeros"), "stripes": ("content", "stripes"), "checker": ("content", "checker"),
+    "three_grey_levels": ("content", "three_grey_levels"), "large_motion": ("content", "large_motion"),
+    "raster_flat": ("content", "raster_flat"), "raster_large_motion": ("content", "raster_large_motion"),
+}
+# bbme_estimate whole, the speculative search forced onto every level (BBME_SPEC_MIN_GABS=0): LIMIT_CONTENTS entries
+REF_SPEC_CASES = ("spec_b16", "spec_b8")
+REF_RANDOM_SEEDS = tuple(range(10))           # of test_random_configurations_twice: default schedule, run twice
+REF_SWEEP_FORMS = {"default": {}, "pass1_strip": LIMIT_REG_FORMS["pass1_strip"], "solve_one_wave": LIMIT_REG_FORMS["solve_one_wave"],
+                   "memo_b8_forward": LIMIT_REG_FORMS["memo_b8_forward"]}
+REF_MC_CASE = "cfg1_like"                     # draw_MVimage / compensation_error after an estimate of this case
+REF_MC_FILLS = (0, 255)
+
+
+def ref_stage_case(oracle, name):
+    """(planes1, planes2, search, block, raster) of a REF_STAGE_CASES entry."""
+    from blockbasedmotionestimation_amd.synth import synth_pair
+    source, key = REF_STAGE_CASES[name]
+    if source == "content":
+        _, f1, f2, search, block, raster = {p[0]: p for p in content_pairs()}[key]
+    else:
+        w, h, search, block, seed, mm = (CASES if source == "case" else RASTER_CASES)[key]
+        f1, f2, _ = synth_pair(w, h, seed, max_motion=mm)
+        raster = source == "raster"
+    p1, p2 = pyramid_planes(oracle, f1, f2, block)
+    return p1, p2, list(search), list(block), raster
+
+
+def ref_random_case(oracle, seed):
+    """(planes1, planes2, search, block) of random configuration `seed`."""
+    f1, f2, search, block = _random_case(np.random.default_rng(9000 + seed))
+    p1, p2 = pyramid_planes(oracle, f1, f2, block)
+    return p1, p2, search, block
+
+
+def stage_key(name, level, block):
+    return "%s_l%d_b%d" % (name, level, block)
+
+
+def mc_stats(image1, frame_fill0, frame_fill255):
+    """[sse, sad, pixels, skipped] of a draw_MVimage frame against image1; a pixel was skipped where the two fills show."""
+    ok = frame_fill0 == frame_fill255
+    d = frame_fill0.astype(np.int64) - image1.astype(np.int64)
+    return [int((d[ok] ** 2).sum()), int(np.abs(d[ok]).sum()), int(ok.sum()), int((~ok).sum())]
+
+
+# lambda * (float)mult * S at :607 is (lambda * mult) * S.  With the schedule's own values -- lambda a power of two, mult 1 or 2 --
+# every product is exact and no association can show; a block size of 12 (lambda = 6) and multipliers such as 37 or 101 make both
+# factors odd multiples, and outliers of a million pixels push S (itself a float32 sum beyond 2^24, so its order of summation
+# counts too) to where each product rounds.  A and B are one pixel apart in their distance to the outlier C, so that where a
+# neighbourhood holds as many A as B the two energies differ by the SADs and a few units of lambda * mult: within the rounding.
+ASSOCIATION_LEVEL = dict(w=1020, h=1020, block=12, seed=101, mults=((37,), (101,), (37, 101), (3,)))
+ASSOCIATION_VECTORS = ((5, -3), (-4, 7), (1000000, 1000000))
+
+
+def association_case():
+    """(plane1, plane2, int32 grid at 12 x 12 blocks) of the association check (oracle against reference only: the product takes
+    neither this block size nor these multipliers)."""
+    g = ASSOCIATION_LEVEL
+    rng = np.random.default_rng(g["seed"])
+    p1 = rng.integers(0, 256, (g["h"], g["w"]), dtype=np.uint8)
+    p2 = rng.integers(0, 256, (g["h"], g["w"]), dtype=np.uint8)
+    field = np.array(ASSOCIATION_VECTORS, np.int32)[rng.choice(3, (g["h"] // g["block"], g["w"] // g["block"]), p=[0.35, 0.35, 0.3])]
+    return p1, p2, field

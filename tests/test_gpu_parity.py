@@ -5,7 +5,7 @@ and bit-exact dense float flow at the end."""
 import numpy as np
 import pytest
 
-from helpers import compare_stagewise, gpu_schedule, oracle_schedule
+from helpers import CASES, RASTER_CASES, _random_case, compare_stagewise, gpu_schedule, oracle_schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -30,48 +30,6 @@ def test_device_probes(bbme):
     t = (C.c_double * 2)()
     _capi.check(_capi.lib().bbme_probe_search_loops(0, t))
     assert 20 < t[0] < 400 and 20 < t[1] < 400
-
-
-CASES = [
-    # (width, height, search_size[], block_size[], seed, max_motion)
-    (320, 208, [30, 30, 30], [16, 16, 16], 1001, 12),          # cfg1-like: B=16, R=7, 3 levels
-    (256, 192, [48], [16], 1002, 14),                           # single level, R=16
-    (384, 256, [48, 48, 48], [16, 16, 16], 1003, 24),           # cfg2-like, 3 levels
-    (512, 384, [80, 80, 80], [16, 16, 16], 1004, 40),           # R=32 (cfg3's search), windows leave the image
-    (256, 256, [72, 72], [8, 8], 1005, 20),                     # cfg4-like: B=8, R=32
-    (512, 512, [64, 64, 64], [32, 32, 32], 1006, 30),           # the reference's own literals: B=32, search 64
-    (320, 256, [24, 40, 30], [8, 16, 8], 1007, 10),             # different block / search per level
-    (200, 120, [30, 30], [16, 16], 1008, 6),                    # needs padding in both dimensions
-    (256, 128, [17, 21], [16, 16], 1009, 3),                    # odd shift (search-block odd), tiny ranges
-    (128, 128, [16], [16], 1010, 0),                            # search_size == block_size: centre only
-    (256, 192, [12, 12], [4, 4], 1011, 5),                      # B=4
-    (512, 512, [80, 80], [64, 64], 1012, 10),                   # B=64 (generic search, 64-lane regulariser groups)
-    (640, 512, [20, 20, 20, 24, 24], [4, 4, 4, 8, 8], 1013, 30),  # five levels, large coarse-to-fine motion
-    (256, 128, [8, 12], [16, 16], 1014, 2),                     # search_size < block_size: centre candidate only
-    (250, 130, [30], [16], 1015, 5),                            # odd-looking size, padded both ways (256 x 144)
-    (1024, 64, [48, 48], [16, 16], 1016, 12),                   # two block rows at the coarse level, very wide
-    (64, 1024, [48, 48], [16, 16], 1017, 12),                   # two block columns, very tall
-    # wide ranges: the fast kernel's packed (SAD, rank) keys at their limits (B=32: ranks up to 16128 need 14 bits)
-    (512, 384, [120], [32], 1018, 40),                          # B=32, R=44
-    (512, 384, [122], [32], 1019, 44),                          # B=32, R=45: 8281 candidates > 2^13
-    (512, 384, [123], [32], 1020, 44),                          # B=32, odd shift, R=45
-    (384, 384, [158], [32], 1021, 60),                          # B=32, R=63 (largest supported)
-    (384, 256, [134], [8], 1022, 60),                           # B=8, R=63
-    (384, 256, [142], [16], 1023, 60),                          # B=16, R=63
-    # ranges beyond the strip kernel's packed keys (R > 63) take the generic kernel, whose window then needs more LDS than a kernel
-    # gets by default (r04; the reference takes any search size, motion_framework.cpp:296-422)
-    (384, 256, [16 + 2 * 64], [16], 1025, 60),                  # B=16, R=64: the first range past the strip kernel
-    (320, 256, [8 + 2 * 100, 8 + 2 * 70], [8, 8], 1026, 70),    # B=8, R=100 over R=70
-    (384, 384, [32 + 2 * 127], [32], 1027, 100),                # B=32, R=127 (largest supported): 286-row window, 87 KB of LDS
-    # 2 x 2 blocks as a level's own block size (r04; the generic search kernel with the block in one dword): alone, under 4 x 4, and
-    # between two levels of larger blocks (copyMVs from a level that is already at 2 x 2 cells when its search ends)
-    (128, 96, [10], [2], 1028, 3),
-    (160, 128, [12, 20], [2, 4], 1029, 4),
-    (192, 128, [14, 10, 24], [4, 2, 8], 1030, 5),
-    # the author's second literal set (main_class.cpp:15-17, commented out there) on the 584 x 388 Middlebury geometry:
-    # 32 x 32 blocks over 16 x 16 ones (search_prediction's mixed-size path) and an odd shift, 42 - 32 = 10 -> R = 5
-    (584, 388, [32, 32, 42], [16, 16, 32], 1024, 10),
-]
 
 
 @pytest.mark.parametrize("w,h,search,block,seed,mm", CASES)
@@ -106,39 +64,6 @@ def test_golden_fixtures(bbme, name):
         assert np.array_equal(g[key].astype(np.int32), mv), key
     assert np.array_equal(g["flow"], flow)
     mf.close()
-
-
-def _random_case(rng):
-    """A random legal configuration and frame pair (small enough for the oracle to take milliseconds)."""
-    levels = int(rng.integers(1, 4))
-    blocks = [int(rng.choice([2, 4, 4, 8, 8, 16, 16, 32])) for _ in range(levels)]
-    # sizes that need no padding keep the search for a legal size trivial; padding is tested elsewhere; every level's width a
-    # multiple of four (the kernels move rows as dwords: only 2 x 2 blocks can ask for less)
-    m = int(np.lcm.reduce([b << i for i, b in enumerate(blocks)] + [4 << (levels - 1)]))
-    w = m * int(rng.integers(max(2, -(-2 * (blocks[-1] << (levels - 1)) // m)), 6))
-    h = m * int(rng.integers(max(2, -(-2 * (blocks[-1] << (levels - 1)) // m)), 5))
-    w, h = min(w, 768), min(h, 512)
-    w, h = max(m * 2, w // m * m), max(m * 2, h // m * m)
-    search = [b + 2 * int(rng.integers(0, 20)) + int(rng.integers(0, 2)) for b in blocks]
-    kind = int(rng.integers(0, 5))
-    if kind == 0:                       # smooth texture + piecewise motion (the bench's recipe)
-        from blockbasedmotionestimation_amd.synth import synth_pair
-        f1, f2, _ = synth_pair(w, h, int(rng.integers(1 << 30)), max_motion=int(rng.integers(0, 12)))
-    elif kind == 1:                     # white noise, shifted
-        f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
-        f2 = np.roll(f1, (int(rng.integers(-9, 10)), int(rng.integers(-9, 10))), axis=(0, 1))
-    elif kind == 2:                     # few grey levels: ties everywhere
-        f1 = (rng.integers(0, 3, (h, w)) * 100).astype(np.uint8)
-        f2 = (rng.integers(0, 3, (h, w)) * 100).astype(np.uint8)
-    elif kind == 3:                     # flat regions next to texture
-        f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
-        f1[: h // 2, : w // 2] = 50
-        f2 = np.roll(f1, 3, axis=1)
-        f2[h // 3:, w // 3:] = 200
-    else:                               # unrelated frames
-        f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
-        f2 = rng.integers(0, 256, (h, w), dtype=np.uint8)
-    return f1, f2, search, blocks
 
 
 @pytest.mark.parametrize("seed", range(40))
@@ -825,16 +750,6 @@ def test_cell_gather_world_size_one_nccl(bbme, oracle, overlap, speculate):
     finally:
         dist.destroy_process_group()
         omf.close()
-
-
-RASTER_CASES = [
-    (320, 208, [30, 30, 30], [16, 16, 16], 2001, 12),           # B=16, R=7, 3 levels
-    (384, 256, [48, 48], [16, 16], 2002, 24),                   # R=16
-    (256, 256, [72, 72], [8, 8], 2003, 20),                     # B=8, R=32: windows and predictions leave the image
-    (512, 512, [64, 64, 64], [32, 32, 32], 2004, 30),           # the reference's literals
-    (256, 192, [12, 12], [4, 4], 2005, 5),                      # B=4
-    (256, 128, [17, 21], [16, 16], 2006, 3),                    # odd search - block
-]
 
 
 @pytest.mark.parametrize("w,h,search,block,seed,mm", RASTER_CASES)

@@ -1,6 +1,7 @@
 """CPU tests of the oracle itself: pin what can be pinned (the .flo codec and EPE against the
-reference's own Middlebury code and ground-truth files), and cross-check the unpinned hot-path
-restatement against an independently structured numpy restatement and the committed vectors."""
+reference's own Middlebury code and ground-truth files), and cross-check the hot-path restatement
+against an independently structured numpy restatement and the committed vectors.  The hot path itself
+is pinned to the reference's compiled core by tests/test_reference_core_cpu.py."""
 import hashlib
 import json
 import os
