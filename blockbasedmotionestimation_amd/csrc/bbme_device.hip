@@ -8,7 +8,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
+#include <type_traits>
 #include <vector>
 
 #include "bbme_internal.hpp"
@@ -26,32 +28,89 @@ using namespace bbme;
 
 namespace {
 
+// Owning handles of device memory and of events: whoever holds one releases it, so an early return leaks nothing.
+// DevBuf is move-only, its sizes are in elements of T; every size expression and its slack stays with the caller (they are
+// contracts with the kernels).  Errors are the library's codes: "allocating <what>: <HIP's text>".
+template <class T>
+class DevBuf {
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    T *get() const { return p_; }
+    operator T *() const { return p_; }
+    size_t size() const { return bytes_ / sizeof(T); }
+    int alloc(size_t n, const char *what) { return alloc_bytes(n * sizeof(T), what); }
+    int alloc_zero(size_t n, const char *what)
+    {
+        if (int rc = alloc(n, what)) return rc;
+        return check(hipMemset(p_, 0, bytes_), what);
+    }
+    // the vector's bytes, and `slack_bytes` behind them that a kernel may load (and mask) but that hold nothing
+    template <class U>
+    int upload(const std::vector<U> &v, const char *what, size_t slack_bytes = 0)
+    {
+        if (int rc = alloc_bytes(v.size() * sizeof(U) + slack_bytes, what)) return rc;
+        return check(hipMemcpy(p_, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice), what);
+    }
+    // scratch: allocated on first use, replaced when more is asked for (the caller orders that against whoever reads it)
+    int ensure(size_t n, const char *what) { return n * sizeof(T) <= bytes_ ? BBME_OK : alloc(n, what); }
+
+private:
+    static int check(hipError_t e, const char *what)
+    {
+        return e == hipSuccess ? BBME_OK : bbme::fail(BBME_ERR_HIP, "allocating %s: %s", what, hipGetErrorString(e));
+    }
+    int alloc_bytes(size_t bytes, const char *what)
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+        bytes_ = 0;
+        if (int rc = check(hipMalloc(&p_, bytes), what)) { p_ = nullptr; return rc; }
+        bytes_ = bytes;
+        return BBME_OK;
+    }
+    T *p_ = nullptr;
+    size_t bytes_ = 0;
+};
+
+struct DevEvent {
+    hipEvent_t ev = nullptr;
+    DevEvent() = default;
+    DevEvent(DevEvent &&o) noexcept : ev(o.ev) { o.ev = nullptr; }
+    ~DevEvent() { if (ev) (void)hipEventDestroy(ev); }
+    operator hipEvent_t() const { return ev; }
+};
+
 struct Level {
     int width = 0, height = 0, block = 0, search = 0, range = 0;
-    uint8_t *img1 = nullptr, *img2 = nullptr;     // padded planes, pitch == width
+    DevBuf<uint8_t> img1, img2_own;               // padded planes, pitch == width
+    uint8_t *img2 = nullptr;                      // img2_own; in a chain context an alias of img1 + one plane (see bbme_ctx::chain)
     // MV grids.  small[]: grids at the level's own block size B (the search writes small[0]; the two sweeps at B go
     // small[0] -> small[1] -> small[0], which then stays untouched until the level's next search: the speculative search
     // of the next finer level predicts from it).  big[]: grids at b < B (capacity (H/2)*(W/2)), ping-pong.
-    mv_t *small[2] = {nullptr, nullptr};
-    mv_t *big[2] = {nullptr, nullptr};
+    DevBuf<mv_t> small[2];
+    DevBuf<mv_t> big[2];
     mv_t *cur_grid = nullptr;                     // the grid that holds the current field
     int cur_block = 0;                            // its block size (0 = nothing yet)
-    mv_t *pred = nullptr;                         // per block: the coarse MV a speculative search started from
-    uint32_t *fix_list = nullptr, *fix_count = nullptr;   // blocks to search again after a speculative search
+    DevBuf<mv_t> pred;                            // per block: the coarse MV a speculative search started from
+    DevBuf<uint32_t> fix_list, fix_count;         // blocks to search again after a speculative search
     mv_t *final_grid() const { return block == 2 ? small[0] : big[1]; }   // where two sweeps per block size leave the 2x2 cells
-    uint32_t *spiral = nullptr;                   // rank -> packed (dx, dy)
+    DevBuf<uint32_t> spiral;                      // rank -> packed (dx, dy)
     int ncand = 0;
     int pitch_dw = 0;
     size_t lds_bytes = 0;
     // fast search kernel (block 8 / 16)
     bool fast = false;
-    uint16_t *rank_of = nullptr;
+    DevBuf<uint16_t> rank_of;
     int rank_pitch = 0;
-    uint32_t *tasks = nullptr, *rounds = nullptr;
+    DevBuf<uint32_t> tasks, rounds;
     int nrounds = 0;
-    uint32_t *tasks2 = nullptr, *rounds2 = nullptr;   // the plan for two waves per macroblock (levels of few blocks)
+    DevBuf<uint32_t> tasks2, rounds2;                 // the plan for two waves per macroblock (levels of few blocks)
     int nrounds2 = 0;
-    uint2 *lane_ranks = nullptr, *lane_ranks2 = nullptr;   // per plan: the ranks of every lane's candidates (FastSearchArgs::lane_ranks)
+    DevBuf<uint2> lane_ranks, lane_ranks2;            // per plan: the ranks of every lane's candidates (FastSearchArgs::lane_ranks)
     bool split_pays = false;                          // the two-wave plan is at least 20 % shorter per wave
     int fast_pitch_dw = 0;
     size_t fast_lds_bytes = 0;
@@ -62,23 +121,9 @@ struct Level {
     uint32_t grid_stride(const mv_t *g) const { return (g == small[0] || g == small[1]) ? small_stride : big_stride; }
 };
 
-}  // namespace
-
-struct bbme_ctx {
-    bbme_params params{};
-    Geometry geom{};
-    int device = 0;
-    int batch = 1;                                // independent frame pairs this context holds (blockIdx.y of every kernel)
-    size_t flow_stride = 0;                       // floats from pair to pair in `flow`
-    uint32_t list_stride = 0, own_stride = 0;     // words from pair to pair in list[] / own
-    size_t raw_stride = 0;                        // bytes from pair to pair in raw[]
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::vector<Level> lv;
-    float *flow = nullptr;                        // dense padded H0 x W0 float2
-    uint32_t *list[2] = {nullptr, nullptr};
-    uint8_t *flags[2] = {nullptr, nullptr};       // dirty flags of the regulariser, one byte per block, all zero between sweeps
-    size_t flag_bytes = 0;
+// Everything the environment tunes, with its default.  Read once per context, at creation (read_tuning): never through
+// statics, so two contexts of a process may differ and a test may set a knob between them.
+struct Tuning {
     int relax_steps = -1;                         // k_reg_iter launches per sweep; -1 = by grid size (BBME_RELAX_STEPS overrides)
     bool split_forced = false;                    // threshold given in the environment: split whatever the plans' lengths (tests)
     long long scan_fine_max = 140000;             // grids of at most this many blocks: scan segments of 4 flags (BBME_SCAN_FINE_MAX)
@@ -88,17 +133,114 @@ struct bbme_ctx {
     int pass1_strip = -1;                         // the strip form of pass 1 at b <= 4 (k_reg_pass1_strip): -1 = batched contexts only; BBME_PASS1_STRIP
     int split_blocks = 10000;                     // levels of at most this many macroblocks: two waves per block (BBME_SEARCH_SPLIT_BLOCKS)
     int round_cap = 0;                            // > 0: test knob, the regulariser's waves give up after this many rounds
-    uint32_t *own = nullptr;                      // ownership counters of the solver, one word per block
-    uint32_t own_pitch = 0;                       // transposed layout: 32 residue classes of own_pitch words
-    uint32_t *counters = nullptr;                 // 64 words (RegArgs::counters)
-    // SAD memo of the regulariser's chain form (bbme_kernels.hpp, "SAD memo"): nine (MV, SAD) words per block at b >= 8
-    unsigned long long *memo = nullptr;
-    uint32_t memo_stride = 0;                     // words from pair to pair
-    size_t memo_blocks = 0;                       // blocks per pair it has room for
-    int memo_level = -1, memo_block = 0;          // the (level, block size) its slots describe; block 0 = nothing
     bool use_memo = true;                         // BBME_MEMO
     int memo_min_block = 16;                      // sweeps at smaller blocks run without it (8: measured slower); BBME_MEMO_MIN_B
     bool memo_forward = false;                    // BBME_MEMO_FORWARD (measured slower: off)
+    int local_rounds = 8;                         // k_reg_iter: heavy rounds of a tile per launch; BBME_LOCAL_ROUNDS
+    int wide_threshold = 16;                      // solver: queue length above which a round takes the throughput form; BBME_WIDE_THRESHOLD
+    int solve_waves = 4;                          // waves per solver workgroup (1, 2 or 4); BBME_SOLVE_WAVES
+    bool solve_share = true;                      // k_reg_solve: idle waves of a workgroup take a sibling's surplus; BBME_SOLVE_SHARE=0
+    int solve_wgs = 256;                          // most workgroups of k_reg_solve (4 independent waves each); r04: 256 measured 1.5 % ahead of 128 (one wave per SIMD)
+    int xcd_remap = 1;                            // XCD-aware block order in k_search_fast; BBME_XCD_REMAP
+    bool loose_plan = false;                      // the round-2 search plan without rim rounds; BBME_LOOSE_PLAN (set at all = on)
+    long long relax_min_blocks = 300000;          // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (launch_sweep)
+    int relax_max_b = 2, relax_s1 = 1, relax_s2 = 0;
+    bool force_generic_search = false;            // BBME_GENERIC_SEARCH=1: use k_search_generic everywhere
+    bool use_graph = true;                        // BBME_NO_GRAPH=1: eager launches
+    bool speculate = true;                        // overlap every level's search with the coarser level's late sweeps; BBME_SPECULATE
+    bool fork_both = false;                       // BBME_SPECULATE_BOTH_GRAPHS=1: both directions' graphs forked (bbme_ctx::graph_forked)
+    // a speculative search may keep at most this many of its (one-wave) workgroups on a CU: the rest of the CU's wave
+    // slots, registers and LDS (40 KB) stay free for the regulariser kernels it runs beside
+    // (r04, on the faster solver.  Behind a level of 16 x 16 blocks -- three late block sizes to hide the search behind -- 6-7 is
+    // best: cfg3 1.614 / 1.585 / 1.591 / 1.626 ms at 8 / 6 / 7 / 5.  Behind a level of 8 x 8 blocks the sweeps are over long
+    // before the search is, and any cap only delays it: cfg4 1.80 / 1.72 / 1.67 / 1.62 ms at 6 / 8 / 10 / 24 = uncapped.)
+    int spec_per_cu = 0;                          // BBME_SPEC_WGS_PER_CU; 0 = by the coarser level's block size (spec_lds_for)
+    int spec_per_cu_l0 = 0;                       // second value of BBME_SPEC_WGS_PER_CU="other,level0": the level-0 launch's own cap
+    // LDS per workgroup of a speculative search launch beside the late sweeps of `coarser_block`-sized level: the occupancy cap
+    size_t spec_lds_for(int coarser_block, int level = 1) const
+    {
+        // (r04: 7, not 6, since the level-0 search -- not the level-1 sweeps beside it, shorter now -- is what the level waits for:
+        //  cfg3 1.494 -> 1.470 ms; 8 and more cost the sweeps more than the search gains)
+        int per_cu = spec_per_cu > 0 ? spec_per_cu : (coarser_block >= 16 ? 7 : 24);
+        if (level == 0 && spec_per_cu_l0 > 0) per_cu = spec_per_cu_l0;
+        return ((size_t)(160 - 40) * 1024 / per_cu) / 256 * 256;
+    }
+    double spec_min_absdiffs = 8e9;               // levels with less search work are not speculated; BBME_SPEC_MIN_GABS
+};
+
+const struct {
+    const char *name;
+    void (*parse)(const char *value, Tuning &t);  // the field(s) the variable sets, with its clamp
+} kKnobs[] = {
+    {"BBME_SOLVE_SHARE", [](const char *e, Tuning &t) { t.solve_share = atoi(e) != 0; }},
+    {"BBME_SOLVE_WGS", [](const char *e, Tuning &t) { t.solve_wgs = std::max(1, std::min(8192, atoi(e))); }},
+    {"BBME_RELAX_STEPS", [](const char *e, Tuning &t) { t.relax_steps = std::max(0, std::min(64, atoi(e))); }},
+    {"BBME_SOLVE_WAVES", [](const char *e, Tuning &t) { const int v = atoi(e); t.solve_waves = v <= 1 ? 1 : (v == 2 ? 2 : 4); }},
+    {"BBME_TEST_ROUND_CAP", [](const char *e, Tuning &t) { t.round_cap = std::max(0, atoi(e)); }},
+    {"BBME_PASS1_LANES_MAX", [](const char *e, Tuning &t) { t.pass1_lanes_max = atoll(e); }},
+    {"BBME_SCAN_FINE_MAX", [](const char *e, Tuning &t) { t.scan_fine_max = atoll(e); }},
+    {"BBME_PASS1_STRIP", [](const char *e, Tuning &t) { t.pass1_strip = atoi(e) != 0 ? 1 : 0; }},
+    {"BBME_LIST_SPLIT", [](const char *e, Tuning &t) { t.list_split = atoi(e) != 0; }},
+    {"BBME_PASS1_LAZY", [](const char *e, Tuning &t) { t.pass1_lazy = atoi(e) != 0; }},
+    {"BBME_SEARCH_SPLIT_BLOCKS", [](const char *e, Tuning &t) { t.split_blocks = std::max(0, atoi(e)); t.split_forced = true; }},
+    {"BBME_NO_GRAPH", [](const char *e, Tuning &t) { t.use_graph = atoi(e) == 0; }},
+    {"BBME_SPECULATE", [](const char *e, Tuning &t) { t.speculate = atoi(e) != 0; }},
+    {"BBME_SPECULATE_BOTH_GRAPHS", [](const char *e, Tuning &t) { t.fork_both = atoi(e) != 0; }},
+    {"BBME_SPEC_WGS_PER_CU", [](const char *e, Tuning &t) {                                   // "n" or "n,n0"
+         t.spec_per_cu = std::max(1, std::min(32, atoi(e)));
+         if (const char *comma = strchr(e, ',')) t.spec_per_cu_l0 = std::max(1, std::min(32, atoi(comma + 1)));
+     }},
+    {"BBME_SPEC_MIN_GABS", [](const char *e, Tuning &t) { t.spec_min_absdiffs = atof(e) * 1e9; }},
+    {"BBME_GENERIC_SEARCH", [](const char *e, Tuning &t) { t.force_generic_search = atoi(e) != 0; }},
+    {"BBME_LOCAL_ROUNDS", [](const char *e, Tuning &t) { t.local_rounds = std::max(1, atoi(e)); }},
+    {"BBME_WIDE_THRESHOLD", [](const char *e, Tuning &t) { t.wide_threshold = std::max(4, atoi(e)); }},
+    {"BBME_MEMO", [](const char *e, Tuning &t) { t.use_memo = atoi(e) != 0; }},
+    {"BBME_MEMO_FORWARD", [](const char *e, Tuning &t) { t.memo_forward = atoi(e) != 0; }},
+    {"BBME_MEMO_MIN_B", [](const char *e, Tuning &t) { t.memo_min_block = std::max(8, atoi(e)); }},
+    {"BBME_XCD_REMAP", [](const char *e, Tuning &t) { t.xcd_remap = atoi(e) != 0; }},
+    {"BBME_LOOSE_PLAN", [](const char *, Tuning &t) { t.loose_plan = true; }},                // presence, whatever the value
+    {"BBME_RELAX_RULE", [](const char *e, Tuning &t) {                                        // leading fields; the rest keep their defaults
+         sscanf(e, "%lld,%d,%d,%d", &t.relax_min_blocks, &t.relax_max_b, &t.relax_s1, &t.relax_s2);
+     }},
+};
+
+Tuning read_tuning(int pairs)
+{
+    Tuning t;
+    // a batched context is throughput-bound (every launch carries several pairs): the chain form of pass 1, which trades
+    // instructions for latency, only pays on its small grids (24 pairs as 4 x 6: 53.7 -> 55.0 Mblocks/s)
+    if (pairs > 1) t.pass1_lanes_max = 40000;
+    for (const auto &k : kKnobs)
+        if (const char *e = getenv(k.name)) k.parse(e, t);
+    return t;
+}
+
+}  // namespace
+
+struct bbme_ctx {
+    bbme_params params{};
+    Geometry geom{};
+    int device = 0;
+    int batch = 1;                                // independent frame pairs this context holds (blockIdx.y of every kernel)
+    Tuning tune;
+    size_t flow_stride = 0;                       // floats from pair to pair in `flow`
+    uint32_t list_stride = 0, own_stride = 0;     // words from pair to pair in list[] / own
+    size_t raw_stride = 0;                        // bytes from pair to pair in raw[]
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    std::vector<Level> lv;
+    DevBuf<float> flow;                           // dense padded H0 x W0 float2
+    DevBuf<uint32_t> list[2];
+    DevBuf<uint8_t> flags[2];                     // dirty flags of the regulariser, one byte per block, all zero between sweeps
+    size_t flag_bytes = 0;
+    DevBuf<uint32_t> own;                         // ownership counters of the solver, one word per block
+    uint32_t own_pitch = 0;                       // transposed layout: 32 residue classes of own_pitch words
+    DevBuf<uint32_t> counters;                    // 64 words (RegArgs::counters)
+    // SAD memo of the regulariser's chain form (bbme_kernels.hpp, "SAD memo"): nine (MV, SAD) words per block at b >= 8
+    DevBuf<unsigned long long> memo;
+    uint32_t memo_stride = 0;                     // words from pair to pair
+    size_t memo_blocks = 0;                       // blocks per pair it has room for
+    int memo_level = -1, memo_block = 0;          // the (level, block size) its slots describe; block 0 = nothing
     uint64_t frames_mask = 0;                     // bit p: pair p has frames (bbme_estimate needs every pair's)
     // chain context (bbme_create_chain): batch + 1 frame SLOTS in one allocation per level (Level::img1; img2 = img1 + one plane
     // stride, so pair p reads slots p and p + 1).  frames_mask then has one bit per slot 0 .. 63, last_slot is slot 64.
@@ -111,36 +253,11 @@ struct bbme_ctx {
         const int n = chain ? batch + 1 : batch;
         return frames_mask == (n >= 64 ? ~0ull : (1ull << n) - 1ull) && (n <= 64 || last_slot);
     }
-    double *epe_scratch = nullptr;                // partial sums + counts of bbme_calculate_mse_device (allocated on first use)
-    int local_rounds = 8;                         // k_reg_iter: heavy rounds of a tile per launch; BBME_LOCAL_ROUNDS
-    int wide_threshold = 16;                      // solver: queue length above which a round takes the throughput form; BBME_WIDE_THRESHOLD
-    int solve_waves = 4;                          // waves per solver workgroup (1, 2 or 4); BBME_SOLVE_WAVES
-    bool solve_share = true;                      // k_reg_solve: idle waves of a workgroup take a sibling's surplus; BBME_SOLVE_SHARE=0
-    int solve_wgs = 256;                          // most workgroups of k_reg_solve (4 independent waves each); r04: 256 measured 1.5 % ahead of 128 (one wave per SIMD)
-    int xcd_remap = 1;                            // XCD-aware block order in k_search_fast; BBME_XCD_REMAP
-    bool loose_plan = false;                      // the round-2 search plan without rim rounds; BBME_LOOSE_PLAN
-    long long relax_min_blocks = 300000;          // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (launch_sweep)
-    int relax_max_b = 2, relax_s1 = 1, relax_s2 = 0;
     bool jacobi = false;                          // opt-in, not bit-exact: Jacobi sweeps (pass 1 only); bbme_set_regularizer_mode
     bool raster_search = false;                   // MF::find_min_block (:246-294) instead of the spiral search; bbme_set_search_mode
-    bool force_generic_search = false;            // BBME_GENERIC_SEARCH=1: use k_search_generic everywhere
-    bool use_graph = true;
     bool relax = true;                            // relaxation launches (k_reg_iter) on large grids of small blocks; bbme_set_relaxation
-    bool speculate = true;                        // overlap every level's search with the coarser level's late sweeps; BBME_SPECULATE
     hipStream_t side_stream = nullptr;            // the speculative searches
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    int spec_per_cu = 0;                          // BBME_SPEC_WGS_PER_CU; 0 = by the coarser level's block size (spec_lds_for)
-    // LDS per workgroup of a speculative search launch beside the late sweeps of `coarser_block`-sized level: the occupancy cap
-    int spec_per_cu_l0 = 0;                       // second value of BBME_SPEC_WGS_PER_CU="other,level0": the level-0 launch's own cap
-    size_t spec_lds_for(int coarser_block, int level = 1) const
-    {
-        // (r04: 7, not 6, since the level-0 search -- not the level-1 sweeps beside it, shorter now -- is what the level waits for:
-        //  cfg3 1.494 -> 1.470 ms; 8 and more cost the sweeps more than the search gains)
-        int per_cu = spec_per_cu > 0 ? spec_per_cu : (coarser_block >= 16 ? 7 : 24);
-        if (level == 0 && spec_per_cu_l0 > 0) per_cu = spec_per_cu_l0;
-        return ((size_t)(160 - 40) * 1024 / per_cu) / 256 * 256;
-    }
-    double spec_min_absdiffs = 8e9;               // levels with less search work are not speculated; BBME_SPEC_MIN_GABS
     hipGraphExec_t graph_exec[2] = {nullptr, nullptr};   // the captured launch sequence of each direction, captured on first use
     // bbme_set_direction: BBME_DIR_BACKWARD exchanges the two plane bases in the arguments of every kernel that reads planes for
     // an estimate or a result (plane1 / plane2 below); setters, the chain roll and the plane accessors stay physical
@@ -148,29 +265,28 @@ struct bbme_ctx {
     // A context keeps ONE graph with the speculative search's forked branch: a second forked graph on the same context replays
     // 0.9 ms slower at 4K whichever direction it is (2.4 ms against 1.43-1.47; 1.57 unforked; profiles/r08_bidirectional.txt).
     // FORWARD's graph always speculates; BACKWARD's only while the context has no FORWARD graph, and capturing FORWARD drops a
-    // forked BACKWARD graph (captured again, unforked, on its next use).  BBME_SPECULATE_BOTH_GRAPHS=1: both forked (measurements).
+    // forked BACKWARD graph (captured again, unforked, on its next use).  Tuning::fork_both: both forked (measurements).
     bool graph_forked[2] = {false, false};
-    bool fork_both = false;
-    const uint8_t *plane1(const Level &L) const { return direction ? L.img2 : L.img1; }
-    const uint8_t *plane2(const Level &L) const { return direction ? L.img1 : L.img2; }
+    const uint8_t *plane1(const Level &L) const { return direction ? L.img2 : L.img1.get(); }
+    const uint8_t *plane2(const Level &L) const { return direction ? L.img1.get() : L.img2; }
     // bbme_estimate_bidirectional: level 0's final grid of the backward half, every pair (bwd_stride words apart), and whether
     // it and the forward grid still describe the frames the context holds
-    mv_t *bwd_cells = nullptr;
+    DevBuf<mv_t> bwd_cells;
     uint32_t bwd_stride = 0;
     bool fields_valid = false;
-    uint8_t *fb_mask = nullptr;                   // bbme_get_consistency_host: a packed CH x CW mask before its download
-    unsigned long long *fb_stats = nullptr;       // consistency statistics: 4 words per pair, then the partials of k_fb_consistency of
-                                                  // bbme_consistency_stats (every pair) and of bbme_cells_consistency_device (one pair)
     bool profiling = false;
     float t_total = 0, t_search = 0, t_reg = 0, t_expand = 0, t_search0 = 0;
-    uint8_t *raw[2] = {nullptr, nullptr};         // bbme_set_frames_host: the unpadded frames in HBM (allocated on first use)
-    float *sub = nullptr;                         // bbme_get_subsampled_flow_host: the packed field before its download
-    size_t sub_bytes = 0;                         // (allocated on first use, grown to the largest asked for)
-    hipEvent_t ev_sub = nullptr;                  // bbme_subsampled_flow_device, bbme_motion_compensate_device: orders the caller's
-                                                  // stream behind the ctx stream
-    uint8_t *mc_plane = nullptr;                  // bbme_get_motion_compensated_host: a level-0-sized plane before its download
-    unsigned long long *mc_stats = nullptr;       // bbme_compensation_error: 4 words per pair, then the partials of k_motion_compensate
-                                                  // (both allocated on first use)
+    hipEvent_t ev_sub = nullptr;                  // stream_behind_ctx: orders a caller's stream behind the ctx stream
+    // scratch of single entry points, allocated on their first use (DevBuf::ensure)
+    DevBuf<double> epe_scratch;                   // partial sums + counts of bbme_calculate_mse_device
+    DevBuf<uint8_t> fb_mask;                      // bbme_get_consistency_host: a packed CH x CW mask before its download
+    DevBuf<unsigned long long> fb_stats;          // consistency statistics: 4 words per pair, then the partials of k_fb_consistency of
+                                                  // bbme_consistency_stats (every pair) and of bbme_cells_consistency_device (one pair)
+    DevBuf<uint8_t> raw[2];                       // bbme_set_frames_host: the unpadded frames in HBM
+    DevBuf<float> sub;                            // bbme_get_subsampled_flow_host: the packed field before its download (grown to
+                                                  // the largest asked for)
+    DevBuf<uint8_t> mc_plane;                     // bbme_get_motion_compensated_host: a level-0-sized plane before its download
+    DevBuf<unsigned long long> mc_stats;          // bbme_compensation_error: 4 words per pair, then the partials of k_motion_compensate
 };
 
 namespace {
@@ -231,6 +347,47 @@ void drop_graph(bbme_ctx *c)
     c->graph_forked[0] = c->graph_forked[1] = false;
 }
 
+// What every setter does that changes the launch sequence (other kernels, another stream): the graphs may still be running
+int settle_and_drop_graphs(bbme_ctx *c)
+{
+    HIP_TRY(hipSetDevice(c->device));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    drop_graph(c);
+    return BBME_OK;
+}
+
+// The stream an entry point enqueues on: the context's own for a null `hip_stream`, else the caller's, ordered behind whatever
+// the context's stream holds at this point
+int stream_behind_ctx(bbme_ctx *c, void *hip_stream, hipStream_t *stream)
+{
+    *stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (*stream == c->stream) return BBME_OK;
+    if (!c->ev_sub) HIP_TRY(hipEventCreateWithFlags(&c->ev_sub, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c->ev_sub, c->stream));
+    HIP_TRY(hipStreamWaitEvent(*stream, c->ev_sub, 0));
+    return BBME_OK;
+}
+
+// An optional window {x0, y0, w, h} inside limit_w x limit_h: the plane of `level`, or (level < 0) a grid of cells.  Touches no device.
+int check_window(const int *window, int limit_w, int limit_h, const char *what, int level)
+{
+    if (!window || (window[0] >= 0 && window[1] >= 0 && window[2] >= 1 && window[3] >= 1 &&
+                    (long long)window[0] + window[2] <= limit_w && (long long)window[1] + window[3] <= limit_h))
+        return BBME_OK;
+    char where[32] = "cells";
+    if (level >= 0) snprintf(where, sizeof where, "plane of level %d", level);
+    return bbme::fail(BBME_ERR_INVALID, "%s: window (%d, %d, %d, %d) is not inside the %dx%d %s", what, window[0], window[1],
+                      window[2], window[3], limit_w, limit_h, where);
+}
+
+// wx0 .. wy1 of McArgs / FbArgs: the window, or the whole full_w x full_h
+template <class Args>
+void set_window(Args &a, const int *window, int full_w, int full_h)
+{
+    a.wx0 = window ? window[0] : 0; a.wy0 = window ? window[1] : 0;
+    a.wx1 = window ? window[0] + window[2] : full_w; a.wy1 = window ? window[1] + window[3] : full_h;
+}
+
 // The regulariser's waves leave at a round cap instead of spinning for ever (RegArgs::round_cap); a sweep that hit
 // it has not reached the fixed point and its field must not be handed out as a result.  Waits for the stream.  On
 // that path the solver's ownership words and counters are stale too: cleared, so that the context stays usable.
@@ -252,6 +409,35 @@ int check_converged(bbme_ctx *c)
                                       "the reference's and has been discarded");
 }
 
+// What every probe starts with.  They own their buffers and events (DevBuf, DevEvent): an error return releases them.
+const char *const kProbe = "probe buffers";
+
+int probe_device(int device)
+{
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
+        return bbme::fail(BBME_ERR_HIP, "no HIP device %d", device);
+    HIP_TRY(hipSetDevice(device));
+    return BBME_OK;
+}
+
+// launch(0), launch(1) on the null stream: the milliseconds the second one took
+template <class Launch>
+int time_second_launch(Launch &&launch, float *ms)
+{
+    DevEvent e0, e1;
+    HIP_TRY(hipEventCreate(&e0.ev));
+    HIP_TRY(hipEventCreate(&e1.ev));
+    for (int rep = 0; rep < 2; ++rep) {
+        HIP_TRY(hipEventRecord(e0, 0));
+        launch(rep);
+        HIP_TRY(hipEventRecord(e1, 0));
+        HIP_TRY(hipEventSynchronize(e1));
+    }
+    HIP_TRY(hipEventElapsedTime(ms, e0, e1));
+    return BBME_OK;
+}
+
 // ---- launches ---------------------------------------------------------------------------
 
 // hipFuncAttributeMaxDynamicSharedMemorySize belongs to a kernel, not to a context: every context of the process that launches
@@ -271,29 +457,14 @@ int raise_lds_limit(int device, const void *kernel, size_t bytes)
     return BBME_OK;
 }
 
-const void *search_generic_kernel(int block)
+// The one place a run-time block size becomes a template argument: f(std::integral_constant<int, B>) for the B of `Bs` that
+// equals `b`, and its return code.
+template <int... Bs, class F>
+int with_block(int b, F &&f)
 {
-    switch (block) {
-    case 2:  return reinterpret_cast<const void *>(&k_search_generic<2>);
-    case 4:  return reinterpret_cast<const void *>(&k_search_generic<4>);
-    case 8:  return reinterpret_cast<const void *>(&k_search_generic<8>);
-    case 16: return reinterpret_cast<const void *>(&k_search_generic<16>);
-    case 32: return reinterpret_cast<const void *>(&k_search_generic<32>);
-    default: return reinterpret_cast<const void *>(&k_search_generic<64>);
-    }
-}
-
-const void *search_fast_kernel(int block)
-{
-    if (block == 16) return reinterpret_cast<const void *>(&k_search_fast<16, 1>);
-    if (block == 32) return reinterpret_cast<const void *>(&k_search_fast<32, 1>);
-    return reinterpret_cast<const void *>(&k_search_fast<8, 1>);
-}
-
-template <int B>
-void launch_search_t(const SearchArgs &a, int nblocks, int batch, size_t lds, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_search_generic<B>, dim3(nblocks, batch), dim3(64), lds, s, a);
+    int rc = BBME_OK;
+    const bool hit = ((b == Bs && ((rc = f(std::integral_constant<int, Bs>{})), true)) || ...);
+    return hit ? rc : bbme::fail(BBME_ERR_UNSUPPORTED, "block size %d", b);
 }
 
 // Where the search of `level` takes its predictions from (copyMVs, :828-843), by mode:
@@ -327,6 +498,13 @@ int set_prediction_source(bbme_ctx *c, int level, int mode, Args &a)
     return BBME_OK;
 }
 
+// Level::tasks2 ..: the plan whose rounds have 128 strips, for two waves per macroblock
+void use_two_wave_plan(FastSearchArgs &a, const Level &L)
+{
+    a.tasks = L.tasks2; a.rounds = L.rounds2; a.nrounds = L.nrounds2; a.lane_ranks = L.lane_ranks2;
+    a.stage_rpp = 128u / ((uint32_t)(L.fast_pitch_dw + 3) / 4);
+}
+
 // `lds_floor`: dynamic LDS to ask for at least -- the speculative launch pads its workgroups so that only
 // ctx::spec_wgs_per_cu of them fit a CU and the regulariser's kernels beside it still find wave slots, registers and LDS.
 int launch_search_fast(bbme_ctx *c, int level, int mode, hipStream_t stream, size_t lds_floor)
@@ -350,55 +528,41 @@ int launch_search_fast(bbme_ctx *c, int level, int mode, hipStream_t stream, siz
     const int nblocks = (L.width / L.block) * (L.height / L.block);
     a.nblocks = nblocks;
     a.cols_magic = (uint64_t)nblocks * (uint64_t)a.cols < (1ull << 32) ? (uint32_t)(((1ull << 32) + (uint64_t)a.cols - 1) / (uint64_t)a.cols) : 0u;
-    a.xcd_remap = c->xcd_remap;
-    const int grid = c->xcd_remap ? ((nblocks + 7) / 8) * 8 : nblocks;
+    a.xcd_remap = c->tune.xcd_remap;
+    int grid = c->tune.xcd_remap ? ((nblocks + 7) / 8) * 8 : nblocks;
     const size_t lds = std::max(L.fast_lds_bytes, lds_floor);
     a.fix_count = L.fix_count;
     a.s_fix_list = L.small_stride;
     const unsigned P = (unsigned)c->batch;
     // a level with fewer macroblocks than the chip has SIMDs: one wave per block leaves most SIMDs idle and every busy one
     // with a single wave, so the launch lasts as long as one block does -- two waves share each block then
-    if (mode == kSearchPlain && L.tasks2 && nblocks <= c->split_blocks && (L.split_pays || c->split_forced)) {
-        a.tasks = L.tasks2; a.rounds = L.rounds2; a.nrounds = L.nrounds2; a.lane_ranks = L.lane_ranks2;
-        a.stage_rpp = 128u / ((uint32_t)(L.fast_pitch_dw + 3) / 4);
-        if (L.block == 16) hipLaunchKernelGGL((k_search_fast<16, 2>), dim3(grid, P), dim3(128), lds, stream, a);
-        else if (L.block == 32) hipLaunchKernelGGL((k_search_fast<32, 2>), dim3(grid, P), dim3(128), lds, stream, a);
-        else hipLaunchKernelGGL((k_search_fast<8, 2>), dim3(grid, P), dim3(128), lds, stream, a);
-        HIP_TRY(hipGetLastError());
-        return BBME_OK;
-    }
-    if (mode == kSearchFixup && a.coarse) {
+    const bool split = L.tasks2 && nblocks <= c->tune.split_blocks && (L.split_pays || c->tune.split_forced);
+    bool two_waves = mode == kSearchPlain && split;
+    const bool list = mode == kSearchFixup && a.coarse;
+    if (list) {
         // list the blocks whose prediction changed, then search those (k_fixup_list, k_search_list)
         a.mode = kSearchPlain;
-        hipLaunchKernelGGL(k_fixup_list, dim3((nblocks + 255) / 256, P), dim3(256), 0, stream, a, L.block, L.fix_count, L.fix_list);
-        const int lgrid = std::max(64, nblocks / 4);
+        hipLaunchKernelGGL(k_fixup_list, dim3((nblocks + 255) / 256, P), dim3(256), 0, stream, a, L.block, L.fix_count.get(), L.fix_list.get());
+        grid = std::max(64, nblocks / 4);
         // two waves per listed block on the levels that are searched with two waves per block anyway (r04): the list is ONE
         // generation of waves, and on a level of 8 160 blocks (~1 200 listed) halves fill the chip where wholes leave three SIMDs
         // in four idle -- 30.4 -> 24.8 us.  Level 0 (~5 000 listed) stays with one wave per block: at two, the 123 registers of
         // the 128-lane form allow four waves per SIMD, 10 000 halves are two and a half generations, 58.8 -> 65.8 us.
-        if (c->list_split && L.tasks2 && nblocks <= c->split_blocks && (L.split_pays || c->split_forced)) {
-            a.tasks = L.tasks2; a.rounds = L.rounds2; a.nrounds = L.nrounds2; a.lane_ranks = L.lane_ranks2;
-            a.stage_rpp = 128u / ((uint32_t)(L.fast_pitch_dw + 3) / 4);
-            if (L.block == 16) hipLaunchKernelGGL((k_search_list<16, 2>), dim3(lgrid, P), dim3(128), lds, stream, a, L.fix_count, L.fix_list);
-            else if (L.block == 32) hipLaunchKernelGGL((k_search_list<32, 2>), dim3(lgrid, P), dim3(128), lds, stream, a, L.fix_count, L.fix_list);
-            else hipLaunchKernelGGL((k_search_list<8, 2>), dim3(lgrid, P), dim3(128), lds, stream, a, L.fix_count, L.fix_list);
-            HIP_TRY(hipGetLastError());
-            return BBME_OK;
-        }
-        if (L.block == 16) hipLaunchKernelGGL(k_search_list<16>, dim3(lgrid, P), dim3(64), lds, stream, a, L.fix_count, L.fix_list);
-        else if (L.block == 32) hipLaunchKernelGGL(k_search_list<32>, dim3(lgrid, P), dim3(64), lds, stream, a, L.fix_count, L.fix_list);
-        else hipLaunchKernelGGL(k_search_list<8>, dim3(lgrid, P), dim3(64), lds, stream, a, L.fix_count, L.fix_list);
-        HIP_TRY(hipGetLastError());
-        return BBME_OK;
+        two_waves = c->tune.list_split && split;
     }
-    if (L.block == 16)
-        hipLaunchKernelGGL((k_search_fast<16, 1>), dim3(grid, P), dim3(64), lds, stream, a);
-    else if (L.block == 32)
-        hipLaunchKernelGGL((k_search_fast<32, 1>), dim3(grid, P), dim3(64), lds, stream, a);
-    else
-        hipLaunchKernelGGL((k_search_fast<8, 1>), dim3(grid, P), dim3(64), lds, stream, a);
-    HIP_TRY(hipGetLastError());
-    return BBME_OK;
+    if (two_waves) use_two_wave_plan(a, L);
+    // the one launch site: the listed blocks (k_search_list) or the whole level (k_search_fast), W waves per block
+    return with_block<8, 16, 32>(L.block, [&](auto B) {
+        auto launch = [&](auto W) {
+            constexpr int kB = decltype(B)::value, kW = decltype(W)::value;
+            if (list) hipLaunchKernelGGL((k_search_list<kB, kW>), dim3(grid, P), dim3(64 * kW), lds, stream, a, L.fix_count.get(), L.fix_list.get());
+            else hipLaunchKernelGGL((k_search_fast<kB, kW>), dim3(grid, P), dim3(64 * kW), lds, stream, a);
+        };
+        if (two_waves) launch(std::integral_constant<int, 2>{});
+        else launch(std::integral_constant<int, 1>{});
+        HIP_TRY(hipGetLastError());
+        return (int)BBME_OK;
+    });
 }
 
 int launch_search(bbme_ctx *c, int level, int mode = kSearchPlain, hipStream_t stream = nullptr, size_t lds_floor = 0)
@@ -406,7 +570,7 @@ int launch_search(bbme_ctx *c, int level, int mode = kSearchPlain, hipStream_t s
     Level &L = c->lv[level];
     if (!stream) stream = c->stream;
     int rc;
-    if (L.fast && !c->force_generic_search && !c->raster_search) {
+    if (L.fast && !c->tune.force_generic_search && !c->raster_search) {
         rc = launch_search_fast(c, level, mode, stream, lds_floor);
     } else {
         SearchArgs a{};
@@ -420,31 +584,25 @@ int launch_search(bbme_ctx *c, int level, int mode = kSearchPlain, hipStream_t s
         a.pitch_dw = L.pitch_dw;
         const int nblocks = (L.width / L.block) * (L.height / L.block);
         const size_t lds = std::max(L.lds_bytes, lds_floor);
-        switch (L.block) {
-        case 2:  launch_search_t<2>(a, nblocks, c->batch, lds, stream); break;
-        case 4:  launch_search_t<4>(a, nblocks, c->batch, lds, stream); break;
-        case 8:  launch_search_t<8>(a, nblocks, c->batch, lds, stream); break;
-        case 16: launch_search_t<16>(a, nblocks, c->batch, lds, stream); break;
-        case 32: launch_search_t<32>(a, nblocks, c->batch, lds, stream); break;
-        case 64: launch_search_t<64>(a, nblocks, c->batch, lds, stream); break;
-        default: return bbme::fail(BBME_ERR_UNSUPPORTED, "block size %d", L.block);
-        }
-        HIP_TRY(hipGetLastError());
-        rc = BBME_OK;
+        rc = with_block<2, 4, 8, 16, 32, 64>(L.block, [&](auto B) {
+            hipLaunchKernelGGL(k_search_generic<B()>, dim3(nblocks, c->batch), dim3(64), lds, stream, a);
+            HIP_TRY(hipGetLastError());
+            return (int)BBME_OK;
+        });
     }
     if (rc == BBME_OK && mode != kSearchSpeculative) { L.cur_grid = L.small[0]; L.cur_block = L.block; }
     return rc;
 }
 
 template <int BS>
-void launch_sweep_t(RegArgs a, uint8_t *const flags[2], int relax_steps, int max_solve_wgs, int solve_waves, bool jacobi,
-                    long long lanes_max, long long fine_max, int strip, bool lazy_ok, unsigned P, hipStream_t s)
+void launch_sweep_t(RegArgs a, uint8_t *const (&flags)[2], int relax_steps, bool jacobi, const Tuning &t, unsigned P, hipStream_t s)
 {
+    const int solve_waves = t.solve_waves;
     constexpr int LPB = RegCfg<BS>::LPB;
     const long long blocks = (long long)a.rows * a.cols;
     const int grid1 = (int)((blocks * LPB + 255) / 256);
     // a multiple of 8 workgroups: one share per XCD (k_reg_solve's bands)
-    const int grid2 = (int)((std::min<long long>(max_solve_wgs, (blocks + 63) / 64) + 7) / 8 * 8);
+    const int grid2 = (int)((std::min<long long>(t.solve_wgs, (blocks + 63) / 64) + 7) / 8 * 8);
     // pass 1 marks flags[0]; relaxation step i consumes flags[i & 1] and marks the other; the solver
     // consumes what the last step marked.  Every flag is zero again afterwards.
     // grids up to ~130 000 blocks: the chain form of pass 1 (a third of the instructions per wave; 16 lanes per block fill the
@@ -456,7 +614,7 @@ void launch_sweep_t(RegArgs a, uint8_t *const flags[2], int relax_steps, int max
                 return;
             }
         }
-        if (BS <= 16 && blocks <= lanes_max)               // (b >= 32: a lane would walk 32+ rows -- 13 against 6 us at b = 32)
+        if (BS <= 16 && blocks <= t.pass1_lanes_max)               // (b >= 32: a lane would walk 32+ rows -- 13 against 6 us at b = 32)
             hipLaunchKernelGGL(k_reg_pass1_lanes<BS>, dim3((unsigned)((blocks * 16 + 255) / 256), P), dim3(256), 0, s, a);
         else {
             if constexpr (BS <= 4) {
@@ -468,8 +626,8 @@ void launch_sweep_t(RegArgs a, uint8_t *const flags[2], int relax_steps, int max
                 // ... and, for any context, the sweeps with a relaxation launch behind pass 1: the strip test alone (level 0: 5.1 us at
                 // b = 4, 6.5 at b = 2, against 15.5 / 18.4 for the whole of k_reg_pass1), the blocks that need their images flagged for
                 // the relaxation's first round (RegArgs::lazy)
-                a.lazy = (lazy_ok && relax_steps > 0 && a.flag_next != nullptr) ? 1 : 0;
-                const bool strip_form = a.lazy || (strip < 0 ? P > 1 : strip != 0);
+                a.lazy = (t.pass1_lazy && relax_steps > 0 && a.flag_next != nullptr) ? 1 : 0;
+                const bool strip_form = a.lazy || (t.pass1_strip < 0 ? P > 1 : t.pass1_strip != 0);
                 if (strip_form && a.cols % 4 == 0 && a.cols >= 12) {
                     hipLaunchKernelGGL(k_reg_pass1_strip<BS>, dim3((unsigned)((blocks / 4 + 255) / 256), P), dim3(256), 0, s, a);
                     return;
@@ -499,12 +657,12 @@ void launch_sweep_t(RegArgs a, uint8_t *const flags[2], int relax_steps, int max
     a.memo_init = 0;                                       // pass 1 has written every slot
     if constexpr (BS >= 8) {
         if (a.memo) {
-            if (blocks <= fine_max) hipLaunchKernelGGL((k_reg_solve<BS, 4, true>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
+            if (blocks <= t.scan_fine_max) hipLaunchKernelGGL((k_reg_solve<BS, 4, true>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
             else hipLaunchKernelGGL((k_reg_solve<BS, 16, true>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
             return;
         }
     }
-    if (blocks <= fine_max) hipLaunchKernelGGL((k_reg_solve<BS, 4>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
+    if (blocks <= t.scan_fine_max) hipLaunchKernelGGL((k_reg_solve<BS, 4>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
     else hipLaunchKernelGGL((k_reg_solve<BS, 16>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
 }
 
@@ -525,7 +683,7 @@ int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false)
     a.old_grid = L.cur_grid;
     a.old_cols = a.cols >> a.old_shift;
     // sweeps at the level's own block size ping-pong in small[], the others in big[] (see Level)
-    mv_t *const *pool = (b == L.block) ? L.small : L.big;
+    const DevBuf<mv_t> *pool = (b == L.block) ? L.small : L.big;
     a.est = (L.cur_grid == pool[0]) ? pool[1] : pool[0];
     // lambda = (float)(B/2), doubled at every halving (motion_framework.cpp:73,95,151); times
     // (float)lambda_multiplier as at :607
@@ -537,49 +695,45 @@ int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false)
     a.own_pitch = c->own_pitch;
     a.s_plane = L.plane_stride; a.s_old = L.grid_stride(a.old_grid); a.s_est = L.grid_stride(a.est);
     a.s_list = c->list_stride; a.s_own = c->own_stride; a.s_flag = (uint32_t)c->flag_bytes;
-    a.local_rounds = c->local_rounds;
-    a.wide_threshold = (uint32_t)c->wide_threshold;
+    a.local_rounds = c->tune.local_rounds;
+    a.wide_threshold = (uint32_t)c->tune.wide_threshold;
     // every round of a wave either empties part of its queue or follows a real change, and a change can only travel
     // along the raster dependency chain (< 2 * rows + cols blocks): the cap is an exit every wave reaches even if
     // that reasoning were wrong; hitting it raises counters[5] and the result is refused (BBME_ERR_STATE)
-    a.round_cap = c->round_cap > 0 ? (uint32_t)c->round_cap : 64u * (uint32_t)(2 * a.rows + a.cols + 16);
+    a.round_cap = c->tune.round_cap > 0 ? (uint32_t)c->tune.round_cap : 64u * (uint32_t)(2 * a.rows + a.cols + 16);
     a.counters = c->counters;
     a.stats = stats ? 1 : 0;
-    a.share = c->solve_share ? 1 : 0;
+    a.share = c->tune.solve_share ? 1 : 0;
     // the SAD memo: sweeps at b >= 8 whose pass 1 runs in the chain form (it is what fills the slots); the first sweep at a
     // (level, block size) finds nothing in it and rewrites every slot
     const long long nblk_memo = (long long)a.rows * a.cols;
-    if (c->use_memo && c->memo && !c->jacobi && b >= c->memo_min_block && nblk_memo <= c->pass1_lanes_max && (size_t)nblk_memo <= c->memo_blocks &&
+    if (c->tune.use_memo && c->memo && !c->jacobi && b >= c->tune.memo_min_block && nblk_memo <= c->tune.pass1_lanes_max && (size_t)nblk_memo <= c->memo_blocks &&
         L.width <= 8192 && L.height <= 8192) {             // (group_sads packs a vector into 2 x 14 bits)
         a.memo = c->memo;
         a.s_memo = c->memo_stride;
         a.memo_init = !(c->memo_level == level && c->memo_block == b);
-        a.memo_forward = c->memo_forward ? 1 : 0;
+        a.memo_forward = c->tune.memo_forward ? 1 : 0;
         c->memo_level = level; c->memo_block = b;
     }
     // relaxation launches (k_reg_iter, 8 local rounds per tile): one more launch (>= 5 us), which only the sweeps with
     // heavy first generations repay -- measured on cfg3 / cfg4 / cfg2: large grids of small blocks, one launch per sweep
     const long long nblk = (long long)a.rows * a.cols;
-    int steps = c->relax_steps;
+    int steps = c->tune.relax_steps;
     if (steps < 0) {
-        // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (tuning knob, read by bbme_create_batch)
+        // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (Tuning)
         // (r03: no relaxation launch in front of the second sweep at a block size -- it changes little, and the launch cost more
         // than it took off the solver: 1.760 -> 1.735 ms per cfg3 pair; r04: nor at 4 x 4 -- with the memo-less solver of this
         // round the chain form takes those sweeps' first generations faster than a 40 us launch does: cfg3 1.566 -> 1.547 ms,
         // cfg4 1.605 -> 1.585 ms, interleaved medians of 5 / 4 runs; and, once the solver's waves shared their queues, only on
         // grids of >= 300 000 blocks: cfg3 1.523 -> 1.496, cfg2 0.699 -> 0.680, cfg4 1.611 -> 1.603, reference literals 1.336 -> 1.331)
-        steps = (c->relax && nblk >= c->relax_min_blocks && b <= c->relax_max_b) ? (mult == 1 ? c->relax_s1 : c->relax_s2) : 0;
+        steps = (c->relax && nblk >= c->tune.relax_min_blocks && b <= c->tune.relax_max_b) ? (mult == 1 ? c->tune.relax_s1 : c->tune.relax_s2) : 0;
     }
-    switch (b) {
-    case 2:  launch_sweep_t<2>(a, c->flags, steps, c->solve_wgs, c->solve_waves, c->jacobi, c->pass1_lanes_max, c->scan_fine_max, c->pass1_strip, c->pass1_lazy, (unsigned)c->batch, c->stream); break;
-    case 4:  launch_sweep_t<4>(a, c->flags, steps, c->solve_wgs, c->solve_waves, c->jacobi, c->pass1_lanes_max, c->scan_fine_max, c->pass1_strip, c->pass1_lazy, (unsigned)c->batch, c->stream); break;
-    case 8:  launch_sweep_t<8>(a, c->flags, steps, c->solve_wgs, c->solve_waves, c->jacobi, c->pass1_lanes_max, c->scan_fine_max, c->pass1_strip, c->pass1_lazy, (unsigned)c->batch, c->stream); break;
-    case 16: launch_sweep_t<16>(a, c->flags, steps, c->solve_wgs, c->solve_waves, c->jacobi, c->pass1_lanes_max, c->scan_fine_max, c->pass1_strip, c->pass1_lazy, (unsigned)c->batch, c->stream); break;
-    case 32: launch_sweep_t<32>(a, c->flags, steps, c->solve_wgs, c->solve_waves, c->jacobi, c->pass1_lanes_max, c->scan_fine_max, c->pass1_strip, c->pass1_lazy, (unsigned)c->batch, c->stream); break;
-    case 64: launch_sweep_t<64>(a, c->flags, steps, c->solve_wgs, c->solve_waves, c->jacobi, c->pass1_lanes_max, c->scan_fine_max, c->pass1_strip, c->pass1_lazy, (unsigned)c->batch, c->stream); break;
-    default: return bbme::fail(BBME_ERR_UNSUPPORTED, "block size %d", b);
-    }
-    HIP_TRY(hipGetLastError());
+    uint8_t *const flags[2] = {c->flags[0], c->flags[1]};
+    if (int rc = with_block<2, 4, 8, 16, 32, 64>(b, [&](auto B) {
+            launch_sweep_t<B()>(a, flags, steps, c->jacobi, c->tune, (unsigned)c->batch, c->stream);
+            HIP_TRY(hipGetLastError());
+            return (int)BBME_OK;
+        })) return rc;
     L.cur_grid = a.est;
     L.cur_block = b;
     return BBME_OK;
@@ -606,7 +760,7 @@ bool worth_speculating(const bbme_ctx *c, int level)
     const Level &L = c->lv[level];
     const double side = 2.0 * L.range + 1.0;
     const double absdiffs = (double)(L.width / L.block) * (L.height / L.block) * side * side * L.block * L.block;
-    return absdiffs >= c->spec_min_absdiffs;
+    return absdiffs >= c->tune.spec_min_absdiffs;
 }
 
 // The level loop of MF::calcMotionBlockMatching (:115-206).  With `speculate`, the search of level l-1 is started on a
@@ -636,7 +790,7 @@ int enqueue_pyramid(bbme_ctx *c, bool speculate)
             if (speculate && l > 0 && b == c->lv[l].block && b > 2 && worth_speculating(c, l - 1)) {
                 HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
                 HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-                if (int rc = launch_search(c, l - 1, kSearchSpeculative, c->side_stream, c->spec_lds_for(c->lv[l].block, l - 1))) return rc;
+                if (int rc = launch_search(c, l - 1, kSearchSpeculative, c->side_stream, c->tune.spec_lds_for(c->lv[l].block, l - 1))) return rc;
                 HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
                 speculated = true;
             }
@@ -648,12 +802,11 @@ int enqueue_pyramid(bbme_ctx *c, bool speculate)
 int profiled_pyramid(bbme_ctx *c)
 {
     // eager launches with events between sections (rank-0 diagnostics; not the timed bench path)
-    std::vector<hipEvent_t> ev;
+    std::vector<DevEvent> ev;
     auto mark = [&]() -> int {
-        hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
-        HIP_TRY(hipEventRecord(e, c->stream));
-        ev.push_back(e);
+        ev.emplace_back();
+        HIP_TRY(hipEventCreate(&ev.back().ev));
+        HIP_TRY(hipEventRecord(ev.back(), c->stream));
         return BBME_OK;
     };
     std::vector<int> kind;   // 0 search, 1 reg, 2 expand ; section i lies between ev[i] and ev[i+1]
@@ -683,7 +836,6 @@ int profiled_pyramid(bbme_ctx *c)
         else c->t_expand += ms;
     }
     HIP_TRY(hipEventElapsedTime(&c->t_total, ev.front(), ev.back()));
-    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
     return BBME_OK;
 }
 
@@ -697,18 +849,6 @@ extern "C" {
 int bbme_create(const bbme_params *params, int width, int height, int device, bbme_ctx **out)
 {
     return bbme_create_batch(params, width, height, device, 1, out);
-}
-
-static int create_context(const bbme_params *params, int width, int height, int device, int pairs, bool chain, bbme_ctx **out);
-
-int bbme_create_batch(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out)
-{
-    return create_context(params, width, height, device, pairs, false, out);
-}
-
-int bbme_create_chain(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out)
-{
-    return create_context(params, width, height, device, pairs, true, out);
 }
 
 static int create_context(const bbme_params *params, int width, int height, int device, int pairs, bool chain, bbme_ctx **out)
@@ -741,67 +881,34 @@ static int create_context(const bbme_params *params, int width, int height, int 
     if (device < 0 || device >= ndev) return bbme::fail(BBME_ERR_INVALID, "device %d of %d", device, ndev);
     HIP_TRY(hipSetDevice(device));
 
-    bbme_ctx *c = new bbme_ctx();
+    // every return below destroys the half-built context, by the one path that sets the device first
+    std::unique_ptr<bbme_ctx, int (*)(bbme_ctx *)> guard(new bbme_ctx(), bbme_destroy);
+    bbme_ctx *c = guard.get();
     c->params = *params; c->geom = g; c->device = device;
     c->batch = pairs;
     c->chain = chain;
+    c->tune = read_tuning(pairs);
     const size_t P = (size_t)pairs;
     auto round64 = [](size_t n) { return (n + 63) / 64 * 64; };
-    if (const char *e = getenv("BBME_SOLVE_SHARE")) c->solve_share = atoi(e) != 0;
-    if (const char *e = getenv("BBME_SOLVE_WGS")) c->solve_wgs = std::max(1, std::min(8192, atoi(e)));
-    if (const char *e = getenv("BBME_RELAX_STEPS")) c->relax_steps = std::max(0, std::min(64, atoi(e)));
-    if (const char *e = getenv("BBME_SOLVE_WAVES")) { const int v = atoi(e); c->solve_waves = v <= 1 ? 1 : (v == 2 ? 2 : 4); }
-    if (const char *e = getenv("BBME_TEST_ROUND_CAP")) c->round_cap = std::max(0, atoi(e));
-    // a batched context is throughput-bound (every launch carries several pairs): the chain form of pass 1, which trades
-    // instructions for latency, only pays on its small grids (24 pairs as 4 x 6: 53.7 -> 55.0 Mblocks/s)
-    if (pairs > 1) c->pass1_lanes_max = 40000;
-    if (const char *e = getenv("BBME_PASS1_LANES_MAX")) c->pass1_lanes_max = atoll(e);
-    if (const char *e = getenv("BBME_SCAN_FINE_MAX")) c->scan_fine_max = atoll(e);
-    if (const char *e = getenv("BBME_PASS1_STRIP")) c->pass1_strip = atoi(e) != 0 ? 1 : 0;
-    if (const char *e = getenv("BBME_LIST_SPLIT")) c->list_split = atoi(e) != 0;
-    if (const char *e = getenv("BBME_PASS1_LAZY")) c->pass1_lazy = atoi(e) != 0;
-    if (const char *e = getenv("BBME_SEARCH_SPLIT_BLOCKS")) { c->split_blocks = std::max(0, atoi(e)); c->split_forced = true; }
-    if (const char *e = getenv("BBME_NO_GRAPH")) c->use_graph = atoi(e) == 0;
-    if (const char *e = getenv("BBME_SPECULATE")) c->speculate = atoi(e) != 0;
-    if (const char *e = getenv("BBME_SPECULATE_BOTH_GRAPHS")) c->fork_both = atoi(e) != 0;
-    {
-        // a speculative search may keep at most this many of its (one-wave) workgroups on a CU: the rest of the CU's wave
-        // slots, registers and LDS (40 KB) stay free for the regulariser kernels it runs beside
-        // (r04, on the faster solver.  Behind a level of 16 x 16 blocks -- three late block sizes to hide the search behind -- 6-7 is
-        // best: cfg3 1.614 / 1.585 / 1.591 / 1.626 ms at 8 / 6 / 7 / 5.  Behind a level of 8 x 8 blocks the sweeps are over long
-        // before the search is, and any cap only delays it: cfg4 1.80 / 1.72 / 1.67 / 1.62 ms at 6 / 8 / 10 / 24 = uncapped.)
-        if (const char *e = getenv("BBME_SPEC_WGS_PER_CU")) {
-            c->spec_per_cu = std::max(1, std::min(32, atoi(e)));
-            if (const char *comma = strchr(e, ',')) c->spec_per_cu_l0 = std::max(1, std::min(32, atoi(comma + 1)));
-        }
-        if (const char *e = getenv("BBME_SPEC_MIN_GABS")) c->spec_min_absdiffs = atof(e) * 1e9;
-    }
-    if (const char *e = getenv("BBME_GENERIC_SEARCH")) c->force_generic_search = atoi(e) != 0;
-    if (const char *e = getenv("BBME_LOCAL_ROUNDS")) c->local_rounds = std::max(1, atoi(e));
-    if (const char *e = getenv("BBME_WIDE_THRESHOLD")) c->wide_threshold = std::max(4, atoi(e));
-    if (const char *e = getenv("BBME_MEMO")) c->use_memo = atoi(e) != 0;
-    if (const char *e = getenv("BBME_MEMO_FORWARD")) c->memo_forward = atoi(e) != 0;
-    if (const char *e = getenv("BBME_MEMO_MIN_B")) c->memo_min_block = std::max(8, atoi(e));
-    if (const char *e = getenv("BBME_XCD_REMAP")) c->xcd_remap = atoi(e) != 0;
-    c->loose_plan = getenv("BBME_LOOSE_PLAN") != nullptr;
-    if (const char *e = getenv("BBME_RELAX_RULE")) sscanf(e, "%lld,%d,%d,%d", &c->relax_min_blocks, &c->relax_max_b, &c->relax_s1, &c->relax_s2);
     c->lv.resize(nl);
-    auto cleanup_fail = [&](int rc) { bbme_destroy(c); return rc; };
     hipError_t err = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
-    if (err != hipSuccess) return cleanup_fail(bbme::fail(BBME_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(err)));
+    if (err != hipSuccess) return bbme::fail(BBME_ERR_HIP, "hipStreamCreate: %s", hipGetErrorString(err));
     c->own_stream = true;
     if ((err = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess ||
         (err = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess)
-        return cleanup_fail(bbme::fail(BBME_ERR_HIP, "creating the side stream: %s", hipGetErrorString(err)));
+        return bbme::fail(BBME_ERR_HIP, "creating the side stream: %s", hipGetErrorString(err));
     size_t max_blocks = 0;
     for (int l = 0; l < nl; ++l) {
         Level &L = c->lv[l];
+        char what[48], what_plan[48];                      // "allocating level 2: out of memory"
+        snprintf(what, sizeof what, "level %d", l);
+        snprintf(what_plan, sizeof what_plan, "search plan of level %d", l);
         L.width = g.padded_width >> l; L.height = g.padded_height >> l;
         L.block = params->block_size[l]; L.search = params->search_size[l];
         // the memo serves the sweeps at b >= memo_min_block whose grid the chain-form pass 1 takes: room for the largest of them
-        for (int b = c->memo_min_block; b <= L.block; b <<= 1) {
+        for (int b = c->tune.memo_min_block; b <= L.block; b <<= 1) {
             const size_t nb = (size_t)(L.width / b) * (L.height / b);
-            if ((long long)nb <= c->pass1_lanes_max) { c->memo_blocks = std::max(c->memo_blocks, nb); break; }
+            if ((long long)nb <= c->tune.pass1_lanes_max) { c->memo_blocks = std::max(c->memo_blocks, nb); break; }
         }
         SpiralTable sp = build_spiral(L.search, L.block);
         L.range = sp.range; L.ncand = (int)sp.dx.size();
@@ -816,32 +923,27 @@ static int create_context(const bbme_params *params, int width, int height, int 
         for (size_t i = 0; i < sp.dx.size(); ++i)
             packed[i] = ((uint32_t)(uint16_t)sp.dx[i]) | ((uint32_t)(uint16_t)sp.dy[i] << 16);
         // a chain context: the P + 1 frame slots of the level in ONE allocation, image 2 of pair p = image 1 of pair p + 1
-        const size_t img1_bytes = (chain ? P + 1 : P) * plane;
-        if ((err = hipMalloc(&L.img1, img1_bytes)) != hipSuccess ||
-            (chain ? (L.img2 = L.img1 + plane, err = hipSuccess) : (err = hipMalloc(&L.img2, P * plane))) != hipSuccess ||
-            (err = hipMalloc(&L.small[0], P * own_blocks * sizeof(mv_t))) != hipSuccess ||
-            (err = hipMalloc(&L.small[1], P * own_blocks * sizeof(mv_t))) != hipSuccess ||
-            (err = hipMalloc(&L.pred, P * own_blocks * sizeof(mv_t))) != hipSuccess ||
-            (err = hipMalloc(&L.fix_list, P * own_blocks * sizeof(uint32_t))) != hipSuccess ||
-            (err = hipMalloc(&L.fix_count, P * 64)) != hipSuccess ||
-            (err = hipMemset(L.fix_count, 0, P * 64)) != hipSuccess ||
-            (err = hipMalloc(&L.big[0], P * cells * sizeof(mv_t))) != hipSuccess ||
-            (err = hipMalloc(&L.big[1], P * cells * sizeof(mv_t))) != hipSuccess ||
-            (err = hipMalloc(&L.spiral, packed.size() * 4)) != hipSuccess ||
-            (err = hipMemset(L.img1, 0, img1_bytes)) != hipSuccess || (!chain && (err = hipMemset(L.img2, 0, P * plane)) != hipSuccess) ||
-            (err = hipMemcpy(L.spiral, packed.data(), packed.size() * 4, hipMemcpyHostToDevice)) != hipSuccess)
-            return cleanup_fail(bbme::fail(BBME_ERR_HIP, "allocating level %d: %s", l, hipGetErrorString(err)));
+        if (int rc = L.img1.alloc_zero((chain ? P + 1 : P) * plane, what)) return rc;
+        if (!chain) if (int rc = L.img2_own.alloc_zero(P * plane, what)) return rc;
+        L.img2 = chain ? L.img1 + plane : L.img2_own.get();
+        for (DevBuf<mv_t> *grid : {&L.small[0], &L.small[1], &L.pred})
+            if (int rc = grid->alloc(P * own_blocks, what)) return rc;
+        if (int rc = L.fix_list.alloc(P * own_blocks, what)) return rc;
+        if (int rc = L.fix_count.alloc_zero(P * 64 / sizeof(uint32_t), what)) return rc;    // 64 bytes per pair
+        if (int rc = L.big[0].alloc(P * cells, what)) return rc;
+        if (int rc = L.big[1].alloc(P * cells, what)) return rc;
+        if (int rc = L.spiral.upload(packed, what)) return rc;
         // the speculative search of this level pads its workgroups to this much LDS (launch_search's lds_floor)
-        const size_t spec_floor = l + 1 < nl ? c->spec_lds_for(params->block_size[l + 1], l) : 0;
+        const size_t spec_floor = l + 1 < nl ? c->tune.spec_lds_for(params->block_size[l + 1], l) : 0;
         if (!((L.block == 8 || L.block == 16 || L.block == 32) && L.range <= 63)) {
             // the generic kernel (block 4 / 64, or a range beyond the strip kernel's packed keys): its window may need more LDS
             // than a kernel gets by default (raise_lds_limit below)
             if (L.lds_bytes > 160 * 1024)
-                return cleanup_fail(bbme::fail(BBME_ERR_UNSUPPORTED, "level %d: a %dx%d block with range %d needs %zu bytes of LDS", l,
-                                               L.block, L.block, L.range, L.lds_bytes));
+                return bbme::fail(BBME_ERR_UNSUPPORTED, "level %d: a %dx%d block with range %d needs %zu bytes of LDS", l,
+                                  L.block, L.block, L.range, L.lds_bytes);
         } else {
             // the strip kernel reads rank rows dy0 .. dy0+S-1 as 4 x u16 per column group
-            SearchPlan plan = plan_search(L.range, L.block, L.block == 32 ? 8 : 16, 64, c->loose_plan);
+            SearchPlan plan = plan_search(L.range, L.block, L.block == 32 ? 8 : 16, 64, c->tune.loose_plan);
             L.fast = true;
             L.rank_pitch = sp.rank_pitch;
             L.nrounds = (int)plan.rounds.size();
@@ -850,11 +952,12 @@ static int create_context(const bbme_params *params, int width, int height, int 
             L.fast_lds_bytes = (((size_t)(L.block + 2 * L.range) * plan.pitch_dw + 3) & ~(size_t)3) * 4 + (size_t)L.block * L.block;
             // only the speculative launch adds a floor, and it is the one-wave k_search_fast (launch_search_fast); the others stay
             // at fast_lds_bytes (< 26 KB)
-            if (int rc = raise_lds_limit(device, search_fast_kernel(L.block), std::max(L.fast_lds_bytes, spec_floor)))
-                return cleanup_fail(rc);
+            if (int rc = with_block<8, 16, 32>(L.block, [&](auto B) {
+                    return raise_lds_limit(device, reinterpret_cast<const void *>(&k_search_fast<B(), 1>), std::max(L.fast_lds_bytes, spec_floor));
+                })) return rc;
             // the device copy of a plan's round codes carries, for strip rounds, where the round's rank entries start in
             // lane_ranks (<< 16, in rows of T entries); lane_ranks itself: per strip round and lane the S entries of 4 ranks
-            auto upload_plan = [&](const SearchPlan &p, int T, uint32_t **d_tasks, uint32_t **d_rounds, uint2 **d_ranks) -> int {
+            auto upload_plan = [&](const SearchPlan &p, int T, DevBuf<uint32_t> &d_tasks, DevBuf<uint32_t> &d_rounds, DevBuf<uint2> &d_ranks) -> int {
                 std::vector<uint32_t> codes(p.rounds);
                 std::vector<uint16_t> ranks;
                 uint32_t cum = 0;
@@ -880,22 +983,14 @@ static int create_context(const bbme_params *params, int width, int height, int 
                     cum += S;
                 }
                 if (ranks.empty()) ranks.assign(4, 0xffffu);
-                hipError_t e;
-                if ((e = hipMalloc(d_tasks, p.tasks.size() * 4)) != hipSuccess ||
-                    (e = hipMalloc(d_rounds, codes.size() * 4)) != hipSuccess ||
-                    (e = hipMalloc(d_ranks, ranks.size() * 2 + 64)) != hipSuccess ||
-                    (e = hipMemcpy(*d_tasks, p.tasks.data(), p.tasks.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-                    (e = hipMemcpy(*d_rounds, codes.data(), codes.size() * 4, hipMemcpyHostToDevice)) != hipSuccess ||
-                    (e = hipMemcpy(*d_ranks, ranks.data(), ranks.size() * 2, hipMemcpyHostToDevice)) != hipSuccess)
-                    return bbme::fail(BBME_ERR_HIP, "allocating search plan of level %d: %s", l, hipGetErrorString(e));
-                return BBME_OK;
+                if (int rc = d_tasks.upload(p.tasks, what_plan)) return rc;
+                if (int rc = d_rounds.upload(codes, what_plan)) return rc;
+                return d_ranks.upload(ranks, what_plan, 64);
             };
-            if ((err = hipMalloc(&L.rank_of, sp.rank_of.size() * 2 + 64)) != hipSuccess ||
-                (err = hipMemcpy(L.rank_of, sp.rank_of.data(), sp.rank_of.size() * 2, hipMemcpyHostToDevice)) != hipSuccess)
-                return cleanup_fail(bbme::fail(BBME_ERR_HIP, "allocating search plan of level %d: %s", l, hipGetErrorString(err)));
-            if (int rc = upload_plan(plan, 64, &L.tasks, &L.rounds, &L.lane_ranks)) return cleanup_fail(rc);
+            if (int rc = L.rank_of.upload(sp.rank_of, what_plan, 64)) return rc;
+            if (int rc = upload_plan(plan, 64, L.tasks, L.rounds, L.lane_ranks)) return rc;
             // shorter strips, so that the 128 lanes of two waves have a full round of them
-            SearchPlan plan2 = plan_search(L.range, L.block, 8, 128, c->loose_plan);
+            SearchPlan plan2 = plan_search(L.range, L.block, 8, 128, c->tune.loose_plan);
             L.nrounds2 = (int)plan2.rounds.size();
             // a round of strips of S rows walks S + B - 1 window rows: the split only pays where it shortens a wave's walk
             // (+-32 at B <= 16: 0.6x; +-16: the square is too small to fill 128 lanes with tall strips, 0.94-1.0x -- measured slower)
@@ -905,11 +1000,13 @@ static int create_context(const bbme_params *params, int width, int height, int 
                 return w;
             };
             L.split_pays = 5 * walk(plan2) <= 4 * walk(plan);
-            if (plan2.pitch_dw != plan.pitch_dw) return cleanup_fail(bbme::fail(BBME_ERR_STATE, "search plans disagree on the window pitch"));
-            if (int rc = upload_plan(plan2, 128, &L.tasks2, &L.rounds2, &L.lane_ranks2)) return cleanup_fail(rc);
+            if (plan2.pitch_dw != plan.pitch_dw) return bbme::fail(BBME_ERR_STATE, "search plans disagree on the window pitch");
+            if (int rc = upload_plan(plan2, 128, L.tasks2, L.rounds2, L.lane_ranks2)) return rc;
         }
         // k_search_generic serves the levels above, and every level in raster mode or under BBME_GENERIC_SEARCH
-        if (int rc = raise_lds_limit(device, search_generic_kernel(L.block), std::max(L.lds_bytes, spec_floor))) return cleanup_fail(rc);
+        if (int rc = with_block<2, 4, 8, 16, 32, 64>(L.block, [&](auto B) {
+                return raise_lds_limit(device, reinterpret_cast<const void *>(&k_search_generic<B()>), std::max(L.lds_bytes, spec_floor));
+            })) return rc;
     }
     // pitch = 33 (mod 64) words: consecutive blocks land 132 bytes (mod 256) apart
     c->own_pitch = (uint32_t)(((max_blocks + 31) / 32 + 63) / 64 * 64 + 33);
@@ -917,31 +1014,35 @@ static int create_context(const bbme_params *params, int width, int height, int 
     c->flag_bytes = (max_blocks + 2047) / 2048 * 2048 + 2048;             // whole 16-flag segments (k_reg_solve), zero beyond the grid
     c->flow_stride = (size_t)g.padded_width * g.padded_height * 2;        // floats
     c->list_stride = (uint32_t)max_blocks; c->own_stride = (uint32_t)bit_words;
-    const size_t flow_bytes = P * c->flow_stride * sizeof(float);
-    if ((err = hipMalloc(&c->flow, flow_bytes)) != hipSuccess ||
-        (err = hipMalloc(&c->list[0], P * max_blocks * 4)) != hipSuccess ||
-        (err = hipMalloc(&c->list[1], P * max_blocks * 4)) != hipSuccess ||
-        (err = hipMalloc(&c->flags[0], P * c->flag_bytes)) != hipSuccess ||
-        (err = hipMalloc(&c->flags[1], P * c->flag_bytes)) != hipSuccess ||
-        (err = hipMemset(c->flags[0], 0, P * c->flag_bytes)) != hipSuccess ||
-        (err = hipMemset(c->flags[1], 0, P * c->flag_bytes)) != hipSuccess ||
-        (err = hipMalloc(&c->own, P * bit_words * 4)) != hipSuccess ||
-        (err = hipMalloc(&c->counters, P * 256)) != hipSuccess ||
-        (err = hipMemset(c->own, 0, P * bit_words * 4)) != hipSuccess ||
-        (err = hipMemset(c->counters, 0, P * 256)) != hipSuccess ||
-        (err = hipMemset(c->flow, 0, flow_bytes)) != hipSuccess)
-        return cleanup_fail(bbme::fail(BBME_ERR_HIP, "allocating work buffers: %s", hipGetErrorString(err)));
-    if (c->use_memo && c->memo_blocks) {
+    const char *work = "work buffers";
+    if (int rc = c->flow.alloc_zero(P * c->flow_stride, work)) return rc;
+    if (int rc = c->list[0].alloc(P * max_blocks, work)) return rc;
+    if (int rc = c->list[1].alloc(P * max_blocks, work)) return rc;
+    if (int rc = c->flags[0].alloc_zero(P * c->flag_bytes, work)) return rc;
+    if (int rc = c->flags[1].alloc_zero(P * c->flag_bytes, work)) return rc;
+    if (int rc = c->own.alloc_zero(P * bit_words, work)) return rc;
+    if (int rc = c->counters.alloc_zero(P * 64, work)) return rc;
+    if (c->tune.use_memo && c->memo_blocks) {
         c->memo_stride = (uint32_t)round64(c->memo_blocks << kMemoSlotShift);
         // every slot starts as "nothing known" (the MV half of the word is what counts: 0x80008000 is never a motion vector)
-        if ((err = hipMalloc(&c->memo, P * c->memo_stride * sizeof(unsigned long long))) != hipSuccess ||
-            (err = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(c->memo), (int)kMemoNoMv, P * c->memo_stride * 2)) != hipSuccess)
-            return cleanup_fail(bbme::fail(BBME_ERR_HIP, "allocating the SAD memo: %s", hipGetErrorString(err)));
+        if (int rc = c->memo.alloc(P * c->memo_stride, "the SAD memo")) return rc;
+        err = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(c->memo.get()), (int)kMemoNoMv, P * c->memo_stride * 2);
+        if (err != hipSuccess) return bbme::fail(BBME_ERR_HIP, "allocating the SAD memo: %s", hipGetErrorString(err));
     }
     HIP_TRY(hipDeviceSynchronize());
     bbme::clear_error();
-    *out = c;
+    *out = guard.release();
     return BBME_OK;
+}
+
+int bbme_create_batch(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out)
+{
+    return create_context(params, width, height, device, pairs, false, out);
+}
+
+int bbme_create_chain(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out)
+{
+    return create_context(params, width, height, device, pairs, true, out);
 }
 
 int bbme_destroy(bbme_ctx *c)
@@ -949,45 +1050,20 @@ int bbme_destroy(bbme_ctx *c)
     if (!c) return BBME_OK;
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    if (c->side_stream) (void)hipStreamSynchronize(c->side_stream);
     drop_graph(c);
-    for (Level &L : c->lv) {
-        (void)hipFree(L.img1);
-        if (!c->chain) (void)hipFree(L.img2);
-        (void)hipFree(L.small[0]); (void)hipFree(L.small[1]); (void)hipFree(L.pred);
-        (void)hipFree(L.fix_list); (void)hipFree(L.fix_count);
-        (void)hipFree(L.big[0]); (void)hipFree(L.big[1]); (void)hipFree(L.spiral);
-        (void)hipFree(L.rank_of); (void)hipFree(L.tasks); (void)hipFree(L.rounds); (void)hipFree(L.tasks2); (void)hipFree(L.rounds2);
-        (void)hipFree(L.lane_ranks); (void)hipFree(L.lane_ranks2);
-    }
-    (void)hipFree(c->flow);
-    (void)hipFree(c->epe_scratch);
-    (void)hipFree(c->raw[0]); (void)hipFree(c->raw[1]);
-    (void)hipFree(c->sub);
-    (void)hipFree(c->mc_plane);
-    (void)hipFree(c->mc_stats);
-    (void)hipFree(c->bwd_cells);
-    (void)hipFree(c->fb_mask);
-    (void)hipFree(c->fb_stats);
-    if (c->ev_sub) (void)hipEventDestroy(c->ev_sub);
-    (void)hipFree(c->list[0]); (void)hipFree(c->list[1]);
-    (void)hipFree(c->own);
-    (void)hipFree(c->flags[0]); (void)hipFree(c->flags[1]);
-    (void)hipFree(c->counters);
-    (void)hipFree(c->memo);
-    if (c->side_stream) { (void)hipStreamSynchronize(c->side_stream); (void)hipStreamDestroy(c->side_stream); }
-    if (c->ev_fork) (void)hipEventDestroy(c->ev_fork);
-    if (c->ev_join) (void)hipEventDestroy(c->ev_join);
+    if (c->side_stream) (void)hipStreamDestroy(c->side_stream);
     if (c->own_stream && c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
+    for (hipEvent_t e : {c->ev_sub, c->ev_fork, c->ev_join})
+        if (e) (void)hipEventDestroy(e);
+    delete c;                                        // the buffers go with it (DevBuf)
     return BBME_OK;
 }
 
 int bbme_set_stream(bbme_ctx *c, void *hip_stream)
 {
     if (int rc = check_ctx(c)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_graph(c);
+    if (int rc = settle_and_drop_graphs(c)) return rc;
     if (c->own_stream) { (void)hipStreamDestroy(c->stream); c->own_stream = false; }
     c->stream = (hipStream_t)hip_stream;
     if (!c->stream) {
@@ -1002,9 +1078,7 @@ int bbme_set_search_mode(bbme_ctx *c, int mode)
     if (int rc = check_ctx(c)) return rc;
     if (mode != BBME_SEARCH_SPIRAL && mode != BBME_SEARCH_RASTER) return bbme::fail(BBME_ERR_INVALID, "search mode %d", mode);
     if (c->raster_search == (mode == BBME_SEARCH_RASTER)) return BBME_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_graph(c);                                   // other kernels in the launch sequence
+    if (int rc = settle_and_drop_graphs(c)) return rc;
     c->raster_search = mode == BBME_SEARCH_RASTER;
     return BBME_OK;
 }
@@ -1014,9 +1088,7 @@ int bbme_set_regularizer_mode(bbme_ctx *c, int mode)
     if (int rc = check_ctx(c)) return rc;
     if (mode != BBME_REG_EXACT && mode != BBME_REG_JACOBI) return bbme::fail(BBME_ERR_INVALID, "regulariser mode %d", mode);
     if (c->jacobi == (mode == BBME_REG_JACOBI)) return BBME_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_graph(c);
+    if (int rc = settle_and_drop_graphs(c)) return rc;
     c->jacobi = mode == BBME_REG_JACOBI;
     return BBME_OK;
 }
@@ -1024,12 +1096,10 @@ int bbme_set_regularizer_mode(bbme_ctx *c, int mode)
 int bbme_set_speculation(bbme_ctx *c, int enabled)
 {
     if (int rc = check_ctx(c)) return rc;
-    if (c->speculate == (enabled != 0)) return BBME_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_graph(c);                                   // the launch sequence changes
-    c->speculate = enabled != 0;
-    if (!c->speculate && c->side_stream) { (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr; }
+    if (c->tune.speculate == (enabled != 0)) return BBME_OK;
+    if (int rc = settle_and_drop_graphs(c)) return rc;
+    c->tune.speculate = enabled != 0;
+    if (!c->tune.speculate && c->side_stream) { (void)hipStreamDestroy(c->side_stream); c->side_stream = nullptr; }
     return BBME_OK;
 }
 
@@ -1037,9 +1107,7 @@ int bbme_set_relaxation(bbme_ctx *c, int enabled)
 {
     if (int rc = check_ctx(c)) return rc;
     if (c->relax == (enabled != 0)) return BBME_OK;
-    HIP_TRY(hipSetDevice(c->device));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    drop_graph(c);                                   // the launch sequence changes
+    if (int rc = settle_and_drop_graphs(c)) return rc;
     c->relax = enabled != 0;
     return BBME_OK;
 }
@@ -1109,7 +1177,7 @@ static int upload_raw(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_
     c->raw_stride = (bytes + 64 + 255) / 256 * 256;
     const uint8_t *src[2] = {image1, image2};
     for (int i = 0; i < 2; ++i) {
-        if (!c->raw[i]) HIP_TRY(hipMalloc(&c->raw[i], c->raw_stride * c->batch));
+        if (int rc = c->raw[i].ensure(c->raw_stride * c->batch, "the upload buffers")) return rc;
         HIP_TRY(hipMemcpy2DAsync(c->raw[i] + pair * c->raw_stride, width, src[i], pitch, width, height, hipMemcpyHostToDevice, c->stream));
     }
     return BBME_OK;
@@ -1303,7 +1371,7 @@ int bbme_set_chain_frames_host_async(bbme_ctx *c, int first, int count, const ui
     const Geometry &g = c->geom;
     const int sw = g.width / scale, sh = g.height / scale;
     c->raw_stride = ((size_t)g.width * g.height + 64 + 255) / 256 * 256;
-    if (!c->raw[0]) HIP_TRY(hipMalloc(&c->raw[0], c->raw_stride * (size_t)(c->batch + 1)));
+    if (int rc = c->raw[0].ensure(c->raw_stride * (size_t)(c->batch + 1), "the upload buffers")) return rc;
     FrameRun run{};
     for (int i = 0; i < count; ++i) {
         uint8_t *d = c->raw[0] + (size_t)(first + i) * c->raw_stride;
@@ -1330,7 +1398,7 @@ int bbme_chain_advance(bbme_ctx *c)
     for (size_t l = 0; l < c->lv.size(); ++l) {
         Level &L = c->lv[l];
         r.src[l] = reinterpret_cast<const uint4 *>(L.img1 + (size_t)c->batch * L.plane_stride);
-        r.dst[l] = reinterpret_cast<uint4 *>(L.img1);
+        r.dst[l] = reinterpret_cast<uint4 *>(L.img1.get());
         r.n16[l] = L.plane_stride / 16;
         most = std::max(most, r.n16[l]);
     }
@@ -1349,7 +1417,7 @@ int bbme_level_planes_device(bbme_ctx *c, int level, uint8_t **d1, uint8_t **d2)
 {
     if (int rc = single_pair_only(c, "bbme_level_planes_device")) return rc;
     if (int rc = check_level(c, level)) return rc;
-    if (d1) *d1 = c->lv[level].img1;
+    if (d1) *d1 = c->lv[level].img1.get();
     if (d2) *d2 = c->lv[level].img2;
     c->mark_pair0();               // the caller fills them in place (pair 0; a chain of one pair: slots 0 and 1)
     c->memo_block = 0;
@@ -1388,13 +1456,13 @@ int bbme_get_level_planes_host(bbme_ctx *c, int level, uint8_t *image1, uint8_t 
 static int run_pyramid(bbme_ctx *c)
 {
     if (c->profiling) { const int rc = profiled_pyramid(c); c->memo_block = 0; return rc; }
-    if (!c->use_graph) { const int rc = enqueue_pyramid(c, c->speculate); c->memo_block = 0; return rc; }
+    if (!c->tune.use_graph) { const int rc = enqueue_pyramid(c, c->tune.speculate); c->memo_block = 0; return rc; }
     hipGraphExec_t &exec = c->graph_exec[c->direction];
     if (!exec) {
         // the launch sequence is fixed (no host decisions inside), so capture it once
         hipGraph_t graph = nullptr;
-        bool fork = c->speculate;                      // (see bbme_ctx::graph_forked)
-        if (!c->fork_both) {
+        bool fork = c->tune.speculate;                      // (see bbme_ctx::graph_forked)
+        if (!c->tune.fork_both) {
             if (c->direction == BBME_DIR_BACKWARD && c->graph_exec[BBME_DIR_FORWARD]) fork = false;
             if (c->direction == BBME_DIR_FORWARD && c->graph_exec[BBME_DIR_BACKWARD] && c->graph_forked[BBME_DIR_BACKWARD]) {
                 HIP_TRY(hipStreamSynchronize(c->stream));          // once per context: the graph may still be running
@@ -1465,10 +1533,8 @@ int bbme_estimate_bidirectional(bbme_ctx *c)
     HIP_TRY(hipSetDevice(c->device));
     const Level &L0 = c->lv[0];
     const uint32_t stride = L0.grid_stride(L0.final_grid());
-    if (!c->bwd_cells) {
-        HIP_TRY(hipMalloc(&c->bwd_cells, (size_t)stride * c->batch * sizeof(mv_t)));
-        c->bwd_stride = stride;
-    }
+    if (int rc = c->bwd_cells.ensure((size_t)stride * c->batch, "the backward cells")) return rc;
+    c->bwd_stride = stride;
     // backward pyramid, its final grid of every pair into the backward cells, forward pyramid: all on the ctx stream, in order
     switch_direction(c, BBME_DIR_BACKWARD);
     int rc = run_pyramid(c);
@@ -1587,7 +1653,8 @@ int bbme_calculate_mse_device(bbme_ctx *c, const float *d_gtruth, int gt_width, 
     constexpr int kMaxGroups = 512;
     const long long n = (long long)gt_width * gt_height;
     const int groups = (int)std::min<long long>(kMaxGroups, (n + 255) / 256);
-    if (!c->epe_scratch) HIP_TRY(hipMalloc(&c->epe_scratch, kMaxGroups * (sizeof(double) + sizeof(unsigned long long))));
+    static_assert(sizeof(double) == sizeof(unsigned long long), "sums and counts share the scratch");
+    if (int rc = c->epe_scratch.ensure(2 * kMaxGroups, "the EPE scratch")) return rc;
     double *d_sum = c->epe_scratch;
     unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(d_sum + kMaxGroups);
     hipLaunchKernelGGL(k_epe, dim3(groups), dim3(256), 0, c->stream, L.cur_grid, L.width / 2,
@@ -1607,7 +1674,7 @@ int bbme_calculate_mse_device(bbme_ctx *c, const float *d_gtruth, int gt_width, 
 }
 
 // main_class.cpp:58-70 from the cell grid: the ceil(W/s) x ceil(H/s) field at every s-th pixel of the unpadded frame, / s
-static int enqueue_subsample(bbme_ctx *c, int pair, int scale, float *d_out, int out_pitch, hipStream_t stream, const char *what)
+static int enqueue_subsample(bbme_ctx *c, int pair, int scale, float *d_out, int out_pitch, void *hip_stream, const char *what)
 {
     if (int rc = check_pair(c, pair)) return rc;
     if (!d_out || scale < 1) return bbme::fail(BBME_ERR_INVALID, "%s: null output or scale %d < 1", what, scale);
@@ -1616,11 +1683,8 @@ static int enqueue_subsample(bbme_ctx *c, int pair, int scale, float *d_out, int
     const Level &L = c->lv[0];
     if (L.cur_block != 2) return bbme::fail(BBME_ERR_STATE, "%s: level 0 has not been regularised down to 2x2 blocks", what);
     HIP_TRY(hipSetDevice(c->device));
-    if (stream != c->stream) {
-        if (!c->ev_sub) HIP_TRY(hipEventCreateWithFlags(&c->ev_sub, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_sub, c->stream));
-        HIP_TRY(hipStreamWaitEvent(stream, c->ev_sub, 0));
-    }
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
     const long long n = (long long)ow * oh;
     hipLaunchKernelGGL(k_subsample, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
                        L.cur_grid + (size_t)pair * L.grid_stride(L.cur_grid), L.width / 2, c->geom.pad_x, c->geom.pad_y, scale,
@@ -1632,8 +1696,7 @@ static int enqueue_subsample(bbme_ctx *c, int pair, int scale, float *d_out, int
 int bbme_subsampled_flow_device(bbme_ctx *c, int pair, int scale, float *d_out, int out_pitch_pixels, void *hip_stream)
 {
     if (int rc = check_ctx(c)) return rc;
-    return enqueue_subsample(c, pair, scale, d_out, out_pitch_pixels,
-                             hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream, "bbme_subsampled_flow_device");
+    return enqueue_subsample(c, pair, scale, d_out, out_pitch_pixels, hip_stream, "bbme_subsampled_flow_device");
 }
 
 int bbme_get_subsampled_flow_host(bbme_ctx *c, int pair, int scale, float *out)
@@ -1643,17 +1706,13 @@ int bbme_get_subsampled_flow_host(bbme_ctx *c, int pair, int scale, float *out)
     if (c->lv[0].cur_block != 2)
         return bbme::fail(BBME_ERR_STATE, "bbme_get_subsampled_flow_host: level 0 has not been regularised down to 2x2 blocks");
     const int ow = (c->geom.width + scale - 1) / scale, oh = (c->geom.height + scale - 1) / scale;
-    const size_t bytes = (size_t)ow * oh * 2 * sizeof(float);
-    if (bytes > c->sub_bytes) {
+    const size_t floats = (size_t)ow * oh * 2, bytes = floats * sizeof(float);
+    if (floats > c->sub.size()) {
         HIP_TRY(hipSetDevice(c->device));
         HIP_TRY(hipStreamSynchronize(c->stream));     // the old buffer may still be being read
-        (void)hipFree(c->sub);
-        c->sub = nullptr;
-        c->sub_bytes = 0;
-        HIP_TRY(hipMalloc(&c->sub, bytes));
-        c->sub_bytes = bytes;
+        if (int rc = c->sub.ensure(floats, "the subsampled field")) return rc;
     }
-    if (int rc = enqueue_subsample(c, pair, scale, c->sub, ow, c->stream, "bbme_get_subsampled_flow_host")) return rc;
+    if (int rc = enqueue_subsample(c, pair, scale, c->sub, ow, nullptr, "bbme_get_subsampled_flow_host")) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->sub, bytes, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
 }
@@ -1669,11 +1728,7 @@ static int check_mc(const bbme_ctx *c, int level, int block, int fill, const int
     if (block < 1 || block > L.block || (block & (block - 1)))
         return bbme::fail(BBME_ERR_INVALID, "%s: block %d is not a power of two in 1..%d", what, block, L.block);
     if (fill < 0 || fill > 255) return bbme::fail(BBME_ERR_INVALID, "%s: fill %d outside 0..255", what, fill);
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > L.width || (long long)window[1] + window[3] > L.height))
-        return bbme::fail(BBME_ERR_INVALID, "%s: window (%d, %d, %d, %d) is not inside the %dx%d plane of level %d", what,
-                          window[0], window[1], window[2], window[3], L.width, L.height, level);
-    return BBME_OK;
+    return check_window(window, L.width, L.height, what, level);
 }
 
 static int check_mc_state(const bbme_ctx *c, int level, const char *what)
@@ -1707,8 +1762,7 @@ static int enqueue_mc(bbme_ctx *c, int pair0, int pairs, int level, int block, i
     a.lcb = __builtin_ctz((unsigned)L.cur_block);
     a.lb = __builtin_ctz((unsigned)block);
     a.fill = fill; a.out_pitch = out_pitch;
-    a.wx0 = window ? window[0] : 0; a.wy0 = window ? window[1] : 0;
-    a.wx1 = window ? window[0] + window[2] : L.width; a.wy1 = window ? window[1] + window[3] : L.height;
+    set_window(a, window, L.width, L.height);
     a.runs_per_row = (L.width + 3) / 4;
     a.runs = (long long)a.runs_per_row * L.height;
     const long long groups = mc_groups(L);
@@ -1729,12 +1783,8 @@ int bbme_motion_compensate_device(bbme_ctx *c, int pair, int level, int block, i
         return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < level width %d", what, out_pitch, c->lv[level].width);
     if (int rc = check_mc_state(c, level, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    if (stream != c->stream) {
-        if (!c->ev_sub) HIP_TRY(hipEventCreateWithFlags(&c->ev_sub, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_sub, c->stream));
-        HIP_TRY(hipStreamWaitEvent(stream, c->ev_sub, 0));
-    }
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
     return enqueue_mc(c, pair, 1, level, block, fill, nullptr, d_out, out_pitch, nullptr, stream);
 }
 
@@ -1747,7 +1797,7 @@ int bbme_get_motion_compensated_host(bbme_ctx *c, int pair, int level, int block
     if (int rc = check_mc_state(c, level, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const Level &L = c->lv[level];
-    if (!c->mc_plane) HIP_TRY(hipMalloc(&c->mc_plane, (size_t)c->lv[0].width * c->lv[0].height));   // level 0 is the largest
+    if (int rc = c->mc_plane.ensure((size_t)c->lv[0].width * c->lv[0].height, "the compensated plane")) return rc;   // level 0 is the largest
     if (int rc = enqueue_mc(c, pair, 1, level, block, fill, nullptr, c->mc_plane, L.width, nullptr, c->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->mc_plane, (size_t)L.width * L.height, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
@@ -1762,8 +1812,7 @@ int bbme_compensation_error(bbme_ctx *c, int level, int block, const int *window
     HIP_TRY(hipSetDevice(c->device));
     const size_t bytes = (size_t)4 * sizeof(unsigned long long) * c->batch;
     // the result words of every pair, then one partial per pair and workgroup of level 0 (the largest plane)
-    if (!c->mc_stats)
-        HIP_TRY(hipMalloc(&c->mc_stats, (size_t)4 * sizeof(unsigned long long) * (BBME_MAX_BATCH + mc_groups(c->lv[0]) * c->batch)));
+    if (int rc = c->mc_stats.ensure((size_t)4 * (BBME_MAX_BATCH + mc_groups(c->lv[0]) * c->batch), "the compensation statistics")) return rc;
     if (int rc = enqueue_mc(c, 0, c->batch, level, block, 0, window, nullptr, 0, c->mc_stats, c->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(stats, c->mc_stats, bytes, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
@@ -1796,11 +1845,7 @@ int bbme_get_backward_cells_host_pair(bbme_ctx *c, int pair, int16_t *cells)
 static int check_fb(int cells_w, int cells_h, int tol, const int *window, const char *what)
 {
     if (tol < 0) return bbme::fail(BBME_ERR_INVALID, "%s: tolerance %d < 0", what, tol);
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > cells_w || (long long)window[1] + window[3] > cells_h))
-        return bbme::fail(BBME_ERR_INVALID, "%s: window (%d, %d, %d, %d) is not inside the %dx%d cells", what, window[0], window[1],
-                          window[2], window[3], cells_w, cells_h);
-    return BBME_OK;
+    return check_window(window, cells_w, cells_h, what, -1);
 }
 
 static long long fb_groups(const Level &L0)
@@ -1811,9 +1856,7 @@ static long long fb_groups(const Level &L0)
 // the result words of every pair, then the partials of a launch over every pair, then those of a one-pair launch
 static int fb_scratch(bbme_ctx *c)
 {
-    if (!c->fb_stats)
-        HIP_TRY(hipMalloc(&c->fb_stats, (size_t)4 * sizeof(unsigned long long) * (BBME_MAX_BATCH + fb_groups(c->lv[0]) * (c->batch + 1))));
-    return BBME_OK;
+    return c->fb_stats.ensure((size_t)4 * (BBME_MAX_BATCH + fb_groups(c->lv[0]) * (c->batch + 1)), "the consistency statistics");
 }
 
 // k_fb_consistency over `pairs` pairs: the mask (rows mask_pitch, pairs s_mask bytes apart) and / or, with d_stats, the statistics
@@ -1827,8 +1870,7 @@ static int enqueue_fb(bbme_ctx *c, const mv_t *d_a, uint32_t s_a, const mv_t *d_
     a.mask = d_mask; a.mask_pitch = mask_pitch; a.s_mask = 0;
     a.partial = d_stats ? partial : nullptr;
     a.cw = L.width / 2; a.ch = L.height / 2; a.tol = tol;
-    a.wx0 = window ? window[0] : 0; a.wy0 = window ? window[1] : 0;
-    a.wx1 = window ? window[0] + window[2] : a.cw; a.wy1 = window ? window[1] + window[3] : a.ch;
+    set_window(a, window, a.cw, a.ch);
     a.runs_per_row = (a.cw + 3) / 4;
     a.runs = (long long)a.runs_per_row * a.ch;
     const long long groups = fb_groups(L);
@@ -1850,12 +1892,8 @@ int bbme_cells_consistency_device(bbme_ctx *c, const int16_t *d_a, const int16_t
         return bbme::fail(BBME_ERR_INVALID, "%s: mask pitch %d < %d cells per row", what, mask_pitch, L.width / 2);
     HIP_TRY(hipSetDevice(c->device));
     if (d_stats4) if (int rc = fb_scratch(c)) return rc;
-    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
-    if (stream != c->stream) {
-        if (!c->ev_sub) HIP_TRY(hipEventCreateWithFlags(&c->ev_sub, hipEventDisableTiming));
-        HIP_TRY(hipEventRecord(c->ev_sub, c->stream));
-        HIP_TRY(hipStreamWaitEvent(stream, c->ev_sub, 0));
-    }
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
     unsigned long long *partial = d_stats4 ? c->fb_stats + (size_t)4 * (BBME_MAX_BATCH + fb_groups(L) * c->batch) : nullptr;
     return enqueue_fb(c, reinterpret_cast<const mv_t *>(d_a), 0, reinterpret_cast<const mv_t *>(d_b), 0, 1, tol, window, d_mask,
                       mask_pitch, partial, d_stats4, stream);
@@ -1879,7 +1917,7 @@ int bbme_get_consistency_host(bbme_ctx *c, int pair, int which, int tol, uint8_t
     HIP_TRY(hipSetDevice(c->device));
     const Level &L = c->lv[0];
     const int cw = L.width / 2, ch = L.height / 2;
-    if (!c->fb_mask) HIP_TRY(hipMalloc(&c->fb_mask, (size_t)cw * ch));
+    if (int rc = c->fb_mask.ensure((size_t)cw * ch, "the consistency mask")) return rc;
     const uint32_t s_f = L.grid_stride(L.final_grid());
     const mv_t *f = L.final_grid() + (size_t)pair * s_f, *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
     if (int rc = enqueue_fb(c, which ? b : f, 0, which ? f : b, 0, 1, tol, nullptr, c->fb_mask, cw, nullptr, nullptr, c->stream)) return rc;
@@ -2026,100 +2064,69 @@ int bbme_get_timings(bbme_ctx *c, float *total, float *search, float *reg, float
 int bbme_probe_rates(int device, double *gops)
 {
     if (!gops) return bbme::fail(BBME_ERR_INVALID, "null output");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return bbme::fail(BBME_ERR_HIP, "no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
-    uint32_t *out = nullptr;
-    HIP_TRY(hipMalloc(&out, 64));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    if (int rc = probe_device(device)) return rc;
+    DevBuf<uint32_t> out;
+    if (int rc = out.alloc(16, kProbe)) return rc;
     const int iters = 4096, grid = 256 * 8;          // 8 workgroups of 4 waves per CU: 8 waves per SIMD
+    void (*const kernels[4])(uint32_t *, int, uint32_t) = {k_probe_rate<0>, k_probe_rate<1>, k_probe_rate<2>, k_probe_rate<5>};
     for (int which = 0; which < 4; ++which) {
-        for (int rep = 0; rep < 2; ++rep) {
-            HIP_TRY(hipEventRecord(e0, 0));
-            if (which == 0) hipLaunchKernelGGL(k_probe_rate<0>, dim3(grid), dim3(256), 0, 0, out, iters, 7u + rep);
-            else if (which == 1) hipLaunchKernelGGL(k_probe_rate<1>, dim3(grid), dim3(256), 0, 0, out, iters, 7u + rep);
-            else if (which == 2) hipLaunchKernelGGL(k_probe_rate<2>, dim3(grid), dim3(256), 0, 0, out, iters, 7u + rep);
-            else hipLaunchKernelGGL(k_probe_rate<5>, dim3(grid), dim3(256), 0, 0, out, iters, 7u + rep);
-            HIP_TRY(hipEventRecord(e1, 0));
-            HIP_TRY(hipEventSynchronize(e1));
-        }
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        if (int rc = time_second_launch([&](int rep) { kernels[which]<<<dim3(grid), dim3(256), 0, 0>>>(out, iters, 7u + rep); }, &ms)) return rc;
         // wave-instructions per second over the whole chip, in units of 1e9 (mixed runs: QSADs only)
         gops[which] = (double)grid * 4 * iters * 8 / (ms * 1e-3) / 1e9;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(out);
     return BBME_OK;
 }
 
 int bbme_probe_search_loops(int device, double *tabs2)
 {
     if (!tabs2) return bbme::fail(BBME_ERR_INVALID, "null output");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return bbme::fail(BBME_ERR_HIP, "no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
-    uint32_t *out = nullptr;
-    HIP_TRY(hipMalloc(&out, 64));
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+    if (int rc = probe_device(device)) return rc;
+    DevBuf<uint32_t> out;
+    if (int rc = out.alloc(16, kProbe)) return rc;
     const int passes = 128, grid = 32768;
     for (int which = 0; which < 2; ++which) {
-        for (int rep = 0; rep < 2; ++rep) {
-            HIP_TRY(hipEventRecord(e0, 0));
-            if (which == 0) hipLaunchKernelGGL(k_probe_search_loop<false>, dim3(grid), dim3(64), 6912 + 21 * 32 * 4, 0, out, passes, 3u + rep);
-            else hipLaunchKernelGGL(k_probe_search_loop<true>, dim3(grid), dim3(64), 27648 + 16 * 5 * 32 + 16 * 5 * 31, 0, out, passes, 3u + rep);
-            HIP_TRY(hipEventRecord(e1, 0));
-            HIP_TRY(hipEventSynchronize(e1));
-        }
         float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        if (int rc = time_second_launch([&](int rep) {
+                if (which == 0) hipLaunchKernelGGL(k_probe_search_loop<false>, dim3(grid), dim3(64), 6912 + 21 * 32 * 4, 0, out.get(), passes, 3u + rep);
+                else hipLaunchKernelGGL(k_probe_search_loop<true>, dim3(grid), dim3(64), 27648 + 16 * 5 * 32 + 16 * 5 * 31, 0, out.get(), passes, 3u + rep);
+            }, &ms)) return rc;
         // abs-diffs: per lane and pass 16 x 16 x 4 instructions of 16 (QSAD: four dx at once) or 4 (v_sad_u8) abs-diffs
         const double absdiff = (double)grid * 64 * passes * 1024 * (which == 0 ? 16 : 4);
         tabs2[which] = absdiff / (ms * 1e-3) / 1e12;
     }
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipFree(out);
     return BBME_OK;
 }
 
 int bbme_probe_latency(int device, unsigned long long *out9)
 {
     if (!out9) return bbme::fail(BBME_ERR_INVALID, "null output");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return bbme::fail(BBME_ERR_HIP, "no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = probe_device(device)) return rc;
     const uint32_t nwords = 1u << 18;                       // 1 MiB: beyond L1, inside an L2
     std::vector<uint32_t> host(nwords);
     uint32_t x = 12345;
     for (uint32_t i = 0; i < nwords; ++i) { x = x * 1664525u + 1013904223u; host[i] = x; }
-    uint32_t *buf = nullptr; unsigned long long *out = nullptr;
-    HIP_TRY(hipMalloc(&buf, nwords * 4)); HIP_TRY(hipMalloc(&out, 9 * 8));
-    HIP_TRY(hipMemcpy(buf, host.data(), nwords * 4, hipMemcpyHostToDevice));
-    for (int rep = 0; rep < 2; ++rep) hipLaunchKernelGGL(k_probe_latency, dim3(1), dim3(64), 0, 0, buf, nwords, out);
+    DevBuf<uint32_t> buf;
+    DevBuf<unsigned long long> out;
+    if (int rc = buf.upload(host, kProbe)) return rc;
+    if (int rc = out.alloc(9, kProbe)) return rc;
+    for (int rep = 0; rep < 2; ++rep) hipLaunchKernelGGL(k_probe_latency, dim3(1), dim3(64), 0, 0, buf.get(), nwords, out.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out9, out, 9 * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(buf); (void)hipFree(out);
     return BBME_OK;
 }
 
 int bbme_probe_xcd(int device, int *xcds_seen, int *violations)
 {
     if (!xcds_seen || !violations) return bbme::fail(BBME_ERR_INVALID, "null output");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return bbme::fail(BBME_ERR_HIP, "no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = probe_device(device)) return rc;
     const int n = 4096;
     std::vector<uint32_t> host(n);
-    uint32_t *d = nullptr;
-    HIP_TRY(hipMalloc(&d, n * 4));
-    hipLaunchKernelGGL(k_probe_xcc, dim3(n), dim3(64), 0, 0, d);
+    DevBuf<uint32_t> d;
+    if (int rc = d.alloc(n, kProbe)) return rc;
+    hipLaunchKernelGGL(k_probe_xcc, dim3(n), dim3(64), 0, 0, d.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(host.data(), d, n * 4, hipMemcpyDeviceToHost));
-    (void)hipFree(d);
     uint32_t seen = 0;
     *violations = 0;
     for (int b = 0; b < n; ++b) {
@@ -2132,53 +2139,45 @@ int bbme_probe_xcd(int device, int *xcds_seen, int *violations)
 
 int bbme_calibrate_read(int device, unsigned mbytes, int repeats)
 {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return bbme::fail(BBME_ERR_HIP, "no HIP device %d", device);
+    if (int rc = probe_device(device)) return rc;
     if (mbytes == 0 || mbytes > 16384 || repeats < 1) return bbme::fail(BBME_ERR_INVALID, "bbme_calibrate_read: bad size");
-    HIP_TRY(hipSetDevice(device));
     const size_t bytes = (size_t)mbytes << 20, n = bytes / 4;
-    uint32_t *buf = nullptr, *out = nullptr;
-    HIP_TRY(hipMalloc(&buf, bytes));
-    HIP_TRY(hipMalloc(&out, 64));
+    DevBuf<uint32_t> buf, out;
+    if (int rc = buf.alloc(n, kProbe)) return rc;
+    if (int rc = out.alloc(16, kProbe)) return rc;
     HIP_TRY(hipMemset(buf, 1, bytes));
     HIP_TRY(hipDeviceSynchronize());
     for (int i = 0; i < repeats; ++i)
-        hipLaunchKernelGGL(k_calib_read_dword, dim3(256 * 8), dim3(256), 0, 0, buf, n, out);
+        hipLaunchKernelGGL(k_calib_read_dword, dim3(256 * 8), dim3(256), 0, 0, buf.get(), n, out.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
-    (void)hipFree(buf); (void)hipFree(out);
     return BBME_OK;
 }
 
 int bbme_selftest_isa(int device, int *mismatches)
 {
     if (!mismatches) return bbme::fail(BBME_ERR_INVALID, "null output");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev)
-        return bbme::fail(BBME_ERR_HIP, "no HIP device %d", device);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = probe_device(device)) return rc;
     const int n = 1 << 16;
     std::vector<uint32_t> a(n), b(n), cc(n), sad(n), al(n), s16(n);
     std::vector<unsigned long long> qs(n);
     uint32_t x = 0x12345678u;
     auto rnd = [&]() { x ^= x << 13; x ^= x >> 17; x ^= x << 5; return x; };
     for (int i = 0; i < n; ++i) { a[i] = rnd(); b[i] = rnd(); cc[i] = rnd(); }
-    uint32_t *da, *db, *dc, *dsad, *dal, *ds16; unsigned long long *dqs;
-    HIP_TRY(hipMalloc(&da, n * 4)); HIP_TRY(hipMalloc(&db, n * 4)); HIP_TRY(hipMalloc(&dc, n * 4));
-    HIP_TRY(hipMalloc(&dsad, n * 4)); HIP_TRY(hipMalloc(&dal, n * 4)); HIP_TRY(hipMalloc(&ds16, n * 4));
-    HIP_TRY(hipMalloc(&dqs, n * 8));
-    HIP_TRY(hipMemcpy(da, a.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(db, b.data(), n * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(dc, cc.data(), n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(k_probe_sad, dim3(n / 256), dim3(256), 0, 0, da, db, dc, dsad, dqs, dal, ds16, n);
+    DevBuf<uint32_t> da, db, dc, dsad, dal, ds16;
+    DevBuf<unsigned long long> dqs;
+    if (int rc = da.upload(a, kProbe)) return rc;
+    if (int rc = db.upload(b, kProbe)) return rc;
+    if (int rc = dc.upload(cc, kProbe)) return rc;
+    for (DevBuf<uint32_t> *d : {&dsad, &dal, &ds16})
+        if (int rc = d->alloc(n, kProbe)) return rc;
+    if (int rc = dqs.alloc(n, kProbe)) return rc;
+    hipLaunchKernelGGL(k_probe_sad, dim3(n / 256), dim3(256), 0, 0, da.get(), db.get(), dc.get(), dsad.get(), dqs.get(), dal.get(), ds16.get(), n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(sad.data(), dsad, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(al.data(), dal, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(s16.data(), ds16, n * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(qs.data(), dqs, n * 8, hipMemcpyDeviceToHost));
-    (void)hipFree(da); (void)hipFree(db); (void)hipFree(dc); (void)hipFree(dsad); (void)hipFree(dal);
-    (void)hipFree(ds16); (void)hipFree(dqs);
     auto absd = [](int p, int q) { return p > q ? p - q : q - p; };
     mismatches[0] = mismatches[1] = mismatches[2] = mismatches[3] = mismatches[4] = 0;
     {   // unaligned dword / x2 / x4 global loads (score_block relies on them)
@@ -2186,13 +2185,13 @@ int bbme_selftest_isa(int device, int *mismatches)
         std::vector<uint8_t> bytes(5 * m + 64);
         for (size_t i = 0; i < bytes.size(); ++i) bytes[i] = (uint8_t)rnd();
         std::vector<uint32_t> got(7 * m);
-        uint8_t *dp; uint32_t *dout;
-        HIP_TRY(hipMalloc(&dp, bytes.size())); HIP_TRY(hipMalloc(&dout, got.size() * 4));
-        HIP_TRY(hipMemcpy(dp, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_probe_unaligned, dim3(m / 256), dim3(256), 0, 0, dp, dout, m);
+        DevBuf<uint8_t> dp;
+        DevBuf<uint32_t> dout;
+        if (int rc = dp.upload(bytes, kProbe)) return rc;
+        if (int rc = dout.alloc(got.size(), kProbe)) return rc;
+        hipLaunchKernelGGL(k_probe_unaligned, dim3(m / 256), dim3(256), 0, 0, dp.get(), dout.get(), m);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(got.data(), dout, got.size() * 4, hipMemcpyDeviceToHost));
-        (void)hipFree(dp); (void)hipFree(dout);
         auto rd = [&](size_t o) { return (uint32_t)bytes[o] | ((uint32_t)bytes[o + 1] << 8) | ((uint32_t)bytes[o + 2] << 16) | ((uint32_t)bytes[o + 3] << 24); };
         for (int i = 0; i < m; ++i) {
             const size_t o = 5 * (size_t)i + (i & 3);
