@@ -109,6 +109,13 @@ SIGNATURES = {
     "bbme_get_consistency_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_consistency_stats": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_cells_consistency_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_cells_interpolate_device": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                C.c_int, C.c_size_t, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "bbme_interpolate_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "bbme_get_interpolated_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_interpolation_stats": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_interpolate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.c_void_p, C.c_void_p]),
     "bbme_pgm_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_flow_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),
     "bbme_get_flow_host_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p]),

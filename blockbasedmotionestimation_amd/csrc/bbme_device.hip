@@ -287,6 +287,9 @@ struct bbme_ctx {
                                                   // the largest asked for)
     DevBuf<uint8_t> mc_plane;                     // bbme_get_motion_compensated_host: a level-0-sized plane before its download
     DevBuf<unsigned long long> mc_stats;          // bbme_compensation_error: 4 words per pair, then the partials of k_motion_compensate
+    DevBuf<uint8_t> ip_plane;                     // bbme_get_interpolated_host: a packed W0 x H0 frame before its download
+    DevBuf<unsigned long long> ip_stats;          // interpolation statistics: 4 words per pair, then the partials of k_interpolate of
+                                                  // bbme_interpolation_stats (every pair) and of bbme_cells_interpolate_device (every phase)
 };
 
 namespace {
@@ -1939,6 +1942,155 @@ int bbme_consistency_stats(bbme_ctx *c, int which, int tol, const int *window, u
     if (int rc = enqueue_fb(c, which ? b : f, which ? s_b : s_f, which ? f : b, which ? s_f : s_b, c->batch, tol, window, nullptr, 0,
                             c->fb_stats + (size_t)4 * BBME_MAX_BATCH, c->fb_stats, c->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(stats, c->fb_stats, (size_t)4 * sizeof(unsigned long long) * c->batch, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+// ---- motion-compensated interpolation between the two frames of a pair (the rule of include/bbme.h; k_interpolate) ----------
+
+// phases num0 .. num0 + count - 1 of den, and the window {cx0, cy0, cw, ch} in cells.  Touches no device.
+static int check_ip(const bbme_ctx *c, int num0, int count, int den, const int *window, const char *what)
+{
+    if (den < 2 || den > 256) return bbme::fail(BBME_ERR_INVALID, "%s: den %d outside 2..256", what, den);
+    if (num0 < 1 || count < 1 || (long long)num0 + count > den)
+        return bbme::fail(BBME_ERR_INVALID, "%s: phases %d .. %d + %d - 1 are not inside 1 .. %d", what, num0, num0, count, den - 1);
+    return check_window(window, c->lv[0].width / 2, c->lv[0].height / 2, what, -1);
+}
+
+static int check_ip_frames(const bbme_ctx *c, int count, int pitch, size_t stride, int min_pitch, int rows, const char *what,
+                           const char *which)
+{
+    if (pitch < min_pitch) return bbme::fail(BBME_ERR_INVALID, "%s: %s pitch %d < %d", what, which, pitch, min_pitch);
+    if (count > 1 && stride < (size_t)pitch * rows)
+        return bbme::fail(BBME_ERR_INVALID, "%s: %s stride %zu < one frame of %d rows of %d bytes", what, which, stride, rows, pitch);
+    return BBME_OK;
+}
+
+static long long ip_groups(const Level &L0)
+{
+    return ((long long)(L0.width / 2 + 3) / 4 * (L0.height / 2) + 256 * kIpRunsPerLane - 1) / (256 * kIpRunsPerLane);
+}
+
+// the result words of every pair, then the partials of a launch over every pair, then those of a one-pair launch of `count`
+// phases; grown, behind both streams, when a launch of more phases comes
+static int ip_scratch(bbme_ctx *c, int count, hipStream_t stream)
+{
+    const size_t need = (size_t)4 * (BBME_MAX_BATCH + ip_groups(c->lv[0]) * (c->batch + count));
+    if (need <= c->ip_stats.size()) return BBME_OK;
+    HIP_TRY(hipStreamSynchronize(c->stream));             // the old buffer may still be being read
+    if (stream != c->stream) HIP_TRY(hipStreamSynchronize(stream));
+    return c->ip_stats.ensure(need, "the interpolation statistics");
+}
+
+// k_interpolate over `pairs` pairs from `pair0` on and `count` phases from num0 on: frames and maps (one pair only) and / or, with
+// d_stats, the statistics (k_mc_reduce adds the partials at `partial` into d_stats[4 (phase pairs + p) ..])
+static int enqueue_ip(bbme_ctx *c, int pair0, int pairs, const mv_t *d_f, uint32_t s_f, const mv_t *d_b, uint32_t s_b, int num0,
+                      int count, int den, const int *window, uint8_t *d_out, int out_pitch, size_t out_stride, uint8_t *d_sel,
+                      int sel_pitch, size_t sel_stride, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    IpArgs a{};
+    a.plane_stride = L.plane_stride;
+    a.img1 = c->plane1(L) + (size_t)pair0 * a.plane_stride;
+    a.img2 = c->plane2(L) + (size_t)pair0 * a.plane_stride;
+    a.fwd = d_f; a.bwd = d_b; a.s_f = s_f; a.s_b = s_b;
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    a.sel = d_sel; a.sel_pitch = sel_pitch; a.sel_stride = sel_stride;
+    a.partial = d_stats ? partial : nullptr;
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2; a.ch = L.height / 2;
+    a.num0 = num0; a.den = den;
+    a.magic = (uint32_t)((1ull << 32) / (unsigned)den + 1ull);
+    set_window(a, window, a.cw, a.ch);
+    a.runs_per_row = (a.cw + 3) / 4;
+    a.runs = (long long)a.runs_per_row * a.ch;
+    const long long groups = ip_groups(L);
+    hipLaunchKernelGGL(k_interpolate, dim3((unsigned)groups, (unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
+    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)(pairs * count)), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+int bbme_cells_interpolate_device(bbme_ctx *c, int pair, const int16_t *d_fwd, const int16_t *d_bwd, int num0, int count, int den,
+                                  const int *window, uint8_t *d_out, int out_pitch, size_t out_stride, uint8_t *d_sel,
+                                  int sel_pitch, size_t sel_stride, unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_interpolate_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_fwd || (!d_out && !d_sel && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_ip(c, num0, count, den, window, what)) return rc;
+    if (d_out) if (int rc = check_ip_frames(c, count, out_pitch, out_stride, L.width, L.height, what, "output")) return rc;
+    if (d_sel) if (int rc = check_ip_frames(c, count, sel_pitch, sel_stride, L.width / 2, L.height / 2, what, "selection map")) return rc;
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (d_stats4) if (int rc = ip_scratch(c, count, stream)) return rc;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    unsigned long long *partial = d_stats4 ? c->ip_stats + (size_t)4 * (BBME_MAX_BATCH + ip_groups(L) * c->batch) : nullptr;
+    return enqueue_ip(c, pair, 1, reinterpret_cast<const mv_t *>(d_fwd), 0, reinterpret_cast<const mv_t *>(d_bwd), 0, num0, count, den,
+                      window, d_out, out_pitch, out_stride, d_sel, sel_pitch, sel_stride, partial, d_stats4, stream);
+}
+
+// what the three calls on the context's own two fields share
+static int check_ip_ctx(const bbme_ctx *c, int num0, int count, int den, const int *window, const char *what)
+{
+    if (int rc = check_ctx(c)) return rc;
+    return check_ip(c, num0, count, den, window, what);
+}
+
+static int check_ip_state(const bbme_ctx *c, const char *what)
+{
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
+    return BBME_OK;
+}
+
+int bbme_interpolate_device(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
+                            void *hip_stream)
+{
+    const char *what = "bbme_interpolate_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_ip_ctx(c, num0, count, den, nullptr, what)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_ip_frames(c, count, out_pitch, out_stride, L.width, L.height, what, "output")) return rc;
+    if (int rc = check_ip_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    const mv_t *f = L.final_grid() + (size_t)pair * L.grid_stride(L.final_grid()), *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
+    return enqueue_ip(c, pair, 1, f, 0, b, 0, num0, count, den, nullptr, d_out, out_pitch, out_stride, nullptr, 0, 0, nullptr, nullptr, stream);
+}
+
+int bbme_get_interpolated_host(bbme_ctx *c, int pair, int num, int den, uint8_t *out)
+{
+    const char *what = "bbme_get_interpolated_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_ip_ctx(c, num, 1, den, nullptr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_ip_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[0];
+    const size_t bytes = (size_t)L.width * L.height;
+    if (int rc = c->ip_plane.ensure(bytes, "the interpolated frame")) return rc;
+    const mv_t *f = L.final_grid() + (size_t)pair * L.grid_stride(L.final_grid()), *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
+    if (int rc = enqueue_ip(c, pair, 1, f, 0, b, 0, num, 1, den, nullptr, c->ip_plane, L.width, 0, nullptr, 0, 0, nullptr, nullptr, c->stream))
+        return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->ip_plane, bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_interpolation_stats(bbme_ctx *c, int num, int den, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_interpolation_stats";
+    if (int rc = check_ip_ctx(c, num, 1, den, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_ip_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = ip_scratch(c, 1, c->stream)) return rc;
+    const Level &L = c->lv[0];
+    if (int rc = enqueue_ip(c, 0, c->batch, L.final_grid(), L.grid_stride(L.final_grid()), c->bwd_cells, c->bwd_stride, num, 1, den, window,
+                            nullptr, 0, 0, nullptr, 0, 0, c->ip_stats + (size_t)4 * BBME_MAX_BATCH, c->ip_stats, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(stats, c->ip_stats, (size_t)4 * sizeof(unsigned long long) * c->batch, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
 }
 

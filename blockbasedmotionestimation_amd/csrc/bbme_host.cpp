@@ -628,6 +628,56 @@ int bbme_cells_consistency_host(const int16_t *a, const int16_t *b, int cells_w,
     return BBME_OK;
 }
 
+// The interpolation rule of include/bbme.h, cell by cell, in the header's own words (the mirror of k_interpolate).
+int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *fwd,
+                          const int16_t *bwd, int num, int den, const int *window, uint8_t *out, uint8_t *sel,
+                          unsigned long long *stats4)
+{
+    if (!image1 || !image2 || !fwd || (!out && !sel && !stats4))
+        return bbme::fail(BBME_ERR_INVALID, "bbme_interpolate_host: null pointer");
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "bbme_interpolate_host: %dx%d is not a plane of 2x2 cells", width, height);
+    if (den < 2 || den > 256 || num < 1 || num >= den)
+        return bbme::fail(BBME_ERR_INVALID, "bbme_interpolate_host: phase %d / %d (2 <= den <= 256, 0 < num < den)", num, den);
+    const int cw = width / 2, ch = height / 2;
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
+        return bbme::fail(BBME_ERR_INVALID, "bbme_interpolate_host: window not inside the %dx%d cells", cw, ch);
+    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
+    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
+    const auto floor_div = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            const int v[3][2] = {{fwd[2 * c], fwd[2 * c + 1]}, {bwd ? -(int)bwd[2 * c] : 0, bwd ? -(int)bwd[2 * c + 1] : 0}, {0, 0}};
+            int best = -1, best_cost = 0, b1x = 0, b1y = 0, b2x = 0, b2y = 0;
+            for (int k = 0; k < 3; ++k) {
+                if (k == 1 && !bwd) continue;
+                const int p1x = ox - floor_div(num * v[k][0] + den / 2, den), p1y = oy - floor_div(num * v[k][1] + den / 2, den);
+                const int p2x = p1x + v[k][0], p2y = p1y + v[k][1];
+                if (p1x < 0 || p2x < 0 || p1x > width - 2 || p2x > width - 2 || p1y < 0 || p2y < 0 || p1y > height - 2 || p2y > height - 2)
+                    continue;
+                int cost = 0;
+                for (int i = 0; i < 2; ++i)
+                    for (int j = 0; j < 2; ++j)
+                        cost += abs((int)image1[(size_t)(p1y + i) * width + p1x + j] - (int)image2[(size_t)(p2y + i) * width + p2x + j]);
+                if (best < 0 || cost < best_cost) { best = k; best_cost = cost; b1x = p1x; b1y = p1y; b2x = p2x; b2y = p2y; }
+            }
+            if (out)
+                for (int i = 0; i < 2; ++i)
+                    for (int j = 0; j < 2; ++j)
+                        out[(size_t)(oy + i) * width + ox + j] =
+                            (uint8_t)(((den - num) * image1[(size_t)(b1y + i) * width + b1x + j] +
+                                       num * image2[(size_t)(b2y + i) * width + b2x + j] + den / 2) / den);
+            if (sel) sel[c] = (uint8_t)best;
+            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) { ++s[best]; s[3] += (unsigned)best_cost; }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 int bbme_subsample_div4(const float *flow_padded, int padded_width, int padded_height,
                         int pad_x, int pad_y, float *out, int out_width, int out_height)
 {

@@ -2845,4 +2845,166 @@ __global__ __launch_bounds__(256) void k_fb_consistency(FbArgs a)
             (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
 }
 
+// =======================================================================================
+// Motion-compensated interpolation at phase num / den from the level-0 planes and the two 2x2-cell grids (the rule of
+// include/bbme.h): output cell (cx, cy) tries v = F[cy][cx], v = -B[cy][cx] (when B is given) and v = 0; a hypothesis reads
+// the 2x2 cell of I1 at p1 = origin - round(num v / den) and the one of I2 at p2 = p1 + v, is valid when both lie inside the
+// plane, and costs their SAD; the cheapest valid one (the earliest of equals) is blended, ((den - num) I1 + num I2 +
+// den / 2) / den.  A memory-bound gather: a lane takes a run of 4 consecutive cells of one cell row (fewer at the row's
+// end), so that F and B arrive as one 16-byte load each and the zero hypothesis as one 8-byte load per plane row; the moved
+// cells are unaligned u16 loads, two per cell and plane, packed into one dword per cell so that v_sad_u8 gives the cost in
+// one instruction.  A lane writes its 8 pixels of each of the two output rows as two dwords (bytes where a caller's row is
+// not dword-aligned or the run is cut by the row's end) and its selections as one dword.
+// Divisions by den are multiply-shifts: with magic = floor(2^32 / den) + 1 = (2^32 + e) / den, 0 < e <= den,
+// umulhi(n, magic) = floor(n / den) for every n with n e < 2^32.  The blend's numerators stay below 255 * 256 + 128 and the
+// shifts', moved to n >= 0 by 32768 den (|num v| < 32768 den), below 2^24, and e <= 256.
+// blockIdx.y = pair (planes plane_stride bytes, grids s_f / s_b words apart), blockIdx.z = phase num0 + z (frames out_stride,
+// maps sel_stride bytes apart): the planes and grids of one pair are read from L2 by every phase but the first.  `out` and
+// `sel` only with one pair per launch.  Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells that selected
+// k = 0, 1, 2 and the sum of the selected costs; a lane holds at most 4 kIpRunsPerLane cells of cost <= 1020, every workgroup
+// stores its four 64-bit sums as a partial in k_motion_compensate's layout, (phase, pair) taking pair's place, and k_mc_reduce
+// adds them up (no atomics onto one line, see McArgs).
+// =======================================================================================
+struct IpArgs {
+    const uint8_t *img1, *img2;           // level-0 padded planes, pitch = width
+    const mv_t *fwd, *bwd;                // cw entries per row, ch rows; bwd may be null
+    uint8_t *out;                         // frames (rows out_pitch, phases out_stride bytes apart), or null
+    uint8_t *sel;                         // one byte k per cell (rows sel_pitch, phases sel_stride bytes apart), or null
+    unsigned long long *partial;          // per (phase, pair) and workgroup {k = 0, k = 1, k = 2, cost}; or null
+    uint32_t plane_stride, s_f, s_b;
+    size_t out_stride, sel_stride;
+    int width, height, cw, ch, num0, den, out_pitch, sel_pitch;
+    uint32_t magic;                       // floor(2^32 / den) + 1
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kIpRunsPerLane = 2;
+
+// the 2x2 cell at (x, y) of a plane as one dword: row y in the low half, row y + 1 in the high half
+__device__ __forceinline__ uint32_t ip_cell(const uint8_t *img, int W, int x, int y)
+{
+    const uint8_t *p = img + (size_t)y * W + x;
+    return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)reinterpret_cast<const ua_u16 *>(p + W)->v << 16;
+}
+
+__global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const uint8_t *img1 = a.img1 + pair * a.plane_stride, *img2 = a.img2 + pair * a.plane_stride;
+    const mv_t *F = a.fwd + pair * a.s_f, *B = a.bwd ? a.bwd + pair * a.s_b : nullptr;
+    const int W = a.width, H = a.height, CW = a.cw, den = a.den, num = a.num0 + (int)blockIdx.z, half = den >> 1;
+    const uint32_t magic = a.magic, w1 = (uint32_t)(den - num), w2 = (uint32_t)num;
+    const int bias = 32768 * den;
+    uint32_t n0 = 0, n1 = 0, n2 = 0, csum = 0;
+#pragma unroll
+    for (int r = 0; r < kIpRunsPerLane; ++r) {
+        const long long i = ((long long)blockIdx.x * kIpRunsPerLane + r) * 256 + threadIdx.x;
+        if (i >= a.runs) break;
+        const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
+        const int n = min(4, CW - x0);                        // cells of the run inside the row
+        const int oy = 2 * cy;
+        uint32_t f[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+        uint32_t z1[4], z2[4];                                // the cells of the zero hypothesis
+        const size_t g0 = (size_t)cy * CW + x0, o0 = (size_t)oy * W + 2 * x0;
+        if (n == 4) {
+            const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(F + g0);
+            f[0] = v.v[0]; f[1] = v.v[1]; f[2] = v.v[2]; f[3] = v.v[3];
+            if (B) {
+                const ua_u32x4 u = *reinterpret_cast<const ua_u32x4 *>(B + g0);
+                b[0] = u.v[0]; b[1] = u.v[1]; b[2] = u.v[2]; b[3] = u.v[3];
+            }
+            const ua_u32x2 t1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0), u1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0 + W);
+            const ua_u32x2 t2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0), u2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0 + W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int sh = 16 * (j & 1);
+                z1[j] = ((t1.v[j >> 1] >> sh) & 0xffffu) | ((u1.v[j >> 1] >> sh) << 16);
+                z2[j] = ((t2.v[j >> 1] >> sh) & 0xffffu) | ((u2.v[j >> 1] >> sh) << 16);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                z1[j] = z2[j] = 0;
+                if (j >= n) continue;
+                f[j] = F[g0 + j];
+                if (B) b[j] = B[g0 + j];
+                z1[j] = ip_cell(img1, W, 2 * (x0 + j), oy);
+                z2[j] = ip_cell(img2, W, 2 * (x0 + j), oy);
+            }
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ks = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox = 2 * (x0 + j);
+            uint32_t c1 = 0, c2 = 0, k = 2u, cost = ~0u;      // nothing selected yet
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (h == 1 && !B) break;
+                const int vx = h ? -mv_x(b[j]) : mv_x(f[j]), vy = h ? -mv_y(b[j]) : mv_y(f[j]);
+                const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
+                const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
+                const int p1x = ox - sx, p1y = oy - sy, p2x = p1x + vx, p2y = p1y + vy;
+                if (p1x < 0 || p2x < 0 || p1x > W - 2 || p2x > W - 2 || p1y < 0 || p2y < 0 || p1y > H - 2 || p2y > H - 2) continue;
+                const uint32_t q1 = ip_cell(img1, W, p1x, p1y), q2 = ip_cell(img2, W, p2x, p2y);
+                const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
+                if (c < cost) { c1 = q1; c2 = q2; k = (uint32_t)h; cost = c; }      // strictly cheaper: the earliest of equals stays
+            }
+            const uint32_t cz = __builtin_amdgcn_sad_u8(z1[j], z2[j], 0u);
+            if (cz < cost) { c1 = z1[j]; c2 = z2[j]; k = 2u; cost = cz; }
+            uint32_t px = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t v = __umulhi(w1 * ((c1 >> (8 * q)) & 0xffu) + w2 * ((c2 >> (8 * q)) & 0xffu) + (uint32_t)half, magic);
+                px |= v << (8 * q);
+            }
+            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
+            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            ks |= k << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                n0 += k == 0u; n1 += k == 1u; n2 += k == 2u;
+                csum += cost;
+            }
+        }
+        if (a.out) {
+            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                const uint32_t *row = y ? row1 : row0;
+                uint8_t *q = o + (size_t)y * a.out_pitch;
+                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
+                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
+                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
+                } else {
+                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+                }
+            }
+        }
+        if (a.sel) {
+            uint8_t *o = a.sel + blockIdx.z * a.sel_stride + (size_t)cy * a.sel_pitch + x0;
+            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = ks;
+            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(ks >> (8 * j));
+        }
+    }
+    if (!a.partial) return;
+    for (int o = 32; o > 0; o >>= 1) {
+        n0 += __shfl_xor(n0, o);
+        n1 += __shfl_xor(n1, o);
+        n2 += __shfl_xor(n2, o);
+        csum += __shfl_xor(csum, o);
+    }
+    __shared__ uint32_t part[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        uint32_t *w = part[threadIdx.x >> 6];
+        w[0] = n0; w[1] = n1; w[2] = n2; w[3] = csum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        a.partial[4 * (((size_t)blockIdx.z * gridDim.y + pair) * gridDim.x + blockIdx.x) + threadIdx.x] =
+            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
 }  // namespace bbme

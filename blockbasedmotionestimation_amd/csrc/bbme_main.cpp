@@ -2,6 +2,7 @@
 //
 //   bbme_cli frame10.pgm frame11.pgm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
+//            [--interpolate PREFIX --factor N]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -12,7 +13,9 @@
 // MF sees, and prints its PSNR against frame 1.  --backward writes the field from frame 2 to frame 1 (the context's direction
 // BACKWARD, include/bbme.h) through the same subsampling and writer as --out; --occlusion writes the forward-backward consistency
 // mask on frame 1 at tolerance 1, one byte per 2x2 cell whose top-left pixel lies in the unpadded frame MF sees (0 consistent,
-// 128 inconsistent, 255 target outside the plane), and prints the three counts.
+// 128 inconsistent, 255 target outside the plane), and prints the three counts.  --interpolate PREFIX --factor N (default 2)
+// writes the N - 1 frames between frame 1 and frame 2, phases k / N (the interpolation rule of include/bbme.h, from both fields),
+// as PREFIX_k.pgm, each the unpadded frame MF sees.
 // Defaults are the reference's literals (:19-21): 4 levels, block 32, search 64.
 #include <chrono>
 #include <cstdio>
@@ -50,7 +53,8 @@ static bool read_pgm(const char *path, bbme::Image8 &img)
 
 int main(int argc, char **argv)
 {
-    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr;
+    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr;
+    int factor = 2;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
     for (int i = 1; i < argc; ++i) {
@@ -62,6 +66,8 @@ int main(int argc, char **argv)
         else if (a == "--mc") mc = next();
         else if (a == "--backward") backward = next();
         else if (a == "--occlusion") occlusion = next();
+        else if (a == "--interpolate") interpolate = next();
+        else if (a == "--factor") factor = atoi(next());
         else if (a == "--levels") levels = atoi(next());
         else if (a == "--block") block = atoi(next());
         else if (a == "--search") search = atoi(next());
@@ -71,10 +77,10 @@ int main(int argc, char **argv)
         else if (!f2) f2 = argv[i];
         else { fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
     }
-    if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS) {
+    if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || (interpolate && (factor < 2 || factor > 256))) {
         fprintf(stderr, "usage: bbme_cli frame1.pgm frame2.pgm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
-                        "[--occlusion occ.pgm]\n");
+                        "[--occlusion occ.pgm] [--interpolate PREFIX --factor N]\n");
         return 2;
     }
     try {
@@ -126,6 +132,16 @@ int main(int argc, char **argv)
             bbme::check(bbme_pgm_write(occlusion, win[2], win[3], mask.cols, mask.data.data() + (size_t)win[1] * mask.cols + win[0]));
             const bbme::ConsistencyStats st = motion_pair.consistencyStats(false, 1);
             printf("consistent %llu inconsistent %llu outside %llu\n", st.consistent, st.inconsistent, st.outside);
+        }
+        if (interpolate) {
+            motion_pair.estimateBidirectional();
+            const int px = motion_pair.padding_x, py = motion_pair.padding_y;
+            for (int k = 1; k < factor; ++k) {
+                const bbme::Image8 img = motion_pair.interpolate(k, factor);
+                const std::string name = std::string(interpolate) + "_" + std::to_string(k) + ".pgm";
+                bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
+                                           img.data.data() + (size_t)py * img.cols + px));
+            }
         }
     } catch (const bbme::Error &e) {
         fprintf(stderr, "%s\n", e.what());

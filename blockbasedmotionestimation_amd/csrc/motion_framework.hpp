@@ -87,6 +87,11 @@ struct ConsistencyStats {
     unsigned long long consistent = 0, inconsistent = 0, outside = 0, discrepancy = 0;
 };
 
+// statistics of an interpolated frame (bbme_interpolation_stats): cells per selected hypothesis, the sum of their costs
+struct InterpolationStats {
+    unsigned long long forward = 0, backward = 0, zero = 0, cost = 0;
+};
+
 // cv::resize(img, img, cv::Size(), 4, 4, cv::INTER_LINEAR) of main_class.cpp:32-33
 inline Image8 resize_x4(const Image8 &src)
 {
@@ -237,6 +242,25 @@ public:
         bbme::check(bbme_consistency_stats(ctx_, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD, tol, window ? window : unpadded, s));
         bbme::ConsistencyStats e;
         e.consistent = s[0]; e.inconsistent = s[1]; e.outside = s[2]; e.discrepancy = s[3];
+        return e;
+    }
+    // The frame at phase num / den between image1 and image2 after estimateBidirectional() (the interpolation rule of
+    // include/bbme.h): the padded plane; an upsample = 4 MF interpolates its 4x planes.
+    bbme::Image8 interpolate(int num = 1, int den = 2)
+    {
+        bbme::Image8 img(padded_height, padded_width);
+        bbme::check(bbme_get_interpolated_host(ctx_, 0, num, den, img.data.data()));
+        return img;
+    }
+    // Its statistics over window {cx0, cy0, cw, ch} in cells; nullptr = unpaddedCells.
+    bbme::InterpolationStats interpolationStats(int num = 1, int den = 2, const int *window = nullptr)
+    {
+        int unpadded[4];
+        unpaddedCells(unpadded);
+        unsigned long long s[4] = {0, 0, 0, 0};
+        bbme::check(bbme_interpolation_stats(ctx_, num, den, window ? window : unpadded, s));
+        bbme::InterpolationStats e;
+        e.forward = s[0]; e.backward = s[1]; e.zero = s[2]; e.cost = s[3];
         return e;
     }
     bbme_ctx *context() { return ctx_; }

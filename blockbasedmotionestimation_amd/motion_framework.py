@@ -23,6 +23,7 @@ from . import _capi
 
 DIR_FORWARD, DIR_BACKWARD = 0, 1                           # bbme_set_direction, `which` of the consistency calls
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2      # classes of a consistency mask
+INTERPOLATION_STAT_KEYS = ("forward", "backward", "zero", "cost")      # the hypothesis a cell selected (0, 1, 2), their SADs
 
 
 def _check_upsample(upsample):
@@ -398,6 +399,83 @@ class MF:
             C.c_void_p(stats.data_ptr() if stats is not None else 0), C.c_void_p(hip_stream_handle or 0)))
         return mask, stats
 
+    # -- motion-compensated interpolation between the two frames (the interpolation rule of include/bbme.h) ---------------
+    def _get_interpolated(self, pair, num, den, out, what):
+        shape = (self.padded_height, self.padded_width)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
+        _capi.check(self._lib.bbme_get_interpolated_host(self._ctx, pair, int(num), int(den), out.ctypes.data))
+        return out
+
+    def interpolate(self, num=1, den=2, pair=0, out=None):
+        """The frame at phase num / den between image1 (phase 0) and image2 (phase 1) after estimate_bidirectional_async():
+        every 2x2 cell motion-compensated along the forward vector, the reversed backward vector or no motion, whichever
+        matches best, and blended -> the padded (H_pad, W_pad) uint8 plane.  An upsample=4 context interpolates its 4x planes."""
+        return self._get_interpolated(pair, num, den, out, "interpolate")
+
+    def interpolate_run(self, den, pair=0):
+        """All den - 1 phases 1 / den .. (den - 1) / den from one launch -> (den - 1, H_pad, W_pad) uint8."""
+        import torch
+        den = int(den)
+        if not 2 <= den <= 256:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_run: den %d outside 2..256" % den)
+        h, w = self.padded_height, self.padded_width
+        frames = torch.empty((den - 1, h, w), dtype=torch.uint8, device="cuda:%d" % self.device)
+        _capi.check(self._lib.bbme_interpolate_device(self._ctx, pair, 1, den - 1, den, C.c_void_p(frames.data_ptr()), w, h * w, None))
+        self.synchronize()
+        return frames.cpu().numpy()
+
+    def _interpolation_stats(self, num, den, window):
+        if window is None:
+            window = self.default_cell_window()
+        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
+        pairs = getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_interpolation_stats(self._ctx, int(num), int(den), win, s))
+        return [dict(zip(INTERPOLATION_STAT_KEYS, s[4 * p:4 * p + 4])) for p in range(pairs)]
+
+    def interpolation_stats(self, num=1, den=2, window=None):
+        """dict(forward, backward, zero, cost) of that frame over window (cx0, cy0, cw, ch) in cells: cells per selected
+        hypothesis and the sum of the selected 2x2 SADs.  Default window: default_cell_window(); "all": every cell."""
+        return self._interpolation_stats(num, den, window)[0]
+
+    def cells_interpolate_device(self, fwd, bwd=None, num0=1, count=1, den=2, pair=0, out=None, sel=None, stats=None, window=None,
+                                 hip_stream_handle=None):
+        """The interpolation rule on the context's planes of `pair` and any two cell grids in HBM: fwd, bwd (may be None)
+        contiguous int16 CUDA tensors (CH, CW, 2); phases num0 .. num0 + count - 1 of den in one launch into out, a uint8 CUDA
+        tensor (count, H_pad, W_pad), sel, uint8 (count, CH, CW) -- rows and frames of both may be further apart than packed --,
+        and stats, a contiguous int64 or uint64 CUDA tensor (count, 4) of (forward, backward, zero, cost) over window (cx0, cy0,
+        cw, ch) in cells (None = all cells); each of the three may be None.  On the given HIP stream (default: the
+        context's), ordered behind the context's stream; no host wait.  Needs frames, but no estimate."""
+        import torch
+        ch, cw = self.cells_shape
+        count = int(count)
+        for t in (fwd, bwd):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_device: grids must be contiguous int16 CUDA tensors "
+                                      "of shape (%d, %d, 2)" % (ch, cw))
+        for t, shape, name in ((out, (count, self.padded_height, self.padded_width), "out"), (sel, (count, ch, cw), "sel")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == shape and t.stride(2) == 1):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_device: %s must be a uint8 CUDA tensor of shape %s "
+                                      "with unit column stride" % (name, shape))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and tuple(stats.shape) == (count, 4)
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_device: stats must be a contiguous int64 or uint64 CUDA "
+                                  "tensor of shape (%d, 4)" % count)
+        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+        _capi.check(self._lib.bbme_cells_interpolate_device(
+            self._ctx, pair, ptr(fwd), ptr(bwd), int(num0), count, int(den), win,
+            ptr(out), out.stride(1) if out is not None else 0, max(out.stride(0), 0) if out is not None else 0,
+            ptr(sel), sel.stride(1) if sel is not None else 0, max(sel.stride(0), 0) if sel is not None else 0,
+            ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+        return out, sel, stats
+
     def calcMotionBlockMatchingSubsampled(self, scale=None):
         """calcMotionBlockMatching followed by get_subsampled_flow: nothing dense crosses PCIe."""
         self.estimate_async()
@@ -575,6 +653,14 @@ class MFBatch(MF):
         """MF.consistency_stats of every pair, in order, from one launch."""
         return self._consistency_stats(which, tol, window)
 
+    def get_pair_interpolated(self, pair, num=1, den=2, out=None):
+        """MF.interpolate of one pair."""
+        return self._get_interpolated(pair, num, den, out, "get_pair_interpolated")
+
+    def interpolation_stats_all(self, num=1, den=2, window=None):
+        """MF.interpolation_stats of every pair, in order, from one launch."""
+        return self._interpolation_stats(num, den, window)
+
     def compensation_errors(self, level=0, block=2, window=None):
         """MF.compensation_error of every pair, in order, from one launch."""
         return self._compensation_stats(level, block, window)
@@ -699,6 +785,29 @@ def cells_consistency(a, b, tol=1, window=None):
     win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
     _capi.check(_capi.lib().bbme_cells_consistency_host(a.ctypes.data, b.ctypes.data, cw, ch, int(tol), win, mask.ctypes.data, s))
     return mask, dict(zip(("consistent", "inconsistent", "outside", "discrepancy"), list(s)))
+
+
+def interpolate_cells(image1, image2, fwd, bwd=None, num=1, den=2, window=None):
+    """The interpolation rule of include/bbme.h on the CPU (bbme_interpolate_host): image1, image2 uint8 (H, W) planes of even
+    size, fwd and bwd (may be None) int16 (H / 2, W / 2, 2) cell grids -> (frame (H, W) uint8, selection (H / 2, W / 2) uint8,
+    dict(forward, backward, zero, cost) over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    image1 = np.ascontiguousarray(image1, np.uint8)
+    image2 = np.ascontiguousarray(image2, np.uint8)
+    fwd = np.ascontiguousarray(fwd, np.int16)
+    bwd = None if bwd is None else np.ascontiguousarray(bwd, np.int16)
+    if image1.ndim != 2 or image1.shape != image2.shape:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells: two uint8 planes of one shape (H, W)")
+    h, w = image1.shape
+    if fwd.shape != (h // 2, w // 2, 2) or (bwd is not None and bwd.shape != fwd.shape):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells: int16 grids of shape (H / 2, W / 2, 2)")
+    out = np.empty((h, w), np.uint8)
+    sel = np.empty((h // 2, w // 2), np.uint8)
+    s = (C.c_ulonglong * 4)()
+    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+    _capi.check(_capi.lib().bbme_interpolate_host(image1.ctypes.data, image2.ctypes.data, w, h, fwd.ctypes.data,
+                                                  None if bwd is None else bwd.ctypes.data, int(num), int(den), win,
+                                                  out.ctypes.data, sel.ctypes.data, s))
+    return out, sel, dict(zip(INTERPOLATION_STAT_KEYS, list(s)))
 
 
 def plan_padding(width, height, search_size, block_size):

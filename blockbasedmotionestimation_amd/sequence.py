@@ -367,6 +367,67 @@ def estimate_frames_bidirectional(frames, search_size, block_size, device=None, 
     return out
 
 
+def interpolate_frames(frames, search_size, block_size, factor, device=None, in_flight=4, batch=2):
+    """Frame-rate up-conversion of a video on ONE GPU: every original frame, and factor - 1 interpolated frames (phases k /
+    factor, the interpolation rule of include/bbme.h) between each consecutive two -> factor * (len(frames) - 1) + 1 uint8
+    (H, W) frames, the interpolated ones the unpadded windows of the padded result.  Runs on the chain plan of
+    estimate_frames_bidirectional (same contexts, rounds and padding of a short round): every frame is set once, both fields
+    of a pair come from the same planes, and the factor - 1 frames of a pair from one launch (MF.interpolate_run)."""
+    from .motion_framework import MFChain
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    factor = int(factor)
+    if not 2 <= factor <= 256:
+        raise ValueError("interpolate_frames: factor %d outside 2..256" % factor)
+    n_pairs = len(frames) - 1
+    if n_pairs < 1:
+        return frames
+    if device is None:
+        device = local_device()
+    per = max(1, min(batch, in_flight, n_pairs))
+    n_slots = max(1, in_flight // per)
+    rounds = plan_frame_segments(n_pairs, n_slots, per)
+    n_ctx = 1 + max(r[0] for r in rounds)
+    chains = [None] * n_ctx
+    between = [None] * n_pairs
+    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
+
+    def collect(slot):
+        first, count = pending[slot]
+        pending[slot] = None
+        mf = chains[slot]
+        h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
+        for p in range(count):
+            run = mf.interpolate_run(factor, pair=p)       # waits for this context's stream only
+            between[first + p] = [np.ascontiguousarray(f[py:py + h, px:px + w]) for f in run]
+
+    try:
+        for slot, first, count, carry in rounds:
+            run = frames[first + 1:first + count + 1]
+            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
+            if not carry:
+                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device)
+                if n_ctx * per > 1:
+                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
+            else:
+                collect(slot)                              # reads the planes the roll is about to replace
+                chains[slot].advance(run)
+            chains[slot].estimate_bidirectional_async()
+            pending[slot] = (first, count)
+        for slot in range(n_ctx):
+            if pending[slot]:
+                collect(slot)
+    finally:
+        for mf in chains:
+            if mf is not None:
+                mf.close()
+    out = []
+    for p in range(n_pairs):
+        out.append(frames[p])
+        out.extend(between[p])
+    out.append(frames[-1])
+    return out
+
+
 def _gpu_compute(search_size, block_size, device):
     from .motion_framework import MF
 

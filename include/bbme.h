@@ -18,6 +18,7 @@
 #ifndef BBME_H
 #define BBME_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -410,6 +411,49 @@ int bbme_get_consistency_host(bbme_ctx *ctx, int pair, int which, int tol, uint8
 int bbme_consistency_stats(bbme_ctx *ctx, int which, int tol, const int *window, unsigned long long *stats);
 int bbme_cells_consistency_host(const int16_t *a, const int16_t *b, int cells_w, int cells_h, int tol, const int *window,
                                 uint8_t *mask, unsigned long long *stats4);
+
+/* INTERPOLATION RULE (this project's own; the reference has no interpolation): the frame at phase num / den between frame 1
+ * (phase 0) and frame 2 (phase 1) of a pair, motion-compensated from both fields.  Inputs: the level-0 padded planes I1 and I2
+ * (W0 x H0 bytes), the cell grid F on frame 1 (forward) and, optionally, the cell grid B on frame 2 (backward), CH x CW int16
+ * (dx, dy) pairs each (CH = H0 / 2, CW = W0 / 2), and the phase, 2 <= den <= 256 and 0 < num < den.  All arithmetic is in 32-bit
+ * integers; den / 2 is the integer half; floor_div rounds towards minus infinity.
+ * Output cell (cx, cy) with origin (ox, oy) = (2 cx, 2 cy) has up to three hypotheses, in this order:
+ *   k = 0: v = F[cy][cx];   k = 1: v = -B[cy][cx] (absent without B);   k = 2: v = (0, 0).
+ * For a hypothesis v = (vx, vy): the shift s = (floor_div(num vx + den / 2, den), floor_div(num vy + den / 2, den)),
+ * p1 = (ox, oy) - s and p2 = p1 + v (so p2 - p1 = v exactly).  It is valid when both 2x2 cells lie inside the plane,
+ * 0 <= p1.x, p2.x <= W0 - 2 and 0 <= p1.y, p2.y <= H0 - 2 (k = 2 always is), and its cost is the sum over the four pixels of
+ * |I1[p1 + (j, i)] - I2[p2 + (j, i)]|, 0..1020.  The valid hypothesis of the smallest cost is selected; of equal costs the earliest.
+ * With its p1 and p2, out[oy + i][ox + j] = ((den - num) I1[p1 + (j, i)] + num I2[p2 + (j, i)] + den / 2) / den for 0 <= i, j < 2.
+ * The selection map holds one byte k per cell.  The statistics over a window {cx0, cy0, cw, ch} IN CELLS (NULL = all cells) are
+ * four exact 64-bit integers: cells that selected k = 0, k = 1, k = 2, and the sum of the selected costs.
+ * One call makes `count` consecutive phases num0 .. num0 + count - 1 of one den in ONE launch (the phase is a grid dimension;
+ * planes and grids come from L2 for all but the first): frame q at d_out + q out_stride, its map at d_sel + q sel_stride, its
+ * statistics at d_stats4[4 q ..].  A context created for up-sampled frames (bbme_set_frames_*_x4) interpolates its 4x planes.
+ * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, den outside 2..256, num0 < 1, count < 1,
+ * num0 + count > den, out_pitch < W0, sel_pitch < CW, a stride below one frame (out_pitch H0, sel_pitch CH) when count > 1, a
+ * window as for the consistency rule, an odd width or height on the host call; BBME_ERR_STATE when frames are unset or a chain
+ * slot is unset, and for the three context-level calls without a valid pair of fields (as the backward cells).  None of these
+ * calls changes context state; their scratch buffers are independent of the other getters'.  All work on single, batched and
+ * chain contexts; in direction BACKWARD the two planes exchange, as for every plane-reading call.
+ * bbme_cells_interpolate_device: the context's planes of `pair` and ANY two grids in HBM of its cell geometry (d_bwd may be
+ * null); d_out, d_sel and d_stats4 each may be null, not all three; on hip_stream (NULL = the ctx stream; another stream is
+ * first ordered behind it); no host wait; needs no valid pair of fields.  Launches with d_stats4 share one scratch buffer per
+ * context: the caller orders those it issues on different streams.
+ * bbme_interpolate_device: the same on the context's own two fields, frames only.
+ * bbme_get_interpolated_host: one phase of the context's own fields; synchronises; packed W0 x H0 bytes.
+ * bbme_interpolation_stats: EVERY pair in one launch, stats[4 p + k]; synchronises (like bbme_consistency_stats).
+ * bbme_interpolate_host: the same rule on the CPU, no GPU, on packed width x height planes (both even) and packed
+ * (height / 2) x (width / 2) grids; out, sel (packed) and stats4 each may be NULL, not all three. */
+int bbme_cells_interpolate_device(bbme_ctx *ctx, int pair, const int16_t *d_fwd, const int16_t *d_bwd, int num0, int count, int den,
+                                  const int *window, uint8_t *d_out, int out_pitch, size_t out_stride, uint8_t *d_sel,
+                                  int sel_pitch, size_t sel_stride, unsigned long long *d_stats4, void *hip_stream);
+int bbme_interpolate_device(bbme_ctx *ctx, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch,
+                            size_t out_stride, void *hip_stream);
+int bbme_get_interpolated_host(bbme_ctx *ctx, int pair, int num, int den, uint8_t *out);
+int bbme_interpolation_stats(bbme_ctx *ctx, int num, int den, const int *window, unsigned long long *stats);
+int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *fwd,
+                          const int16_t *bwd, int num, int den, const int *window, uint8_t *out, uint8_t *sel,
+                          unsigned long long *stats4);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
