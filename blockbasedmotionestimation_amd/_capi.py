@@ -116,6 +116,11 @@ SIGNATURES = {
     "bbme_interpolation_stats": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_interpolate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_cells_color_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_flow_color_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_get_flow_color_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),
+    "bbme_flow_ranges": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_cells_color_host": (C.c_int, [C.c_void_p] + [C.c_int] * 7 + [C.c_float, C.c_void_p, C.c_void_p]),
     "bbme_pgm_write": (C.c_int, [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_flow_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p)]),
     "bbme_get_flow_host_pair": (C.c_int, [_ctx, C.c_int, C.c_void_p]),

@@ -290,6 +290,10 @@ struct bbme_ctx {
     DevBuf<uint8_t> ip_plane;                     // bbme_get_interpolated_host: a packed W0 x H0 frame before its download
     DevBuf<unsigned long long> ip_stats;          // interpolation statistics: 4 words per pair, then the partials of k_interpolate of
                                                   // bbme_interpolation_stats (every pair) and of bbme_cells_interpolate_device (every phase)
+    DevBuf<uint32_t> color_range;                 // colour coding: the key words of every slot (pair 0 .. batch - 1, then the slot of
+                                                  // bbme_cells_color_device; k_color_range), then five floats per slot
+    DevBuf<uint8_t> color_img;                    // bbme_get_flow_color_host: the packed B,G,R image before its download (grown to
+                                                  // the largest asked for)
 };
 
 namespace {
@@ -1942,6 +1946,163 @@ int bbme_consistency_stats(bbme_ctx *c, int which, int tol, const int *window, u
     if (int rc = enqueue_fb(c, which ? b : f, which ? s_b : s_f, which ? f : b, which ? s_f : s_b, c->batch, tol, window, nullptr, 0,
                             c->fb_stats + (size_t)4 * BBME_MAX_BATCH, c->fb_stats, c->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(stats, c->fb_stats, (size_t)4 * sizeof(unsigned long long) * c->batch, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+// ---- colour coding of a cell grid: Flow::MotionToColor of the subsampled field (the colour rule of include/bbme.h) ----------
+
+// slots of bbme_ctx::color_range: one per pair, and one for the grids a caller brings (bbme_cells_color_device)
+constexpr int kColorSlots = BBME_MAX_BATCH + 1;
+
+// scale and the image it gives; with an image, its pitch.  Touches no device.
+static int check_color(const bbme_ctx *c, int scale, const uint8_t *d_bgr, int pitch, const char *what, int *ow, int *oh)
+{
+    if (scale < 1) return bbme::fail(BBME_ERR_INVALID, "%s: scale %d < 1", what, scale);
+    *ow = (int)(((long long)c->geom.width + scale - 1) / scale);
+    *oh = (int)(((long long)c->geom.height + scale - 1) / scale);
+    if (d_bgr && pitch < 3 * *ow) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x %d bytes", what, pitch, *ow);
+    return BBME_OK;
+}
+
+// the cells `which` names, every pair of them `*stride` words apart
+static int color_source(const bbme_ctx *c, int which, const char *what, const mv_t **cells, uint32_t *stride)
+{
+    const Level &L = c->lv[0];
+    if (which == BBME_DIR_BACKWARD) {
+        if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
+        *cells = c->bwd_cells;
+        *stride = c->bwd_stride;
+    } else {
+        if (L.cur_block != 2) return bbme::fail(BBME_ERR_STATE, "%s: level 0 has not been regularised down to 2x2 blocks", what);
+        *cells = L.cur_grid;
+        *stride = L.grid_stride(L.cur_grid);
+    }
+    return BBME_OK;
+}
+
+// Range pass over `pairs` grids (s_cells words apart) into slots slot .. slot + pairs - 1, when somebody reads it -- the caller
+// (want_range; d_range: also there) or the image, which needs the max radius unless maxmotion overrides it --, then the image of
+// the first grid into d_bgr, if any.  All on `stream`, no host wait.
+static int enqueue_color(bbme_ctx *c, const mv_t *cells, uint32_t s_cells, int pairs, int slot, int scale, float maxmotion,
+                         uint8_t *d_bgr, int pitch, bool want_range, float *d_range, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    ColorArgs a{};
+    a.cells = cells; a.s_cells = s_cells; a.cell_cols = L.width / 2;
+    a.pad_x = c->geom.pad_x; a.pad_y = c->geom.pad_y; a.scale = scale;
+    a.ow = (int)(((long long)c->geom.width + scale - 1) / scale);
+    a.oh = (int)(((long long)c->geom.height + scale - 1) / scale);
+    a.ncx = scale == 1 ? ((a.pad_x + c->geom.width - 1) >> 1) - (a.pad_x >> 1) + 1 : a.ow;
+    a.ncy = scale == 1 ? ((a.pad_y + c->geom.height - 1) >> 1) - (a.pad_y >> 1) + 1 : a.oh;
+    uint32_t *keys = c->color_range + (size_t)slot * kColorKeyCopies * kColorKeyStride;
+    float *range = reinterpret_cast<float *>(c->color_range + (size_t)kColorSlots * kColorKeyCopies * kColorKeyStride) + 5 * slot;
+    if (want_range || d_range || !(maxmotion > 0)) {
+        a.keys = keys;
+        a.tiles_x = (a.ncx + 256 * kColorCellsPerLane - 1) / (256 * kColorCellsPerLane);
+        const long long groups = (long long)a.tiles_x * a.ncy;
+        hipLaunchKernelGGL(k_color_range_init, dim3((unsigned)pairs), dim3(256), 0, stream, keys);
+        hipLaunchKernelGGL(k_color_range, dim3((unsigned)groups, (unsigned)pairs), dim3(256), 0, stream, a);
+        hipLaunchKernelGGL(k_color_range_finish, dim3((unsigned)pairs), dim3(64), 0, stream, keys, range, d_range);
+    }
+    if (d_bgr) {
+        a.range = range; a.maxmotion = maxmotion; a.out = d_bgr; a.pitch = pitch;
+        a.tiles_x = (a.ncx + 63) / 64;
+        const long long tiles = (long long)a.tiles_x * ((a.ncy + 4 * kColorRowsPerWave - 1) / (4 * kColorRowsPerWave));
+        hipLaunchKernelGGL(k_color_image, dim3((unsigned)tiles), dim3(256), 0, stream, a);
+    }
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+// the five floats of every slot, behind the slots' key words
+static const float *color_floats(const bbme_ctx *c)
+{
+    return reinterpret_cast<const float *>(c->color_range + (size_t)kColorSlots * kColorKeyCopies * kColorKeyStride);
+}
+
+static int color_scratch(bbme_ctx *c)
+{
+    return c->color_range.ensure((size_t)kColorSlots * (kColorKeyCopies * kColorKeyStride + 5), "the colour ranges");
+}
+
+int bbme_cells_color_device(bbme_ctx *c, const int16_t *d_cells, int scale, float maxmotion, uint8_t *d_bgr, int out_pitch_bytes,
+                            float *d_range, void *hip_stream)
+{
+    const char *what = "bbme_cells_color_device";
+    if (int rc = check_ctx(c)) return rc;
+    if (!d_cells || (!d_bgr && !d_range)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    int ow, oh;
+    if (int rc = check_color(c, scale, d_bgr, out_pitch_bytes, what, &ow, &oh)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = color_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_color(c, reinterpret_cast<const mv_t *>(d_cells), 0, 1, BBME_MAX_BATCH, scale, maxmotion, d_bgr, out_pitch_bytes,
+                         false, d_range, stream);
+}
+
+int bbme_flow_color_device(bbme_ctx *c, int pair, int which, int scale, float maxmotion, uint8_t *d_bgr, int out_pitch_bytes,
+                           float *d_range, void *hip_stream)
+{
+    const char *what = "bbme_flow_color_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (which != BBME_DIR_FORWARD && which != BBME_DIR_BACKWARD) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    if (!d_bgr && !d_range) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    int ow, oh;
+    if (int rc = check_color(c, scale, d_bgr, out_pitch_bytes, what, &ow, &oh)) return rc;
+    const mv_t *cells;
+    uint32_t stride;
+    if (int rc = color_source(c, which, what, &cells, &stride)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = color_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_color(c, cells + (size_t)pair * stride, 0, 1, pair, scale, maxmotion, d_bgr, out_pitch_bytes, false, d_range, stream);
+}
+
+int bbme_get_flow_color_host(bbme_ctx *c, int pair, int which, int scale, float maxmotion, uint8_t *bgr, float *range5)
+{
+    const char *what = "bbme_get_flow_color_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (which != BBME_DIR_FORWARD && which != BBME_DIR_BACKWARD) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    if (!bgr && !range5) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    int ow, oh;
+    if (int rc = check_color(c, scale, nullptr, 0, what, &ow, &oh)) return rc;
+    const mv_t *cells;
+    uint32_t stride;
+    if (int rc = color_source(c, which, what, &cells, &stride)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = color_scratch(c)) return rc;
+    const size_t bytes = (size_t)ow * oh * 3;
+    if (bgr && bytes > c->color_img.size()) {
+        HIP_TRY(hipStreamSynchronize(c->stream));     // the old buffer may still be being read
+        if (int rc = c->color_img.ensure(bytes, "the colour image")) return rc;
+    }
+    if (int rc = enqueue_color(c, cells + (size_t)pair * stride, 0, 1, pair, scale, maxmotion, bgr ? c->color_img.get() : nullptr, 3 * ow,
+                               range5 != nullptr, nullptr, c->stream)) return rc;
+    if (bgr) HIP_TRY(hipMemcpyAsync(bgr, c->color_img, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (range5)
+        HIP_TRY(hipMemcpyAsync(range5, color_floats(c) + 5 * pair, 5 * sizeof(float),
+                               hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_flow_ranges(bbme_ctx *c, int which, int scale, float *ranges)
+{
+    const char *what = "bbme_flow_ranges";
+    if (int rc = check_ctx(c)) return rc;
+    if (which != BBME_DIR_FORWARD && which != BBME_DIR_BACKWARD) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    if (!ranges) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    int ow, oh;
+    if (int rc = check_color(c, scale, nullptr, 0, what, &ow, &oh)) return rc;
+    const mv_t *cells;
+    uint32_t stride;
+    if (int rc = color_source(c, which, what, &cells, &stride)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = color_scratch(c)) return rc;
+    if (int rc = enqueue_color(c, cells, stride, c->batch, 0, scale, -1.0f, nullptr, 0, true, nullptr, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(ranges, color_floats(c), (size_t)5 * sizeof(float) * c->batch,
+                           hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
 }
 

@@ -434,6 +434,57 @@ void motion_to_color(const float *flow, int width, int height, float maxmotion, 
     }
 }
 
+// The colour rule of include/bbme.h on a 2x2-cell grid: MotionToColor of the field the driver's subsampling makes of the
+// grid, with compute_color's expressions except the hue angle, which is the double atan2 rounded to float (what the kernels
+// of bbme_kernels.hpp can reproduce; compute_color's float atan2 is whatever the platform's libm makes of it).
+void cells_color(const int16_t *cells, int cells_w, int width, int height, int pad_x, int pad_y, int scale, float maxmotion,
+                 uint8_t *bgr, float range[5])
+{
+#pragma clang fp contract(off)
+    const int ow = (int)(((long long)width + scale - 1) / scale), oh = (int)(((long long)height + scale - 1) / scale);
+    const float s = (float)scale;
+    auto cell = [&](int x, int y) { return cells + 2 * ((size_t)((pad_y + scale * y) >> 1) * cells_w + ((pad_x + scale * x) >> 1)); };
+    float maxx = -999, maxy = -999, minx = 999, miny = 999, maxrad = -1;
+    if (range || !(maxmotion > 0))
+        for (int y = 0; y < oh; ++y)
+            for (int x = 0; x < ow; ++x) {
+                const int16_t *m = cell(x, y);
+                const float fx = (float)m[0] / s, fy = (float)m[1] / s;
+                maxx = maxx > fx ? maxx : fx;
+                maxy = maxy > fy ? maxy : fy;
+                minx = minx < fx ? minx : fx;
+                miny = miny < fy ? miny : fy;
+                const float rad = std::sqrt(fx * fx + fy * fy);
+                maxrad = maxrad > rad ? maxrad : rad;
+            }
+    if (range) { range[0] = maxrad; range[1] = minx; range[2] = maxx; range[3] = miny; range[4] = maxy; }
+    if (!bgr) return;
+    if (maxmotion > 0) maxrad = maxmotion;
+    if (maxrad == 0) maxrad = 1;
+    const int ncols = ColorWheel::kCols;
+    for (int y = 0; y < oh; ++y)
+        for (int x = 0; x < ow; ++x) {
+            const int16_t *m = cell(x, y);
+            const float fx = (float)m[0] / s / maxrad, fy = (float)m[1] / s / maxrad;
+            const float rad = std::sqrt(fx * fx + fy * fy);
+            const float angle = (float)std::atan2((double)-fy, (double)-fx);
+            const float a = (float)((double)angle / 3.14159265358979323846);
+            const float fk = (a + 1.0f) / 2.0f * (float)(ncols - 1);
+            const int k0 = (int)fk;
+            const int k1 = (k0 + 1) % ncols;
+            const float f = fk - (float)k0;
+            uint8_t *pix = bgr + 3 * ((size_t)y * ow + x);
+            for (int b = 0; b < 3; ++b) {
+                const float col0 = (float)g_wheel.rgb[k0][b] / 255.0f;
+                const float col1 = (float)g_wheel.rgb[k1][b] / 255.0f;
+                float col = (1 - f) * col0 + f * col1;
+                if (rad <= 1) col = 1 - rad * (1 - col);
+                else col = (float)(col * .75);
+                pix[2 - b] = (uint8_t)(int)(255.0 * col);
+            }
+        }
+}
+
 int ppm_write_bgr(const char *filename, int width, int height, const uint8_t *bgr)
 {
     FILE *f = fopen(filename, "wb");
@@ -594,6 +645,20 @@ int bbme_motion_compensate_host(const uint8_t *image1, const uint8_t *image2, in
                    (long long)window[0] + window[2] > width || (long long)window[1] + window[3] > height))
         return bbme::fail(BBME_ERR_INVALID, "bbme_motion_compensate_host: window not inside the %dx%d plane", width, height);
     bbme::motion_compensate(image1, image2, width, height, grid, grid_block, block, fill, window, out, stats4);
+    return BBME_OK;
+}
+
+int bbme_cells_color_host(const int16_t *cells, int cells_w, int cells_h, int width, int height, int pad_x, int pad_y, int scale,
+                          float maxmotion, uint8_t *bgr, float *range5)
+{
+    const char *what = "bbme_cells_color_host";
+    if (!cells || (!bgr && !range5)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (scale < 1) return bbme::fail(BBME_ERR_INVALID, "%s: scale %d < 1", what, scale);
+    if (cells_w < 1 || cells_h < 1 || width < 1 || height < 1 || pad_x < 0 || pad_y < 0 ||
+        (long long)pad_x + width > 2LL * cells_w || (long long)pad_y + height > 2LL * cells_h)
+        return bbme::fail(BBME_ERR_INVALID, "%s: the %dx%d frame at (%d, %d) is not inside the %dx%d cells", what, width, height,
+                          pad_x, pad_y, cells_w, cells_h);
+    bbme::cells_color(cells, cells_w, width, height, pad_x, pad_y, scale, maxmotion, bgr, range5);
     return BBME_OK;
 }
 

@@ -2160,6 +2160,243 @@ __global__ __launch_bounds__(256) void k_subsample(const mv_t *cells, int cell_c
 }
 
 // =======================================================================================
+// Flow::MotionToColor (rw_flow.cpp:202-275) of the subsampled field, straight from the 2x2-cell grid (the colour rule of
+// include/bbme.h).  Pixel (x, y) of the ow x oh image samples cell ((pad_y + s y) >> 1, (pad_x + s x) >> 1), so the field has
+// one value per SAMPLED cell: ncx x ncy of them, sampled column i being cell column (pad_x >> 1) + i at s = 1 (a cell then
+// covers up to 2x2 pixels) and (pad_x + s i) >> 1 = pixel column i at s >= 2.  Both passes evaluate sampled cells, not pixels.
+//   k_color_range_init    the five words of every pair <- the keys of the reference's sentinels -1, 999, -999, 999, -999
+//   k_color_range         max radius, min / max u, min / max v over the sampled cells: a workgroup takes 256 kColorCellsPerLane
+//                         consecutive cells of one sampled row, a lane folds its cells, a wave its lanes by shuffles, the
+//                         workgroup its four waves through LDS, and five lanes issue one atomic max / min each on the pair's
+//                         words.  The words hold float_key(), an order-preserving map of float bits to unsigned integers, so
+//                         the result is the exact max / min whatever the schedule.  The five words exist kColorKeyCopies times
+//                         per pair, 128 bytes apart, and workgroup g adds to copy g mod kColorKeyCopies: two thousand
+//                         workgroups adding to ONE line took 50 us per 4K pair, the line's atomics being served one after the
+//                         other (profiles/r10_flow_color.txt).
+//   k_color_range_finish  folds the copies and turns keys into floats (the context's copy that k_color_image reads, the caller's)
+//   k_color_image         a workgroup takes 64 sampled columns x 4 kColorRowsPerWave sampled rows, one wave per row (every fourth
+//                         row of them, one after the other): every lane colours one cell (B | G << 8 | R << 16) into LDS,
+//                         then the wave writes the pixel row(s) its cells cover: the bytes of
+//                         the row segment as whole dwords at 4-byte aligned addresses, each funnel-shifted from the two pixels
+//                         it straddles, and single bytes only for the up to 3 + 3 bytes in front of the first and behind the
+//                         last aligned dword (none when the caller's rows are dword-aligned and s >= 2 or pad_x is even: a
+//                         tile's segment is then 192 or 384 bytes from a multiple of 192 or 384).
+// The reference's float / double expression order is kept and nothing is contracted into an FMA; the hue angle is the double
+// atan2 rounded to float (include/bbme.h says why).  The 55 x 3 wheel, already divided by 255.0f, is constant memory copied to LDS.
+// =======================================================================================
+struct ColorWheelTable {
+    float c[55 * 3];                                       // entry k, channel b (R, G, B) -> (float)level / 255.0f
+    constexpr ColorWheelTable() : c{}
+    {
+        const int len[6] = {15, 6, 4, 11, 13, 6};          // RY YG GC CB BM MR (makecolorwheel, rw_flow.cpp:277-300)
+        const int moving[6] = {1, 0, 2, 1, 0, 2};          // channel that changes
+        const int rising[6] = {1, 0, 1, 0, 1, 0};          // ... upwards or downwards
+        const int base[6][3] = {{255, 0, 0}, {255, 255, 0}, {0, 255, 0}, {0, 255, 255}, {0, 0, 255}, {255, 0, 255}};
+        int k = 0;
+        for (int t = 0; t < 6; ++t)
+            for (int i = 0; i < len[t]; ++i, ++k) {
+                const int step = 255 * i / len[t];
+                for (int b = 0; b < 3; ++b) {
+                    const int level = b != moving[t] ? base[t][b] : rising[t] ? step : 255 - step;
+                    c[3 * k + b] = (float)level / 255.0f;
+                }
+            }
+    }
+};
+__constant__ ColorWheelTable d_color_wheel{};
+
+struct ColorArgs {
+    const mv_t *cells;                    // cell_cols entries per row
+    uint32_t s_cells;                     // words from pair to pair (k_color_range: blockIdx.y = pair)
+    int cell_cols, pad_x, pad_y, scale;
+    int ow, oh;                           // the image: ceil(W / scale) x ceil(H / scale)
+    int ncx, ncy;                         // sampled cells per row, rows of them
+    uint32_t *keys;                       // k_color_range: kColorKeyCopies x kColorKeyStride words per pair
+    const float *range;                   // k_color_image: the pair's five floats ([0] = max radius)
+    float maxmotion;
+    uint8_t *out;                         // B, G, R per pixel, rows pitch bytes apart
+    int pitch;
+    int tiles_x;                          // k_color_image: ceil(ncx / 64); k_color_range: ceil(ncx / (256 kColorCellsPerLane))
+};
+
+constexpr int kColorCellsPerLane = 4;
+constexpr int kColorKeyCopies = 32;       // copies of a pair's five words ...
+constexpr int kColorKeyStride = 32;       // ... this many words apart (one 128-byte line each)
+
+__device__ __forceinline__ uint32_t float_key(float f)
+{
+    const uint32_t b = __float_as_uint(f);
+    return b ^ ((uint32_t)((int32_t)b >> 31) | 0x80000000u);
+}
+__device__ __forceinline__ float key_float(uint32_t k)
+{
+    return __uint_as_float(k ^ (((k >> 31) - 1u) | 0x80000000u));
+}
+// (float)d / (float)scale.  For scale = 2^k the quotient is d times the exactly representable 2^-k, the same bits for every
+// int16 d without the dozen instructions of a correctly rounded division (scale 1, 2 and 4 are what callers use)
+__device__ __forceinline__ float color_component(int d, int scale)
+{
+    if ((scale & (scale - 1)) == 0) return (float)d * (1.0f / (float)scale);
+    return (float)d / (float)scale;
+}
+__device__ __forceinline__ int color_cell_col(const ColorArgs &a, int i) { return a.scale == 1 ? (a.pad_x >> 1) + i : (a.pad_x + a.scale * i) >> 1; }
+__device__ __forceinline__ int color_cell_row(const ColorArgs &a, int j) { return a.scale == 1 ? (a.pad_y >> 1) + j : (a.pad_y + a.scale * j) >> 1; }
+
+// one workgroup per pair
+__global__ __launch_bounds__(256) void k_color_range_init(uint32_t *keys)
+{
+    const int copy = threadIdx.x >> 3, k = threadIdx.x & 7;
+    if (k < 5) keys[((size_t)blockIdx.x * kColorKeyCopies + copy) * kColorKeyStride + k] = float_key(k == 0 ? -1.0f : (k & 1) ? 999.0f : -999.0f);
+}
+
+__global__ __launch_bounds__(64) void k_color_range_finish(const uint32_t *keys, float *range, float *user_range)
+{
+    const int k = threadIdx.x;
+    if (k >= 5) return;
+    const uint32_t *word = keys + (size_t)blockIdx.x * kColorKeyCopies * kColorKeyStride + k;
+    uint32_t key = word[0];
+    for (int c = 1; c < kColorKeyCopies; ++c) {
+        const uint32_t other = word[c * kColorKeyStride];
+        key = (k == 1 || k == 3) ? min(key, other) : max(key, other);
+    }
+    const float f = key_float(key);
+    range[5 * blockIdx.x + k] = f;
+    if (user_range) user_range[5 * blockIdx.x + k] = f;
+}
+
+__global__ __launch_bounds__(256) void k_color_range(ColorArgs a)
+{
+#pragma clang fp contract(off)
+    const mv_t *cells = a.cells + (size_t)blockIdx.y * a.s_cells;
+    float r[5] = {-1.0f, 999.0f, -999.0f, 999.0f, -999.0f};                // max radius, min u, max u, min v, max v
+    const int j = (int)(blockIdx.x / (unsigned)a.tiles_x);
+    const int i0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * (256 * kColorCellsPerLane) + (int)threadIdx.x;
+    const mv_t *row = cells + (size_t)color_cell_row(a, j) * a.cell_cols;
+#pragma unroll
+    for (int k = 0; k < kColorCellsPerLane; ++k) {
+        const int i = i0 + 256 * k;
+        if (i >= a.ncx) break;
+        const mv_t m = row[color_cell_col(a, i)];
+        const float u = color_component(mv_x(m), a.scale), v = color_component(mv_y(m), a.scale);
+        const float rad = sqrtf(u * u + v * v);
+        r[0] = r[0] > rad ? r[0] : rad;
+        r[1] = r[1] < u ? r[1] : u;
+        r[2] = r[2] > u ? r[2] : u;
+        r[3] = r[3] < v ? r[3] : v;
+        r[4] = r[4] > v ? r[4] : v;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) {
+            const float other = __shfl_xor(r[k], o);
+            r[k] = (k == 1 || k == 3) ? (r[k] < other ? r[k] : other) : (r[k] > other ? r[k] : other);
+        }
+    }
+    __shared__ float part[4][5];
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < 5; ++k) part[threadIdx.x >> 6][k] = r[k];
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int k = threadIdx.x;
+        const bool is_min = k == 1 || k == 3;
+        float f = part[0][k];
+        for (int w = 1; w < 4; ++w) f = is_min ? (f < part[w][k] ? f : part[w][k]) : (f > part[w][k] ? f : part[w][k]);
+        uint32_t *word = a.keys + ((size_t)blockIdx.y * kColorKeyCopies + blockIdx.x % kColorKeyCopies) * kColorKeyStride + k;
+        if (is_min) atomicMin(word, float_key(f));
+        else atomicMax(word, float_key(f));
+    }
+}
+
+// computeColor (rw_flow.cpp:251-275) of (fx, fy) -> B | G << 8 | R << 16; wheel = the table above in LDS
+__device__ __forceinline__ uint32_t color_of(float fx, float fy, const float *wheel)
+{
+#pragma clang fp contract(off)
+    const int ncols = 55;
+    const float rad = sqrtf(fx * fx + fy * fy);
+    const float angle = (float)atan2((double)-fy, (double)-fx);        // the rule's angle: double atan2, rounded to float
+    const float an = (float)((double)angle / 3.14159265358979323846);
+    const float fk = (an + 1.0f) / 2.0f * (float)(ncols - 1);
+    int k0 = (int)fk;
+    k0 = k0 < 0 ? 0 : k0 > ncols - 1 ? ncols - 1 : k0;                  // (no finite input leaves 0 .. 54; keeps the LDS index in range)
+    const int k1 = k0 + 1 == ncols ? 0 : k0 + 1;
+    const float f = fk - (float)k0;
+    uint32_t packed = 0;
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+        const float col0 = wheel[3 * k0 + b], col1 = wheel[3 * k1 + b];
+        float col = (1 - f) * col0 + f * col1;
+        if (rad <= 1) col = 1 - rad * (1 - col);
+        else col = (float)(col * .75);
+        packed |= ((uint32_t)(int)(255.0 * col) & 255u) << (8 * (2 - b));
+    }
+    return packed;
+}
+
+// sampled rows a wave of k_color_image colours, one after the other.  More than one (all cells loaded up front, the wheel copied
+// once) measured no faster at 4K (26.5 against 25.8 us with 4) and slower on a 960 x 540 picture (7.8 against 6.3 us): the
+// kernel is bound by its arithmetic, not by its loads
+constexpr int kColorRowsPerWave = 1;
+
+__global__ __launch_bounds__(256) void k_color_image(ColorArgs a)
+{
+#pragma clang fp contract(off)
+    __shared__ float s_wheel[55 * 3];
+    __shared__ uint32_t s_col[4][68];
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int i0 = (int)(blockIdx.x % (unsigned)a.tiles_x) * 64;
+    const int j0 = (int)(blockIdx.x / (unsigned)a.tiles_x) * (4 * kColorRowsPerWave) + w;      // rows j0, j0 + 4, ...
+    // every load the tile needs is under way before the first barrier: the cells of all its rows, the wheel, the max radius
+    const int cx = color_cell_col(a, min(i0 + lane, a.ncx - 1));
+    mv_t m[kColorRowsPerWave];
+#pragma unroll
+    for (int t = 0; t < kColorRowsPerWave; ++t)
+        m[t] = a.cells[(size_t)color_cell_row(a, min(j0 + 4 * t, a.ncy - 1)) * a.cell_cols + cx];
+    if (threadIdx.x < 55 * 3) s_wheel[threadIdx.x] = d_color_wheel.c[threadIdx.x];
+    if (lane < 4) s_col[w][64 + lane] = 0;
+    float maxrad = a.maxmotion > 0 ? a.maxmotion : a.range[0];
+    if (maxrad == 0) maxrad = 1;
+    // the pixel columns this tile's cells cover, [px0, px1); pixel p of them -> its cell's slot in s_col[w][]
+    const int cx0 = color_cell_col(a, i0);
+    int px0 = i0, px1 = min(a.ow, i0 + 64);
+    if (a.scale == 1) { px0 = max(0, 2 * cx0 - a.pad_x); px1 = min(a.ow, 2 * (cx0 + 64) - a.pad_x); }
+    const int nbytes = 3 * (px1 - px0);
+    const int rel0 = a.scale == 1 ? a.pad_x + px0 - 2 * cx0 : 0, sh = a.scale == 1 ? 1 : 0;
+    const uint32_t *col = s_col[w];
+    for (int t = 0; t < kColorRowsPerWave; ++t) {
+        const int j = j0 + 4 * t;
+        __syncthreads();                                     // the wheel is there (t = 0); row t - 1 has been read
+        const float u = color_component(mv_x(m[t]), a.scale), v = color_component(mv_y(m[t]), a.scale);
+        s_col[w][lane] = color_of(u / maxrad, v / maxrad, s_wheel);
+        __syncthreads();
+        if (j >= a.ncy) continue;                            // (whole waves: the barriers stay uniform)
+        int y0 = j, y1 = j + 1;                              // the pixel rows sampled row j covers
+        if (a.scale == 1) {
+            const int cy = color_cell_row(a, j);
+            y0 = max(0, 2 * cy - a.pad_y); y1 = min(a.oh, 2 * cy - a.pad_y + 2);
+        }
+        // at scale 1 a cell covers two pixel rows: when they are aligned alike, their dwords are assembled once
+        const bool twin = y1 - y0 == 2 && (a.pitch & 3) == 0;
+        for (int y = y0; y < y1; y += twin ? 2 : 1) {
+            uint8_t *row = a.out + (size_t)y * a.pitch + 3 * (size_t)px0;
+            const int head = min(nbytes, (int)((4u - (uint32_t)((uintptr_t)row & 3u)) & 3u));
+            const int ndw = (nbytes - head) >> 2, tail = nbytes - head - 4 * ndw;
+            for (int d = lane; d < ndw; d += 64) {
+                const int o = head + 4 * d, p = o / 3, ch = o - 3 * p;
+                const unsigned long long v2 = (unsigned long long)col[(rel0 + p) >> sh] | (unsigned long long)col[(rel0 + p + 1) >> sh] << 24;
+                *reinterpret_cast<uint32_t *>(row + o) = (uint32_t)(v2 >> (8 * ch));
+                if (twin) *reinterpret_cast<uint32_t *>(row + a.pitch + o) = (uint32_t)(v2 >> (8 * ch));
+            }
+            if (lane < head + tail) {                        // the bytes around the aligned dwords
+                const int o = lane < head ? lane : 4 * ndw + lane, p = o / 3, ch = o - 3 * p;
+                const uint8_t b = (uint8_t)(col[(rel0 + p) >> sh] >> (8 * ch));
+                row[o] = b;
+                if (twin) row[a.pitch + o] = b;
+            }
+        }
+    }
+}
+
+// =======================================================================================
 // MF::MF on the GPU (motion_framework.cpp:57-61, 86-106): zero border and pyrDown cascade.  Both frames of the pair
 // in one launch (blockIdx.y).  Bandwidth-bound byte work: 16 bytes per thread for the border copy, four output pixels
 // per thread for pyrDown (dword loads, the 5-tap rows as v_dot4_u32_u8 on re-aligned dwords).

@@ -2,7 +2,7 @@
 //
 //   bbme_cli frame10.pgm frame11.pgm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
-//            [--interpolate PREFIX --factor N]
+//            [--interpolate PREFIX --factor N] [--backward-color back.ppm]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -15,7 +15,9 @@
 // mask on frame 1 at tolerance 1, one byte per 2x2 cell whose top-left pixel lies in the unpadded frame MF sees (0 consistent,
 // 128 inconsistent, 255 target outside the plane), and prints the three counts.  --interpolate PREFIX --factor N (default 2)
 // writes the N - 1 frames between frame 1 and frame 2, phases k / N (the interpolation rule of include/bbme.h, from both fields),
-// as PREFIX_k.pgm, each the unpadded frame MF sees.
+// as PREFIX_k.pgm, each the unpadded frame MF sees.  --backward-color writes the colour coding (:73-75) of the backward field of a
+// bidirectional estimate at the driver's subsampling; the image is made on the GPU from the cells (the colour rule of
+// include/bbme.h) and only its bytes come back.  --color stays the host's Flow::MotionToColor of the downloaded field.
 // Defaults are the reference's literals (:19-21): 4 levels, block 32, search 64.
 #include <chrono>
 #include <cstdio>
@@ -53,7 +55,8 @@ static bool read_pgm(const char *path, bbme::Image8 &img)
 
 int main(int argc, char **argv)
 {
-    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr;
+    const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
+               *backward_color = nullptr;
     int factor = 2;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
@@ -67,6 +70,7 @@ int main(int argc, char **argv)
         else if (a == "--backward") backward = next();
         else if (a == "--occlusion") occlusion = next();
         else if (a == "--interpolate") interpolate = next();
+        else if (a == "--backward-color") backward_color = next();
         else if (a == "--factor") factor = atoi(next());
         else if (a == "--levels") levels = atoi(next());
         else if (a == "--block") block = atoi(next());
@@ -80,7 +84,7 @@ int main(int argc, char **argv)
     if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || (interpolate && (factor < 2 || factor > 256))) {
         fprintf(stderr, "usage: bbme_cli frame1.pgm frame2.pgm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
-                        "[--occlusion occ.pgm] [--interpolate PREFIX --factor N]\n");
+                        "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm]\n");
         return 2;
     }
     try {
@@ -142,6 +146,11 @@ int main(int argc, char **argv)
                 bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
                                            img.data.data() + (size_t)py * img.cols + px));
             }
+        }
+        if (backward_color) {
+            motion_pair.estimateBidirectional();
+            const bbme::ImageBGR img = motion_pair.flowColor(scale, -1.0f, true);
+            bbme::check(bbme_ppm_write_bgr(backward_color, img.cols, img.rows, img.data.data()));
         }
     } catch (const bbme::Error &e) {
         fprintf(stderr, "%s\n", e.what());

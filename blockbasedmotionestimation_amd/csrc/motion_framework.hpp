@@ -263,6 +263,19 @@ public:
         e.forward = s[0]; e.backward = s[1]; e.zero = s[2]; e.cost = s[3];
         return e;
     }
+    // Flow::MotionToColor of the field calcMotionBlockMatchingSubsampled(scale) returns, on the GPU from the cells (the colour
+    // rule of include/bbme.h): only the B,G,R image is downloaded.  backward = true: the backward field after
+    // estimateBidirectional().  scale 0 = upsample; maxmotion > 0 replaces the normalising radius; range5, if given, receives
+    // {max radius, min u, max u, min v, max v}.
+    bbme::ImageBGR flowColor(int scale = 0, float maxmotion = -1.0f, bool backward = false, float *range5 = nullptr)
+    {
+        if (scale == 0) scale = upsample;
+        const int w = padded_width - 2 * padding_x, h = padded_height - 2 * padding_y;
+        bbme::ImageBGR img(scale > 0 ? (h + scale - 1) / scale : 0, scale > 0 ? (w + scale - 1) / scale : 0);
+        bbme::check(bbme_get_flow_color_host(ctx_, 0, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD, scale, maxmotion,
+                                             img.data.data(), range5));
+        return img;
+    }
     bbme_ctx *context() { return ctx_; }
 
     const int upsample = 1;       // 4: constructed from the original frames of the reference's x4 pipeline

@@ -136,6 +136,15 @@ class MF:
         if image1.stride(1) != 1 or image2.stride(1) != 1 or image1.stride(0) != image2.stride(0):
             raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must have unit column stride and a common row pitch")
 
+    def _behind_torch(self, *tensors):
+        """torch tensors handed to a *_device call may still be being written (a fill, an upload) or read by work on torch's
+        current stream, which nothing orders against the context's non-blocking stream: order the context's stream behind it,
+        as the frame setters do.  A caller's stream is ordered behind the context's by the library, so it is covered too.  No
+        host wait."""
+        import torch
+        for dev in {t.device for t in tensors if t is not None}:
+            _capi.check(self._lib.bbme_wait_for_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
     def set_frames_device(self, image1, image2):
         """Frames already in HBM (torch uint8 CUDA tensors, H x W of the source size): (x4 up-sampling,) padding and
         pyramid on the GPU."""
@@ -243,6 +252,7 @@ class MF:
                 and out.stride(0) >= 2 * cols):
             raise _capi.BbmeError(_capi.ERR_INVALID, "subsampled_flow_device: out must be a float32 CUDA tensor of shape "
                                   "(%d, %d, 2) with unit pixel stride" % (rows, cols))
+        self._behind_torch(out)
         _capi.check(self._lib.bbme_subsampled_flow_device(self._ctx, pair, scale, C.c_void_p(out.data_ptr()),
                                                           out.stride(0) // 2, C.c_void_p(hip_stream_handle or 0)))
         return out
@@ -273,6 +283,7 @@ class MF:
                 and out.stride(1) == 1 and out.stride(0) >= w):
             raise _capi.BbmeError(_capi.ERR_INVALID, "motion_compensated_device: out must be a uint8 CUDA tensor of shape "
                                   "(%d, %d) with unit column stride" % (h, w))
+        self._behind_torch(out)
         _capi.check(self._lib.bbme_motion_compensate_device(self._ctx, pair, level, block, fill, C.c_void_p(out.data_ptr()),
                                                             out.stride(0), C.c_void_p(hip_stream_handle or 0)))
         return out
@@ -393,11 +404,85 @@ class MF:
             raise _capi.BbmeError(_capi.ERR_INVALID, "cells_consistency_device: stats must be a contiguous int64 or uint64 CUDA "
                                   "tensor of 4")
         win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+        self._behind_torch(a, b, mask, stats)
         _capi.check(self._lib.bbme_cells_consistency_device(
             self._ctx, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), int(tol), win,
             C.c_void_p(mask.data_ptr() if mask is not None else 0), mask.stride(0) if mask is not None else 0,
             C.c_void_p(stats.data_ptr() if stats is not None else 0), C.c_void_p(hip_stream_handle or 0)))
         return mask, stats
+
+    # -- colour coding of the field: Flow::MotionToColor on the GPU, from the cells (the colour rule of include/bbme.h) ----------
+    def color_shape(self, scale=None):
+        """(rows, cols, 3) of the colour image: the subsampled field's size; scale defaults to upsample."""
+        return self.subsampled_shape(scale)[:2] + (3,)
+
+    def _get_flow_color(self, pair, scale, maxmotion, which, out, what):
+        shape = self.color_shape(scale)
+        scale = self.upsample if scale is None else int(scale)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
+        rng = (C.c_float * 5)()
+        _capi.check(self._lib.bbme_get_flow_color_host(self._ctx, pair, _which(which), scale, float(maxmotion), out.ctypes.data, rng))
+        self.last_color_range = tuple(rng)
+        return out
+
+    def flow_color(self, scale=None, maxmotion=-1.0, which="forward", pair=0, out=None):
+        """Flow::MotionToColor of get_subsampled_flow(scale) without the field ever leaving the GPU -> (rows, cols, 3) uint8,
+        B,G,R; only the image is downloaded.  which="backward": the backward field after estimate_bidirectional_async().
+        maxmotion > 0 replaces the normalising radius.  Sets last_color_range = (max radius, min u, max u, min v, max v).
+        The hue angle is the double atan2 rounded to float (include/bbme.h), so a channel may be one level from
+        Flow().MotionToColor's where the platform's float atan2 rounds the other way."""
+        return self._get_flow_color(pair, scale, maxmotion, which, out, "flow_color")
+
+    def _color_tensors(self, scale, out, range, what):
+        import torch
+        rows, cols, _ = self.color_shape(scale)
+        if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (rows, cols, 3)
+                                    and out.stride(2) == 1 and out.stride(1) == 3 and out.stride(0) >= 3 * cols):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape (%d, %d, 3) with packed "
+                                  "pixels" % (what, rows, cols))
+        if range is not None and not (range.is_cuda and range.dtype == torch.float32 and range.numel() == 5 and range.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: range must be a contiguous float32 CUDA tensor of 5" % what)
+        return (C.c_void_p(out.data_ptr() if out is not None else 0), out.stride(0) if out is not None else 0,
+                C.c_void_p(range.data_ptr() if range is not None else 0))
+
+    def flow_color_device(self, out, scale=None, maxmotion=-1.0, which="forward", pair=0, range=None, hip_stream_handle=None):
+        """flow_color into a uint8 CUDA tensor of shape (rows, cols, 3) whose rows may be further apart than 3 cols bytes (a
+        column slice of a wider tensor; any alignment), and / or the five range floats into a float32 CUDA tensor; on the
+        given HIP stream (default: the context's), ordered behind the context's stream; no host wait."""
+        scale = self.upsample if scale is None else int(scale)
+        o, pitch, r = self._color_tensors(scale, out, range, "flow_color_device")
+        self._behind_torch(out, range)
+        _capi.check(self._lib.bbme_flow_color_device(self._ctx, pair, _which(which), scale, float(maxmotion), o, pitch, r,
+                                                     C.c_void_p(hip_stream_handle or 0)))
+        return out, range
+
+    def cells_color_device(self, cells, out=None, range=None, scale=None, maxmotion=-1.0, hip_stream_handle=None):
+        """The colour rule on any cell grid in HBM: cells a contiguous int16 CUDA tensor (CH, CW, 2); out and range as in
+        flow_color_device, each may be None.  Needs no estimate."""
+        import torch
+        ch, cw = self.cells_shape
+        if not (cells.is_cuda and cells.dtype == torch.int16 and tuple(cells.shape) == (ch, cw, 2) and cells.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_color_device: cells must be a contiguous int16 CUDA tensor of shape "
+                                  "(%d, %d, 2)" % (ch, cw))
+        scale = self.upsample if scale is None else int(scale)
+        o, pitch, r = self._color_tensors(scale, out, range, "cells_color_device")
+        self._behind_torch(cells, out, range)
+        _capi.check(self._lib.bbme_cells_color_device(self._ctx, C.c_void_p(cells.data_ptr()), scale, float(maxmotion), o, pitch, r,
+                                                      C.c_void_p(hip_stream_handle or 0)))
+        return out, range
+
+    def _flow_ranges(self, which, scale):
+        scale = self.upsample if scale is None else int(scale)
+        out = np.empty((getattr(self, "batch", 1), 5), np.float32)
+        _capi.check(self._lib.bbme_flow_ranges(self._ctx, _which(which), scale, out.ctypes.data))
+        return out
+
+    def flow_range(self, which="forward", scale=None):
+        """(max radius, min u, max u, min v, max v) of the subsampled field, from the cells on the GPU."""
+        return tuple(float(v) for v in self._flow_ranges(which, scale)[0])
 
     # -- motion-compensated interpolation between the two frames (the interpolation rule of include/bbme.h) ---------------
     def _get_interpolated(self, pair, num, den, out, what):
@@ -469,6 +554,7 @@ class MF:
         def ptr(t):
             return C.c_void_p(t.data_ptr() if t is not None else 0)
 
+        self._behind_torch(fwd, bwd, out, sel, stats)
         _capi.check(self._lib.bbme_cells_interpolate_device(
             self._ctx, pair, ptr(fwd), ptr(bwd), int(num0), count, int(den), win,
             ptr(out), out.stride(1) if out is not None else 0, max(out.stride(0), 0) if out is not None else 0,
@@ -512,6 +598,7 @@ class MF:
         assert gtruth.is_cuda and gtruth.is_contiguous() and gtruth.dim() == 3 and gtruth.shape[2] == 2
         assert gtruth.dtype.itemsize == 4 and gtruth.dtype.is_floating_point
         out = C.c_double()
+        self._behind_torch(gtruth)
         _capi.check(self._lib.bbme_calculate_mse_device(self._ctx, C.c_void_p(gtruth.data_ptr()), gtruth.shape[1],
                                                         gtruth.shape[0], int(scale), C.byref(out)))
         return out.value
@@ -653,6 +740,15 @@ class MFBatch(MF):
         """MF.consistency_stats of every pair, in order, from one launch."""
         return self._consistency_stats(which, tol, window)
 
+    def get_pair_flow_color(self, pair, scale=None, maxmotion=-1.0, which="forward", out=None):
+        """MF.flow_color of one pair."""
+        return self._get_flow_color(pair, scale, maxmotion, which, out, "get_pair_flow_color")
+
+    def flow_ranges_all(self, which="forward", scale=None):
+        """MF.flow_range of every pair from one launch -> (pairs, 5) float32; a video is coloured with one common maxmotion
+        by passing flow_ranges_all()[:, 0].max() to get_pair_flow_color."""
+        return self._flow_ranges(which, scale)
+
     def get_pair_interpolated(self, pair, num=1, den=2, out=None):
         """MF.interpolate of one pair."""
         return self._get_interpolated(pair, num, den, out, "get_pair_interpolated")
@@ -785,6 +881,22 @@ def cells_consistency(a, b, tol=1, window=None):
     win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
     _capi.check(_capi.lib().bbme_cells_consistency_host(a.ctypes.data, b.ctypes.data, cw, ch, int(tol), win, mask.ctypes.data, s))
     return mask, dict(zip(("consistent", "inconsistent", "outside", "discrepancy"), list(s)))
+
+
+def color_cells(cells, width, height, pad_x=0, pad_y=0, scale=1, maxmotion=-1.0):
+    """The colour rule of include/bbme.h on the CPU (bbme_cells_color_host): cells an int16 (CH, CW, 2) grid, the width x height
+    frame at (pad_x, pad_y) of its 2 CW x 2 CH plane -> ((ceil(height / scale), ceil(width / scale), 3) uint8 B,G,R,
+    (max radius, min u, max u, min v, max v))."""
+    cells = np.ascontiguousarray(cells, np.int16)
+    if cells.ndim != 3 or cells.shape[2] != 2:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "color_cells: an int16 grid of shape (CH, CW, 2)")
+    scale = int(scale)
+    rows, cols = (-(-int(height) // scale), -(-int(width) // scale)) if scale >= 1 else (0, 0)
+    out = np.empty((max(rows, 0), max(cols, 0), 3), np.uint8)
+    rng = (C.c_float * 5)()
+    _capi.check(_capi.lib().bbme_cells_color_host(cells.ctypes.data, cells.shape[1], cells.shape[0], int(width), int(height),
+                                                  int(pad_x), int(pad_y), scale, float(maxmotion), out.ctypes.data, rng))
+    return out, tuple(rng)
 
 
 def interpolate_cells(image1, image2, fwd, bwd=None, num=1, den=2, window=None):

@@ -428,6 +428,59 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
     return out
 
 
+def colorize_frames(frames, search_size, block_size, maxmotion=-1.0, scale=1, in_flight=4, batch=2, device=None):
+    """The colour-coded forward field of the len(frames) - 1 consecutive pairs of a video on ONE GPU (the colour rule of
+    include/bbme.h at subsampling `scale`): -> ((P, oh, ow, 3) uint8 B,G,R images, (P, 5) float32 ranges (max radius, min u,
+    max u, min v, max v)).  maxmotion > 0 normalises every picture by the same radius; otherwise each by its own.  Runs on the
+    chain plan of estimate_frames_pipelined (same contexts, rounds and padding of a short round): every frame is set once, a
+    round's ranges come from one launch (MFBatch.flow_ranges_all) and only the images' bytes are downloaded."""
+    from .motion_framework import MFChain
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    n_pairs = len(frames) - 1
+    if n_pairs < 1:
+        return np.empty((0, 0, 0, 3), np.uint8), np.empty((0, 5), np.float32)
+    if device is None:
+        device = local_device()
+    per = max(1, min(batch, in_flight, n_pairs))
+    n_slots = max(1, in_flight // per)
+    rounds = plan_frame_segments(n_pairs, n_slots, per)
+    n_ctx = 1 + max(r[0] for r in rounds)
+    chains = [None] * n_ctx
+    images = [None] * n_pairs
+    ranges = np.empty((n_pairs, 5), np.float32)
+    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
+
+    def collect(slot):
+        first, count = pending[slot]
+        pending[slot] = None
+        mf = chains[slot]
+        ranges[first:first + count] = mf.flow_ranges_all("forward", scale)[:count]      # waits for this context's stream only
+        for p in range(count):
+            images[first + p] = mf.get_pair_flow_color(p, scale, maxmotion)
+
+    try:
+        for slot, first, count, carry in rounds:
+            run = frames[first + 1:first + count + 1]
+            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
+            if not carry:
+                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device)
+                if n_ctx * per > 1:
+                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
+            else:
+                collect(slot)
+                chains[slot].advance(run)
+            chains[slot].estimate_async()
+            pending[slot] = (first, count)
+        for slot in range(n_ctx):
+            if pending[slot]:
+                collect(slot)
+    finally:
+        for mf in chains:
+            if mf is not None:
+                mf.close()
+    return np.stack(images), ranges
+
+
 def _gpu_compute(search_size, block_size, device):
     from .motion_framework import MF
 

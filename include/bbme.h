@@ -412,6 +412,58 @@ int bbme_consistency_stats(bbme_ctx *ctx, int which, int tol, const int *window,
 int bbme_cells_consistency_host(const int16_t *a, const int16_t *b, int cells_w, int cells_h, int tol, const int *window,
                                 uint8_t *mask, unsigned long long *stats4);
 
+/* COLOUR RULE: Flow::MotionToColor (rw_flow.cpp:202-249, with computeColor :251-275) of the field the driver makes of the result
+ * (main_class.cpp:58-75: strip the padding, every scale-th pixel, divide by scale, MotionToColor), straight from a 2x2-cell grid.
+ * Input: a cell grid, int16 (dx, dy) per cell, CH x CW = (padded_h / 2) x (padded_w / 2); a subsampling step scale >= 1; maxmotion.
+ * Output: the ow x oh B,G,R image, ow = ceil(W / scale), oh = ceil(H / scale) of the unpadded W x H frame, and
+ * range[5] = {max radius, min u, max u, min v, max v}.
+ * Pixel (x, y) takes (dx, dy) = cell[(pad_y + scale y) >> 1][(pad_x + scale x) >> 1], u = (float)dx / (float)scale, v likewise:
+ * exactly the field of bbme_subsampled_flow_device / bbme_get_subsampled_flow_host.
+ * Range pass, as MotionToColor's (:205-221): max u, max v, min u, min v start from the reference's sentinels -999, -999, 999, 999
+ * and the max radius from -1, and every pixel is folded in with rad = sqrtf(u * u + v * v) in float (no FMA).  The sentinels
+ * matter: a four-level field of search range 127 can exceed 999, and a minimum then stays 999 as bbme_motion_to_color reports it.
+ * maxrad = maxmotion if maxmotion > 0, else the max radius; a maxrad of 0 becomes 1 (:225-229).  (No cell is "unknown".)
+ * Colour pass: computeColor of (fx, fy) = (u / maxrad, v / maxrad) in the reference's float / double expression order, as
+ * compute_color of csrc/bbme_host.cpp states it (rad = sqrtf(fx * fx + fy * fy); fk = (a + 1.0f) / 2.0f * 54.0f; k0 = (int)fk;
+ * k1 = (k0 + 1) % 55; f = fk - k0; per channel col = (1 - f) * col0 + f * col1 with col_i = wheel / 255.0f, then
+ * 1 - rad * (1 - col) for rad <= 1, else (float)(col * .75); byte = (int)(255.0 * col)), nothing contracted into an FMA --
+ * with ONE deliberate difference, the hue angle.  The reference's atan2(-fy, -fx) on floats is the platform's float atan2f,
+ * which need not be correctly rounded (glibc 2.35's differs from the rounded double result in the last bit on about 16 % of
+ * arguments) and which a GPU cannot reproduce version by version.  The rule here is
+ *     A = (float)atan2((double)-fy, (double)-fx),  a = (float)((double)A / 3.14159265358979323846).
+ * Signs of zero survive: dy = 0 gives -fy = -0.0f, and atan2(-0.0, negative) is -pi, not +pi.
+ * What that costs: against bbme_motion_to_color of the same field the range is identical and the image agrees except where an
+ * angle one float ulp apart moves a channel across an integer boundary -- no channel by more than 1 level, and on the integer
+ * vectors |d| <= 64 at scale 1 and 4 no channel at all (tests/test_flow_color_cpu.py holds it to at most 1e-4 of the channels).
+ * All entry points: BBME_ERR_INVALID for a null context or pointer, a pair out of range, `which` not BBME_DIR_FORWARD /
+ * BBME_DIR_BACKWARD, scale < 1, a pitch below 3 ow.  They work on single, batched and chain contexts and on contexts made for
+ * up-sampled frames, and change no context state (grids, flow, cells, backward cells, SAD memo, captured graphs); their scratch
+ * buffers are the context's own and independent of the other getters'.  When maxmotion > 0 and no range is asked for, the range
+ * pass is not run.
+ * bbme_cells_color_device: the rule on ANY cell grid in HBM of this context's cell geometry; needs no estimate.  d_bgr (rows
+ * out_pitch_bytes apart; any alignment) and d_range (five floats) each may be null, not both; on hip_stream (NULL = the ctx
+ * stream; another stream is first ordered behind it); no host wait.  The two passes meet in HBM, not on the host.  Calls
+ * share one scratch slot per context: the caller orders those it issues on different streams.
+ * bbme_flow_color_device: the same on the context's own cells of `pair` (scratch slot: one per pair): which = BBME_DIR_FORWARD
+ * the current level-0 cells (BBME_ERR_STATE before level 0 has reached 2x2 blocks, as bbme_subsampled_flow_device), which =
+ * BBME_DIR_BACKWARD the cells kept by bbme_estimate_bidirectional (BBME_ERR_STATE without a valid pair of fields, as
+ * bbme_backward_cells_device_pair).
+ * bbme_get_flow_color_host: synchronises; packed rows of 3 ow bytes into bgr, the five floats into range5; each may be NULL,
+ * not both.
+ * bbme_flow_ranges: the five floats of EVERY pair from one launch, ranges[5 p + k]; synchronises.  (A video coloured with one
+ * common maxmotion takes the largest ranges[5 p].)
+ * bbme_cells_color_host: the same rule on the CPU, no GPU, on a packed cells_h x cells_w grid: the width x height frame at
+ * (pad_x, pad_y) of the 2 cells_w x 2 cells_h plane (BBME_ERR_INVALID when it does not lie inside); bgr (packed) and range5
+ * each may be NULL, not both. */
+int bbme_cells_color_device(bbme_ctx *ctx, const int16_t *d_cells, int scale, float maxmotion, uint8_t *d_bgr, int out_pitch_bytes,
+                            float *d_range, void *hip_stream);
+int bbme_flow_color_device(bbme_ctx *ctx, int pair, int which, int scale, float maxmotion, uint8_t *d_bgr, int out_pitch_bytes,
+                           float *d_range, void *hip_stream);
+int bbme_get_flow_color_host(bbme_ctx *ctx, int pair, int which, int scale, float maxmotion, uint8_t *bgr, float *range5);
+int bbme_flow_ranges(bbme_ctx *ctx, int which, int scale, float *ranges);
+int bbme_cells_color_host(const int16_t *cells, int cells_w, int cells_h, int width, int height, int pad_x, int pad_y, int scale,
+                          float maxmotion, uint8_t *bgr, float *range5);
+
 /* INTERPOLATION RULE (this project's own; the reference has no interpolation): the frame at phase num / den between frame 1
  * (phase 0) and frame 2 (phase 1) of a pair, motion-compensated from both fields.  Inputs: the level-0 padded planes I1 and I2
  * (W0 x H0 bytes), the cell grid F on frame 1 (forward) and, optionally, the cell grid B on frame 2 (backward), CH x CW int16
