@@ -79,6 +79,7 @@ SIGNATURES = {
     "bbme_set_chain_frames_host_async": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int, C.c_int]),
     "bbme_set_chain_frames_device": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int, C.c_int]),
     "bbme_chain_advance": (C.c_int, [_ctx]),
+    "bbme_get_chain_plane_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
     "bbme_destroy": (C.c_int, [_ctx]),
     "bbme_set_stream": (C.c_int, [_ctx, C.c_void_p]),
     "bbme_get_stream": (C.c_int, [_ctx, _P(C.c_void_p)]),

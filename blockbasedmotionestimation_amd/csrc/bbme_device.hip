@@ -1212,6 +1212,17 @@ int bbme_set_frames_device(bbme_ctx *c, const uint8_t *d_image1, const uint8_t *
 
 static int enqueue_cascade(bbme_ctx *c, int pair);
 
+// k_pyr_down4 / k_pyr_down4_run make four output pixels per thread from 16-byte loads: the SOURCE level of a pyrDown must be a
+// multiple of 8 pixels wide.  create_context refuses every level width that is not a multiple of 4, and a source level is twice
+// the level below it, so this holds for every context there is; a geometry that broke it must fail here, not compute something.
+static int check_pyr_down_source(const Level &P, size_t level)
+{
+    if (P.width % 8 != 0)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "level %zu is %d pixels wide: pyrDown needs a source width that is a multiple of 8",
+                          level, P.width);
+    return BBME_OK;
+}
+
 int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
 {
     if (int rc = pair_context_only(c, "bbme_set_frames_device")) return rc;
@@ -1237,13 +1248,9 @@ static int enqueue_cascade(bbme_ctx *c, int pair)
     for (size_t l = 1; l < c->lv.size(); ++l) {
         Level &P = c->lv[l - 1], &L = c->lv[l];
         PlanePair q{{P.img1 + pp_ * P.plane_stride, P.img2 + pp_ * P.plane_stride}, {L.img1 + pp_ * L.plane_stride, L.img2 + pp_ * L.plane_stride}};
-        if (P.width % 8 == 0) {
-            const long long n = (long long)(L.width / 4) * L.height;
-            hipLaunchKernelGGL(k_pyr_down4, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, c->stream, q, P.width, P.height);
-        } else {
-            const long long n = (long long)L.width * L.height;
-            hipLaunchKernelGGL(k_pyr_down, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, c->stream, q, P.width, P.height);
-        }
+        if (int rc = check_pyr_down_source(P, l - 1)) return rc;
+        const long long n = (long long)(L.width / 4) * L.height;
+        hipLaunchKernelGGL(k_pyr_down4, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, c->stream, q, P.width, P.height);
     }
     HIP_TRY(hipGetLastError());
     c->frames_mask |= 1ull << pair;
@@ -1344,15 +1351,10 @@ static int enqueue_chain_run(bbme_ctx *c, int first, int count, const FrameRun &
         Level &P = c->lv[l - 1], &L = c->lv[l];
         const uint8_t *src = P.img1 + (size_t)first * P.plane_stride;
         uint8_t *dst = L.img1 + (size_t)first * L.plane_stride;
-        if (P.width % 8 == 0) {
-            const long long n = (long long)(L.width / 4) * L.height;
-            hipLaunchKernelGGL(k_pyr_down4_run, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, c->stream,
-                               src, P.plane_stride, dst, L.plane_stride, P.width, P.height);
-        } else {
-            const long long n = (long long)L.width * L.height;
-            hipLaunchKernelGGL(k_pyr_down_run, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, c->stream,
-                               src, P.plane_stride, dst, L.plane_stride, P.width, P.height);
-        }
+        if (int rc = check_pyr_down_source(P, l - 1)) return rc;
+        const long long n = (long long)(L.width / 4) * L.height;
+        hipLaunchKernelGGL(k_pyr_down4_run, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, c->stream,
+                           src, P.plane_stride, dst, L.plane_stride, P.width, P.height);
     }
     HIP_TRY(hipGetLastError());
     for (int i = 0; i < count; ++i) c->mark_slot(first + i);
@@ -1417,6 +1419,20 @@ int bbme_chain_advance(bbme_ctx *c)
     c->last_slot = false;
     c->memo_block = 0;
     c->fields_valid = false;
+    return BBME_OK;
+}
+
+int bbme_get_chain_plane_host(bbme_ctx *c, int level, int slot, uint8_t *image)
+{
+    const char *what = "bbme_get_chain_plane_host";
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (int rc = check_level(c, level)) return rc;
+    if (slot < 0 || slot > c->batch) return bbme::fail(BBME_ERR_INVALID, "%s: slot %d of %d", what, slot, c->batch + 1);
+    if (!image) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[level];
+    HIP_TRY(hipMemcpyAsync(image, L.img1 + (size_t)slot * L.plane_stride, (size_t)L.width * L.height, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return BBME_OK;
 }
 

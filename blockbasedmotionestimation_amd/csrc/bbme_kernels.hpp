@@ -2522,36 +2522,9 @@ __device__ __forceinline__ int mirror101(int p, int n)
     return p;
 }
 
-// one output pixel per thread: planes whose half width is not a multiple of 4
-__device__ __forceinline__ void pyr_down_plane(const uint8_t *src, uint8_t *dst, int sw, int sh)
-{
-    const int dw = sw / 2, dh = sh / 2;
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t >= (long long)dw * dh) return;
-    const int x = (int)(t % dw), y = (int)(t / dw);
-    const int wgt[5] = {1, 4, 6, 4, 1};
-    int xs[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) xs[k] = mirror101(2 * x + k - 2, sw);
-    int acc = 0;
-#pragma unroll
-    for (int ky = 0; ky < 5; ++ky) {
-        const uint8_t *row = src + (size_t)mirror101(2 * y + ky - 2, sh) * sw;
-        int h = 0;
-#pragma unroll
-        for (int kx = 0; kx < 5; ++kx) h += wgt[kx] * row[xs[kx]];
-        acc += wgt[ky] * h;
-    }
-    dst[(size_t)y * dw + x] = (uint8_t)((acc + 128) >> 8);
-}
-
-__global__ __launch_bounds__(256) void k_pyr_down(PlanePair p, int sw, int sh)
-{
-    pyr_down_plane(p.src[blockIdx.y], p.dst[blockIdx.y], sw, sh);
-}
-
-// four output pixels per thread (sw a multiple of 8): output x = 4k + c reads input bytes 8k + 2c - 2 .. 8k + 2c + 2, all
-// inside the four dwords at 8k - 4 .. 8k + 11.  h = [1 4 6 4] . bytes[o .. o+3] (v_dot4_u32_u8 on a re-aligned dword)
+// four output pixels per thread.  sw is a multiple of 8 (the host checks it where it launches: a context's level widths are
+// multiples of 4, so every level that is pyrDown's source is a multiple of 8 wide).  Output x = 4k + c reads input bytes
+// 8k + 2c - 2 .. 8k + 2c + 2, all inside the four dwords at 8k - 4 .. 8k + 11.  h = [1 4 6 4] . bytes[o .. o+3] (v_dot4_u32_u8 on a re-aligned dword)
 // + byte[o + 4]; out = (h0 + 4 h1 + 6 h2 + 4 h3 + h4 + 128) >> 8 over the five (mirrored) rows -- the same integers as
 // the separable host form, no rounding in between.
 __device__ __forceinline__ void pyr_down4_plane(const uint8_t *src, uint8_t *dst, int sw, int sh)
@@ -2568,7 +2541,8 @@ __device__ __forceinline__ void pyr_down4_plane(const uint8_t *src, uint8_t *dst
     for (int ky = 0; ky < 5; ++ky) {
         // the four dwords around input byte 8k in ONE 16-byte load (any byte alignment is fine on gfx950): a quarter of the load
         // instructions of four dword loads.  The first thread of a row starts at the row itself (nothing may be read in front of
-        // the plane); the last one reads up to 4 bytes past the row (the next row, or the plane's slack) and ignores them.
+        // the plane); the last one reads up to 4 bytes past the row (the next row, or the plane's slack) and ignores them.  On a
+        // row of 8 bytes the one thread is both: it starts at the row and reads 8 bytes past it (the slack is 256 bytes at least).
         const uint8_t *row = src + (size_t)mirror101(2 * y + ky - 2, sh) * sw + 8 * k;
         const ua_u128 v = *reinterpret_cast<const ua_u128 *>(row - (left ? 0 : 4));
         uint32_t d[4];
@@ -2615,11 +2589,6 @@ __global__ __launch_bounds__(256) void k_resize_x4_pad_run(FrameRun run, uint8_t
                                                            int pad_x, int pad_y, int pw, int ph)
 {
     resize_x4_pad_plane(run.src[blockIdx.y], dst + (size_t)blockIdx.y * s_dst, sw, sh, pitch, pad_x, pad_y, pw, ph);
-}
-
-__global__ __launch_bounds__(256) void k_pyr_down_run(const uint8_t *src, uint32_t s_src, uint8_t *dst, uint32_t s_dst, int sw, int sh)
-{
-    pyr_down_plane(src + (size_t)blockIdx.y * s_src, dst + (size_t)blockIdx.y * s_dst, sw, sh);
 }
 
 __global__ __launch_bounds__(256) void k_pyr_down4_run(const uint8_t *src, uint32_t s_src, uint8_t *dst, uint32_t s_dst, int sw, int sh)

@@ -841,6 +841,13 @@ class MFChain(MFBatch):
         if not wait:
             self._host_frames_in_flight = frames          # keeps converted copies alive until the next run replaces them
 
+    def get_slot_plane(self, level, slot):
+        """The padded plane of frame slot `slot` at `level` (bbme_get_chain_plane_host) -> (level height, level width) uint8."""
+        w, h, _, _ = self.level_geometry(level)
+        out = np.empty((h, w), np.uint8)
+        _capi.check(self._lib.bbme_get_chain_plane_host(self._ctx, level, slot, out.ctypes.data))
+        return out
+
     def _check_device_run(self, frames):
         import torch
         for t in frames:

@@ -213,13 +213,18 @@ int bbme_set_frames_device_x4(bbme_ctx *ctx, int pair, const uint8_t *d_image1, 
  * motion-compensation calls -- returns BBME_ERR_STATE.  Every frame setter and the roll reset the SAD memo.  The pair setters
  * (bbme_set_frames_*) return BBME_ERR_UNSUPPORTED on a chain context, the chain calls BBME_ERR_UNSUPPORTED on any other;
  * BBME_ERR_INVALID for first / count outside the slots, a null table or entry, pitch < width / scale, scale not 1 or 4, or
- * scale 4 on a context whose width or height is not a multiple of 4. */
+ * scale 4 on a context whose width or height is not a multiple of 4.
+ * bbme_get_chain_plane_host: the padded plane of one slot (0 .. pairs) at one level, level width x level height bytes, as it
+ * stands when the ctx stream reaches the call (set or not); returns after the copy.  For inspection: a chain of more than one
+ * pair has no other plane getter (bbme_get_level_planes_host addresses one pair).  BBME_ERR_INVALID for a slot or level outside
+ * the context or a null output. */
 int bbme_create_chain(const bbme_params *params, int width, int height, int device, int pairs, bbme_ctx **out);
 int bbme_chain_frames(const bbme_ctx *ctx, int *frames);
 int bbme_set_chain_frames_host(bbme_ctx *ctx, int first, int count, const uint8_t *const *frames, int pitch, int scale);
 int bbme_set_chain_frames_host_async(bbme_ctx *ctx, int first, int count, const uint8_t *const *frames, int pitch, int scale);
 int bbme_set_chain_frames_device(bbme_ctx *ctx, int first, int count, const uint8_t *const *d_frames, int pitch, int scale);
 int bbme_chain_advance(bbme_ctx *ctx);
+int bbme_get_chain_plane_host(bbme_ctx *ctx, int level, int slot, uint8_t *image);
 /* Which of the reference's two block searches MF::calcLevelBM calls (motion_framework.cpp:235-236): the spiral full
  * search find_min_block_spiral (:296-422, the live one: ties go to the candidate visited first on the spiral; a
  * prediction outside the image gives a zero MV) or the raster full search find_min_block (:246-294, commented out in the

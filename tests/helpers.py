@@ -713,3 +713,28 @@ def association_case():
     p2 = rng.integers(0, 256, (g["h"], g["w"]), dtype=np.uint8)
     field = np.array(ASSOCIATION_VECTORS, np.int32)[rng.choice(3, (g["h"] // g["block"], g["w"] // g["block"]), p=[0.35, 0.35, 0.3])]
     return p1, p2, field
+
+
+# ---- frames for the plane kernels (x4 up-sampling, zero border, pyrDown): content on which a wrong filter weight or a wrong ----
+# ---- truncation shows, where a smooth texture would hide it ------------------------------------------------------------------
+HARD_CONTENTS = ("noise", "binary", "checker", "ramp_x", "ramp_y", "white")
+
+
+def hard_content(name, h, w, seed=0):
+    """One (h, w) uint8 frame: uniform noise, binary noise of 0 / 255, a checkerboard of period 1 in 0 / 255, a ramp along x or
+    along y over the whole value range, constant 255."""
+    rng = np.random.default_rng([seed, HARD_CONTENTS.index(name), h, w])
+    y, x = np.mgrid[0:h, 0:w]
+    if name == "noise":
+        return rng.integers(0, 256, (h, w), dtype=np.uint8)
+    if name == "binary":
+        return (rng.integers(0, 2, (h, w)) * 255).astype(np.uint8)
+    if name == "checker":
+        return (((x + y) & 1) * 255).astype(np.uint8)
+    if name == "ramp_x":
+        return (x * 255 // max(w - 1, 1)).astype(np.uint8)
+    if name == "ramp_y":
+        return (y * 255 // max(h - 1, 1)).astype(np.uint8)
+    if name == "white":
+        return np.full((h, w), 255, np.uint8)
+    raise ValueError(name)

@@ -1,6 +1,7 @@
 """The colour rule of include/bbme.h ("COLOUR RULE") on the CPU: bbme.color_cells (bbme_cells_color_host) is, bit for bit, a numpy
 float32 restatement of the rule -- image and range -- on every integer vector with |dx|, |dy| <= 40, on vectors on the axes (the
-signed-zero seam of the hue angle), on an all-zero grid and on a grid beyond the range pass's sentinels; it agrees with
+signed-zero seam of the hue angle), on an all-zero grid, on a grid beyond the range pass's sentinels and on a wide grid of
+vectors over the whole int16 range (with normalising radii from the smallest normal float to 3e38); it agrees with
 Flow::MotionToColor of the field the grid defines (the oracle's restatement and, where it was built, the reference's own code)
 in the range exactly and in the image within the cap this project already puts between two atan2 implementations
 (tests/test_host_cpu.py: no channel more than one level off, at most 1e-4 of the channels off at all)."""
@@ -39,13 +40,19 @@ def subsampled_field(cells, width, height, pad_x, pad_y, scale):
 
 def np_color_cells(cells, width, height, pad_x=0, pad_y=0, scale=1, maxmotion=-1.0):
     """The colour rule, every operation in the type the rule gives it -> ((oh, ow, 3) uint8 B,G,R, range tuple)."""
-    f32 = np.float32
     field = subsampled_field(np.asarray(cells, np.int16), width, height, pad_x, pad_y, scale)
+    with np.errstate(all="ignore"):       # u / maxrad may overflow; np.where evaluates the branch it does not select (inf * 0)
+        return _np_color_field(field, np.float32(maxmotion))
+
+
+def _np_color_field(field, maxmotion):
+    """MotionToColor of an (oh, ow, 2) float32 field; maxmotion a float32."""
+    f32 = np.float32
     u, v = field[..., 0], field[..., 1]
     rad = np.sqrt(u * u + v * v)
     assert rad.dtype == np.float32
     rng = (max(f32(-1), rad.max()), min(f32(999), u.min()), max(f32(-999), u.max()), min(f32(999), v.min()), max(f32(-999), v.max()))
-    maxrad = f32(maxmotion) if maxmotion > 0 else rng[0]
+    maxrad = maxmotion if maxmotion > 0 else rng[0]
     if maxrad == 0:
         maxrad = f32(1)
     fx, fy = u / maxrad, v / maxrad
@@ -98,7 +105,24 @@ def beyond_sentinels_grid():
     return g
 
 
-GRIDS = {"all": all_vectors_grid, "axes": axes_grid, "zero": lambda: np.zeros((5, 7, 2), np.int16), "beyond": beyond_sentinels_grid}
+INT16_EDGES = [(32767, 5), (-32767, -32767), (16384, -16384), (-16384, 0), (-32768, -32768), (-32768, 32767), (3, -32768),
+               (32767, 32767), (-32768, 0), (0, 32767)]            # helpers.INT16_SPECIALS and two vectors on the axes
+EXTREME_MAXMOTIONS = (1.1754944e-38, 3.0e38)     # the smallest normal float: u / maxrad overflows; 3e38: everything at the centre
+
+
+def full_range_grid():
+    """16 x 1050 cells (a 2100 x 32 frame: rows longer than the 1024 cells a range workgroup takes) of vectors over the whole int16
+    range, the bounds themselves at known cells: in the first and last cell, and on both sides of column 1024."""
+    rng = np.random.default_rng(17)
+    g = rng.integers(-32768, 32768, (16, 1050, 2)).astype(np.int16)
+    for k, v in enumerate(INT16_EDGES):
+        g[k, (0, 255, 256, 511, 512, 767, 768, 1023, 1024, 1049)[k]] = v
+        g[15 - k % 4, 1024 + 2 * k] = v
+    return g
+
+
+GRIDS = {"all": all_vectors_grid, "axes": axes_grid, "zero": lambda: np.zeros((5, 7, 2), np.int16), "beyond": beyond_sentinels_grid,
+         "full": full_range_grid}
 
 
 def assert_within_atan2_cap(got, ref, what):
@@ -112,7 +136,7 @@ def test_color_cells_equals_the_numpy_restatement(bbme, name):
     g = GRIDS[name]()
     ch, cw = g.shape[:2]
     for scale in SCALES:
-        for maxmotion in MAXMOTIONS:
+        for maxmotion in MAXMOTIONS + (EXTREME_MAXMOTIONS if name == "full" else ()):
             got, got_range = bbme.color_cells(g, 2 * cw, 2 * ch, 0, 0, scale, maxmotion)
             exp, exp_range = np_color_cells(g, 2 * cw, 2 * ch, 0, 0, scale, maxmotion)
             assert got.shape == (-(-2 * ch // scale), -(-2 * cw // scale), 3) and got.dtype == np.uint8
@@ -128,6 +152,12 @@ def test_color_cells_equals_the_numpy_restatement(bbme, name):
         flow = bbme.Flow()
         flow.MotionToColor(field, verbose=False)
         assert flow.last_range == r                                                 # exactly as bbme_motion_to_color reports it
+    if name == "full":
+        assert bbme.color_cells(g, 2 * cw, 2 * ch)[1] == (float(np.sqrt(np.float32(2) * np.float32(32768) ** 2)), -32768.0, 32767.0, -32768.0, 32767.0)
+        img = bbme.color_cells(g, 2 * cw, 2 * ch, maxmotion=3.0e38)[0]
+        assert (img >= 254).all()                                                   # the wheel's centre: white
+        img = bbme.color_cells(g, 2 * cw, 2 * ch, maxmotion=1.1754944e-38)[0]
+        assert (img.max(-1) == 191).all()                                           # inf or huge radii: a pure hue x 0.75
     if name == "all":
         rad = np.sqrt((g.astype(np.float32) ** 2).sum(-1)) / np.float32(4)
         assert (rad > 7.5).any() and (rad <= 7.5).any()                            # both branches of the saturation at scale 4

@@ -61,9 +61,12 @@ def _status(lib, call):
 ], ids=["padded", "w104_52", "w112_56_28", "x4", "x4_odd"])
 def test_chain_of_one_pair_has_the_planes_of_an_mf(bbme, w, h, search, block, upsample):
     """bbme_get_level_planes_host of a chain of one pair (slot 0, slot 1) on every level against an MF on the same two frames.
-    The one-pixel-per-thread k_pyr_down serves source levels whose width is not a multiple of 8; a context only accepts
-    geometries whose every level width is a multiple of 4, so a level that is pyrDown's SOURCE is always a multiple of 8 wide
-    and only the coarsest level can be narrower (52 and 28 here) -- the closest a context gets to that kernel."""
+    A context only accepts geometries whose every level width is a multiple of 4, so a level that is pyrDown's SOURCE is always
+    a multiple of 8 wide (what k_pyr_down4_run needs) and only the coarsest level can be anything else (52 and 28 here)."""
+    widths = [bbme.plan_padding(w * upsample, h * upsample, search, block)[0] >> l for l in range(len(block))]
+    assert all(x % 8 == 0 for x in widths[:-1]) and widths[-1] % 4 == 0
+    if (w, upsample) == (100, 1):
+        assert widths == ([104, 52] if len(block) == 2 else [112, 56, 28])
     rng = np.random.default_rng(w * 31 + h)
     f = [rng.integers(0, 256, (h, w), dtype=np.uint8) for _ in range(2)]
     mf = bbme.MF(f[0], f[1], search, block, upsample=upsample)
@@ -74,6 +77,13 @@ def test_chain_of_one_pair_has_the_planes_of_an_mf(bbme, w, h, search, block, up
     for l in range(len(block)):
         (a, b), (ea, eb) = chain.get_level_planes(l), mf.get_level_planes(l)
         assert np.array_equal(a, ea) and np.array_equal(b, eb), "level %d" % l
+        # the getter by slot (the only one a chain of more than one pair has) reads the same bytes
+        assert np.array_equal(chain.get_slot_plane(l, 0), ea) and np.array_equal(chain.get_slot_plane(l, 1), eb), "level %d" % l
+    plane = np.zeros((mf.padded_height, mf.padded_width), np.uint8)
+    for ctx, level, slot, status in ((chain._ctx, 0, 2, ERR_INVALID), (chain._ctx, 0, -1, ERR_INVALID), (chain._ctx, len(block), 0, ERR_INVALID),
+                                     (mf._ctx, 0, 0, ERR_UNSUPPORTED)):
+        assert chain._lib.bbme_get_chain_plane_host(ctx, level, slot, plane.ctypes.data) == status, (level, slot)
+    assert chain._lib.bbme_get_chain_plane_host(chain._ctx, 0, 0, None) == ERR_INVALID
     # a run of one frame into either slot
     g = [rng.integers(0, 256, (h, w), dtype=np.uint8) for _ in range(2)]
     mf.set_frames(g[0], f[1])

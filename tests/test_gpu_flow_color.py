@@ -6,6 +6,12 @@ store path (row tails, caller pitches and offsets that are no multiple of 4, odd
 atan2 cap of tests/test_host_cpu.py, taken over DISTINCT vectors; batches and chains equal single contexts; the calls change no
 context state and refuse bad arguments; bbme_cli --backward-color writes the same pixels.
 
+Rows of more than 1024 sampled cells (frames 2100, 2098 and 1030 pixels wide, 8 to 32 high) reach what the 200 x 170 contexts
+cannot: the second, third and fourth cell a lane of k_color_range folds and its second workgroup per row.  There one cell at a time
+carries the only large vector, so the range -- and with it every pixel of the image -- is right only if that lane-iteration of that
+tile is; vectors over the whole int16 range with normalising radii down to the smallest normal float and up to 3e38; batches and
+chains whose extreme lies beyond column 1024 in one pair only; the image buffer growing from call to call.
+
 Contexts are 200 x 170 frames (padded 208 x 176: an even pad_x, an odd pad_y, 104 x 88 cells, room for the 81 x 81 block) with
 blocks of 8 and search windows of 4 on two levels (the centre candidate only: the cheapest estimate), and, so that the real
 estimates also carry motion, the same with search windows of 16."""
@@ -15,7 +21,8 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_flow_color_cpu import all_vectors_grid, assert_within_atan2_cap, axes_grid
+from test_flow_color_cpu import (EXTREME_MAXMOTIONS, all_vectors_grid, assert_within_atan2_cap, axes_grid, full_range_grid,
+                                 np_color_cells, subsampled_field)
 from test_gpu_bidirectional import _write_pgm
 
 pytestmark = pytest.mark.gpu
@@ -134,6 +141,168 @@ def test_store_paths(bbme, w, h):
     _assert_device_equals_host(bbme, mf, cells, 2, -1.0, "scale 2", pitch_extra=3, offset=3)
     _assert_device_equals_host(bbme, mf, cells, 64, -1.0, "scale 64", pitch_extra=1, offset=1)
     _assert_device_equals_host(bbme, mf, cells, 1000, -1.0, "one pixel", pitch_extra=2, offset=1)
+    mf.close()
+
+
+# ---- rows of more than 1024 sampled cells: every lane-iteration and both tiles of k_color_range ------------------------------
+
+# (frame, search, block) -> (padded width, padded height, pad_x, pad_y).  A search window <= the block is the centre candidate only
+WIDE = {"2100x8": ((2100, 8, [4], [4]), (2100, 8, 0, 0)),         # 1050 sampled cells per row at scale 1 and 2: two range tiles
+        "2098x16": ((2098, 16, [8], [8]), (2104, 16, 3, 0)),      # odd pad_x: a cell straddles column 0, in every one of 17 image tiles
+        "1030x8": ((1030, 8, [4], [4]), (1032, 8, 1, 0))}         # 516 cells per row: lane-iterations 0 .. 2 of one tile
+PROBE_COLUMNS = (255, 256, 511, 512, 767, 768, 1023, 1024)        # both sides of every lane-iteration's and of the tile's boundary
+PROBE_VECTORS = ((300, 200), (-300, -200))
+
+
+def _zero_mf(bbme, w, h, search, block, expect):
+    z = np.zeros((h, w), np.uint8)
+    assert bbme.plan_padding(w, h, search, block) == expect
+    mf = bbme.MF(z, z, search, block)
+    assert (mf.padded_width, mf.padded_height, mf.padding_x, mf.padding_y) == expect
+    return mf
+
+
+def _sampled(mf, scale):
+    """(ncx, ncy): the sampled cells per row and the rows of them, as the range pass counts them."""
+    px, py, w, h = mf.padding_x, mf.padding_y, mf.orig_width, mf.orig_height
+    if scale == 1:
+        return ((px + w - 1) >> 1) - (px >> 1) + 1, ((py + h - 1) >> 1) - (py >> 1) + 1
+    return -(-w // scale), -(-h // scale)
+
+
+def _sampled_cell(mf, scale, i, j):
+    """(row, column) of the one cell that sampled column i of sampled row j reads."""
+    px, py = mf.padding_x, mf.padding_y
+    if scale == 1:
+        return (py >> 1) + j, (px >> 1) + i
+    return (py + scale * j) >> 1, (px + scale * i) >> 1
+
+
+def _assert_device_equals_restatement(bbme, mf, cells, scale, maxmotion, what, **kw):
+    """Device against the numpy restatement (and the restatement against the host mirror): image and range, bit for bit."""
+    img, r = _device(mf, cells, scale, maxmotion, **kw)
+    exp, exp_range = np_color_cells(cells, mf.orig_width, mf.orig_height, mf.padding_x, mf.padding_y, scale, maxmotion)
+    host, host_range = _host(bbme, mf, cells, scale, maxmotion)
+    assert host_range == exp_range and np.array_equal(host, exp), (what, scale, maxmotion, "host mirror against numpy")
+    assert r is None or r == exp_range, (what, scale, maxmotion, r, exp_range)
+    if img is not None and not np.array_equal(img, exp):
+        bad = np.argwhere((img != exp).any(-1))
+        y, x = bad[0]
+        cell = cells[(mf.padding_y + scale * y) >> 1, (mf.padding_x + scale * x) >> 1]
+        raise AssertionError("%s scale %d maxmotion %g: %d pixels differ, first (%d, %d) vector %s: device %s numpy %s"
+                             % (what, scale, maxmotion, len(bad), x, y, tuple(cell), img[y, x], exp[y, x]))
+    return exp_range
+
+
+@pytest.mark.parametrize("name", list(WIDE))
+def test_one_large_vector_in_every_lane_iteration_and_tile(bbme, name):
+    """A grid of vectors in [-20, 20] in which ONE cell -- the one sampled column i* of the last sampled row reads -- holds
+    (+300, +200) or (-300, -200): max radius and max u / max v (min u / min v) then come from that cell alone, i.e. from lane
+    i* % 256 in iteration (i* % 1024) / 256 of range tile i* / 1024, and the image is normalised by it."""
+    (w, h, search, block), plan = WIDE[name]
+    mf = _zero_mf(bbme, w, h, search, block, plan)
+    ch, cw = mf.cells_shape
+    base = np.random.default_rng(w).integers(-20, 21, (ch, cw, 2)).astype(np.int16)
+    calls = 0
+    for scale in (1, 2, 3):
+        ncx, ncy = _sampled(mf, scale)
+        assert mf.color_shape(scale)[:2] == ((ncy, ncx) if scale > 1 else (h, w))
+        base_range = np_color_cells(base, w, h, mf.padding_x, mf.padding_y, scale)[1]
+        if scale == 1:
+            assert base_range == (float(np.sqrt(np.float32(800))), -20.0, 20.0, -20.0, 20.0)
+        columns = [i for i in PROBE_COLUMNS if i < ncx - 1] + [ncx - 1]
+        if name == "2100x8":
+            assert ncx == (1050, 1050, 700)[scale - 1] and len(columns) == (9, 9, 5)[scale - 1]
+        for i in columns:
+            for vec in PROBE_VECTORS:
+                cells = base.copy()
+                cells[_sampled_cell(mf, scale, i, ncy - 1)] = vec
+                what = "%s column %d vector %s" % (name, i, vec)
+                kw = {}
+                if name == "2098x16":                  # 3 x 2098 bytes a row: 6294 + 5 and 6294 + 2 (a multiple of 4: twin rows)
+                    kw = dict(pitch_extra=5, offset=3) if vec[0] > 0 else dict(pitch_extra=2, offset=1)
+                fixed = i == columns[-2] and vec[0] > 0
+                r = _assert_device_equals_restatement(bbme, mf, cells, scale, FIXED if fixed else -1.0, what, **kw)
+                # without that cell the range is another one: the comparison above hangs on this one lane-iteration
+                lo = vec[0] < 0
+                assert r[0] != base_range[0] and r[1 + (not lo)] != base_range[1 + (not lo)] and r[3 + (not lo)] != base_range[3 + (not lo)], what
+                assert r[1 + lo] == base_range[1 + lo] and r[3 + lo] == base_range[3 + lo], what
+                if name == "2100x8" and scale == 1:
+                    assert r == ((float(np.sqrt(np.float32(130000))), -20.0, 300.0, -20.0, 200.0) if not lo else
+                                 (float(np.sqrt(np.float32(130000))), -300.0, 20.0, -200.0, 20.0)), what
+                if i == columns[-1]:
+                    _assert_device_equals_restatement(bbme, mf, cells, scale, -1.0, what + ", range only", want=("range",))
+                    _assert_device_equals_restatement(bbme, mf, cells, scale, -1.0, what + ", image only", want=("out",), **kw)
+                calls += 1
+    assert calls == {"2100x8": 46, "2098x16": 46, "1030x8": 26}[name]
+    mf.close()
+
+
+def test_vectors_over_the_whole_int16_range(bbme):
+    """16 x 1050 cells of random int16 vectors with the bounds at known cells, normalised by their own radius (46341), by 7.5, by
+    the smallest normal float (u / maxrad overflows to infinity: radius inf, the angle still finite) and by 3e38 (quotients
+    underflow: everything at the wheel's centre): device == host mirror == numpy restatement, image and range."""
+    mf = _zero_mf(bbme, 2100, 32, [4], [4], (2100, 32, 0, 0))
+    cells = full_range_grid()
+    assert cells.shape[:2] == mf.cells_shape
+    for scale in (1, 3, 4):
+        for maxmotion in (-1.0, FIXED) + EXTREME_MAXMOTIONS:
+            _assert_device_equals_restatement(bbme, mf, cells, scale, maxmotion, "full range")
+    r = _device(mf, cells, 1, -1.0, want=("range",))[1]
+    assert r == (float(np.sqrt(np.float32(2) * np.float32(32768) ** 2)), -32768.0, 32767.0, -32768.0, 32767.0)
+    mf.close()
+
+
+def _rolled_beyond(frame, cut, shift=3):
+    """The frame with its columns from `cut` on rolled right by `shift` pixels: the true motion there is (+shift, 0)."""
+    out = frame.copy()
+    out[:, cut:] = np.roll(frame[:, cut:], shift, axis=1)
+    return out
+
+
+def test_every_pairs_range_from_one_launch_on_wide_rows(bbme):
+    """bbme_flow_ranges on rows of two range tiles, the pair as blockIdx.y: pair 0 moves from column 400 on, pair 1 only from
+    column 2060 on -- its extreme u lies in the second tile alone --, pair 2 not at all."""
+    w, h, search, block = 2100, 8, [12], [4]
+    assert bbme.plan_padding(w, h, search, block) == (2100, 8, 0, 0)
+    f0 = np.random.default_rng(2100).integers(0, 256, (h, w), dtype=np.uint8)
+    f1 = _rolled_beyond(f0, 400)
+    f2 = _rolled_beyond(f1, 2060)
+    video = [f0, f1, f2, f2.copy()]
+    batch = bbme.MFBatch([(video[p], video[p + 1]) for p in range(3)], search, block)
+    chain = bbme.MFChain(video, search, block)
+    for ctx, what in ((batch, "batch"), (chain, "chain")):
+        ctx.estimate_async()
+        cells = [ctx.get_pair_cells(p) for p in range(3)]
+        u = cells[1][..., 0]                               # scale 1, no padding: sampled column i is cell column i
+        assert u.max() == 3 and (u[:, :1024] < 3).all() and (u[:, 1024:] == 3).any(), what
+        assert cells[0][..., 0].max() == 3 and (cells[0][:, :1024, 0] == 3).any() and not cells[2].any(), what
+        for scale in (1, 2, 3):
+            exp = [np_color_cells(c, w, h, 0, 0, scale) for c in cells]
+            ranges = ctx.flow_ranges_all("forward", scale)
+            assert ranges.shape == (3, 5) and ranges.dtype == np.float32
+            assert [tuple(float(v) for v in row) for row in ranges] == [e[1] for e in exp], (what, scale)
+            for p in range(3):
+                assert np.array_equal(ctx.get_pair_flow_color(p, scale), exp[p][0]), (what, scale, p)
+                assert ctx.last_color_range == exp[p][1], (what, scale, p)
+        assert [tuple(float(v) for v in row)[2] for row in ctx.flow_ranges_all("forward", 1)] == [3.0, 3.0, 0.0], what
+        ctx.close()
+
+
+def test_the_image_buffer_grows_from_call_to_call(bbme):
+    """bbme_get_flow_color_host's device image is as large as the largest image asked for so far: smallest first."""
+    f1, f2 = _pair(bbme)
+    mf = bbme.MF(f1, f2, *MOVING)
+    mf.estimate_async()
+    cells = mf.get_cells()
+    sizes = []
+    for scale in (4, 3, 1, 4, 2):
+        got = mf.flow_color(scale)
+        exp, exp_range = _host(bbme, mf, cells, scale, -1.0)
+        assert got.shape == exp.shape and np.array_equal(got, exp), scale
+        assert mf.last_color_range == exp_range, scale
+        sizes.append(got.size)
+    assert sizes[0] < sizes[1] < sizes[2] and sizes[3] < sizes[2]
     mf.close()
 
 

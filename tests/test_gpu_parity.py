@@ -349,36 +349,74 @@ def test_device_frames_gpu_pyramid(bbme, oracle):
     mf.close()
 
 
+# (w, h) of a case below -> (its level widths, narrow).  narrow: also on 0 / 255 noise, and through a chain context of two pairs
+PYRAMID_WIDTHS = {(250, 130): ([256], False), (100, 60): ([112, 56, 28], False), (1000, 700): ([1024, 512, 256, 128], False),
+                  (1920, 1080): ([1920, 960, 480], False), (3840, 2160): ([3840, 1920, 960, 480], False),
+                  (16, 16): ([16, 8, 4], True), (8, 8): ([8, 4], True), (24, 16): ([24, 12], True), (40, 32): ([40, 20], True)}
+
+
 @pytest.mark.parametrize("w,h,search,block", [
     (250, 130, [30], [16]),                              # padded both ways, one level (border copy only)
-    (100, 60, [12, 12, 12], [4, 4, 4]),                  # level widths 104 / 52 / 26: the one-pixel-per-thread pyrDown
+    (100, 60, [12, 12, 12], [4, 4, 4]),                  # padded to 112 x 64, level widths 112 / 56 / 28: pyrDown rows of 14 and 7 threads
     (1000, 700, [24, 24, 24, 24], [8, 8, 8, 8]),         # odd-looking size, four levels
     (1920, 1080, [48, 48, 48], [16, 16, 16]),            # cfg2
     (3840, 2160, [80, 80, 80, 80], [16, 16, 16, 16]),    # cfg3: the bench's geometry
+    # the narrowest levels a context takes.  Every level width is a multiple of 4, so every level that is pyrDown's source is a
+    # multiple of 8 wide; a source row of 8 pixels is served by ONE thread, which is the row's first and its last at once
+    (16, 16, [2, 2, 2], [2, 2, 2]),                      # 16 / 8 / 4: two threads per row, then one
+    (8, 8, [2, 2], [2, 2]),                              # 8 / 4: one thread per row
+    (24, 16, [2, 2], [2, 2]),                            # 24 / 12: three threads per row
+    (40, 32, [4, 4], [4, 4]),                            # 40 / 20: five
 ])
 def test_gpu_pyramid_planes_match_the_oracle(bbme, oracle, w, h, search, block):
     """MF::MF on the GPU (zero border :57-61, pyrDown cascade :86-106) for frames in HBM and for host frames (which take
-    the same kernels): every plane of every level equals the oracle's, including rows of a strided (pitch > width) tensor."""
+    the same kernels): every plane of every level equals the oracle's, including rows of a strided (pitch > width) tensor.
+    The narrow cases also run on 0 / 255 noise and through the frame runs of a chain context of two pairs, whose three slots must
+    hold the same planes."""
     import torch
-    rng = np.random.default_rng(w * 7 + h)
-    f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
-    f2 = rng.integers(0, 256, (h, w), dtype=np.uint8)
     L = len(block)
-    omf = oracle.OracleMF(f1, f2, search, block)
-    wide = torch.zeros((2, h, w + 13), dtype=torch.uint8, device="cuda")
-    wide[0, :, :w] = torch.from_numpy(f1).cuda()
-    wide[1, :, :w] = torch.from_numpy(f2).cuda()
-    for frames_on_device in (True, False):
-        if frames_on_device:
-            mf = bbme.MF(wide[0, :, :w], wide[1, :, :w], search, block, L, frames_on_device=True)
-        else:
-            mf = bbme.MF(f1, f2, search, block, L)
-        for lvl in range(L):
-            a, b = mf.get_level_planes(lvl)
-            assert np.array_equal(a, omf.image(lvl, 1)), "image1 plane of level %d (device frames: %s)" % (lvl, frames_on_device)
-            assert np.array_equal(b, omf.image(lvl, 2)), "image2 plane of level %d (device frames: %s)" % (lvl, frames_on_device)
-        mf.close()
-    omf.close()
+    widths, narrow = PYRAMID_WIDTHS[w, h]
+    assert [bbme.plan_padding(w, h, search, block)[0] >> l for l in range(L)] == widths
+    assert all(x % 4 == 0 for x in widths) and all(x % 8 == 0 for x in widths[:-1])
+    rng = np.random.default_rng(w * 7 + h)
+    contents = [[rng.integers(0, 256, (h, w), dtype=np.uint8) for _ in range(2)]]
+    if narrow:
+        contents.append([(rng.integers(0, 2, (h, w)) * 255).astype(np.uint8) for _ in range(2)])
+    for f1, f2 in contents:
+        omf = oracle.OracleMF(f1, f2, search, block)
+        assert [omf.level_shape(l)[1] for l in range(L)] == widths
+        if narrow:                                                    # the oracle's planes are its pad_zero / pyr_down cascade
+            p = oracle.pad_zero(f1, omf.padding_x, omf.padding_y)
+            for lvl in range(L):
+                assert np.array_equal(p, omf.image(lvl, 1))
+                p = oracle.pyr_down(p)
+        wide = torch.zeros((2, h, w + 13), dtype=torch.uint8, device="cuda")
+        wide[0, :, :w] = torch.from_numpy(f1).cuda()
+        wide[1, :, :w] = torch.from_numpy(f2).cuda()
+        for frames_on_device in (True, False):
+            if frames_on_device:
+                mf = bbme.MF(wide[0, :, :w], wide[1, :, :w], search, block, L, frames_on_device=True)
+            else:
+                mf = bbme.MF(f1, f2, search, block, L)
+            assert [mf.level_geometry(lvl)[0] for lvl in range(L)] == widths
+            for lvl in range(L):
+                a, b = mf.get_level_planes(lvl)
+                assert np.array_equal(a, omf.image(lvl, 1)), "image1 plane of level %d (device frames: %s)" % (lvl, frames_on_device)
+                assert np.array_equal(b, omf.image(lvl, 2)), "image2 plane of level %d (device frames: %s)" % (lvl, frames_on_device)
+            mf.close()
+        if narrow:
+            for frames_on_device in (True, False):
+                if frames_on_device:
+                    chain = bbme.MFChain([wide[0, :, :w], wide[1, :, :w], wide[0, :, :w]], search, block, L, frames_on_device=True)
+                else:
+                    chain = bbme.MFChain([f1, f2, f1], search, block, L)
+                assert chain.batch == 2
+                for lvl in range(L):
+                    for slot in range(3):
+                        assert np.array_equal(chain.get_slot_plane(lvl, slot), omf.image(lvl, 1 + slot % 2)), \
+                            "slot %d of level %d (device frames: %s)" % (slot, lvl, frames_on_device)
+                chain.close()
+        omf.close()
 
 
 def _write_pgm(path, img):

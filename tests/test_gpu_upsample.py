@@ -1,12 +1,19 @@
 """The reference's x4 pipeline on the GPU (main_class.cpp:32-33, 58-70): original frames in (k_resize_x4_pad writes the
 level-0 planes), the subsampled field out (k_subsample reads the 2x2-cell grid).  Everything must be byte for byte what the
-host pipeline resize_x4 -> MF -> get_flow -> subsample_div4 gives."""
+host pipeline resize_x4 -> MF -> get_flow -> subsample_div4 gives.
+
+The planes are also compared with the CPU oracle (resize_linear_x4, pad_zero, pyr_down) on content that tells a wrong filter weight
+or truncation apart -- noise, 0 / 255 noise, a checkerboard of period 1, ramps, white -- and on the smallest sources there are:
+one column, one row, rows shorter than the kernel's 8-byte window; through host frames, device frames with a pitch and the
+frame runs of a chain context."""
 import ctypes as C
 import os
 import subprocess
 
 import numpy as np
 import pytest
+
+from helpers import HARD_CONTENTS, hard_content
 
 pytestmark = pytest.mark.gpu
 
@@ -80,6 +87,84 @@ def test_x4_planes_equal_host_resize(bbme, w, h, cfg):
         assert np.array_equal(a, exp[l][0]) and np.array_equal(b, exp[l][1]), "device x4, level %d" % l
     mf.close()
     host.close()
+
+
+# (source width, source height, search, block, (padded width, padded height, pad_x, pad_y) of the x4 frame)
+HARD_SOURCES = [(1, 1, [2], [2], (4, 4, 0, 0)),                   # one source pixel: sw - 1 == 0 and sh == 1, every tap clamped
+                (2, 1, [2], [2], (8, 4, 0, 0)),                   # one row
+                (1, 2, [2], [2], (4, 8, 0, 0)),                   # one column
+                (3, 2, [2], [2], (12, 8, 0, 0)),                  # a row shorter than the 8 bytes a thread gathers
+                (5, 3, [8], [8], (24, 16, 2, 2)),                 # padded both ways, the row's last chunk is half a chunk
+                (9, 7, [4, 4], [4, 4], (40, 32, 2, 2)),           # two levels: a pyrDown row of five threads
+                (45, 22) + SMALL + ((192, 96, 6, 4),)]
+
+
+def _oracle_planes(oracle, frame, pad_x, pad_y, levels):
+    planes = [oracle.pad_zero(oracle.resize_linear_x4(frame), pad_x, pad_y)]
+    for _ in range(levels - 1):
+        planes.append(oracle.pyr_down(planes[-1]))
+    return planes
+
+
+@pytest.mark.parametrize("w,h,search,block,plan", HARD_SOURCES, ids=["%dx%d" % c[:2] for c in HARD_SOURCES])
+def test_x4_planes_of_hard_content_equal_the_oracle(bbme, oracle, w, h, search, block, plan):
+    """Every plane of every level against oracle.pad_zero(oracle.resize_linear_x4(frame)) and its pyr_down cascade -- not
+    against a second context of this library.  The contexts are re-used from content to content, so every byte of a plane has
+    to be written again each time."""
+    import torch
+    assert bbme.plan_padding(4 * w, 4 * h, search, block) == plan
+    L = len(block)
+    frames = [hard_content(name, h, w, seed=7) for name in HARD_CONTENTS]
+    exp = [_oracle_planes(oracle, f, plan[2], plan[3], L) for f in frames]
+    assert exp[0][0].shape == (plan[1], plan[0])
+    n = len(frames)
+    mf = chain = None
+    for k in range(n):
+        a, b = k, (k + 1) % n
+        # host frames
+        if mf is None:
+            mf = bbme.MF(frames[a], frames[b], search, block, upsample=4)
+            assert (mf.padded_width, mf.padded_height, mf.padding_x, mf.padding_y) == plan
+        else:
+            mf.set_frames(frames[a], frames[b])
+        for l in range(L):
+            p1, p2 = mf.get_level_planes(l)
+            assert np.array_equal(p1, exp[a][l]) and np.array_equal(p2, exp[b][l]), ("host", HARD_CONTENTS[a], l)
+        # device frames, rows further apart than the frame is wide; the other order, so that both planes change
+        dev = []
+        for f in (frames[b], frames[a]):
+            big = torch.full((h, w + 13), 7, dtype=torch.uint8, device="cuda")
+            big[:, :w] = torch.from_numpy(f).cuda()
+            dev.append(big[:, :w])
+        mf.set_frames_device(*dev)
+        for l in range(L):
+            p1, p2 = mf.get_level_planes(l)
+            assert np.array_equal(p1, exp[b][l]) and np.array_equal(p2, exp[a][l]), ("device", HARD_CONTENTS[a], l)
+    mf.close()
+    # a chain of two pairs: three frames per run, the frame as a grid dimension (k_resize_x4_pad_run, k_pyr_down4_run)
+    for first in (0, 3, 1):
+        run = [(first + i) % n for i in range(3)]
+        if chain is None:
+            chain = bbme.MFChain([frames[i] for i in run], search, block, upsample=4)
+            assert chain.batch == 2 and chain.slots == 3
+        else:
+            chain.set_frame_run(0, [frames[i] for i in run])
+        for slot, i in enumerate(run):
+            for l in range(L):
+                assert np.array_equal(chain.get_slot_plane(l, slot), exp[i][l]), ("chain", HARD_CONTENTS[i], slot, l)
+    chain.close()
+    # frames in HBM; then a run with a pitch into the last two slots only: the first keeps its planes
+    chain = bbme.MFChain([torch.from_numpy(frames[i]).cuda() for i in (2, 3, 5)], search, block, frames_on_device=True, upsample=4)
+    dev = []
+    for i in (4, 0):
+        big = torch.full((h, w + 5), 9, dtype=torch.uint8, device="cuda")
+        big[:, :w] = torch.from_numpy(frames[i]).cuda()
+        dev.append(big[:, :w])
+    chain.set_frame_run(1, dev)
+    for slot, i in enumerate((2, 4, 0)):
+        for l in range(L):
+            assert np.array_equal(chain.get_slot_plane(l, slot), exp[i][l]), ("chain, device run", HARD_CONTENTS[i], slot, l)
+    chain.close()
 
 
 @pytest.fixture(scope="module")

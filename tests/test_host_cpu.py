@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
+from helpers import HARD_CONTENTS, hard_content
 
 
 def test_library_exports_every_declared_symbol(bbme):
@@ -99,6 +100,18 @@ def test_pad_pyrdown_resize_match_oracle(bbme, oracle):
         assert np.array_equal(bbme.pad_zero(img, 5, 3), oracle.pad_zero(img, 5, 3))
         assert np.array_equal(bbme.pyr_down(img), oracle.pyr_down(img))
         assert np.array_equal(bbme.resize_x4(img), oracle.resize_linear_x4(img))
+    # the x4 filter's clamps on the smallest sources (one column: sw - 1 == 0; one row; rows shorter than the device kernel's 8-byte
+    # window) and on content where a wrong weight or a wrong truncation of the two-stage fixed point shows: 0 / 255 next to each other
+    for (h, w) in [(1, 1), (3, 1), (1, 3), (3, 2), (4, 5), (2, 1), (1, 2), (2, 3), (3, 5), (7, 9), (22, 45)]:
+        for name in HARD_CONTENTS:
+            img = hard_content(name, h, w, seed=3)
+            assert np.array_equal(bbme.resize_x4(img), oracle.resize_linear_x4(img)), (name, h, w)
+            assert np.array_equal(bbme.pad_zero(img, 2, 2), oracle.pad_zero(img, 2, 2)), (name, h, w)
+    for (h, w) in [(4, 8), (8, 8), (16, 16), (16, 24), (32, 40), (2, 2)]:
+        for name in HARD_CONTENTS:
+            img = hard_content(name, h, w, seed=4)
+            assert np.array_equal(bbme.pyr_down(img), oracle.pyr_down(img)), (name, h, w)
+    assert np.all(bbme.resize_x4(hard_content("white", 3, 2)) == 255)
     # constant images stay constant, a pyrDown of a ramp stays a ramp in the interior
     c = np.full((32, 32), 201, np.uint8)
     assert np.all(bbme.pyr_down(c) == 201) and np.all(bbme.resize_x4(c) == 201)
