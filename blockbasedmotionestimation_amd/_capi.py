@@ -117,6 +117,20 @@ SIGNATURES = {
     "bbme_interpolation_stats": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_interpolate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_bgr_to_gray_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_set_frames_host_bgr": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bbme_set_frames_host_bgr_async": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bbme_set_frames_device_bgr": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int]),
+    "bbme_set_chain_frames_host_bgr": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int]),
+    "bbme_set_chain_frames_host_bgr_async": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int]),
+    "bbme_set_chain_frames_device_bgr": (C.c_int, [_ctx, C.c_int, C.c_int, _P(C.c_void_p), C.c_int]),
+    "bbme_bgr_frames_device_pair": (C.c_int, [_ctx, C.c_int, _P(C.c_void_p), _P(C.c_void_p)]),
+    "bbme_cells_interpolate_bgr_device": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                    C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "bbme_interpolate_bgr_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "bbme_get_interpolated_bgr_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_interpolate_bgr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "bbme_cells_color_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_flow_color_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_get_flow_color_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_void_p]),

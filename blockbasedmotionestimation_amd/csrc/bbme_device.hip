@@ -294,6 +294,18 @@ struct bbme_ctx {
                                                   // bbme_cells_color_device; k_color_range), then five floats per slot
     DevBuf<uint8_t> color_img;                    // bbme_get_flow_color_host: the packed B,G,R image before its download (grown to
                                                   // the largest asked for)
+    // COLOUR STORE (include/bbme.h): one packed B,G,R frame (pitch 3 width) per frame the context holds, bgr_stride bytes apart,
+    // allocated by the first *_bgr setter: frame i of pair p in slot 2 p + i, on a chain context frame slot s in slot s.
+    // bgr_set[slot]: the slot's colour is what its luma plane was made from (cleared by every grey setter of that frame).
+    DevBuf<uint8_t> bgr;
+    size_t bgr_stride = 0;
+    std::vector<uint8_t> bgr_set;
+    int bgr_slot(int pair, int which) const { return chain ? pair + which : 2 * pair + which; }
+    void clear_bgr(int slot, int count = 1)
+    {
+        for (int s = slot; s < slot + count && s < (int)bgr_set.size(); ++s) bgr_set[s] = 0;
+    }
+    DevBuf<uint8_t> ip_bgr;                       // bbme_get_interpolated_bgr_host: a packed 3 W x H frame before its download
 };
 
 namespace {
@@ -1237,6 +1249,7 @@ int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, 
     const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
     hipLaunchKernelGGL(k_pad_zero, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
                        pp, g.width, g.height, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    c->clear_bgr(c->bgr_slot(pair, 0), 2);              // grey frames: the stored colour is no longer theirs
     return enqueue_cascade(c, pair);
 }
 
@@ -1286,6 +1299,7 @@ int bbme_set_frames_device_x4(bbme_ctx *c, int pair, const uint8_t *d_image1, co
     const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
     hipLaunchKernelGGL(k_resize_x4_pad, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
                        pp, g.width / 4, g.height / 4, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    c->clear_bgr(c->bgr_slot(pair, 0), 2);
     return enqueue_cascade(c, pair);
 }
 
@@ -1332,21 +1346,10 @@ static int check_chain_run(const bbme_ctx *c, int first, int count, const uint8_
     return BBME_OK;
 }
 
-// `count` frames in HBM into slots first .. : border (or x4 up-sampling + border) as one launch, then one pyrDown launch per
-// level, all frames of the run in each (blockIdx.y); and the bookkeeping every frame setter shares (enqueue_cascade)
-static int enqueue_chain_run(bbme_ctx *c, int first, int count, const FrameRun &run, int pitch, int scale)
+// The pyrDown cascade of slots first .. first + count - 1 from their level-0 planes, one launch per level, all frames of the run
+// in each (blockIdx.y); and the bookkeeping every frame setter shares (enqueue_cascade)
+static int enqueue_chain_cascade(bbme_ctx *c, int first, int count)
 {
-    const Geometry &g = c->geom;
-    Level &L0 = c->lv[0];
-    uint8_t *dst0 = L0.img1 + (size_t)first * L0.plane_stride;
-    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
-    const dim3 grid0((unsigned)((chunks + 255) / 256), (unsigned)count);
-    if (scale == 4)
-        hipLaunchKernelGGL(k_resize_x4_pad_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width / 4, g.height / 4,
-                           pitch, g.pad_x, g.pad_y, L0.width, L0.height);
-    else
-        hipLaunchKernelGGL(k_pad_zero_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width, g.height, pitch,
-                           g.pad_x, g.pad_y, L0.width, L0.height);
     for (size_t l = 1; l < c->lv.size(); ++l) {
         Level &P = c->lv[l - 1], &L = c->lv[l];
         const uint8_t *src = P.img1 + (size_t)first * P.plane_stride;
@@ -1361,6 +1364,24 @@ static int enqueue_chain_run(bbme_ctx *c, int first, int count, const FrameRun &
     c->memo_block = 0;                                  // new planes: what the SAD memo holds is no longer true
     c->fields_valid = false;
     return BBME_OK;
+}
+
+// `count` grey frames in HBM into slots first .. : border (or x4 up-sampling + border) as one launch, then the cascade
+static int enqueue_chain_run(bbme_ctx *c, int first, int count, const FrameRun &run, int pitch, int scale)
+{
+    const Geometry &g = c->geom;
+    Level &L0 = c->lv[0];
+    uint8_t *dst0 = L0.img1 + (size_t)first * L0.plane_stride;
+    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
+    const dim3 grid0((unsigned)((chunks + 255) / 256), (unsigned)count);
+    if (scale == 4)
+        hipLaunchKernelGGL(k_resize_x4_pad_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width / 4, g.height / 4,
+                           pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    else
+        hipLaunchKernelGGL(k_pad_zero_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width, g.height, pitch,
+                           g.pad_x, g.pad_y, L0.width, L0.height);
+    c->clear_bgr(first, count);                         // grey frames: the stored colour is no longer theirs
+    return enqueue_chain_cascade(c, first, count);
 }
 
 int bbme_set_chain_frames_device(bbme_ctx *c, int first, int count, const uint8_t *const *d_frames, int pitch, int scale)
@@ -1414,11 +1435,18 @@ int bbme_chain_advance(bbme_ctx *c)
     const unsigned wgs = std::max(1u, std::min(2048u, (most + 255u) / 256u));
     hipLaunchKernelGGL(k_chain_roll, dim3(wgs, (unsigned)c->lv.size()), dim3(256), 0, c->stream, r);
     HIP_TRY(hipGetLastError());
+    const bool had_bgr = !c->bgr_set.empty() && c->bgr_set[c->batch] != 0;
+    c->clear_bgr(0, c->batch + 1);
     const bool had_last = c->batch < 64 ? (c->frames_mask >> c->batch) & 1ull : c->last_slot;
     c->frames_mask = had_last ? 1ull : 0ull;         // slot 0 is as set as the slot it came from
     c->last_slot = false;
     c->memo_block = 0;
     c->fields_valid = false;
+    if (had_bgr) {                                      // the last slot's colour goes with its planes; slot 0 has colour once the copy is enqueued
+        HIP_TRY(hipMemcpyAsync(c->bgr.get(), c->bgr + (size_t)c->batch * c->bgr_stride, c->bgr_stride, hipMemcpyDeviceToDevice,
+                               c->stream));
+        c->bgr_set[0] = 1;
+    }
     return BBME_OK;
 }
 
@@ -1433,6 +1461,134 @@ int bbme_get_chain_plane_host(bbme_ctx *c, int level, int slot, uint8_t *image)
     const Level &L = c->lv[level];
     HIP_TRY(hipMemcpyAsync(image, L.img1 + (size_t)slot * L.plane_stride, (size_t)L.width * L.height, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
+    return BBME_OK;
+}
+
+// ---- colour frames in (the luma rule of include/bbme.h; k_bgr_pad, k_bgr_pad_run) and the colour store ------------------
+
+// the colour store, allocated on first use: one packed frame per frame of the context
+static int bgr_store(bbme_ctx *c)
+{
+    if (c->bgr.get()) return BBME_OK;
+    const size_t slots = c->chain ? (size_t)c->batch + 1 : (size_t)2 * c->batch;
+    c->bgr_stride = ((size_t)3 * c->geom.width * c->geom.height + 255) / 256 * 256;
+    if (int rc = c->bgr.alloc(c->bgr_stride * slots, "the colour store")) return rc;
+    c->bgr_set.assign(slots, 0);
+    return BBME_OK;
+}
+
+static int check_bgr_pair(const bbme_ctx *c, int pair, const void *image1, const void *image2, int pitch, const char *what)
+{
+    if (int rc = pair_context_only(c, what)) return rc;
+    if (!image1 || !image2 || (long long)pitch < 3LL * c->geom.width || pair < 0 || pair >= c->batch)
+        return bbme::fail(BBME_ERR_INVALID, "%s: bad arguments (pitch %d, 3 x width %d, pair %d of %d)", what, pitch,
+                          3 * c->geom.width, pair, c->batch);
+    return BBME_OK;
+}
+
+// Both colour frames of a pair in HBM (rows `pitch` bytes apart) into its level-0 luma planes, then the cascade.  keep: the
+// frames are a caller's and are copied into the pair's slots of the store in the same pass; otherwise they ARE those slots.
+static int enqueue_bgr_pair(bbme_ctx *c, int pair, const uint8_t *d1, const uint8_t *d2, int pitch, bool keep)
+{
+    const Geometry &g = c->geom;
+    const size_t pp_ = (size_t)pair;
+    Level &L0 = c->lv[0];
+    uint8_t *s1 = c->bgr + (size_t)c->bgr_slot(pair, 0) * c->bgr_stride, *s2 = c->bgr + (size_t)c->bgr_slot(pair, 1) * c->bgr_stride;
+    BgrPair pp{{d1, d2}, {L0.img1 + pp_ * L0.plane_stride, L0.img2 + pp_ * L0.plane_stride}, {keep ? s1 : nullptr, keep ? s2 : nullptr}};
+    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
+    hipLaunchKernelGGL(k_bgr_pad, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
+                       pp, g.width, g.height, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    if (int rc = enqueue_cascade(c, pair)) return rc;
+    c->bgr_set[c->bgr_slot(pair, 0)] = c->bgr_set[c->bgr_slot(pair, 1)] = 1;
+    return BBME_OK;
+}
+
+int bbme_set_frames_device_bgr(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
+{
+    if (int rc = check_bgr_pair(c, pair, d_image1, d_image2, pitch, "bbme_set_frames_device_bgr")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = bgr_store(c)) return rc;
+    return enqueue_bgr_pair(c, pair, d_image1, d_image2, pitch, true);
+}
+
+int bbme_set_frames_host_bgr_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    if (int rc = check_bgr_pair(c, pair, image1, image2, pitch, "bbme_set_frames_host_bgr")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = bgr_store(c)) return rc;
+    // straight into the store, packed: the frame crosses PCIe once, and the conversion reads it where it stays
+    const size_t row = (size_t)3 * c->geom.width;
+    const uint8_t *src[2] = {image1, image2};
+    uint8_t *slot[2];
+    for (int i = 0; i < 2; ++i) {
+        slot[i] = c->bgr + (size_t)c->bgr_slot(pair, i) * c->bgr_stride;
+        c->bgr_set[c->bgr_slot(pair, i)] = 0;               // until the planes are made of it
+        HIP_TRY(hipMemcpy2DAsync(slot[i], row, src[i], (size_t)pitch, row, (size_t)c->geom.height, hipMemcpyHostToDevice, c->stream));
+    }
+    return enqueue_bgr_pair(c, pair, slot[0], slot[1], (int)row, false);
+}
+
+int bbme_set_frames_host_bgr(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    if (int rc = bbme_set_frames_host_bgr_async(c, pair, image1, image2, pitch)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
+    return BBME_OK;
+}
+
+static int check_bgr_run(const bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, const char *what)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_chain_run(c, first, count, frames, c->geom.width, 1, what)) return rc;      // the slots and the table
+    if ((long long)pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: pitch %d < 3 x frame width %d", what, pitch, c->geom.width);
+    return BBME_OK;
+}
+
+// enqueue_bgr_pair for the slots first .. first + count - 1 of a chain context
+static int enqueue_bgr_run(bbme_ctx *c, int first, int count, const FrameRun &run, int pitch, bool keep)
+{
+    const Geometry &g = c->geom;
+    Level &L0 = c->lv[0];
+    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
+    hipLaunchKernelGGL(k_bgr_pad_run, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, run,
+                       L0.img1 + (size_t)first * L0.plane_stride, L0.plane_stride,
+                       keep ? c->bgr + (size_t)first * c->bgr_stride : nullptr, c->bgr_stride, g.width, g.height, pitch, g.pad_x,
+                       g.pad_y, L0.width, L0.height);
+    if (int rc = enqueue_chain_cascade(c, first, count)) return rc;
+    for (int i = 0; i < count; ++i) c->bgr_set[first + i] = 1;
+    return BBME_OK;
+}
+
+int bbme_set_chain_frames_device_bgr(bbme_ctx *c, int first, int count, const uint8_t *const *d_frames, int pitch)
+{
+    if (int rc = check_bgr_run(c, first, count, d_frames, pitch, "bbme_set_chain_frames_device_bgr")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = bgr_store(c)) return rc;
+    FrameRun run{};
+    for (int i = 0; i < count; ++i) run.src[i] = d_frames[i];
+    return enqueue_bgr_run(c, first, count, run, pitch, true);
+}
+
+int bbme_set_chain_frames_host_bgr_async(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch)
+{
+    if (int rc = check_bgr_run(c, first, count, frames, pitch, "bbme_set_chain_frames_host_bgr")) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = bgr_store(c)) return rc;
+    const size_t row = (size_t)3 * c->geom.width;
+    FrameRun run{};
+    for (int i = 0; i < count; ++i) {
+        uint8_t *d = c->bgr + (size_t)(first + i) * c->bgr_stride;
+        c->bgr_set[first + i] = 0;
+        HIP_TRY(hipMemcpy2DAsync(d, row, frames[i], (size_t)pitch, row, (size_t)c->geom.height, hipMemcpyHostToDevice, c->stream));
+        run.src[i] = d;
+    }
+    return enqueue_bgr_run(c, first, count, run, (int)row, false);
+}
+
+int bbme_set_chain_frames_host_bgr(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch)
+{
+    if (int rc = bbme_set_chain_frames_host_bgr_async(c, first, count, frames, pitch)) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
     return BBME_OK;
 }
 
@@ -1458,6 +1614,7 @@ int bbme_set_level_planes_host(bbme_ctx *c, int level, const uint8_t *image1, co
     HIP_TRY(hipMemcpyAsync(L.img2, image2, (size_t)L.width * L.height, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->mark_pair0();
+    c->clear_bgr(0, 2);                                 // pair 0's frames (a chain of one pair: slots 0 and 1)
     c->memo_block = 0;
     c->fields_valid = false;
     return BBME_OK;
@@ -2268,6 +2425,133 @@ int bbme_interpolation_stats(bbme_ctx *c, int num, int den, const int *window, u
     if (int rc = enqueue_ip(c, 0, c->batch, L.final_grid(), L.grid_stride(L.final_grid()), c->bwd_cells, c->bwd_stride, num, 1, den, window,
                             nullptr, 0, 0, nullptr, 0, 0, c->ip_stats + (size_t)4 * BBME_MAX_BATCH, c->ip_stats, c->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(stats, c->ip_stats, (size_t)4 * sizeof(unsigned long long) * c->batch, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+// ---- colour frames out (the BGR interpolation rule of include/bbme.h; k_interpolate_bgr) -----------------------------------
+
+// the stored colour of `pair` as the current direction reads it (frame 1, frame 2), or BBME_ERR_STATE
+static int stored_bgr(const bbme_ctx *c, int pair, const char *what, const uint8_t **bgr1, const uint8_t **bgr2)
+{
+    const int s1 = c->bgr_slot(pair, c->direction ? 1 : 0), s2 = c->bgr_slot(pair, c->direction ? 0 : 1);
+    if (c->bgr_set.empty() || !c->bgr_set[s1] || !c->bgr_set[s2])
+        return bbme::fail(BBME_ERR_STATE, "%s: pair %d has no stored colour (set both frames with a *_bgr setter)", what, pair);
+    *bgr1 = c->bgr + (size_t)s1 * c->bgr_stride;
+    *bgr2 = c->bgr + (size_t)s2 * c->bgr_stride;
+    return BBME_OK;
+}
+
+int bbme_bgr_frames_device_pair(bbme_ctx *c, int pair, const uint8_t **d_bgr1, const uint8_t **d_bgr2)
+{
+    const char *what = "bbme_bgr_frames_device_pair";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!d_bgr1 || !d_bgr2) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const uint8_t *a = nullptr, *b = nullptr;
+    if (int rc = stored_bgr(c, pair, what, &a, &b)) return rc;
+    *d_bgr1 = c->direction ? b : a;                        // physical: image 1 as it was set
+    *d_bgr2 = c->direction ? a : b;
+    return BBME_OK;
+}
+
+// k_interpolate_bgr over `count` phases from num0 on, one pair; bgr1 / bgr2 already in the direction's order
+static int enqueue_ip_bgr(bbme_ctx *c, int pair, const mv_t *d_f, const mv_t *d_b, const uint8_t *bgr1, const uint8_t *bgr2, int bgr_pitch,
+                          int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    const Geometry &g = c->geom;
+    IpBgrArgs a{};
+    a.img1 = c->plane1(L) + (size_t)pair * L.plane_stride;
+    a.img2 = c->plane2(L) + (size_t)pair * L.plane_stride;
+    a.fwd = d_f; a.bwd = d_b;
+    a.bgr1 = bgr1; a.bgr2 = bgr2; a.bgr_pitch = bgr_pitch;
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2;
+    a.fw = g.width; a.fh = g.height; a.pad_x = g.pad_x; a.pad_y = g.pad_y;
+    a.num0 = num0; a.den = den;
+    a.magic = (uint32_t)((1ull << 32) / (unsigned)den + 1ull);
+    a.runs_per_row = (a.cw + 3) / 4;
+    a.runs = (long long)a.runs_per_row * (L.height / 2);
+    hipLaunchKernelGGL(k_interpolate_bgr, dim3((unsigned)ip_groups(L), 1, (unsigned)count), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+// phases, output pitch and stride of the colour calls.  Touches no device.
+static int check_ip_bgr(const bbme_ctx *c, int num0, int count, int den, const uint8_t *d_out, int out_pitch, size_t out_stride,
+                        const char *what)
+{
+    if (int rc = check_ip(c, num0, count, den, nullptr, what)) return rc;
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if ((long long)out_pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x frame width %d", what, out_pitch, c->geom.width);
+    return check_ip_frames(c, count, out_pitch, out_stride, out_pitch, c->geom.height, what, "output");
+}
+
+int bbme_cells_interpolate_bgr_device(bbme_ctx *c, int pair, const int16_t *d_fwd, const int16_t *d_bwd, const uint8_t *d_bgr1,
+                                      const uint8_t *d_bgr2, int bgr_pitch, int num0, int count, int den, uint8_t *d_out,
+                                      int out_pitch, size_t out_stride, void *hip_stream)
+{
+    const char *what = "bbme_cells_interpolate_bgr_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!d_fwd) return bbme::fail(BBME_ERR_INVALID, "%s: null forward grid", what);
+    if (int rc = check_ip_bgr(c, num0, count, den, d_out, out_pitch, out_stride, what)) return rc;
+    if ((d_bgr1 == nullptr) != (d_bgr2 == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: one colour frame without the other (both, or neither for the stored colour)", what);
+    if (d_bgr1 && (long long)bgr_pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, bgr_pitch, c->geom.width);
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    const uint8_t *bgr1 = c->direction ? d_bgr2 : d_bgr1, *bgr2 = c->direction ? d_bgr1 : d_bgr2;
+    if (!d_bgr1) {
+        if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
+        bgr_pitch = 3 * c->geom.width;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_ip_bgr(c, pair, reinterpret_cast<const mv_t *>(d_fwd), reinterpret_cast<const mv_t *>(d_bwd), bgr1, bgr2, bgr_pitch,
+                          num0, count, den, d_out, out_pitch, out_stride, stream);
+}
+
+// the context's own two fields and stored colour of `pair` on `stream`
+static int enqueue_own_ip_bgr(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
+                              hipStream_t stream, const char *what)
+{
+    const Level &L = c->lv[0];
+    const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
+    if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
+    const mv_t *f = L.final_grid() + (size_t)pair * L.grid_stride(L.final_grid()), *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
+    return enqueue_ip_bgr(c, pair, f, b, bgr1, bgr2, 3 * c->geom.width, num0, count, den, d_out, out_pitch, out_stride, stream);
+}
+
+int bbme_interpolate_bgr_device(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
+                                void *hip_stream)
+{
+    const char *what = "bbme_interpolate_bgr_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_ip_bgr(c, num0, count, den, d_out, out_pitch, out_stride, what)) return rc;
+    if (int rc = check_ip_state(c, what)) return rc;
+    const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
+    if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;       // before anything is enqueued
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_ip_bgr(c, pair, num0, count, den, d_out, out_pitch, out_stride, stream, what);
+}
+
+int bbme_get_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int den, uint8_t *out)
+{
+    const char *what = "bbme_get_interpolated_bgr_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_ip(c, num, 1, den, nullptr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_ip_state(c, what)) return rc;
+    const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
+    if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)3 * c->geom.width * c->geom.height;
+    if (int rc = c->ip_bgr.ensure(bytes, "the interpolated colour frame")) return rc;
+    if (int rc = enqueue_own_ip_bgr(c, pair, num, 1, den, c->ip_bgr, 3 * c->geom.width, 0, c->stream, what)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->ip_bgr, bytes, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
 }
 

@@ -743,6 +743,55 @@ int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int widt
     return BBME_OK;
 }
 
+// The luma rule of include/bbme.h (the mirror of bgr_luma in bbme_kernels.hpp).
+int bbme_bgr_to_gray_host(const uint8_t *bgr, int width, int height, int pitch, uint8_t *gray)
+{
+    if (!bgr || !gray) return bbme::fail(BBME_ERR_INVALID, "bbme_bgr_to_gray_host: null pointer");
+    if (width < 1 || height < 1 || (long long)pitch < 3LL * width)
+        return bbme::fail(BBME_ERR_INVALID, "bbme_bgr_to_gray_host: bad arguments (%dx%d, pitch %d)", width, height, pitch);
+    for (int y = 0; y < height; ++y) {
+        const uint8_t *p = bgr + (size_t)y * pitch;
+        for (int x = 0; x < width; ++x, p += 3)
+            gray[(size_t)y * width + x] = (uint8_t)((1868 * p[0] + 9617 * p[1] + 4899 * p[2] + 8192) >> 14);
+    }
+    return BBME_OK;
+}
+
+// The BGR interpolation rule of include/bbme.h: the selection of bbme_interpolate_host on the luma planes (its map tells which
+// hypothesis; p1 and p2 follow from it), then the blend of the two colour frames pixel by pixel (the mirror of k_interpolate_bgr).
+int bbme_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int padded_w, int padded_h, const uint8_t *bgr1,
+                              const uint8_t *bgr2, int width, int height, int pad_x, int pad_y, const int16_t *fwd,
+                              const int16_t *bwd, int num, int den, uint8_t *out)
+{
+    const char *what = "bbme_interpolate_bgr_host";
+    if (!luma1 || !luma2 || !bgr1 || !bgr2 || !fwd || !out) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 1 || height < 1 || pad_x < 0 || pad_y < 0 || (long long)width + 2LL * pad_x != padded_w ||
+        (long long)height + 2LL * pad_y != padded_h)
+        return bbme::fail(BBME_ERR_INVALID, "%s: the %dx%d frame with padding (%d, %d) is not the %dx%d plane", what, width, height,
+                          pad_x, pad_y, padded_w, padded_h);
+    const int cw = padded_w / 2;
+    std::vector<uint8_t> sel((size_t)cw * (padded_h / 2) + 1);
+    if (int rc = bbme_interpolate_host(luma1, luma2, padded_w, padded_h, fwd, bwd, num, den, nullptr, nullptr, sel.data(), nullptr))
+        return rc;                                            // odd planes and bad phases are refused there
+    const auto floor_div = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+    const auto texel = [&](const uint8_t *img, int x, int y, int c) {
+        return x < 0 || y < 0 || x >= width || y >= height ? 0 : (int)img[((size_t)y * width + x) * 3 + c];
+    };
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const int X = x + pad_x, Y = y + pad_y, cx = X >> 1, cy = Y >> 1;
+            const size_t c = (size_t)cy * cw + cx;
+            const int k = sel[c];
+            const int vx = k == 0 ? fwd[2 * c] : k == 1 ? -(int)bwd[2 * c] : 0, vy = k == 0 ? fwd[2 * c + 1] : k == 1 ? -(int)bwd[2 * c + 1] : 0;
+            const int p1x = 2 * cx - floor_div(num * vx + den / 2, den), p1y = 2 * cy - floor_div(num * vy + den / 2, den);
+            const int q1x = p1x + (X & 1) - pad_x, q1y = p1y + (Y & 1) - pad_y, q2x = q1x + vx, q2y = q1y + vy;
+            for (int ch = 0; ch < 3; ++ch)
+                out[((size_t)y * width + x) * 3 + ch] =
+                    (uint8_t)(((den - num) * texel(bgr1, q1x, q1y, ch) + num * texel(bgr2, q2x, q2y, ch) + den / 2) / den);
+        }
+    return BBME_OK;
+}
+
 int bbme_subsample_div4(const float *flow_padded, int padded_width, int padded_height,
                         int pad_x, int pad_y, float *out, int out_width, int out_height)
 {

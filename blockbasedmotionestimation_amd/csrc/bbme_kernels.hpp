@@ -2609,6 +2609,82 @@ __global__ __launch_bounds__(256) void k_chain_roll(ChainRoll r)
 }
 
 // =======================================================================================
+// Colour frames in (the luma rule of include/bbme.h): B,G,R frames, rows `pitch` >= 3 width bytes apart at any alignment,
+// become the zero-bordered level-0 luma planes in ONE pass -- conversion and border, pad_zero_plane's launch shape and stores:
+// a thread makes 16 bytes of a plane row from the 48 source bytes under them (three unaligned 16-byte loads inside the frame,
+// bytes at its edges).  With `keep` it also writes those 48 bytes to the packed copy (pitch 3 width) the context keeps of a
+// caller's frame: every pixel of the frame lies under exactly one thread.  Bandwidth-bound like the grey border copy, on four
+// (with keep, seven) bytes per pixel instead of two.  k_bgr_pad: the two frames of a pair (blockIdx.y); k_bgr_pad_run: the
+// frames of a chain run (run.src[f] -> slot f of dst and of keep).
+// =======================================================================================
+struct BgrPair { const uint8_t *src[2]; uint8_t *dst[2]; uint8_t *keep[2]; };
+
+__device__ __forceinline__ uint32_t bgr_luma(uint32_t b, uint32_t g, uint32_t r)
+{
+    return (1868u * b + 9617u * g + 4899u * r + 8192u) >> 14;
+}
+
+__device__ __forceinline__ void bgr_pad_plane(const uint8_t *src, uint8_t *dst, uint8_t *keep, int width, int height, int pitch,
+                                              int pad_x, int pad_y, int pw, int ph)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;    // 16 output bytes (pw is a multiple of 4)
+    const int per_row = (pw + 15) / 16;
+    if (t >= (long long)per_row * ph) return;
+    const int y = (int)(t / per_row), x0 = (int)(t % per_row) * 16;
+    const int sy = y - pad_y, sx0 = x0 - pad_x;
+    uint32_t w[4] = {0, 0, 0, 0};
+    if (sy >= 0 && sy < height) {
+        const uint8_t *row = src + (size_t)sy * pitch;
+        uint8_t *kept = keep ? keep + (size_t)sy * width * 3 : nullptr;
+        uint32_t c[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};       // 16 pixels of B,G,R; 0 outside the frame
+        if (sx0 >= 0 && sx0 + 16 <= width) {
+#pragma unroll
+            for (int q = 0; q < 3; ++q) {
+                const ua_u128 v = *reinterpret_cast<const ua_u128 *>(row + 3 * sx0 + 16 * q);
+                c[4 * q] = v.v[0]; c[4 * q + 1] = v.v[1]; c[4 * q + 2] = v.v[2]; c[4 * q + 3] = v.v[3];
+                if (kept) *reinterpret_cast<ua_u128 *>(kept + 3 * sx0 + 16 * q) = v;
+            }
+        } else {
+#pragma unroll
+            for (int b = 0; b < 48; ++b) {
+                const int sx = sx0 + b / 3;
+                if (sx < 0 || sx >= width) continue;
+                const uint8_t v = row[3 * sx + b % 3];
+                c[b >> 2] |= (uint32_t)v << (8 * (b & 3));
+                if (kept) kept[3 * sx + b % 3] = v;
+            }
+        }
+#pragma unroll
+        for (int b = 0; b < 16; ++b) {
+            const auto ch = [&](int k) { return (c[(3 * b + k) >> 2] >> (8 * ((3 * b + k) & 3))) & 0xffu; };
+            w[b >> 2] |= bgr_luma(ch(0), ch(1), ch(2)) << (8 * (b & 3));
+        }
+    }
+    uint8_t *o = dst + (size_t)y * pw + x0;
+    if (x0 + 16 <= pw && (((uintptr_t)o) & 15u) == 0) {               // the usual case: one 16-byte store
+        *reinterpret_cast<uint4 *>(o) = make_uint4(w[0], w[1], w[2], w[3]);
+    } else {
+        uint32_t *out = reinterpret_cast<uint32_t *>(o);
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+            if (x0 + 4 * q < pw) out[q] = w[q];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_bgr_pad(BgrPair p, int width, int height, int pitch, int pad_x, int pad_y, int pw, int ph)
+{
+    bgr_pad_plane(p.src[blockIdx.y], p.dst[blockIdx.y], p.keep[blockIdx.y], width, height, pitch, pad_x, pad_y, pw, ph);
+}
+
+// keep: slot `first` of the colour store (slots s_keep bytes apart), or null
+__global__ __launch_bounds__(256) void k_bgr_pad_run(FrameRun run, uint8_t *dst, uint32_t s_dst, uint8_t *keep, size_t s_keep,
+                                                     int width, int height, int pitch, int pad_x, int pad_y, int pw, int ph)
+{
+    bgr_pad_plane(run.src[blockIdx.y], dst + (size_t)blockIdx.y * s_dst, keep ? keep + blockIdx.y * s_keep : nullptr, width, height,
+                  pitch, pad_x, pad_y, pw, ph);
+}
+
+// =======================================================================================
 // PMC calibration (bbme_calibrate_read): reads n dwords once with one aligned dword per lane --
 // the access shape of the search kernel's window staging -- so that FETCH_SIZE can be scaled by a
 // known byte count before it is quoted (MI355X_MICROARCH.md, HBM section).
@@ -3095,6 +3171,72 @@ __device__ __forceinline__ uint32_t ip_cell(const uint8_t *img, int W, int x, in
     return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)reinterpret_cast<const ua_u16 *>(p + W)->v << 16;
 }
 
+// One run of a cell row, cells x0 .. x0 + n - 1 (n = 1..4) of row cy: the grids' entries and the cells of the zero hypothesis
+struct IpRun { uint32_t f[4], b[4], z1[4], z2[4]; };
+
+__device__ __forceinline__ IpRun ip_load_run(const uint8_t *img1, const uint8_t *img2, const mv_t *F, const mv_t *B, int W, int CW,
+                                             int cy, int x0, int n)
+{
+    IpRun r;
+    const int oy = 2 * cy;
+    const size_t g0 = (size_t)cy * CW + x0, o0 = (size_t)oy * W + 2 * x0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) r.f[j] = r.b[j] = 0;
+    if (n == 4) {
+        const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(F + g0);
+        r.f[0] = v.v[0]; r.f[1] = v.v[1]; r.f[2] = v.v[2]; r.f[3] = v.v[3];
+        if (B) {
+            const ua_u32x4 u = *reinterpret_cast<const ua_u32x4 *>(B + g0);
+            r.b[0] = u.v[0]; r.b[1] = u.v[1]; r.b[2] = u.v[2]; r.b[3] = u.v[3];
+        }
+        const ua_u32x2 t1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0), u1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0 + W);
+        const ua_u32x2 t2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0), u2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0 + W);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int sh = 16 * (j & 1);
+            r.z1[j] = ((t1.v[j >> 1] >> sh) & 0xffffu) | ((u1.v[j >> 1] >> sh) << 16);
+            r.z2[j] = ((t2.v[j >> 1] >> sh) & 0xffffu) | ((u2.v[j >> 1] >> sh) << 16);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            r.z1[j] = r.z2[j] = 0;
+            if (j >= n) continue;
+            r.f[j] = F[g0 + j];
+            if (B) r.b[j] = B[g0 + j];
+            r.z1[j] = ip_cell(img1, W, 2 * (x0 + j), oy);
+            r.z2[j] = ip_cell(img2, W, 2 * (x0 + j), oy);
+        }
+    }
+    return r;
+}
+
+// What the cell with origin (ox, oy) selects: hypothesis k and its cost, its two cells c1 (of I1 at p1) and c2 (of I2 at
+// p2 = p1 + v).  Shared by k_interpolate, which blends the cells, and k_interpolate_bgr, which gathers colour at p1 and p2.
+struct IpPick { uint32_t c1, c2, k, cost; int p1x, p1y, vx, vy; };
+
+__device__ __forceinline__ IpPick ip_select(const uint8_t *img1, const uint8_t *img2, int W, int H, int ox, int oy, uint32_t f,
+                                            uint32_t b, bool has_b, uint32_t z1, uint32_t z2, int num, int half, int bias,
+                                            uint32_t magic)
+{
+    IpPick s{0u, 0u, 2u, ~0u, ox, oy, 0, 0};                  // nothing selected yet
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h == 1 && !has_b) break;
+        const int vx = h ? -mv_x(b) : mv_x(f), vy = h ? -mv_y(b) : mv_y(f);
+        const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
+        const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
+        const int p1x = ox - sx, p1y = oy - sy, p2x = p1x + vx, p2y = p1y + vy;
+        if (p1x < 0 || p2x < 0 || p1x > W - 2 || p2x > W - 2 || p1y < 0 || p2y < 0 || p1y > H - 2 || p2y > H - 2) continue;
+        const uint32_t q1 = ip_cell(img1, W, p1x, p1y), q2 = ip_cell(img2, W, p2x, p2y);
+        const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
+        if (c < s.cost) s = IpPick{q1, q2, (uint32_t)h, c, p1x, p1y, vx, vy};      // strictly cheaper: the earliest of equals stays
+    }
+    const uint32_t cz = __builtin_amdgcn_sad_u8(z1, z2, 0u);
+    if (cz < s.cost) s = IpPick{z1, z2, 2u, cz, ox, oy, 0, 0};
+    return s;
+}
+
 __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
 {
     const size_t pair = blockIdx.y;
@@ -3111,56 +3253,16 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
         const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
         const int n = min(4, CW - x0);                        // cells of the run inside the row
         const int oy = 2 * cy;
-        uint32_t f[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
-        uint32_t z1[4], z2[4];                                // the cells of the zero hypothesis
-        const size_t g0 = (size_t)cy * CW + x0, o0 = (size_t)oy * W + 2 * x0;
-        if (n == 4) {
-            const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(F + g0);
-            f[0] = v.v[0]; f[1] = v.v[1]; f[2] = v.v[2]; f[3] = v.v[3];
-            if (B) {
-                const ua_u32x4 u = *reinterpret_cast<const ua_u32x4 *>(B + g0);
-                b[0] = u.v[0]; b[1] = u.v[1]; b[2] = u.v[2]; b[3] = u.v[3];
-            }
-            const ua_u32x2 t1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0), u1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0 + W);
-            const ua_u32x2 t2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0), u2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0 + W);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int sh = 16 * (j & 1);
-                z1[j] = ((t1.v[j >> 1] >> sh) & 0xffffu) | ((u1.v[j >> 1] >> sh) << 16);
-                z2[j] = ((t2.v[j >> 1] >> sh) & 0xffffu) | ((u2.v[j >> 1] >> sh) << 16);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                z1[j] = z2[j] = 0;
-                if (j >= n) continue;
-                f[j] = F[g0 + j];
-                if (B) b[j] = B[g0 + j];
-                z1[j] = ip_cell(img1, W, 2 * (x0 + j), oy);
-                z2[j] = ip_cell(img2, W, 2 * (x0 + j), oy);
-            }
-        }
+        const IpRun run = ip_load_run(img1, img2, F, B, W, CW, cy, x0, n);
         const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
         uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ks = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n) break;
             const int ox = 2 * (x0 + j);
-            uint32_t c1 = 0, c2 = 0, k = 2u, cost = ~0u;      // nothing selected yet
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if (h == 1 && !B) break;
-                const int vx = h ? -mv_x(b[j]) : mv_x(f[j]), vy = h ? -mv_y(b[j]) : mv_y(f[j]);
-                const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
-                const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
-                const int p1x = ox - sx, p1y = oy - sy, p2x = p1x + vx, p2y = p1y + vy;
-                if (p1x < 0 || p2x < 0 || p1x > W - 2 || p2x > W - 2 || p1y < 0 || p2y < 0 || p1y > H - 2 || p2y > H - 2) continue;
-                const uint32_t q1 = ip_cell(img1, W, p1x, p1y), q2 = ip_cell(img2, W, p2x, p2y);
-                const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
-                if (c < cost) { c1 = q1; c2 = q2; k = (uint32_t)h; cost = c; }      // strictly cheaper: the earliest of equals stays
-            }
-            const uint32_t cz = __builtin_amdgcn_sad_u8(z1[j], z2[j], 0u);
-            if (cz < cost) { c1 = z1[j]; c2 = z2[j]; k = 2u; cost = cz; }
+            const IpPick s = ip_select(img1, img2, W, H, ox, oy, run.f[j], run.b[j], B != nullptr, run.z1[j], run.z2[j], num, half,
+                                       bias, magic);
+            const uint32_t c1 = s.c1, c2 = s.c2, k = s.k, cost = s.cost;
             uint32_t px = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -3211,6 +3313,100 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
     if (threadIdx.x < 4)
         a.partial[4 * (((size_t)blockIdx.z * gridDim.y + pair) * gridDim.x + blockIdx.x) + threadIdx.x] =
             (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+// =======================================================================================
+// The BGR interpolation rule of include/bbme.h: k_interpolate's selection on the LUMA planes (ip_load_run, ip_select: the same
+// loads, multiply-shifts and v_sad_u8), then the blend of the two B,G,R frames at the selected p1 and p2, written as the
+// unpadded frame.  Same split as k_interpolate -- a lane takes a run of 4 cells, blockIdx.z = phase, so every phase but the
+// first finds planes, grids and colour in L2 -- and the same kind of kernel, a memory-bound gather with three times the pixel
+// bytes: per cell and frame two rows of two pixels, 6 contiguous bytes each, as one unaligned dword and one u16 load where both
+// pixels lie inside the frame, by bytes (0 outside) where they straddle its edge.  A run's output row is 8 pixels = 24 bytes,
+// collected in three 64-bit words: six dword stores when the run is whole, wholly inside the frame and its row address
+// dword-aligned; bytes otherwise (an odd pad_x, a caller's odd pitch, a cut run, the frame's edges -- with an odd padding
+// cells straddle the frame and only their pixels inside are written).  Runs wholly outside the frame load nothing.
+// =======================================================================================
+struct IpBgrArgs {
+    const uint8_t *img1, *img2;           // level-0 padded luma planes of the pair, pitch = width
+    const mv_t *fwd, *bwd;                // cw entries per row; bwd may be null
+    const uint8_t *bgr1, *bgr2;           // the fw x fh colour frames, rows bgr_pitch bytes apart
+    uint8_t *out;                         // fw x fh B,G,R frames, rows out_pitch, phases out_stride bytes apart
+    size_t out_stride;
+    int width, height, cw, fw, fh, pad_x, pad_y, num0, den, bgr_pitch, out_pitch;
+    uint32_t magic;                       // floor(2^32 / den) + 1
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * (height / 2)
+};
+
+// pixels (x, y) and (x + 1, y) of a colour frame as six bytes B,G,R,B,G,R from bit 0 up; a pixel outside the frame is 0
+__device__ __forceinline__ uint64_t bgr_two(const uint8_t *img, int pitch, int fw, int fh, int x, int y)
+{
+    if (y < 0 || y >= fh || x < -1 || x >= fw) return 0;
+    const uint8_t *row = img + (size_t)y * pitch;
+    if (x >= 0 && x + 1 < fw)
+        return (uint64_t)reinterpret_cast<const ua_u32 *>(row + 3 * x)->v | (uint64_t)reinterpret_cast<const ua_u16 *>(row + 3 * x + 4)->v << 32;
+    const int px = x < 0 ? 0 : x;                             // the one pixel inside: the second of the two (x = -1) or the first
+    const uint64_t v = (uint64_t)row[3 * px] | (uint64_t)row[3 * px + 1] << 8 | (uint64_t)row[3 * px + 2] << 16;
+    return x < 0 ? v << 24 : v;
+}
+
+__global__ __launch_bounds__(256) void k_interpolate_bgr(IpBgrArgs a)
+{
+    const mv_t *F = a.fwd, *B = a.bwd;
+    const int W = a.width, H = a.height, CW = a.cw, den = a.den, num = a.num0 + (int)blockIdx.z, half = den >> 1;
+    const uint32_t magic = a.magic, w1 = (uint32_t)(den - num), w2 = (uint32_t)num;
+    const int bias = 32768 * den;
+#pragma unroll
+    for (int r = 0; r < kIpRunsPerLane; ++r) {
+        const long long i = ((long long)blockIdx.x * kIpRunsPerLane + r) * 256 + threadIdx.x;
+        if (i >= a.runs) break;
+        const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
+        const int n = min(4, CW - x0);                        // cells of the run inside the row
+        const int oy = 2 * cy;
+        const int fy = oy - a.pad_y, fx = 2 * x0 - a.pad_x;    // the run's first pixel in frame coordinates
+        if (fy + 1 < 0 || fy >= a.fh || fx + 2 * n <= 0 || fx >= a.fw) continue;      // no pixel of the run is in the frame
+        const IpRun run = ip_load_run(a.img1, a.img2, F, B, W, CW, cy, x0, n);
+        uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows, 24 bytes each
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const IpPick s = ip_select(a.img1, a.img2, W, H, 2 * (x0 + j), oy, run.f[j], run.b[j], B != nullptr, run.z1[j], run.z2[j],
+                                       num, half, bias, magic);
+            const int q1x = s.p1x - a.pad_x, q1y = s.p1y - a.pad_y, q2x = q1x + s.vx, q2y = q1y + s.vy;
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                const uint64_t c1 = bgr_two(a.bgr1, a.bgr_pitch, a.fw, a.fh, q1x, q1y + y);
+                const uint64_t c2 = bgr_two(a.bgr2, a.bgr_pitch, a.fw, a.fh, q2x, q2y + y);
+                uint64_t px = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    const uint32_t v = __umulhi(w1 * ((uint32_t)(c1 >> (8 * q)) & 0xffu) + w2 * ((uint32_t)(c2 >> (8 * q)) & 0xffu) +
+                                                (uint32_t)half, magic);
+                    px |= (uint64_t)v << (8 * q);
+                }
+                const int bit = 48 * j;                       // the cell's six bytes go to bytes 6 j .. 6 j + 5 of the row
+                rows[y][bit >> 6] |= px << (bit & 63);
+                if ((bit & 63) > 16) rows[y][(bit >> 6) + 1] |= px >> (64 - (bit & 63));
+            }
+        }
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+            if (fy + y < 0 || fy + y >= a.fh) continue;
+            uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(fy + y) * a.out_pitch + (ptrdiff_t)3 * fx;
+            if (n == 4 && fx >= 0 && fx + 8 <= a.fw && ((uintptr_t)q & 3u) == 0) {
+                uint32_t *o = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+                for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[y][d >> 1] >> (32 * (d & 1)));
+            } else {
+#pragma unroll
+                for (int p = 0; p < 8; ++p) {
+                    if (p >= 2 * n || fx + p < 0 || fx + p >= a.fw) continue;
+#pragma unroll
+                    for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[y][k >> 3] >> (8 * (k & 7)));
+                }
+            }
+        }
+    }
 }
 
 }  // namespace bbme

@@ -1,6 +1,6 @@
 // bbme_main.cpp -- the reference's driver (main_class.cpp:6-85) as a real command line.
 //
-//   bbme_cli frame10.pgm frame11.pgm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
+//   bbme_cli frame10.pgm|.ppm frame11.pgm|.ppm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
 //            [--interpolate PREFIX --factor N] [--backward-color back.ppm]
 //
@@ -18,16 +18,23 @@
 // as PREFIX_k.pgm, each the unpadded frame MF sees.  --backward-color writes the colour coding (:73-75) of the backward field of a
 // bidirectional estimate at the driver's subsampling; the image is made on the GPU from the cells (the colour rule of
 // include/bbme.h) and only its bytes come back.  --color stays the host's Flow::MotionToColor of the downloaded field.
+// Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
+// computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
+// GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
+// colour frames by the BGR interpolation rule; that needs --no-upsample (there is no up-sampled colour).
 // Defaults are the reference's literals (:19-21): 4 levels, block 32, search 64.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
+#include <utility>
 
 #include "rw_flow.hpp"
 
-static bool read_pgm(const char *path, bbme::Image8 &img)
+// a binary PGM (P5) into `img`, or a binary PPM (P6; R,G,B per pixel in the file) into `bgr`; *colour tells which
+static bool read_pnm(const char *path, bbme::Image8 &img, bbme::ImageBGR &bgr, bool *colour)
 {
     FILE *f = fopen(path, "rb");
     if (!f) return false;
@@ -40,12 +47,17 @@ static bool read_pgm(const char *path, bbme::Image8 &img)
             else if (c != ' ' && c != '\n' && c != '\r' && c != '\t') { ungetc(c, f); break; }
         }
     };
-    bool ok = fread(magic, 1, 2, f) == 2 && magic[0] == 'P' && magic[1] == '5';
+    bool ok = fread(magic, 1, 2, f) == 2 && magic[0] == 'P' && (magic[1] == '5' || magic[1] == '6');
+    *colour = ok && magic[1] == '6';
     if (ok) { skip(); ok = fscanf(f, "%d", &w) == 1; }
     if (ok) { skip(); ok = fscanf(f, "%d", &h) == 1; }
     if (ok) { skip(); ok = fscanf(f, "%d", &maxv) == 1 && maxv == 255; }
     if (ok) ok = fgetc(f) != EOF && w > 0 && h > 0;
-    if (ok) {
+    if (ok && *colour) {
+        bgr = bbme::ImageBGR(h, w);
+        ok = fread(bgr.data.data(), 1, bgr.data.size(), f) == bgr.data.size();
+        for (size_t i = 0; ok && i < bgr.data.size(); i += 3) std::swap(bgr.data[i], bgr.data[i + 2]);
+    } else if (ok) {
         img = bbme::Image8(h, w);
         ok = fread(img.data.data(), 1, img.data.size(), f) == img.data.size();
     }
@@ -82,22 +94,35 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
     }
     if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || (interpolate && (factor < 2 || factor > 256))) {
-        fprintf(stderr, "usage: bbme_cli frame1.pgm frame2.pgm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
+        fprintf(stderr, "usage: bbme_cli frame1.pgm|.ppm frame2.pgm|.ppm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm]\n");
         return 2;
     }
     try {
         bbme::Image8 image1, image2;
-        if (!read_pgm(f1, image1) || !read_pgm(f2, image2)) {
+        bbme::ImageBGR bgr1, bgr2;
+        bool colour = false, colour2 = false;
+        if (!read_pnm(f1, image1, bgr1, &colour) || !read_pnm(f2, image2, bgr2, &colour2)) {
             fprintf(stderr, "Could not open one of the images\n");                    // main_class.cpp:40
             return 1;
         }
+        if (colour != colour2) {
+            fprintf(stderr, "One frame is grey (P5) and the other colour (P6): give two frames of one kind\n");
+            return 1;
+        }
+        if (colour && upsample && interpolate) {
+            fprintf(stderr, "--interpolate on colour frames needs --no-upsample\n");
+            return 2;
+        }
+        if (colour && upsample) { image1 = bbme::bgr_to_gray(bgr1); image2 = bbme::bgr_to_gray(bgr2); }
         const int scale = upsample ? 4 : 1;
         std::vector<int> search_size(levels, search), block_size(levels, block);
         // the x4 up-sampling (:32-33) runs on the GPU from the original frames; the padding strip and the every-4th-pixel / 4
         // subsampling (:58-70) too, so only the original-sized field comes back
-        MF motion_pair(image1, image2, search_size.data(), block_size.data(), levels, device, scale);
+        std::unique_ptr<MF> mf(colour && !upsample ? new MF(bgr1, bgr2, search_size.data(), block_size.data(), levels, device)
+                                                   : new MF(image1, image2, search_size.data(), block_size.data(), levels, device, scale));
+        MF &motion_pair = *mf;
         const auto t1 = std::chrono::steady_clock::now();
         bbme::ImageFlow subpix = motion_pair.calcMotionBlockMatchingSubsampled(scale);
         const auto t2 = std::chrono::steady_clock::now();
@@ -141,6 +166,12 @@ int main(int argc, char **argv)
             motion_pair.estimateBidirectional();
             const int px = motion_pair.padding_x, py = motion_pair.padding_y;
             for (int k = 1; k < factor; ++k) {
+                if (colour) {
+                    const bbme::ImageBGR img = motion_pair.interpolateBGR(k, factor);
+                    const std::string name = std::string(interpolate) + "_" + std::to_string(k) + ".ppm";
+                    bbme::check(bbme_ppm_write_bgr(name.c_str(), img.cols, img.rows, img.data.data()));
+                    continue;
+                }
                 const bbme::Image8 img = motion_pair.interpolate(k, factor);
                 const std::string name = std::string(interpolate) + "_" + std::to_string(k) + ".pgm";
                 bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,

@@ -100,6 +100,14 @@ inline Image8 resize_x4(const Image8 &src)
     return dst;
 }
 
+// the luma of a B,G,R image (the luma rule of include/bbme.h)
+inline Image8 bgr_to_gray(const ImageBGR &src)
+{
+    Image8 dst(src.rows, src.cols);
+    check(bbme_bgr_to_gray_host(src.data.data(), src.cols, src.rows, 3 * src.cols, dst.data.data()));
+    return dst;
+}
+
 }  // namespace bbme
 
 class MF {
@@ -112,19 +120,22 @@ public:
         : upsample(upsample)
     {
         if (upsample != 1 && upsample != 4) throw bbme::Error(BBME_ERR_INVALID, "upsample must be 1 or 4");
-        if (num_levels <= 0) throw bbme::Error(BBME_ERR_INVALID, "num_levels must be > 0");                       // assert :7
         if (image1.rows != image2.rows || image1.cols != image2.cols)
             throw bbme::Error(BBME_ERR_INVALID, "image1.size() != image2.size()");                                 // assert :8
-        bbme_params p{};
-        p.num_levels = num_levels;
-        for (int i = 0; i < num_levels && i < BBME_MAX_LEVELS; ++i) {
-            p.block_size[i] = block_size[i];
-            p.search_size[i] = search_size[i];
-        }
-        bbme::check(bbme_create(&p, image1.cols * upsample, image1.rows * upsample, device, &ctx_));
-        bbme::check(bbme_get_geometry(ctx_, &padded_width, &padded_height, &padding_x, &padding_y));
+        create(image1.cols * upsample, image1.rows * upsample, search_size, block_size, num_levels, device);
         int rc = upsample == 4 ? bbme_set_frames_host_x4(ctx_, 0, image1.data.data(), image2.data.data(), image1.cols)
                                : bbme_set_frames_host(ctx_, image1.data.data(), image2.data.data(), image1.cols);
+        if (rc != BBME_OK) { bbme_destroy(ctx_); ctx_ = nullptr; bbme::check(rc); }
+    }
+    // Colour frames, B,G,R (include/bbme.h: the luma rule makes the planes on the GPU, the context keeps the colour for
+    // interpolateBGR); every estimate and result is the luma's.  There is no up-sampled form.
+    MF(const bbme::ImageBGR &image1, const bbme::ImageBGR &image2, const int search_size[], const int block_size[],
+       const int num_levels, int device = 0)
+    {
+        if (image1.rows != image2.rows || image1.cols != image2.cols)
+            throw bbme::Error(BBME_ERR_INVALID, "image1.size() != image2.size()");
+        create(image1.cols, image1.rows, search_size, block_size, num_levels, device);
+        const int rc = bbme_set_frames_host_bgr(ctx_, 0, image1.data.data(), image2.data.data(), 3 * image1.cols);
         if (rc != BBME_OK) { bbme_destroy(ctx_); ctx_ = nullptr; bbme::check(rc); }
     }
 #ifdef BBME_WITH_OPENCV
@@ -252,6 +263,13 @@ public:
         bbme::check(bbme_get_interpolated_host(ctx_, 0, num, den, img.data.data()));
         return img;
     }
+    // The same frame in colour (the BGR interpolation rule of include/bbme.h), for an MF made of colour frames: the UNPADDED frame.
+    bbme::ImageBGR interpolateBGR(int num = 1, int den = 2)
+    {
+        bbme::ImageBGR img(padded_height - 2 * padding_y, padded_width - 2 * padding_x);
+        bbme::check(bbme_get_interpolated_bgr_host(ctx_, 0, num, den, img.data.data()));
+        return img;
+    }
     // Its statistics over window {cx0, cy0, cw, ch} in cells; nullptr = unpaddedCells.
     bbme::InterpolationStats interpolationStats(int num = 1, int den = 2, const int *window = nullptr)
     {
@@ -286,6 +304,19 @@ public:
     int padding_y = 0;
 
 private:
+    // MF::MF up to the frames: the context for width x height frames and the public geometry
+    void create(int width, int height, const int search_size[], const int block_size[], int num_levels, int device)
+    {
+        if (num_levels <= 0) throw bbme::Error(BBME_ERR_INVALID, "num_levels must be > 0");                       // assert :7
+        bbme_params p{};
+        p.num_levels = num_levels;
+        for (int i = 0; i < num_levels && i < BBME_MAX_LEVELS; ++i) {
+            p.block_size[i] = block_size[i];
+            p.search_size[i] = search_size[i];
+        }
+        bbme::check(bbme_create(&p, width, height, device, &ctx_));
+        bbme::check(bbme_get_geometry(ctx_, &padded_width, &padded_height, &padding_x, &padding_y));
+    }
 #ifdef BBME_WITH_OPENCV
     static bbme::Image8 from_mat(const cv::Mat &m)
     {

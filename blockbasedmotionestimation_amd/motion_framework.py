@@ -54,15 +54,15 @@ class MF:
         self._torch_frames = None
         if frames_on_device:
             import torch
-            if tuple(image1.shape) != tuple(image2.shape):
+            if tuple(image1.shape) != tuple(image2.shape) or not _is_frame_shape(tuple(image1.shape)):
                 raise _capi.BbmeError(_capi.ERR_INVALID, "image1.size() != image2.size()")
-            h, w = image1.shape
+            h, w = image1.shape[:2]
         else:
             image1 = np.ascontiguousarray(image1, dtype=np.uint8)
             image2 = np.ascontiguousarray(image2, dtype=np.uint8)
-            if image1.ndim != 2 or image1.shape != image2.shape:                        # assert :8
+            if not _is_frame_shape(image1.shape) or image1.shape != image2.shape:       # assert :8
                 raise _capi.BbmeError(_capi.ERR_INVALID, "image1.size() != image2.size()")
-            h, w = image1.shape
+            h, w = image1.shape[:2]
         self.source_height, self.source_width = h, w
         self.orig_height, self.orig_width = h * upsample, w * upsample
         self.params = _capi.make_params(search_size, block_size)
@@ -99,13 +99,22 @@ class MF:
     def _host_frames(self, image1, image2):
         image1 = np.ascontiguousarray(image1, dtype=np.uint8)
         image2 = np.ascontiguousarray(image2, dtype=np.uint8)
-        if image1.shape != (self.source_height, self.source_width) or image2.shape != image1.shape:
+        if image1.shape not in self._frame_shapes() or image2.shape != image1.shape:
             raise _capi.BbmeError(_capi.ERR_INVALID, "frames must keep the size the context was created for")
         return image1, image2
 
+    def _frame_shapes(self):
+        """The shapes a frame of this context may have: grey (H, W), or colour (H, W, 3) in B,G,R order (the luma rule of
+        include/bbme.h; not on an upsample=4 context)."""
+        grey = (self.source_height, self.source_width)
+        return (grey,) if self.upsample == 4 else (grey, grey + (3,))
+
     def _set_host_pair(self, pair, image1, image2):
         image1, image2 = self._host_frames(image1, image2)
-        if self.upsample == 4:
+        if image1.ndim == 3:
+            _capi.check(self._lib.bbme_set_frames_host_bgr(self._ctx, pair, image1.ctypes.data, image2.ctypes.data,
+                                                           3 * self.source_width))
+        elif self.upsample == 4:
             _capi.check(self._lib.bbme_set_frames_host_x4(self._ctx, pair, image1.ctypes.data, image2.ctypes.data,
                                                           self.source_width))
         else:
@@ -118,6 +127,8 @@ class MF:
         import torch
         _capi.check(self._lib.bbme_wait_for_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(image1.device).cuda_stream)))
         setter = self._lib.bbme_set_frames_device_x4 if self.upsample == 4 else self._lib.bbme_set_frames_device_pair
+        if image1.dim() == 3:
+            setter = self._lib.bbme_set_frames_device_bgr
         _capi.check(setter(self._ctx, pair, image1.data_ptr(), image2.data_ptr(), image1.stride(0)))
 
     def set_frames(self, image1, image2):
@@ -130,11 +141,12 @@ class MF:
         refused here (the C-ABI sees only a pointer and a pitch)."""
         import torch
         for t in (image1, image2):
-            if not (t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and tuple(t.shape) == (self.source_height, self.source_width)):
-                raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must be 2-D uint8 CUDA tensors of %d x %d (the size the "
-                                      "context was created for)" % (self.source_height, self.source_width))
-        if image1.stride(1) != 1 or image2.stride(1) != 1 or image1.stride(0) != image2.stride(0):
-            raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must have unit column stride and a common row pitch")
+            if not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) in self._frame_shapes() and t.shape == image1.shape):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must be uint8 CUDA tensors of %d x %d, or %d x %d x 3 in "
+                                      "B,G,R order (the size the context was created for)"
+                                      % (self.source_height, self.source_width, self.source_height, self.source_width))
+        if not (_packed_pixels(image1) and _packed_pixels(image2)) or image1.stride(0) != image2.stride(0):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must have packed pixels and a common row pitch")
 
     def _behind_torch(self, *tensors):
         """torch tensors handed to a *_device call may still be being written (a fill, an upload) or read by work on torch's
@@ -512,6 +524,71 @@ class MF:
         self.synchronize()
         return frames.cpu().numpy()
 
+    # -- colour frames out (the BGR interpolation rule of include/bbme.h): needs frames set as (H, W, 3) ------------------------
+    def interpolate_bgr(self, num=1, den=2, pair=0, out=None):
+        """interpolate() in colour: the selection of the grey frame, made on the luma planes, applied to the B,G,R frames the
+        context was fed -> the UNPADDED (H, W, 3) uint8 frame.  BbmeError (ERR_STATE) when a frame of the pair was set grey."""
+        shape = (self.orig_height, self.orig_width, 3)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_bgr: out must be a C-contiguous uint8 array of shape %s" % (shape,))
+        _capi.check(self._lib.bbme_get_interpolated_bgr_host(self._ctx, pair, int(num), int(den), out.ctypes.data))
+        return out
+
+    def interpolate_run_bgr(self, factor, pair=0):
+        """All factor - 1 phases 1 / factor .. (factor - 1) / factor from one launch -> (factor - 1, H, W, 3) uint8."""
+        import torch
+        den = int(factor)
+        if not 2 <= den <= 256:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_run_bgr: factor %d outside 2..256" % den)
+        h, w = self.orig_height, self.orig_width
+        frames = torch.empty((den - 1, h, w, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
+        _capi.check(self._lib.bbme_interpolate_bgr_device(self._ctx, pair, 1, den - 1, den, C.c_void_p(frames.data_ptr()), 3 * w,
+                                                          3 * h * w, None))
+        self.synchronize()
+        return frames.cpu().numpy()
+
+    def cells_interpolate_bgr_device(self, fwd, bwd=None, bgr1=None, bgr2=None, num0=1, count=1, den=2, pair=0, out=None,
+                                     hip_stream_handle=None):
+        """The BGR interpolation rule on the context's luma planes of `pair` and any two cell grids in HBM (as
+        cells_interpolate_device): bgr1, bgr2 uint8 CUDA tensors (H, W, 3) with packed pixels and a common row pitch, or both
+        None for the colour the context stored; phases num0 .. num0 + count - 1 of den in one launch into out, a uint8 CUDA
+        tensor (count, H, W, 3) with packed pixels whose rows and frames may be further apart than packed (any alignment).  On
+        the given HIP stream (default: the context's), ordered behind the context's stream; no host wait.  Needs no estimate."""
+        import torch
+        ch, cw = self.cells_shape
+        h, w = self.orig_height, self.orig_width
+        count = int(count)
+        for t in (fwd, bwd):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_bgr_device: grids must be contiguous int16 CUDA tensors "
+                                      "of shape (%d, %d, 2)" % (ch, cw))
+        for t in (bgr1, bgr2):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and _packed_pixels(t)
+                                      and (bgr1 is None or t.stride(0) == bgr1.stride(0))):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_bgr_device: colour frames must be uint8 CUDA tensors of "
+                                      "shape (%d, %d, 3) with packed pixels and a common row pitch" % (h, w))
+        if out is None or not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (count, h, w, 3)
+                               and out.stride(3) == 1 and out.stride(2) == 3):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_bgr_device: out must be a uint8 CUDA tensor of shape "
+                                  "(%d, %d, %d, 3) with packed pixels" % (count, h, w))
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+        self._behind_torch(fwd, bwd, bgr1, bgr2, out)
+        _capi.check(self._lib.bbme_cells_interpolate_bgr_device(
+            self._ctx, pair, ptr(fwd), ptr(bwd), ptr(bgr1), ptr(bgr2), bgr1.stride(0) if bgr1 is not None else 0, int(num0), count,
+            int(den), ptr(out), out.stride(1), max(out.stride(0), 0), C.c_void_p(hip_stream_handle or 0)))
+        return out
+
+    def bgr_frames_device_ptrs(self, pair=0):
+        """Device pointers of the two stored colour frames of `pair` (packed, pitch 3 W), bbme_bgr_frames_device_pair."""
+        a, b = C.c_void_p(), C.c_void_p()
+        _capi.check(self._lib.bbme_bgr_frames_device_pair(self._ctx, pair, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def _interpolation_stats(self, num, den, window):
         if window is None:
             window = self.default_cell_window()
@@ -672,7 +749,7 @@ class MFBatch(MF):
         self.device = device
         self.batch = len(pairs)
         self._torch_frames = [None] * self.batch
-        h, w = pairs[0][0].shape
+        h, w = pairs[0][0].shape[:2]
         self.source_height, self.source_width = h, w
         self.orig_height, self.orig_width = h * upsample, w * upsample
         self.params = _capi.make_params(list(search_size)[:num_levels], list(block_size)[:num_levels])
@@ -794,7 +871,7 @@ class MFChain(MFBatch):
         self.batch = len(frames) - 1
         self.frames_on_device = bool(frames_on_device)
         self._torch_frames = [None] * len(frames)
-        h, w = frames[0].shape
+        h, w = frames[0].shape[:2]
         self.source_height, self.source_width = h, w
         self.orig_height, self.orig_width = h * upsample, w * upsample
         self.params = _capi.make_params(list(search_size)[:num_levels], list(block_size)[:num_levels])
@@ -828,16 +905,23 @@ class MFChain(MFBatch):
             for i, t in enumerate(frames):
                 table[i] = t.data_ptr()
             _capi.check(self._lib.bbme_wait_for_stream(self._ctx, C.c_void_p(torch.cuda.current_stream(frames[0].device).cuda_stream)))
-            _capi.check(self._lib.bbme_set_chain_frames_device(self._ctx, first, n, table, frames[0].stride(0), self.upsample))
+            if frames[0].dim() == 3:
+                _capi.check(self._lib.bbme_set_chain_frames_device_bgr(self._ctx, first, n, table, frames[0].stride(0)))
+            else:
+                _capi.check(self._lib.bbme_set_chain_frames_device(self._ctx, first, n, table, frames[0].stride(0), self.upsample))
             self._torch_frames[first:first + n] = frames
             return
         frames = [np.ascontiguousarray(f, dtype=np.uint8) for f in frames]
         for i, f in enumerate(frames):
-            if f.shape != (self.source_height, self.source_width):
-                raise _capi.BbmeError(_capi.ERR_INVALID, "frames must keep the size the context was created for")
+            if f.shape not in self._frame_shapes() or f.shape != frames[0].shape:
+                raise _capi.BbmeError(_capi.ERR_INVALID, "frames must keep the size the context was created for, all grey or all colour")
             table[i] = f.ctypes.data
-        setter = self._lib.bbme_set_chain_frames_host if wait else self._lib.bbme_set_chain_frames_host_async
-        _capi.check(setter(self._ctx, first, n, table, self.source_width, self.upsample))
+        if frames[0].ndim == 3:
+            setter = self._lib.bbme_set_chain_frames_host_bgr if wait else self._lib.bbme_set_chain_frames_host_bgr_async
+            _capi.check(setter(self._ctx, first, n, table, 3 * self.source_width))
+        else:
+            setter = self._lib.bbme_set_chain_frames_host if wait else self._lib.bbme_set_chain_frames_host_async
+            _capi.check(setter(self._ctx, first, n, table, self.source_width, self.upsample))
         if not wait:
             self._host_frames_in_flight = frames          # keeps converted copies alive until the next run replaces them
 
@@ -851,10 +935,11 @@ class MFChain(MFBatch):
     def _check_device_run(self, frames):
         import torch
         for t in frames:
-            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and t.dim() == 2 and tuple(t.shape) == (self.source_height, self.source_width)
-                    and t.stride(1) == 1 and t.stride(0) == frames[0].stride(0)):
-                raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must be 2-D uint8 CUDA tensors of %d x %d with unit column "
-                                      "stride and a common row pitch" % (self.source_height, self.source_width))
+            if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) in self._frame_shapes()
+                    and t.shape == frames[0].shape and _packed_pixels(t) and t.stride(0) == frames[0].stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "device frames must be uint8 CUDA tensors of %d x %d (or, all of them, "
+                                      "%d x %d x 3 in B,G,R order) with packed pixels and a common row pitch"
+                                      % (self.source_height, self.source_width, self.source_height, self.source_width))
 
     def advance(self, new_frames, wait=True):
         """The next round of the video: the last slot becomes slot 0 on the GPU (bbme_chain_advance: one copy launch, nothing
@@ -864,6 +949,16 @@ class MFChain(MFBatch):
         new_frames = list(new_frames)
         if new_frames:
             self.set_frame_run(1, new_frames, wait=wait)
+
+
+def _is_frame_shape(shape):
+    """(H, W) grey or (H, W, 3) B,G,R."""
+    return len(shape) == 2 or (len(shape) == 3 and shape[2] == 3)
+
+
+def _packed_pixels(t):
+    """A frame tensor whose pixels lie side by side in a row: unit column stride (grey), or 3 bytes per pixel (B,G,R)."""
+    return t.stride(1) == 1 if t.dim() == 2 else (t.stride(2) == 1 and t.stride(1) == 3)
 
 
 def _which(which):
@@ -927,6 +1022,44 @@ def interpolate_cells(image1, image2, fwd, bwd=None, num=1, den=2, window=None):
                                                   None if bwd is None else bwd.ctypes.data, int(num), int(den), win,
                                                   out.ctypes.data, sel.ctypes.data, s))
     return out, sel, dict(zip(INTERPOLATION_STAT_KEYS, list(s)))
+
+
+def bgr_to_gray(frame):
+    """The luma rule of include/bbme.h on the CPU (bbme_bgr_to_gray_host): frame uint8 (H, W, 3) in B,G,R order, its rows any
+    distance >= 3 W apart (a column slice of a wider array is read in place) -> (H, W) uint8,
+    Y = (1868 B + 9617 G + 4899 R + 8192) >> 14."""
+    frame = np.asarray(frame)
+    if frame.dtype != np.uint8 or frame.ndim != 3 or frame.shape[2] != 3:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "bgr_to_gray: a uint8 frame of shape (H, W, 3)")
+    h, w = frame.shape[:2]
+    if frame.strides[1:] != (3, 1) or frame.strides[0] < 3 * w:
+        frame = np.ascontiguousarray(frame)
+    out = np.empty((h, w), np.uint8)
+    _capi.check(_capi.lib().bbme_bgr_to_gray_host(frame.ctypes.data, w, h, frame.strides[0], out.ctypes.data))
+    return out
+
+
+def interpolate_cells_bgr(luma1, luma2, bgr1, bgr2, fwd, bwd=None, num=1, den=2, pad_x=0, pad_y=0):
+    """The BGR interpolation rule of include/bbme.h on the CPU (bbme_interpolate_bgr_host): luma1, luma2 the padded uint8
+    (H0, W0) luma planes, bgr1, bgr2 the uint8 (H, W, 3) colour frames whose lumas they hold at (pad_x, pad_y) (H0 = H + 2 pad_y,
+    W0 = W + 2 pad_x), fwd and bwd (may be None) int16 (H0 / 2, W0 / 2, 2) cell grids -> the unpadded (H, W, 3) uint8 frame."""
+    luma1 = np.ascontiguousarray(luma1, np.uint8)
+    luma2 = np.ascontiguousarray(luma2, np.uint8)
+    bgr1 = np.ascontiguousarray(bgr1, np.uint8)
+    bgr2 = np.ascontiguousarray(bgr2, np.uint8)
+    fwd = np.ascontiguousarray(fwd, np.int16)
+    bwd = None if bwd is None else np.ascontiguousarray(bwd, np.int16)
+    if luma1.ndim != 2 or luma1.shape != luma2.shape or bgr1.ndim != 3 or bgr1.shape[2] != 3 or bgr1.shape != bgr2.shape:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells_bgr: two uint8 planes (H0, W0) and two uint8 frames (H, W, 3)")
+    h0, w0 = luma1.shape
+    h, w = bgr1.shape[:2]
+    if fwd.shape != (h0 // 2, w0 // 2, 2) or (bwd is not None and bwd.shape != fwd.shape):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells_bgr: int16 grids of shape (H0 / 2, W0 / 2, 2)")
+    out = np.empty((h, w, 3), np.uint8)
+    _capi.check(_capi.lib().bbme_interpolate_bgr_host(luma1.ctypes.data, luma2.ctypes.data, w0, h0, bgr1.ctypes.data, bgr2.ctypes.data,
+                                                      w, h, int(pad_x), int(pad_y), fwd.ctypes.data,
+                                                      None if bwd is None else bwd.ctypes.data, int(num), int(den), out.ctypes.data))
+    return out
 
 
 def plan_padding(width, height, search_size, block_size):

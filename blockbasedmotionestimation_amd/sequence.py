@@ -372,9 +372,13 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
     factor, the interpolation rule of include/bbme.h) between each consecutive two -> factor * (len(frames) - 1) + 1 uint8
     (H, W) frames, the interpolated ones the unpadded windows of the padded result.  Runs on the chain plan of
     estimate_frames_bidirectional (same contexts, rounds and padding of a short round): every frame is set once, both fields
-    of a pair come from the same planes, and the factor - 1 frames of a pair from one launch (MF.interpolate_run)."""
+    of a pair come from the same planes, and the factor - 1 frames of a pair from one launch (MF.interpolate_run).
+    Colour video: (H, W, 3) frames in B,G,R order give (H, W, 3) frames on the same plan -- the luma planes are made on the
+    GPU from the colour frames (the luma rule), the fields are the luma's, and the frames in between come from the stored
+    colour by the BGR interpolation rule (MF.interpolate_run_bgr); still every frame is set once."""
     from .motion_framework import MFChain
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    bgr = bool(frames) and frames[0].ndim == 3
     factor = int(factor)
     if not 2 <= factor <= 256:
         raise ValueError("interpolate_frames: factor %d outside 2..256" % factor)
@@ -397,6 +401,9 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
         mf = chains[slot]
         h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
         for p in range(count):
+            if bgr:
+                between[first + p] = list(mf.interpolate_run_bgr(factor, pair=p))
+                continue
             run = mf.interpolate_run(factor, pair=p)       # waits for this context's stream only
             between[first + p] = [np.ascontiguousarray(f[py:py + h, px:px + w]) for f in run]
 

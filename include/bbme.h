@@ -512,6 +512,77 @@ int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int widt
                           const int16_t *bwd, int num, int den, const int *window, uint8_t *out, uint8_t *sel,
                           unsigned long long *stats4);
 
+/* ---- colour video: B,G,R frames in, motion-compensated B,G,R frames out ("bgr" in names; "color" means the flow colour coding) -- */
+
+/* LUMA RULE (this project's own; the reference's driver reads its colour PNGs as grey, imread(path, 0), main_class.cpp:24-26, and
+ * no bit-identity with any library's conversion is claimed).  A colour frame is H rows of W pixels of 3 bytes in B,G,R order (the
+ * order of bbme_ppm_write_bgr's input), consecutive rows `pitch` >= 3 W bytes apart.  Its luma is
+ *     Y = (1868 B + 9617 G + 4899 R + 8192) >> 14,   in 32-bit integers:
+ * the BT.601 weights in 14 bits.  They sum to 16384, so B = G = R = g gives Y = g exactly, and Y <= 255 always.
+ * bbme_bgr_to_gray_host: the rule on the CPU, no GPU; `gray` is packed width x height.
+ * The *_bgr frame setters below are, plane by plane and bit for bit, the grey setter of the same name on that luma -- the level-0
+ * planes are pad_zero(Y), deeper levels its pyrDown cascade -- from ONE kernel that converts and writes the zero border, and they
+ * keep the colour: a context holds one packed (pitch 3 W) B,G,R copy per frame, 2 per pair, or one per slot on a chain context, in
+ * a COLOUR STORE allocated by the first colour setter.  Host setters upload straight into the store (the frame crosses PCIe once)
+ * and convert from there; device setters read the caller's frames on the ctx stream and copy them into the store in the same pass.
+ * A frame HAS COLOUR from a *_bgr setter until a grey setter of that frame (bbme_set_frames_*, the _x4 forms,
+ * bbme_set_chain_frames_* on its slot, bbme_set_level_planes_host): the stored colour then is not what the luma plane was made
+ * from, and the calls that read stored colour return BBME_ERR_STATE.  bbme_chain_advance moves the last slot's colour with its
+ * planes.  (Planes refilled in place through bbme_level_planes_device are the caller's business, as for the SAD memo.)
+ * Scale 1 only: there is no colour form of the x4 setters.  Bookkeeping (frames set, SAD memo, validity of the pair of fields),
+ * waiting (_host returns after the upload, _host_async only enqueues, _device reads HBM on the ctx stream) and the pair / chain
+ * refusals are the grey setters'; BBME_ERR_INVALID for a null pointer, a pair, first or count out of range, pitch < 3 W.
+ * A caller's device frames must not overlap the colour store (the pointers bbme_bgr_frames_device_pair returns): the device
+ * setters write the store in the pass that reads the frames.
+ * bbme_bgr_frames_device_pair: the stored frames of `pair` as set (image 1, image 2; physical in both directions), pitch 3 W;
+ * BBME_ERR_STATE unless both have colour. */
+int bbme_bgr_to_gray_host(const uint8_t *bgr, int width, int height, int pitch, uint8_t *gray);
+int bbme_set_frames_host_bgr(bbme_ctx *ctx, int pair, const uint8_t *image1, const uint8_t *image2, int pitch);
+int bbme_set_frames_host_bgr_async(bbme_ctx *ctx, int pair, const uint8_t *image1, const uint8_t *image2, int pitch);
+int bbme_set_frames_device_bgr(bbme_ctx *ctx, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch);
+int bbme_set_chain_frames_host_bgr(bbme_ctx *ctx, int first, int count, const uint8_t *const *frames, int pitch);
+int bbme_set_chain_frames_host_bgr_async(bbme_ctx *ctx, int first, int count, const uint8_t *const *frames, int pitch);
+int bbme_set_chain_frames_device_bgr(bbme_ctx *ctx, int first, int count, const uint8_t *const *d_frames, int pitch);
+int bbme_bgr_frames_device_pair(bbme_ctx *ctx, int pair, const uint8_t **d_bgr1, const uint8_t **d_bgr2);
+
+/* BGR INTERPOLATION RULE.  Inputs: those of the interpolation rule -- the level-0 padded LUMA planes I1, I2 (W0 x H0), the cell
+ * grids F and, optionally, B, the phase num / den -- and the two colour frames C1, C2 (W x H pixels of B,G,R) whose lumas the
+ * planes hold at (pad_x, pad_y): W0 = W + 2 pad_x, H0 = H + 2 pad_y.
+ * Selection is EXACTLY the interpolation rule's, on the luma planes, in padded coordinates: hypotheses, their order, validity,
+ * cost, ties, p1 and p2 are unchanged, so the selection map and the statistics of a colour frame are those
+ * bbme_cells_interpolate_device returns; the colour calls make neither.
+ * The output is the UNPADDED W x H B,G,R frame.  Output pixel (x, y) has the padded position (X, Y) = (x + pad_x, y + pad_y) and
+ * belongs to cell (X >> 1, Y >> 1) at offset (j, i) = (X & 1, Y & 1).  With that cell's p1 and p2, for every channel c
+ *     out[y][x][c] = ((den - num) C1[q1][c] + num C2[q2][c] + den / 2) / den,
+ *     q1 = p1 + (j, i) - (pad_x, pad_y),  q2 = p2 + (j, i) - (pad_x, pad_y)   (frame coordinates),
+ * where a q outside [0, W) x [0, H) reads 0 in every channel: the zero border the luma planes have.  pad_x and pad_y may be odd
+ * (bbme_plan_padding only makes the padded size minus the frame's even): cells then straddle the frame's edge and only their pixels
+ * inside the frame are written.  On frames with B = G = R every channel of the result is the unpadded window of the grey result.
+ * `count` consecutive phases come from one launch, frame q at d_out + q out_stride, rows out_pitch bytes apart (any alignment).
+ * Errors: BBME_ERR_INVALID as for the grey calls (null context or required pointer, pair, den, num0, count), and for
+ * out_pitch < 3 W, bgr_pitch < 3 W, a stride below one frame (out_pitch H) when count > 1, exactly one of d_bgr1 / d_bgr2 null;
+ * BBME_ERR_STATE when frames are unset, when stored colour is asked for and either frame of the pair has none, and for the two context-level calls
+ * without a valid pair of fields.  None of these calls changes context state.  All work on single, batched and chain contexts; in
+ * direction BACKWARD the two colour frames exchange together with the two planes (callers' frames too).
+ * bbme_cells_interpolate_bgr_device: the context's planes of `pair`, ANY two grids in HBM of its cell geometry (d_bwd may be
+ * null) and either the stored colour (d_bgr1 = d_bgr2 = null) or a caller's two frames in HBM, rows bgr_pitch bytes apart -- whose
+ * lumas must be what the planes were made from for the result to mean anything; on hip_stream (NULL = the ctx stream; another
+ * stream is first ordered behind it); no host wait; needs no valid pair of fields.
+ * bbme_interpolate_bgr_device: the same on the context's own two fields and stored colour.
+ * bbme_get_interpolated_bgr_host: one phase of those; synchronises; packed rows of 3 W bytes.
+ * bbme_interpolate_bgr_host: the rule on the CPU, no GPU: packed padded_w x padded_h luma planes (both even), packed width x height
+ * colour frames, packed (padded_h / 2) x (padded_w / 2) grids (bwd may be NULL), out packed 3 width x height; BBME_ERR_INVALID
+ * unless padded_w = width + 2 pad_x and padded_h = height + 2 pad_y with pads >= 0. */
+int bbme_cells_interpolate_bgr_device(bbme_ctx *ctx, int pair, const int16_t *d_fwd, const int16_t *d_bwd, const uint8_t *d_bgr1,
+                                      const uint8_t *d_bgr2, int bgr_pitch, int num0, int count, int den, uint8_t *d_out,
+                                      int out_pitch, size_t out_stride, void *hip_stream);
+int bbme_interpolate_bgr_device(bbme_ctx *ctx, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch,
+                                size_t out_stride, void *hip_stream);
+int bbme_get_interpolated_bgr_host(bbme_ctx *ctx, int pair, int num, int den, uint8_t *out);
+int bbme_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int padded_w, int padded_h, const uint8_t *bgr1,
+                              const uint8_t *bgr2, int width, int height, int pad_x, int pad_y, const int16_t *fwd,
+                              const int16_t *bwd, int num, int den, uint8_t *out);
+
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
 /* copyMVs (:828-843) + calcLevelBM (:226-244) of one level.  Leaves that level's MV
