@@ -86,8 +86,12 @@ struct DevEvent {
 
 struct Level {
     int width = 0, height = 0, block = 0, search = 0, range = 0;
-    DevBuf<uint8_t> img1, img2_own;               // padded planes, pitch == width
-    uint8_t *img2 = nullptr;                      // img2_own; in a chain context an alias of img1 + one plane (see bbme_ctx::chain)
+    // Every padded plane of the level (pitch == width), one plane_stride apart, in ONE allocation.  A pair or batch context: the
+    // image-1 planes of its pairs, then, from frame_step on, their image-2 planes.  A chain context: its pairs + 1 frame slots.
+    // Either way pair p reads img1 + p * plane_stride and img2 + p * plane_stride, and the slack behind every plane is zero.
+    DevBuf<uint8_t> img1;
+    uint8_t *img2 = nullptr;                      // img1 + frame_step
+    size_t frame_step = 0;                        // bytes from a pair's image 1 to its image 2: on a chain one plane_stride
     // MV grids.  small[]: grids at the level's own block size B (the search writes small[0]; the two sweeps at B go
     // small[0] -> small[1] -> small[0], which then stays untouched until the level's next search: the speculative search
     // of the next finer level predicts from it).  big[]: grids at b < B (capacity (H/2)*(W/2)), ping-pong.
@@ -115,7 +119,7 @@ struct Level {
     int fast_pitch_dw = 0;
     size_t fast_lds_bytes = 0;
     // batch: every per-pair buffer holds ctx->batch copies, pair p at p * stride elements (multiples of 64 elements)
-    uint32_t plane_stride = 0;                        // img1 / img2, bytes
+    uint32_t plane_stride = 0;                        // img1 / img2, bytes (frame_step and every product with it: size_t)
     uint32_t small_stride = 0;                        // small[], pred, fix_list: words
     uint32_t big_stride = 0;                          // big[]: words
     uint32_t grid_stride(const mv_t *g) const { return (g == small[0] || g == small[1]) ? small_stride : big_stride; }
@@ -225,7 +229,7 @@ struct bbme_ctx {
     Tuning tune;
     size_t flow_stride = 0;                       // floats from pair to pair in `flow`
     uint32_t list_stride = 0, own_stride = 0;     // words from pair to pair in list[] / own
-    size_t raw_stride = 0;                        // bytes from pair to pair in raw[]
+    size_t raw_stride = 0;                        // bytes from slot to slot in raw
     hipStream_t stream = nullptr;
     bool own_stream = false;
     std::vector<Level> lv;
@@ -241,18 +245,14 @@ struct bbme_ctx {
     uint32_t memo_stride = 0;                     // words from pair to pair
     size_t memo_blocks = 0;                       // blocks per pair it has room for
     int memo_level = -1, memo_block = 0;          // the (level, block size) its slots describe; block 0 = nothing
-    uint64_t frames_mask = 0;                     // bit p: pair p has frames (bbme_estimate needs every pair's)
-    // chain context (bbme_create_chain): batch + 1 frame SLOTS in one allocation per level (Level::img1; img2 = img1 + one plane
-    // stride, so pair p reads slots p and p + 1).  frames_mask then has one bit per slot 0 .. 63, last_slot is slot 64.
+    // FRAME SLOTS: every frame the context holds has one number, used for its planes (Level::img1), the upload buffer, the colour
+    // store and the two vectors of flags below.  A pair or batch context holds 2 batch frames, frame `which` of pair p in slot
+    // which * batch + p; a chain context (bbme_create_chain) holds batch + 1, pair p reading slots p and p + 1.
     bool chain = false;
-    bool last_slot = false;
-    void mark_slot(int s) { if (s < 64) frames_mask |= 1ull << s; else last_slot = true; }
-    void mark_pair0() { if (chain) { mark_slot(0); mark_slot(1); } else frames_mask |= 1ull; }
-    bool frames_set() const
-    {
-        const int n = chain ? batch + 1 : batch;
-        return frames_mask == (n >= 64 ? ~0ull : (1ull << n) - 1ull) && (n <= 64 || last_slot);
-    }
+    int frames() const { return chain ? batch + 1 : 2 * batch; }
+    int slot(int pair, int which) const { return chain ? pair + which : which * batch + pair; }
+    std::vector<uint8_t> slot_set;                // per slot: it has planes (bbme_estimate needs every slot's)
+    bool frames_set() const { return std::find(slot_set.begin(), slot_set.end(), 0) == slot_set.end(); }
     bool jacobi = false;                          // opt-in, not bit-exact: Jacobi sweeps (pass 1 only); bbme_set_regularizer_mode
     bool raster_search = false;                   // MF::find_min_block (:246-294) instead of the spiral search; bbme_set_search_mode
     bool relax = true;                            // relaxation launches (k_reg_iter) on large grids of small blocks; bbme_set_relaxation
@@ -282,7 +282,7 @@ struct bbme_ctx {
     DevBuf<uint8_t> fb_mask;                      // bbme_get_consistency_host: a packed CH x CW mask before its download
     DevBuf<unsigned long long> fb_stats;          // consistency statistics: 4 words per pair, then the partials of k_fb_consistency of
                                                   // bbme_consistency_stats (every pair) and of bbme_cells_consistency_device (one pair)
-    DevBuf<uint8_t> raw[2];                       // bbme_set_frames_host: the unpadded frames in HBM
+    DevBuf<uint8_t> raw;                          // the host setters' upload buffer: one unpadded grey frame per slot
     DevBuf<float> sub;                            // bbme_get_subsampled_flow_host: the packed field before its download (grown to
                                                   // the largest asked for)
     DevBuf<uint8_t> mc_plane;                     // bbme_get_motion_compensated_host: a level-0-sized plane before its download
@@ -294,17 +294,12 @@ struct bbme_ctx {
                                                   // bbme_cells_color_device; k_color_range), then five floats per slot
     DevBuf<uint8_t> color_img;                    // bbme_get_flow_color_host: the packed B,G,R image before its download (grown to
                                                   // the largest asked for)
-    // COLOUR STORE (include/bbme.h): one packed B,G,R frame (pitch 3 width) per frame the context holds, bgr_stride bytes apart,
-    // allocated by the first *_bgr setter: frame i of pair p in slot 2 p + i, on a chain context frame slot s in slot s.
-    // bgr_set[slot]: the slot's colour is what its luma plane was made from (cleared by every grey setter of that frame).
+    // COLOUR STORE (include/bbme.h): one packed B,G,R frame (pitch 3 width) per slot, bgr_stride bytes apart, allocated by the
+    // first *_bgr setter.  bgr_set[slot]: the slot's colour is what its luma plane was made from (cleared by every grey setter
+    // of that frame).
     DevBuf<uint8_t> bgr;
     size_t bgr_stride = 0;
     std::vector<uint8_t> bgr_set;
-    int bgr_slot(int pair, int which) const { return chain ? pair + which : 2 * pair + which; }
-    void clear_bgr(int slot, int count = 1)
-    {
-        for (int s = slot; s < slot + count && s < (int)bgr_set.size(); ++s) bgr_set[s] = 0;
-    }
     DevBuf<uint8_t> ip_bgr;                       // bbme_get_interpolated_bgr_host: a packed 3 W x H frame before its download
 };
 
@@ -906,6 +901,9 @@ static int create_context(const bbme_params *params, int width, int height, int 
     c->params = *params; c->geom = g; c->device = device;
     c->batch = pairs;
     c->chain = chain;
+    c->slot_set.assign(c->frames(), 0);
+    c->bgr_set.assign(c->frames(), 0);
+    c->raw_stride = ((size_t)g.width * g.height + 64 + 255) / 256 * 256;
     c->tune = read_tuning(pairs);
     const size_t P = (size_t)pairs;
     auto round64 = [](size_t n) { return (n + 63) / 64 * 64; };
@@ -941,10 +939,11 @@ static int create_context(const bbme_params *params, int width, int height, int 
         std::vector<uint32_t> packed(sp.dx.size());
         for (size_t i = 0; i < sp.dx.size(); ++i)
             packed[i] = ((uint32_t)(uint16_t)sp.dx[i]) | ((uint32_t)(uint16_t)sp.dy[i] << 16);
-        // a chain context: the P + 1 frame slots of the level in ONE allocation, image 2 of pair p = image 1 of pair p + 1
-        if (int rc = L.img1.alloc_zero((chain ? P + 1 : P) * plane, what)) return rc;
-        if (!chain) if (int rc = L.img2_own.alloc_zero(P * plane, what)) return rc;
-        L.img2 = chain ? L.img1 + plane : L.img2_own.get();
+        // a chain context: P + 1 frame slots, image 2 of pair p = image 1 of pair p + 1.  Otherwise the P image-1 planes, then the
+        // P image-2 planes from the next multiple of 4 KiB on (the alignment an allocation of their own would give them)
+        L.frame_step = chain ? plane : (P * plane + 4095) / 4096 * 4096;
+        if (int rc = L.img1.alloc_zero(chain ? (P + 1) * plane : L.frame_step + P * plane, what)) return rc;
+        L.img2 = L.img1 + L.frame_step;
         for (DevBuf<mv_t> *grid : {&L.small[0], &L.small[1], &L.pred})
             if (int rc = grid->alloc(P * own_blocks, what)) return rc;
         if (int rc = L.fix_list.alloc(P * own_blocks, what)) return rc;
@@ -1173,61 +1172,51 @@ int bbme_level_geometry(const bbme_ctx *c, int level, int *w, int *h, int *b, in
     return BBME_OK;
 }
 
-int bbme_set_frames_host(bbme_ctx *c, const uint8_t *image1, const uint8_t *image2, int pitch)
-{
-    if (int rc = bbme_set_frames_host_async(c, 0, image1, image2, pitch)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
-    return BBME_OK;
-}
+// ---- frame setters: one check, one upload, one preparation path for every kind of context and of frame --------------------
 
-int bbme_set_frames_host_pair(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
-{
-    if (int rc = bbme_set_frames_host_async(c, pair, image1, image2, pitch)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return BBME_OK;
-}
+namespace {
 
-// Enqueues the upload of a pair's two (width x height, rows `pitch` bytes apart) host frames into raw[], packed (pitch = width).
-// raw[] has room for the context's frame size; the x4 setters upload frames of a sixteenth of that.
-static int upload_raw(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int width, int height, int pitch)
+// WHICH FRAMES a setter writes: `count` slots from `first` on, `step` slots apart (bbme_ctx, "frame slots").  The two frames
+// of a pair are a run of two with the step of a whole batch; a run of a chain context's slots has step 1.  At every level
+// the set's first plane is img1 + first * plane_stride and its planes lie frame_step apart: that is what frame_step is.
+struct FrameSet {
+    int first, count, step;
+    int slot(int i) const { return first + i * step; }
+    uint8_t *planes(const Level &L) const { return L.img1 + (size_t)first * L.plane_stride; }
+};
+FrameSet frames_of_pair(const bbme_ctx *c, int pair) { return {pair, 2, c->batch}; }
+FrameSet frames_of_run(int first, int count) { return {first, count, 1}; }
+
+// What the frames of a setter are made of.  kNoFormat: a chain setter's `scale` that is neither 1 nor 4.
+enum FrameFormat { kGrey, kGreyX4, kBgr, kNoFormat };
+FrameFormat grey_format(int scale) { return scale == 1 ? kGrey : scale == 4 ? kGreyX4 : kNoFormat; }
+
+// The arguments of every frame setter.  by_slot: a chain setter (`first`, `count` are slots of a chain context), else a pair
+// setter (`first` is the pair, count 2).  Touches no device.
+int check_frames(const bbme_ctx *c, bool by_slot, int first, int count, const uint8_t *const *frames, int pitch, FrameFormat fmt,
+                 const char *what)
 {
+    if (int rc = by_slot ? chain_context_only(c, what) : pair_context_only(c, what)) return rc;
     const Geometry &g = c->geom;
-    const size_t bytes = (size_t)g.width * g.height;
-    c->raw_stride = (bytes + 64 + 255) / 256 * 256;
-    const uint8_t *src[2] = {image1, image2};
-    for (int i = 0; i < 2; ++i) {
-        if (int rc = c->raw[i].ensure(c->raw_stride * c->batch, "the upload buffers")) return rc;
-        HIP_TRY(hipMemcpy2DAsync(c->raw[i] + pair * c->raw_stride, width, src[i], pitch, width, height, hipMemcpyHostToDevice, c->stream));
-    }
+    if (fmt == kNoFormat) return bbme::fail(BBME_ERR_INVALID, "%s: scale is neither 1 nor 4", what);
+    if (fmt == kGreyX4 && (g.width % 4 || g.height % 4))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the context's frame (%dx%d) is not a multiple of 4 in both dimensions", what,
+                          g.width, g.height);
+    if (by_slot && (first < 0 || count < 1 || first > c->batch || count > c->batch + 1 - first))
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d of %d", what, first, first + count - 1, c->batch + 1);
+    if (!by_slot && (first < 0 || first >= c->batch)) return bbme::fail(BBME_ERR_INVALID, "%s: pair %d of %d", what, first, c->batch);
+    if (!frames) return bbme::fail(BBME_ERR_INVALID, "%s: null frame table", what);
+    for (int i = 0; i < count; ++i)
+        if (!frames[i]) return bbme::fail(BBME_ERR_INVALID, "%s: frame %d of the %s is null", what, i, by_slot ? "run" : "pair");
+    const long long row = fmt == kBgr ? 3LL * g.width : fmt == kGreyX4 ? g.width / 4 : g.width;
+    if (pitch < row) return bbme::fail(BBME_ERR_INVALID, "%s: pitch %d < %lld bytes of a frame's row", what, pitch, row);
     return BBME_OK;
 }
 
-int bbme_set_frames_host_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
-{
-    if (int rc = pair_context_only(c, "bbme_set_frames_host")) return rc;
-    if (!image1 || !image2 || pitch < c->geom.width || pair < 0 || pair >= c->batch)
-        return bbme::fail(BBME_ERR_INVALID, "bbme_set_frames_host: bad arguments");
-    HIP_TRY(hipSetDevice(c->device));
-    // the frames as they are go to HBM; zero border and pyrDown cascade run there (bbme_set_frames_device) -- the same
-    // integers as bbme_pad_zero_host / bbme_pyr_down_host produce, without 18 ms of single-threaded host filtering at 4K
-    const Geometry &g = c->geom;
-    if (int rc = upload_raw(c, pair, image1, image2, g.width, g.height, pitch)) return rc;
-    // no host wait: with pinned source buffers the upload, the border, the pyramid and an estimate behind them overlap whatever
-    // the host does next; the buffers must stay untouched until the context's stream has passed this point
-    return bbme_set_frames_device_pair(c, pair, c->raw[0] + pair * c->raw_stride, c->raw[1] + pair * c->raw_stride, g.width);
-}
-
-int bbme_set_frames_device(bbme_ctx *c, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
-{
-    return bbme_set_frames_device_pair(c, 0, d_image1, d_image2, pitch);
-}
-
-static int enqueue_cascade(bbme_ctx *c, int pair);
-
-// k_pyr_down4 / k_pyr_down4_run make four output pixels per thread from 16-byte loads: the SOURCE level of a pyrDown must be a
-// multiple of 8 pixels wide.  create_context refuses every level width that is not a multiple of 4, and a source level is twice
-// the level below it, so this holds for every context there is; a geometry that broke it must fail here, not compute something.
-static int check_pyr_down_source(const Level &P, size_t level)
+// k_pyr_down4_run makes four output pixels per thread from 16-byte loads: the SOURCE level of a pyrDown must be a multiple of
+// 8 pixels wide.  create_context refuses every level width that is not a multiple of 4, and a source level is twice the level
+// below it, so this holds for every context there is; a geometry that broke it must fail here, not compute something.
+int check_pyr_down_source(const Level &P, size_t level)
 {
     if (P.width % 8 != 0)
         return bbme::fail(BBME_ERR_UNSUPPORTED, "level %zu is %d pixels wide: pyrDown needs a source width that is a multiple of 8",
@@ -1235,88 +1224,189 @@ static int check_pyr_down_source(const Level &P, size_t level)
     return BBME_OK;
 }
 
-int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
+// The frames of `set` from `src` in HBM (rows `pitch` bytes apart) into their planes of every level, one launch per level with
+// every frame of the set in it (blockIdx.y): zero border -- with the x4 up-sampling (main_class.cpp:32-33; sources of a quarter
+// of the frame) or the luma conversion fused in -- then MF::MF's pyrDown cascade (motion_framework.cpp:86-106).  kBgr with
+// `keep`: the sources are a caller's and are copied into the set's slots of the colour store in the same pass; without, they
+// ARE those slots.  And the bookkeeping of every frame setter.  No host wait: upload, border, pyramid and an estimate behind
+// them overlap whatever the host does next.
+int prepare_frames(bbme_ctx *c, FrameSet set, const FrameRun &src, int pitch, FrameFormat fmt, bool keep = false)
 {
-    if (int rc = pair_context_only(c, "bbme_set_frames_device")) return rc;
-    if (!d_image1 || !d_image2 || pitch < c->geom.width || pair < 0 || pair >= c->batch)
-        return bbme::fail(BBME_ERR_INVALID, "bbme_set_frames_device: bad arguments");
-    HIP_TRY(hipSetDevice(c->device));
     const Geometry &g = c->geom;
-    const size_t pp_ = (size_t)pair;
-    // both frames per launch: zero border into the level-0 planes, then the pyrDown cascade
     Level &L0 = c->lv[0];
-    PlanePair pp{{d_image1, d_image2}, {L0.img1 + pp_ * L0.plane_stride, L0.img2 + pp_ * L0.plane_stride}};
     const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
-    hipLaunchKernelGGL(k_pad_zero, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
-                       pp, g.width, g.height, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
-    c->clear_bgr(c->bgr_slot(pair, 0), 2);              // grey frames: the stored colour is no longer theirs
-    return enqueue_cascade(c, pair);
-}
-
-// MF::MF's pyrDown cascade (motion_framework.cpp:86-106) of one pair from its level-0 planes, and the bookkeeping every frame
-// setter shares: the pair has frames, and what the SAD memo holds is no longer true
-static int enqueue_cascade(bbme_ctx *c, int pair)
-{
-    const size_t pp_ = (size_t)pair;
+    const dim3 grid0((unsigned)((chunks + 255) / 256), (unsigned)set.count);
+    if (fmt == kBgr)
+        hipLaunchKernelGGL(k_bgr_pad_run, grid0, dim3(256), 0, c->stream, src, set.planes(L0), L0.frame_step,
+                           keep ? c->bgr + (size_t)set.first * c->bgr_stride : nullptr, (size_t)set.step * c->bgr_stride, g.width,
+                           g.height, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    else if (fmt == kGreyX4)
+        hipLaunchKernelGGL(k_resize_x4_pad_run, grid0, dim3(256), 0, c->stream, src, set.planes(L0), L0.frame_step, g.width / 4,
+                           g.height / 4, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
+    else
+        hipLaunchKernelGGL(k_pad_zero_run, grid0, dim3(256), 0, c->stream, src, set.planes(L0), L0.frame_step, g.width, g.height,
+                           pitch, g.pad_x, g.pad_y, L0.width, L0.height);
     for (size_t l = 1; l < c->lv.size(); ++l) {
         Level &P = c->lv[l - 1], &L = c->lv[l];
-        PlanePair q{{P.img1 + pp_ * P.plane_stride, P.img2 + pp_ * P.plane_stride}, {L.img1 + pp_ * L.plane_stride, L.img2 + pp_ * L.plane_stride}};
         if (int rc = check_pyr_down_source(P, l - 1)) return rc;
         const long long n = (long long)(L.width / 4) * L.height;
-        hipLaunchKernelGGL(k_pyr_down4, dim3((unsigned)((n + 255) / 256), 2), dim3(256), 0, c->stream, q, P.width, P.height);
+        hipLaunchKernelGGL(k_pyr_down4_run, dim3((unsigned)((n + 255) / 256), (unsigned)set.count), dim3(256), 0, c->stream,
+                           set.planes(P), P.frame_step, set.planes(L), L.frame_step, P.width, P.height);
     }
     HIP_TRY(hipGetLastError());
-    c->frames_mask |= 1ull << pair;
+    for (int i = 0; i < set.count; ++i) {
+        c->slot_set[set.slot(i)] = 1;
+        c->bgr_set[set.slot(i)] = fmt == kBgr;
+    }
     c->memo_block = 0;                                  // new planes: what the SAD memo holds is no longer true
     c->fields_valid = false;
     return BBME_OK;
 }
 
-// ---- x4 up-sampling on the device (main_class.cpp:32-33): frames of (width / 4) x (height / 4) ------------------------
-
-static int check_x4(const bbme_ctx *c, int pair, const void *image1, const void *image2, int pitch, const char *what)
+// the colour store, allocated on first use: one packed frame per slot
+int bgr_store(bbme_ctx *c)
 {
-    if (int rc = pair_context_only(c, what)) return rc;
+    if (c->bgr.get()) return BBME_OK;
+    c->bgr_stride = ((size_t)3 * c->geom.width * c->geom.height + 255) / 256 * 256;
+    return c->bgr.alloc(c->bgr_stride * (size_t)c->frames(), "the colour store");
+}
+
+// A device setter: frames in HBM.  B,G,R frames are kept (copied into the colour store).
+int set_frames_device(bbme_ctx *c, bool by_slot, int first, int count, const uint8_t *const *d_frames, int pitch, FrameFormat fmt,
+                      const char *what)
+{
+    if (int rc = check_frames(c, by_slot, first, count, d_frames, pitch, fmt, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (fmt == kBgr) if (int rc = bgr_store(c)) return rc;
+    FrameRun run{};
+    for (int i = 0; i < count; ++i) run.src[i] = d_frames[i];
+    return prepare_frames(c, by_slot ? frames_of_run(first, count) : frames_of_pair(c, first), run, pitch, fmt, fmt == kBgr);
+}
+
+// A host setter: every frame crosses PCIe once, packed, on the context's stream -- grey frames as they are into their slots of
+// the upload buffer (room for the context's frame size; x4 sources are a sixteenth of that), B,G,R frames straight into their
+// slots of the colour store, where the conversion reads them and where they stay.  Border and cascade run in HBM (the same
+// integers as bbme_pad_zero_host / bbme_pyr_down_host, without 18 ms of single-threaded host filtering at 4K).  The caller's
+// buffers must stay untouched until the context's stream has passed this point.
+int set_frames_host(bbme_ctx *c, bool by_slot, int first, int count, const uint8_t *const *frames, int pitch, FrameFormat fmt,
+                    const char *what)
+{
+    if (int rc = check_frames(c, by_slot, first, count, frames, pitch, fmt, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const FrameSet set = by_slot ? frames_of_run(first, count) : frames_of_pair(c, first);
     const Geometry &g = c->geom;
-    if (g.width % 4 || g.height % 4)
-        return bbme::fail(BBME_ERR_INVALID, "%s: the context's frame (%dx%d) is not a multiple of 4 in both dimensions", what,
-                          g.width, g.height);
-    if (!image1 || !image2 || pitch < g.width / 4 || pair < 0 || pair >= c->batch)
-        return bbme::fail(BBME_ERR_INVALID, "%s: bad arguments (pitch %d, source width %d, pair %d of %d)", what, pitch,
-                          g.width / 4, pair, c->batch);
+    const int scale = fmt == kGreyX4 ? 4 : 1;
+    const size_t row = (size_t)(fmt == kBgr ? 3 : 1) * (g.width / scale), rows = (size_t)(g.height / scale);
+    if (int rc = fmt == kBgr ? bgr_store(c) : c->raw.ensure(c->raw_stride * (size_t)c->frames(), "the upload buffer")) return rc;
+    FrameRun run{};
+    for (int i = 0; i < count; ++i) {
+        uint8_t *d = fmt == kBgr ? c->bgr + (size_t)set.slot(i) * c->bgr_stride : c->raw + (size_t)set.slot(i) * c->raw_stride;
+        c->bgr_set[set.slot(i)] = 0;                        // the store's slot, or the plane it described, is being overwritten
+        HIP_TRY(hipMemcpy2DAsync(d, row, frames[i], (size_t)pitch, row, rows, hipMemcpyHostToDevice, c->stream));
+        run.src[i] = d;
+    }
+    return prepare_frames(c, set, run, (int)row, fmt);
+}
+
+// The blocking form of a host setter: on return the caller may re-use its buffers
+int then_wait(bbme_ctx *c, int rc)
+{
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return BBME_OK;
+}
+
+}  // namespace
+
+int bbme_set_frames_device_pair(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
+{
+    const uint8_t *const frames[2] = {d_image1, d_image2};
+    return set_frames_device(c, false, pair, 2, frames, pitch, kGrey, "bbme_set_frames_device");
+}
+
+int bbme_set_frames_device(bbme_ctx *c, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
+{
+    return bbme_set_frames_device_pair(c, 0, d_image1, d_image2, pitch);
+}
+
+int bbme_set_frames_host_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    const uint8_t *const frames[2] = {image1, image2};
+    return set_frames_host(c, false, pair, 2, frames, pitch, kGrey, "bbme_set_frames_host");
+}
+
+int bbme_set_frames_host_pair(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    return then_wait(c, bbme_set_frames_host_async(c, pair, image1, image2, pitch));
+}
+
+int bbme_set_frames_host(bbme_ctx *c, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    return bbme_set_frames_host_pair(c, 0, image1, image2, pitch);
 }
 
 int bbme_set_frames_device_x4(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
 {
-    if (int rc = check_x4(c, pair, d_image1, d_image2, pitch, "bbme_set_frames_device_x4")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const Geometry &g = c->geom;
-    const size_t pp_ = (size_t)pair;
-    // both frames per launch: up-sampling and zero border into the level-0 planes (every byte), then the pyrDown cascade
-    Level &L0 = c->lv[0];
-    PlanePair pp{{d_image1, d_image2}, {L0.img1 + pp_ * L0.plane_stride, L0.img2 + pp_ * L0.plane_stride}};
-    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
-    hipLaunchKernelGGL(k_resize_x4_pad, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
-                       pp, g.width / 4, g.height / 4, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
-    c->clear_bgr(c->bgr_slot(pair, 0), 2);
-    return enqueue_cascade(c, pair);
+    const uint8_t *const frames[2] = {d_image1, d_image2};
+    return set_frames_device(c, false, pair, 2, frames, pitch, kGreyX4, "bbme_set_frames_device_x4");
 }
 
 int bbme_set_frames_host_x4_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
 {
-    if (int rc = check_x4(c, pair, image1, image2, pitch, "bbme_set_frames_host_x4")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const int sw = c->geom.width / 4, sh = c->geom.height / 4;
-    if (int rc = upload_raw(c, pair, image1, image2, sw, sh, pitch)) return rc;
-    return bbme_set_frames_device_x4(c, pair, c->raw[0] + pair * c->raw_stride, c->raw[1] + pair * c->raw_stride, sw);
+    const uint8_t *const frames[2] = {image1, image2};
+    return set_frames_host(c, false, pair, 2, frames, pitch, kGreyX4, "bbme_set_frames_host_x4");
 }
 
 int bbme_set_frames_host_x4(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
 {
-    if (int rc = bbme_set_frames_host_x4_async(c, pair, image1, image2, pitch)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
-    return BBME_OK;
+    return then_wait(c, bbme_set_frames_host_x4_async(c, pair, image1, image2, pitch));
+}
+
+int bbme_set_frames_device_bgr(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
+{
+    const uint8_t *const frames[2] = {d_image1, d_image2};
+    return set_frames_device(c, false, pair, 2, frames, pitch, kBgr, "bbme_set_frames_device_bgr");
+}
+
+int bbme_set_frames_host_bgr_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    const uint8_t *const frames[2] = {image1, image2};
+    return set_frames_host(c, false, pair, 2, frames, pitch, kBgr, "bbme_set_frames_host_bgr");
+}
+
+int bbme_set_frames_host_bgr(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
+{
+    return then_wait(c, bbme_set_frames_host_bgr_async(c, pair, image1, image2, pitch));
+}
+
+int bbme_set_chain_frames_device(bbme_ctx *c, int first, int count, const uint8_t *const *d_frames, int pitch, int scale)
+{
+    return set_frames_device(c, true, first, count, d_frames, pitch, grey_format(scale), "bbme_set_chain_frames_device");
+}
+
+int bbme_set_chain_frames_host_async(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale)
+{
+    return set_frames_host(c, true, first, count, frames, pitch, grey_format(scale), "bbme_set_chain_frames_host");
+}
+
+int bbme_set_chain_frames_host(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale)
+{
+    return then_wait(c, bbme_set_chain_frames_host_async(c, first, count, frames, pitch, scale));
+}
+
+int bbme_set_chain_frames_device_bgr(bbme_ctx *c, int first, int count, const uint8_t *const *d_frames, int pitch)
+{
+    return set_frames_device(c, true, first, count, d_frames, pitch, kBgr, "bbme_set_chain_frames_device_bgr");
+}
+
+int bbme_set_chain_frames_host_bgr_async(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch)
+{
+    return set_frames_host(c, true, first, count, frames, pitch, kBgr, "bbme_set_chain_frames_host_bgr");
+}
+
+int bbme_set_chain_frames_host_bgr(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch)
+{
+    return then_wait(c, bbme_set_chain_frames_host_bgr_async(c, first, count, frames, pitch));
 }
 
 // ---- chain contexts: frames by slot, rolled forward through a video ----------------------------------------------------
@@ -1326,95 +1416,6 @@ int bbme_chain_frames(const bbme_ctx *c, int *frames)
     if (int rc = check_ctx(c)) return rc;
     if (!frames) return bbme::fail(BBME_ERR_INVALID, "null output");
     *frames = c->chain ? c->batch + 1 : 0;
-    return BBME_OK;
-}
-
-static int check_chain_run(const bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale, const char *what)
-{
-    if (int rc = chain_context_only(c, what)) return rc;
-    const Geometry &g = c->geom;
-    if (scale != 1 && scale != 4) return bbme::fail(BBME_ERR_INVALID, "%s: scale %d (1 or 4)", what, scale);
-    if (scale == 4 && (g.width % 4 || g.height % 4))
-        return bbme::fail(BBME_ERR_INVALID, "%s: the context's frame (%dx%d) is not a multiple of 4 in both dimensions", what,
-                          g.width, g.height);
-    if (first < 0 || count < 1 || first > c->batch || count > c->batch + 1 - first)
-        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d of %d", what, first, first + count - 1, c->batch + 1);
-    if (!frames) return bbme::fail(BBME_ERR_INVALID, "%s: null frame table", what);
-    for (int i = 0; i < count; ++i)
-        if (!frames[i]) return bbme::fail(BBME_ERR_INVALID, "%s: frame %d of the run is null", what, i);
-    if (pitch < g.width / scale) return bbme::fail(BBME_ERR_INVALID, "%s: pitch %d < frame width %d", what, pitch, g.width / scale);
-    return BBME_OK;
-}
-
-// The pyrDown cascade of slots first .. first + count - 1 from their level-0 planes, one launch per level, all frames of the run
-// in each (blockIdx.y); and the bookkeeping every frame setter shares (enqueue_cascade)
-static int enqueue_chain_cascade(bbme_ctx *c, int first, int count)
-{
-    for (size_t l = 1; l < c->lv.size(); ++l) {
-        Level &P = c->lv[l - 1], &L = c->lv[l];
-        const uint8_t *src = P.img1 + (size_t)first * P.plane_stride;
-        uint8_t *dst = L.img1 + (size_t)first * L.plane_stride;
-        if (int rc = check_pyr_down_source(P, l - 1)) return rc;
-        const long long n = (long long)(L.width / 4) * L.height;
-        hipLaunchKernelGGL(k_pyr_down4_run, dim3((unsigned)((n + 255) / 256), (unsigned)count), dim3(256), 0, c->stream,
-                           src, P.plane_stride, dst, L.plane_stride, P.width, P.height);
-    }
-    HIP_TRY(hipGetLastError());
-    for (int i = 0; i < count; ++i) c->mark_slot(first + i);
-    c->memo_block = 0;                                  // new planes: what the SAD memo holds is no longer true
-    c->fields_valid = false;
-    return BBME_OK;
-}
-
-// `count` grey frames in HBM into slots first .. : border (or x4 up-sampling + border) as one launch, then the cascade
-static int enqueue_chain_run(bbme_ctx *c, int first, int count, const FrameRun &run, int pitch, int scale)
-{
-    const Geometry &g = c->geom;
-    Level &L0 = c->lv[0];
-    uint8_t *dst0 = L0.img1 + (size_t)first * L0.plane_stride;
-    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
-    const dim3 grid0((unsigned)((chunks + 255) / 256), (unsigned)count);
-    if (scale == 4)
-        hipLaunchKernelGGL(k_resize_x4_pad_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width / 4, g.height / 4,
-                           pitch, g.pad_x, g.pad_y, L0.width, L0.height);
-    else
-        hipLaunchKernelGGL(k_pad_zero_run, grid0, dim3(256), 0, c->stream, run, dst0, L0.plane_stride, g.width, g.height, pitch,
-                           g.pad_x, g.pad_y, L0.width, L0.height);
-    c->clear_bgr(first, count);                         // grey frames: the stored colour is no longer theirs
-    return enqueue_chain_cascade(c, first, count);
-}
-
-int bbme_set_chain_frames_device(bbme_ctx *c, int first, int count, const uint8_t *const *d_frames, int pitch, int scale)
-{
-    if (int rc = check_chain_run(c, first, count, d_frames, pitch, scale, "bbme_set_chain_frames_device")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    FrameRun run{};
-    for (int i = 0; i < count; ++i) run.src[i] = d_frames[i];
-    return enqueue_chain_run(c, first, count, run, pitch, scale);
-}
-
-int bbme_set_chain_frames_host_async(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale)
-{
-    if (int rc = check_chain_run(c, first, count, frames, pitch, scale, "bbme_set_chain_frames_host")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    // every frame crosses PCIe once, packed, into its slot of ONE upload buffer (as upload_raw: room for the context's frame size)
-    const Geometry &g = c->geom;
-    const int sw = g.width / scale, sh = g.height / scale;
-    c->raw_stride = ((size_t)g.width * g.height + 64 + 255) / 256 * 256;
-    if (int rc = c->raw[0].ensure(c->raw_stride * (size_t)(c->batch + 1), "the upload buffers")) return rc;
-    FrameRun run{};
-    for (int i = 0; i < count; ++i) {
-        uint8_t *d = c->raw[0] + (size_t)(first + i) * c->raw_stride;
-        HIP_TRY(hipMemcpy2DAsync(d, sw, frames[i], pitch, sw, sh, hipMemcpyHostToDevice, c->stream));
-        run.src[i] = d;
-    }
-    return enqueue_chain_run(c, first, count, run, sw, scale);
-}
-
-int bbme_set_chain_frames_host(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, int scale)
-{
-    if (int rc = bbme_set_chain_frames_host_async(c, first, count, frames, pitch, scale)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
     return BBME_OK;
 }
 
@@ -1435,11 +1436,11 @@ int bbme_chain_advance(bbme_ctx *c)
     const unsigned wgs = std::max(1u, std::min(2048u, (most + 255u) / 256u));
     hipLaunchKernelGGL(k_chain_roll, dim3(wgs, (unsigned)c->lv.size()), dim3(256), 0, c->stream, r);
     HIP_TRY(hipGetLastError());
-    const bool had_bgr = !c->bgr_set.empty() && c->bgr_set[c->batch] != 0;
-    c->clear_bgr(0, c->batch + 1);
-    const bool had_last = c->batch < 64 ? (c->frames_mask >> c->batch) & 1ull : c->last_slot;
-    c->frames_mask = had_last ? 1ull : 0ull;         // slot 0 is as set as the slot it came from
-    c->last_slot = false;
+    // slot 0 takes the last slot's flags (it is as set as the slot it came from), the rest are cleared
+    const uint8_t had_last = c->slot_set[c->batch], had_bgr = c->bgr_set[c->batch];
+    c->slot_set.assign(c->slot_set.size(), 0);
+    c->bgr_set.assign(c->bgr_set.size(), 0);
+    c->slot_set[0] = had_last;
     c->memo_block = 0;
     c->fields_valid = false;
     if (had_bgr) {                                      // the last slot's colour goes with its planes; slot 0 has colour once the copy is enqueued
@@ -1464,141 +1465,13 @@ int bbme_get_chain_plane_host(bbme_ctx *c, int level, int slot, uint8_t *image)
     return BBME_OK;
 }
 
-// ---- colour frames in (the luma rule of include/bbme.h; k_bgr_pad, k_bgr_pad_run) and the colour store ------------------
-
-// the colour store, allocated on first use: one packed frame per frame of the context
-static int bgr_store(bbme_ctx *c)
-{
-    if (c->bgr.get()) return BBME_OK;
-    const size_t slots = c->chain ? (size_t)c->batch + 1 : (size_t)2 * c->batch;
-    c->bgr_stride = ((size_t)3 * c->geom.width * c->geom.height + 255) / 256 * 256;
-    if (int rc = c->bgr.alloc(c->bgr_stride * slots, "the colour store")) return rc;
-    c->bgr_set.assign(slots, 0);
-    return BBME_OK;
-}
-
-static int check_bgr_pair(const bbme_ctx *c, int pair, const void *image1, const void *image2, int pitch, const char *what)
-{
-    if (int rc = pair_context_only(c, what)) return rc;
-    if (!image1 || !image2 || (long long)pitch < 3LL * c->geom.width || pair < 0 || pair >= c->batch)
-        return bbme::fail(BBME_ERR_INVALID, "%s: bad arguments (pitch %d, 3 x width %d, pair %d of %d)", what, pitch,
-                          3 * c->geom.width, pair, c->batch);
-    return BBME_OK;
-}
-
-// Both colour frames of a pair in HBM (rows `pitch` bytes apart) into its level-0 luma planes, then the cascade.  keep: the
-// frames are a caller's and are copied into the pair's slots of the store in the same pass; otherwise they ARE those slots.
-static int enqueue_bgr_pair(bbme_ctx *c, int pair, const uint8_t *d1, const uint8_t *d2, int pitch, bool keep)
-{
-    const Geometry &g = c->geom;
-    const size_t pp_ = (size_t)pair;
-    Level &L0 = c->lv[0];
-    uint8_t *s1 = c->bgr + (size_t)c->bgr_slot(pair, 0) * c->bgr_stride, *s2 = c->bgr + (size_t)c->bgr_slot(pair, 1) * c->bgr_stride;
-    BgrPair pp{{d1, d2}, {L0.img1 + pp_ * L0.plane_stride, L0.img2 + pp_ * L0.plane_stride}, {keep ? s1 : nullptr, keep ? s2 : nullptr}};
-    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
-    hipLaunchKernelGGL(k_bgr_pad, dim3((unsigned)((chunks + 255) / 256), 2), dim3(256), 0, c->stream,
-                       pp, g.width, g.height, pitch, g.pad_x, g.pad_y, L0.width, L0.height);
-    if (int rc = enqueue_cascade(c, pair)) return rc;
-    c->bgr_set[c->bgr_slot(pair, 0)] = c->bgr_set[c->bgr_slot(pair, 1)] = 1;
-    return BBME_OK;
-}
-
-int bbme_set_frames_device_bgr(bbme_ctx *c, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch)
-{
-    if (int rc = check_bgr_pair(c, pair, d_image1, d_image2, pitch, "bbme_set_frames_device_bgr")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = bgr_store(c)) return rc;
-    return enqueue_bgr_pair(c, pair, d_image1, d_image2, pitch, true);
-}
-
-int bbme_set_frames_host_bgr_async(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
-{
-    if (int rc = check_bgr_pair(c, pair, image1, image2, pitch, "bbme_set_frames_host_bgr")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = bgr_store(c)) return rc;
-    // straight into the store, packed: the frame crosses PCIe once, and the conversion reads it where it stays
-    const size_t row = (size_t)3 * c->geom.width;
-    const uint8_t *src[2] = {image1, image2};
-    uint8_t *slot[2];
-    for (int i = 0; i < 2; ++i) {
-        slot[i] = c->bgr + (size_t)c->bgr_slot(pair, i) * c->bgr_stride;
-        c->bgr_set[c->bgr_slot(pair, i)] = 0;               // until the planes are made of it
-        HIP_TRY(hipMemcpy2DAsync(slot[i], row, src[i], (size_t)pitch, row, (size_t)c->geom.height, hipMemcpyHostToDevice, c->stream));
-    }
-    return enqueue_bgr_pair(c, pair, slot[0], slot[1], (int)row, false);
-}
-
-int bbme_set_frames_host_bgr(bbme_ctx *c, int pair, const uint8_t *image1, const uint8_t *image2, int pitch)
-{
-    if (int rc = bbme_set_frames_host_bgr_async(c, pair, image1, image2, pitch)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
-    return BBME_OK;
-}
-
-static int check_bgr_run(const bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch, const char *what)
-{
-    if (int rc = check_ctx(c)) return rc;
-    if (int rc = check_chain_run(c, first, count, frames, c->geom.width, 1, what)) return rc;      // the slots and the table
-    if ((long long)pitch < 3LL * c->geom.width)
-        return bbme::fail(BBME_ERR_INVALID, "%s: pitch %d < 3 x frame width %d", what, pitch, c->geom.width);
-    return BBME_OK;
-}
-
-// enqueue_bgr_pair for the slots first .. first + count - 1 of a chain context
-static int enqueue_bgr_run(bbme_ctx *c, int first, int count, const FrameRun &run, int pitch, bool keep)
-{
-    const Geometry &g = c->geom;
-    Level &L0 = c->lv[0];
-    const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
-    hipLaunchKernelGGL(k_bgr_pad_run, dim3((unsigned)((chunks + 255) / 256), (unsigned)count), dim3(256), 0, c->stream, run,
-                       L0.img1 + (size_t)first * L0.plane_stride, L0.plane_stride,
-                       keep ? c->bgr + (size_t)first * c->bgr_stride : nullptr, c->bgr_stride, g.width, g.height, pitch, g.pad_x,
-                       g.pad_y, L0.width, L0.height);
-    if (int rc = enqueue_chain_cascade(c, first, count)) return rc;
-    for (int i = 0; i < count; ++i) c->bgr_set[first + i] = 1;
-    return BBME_OK;
-}
-
-int bbme_set_chain_frames_device_bgr(bbme_ctx *c, int first, int count, const uint8_t *const *d_frames, int pitch)
-{
-    if (int rc = check_bgr_run(c, first, count, d_frames, pitch, "bbme_set_chain_frames_device_bgr")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = bgr_store(c)) return rc;
-    FrameRun run{};
-    for (int i = 0; i < count; ++i) run.src[i] = d_frames[i];
-    return enqueue_bgr_run(c, first, count, run, pitch, true);
-}
-
-int bbme_set_chain_frames_host_bgr_async(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch)
-{
-    if (int rc = check_bgr_run(c, first, count, frames, pitch, "bbme_set_chain_frames_host_bgr")) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = bgr_store(c)) return rc;
-    const size_t row = (size_t)3 * c->geom.width;
-    FrameRun run{};
-    for (int i = 0; i < count; ++i) {
-        uint8_t *d = c->bgr + (size_t)(first + i) * c->bgr_stride;
-        c->bgr_set[first + i] = 0;
-        HIP_TRY(hipMemcpy2DAsync(d, row, frames[i], (size_t)pitch, row, (size_t)c->geom.height, hipMemcpyHostToDevice, c->stream));
-        run.src[i] = d;
-    }
-    return enqueue_bgr_run(c, first, count, run, (int)row, false);
-}
-
-int bbme_set_chain_frames_host_bgr(bbme_ctx *c, int first, int count, const uint8_t *const *frames, int pitch)
-{
-    if (int rc = bbme_set_chain_frames_host_bgr_async(c, first, count, frames, pitch)) return rc;
-    HIP_TRY(hipStreamSynchronize(c->stream));        // the caller may re-use its buffers
-    return BBME_OK;
-}
-
 int bbme_level_planes_device(bbme_ctx *c, int level, uint8_t **d1, uint8_t **d2)
 {
     if (int rc = single_pair_only(c, "bbme_level_planes_device")) return rc;
     if (int rc = check_level(c, level)) return rc;
     if (d1) *d1 = c->lv[level].img1.get();
     if (d2) *d2 = c->lv[level].img2;
-    c->mark_pair0();               // the caller fills them in place (pair 0; a chain of one pair: slots 0 and 1)
+    c->slot_set[0] = c->slot_set[1] = 1;    // the caller fills them in place (the one pair's frames are slots 0 and 1 on either kind of context)
     c->memo_block = 0;
     return BBME_OK;
 }
@@ -1613,8 +1486,8 @@ int bbme_set_level_planes_host(bbme_ctx *c, int level, const uint8_t *image1, co
     HIP_TRY(hipMemcpyAsync(L.img1, image1, (size_t)L.width * L.height, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(L.img2, image2, (size_t)L.width * L.height, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    c->mark_pair0();
-    c->clear_bgr(0, 2);                                 // pair 0's frames (a chain of one pair: slots 0 and 1)
+    c->slot_set[0] = c->slot_set[1] = 1;                // the one pair's frames: slots 0 and 1 on either kind of context
+    c->bgr_set[0] = c->bgr_set[1] = 0;
     c->memo_block = 0;
     c->fields_valid = false;
     return BBME_OK;
@@ -2433,8 +2306,8 @@ int bbme_interpolation_stats(bbme_ctx *c, int num, int den, const int *window, u
 // the stored colour of `pair` as the current direction reads it (frame 1, frame 2), or BBME_ERR_STATE
 static int stored_bgr(const bbme_ctx *c, int pair, const char *what, const uint8_t **bgr1, const uint8_t **bgr2)
 {
-    const int s1 = c->bgr_slot(pair, c->direction ? 1 : 0), s2 = c->bgr_slot(pair, c->direction ? 0 : 1);
-    if (c->bgr_set.empty() || !c->bgr_set[s1] || !c->bgr_set[s2])
+    const int s1 = c->slot(pair, c->direction ? 1 : 0), s2 = c->slot(pair, c->direction ? 0 : 1);
+    if (!c->bgr_set[s1] || !c->bgr_set[s2])
         return bbme::fail(BBME_ERR_STATE, "%s: pair %d has no stored colour (set both frames with a *_bgr setter)", what, pair);
     *bgr1 = c->bgr + (size_t)s1 * c->bgr_stride;
     *bgr2 = c->bgr + (size_t)s2 * c->bgr_stride;

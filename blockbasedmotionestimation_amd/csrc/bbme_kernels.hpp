@@ -2397,14 +2397,20 @@ __global__ __launch_bounds__(256) void k_color_image(ColorArgs a)
 }
 
 // =======================================================================================
-// MF::MF on the GPU (motion_framework.cpp:57-61, 86-106): zero border and pyrDown cascade.  Both frames of the pair
-// in one launch (blockIdx.y).  Bandwidth-bound byte work: 16 bytes per thread for the border copy, four output pixels
-// per thread for pyrDown (dword loads, the 5-tap rows as v_dot4_u32_u8 on re-aligned dwords).
+// Frame preparation.  MF::MF on the GPU (motion_framework.cpp:57-61, 86-106): zero border and pyrDown cascade, with the x4
+// up-sampling or the B,G,R -> luma conversion fused into the border pass where the frames come that way.  Bandwidth-bound byte
+// work: 16 bytes per thread for the border copy, four output pixels per thread for pyrDown (dword loads, the 5-tap rows as
+// v_dot4_u32_u8 on re-aligned dwords).
+// The bodies are __device__ functions of one plane.  ONE family of kernels runs them, the *_run kernels: the frames of a SET in
+// one launch per step, blockIdx.y = frame of the set.  A set is {first slot address, count, step}: the two frames of a pair (the
+// pair's image-1 plane, 2, the distance from image 1 to image 2) or a run of a chain context's slots (the first slot, count, one
+// plane stride).  Level 0: frame f is read from run.src[f] (a kernel-argument table: a caller's frames lie anywhere) and written
+// to dst + f * s_dst; the cascade reads and writes planes of the context (src + f * s_src -> dst + f * s_dst).  So a setter costs
+// num_levels launches whatever the number of frames.  The steps are size_t: a pair's is the image-1 planes of a whole batch.
 // =======================================================================================
-struct PlanePair { const uint8_t *src[2]; uint8_t *dst[2]; };
+constexpr int kMaxChainFrames = 65;                    // BBME_MAX_BATCH pairs are one frame more
+struct FrameRun { const uint8_t *src[kMaxChainFrames]; };
 
-// (the bodies are __device__ functions of one plane: k_pad_zero & co. take the two frames of a pair, the *_run kernels
-//  further down the frames of a run -- the same integers either way)
 __device__ __forceinline__ void pad_zero_plane(const uint8_t *src, uint8_t *dst, int width, int height, int pitch,
                                                int pad_x, int pad_y, int pw, int ph)
 {
@@ -2438,10 +2444,10 @@ __device__ __forceinline__ void pad_zero_plane(const uint8_t *src, uint8_t *dst,
     }
 }
 
-__global__ __launch_bounds__(256) void k_pad_zero(PlanePair p, int width, int height, int pitch,
-                                                  int pad_x, int pad_y, int pw, int ph)
+__global__ __launch_bounds__(256) void k_pad_zero_run(FrameRun run, uint8_t *dst, size_t s_dst, int width, int height, int pitch,
+                                                      int pad_x, int pad_y, int pw, int ph)
 {
-    pad_zero_plane(p.src[blockIdx.y], p.dst[blockIdx.y], width, height, pitch, pad_x, pad_y, pw, ph);
+    pad_zero_plane(run.src[blockIdx.y], dst + blockIdx.y * s_dst, width, height, pitch, pad_x, pad_y, pw, ph);
 }
 
 // =======================================================================================
@@ -2450,7 +2456,7 @@ __global__ __launch_bounds__(256) void k_pad_zero(PlanePair p, int width, int he
 // bbme::resize_x4 (bbme_host.cpp), whose coefficients repeat with period 4: phase p of an output coordinate d = 4k + p
 // samples source k - 1 (p = 0, 1) or k (p = 2, 3) with weights (768, 1280), (256, 1792), (1792, 256), (1280, 768).
 // Horizontally a first column outside the source resets them to (2048, 0) (output columns 0, 1, 4W-2, 4W-1);
-// vertically only the row index is clamped.  Both frames per launch (blockIdx.y), 16 output bytes per thread, the
+// vertically only the row index is clamped.  16 output bytes per thread, the
 // source bytes a thread needs (at most 7 per row) held in one 64-bit word per row.  sw, sh: source size; pw, ph: plane.
 // =======================================================================================
 __device__ __forceinline__ int resize_x4_w0(int phase)      // weight of the first tap; the second is 2048 minus it
@@ -2509,10 +2515,10 @@ __device__ __forceinline__ void resize_x4_pad_plane(const uint8_t *src, uint8_t 
     }
 }
 
-__global__ __launch_bounds__(256) void k_resize_x4_pad(PlanePair p, int sw, int sh, int pitch,
-                                                       int pad_x, int pad_y, int pw, int ph)
+__global__ __launch_bounds__(256) void k_resize_x4_pad_run(FrameRun run, uint8_t *dst, size_t s_dst, int sw, int sh, int pitch,
+                                                           int pad_x, int pad_y, int pw, int ph)
 {
-    resize_x4_pad_plane(p.src[blockIdx.y], p.dst[blockIdx.y], sw, sh, pitch, pad_x, pad_y, pw, ph);
+    resize_x4_pad_plane(run.src[blockIdx.y], dst + blockIdx.y * s_dst, sw, sh, pitch, pad_x, pad_y, pw, ph);
 }
 
 __device__ __forceinline__ int mirror101(int p, int n)
@@ -2564,36 +2570,9 @@ __device__ __forceinline__ void pyr_down4_plane(const uint8_t *src, uint8_t *dst
     *reinterpret_cast<uint32_t *>(dst + (size_t)y * dw + 4 * k) = out;
 }
 
-__global__ __launch_bounds__(256) void k_pyr_down4(PlanePair p, int sw, int sh)
+__global__ __launch_bounds__(256) void k_pyr_down4_run(const uint8_t *src, size_t s_src, uint8_t *dst, size_t s_dst, int sw, int sh)
 {
-    pyr_down4_plane(p.src[blockIdx.y], p.dst[blockIdx.y], sw, sh);
-}
-
-// =======================================================================================
-// Frame preparation of a chain context (bbme_create_chain): the frames of a RUN in one launch per step, blockIdx.y = frame
-// of the run.  Level 0: frame f is read from run.src[f] (a kernel-argument table: the frames of a video lie anywhere) and
-// written to dst + f * s_dst, the slots of the context lying one plane stride apart; the cascade reads and writes slots
-// (src + f * s_src -> dst + f * s_dst).  So a round costs num_levels launches whatever the number of frames.  Per plane the
-// bodies above, unchanged.
-// =======================================================================================
-constexpr int kMaxChainFrames = 65;                    // BBME_MAX_BATCH pairs are one frame more
-struct FrameRun { const uint8_t *src[kMaxChainFrames]; };
-
-__global__ __launch_bounds__(256) void k_pad_zero_run(FrameRun run, uint8_t *dst, uint32_t s_dst, int width, int height, int pitch,
-                                                      int pad_x, int pad_y, int pw, int ph)
-{
-    pad_zero_plane(run.src[blockIdx.y], dst + (size_t)blockIdx.y * s_dst, width, height, pitch, pad_x, pad_y, pw, ph);
-}
-
-__global__ __launch_bounds__(256) void k_resize_x4_pad_run(FrameRun run, uint8_t *dst, uint32_t s_dst, int sw, int sh, int pitch,
-                                                           int pad_x, int pad_y, int pw, int ph)
-{
-    resize_x4_pad_plane(run.src[blockIdx.y], dst + (size_t)blockIdx.y * s_dst, sw, sh, pitch, pad_x, pad_y, pw, ph);
-}
-
-__global__ __launch_bounds__(256) void k_pyr_down4_run(const uint8_t *src, uint32_t s_src, uint8_t *dst, uint32_t s_dst, int sw, int sh)
-{
-    pyr_down4_plane(src + (size_t)blockIdx.y * s_src, dst + (size_t)blockIdx.y * s_dst, sw, sh);
+    pyr_down4_plane(src + blockIdx.y * s_src, dst + blockIdx.y * s_dst, sw, sh);
 }
 
 // bbme_chain_advance: the last slot of every level becomes slot 0, all levels in one launch (blockIdx.y = level).  Whole
@@ -2614,10 +2593,9 @@ __global__ __launch_bounds__(256) void k_chain_roll(ChainRoll r)
 // a thread makes 16 bytes of a plane row from the 48 source bytes under them (three unaligned 16-byte loads inside the frame,
 // bytes at its edges).  With `keep` it also writes those 48 bytes to the packed copy (pitch 3 width) the context keeps of a
 // caller's frame: every pixel of the frame lies under exactly one thread.  Bandwidth-bound like the grey border copy, on four
-// (with keep, seven) bytes per pixel instead of two.  k_bgr_pad: the two frames of a pair (blockIdx.y); k_bgr_pad_run: the
-// frames of a chain run (run.src[f] -> slot f of dst and of keep).
+// (with keep, seven) bytes per pixel instead of two.  k_bgr_pad_run: the frames of a set, as the kernels of the frame
+// preparation above (run.src[f] -> frame f of dst and of keep).
 // =======================================================================================
-struct BgrPair { const uint8_t *src[2]; uint8_t *dst[2]; uint8_t *keep[2]; };
 
 __device__ __forceinline__ uint32_t bgr_luma(uint32_t b, uint32_t g, uint32_t r)
 {
@@ -2671,16 +2649,11 @@ __device__ __forceinline__ void bgr_pad_plane(const uint8_t *src, uint8_t *dst, 
     }
 }
 
-__global__ __launch_bounds__(256) void k_bgr_pad(BgrPair p, int width, int height, int pitch, int pad_x, int pad_y, int pw, int ph)
-{
-    bgr_pad_plane(p.src[blockIdx.y], p.dst[blockIdx.y], p.keep[blockIdx.y], width, height, pitch, pad_x, pad_y, pw, ph);
-}
-
-// keep: slot `first` of the colour store (slots s_keep bytes apart), or null
-__global__ __launch_bounds__(256) void k_bgr_pad_run(FrameRun run, uint8_t *dst, uint32_t s_dst, uint8_t *keep, size_t s_keep,
+// keep: the set's first slot of the colour store (its frames s_keep bytes apart), or null
+__global__ __launch_bounds__(256) void k_bgr_pad_run(FrameRun run, uint8_t *dst, size_t s_dst, uint8_t *keep, size_t s_keep,
                                                      int width, int height, int pitch, int pad_x, int pad_y, int pw, int ph)
 {
-    bgr_pad_plane(run.src[blockIdx.y], dst + (size_t)blockIdx.y * s_dst, keep ? keep + blockIdx.y * s_keep : nullptr, width, height,
+    bgr_pad_plane(run.src[blockIdx.y], dst + blockIdx.y * s_dst, keep ? keep + blockIdx.y * s_keep : nullptr, width, height,
                   pitch, pad_x, pad_y, pw, ph);
 }
 

@@ -191,8 +191,9 @@ int bbme_set_frames_host_x4_async(bbme_ctx *ctx, int pair, const uint8_t *image1
 int bbme_set_frames_device_x4(bbme_ctx *ctx, int pair, const uint8_t *d_image1, const uint8_t *d_image2, int pitch);
 /* A CHAIN context: `pairs` (1..BBME_MAX_BATCH) CONSECUTIVE pairs of a video over pairs + 1 frame slots, pair p = (slot p,
  * slot p + 1).  A video f0, f1, ... has the pairs (f0, f1), (f1, f2), ...: every inner frame is image 2 of one pair and image 1
- * of the next, and a batched context uploads it, pads it and runs it through the pyrDown cascade twice.  Here every level holds
- * its pairs + 1 planes one plane stride apart in ONE allocation, image1 = its start and image2 = one stride further, so a frame
+ * of the next, and a batched context uploads it, pads it and runs it through the pyrDown cascade twice.  Every context keeps a
+ * level's planes one plane stride apart in one allocation, image1 = its start; a batched context holds its pairs' image-1 planes
+ * and, behind them, their image-2 planes, a chain context holds pairs + 1 planes with image2 = one stride further, so a frame
  * is set once and pair p reads slots p and p + 1 -- the kernels of bbme_estimate address pairs by that stride anyway and are
  * untouched.  Validation, errors and everything not named below (streams, modes, speculation / relaxation switches, *_pair
  * getters, bbme_subsampled_flow_device, bbme_compensation_error, the knobs) as bbme_create_batch with `pairs` pairs;
@@ -522,9 +523,10 @@ int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int widt
  * bbme_bgr_to_gray_host: the rule on the CPU, no GPU; `gray` is packed width x height.
  * The *_bgr frame setters below are, plane by plane and bit for bit, the grey setter of the same name on that luma -- the level-0
  * planes are pad_zero(Y), deeper levels its pyrDown cascade -- from ONE kernel that converts and writes the zero border, and they
- * keep the colour: a context holds one packed (pitch 3 W) B,G,R copy per frame, 2 per pair, or one per slot on a chain context, in
- * a COLOUR STORE allocated by the first colour setter.  Host setters upload straight into the store (the frame crosses PCIe once)
- * and convert from there; device setters read the caller's frames on the ctx stream and copy them into the store in the same pass.
+ * keep the colour: a context holds one packed (pitch 3 W) B,G,R copy per frame it holds (the two of every pair, or the slots of
+ * a chain context: bbme_bgr_frames_device_pair tells where a pair's lie), in a COLOUR STORE allocated by the first colour setter.
+ * Host setters upload straight into the store (the frame crosses PCIe once) and convert from there; device setters read the
+ * caller's frames on the ctx stream and copy them into the store in the same pass.
  * A frame HAS COLOUR from a *_bgr setter until a grey setter of that frame (bbme_set_frames_*, the _x4 forms,
  * bbme_set_chain_frames_* on its slot, bbme_set_level_planes_host): the stored colour then is not what the luma plane was made
  * from, and the calls that read stored colour return BBME_ERR_STATE.  bbme_chain_advance moves the last slot's colour with its

@@ -1,8 +1,8 @@
 """Colour video (the luma rule and the BGR interpolation rule of include/bbme.h) at the size a user runs, on the cfg3 4K pair
 made colour (three pointwise maps of the grey frames) and after its bidirectional estimate:
 
-  p   grey frames in HBM -> planes + pyramid       bbme_set_frames_device_pair   (k_pad_zero, the grey route's border copy)
-  q   colour frames in HBM -> planes + pyramid     bbme_set_frames_device_bgr    (k_bgr_pad: convert + border + the kept copy)
+  p   grey frames in HBM -> planes + pyramid       bbme_set_frames_device_pair   (k_pad_zero_run, the grey route's border copy)
+  q   colour frames in HBM -> planes + pyramid     bbme_set_frames_device_bgr    (k_bgr_pad_run: convert + border + the kept copy)
   a   grey, one phase, 1 / 2                       bbme_interpolate_device       (k_interpolate)
   b   grey, a run of 3 phases, 1 / 4 .. 3 / 4      bbme_interpolate_device, one launch
   A   colour, one phase, 1 / 2                     bbme_interpolate_bgr_device   (k_interpolate_bgr)
@@ -34,7 +34,7 @@ W, H, SEARCH, BLOCK, LEVELS = 3840, 2160, 80, 16, 4       # bench.py's cfg3
 REF_GBS = 3800.0                                           # what k_fb_consistency reached
 WARMUP = 10
 # name, what the case does, the kernel it is about, phases per launch
-CASES = [("p", "grey frames in", "k_pad_zero", 0), ("q", "colour frames in", "k_bgr_pad", 0),
+CASES = [("p", "grey frames in", "k_pad_zero_run", 0), ("q", "colour frames in", "k_bgr_pad_run", 0),
          ("a", "grey, 1 phase", "k_interpolate", 1), ("b", "grey, 3 phases", "k_interpolate", 3),
          ("A", "colour, 1 phase", "k_interpolate_bgr", 1), ("B", "colour, 3 phases", "k_interpolate_bgr", 3)]
 
@@ -142,7 +142,7 @@ def report(trace_dir, reps):
     rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r["Start_Timestamp"]))
 
     def family(name):
-        for k in ("k_interpolate_bgr", "k_interpolate", "k_bgr_pad_run", "k_bgr_pad", "k_pad_zero_run", "k_pad_zero"):
+        for k in ("k_interpolate_bgr", "k_interpolate", "k_bgr_pad_run", "k_pad_zero_run"):
             if k in name:
                 return k
         return None
@@ -153,12 +153,12 @@ def report(trace_dir, reps):
     from blockbasedmotionestimation_amd.motion_framework import plan_padding
     pw, ph, _, _ = plan_padding(W, H, [SEARCH] * LEVELS, [BLOCK] * LEVELS)
     n = WARMUP + reps
-    # the constructor's host setter is the first k_bgr_pad dispatch; a family's cases follow one another
+    # the constructor's host setter is the first k_bgr_pad_run dispatch; a family's cases follow one another
     first = {"p": 0, "q": 1, "a": 0, "b": n, "A": 0, "B": n}
     print("kernel times from %s (run with --host-reps 0)" % os.path.relpath(f, trace_dir))
     for name, what, kernel, phases in CASES:
         d = dur.get(kernel, [])
-        expected = {"k_pad_zero": n, "k_bgr_pad": n + 1}.get(kernel, 2 * n)
+        expected = {"k_pad_zero_run": n, "k_bgr_pad_run": n + 1}.get(kernel, 2 * n)
         if len(d) != expected:
             raise SystemExit("%d %s dispatches, %d expected: the trace does not hold the probe's sequence" % (len(d), kernel, expected))
         timed = d[first[name] + WARMUP:first[name] + n]

@@ -230,8 +230,8 @@ def run_trace(name, shape, rounds, device):
         forms.check_round(r, name)
     forms.close()
     # creation: MFBatch sets P pairs, MFChain one run; then `rounds` rounds of each
-    n = {"k_pad_zero": contexts * pairs * (1 + rounds), "k_pyr_down4": contexts * pairs * (1 + rounds) * (levels - 1),
-         "k_pad_zero_run": contexts * (1 + rounds), "k_pyr_down4_run": contexts * (1 + rounds) * (levels - 1),
+    # (one launch per setter and level: P pair setters of the batched form, one run setter of the chain)
+    n = {"k_pad_zero_run": contexts * (pairs + 1) * (1 + rounds), "k_pyr_down4_run": contexts * (pairs + 1) * (1 + rounds) * (levels - 1),
          "k_chain_roll": contexts * rounds}
     print("%s: %d contexts x %d pairs, %d levels, %d rounds of each form after the contexts' first frames" %
           (name, contexts, pairs, levels, rounds))

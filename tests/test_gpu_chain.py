@@ -409,7 +409,7 @@ def test_refusals(bbme):
 
 
 def test_a_chain_of_64_pairs_has_65_slots(bbme):
-    """frames_mask is one 64-bit word; 64 pairs are 65 slots."""
+    """64 pairs are 65 frame slots: one more than a 64-bit word of flags would hold."""
     from blockbasedmotionestimation_amd import _capi
     lib = _capi.lib()
     search, block = [30, 30], [16, 16]

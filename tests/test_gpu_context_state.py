@@ -460,3 +460,132 @@ def test_set_stream_between_graph_replays(bbme, oracle, monkeypatch):
     mf.set_frames(seq[3][1], seq[3][2])
     _assert_same(mf.calcMotionBlockMatching(), seq[3][4], "back on an own stream")
     mf.close()
+
+
+# ---- F. the pair setters on a batch: one slot numbering for the planes, the upload buffer and the colour store ----------
+# 48 x 40 frames are padded to 64 x 64 / 32 x 32: at both levels the image-2 planes of three pairs start where no multiple of
+# the plane stride lies, and the planes, the upload buffer and the colour store each keep frame `which` of pair p in slot
+# which * 3 + p.  A wrong step or slot number puts a frame of pair 1 into a plane of pair 0 or 2, or takes it from theirs.
+SMALL = ([30, 30], [16, 16])
+PAIR_SETTERS = ["grey_host", "grey_device", "x4_host", "x4_device", "bgr_host", "bgr_device"]
+SHIFTS = {"x4": [(1, -1), (-1, 1), (1, 1), (0, -1)]}        # source pixels: four times as far in the frame
+SHIFTS["grey"] = SHIFTS["bgr"] = [(3, -2), (-1, 4), (2, 2), (-3, -1)]
+
+
+def _small_pair(fmt, i):
+    """Content i of a format: noise and the same noise moved by SHIFTS[fmt][i]; x4: sources of a quarter of the frame; bgr:
+    three pointwise maps of the grey pair."""
+    w, h = (12, 10) if fmt == "x4" else (48, 40)
+    f1 = np.random.default_rng(5200 + i).integers(0, 256, (h, w), dtype=np.uint8)
+    f2 = np.roll(f1, SHIFTS[fmt][i], axis=(0, 1))
+    if fmt == "bgr":
+        f1, f2 = (np.stack([v, 255 - v, (v.astype(np.int32) * 3 // 4 + 30).astype(np.uint8)], -1) for v in (f1, f2))
+    return np.ascontiguousarray(f1), np.ascontiguousarray(f2)
+
+
+def _call_pair_setter(lib, ctx, kind, pair, f1, f2, alive):
+    """The C-ABI pair setter of `kind` on packed host frames, or on frames in HBM whose rows are 13 bytes further apart."""
+    import torch
+    from blockbasedmotionestimation_amd import _capi
+    fmt, where = kind.split("_")
+    setter = getattr(lib, {"grey": "bbme_set_frames_%s_pair", "x4": "bbme_set_frames_%s_x4", "bgr": "bbme_set_frames_%s_bgr"}[fmt] % where)
+    h, row = f1.shape[0], f1[0].size
+    if where == "host":
+        _capi.check(setter(ctx, pair, f1.ctypes.data, f2.ctypes.data, row))
+        return
+    wide = torch.full((2, h, row + 13), 0xAA, dtype=torch.uint8, device="cuda")
+    wide[0, :, :row] = torch.from_numpy(f1.reshape(h, row)).cuda()
+    wide[1, :, :row] = torch.from_numpy(f2.reshape(h, row)).cuda()
+    torch.cuda.synchronize()
+    _capi.check(setter(ctx, pair, wide[0].data_ptr(), wide[1].data_ptr(), row + 13))
+    alive.append(wide)                                     # until the context's stream has read it
+
+
+def _stored_colour(mf, pair, shape):
+    """The two frames the colour store holds for `pair` (packed, pitch 3 W)."""
+    mf.synchronize()
+    out = []
+    for ptr in mf.bgr_frames_device_ptrs(pair):
+        buf = np.empty(shape, np.uint8)
+        assert _hip().hipMemcpy(buf.ctypes.data, ptr, buf.nbytes, 2) == 0
+        out.append(buf)
+    return out
+
+
+@pytest.mark.parametrize("kind", PAIR_SETTERS)
+def test_resetting_one_pair_of_a_batch_through_every_pair_setter(bbme, kind):
+    """A batch of three pairs, every pair set through the setter under test, then pair 1 alone set again to other content: the
+    cells of pairs 0 and 2 stay what they were, every pair's cells are those of a single context on the same frames, and the
+    colour store holds every pair's frames in its own slots."""
+    from blockbasedmotionestimation_amd import _capi
+    lib = _capi.lib()
+    fmt = kind.split("_")[0]
+    up = 4 if fmt == "x4" else 1
+    search, block = SMALL
+    content = [_small_pair(fmt, i) for i in range(4)]          # pairs 0, 1, 2, and what pair 1 is set to again
+    singles = []
+    for f1, f2 in content:
+        mf = bbme.MF(f1, f2, search, block, upsample=up)
+        mf.estimate_async()
+        singles.append(mf.get_cells())
+        mf.close()
+    assert all(not np.array_equal(singles[i], singles[j]) for i in range(4) for j in range(i))     # the test can tell them apart
+    z = np.zeros(content[0][0].shape[:2], np.uint8)
+    mb = bbme.MFBatch([(z, z)] * 3, search, block, upsample=up)
+    assert (mb.padded_width, mb.padded_height) == (64, 64)
+    alive = []
+    for p in range(3):
+        _call_pair_setter(lib, mb._ctx, kind, p, *content[p], alive)
+    mb.estimate_async()
+    before = [mb.get_pair_cells(p) for p in range(3)]
+    for p in range(3):
+        assert np.array_equal(before[p], singles[p]), "pair %d" % p
+        if fmt == "bgr":
+            assert all(np.array_equal(a, b) for a, b in zip(_stored_colour(mb, p, content[p][0].shape), content[p])), "colour of pair %d" % p
+    _call_pair_setter(lib, mb._ctx, kind, 1, *content[3], alive)
+    mb.estimate_async()
+    for p, exp in enumerate((singles[0], singles[3], singles[2])):
+        assert np.array_equal(mb.get_pair_cells(p), exp), "pair %d after pair 1 was set again" % p
+    assert np.array_equal(mb.get_pair_cells(0), before[0]) and np.array_equal(mb.get_pair_cells(2), before[2])
+    if fmt == "bgr":
+        now = (content[0], content[3], content[2])
+        for p in range(3):
+            assert all(np.array_equal(a, b) for a, b in zip(_stored_colour(mb, p, now[p][0].shape), now[p])), "colour of pair %d" % p
+        # a grey setter of pair 1 withdraws the colour of pair 1 only
+        mb.set_pair(1, content[1][0][..., 0], content[1][1][..., 0])
+        with pytest.raises(bbme.BbmeError) as e:
+            mb.bgr_frames_device_ptrs(1)
+        assert e.value.status == _capi.ERR_STATE
+        for p in (0, 2):
+            assert all(np.array_equal(a, b) for a, b in zip(_stored_colour(mb, p, now[p][0].shape), now[p])), "colour of pair %d" % p
+    mb.close()
+
+
+def test_a_batch_of_64_pairs_set_last_pair_first(bbme):
+    """BBME_MAX_BATCH pairs are 128 frame slots, one flag each (where a 64-bit word of pairs used to end): pair 63 set first and
+    pair 0 last, an estimate refused until every pair has frames.  8 x 8 frames in two levels of 2 x 2 blocks, +-1: the narrowest
+    levels a context takes (test_gpu_parity).  The chain's counterpart is test_gpu_chain.test_a_chain_of_64_pairs_has_65_slots."""
+    from blockbasedmotionestimation_amd import _capi
+    lib = _capi.lib()
+    w, h, search, block = 8, 8, [4, 4], [2, 2]
+    rng = np.random.default_rng(5300)
+    pairs = []
+    for p in range(64):
+        f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+        pairs.append((f1, np.ascontiguousarray(np.roll(f1, (p % 3 - 1, p // 3 % 3 - 1), axis=(0, 1)))))
+    params = _capi.make_params(search, block)
+    ctx = C.c_void_p()
+    assert lib.bbme_create_batch(C.byref(params), w, h, 0, 65, C.byref(ctx)) == _capi.ERR_INVALID
+    _capi.check(lib.bbme_create_batch(C.byref(params), w, h, 0, 64, C.byref(ctx)))
+    for p in [63] + list(range(1, 63)) + [0]:
+        assert lib.bbme_estimate(ctx) == _capi.ERR_STATE, "before pair %d is set" % p
+        _capi.check(lib.bbme_set_frames_host_pair(ctx, p, pairs[p][0].ctypes.data, pairs[p][1].ctypes.data, w))
+    _capi.check(lib.bbme_estimate(ctx))
+    for p in (0, 31, 63):
+        got = np.empty((h // 2, w // 2, 2), np.int16)
+        _capi.check(lib.bbme_get_cells_host_pair(ctx, p, got.ctypes.data))
+        mf = bbme.MF(pairs[p][0], pairs[p][1], search, block)
+        mf.estimate_async()
+        assert np.array_equal(got, mf.get_cells()), "pair %d" % p
+        mf.close()
+    _capi.check(lib.bbme_destroy(ctx))

@@ -1,4 +1,4 @@
-"""The reference's x4 pipeline on the GPU (main_class.cpp:32-33, 58-70): original frames in (k_resize_x4_pad writes the
+"""The reference's x4 pipeline on the GPU (main_class.cpp:32-33, 58-70): original frames in (k_resize_x4_pad_run writes the
 level-0 planes), the subsampled field out (k_subsample reads the 2x2-cell grid).  Everything must be byte for byte what the
 host pipeline resize_x4 -> MF -> get_flow -> subsample_div4 gives.
 
