@@ -301,6 +301,9 @@ struct bbme_ctx {
     size_t bgr_stride = 0;
     std::vector<uint8_t> bgr_set;
     DevBuf<uint8_t> ip_bgr;                       // bbme_get_interpolated_bgr_host: a packed 3 W x H frame before its download
+    DevBuf<uint8_t> tf_plane;                     // bbme_get_temporal_filtered_host: a packed W0 x H0 frame before its download
+    DevBuf<unsigned long long> tf_stats;          // temporal filter statistics: 4 words per frame, then the partials of k_temporal_filter
+                                                  // of bbme_temporal_filter_stats (every frame) and of bbme_cells_temporal_filter_device (one)
 };
 
 namespace {
@@ -2426,6 +2429,232 @@ int bbme_get_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int den, uint
     if (int rc = enqueue_own_ip_bgr(c, pair, num, 1, den, c->ip_bgr, 3 * c->geom.width, 0, c->stream, what)) return rc;
     HIP_TRY(hipMemcpyAsync(out, c->ip_bgr, bytes, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
+}
+
+// ---- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rule of include/bbme.h; k_temporal_filter) --
+
+constexpr int kTfMaxFrames = 2 * BBME_MAX_BATCH;          // a batch holds 2 batch frames, a chain batch + 1
+
+static long long tf_groups(const Level &L0)
+{
+    return ((long long)(L0.width / 2 + 3) / 4 * (L0.height / 2) + 256 * kTfRunsPerLane - 1) / (256 * kTfRunsPerLane);
+}
+
+// the result words of every frame, then the partials of a launch over every frame, then those of a one-frame launch: one size
+// per context, so it is never replaced under a launch that reads it
+static int tf_scratch(bbme_ctx *c)
+{
+    return c->tf_stats.ensure((size_t)4 * (kTfMaxFrames + tf_groups(c->lv[0]) * (c->frames() + 1)), "the temporal filter statistics");
+}
+
+static int check_tf(const bbme_ctx *c, int thr, const int *window, const char *what)
+{
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    return check_window(window, c->lv[0].width / 2, c->lv[0].height / 2, what, -1);
+}
+
+static int check_tf_state(const bbme_ctx *c, const char *what)
+{
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
+    return BBME_OK;
+}
+
+// geometry, strength and the magics of both divisions
+static TfArgs tf_args(const bbme_ctx *c, int thr, const int *window)
+{
+    const Level &L = c->lv[0];
+    TfArgs a{};
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2; a.ch = L.height / 2;
+    a.thr = thr;
+    a.magic_thr = thr > 1 ? (uint32_t)((1ull << 32) / (unsigned)thr + 1ull) : 0u;      // thr = 1: k_temporal_filter does not divide
+    for (int S = 8; S <= 24; ++S) a.magic_s[S - 8] = (uint32_t)((1ull << 32) / (unsigned)S + 1ull);
+    set_window(a, window, a.cw, a.ch);
+    a.runs_per_row = (a.cw + 3) / 4;
+    a.runs = (long long)a.runs_per_row * a.ch;
+    return a;
+}
+
+// k_temporal_filter over `pairs` x `count` frames (blockIdx.y, blockIdx.z) and, with d_stats, k_mc_reduce of the partials into
+// d_stats[4 (y count + z) ..]
+static int enqueue_tf(bbme_ctx *c, TfArgs &a, int pairs, int count, unsigned long long *partial, unsigned long long *d_stats,
+                      hipStream_t stream)
+{
+    a.partial = d_stats ? partial : nullptr;
+    const long long groups = tf_groups(c->lv[0]);
+    hipLaunchKernelGGL(k_temporal_filter, dim3((unsigned)groups, (unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
+    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)(pairs * count)), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+// The context's own frames as k_temporal_filter addresses them.  Chain: slots first .. first + count - 1 along z, neighbours one
+// plane_stride to either side, into-previous = backward cells of pair slot - 1, into-next = forward cells of pair slot.  Pair or
+// batch: image 1 and image 2 of pairs pair0 .. along z = which (from which0 on), image 1 with its next neighbour only and image 2
+// with its previous one.  A base that a launch never dereferences (the first slot's previous frame, ...) is address arithmetic only.
+static TfArgs tf_own_frames(const bbme_ctx *c, int thr, const int *window, int pair0, int first, int count)
+{
+    const Level &L = c->lv[0];
+    TfArgs a = tf_args(c, thr, window);
+    const long long ps = L.plane_stride, s_f = L.grid_stride(L.final_grid()), s_b = c->bwd_stride;
+    const uintptr_t img = reinterpret_cast<uintptr_t>(L.img1.get()), f = reinterpret_cast<uintptr_t>(L.final_grid()),
+                    b = reinterpret_cast<uintptr_t>(c->bwd_cells.get());
+    if (c->chain) {                                       // `first` is a slot
+        a.cur = reinterpret_cast<const uint8_t *>(img + first * ps);
+        a.prev = reinterpret_cast<const uint8_t *>(img + (first - 1) * ps);
+        a.next = reinterpret_cast<const uint8_t *>(img + (first + 1) * ps);
+        a.gp = reinterpret_cast<const mv_t *>(b + (first - 1) * s_b * (long long)sizeof(mv_t));
+        a.gn = reinterpret_cast<const mv_t *>(f + first * s_f * (long long)sizeof(mv_t));
+        a.cur_z = a.prev_z = a.next_z = ps;
+        a.gp_z = s_b; a.gn_z = s_f;
+        a.first_prev = first > 0;
+        a.last_next = first + count - 1 < c->batch;
+    } else {                                              // `first` is which
+        const long long step = (long long)L.frame_step;
+        a.cur = reinterpret_cast<const uint8_t *>(img + pair0 * ps + first * step);
+        a.prev = reinterpret_cast<const uint8_t *>(img + pair0 * ps + (first - 1) * step);
+        a.next = reinterpret_cast<const uint8_t *>(img + pair0 * ps + (first + 1) * step);
+        a.gp = reinterpret_cast<const mv_t *>(b + pair0 * s_b * (long long)sizeof(mv_t));
+        a.gn = reinterpret_cast<const mv_t *>(f + pair0 * s_f * (long long)sizeof(mv_t));
+        a.cur_y = a.prev_y = a.next_y = ps;
+        a.cur_z = a.prev_z = a.next_z = step;
+        a.gp_y = s_b; a.gn_y = s_f;
+        a.first_prev = first > 0;                         // image 2 has image 1 behind it
+        a.last_next = first + count - 1 < 1;              // image 1 has image 2 ahead
+    }
+    return a;
+}
+
+int bbme_cells_temporal_filter_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                      const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window, uint8_t *d_out,
+                                      int out_pitch, uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4,
+                                      void *hip_stream)
+{
+    const char *what = "bbme_cells_temporal_filter_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_cur || (!d_out && !d_weights && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if ((d_prev == nullptr) != (d_to_prev == nullptr) || (d_next == nullptr) != (d_to_next == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its plane and its grid", what);
+    if (!d_prev && !d_next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if (d_out && out_pitch < L.width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d", what, out_pitch, L.width);
+    if (d_weights && weights_pitch < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: weight map pitch %d < %d cells per row", what, weights_pitch, L.width / 2);
+    // the frame is written while other lanes still gather from the planes: an output inside an input plane is a race, not a result
+    if (d_out) {
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (size_t)out_pitch * (L.height - 1) + L.width;
+        for (const uint8_t *in : {d_prev, d_cur, d_next}) {
+            const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (size_t)L.width * L.height;
+            if (in && o0 < i1 && i0 < o1) return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input plane", what);
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = tf_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    TfArgs a = tf_args(c, thr, window);
+    a.cur = d_cur; a.prev = d_prev; a.next = d_next;
+    a.gp = reinterpret_cast<const mv_t *>(d_to_prev); a.gn = reinterpret_cast<const mv_t *>(d_to_next);
+    a.first_prev = a.last_next = 1;
+    a.out = d_out; a.out_pitch = out_pitch;
+    a.wmap = d_weights; a.wmap_pitch = weights_pitch;
+    unsigned long long *partial = d_stats4 ? c->tf_stats + (size_t)4 * (kTfMaxFrames + tf_groups(L) * c->frames()) : nullptr;
+    return enqueue_tf(c, a, 1, 1, partial, d_stats4, stream);
+}
+
+// frame `which` of `pair` of the context's own, into d_out on `stream`
+static int enqueue_own_tf(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, hipStream_t stream)
+{
+    TfArgs a = c->chain ? tf_own_frames(c, thr, nullptr, 0, pair + which, 1) : tf_own_frames(c, thr, nullptr, pair, which, 1);
+    a.out = d_out; a.out_pitch = out_pitch;
+    return enqueue_tf(c, a, 1, 1, nullptr, nullptr, stream);
+}
+
+static int check_tf_frame(const bbme_ctx *c, int pair, int which, int thr, const char *what)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (which != 0 && which != 1) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    return check_tf(c, thr, nullptr, what);
+}
+
+int bbme_temporal_filter_device(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    const char *what = "bbme_temporal_filter_device";
+    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (out_pitch < c->lv[0].width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d", what, out_pitch, c->lv[0].width);
+    if (int rc = check_tf_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_tf(c, pair, which, thr, d_out, out_pitch, stream);
+}
+
+int bbme_temporal_filter_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
+                                      void *hip_stream)
+{
+    const char *what = "bbme_temporal_filter_chain_device";
+    if (int rc = chain_context_only(c, what)) return rc;
+    const Level &L = c->lv[0];
+    if (first < 0 || count < 1 || (long long)first + count > c->batch + 1)
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside 0 .. %d", what, first, first, count, c->batch);
+    if (int rc = check_tf(c, thr, nullptr, what)) return rc;
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (out_pitch < L.width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d", what, out_pitch, L.width);
+    if (count > 1 && out_stride < (size_t)out_pitch * L.height)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output stride %zu < one frame of %d rows of %d bytes", what, out_stride, L.height, out_pitch);
+    if (int rc = check_tf_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    TfArgs a = tf_own_frames(c, thr, nullptr, 0, first, count);
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    return enqueue_tf(c, a, 1, count, nullptr, nullptr, stream);
+}
+
+int bbme_get_temporal_filtered_host(bbme_ctx *c, int pair, int which, int thr, uint8_t *out)
+{
+    const char *what = "bbme_get_temporal_filtered_host";
+    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_tf_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[0];
+    const size_t bytes = (size_t)L.width * L.height;
+    if (int rc = c->tf_plane.ensure(bytes, "the filtered frame")) return rc;
+    if (int rc = enqueue_own_tf(c, pair, which, thr, c->tf_plane, L.width, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->tf_plane, bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_temporal_filter_stats";
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_tf_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = tf_scratch(c)) return rc;
+    // chain: one pair row, every slot along z; otherwise every pair along y, which along z: frame y gridDim.z + z either way
+    const int pairs = c->chain ? 1 : c->batch, count = c->chain ? c->batch + 1 : 2;
+    TfArgs a = tf_own_frames(c, thr, window, 0, 0, count);
+    if (int rc = enqueue_tf(c, a, pairs, count, c->tf_stats + (size_t)4 * kTfMaxFrames, c->tf_stats, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(stats, c->tf_stats, (size_t)4 * sizeof(unsigned long long) * c->frames(), hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_frame_plane_device(bbme_ctx *c, int pair, int which, int level, const uint8_t **d_plane)
+{
+    const char *what = "bbme_frame_plane_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_level(c, level)) return rc;
+    if (which != 0 && which != 1) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    if (!d_plane) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const Level &L = c->lv[level];
+    *d_plane = L.img1 + (size_t)pair * L.plane_stride + (size_t)which * L.frame_step;
+    return BBME_OK;
 }
 
 int bbme_stage_search(bbme_ctx *c, int level)

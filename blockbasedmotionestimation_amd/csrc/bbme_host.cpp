@@ -743,6 +743,65 @@ int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int widt
     return BBME_OK;
 }
 
+// The temporal filter rule of include/bbme.h, cell by cell, in the header's own words (the mirror of k_temporal_filter).
+int bbme_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height,
+                              const int16_t *to_prev, const int16_t *to_next, int thr, const int *window, uint8_t *out,
+                              uint8_t *weights, unsigned long long *stats4)
+{
+    const char *what = "bbme_temporal_filter_host";
+    if (!cur || (!out && !weights && !stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if ((prev == nullptr) != (to_prev == nullptr) || (next == nullptr) != (to_next == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its plane and its grid", what);
+    if (!prev && !next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    const int cw = width / 2, ch = height / 2;
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
+        return bbme::fail(BBME_ERR_INVALID, "%s: window not inside the %dx%d cells", what, cw, ch);
+    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
+    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
+    const uint8_t *planes[2] = {prev, next};
+    const int16_t *grids[2] = {to_prev, to_next};
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            int w[2] = {0, 0}, px[2] = {0, 0}, py[2] = {0, 0};
+            for (int k = 0; k < 2; ++k) {
+                if (!planes[k]) continue;
+                px[k] = ox + grids[k][2 * c];
+                py[k] = oy + grids[k][2 * c + 1];
+                if (px[k] < 0 || py[k] < 0 || px[k] > width - 2 || py[k] > height - 2) continue;
+                int cost = 0;
+                for (int i = 0; i < 2; ++i)
+                    for (int j = 0; j < 2; ++j)
+                        cost += abs((int)cur[(size_t)(oy + i) * width + ox + j] - (int)planes[k][(size_t)(py[k] + i) * width + px[k] + j]);
+                if (cost < thr) w[k] = 8 * (thr - cost) / thr;
+            }
+            const int S = 8 + w[0] + w[1];
+            unsigned diff = 0;
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j) {
+                    const int cpx = cur[(size_t)(oy + i) * width + ox + j];
+                    int acc = 8 * cpx + S / 2;
+                    for (int k = 0; k < 2; ++k)
+                        if (w[k]) acc += w[k] * planes[k][(size_t)(py[k] + i) * width + px[k] + j];
+                    const int v = acc / S;
+                    if (out) out[(size_t)(oy + i) * width + ox + j] = (uint8_t)v;
+                    diff += (unsigned)abs(v - cpx);
+                }
+            if (weights) weights[c] = (uint8_t)(w[0] | w[1] << 4);
+            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) {
+                s[0] += w[0] > 0; s[1] += w[1] > 0; s[2] += (unsigned)(w[0] + w[1]); s[3] += diff;
+            }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 // The luma rule of include/bbme.h (the mirror of bgr_luma in bbme_kernels.hpp).
 int bbme_bgr_to_gray_host(const uint8_t *bgr, int width, int height, int pitch, uint8_t *gray)
 {

@@ -3382,4 +3382,173 @@ __global__ __launch_bounds__(256) void k_interpolate_bgr(IpBgrArgs a)
     }
 }
 
+// =======================================================================================
+// K9.  Motion-compensated temporal filter of a frame C with its previous frame P and / or its next frame N (the TEMPORAL FILTER
+// RULE of include/bbme.h): output cell (cx, cy) with origin o reads, for each present neighbour X with grid G on C, the 2x2 cell
+// of X at p = o + G[cy][cx]; inside the plane and with cost = SAD(C cell, X cell) < thr it gets the weight w = 8 (thr - cost) /
+// thr (0..8), otherwise 0, and out = (8 C + wP P + wN N + S / 2) / S with S = 8 + wP + wN.  A memory-bound gather in the mould
+// of k_interpolate: a lane takes a run of 4 consecutive cells of one cell row (fewer at the row's end), so that GP and GN arrive
+// as one 16-byte load each and C as one 8-byte load per plane row; each moved cell is two unaligned u16 loads packed into one
+// dword (ip_cell), so that v_sad_u8 gives the cost -- and, on the finished cell, |out - C| -- in one instruction.  A lane writes
+// its 8 pixels of each of the two output rows as two dwords (bytes where a caller's row is not dword-aligned or the run is cut
+// by the row's end) and its four weight bytes wP | wN << 4 as one dword.
+// Both divisions are multiply-shifts by k_interpolate's argument: with magic = floor(2^32 / d) + 1 = (2^32 + e) / d, 0 < e <= d,
+// umulhi(n, magic) = floor(n / d) for every n with n e < 2^32.  By thr: n = 8 (thr - cost) <= 8 * 1021 and e <= 1021, n e < 2^23
+// (thr = 1 has no 32-bit magic, 2^32 + 1: there only cost 0 passes, and cost 0 is answered without the division).
+// By S: n <= 255 * 24 + 12 and e <= 24, n e < 2^18; S is the lane's own, so the 17 magics of S = 8..24 come with the arguments
+// and are read from LDS.
+// blockIdx.y = batch pair, blockIdx.z = the frame of a run: each of the five inputs is addressed as base + y s_y + z s_z (bytes for
+// planes, words for grids), frames lie out_stride bytes apart along z and need gridDim.y = 1; the map only with one frame per launch.  Along z the
+// first frame has its previous neighbour only with first_prev and the last its next one only with last_next, so that one launch
+// serves the frames of a chain (z = slot) as well as the 2 frames of every pair of a batch (z = which).  Statistics over the window
+// [wx0, wx1) x [wy0, wy1) in cells: cells with wP > 0, cells with wN > 0, the sum of wP + wN and the sum of |out - C| over the
+// cells' pixels; a lane holds at most 4 kTfRunsPerLane cells of at most 1020 each, every workgroup stores its four 64-bit sums as
+// a partial in k_motion_compensate's layout, frame y gridDim.z + z taking pair's place, and k_mc_reduce adds them up (no atomics
+// onto one line, see McArgs).
+// =======================================================================================
+struct TfArgs {
+    const uint8_t *cur, *prev, *next;     // level-0 padded planes, pitch = width; prev / next null = no such neighbour at all
+    const mv_t *gp, *gn;                  // cw entries per row, ch rows: on C, into P and into N
+    uint8_t *out;                         // frames (rows out_pitch, frames out_stride bytes apart), or null
+    uint8_t *wmap;                        // one byte wP | wN << 4 per cell (rows wmap_pitch bytes apart; one-frame launches only), or null
+    unsigned long long *partial;          // per frame and workgroup {cells wP > 0, cells wN > 0, weights, |out - C|}; or null
+    long long cur_y, cur_z, prev_y, prev_z, next_y, next_z;      // bytes from pair to pair and from frame to frame
+    long long gp_y, gp_z, gn_y, gn_z;                            // words
+    size_t out_stride;
+    int width, height, cw, ch, thr, out_pitch, wmap_pitch;
+    int first_prev, last_next;
+    uint32_t magic_thr;                   // floor(2^32 / thr) + 1; not used at thr = 1
+    uint32_t magic_s[17];                 // floor(2^32 / S) + 1 for S = 8..24
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kTfRunsPerLane = 2;
+
+// One neighbour of the cell c with origin (ox, oy): its weight, and its cell in *q when the weight is not 0
+__device__ __forceinline__ uint32_t tf_weight(const uint8_t *X, int W, int H, int ox, int oy, mv_t g, uint32_t c, uint32_t thr,
+                                              uint32_t magic_thr, uint32_t *q)
+{
+    const int px = ox + mv_x(g), py = oy + mv_y(g);
+    *q = 0;
+    if (px < 0 || py < 0 || px > W - 2 || py > H - 2) return 0u;
+    const uint32_t x = ip_cell(X, W, px, py);
+    const uint32_t cost = __builtin_amdgcn_sad_u8(c, x, 0u);
+    if (cost >= thr) return 0u;
+    *q = x;
+    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
+}
+
+__global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
+{
+    __shared__ uint32_t magic_s[17];
+    if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
+    __syncthreads();
+    const long long y = blockIdx.y, z = blockIdx.z;
+    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
+    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
+    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
+    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
+    const mv_t *GP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *GN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    const int W = a.width, H = a.height, CW = a.cw;
+    const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
+    uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
+#pragma unroll
+    for (int r = 0; r < kTfRunsPerLane; ++r) {
+        const long long i = ((long long)blockIdx.x * kTfRunsPerLane + r) * 256 + threadIdx.x;
+        if (i >= a.runs) break;
+        const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
+        const int n = min(4, CW - x0);                        // cells of the run inside the row
+        const int oy = 2 * cy;
+        const size_t g0 = (size_t)cy * CW + x0, o0 = (size_t)oy * W + 2 * x0;
+        uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
+        if (n == 4) {
+            if (has_p) {
+                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GP + g0);
+                gp[0] = v.v[0]; gp[1] = v.v[1]; gp[2] = v.v[2]; gp[3] = v.v[3];
+            }
+            if (has_n) {
+                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GN + g0);
+                gn[0] = v.v[0]; gn[1] = v.v[1]; gn[2] = v.v[2]; gn[3] = v.v[3];
+            }
+            const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(C + o0), u = *reinterpret_cast<const ua_u32x2 *>(C + o0 + W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int sh = 16 * (j & 1);
+                c[j] = ((t.v[j >> 1] >> sh) & 0xffffu) | ((u.v[j >> 1] >> sh) << 16);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= n) continue;
+                if (has_p) gp[j] = GP[g0 + j];
+                if (has_n) gn[j] = GN[g0 + j];
+                c[j] = ip_cell(C, W, 2 * (x0 + j), oy);
+            }
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ws = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox = 2 * (x0 + j);
+            uint32_t qp = 0, qn = 0;
+            const uint32_t wp = has_p ? tf_weight(P, W, H, ox, oy, gp[j], c[j], thr, magic_thr, &qp) : 0u;
+            const uint32_t wn = has_n ? tf_weight(N, W, H, ox, oy, gn[j], c[j], thr, magic_thr, &qn) : 0u;
+            const uint32_t S = 8u + wp + wn, m = magic_s[wp + wn], half = S >> 1;
+            uint32_t px = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t v = __umulhi(8u * ((c[j] >> (8 * q)) & 0xffu) + wp * ((qp >> (8 * q)) & 0xffu) +
+                                            wn * ((qn >> (8 * q)) & 0xffu) + half, m);
+                px |= v << (8 * q);
+            }
+            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
+            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            ws |= (wp | wn << 4) << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                np += wp != 0u; nn += wn != 0u;
+                wsum += wp + wn;
+                dsum += __builtin_amdgcn_sad_u8(px, c[j], 0u);
+            }
+        }
+        if (a.out) {
+            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                const uint32_t *row = yy ? row1 : row0;
+                uint8_t *q = o + (size_t)yy * a.out_pitch;
+                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
+                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
+                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
+                } else {
+                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+                }
+            }
+        }
+        if (a.wmap) {
+            uint8_t *o = a.wmap + (size_t)cy * a.wmap_pitch + x0;
+            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = ws;
+            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(ws >> (8 * j));
+        }
+    }
+    if (!a.partial) return;
+    for (int o = 32; o > 0; o >>= 1) {
+        np += __shfl_xor(np, o);
+        nn += __shfl_xor(nn, o);
+        wsum += __shfl_xor(wsum, o);
+        dsum += __shfl_xor(dsum, o);
+    }
+    __shared__ uint32_t part[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        uint32_t *w = part[threadIdx.x >> 6];
+        w[0] = np; w[1] = nn; w[2] = wsum; w[3] = dsum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        a.partial[4 * (((size_t)blockIdx.y * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x) + threadIdx.x] =
+            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
 }  // namespace bbme

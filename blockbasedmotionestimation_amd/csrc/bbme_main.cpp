@@ -2,7 +2,7 @@
 //
 //   bbme_cli frame10.pgm|.ppm frame11.pgm|.ppm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
-//            [--interpolate PREFIX --factor N] [--backward-color back.ppm]
+//            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -18,6 +18,9 @@
 // as PREFIX_k.pgm, each the unpadded frame MF sees.  --backward-color writes the colour coding (:73-75) of the backward field of a
 // bidirectional estimate at the driver's subsampling; the image is made on the GPU from the cells (the colour rule of
 // include/bbme.h) and only its bytes come back.  --color stays the host's Flow::MotionToColor of the downloaded field.
+// --denoise PREFIX --strength T (default 64, 1..1021) writes PREFIX_1.pgm and PREFIX_2.pgm: each frame averaged with the other one,
+// motion-aligned, where their 2x2 cells match better than T (the temporal filter rule of include/bbme.h, one neighbour each), as
+// the unpadded frames; it needs --no-upsample (the frames written are the frames read; on colour frames, their luma).
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -68,8 +71,8 @@ static bool read_pnm(const char *path, bbme::Image8 &img, bbme::ImageBGR &bgr, b
 int main(int argc, char **argv)
 {
     const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
-               *backward_color = nullptr;
-    int factor = 2;
+               *backward_color = nullptr, *denoise = nullptr;
+    int factor = 2, strength = 64;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
     for (int i = 1; i < argc; ++i) {
@@ -83,6 +86,8 @@ int main(int argc, char **argv)
         else if (a == "--occlusion") occlusion = next();
         else if (a == "--interpolate") interpolate = next();
         else if (a == "--backward-color") backward_color = next();
+        else if (a == "--denoise") denoise = next();
+        else if (a == "--strength") strength = atoi(next());
         else if (a == "--factor") factor = atoi(next());
         else if (a == "--levels") levels = atoi(next());
         else if (a == "--block") block = atoi(next());
@@ -93,10 +98,16 @@ int main(int argc, char **argv)
         else if (!f2) f2 = argv[i];
         else { fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
     }
-    if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || (interpolate && (factor < 2 || factor > 256))) {
+    if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || (interpolate && (factor < 2 || factor > 256)) ||
+        (denoise && (strength < 1 || strength > 1021))) {
         fprintf(stderr, "usage: bbme_cli frame1.pgm|.ppm frame2.pgm|.ppm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
-                        "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm]\n");
+                        "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
+                        "[--denoise PREFIX --strength T]\n");
+        return 2;
+    }
+    if (denoise && upsample) {
+        fprintf(stderr, "--denoise needs --no-upsample\n");
         return 2;
     }
     try {
@@ -174,6 +185,16 @@ int main(int argc, char **argv)
                 }
                 const bbme::Image8 img = motion_pair.interpolate(k, factor);
                 const std::string name = std::string(interpolate) + "_" + std::to_string(k) + ".pgm";
+                bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
+                                           img.data.data() + (size_t)py * img.cols + px));
+            }
+        }
+        if (denoise) {
+            motion_pair.estimateBidirectional();
+            const int px = motion_pair.padding_x, py = motion_pair.padding_y;
+            for (int which = 0; which < 2; ++which) {
+                const bbme::Image8 img = motion_pair.temporalFilter(strength, which);
+                const std::string name = std::string(denoise) + "_" + std::to_string(which + 1) + ".pgm";
                 bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
                                            img.data.data() + (size_t)py * img.cols + px));
             }

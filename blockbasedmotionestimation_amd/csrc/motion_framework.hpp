@@ -263,6 +263,14 @@ public:
         bbme::check(bbme_get_interpolated_host(ctx_, 0, num, den, img.data.data()));
         return img;
     }
+    // Frame `which` (0 = image1, 1 = image2) averaged with the other frame, motion-aligned, where their 2x2 cells match better
+    // than `strength` (the temporal filter rule of include/bbme.h) after estimateBidirectional(): the padded plane.
+    bbme::Image8 temporalFilter(int strength, int which = 0)
+    {
+        bbme::Image8 img(padded_height, padded_width);
+        bbme::check(bbme_get_temporal_filtered_host(ctx_, 0, which, strength, img.data.data()));
+        return img;
+    }
     // The same frame in colour (the BGR interpolation rule of include/bbme.h), for an MF made of colour frames: the UNPADDED frame.
     bbme::ImageBGR interpolateBGR(int num = 1, int den = 2)
     {

@@ -24,6 +24,7 @@ from . import _capi
 DIR_FORWARD, DIR_BACKWARD = 0, 1                           # bbme_set_direction, `which` of the consistency calls
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2      # classes of a consistency mask
 INTERPOLATION_STAT_KEYS = ("forward", "backward", "zero", "cost")      # the hypothesis a cell selected (0, 1, 2), their SADs
+TEMPORAL_STAT_KEYS = ("prev_cells", "next_cells", "weight", "change")  # cells with wP > 0, with wN > 0, sum of weights, sum |out - C|
 
 
 def _check_upsample(upsample):
@@ -639,6 +640,105 @@ class MF:
             ptr(stats), C.c_void_p(hip_stream_handle or 0)))
         return out, sel, stats
 
+    # -- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rule of include/bbme.h) ------
+    def _get_temporal_filtered(self, pair, which, strength, out, what):
+        shape = (self.padded_height, self.padded_width)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
+        _capi.check(self._lib.bbme_get_temporal_filtered_host(self._ctx, pair, int(which), int(strength), out.ctypes.data))
+        return out
+
+    def temporal_filter(self, strength, which=0, pair=0, out=None):
+        """Frame `which` (0 = image1, 1 = image2) of the pair after estimate_bidirectional_async(), averaged with its
+        motion-aligned neighbour wherever their 2x2 cells match better than `strength` (1..1021, a 2x2 SAD) -> the padded
+        (H_pad, W_pad) uint8 plane.  image1 is filtered with image2 along the forward cells, image2 with image1 along the
+        backward cells; on an MFChain the frame is slot pair + which and uses both neighbours where it has them."""
+        return self._get_temporal_filtered(pair, which, strength, out, "temporal_filter")
+
+    def temporal_filter_stats(self, strength, window=None):
+        """One dict(prev_cells, next_cells, weight, change) per frame of the context, from one launch, over window (cx0, cy0, cw,
+        ch) in cells: cells that took their previous / next neighbour, the sum of the weights and the sum of |out - frame| over
+        the window's pixels.  Frames in the order image1, image2 of pair 0, of pair 1, ...; on an MFChain slot by slot.  Default
+        window: default_cell_window(); "all": every cell."""
+        if window is None:
+            window = self.default_cell_window()
+        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
+        n = C.c_int()
+        _capi.check(self._lib.bbme_chain_frames(self._ctx, C.byref(n)))
+        frames = n.value or 2 * getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * frames))()
+        _capi.check(self._lib.bbme_temporal_filter_stats(self._ctx, int(strength), win, s))
+        return [dict(zip(TEMPORAL_STAT_KEYS, s[4 * f:4 * f + 4])) for f in range(frames)]
+
+    def cells_temporal_filter_device(self, cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, out=None, weights=None,
+                                     stats=None, window=None, hip_stream_handle=None):
+        """The temporal filter rule on any three planes and any two cell grids in HBM: cur, prev, next contiguous uint8 CUDA
+        tensors (H_pad, W_pad), to_prev, to_next contiguous int16 CUDA tensors (CH, CW, 2) on cur; a neighbour is its plane and
+        its grid, either neighbour may be None.  Into out, a uint8 CUDA tensor (H_pad, W_pad), weights, uint8 (CH, CW) holding
+        wP | wN << 4 -- rows of both may be further apart than packed --, and stats, a contiguous int64 or uint64 CUDA tensor of 4
+        (TEMPORAL_STAT_KEYS) over window (cx0, cy0, cw, ch) in cells (None = all cells); each of the three may be None.  On the
+        given HIP stream (default: the context's), ordered behind the context's stream; no host wait.  Needs neither frames nor
+        an estimate."""
+        import torch
+        ch, cw = self.cells_shape
+        h, w = self.padded_height, self.padded_width
+        for t in (cur, prev, next):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_device: planes must be contiguous uint8 CUDA tensors "
+                                      "of shape (%d, %d)" % (h, w))
+        for t in (to_prev, to_next):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_device: grids must be contiguous int16 CUDA tensors "
+                                      "of shape (%d, %d, 2)" % (ch, cw))
+        for t, shape, name in ((out, (h, w), "out"), (weights, (ch, cw), "weights")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == shape and t.stride(1) == 1):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_device: %s must be a uint8 CUDA tensor of shape %s "
+                                      "with unit column stride" % (name, shape))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_device: stats must be a contiguous int64 or uint64 CUDA "
+                                  "tensor of 4")
+        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+        self._behind_torch(cur, prev, next, to_prev, to_next, out, weights, stats)
+        _capi.check(self._lib.bbme_cells_temporal_filter_device(
+            self._ctx, ptr(prev), ptr(cur), ptr(next), ptr(to_prev), ptr(to_next), int(strength), win,
+            ptr(out), out.stride(0) if out is not None else 0, ptr(weights), weights.stride(0) if weights is not None else 0,
+            ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+        return out, weights, stats
+
+    def _hbm_view(self, ptr, shape, typestr):
+        """A torch view of memory the context owns (no copy; valid while the context lives and holds what it held)."""
+        import torch
+
+        class _View:
+            pass
+        v = _View()
+        v.__cuda_array_interface__ = {"shape": shape, "typestr": typestr, "data": (ptr, False), "version": 2, "strides": None}
+        return torch.as_tensor(v, device=torch.device("cuda", self.device))
+
+    def frame_plane_tensor(self, pair=0, which=0):
+        """The level-0 padded plane of frame `which` of `pair` in HBM (bbme_frame_plane_device) as a (H_pad, W_pad) uint8 torch
+        view; on an MFChain slot pair + which.  Read it only: the context's estimates depend on it."""
+        p = C.c_void_p()
+        _capi.check(self._lib.bbme_frame_plane_device(self._ctx, pair, int(which), 0, C.byref(p)))
+        return self._hbm_view(p.value, (self.padded_height, self.padded_width), "|u1")
+
+    def cells_tensor(self, pair=0):
+        """The forward 2x2-cell grid of `pair` in HBM as a (CH, CW, 2) int16 torch view."""
+        p = C.c_void_p()
+        _capi.check(self._lib.bbme_cells_device_pair(self._ctx, pair, C.byref(p)))
+        return self._hbm_view(p.value, self.cells_shape + (2,), "<i2")
+
+    def backward_cells_tensor(self, pair=0):
+        """The backward 2x2-cell grid of `pair` in HBM after estimate_bidirectional_async() as a (CH, CW, 2) int16 torch view."""
+        return self._hbm_view(self.backward_cells_device_ptr(pair), self.cells_shape + (2,), "<i2")
+
     def calcMotionBlockMatchingSubsampled(self, scale=None):
         """calcMotionBlockMatching followed by get_subsampled_flow: nothing dense crosses PCIe."""
         self.estimate_async()
@@ -834,6 +934,10 @@ class MFBatch(MF):
         """MF.interpolation_stats of every pair, in order, from one launch."""
         return self._interpolation_stats(num, den, window)
 
+    def get_frame_filtered(self, pair, which, strength, out=None):
+        """MF.temporal_filter of frame `which` of one pair."""
+        return self._get_temporal_filtered(pair, which, strength, out, "get_frame_filtered")
+
     def compensation_errors(self, level=0, block=2, window=None):
         """MF.compensation_error of every pair, in order, from one launch."""
         return self._compensation_stats(level, block, window)
@@ -924,6 +1028,23 @@ class MFChain(MFBatch):
             _capi.check(setter(self._ctx, first, n, table, self.source_width, self.upsample))
         if not wait:
             self._host_frames_in_flight = frames          # keeps converted copies alive until the next run replaces them
+
+    def temporal_filter_run(self, strength, first=0, count=None):
+        """Slots first .. first + count - 1 (default: to the last) filtered from one launch -> (count, H_pad, W_pad) uint8: the
+        first slot of the chain has no previous and the last no next neighbour, every other slot uses both."""
+        import torch
+        first = int(first)
+        count = self.batch + 1 - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.batch + 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_run: slots %d .. %d of a chain of %d"
+                                  % (first, first + count - 1, self.batch + 1))
+        h, w = self.padded_height, self.padded_width
+        frames = torch.empty((count, h, w), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._behind_torch(frames)
+        _capi.check(self._lib.bbme_temporal_filter_chain_device(self._ctx, first, count, int(strength), C.c_void_p(frames.data_ptr()),
+                                                                w, h * w, None))
+        self.synchronize()
+        return frames.cpu().numpy()
 
     def get_slot_plane(self, level, slot):
         """The padded plane of frame slot `slot` at `level` (bbme_get_chain_plane_host) -> (level height, level width) uint8."""
@@ -1022,6 +1143,38 @@ def interpolate_cells(image1, image2, fwd, bwd=None, num=1, den=2, window=None):
                                                   None if bwd is None else bwd.ctypes.data, int(num), int(den), win,
                                                   out.ctypes.data, sel.ctypes.data, s))
     return out, sel, dict(zip(INTERPOLATION_STAT_KEYS, list(s)))
+
+
+def temporal_filter_cells(cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, window=None):
+    """The temporal filter rule of include/bbme.h on the CPU (bbme_temporal_filter_host): cur, prev, next uint8 (H, W) planes of
+    even size, to_prev, to_next int16 (H / 2, W / 2, 2) cell grids on cur; a neighbour is its plane and its grid, either may be
+    None -> (frame (H, W) uint8, weights (H / 2, W / 2) uint8 holding wP | wN << 4, dict(prev_cells, next_cells, weight, change)
+    over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    cur = np.ascontiguousarray(cur, np.uint8)
+    if cur.ndim != 2:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells: uint8 planes of one shape (H, W)")
+    h, w = cur.shape
+    planes, grids = [], []
+    for plane, grid in ((prev, to_prev), (next, to_next)):
+        plane = None if plane is None else np.ascontiguousarray(plane, np.uint8)
+        grid = None if grid is None else np.ascontiguousarray(grid, np.int16)
+        if plane is not None and plane.shape != cur.shape:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells: uint8 planes of one shape (H, W)")
+        if grid is not None and grid.shape != (h // 2, w // 2, 2):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells: int16 grids of shape (H / 2, W / 2, 2)")
+        planes.append(plane)
+        grids.append(grid)
+    out = np.empty((h, w), np.uint8)
+    wmap = np.empty((h // 2, w // 2), np.uint8)
+    s = (C.c_ulonglong * 4)()
+    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data
+
+    _capi.check(_capi.lib().bbme_temporal_filter_host(ptr(planes[0]), cur.ctypes.data, ptr(planes[1]), w, h, ptr(grids[0]),
+                                                      ptr(grids[1]), int(strength), win, out.ctypes.data, wmap.ctypes.data, s))
+    return out, wmap, dict(zip(TEMPORAL_STAT_KEYS, list(s)))
 
 
 def bgr_to_gray(frame):

@@ -435,6 +435,97 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
     return out
 
 
+def denoise_frames(frames, search_size, block_size, strength, device=None, in_flight=4, batch=2):
+    """Motion-compensated temporal denoising of a grey video on ONE GPU (the temporal filter rule of include/bbme.h): every
+    frame averaged with its two motion-aligned neighbours wherever their 2x2 cells match better than `strength` -> len(frames)
+    unpadded uint8 (H, W) frames.  The first and the last frame of the video have one neighbour, every other frame two, the
+    frames at round and segment boundaries included.  Runs on the chain plan of estimate_frames_bidirectional (same contexts,
+    rounds and padding of a short round): every frame is set once and every pair estimated once, both ways.  A round's inner
+    frames come from one launch (MFChain.temporal_filter_run).  A frame at a boundary -- the last of one round and the first
+    of the next, of the same context (carried by advance) or of the neighbouring one -- has its previous frame and the grid
+    into it in one round and its next frame and the grid into that in the other: the round that comes first copies its half on
+    the GPU (planes and grid; the roll and the next estimate overwrite them) and the other filters the frame through
+    MF.cells_temporal_filter_device from the copies and its own buffers.  No plane or grid goes through the host."""
+    from .motion_framework import MFChain
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    n_pairs = len(frames) - 1
+    if n_pairs < 1:
+        return frames
+    if device is None:
+        device = local_device()
+    import torch
+    strength = int(strength)
+    per = max(1, min(batch, in_flight, n_pairs))
+    n_slots = max(1, in_flight // per)
+    rounds = plan_frame_segments(n_pairs, n_slots, per)
+    n_ctx = 1 + max(r[0] for r in rounds)
+    chains = [None] * n_ctx
+    out = [None] * len(frames)
+    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
+    before, after = {}, {}                                 # frame -> copies of (previous plane, grid into it) / (frame, next plane, grid)
+
+    def boundary(mf, g, prev, to_prev, cur, nxt, to_next):
+        flt = torch.empty_like(cur)
+        mf.cells_temporal_filter_device(cur, prev, nxt, to_prev, to_next, strength, out=flt)
+        mf.synchronize()
+        keep(mf, g, flt.cpu().numpy())
+
+    def keep(mf, g, plane):
+        h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
+        out[g] = np.ascontiguousarray(plane[py:py + h, px:px + w])
+
+    def collect(slot):
+        first, count = pending[slot]
+        pending[slot] = None
+        mf = chains[slot]
+        lo = 0 if first == 0 else 1                        # the video's first frame has no previous one anywhere: the chain's own slot 0
+        if count > lo:
+            for q, plane in enumerate(mf.temporal_filter_run(strength, lo, count - lo)):      # waits for this context's stream only
+                keep(mf, first + lo + q, plane)
+        else:
+            mf.synchronize()
+        with torch.cuda.device(device):
+            # the round's first frame: its next half is here
+            if first > 0:
+                half = (mf.frame_plane_tensor(0, 0), mf.frame_plane_tensor(0, 1), mf.cells_tensor(0))
+                if first in before:
+                    boundary(mf, first, *before.pop(first), *half)
+                else:
+                    after[first] = tuple(t.clone() for t in half)
+            # the round's last frame: its previous half is here
+            last = first + count
+            half = (mf.frame_plane_tensor(count - 1, 0), mf.backward_cells_tensor(count - 1))
+            if last == n_pairs:
+                boundary(mf, last, *half, mf.frame_plane_tensor(count - 1, 1), None, None)
+            elif last in after:
+                boundary(mf, last, *half, *after.pop(last))
+            else:
+                before[last] = tuple(t.clone() for t in half)
+            torch.cuda.current_stream().synchronize()      # the copies are taken before the roll and the next estimate overwrite them
+
+    try:
+        for slot, first, count, carry in rounds:
+            run = frames[first + 1:first + count + 1]
+            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
+            if not carry:
+                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device)
+                if n_ctx * per > 1:
+                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
+            else:
+                collect(slot)                              # reads the planes the roll is about to replace
+                chains[slot].advance(run)
+            chains[slot].estimate_bidirectional_async()
+            pending[slot] = (first, count)
+        for slot in range(n_ctx):
+            if pending[slot]:
+                collect(slot)
+    finally:
+        for mf in chains:
+            if mf is not None:
+                mf.close()
+    return out
+
+
 def colorize_frames(frames, search_size, block_size, maxmotion=-1.0, scale=1, in_flight=4, batch=2, device=None):
     """The colour-coded forward field of the len(frames) - 1 consecutive pairs of a video on ONE GPU (the colour rule of
     include/bbme.h at subsampling `scale`): -> ((P, oh, ow, 3) uint8 B,G,R images, (P, 5) float32 ranges (max radius, min u,

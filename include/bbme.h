@@ -585,6 +585,71 @@ int bbme_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int pa
                               const uint8_t *bgr2, int width, int height, int pad_x, int pad_y, const int16_t *fwd,
                               const int16_t *bwd, int num, int den, uint8_t *out);
 
+/* ---- motion-compensated temporal denoising: a frame averaged with its two motion-aligned neighbours ---------------------- */
+
+/* TEMPORAL FILTER RULE (this project's own; the reference has no temporal filter).  Inputs: the plane C of the frame to filter;
+ * optionally the plane P of the previous frame with the cell grid GP on C that points into P; optionally the plane N of the next
+ * frame with the cell grid GN on C that points into N; a strength thr, 1 <= thr <= 1021.  Planes are packed W0 x H0 bytes (the
+ * level-0 padded geometry), grids CH x CW int16 (dx, dy) pairs, CH = H0 / 2, CW = W0 / 2.  A neighbour is PRESENT when its plane
+ * and its grid are both given; at least one must be.  All arithmetic is in 32-bit integers; every division is the floor
+ * division of non-negative numbers.
+ * For output cell (cx, cy) with origin o = (2 cx, 2 cy) and each present neighbour X (P or N) with grid G:
+ *   v = G[cy][cx], p = o + v;
+ *   the neighbour is valid when 0 <= p.x <= W0 - 2 and 0 <= p.y <= H0 - 2;
+ *   cost = sum over the four pixels 0 <= i, j < 2 of |C[o + (j, i)] - X[p + (j, i)]|, 0..1020;
+ *   w = 8 (thr - cost) / thr if the neighbour is valid and cost < thr, else 0.
+ * So w is in 0..8 and w = 8 only at cost 0; an absent neighbour has w = 0.  With S = 8 + wP + wN (8..24),
+ *   out[o + (j, i)] = (8 C[o + (j, i)] + wP P[pP + (j, i)] + wN N[pN + (j, i)] + S / 2) / S    for 0 <= i, j < 2.
+ * The weight map holds one byte per cell, wP | wN << 4.  The statistics over a window {cx0, cy0, cw, ch} IN CELLS (NULL = all
+ * cells) are four exact 64-bit integers: cells with wP > 0, cells with wN > 0, the sum of wP + wN, and the sum over the window's
+ * pixels of |out - C|.  The statistics and the map do not need the frame to be written.
+ * On a context with its own fields (bbme_estimate_bidirectional) the grid into the previous frame is the BACKWARD cells of the
+ * pair the frame is image 2 of, and the grid into the next frame the FORWARD cells of the pair it is image 1 of: both live on
+ * the frame itself.  A context made for up-sampled frames filters its 4x planes; on a colour context the planes are the luma and
+ * that is what is filtered (applying the weights to the stored B,G,R frames is a follow-up, not part of this interface).
+ * Errors: BBME_ERR_INVALID for a null context or required pointer, pair / which / first / count out of range, thr outside
+ * 1..1021, out_pitch < W0, weights_pitch < CW, out_stride below one frame (out_pitch H0) when count > 1, a window as for the
+ * consistency rule, exactly one of a neighbour's plane and grid, no neighbour at all, a d_out of bbme_cells_temporal_filter_device
+ * that overlaps one of its input planes, an odd width or height on the host call;
+ * BBME_ERR_UNSUPPORTED for bbme_temporal_filter_chain_device on anything but a chain context; BBME_ERR_STATE for the four
+ * context-level calls (bbme_temporal_filter_device, _chain_device, bbme_get_temporal_filtered_host, bbme_temporal_filter_stats)
+ * without a valid pair of fields, exactly as bbme_backward_cells_device_pair -- hence they always run in direction FORWARD.
+ * None of these calls changes context state (grids, memo, flow, cells, backward cells, captured graphs, colour store); their
+ * scratch buffers are the context's own and independent of the other getters'.  Outputs must not overlap inputs.
+ * bbme_temporal_filter_host: the rule on the CPU, no GPU, on packed width x height planes (both even) and packed
+ * (height / 2) x (width / 2) grids; out, weights (packed) and stats4 each may be NULL, not all three.
+ * bbme_cells_temporal_filter_device: ANY three packed planes and ANY two grids in HBM of the context's level-0 / cell geometry
+ * (another context's, or a caller's copies); no frames set and no estimate needed; d_out (rows out_pitch bytes apart), d_weights
+ * (rows weights_pitch apart) and d_stats4 each may be null, not all three; on hip_stream (NULL = the ctx stream; another stream is
+ * first ordered behind it); no host wait.  Launches with d_stats4 share one scratch buffer per context: the caller orders those
+ * it issues on different streams.
+ * bbme_temporal_filter_device: frame `which` (0 = image 1, 1 = image 2) of `pair` from the context's own planes and fields.  On a
+ * pair or batched context image 1 has only its next neighbour (image 2, forward cells) and image 2 only its previous one (image 1,
+ * backward cells).  On a chain context the frame is slot pair + which and uses both neighbours where they exist: slot f - 1 with
+ * the backward cells of pair f - 1, slot f + 1 with the forward cells of pair f; (p, 1) and (p + 1, 0) name the same frame and
+ * give the same bytes.
+ * bbme_temporal_filter_chain_device: chain contexts only; slots first .. first + count - 1 from ONE launch (the frame is a grid
+ * dimension), frame q at d_out + q out_stride.
+ * bbme_get_temporal_filtered_host: one frame as bbme_temporal_filter_device; synchronises; packed W0 x H0 bytes.
+ * bbme_temporal_filter_stats: EVERY frame of the context from one launch; synchronises.  On a chain stats[4 f + k] for the slots
+ * f = 0 .. pairs, otherwise stats[4 (2 p + which) + k].
+ * bbme_frame_plane_device: the padded plane of frame `which` of `pair` at `level`, on any kind of context (physical in both
+ * directions; on a chain slot pair + which).  Read-only: unlike bbme_level_planes_device it marks nothing as set.  A caller that
+ * carries a frame across bbme_chain_advance has to copy it out on the GPU first. */
+int bbme_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height,
+                              const int16_t *to_prev, const int16_t *to_next, int thr, const int *window, uint8_t *out,
+                              uint8_t *weights, unsigned long long *stats4);
+int bbme_cells_temporal_filter_device(bbme_ctx *ctx, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                      const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window, uint8_t *d_out,
+                                      int out_pitch, uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4,
+                                      void *hip_stream);
+int bbme_temporal_filter_device(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream);
+int bbme_temporal_filter_chain_device(bbme_ctx *ctx, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                      size_t out_stride, void *hip_stream);
+int bbme_get_temporal_filtered_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
+int bbme_temporal_filter_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
+int bbme_frame_plane_device(bbme_ctx *ctx, int pair, int which, int level, const uint8_t **d_plane);
+
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
 /* copyMVs (:828-843) + calcLevelBM (:226-244) of one level.  Leaves that level's MV
