@@ -738,3 +738,103 @@ def hard_content(name, h, w, seed=0):
     if name == "white":
         return np.full((h, w), 255, np.uint8)
     raise ValueError(name)
+
+
+# ---- content of the scale tests (tests/test_scale_cpu.py proves what it does, tests/test_gpu_scale.py runs the gather kernels ----
+# ---- on it): the smallest planes on which k_mc_reduce's lanes take a second trip through the partials ------------------------
+SCALE_G1 = dict(w=2058, h=1038, search=[12], block=[4])      # pads to 2060 x 1040, pad (1, 1): 1030 x 520 cells
+SCALE_G2 = dict(w=2058, h=2070, search=[12], block=[4])      # pads to 2060 x 2072: k_fb_consistency's 262 workgroups
+SCALE_SEED = 7
+SCALE_STRENGTH = 64
+SCALE_MC_WINDOW = (37, 21, 1998, 1000)                       # pixels, odd on every side
+SCALE_SHIFTS = ((2, -2), (-2, 4), (4, 2), (-4, -2))          # (rows, columns) a video's frame k + 1 is rolled by against frame k
+
+
+def scale_plane(rng, h, w):
+    """Low-amplitude noise: the 2x2 SADs of unrelated cells spread over 0..90, so that a strength of 64 meets every weight and
+    three unrelated hypotheses win about a third of the cells each (planes of 0..255 give the filter a weight in 1 cell of 800)."""
+    return rng.integers(0, 24, (h, w), dtype=np.uint8)
+
+
+def scale_frames(h, w, n, seed=SCALE_SEED):
+    """n unrelated source frames of low-amplitude noise."""
+    rng = np.random.default_rng(seed)
+    return [scale_plane(rng, h, w) for _ in range(n)]
+
+
+def scale_grids(ch, cw, seed=SCALE_SEED):
+    """The two cell grids of the injected-grid tests (test_interpolation_cpu.random_grids, reach 5)."""
+    from test_interpolation_cpu import random_grids
+    return random_grids(ch, cw, np.random.default_rng(seed), reach=5)
+
+
+def scale_filter_content(h0, w0, seed=SCALE_SEED):
+    """(C, P, to_prev, N, to_next) of padded size: three unrelated low-amplitude planes and two random grids; in cell rows 0..7
+    both neighbours are C itself under zero vectors (cost 0: weight 8, which noise never gives); in cell rows 8..15 to_next
+    points outside (one-sided cells)."""
+    from test_interpolation_cpu import random_grids
+    rng = np.random.default_rng(seed)
+    cur, prev, nxt = (scale_plane(rng, h0, w0) for _ in range(3))
+    gp, gn = random_grids(h0 // 2, w0 // 2, rng, reach=5)
+    prev[:16], nxt[:16] = cur[:16], cur[:16]
+    gp[:8], gn[:8] = 0, 0
+    gn[8:16] = (32767, 32767)
+    return cur, prev, gp, nxt, gn
+
+
+def scale_bgr_frames(h, w, seed=SCALE_SEED):
+    """Two unrelated B,G,R frames of the source size."""
+    rng = np.random.default_rng(seed + 1)
+    return rng.integers(0, 256, (h, w, 3), dtype=np.uint8), rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+
+
+def scale_mc_content(h, w, h0, w0, block, seed=SCALE_SEED):
+    """(image1, image2 source frames of 0..255, grid at `block`): vectors of -20..20 drawn per 16 x 16 block and handed down to
+    the `block` grid, so that blocks along all four borders leave the plane and the SSE of the rest passes 2^32."""
+    from test_motion_compensation_cpu import block_mvs_from_grid
+    rng = np.random.default_rng(seed + 2)
+    f1 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    f2 = rng.integers(0, 256, (h, w), dtype=np.uint8)
+    grid16 = rng.integers(-20, 21, (-(-h0 // 16), -(-w0 // 16), 2)).astype(np.int16)
+    return f1, f2, np.ascontiguousarray(block_mvs_from_grid(grid16, 16, block, h0, w0))
+
+
+def scale_video(h, w, n, seed=SCALE_SEED):
+    """n source frames: low-amplitude noise, frame k + 1 = frame k rolled by SCALE_SHIFTS[k] plus fresh noise of 0..7, except in
+    a rectangle, another one per frame, of unrelated noise: there the two fields of a pair contradict each other and the filter
+    finds few matches, so that no two pairs of a video share a statistic."""
+    rng = np.random.default_rng(seed + 3)
+    frames = [scale_plane(rng, h, w)]
+    for k in range(n - 1):
+        f = (np.roll(frames[-1], SCALE_SHIFTS[k % len(SCALE_SHIFTS)], axis=(0, 1)) + rng.integers(0, 8, (h, w))).astype(np.uint8)
+        y0, y1, x0, x1 = h * (k + 1) // 9, h * (2 * k + 4) // 9, w * (k + 1) // 7, w * (k + 4) // 7
+        f[y0:y1, x0:x1] = scale_plane(rng, y1 - y0, x1 - x0)
+        frames.append(f)
+    return frames
+
+
+def scale_groups(w0, h0, runs_per_lane, cells=True):
+    """(runs, workgroups, runs in the last workgroup) of a gather kernel whose lanes take runs_per_lane runs of 4 cells (of 4
+    pixels with cells=False) along a row: the arithmetic of mc_groups / fb_groups / ip_groups / tf_groups (csrc/bbme_device.hip)."""
+    cols, rows = (w0 // 2, h0 // 2) if cells else (w0, h0)
+    runs = (cols + 3) // 4 * rows
+    per_group = 256 * runs_per_lane
+    groups = (runs + per_group - 1) // per_group
+    return runs, groups, runs - (groups - 1) * per_group
+
+
+def stats_differ_pairwise(stats, absent_ok=False, words=(0, 1, 2, 3)):
+    """Every one of the four words (or of `words`) differs between any two of the launch's pairs / frames / phases: a partial
+    read from the wrong one, or a reduction over the wrong pair's partials, changes every word it touches.  absent_ok: a word
+    may be 0 in both (frames that have no previous, or no next, neighbour by construction)."""
+    stats = [tuple(s) for s in stats]
+    return all(a[k] != b[k] or (absent_ok and a[k] == 0)
+               for i, a in enumerate(stats) for b in stats[i + 1:] for k in words)
+
+
+def scale_cell_windows(pad_x, pad_y, w, h):
+    """(default, odd) windows in cells: the cells whose top-left pixel lies in the unpadded frame (MF.default_cell_window), and
+    that window cut by another 3, 1, 5 and 4 cells at its left, top, right and bottom."""
+    x0, y0 = -(-pad_x // 2), -(-pad_y // 2)
+    x1, y1 = -(-(pad_x + w) // 2), -(-(pad_y + h) // 2)
+    return (x0, y0, x1 - x0, y1 - y0), (x0 + 3, y0 + 1, x1 - x0 - 8, y1 - y0 - 5)

@@ -1,6 +1,8 @@
 """Motion compensation on the GPU (k_motion_compensate: MF::draw_MVimage, motion_framework.cpp:887-905, and its residual
 statistics): every frame byte for byte and every statistic exactly what the numpy restatement of include/bbme.h's rule gives
-on the oracle's level planes and MVs, after bbme_estimate and in the reference's stage states."""
+on the oracle's level planes and MVs, after bbme_estimate and in the reference's stage states, and on injected grids (the
+counterpart of test_motion_compensation_cpu.test_host_rule_equals_numpy): every block size under every grid block, vectors that
+leave on all four sides, that sit exactly at and one past each bound, and int16's extremes."""
 import ctypes as C
 import subprocess
 
@@ -8,7 +10,7 @@ import numpy as np
 import pytest
 
 from helpers import oracle_schedule
-from test_motion_compensation_cpu import np_draw_mvimage, np_stats
+from test_motion_compensation_cpu import block_mvs_from_grid, np_draw_mvimage, np_stats
 
 pytestmark = pytest.mark.gpu
 
@@ -136,6 +138,117 @@ def test_stage_states_equal_the_oracle(bbme, oracle):
     assert np.array_equal(mf.get_flow(), omf.flow(0))
     omf.close()
     mf.close()
+
+
+# name: (width, height, search, block, level the grids are injected at); planes are noise of 0..255, level 1's injected too
+INJECT_CONTEXTS = {"b32": (192, 128, [40], [32], 0), "b16_level1": (256, 192, [48, 48], [16, 16], 1)}
+INJECT_GRIDS = ("random", "bounds", "extremes")
+EXTREMES = [(32767, 32767), (-32767, -32767), (32767, -32767), (-32767, 32767), (-32768, -32768), (32767, 0), (0, -32767)]
+
+
+@pytest.fixture(scope="module", params=list(INJECT_CONTEXTS))
+def inject_context(bbme, request):
+    w, h, search, block, level = INJECT_CONTEXTS[request.param]
+    rng = np.random.default_rng(w + h)
+    mf = bbme.MF(rng.integers(0, 256, (h, w), dtype=np.uint8), rng.integers(0, 256, (h, w), dtype=np.uint8), search, block)
+    assert (mf.padded_width, mf.padded_height) == (w, h)
+    if level:
+        mf.set_level_planes(level, rng.integers(0, 256, (h >> level, w >> level), dtype=np.uint8),
+                            rng.integers(0, 256, (h >> level, w >> level), dtype=np.uint8))
+    image1, image2 = mf.get_level_planes(level)
+    assert image2.shape == (h >> level, w >> level)
+    yield mf, level, block[level], image1, image2
+    mf.close()
+
+
+def _bound_targets(size, b):
+    """Source positions of a b-block along one axis: one before the plane, the first and the last inside, one past the last."""
+    return (-1, 0, size - b, size - b + 1)
+
+
+def _injected_grid(kind, rows, cols, gb, b, W, H, rng):
+    """(rows, cols, 2) int16 grid at grid block gb for b-blocks.  random: vectors of up to half the plane, so that blocks leave on
+    all four sides.  bounds: grid block number i puts the source of its first b-block at _bound_targets(W)[i % 4] and
+    _bound_targets(H)[i // 4 % 4].  extremes: zeros mixed with int16's extremes."""
+    if kind == "random":
+        return np.stack([rng.integers(-W // 2, W // 2 + 1, (rows, cols)), rng.integers(-H // 2, H // 2 + 1, (rows, cols))], -1).astype(np.int16)
+    if kind == "bounds":
+        gy, gx = np.mgrid[0:rows, 0:cols]
+        i = gy * cols + gx
+        tx, ty = np.array(_bound_targets(W, b))[i % 4], np.array(_bound_targets(H, b))[i // 4 % 4]
+        return np.stack([tx - gx * gb, ty - gy * gb], -1).astype(np.int16)
+    grid = np.zeros((rows, cols, 2), np.int16)
+    hit = rng.random((rows, cols)) < 0.5
+    hit.flat[:2] = (True, False)
+    grid[hit] = np.array(EXTREMES, np.int16)[rng.integers(0, len(EXTREMES), int(hit.sum()))]
+    return grid
+
+
+@pytest.mark.parametrize("kind", INJECT_GRIDS)
+def test_injected_grids_equal_numpy(bbme, inject_context, kind):
+    from blockbasedmotionestimation_amd import _capi
+    mf, level, B, image1, image2 = inject_context
+    H, W = image2.shape
+    rng = np.random.default_rng(len(kind) + W)
+    windows = ((0, 0, W, H), (5, 3, W - 11, H - 8))
+    combos, leaves = 0, np.zeros(4, bool)                     # a block left at the left, right, top, bottom
+    for b in _blocks(B):
+        for gb in sorted({2, b, B}):
+            if b > gb:
+                continue
+            if gb < 2:                                          # a grid is held at 2..B: there is no 1 x 1 grid to inject
+                with pytest.raises(bbme.BbmeError) as e:
+                    mf.stage_set_mvs(level, gb, np.zeros((H, W, 2), np.int16))
+                assert e.value.status == _capi.ERR_INVALID
+                continue
+            rows, cols = H // gb, W // gb
+            grid = _injected_grid(kind, rows, cols, gb, b, W, H, rng)
+            mf.stage_set_mvs(level, gb, grid)
+            mvs = block_mvs_from_grid(grid.astype(np.int32), gb, b, H, W)
+            for fill in (0, 255):
+                exp, ok = np_draw_mvimage(image2, mvs, b, fill)
+                got = mf.draw_MVimage(level, b, fill)
+                assert np.array_equal(got, exp), "block %d under %d, fill %d: %d bytes differ" % (b, gb, fill, (got != exp).sum())
+            for window in windows:
+                st = mf.compensation_error(level, b, window)
+                assert (st["sse"], st["sad"], st["pixels"], st["skipped"]) == np_stats(image1, exp, ok, window), (b, gb, window)
+            first = ok[::gb, ::gb]                              # the first b-block of every grid block
+            if kind == "random":
+                ys, xs = np.mgrid[0:H:b, 0:W:b]
+                sx, sy = xs + mvs[..., 0], ys + mvs[..., 1]
+                leaves |= np.array([(sx < 0).any(), (sx > W - b).any(), (sy < 0).any(), (sy > H - b).any()])
+                assert ok.any() and not ok.all(), (b, gb)
+            elif kind == "bounds":
+                i = np.arange(rows * cols).reshape(rows, cols)
+                assert len(np.unique(i % 16)) == 16
+                inside_x, inside_y = np.isin(i % 4, (1, 2)), np.isin(i // 4 % 4, (1, 2))
+                assert np.array_equal(first, inside_x & inside_y), (b, gb)
+                for other, this in ((inside_y, i % 4), (inside_x, i // 4 % 4)):          # accepted at, rejected one past, every bound
+                    for at, past in ((1, 0), (2, 3)):
+                        assert first[other & (this == at)].all() and not first[other & (this == past)].any(), (b, gb)
+            else:
+                moved = (mvs != 0).any(-1)
+                zero = np.repeat(np.repeat(~moved, b, 0), b, 1)
+                assert moved.any() and not moved.all()
+                assert np.array_equal(ok, zero) and np.array_equal(exp, np.where(zero, image2, 255))
+                assert mf.compensation_error(level, b, windows[0])["skipped"] == int(moved.sum()) * b * b
+            combos += 1
+    assert combos == {32: 11, 16: 9}[B] and (kind != "random" or leaves.all())
+
+
+def test_injected_grid_into_a_strided_view(bbme, inject_context):
+    import torch
+    mf, level, B, _, image2 = inject_context
+    H, W = image2.shape
+    grid = _injected_grid("random", H // B, W // B, B, 4, W, H, np.random.default_rng(W))
+    mf.stage_set_mvs(level, B, grid)
+    for b in (1, 4, B):
+        exp, _ = np_draw_mvimage(image2, block_mvs_from_grid(grid.astype(np.int32), B, b, H, W), b, 9)
+        big = torch.full((H, W + 13), 0xAB, dtype=torch.uint8, device="cuda")
+        mf.motion_compensated_device(big[:, :W], level, b, 9)
+        mf.synchronize()
+        got = big.cpu().numpy()
+        assert np.array_equal(got[:, :W], exp) and (got[:, W:] == 0xAB).all(), b
 
 
 def test_batch_equals_single_contexts(bbme):
