@@ -304,6 +304,9 @@ struct bbme_ctx {
     DevBuf<uint8_t> tf_plane;                     // bbme_get_temporal_filtered_host: a packed W0 x H0 frame before its download
     DevBuf<unsigned long long> tf_stats;          // temporal filter statistics: 4 words per frame, then the partials of k_temporal_filter
                                                   // of bbme_temporal_filter_stats (every frame) and of bbme_cells_temporal_filter_device (one)
+    DevBuf<uint8_t> tf_bgr;                       // bbme_get_temporal_filtered_bgr_host: a packed 3 W x H frame before its download
+    DevBuf<unsigned long long> tf_bgr_stats;      // tf_stats' layout for k_temporal_filter_bgr (bbme_temporal_filter_bgr_stats,
+                                                  // bbme_cells_temporal_filter_bgr_device)
 };
 
 namespace {
@@ -2642,6 +2645,212 @@ int bbme_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, unsigned
     TfArgs a = tf_own_frames(c, thr, window, 0, 0, count);
     if (int rc = enqueue_tf(c, a, pairs, count, c->tf_stats + (size_t)4 * kTfMaxFrames, c->tf_stats, c->stream)) return rc;
     HIP_TRY(hipMemcpyAsync(stats, c->tf_stats, (size_t)4 * sizeof(unsigned long long) * c->frames(), hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+// ---- the same on the B,G,R frames (the BGR temporal filter rule of include/bbme.h; k_temporal_filter_bgr) ------------------------
+
+// the result words of every frame, then the partials of a launch over every frame, then those of a one-frame launch (tf_scratch's
+// layout, in a buffer of its own)
+static int tf_bgr_scratch(bbme_ctx *c)
+{
+    return c->tf_bgr_stats.ensure((size_t)4 * (kTfMaxFrames + tf_groups(c->lv[0]) * (c->frames() + 1)),
+                                  "the colour temporal filter statistics");
+}
+
+// geometry, strength, the magics of both divisions and the window: TfArgs' own, and the frame inside the padded view
+static TfBgrArgs tf_bgr_args(const bbme_ctx *c, int thr, const int *window)
+{
+    const TfArgs t = tf_args(c, thr, window);
+    const Geometry &g = c->geom;
+    TfBgrArgs a{};
+    a.width = t.width; a.height = t.height; a.cw = t.cw; a.ch = t.ch;
+    a.fw = g.width; a.fh = g.height; a.pad_x = g.pad_x; a.pad_y = g.pad_y;
+    a.thr = thr; a.magic_thr = t.magic_thr;
+    memcpy(a.magic_s, t.magic_s, sizeof a.magic_s);
+    a.wx0 = t.wx0; a.wy0 = t.wy0; a.wx1 = t.wx1; a.wy1 = t.wy1;
+    a.runs_per_row = t.runs_per_row; a.runs = t.runs;
+    return a;
+}
+
+// k_temporal_filter_bgr over `pairs` x `count` frames (blockIdx.y, blockIdx.z) and, with d_stats, k_mc_reduce of the partials into
+// d_stats[4 (y count + z) ..]
+static int enqueue_tf_bgr(bbme_ctx *c, TfBgrArgs &a, int pairs, int count, unsigned long long *partial, unsigned long long *d_stats,
+                          hipStream_t stream)
+{
+    a.partial = d_stats ? partial : nullptr;
+    const long long groups = tf_groups(c->lv[0]);
+    hipLaunchKernelGGL(k_temporal_filter_bgr, dim3((unsigned)groups, (unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
+    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)(pairs * count)), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+// BBME_ERR_STATE unless the slots lo .. hi of the colour store (clamped to the context's) all have colour
+static int check_tf_bgr_colour(const bbme_ctx *c, int lo, int hi, const char *what)
+{
+    for (int s = std::max(lo, 0); s <= std::min(hi, c->frames() - 1); ++s)
+        if (!c->bgr_set[s])
+            return bbme::fail(BBME_ERR_STATE, "%s: frame slot %d has no stored colour (set it with a *_bgr setter)", what, s);
+    return BBME_OK;
+}
+
+// The context's stored colour frames as k_temporal_filter_bgr addresses them: tf_own_frames' layout and grids, with the colour
+// store's slots (chain: slot; pair or batch: which x batch + pair) in the planes' place.  Slot offsets in 64 bits: a deep chain's
+// store exceeds 4 GB.
+static TfBgrArgs tf_bgr_own_frames(const bbme_ctx *c, int thr, const int *window, int pair0, int first, int count)
+{
+    const TfArgs t = tf_own_frames(c, thr, window, pair0, first, count);
+    TfBgrArgs a = tf_bgr_args(c, thr, window);
+    const long long ss = (long long)c->bgr_stride, step = c->chain ? ss : ss * c->batch;
+    const uintptr_t store = reinterpret_cast<uintptr_t>(c->bgr.get());
+    const uintptr_t cur = store + (c->chain ? first * ss : pair0 * ss + first * step);
+    a.cur = reinterpret_cast<const uint8_t *>(cur);
+    a.prev = reinterpret_cast<const uint8_t *>(cur - step);
+    a.next = reinterpret_cast<const uint8_t *>(cur + step);
+    a.cur_z = a.prev_z = a.next_z = step;
+    if (!c->chain) a.cur_y = a.prev_y = a.next_y = ss;
+    a.bgr_pitch = 3 * c->geom.width;
+    a.gp = t.gp; a.gn = t.gn;
+    a.gp_y = t.gp_y; a.gp_z = t.gp_z; a.gn_y = t.gn_y; a.gn_z = t.gn_z;
+    a.first_prev = t.first_prev; a.last_next = t.last_next;
+    return a;
+}
+
+// out_pitch of a colour frame.  Touches no device.
+static int check_tf_bgr_out(const bbme_ctx *c, const uint8_t *d_out, int out_pitch, const char *what)
+{
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if ((long long)out_pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x frame width %d", what, out_pitch, c->geom.width);
+    return BBME_OK;
+}
+
+int bbme_cells_temporal_filter_bgr_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next, int bgr_pitch,
+                                          const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window,
+                                          uint8_t *d_out, int out_pitch, uint8_t *d_weights, int weights_pitch,
+                                          unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_temporal_filter_bgr_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    const Geometry &g = c->geom;
+    if (!d_cur || (!d_out && !d_weights && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if ((d_prev == nullptr) != (d_to_prev == nullptr) || (d_next == nullptr) != (d_to_next == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its frame and its grid", what);
+    if (!d_prev && !d_next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if ((long long)bgr_pitch < 3LL * g.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, bgr_pitch, g.width);
+    if (d_out) if (int rc = check_tf_bgr_out(c, d_out, out_pitch, what)) return rc;
+    if (d_weights && weights_pitch < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: weight map pitch %d < %d cells per row", what, weights_pitch, L.width / 2);
+    // the frame is written while other lanes still gather from the frames: an output inside an input frame is a race, not a result
+    if (d_out) {
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (size_t)out_pitch * (g.height - 1) + (size_t)3 * g.width;
+        for (const uint8_t *in : {d_prev, d_cur, d_next}) {
+            const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (size_t)bgr_pitch * (g.height - 1) + (size_t)3 * g.width;
+            if (in && o0 < i1 && i0 < o1) return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input frame", what);
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = tf_bgr_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    TfBgrArgs a = tf_bgr_args(c, thr, window);
+    a.cur = d_cur; a.prev = d_prev; a.next = d_next; a.bgr_pitch = bgr_pitch;
+    a.gp = reinterpret_cast<const mv_t *>(d_to_prev); a.gn = reinterpret_cast<const mv_t *>(d_to_next);
+    a.first_prev = a.last_next = 1;
+    a.out = d_out; a.out_pitch = out_pitch;
+    a.wmap = d_weights; a.wmap_pitch = weights_pitch;
+    unsigned long long *partial = d_stats4 ? c->tf_bgr_stats + (size_t)4 * (kTfMaxFrames + tf_groups(L) * c->frames()) : nullptr;
+    return enqueue_tf_bgr(c, a, 1, 1, partial, d_stats4, stream);
+}
+
+// BBME_ERR_STATE unless frame `which` of `pair` and the neighbours the rule gives it have colour
+static int check_tf_bgr_frame_colour(const bbme_ctx *c, int pair, int which, const char *what)
+{
+    if (c->chain) return check_tf_bgr_colour(c, pair + which - 1, pair + which + 1, what);
+    for (int w = 0; w < 2; ++w)
+        if (!c->bgr_set[c->slot(pair, w)])
+            return bbme::fail(BBME_ERR_STATE, "%s: pair %d has no stored colour (set both frames with a *_bgr setter)", what, pair);
+    return BBME_OK;
+}
+
+// frame `which` of `pair` of the context's own, into d_out on `stream`
+static int enqueue_own_tf_bgr(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, hipStream_t stream)
+{
+    TfBgrArgs a = c->chain ? tf_bgr_own_frames(c, thr, nullptr, 0, pair + which, 1) : tf_bgr_own_frames(c, thr, nullptr, pair, which, 1);
+    a.out = d_out; a.out_pitch = out_pitch;
+    return enqueue_tf_bgr(c, a, 1, 1, nullptr, nullptr, stream);
+}
+
+int bbme_temporal_filter_bgr_device(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    const char *what = "bbme_temporal_filter_bgr_device";
+    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
+    if (int rc = check_tf_bgr_out(c, d_out, out_pitch, what)) return rc;
+    if (int rc = check_tf_state(c, what)) return rc;
+    if (int rc = check_tf_bgr_frame_colour(c, pair, which, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_tf_bgr(c, pair, which, thr, d_out, out_pitch, stream);
+}
+
+int bbme_temporal_filter_bgr_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
+                                          void *hip_stream)
+{
+    const char *what = "bbme_temporal_filter_bgr_chain_device";
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (first < 0 || count < 1 || (long long)first + count > c->batch + 1)
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside 0 .. %d", what, first, first, count, c->batch);
+    if (int rc = check_tf(c, thr, nullptr, what)) return rc;
+    if (int rc = check_tf_bgr_out(c, d_out, out_pitch, what)) return rc;
+    if (count > 1 && out_stride < (size_t)out_pitch * c->geom.height)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output stride %zu < one frame of %d rows of %d bytes", what, out_stride, c->geom.height,
+                          out_pitch);
+    if (int rc = check_tf_state(c, what)) return rc;
+    if (int rc = check_tf_bgr_colour(c, first - 1, first + count, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    TfBgrArgs a = tf_bgr_own_frames(c, thr, nullptr, 0, first, count);
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    return enqueue_tf_bgr(c, a, 1, count, nullptr, nullptr, stream);
+}
+
+int bbme_get_temporal_filtered_bgr_host(bbme_ctx *c, int pair, int which, int thr, uint8_t *out)
+{
+    const char *what = "bbme_get_temporal_filtered_bgr_host";
+    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_tf_state(c, what)) return rc;
+    if (int rc = check_tf_bgr_frame_colour(c, pair, which, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t bytes = (size_t)3 * c->geom.width * c->geom.height;
+    if (int rc = c->tf_bgr.ensure(bytes, "the filtered colour frame")) return rc;
+    if (int rc = enqueue_own_tf_bgr(c, pair, which, thr, c->tf_bgr, 3 * c->geom.width, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, c->tf_bgr, bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_temporal_filter_bgr_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_temporal_filter_bgr_stats";
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_tf_state(c, what)) return rc;
+    if (int rc = check_tf_bgr_colour(c, 0, c->frames() - 1, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = tf_bgr_scratch(c)) return rc;
+    // chain: one pair row, every slot along z; otherwise every pair along y, which along z: frame y gridDim.z + z either way
+    const int pairs = c->chain ? 1 : c->batch, count = c->chain ? c->batch + 1 : 2;
+    TfBgrArgs a = tf_bgr_own_frames(c, thr, window, 0, 0, count);
+    if (int rc = enqueue_tf_bgr(c, a, pairs, count, c->tf_bgr_stats + (size_t)4 * kTfMaxFrames, c->tf_bgr_stats, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(stats, c->tf_bgr_stats, (size_t)4 * sizeof(unsigned long long) * c->frames(), hipMemcpyDeviceToHost,
+                           c->stream));
     return check_converged(c);
 }
 

@@ -851,6 +851,82 @@ int bbme_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int pa
     return BBME_OK;
 }
 
+// The BGR temporal filter rule of include/bbme.h, cell by cell of the padded view, in the header's own words (the mirror of
+// k_temporal_filter_bgr).
+int bbme_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height, int pad_x,
+                                  int pad_y, const int16_t *to_prev, const int16_t *to_next, int thr, const int *window, uint8_t *out,
+                                  uint8_t *weights, unsigned long long *stats4)
+{
+    const char *what = "bbme_temporal_filter_bgr_host";
+    if (!cur || (!out && !weights && !stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if ((prev == nullptr) != (to_prev == nullptr) || (next == nullptr) != (to_next == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its frame and its grid", what);
+    if (!prev && !next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (width < 1 || height < 1 || pad_x < 0 || pad_y < 0 || (long long)width + 2LL * pad_x > INT32_MAX ||
+        (long long)height + 2LL * pad_y > INT32_MAX)
+        return bbme::fail(BBME_ERR_INVALID, "%s: bad frame %dx%d with padding (%d, %d)", what, width, height, pad_x, pad_y);
+    const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y;
+    if ((W0 & 1) || (H0 & 1)) return bbme::fail(BBME_ERR_INVALID, "%s: the padded view %dx%d is not a plane of 2x2 cells", what, W0, H0);
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    const int cw = W0 / 2, ch = H0 / 2;
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
+        return bbme::fail(BBME_ERR_INVALID, "%s: window not inside the %dx%d cells", what, cw, ch);
+    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
+    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
+    // channel k of the pixel at the padded position (X, Y): 0 outside the frame
+    const auto texel = [&](const uint8_t *img, int X, int Y, int k) {
+        const int x = X - pad_x, y = Y - pad_y;
+        return x < 0 || y < 0 || x >= width || y >= height ? 0 : (int)img[((size_t)y * width + x) * 3 + k];
+    };
+    const uint8_t *frames[2] = {prev, next};
+    const int16_t *grids[2] = {to_prev, to_next};
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            int w[2] = {0, 0}, px[2] = {0, 0}, py[2] = {0, 0};
+            for (int k = 0; k < 2; ++k) {
+                if (!frames[k]) continue;
+                px[k] = ox + grids[k][2 * c];
+                py[k] = oy + grids[k][2 * c + 1];
+                if (px[k] < 0 || py[k] < 0 || px[k] > W0 - 2 || py[k] > H0 - 2) continue;
+                int cost = 0;
+                for (int chn = 0; chn < 3; ++chn) {
+                    int cc = 0;
+                    for (int i = 0; i < 2; ++i)
+                        for (int j = 0; j < 2; ++j)
+                            cc += abs(texel(cur, ox + j, oy + i, chn) - texel(frames[k], px[k] + j, py[k] + i, chn));
+                    if (cc > cost) cost = cc;
+                }
+                if (cost < thr) w[k] = 8 * (thr - cost) / thr;
+            }
+            const int S = 8 + w[0] + w[1];
+            unsigned diff = 0;
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j) {
+                    const int x = ox + j - pad_x, y = oy + i - pad_y;
+                    const bool inside = x >= 0 && y >= 0 && x < width && y < height;
+                    for (int chn = 0; chn < 3; ++chn) {
+                        const int cpx = texel(cur, ox + j, oy + i, chn);
+                        int acc = 8 * cpx + S / 2;
+                        for (int k = 0; k < 2; ++k)
+                            if (w[k]) acc += w[k] * texel(frames[k], px[k] + j, py[k] + i, chn);
+                        const int v = acc / S;
+                        if (out && inside) out[((size_t)y * width + x) * 3 + chn] = (uint8_t)v;
+                        diff += (unsigned)abs(v - cpx);
+                    }
+                }
+            if (weights) weights[c] = (uint8_t)(w[0] | w[1] << 4);
+            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) {
+                s[0] += w[0] > 0; s[1] += w[1] > 0; s[2] += (unsigned)(w[0] + w[1]); s[3] += diff;
+            }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 int bbme_subsample_div4(const float *flow_padded, int padded_width, int padded_height,
                         int pad_x, int pad_y, float *out, int out_width, int out_height)
 {

@@ -3551,4 +3551,213 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
             (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
 }
 
+// =======================================================================================
+// K9b.  The BGR TEMPORAL FILTER RULE of include/bbme.h: K9 on three B,G,R frames, the cost of a neighbour's cell being the LARGEST
+// of its three per-channel 2x2 SADs, and the UNPADDED frame written.  It reads no luma plane: the cells are those of the padded
+// view (a pixel outside the fw x fh frame is 0 in every channel), cell (cx, cy) with origin o = (2 cx, 2 cy) holding the frame's
+// pixels o - (pad_x, pad_y) + (j, i).  Same split as k_temporal_filter (a lane takes a run of 4 cells of one cell row,
+// kTfRunsPerLane runs per lane, GP and GN as one 16-byte load each, blockIdx.y = batch pair, blockIdx.z = the frame of a run, every
+// input base + y s_y + z s_z in 64 bits, first_prev / last_next) and the colour accesses of k_interpolate_bgr: a neighbour's cell
+// row is 6 contiguous bytes (bgr_two: one unaligned dword and one u16 load, bytes at the frame's edge, 0 outside); the run's own
+// row is 24 bytes, three unaligned 8-byte loads where the run is whole and inside the frame and bgr_two cell by cell otherwise;
+// the output row is collected in three 64-bit words and leaves as six dword stores when the run is whole, inside the frame and its
+// row address dword-aligned, by bytes otherwise (with an odd padding cells straddle the frame's edge and only their pixels inside
+// are written).  A run with no pixel in the frame is skipped before any load unless the map or the statistics are asked for: its
+// cells are all-zero on C but belong to both.
+// A cell row of a frame is the dword B0 G0 R0 B1 and the u16 G1 R1: the two u16 of a cell share a dword, and the per-channel SADs
+// are v_sad_u8 on channel-masked dwords (B: 2, G and R: 3 each).  The divisions are K9's multiply-shifts with K9's bounds.
+// Statistics as K9 (|out - C| over the cells' four pixels and three channels, at most 3060 a cell), same partial layout.
+// =======================================================================================
+struct TfBgrArgs {
+    const uint8_t *cur, *prev, *next;     // fw x fh B,G,R frames, rows bgr_pitch bytes apart; prev / next null = no such neighbour at all
+    const mv_t *gp, *gn;                  // cw entries per row, ch rows: on C, into P and into N
+    uint8_t *out;                         // fw x fh B,G,R frames (rows out_pitch, frames out_stride bytes apart), or null
+    uint8_t *wmap;                        // one byte wP | wN << 4 per cell (rows wmap_pitch bytes apart; one-frame launches only), or null
+    unsigned long long *partial;          // per frame and workgroup {cells wP > 0, cells wN > 0, weights, |out - C|}; or null
+    long long cur_y, cur_z, prev_y, prev_z, next_y, next_z;      // bytes from pair to pair and from frame to frame
+    long long gp_y, gp_z, gn_y, gn_z;                            // words
+    size_t out_stride;
+    int width, height, cw, ch, fw, fh, pad_x, pad_y, thr, bgr_pitch, out_pitch, wmap_pitch;      // width x height: the padded view
+    int first_prev, last_next;
+    uint32_t magic_thr;                   // floor(2^32 / thr) + 1; not used at thr = 1
+    uint32_t magic_s[17];                 // floor(2^32 / S) + 1 for S = 8..24
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+struct __attribute__((packed, aligned(1))) ua_u64 { uint64_t v; };
+
+// the largest per-channel SAD of two cells; lo0, lo1: B0 G0 R0 B1 of the cell's rows, hi: G1 R1 of row 0 | G1 R1 of row 1 << 16
+__device__ __forceinline__ uint32_t bgr_cell_cost(uint32_t c0, uint32_t c1, uint32_t ch, uint32_t x0, uint32_t x1, uint32_t xh)
+{
+    const uint32_t mB = 0xff0000ffu, mG = 0x0000ff00u, mR = 0x00ff0000u, hG = 0x00ff00ffu, hR = 0xff00ff00u;
+    const uint32_t b = __builtin_amdgcn_sad_u8(c0 & mB, x0 & mB, __builtin_amdgcn_sad_u8(c1 & mB, x1 & mB, 0u));
+    const uint32_t g = __builtin_amdgcn_sad_u8(c0 & mG, x0 & mG, __builtin_amdgcn_sad_u8(c1 & mG, x1 & mG,
+                                               __builtin_amdgcn_sad_u8(ch & hG, xh & hG, 0u)));
+    const uint32_t r = __builtin_amdgcn_sad_u8(c0 & mR, x0 & mR, __builtin_amdgcn_sad_u8(c1 & mR, x1 & mR,
+                                               __builtin_amdgcn_sad_u8(ch & hR, xh & hR, 0u)));
+    return max(b, max(g, r));
+}
+
+// One neighbour of the cell (c0, c1: its two rows of 6 bytes) with origin (ox, oy) on the padded view: its weight, and its two
+// rows in q[] when the weight is not 0
+__device__ __forceinline__ uint32_t tf_bgr_weight(const uint8_t *X, const TfBgrArgs &a, int ox, int oy, mv_t g, uint64_t c0, uint64_t c1,
+                                                  uint32_t thr, uint32_t magic_thr, uint64_t *q)
+{
+    const int px = ox + mv_x(g), py = oy + mv_y(g);
+    q[0] = q[1] = 0;
+    if (px < 0 || py < 0 || px > a.width - 2 || py > a.height - 2) return 0u;
+    const uint64_t x0 = bgr_two(X, a.bgr_pitch, a.fw, a.fh, px - a.pad_x, py - a.pad_y);
+    const uint64_t x1 = bgr_two(X, a.bgr_pitch, a.fw, a.fh, px - a.pad_x, py - a.pad_y + 1);
+    const uint32_t cost = bgr_cell_cost((uint32_t)c0, (uint32_t)c1, (uint32_t)(c0 >> 32) | (uint32_t)(c1 >> 32) << 16,
+                                        (uint32_t)x0, (uint32_t)x1, (uint32_t)(x0 >> 32) | (uint32_t)(x1 >> 32) << 16);
+    if (cost >= thr) return 0u;
+    q[0] = x0; q[1] = x1;
+    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
+}
+
+__global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
+{
+    __shared__ uint32_t magic_s[17];
+    if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
+    __syncthreads();
+    const long long y = blockIdx.y, z = blockIdx.z;
+    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
+    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
+    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
+    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
+    const mv_t *GP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *GN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    const int CW = a.cw;
+    const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
+    uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
+#pragma unroll
+    for (int r = 0; r < kTfRunsPerLane; ++r) {
+        const long long i = ((long long)blockIdx.x * kTfRunsPerLane + r) * 256 + threadIdx.x;
+        if (i >= a.runs) break;
+        const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
+        const int n = min(4, CW - x0);                        // cells of the run inside the row
+        const int oy = 2 * cy;
+        const int fy = oy - a.pad_y, fx = 2 * x0 - a.pad_x;    // the run's first pixel in frame coordinates
+        if (fy + 1 < 0 || fy >= a.fh || fx + 2 * n <= 0 || fx >= a.fw) {      // no pixel of the run is in the frame
+            if (!a.partial && !a.wmap) continue;
+        }
+        const size_t g0 = (size_t)cy * CW + x0;
+        uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0};
+        if (n == 4) {
+            if (has_p) {
+                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GP + g0);
+                gp[0] = v.v[0]; gp[1] = v.v[1]; gp[2] = v.v[2]; gp[3] = v.v[3];
+            }
+            if (has_n) {
+                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GN + g0);
+                gn[0] = v.v[0]; gn[1] = v.v[1]; gn[2] = v.v[2]; gn[3] = v.v[3];
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= n) continue;
+                if (has_p) gp[j] = GP[g0 + j];
+                if (has_n) gn[j] = GN[g0 + j];
+            }
+        }
+        const bool whole = n == 4 && fx >= 0 && fx + 8 <= a.fw;      // the run's 8 pixels lie inside a frame row
+        uint64_t crow[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's own two rows, 24 bytes each
+        if (whole) {
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                if (fy + yy < 0 || fy + yy >= a.fh) continue;
+                const uint8_t *q = C + (size_t)(fy + yy) * a.bgr_pitch + (size_t)3 * fx;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) crow[yy][d] = reinterpret_cast<const ua_u64 *>(q)[d].v;
+            }
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows
+        uint32_t ws = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox = 2 * (x0 + j);
+            const int bit = 48 * j, wd = bit >> 6, sh = bit & 63;      // the cell's six bytes are bytes 6 j .. 6 j + 5 of a row
+            uint64_t c[2];
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                if (whole) {
+                    uint64_t v = crow[yy][wd] >> sh;
+                    if (sh > 16) v |= crow[yy][wd + 1] << (64 - sh);
+                    c[yy] = v & 0xffffffffffffull;
+                } else {
+                    c[yy] = bgr_two(C, a.bgr_pitch, a.fw, a.fh, fx + 2 * j, fy + yy);
+                }
+            }
+            uint64_t qp[2] = {0, 0}, qn[2] = {0, 0};
+            const uint32_t wp = has_p ? tf_bgr_weight(P, a, ox, oy, gp[j], c[0], c[1], thr, magic_thr, qp) : 0u;
+            const uint32_t wn = has_n ? tf_bgr_weight(N, a, ox, oy, gn[j], c[0], c[1], thr, magic_thr, qn) : 0u;
+            const uint32_t S = 8u + wp + wn, m = magic_s[wp + wn], half = S >> 1;
+            uint32_t diff = 0;
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                uint64_t px = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    const uint32_t v = __umulhi(8u * ((uint32_t)(c[yy] >> (8 * q)) & 0xffu) + wp * ((uint32_t)(qp[yy] >> (8 * q)) & 0xffu) +
+                                                wn * ((uint32_t)(qn[yy] >> (8 * q)) & 0xffu) + half, m);
+                    px |= (uint64_t)v << (8 * q);
+                }
+                rows[yy][wd] |= px << sh;
+                if (sh > 16) rows[yy][wd + 1] |= px >> (64 - sh);
+                diff = __builtin_amdgcn_sad_u8((uint32_t)px, (uint32_t)c[yy], diff);
+                diff = __builtin_amdgcn_sad_u8((uint32_t)(px >> 32), (uint32_t)(c[yy] >> 32), diff);
+            }
+            ws |= (wp | wn << 4) << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                np += wp != 0u; nn += wn != 0u;
+                wsum += wp + wn;
+                dsum += diff;
+            }
+        }
+        if (a.out) {
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                if (fy + yy < 0 || fy + yy >= a.fh) continue;
+                uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(fy + yy) * a.out_pitch + (ptrdiff_t)3 * fx;
+                if (whole && ((uintptr_t)q & 3u) == 0) {
+                    uint32_t *o = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+                    for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[yy][d >> 1] >> (32 * (d & 1)));
+                } else {
+#pragma unroll
+                    for (int p = 0; p < 8; ++p) {
+                        if (p >= 2 * n || fx + p < 0 || fx + p >= a.fw) continue;
+#pragma unroll
+                        for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[yy][k >> 3] >> (8 * (k & 7)));
+                    }
+                }
+            }
+        }
+        if (a.wmap) {
+            uint8_t *o = a.wmap + (size_t)cy * a.wmap_pitch + x0;
+            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = ws;
+            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(ws >> (8 * j));
+        }
+    }
+    if (!a.partial) return;
+    for (int o = 32; o > 0; o >>= 1) {
+        np += __shfl_xor(np, o);
+        nn += __shfl_xor(nn, o);
+        wsum += __shfl_xor(wsum, o);
+        dsum += __shfl_xor(dsum, o);
+    }
+    __shared__ uint32_t part[4][4];
+    if ((threadIdx.x & 63) == 0) {
+        uint32_t *w = part[threadIdx.x >> 6];
+        w[0] = np; w[1] = nn; w[2] = wsum; w[3] = dsum;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        a.partial[4 * (((size_t)blockIdx.y * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x) + threadIdx.x] =
+            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
 }  // namespace bbme

@@ -20,7 +20,9 @@
 // include/bbme.h) and only its bytes come back.  --color stays the host's Flow::MotionToColor of the downloaded field.
 // --denoise PREFIX --strength T (default 64, 1..1021) writes PREFIX_1.pgm and PREFIX_2.pgm: each frame averaged with the other one,
 // motion-aligned, where their 2x2 cells match better than T (the temporal filter rule of include/bbme.h, one neighbour each), as
-// the unpadded frames; it needs --no-upsample (the frames written are the frames read; on colour frames, their luma).
+// the unpadded frames; it needs --no-upsample (the frames written are the frames read; on colour frames, their luma).  On colour
+// frames it also writes PREFIX_1.ppm and PREFIX_2.ppm: the colour frames filtered by the BGR temporal filter rule, whose weights
+// come from the colour frames themselves (the largest per-channel 2x2 SAD) and not from the luma.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -103,7 +105,9 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: bbme_cli frame1.pgm|.ppm frame2.pgm|.ppm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
-                        "[--denoise PREFIX --strength T]\n");
+                        "[--denoise PREFIX --strength T]\n"
+                        "--denoise writes PREFIX_1.pgm and PREFIX_2.pgm (on .ppm frames their luma) and, on .ppm frames, the "
+                        "filtered colour frames PREFIX_1.ppm and PREFIX_2.ppm; it needs --no-upsample\n");
         return 2;
     }
     if (denoise && upsample) {
@@ -197,6 +201,11 @@ int main(int argc, char **argv)
                 const std::string name = std::string(denoise) + "_" + std::to_string(which + 1) + ".pgm";
                 bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
                                            img.data.data() + (size_t)py * img.cols + px));
+                if (colour) {                          // the colour frame itself, by the BGR temporal filter rule
+                    const bbme::ImageBGR bgr = motion_pair.temporalFilterBgr(strength, which);
+                    const std::string ppm = std::string(denoise) + "_" + std::to_string(which + 1) + ".ppm";
+                    bbme::check(bbme_ppm_write_bgr(ppm.c_str(), bgr.cols, bgr.rows, bgr.data.data()));
+                }
             }
         }
         if (backward_color) {

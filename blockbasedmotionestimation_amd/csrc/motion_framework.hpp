@@ -278,6 +278,15 @@ public:
         bbme::check(bbme_get_interpolated_bgr_host(ctx_, 0, num, den, img.data.data()));
         return img;
     }
+    // temporalFilter in colour (the BGR temporal filter rule of include/bbme.h), for an MF made of colour frames: the stored
+    // B,G,R frame `which` averaged with the other one where their 2x2 cells match better than `strength` in every channel;
+    // the UNPADDED frame.
+    bbme::ImageBGR temporalFilterBgr(int strength, int which = 0)
+    {
+        bbme::ImageBGR img(padded_height - 2 * padding_y, padded_width - 2 * padding_x);
+        bbme::check(bbme_get_temporal_filtered_bgr_host(ctx_, 0, which, strength, img.data.data()));
+        return img;
+    }
     // Its statistics over window {cx0, cy0, cw, ch} in cells; nullptr = unpaddedCells.
     bbme::InterpolationStats interpolationStats(int num = 1, int den = 2, const int *window = nullptr)
     {

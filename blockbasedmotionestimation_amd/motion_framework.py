@@ -712,6 +712,88 @@ class MF:
             ptr(stats), C.c_void_p(hip_stream_handle or 0)))
         return out, weights, stats
 
+    # -- the same on the B,G,R frames (the BGR temporal filter rule of include/bbme.h): needs frames set as (H, W, 3) -----------
+    def _get_temporal_filtered_bgr(self, pair, which, strength, out, what):
+        shape = (self.orig_height, self.orig_width, 3)
+        if out is None:
+            out = np.empty(shape, np.uint8)
+        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
+        _capi.check(self._lib.bbme_get_temporal_filtered_bgr_host(self._ctx, pair, int(which), int(strength), out.ctypes.data))
+        return out
+
+    def temporal_filter_bgr(self, strength, which=0, pair=0, out=None):
+        """temporal_filter() in colour: the stored B,G,R frame `which` averaged with its motion-aligned neighbour(s) wherever
+        their 2x2 cells match better than `strength` in EVERY channel (the cost is the largest per-channel 2x2 SAD; the luma
+        planes are not read) -> the UNPADDED (H, W, 3) uint8 frame.  Neighbours and grids as temporal_filter().  BbmeError
+        (ERR_STATE) when the frame or a neighbour it uses was set grey."""
+        return self._get_temporal_filtered_bgr(pair, which, strength, out, "temporal_filter_bgr")
+
+    def temporal_filter_bgr_stats(self, strength, window=None):
+        """temporal_filter_stats() of the colour filter: one dict(prev_cells, next_cells, weight, change) per frame of the context
+        from one launch, over window (cx0, cy0, cw, ch) in cells of the padded view; `change` sums |out - frame| over the window's
+        pixels and three channels.  Default window: default_cell_window(); "all": every cell."""
+        if window is None:
+            window = self.default_cell_window()
+        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
+        n = C.c_int()
+        _capi.check(self._lib.bbme_chain_frames(self._ctx, C.byref(n)))
+        frames = n.value or 2 * getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * frames))()
+        _capi.check(self._lib.bbme_temporal_filter_bgr_stats(self._ctx, int(strength), win, s))
+        return [dict(zip(TEMPORAL_STAT_KEYS, s[4 * f:4 * f + 4])) for f in range(frames)]
+
+    def cells_temporal_filter_bgr_device(self, cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, out=None,
+                                         weights=None, stats=None, window=None, hip_stream_handle=None):
+        """The BGR temporal filter rule on any three colour frames and any two cell grids in HBM: cur, prev, next uint8 CUDA
+        tensors (H, W, 3) with packed pixels and a common row pitch, to_prev, to_next contiguous int16 CUDA tensors (CH, CW, 2) on
+        cur; a neighbour is its frame and its grid, either neighbour may be None.  Into out, a uint8 CUDA tensor (H, W, 3) with
+        packed pixels, weights, uint8 (CH, CW) holding wP | wN << 4 -- rows of both may be further apart than packed --, and
+        stats, a contiguous int64 or uint64 CUDA tensor of 4 (TEMPORAL_STAT_KEYS) over window (cx0, cy0, cw, ch) in cells (None =
+        all cells); each of the three may be None.  On the given HIP stream (default: the context's), ordered behind the
+        context's stream; no host wait.  Needs neither frames nor an estimate."""
+        import torch
+        ch, cw = self.cells_shape
+        h, w = self.orig_height, self.orig_width
+        for t in (cur, prev, next):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and _packed_pixels(t)
+                                      and cur is not None and t.stride(0) == cur.stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_bgr_device: colour frames must be uint8 CUDA tensors "
+                                      "of shape (%d, %d, 3) with packed pixels and a common row pitch" % (h, w))
+        for t in (to_prev, to_next):
+            if t is not None and not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_bgr_device: grids must be contiguous int16 CUDA "
+                                      "tensors of shape (%d, %d, 2)" % (ch, cw))
+        if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3) and _packed_pixels(out)):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_bgr_device: out must be a uint8 CUDA tensor of shape "
+                                  "(%d, %d, 3) with packed pixels" % (h, w))
+        if weights is not None and not (weights.is_cuda and weights.dtype == torch.uint8 and tuple(weights.shape) == (ch, cw)
+                                        and weights.stride(1) == 1):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_bgr_device: weights must be a uint8 CUDA tensor of shape "
+                                  "(%d, %d) with unit column stride" % (ch, cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_bgr_device: stats must be a contiguous int64 or uint64 "
+                                  "CUDA tensor of 4")
+        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr() if t is not None else 0)
+
+        self._behind_torch(cur, prev, next, to_prev, to_next, out, weights, stats)
+        _capi.check(self._lib.bbme_cells_temporal_filter_bgr_device(
+            self._ctx, ptr(prev), ptr(cur), ptr(next), cur.stride(0) if cur is not None else 0, ptr(to_prev), ptr(to_next),
+            int(strength), win, ptr(out), out.stride(0) if out is not None else 0, ptr(weights),
+            weights.stride(0) if weights is not None else 0, ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+        return out, weights, stats
+
+    def frame_bgr_tensor(self, pair=0, which=0):
+        """The stored colour frame `which` of `pair` in HBM (bbme_bgr_frames_device_pair) as a (H, W, 3) uint8 torch view; on an
+        MFChain slot pair + which.  BbmeError (ERR_STATE) unless both frames of the pair have colour.  Read it only."""
+        if which not in (0, 1):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "frame_bgr_tensor: which = %r (0 or 1)" % (which,))
+        return self._hbm_view(self.bgr_frames_device_ptrs(pair)[int(which)], (self.orig_height, self.orig_width, 3), "|u1")
+
     def _hbm_view(self, ptr, shape, typestr):
         """A torch view of memory the context owns (no copy; valid while the context lives and holds what it held)."""
         import torch
@@ -938,6 +1020,10 @@ class MFBatch(MF):
         """MF.temporal_filter of frame `which` of one pair."""
         return self._get_temporal_filtered(pair, which, strength, out, "get_frame_filtered")
 
+    def get_frame_filtered_bgr(self, pair, which, strength, out=None):
+        """MF.temporal_filter_bgr of frame `which` of one pair."""
+        return self._get_temporal_filtered_bgr(pair, which, strength, out, "get_frame_filtered_bgr")
+
     def compensation_errors(self, level=0, block=2, window=None):
         """MF.compensation_error of every pair, in order, from one launch."""
         return self._compensation_stats(level, block, window)
@@ -1043,6 +1129,23 @@ class MFChain(MFBatch):
         self._behind_torch(frames)
         _capi.check(self._lib.bbme_temporal_filter_chain_device(self._ctx, first, count, int(strength), C.c_void_p(frames.data_ptr()),
                                                                 w, h * w, None))
+        self.synchronize()
+        return frames.cpu().numpy()
+
+    def temporal_filter_run_bgr(self, strength, first=0, count=None):
+        """temporal_filter_run() in colour: the stored B,G,R frames of slots first .. first + count - 1 (default: to the last)
+        filtered from one launch -> (count, H, W, 3) uint8, unpadded."""
+        import torch
+        first = int(first)
+        count = self.batch + 1 - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.batch + 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_run_bgr: slots %d .. %d of a chain of %d"
+                                  % (first, first + count - 1, self.batch + 1))
+        h, w = self.orig_height, self.orig_width
+        frames = torch.empty((count, h, w, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._behind_torch(frames)
+        _capi.check(self._lib.bbme_temporal_filter_bgr_chain_device(self._ctx, first, count, int(strength),
+                                                                    C.c_void_p(frames.data_ptr()), 3 * w, 3 * h * w, None))
         self.synchronize()
         return frames.cpu().numpy()
 
@@ -1174,6 +1277,44 @@ def temporal_filter_cells(cur, prev=None, next=None, to_prev=None, to_next=None,
 
     _capi.check(_capi.lib().bbme_temporal_filter_host(ptr(planes[0]), cur.ctypes.data, ptr(planes[1]), w, h, ptr(grids[0]),
                                                       ptr(grids[1]), int(strength), win, out.ctypes.data, wmap.ctypes.data, s))
+    return out, wmap, dict(zip(TEMPORAL_STAT_KEYS, list(s)))
+
+
+def temporal_filter_cells_bgr(cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, pad_x=0, pad_y=0, window=None):
+    """The BGR temporal filter rule of include/bbme.h on the CPU (bbme_temporal_filter_bgr_host): cur, prev, next uint8 (H, W, 3)
+    colour frames, read as if zero-padded by (pad_x, pad_y) to an even H0 x W0, to_prev, to_next int16 (H0 / 2, W0 / 2, 2) cell
+    grids on cur; a neighbour is its frame and its grid, either may be None -> (frame (H, W, 3) uint8, weights (H0 / 2, W0 / 2)
+    uint8 holding wP | wN << 4, dict(prev_cells, next_cells, weight, change) over window (cx0, cy0, cw, ch) in cells, None = all
+    cells)."""
+    cur = np.ascontiguousarray(cur, np.uint8)
+    if cur.ndim != 3 or cur.shape[2] != 3:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: uint8 frames of one shape (H, W, 3)")
+    h, w = cur.shape[:2]
+    pad_x, pad_y = int(pad_x), int(pad_y)
+    h0, w0 = h + 2 * pad_y, w + 2 * pad_x
+    if pad_x < 0 or pad_y < 0 or h0 % 2 or w0 % 2:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: paddings >= 0 that make the padded size even")
+    frames, grids = [], []
+    for frame, grid in ((prev, to_prev), (next, to_next)):
+        frame = None if frame is None else np.ascontiguousarray(frame, np.uint8)
+        grid = None if grid is None else np.ascontiguousarray(grid, np.int16)
+        if frame is not None and frame.shape != cur.shape:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: uint8 frames of one shape (H, W, 3)")
+        if grid is not None and grid.shape != (h0 // 2, w0 // 2, 2):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: int16 grids of shape (H0 / 2, W0 / 2, 2)")
+        frames.append(frame)
+        grids.append(grid)
+    out = np.empty((h, w, 3), np.uint8)
+    wmap = np.empty((h0 // 2, w0 // 2), np.uint8)
+    s = (C.c_ulonglong * 4)()
+    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+
+    def ptr(a):
+        return None if a is None else a.ctypes.data
+
+    _capi.check(_capi.lib().bbme_temporal_filter_bgr_host(ptr(frames[0]), cur.ctypes.data, ptr(frames[1]), w, h, pad_x, pad_y,
+                                                          ptr(grids[0]), ptr(grids[1]), int(strength), win, out.ctypes.data,
+                                                          wmap.ctypes.data, s))
     return out, wmap, dict(zip(TEMPORAL_STAT_KEYS, list(s)))
 
 

@@ -436,16 +436,20 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
 
 
 def denoise_frames(frames, search_size, block_size, strength, device=None, in_flight=4, batch=2):
-    """Motion-compensated temporal denoising of a grey video on ONE GPU (the temporal filter rule of include/bbme.h): every
+    """Motion-compensated temporal denoising of a video on ONE GPU (the temporal filter rule of include/bbme.h): every
     frame averaged with its two motion-aligned neighbours wherever their 2x2 cells match better than `strength` -> len(frames)
-    unpadded uint8 (H, W) frames.  The first and the last frame of the video have one neighbour, every other frame two, the
-    frames at round and segment boundaries included.  Runs on the chain plan of estimate_frames_bidirectional (same contexts,
+    unpadded uint8 (H, W) frames.  A COLOUR video, (H, W, 3) frames in B,G,R order, gives (H, W, 3) frames by the BGR temporal
+    filter rule: the motion is estimated on the luma and the weights come from the colour frames (this function used to promise
+    grey frames only; what it did with colour ones was never defined).  The first and the last frame of the video have one
+    neighbour, every other frame two, the frames at round and segment boundaries included.  Runs on the chain plan of estimate_frames_bidirectional (same contexts,
     rounds and padding of a short round): every frame is set once and every pair estimated once, both ways.  A round's inner
     frames come from one launch (MFChain.temporal_filter_run).  A frame at a boundary -- the last of one round and the first
     of the next, of the same context (carried by advance) or of the neighbouring one -- has its previous frame and the grid
     into it in one round and its next frame and the grid into that in the other: the round that comes first copies its half on
     the GPU (planes and grid; the roll and the next estimate overwrite them) and the other filters the frame through
-    MF.cells_temporal_filter_device from the copies and its own buffers.  No plane or grid goes through the host."""
+    MF.cells_temporal_filter_device from the copies and its own buffers.  No plane or grid goes through the host.  In colour
+    the same plan, rounds and copies, of the stored colour frames in the planes' place (MFChain.temporal_filter_run_bgr,
+    MF.frame_bgr_tensor, MF.cells_temporal_filter_bgr_device)."""
     from .motion_framework import MFChain
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     n_pairs = len(frames) - 1
@@ -455,6 +459,7 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
         device = local_device()
     import torch
     strength = int(strength)
+    bgr = frames[0].ndim == 3
     per = max(1, min(batch, in_flight, n_pairs))
     n_slots = max(1, in_flight // per)
     rounds = plan_frame_segments(n_pairs, n_slots, per)
@@ -466,11 +471,15 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
 
     def boundary(mf, g, prev, to_prev, cur, nxt, to_next):
         flt = torch.empty_like(cur)
-        mf.cells_temporal_filter_device(cur, prev, nxt, to_prev, to_next, strength, out=flt)
+        (mf.cells_temporal_filter_bgr_device if bgr else mf.cells_temporal_filter_device)(cur, prev, nxt, to_prev, to_next, strength,
+                                                                                          out=flt)
         mf.synchronize()
         keep(mf, g, flt.cpu().numpy())
 
     def keep(mf, g, plane):
+        if bgr:                                            # the colour calls write the unpadded frame
+            out[g] = np.ascontiguousarray(plane)
+            return
         h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
         out[g] = np.ascontiguousarray(plane[py:py + h, px:px + w])
 
@@ -478,25 +487,27 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
         first, count = pending[slot]
         pending[slot] = None
         mf = chains[slot]
+        frame_tensor = mf.frame_bgr_tensor if bgr else mf.frame_plane_tensor
         lo = 0 if first == 0 else 1                        # the video's first frame has no previous one anywhere: the chain's own slot 0
         if count > lo:
-            for q, plane in enumerate(mf.temporal_filter_run(strength, lo, count - lo)):      # waits for this context's stream only
+            run = mf.temporal_filter_run_bgr if bgr else mf.temporal_filter_run
+            for q, plane in enumerate(run(strength, lo, count - lo)):      # waits for this context's stream only
                 keep(mf, first + lo + q, plane)
         else:
             mf.synchronize()
         with torch.cuda.device(device):
             # the round's first frame: its next half is here
             if first > 0:
-                half = (mf.frame_plane_tensor(0, 0), mf.frame_plane_tensor(0, 1), mf.cells_tensor(0))
+                half = (frame_tensor(0, 0), frame_tensor(0, 1), mf.cells_tensor(0))
                 if first in before:
                     boundary(mf, first, *before.pop(first), *half)
                 else:
                     after[first] = tuple(t.clone() for t in half)
             # the round's last frame: its previous half is here
             last = first + count
-            half = (mf.frame_plane_tensor(count - 1, 0), mf.backward_cells_tensor(count - 1))
+            half = (frame_tensor(count - 1, 0), mf.backward_cells_tensor(count - 1))
             if last == n_pairs:
-                boundary(mf, last, *half, mf.frame_plane_tensor(count - 1, 1), None, None)
+                boundary(mf, last, *half, frame_tensor(count - 1, 1), None, None)
             elif last in after:
                 boundary(mf, last, *half, *after.pop(last))
             else:

@@ -606,7 +606,8 @@ int bbme_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int pa
  * On a context with its own fields (bbme_estimate_bidirectional) the grid into the previous frame is the BACKWARD cells of the
  * pair the frame is image 2 of, and the grid into the next frame the FORWARD cells of the pair it is image 1 of: both live on
  * the frame itself.  A context made for up-sampled frames filters its 4x planes; on a colour context the planes are the luma and
- * that is what is filtered (applying the weights to the stored B,G,R frames is a follow-up, not part of this interface).
+ * that is what these calls filter, exactly as on a grey context; the colour frames themselves are filtered by the BGR TEMPORAL
+ * FILTER RULE below, which takes its weights from the colour frames and not from the luma (the table there says why).
  * Errors: BBME_ERR_INVALID for a null context or required pointer, pair / which / first / count out of range, thr outside
  * 1..1021, out_pitch < W0, weights_pitch < CW, out_stride below one frame (out_pitch H0) when count > 1, a window as for the
  * consistency rule, exactly one of a neighbour's plane and grid, no neighbour at all, a d_out of bbme_cells_temporal_filter_device
@@ -649,6 +650,67 @@ int bbme_temporal_filter_chain_device(bbme_ctx *ctx, int first, int count, int t
 int bbme_get_temporal_filtered_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
 int bbme_temporal_filter_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 int bbme_frame_plane_device(bbme_ctx *ctx, int pair, int which, int level, const uint8_t **d_plane);
+
+/* BGR TEMPORAL FILTER RULE (this project's own).  Inputs: the W x H B,G,R frame C to filter; optionally the previous frame P with
+ * the cell grid GP on C that points into P; optionally the next frame N with the cell grid GN; the paddings pad_x, pad_y >= 0 with
+ * W0 = W + 2 pad_x and H0 = H + 2 pad_y both even; a strength thr, 1 <= thr <= 1021.  Grids are CH x CW int16 (dx, dy) pairs,
+ * CH = H0 / 2, CW = W0 / 2: the geometry a context's cells have.  Every frame is read as if zero-padded to W0 x H0: the pixel at
+ * the padded position (X, Y) is frame pixel (X - pad_x, Y - pad_y), and 0 in every channel outside [0, W) x [0, H).  All
+ * arithmetic is in 32-bit integers; every division is the floor division of non-negative numbers.
+ * For cell (cx, cy) with origin o = (2 cx, 2 cy) and each present neighbour X (P or N) with grid G:
+ *   p = o + G[cy][cx], valid when 0 <= p.x <= W0 - 2 and 0 <= p.y <= H0 - 2 (the grey rule's validity);
+ *   cost_c = sum over the four pixels 0 <= i, j < 2 of |C[o + (j, i)][c] - X[p + (j, i)][c]|   for each channel c;
+ *   cost = max(cost_B, cost_G, cost_R), 0..1020;
+ *   w = 8 (thr - cost) / thr if the neighbour is valid and cost < thr, else 0.
+ * With S = 8 + wP + wN, every channel of every pixel of the cell is
+ *   out[o + (j, i)] = (8 C[o + (j, i)] + wP P[pP + (j, i)] + wN N[pN + (j, i)] + S / 2) / S.
+ * The output is the UNPADDED W x H frame: with an odd padding cells straddle the frame's edge and only their pixels inside the
+ * frame are written.  The weight map is the grey one, a byte wP | wN << 4 per cell of the padded view.  The statistics over a
+ * window in cells: cells with wP > 0, cells with wN > 0, the sum of wP + wN, and the sum of |out - C| over the window's cells' four
+ * pixels and three channels, on the padded view (a cell outside the frame is all-zero on C and counts like any other).
+ * On frames with B = G = R the three costs are equal and the rule is the grey one: every channel of the frame is the unpadded
+ * window of the grey result on that (zero-padded) plane, the map and the first three statistics are the grey ones, and the fourth
+ * is three times the grey one.
+ * WHY NOT THE LUMA'S WEIGHTS.  A 2x2 luma SAD below the strength says almost nothing about B, whose luma weight is 0.114: cells
+ * that differ in B or R pass and ghost.  PSNR gain in dB of the filtered middle frame over the noisy one, interior only, worst
+ * channel over the nine cases of tests/test_temporal_filter_cpu.py's quality test with one independent texture per channel and
+ * the fields estimated on the luma of the noisy frames (tests/test_temporal_filter_bgr_cpu.py holds the rule's column and that the
+ * luma's does worse):
+ *     weights from                              two-sided    one-sided
+ *     the luma SAD                                +0.71        -1.33
+ *     (SAD_B + 2 SAD_G + SAD_R + 2) >> 2          +3.61        +1.76
+ *     max(SAD_B, SAD_G, SAD_R)  (this rule)       +3.90        +2.14
+ * The grey rule reaches 3.82 and 1.99 on the same videos in grey.  The rule reads no luma plane.
+ * The context-level calls follow the grey ones in everything the rule does not change -- neighbours (image 1 its next, image 2
+ * its previous one; a chain slot both where they exist), grids (the backward cells of the pair the frame is image 2 of, the forward
+ * cells of the pair it is image 1 of), refusals, direction FORWARD, "changes no context state", scratch buffers of their own -- on
+ * the stored colour (the COLOUR STORE above), and add: BBME_ERR_STATE when a frame they read (the frame or a neighbour the rule gives
+ * it; for the statistics every frame) has no stored colour, as after a grey setter of that frame; BBME_ERR_INVALID for
+ * out_pitch < 3 W, bgr_pitch < 3 W, an out_stride below one frame (out_pitch H) when count > 1.
+ * bbme_temporal_filter_bgr_host: the rule on the CPU, no GPU: packed width x height frames, packed grids, out packed 3 width x
+ * height, weights packed CH x CW; out, weights and stats4 each may be NULL, not all three; BBME_ERR_INVALID for an odd W0 or H0,
+ * negative pads and the grey host call's refusals.
+ * bbme_cells_temporal_filter_bgr_device: ANY three colour frames in HBM with one common pitch bgr_pitch >= 3 W and ANY two grids
+ * of the context's cell geometry; no frames set and no estimate needed; d_out (rows out_pitch >= 3 W bytes apart, any alignment),
+ * d_weights and d_stats4 each may be null, not all three; d_out must not overlap an input frame; on hip_stream (NULL = the ctx
+ * stream; another stream is first ordered behind it); no host wait.  Launches with d_stats4 share one scratch buffer per context.
+ * bbme_temporal_filter_bgr_device: frame `which` of `pair` from the stored colour and the context's own fields.
+ * bbme_temporal_filter_bgr_chain_device: chain contexts only; slots first .. first + count - 1 from ONE launch, frame q at
+ * d_out + q out_stride.
+ * bbme_get_temporal_filtered_bgr_host: one frame as bbme_temporal_filter_bgr_device; synchronises; packed rows of 3 W bytes.
+ * bbme_temporal_filter_bgr_stats: EVERY frame of the context from one launch; synchronises; laid out as bbme_temporal_filter_stats. */
+int bbme_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height, int pad_x,
+                                  int pad_y, const int16_t *to_prev, const int16_t *to_next, int thr, const int *window,
+                                  uint8_t *out, uint8_t *weights, unsigned long long *stats4);
+int bbme_cells_temporal_filter_bgr_device(bbme_ctx *ctx, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                          int bgr_pitch, const int16_t *d_to_prev, const int16_t *d_to_next, int thr,
+                                          const int *window, uint8_t *d_out, int out_pitch, uint8_t *d_weights, int weights_pitch,
+                                          unsigned long long *d_stats4, void *hip_stream);
+int bbme_temporal_filter_bgr_device(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream);
+int bbme_temporal_filter_bgr_chain_device(bbme_ctx *ctx, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                          size_t out_stride, void *hip_stream);
+int bbme_get_temporal_filtered_bgr_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
+int bbme_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
