@@ -76,6 +76,30 @@ private:
     size_t bytes_ = 0;
 };
 
+// Statistics scratch of a gather stage (k_motion_compensate .. k_temporal_filter_bgr): `slots` result quadruples (one per pair or
+// frame, filled by k_mc_reduce), then the kernel's partials, four words per workgroup -- `groups` per pair or frame --, of a launch
+// over everything the context holds (`all` pairs or frames), then those of a caller's launch over `caller` more.  The layout is
+// the stage's (layout() names the same one at every call); how the buffer may grow is its caller's business.
+struct StatsScratch {
+    void layout(int slots, long long groups, int all) { slots_ = slots; groups_ = groups; all_ = all; }
+    size_t words(int caller) const { return (size_t)4 * (slots_ + groups_ * (all_ + caller)); }
+    size_t size() const { return buf_.size(); }
+    int ensure(int caller, const char *what) { return buf_.ensure(words(caller), what); }
+    int ensure(int slots, long long groups, int all, int caller, const char *what)
+    {
+        layout(slots, groups, all);
+        return ensure(caller, what);
+    }
+    unsigned long long *results() const { return buf_; }
+    unsigned long long *partials_all() const { return buf_ + (size_t)4 * slots_; }
+    unsigned long long *partials_caller() const { return buf_ + words(0); }
+
+private:
+    DevBuf<unsigned long long> buf_;
+    int slots_ = 0, all_ = 0;
+    long long groups_ = 0;
+};
+
 struct DevEvent {
     hipEvent_t ev = nullptr;
     DevEvent() = default;
@@ -280,16 +304,15 @@ struct bbme_ctx {
     // scratch of single entry points, allocated on their first use (DevBuf::ensure)
     DevBuf<double> epe_scratch;                   // partial sums + counts of bbme_calculate_mse_device
     DevBuf<uint8_t> fb_mask;                      // bbme_get_consistency_host: a packed CH x CW mask before its download
-    DevBuf<unsigned long long> fb_stats;          // consistency statistics: 4 words per pair, then the partials of k_fb_consistency of
-                                                  // bbme_consistency_stats (every pair) and of bbme_cells_consistency_device (one pair)
+    StatsScratch fb_stats;                        // bbme_consistency_stats (every pair) and bbme_cells_consistency_device (one pair)
     DevBuf<uint8_t> raw;                          // the host setters' upload buffer: one unpadded grey frame per slot
     DevBuf<float> sub;                            // bbme_get_subsampled_flow_host: the packed field before its download (grown to
                                                   // the largest asked for)
     DevBuf<uint8_t> mc_plane;                     // bbme_get_motion_compensated_host: a level-0-sized plane before its download
-    DevBuf<unsigned long long> mc_stats;          // bbme_compensation_error: 4 words per pair, then the partials of k_motion_compensate
+    StatsScratch mc_stats;                        // bbme_compensation_error (every pair)
     DevBuf<uint8_t> ip_plane;                     // bbme_get_interpolated_host: a packed W0 x H0 frame before its download
-    DevBuf<unsigned long long> ip_stats;          // interpolation statistics: 4 words per pair, then the partials of k_interpolate of
-                                                  // bbme_interpolation_stats (every pair) and of bbme_cells_interpolate_device (every phase)
+    StatsScratch ip_stats;                        // bbme_interpolation_stats (every pair) and bbme_cells_interpolate_device (one pair,
+                                                  // every phase): grows with the phases
     DevBuf<uint32_t> color_range;                 // colour coding: the key words of every slot (pair 0 .. batch - 1, then the slot of
                                                   // bbme_cells_color_device; k_color_range), then five floats per slot
     DevBuf<uint8_t> color_img;                    // bbme_get_flow_color_host: the packed B,G,R image before its download (grown to
@@ -302,11 +325,9 @@ struct bbme_ctx {
     std::vector<uint8_t> bgr_set;
     DevBuf<uint8_t> ip_bgr;                       // bbme_get_interpolated_bgr_host: a packed 3 W x H frame before its download
     DevBuf<uint8_t> tf_plane;                     // bbme_get_temporal_filtered_host: a packed W0 x H0 frame before its download
-    DevBuf<unsigned long long> tf_stats;          // temporal filter statistics: 4 words per frame, then the partials of k_temporal_filter
-                                                  // of bbme_temporal_filter_stats (every frame) and of bbme_cells_temporal_filter_device (one)
+    StatsScratch tf_stats;                        // bbme_temporal_filter_stats (every frame) and bbme_cells_temporal_filter_device (one)
     DevBuf<uint8_t> tf_bgr;                       // bbme_get_temporal_filtered_bgr_host: a packed 3 W x H frame before its download
-    DevBuf<unsigned long long> tf_bgr_stats;      // tf_stats' layout for k_temporal_filter_bgr (bbme_temporal_filter_bgr_stats,
-                                                  // bbme_cells_temporal_filter_bgr_device)
+    StatsScratch tf_bgr_stats;                    // the same of bbme_temporal_filter_bgr_stats and bbme_cells_temporal_filter_bgr_device
 };
 
 namespace {
@@ -1776,6 +1797,102 @@ int bbme_get_subsampled_flow_host(bbme_ctx *c, int pair, int scale, float *out)
     return check_converged(c);
 }
 
+}  // extern "C": the stages from here on share templates, which need C++ linkage; their entry points have C linkage from bbme.h
+
+// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter) ----
+// Every stage is one launch in which a lane takes runs of 4 units (pixels or cells) along a row, over (workgroups, pairs, phases
+// or frames), with optional statistics: the kernel's partials, then k_mc_reduce.  One run split, one launch path, one scratch
+// layout, one pair of output checks and one pair of download helpers serve all of them.
+
+// workgroups of a launch whose lanes take up to runs_per_lane runs each
+static long long gather_groups(int units_per_row, int rows, int runs_per_lane)
+{
+    return ((long long)(units_per_row + 3) / 4 * rows + 256 * runs_per_lane - 1) / (256 * runs_per_lane);
+}
+
+// the stages on level 0's 2x2 cells
+static long long cell_groups(const bbme_ctx *c, int runs_per_lane)
+{
+    return gather_groups(c->lv[0].width / 2, c->lv[0].height / 2, runs_per_lane);
+}
+
+template <class Args>
+static void set_runs(Args &a, int units_per_row, int rows)
+{
+    a.runs_per_row = (units_per_row + 3) / 4;
+    a.runs = (long long)a.runs_per_row * rows;
+}
+
+// `kernel` over (groups, pairs, count) and, with d_stats, k_mc_reduce of its partials at `partial` into d_stats[4 (y count + z) ..]
+// (k_interpolate: 4 (z pairs + y))
+template <class Args>
+static int launch_gather(void (*kernel)(Args), Args &a, long long groups, int pairs, int count, unsigned long long *partial,
+                         unsigned long long *d_stats, hipStream_t stream)
+{
+    a.partial = d_stats ? partial : nullptr;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)groups, (unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
+    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)(pairs * count)), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+// A frame or map that a caller brings: pitch at least a row; with more than one frame, stride at least a frame.  Touches no device.
+static int check_frames(int count, int pitch, size_t stride, int min_pitch, int rows, const char *what, const char *which)
+{
+    if (pitch < min_pitch) return bbme::fail(BBME_ERR_INVALID, "%s: %s pitch %d < %d", what, which, pitch, min_pitch);
+    if (count > 1 && stride < (size_t)pitch * rows)
+        return bbme::fail(BBME_ERR_INVALID, "%s: %s stride %zu < one frame of %d rows of %d bytes", what, which, stride, rows, pitch);
+    return BBME_OK;
+}
+
+// the same of B,G,R frames of the context's size
+static int check_bgr_frames(const bbme_ctx *c, int count, int pitch, size_t stride, const char *what)
+{
+    if ((long long)pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x frame width %d", what, pitch, c->geom.width);
+    return check_frames(count, pitch, stride, pitch, c->geom.height, what, "output");
+}
+
+// A frame is written while other lanes still gather from the inputs: an output inside an input is a race, not a result.
+// Frames of `rows` rows of row_bytes, the output's out_pitch and the inputs' in_pitch bytes apart; a null input is absent.
+static bool overlaps_input(const uint8_t *d_out, int out_pitch, std::initializer_list<const uint8_t *> inputs, int in_pitch,
+                           int row_bytes, int rows)
+{
+    const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (size_t)out_pitch * (rows - 1) + (size_t)row_bytes;
+    for (const uint8_t *in : inputs) {
+        const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (size_t)in_pitch * (rows - 1) + (size_t)row_bytes;
+        if (in && o0 < i1 && i0 < o1) return true;
+    }
+    return false;
+}
+
+// the forward and the backward 2x2 cells of `pair` of the context's own bidirectional estimate
+static void own_fields(const bbme_ctx *c, int pair, const mv_t **f, const mv_t **b)
+{
+    const Level &L = c->lv[0];
+    *f = L.final_grid() + (size_t)pair * L.grid_stride(L.final_grid());
+    *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
+}
+
+// What the host getters share: `bytes` of `staging`, filled by enqueue(staging) on the context's stream, copied down; waits.
+template <class Enqueue>
+static int download_staged(bbme_ctx *c, DevBuf<uint8_t> &staging, size_t bytes, const char *staging_what, uint8_t *out, Enqueue enqueue)
+{
+    if (int rc = staging.ensure(bytes, staging_what)) return rc;
+    if (int rc = enqueue(staging.get())) return rc;
+    HIP_TRY(hipMemcpyAsync(out, staging, bytes, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+// What the statistics calls share: enqueue() on the context's stream, the first n result quadruples of `s` copied down; waits.
+template <class Enqueue>
+static int download_stats(bbme_ctx *c, const StatsScratch &s, int n, unsigned long long *stats, Enqueue enqueue)
+{
+    if (int rc = enqueue()) return rc;
+    HIP_TRY(hipMemcpyAsync(stats, s.results(), (size_t)4 * sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
 // ---- motion compensation: MF::draw_MVimage (motion_framework.cpp:887-905) and its residual statistics ---------------------
 
 // The arguments every motion-compensation entry point shares (include/bbme.h): level, block size, fill and window are valid,
@@ -1797,13 +1914,10 @@ static int check_mc_state(const bbme_ctx *c, int level, const char *what)
     return BBME_OK;
 }
 
-static long long mc_groups(const Level &L)
-{
-    return ((long long)(L.width + 3) / 4 * L.height + 256 * kMcRunsPerLane - 1) / (256 * kMcRunsPerLane);
-}
+static long long mc_groups(const Level &L) { return gather_groups(L.width, L.height, kMcRunsPerLane); }
 
 // k_motion_compensate over `pairs` pairs from `pair0` on: the frame into d_out (one pair only) and/or, with d_stats, the
-// statistics (k_mc_reduce adds the partials, kept behind the 4 words per pair of c->mc_stats, into d_stats[4 p ..])
+// statistics (partials in c->mc_stats)
 static int enqueue_mc(bbme_ctx *c, int pair0, int pairs, int level, int block, int fill, const int *window, uint8_t *d_out,
                       int out_pitch, unsigned long long *d_stats, hipStream_t stream)
 {
@@ -1815,20 +1929,14 @@ static int enqueue_mc(bbme_ctx *c, int pair0, int pairs, int level, int block, i
     a.img2 = c->plane2(L) + (size_t)pair0 * a.plane_stride;
     a.grid = L.cur_grid + (size_t)pair0 * a.grid_stride;
     a.out = d_out;
-    a.partial = d_stats ? c->mc_stats + (size_t)4 * BBME_MAX_BATCH : nullptr;
     a.width = L.width; a.height = L.height;
     a.gcols = L.width / L.cur_block;
     a.lcb = __builtin_ctz((unsigned)L.cur_block);
     a.lb = __builtin_ctz((unsigned)block);
     a.fill = fill; a.out_pitch = out_pitch;
     set_window(a, window, L.width, L.height);
-    a.runs_per_row = (L.width + 3) / 4;
-    a.runs = (long long)a.runs_per_row * L.height;
-    const long long groups = mc_groups(L);
-    hipLaunchKernelGGL(k_motion_compensate, dim3((unsigned)groups, (unsigned)pairs), dim3(256), 0, stream, a);
-    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)pairs), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
-    HIP_TRY(hipGetLastError());
-    return BBME_OK;
+    set_runs(a, L.width, L.height);
+    return launch_gather(k_motion_compensate, a, mc_groups(L), pairs, 1, c->mc_stats.partials_all(), d_stats, stream);
 }
 
 int bbme_motion_compensate_device(bbme_ctx *c, int pair, int level, int block, int fill, uint8_t *d_out, int out_pitch,
@@ -1857,9 +1965,9 @@ int bbme_get_motion_compensated_host(bbme_ctx *c, int pair, int level, int block
     HIP_TRY(hipSetDevice(c->device));
     const Level &L = c->lv[level];
     if (int rc = c->mc_plane.ensure((size_t)c->lv[0].width * c->lv[0].height, "the compensated plane")) return rc;   // level 0 is the largest
-    if (int rc = enqueue_mc(c, pair, 1, level, block, fill, nullptr, c->mc_plane, L.width, nullptr, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->mc_plane, (size_t)L.width * L.height, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    return download_staged(c, c->mc_plane, (size_t)L.width * L.height, "the compensated plane", out, [&](uint8_t *d) {
+        return enqueue_mc(c, pair, 1, level, block, fill, nullptr, d, L.width, nullptr, c->stream);
+    });
 }
 
 int bbme_compensation_error(bbme_ctx *c, int level, int block, const int *window, unsigned long long *stats)
@@ -1869,12 +1977,11 @@ int bbme_compensation_error(bbme_ctx *c, int level, int block, const int *window
     if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
     if (int rc = check_mc_state(c, level, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)4 * sizeof(unsigned long long) * c->batch;
-    // the result words of every pair, then one partial per pair and workgroup of level 0 (the largest plane)
-    if (int rc = c->mc_stats.ensure((size_t)4 * (BBME_MAX_BATCH + mc_groups(c->lv[0]) * c->batch), "the compensation statistics")) return rc;
-    if (int rc = enqueue_mc(c, 0, c->batch, level, block, 0, window, nullptr, 0, c->mc_stats, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(stats, c->mc_stats, bytes, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    // one partial per pair and workgroup of level 0 (the largest plane); no caller's launch has statistics
+    if (int rc = c->mc_stats.ensure(BBME_MAX_BATCH, mc_groups(c->lv[0]), c->batch, 0, "the compensation statistics")) return rc;
+    return download_stats(c, c->mc_stats, c->batch, stats, [&] {
+        return enqueue_mc(c, 0, c->batch, level, block, 0, window, nullptr, 0, c->mc_stats.results(), c->stream);
+    });
 }
 
 // ---- forward-backward consistency of two cell grids (the rule of include/bbme.h; k_fb_consistency) -----------------------------
@@ -1907,19 +2014,12 @@ static int check_fb(int cells_w, int cells_h, int tol, const int *window, const 
     return check_window(window, cells_w, cells_h, what, -1);
 }
 
-static long long fb_groups(const Level &L0)
-{
-    return ((long long)(L0.width / 2 + 3) / 4 * (L0.height / 2) + 256 * kFbRunsPerLane - 1) / (256 * kFbRunsPerLane);
-}
-
-// the result words of every pair, then the partials of a launch over every pair, then those of a one-pair launch
 static int fb_scratch(bbme_ctx *c)
 {
-    return c->fb_stats.ensure((size_t)4 * (BBME_MAX_BATCH + fb_groups(c->lv[0]) * (c->batch + 1)), "the consistency statistics");
+    return c->fb_stats.ensure(BBME_MAX_BATCH, cell_groups(c, kFbRunsPerLane), c->batch, 1, "the consistency statistics");
 }
 
 // k_fb_consistency over `pairs` pairs: the mask (rows mask_pitch, pairs s_mask bytes apart) and / or, with d_stats, the statistics
-// (k_mc_reduce adds the partials at `partial` into d_stats[4 p ..])
 static int enqueue_fb(bbme_ctx *c, const mv_t *d_a, uint32_t s_a, const mv_t *d_b, uint32_t s_b, int pairs, int tol, const int *window,
                       uint8_t *d_mask, int mask_pitch, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
 {
@@ -1927,16 +2027,10 @@ static int enqueue_fb(bbme_ctx *c, const mv_t *d_a, uint32_t s_a, const mv_t *d_
     FbArgs a{};
     a.a = d_a; a.b = d_b; a.s_a = s_a; a.s_b = s_b;
     a.mask = d_mask; a.mask_pitch = mask_pitch; a.s_mask = 0;
-    a.partial = d_stats ? partial : nullptr;
     a.cw = L.width / 2; a.ch = L.height / 2; a.tol = tol;
     set_window(a, window, a.cw, a.ch);
-    a.runs_per_row = (a.cw + 3) / 4;
-    a.runs = (long long)a.runs_per_row * a.ch;
-    const long long groups = fb_groups(L);
-    hipLaunchKernelGGL(k_fb_consistency, dim3((unsigned)groups, (unsigned)pairs), dim3(256), 0, stream, a);
-    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)pairs), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
-    HIP_TRY(hipGetLastError());
-    return BBME_OK;
+    set_runs(a, a.cw, a.ch);
+    return launch_gather(k_fb_consistency, a, cell_groups(c, kFbRunsPerLane), pairs, 1, partial, d_stats, stream);
 }
 
 int bbme_cells_consistency_device(bbme_ctx *c, const int16_t *d_a, const int16_t *d_b, int tol, const int *window, uint8_t *d_mask,
@@ -1953,9 +2047,8 @@ int bbme_cells_consistency_device(bbme_ctx *c, const int16_t *d_a, const int16_t
     if (d_stats4) if (int rc = fb_scratch(c)) return rc;
     hipStream_t stream;
     if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    unsigned long long *partial = d_stats4 ? c->fb_stats + (size_t)4 * (BBME_MAX_BATCH + fb_groups(L) * c->batch) : nullptr;
     return enqueue_fb(c, reinterpret_cast<const mv_t *>(d_a), 0, reinterpret_cast<const mv_t *>(d_b), 0, 1, tol, window, d_mask,
-                      mask_pitch, partial, d_stats4, stream);
+                      mask_pitch, c->fb_stats.partials_caller(), d_stats4, stream);
 }
 
 // A = the forward cells, B = the backward cells of `which` = BBME_DIR_FORWARD, the other way round for BBME_DIR_BACKWARD
@@ -1974,14 +2067,12 @@ int bbme_get_consistency_host(bbme_ctx *c, int pair, int which, int tol, uint8_t
     if (!mask) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
     if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
     HIP_TRY(hipSetDevice(c->device));
-    const Level &L = c->lv[0];
-    const int cw = L.width / 2, ch = L.height / 2;
-    if (int rc = c->fb_mask.ensure((size_t)cw * ch, "the consistency mask")) return rc;
-    const uint32_t s_f = L.grid_stride(L.final_grid());
-    const mv_t *f = L.final_grid() + (size_t)pair * s_f, *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
-    if (int rc = enqueue_fb(c, which ? b : f, 0, which ? f : b, 0, 1, tol, nullptr, c->fb_mask, cw, nullptr, nullptr, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(mask, c->fb_mask, (size_t)cw * ch, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
+    const mv_t *f, *b;
+    own_fields(c, pair, &f, &b);
+    return download_staged(c, c->fb_mask, (size_t)cw * ch, "the consistency mask", mask, [&](uint8_t *d) {
+        return enqueue_fb(c, which ? b : f, 0, which ? f : b, 0, 1, tol, nullptr, d, cw, nullptr, nullptr, c->stream);
+    });
 }
 
 int bbme_consistency_stats(bbme_ctx *c, int which, int tol, const int *window, unsigned long long *stats)
@@ -1995,10 +2086,10 @@ int bbme_consistency_stats(bbme_ctx *c, int which, int tol, const int *window, u
     const Level &L = c->lv[0];
     const uint32_t s_f = L.grid_stride(L.final_grid()), s_b = c->bwd_stride;
     const mv_t *f = L.final_grid(), *b = c->bwd_cells;
-    if (int rc = enqueue_fb(c, which ? b : f, which ? s_b : s_f, which ? f : b, which ? s_f : s_b, c->batch, tol, window, nullptr, 0,
-                            c->fb_stats + (size_t)4 * BBME_MAX_BATCH, c->fb_stats, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(stats, c->fb_stats, (size_t)4 * sizeof(unsigned long long) * c->batch, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    return download_stats(c, c->fb_stats, c->batch, stats, [&] {
+        return enqueue_fb(c, which ? b : f, which ? s_b : s_f, which ? f : b, which ? s_f : s_b, c->batch, tol, window, nullptr, 0,
+                          c->fb_stats.partials_all(), c->fb_stats.results(), c->stream);
+    });
 }
 
 // ---- colour coding of a cell grid: Flow::MotionToColor of the subsampled field (the colour rule of include/bbme.h) ----------
@@ -2169,57 +2260,46 @@ static int check_ip(const bbme_ctx *c, int num0, int count, int den, const int *
     return check_window(window, c->lv[0].width / 2, c->lv[0].height / 2, what, -1);
 }
 
-static int check_ip_frames(const bbme_ctx *c, int count, int pitch, size_t stride, int min_pitch, int rows, const char *what,
-                           const char *which)
-{
-    if (pitch < min_pitch) return bbme::fail(BBME_ERR_INVALID, "%s: %s pitch %d < %d", what, which, pitch, min_pitch);
-    if (count > 1 && stride < (size_t)pitch * rows)
-        return bbme::fail(BBME_ERR_INVALID, "%s: %s stride %zu < one frame of %d rows of %d bytes", what, which, stride, rows, pitch);
-    return BBME_OK;
-}
-
-static long long ip_groups(const Level &L0)
-{
-    return ((long long)(L0.width / 2 + 3) / 4 * (L0.height / 2) + 256 * kIpRunsPerLane - 1) / (256 * kIpRunsPerLane);
-}
-
-// the result words of every pair, then the partials of a launch over every pair, then those of a one-pair launch of `count`
-// phases; grown, behind both streams, when a launch of more phases comes
+// partials of a launch over every pair, then those of a one-pair launch of `count` phases; grown, behind both streams, when a
+// launch of more phases comes
 static int ip_scratch(bbme_ctx *c, int count, hipStream_t stream)
 {
-    const size_t need = (size_t)4 * (BBME_MAX_BATCH + ip_groups(c->lv[0]) * (c->batch + count));
-    if (need <= c->ip_stats.size()) return BBME_OK;
+    StatsScratch &s = c->ip_stats;
+    s.layout(BBME_MAX_BATCH, cell_groups(c, kIpRunsPerLane), c->batch);
+    if (s.words(count) <= s.size()) return BBME_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));             // the old buffer may still be being read
     if (stream != c->stream) HIP_TRY(hipStreamSynchronize(stream));
-    return c->ip_stats.ensure(need, "the interpolation statistics");
+    return s.ensure(count, "the interpolation statistics");
+}
+
+// what IpArgs and IpBgrArgs share: the planes of `pair0`, the two grids, the output frames, the phases and their division
+static void ip_fill(IpCommon &a, const bbme_ctx *c, int pair0, const mv_t *d_f, const mv_t *d_b, int num0, int den, uint8_t *d_out,
+                    int out_pitch, size_t out_stride)
+{
+    const Level &L = c->lv[0];
+    a.img1 = c->plane1(L) + (size_t)pair0 * L.plane_stride;
+    a.img2 = c->plane2(L) + (size_t)pair0 * L.plane_stride;
+    a.fwd = d_f; a.bwd = d_b;
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2;
+    a.num0 = num0; a.den = den;
+    a.magic = (uint32_t)((1ull << 32) / (unsigned)den + 1ull);
+    set_runs(a, a.cw, L.height / 2);
 }
 
 // k_interpolate over `pairs` pairs from `pair0` on and `count` phases from num0 on: frames and maps (one pair only) and / or, with
-// d_stats, the statistics (k_mc_reduce adds the partials at `partial` into d_stats[4 (phase pairs + p) ..])
+// d_stats, the statistics
 static int enqueue_ip(bbme_ctx *c, int pair0, int pairs, const mv_t *d_f, uint32_t s_f, const mv_t *d_b, uint32_t s_b, int num0,
                       int count, int den, const int *window, uint8_t *d_out, int out_pitch, size_t out_stride, uint8_t *d_sel,
                       int sel_pitch, size_t sel_stride, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
 {
-    const Level &L = c->lv[0];
     IpArgs a{};
-    a.plane_stride = L.plane_stride;
-    a.img1 = c->plane1(L) + (size_t)pair0 * a.plane_stride;
-    a.img2 = c->plane2(L) + (size_t)pair0 * a.plane_stride;
-    a.fwd = d_f; a.bwd = d_b; a.s_f = s_f; a.s_b = s_b;
-    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    ip_fill(a, c, pair0, d_f, d_b, num0, den, d_out, out_pitch, out_stride);
+    a.plane_stride = c->lv[0].plane_stride; a.s_f = s_f; a.s_b = s_b;
     a.sel = d_sel; a.sel_pitch = sel_pitch; a.sel_stride = sel_stride;
-    a.partial = d_stats ? partial : nullptr;
-    a.width = L.width; a.height = L.height; a.cw = L.width / 2; a.ch = L.height / 2;
-    a.num0 = num0; a.den = den;
-    a.magic = (uint32_t)((1ull << 32) / (unsigned)den + 1ull);
+    a.ch = a.height / 2;
     set_window(a, window, a.cw, a.ch);
-    a.runs_per_row = (a.cw + 3) / 4;
-    a.runs = (long long)a.runs_per_row * a.ch;
-    const long long groups = ip_groups(L);
-    hipLaunchKernelGGL(k_interpolate, dim3((unsigned)groups, (unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
-    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)(pairs * count)), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
-    HIP_TRY(hipGetLastError());
-    return BBME_OK;
+    return launch_gather(k_interpolate, a, cell_groups(c, kIpRunsPerLane), pairs, count, partial, d_stats, stream);
 }
 
 int bbme_cells_interpolate_device(bbme_ctx *c, int pair, const int16_t *d_fwd, const int16_t *d_bwd, int num0, int count, int den,
@@ -2231,16 +2311,15 @@ int bbme_cells_interpolate_device(bbme_ctx *c, int pair, const int16_t *d_fwd, c
     const Level &L = c->lv[0];
     if (!d_fwd || (!d_out && !d_sel && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
     if (int rc = check_ip(c, num0, count, den, window, what)) return rc;
-    if (d_out) if (int rc = check_ip_frames(c, count, out_pitch, out_stride, L.width, L.height, what, "output")) return rc;
-    if (d_sel) if (int rc = check_ip_frames(c, count, sel_pitch, sel_stride, L.width / 2, L.height / 2, what, "selection map")) return rc;
+    if (d_out) if (int rc = check_frames(count, out_pitch, out_stride, L.width, L.height, what, "output")) return rc;
+    if (d_sel) if (int rc = check_frames(count, sel_pitch, sel_stride, L.width / 2, L.height / 2, what, "selection map")) return rc;
     if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
     if (d_stats4) if (int rc = ip_scratch(c, count, stream)) return rc;
     if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    unsigned long long *partial = d_stats4 ? c->ip_stats + (size_t)4 * (BBME_MAX_BATCH + ip_groups(L) * c->batch) : nullptr;
     return enqueue_ip(c, pair, 1, reinterpret_cast<const mv_t *>(d_fwd), 0, reinterpret_cast<const mv_t *>(d_bwd), 0, num0, count, den,
-                      window, d_out, out_pitch, out_stride, d_sel, sel_pitch, sel_stride, partial, d_stats4, stream);
+                      window, d_out, out_pitch, out_stride, d_sel, sel_pitch, sel_stride, c->ip_stats.partials_caller(), d_stats4, stream);
 }
 
 // what the three calls on the context's own two fields share
@@ -2250,11 +2329,21 @@ static int check_ip_ctx(const bbme_ctx *c, int num0, int count, int den, const i
     return check_ip(c, num0, count, den, window, what);
 }
 
-static int check_ip_state(const bbme_ctx *c, const char *what)
+// frames and a valid bidirectional estimate: what interpolation and the temporal filter need of the context's own state
+static int check_fields_state(const bbme_ctx *c, const char *what)
 {
     if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
     if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
     return BBME_OK;
+}
+
+// the context's own two fields of `pair`, `count` phases into d_out on `stream`
+static int enqueue_own_ip(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
+                          hipStream_t stream)
+{
+    const mv_t *f, *b;
+    own_fields(c, pair, &f, &b);
+    return enqueue_ip(c, pair, 1, f, 0, b, 0, num0, count, den, nullptr, d_out, out_pitch, out_stride, nullptr, 0, 0, nullptr, nullptr, stream);
 }
 
 int bbme_interpolate_device(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
@@ -2263,15 +2352,13 @@ int bbme_interpolate_device(bbme_ctx *c, int pair, int num0, int count, int den,
     const char *what = "bbme_interpolate_device";
     if (int rc = check_pair(c, pair)) return rc;
     if (int rc = check_ip_ctx(c, num0, count, den, nullptr, what)) return rc;
-    const Level &L = c->lv[0];
     if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_ip_frames(c, count, out_pitch, out_stride, L.width, L.height, what, "output")) return rc;
-    if (int rc = check_ip_state(c, what)) return rc;
+    if (int rc = check_frames(count, out_pitch, out_stride, c->lv[0].width, c->lv[0].height, what, "output")) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t stream;
     if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    const mv_t *f = L.final_grid() + (size_t)pair * L.grid_stride(L.final_grid()), *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
-    return enqueue_ip(c, pair, 1, f, 0, b, 0, num0, count, den, nullptr, d_out, out_pitch, out_stride, nullptr, 0, 0, nullptr, nullptr, stream);
+    return enqueue_own_ip(c, pair, num0, count, den, d_out, out_pitch, out_stride, stream);
 }
 
 int bbme_get_interpolated_host(bbme_ctx *c, int pair, int num, int den, uint8_t *out)
@@ -2280,16 +2367,12 @@ int bbme_get_interpolated_host(bbme_ctx *c, int pair, int num, int den, uint8_t 
     if (int rc = check_pair(c, pair)) return rc;
     if (int rc = check_ip_ctx(c, num, 1, den, nullptr, what)) return rc;
     if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_ip_state(c, what)) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const Level &L = c->lv[0];
-    const size_t bytes = (size_t)L.width * L.height;
-    if (int rc = c->ip_plane.ensure(bytes, "the interpolated frame")) return rc;
-    const mv_t *f = L.final_grid() + (size_t)pair * L.grid_stride(L.final_grid()), *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
-    if (int rc = enqueue_ip(c, pair, 1, f, 0, b, 0, num, 1, den, nullptr, c->ip_plane, L.width, 0, nullptr, 0, 0, nullptr, nullptr, c->stream))
-        return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->ip_plane, bytes, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    return download_staged(c, c->ip_plane, (size_t)L.width * L.height, "the interpolated frame", out, [&](uint8_t *d) {
+        return enqueue_own_ip(c, pair, num, 1, den, d, L.width, 0, c->stream);
+    });
 }
 
 int bbme_interpolation_stats(bbme_ctx *c, int num, int den, const int *window, unsigned long long *stats)
@@ -2297,14 +2380,14 @@ int bbme_interpolation_stats(bbme_ctx *c, int num, int den, const int *window, u
     const char *what = "bbme_interpolation_stats";
     if (int rc = check_ip_ctx(c, num, 1, den, window, what)) return rc;
     if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_ip_state(c, what)) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = ip_scratch(c, 1, c->stream)) return rc;
     const Level &L = c->lv[0];
-    if (int rc = enqueue_ip(c, 0, c->batch, L.final_grid(), L.grid_stride(L.final_grid()), c->bwd_cells, c->bwd_stride, num, 1, den, window,
-                            nullptr, 0, 0, nullptr, 0, 0, c->ip_stats + (size_t)4 * BBME_MAX_BATCH, c->ip_stats, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(stats, c->ip_stats, (size_t)4 * sizeof(unsigned long long) * c->batch, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    return download_stats(c, c->ip_stats, c->batch, stats, [&] {
+        return enqueue_ip(c, 0, c->batch, L.final_grid(), L.grid_stride(L.final_grid()), c->bwd_cells, c->bwd_stride, num, 1, den, window,
+                          nullptr, 0, 0, nullptr, 0, 0, c->ip_stats.partials_all(), c->ip_stats.results(), c->stream);
+    });
 }
 
 // ---- colour frames out (the BGR interpolation rule of include/bbme.h; k_interpolate_bgr) -----------------------------------
@@ -2332,25 +2415,17 @@ int bbme_bgr_frames_device_pair(bbme_ctx *c, int pair, const uint8_t **d_bgr1, c
     return BBME_OK;
 }
 
-// k_interpolate_bgr over `count` phases from num0 on, one pair; bgr1 / bgr2 already in the direction's order
+// k_interpolate_bgr over `count` phases from num0 on, one pair; bgr1 / bgr2 already in the direction's order.  No statistics, no
+// map: its own launch.
 static int enqueue_ip_bgr(bbme_ctx *c, int pair, const mv_t *d_f, const mv_t *d_b, const uint8_t *bgr1, const uint8_t *bgr2, int bgr_pitch,
                           int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride, hipStream_t stream)
 {
-    const Level &L = c->lv[0];
     const Geometry &g = c->geom;
     IpBgrArgs a{};
-    a.img1 = c->plane1(L) + (size_t)pair * L.plane_stride;
-    a.img2 = c->plane2(L) + (size_t)pair * L.plane_stride;
-    a.fwd = d_f; a.bwd = d_b;
+    ip_fill(a, c, pair, d_f, d_b, num0, den, d_out, out_pitch, out_stride);
     a.bgr1 = bgr1; a.bgr2 = bgr2; a.bgr_pitch = bgr_pitch;
-    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
-    a.width = L.width; a.height = L.height; a.cw = L.width / 2;
     a.fw = g.width; a.fh = g.height; a.pad_x = g.pad_x; a.pad_y = g.pad_y;
-    a.num0 = num0; a.den = den;
-    a.magic = (uint32_t)((1ull << 32) / (unsigned)den + 1ull);
-    a.runs_per_row = (a.cw + 3) / 4;
-    a.runs = (long long)a.runs_per_row * (L.height / 2);
-    hipLaunchKernelGGL(k_interpolate_bgr, dim3((unsigned)ip_groups(L), 1, (unsigned)count), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(k_interpolate_bgr, dim3((unsigned)cell_groups(c, kIpRunsPerLane), 1, (unsigned)count), dim3(256), 0, stream, a);
     HIP_TRY(hipGetLastError());
     return BBME_OK;
 }
@@ -2361,9 +2436,7 @@ static int check_ip_bgr(const bbme_ctx *c, int num0, int count, int den, const u
 {
     if (int rc = check_ip(c, num0, count, den, nullptr, what)) return rc;
     if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if ((long long)out_pitch < 3LL * c->geom.width)
-        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x frame width %d", what, out_pitch, c->geom.width);
-    return check_ip_frames(c, count, out_pitch, out_stride, out_pitch, c->geom.height, what, "output");
+    return check_bgr_frames(c, count, out_pitch, out_stride, what);
 }
 
 int bbme_cells_interpolate_bgr_device(bbme_ctx *c, int pair, const int16_t *d_fwd, const int16_t *d_bwd, const uint8_t *d_bgr1,
@@ -2395,10 +2468,10 @@ int bbme_cells_interpolate_bgr_device(bbme_ctx *c, int pair, const int16_t *d_fw
 static int enqueue_own_ip_bgr(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
                               hipStream_t stream, const char *what)
 {
-    const Level &L = c->lv[0];
     const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
     if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
-    const mv_t *f = L.final_grid() + (size_t)pair * L.grid_stride(L.final_grid()), *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
+    const mv_t *f, *b;
+    own_fields(c, pair, &f, &b);
     return enqueue_ip_bgr(c, pair, f, b, bgr1, bgr2, 3 * c->geom.width, num0, count, den, d_out, out_pitch, out_stride, stream);
 }
 
@@ -2408,7 +2481,7 @@ int bbme_interpolate_bgr_device(bbme_ctx *c, int pair, int num0, int count, int 
     const char *what = "bbme_interpolate_bgr_device";
     if (int rc = check_pair(c, pair)) return rc;
     if (int rc = check_ip_bgr(c, num0, count, den, d_out, out_pitch, out_stride, what)) return rc;
-    if (int rc = check_ip_state(c, what)) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
     const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
     if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;       // before anything is enqueued
     HIP_TRY(hipSetDevice(c->device));
@@ -2423,268 +2496,19 @@ int bbme_get_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int den, uint
     if (int rc = check_pair(c, pair)) return rc;
     if (int rc = check_ip(c, num, 1, den, nullptr, what)) return rc;
     if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_ip_state(c, what)) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
     const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
     if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)3 * c->geom.width * c->geom.height;
-    if (int rc = c->ip_bgr.ensure(bytes, "the interpolated colour frame")) return rc;
-    if (int rc = enqueue_own_ip_bgr(c, pair, num, 1, den, c->ip_bgr, 3 * c->geom.width, 0, c->stream, what)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->ip_bgr, bytes, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    return download_staged(c, c->ip_bgr, (size_t)3 * c->geom.width * c->geom.height, "the interpolated colour frame", out, [&](uint8_t *d) {
+        return enqueue_own_ip_bgr(c, pair, num, 1, den, d, 3 * c->geom.width, 0, c->stream, what);
+    });
 }
 
-// ---- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rule of include/bbme.h; k_temporal_filter) --
+// ---- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rules of include/bbme.h) --------------
+// Written once over a flavour: TfGrey filters the level-0 planes (k_temporal_filter), TfBgr the B,G,R frames (k_temporal_filter_bgr).
 
 constexpr int kTfMaxFrames = 2 * BBME_MAX_BATCH;          // a batch holds 2 batch frames, a chain batch + 1
-
-static long long tf_groups(const Level &L0)
-{
-    return ((long long)(L0.width / 2 + 3) / 4 * (L0.height / 2) + 256 * kTfRunsPerLane - 1) / (256 * kTfRunsPerLane);
-}
-
-// the result words of every frame, then the partials of a launch over every frame, then those of a one-frame launch: one size
-// per context, so it is never replaced under a launch that reads it
-static int tf_scratch(bbme_ctx *c)
-{
-    return c->tf_stats.ensure((size_t)4 * (kTfMaxFrames + tf_groups(c->lv[0]) * (c->frames() + 1)), "the temporal filter statistics");
-}
-
-static int check_tf(const bbme_ctx *c, int thr, const int *window, const char *what)
-{
-    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
-    return check_window(window, c->lv[0].width / 2, c->lv[0].height / 2, what, -1);
-}
-
-static int check_tf_state(const bbme_ctx *c, const char *what)
-{
-    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
-    if (!c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate", what);
-    return BBME_OK;
-}
-
-// geometry, strength and the magics of both divisions
-static TfArgs tf_args(const bbme_ctx *c, int thr, const int *window)
-{
-    const Level &L = c->lv[0];
-    TfArgs a{};
-    a.width = L.width; a.height = L.height; a.cw = L.width / 2; a.ch = L.height / 2;
-    a.thr = thr;
-    a.magic_thr = thr > 1 ? (uint32_t)((1ull << 32) / (unsigned)thr + 1ull) : 0u;      // thr = 1: k_temporal_filter does not divide
-    for (int S = 8; S <= 24; ++S) a.magic_s[S - 8] = (uint32_t)((1ull << 32) / (unsigned)S + 1ull);
-    set_window(a, window, a.cw, a.ch);
-    a.runs_per_row = (a.cw + 3) / 4;
-    a.runs = (long long)a.runs_per_row * a.ch;
-    return a;
-}
-
-// k_temporal_filter over `pairs` x `count` frames (blockIdx.y, blockIdx.z) and, with d_stats, k_mc_reduce of the partials into
-// d_stats[4 (y count + z) ..]
-static int enqueue_tf(bbme_ctx *c, TfArgs &a, int pairs, int count, unsigned long long *partial, unsigned long long *d_stats,
-                      hipStream_t stream)
-{
-    a.partial = d_stats ? partial : nullptr;
-    const long long groups = tf_groups(c->lv[0]);
-    hipLaunchKernelGGL(k_temporal_filter, dim3((unsigned)groups, (unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
-    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)(pairs * count)), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
-    HIP_TRY(hipGetLastError());
-    return BBME_OK;
-}
-
-// The context's own frames as k_temporal_filter addresses them.  Chain: slots first .. first + count - 1 along z, neighbours one
-// plane_stride to either side, into-previous = backward cells of pair slot - 1, into-next = forward cells of pair slot.  Pair or
-// batch: image 1 and image 2 of pairs pair0 .. along z = which (from which0 on), image 1 with its next neighbour only and image 2
-// with its previous one.  A base that a launch never dereferences (the first slot's previous frame, ...) is address arithmetic only.
-static TfArgs tf_own_frames(const bbme_ctx *c, int thr, const int *window, int pair0, int first, int count)
-{
-    const Level &L = c->lv[0];
-    TfArgs a = tf_args(c, thr, window);
-    const long long ps = L.plane_stride, s_f = L.grid_stride(L.final_grid()), s_b = c->bwd_stride;
-    const uintptr_t img = reinterpret_cast<uintptr_t>(L.img1.get()), f = reinterpret_cast<uintptr_t>(L.final_grid()),
-                    b = reinterpret_cast<uintptr_t>(c->bwd_cells.get());
-    if (c->chain) {                                       // `first` is a slot
-        a.cur = reinterpret_cast<const uint8_t *>(img + first * ps);
-        a.prev = reinterpret_cast<const uint8_t *>(img + (first - 1) * ps);
-        a.next = reinterpret_cast<const uint8_t *>(img + (first + 1) * ps);
-        a.gp = reinterpret_cast<const mv_t *>(b + (first - 1) * s_b * (long long)sizeof(mv_t));
-        a.gn = reinterpret_cast<const mv_t *>(f + first * s_f * (long long)sizeof(mv_t));
-        a.cur_z = a.prev_z = a.next_z = ps;
-        a.gp_z = s_b; a.gn_z = s_f;
-        a.first_prev = first > 0;
-        a.last_next = first + count - 1 < c->batch;
-    } else {                                              // `first` is which
-        const long long step = (long long)L.frame_step;
-        a.cur = reinterpret_cast<const uint8_t *>(img + pair0 * ps + first * step);
-        a.prev = reinterpret_cast<const uint8_t *>(img + pair0 * ps + (first - 1) * step);
-        a.next = reinterpret_cast<const uint8_t *>(img + pair0 * ps + (first + 1) * step);
-        a.gp = reinterpret_cast<const mv_t *>(b + pair0 * s_b * (long long)sizeof(mv_t));
-        a.gn = reinterpret_cast<const mv_t *>(f + pair0 * s_f * (long long)sizeof(mv_t));
-        a.cur_y = a.prev_y = a.next_y = ps;
-        a.cur_z = a.prev_z = a.next_z = step;
-        a.gp_y = s_b; a.gn_y = s_f;
-        a.first_prev = first > 0;                         // image 2 has image 1 behind it
-        a.last_next = first + count - 1 < 1;              // image 1 has image 2 ahead
-    }
-    return a;
-}
-
-int bbme_cells_temporal_filter_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
-                                      const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window, uint8_t *d_out,
-                                      int out_pitch, uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4,
-                                      void *hip_stream)
-{
-    const char *what = "bbme_cells_temporal_filter_device";
-    if (int rc = check_ctx(c)) return rc;
-    const Level &L = c->lv[0];
-    if (!d_cur || (!d_out && !d_weights && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
-    if ((d_prev == nullptr) != (d_to_prev == nullptr) || (d_next == nullptr) != (d_to_next == nullptr))
-        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its plane and its grid", what);
-    if (!d_prev && !d_next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
-    if (int rc = check_tf(c, thr, window, what)) return rc;
-    if (d_out && out_pitch < L.width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d", what, out_pitch, L.width);
-    if (d_weights && weights_pitch < L.width / 2)
-        return bbme::fail(BBME_ERR_INVALID, "%s: weight map pitch %d < %d cells per row", what, weights_pitch, L.width / 2);
-    // the frame is written while other lanes still gather from the planes: an output inside an input plane is a race, not a result
-    if (d_out) {
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (size_t)out_pitch * (L.height - 1) + L.width;
-        for (const uint8_t *in : {d_prev, d_cur, d_next}) {
-            const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (size_t)L.width * L.height;
-            if (in && o0 < i1 && i0 < o1) return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input plane", what);
-        }
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    if (d_stats4) if (int rc = tf_scratch(c)) return rc;
-    hipStream_t stream;
-    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    TfArgs a = tf_args(c, thr, window);
-    a.cur = d_cur; a.prev = d_prev; a.next = d_next;
-    a.gp = reinterpret_cast<const mv_t *>(d_to_prev); a.gn = reinterpret_cast<const mv_t *>(d_to_next);
-    a.first_prev = a.last_next = 1;
-    a.out = d_out; a.out_pitch = out_pitch;
-    a.wmap = d_weights; a.wmap_pitch = weights_pitch;
-    unsigned long long *partial = d_stats4 ? c->tf_stats + (size_t)4 * (kTfMaxFrames + tf_groups(L) * c->frames()) : nullptr;
-    return enqueue_tf(c, a, 1, 1, partial, d_stats4, stream);
-}
-
-// frame `which` of `pair` of the context's own, into d_out on `stream`
-static int enqueue_own_tf(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, hipStream_t stream)
-{
-    TfArgs a = c->chain ? tf_own_frames(c, thr, nullptr, 0, pair + which, 1) : tf_own_frames(c, thr, nullptr, pair, which, 1);
-    a.out = d_out; a.out_pitch = out_pitch;
-    return enqueue_tf(c, a, 1, 1, nullptr, nullptr, stream);
-}
-
-static int check_tf_frame(const bbme_ctx *c, int pair, int which, int thr, const char *what)
-{
-    if (int rc = check_pair(c, pair)) return rc;
-    if (which != 0 && which != 1) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
-    return check_tf(c, thr, nullptr, what);
-}
-
-int bbme_temporal_filter_device(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
-{
-    const char *what = "bbme_temporal_filter_device";
-    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
-    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (out_pitch < c->lv[0].width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d", what, out_pitch, c->lv[0].width);
-    if (int rc = check_tf_state(c, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream;
-    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    return enqueue_own_tf(c, pair, which, thr, d_out, out_pitch, stream);
-}
-
-int bbme_temporal_filter_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
-                                      void *hip_stream)
-{
-    const char *what = "bbme_temporal_filter_chain_device";
-    if (int rc = chain_context_only(c, what)) return rc;
-    const Level &L = c->lv[0];
-    if (first < 0 || count < 1 || (long long)first + count > c->batch + 1)
-        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside 0 .. %d", what, first, first, count, c->batch);
-    if (int rc = check_tf(c, thr, nullptr, what)) return rc;
-    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (out_pitch < L.width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d", what, out_pitch, L.width);
-    if (count > 1 && out_stride < (size_t)out_pitch * L.height)
-        return bbme::fail(BBME_ERR_INVALID, "%s: output stride %zu < one frame of %d rows of %d bytes", what, out_stride, L.height, out_pitch);
-    if (int rc = check_tf_state(c, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream;
-    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    TfArgs a = tf_own_frames(c, thr, nullptr, 0, first, count);
-    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
-    return enqueue_tf(c, a, 1, count, nullptr, nullptr, stream);
-}
-
-int bbme_get_temporal_filtered_host(bbme_ctx *c, int pair, int which, int thr, uint8_t *out)
-{
-    const char *what = "bbme_get_temporal_filtered_host";
-    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
-    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_tf_state(c, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const Level &L = c->lv[0];
-    const size_t bytes = (size_t)L.width * L.height;
-    if (int rc = c->tf_plane.ensure(bytes, "the filtered frame")) return rc;
-    if (int rc = enqueue_own_tf(c, pair, which, thr, c->tf_plane, L.width, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->tf_plane, bytes, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
-}
-
-int bbme_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
-{
-    const char *what = "bbme_temporal_filter_stats";
-    if (int rc = check_ctx(c)) return rc;
-    if (int rc = check_tf(c, thr, window, what)) return rc;
-    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_tf_state(c, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = tf_scratch(c)) return rc;
-    // chain: one pair row, every slot along z; otherwise every pair along y, which along z: frame y gridDim.z + z either way
-    const int pairs = c->chain ? 1 : c->batch, count = c->chain ? c->batch + 1 : 2;
-    TfArgs a = tf_own_frames(c, thr, window, 0, 0, count);
-    if (int rc = enqueue_tf(c, a, pairs, count, c->tf_stats + (size_t)4 * kTfMaxFrames, c->tf_stats, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(stats, c->tf_stats, (size_t)4 * sizeof(unsigned long long) * c->frames(), hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
-}
-
-// ---- the same on the B,G,R frames (the BGR temporal filter rule of include/bbme.h; k_temporal_filter_bgr) ------------------------
-
-// the result words of every frame, then the partials of a launch over every frame, then those of a one-frame launch (tf_scratch's
-// layout, in a buffer of its own)
-static int tf_bgr_scratch(bbme_ctx *c)
-{
-    return c->tf_bgr_stats.ensure((size_t)4 * (kTfMaxFrames + tf_groups(c->lv[0]) * (c->frames() + 1)),
-                                  "the colour temporal filter statistics");
-}
-
-// geometry, strength, the magics of both divisions and the window: TfArgs' own, and the frame inside the padded view
-static TfBgrArgs tf_bgr_args(const bbme_ctx *c, int thr, const int *window)
-{
-    const TfArgs t = tf_args(c, thr, window);
-    const Geometry &g = c->geom;
-    TfBgrArgs a{};
-    a.width = t.width; a.height = t.height; a.cw = t.cw; a.ch = t.ch;
-    a.fw = g.width; a.fh = g.height; a.pad_x = g.pad_x; a.pad_y = g.pad_y;
-    a.thr = thr; a.magic_thr = t.magic_thr;
-    memcpy(a.magic_s, t.magic_s, sizeof a.magic_s);
-    a.wx0 = t.wx0; a.wy0 = t.wy0; a.wx1 = t.wx1; a.wy1 = t.wy1;
-    a.runs_per_row = t.runs_per_row; a.runs = t.runs;
-    return a;
-}
-
-// k_temporal_filter_bgr over `pairs` x `count` frames (blockIdx.y, blockIdx.z) and, with d_stats, k_mc_reduce of the partials into
-// d_stats[4 (y count + z) ..]
-static int enqueue_tf_bgr(bbme_ctx *c, TfBgrArgs &a, int pairs, int count, unsigned long long *partial, unsigned long long *d_stats,
-                          hipStream_t stream)
-{
-    a.partial = d_stats ? partial : nullptr;
-    const long long groups = tf_groups(c->lv[0]);
-    hipLaunchKernelGGL(k_temporal_filter_bgr, dim3((unsigned)groups, (unsigned)pairs, (unsigned)count), dim3(256), 0, stream, a);
-    if (d_stats) hipLaunchKernelGGL(k_mc_reduce, dim3((unsigned)(pairs * count)), dim3(256), 0, stream, a.partial, (int)groups, d_stats);
-    HIP_TRY(hipGetLastError());
-    return BBME_OK;
-}
 
 // BBME_ERR_STATE unless the slots lo .. hi of the colour store (clamped to the context's) all have colour
 static int check_tf_bgr_colour(const bbme_ctx *c, int lo, int hi, const char *what)
@@ -2693,78 +2517,6 @@ static int check_tf_bgr_colour(const bbme_ctx *c, int lo, int hi, const char *wh
         if (!c->bgr_set[s])
             return bbme::fail(BBME_ERR_STATE, "%s: frame slot %d has no stored colour (set it with a *_bgr setter)", what, s);
     return BBME_OK;
-}
-
-// The context's stored colour frames as k_temporal_filter_bgr addresses them: tf_own_frames' layout and grids, with the colour
-// store's slots (chain: slot; pair or batch: which x batch + pair) in the planes' place.  Slot offsets in 64 bits: a deep chain's
-// store exceeds 4 GB.
-static TfBgrArgs tf_bgr_own_frames(const bbme_ctx *c, int thr, const int *window, int pair0, int first, int count)
-{
-    const TfArgs t = tf_own_frames(c, thr, window, pair0, first, count);
-    TfBgrArgs a = tf_bgr_args(c, thr, window);
-    const long long ss = (long long)c->bgr_stride, step = c->chain ? ss : ss * c->batch;
-    const uintptr_t store = reinterpret_cast<uintptr_t>(c->bgr.get());
-    const uintptr_t cur = store + (c->chain ? first * ss : pair0 * ss + first * step);
-    a.cur = reinterpret_cast<const uint8_t *>(cur);
-    a.prev = reinterpret_cast<const uint8_t *>(cur - step);
-    a.next = reinterpret_cast<const uint8_t *>(cur + step);
-    a.cur_z = a.prev_z = a.next_z = step;
-    if (!c->chain) a.cur_y = a.prev_y = a.next_y = ss;
-    a.bgr_pitch = 3 * c->geom.width;
-    a.gp = t.gp; a.gn = t.gn;
-    a.gp_y = t.gp_y; a.gp_z = t.gp_z; a.gn_y = t.gn_y; a.gn_z = t.gn_z;
-    a.first_prev = t.first_prev; a.last_next = t.last_next;
-    return a;
-}
-
-// out_pitch of a colour frame.  Touches no device.
-static int check_tf_bgr_out(const bbme_ctx *c, const uint8_t *d_out, int out_pitch, const char *what)
-{
-    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if ((long long)out_pitch < 3LL * c->geom.width)
-        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x frame width %d", what, out_pitch, c->geom.width);
-    return BBME_OK;
-}
-
-int bbme_cells_temporal_filter_bgr_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next, int bgr_pitch,
-                                          const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window,
-                                          uint8_t *d_out, int out_pitch, uint8_t *d_weights, int weights_pitch,
-                                          unsigned long long *d_stats4, void *hip_stream)
-{
-    const char *what = "bbme_cells_temporal_filter_bgr_device";
-    if (int rc = check_ctx(c)) return rc;
-    const Level &L = c->lv[0];
-    const Geometry &g = c->geom;
-    if (!d_cur || (!d_out && !d_weights && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
-    if ((d_prev == nullptr) != (d_to_prev == nullptr) || (d_next == nullptr) != (d_to_next == nullptr))
-        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its frame and its grid", what);
-    if (!d_prev && !d_next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
-    if (int rc = check_tf(c, thr, window, what)) return rc;
-    if ((long long)bgr_pitch < 3LL * g.width)
-        return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, bgr_pitch, g.width);
-    if (d_out) if (int rc = check_tf_bgr_out(c, d_out, out_pitch, what)) return rc;
-    if (d_weights && weights_pitch < L.width / 2)
-        return bbme::fail(BBME_ERR_INVALID, "%s: weight map pitch %d < %d cells per row", what, weights_pitch, L.width / 2);
-    // the frame is written while other lanes still gather from the frames: an output inside an input frame is a race, not a result
-    if (d_out) {
-        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out), o1 = o0 + (size_t)out_pitch * (g.height - 1) + (size_t)3 * g.width;
-        for (const uint8_t *in : {d_prev, d_cur, d_next}) {
-            const uintptr_t i0 = reinterpret_cast<uintptr_t>(in), i1 = i0 + (size_t)bgr_pitch * (g.height - 1) + (size_t)3 * g.width;
-            if (in && o0 < i1 && i0 < o1) return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input frame", what);
-        }
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    if (d_stats4) if (int rc = tf_bgr_scratch(c)) return rc;
-    hipStream_t stream;
-    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    TfBgrArgs a = tf_bgr_args(c, thr, window);
-    a.cur = d_cur; a.prev = d_prev; a.next = d_next; a.bgr_pitch = bgr_pitch;
-    a.gp = reinterpret_cast<const mv_t *>(d_to_prev); a.gn = reinterpret_cast<const mv_t *>(d_to_next);
-    a.first_prev = a.last_next = 1;
-    a.out = d_out; a.out_pitch = out_pitch;
-    a.wmap = d_weights; a.wmap_pitch = weights_pitch;
-    unsigned long long *partial = d_stats4 ? c->tf_bgr_stats + (size_t)4 * (kTfMaxFrames + tf_groups(L) * c->frames()) : nullptr;
-    return enqueue_tf_bgr(c, a, 1, 1, partial, d_stats4, stream);
 }
 
 // BBME_ERR_STATE unless frame `which` of `pair` and the neighbours the rule gives it have colour
@@ -2777,82 +2529,321 @@ static int check_tf_bgr_frame_colour(const bbme_ctx *c, int pair, int which, con
     return BBME_OK;
 }
 
-// frame `which` of `pair` of the context's own, into d_out on `stream`
-static int enqueue_own_tf_bgr(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, hipStream_t stream)
+// A flavour names the argument type and kernel, the size of a frame (`rows` rows of row_bytes), the staging buffer and the
+// statistics scratch, what the arguments hold beyond TfArgs, and the context's own frames: their base, s_pair bytes from pair to
+// pair and s_frame from a frame to its next neighbour.  What only colour checks hangs on `bgr` in the bodies below.
+struct TfGrey {
+    using Args = TfArgs;
+    static constexpr bool bgr = false;
+    static constexpr const char *input = "plane", *staging_what = "the filtered frame", *stats_what = "the temporal filter statistics";
+    static auto kernel() { return k_temporal_filter; }
+    static int row_bytes(const bbme_ctx *c) { return c->lv[0].width; }
+    static int rows(const bbme_ctx *c) { return c->lv[0].height; }
+    static DevBuf<uint8_t> &staging(bbme_ctx *c) { return c->tf_plane; }
+    static StatsScratch &stats(bbme_ctx *c) { return c->tf_stats; }
+    static void geometry(const bbme_ctx *, TfArgs &) {}
+    static const uint8_t *own(const bbme_ctx *c, long long *s_pair, long long *s_frame)
+    {
+        const Level &L = c->lv[0];
+        *s_pair = L.plane_stride;
+        *s_frame = c->chain ? (long long)L.plane_stride : (long long)L.frame_step;
+        return L.img1;
+    }
+};
+
+struct TfBgr {
+    using Args = TfBgrArgs;
+    static constexpr bool bgr = true;
+    static constexpr const char *input = "frame", *staging_what = "the filtered colour frame",
+                                *stats_what = "the colour temporal filter statistics";
+    static auto kernel() { return k_temporal_filter_bgr; }
+    static int row_bytes(const bbme_ctx *c) { return 3 * c->geom.width; }
+    static int rows(const bbme_ctx *c) { return c->geom.height; }
+    static DevBuf<uint8_t> &staging(bbme_ctx *c) { return c->tf_bgr; }
+    static StatsScratch &stats(bbme_ctx *c) { return c->tf_bgr_stats; }
+    static void geometry(const bbme_ctx *c, TfBgrArgs &a)      // the frame inside the padded view
+    {
+        a.fw = c->geom.width; a.fh = c->geom.height; a.pad_x = c->geom.pad_x; a.pad_y = c->geom.pad_y;
+        a.bgr_pitch = 3 * c->geom.width;
+    }
+    // the colour store's slots (chain: slot; pair or batch: which x batch + pair).  In 64 bits: a deep chain's store exceeds 4 GB.
+    static const uint8_t *own(const bbme_ctx *c, long long *s_pair, long long *s_frame)
+    {
+        *s_pair = (long long)c->bgr_stride;
+        *s_frame = c->chain ? *s_pair : *s_pair * c->batch;
+        return c->bgr;
+    }
+};
+
+// pitch and, with more than one frame, stride of a caller's output frames
+template <class F>
+static int check_tf_out(const bbme_ctx *c, int count, int pitch, size_t stride, const char *what)
 {
-    TfBgrArgs a = c->chain ? tf_bgr_own_frames(c, thr, nullptr, 0, pair + which, 1) : tf_bgr_own_frames(c, thr, nullptr, pair, which, 1);
+    if (F::bgr) return check_bgr_frames(c, count, pitch, stride, what);
+    return check_frames(count, pitch, stride, F::row_bytes(c), F::rows(c), what, "output");
+}
+
+static long long tf_groups(const bbme_ctx *c) { return cell_groups(c, kTfRunsPerLane); }
+
+// result words of every frame, partials of a launch over every frame, then those of a one-frame launch: one size per context, so
+// it is never replaced under a launch that reads it
+template <class F>
+static int tf_scratch(bbme_ctx *c)
+{
+    return F::stats(c).ensure(kTfMaxFrames, tf_groups(c), c->frames(), 1, F::stats_what);
+}
+
+static int check_tf(const bbme_ctx *c, int thr, const int *window, const char *what)
+{
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    return check_window(window, c->lv[0].width / 2, c->lv[0].height / 2, what, -1);
+}
+
+// what both flavours' arguments share: geometry, strength, the magics of both divisions and the window
+static void tf_fill(TfArgs &a, const bbme_ctx *c, int thr, const int *window)
+{
+    const Level &L = c->lv[0];
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2; a.ch = L.height / 2;
+    a.thr = thr;
+    a.magic_thr = thr > 1 ? (uint32_t)((1ull << 32) / (unsigned)thr + 1ull) : 0u;      // thr = 1: the kernels do not divide
+    for (int S = 8; S <= 24; ++S) a.magic_s[S - 8] = (uint32_t)((1ull << 32) / (unsigned)S + 1ull);
+    set_window(a, window, a.cw, a.ch);
+    set_runs(a, a.cw, a.ch);
+}
+
+template <class F>
+static typename F::Args tf_args(const bbme_ctx *c, int thr, const int *window)
+{
+    typename F::Args a{};
+    tf_fill(a, c, thr, window);
+    F::geometry(c, a);
+    return a;
+}
+
+// the flavour's kernel over `pairs` x `count` frames (blockIdx.y, blockIdx.z)
+template <class F>
+static int enqueue_tf(bbme_ctx *c, typename F::Args &a, int pairs, int count, unsigned long long *partial, unsigned long long *d_stats,
+                      hipStream_t stream)
+{
+    return launch_gather(F::kernel(), a, tf_groups(c), pairs, count, partial, d_stats, stream);
+}
+
+// The context's own frames as the kernels address them.  Chain: slots first .. first + count - 1 along z, neighbours one slot to
+// either side, into-previous = backward cells of pair slot - 1, into-next = forward cells of pair slot.  Pair or batch: image 1
+// and image 2 of pairs pair0 .. along z = which (from which0 on), image 1 with its next neighbour only and image 2 with its
+// previous one.  A base that a launch never dereferences (the first slot's previous frame, ...) is address arithmetic only.
+static void tf_own_fill(TfArgs &a, const bbme_ctx *c, const uint8_t *frames, long long s_pair, long long s_frame, int pair0, int first,
+                        int count)
+{
+    const Level &L = c->lv[0];
+    const long long s_f = L.grid_stride(L.final_grid()), s_b = c->bwd_stride;
+    const uintptr_t f = reinterpret_cast<uintptr_t>(L.final_grid()), b = reinterpret_cast<uintptr_t>(c->bwd_cells.get());
+    const uintptr_t cur = reinterpret_cast<uintptr_t>(frames) + (c->chain ? 0 : pair0 * s_pair) + first * s_frame;   // chain: `first` is a slot
+    a.cur = reinterpret_cast<const uint8_t *>(cur);
+    a.prev = reinterpret_cast<const uint8_t *>(cur - s_frame);
+    a.next = reinterpret_cast<const uint8_t *>(cur + s_frame);
+    a.cur_z = a.prev_z = a.next_z = s_frame;
+    a.first_prev = first > 0;                             // pair or batch: image 2 has image 1 behind it
+    if (c->chain) {
+        a.gp = reinterpret_cast<const mv_t *>(b + (first - 1) * s_b * (long long)sizeof(mv_t));
+        a.gn = reinterpret_cast<const mv_t *>(f + first * s_f * (long long)sizeof(mv_t));
+        a.gp_z = s_b; a.gn_z = s_f;
+        a.last_next = first + count - 1 < c->batch;
+    } else {
+        a.cur_y = a.prev_y = a.next_y = s_pair;
+        a.gp = reinterpret_cast<const mv_t *>(b + pair0 * s_b * (long long)sizeof(mv_t));
+        a.gn = reinterpret_cast<const mv_t *>(f + pair0 * s_f * (long long)sizeof(mv_t));
+        a.gp_y = s_b; a.gn_y = s_f;
+        a.last_next = first + count - 1 < 1;              // image 1 has image 2 ahead
+    }
+}
+
+template <class F>
+static typename F::Args tf_own_frames(const bbme_ctx *c, int thr, const int *window, int pair0, int first, int count)
+{
+    typename F::Args a = tf_args<F>(c, thr, window);
+    long long s_pair, s_frame;
+    const uint8_t *frames = F::own(c, &s_pair, &s_frame);
+    tf_own_fill(a, c, frames, s_pair, s_frame, pair0, first, count);
+    return a;
+}
+
+// bbme_cells_temporal_filter_device and its colour twin: a caller's frames (rows in_pitch bytes apart) and grids
+template <class F>
+static int tf_cells(bbme_ctx *c, const char *what, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next, int in_pitch,
+                    const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window, uint8_t *d_out, int out_pitch,
+                    uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4, void *hip_stream)
+{
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_cur || (!d_out && !d_weights && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if ((d_prev == nullptr) != (d_to_prev == nullptr) || (d_next == nullptr) != (d_to_next == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its %s and its grid", what, F::input);
+    if (!d_prev && !d_next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if (F::bgr && (long long)in_pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, in_pitch, c->geom.width);
+    if (d_out) if (int rc = check_tf_out<F>(c, 1, out_pitch, 0, what)) return rc;
+    if (d_weights && weights_pitch < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: weight map pitch %d < %d cells per row", what, weights_pitch, L.width / 2);
+    if (d_out && overlaps_input(d_out, out_pitch, {d_prev, d_cur, d_next}, in_pitch, F::row_bytes(c), F::rows(c)))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input %s", what, F::input);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = tf_scratch<F>(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    typename F::Args a = tf_args<F>(c, thr, window);
+    a.cur = d_cur; a.prev = d_prev; a.next = d_next;
+    if constexpr (F::bgr) a.bgr_pitch = in_pitch;
+    a.gp = reinterpret_cast<const mv_t *>(d_to_prev); a.gn = reinterpret_cast<const mv_t *>(d_to_next);
+    a.first_prev = a.last_next = 1;
     a.out = d_out; a.out_pitch = out_pitch;
-    return enqueue_tf_bgr(c, a, 1, 1, nullptr, nullptr, stream);
+    a.wmap = d_weights; a.wmap_pitch = weights_pitch;
+    return enqueue_tf<F>(c, a, 1, 1, F::stats(c).partials_caller(), d_stats4, stream);
+}
+
+// frame `which` of `pair` of the context's own, into d_out on `stream`
+template <class F>
+static int enqueue_own_tf(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, hipStream_t stream)
+{
+    typename F::Args a = c->chain ? tf_own_frames<F>(c, thr, nullptr, 0, pair + which, 1) : tf_own_frames<F>(c, thr, nullptr, pair, which, 1);
+    a.out = d_out; a.out_pitch = out_pitch;
+    return enqueue_tf<F>(c, a, 1, 1, nullptr, nullptr, stream);
+}
+
+// pair, which and strength, a non-null output, the context's state and that frame `which` of `pair` and the neighbours the rule
+// gives it are there
+template <class F>
+static int check_tf_frame(const bbme_ctx *c, int pair, int which, int thr, const uint8_t *out, const int *out_pitch, const char *what)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (which != 0 && which != 1) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    if (int rc = check_tf(c, thr, nullptr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (out_pitch) if (int rc = check_tf_out<F>(c, 1, *out_pitch, 0, what)) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
+    return F::bgr ? check_tf_bgr_frame_colour(c, pair, which, what) : BBME_OK;
+}
+
+template <class F>
+static int tf_device(bbme_ctx *c, const char *what, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    if (int rc = check_tf_frame<F>(c, pair, which, thr, d_out, &out_pitch, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_tf<F>(c, pair, which, thr, d_out, out_pitch, stream);
+}
+
+template <class F>
+static int tf_chain(bbme_ctx *c, const char *what, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
+                    void *hip_stream)
+{
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (first < 0 || count < 1 || (long long)first + count > c->batch + 1)
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside 0 .. %d", what, first, first, count, c->batch);
+    if (int rc = check_tf(c, thr, nullptr, what)) return rc;
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_tf_out<F>(c, count, out_pitch, out_stride, what)) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
+    if (F::bgr) if (int rc = check_tf_bgr_colour(c, first - 1, first + count, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    typename F::Args a = tf_own_frames<F>(c, thr, nullptr, 0, first, count);
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    return enqueue_tf<F>(c, a, 1, count, nullptr, nullptr, stream);
+}
+
+template <class F>
+static int tf_host(bbme_ctx *c, const char *what, int pair, int which, int thr, uint8_t *out)
+{
+    if (int rc = check_tf_frame<F>(c, pair, which, thr, out, nullptr, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return download_staged(c, F::staging(c), (size_t)F::row_bytes(c) * F::rows(c), F::staging_what, out, [&](uint8_t *d) {
+        return enqueue_own_tf<F>(c, pair, which, thr, d, F::row_bytes(c), c->stream);
+    });
+}
+
+template <class F>
+static int tf_stats(bbme_ctx *c, const char *what, int thr, const int *window, unsigned long long *stats)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_fields_state(c, what)) return rc;
+    if (F::bgr) if (int rc = check_tf_bgr_colour(c, 0, c->frames() - 1, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = tf_scratch<F>(c)) return rc;
+    // chain: one pair row, every slot along z; otherwise every pair along y, which along z: frame y gridDim.z + z either way
+    const int pairs = c->chain ? 1 : c->batch, count = c->chain ? c->batch + 1 : 2;
+    typename F::Args a = tf_own_frames<F>(c, thr, window, 0, 0, count);
+    return download_stats(c, F::stats(c), c->frames(), stats, [&] {
+        return enqueue_tf<F>(c, a, pairs, count, F::stats(c).partials_all(), F::stats(c).results(), c->stream);
+    });
+}
+
+int bbme_cells_temporal_filter_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                      const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window, uint8_t *d_out,
+                                      int out_pitch, uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4,
+                                      void *hip_stream)
+{
+    return tf_cells<TfGrey>(c, "bbme_cells_temporal_filter_device", d_prev, d_cur, d_next, c ? c->lv[0].width : 0, d_to_prev, d_to_next,
+                            thr, window, d_out, out_pitch, d_weights, weights_pitch, d_stats4, hip_stream);
+}
+
+int bbme_temporal_filter_device(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    return tf_device<TfGrey>(c, "bbme_temporal_filter_device", pair, which, thr, d_out, out_pitch, hip_stream);
+}
+
+int bbme_temporal_filter_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
+                                      void *hip_stream)
+{
+    return tf_chain<TfGrey>(c, "bbme_temporal_filter_chain_device", first, count, thr, d_out, out_pitch, out_stride, hip_stream);
+}
+
+int bbme_get_temporal_filtered_host(bbme_ctx *c, int pair, int which, int thr, uint8_t *out)
+{
+    return tf_host<TfGrey>(c, "bbme_get_temporal_filtered_host", pair, which, thr, out);
+}
+
+int bbme_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
+{
+    return tf_stats<TfGrey>(c, "bbme_temporal_filter_stats", thr, window, stats);
+}
+
+int bbme_cells_temporal_filter_bgr_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next, int bgr_pitch,
+                                          const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window,
+                                          uint8_t *d_out, int out_pitch, uint8_t *d_weights, int weights_pitch,
+                                          unsigned long long *d_stats4, void *hip_stream)
+{
+    return tf_cells<TfBgr>(c, "bbme_cells_temporal_filter_bgr_device", d_prev, d_cur, d_next, bgr_pitch, d_to_prev, d_to_next, thr, window,
+                           d_out, out_pitch, d_weights, weights_pitch, d_stats4, hip_stream);
 }
 
 int bbme_temporal_filter_bgr_device(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
 {
-    const char *what = "bbme_temporal_filter_bgr_device";
-    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
-    if (int rc = check_tf_bgr_out(c, d_out, out_pitch, what)) return rc;
-    if (int rc = check_tf_state(c, what)) return rc;
-    if (int rc = check_tf_bgr_frame_colour(c, pair, which, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream;
-    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    return enqueue_own_tf_bgr(c, pair, which, thr, d_out, out_pitch, stream);
+    return tf_device<TfBgr>(c, "bbme_temporal_filter_bgr_device", pair, which, thr, d_out, out_pitch, hip_stream);
 }
 
 int bbme_temporal_filter_bgr_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
                                           void *hip_stream)
 {
-    const char *what = "bbme_temporal_filter_bgr_chain_device";
-    if (int rc = chain_context_only(c, what)) return rc;
-    if (first < 0 || count < 1 || (long long)first + count > c->batch + 1)
-        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside 0 .. %d", what, first, first, count, c->batch);
-    if (int rc = check_tf(c, thr, nullptr, what)) return rc;
-    if (int rc = check_tf_bgr_out(c, d_out, out_pitch, what)) return rc;
-    if (count > 1 && out_stride < (size_t)out_pitch * c->geom.height)
-        return bbme::fail(BBME_ERR_INVALID, "%s: output stride %zu < one frame of %d rows of %d bytes", what, out_stride, c->geom.height,
-                          out_pitch);
-    if (int rc = check_tf_state(c, what)) return rc;
-    if (int rc = check_tf_bgr_colour(c, first - 1, first + count, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    hipStream_t stream;
-    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    TfBgrArgs a = tf_bgr_own_frames(c, thr, nullptr, 0, first, count);
-    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
-    return enqueue_tf_bgr(c, a, 1, count, nullptr, nullptr, stream);
+    return tf_chain<TfBgr>(c, "bbme_temporal_filter_bgr_chain_device", first, count, thr, d_out, out_pitch, out_stride, hip_stream);
 }
 
 int bbme_get_temporal_filtered_bgr_host(bbme_ctx *c, int pair, int which, int thr, uint8_t *out)
 {
-    const char *what = "bbme_get_temporal_filtered_bgr_host";
-    if (int rc = check_tf_frame(c, pair, which, thr, what)) return rc;
-    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_tf_state(c, what)) return rc;
-    if (int rc = check_tf_bgr_frame_colour(c, pair, which, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    const size_t bytes = (size_t)3 * c->geom.width * c->geom.height;
-    if (int rc = c->tf_bgr.ensure(bytes, "the filtered colour frame")) return rc;
-    if (int rc = enqueue_own_tf_bgr(c, pair, which, thr, c->tf_bgr, 3 * c->geom.width, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->tf_bgr, bytes, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    return tf_host<TfBgr>(c, "bbme_get_temporal_filtered_bgr_host", pair, which, thr, out);
 }
 
 int bbme_temporal_filter_bgr_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
 {
-    const char *what = "bbme_temporal_filter_bgr_stats";
-    if (int rc = check_ctx(c)) return rc;
-    if (int rc = check_tf(c, thr, window, what)) return rc;
-    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
-    if (int rc = check_tf_state(c, what)) return rc;
-    if (int rc = check_tf_bgr_colour(c, 0, c->frames() - 1, what)) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    if (int rc = tf_bgr_scratch(c)) return rc;
-    // chain: one pair row, every slot along z; otherwise every pair along y, which along z: frame y gridDim.z + z either way
-    const int pairs = c->chain ? 1 : c->batch, count = c->chain ? c->batch + 1 : 2;
-    TfBgrArgs a = tf_bgr_own_frames(c, thr, window, 0, 0, count);
-    if (int rc = enqueue_tf_bgr(c, a, pairs, count, c->tf_bgr_stats + (size_t)4 * kTfMaxFrames, c->tf_bgr_stats, c->stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(stats, c->tf_bgr_stats, (size_t)4 * sizeof(unsigned long long) * c->frames(), hipMemcpyDeviceToHost,
-                           c->stream));
-    return check_converged(c);
+    return tf_stats<TfBgr>(c, "bbme_temporal_filter_bgr_stats", thr, window, stats);
 }
+
+extern "C" {
 
 int bbme_frame_plane_device(bbme_ctx *c, int pair, int which, int level, const uint8_t **d_plane)
 {

@@ -21,7 +21,12 @@ __device__ __forceinline__ int mv_x(mv_t m) { return (int)(int16_t)(m & 0xffffu)
 __device__ __forceinline__ int mv_y(mv_t m) { return (int)(int16_t)(m >> 16); }
 __device__ __forceinline__ mv_t mv_pack(int x, int y) { return ((uint32_t)x & 0xffffu) | ((uint32_t)y << 16); }
 
-// 16 bytes at any byte address (gfx950 global loads need no alignment; bbme_selftest_isa checks it)
+// 2 .. 16 bytes at any byte address (gfx950 global loads need no alignment; bbme_selftest_isa checks it)
+struct __attribute__((packed, aligned(1))) ua_u16 { uint16_t v; };
+struct __attribute__((packed, aligned(1))) ua_u32 { uint32_t v; };
+struct __attribute__((packed, aligned(1))) ua_u32x2 { uint32_t v[2]; };
+struct __attribute__((packed, aligned(1))) ua_u32x4 { uint32_t v[4]; };
+struct __attribute__((packed, aligned(1))) ua_u64 { uint64_t v; };
 struct __attribute__((packed, aligned(1))) ua_u128 { uint32_t v[4]; };
 
 // DPP move within a row of 16 lanes (CTRL: quad_perm 0x00-0xff, row_mirror 0x140, row_half_mirror 0x141,
@@ -2839,9 +2844,6 @@ __global__ void k_probe_xcc(uint32_t *out)
 }
 
 // unaligned global loads: dword / dwordx2 / dwordx4 at arbitrary byte addresses
-struct __attribute__((packed, aligned(1))) ua_u32 { uint32_t v; };
-struct __attribute__((packed, aligned(1))) ua_u32x2 { uint32_t v[2]; };
-struct __attribute__((packed, aligned(1))) ua_u32x4 { uint32_t v[4]; };
 __global__ void k_probe_unaligned(const uint8_t *p, uint32_t *out, int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2870,6 +2872,76 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 }
 
 // =======================================================================================
+// What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
+// k_temporal_filter and K9b k_temporal_filter_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
+// runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window.
+// =======================================================================================
+
+// Run split: run r (0 .. RPL - 1) of this lane is run gather_index<RPL>(r) of the plane's runs -- past the last one the lane is
+// done, its later runs are past it too --, and run i lies in row `row`, starts at unit x0 and holds the n = 1..4 units of it that
+// lie inside the row of `units`.  (One helper with the test inside costs registers: the compiler then no longer sees the loop's
+// exit before the division.)
+template <int RPL>
+__device__ __forceinline__ long long gather_index(int r)
+{
+    return ((long long)blockIdx.x * RPL + r) * 256 + threadIdx.x;
+}
+
+__device__ __forceinline__ void gather_split(long long i, int runs_per_row, int units, int &row, int &x0, int &n)
+{
+    row = (int)(i / runs_per_row);
+    x0 = (int)(i % runs_per_row) * 4;
+    n = min(4, units - x0);
+}
+
+// The four grid words of a run: one unaligned 16-byte load when the run is whole, word by word otherwise (the others 0).
+__device__ __forceinline__ void load_mv4(const mv_t *src, int n, uint32_t (&m)[4])
+{
+    m[0] = m[1] = m[2] = m[3] = 0;
+    if (n == 4) {
+        const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(src);
+        m[0] = v.v[0]; m[1] = v.v[1]; m[2] = v.v[2]; m[3] = v.v[3];
+    } else {
+#pragma unroll
+        for (int j = 0; j < 3; ++j)
+            if (j < n) m[j] = src[j];
+    }
+}
+
+// One byte per unit of a run, byte j of v for unit x0 + j: one dword when the run is whole and its address dword-aligned (a
+// caller's rows need not be), bytes otherwise.
+__device__ __forceinline__ void store_bytes4(uint8_t *o, int n, uint32_t v)
+{
+    if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = v;
+    else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(v >> (8 * j));
+}
+
+// Statistics tail: the lane's four counters summed over its wave, the four waves' sums over the workgroup through `part`, and
+// the workgroup's four 64-bit sums stored as the partial of (frame, workgroup) at word 4 (frame gridDim.x + blockIdx.x), for
+// k_mc_reduce to add up.  (64-bit atomics into the frame's four words instead: the 2040 workgroups of a 4K plane queue on that
+// one cache line, 34 us against 11 us for the same pass writing the frame.)  A wave's 32-bit sums must not overflow: every
+// kernel says why its own do not.  `part` is the kernel's: __shared__ inside a helper would be a module-level LDS variable.
+__device__ __forceinline__ void store_partial4(unsigned long long *partial, size_t frame, uint32_t (&part)[4][4], uint32_t s0,
+                                               uint32_t s1, uint32_t s2, uint32_t s3)
+{
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o);
+        s1 += __shfl_xor(s1, o);
+        s2 += __shfl_xor(s2, o);
+        s3 += __shfl_xor(s3, o);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        uint32_t *w = part[threadIdx.x >> 6];
+        w[0] = s0; w[1] = s1; w[2] = s2; w[3] = s3;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4)
+        partial[4 * (frame * gridDim.x + blockIdx.x) + threadIdx.x] =
+            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+// =======================================================================================
 // MF::draw_MVimage (motion_framework.cpp:887-905) fused with the residual statistics of the compensated frame against
 // image1.  b-block (X, Y) = (bx b, by b) takes its MV from grid[Y >> lcb][X >> lcb] (the current grid, cur_block =
 // 1 << lcb >= 2) and copies the b x b block of image2 at (X + dx, Y + dy) when that lies inside the plane; a skipped
@@ -2878,9 +2950,9 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 // both pixels of a half share a grid cell.  image1 is read (as a dword) only when statistics are asked for.
 // Statistics over the window [wx0, wx1) x [wy0, wy1): sse, sad and pixels over compensated pixels, skipped over the
 // others.  A lane sums at most kMcRunsPerLane runs in 32 bits and a wave's sum stays below 2^32
-// (64 * 4 * 4 * 255^2); every workgroup stores its four 64-bit sums as a partial (pair p, workgroup g at word
-// 4 (p gridDim.x + g)) and k_mc_reduce adds them up.  (64-bit atomics into the pair's four words instead: the 2040
-// workgroups of a 4K plane queue on that one cache line, 34 us against 11 us for the same pass writing the frame.)
+// (64 * 4 * 4 * 255^2).  Run split, output store and statistics tail are the shared ones (gather_index / gather_split,
+// store_bytes4, store_partial4 with frame = pair) but written out here: through the first and the last this kernel takes 4 more
+// SGPRs and 2 more VGPRs, and with store_bytes4 alone its frame-and-statistics pass measured 0.8 % above the written-out text.
 // Batch: blockIdx.y = pair (planes plane_stride bytes, grids grid_stride words apart); `out` only with one pair per launch.
 // =======================================================================================
 struct McArgs {
@@ -2896,8 +2968,6 @@ struct McArgs {
 };
 
 constexpr int kMcRunsPerLane = 4;
-
-struct __attribute__((packed, aligned(1))) ua_u16 { uint16_t v; };
 
 __global__ __launch_bounds__(256) void k_motion_compensate(McArgs a)
 {
@@ -3010,16 +3080,16 @@ __global__ __launch_bounds__(256) void k_mc_reduce(const unsigned long long *par
 }
 
 // =======================================================================================
-// Forward-backward consistency of two 2x2-cell grids (the rule of include/bbme.h): cell (cx, cy) of A with (dx, dy) looks
+// K6.  Forward-backward consistency of two 2x2-cell grids (the rule of include/bbme.h): cell (cx, cy) of A with (dx, dy) looks
 // at pixel (tx, ty) = (2 cx + dx, 2 cy + dy); outside the 2 CW x 2 CH plane it is class 2, otherwise (ex, ey) =
-// B[ty >> 1][tx >> 1], d = |dx + ex| + |dy + ey| and the class is d > tol.  A memory-bound gather: a lane takes a run of 4
-// consecutive cells of one row, so that A arrives as one 16-byte load and the mask leaves as one dword (the last run of a
-// row holds 2 cells when CW is not a multiple of 4; a caller's mask rows need not be dword-aligned); the four reads of B
-// are 4-byte gathers near the lane's own position (fields are piecewise smooth) and are left to L2.
+// B[ty >> 1][tx >> 1], d = |dx + ex| + |dy + ey| and the class is d > tol.  A lane takes a run of 4 consecutive cells of one
+// row (the last run of a row holds 2 cells when CW is not a multiple of 4), A arrives as one 16-byte load and the mask leaves as
+// one dword; the four reads of B are 4-byte gathers near the lane's own position (fields are piecewise smooth) and are left to L2.
 // Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells of class 0, 1, 2 and the sum of d over classes 0 and
-// 1.  A lane holds at most 4 kFbRunsPerLane = 16 cells, so a wave's 32-bit sum of d stays below 16 * 64 * 131 070 < 2^27;
-// every workgroup stores its four 64-bit sums as a partial in k_motion_compensate's layout and k_mc_reduce adds them up
-// (no atomics onto one line, see McArgs).  blockIdx.y = pair; mask and partial are each optional.
+// 1.  A lane holds at most 4 kFbRunsPerLane = 16 cells, so a wave's 32-bit sum of d stays below 16 * 64 * 131 070 < 2^27.
+// Run split, grid words, mask store and statistics tail are the shared ones (gather_index / gather_split, load_mv4, store_bytes4,
+// store_partial4 with frame = pair) but written out here: through the helpers the registers stay as they are, but the launches
+// with statistics measured 1.3 to 4.3 % above the written-out text.  blockIdx.y = pair; mask and partial are each optional.
 // =======================================================================================
 struct FbArgs {
     const mv_t *a, *b;                    // cw entries per row, ch rows
@@ -3101,7 +3171,7 @@ __global__ __launch_bounds__(256) void k_fb_consistency(FbArgs a)
 }
 
 // =======================================================================================
-// Motion-compensated interpolation at phase num / den from the level-0 planes and the two 2x2-cell grids (the rule of
+// K7.  Motion-compensated interpolation at phase num / den from the level-0 planes and the two 2x2-cell grids (the rule of
 // include/bbme.h): output cell (cx, cy) tries v = F[cy][cx], v = -B[cy][cx] (when B is given) and v = 0; a hypothesis reads
 // the 2x2 cell of I1 at p1 = origin - round(num v / den) and the one of I2 at p2 = p1 + v, is valid when both lie inside the
 // plane, and costs their SAD; the cheapest valid one (the earliest of equals) is blended, ((den - num) I1 + num I2 +
@@ -3116,23 +3186,30 @@ __global__ __launch_bounds__(256) void k_fb_consistency(FbArgs a)
 // blockIdx.y = pair (planes plane_stride bytes, grids s_f / s_b words apart), blockIdx.z = phase num0 + z (frames out_stride,
 // maps sel_stride bytes apart): the planes and grids of one pair are read from L2 by every phase but the first.  `out` and
 // `sel` only with one pair per launch.  Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells that selected
-// k = 0, 1, 2 and the sum of the selected costs; a lane holds at most 4 kIpRunsPerLane cells of cost <= 1020, every workgroup
-// stores its four 64-bit sums as a partial in k_motion_compensate's layout, (phase, pair) taking pair's place, and k_mc_reduce
-// adds them up (no atomics onto one line, see McArgs).
+// k = 0, 1, 2 and the sum of the selected costs; a lane holds at most 4 kIpRunsPerLane cells of cost <= 1020.  The selection map
+// leaves by store_bytes4.  Run split, grid words (ip_load_run) and statistics tail are the shared ones (gather_index /
+// gather_split, load_mv4, store_partial4 with frame = (phase, pair)) but written out here: through the helpers this kernel or
+// k_interpolate_bgr, which shares ip_load_run, takes one more VGPR.
 // =======================================================================================
-struct IpArgs {
-    const uint8_t *img1, *img2;           // level-0 padded planes, pitch = width
-    const mv_t *fwd, *bwd;                // cw entries per row, ch rows; bwd may be null
+// what k_interpolate and k_interpolate_bgr both take
+struct IpCommon {
+    const uint8_t *img1, *img2;           // level-0 padded (luma) planes, pitch = width
+    const mv_t *fwd, *bwd;                // cw entries per row, height / 2 rows; bwd may be null
     uint8_t *out;                         // frames (rows out_pitch, phases out_stride bytes apart), or null
+    size_t out_stride;
+    int width, height, cw, num0, den, out_pitch;
+    uint32_t magic;                       // floor(2^32 / den) + 1
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * height / 2
+};
+
+struct IpArgs : IpCommon {
     uint8_t *sel;                         // one byte k per cell (rows sel_pitch, phases sel_stride bytes apart), or null
     unsigned long long *partial;          // per (phase, pair) and workgroup {k = 0, k = 1, k = 2, cost}; or null
     uint32_t plane_stride, s_f, s_b;
-    size_t out_stride, sel_stride;
-    int width, height, cw, ch, num0, den, out_pitch, sel_pitch;
-    uint32_t magic;                       // floor(2^32 / den) + 1
+    size_t sel_stride;
+    int ch, sel_pitch;
     int wx0, wy0, wx1, wy1;
-    int runs_per_row;                     // ceil(cw / 4)
-    long long runs;                       // runs_per_row * ch
 };
 
 constexpr int kIpRunsPerLane = 2;
@@ -3264,11 +3341,7 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
                 }
             }
         }
-        if (a.sel) {
-            uint8_t *o = a.sel + blockIdx.z * a.sel_stride + (size_t)cy * a.sel_pitch + x0;
-            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = ks;
-            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(ks >> (8 * j));
-        }
+        if (a.sel) store_bytes4(a.sel + blockIdx.z * a.sel_stride + (size_t)cy * a.sel_pitch + x0, n, ks);
     }
     if (!a.partial) return;
     for (int o = 32; o > 0; o >>= 1) {
@@ -3289,7 +3362,7 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
 }
 
 // =======================================================================================
-// The BGR interpolation rule of include/bbme.h: k_interpolate's selection on the LUMA planes (ip_load_run, ip_select: the same
+// K7b.  The BGR interpolation rule of include/bbme.h: k_interpolate's selection on the LUMA planes (ip_load_run, ip_select: the same
 // loads, multiply-shifts and v_sad_u8), then the blend of the two B,G,R frames at the selected p1 and p2, written as the
 // unpadded frame.  Same split as k_interpolate -- a lane takes a run of 4 cells, blockIdx.z = phase, so every phase but the
 // first finds planes, grids and colour in L2 -- and the same kind of kernel, a memory-bound gather with three times the pixel
@@ -3299,16 +3372,9 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
 // dword-aligned; bytes otherwise (an odd pad_x, a caller's odd pitch, a cut run, the frame's edges -- with an odd padding
 // cells straddle the frame and only their pixels inside are written).  Runs wholly outside the frame load nothing.
 // =======================================================================================
-struct IpBgrArgs {
-    const uint8_t *img1, *img2;           // level-0 padded luma planes of the pair, pitch = width
-    const mv_t *fwd, *bwd;                // cw entries per row; bwd may be null
+struct IpBgrArgs : IpCommon {           // out: the fw x fh B,G,R frames
     const uint8_t *bgr1, *bgr2;           // the fw x fh colour frames, rows bgr_pitch bytes apart
-    uint8_t *out;                         // fw x fh B,G,R frames, rows out_pitch, phases out_stride bytes apart
-    size_t out_stride;
-    int width, height, cw, fw, fh, pad_x, pad_y, num0, den, bgr_pitch, out_pitch;
-    uint32_t magic;                       // floor(2^32 / den) + 1
-    int runs_per_row;                     // ceil(cw / 4)
-    long long runs;                       // runs_per_row * (height / 2)
+    int fw, fh, pad_x, pad_y, bgr_pitch;
 };
 
 // pixels (x, y) and (x + 1, y) of a colour frame as six bytes B,G,R,B,G,R from bit 0 up; a pixel outside the frame is 0
@@ -3386,12 +3452,11 @@ __global__ __launch_bounds__(256) void k_interpolate_bgr(IpBgrArgs a)
 // K9.  Motion-compensated temporal filter of a frame C with its previous frame P and / or its next frame N (the TEMPORAL FILTER
 // RULE of include/bbme.h): output cell (cx, cy) with origin o reads, for each present neighbour X with grid G on C, the 2x2 cell
 // of X at p = o + G[cy][cx]; inside the plane and with cost = SAD(C cell, X cell) < thr it gets the weight w = 8 (thr - cost) /
-// thr (0..8), otherwise 0, and out = (8 C + wP P + wN N + S / 2) / S with S = 8 + wP + wN.  A memory-bound gather in the mould
-// of k_interpolate: a lane takes a run of 4 consecutive cells of one cell row (fewer at the row's end), so that GP and GN arrive
-// as one 16-byte load each and C as one 8-byte load per plane row; each moved cell is two unaligned u16 loads packed into one
+// thr (0..8), otherwise 0, and out = (8 C + wP P + wN N + S / 2) / S with S = 8 + wP + wN.  The shared split of runs of 4 cells
+// (gather_index / gather_split): GP and GN arrive by load_mv4 and C as one 8-byte load per plane row; each moved cell is two unaligned u16 loads packed into one
 // dword (ip_cell), so that v_sad_u8 gives the cost -- and, on the finished cell, |out - C| -- in one instruction.  A lane writes
 // its 8 pixels of each of the two output rows as two dwords (bytes where a caller's row is not dword-aligned or the run is cut
-// by the row's end) and its four weight bytes wP | wN << 4 as one dword.
+// by the row's end) and its four weight bytes wP | wN << 4 by store_bytes4.
 // Both divisions are multiply-shifts by k_interpolate's argument: with magic = floor(2^32 / d) + 1 = (2^32 + e) / d, 0 < e <= d,
 // umulhi(n, magic) = floor(n / d) for every n with n e < 2^32.  By thr: n = 8 (thr - cost) <= 8 * 1021 and e <= 1021, n e < 2^23
 // (thr = 1 has no 32-bit magic, 2^32 + 1: there only cost 0 passes, and cost 0 is answered without the division).
@@ -3402,9 +3467,7 @@ __global__ __launch_bounds__(256) void k_interpolate_bgr(IpBgrArgs a)
 // first frame has its previous neighbour only with first_prev and the last its next one only with last_next, so that one launch
 // serves the frames of a chain (z = slot) as well as the 2 frames of every pair of a batch (z = which).  Statistics over the window
 // [wx0, wx1) x [wy0, wy1) in cells: cells with wP > 0, cells with wN > 0, the sum of wP + wN and the sum of |out - C| over the
-// cells' pixels; a lane holds at most 4 kTfRunsPerLane cells of at most 1020 each, every workgroup stores its four 64-bit sums as
-// a partial in k_motion_compensate's layout, frame y gridDim.z + z taking pair's place, and k_mc_reduce adds them up (no atomics
-// onto one line, see McArgs).
+// cells' pixels; a lane holds at most 4 kTfRunsPerLane cells of at most 1020 each (store_partial4, frame = y gridDim.z + z).
 // =======================================================================================
 struct TfArgs {
     const uint8_t *cur, *prev, *next;     // level-0 padded planes, pitch = width; prev / next null = no such neighbour at all
@@ -3456,22 +3519,16 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
     uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
 #pragma unroll
     for (int r = 0; r < kTfRunsPerLane; ++r) {
-        const long long i = ((long long)blockIdx.x * kTfRunsPerLane + r) * 256 + threadIdx.x;
+        const long long i = gather_index<kTfRunsPerLane>(r);
         if (i >= a.runs) break;
-        const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
-        const int n = min(4, CW - x0);                        // cells of the run inside the row
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
         const int oy = 2 * cy;
         const size_t g0 = (size_t)cy * CW + x0, o0 = (size_t)oy * W + 2 * x0;
         uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
+        if (has_p) load_mv4(GP + g0, n, gp);
+        if (has_n) load_mv4(GN + g0, n, gn);
         if (n == 4) {
-            if (has_p) {
-                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GP + g0);
-                gp[0] = v.v[0]; gp[1] = v.v[1]; gp[2] = v.v[2]; gp[3] = v.v[3];
-            }
-            if (has_n) {
-                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GN + g0);
-                gn[0] = v.v[0]; gn[1] = v.v[1]; gn[2] = v.v[2]; gn[3] = v.v[3];
-            }
             const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(C + o0), u = *reinterpret_cast<const ua_u32x2 *>(C + o0 + W);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -3482,8 +3539,6 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (j >= n) continue;
-                if (has_p) gp[j] = GP[g0 + j];
-                if (has_n) gn[j] = GN[g0 + j];
                 c[j] = ip_cell(C, W, 2 * (x0 + j), oy);
             }
         }
@@ -3527,37 +3582,20 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
                 }
             }
         }
-        if (a.wmap) {
-            uint8_t *o = a.wmap + (size_t)cy * a.wmap_pitch + x0;
-            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = ws;
-            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(ws >> (8 * j));
-        }
+        if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
     }
     if (!a.partial) return;
-    for (int o = 32; o > 0; o >>= 1) {
-        np += __shfl_xor(np, o);
-        nn += __shfl_xor(nn, o);
-        wsum += __shfl_xor(wsum, o);
-        dsum += __shfl_xor(dsum, o);
-    }
     __shared__ uint32_t part[4][4];
-    if ((threadIdx.x & 63) == 0) {
-        uint32_t *w = part[threadIdx.x >> 6];
-        w[0] = np; w[1] = nn; w[2] = wsum; w[3] = dsum;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4)
-        a.partial[4 * (((size_t)blockIdx.y * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x) + threadIdx.x] =
-            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
 }
 
 // =======================================================================================
 // K9b.  The BGR TEMPORAL FILTER RULE of include/bbme.h: K9 on three B,G,R frames, the cost of a neighbour's cell being the LARGEST
 // of its three per-channel 2x2 SADs, and the UNPADDED frame written.  It reads no luma plane: the cells are those of the padded
 // view (a pixel outside the fw x fh frame is 0 in every channel), cell (cx, cy) with origin o = (2 cx, 2 cy) holding the frame's
-// pixels o - (pad_x, pad_y) + (j, i).  Same split as k_temporal_filter (a lane takes a run of 4 cells of one cell row,
-// kTfRunsPerLane runs per lane, GP and GN as one 16-byte load each, blockIdx.y = batch pair, blockIdx.z = the frame of a run, every
-// input base + y s_y + z s_z in 64 bits, first_prev / last_next) and the colour accesses of k_interpolate_bgr: a neighbour's cell
+// pixels o - (pad_x, pad_y) + (j, i).  Same split, grid loads, map store and statistics tail as k_temporal_filter, same
+// arguments (TfBgrArgs is TfArgs and the frame's place in the padded view: blockIdx.y = batch pair, blockIdx.z = the frame of a
+// run, every input base + y s_y + z s_z in 64 bits, first_prev / last_next) and the colour accesses of k_interpolate_bgr: a neighbour's cell
 // row is 6 contiguous bytes (bgr_two: one unaligned dword and one u16 load, bytes at the frame's edge, 0 outside); the run's own
 // row is 24 bytes, three unaligned 8-byte loads where the run is whole and inside the frame and bgr_two cell by cell otherwise;
 // the output row is collected in three 64-bit words and leaves as six dword stores when the run is whole, inside the frame and its
@@ -3568,25 +3606,11 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
 // are v_sad_u8 on channel-masked dwords (B: 2, G and R: 3 each).  The divisions are K9's multiply-shifts with K9's bounds.
 // Statistics as K9 (|out - C| over the cells' four pixels and three channels, at most 3060 a cell), same partial layout.
 // =======================================================================================
-struct TfBgrArgs {
-    const uint8_t *cur, *prev, *next;     // fw x fh B,G,R frames, rows bgr_pitch bytes apart; prev / next null = no such neighbour at all
-    const mv_t *gp, *gn;                  // cw entries per row, ch rows: on C, into P and into N
-    uint8_t *out;                         // fw x fh B,G,R frames (rows out_pitch, frames out_stride bytes apart), or null
-    uint8_t *wmap;                        // one byte wP | wN << 4 per cell (rows wmap_pitch bytes apart; one-frame launches only), or null
-    unsigned long long *partial;          // per frame and workgroup {cells wP > 0, cells wN > 0, weights, |out - C|}; or null
-    long long cur_y, cur_z, prev_y, prev_z, next_y, next_z;      // bytes from pair to pair and from frame to frame
-    long long gp_y, gp_z, gn_y, gn_z;                            // words
-    size_t out_stride;
-    int width, height, cw, ch, fw, fh, pad_x, pad_y, thr, bgr_pitch, out_pitch, wmap_pitch;      // width x height: the padded view
-    int first_prev, last_next;
-    uint32_t magic_thr;                   // floor(2^32 / thr) + 1; not used at thr = 1
-    uint32_t magic_s[17];                 // floor(2^32 / S) + 1 for S = 8..24
-    int wx0, wy0, wx1, wy1;
-    int runs_per_row;                     // ceil(cw / 4)
-    long long runs;                       // runs_per_row * ch
+// TfArgs, with cur / prev / next and out the fw x fh B,G,R frames (rows bgr_pitch and out_pitch bytes apart) and width x height the
+// padded view, and the frame's place inside that view
+struct TfBgrArgs : TfArgs {
+    int fw, fh, pad_x, pad_y, bgr_pitch;
 };
-
-struct __attribute__((packed, aligned(1))) ua_u64 { uint64_t v; };
 
 // the largest per-channel SAD of two cells; lo0, lo1: B0 G0 R0 B1 of the cell's rows, hi: G1 R1 of row 0 | G1 R1 of row 1 << 16
 __device__ __forceinline__ uint32_t bgr_cell_cost(uint32_t c0, uint32_t c1, uint32_t ch, uint32_t x0, uint32_t x1, uint32_t xh)
@@ -3633,10 +3657,10 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
     uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
 #pragma unroll
     for (int r = 0; r < kTfRunsPerLane; ++r) {
-        const long long i = ((long long)blockIdx.x * kTfRunsPerLane + r) * 256 + threadIdx.x;
+        const long long i = gather_index<kTfRunsPerLane>(r);
         if (i >= a.runs) break;
-        const int cy = (int)(i / a.runs_per_row), x0 = (int)(i % a.runs_per_row) * 4;
-        const int n = min(4, CW - x0);                        // cells of the run inside the row
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
         const int oy = 2 * cy;
         const int fy = oy - a.pad_y, fx = 2 * x0 - a.pad_x;    // the run's first pixel in frame coordinates
         if (fy + 1 < 0 || fy >= a.fh || fx + 2 * n <= 0 || fx >= a.fw) {      // no pixel of the run is in the frame
@@ -3644,23 +3668,8 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
         }
         const size_t g0 = (size_t)cy * CW + x0;
         uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0};
-        if (n == 4) {
-            if (has_p) {
-                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GP + g0);
-                gp[0] = v.v[0]; gp[1] = v.v[1]; gp[2] = v.v[2]; gp[3] = v.v[3];
-            }
-            if (has_n) {
-                const ua_u32x4 v = *reinterpret_cast<const ua_u32x4 *>(GN + g0);
-                gn[0] = v.v[0]; gn[1] = v.v[1]; gn[2] = v.v[2]; gn[3] = v.v[3];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (j >= n) continue;
-                if (has_p) gp[j] = GP[g0 + j];
-                if (has_n) gn[j] = GN[g0 + j];
-            }
-        }
+        if (has_p) load_mv4(GP + g0, n, gp);
+        if (has_n) load_mv4(GN + g0, n, gn);
         const bool whole = n == 4 && fx >= 0 && fx + 8 <= a.fw;      // the run's 8 pixels lie inside a frame row
         uint64_t crow[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's own two rows, 24 bytes each
         if (whole) {
@@ -3736,28 +3745,11 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
                 }
             }
         }
-        if (a.wmap) {
-            uint8_t *o = a.wmap + (size_t)cy * a.wmap_pitch + x0;
-            if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = ws;
-            else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(ws >> (8 * j));
-        }
+        if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
     }
     if (!a.partial) return;
-    for (int o = 32; o > 0; o >>= 1) {
-        np += __shfl_xor(np, o);
-        nn += __shfl_xor(nn, o);
-        wsum += __shfl_xor(wsum, o);
-        dsum += __shfl_xor(dsum, o);
-    }
     __shared__ uint32_t part[4][4];
-    if ((threadIdx.x & 63) == 0) {
-        uint32_t *w = part[threadIdx.x >> 6];
-        w[0] = np; w[1] = nn; w[2] = wsum; w[3] = dsum;
-    }
-    __syncthreads();
-    if (threadIdx.x < 4)
-        a.partial[4 * (((size_t)blockIdx.y * gridDim.z + blockIdx.z) * gridDim.x + blockIdx.x) + threadIdx.x] =
-            (unsigned long long)part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+    store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
 }
 
 }  // namespace bbme

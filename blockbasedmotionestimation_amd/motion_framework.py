@@ -33,6 +33,27 @@ def _check_upsample(upsample):
     return upsample
 
 
+def _ptr(t):
+    """The address of a CUDA tensor's or a numpy array's data for a C entry point; None is the null pointer."""
+    if t is None:
+        return C.c_void_p(0)
+    return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data)
+
+
+def _window(window):
+    """(x0, y0, w, h) as the four ints of a C entry point; None stays None (the call's whole plane or grid)."""
+    return None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+
+
+def _host_out(out, shape, dtype, what):
+    """A host result array: a new one, or the caller's when it has that shape and type and is C-contiguous."""
+    if out is None:
+        return np.empty(shape, dtype)
+    if out.shape != shape or out.dtype != dtype or not out.flags.c_contiguous:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous %s array of shape %s" % (what, np.dtype(dtype).name, shape))
+    return out
+
+
 class MF:
     """upsample=4: image1 / image2 are the original frames of the reference's pipeline, which up-samples them x4 before
     MF::MF (main_class.cpp:32-33).  The context is created at the up-sampled size (orig_width / orig_height keep meaning
@@ -223,10 +244,7 @@ class MF:
         """The dense padded field; `out` may be a preallocated C-contiguous float32 array of that shape, e.g. a view
         of pinned memory (the 66.8 MB of a 4K field download about three times faster into pinned memory)."""
         shape = (self.padded_height, self.padded_width, 2)
-        if out is None:
-            out = np.empty(shape, np.float32)
-        elif out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "get_flow: out must be a C-contiguous float32 array of shape %s" % (shape,))
+        out = _host_out(out, shape, np.float32, "get_flow")
         _capi.check(self._lib.bbme_get_flow_host(self._ctx, out.ctypes.data))
         return out
 
@@ -240,10 +258,7 @@ class MF:
     def _get_subsampled(self, pair, scale, out, what):
         shape = self.subsampled_shape(scale)
         scale = self.upsample if scale is None else int(scale)
-        if out is None:
-            out = np.empty(shape, np.float32)
-        elif out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous float32 array of shape %s" % (what, shape))
+        out = _host_out(out, shape, np.float32, what)
         _capi.check(self._lib.bbme_get_subsampled_flow_host(self._ctx, pair, scale, out.ctypes.data))
         return out
 
@@ -273,10 +288,7 @@ class MF:
     # -- motion compensation (MF::draw_MVimage, motion_framework.cpp:887-905; rule in include/bbme.h) -----------------
     def _get_motion_compensated(self, pair, level, block, fill, out, what):
         w, h, _, _ = self.level_geometry(level)
-        if out is None:
-            out = np.empty((h, w), np.uint8)
-        elif out.shape != (h, w) or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, (h, w)))
+        out = _host_out(out, (h, w), np.uint8, what)
         _capi.check(self._lib.bbme_get_motion_compensated_host(self._ctx, pair, level, block, fill, out.ctypes.data))
         return out
 
@@ -304,7 +316,7 @@ class MF:
     def _compensation_stats(self, level, block, window):
         if window is None and level == 0:
             window = (self.padding_x, self.padding_y, self.orig_width, self.orig_height)
-        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+        win = _window(window)
         pairs = getattr(self, "batch", 1)
         s = (C.c_ulonglong * (4 * pairs))()
         _capi.check(self._lib.bbme_compensation_error(self._ctx, level, block, win, s))
@@ -347,10 +359,7 @@ class MF:
 
     def _get_backward_cells(self, pair, out, what):
         shape = self.cells_shape + (2,)
-        if out is None:
-            out = np.empty(shape, np.int16)
-        elif out.shape != shape or out.dtype != np.int16 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous int16 array of shape %s" % (what, shape))
+        out = _host_out(out, shape, np.int16, what)
         _capi.check(self._lib.bbme_get_backward_cells_host_pair(self._ctx, pair, out.ctypes.data))
         return out
 
@@ -368,10 +377,7 @@ class MF:
         2 target outside the plane.  which="forward": the mask on frame 1 (forward vector followed, backward vector read
         there); "backward": on frame 2."""
         shape = self.cells_shape
-        if out is None:
-            out = np.empty(shape, np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "consistency: out must be a C-contiguous uint8 array of shape %s" % (shape,))
+        out = _host_out(out, shape, np.uint8, "consistency")
         _capi.check(self._lib.bbme_get_consistency_host(self._ctx, pair, _which(which), int(tol), out.ctypes.data))
         return out
 
@@ -381,10 +387,20 @@ class MF:
         x1, y1 = -(-(self.padding_x + self.orig_width) // 2), -(-(self.padding_y + self.orig_height) // 2)
         return (x0, y0, x1 - x0, y1 - y0)
 
-    def _consistency_stats(self, which, tol, window):
+    def _stats_window(self, window):
+        """The window of the statistics calls on cells: default_cell_window() by default, "all" for every cell."""
         if window is None:
             window = self.default_cell_window()
-        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
+        return None if window == "all" else _window(window)
+
+    def _frame_count(self):
+        """Frames the context holds: the slots of an MFChain, else two per pair."""
+        n = C.c_int()
+        _capi.check(self._lib.bbme_chain_frames(self._ctx, C.byref(n)))
+        return n.value or 2 * getattr(self, "batch", 1)
+
+    def _consistency_stats(self, which, tol, window):
+        win = self._stats_window(window)
         pairs = getattr(self, "batch", 1)
         s = (C.c_ulonglong * (4 * pairs))()
         _capi.check(self._lib.bbme_consistency_stats(self._ctx, _which(which), int(tol), win, s))
@@ -416,7 +432,7 @@ class MF:
                                       and stats.is_contiguous()):
             raise _capi.BbmeError(_capi.ERR_INVALID, "cells_consistency_device: stats must be a contiguous int64 or uint64 CUDA "
                                   "tensor of 4")
-        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+        win = _window(window)
         self._behind_torch(a, b, mask, stats)
         _capi.check(self._lib.bbme_cells_consistency_device(
             self._ctx, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), int(tol), win,
@@ -432,10 +448,7 @@ class MF:
     def _get_flow_color(self, pair, scale, maxmotion, which, out, what):
         shape = self.color_shape(scale)
         scale = self.upsample if scale is None else int(scale)
-        if out is None:
-            out = np.empty(shape, np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
+        out = _host_out(out, shape, np.uint8, what)
         rng = (C.c_float * 5)()
         _capi.check(self._lib.bbme_get_flow_color_host(self._ctx, pair, _which(which), scale, float(maxmotion), out.ctypes.data, rng))
         self.last_color_range = tuple(rng)
@@ -498,14 +511,26 @@ class MF:
         return tuple(float(v) for v in self._flow_ranges(which, scale)[0])
 
     # -- motion-compensated interpolation between the two frames (the interpolation rule of include/bbme.h) ---------------
-    def _get_interpolated(self, pair, num, den, out, what):
-        shape = (self.padded_height, self.padded_width)
-        if out is None:
-            out = np.empty(shape, np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
-        _capi.check(self._lib.bbme_get_interpolated_host(self._ctx, pair, int(num), int(den), out.ctypes.data))
+    def _out_shape(self, bgr):
+        """What interpolation and the temporal filter write: the padded grey plane or, in colour, the unpadded B,G,R frame."""
+        return (self.orig_height, self.orig_width, 3) if bgr else (self.padded_height, self.padded_width)
+
+    def _get_interpolated(self, pair, num, den, out, what, bgr=False):
+        out = _host_out(out, self._out_shape(bgr), np.uint8, what)
+        get = self._lib.bbme_get_interpolated_bgr_host if bgr else self._lib.bbme_get_interpolated_host
+        _capi.check(get(self._ctx, pair, int(num), int(den), out.ctypes.data))
         return out
+
+    def _interpolate_run(self, den, pair, what, bgr):
+        import torch
+        den = int(den)
+        if not 2 <= den <= 256:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s %d outside 2..256" % (what, den))
+        frames = torch.empty((den - 1,) + self._out_shape(bgr), dtype=torch.uint8, device="cuda:%d" % self.device)
+        run = self._lib.bbme_interpolate_bgr_device if bgr else self._lib.bbme_interpolate_device
+        _capi.check(run(self._ctx, pair, 1, den - 1, den, _ptr(frames), frames.stride(1), frames.stride(0), None))
+        self.synchronize()
+        return frames.cpu().numpy()
 
     def interpolate(self, num=1, den=2, pair=0, out=None):
         """The frame at phase num / den between image1 (phase 0) and image2 (phase 1) after estimate_bidirectional_async():
@@ -515,40 +540,17 @@ class MF:
 
     def interpolate_run(self, den, pair=0):
         """All den - 1 phases 1 / den .. (den - 1) / den from one launch -> (den - 1, H_pad, W_pad) uint8."""
-        import torch
-        den = int(den)
-        if not 2 <= den <= 256:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_run: den %d outside 2..256" % den)
-        h, w = self.padded_height, self.padded_width
-        frames = torch.empty((den - 1, h, w), dtype=torch.uint8, device="cuda:%d" % self.device)
-        _capi.check(self._lib.bbme_interpolate_device(self._ctx, pair, 1, den - 1, den, C.c_void_p(frames.data_ptr()), w, h * w, None))
-        self.synchronize()
-        return frames.cpu().numpy()
+        return self._interpolate_run(den, pair, "interpolate_run: den", False)
 
     # -- colour frames out (the BGR interpolation rule of include/bbme.h): needs frames set as (H, W, 3) ------------------------
     def interpolate_bgr(self, num=1, den=2, pair=0, out=None):
         """interpolate() in colour: the selection of the grey frame, made on the luma planes, applied to the B,G,R frames the
         context was fed -> the UNPADDED (H, W, 3) uint8 frame.  BbmeError (ERR_STATE) when a frame of the pair was set grey."""
-        shape = (self.orig_height, self.orig_width, 3)
-        if out is None:
-            out = np.empty(shape, np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_bgr: out must be a C-contiguous uint8 array of shape %s" % (shape,))
-        _capi.check(self._lib.bbme_get_interpolated_bgr_host(self._ctx, pair, int(num), int(den), out.ctypes.data))
-        return out
+        return self._get_interpolated(pair, num, den, out, "interpolate_bgr", bgr=True)
 
     def interpolate_run_bgr(self, factor, pair=0):
         """All factor - 1 phases 1 / factor .. (factor - 1) / factor from one launch -> (factor - 1, H, W, 3) uint8."""
-        import torch
-        den = int(factor)
-        if not 2 <= den <= 256:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_run_bgr: factor %d outside 2..256" % den)
-        h, w = self.orig_height, self.orig_width
-        frames = torch.empty((den - 1, h, w, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
-        _capi.check(self._lib.bbme_interpolate_bgr_device(self._ctx, pair, 1, den - 1, den, C.c_void_p(frames.data_ptr()), 3 * w,
-                                                          3 * h * w, None))
-        self.synchronize()
-        return frames.cpu().numpy()
+        return self._interpolate_run(factor, pair, "interpolate_run_bgr: factor", True)
 
     def cells_interpolate_bgr_device(self, fwd, bwd=None, bgr1=None, bgr2=None, num0=1, count=1, den=2, pair=0, out=None,
                                      hip_stream_handle=None):
@@ -575,13 +577,10 @@ class MF:
             raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_bgr_device: out must be a uint8 CUDA tensor of shape "
                                   "(%d, %d, %d, 3) with packed pixels" % (count, h, w))
 
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if t is not None else 0)
-
         self._behind_torch(fwd, bwd, bgr1, bgr2, out)
         _capi.check(self._lib.bbme_cells_interpolate_bgr_device(
-            self._ctx, pair, ptr(fwd), ptr(bwd), ptr(bgr1), ptr(bgr2), bgr1.stride(0) if bgr1 is not None else 0, int(num0), count,
-            int(den), ptr(out), out.stride(1), max(out.stride(0), 0), C.c_void_p(hip_stream_handle or 0)))
+            self._ctx, pair, _ptr(fwd), _ptr(bwd), _ptr(bgr1), _ptr(bgr2), bgr1.stride(0) if bgr1 is not None else 0, int(num0), count,
+            int(den), _ptr(out), out.stride(1), max(out.stride(0), 0), C.c_void_p(hip_stream_handle or 0)))
         return out
 
     def bgr_frames_device_ptrs(self, pair=0):
@@ -591,9 +590,7 @@ class MF:
         return a.value, b.value
 
     def _interpolation_stats(self, num, den, window):
-        if window is None:
-            window = self.default_cell_window()
-        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
+        win = self._stats_window(window)
         pairs = getattr(self, "batch", 1)
         s = (C.c_ulonglong * (4 * pairs))()
         _capi.check(self._lib.bbme_interpolation_stats(self._ctx, int(num), int(den), win, s))
@@ -627,28 +624,29 @@ class MF:
                                       and stats.is_contiguous()):
             raise _capi.BbmeError(_capi.ERR_INVALID, "cells_interpolate_device: stats must be a contiguous int64 or uint64 CUDA "
                                   "tensor of shape (%d, 4)" % count)
-        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if t is not None else 0)
+        win = _window(window)
 
         self._behind_torch(fwd, bwd, out, sel, stats)
         _capi.check(self._lib.bbme_cells_interpolate_device(
-            self._ctx, pair, ptr(fwd), ptr(bwd), int(num0), count, int(den), win,
-            ptr(out), out.stride(1) if out is not None else 0, max(out.stride(0), 0) if out is not None else 0,
-            ptr(sel), sel.stride(1) if sel is not None else 0, max(sel.stride(0), 0) if sel is not None else 0,
-            ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+            self._ctx, pair, _ptr(fwd), _ptr(bwd), int(num0), count, int(den), win,
+            _ptr(out), out.stride(1) if out is not None else 0, max(out.stride(0), 0) if out is not None else 0,
+            _ptr(sel), sel.stride(1) if sel is not None else 0, max(sel.stride(0), 0) if sel is not None else 0,
+            _ptr(stats), C.c_void_p(hip_stream_handle or 0)))
         return out, sel, stats
 
     # -- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rule of include/bbme.h) ------
-    def _get_temporal_filtered(self, pair, which, strength, out, what):
-        shape = (self.padded_height, self.padded_width)
-        if out is None:
-            out = np.empty(shape, np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
-        _capi.check(self._lib.bbme_get_temporal_filtered_host(self._ctx, pair, int(which), int(strength), out.ctypes.data))
+    def _get_temporal_filtered(self, pair, which, strength, out, what, bgr=False):
+        out = _host_out(out, self._out_shape(bgr), np.uint8, what)
+        get = self._lib.bbme_get_temporal_filtered_bgr_host if bgr else self._lib.bbme_get_temporal_filtered_host
+        _capi.check(get(self._ctx, pair, int(which), int(strength), out.ctypes.data))
         return out
+
+    def _temporal_filter_stats(self, strength, window, bgr):
+        frames = self._frame_count()
+        s = (C.c_ulonglong * (4 * frames))()
+        stats = self._lib.bbme_temporal_filter_bgr_stats if bgr else self._lib.bbme_temporal_filter_stats
+        _capi.check(stats(self._ctx, int(strength), self._stats_window(window), s))
+        return [dict(zip(TEMPORAL_STAT_KEYS, s[4 * f:4 * f + 4])) for f in range(frames)]
 
     def temporal_filter(self, strength, which=0, pair=0, out=None):
         """Frame `which` (0 = image1, 1 = image2) of the pair after estimate_bidirectional_async(), averaged with its
@@ -662,15 +660,7 @@ class MF:
         ch) in cells: cells that took their previous / next neighbour, the sum of the weights and the sum of |out - frame| over
         the window's pixels.  Frames in the order image1, image2 of pair 0, of pair 1, ...; on an MFChain slot by slot.  Default
         window: default_cell_window(); "all": every cell."""
-        if window is None:
-            window = self.default_cell_window()
-        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
-        n = C.c_int()
-        _capi.check(self._lib.bbme_chain_frames(self._ctx, C.byref(n)))
-        frames = n.value or 2 * getattr(self, "batch", 1)
-        s = (C.c_ulonglong * (4 * frames))()
-        _capi.check(self._lib.bbme_temporal_filter_stats(self._ctx, int(strength), win, s))
-        return [dict(zip(TEMPORAL_STAT_KEYS, s[4 * f:4 * f + 4])) for f in range(frames)]
+        return self._temporal_filter_stats(strength, window, False)
 
     def cells_temporal_filter_device(self, cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, out=None, weights=None,
                                      stats=None, window=None, hip_stream_handle=None):
@@ -700,48 +690,28 @@ class MF:
                                       and stats.is_contiguous()):
             raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_device: stats must be a contiguous int64 or uint64 CUDA "
                                   "tensor of 4")
-        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if t is not None else 0)
+        win = _window(window)
 
         self._behind_torch(cur, prev, next, to_prev, to_next, out, weights, stats)
         _capi.check(self._lib.bbme_cells_temporal_filter_device(
-            self._ctx, ptr(prev), ptr(cur), ptr(next), ptr(to_prev), ptr(to_next), int(strength), win,
-            ptr(out), out.stride(0) if out is not None else 0, ptr(weights), weights.stride(0) if weights is not None else 0,
-            ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+            self._ctx, _ptr(prev), _ptr(cur), _ptr(next), _ptr(to_prev), _ptr(to_next), int(strength), win,
+            _ptr(out), out.stride(0) if out is not None else 0, _ptr(weights), weights.stride(0) if weights is not None else 0,
+            _ptr(stats), C.c_void_p(hip_stream_handle or 0)))
         return out, weights, stats
 
     # -- the same on the B,G,R frames (the BGR temporal filter rule of include/bbme.h): needs frames set as (H, W, 3) -----------
-    def _get_temporal_filtered_bgr(self, pair, which, strength, out, what):
-        shape = (self.orig_height, self.orig_width, 3)
-        if out is None:
-            out = np.empty(shape, np.uint8)
-        elif out.shape != shape or out.dtype != np.uint8 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a C-contiguous uint8 array of shape %s" % (what, shape))
-        _capi.check(self._lib.bbme_get_temporal_filtered_bgr_host(self._ctx, pair, int(which), int(strength), out.ctypes.data))
-        return out
-
     def temporal_filter_bgr(self, strength, which=0, pair=0, out=None):
         """temporal_filter() in colour: the stored B,G,R frame `which` averaged with its motion-aligned neighbour(s) wherever
         their 2x2 cells match better than `strength` in EVERY channel (the cost is the largest per-channel 2x2 SAD; the luma
         planes are not read) -> the UNPADDED (H, W, 3) uint8 frame.  Neighbours and grids as temporal_filter().  BbmeError
         (ERR_STATE) when the frame or a neighbour it uses was set grey."""
-        return self._get_temporal_filtered_bgr(pair, which, strength, out, "temporal_filter_bgr")
+        return self._get_temporal_filtered(pair, which, strength, out, "temporal_filter_bgr", bgr=True)
 
     def temporal_filter_bgr_stats(self, strength, window=None):
         """temporal_filter_stats() of the colour filter: one dict(prev_cells, next_cells, weight, change) per frame of the context
         from one launch, over window (cx0, cy0, cw, ch) in cells of the padded view; `change` sums |out - frame| over the window's
         pixels and three channels.  Default window: default_cell_window(); "all": every cell."""
-        if window is None:
-            window = self.default_cell_window()
-        win = None if window == "all" else (C.c_int * 4)(*[int(v) for v in window])
-        n = C.c_int()
-        _capi.check(self._lib.bbme_chain_frames(self._ctx, C.byref(n)))
-        frames = n.value or 2 * getattr(self, "batch", 1)
-        s = (C.c_ulonglong * (4 * frames))()
-        _capi.check(self._lib.bbme_temporal_filter_bgr_stats(self._ctx, int(strength), win, s))
-        return [dict(zip(TEMPORAL_STAT_KEYS, s[4 * f:4 * f + 4])) for f in range(frames)]
+        return self._temporal_filter_stats(strength, window, True)
 
     def cells_temporal_filter_bgr_device(self, cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, out=None,
                                          weights=None, stats=None, window=None, hip_stream_handle=None):
@@ -775,16 +745,13 @@ class MF:
                                       and stats.is_contiguous()):
             raise _capi.BbmeError(_capi.ERR_INVALID, "cells_temporal_filter_bgr_device: stats must be a contiguous int64 or uint64 "
                                   "CUDA tensor of 4")
-        win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr() if t is not None else 0)
+        win = _window(window)
 
         self._behind_torch(cur, prev, next, to_prev, to_next, out, weights, stats)
         _capi.check(self._lib.bbme_cells_temporal_filter_bgr_device(
-            self._ctx, ptr(prev), ptr(cur), ptr(next), cur.stride(0) if cur is not None else 0, ptr(to_prev), ptr(to_next),
-            int(strength), win, ptr(out), out.stride(0) if out is not None else 0, ptr(weights),
-            weights.stride(0) if weights is not None else 0, ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+            self._ctx, _ptr(prev), _ptr(cur), _ptr(next), cur.stride(0) if cur is not None else 0, _ptr(to_prev), _ptr(to_next),
+            int(strength), win, _ptr(out), out.stride(0) if out is not None else 0, _ptr(weights),
+            weights.stride(0) if weights is not None else 0, _ptr(stats), C.c_void_p(hip_stream_handle or 0)))
         return out, weights, stats
 
     def frame_bgr_tensor(self, pair=0, which=0):
@@ -828,10 +795,7 @@ class MF:
 
     def get_cells(self, out=None):
         shape = (self.padded_height // 2, self.padded_width // 2, 2)
-        if out is None:
-            out = np.empty(shape, np.int16)
-        elif out.shape != shape or out.dtype != np.int16 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "get_cells: out must be a C-contiguous int16 array of shape %s" % (shape,))
+        out = _host_out(out, shape, np.int16, "get_cells")
         _capi.check(self._lib.bbme_get_cells_host(self._ctx, out.ctypes.data))
         return out
 
@@ -967,19 +931,13 @@ class MFBatch(MF):
 
     def get_pair_flow(self, pair, out=None):
         shape = (self.padded_height, self.padded_width, 2)
-        if out is None:
-            out = np.empty(shape, np.float32)
-        elif out.shape != shape or out.dtype != np.float32 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "get_pair_flow: out must be a C-contiguous float32 array of shape %s" % (shape,))
+        out = _host_out(out, shape, np.float32, "get_pair_flow")
         _capi.check(self._lib.bbme_get_flow_host_pair(self._ctx, pair, out.ctypes.data))
         return out
 
     def get_pair_cells(self, pair, out=None):
         shape = (self.padded_height // 2, self.padded_width // 2, 2)
-        if out is None:
-            out = np.empty(shape, np.int16)
-        elif out.shape != shape or out.dtype != np.int16 or not out.flags.c_contiguous:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "get_pair_cells: out must be a C-contiguous int16 array of shape %s" % (shape,))
+        out = _host_out(out, shape, np.int16, "get_pair_cells")
         _capi.check(self._lib.bbme_get_cells_host_pair(self._ctx, pair, out.ctypes.data))
         return out
 
@@ -1022,7 +980,7 @@ class MFBatch(MF):
 
     def get_frame_filtered_bgr(self, pair, which, strength, out=None):
         """MF.temporal_filter_bgr of frame `which` of one pair."""
-        return self._get_temporal_filtered_bgr(pair, which, strength, out, "get_frame_filtered_bgr")
+        return self._get_temporal_filtered(pair, which, strength, out, "get_frame_filtered_bgr", bgr=True)
 
     def compensation_errors(self, level=0, block=2, window=None):
         """MF.compensation_error of every pair, in order, from one launch."""
@@ -1115,39 +1073,28 @@ class MFChain(MFBatch):
         if not wait:
             self._host_frames_in_flight = frames          # keeps converted copies alive until the next run replaces them
 
-    def temporal_filter_run(self, strength, first=0, count=None):
-        """Slots first .. first + count - 1 (default: to the last) filtered from one launch -> (count, H_pad, W_pad) uint8: the
-        first slot of the chain has no previous and the last no next neighbour, every other slot uses both."""
+    def _temporal_filter_run(self, strength, first, count, what, bgr):
         import torch
         first = int(first)
         count = self.batch + 1 - first if count is None else int(count)
         if first < 0 or count < 1 or first + count > self.batch + 1:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_run: slots %d .. %d of a chain of %d"
-                                  % (first, first + count - 1, self.batch + 1))
-        h, w = self.padded_height, self.padded_width
-        frames = torch.empty((count, h, w), dtype=torch.uint8, device="cuda:%d" % self.device)
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: slots %d .. %d of a chain of %d" % (what, first, first + count - 1, self.batch + 1))
+        frames = torch.empty((count,) + self._out_shape(bgr), dtype=torch.uint8, device="cuda:%d" % self.device)
         self._behind_torch(frames)
-        _capi.check(self._lib.bbme_temporal_filter_chain_device(self._ctx, first, count, int(strength), C.c_void_p(frames.data_ptr()),
-                                                                w, h * w, None))
+        run = self._lib.bbme_temporal_filter_bgr_chain_device if bgr else self._lib.bbme_temporal_filter_chain_device
+        _capi.check(run(self._ctx, first, count, int(strength), _ptr(frames), frames.stride(1), frames.stride(0), None))
         self.synchronize()
         return frames.cpu().numpy()
+
+    def temporal_filter_run(self, strength, first=0, count=None):
+        """Slots first .. first + count - 1 (default: to the last) filtered from one launch -> (count, H_pad, W_pad) uint8: the
+        first slot of the chain has no previous and the last no next neighbour, every other slot uses both."""
+        return self._temporal_filter_run(strength, first, count, "temporal_filter_run", False)
 
     def temporal_filter_run_bgr(self, strength, first=0, count=None):
         """temporal_filter_run() in colour: the stored B,G,R frames of slots first .. first + count - 1 (default: to the last)
         filtered from one launch -> (count, H, W, 3) uint8, unpadded."""
-        import torch
-        first = int(first)
-        count = self.batch + 1 - first if count is None else int(count)
-        if first < 0 or count < 1 or first + count > self.batch + 1:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_run_bgr: slots %d .. %d of a chain of %d"
-                                  % (first, first + count - 1, self.batch + 1))
-        h, w = self.orig_height, self.orig_width
-        frames = torch.empty((count, h, w, 3), dtype=torch.uint8, device="cuda:%d" % self.device)
-        self._behind_torch(frames)
-        _capi.check(self._lib.bbme_temporal_filter_bgr_chain_device(self._ctx, first, count, int(strength),
-                                                                    C.c_void_p(frames.data_ptr()), 3 * w, 3 * h * w, None))
-        self.synchronize()
-        return frames.cpu().numpy()
+        return self._temporal_filter_run(strength, first, count, "temporal_filter_run_bgr", True)
 
     def get_slot_plane(self, level, slot):
         """The padded plane of frame slot `slot` at `level` (bbme_get_chain_plane_host) -> (level height, level width) uint8."""
@@ -1204,7 +1151,7 @@ def cells_consistency(a, b, tol=1, window=None):
     ch, cw = a.shape[:2]
     mask = np.empty((ch, cw), np.uint8)
     s = (C.c_ulonglong * 4)()
-    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+    win = _window(window)
     _capi.check(_capi.lib().bbme_cells_consistency_host(a.ctypes.data, b.ctypes.data, cw, ch, int(tol), win, mask.ctypes.data, s))
     return mask, dict(zip(("consistent", "inconsistent", "outside", "discrepancy"), list(s)))
 
@@ -1241,11 +1188,44 @@ def interpolate_cells(image1, image2, fwd, bwd=None, num=1, den=2, window=None):
     out = np.empty((h, w), np.uint8)
     sel = np.empty((h // 2, w // 2), np.uint8)
     s = (C.c_ulonglong * 4)()
-    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
+    win = _window(window)
     _capi.check(_capi.lib().bbme_interpolate_host(image1.ctypes.data, image2.ctypes.data, w, h, fwd.ctypes.data,
                                                   None if bwd is None else bwd.ctypes.data, int(num), int(den), win,
                                                   out.ctypes.data, sel.ctypes.data, s))
     return out, sel, dict(zip(INTERPOLATION_STAT_KEYS, list(s)))
+
+
+def _temporal_filter_cells(what, cur, prev, next, to_prev, to_next, strength, window, bgr=False, pad_x=0, pad_y=0):
+    """temporal_filter_cells (grey planes: they are their own padded view, so no padding and nothing to check about it) and, with
+    bgr, temporal_filter_cells_bgr (colour frames inside a view padded by pad_x, pad_y); `what` names the caller in the errors."""
+    shapes = "uint8 frames of one shape (H, W, 3)" if bgr else "uint8 planes of one shape (H, W)"
+    grid_shapes = "int16 grids of shape (H0 / 2, W0 / 2, 2)" if bgr else "int16 grids of shape (H / 2, W / 2, 2)"
+    cur = np.ascontiguousarray(cur, np.uint8)
+    if cur.ndim != (3 if bgr else 2) or (bgr and cur.shape[2] != 3):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: %s" % (what, shapes))
+    h, w = cur.shape[:2]
+    pad_x, pad_y = int(pad_x), int(pad_y)
+    h0, w0 = h + 2 * pad_y, w + 2 * pad_x                 # the padded view the cells lie on; grey planes are it
+    if bgr and (pad_x < 0 or pad_y < 0 or h0 % 2 or w0 % 2):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: paddings >= 0 that make the padded size even" % what)
+    frames, grids = [], []
+    for frame, grid in ((prev, to_prev), (next, to_next)):
+        frame = None if frame is None else np.ascontiguousarray(frame, np.uint8)
+        grid = None if grid is None else np.ascontiguousarray(grid, np.int16)
+        if frame is not None and frame.shape != cur.shape:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: %s" % (what, shapes))
+        if grid is not None and grid.shape != (h0 // 2, w0 // 2, 2):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: %s" % (what, grid_shapes))
+        frames.append(frame)
+        grids.append(grid)
+    out = np.empty(cur.shape, np.uint8)
+    wmap = np.empty((h0 // 2, w0 // 2), np.uint8)
+    s = (C.c_ulonglong * 4)()
+    size = (w, h, pad_x, pad_y) if bgr else (w, h)
+    run = _capi.lib().bbme_temporal_filter_bgr_host if bgr else _capi.lib().bbme_temporal_filter_host
+    _capi.check(run(_ptr(frames[0]), cur.ctypes.data, _ptr(frames[1]), *size, _ptr(grids[0]), _ptr(grids[1]), int(strength),
+                    _window(window), out.ctypes.data, wmap.ctypes.data, s))
+    return out, wmap, dict(zip(TEMPORAL_STAT_KEYS, list(s)))
 
 
 def temporal_filter_cells(cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, window=None):
@@ -1253,31 +1233,7 @@ def temporal_filter_cells(cur, prev=None, next=None, to_prev=None, to_next=None,
     even size, to_prev, to_next int16 (H / 2, W / 2, 2) cell grids on cur; a neighbour is its plane and its grid, either may be
     None -> (frame (H, W) uint8, weights (H / 2, W / 2) uint8 holding wP | wN << 4, dict(prev_cells, next_cells, weight, change)
     over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
-    cur = np.ascontiguousarray(cur, np.uint8)
-    if cur.ndim != 2:
-        raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells: uint8 planes of one shape (H, W)")
-    h, w = cur.shape
-    planes, grids = [], []
-    for plane, grid in ((prev, to_prev), (next, to_next)):
-        plane = None if plane is None else np.ascontiguousarray(plane, np.uint8)
-        grid = None if grid is None else np.ascontiguousarray(grid, np.int16)
-        if plane is not None and plane.shape != cur.shape:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells: uint8 planes of one shape (H, W)")
-        if grid is not None and grid.shape != (h // 2, w // 2, 2):
-            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells: int16 grids of shape (H / 2, W / 2, 2)")
-        planes.append(plane)
-        grids.append(grid)
-    out = np.empty((h, w), np.uint8)
-    wmap = np.empty((h // 2, w // 2), np.uint8)
-    s = (C.c_ulonglong * 4)()
-    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
-
-    def ptr(a):
-        return None if a is None else a.ctypes.data
-
-    _capi.check(_capi.lib().bbme_temporal_filter_host(ptr(planes[0]), cur.ctypes.data, ptr(planes[1]), w, h, ptr(grids[0]),
-                                                      ptr(grids[1]), int(strength), win, out.ctypes.data, wmap.ctypes.data, s))
-    return out, wmap, dict(zip(TEMPORAL_STAT_KEYS, list(s)))
+    return _temporal_filter_cells("temporal_filter_cells", cur, prev, next, to_prev, to_next, strength, window)
 
 
 def temporal_filter_cells_bgr(cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, pad_x=0, pad_y=0, window=None):
@@ -1286,36 +1242,8 @@ def temporal_filter_cells_bgr(cur, prev=None, next=None, to_prev=None, to_next=N
     grids on cur; a neighbour is its frame and its grid, either may be None -> (frame (H, W, 3) uint8, weights (H0 / 2, W0 / 2)
     uint8 holding wP | wN << 4, dict(prev_cells, next_cells, weight, change) over window (cx0, cy0, cw, ch) in cells, None = all
     cells)."""
-    cur = np.ascontiguousarray(cur, np.uint8)
-    if cur.ndim != 3 or cur.shape[2] != 3:
-        raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: uint8 frames of one shape (H, W, 3)")
-    h, w = cur.shape[:2]
-    pad_x, pad_y = int(pad_x), int(pad_y)
-    h0, w0 = h + 2 * pad_y, w + 2 * pad_x
-    if pad_x < 0 or pad_y < 0 or h0 % 2 or w0 % 2:
-        raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: paddings >= 0 that make the padded size even")
-    frames, grids = [], []
-    for frame, grid in ((prev, to_prev), (next, to_next)):
-        frame = None if frame is None else np.ascontiguousarray(frame, np.uint8)
-        grid = None if grid is None else np.ascontiguousarray(grid, np.int16)
-        if frame is not None and frame.shape != cur.shape:
-            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: uint8 frames of one shape (H, W, 3)")
-        if grid is not None and grid.shape != (h0 // 2, w0 // 2, 2):
-            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_cells_bgr: int16 grids of shape (H0 / 2, W0 / 2, 2)")
-        frames.append(frame)
-        grids.append(grid)
-    out = np.empty((h, w, 3), np.uint8)
-    wmap = np.empty((h0 // 2, w0 // 2), np.uint8)
-    s = (C.c_ulonglong * 4)()
-    win = None if window is None else (C.c_int * 4)(*[int(v) for v in window])
-
-    def ptr(a):
-        return None if a is None else a.ctypes.data
-
-    _capi.check(_capi.lib().bbme_temporal_filter_bgr_host(ptr(frames[0]), cur.ctypes.data, ptr(frames[1]), w, h, pad_x, pad_y,
-                                                          ptr(grids[0]), ptr(grids[1]), int(strength), win, out.ctypes.data,
-                                                          wmap.ctypes.data, s))
-    return out, wmap, dict(zip(TEMPORAL_STAT_KEYS, list(s)))
+    return _temporal_filter_cells("temporal_filter_cells_bgr", cur, prev, next, to_prev, to_next, strength, window, bgr=True,
+                                  pad_x=pad_x, pad_y=pad_y)
 
 
 def bgr_to_gray(frame):

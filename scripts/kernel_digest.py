@@ -11,7 +11,9 @@ the same kernels when `diff` of their outputs is empty.
 The hash is over the disassembly without addresses, with ONE operand masked: the 32-bit literal of the s_add_u32 that
 follows an s_getpc_b64.  It is the distance from that instruction to its target (.rodata, or another function), so it
 changes when functions are merely placed in another order -- which the order of first template instantiation on the
-host side decides.  Everything else in a function is position-independent.  No GPU needed.
+host side decides.  Everything else in a function is position-independent.  The `s_nop 0` lines (and the `...` of a zero fill) that the disassembler
+prints between a function's last instruction and the next symbol are alignment padding, as many as the placement of the
+NEXT function needs: they are outside the symbol's size and are not hashed.  No GPU needed.
 """
 import argparse
 import hashlib
@@ -80,13 +82,13 @@ def resources(co):
 
 def code_hashes(co):
     """function symbol -> sha256 of its instructions, placement masked (see the module's docstring)"""
-    hashes, name, h, after_getpc = {}, None, None, False
+    hashes, name, h, after_getpc, held = {}, None, None, False, b""
     for line in _run(_tool("llvm-objdump"), "-d", "--no-show-raw-insn", co).splitlines():
         m = re.match(r"^[0-9a-f]+ <(.+)>:$", line)
         if m:
             if name:
                 hashes[name] = h.hexdigest()
-            name, h, after_getpc = m.group(1), hashlib.sha256(), False
+            name, h, after_getpc, held = m.group(1), hashlib.sha256(), False, b""
             continue
         if name is None or not line.startswith("\t"):
             continue
@@ -94,7 +96,11 @@ def code_hashes(co):
         if after_getpc:
             insn = re.sub(r"^(s_add_u32 s\d+, s\d+,) \S+$", r"\1 <pc-relative>", insn)
         after_getpc = insn.startswith("s_getpc_b64")
-        h.update(insn.encode() + b"\n")
+        if insn in ("s_nop 0", "..."):                            # hashed only once an instruction follows: a trailing run is padding
+            held += insn.encode() + b"\n"
+            continue
+        h.update(held + insn.encode() + b"\n")
+        held = b""
     if name:
         hashes[name] = h.hexdigest()
     return hashes

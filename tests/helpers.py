@@ -815,7 +815,7 @@ def scale_video(h, w, n, seed=SCALE_SEED):
 
 def scale_groups(w0, h0, runs_per_lane, cells=True):
     """(runs, workgroups, runs in the last workgroup) of a gather kernel whose lanes take runs_per_lane runs of 4 cells (of 4
-    pixels with cells=False) along a row: the arithmetic of mc_groups / fb_groups / ip_groups / tf_groups (csrc/bbme_device.hip)."""
+    pixels with cells=False) along a row: the arithmetic of gather_groups (csrc/bbme_device.hip)."""
     cols, rows = (w0 // 2, h0 // 2) if cells else (w0, h0)
     runs = (cols + 3) // 4 * rows
     per_group = 256 * runs_per_lane
