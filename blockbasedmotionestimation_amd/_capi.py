@@ -148,6 +148,13 @@ SIGNATURES = {
     "bbme_temporal_filter_bgr_chain_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "bbme_get_temporal_filtered_bgr_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_temporal_filter_bgr_stats": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_subpel_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_cells_subpel_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p,
+                                           C.c_void_p]),
+    "bbme_subpel_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_get_subpel_cells_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_subpel_stats": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_get_subpel_flow_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
     "bbme_frame_plane_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
     "bbme_cells_color_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_flow_color_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

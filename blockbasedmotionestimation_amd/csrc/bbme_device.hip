@@ -328,6 +328,10 @@ struct bbme_ctx {
     StatsScratch tf_stats;                        // bbme_temporal_filter_stats (every frame) and bbme_cells_temporal_filter_device (one)
     DevBuf<uint8_t> tf_bgr;                       // bbme_get_temporal_filtered_bgr_host: a packed 3 W x H frame before its download
     StatsScratch tf_bgr_stats;                    // the same of bbme_temporal_filter_bgr_stats and bbme_cells_temporal_filter_bgr_device
+    int src_scale = 1;                            // 4 after a setter of frames to up-sample (bbme_set_frames_*_x4, scale 4 of a chain), else 1
+    DevBuf<mv_t> sp_cells;                        // bbme_get_subpel_cells_host / _flow_host: a packed CH x CW quarter-pel grid
+    DevBuf<float> sp_flow;                        // bbme_get_subpel_flow_host: the packed field before its download
+    StatsScratch sp_stats;                        // bbme_subpel_stats (every pair) and bbme_cells_subpel_device (one pair)
 };
 
 namespace {
@@ -1261,6 +1265,7 @@ int prepare_frames(bbme_ctx *c, FrameSet set, const FrameRun &src, int pitch, Fr
 {
     const Geometry &g = c->geom;
     Level &L0 = c->lv[0];
+    c->src_scale = fmt == kGreyX4 ? 4 : 1;
     const long long chunks = (long long)((L0.width + 15) / 16) * L0.height;
     const dim3 grid0((unsigned)((chunks + 255) / 256), (unsigned)set.count);
     if (fmt == kBgr)
@@ -2841,6 +2846,174 @@ int bbme_get_temporal_filtered_bgr_host(bbme_ctx *c, int pair, int which, int th
 int bbme_temporal_filter_bgr_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
 {
     return tf_stats<TfBgr>(c, "bbme_temporal_filter_bgr_stats", thr, window, stats);
+}
+
+// ---- quarter-pel refinement of a cell grid (the SUBPEL RULE of include/bbme.h; K10 k_subpel_refine) ------------------------------
+
+static int sp_tiles_x(const bbme_ctx *c) { return (c->lv[0].width / 2 + kSpTileW - 1) / kSpTileW; }
+static long long sp_groups(const bbme_ctx *c) { return (long long)sp_tiles_x(c) * ((c->lv[0].height / 2 + kSpTileH - 1) / kSpTileH); }
+
+// result words of every pair, partials of a launch over every pair, then those of a caller's launch: one size per context
+static int sp_scratch(bbme_ctx *c)
+{
+    return c->sp_stats.ensure(BBME_MAX_BATCH, sp_groups(c), c->batch, 1, "the subpel statistics");
+}
+
+// geometry and window.  Touches no device.
+static int check_sp(const bbme_ctx *c, const int *window, const char *what)
+{
+    const Level &L = c->lv[0];
+    if (L.width > 8188 || L.height > 8188)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: a %dx%d plane is beyond 8188 (quarter-pel vectors would not fit 16 bits)", what,
+                          L.width, L.height);
+    return check_window(window, L.width / 2, L.height / 2, what, -1);
+}
+
+static int check_which(int which, const char *what)
+{
+    if (which != 0 && which != 1) return bbme::fail(BBME_ERR_INVALID, "%s: which = %d (0 or 1)", what, which);
+    return BBME_OK;
+}
+
+// The context's own planes and grid of `which`, pairs s_plane bytes and *s_grid words apart: 0 = the current level-0 cells against
+// (image 1, image 2) of the context's direction, 1 = the backward cells against (image 2, image 1).
+static int sp_source(const bbme_ctx *c, int which, const char *what, const uint8_t **img1, const uint8_t **img2, const mv_t **grid,
+                     uint32_t *s_grid)
+{
+    const Level &L = c->lv[0];
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    if (int rc = color_source(c, which, what, grid, s_grid)) return rc;
+    *img1 = which ? L.img2 : c->plane1(L);
+    *img2 = which ? L.img1.get() : c->plane2(L);
+    return BBME_OK;
+}
+
+// k_subpel_refine over `pairs` pairs: the grid (rows out_pitch, pairs s_out cells apart) and / or, with d_stats, the statistics
+static int enqueue_sp(bbme_ctx *c, const uint8_t *img1, const uint8_t *img2, size_t s_plane, const mv_t *grid, size_t s_grid, int pairs,
+                      const int *window, mv_t *d_out, int out_pitch, size_t s_out, unsigned long long *partial,
+                      unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    SpArgs a{};
+    a.img1 = img1; a.img2 = img2; a.grid = grid; a.out = d_out;
+    a.s_plane = s_plane; a.s_grid = s_grid; a.s_out = s_out;
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2; a.ch = L.height / 2;
+    a.out_pitch = out_pitch; a.tiles_x = sp_tiles_x(c);
+    set_window(a, window, a.cw, a.ch);
+    return launch_gather(k_subpel_refine, a, sp_groups(c), pairs, 1, partial, d_stats, stream);
+}
+
+static int enqueue_own_sp(bbme_ctx *c, int pair, int which, mv_t *d_out, int out_pitch, hipStream_t stream, const char *what)
+{
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+    const size_t s_plane = c->lv[0].plane_stride;
+    return enqueue_sp(c, i1 + pair * s_plane, i2 + pair * s_plane, 0, grid + (size_t)pair * s_grid, 0, 1, nullptr, d_out, out_pitch, 0,
+                      nullptr, nullptr, stream);
+}
+
+int bbme_cells_subpel_device(bbme_ctx *c, const uint8_t *d_image1, const uint8_t *d_image2, const int16_t *d_cells, const int *window,
+                             int16_t *d_q4, int q4_pitch_cells, unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_subpel_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    const int cw = L.width / 2, ch = L.height / 2;
+    if (!d_image1 || !d_image2 || !d_cells || (!d_q4 && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_sp(c, window, what)) return rc;
+    if (d_q4 && q4_pitch_cells < cw) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d cells per row", what, q4_pitch_cells, cw);
+    if (d_q4 && overlaps_input(reinterpret_cast<const uint8_t *>(d_q4), q4_pitch_cells * 4, {reinterpret_cast<const uint8_t *>(d_cells)},
+                               cw * 4, cw * 4, ch))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps the input grid", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = sp_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_sp(c, d_image1, d_image2, 0, reinterpret_cast<const mv_t *>(d_cells), 0, 1, window, reinterpret_cast<mv_t *>(d_q4),
+                      q4_pitch_cells, 0, c->sp_stats.partials_caller(), d_stats4, stream);
+}
+
+int bbme_subpel_device(bbme_ctx *c, int pair, int which, int16_t *d_q4, int q4_pitch_cells, void *hip_stream)
+{
+    const char *what = "bbme_subpel_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (!d_q4) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_sp(c, nullptr, what)) return rc;
+    if (q4_pitch_cells < c->lv[0].width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d cells per row", what, q4_pitch_cells, c->lv[0].width / 2);
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;       // the state, before anything is enqueued
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_sp(c, pair, which, reinterpret_cast<mv_t *>(d_q4), q4_pitch_cells, stream, what);
+}
+
+// the refined grid of (pair, which) in c->sp_cells, packed, on the context's stream
+static int own_sp_staged(bbme_ctx *c, int pair, int which, const char *what)
+{
+    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
+    if (int rc = c->sp_cells.ensure((size_t)cw * ch, "the quarter-pel cells")) return rc;
+    return enqueue_own_sp(c, pair, which, c->sp_cells, cw, c->stream, what);
+}
+
+static int check_sp_get(const bbme_ctx *c, int pair, int which, const void *out, const char *what)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    return check_sp(c, nullptr, what);
+}
+
+int bbme_get_subpel_cells_host(bbme_ctx *c, int pair, int which, int16_t *q4)
+{
+    const char *what = "bbme_get_subpel_cells_host";
+    if (int rc = check_sp_get(c, pair, which, q4, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = own_sp_staged(c, pair, which, what)) return rc;
+    const size_t n = (size_t)(c->lv[0].width / 2) * (c->lv[0].height / 2);
+    HIP_TRY(hipMemcpyAsync(q4, c->sp_cells, n * sizeof(mv_t), hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
+}
+
+int bbme_subpel_stats(bbme_ctx *c, int which, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_subpel_stats";
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (int rc = check_sp(c, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = sp_scratch(c)) return rc;
+    return download_stats(c, c->sp_stats, c->batch, stats, [&] {
+        return enqueue_sp(c, i1, i2, c->lv[0].plane_stride, grid, s_grid, c->batch, window, nullptr, 0, 0, c->sp_stats.partials_all(),
+                          c->sp_stats.results(), c->stream);
+    });
+}
+
+int bbme_get_subpel_flow_host(bbme_ctx *c, int pair, int which, float *flow)
+{
+    const char *what = "bbme_get_subpel_flow_host";
+    if (int rc = check_sp_get(c, pair, which, flow, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = own_sp_staged(c, pair, which, what)) return rc;
+    const int scale = c->src_scale, ow = (c->geom.width + scale - 1) / scale, oh = (c->geom.height + scale - 1) / scale;
+    const size_t floats = (size_t)ow * oh * 2;
+    if (int rc = c->sp_flow.ensure(floats, "the quarter-pel field")) return rc;
+    hipLaunchKernelGGL(k_subsample_q4, dim3((unsigned)(((long long)ow * oh + 255) / 256)), dim3(256), 0, c->stream, c->sp_cells.get(),
+                       c->lv[0].width / 2, c->geom.pad_x, c->geom.pad_y, scale, c->sp_flow.get(), ow, oh);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(flow, c->sp_flow, floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+    return check_converged(c);
 }
 
 extern "C" {

@@ -939,6 +939,69 @@ int bbme_subsample_div4(const float *flow_padded, int padded_width, int padded_h
     return BBME_OK;
 }
 
+// The SUBPEL RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_subpel_refine).  A candidate's
+// samples are taken the separable way the rule allows: the horizontal sums of the nine rows it touches, then the vertical sum
+// with the single rounding.
+int bbme_subpel_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *cells, const int *window,
+                     int16_t *out_q4, unsigned long long *stats4)
+{
+    const char *what = "bbme_subpel_host";
+    if (!image1 || !image2 || !cells || (!out_q4 && !stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
+    if (width > 8188 || height > 8188)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: %dx%d is beyond 8188 (quarter-pel vectors would not fit 16 bits)", what, width, height);
+    const int cw = width / 2, ch = height / 2;
+    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
+        return bbme::fail(BBME_ERR_INVALID, "%s: window not inside the %dx%d cells", what, cw, ch);
+    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
+    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
+    const auto sat16 = [](int v) { return (int16_t)(v < -32768 ? -32768 : v > 32767 ? 32767 : v); };
+    static const int order[8][2] = {{-1, -1}, {0, -1}, {1, -1}, {-1, 0}, {1, 0}, {-1, 1}, {0, 1}, {1, 1}};
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            const int vx = cells[2 * c], vy = cells[2 * c + 1];
+            const int ax = 2 * cx - 3, ay = 2 * cy - 3, bx = ax + vx, by = ay + vy;
+            int qx = 0, qy = 0;
+            if (ax >= 0 && ax + 8 <= width && ay >= 0 && ay + 8 <= height && bx >= 2 && bx + 10 <= width && by >= 2 && by + 10 <= height) {
+                int ref[8][8], patch[10][10];                 // I1's window; I2 at b + (-1 .. 8, -1 .. 8)
+                for (int i = 0; i < 8; ++i)
+                    for (int j = 0; j < 8; ++j) ref[i][j] = image1[(size_t)(ay + i) * width + ax + j];
+                for (int i = 0; i < 10; ++i)
+                    for (int j = 0; j < 10; ++j) patch[i][j] = image2[(size_t)(by - 1 + i) * width + bx - 1 + j];
+                const auto cost = [&](int cqx, int cqy) {
+                    const int ix = cqx >> 2, iy = cqy >> 2, fx = cqx & 3, fy = cqy & 3;
+                    int h[9][8];
+                    for (int i = 0; i < 9; ++i)
+                        for (int j = 0; j < 8; ++j)
+                            h[i][j] = (4 - fx) * patch[1 + iy + i][1 + ix + j] + fx * patch[1 + iy + i][2 + ix + j];
+                    int sum = 0;
+                    for (int i = 0; i < 8; ++i)
+                        for (int j = 0; j < 8; ++j) sum += abs(ref[i][j] - (((4 - fy) * h[i][j] + fy * h[i + 1][j] + 8) >> 4));
+                    return sum;
+                };
+                const int cost0 = cost(0, 0);
+                int best = cost0;
+                for (int step = 2; step >= 1; --step) {
+                    const int c0x = qx, c0y = qy;
+                    for (const auto &d : order) {
+                        const int k = cost(c0x + step * d[0], c0y + step * d[1]);
+                        if (k < best) { best = k; qx = c0x + step * d[0]; qy = c0y + step * d[1]; }
+                    }
+                }
+                if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) {
+                    ++s[0]; s[1] += qx != 0 || qy != 0; s[2] += (unsigned)cost0; s[3] += (unsigned)best;
+                }
+            }
+            if (out_q4) { out_q4[2 * c] = sat16(4 * vx + qx); out_q4[2 * c + 1] = sat16(4 * vy + qy); }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 int bbme_spiral_host(int search_size, int block_size, int16_t *dx, int16_t *dy, int capacity, int *count)
 {
     if (!count) return bbme::fail(BBME_ERR_INVALID, "bbme_spiral_host: null count");

@@ -3752,4 +3752,141 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
     store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
 }
 
+
+// =======================================================================================
+// K10.  Quarter-pel refinement of a 2x2-cell grid at the planes' own resolution (the SUBPEL RULE of include/bbme.h): a valid cell
+// compares I1's 8 x 8 window around it with bilinear quarter-pel samples of I2 at 17 offsets q -- (0, 0), the eight half-pel
+// neighbours, the eight quarter-pel neighbours of the best of those -- and leaves sat16(4 v + q).
+// One cell per lane, a workgroup a tile of 32 x 8 cells (blockIdx.x = tile, row-major; a wave two tile rows), so that neighbouring
+// lanes' windows overlap in L1 / TA: the window is 8 unaligned 8-byte loads, I2's 10 x 10 patch b + (-1 .. 8, -1 .. 8) ten unaligned
+// 8 + 4-byte loads (12 bytes: the two past the patch are b.x + 9 and b.x + 10 <= W0 of a row that is not the plane's last), and
+// with cells that share v the lanes' addresses run along the rows as the window's do.  Both stay in registers as bytes, 16 + 30
+// dwords, for all 17 candidates; the loads are 18 of the 6 800 instructions a valid cell takes, so neither goes through LDS.
+// A candidate (sp_cost) is the rule's separable form on 16-bit pairs.  Its integer part picks, per lane, the nine patch rows
+// (v_cndmask) and, along x, the byte pairs (v_perm_b32 with a selector that holds the shift); then per row four v_pk_mul_lo_u16 /
+// v_pk_mad_u16 give the horizontal sums (4 - fx) P0 + fx P1 of eight pixels, per output row a v_pk_mul_lo_u16, a v_pk_mad_u16,
+// a v_pk_add_u16 (the rounding 8) and a v_pk_lshrrev_b16 per pixel pair the samples, two v_perm_b32 repack them to bytes and two
+// v_sad_u8 add |I1 - sample|: about 400 VALU a candidate (88 v_perm_b32, 168 packed 16-bit, 16 v_sad_u8, 27 v_cndmask, moves).  The 17 candidates are one loop (not unrolled: the order of the rule's visits is its index), a lane keeping best
+// and q; ties keep the earlier candidate because the comparison is strict.
+// Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: valid cells, cells with q != 0, the sums of cost(0, 0) and of
+// best; a lane holds one cell of at most 16320 (store_partial4, frame = pair).  blockIdx.y = pair: planes s_plane bytes, grids
+// s_grid and outputs s_out words apart.
+// =======================================================================================
+struct SpArgs {
+    const uint8_t *img1, *img2;           // packed width x height planes
+    const mv_t *grid;                     // cw entries per row, ch rows: integer vectors on img1 into img2
+    mv_t *out;                            // quarter-pel vectors, rows out_pitch cells apart; or null
+    unsigned long long *partial;          // per pair and workgroup {valid, moved, cost(0, 0), best}; or null
+    size_t s_plane, s_grid, s_out;
+    int width, height, cw, ch, out_pitch, tiles_x;
+    int wx0, wy0, wx1, wy1;
+};
+
+constexpr int kSpTileW = 32, kSpTileH = 8;
+
+typedef unsigned short sp_u16x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ sp_u16x2 sp_pair(uint32_t v) { return __builtin_bit_cast(sp_u16x2, v); }
+__device__ __forceinline__ sp_u16x2 sp_splat(int v) { return sp_u16x2{(unsigned short)v, (unsigned short)v}; }
+
+// cost(q) of the rule: ref = I1's window, two dwords per row; pat = I2 at b + (-1 .. 10, -1 .. 8), three dwords per row
+__device__ __forceinline__ uint32_t sp_cost(const uint32_t (&ref)[8][2], const uint32_t (&pat)[10][3], int qx, int qy)
+{
+    const bool up = qy < 0;                                   // iy = -1: the rows start one higher
+    const uint32_t sx = (uint32_t)(1 + (qx >> 2));            // first byte of a row's nine: 0 or 1
+    // byte pair (k, k + 1) of two dwords as two 16-bit values: the selector of v_perm_b32 (0x0c = a zero byte)
+    const uint32_t s0 = 0x0c010c00u + sx * 0x00010001u, s1 = s0 + 0x00010001u, s2 = s1 + 0x00010001u, s3 = s2 + 0x00010001u;
+    const sp_u16x2 wx1 = sp_splat(qx & 3), wx0 = sp_splat(4 - (qx & 3)), wy1 = sp_splat(qy & 3), wy0 = sp_splat(4 - (qy & 3));
+    const sp_u16x2 half = sp_splat(8), four = sp_splat(4);
+    sp_u16x2 above[4] = {};
+    uint32_t sum = 0;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) {
+        const uint32_t d0 = up ? pat[i][0] : pat[i + 1][0], d1 = up ? pat[i][1] : pat[i + 1][1], d2 = up ? pat[i][2] : pat[i + 1][2];
+        sp_u16x2 h[4];
+        h[0] = sp_pair(__builtin_amdgcn_perm(d1, d0, s0)) * wx0 + sp_pair(__builtin_amdgcn_perm(d1, d0, s1)) * wx1;
+        h[1] = sp_pair(__builtin_amdgcn_perm(d1, d0, s2)) * wx0 + sp_pair(__builtin_amdgcn_perm(d1, d0, s3)) * wx1;
+        h[2] = sp_pair(__builtin_amdgcn_perm(d2, d1, s0)) * wx0 + sp_pair(__builtin_amdgcn_perm(d2, d1, s1)) * wx1;
+        h[3] = sp_pair(__builtin_amdgcn_perm(d2, d1, s2)) * wx0 + sp_pair(__builtin_amdgcn_perm(d2, d1, s3)) * wx1;
+        if (i > 0) {
+            uint32_t v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[k] = __builtin_bit_cast(uint32_t, (above[k] * wy0 + h[k] * wy1 + half) >> four);
+            sum = __builtin_amdgcn_sad_u8(ref[i - 1][0], __builtin_amdgcn_perm(v[1], v[0], 0x06040200u), sum);
+            sum = __builtin_amdgcn_sad_u8(ref[i - 1][1], __builtin_amdgcn_perm(v[3], v[2], 0x06040200u), sum);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) above[k] = h[k];
+    }
+    return sum;
+}
+
+__global__ __launch_bounds__(256) void k_subpel_refine(SpArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const uint8_t *I1 = a.img1 + pair * a.s_plane, *I2 = a.img2 + pair * a.s_plane;
+    const int W = a.width, H = a.height;
+    const int cx = (int)(blockIdx.x % (unsigned)a.tiles_x) * kSpTileW + (int)(threadIdx.x & (kSpTileW - 1));
+    const int cy = (int)(blockIdx.x / (unsigned)a.tiles_x) * kSpTileH + (int)(threadIdx.x / kSpTileW);
+    uint32_t nvalid = 0, nmoved = 0, sum0 = 0, sumb = 0;
+    if (cx < a.cw && cy < a.ch) {
+        const mv_t g = a.grid[pair * a.s_grid + (size_t)cy * a.cw + cx];
+        const int vx = mv_x(g), vy = mv_y(g);
+        const int ax = 2 * cx - 3, ay = 2 * cy - 3, bx = ax + vx, by = ay + vy;
+        int qx = 0, qy = 0;
+        if (ax >= 0 && ax + 8 <= W && ay >= 0 && ay + 8 <= H && bx >= 2 && bx + 10 <= W && by >= 2 && by + 10 <= H) {
+            uint32_t ref[8][2], pat[10][3];
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(I1 + (size_t)(ay + i) * W + ax);
+                ref[i][0] = t.v[0]; ref[i][1] = t.v[1];
+            }
+#pragma unroll
+            for (int i = 0; i < 10; ++i) {
+                const uint8_t *row = I2 + (size_t)(by - 1 + i) * W + (bx - 1);
+                const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(row);
+                pat[i][0] = t.v[0]; pat[i][1] = t.v[1];
+                pat[i][2] = reinterpret_cast<const ua_u32 *>(row + 8)->v;
+            }
+            int best = 0x7fffffff, cost0 = 0, ox = 0, oy = 0;     // (ox, oy): the q a stage starts from
+#pragma unroll 1
+            for (int k = 0; k < 17; ++k) {
+                int dx = 0, dy = 0;
+                if (k) {                                          // the rule's order: the 3 x 3 raster without its centre
+                    const int t = (k - 1) & 7, idx = t + (t >= 4);
+                    dx = idx % 3 - 1; dy = idx / 3 - 1;
+                    if (k < 9) { dx *= 2; dy *= 2; }
+                }
+                if (k == 9) { ox = qx; oy = qy; }
+                const int tx = ox + dx, ty = oy + dy;
+                const int cost = (int)sp_cost(ref, pat, tx, ty);
+                if (k == 0) cost0 = cost;
+                if (cost < best) { best = cost; qx = tx; qy = ty; }
+            }
+            if (a.partial && cx >= a.wx0 && cx < a.wx1 && cy >= a.wy0 && cy < a.wy1) {
+                nvalid = 1; nmoved = (qx | qy) != 0; sum0 = (uint32_t)cost0; sumb = (uint32_t)best;
+            }
+        }
+        if (a.out) {
+            const int ux = min(max(4 * vx + qx, -32768), 32767), uy = min(max(4 * vy + qy, -32768), 32767);
+            a.out[pair * a.s_out + (size_t)cy * a.out_pitch + cx] = ((uint32_t)ux & 0xffffu) | ((uint32_t)uy << 16);
+        }
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, pair, part, nvalid, nmoved, sum0, sumb);
+}
+
+// The quarter-pel grid as the driver's field (main_class.cpp:58-70, k_subsample's indexing): out(y, x) = cell((pad_y + s y) >> 1,
+// (pad_x + s x) >> 1) / (4 s) for the ceil(W / s) x ceil(H / s) field of the unpadded frame; packed rows.  One pixel per thread.
+__global__ __launch_bounds__(256) void k_subsample_q4(const mv_t *cells, int cell_cols, int pad_x, int pad_y, int scale, float *out,
+                                                      int out_width, int out_height)
+{
+    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (t >= (long long)out_width * out_height) return;
+    const int x = (int)(t % out_width), y = (int)(t / out_width);
+    const mv_t m = cells[(size_t)((pad_y + scale * y) >> 1) * cell_cols + ((pad_x + scale * x) >> 1)];
+    const float s = (float)(4 * scale);
+    *reinterpret_cast<float2 *>(out + 2 * (size_t)t) = make_float2((float)mv_x(m) / s, (float)mv_y(m) / s);
+}
+
 }  // namespace bbme

@@ -2,7 +2,7 @@
 //
 //   bbme_cli frame10.pgm|.ppm frame11.pgm|.ppm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
-//            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T]
+//            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T] [--subpel sub.flo]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -23,6 +23,9 @@
 // the unpadded frames; it needs --no-upsample (the frames written are the frames read; on colour frames, their luma).  On colour
 // frames it also writes PREFIX_1.ppm and PREFIX_2.ppm: the colour frames filtered by the BGR temporal filter rule, whose weights
 // come from the colour frames themselves (the largest per-channel 2x2 SAD) and not from the luma.
+// --subpel writes the estimated field refined to quarter-pel on the planes the estimate ran on (the subpel rule of include/bbme.h),
+// through the same writer as --out, and with --gt prints its EPE too: with --no-upsample sub-pixel vectors at the frames' own
+// resolution, a sixteenth of the pixels of the reference's pipeline; without it sixteenths of a pixel of the frames read.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -73,7 +76,7 @@ static bool read_pnm(const char *path, bbme::Image8 &img, bbme::ImageBGR &bgr, b
 int main(int argc, char **argv)
 {
     const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
-               *backward_color = nullptr, *denoise = nullptr;
+               *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr;
     int factor = 2, strength = 64;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
@@ -89,6 +92,7 @@ int main(int argc, char **argv)
         else if (a == "--interpolate") interpolate = next();
         else if (a == "--backward-color") backward_color = next();
         else if (a == "--denoise") denoise = next();
+        else if (a == "--subpel") subpel = next();
         else if (a == "--strength") strength = atoi(next());
         else if (a == "--factor") factor = atoi(next());
         else if (a == "--levels") levels = atoi(next());
@@ -105,7 +109,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: bbme_cli frame1.pgm|.ppm frame2.pgm|.ppm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
-                        "[--denoise PREFIX --strength T]\n"
+                        "[--denoise PREFIX --strength T] [--subpel sub.flo]\n"
                         "--denoise writes PREFIX_1.pgm and PREFIX_2.pgm (on .ppm frames their luma) and, on .ppm frames, the "
                         "filtered colour frames PREFIX_1.ppm and PREFIX_2.ppm; it needs --no-upsample\n");
         return 2;
@@ -153,6 +157,15 @@ int main(int argc, char **argv)
             bbme::ImageFlow gtruth;
             file.ReadFlowFile(gtruth, gt);
             printf("Calculated MSE is %.9g\n", file.CalculateMSE(gtruth, subpix));       // :82
+        }
+        if (subpel) {                                  // before anything below replaces the forward field
+            const bbme::ImageFlow refined = motion_pair.subpelFlow();
+            file.WriteFlowFile(refined, subpel);
+            if (gt) {
+                bbme::ImageFlow gtruth;
+                file.ReadFlowFile(gtruth, gt);
+                printf("Calculated MSE after quarter-pel refinement is %.9g\n", file.CalculateMSE(gtruth, refined));
+            }
         }
         if (mc) {
             const bbme::Image8 img = motion_pair.drawMVimage(0, 2, 0);

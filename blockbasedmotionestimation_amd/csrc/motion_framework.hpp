@@ -179,6 +179,19 @@ public:
         bbme::check(bbme_get_subsampled_flow_host(ctx_, 0, scale, flow.data.data()));
         return flow;
     }
+    // The current field refined to quarter-pel on the level-0 planes (the SUBPEL RULE of include/bbme.h), as the driver's field of
+    // the source frame: every pixel its cell's quarter-pel vector / 4, or, on frames up-sampled x4, every 4th pixel / 16.
+    // backward = true: the backward field after estimateBidirectional().  Needs an estimate.
+    bbme::ImageFlow subpelFlow(bool backward = false)
+    {
+        int w = 0, h = 0;
+        bbme::check(bbme_level_geometry(ctx_, 0, &w, &h, nullptr, nullptr));
+        w -= 2 * padding_x;
+        h -= 2 * padding_y;
+        bbme::ImageFlow flow((h + upsample - 1) / upsample, (w + upsample - 1) / upsample);
+        bbme::check(bbme_get_subpel_flow_host(ctx_, 0, backward ? 1 : 0, flow.data.data()));
+        return flow;
+    }
     // MF::draw_MVimage (motion_framework.cpp:887-905) from the level's current MV grid with b x b blocks (include/bbme.h):
     // the padded W_l x H_l plane, skipped blocks set to `fill`.  (level 0, block 2) after calcMotionBlockMatching is the
     // reference's "MC_imageL1" (:213-216).

@@ -440,6 +440,75 @@ class MF:
             C.c_void_p(stats.data_ptr() if stats is not None else 0), C.c_void_p(hip_stream_handle or 0)))
         return mask, stats
 
+    # -- quarter-pel refinement of the cells at the planes' own resolution (the SUBPEL RULE of include/bbme.h) -----------------------
+    def _subpel_cells(self, pair, which, out, what):
+        out = _host_out(out, self.cells_shape + (2,), np.int16, what)
+        _capi.check(self._lib.bbme_get_subpel_cells_host(self._ctx, pair, _which(which), out.ctypes.data))
+        return out
+
+    def subpel_cells(self, which="forward", pair=0, out=None):
+        """The context's cells refined to quarter-pel on its level-0 planes -> (CH, CW, 2) int16, 4 x integer vector + q with
+        q in [-3, 3]^2.  which="forward": the current cells against (image 1, image 2), after estimate_async() or
+        estimate_bidirectional_async(); "backward": the backward cells against (image 2, image 1).  An upsample=4 context
+        refines its 4x planes (1/16 pel of the source)."""
+        return self._subpel_cells(pair, which, out, "subpel_cells")
+
+    def _subpel_flow(self, pair, which, out, what):
+        out = _host_out(out, self.subsampled_shape(), np.float32, what)
+        _capi.check(self._lib.bbme_get_subpel_flow_host(self._ctx, pair, _which(which), out.ctypes.data))
+        return out
+
+    def subpel_flow(self, which="forward", pair=0, out=None):
+        """The refined field of the unpadded source frame -> (H, W, 2) float32 in pixels of the source: every pixel its cell's
+        quarter-pel vector / 4; on an upsample=4 context every 4th pixel of the 4x frame, / 16.  Ready for Flow.write_flow_file
+        and Flow.calculate_mse."""
+        return self._subpel_flow(pair, which, out, "subpel_flow")
+
+    def _subpel_stats(self, which, window):
+        win = self._stats_window(window)
+        pairs = getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_subpel_stats(self._ctx, _which(which), win, s))
+        return [dict(zip(_SUBPEL_STATS, s[4 * p:4 * p + 4])) for p in range(pairs)]
+
+    def subpel_stats(self, which="forward", window=None):
+        """dict(valid, moved, cost_integer, cost_refined) of the refinement over window (cx0, cy0, cw, ch) in cells: valid cells,
+        cells with q != (0, 0), and the sums of the 8x8 window's SAD at the integer vector and at the refined one over the
+        valid cells.  Default window: default_cell_window(); "all": every cell of the padded grid."""
+        return self._subpel_stats(which, window)[0]
+
+    def cells_subpel_device(self, i1, i2, cells, out=None, stats=None, window=None, stream=None):
+        """The subpel rule on any two planes and any cell grid in HBM: i1, i2 contiguous uint8 CUDA tensors (H_pad, W_pad), cells a
+        contiguous int16 CUDA tensor (CH, CW, 2); out an int16 CUDA tensor (CH, CW, 2) whose rows may be further apart than CW
+        cells; stats an int64 or uint64 CUDA tensor of 4 (valid, moved, cost_integer, cost_refined) over window (cx0, cy0, cw, ch)
+        in cells (None = all cells).  On the given HIP stream handle (default: the context's), ordered behind the context's
+        stream; no host wait.  Needs no frames and no estimate."""
+        import torch
+        what = "cells_subpel_device"
+        ch, cw = self.cells_shape
+        for t in (i1, i2):
+            if not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (2 * ch, 2 * cw) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: planes must be contiguous uint8 CUDA tensors of shape (%d, %d)"
+                                      % (what, 2 * ch, 2 * cw))
+        if not (cells.is_cuda and cells.dtype == torch.int16 and tuple(cells.shape) == (ch, cw, 2) and cells.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: cells must be a contiguous int16 CUDA tensor of shape (%d, %d, 2)"
+                                  % (what, ch, cw))
+        if out is not None and not (out.is_cuda and out.dtype == torch.int16 and tuple(out.shape) == (ch, cw, 2)
+                                    and out.stride(2) == 1 and out.stride(1) == 2 and out.stride(0) >= 2 * cw
+                                    and out.stride(0) % 2 == 0 and out.data_ptr() % 4 == 0):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be an int16 CUDA tensor of shape (%d, %d, 2) with packed cells "
+                                  "and rows a whole number of cells apart" % (what, ch, cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 4" % what)
+        win = _window(window)
+        self._behind_torch(i1, i2, cells, out, stats)
+        _capi.check(self._lib.bbme_cells_subpel_device(
+            self._ctx, C.c_void_p(i1.data_ptr()), C.c_void_p(i2.data_ptr()), C.c_void_p(cells.data_ptr()), win,
+            C.c_void_p(out.data_ptr() if out is not None else 0), out.stride(0) // 2 if out is not None else 0,
+            C.c_void_p(stats.data_ptr() if stats is not None else 0), C.c_void_p(stream or 0)))
+        return out, stats
+
     # -- colour coding of the field: Flow::MotionToColor on the GPU, from the cells (the colour rule of include/bbme.h) ----------
     def color_shape(self, scale=None):
         """(rows, cols, 3) of the colour image: the subsampled field's size; scale defaults to upsample."""
@@ -953,6 +1022,18 @@ class MFBatch(MF):
         """MF.get_backward_cells of one pair."""
         return self._get_backward_cells(pair, out, "get_pair_backward_cells")
 
+    def get_pair_subpel_cells(self, pair, which="forward", out=None):
+        """Pair `pair`'s cells refined to quarter-pel -> (CH, CW, 2) int16 (MF.subpel_cells)."""
+        return self._subpel_cells(pair, which, out, "get_pair_subpel_cells")
+
+    def get_pair_subpel_flow(self, pair, which="forward", out=None):
+        """Pair `pair`'s refined field of the unpadded source frame -> (H, W, 2) float32 (MF.subpel_flow)."""
+        return self._subpel_flow(pair, which, out, "get_pair_subpel_flow")
+
+    def subpel_stats_all(self, which="forward", window=None):
+        """MF.subpel_stats of every pair, from one launch -> list of dicts."""
+        return self._subpel_stats(which, window)
+
     def consistency_stats_all(self, which="forward", tol=1, window=None):
         """MF.consistency_stats of every pair, in order, from one launch."""
         return self._consistency_stats(which, tol, window)
@@ -1138,6 +1219,26 @@ def _which(which):
     if which in ("backward", 1, True):
         return 1
     raise _capi.BbmeError(_capi.ERR_INVALID, "which must be 'forward' or 'backward', not %r" % (which,))
+
+
+_SUBPEL_STATS = ("valid", "moved", "cost_integer", "cost_refined")
+
+
+def subpel_cells(image1, image2, cells, window=None):
+    """The subpel rule of include/bbme.h on the CPU (bbme_subpel_host): image1, image2 uint8 (H, W) planes (both even), cells an
+    int16 (H / 2, W / 2, 2) grid of integer vectors on image1 into image2 -> (quarter-pel grid (H / 2, W / 2, 2) int16,
+    dict(valid, moved, cost_integer, cost_refined) over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    image1 = np.ascontiguousarray(image1, np.uint8)
+    image2 = np.ascontiguousarray(image2, np.uint8)
+    cells = np.ascontiguousarray(cells, np.int16)
+    if image1.ndim != 2 or image1.shape != image2.shape or cells.shape != (image1.shape[0] // 2, image1.shape[1] // 2, 2):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "subpel_cells: two uint8 planes of one shape (H, W) and an int16 grid (H / 2, W / 2, 2)")
+    h, w = image1.shape
+    out = np.empty(cells.shape, np.int16)
+    s = (C.c_ulonglong * 4)()
+    _capi.check(_capi.lib().bbme_subpel_host(image1.ctypes.data, image2.ctypes.data, w, h, cells.ctypes.data, _window(window),
+                                             out.ctypes.data, s))
+    return out, dict(zip(_SUBPEL_STATS, list(s)))
 
 
 def cells_consistency(a, b, tol=1, window=None):

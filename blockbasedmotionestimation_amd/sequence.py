@@ -254,12 +254,14 @@ def shard_frames(n_frames, rank, world_size):
     return (first, first + count) if count else None
 
 
-def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_flight=4, batch=2, upsample=1):
+def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_flight=4, batch=2, upsample=1, subpel=False):
     """The len(frames) - 1 consecutive pairs of a video on ONE GPU: the unpadded (H, W, 2) float32 fields in order, the same
     as estimate_pairs_pipelined(list(zip(frames, frames[1:])), ...), but on chain contexts (MFChain) that follow
     plan_frame_segments: in_flight // batch contexts, each walking a contiguous segment of the video; a context's first round
     sets count + 1 frames, every later round rolls its last frame to slot 0 and sets `count`.  A short last round is padded by
-    repeating its last frame (the padded pairs are not read).  upsample=4: original frames, fields of the up-sampled size."""
+    repeating its last frame (the padded pairs are not read).  upsample=4: original frames, fields of the up-sampled size.
+    subpel=True: instead of the fields, every pair's cells refined to quarter-pel on its level-0 planes (MF.subpel_cells), the
+    padded (CH, CW, 2) int16 grids in quarter pixels (of the up-sampled frame with upsample=4)."""
     from .motion_framework import MFChain
     frames = list(frames)
     n_pairs = len(frames) - 1
@@ -281,6 +283,9 @@ def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_f
         mf = chains[slot]
         h, w = mf.orig_height, mf.orig_width
         for p in range(count):
+            if subpel:
+                out[first + p] = mf.get_pair_subpel_cells(p)       # waits for this context's stream only
+                continue
             flow = mf.get_pair_flow(p)                     # waits for this context's stream only
             out[first + p] = np.ascontiguousarray(flow[mf.padding_y:mf.padding_y + h, mf.padding_x:mf.padding_x + w])
 

@@ -712,6 +712,66 @@ int bbme_temporal_filter_bgr_chain_device(bbme_ctx *ctx, int first, int count, i
 int bbme_get_temporal_filtered_bgr_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
 int bbme_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 
+/* SUBPEL RULE (this project's own; the reference gets sub-pixel vectors only by estimating frames it has enlarged x4,
+ * main_class.cpp:19-21, 32-33, 58-70): quarter-pel refinement of a cell grid at the planes' own resolution.  Inputs: two packed planes
+ * I1 and I2 of W0 x H0 bytes (level-0 padded geometry) and a grid G of CH x CW int16 (dx, dy) integer vectors on I1 pointing into
+ * I2, CH = H0 / 2, CW = W0 / 2.  All arithmetic is in 32-bit integers; >> of a negative number is the arithmetic shift.
+ * Sample.  For an integer pixel position p and a quarter-pel offset q = (qx, qy): i = (qx >> 2, qy >> 2), f = (qx & 3, qy & 3),
+ * P00, P10, P01, P11 the pixels of I2 at p + i + (0, 0), (1, 0), (0, 1), (1, 1), and
+ *   sample(p, q) = ((4 - fx) (4 - fy) P00 + fx (4 - fy) P10 + (4 - fx) fy P01 + fx fy P11 + 8) >> 4.
+ * It is exactly separable -- the horizontal sum (4 - fx) P0 + fx P1 (<= 1020) of both rows first, then the vertical one with the
+ * single rounding -- and fits 16 bits throughout.
+ * Cell.  For output cell (cx, cy) with origin o = (2 cx, 2 cy) and v = G[cy][cx]: the window anchor is a = o - (3, 3) (an 8 x 8
+ * window around the cell) and b = a + v.  The cell is VALID when 0 <= a.x, a.x + 8 <= W0, 0 <= a.y, a.y + 8 <= H0, 2 <= b.x,
+ * b.x + 10 <= W0, 2 <= b.y and b.y + 10 <= H0: every sample of every candidate then lies in the plane, with one spare pixel.
+ *   cost(q) = sum over 0 <= i, j < 8 of |I1[a + (j, i)] - sample(b + (j, i), q)|,   0..16320.
+ * Search.  Start with q = (0, 0) and best = cost(q).  Then for s = 2 and afterwards for s = 1: let c be the q at the start of the
+ * stage; visit d in the order (-1,-1), (0,-1), (1,-1), (-1,0), (1,0), (-1,1), (0,1), (1,1); if cost(c + s d) < best (strictly),
+ * best becomes that cost and q becomes c + s d.  That is 17 costs per valid cell and q in [-3, 3]^2.  An invalid cell keeps
+ * q = (0, 0).  (Why this shape: on the Venus pair of tests/test_subpel_cpu.py a parabola through the integer SADs, a 4 x 4 or a
+ * 16 x 16 window and a leading +-1-pel stage all end further from the ground truth; README.md has the table.)
+ * Outputs.  The quarter-pel grid, one int16 pair per cell: sat16(4 v + q), saturation to -32768..32767 being possible on invalid
+ * cells only (a valid cell has |v| < max(W0, H0)); hence BBME_ERR_UNSUPPORTED for a geometry with W0 or H0 > 8188.  The statistics
+ * over a window {cx0, cy0, cw, ch} IN CELLS (NULL = all cells) are four exact 64-bit integers: valid cells, cells with
+ * q != (0, 0), the sum of cost(0, 0) over the valid cells and the sum of best over the valid cells.  The statistics do not need
+ * the grid to be written.
+ * A context made for up-sampled frames (bbme_set_frames_*_x4) refines its 4x planes: the result is then 1/16 pel of the source.
+ * A colour context refines on its luma planes.  Nothing that takes a cell grid (compensation, interpolation, the temporal
+ * filters) reads quarter-pel vectors: their rules are integer.
+ * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, q4_pitch_cells < CW, a
+ * window as for the consistency rule, a d_q4 of bbme_cells_subpel_device that overlaps its input grid, an odd width or height on
+ * the host call; BBME_ERR_UNSUPPORTED beyond 8188; BBME_ERR_STATE when frames are unset or a chain slot is unset, for which = 0
+ * before level 0 has reached 2x2 blocks (as bbme_subsampled_flow_device) and for which = 1 without a valid pair of fields (as
+ * bbme_backward_cells_device_pair).  None of these calls changes context state (grids, memo, flow, cells, backward cells, captured
+ * graphs, colour store); their scratch buffers are the context's own and independent of the other getters'.  Outputs must not
+ * overlap inputs.  All work on single, batched and chain contexts.
+ * bbme_subpel_host: the rule on the CPU, no GPU, on packed width x height planes (both even) and a packed
+ * (height / 2) x (width / 2) grid; out_q4 (packed) and stats4 each may be NULL, not both.
+ * bbme_cells_subpel_device: ANY two packed planes and ANY grid in HBM of the context's level-0 / cell geometry (another
+ * context's, or a caller's copies); no frames set and no estimate needed; d_q4 (rows q4_pitch_cells int16 pairs apart) and
+ * d_stats4 each may be null, not both; on hip_stream (NULL = the ctx stream; another stream is first ordered behind it); no host
+ * wait.  Launches with d_stats4 share one scratch buffer per context: the caller orders those it issues on different streams.
+ * bbme_subpel_device: the context's own: which = 0 refines the current level-0 cells of `pair` against (image 1, image 2) -- after
+ * bbme_estimate or bbme_estimate_bidirectional; in direction BACKWARD the planes exchange as for every plane-reading call --,
+ * which = 1 the backward cells kept by bbme_estimate_bidirectional against (image 2, image 1).  On a chain context the planes
+ * are slots pair and pair + 1.
+ * bbme_get_subpel_cells_host: the same; synchronises; packed CH x CW int16 pairs.
+ * bbme_subpel_stats: EVERY pair of the context from ONE launch, stats[4 p + k]; synchronises (like bbme_consistency_stats).
+ * bbme_get_subpel_flow_host: the float32 (u, v) field of `pair` on the unpadded frame, packed rows: pixel (x, y) takes the
+ * quarter-pel vector of cell ((pad_y + y) >> 1, (pad_x + x) >> 1) -- the cell bbme_get_subsampled_flow_host samples -- divided by 4
+ * (exact in float), W x H pixels.  On a context whose frames were last set to be up-sampled (bbme_set_frames_*_x4, scale 4 of
+ * bbme_set_chain_frames_*) it is the driver's subsampling in sixteenths: the (W / 4) x (H / 4) field of the source frame, pixel
+ * (x, y) from cell ((pad_y + 4 y) >> 1, (pad_x + 4 x) >> 1), divided by 16.
+ * Refined and expanded on the GPU; synchronises.  Ready for bbme_flo_write and bbme_calculate_mse. */
+int bbme_subpel_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *cells, const int *window,
+                     int16_t *out_q4, unsigned long long *stats4);
+int bbme_cells_subpel_device(bbme_ctx *ctx, const uint8_t *d_image1, const uint8_t *d_image2, const int16_t *d_cells,
+                             const int *window, int16_t *d_q4, int q4_pitch_cells, unsigned long long *d_stats4, void *hip_stream);
+int bbme_subpel_device(bbme_ctx *ctx, int pair, int which, int16_t *d_q4, int q4_pitch_cells, void *hip_stream);
+int bbme_get_subpel_cells_host(bbme_ctx *ctx, int pair, int which, int16_t *q4);
+int bbme_subpel_stats(bbme_ctx *ctx, int which, const int *window, unsigned long long *stats);
+int bbme_get_subpel_flow_host(bbme_ctx *ctx, int pair, int which, float *flow);
+
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
 /* copyMVs (:828-843) + calcLevelBM (:226-244) of one level.  Leaves that level's MV
