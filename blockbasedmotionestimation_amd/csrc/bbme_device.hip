@@ -303,34 +303,36 @@ struct bbme_ctx {
     hipEvent_t ev_sub = nullptr;                  // stream_behind_ctx: orders a caller's stream behind the ctx stream
     // scratch of single entry points, allocated on their first use (DevBuf::ensure)
     DevBuf<double> epe_scratch;                   // partial sums + counts of bbme_calculate_mse_device
-    DevBuf<uint8_t> fb_mask;                      // bbme_get_consistency_host: a packed CH x CW mask before its download
+    // STAGING AREA of the host getters (bbme_get_*_host): the packed product before its download (download_staged).  Every host
+    // getter waits for the context's stream before it returns, so the area is free on entry: one area serves them all, and it
+    // only grows (on the context's device) -- to the largest product asked for so far.
+    DevBuf<uint8_t> staging;
+    template <class T>
+    int staged(size_t n, const char *what, T **p)      // room for n elements of T, at least
+    {
+        if (n * sizeof(T) > staging.size()) {
+            HIP_TRY(hipSetDevice(device));
+            if (int rc = staging.ensure(n * sizeof(T), what)) return rc;
+        }
+        *p = reinterpret_cast<T *>(staging.get());
+        return BBME_OK;
+    }
     StatsScratch fb_stats;                        // bbme_consistency_stats (every pair) and bbme_cells_consistency_device (one pair)
     DevBuf<uint8_t> raw;                          // the host setters' upload buffer: one unpadded grey frame per slot
-    DevBuf<float> sub;                            // bbme_get_subsampled_flow_host: the packed field before its download (grown to
-                                                  // the largest asked for)
-    DevBuf<uint8_t> mc_plane;                     // bbme_get_motion_compensated_host: a level-0-sized plane before its download
     StatsScratch mc_stats;                        // bbme_compensation_error (every pair)
-    DevBuf<uint8_t> ip_plane;                     // bbme_get_interpolated_host: a packed W0 x H0 frame before its download
     StatsScratch ip_stats;                        // bbme_interpolation_stats (every pair) and bbme_cells_interpolate_device (one pair,
                                                   // every phase): grows with the phases
     DevBuf<uint32_t> color_range;                 // colour coding: the key words of every slot (pair 0 .. batch - 1, then the slot of
                                                   // bbme_cells_color_device; k_color_range), then five floats per slot
-    DevBuf<uint8_t> color_img;                    // bbme_get_flow_color_host: the packed B,G,R image before its download (grown to
-                                                  // the largest asked for)
     // COLOUR STORE (include/bbme.h): one packed B,G,R frame (pitch 3 width) per slot, bgr_stride bytes apart, allocated by the
     // first *_bgr setter.  bgr_set[slot]: the slot's colour is what its luma plane was made from (cleared by every grey setter
     // of that frame).
     DevBuf<uint8_t> bgr;
     size_t bgr_stride = 0;
     std::vector<uint8_t> bgr_set;
-    DevBuf<uint8_t> ip_bgr;                       // bbme_get_interpolated_bgr_host: a packed 3 W x H frame before its download
-    DevBuf<uint8_t> tf_plane;                     // bbme_get_temporal_filtered_host: a packed W0 x H0 frame before its download
     StatsScratch tf_stats;                        // bbme_temporal_filter_stats (every frame) and bbme_cells_temporal_filter_device (one)
-    DevBuf<uint8_t> tf_bgr;                       // bbme_get_temporal_filtered_bgr_host: a packed 3 W x H frame before its download
     StatsScratch tf_bgr_stats;                    // the same of bbme_temporal_filter_bgr_stats and bbme_cells_temporal_filter_bgr_device
     int src_scale = 1;                            // 4 after a setter of frames to up-sample (bbme_set_frames_*_x4, scale 4 of a chain), else 1
-    DevBuf<mv_t> sp_cells;                        // bbme_get_subpel_cells_host / _flow_host: a packed CH x CW quarter-pel grid
-    DevBuf<float> sp_flow;                        // bbme_get_subpel_flow_host: the packed field before its download
     StatsScratch sp_stats;                        // bbme_subpel_stats (every pair) and bbme_cells_subpel_device (one pair)
 };
 
@@ -1784,24 +1786,6 @@ int bbme_subsampled_flow_device(bbme_ctx *c, int pair, int scale, float *d_out, 
     return enqueue_subsample(c, pair, scale, d_out, out_pitch_pixels, hip_stream, "bbme_subsampled_flow_device");
 }
 
-int bbme_get_subsampled_flow_host(bbme_ctx *c, int pair, int scale, float *out)
-{
-    if (int rc = check_pair(c, pair)) return rc;
-    if (!out || scale < 1) return bbme::fail(BBME_ERR_INVALID, "bbme_get_subsampled_flow_host: null output or scale %d < 1", scale);
-    if (c->lv[0].cur_block != 2)
-        return bbme::fail(BBME_ERR_STATE, "bbme_get_subsampled_flow_host: level 0 has not been regularised down to 2x2 blocks");
-    const int ow = (c->geom.width + scale - 1) / scale, oh = (c->geom.height + scale - 1) / scale;
-    const size_t floats = (size_t)ow * oh * 2, bytes = floats * sizeof(float);
-    if (floats > c->sub.size()) {
-        HIP_TRY(hipSetDevice(c->device));
-        HIP_TRY(hipStreamSynchronize(c->stream));     // the old buffer may still be being read
-        if (int rc = c->sub.ensure(floats, "the subsampled field")) return rc;
-    }
-    if (int rc = enqueue_subsample(c, pair, scale, c->sub, ow, nullptr, "bbme_get_subsampled_flow_host")) return rc;
-    HIP_TRY(hipMemcpyAsync(out, c->sub, bytes, hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
-}
-
 }  // extern "C": the stages from here on share templates, which need C++ linkage; their entry points have C linkage from bbme.h
 
 // ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter) ----
@@ -1879,14 +1863,30 @@ static void own_fields(const bbme_ctx *c, int pair, const mv_t **f, const mv_t *
     *b = c->bwd_cells + (size_t)pair * c->bwd_stride;
 }
 
-// What the host getters share: `bytes` of `staging`, filled by enqueue(staging) on the context's stream, copied down; waits.
-template <class Enqueue>
-static int download_staged(bbme_ctx *c, DevBuf<uint8_t> &staging, size_t bytes, const char *staging_what, uint8_t *out, Enqueue enqueue)
+// One more device-to-host copy that rides on a host getter's wait (bbme_get_flow_color_host: the five range floats)
+struct ExtraCopy { void *dst = nullptr; const void *src = nullptr; size_t bytes = 0; };
+
+// What the host getters share: n elements of T in the context's staging area, filled by enqueue(T *, scratch) on the context's
+// stream and copied down to `out`; waits.  `scratch` is a second region of scratch_bytes at a 256-byte-aligned offset behind
+// them, for a product made in two steps.  n = 0: nothing is staged or copied and enqueue gets null.
+template <class T, class Enqueue>
+static int download_staged_with_scratch(bbme_ctx *c, size_t n, const char *what, T *out, size_t scratch_bytes, Enqueue enqueue,
+                                        ExtraCopy extra = {})
 {
-    if (int rc = staging.ensure(bytes, staging_what)) return rc;
-    if (int rc = enqueue(staging.get())) return rc;
-    HIP_TRY(hipMemcpyAsync(out, staging, bytes, hipMemcpyDeviceToHost, c->stream));
+    const size_t bytes = n * sizeof(T), scratch_at = (bytes + 255) / 256 * 256;
+    uint8_t *area;
+    if (int rc = c->staged(scratch_bytes ? scratch_at + scratch_bytes : bytes, what, &area)) return rc;
+    T *d = n ? reinterpret_cast<T *>(area) : nullptr;
+    if (int rc = enqueue(d, area + scratch_at)) return rc;
+    if (n) HIP_TRY(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, c->stream));
+    if (extra.bytes) HIP_TRY(hipMemcpyAsync(extra.dst, extra.src, extra.bytes, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
+}
+
+template <class T, class Enqueue>
+static int download_staged(bbme_ctx *c, size_t n, const char *what, T *out, Enqueue enqueue, ExtraCopy extra = {})
+{
+    return download_staged_with_scratch(c, n, what, out, 0, [&](T *d, uint8_t *) { return enqueue(d); }, extra);
 }
 
 // What the statistics calls share: enqueue() on the context's stream, the first n result quadruples of `s` copied down; waits.
@@ -1896,6 +1896,18 @@ static int download_stats(bbme_ctx *c, const StatsScratch &s, int n, unsigned lo
     if (int rc = enqueue()) return rc;
     HIP_TRY(hipMemcpyAsync(stats, s.results(), (size_t)4 * sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
     return check_converged(c);
+}
+
+int bbme_get_subsampled_flow_host(bbme_ctx *c, int pair, int scale, float *out)
+{
+    const char *what = "bbme_get_subsampled_flow_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!out || scale < 1) return bbme::fail(BBME_ERR_INVALID, "%s: null output or scale %d < 1", what, scale);
+    if (c->lv[0].cur_block != 2) return bbme::fail(BBME_ERR_STATE, "%s: level 0 has not been regularised down to 2x2 blocks", what);
+    const int ow = (c->geom.width + scale - 1) / scale, oh = (c->geom.height + scale - 1) / scale;
+    return download_staged(c, (size_t)ow * oh * 2, "the subsampled field", out, [&](float *d) {
+        return enqueue_subsample(c, pair, scale, d, ow, nullptr, what);
+    });
 }
 
 // ---- motion compensation: MF::draw_MVimage (motion_framework.cpp:887-905) and its residual statistics ---------------------
@@ -1969,8 +1981,7 @@ int bbme_get_motion_compensated_host(bbme_ctx *c, int pair, int level, int block
     if (int rc = check_mc_state(c, level, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const Level &L = c->lv[level];
-    if (int rc = c->mc_plane.ensure((size_t)c->lv[0].width * c->lv[0].height, "the compensated plane")) return rc;   // level 0 is the largest
-    return download_staged(c, c->mc_plane, (size_t)L.width * L.height, "the compensated plane", out, [&](uint8_t *d) {
+    return download_staged(c, (size_t)L.width * L.height, "the compensated plane", out, [&](uint8_t *d) {
         return enqueue_mc(c, pair, 1, level, block, fill, nullptr, d, L.width, nullptr, c->stream);
     });
 }
@@ -2075,7 +2086,7 @@ int bbme_get_consistency_host(bbme_ctx *c, int pair, int which, int tol, uint8_t
     const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
     const mv_t *f, *b;
     own_fields(c, pair, &f, &b);
-    return download_staged(c, c->fb_mask, (size_t)cw * ch, "the consistency mask", mask, [&](uint8_t *d) {
+    return download_staged(c, (size_t)cw * ch, "the consistency mask", mask, [&](uint8_t *d) {
         return enqueue_fb(c, which ? b : f, 0, which ? f : b, 0, 1, tol, nullptr, d, cw, nullptr, nullptr, c->stream);
     });
 }
@@ -2221,18 +2232,10 @@ int bbme_get_flow_color_host(bbme_ctx *c, int pair, int which, int scale, float 
     if (int rc = color_source(c, which, what, &cells, &stride)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     if (int rc = color_scratch(c)) return rc;
-    const size_t bytes = (size_t)ow * oh * 3;
-    if (bgr && bytes > c->color_img.size()) {
-        HIP_TRY(hipStreamSynchronize(c->stream));     // the old buffer may still be being read
-        if (int rc = c->color_img.ensure(bytes, "the colour image")) return rc;
-    }
-    if (int rc = enqueue_color(c, cells + (size_t)pair * stride, 0, 1, pair, scale, maxmotion, bgr ? c->color_img.get() : nullptr, 3 * ow,
-                               range5 != nullptr, nullptr, c->stream)) return rc;
-    if (bgr) HIP_TRY(hipMemcpyAsync(bgr, c->color_img, bytes, hipMemcpyDeviceToHost, c->stream));
-    if (range5)
-        HIP_TRY(hipMemcpyAsync(range5, color_floats(c) + 5 * pair, 5 * sizeof(float),
-                               hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    return download_staged(c, bgr ? (size_t)ow * oh * 3 : 0, "the colour image", bgr, [&](uint8_t *d) {
+        return enqueue_color(c, cells + (size_t)pair * stride, 0, 1, pair, scale, maxmotion, d, 3 * ow, range5 != nullptr, nullptr,
+                             c->stream);
+    }, ExtraCopy{range5, color_floats(c) + 5 * pair, range5 ? 5 * sizeof(float) : 0});
 }
 
 int bbme_flow_ranges(bbme_ctx *c, int which, int scale, float *ranges)
@@ -2375,7 +2378,7 @@ int bbme_get_interpolated_host(bbme_ctx *c, int pair, int num, int den, uint8_t 
     if (int rc = check_fields_state(c, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     const Level &L = c->lv[0];
-    return download_staged(c, c->ip_plane, (size_t)L.width * L.height, "the interpolated frame", out, [&](uint8_t *d) {
+    return download_staged(c, (size_t)L.width * L.height, "the interpolated frame", out, [&](uint8_t *d) {
         return enqueue_own_ip(c, pair, num, 1, den, d, L.width, 0, c->stream);
     });
 }
@@ -2505,7 +2508,7 @@ int bbme_get_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int den, uint
     const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
     if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    return download_staged(c, c->ip_bgr, (size_t)3 * c->geom.width * c->geom.height, "the interpolated colour frame", out, [&](uint8_t *d) {
+    return download_staged(c, (size_t)3 * c->geom.width * c->geom.height, "the interpolated colour frame", out, [&](uint8_t *d) {
         return enqueue_own_ip_bgr(c, pair, num, 1, den, d, 3 * c->geom.width, 0, c->stream, what);
     });
 }
@@ -2534,9 +2537,9 @@ static int check_tf_bgr_frame_colour(const bbme_ctx *c, int pair, int which, con
     return BBME_OK;
 }
 
-// A flavour names the argument type and kernel, the size of a frame (`rows` rows of row_bytes), the staging buffer and the
-// statistics scratch, what the arguments hold beyond TfArgs, and the context's own frames: their base, s_pair bytes from pair to
-// pair and s_frame from a frame to its next neighbour.  What only colour checks hangs on `bgr` in the bodies below.
+// A flavour names the argument type and kernel, the size of a frame (`rows` rows of row_bytes), the statistics scratch, what the
+// arguments hold beyond TfArgs, and the context's own frames: their base, s_pair bytes from pair to pair and s_frame from a frame
+// to its next neighbour.  What only colour checks hangs on `bgr` in the bodies below.
 struct TfGrey {
     using Args = TfArgs;
     static constexpr bool bgr = false;
@@ -2544,7 +2547,6 @@ struct TfGrey {
     static auto kernel() { return k_temporal_filter; }
     static int row_bytes(const bbme_ctx *c) { return c->lv[0].width; }
     static int rows(const bbme_ctx *c) { return c->lv[0].height; }
-    static DevBuf<uint8_t> &staging(bbme_ctx *c) { return c->tf_plane; }
     static StatsScratch &stats(bbme_ctx *c) { return c->tf_stats; }
     static void geometry(const bbme_ctx *, TfArgs &) {}
     static const uint8_t *own(const bbme_ctx *c, long long *s_pair, long long *s_frame)
@@ -2564,7 +2566,6 @@ struct TfBgr {
     static auto kernel() { return k_temporal_filter_bgr; }
     static int row_bytes(const bbme_ctx *c) { return 3 * c->geom.width; }
     static int rows(const bbme_ctx *c) { return c->geom.height; }
-    static DevBuf<uint8_t> &staging(bbme_ctx *c) { return c->tf_bgr; }
     static StatsScratch &stats(bbme_ctx *c) { return c->tf_bgr_stats; }
     static void geometry(const bbme_ctx *c, TfBgrArgs &a)      // the frame inside the padded view
     {
@@ -2765,7 +2766,7 @@ static int tf_host(bbme_ctx *c, const char *what, int pair, int which, int thr, 
 {
     if (int rc = check_tf_frame<F>(c, pair, which, thr, out, nullptr, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    return download_staged(c, F::staging(c), (size_t)F::row_bytes(c) * F::rows(c), F::staging_what, out, [&](uint8_t *d) {
+    return download_staged(c, (size_t)F::row_bytes(c) * F::rows(c), F::staging_what, out, [&](uint8_t *d) {
         return enqueue_own_tf<F>(c, pair, which, thr, d, F::row_bytes(c), c->stream);
     });
 }
@@ -2954,14 +2955,6 @@ int bbme_subpel_device(bbme_ctx *c, int pair, int which, int16_t *d_q4, int q4_p
     return enqueue_own_sp(c, pair, which, reinterpret_cast<mv_t *>(d_q4), q4_pitch_cells, stream, what);
 }
 
-// the refined grid of (pair, which) in c->sp_cells, packed, on the context's stream
-static int own_sp_staged(bbme_ctx *c, int pair, int which, const char *what)
-{
-    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
-    if (int rc = c->sp_cells.ensure((size_t)cw * ch, "the quarter-pel cells")) return rc;
-    return enqueue_own_sp(c, pair, which, c->sp_cells, cw, c->stream, what);
-}
-
 static int check_sp_get(const bbme_ctx *c, int pair, int which, const void *out, const char *what)
 {
     if (int rc = check_pair(c, pair)) return rc;
@@ -2975,10 +2968,10 @@ int bbme_get_subpel_cells_host(bbme_ctx *c, int pair, int which, int16_t *q4)
     const char *what = "bbme_get_subpel_cells_host";
     if (int rc = check_sp_get(c, pair, which, q4, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = own_sp_staged(c, pair, which, what)) return rc;
-    const size_t n = (size_t)(c->lv[0].width / 2) * (c->lv[0].height / 2);
-    HIP_TRY(hipMemcpyAsync(q4, c->sp_cells, n * sizeof(mv_t), hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
+    return download_staged(c, (size_t)cw * ch, "the quarter-pel cells", reinterpret_cast<mv_t *>(q4), [&](mv_t *d) {
+        return enqueue_own_sp(c, pair, which, d, cw, c->stream, what);
+    });
 }
 
 int bbme_subpel_stats(bbme_ctx *c, int which, const int *window, unsigned long long *stats)
@@ -3005,15 +2998,18 @@ int bbme_get_subpel_flow_host(bbme_ctx *c, int pair, int which, float *flow)
     const char *what = "bbme_get_subpel_flow_host";
     if (int rc = check_sp_get(c, pair, which, flow, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
-    if (int rc = own_sp_staged(c, pair, which, what)) return rc;
+    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
     const int scale = c->src_scale, ow = (c->geom.width + scale - 1) / scale, oh = (c->geom.height + scale - 1) / scale;
-    const size_t floats = (size_t)ow * oh * 2;
-    if (int rc = c->sp_flow.ensure(floats, "the quarter-pel field")) return rc;
-    hipLaunchKernelGGL(k_subsample_q4, dim3((unsigned)(((long long)ow * oh + 255) / 256)), dim3(256), 0, c->stream, c->sp_cells.get(),
-                       c->lv[0].width / 2, c->geom.pad_x, c->geom.pad_y, scale, c->sp_flow.get(), ow, oh);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(flow, c->sp_flow, floats * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-    return check_converged(c);
+    // the field in the area's first region, the packed quarter-pel cells it is expanded from in the second
+    return download_staged_with_scratch(c, (size_t)ow * oh * 2, "the quarter-pel field", flow, (size_t)cw * ch * sizeof(mv_t),
+                                        [&](float *d, uint8_t *scratch) {
+        mv_t *q4 = reinterpret_cast<mv_t *>(scratch);
+        if (int rc = enqueue_own_sp(c, pair, which, q4, cw, c->stream, what)) return rc;
+        hipLaunchKernelGGL(k_subsample_q4, dim3((unsigned)(((long long)ow * oh + 255) / 256)), dim3(256), 0, c->stream, q4, cw,
+                           c->geom.pad_x, c->geom.pad_y, scale, d, ow, oh);
+        HIP_TRY(hipGetLastError());
+        return (int)BBME_OK;
+    });
 }
 
 extern "C" {

@@ -513,13 +513,29 @@ void subsample_div4(const float *flow_padded, int padded_width, int padded_heigh
         }
 }
 
+// The window of a rule's statistics: {x0, y0, w, h} inside limit_w x limit_h cells (or pixels of a plane), null = all of them.
+struct CellWindow {
+    int x0 = 0, y0 = 0, x1 = 0, y1 = 0;
+    // BBME_OK, or BBME_ERR_INVALID "<what>: window not inside the <limit_w>x<limit_h> <unit>"
+    int set(const int *window, int limit_w, int limit_h, const char *what, const char *unit)
+    {
+        if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
+                       (long long)window[0] + window[2] > limit_w || (long long)window[1] + window[3] > limit_h))
+            return fail(BBME_ERR_INVALID, "%s: window not inside the %dx%d %s", what, limit_w, limit_h, unit);
+        x0 = window ? window[0] : 0;
+        y0 = window ? window[1] : 0;
+        x1 = window ? window[0] + window[2] : limit_w;
+        y1 = window ? window[1] + window[3] : limit_h;
+        return BBME_OK;
+    }
+    bool contains(int x, int y) const { return x >= x0 && x < x1 && y >= y0 && y < y1; }
+};
+
 // MF::draw_MVimage (motion_framework.cpp:887-905) as include/bbme.h states it, block by block, with the residual statistics
-void motion_compensate(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *grid, int grid_block,
-                       int block, int fill, const int window[4], uint8_t *out, unsigned long long stats[4])
+static void motion_compensate(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *grid, int grid_block,
+                              int block, int fill, const CellWindow &win, uint8_t *out, unsigned long long stats[4])
 {
     const int gcols = (width + grid_block - 1) / grid_block;
-    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
-    const int wx1 = window ? window[0] + window[2] : width, wy1 = window ? window[1] + window[3] : height;
     unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
     for (int Y = 0; Y < height; Y += block)
         for (int X = 0; X < width; X += block) {
@@ -530,7 +546,7 @@ void motion_compensate(const uint8_t *image1, const uint8_t *image2, int width, 
                 for (int j = 0; j < block && X + j < width; ++j) {
                     const int v = ok ? image2[(size_t)(sy + i) * width + sx + j] : fill;
                     if (out) out[(size_t)(Y + i) * width + X + j] = (uint8_t)v;
-                    if (!stats || Y + i < wy0 || Y + i >= wy1 || X + j < wx0 || X + j >= wx1) continue;
+                    if (!stats || !win.contains(X + j, Y + i)) continue;
                     if (!ok) { ++skipped; continue; }
                     const int d = v - image1[(size_t)(Y + i) * width + X + j];
                     sse += (unsigned long long)(d * d);
@@ -539,6 +555,83 @@ void motion_compensate(const uint8_t *image1, const uint8_t *image2, int width, 
                 }
         }
     if (stats) { stats[0] = sse; stats[1] = sad; stats[2] = pixels; stats[3] = skipped; }
+}
+
+// Hypothesis k of the interpolation rule at cell (cx, cy) of a grid cw cells wide, for the phase num / den: its vector v (0: the
+// forward one, 1: minus the backward one, 2: zero) and where its two 2x2 blocks start -- p1 = the cell's origin - round(num v /
+// den) in frame 1, p2 = p1 + v in frame 2.
+struct Hypothesis { int vx, vy, p1x, p1y, p2x, p2y; };
+static Hypothesis hypothesis(const int16_t *fwd, const int16_t *bwd, int cw, int cx, int cy, int k, int num, int den)
+{
+    const auto floor_div = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+    const size_t c = (size_t)cy * cw + cx;
+    Hypothesis h;
+    h.vx = k == 0 ? fwd[2 * c] : k == 1 ? -(int)bwd[2 * c] : 0;
+    h.vy = k == 0 ? fwd[2 * c + 1] : k == 1 ? -(int)bwd[2 * c + 1] : 0;
+    h.p1x = 2 * cx - floor_div(num * h.vx + den / 2, den);
+    h.p1y = 2 * cy - floor_div(num * h.vy + den / 2, den);
+    h.p2x = h.p1x + h.vx;
+    h.p2y = h.p1y + h.vy;
+    return h;
+}
+
+// The temporal filter rule of include/bbme.h, cell by cell of the padded view, in the header's own words (the mirror of
+// k_temporal_filter and k_temporal_filter_bgr), for frames of `chans` interleaved channels: the width x height frame sits at
+// (pad_x, pad_y) of the view and reads 0 outside itself; a neighbour's cost is the largest of its channels' 2x2 SADs.  A grey
+// plane is one channel without padding (the plane is the view); a B,G,R frame is three.
+static void temporal_filter(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int chans, int width, int height, int pad_x,
+                            int pad_y, const int16_t *to_prev, const int16_t *to_next, int thr, const CellWindow &win, uint8_t *out,
+                            uint8_t *weights, unsigned long long *stats4)
+{
+    const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y, cw = W0 / 2, ch = H0 / 2;
+    // channel k of the pixel at the view's position (X, Y): 0 outside the frame
+    const auto texel = [&](const uint8_t *img, int X, int Y, int k) {
+        const int x = X - pad_x, y = Y - pad_y;
+        return x < 0 || y < 0 || x >= width || y >= height ? 0 : (int)img[((size_t)y * width + x) * chans + k];
+    };
+    const uint8_t *frames[2] = {prev, next};
+    const int16_t *grids[2] = {to_prev, to_next};
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            int w[2] = {0, 0}, px[2] = {0, 0}, py[2] = {0, 0};
+            for (int k = 0; k < 2; ++k) {
+                if (!frames[k]) continue;
+                px[k] = ox + grids[k][2 * c];
+                py[k] = oy + grids[k][2 * c + 1];
+                if (px[k] < 0 || py[k] < 0 || px[k] > W0 - 2 || py[k] > H0 - 2) continue;
+                int cost = 0;
+                for (int chn = 0; chn < chans; ++chn) {
+                    int cc = 0;
+                    for (int i = 0; i < 2; ++i)
+                        for (int j = 0; j < 2; ++j)
+                            cc += abs(texel(cur, ox + j, oy + i, chn) - texel(frames[k], px[k] + j, py[k] + i, chn));
+                    if (cc > cost) cost = cc;
+                }
+                if (cost < thr) w[k] = 8 * (thr - cost) / thr;
+            }
+            const int S = 8 + w[0] + w[1];
+            unsigned diff = 0;
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j) {
+                    const int x = ox + j - pad_x, y = oy + i - pad_y;
+                    const bool inside = x >= 0 && y >= 0 && x < width && y < height;
+                    for (int chn = 0; chn < chans; ++chn) {
+                        const int cpx = texel(cur, ox + j, oy + i, chn);
+                        int acc = 8 * cpx + S / 2;
+                        for (int k = 0; k < 2; ++k)
+                            if (w[k]) acc += w[k] * texel(frames[k], px[k] + j, py[k] + i, chn);
+                        const int v = acc / S;
+                        if (out && inside) out[((size_t)y * width + x) * chans + chn] = (uint8_t)v;
+                        diff += (unsigned)abs(v - cpx);
+                    }
+                }
+            if (weights) weights[c] = (uint8_t)(w[0] | w[1] << 4);
+            if (win.contains(cx, cy)) { s[0] += w[0] > 0; s[1] += w[1] > 0; s[2] += (unsigned)(w[0] + w[1]); s[3] += diff; }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
 }
 
 }  // namespace bbme
@@ -641,10 +734,9 @@ int bbme_motion_compensate_host(const uint8_t *image1, const uint8_t *image2, in
     if (width < 1 || height < 1 || grid_block < 1 || block < 1 || (block & (block - 1)) || fill < 0 || fill > 255)
         return bbme::fail(BBME_ERR_INVALID, "bbme_motion_compensate_host: bad arguments (%dx%d, grid block %d, block %d, fill %d)",
                           width, height, grid_block, block, fill);
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > width || (long long)window[1] + window[3] > height))
-        return bbme::fail(BBME_ERR_INVALID, "bbme_motion_compensate_host: window not inside the %dx%d plane", width, height);
-    bbme::motion_compensate(image1, image2, width, height, grid, grid_block, block, fill, window, out, stats4);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, width, height, "bbme_motion_compensate_host", "plane")) return rc;
+    bbme::motion_compensate(image1, image2, width, height, grid, grid_block, block, fill, win, out, stats4);
     return BBME_OK;
 }
 
@@ -668,11 +760,8 @@ int bbme_cells_consistency_host(const int16_t *a, const int16_t *b, int cells_w,
     if (!a || !b || (!mask && !stats4)) return bbme::fail(BBME_ERR_INVALID, "bbme_cells_consistency_host: null pointer");
     if (cells_w < 1 || cells_h < 1 || tol < 0)
         return bbme::fail(BBME_ERR_INVALID, "bbme_cells_consistency_host: bad arguments (%dx%d cells, tolerance %d)", cells_w, cells_h, tol);
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > cells_w || (long long)window[1] + window[3] > cells_h))
-        return bbme::fail(BBME_ERR_INVALID, "bbme_cells_consistency_host: window not inside the %dx%d cells", cells_w, cells_h);
-    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
-    const int wx1 = window ? window[0] + window[2] : cells_w, wy1 = window ? window[1] + window[3] : cells_h;
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cells_w, cells_h, "bbme_cells_consistency_host", "cells")) return rc;
     unsigned long long s[4] = {0, 0, 0, 0};
     for (int cy = 0; cy < cells_h; ++cy)
         for (int cx = 0; cx < cells_w; ++cx) {
@@ -687,7 +776,7 @@ int bbme_cells_consistency_host(const int16_t *a, const int16_t *b, int cells_w,
                 cls = d <= (unsigned)tol ? BBME_FB_CONSISTENT : BBME_FB_INCONSISTENT;
             }
             if (mask) mask[i] = (uint8_t)cls;
-            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) { ++s[cls]; s[3] += d; }
+            if (win.contains(cx, cy)) { ++s[cls]; s[3] += d; }
         }
     if (stats4) memcpy(stats4, s, sizeof s);
     return BBME_OK;
@@ -705,30 +794,26 @@ int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int widt
     if (den < 2 || den > 256 || num < 1 || num >= den)
         return bbme::fail(BBME_ERR_INVALID, "bbme_interpolate_host: phase %d / %d (2 <= den <= 256, 0 < num < den)", num, den);
     const int cw = width / 2, ch = height / 2;
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
-        return bbme::fail(BBME_ERR_INVALID, "bbme_interpolate_host: window not inside the %dx%d cells", cw, ch);
-    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
-    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
-    const auto floor_div = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cw, ch, "bbme_interpolate_host", "cells")) return rc;
     unsigned long long s[4] = {0, 0, 0, 0};
     for (int cy = 0; cy < ch; ++cy)
         for (int cx = 0; cx < cw; ++cx) {
             const size_t c = (size_t)cy * cw + cx;
             const int ox = 2 * cx, oy = 2 * cy;
-            const int v[3][2] = {{fwd[2 * c], fwd[2 * c + 1]}, {bwd ? -(int)bwd[2 * c] : 0, bwd ? -(int)bwd[2 * c + 1] : 0}, {0, 0}};
             int best = -1, best_cost = 0, b1x = 0, b1y = 0, b2x = 0, b2y = 0;
             for (int k = 0; k < 3; ++k) {
                 if (k == 1 && !bwd) continue;
-                const int p1x = ox - floor_div(num * v[k][0] + den / 2, den), p1y = oy - floor_div(num * v[k][1] + den / 2, den);
-                const int p2x = p1x + v[k][0], p2y = p1y + v[k][1];
-                if (p1x < 0 || p2x < 0 || p1x > width - 2 || p2x > width - 2 || p1y < 0 || p2y < 0 || p1y > height - 2 || p2y > height - 2)
+                const bbme::Hypothesis h = bbme::hypothesis(fwd, bwd, cw, cx, cy, k, num, den);
+                if (h.p1x < 0 || h.p2x < 0 || h.p1x > width - 2 || h.p2x > width - 2 || h.p1y < 0 || h.p2y < 0 || h.p1y > height - 2 ||
+                    h.p2y > height - 2)
                     continue;
                 int cost = 0;
                 for (int i = 0; i < 2; ++i)
                     for (int j = 0; j < 2; ++j)
-                        cost += abs((int)image1[(size_t)(p1y + i) * width + p1x + j] - (int)image2[(size_t)(p2y + i) * width + p2x + j]);
-                if (best < 0 || cost < best_cost) { best = k; best_cost = cost; b1x = p1x; b1y = p1y; b2x = p2x; b2y = p2y; }
+                        cost += abs((int)image1[(size_t)(h.p1y + i) * width + h.p1x + j] -
+                                    (int)image2[(size_t)(h.p2y + i) * width + h.p2x + j]);
+                if (best < 0 || cost < best_cost) { best = k; best_cost = cost; b1x = h.p1x; b1y = h.p1y; b2x = h.p2x; b2y = h.p2y; }
             }
             if (out)
                 for (int i = 0; i < 2; ++i)
@@ -737,13 +822,13 @@ int bbme_interpolate_host(const uint8_t *image1, const uint8_t *image2, int widt
                             (uint8_t)(((den - num) * image1[(size_t)(b1y + i) * width + b1x + j] +
                                        num * image2[(size_t)(b2y + i) * width + b2x + j] + den / 2) / den);
             if (sel) sel[c] = (uint8_t)best;
-            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) { ++s[best]; s[3] += (unsigned)best_cost; }
+            if (win.contains(cx, cy)) { ++s[best]; s[3] += (unsigned)best_cost; }
         }
     if (stats4) memcpy(stats4, s, sizeof s);
     return BBME_OK;
 }
 
-// The temporal filter rule of include/bbme.h, cell by cell, in the header's own words (the mirror of k_temporal_filter).
+// The temporal filter rule on grey planes: bbme::temporal_filter with one channel, the plane being the padded view.
 int bbme_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height,
                               const int16_t *to_prev, const int16_t *to_next, int thr, const int *window, uint8_t *out,
                               uint8_t *weights, unsigned long long *stats4)
@@ -756,49 +841,9 @@ int bbme_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, const uin
     if (width < 2 || height < 2 || (width & 1) || (height & 1))
         return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
     if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
-    const int cw = width / 2, ch = height / 2;
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
-        return bbme::fail(BBME_ERR_INVALID, "%s: window not inside the %dx%d cells", what, cw, ch);
-    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
-    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
-    const uint8_t *planes[2] = {prev, next};
-    const int16_t *grids[2] = {to_prev, to_next};
-    unsigned long long s[4] = {0, 0, 0, 0};
-    for (int cy = 0; cy < ch; ++cy)
-        for (int cx = 0; cx < cw; ++cx) {
-            const size_t c = (size_t)cy * cw + cx;
-            const int ox = 2 * cx, oy = 2 * cy;
-            int w[2] = {0, 0}, px[2] = {0, 0}, py[2] = {0, 0};
-            for (int k = 0; k < 2; ++k) {
-                if (!planes[k]) continue;
-                px[k] = ox + grids[k][2 * c];
-                py[k] = oy + grids[k][2 * c + 1];
-                if (px[k] < 0 || py[k] < 0 || px[k] > width - 2 || py[k] > height - 2) continue;
-                int cost = 0;
-                for (int i = 0; i < 2; ++i)
-                    for (int j = 0; j < 2; ++j)
-                        cost += abs((int)cur[(size_t)(oy + i) * width + ox + j] - (int)planes[k][(size_t)(py[k] + i) * width + px[k] + j]);
-                if (cost < thr) w[k] = 8 * (thr - cost) / thr;
-            }
-            const int S = 8 + w[0] + w[1];
-            unsigned diff = 0;
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) {
-                    const int cpx = cur[(size_t)(oy + i) * width + ox + j];
-                    int acc = 8 * cpx + S / 2;
-                    for (int k = 0; k < 2; ++k)
-                        if (w[k]) acc += w[k] * planes[k][(size_t)(py[k] + i) * width + px[k] + j];
-                    const int v = acc / S;
-                    if (out) out[(size_t)(oy + i) * width + ox + j] = (uint8_t)v;
-                    diff += (unsigned)abs(v - cpx);
-                }
-            if (weights) weights[c] = (uint8_t)(w[0] | w[1] << 4);
-            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) {
-                s[0] += w[0] > 0; s[1] += w[1] > 0; s[2] += (unsigned)(w[0] + w[1]); s[3] += diff;
-            }
-        }
-    if (stats4) memcpy(stats4, s, sizeof s);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, width / 2, height / 2, what, "cells")) return rc;
+    bbme::temporal_filter(prev, cur, next, 1, width, height, 0, 0, to_prev, to_next, thr, win, out, weights, stats4);
     return BBME_OK;
 }
 
@@ -832,18 +877,14 @@ int bbme_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int pa
     std::vector<uint8_t> sel((size_t)cw * (padded_h / 2) + 1);
     if (int rc = bbme_interpolate_host(luma1, luma2, padded_w, padded_h, fwd, bwd, num, den, nullptr, nullptr, sel.data(), nullptr))
         return rc;                                            // odd planes and bad phases are refused there
-    const auto floor_div = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
     const auto texel = [&](const uint8_t *img, int x, int y, int c) {
         return x < 0 || y < 0 || x >= width || y >= height ? 0 : (int)img[((size_t)y * width + x) * 3 + c];
     };
     for (int y = 0; y < height; ++y)
         for (int x = 0; x < width; ++x) {
             const int X = x + pad_x, Y = y + pad_y, cx = X >> 1, cy = Y >> 1;
-            const size_t c = (size_t)cy * cw + cx;
-            const int k = sel[c];
-            const int vx = k == 0 ? fwd[2 * c] : k == 1 ? -(int)bwd[2 * c] : 0, vy = k == 0 ? fwd[2 * c + 1] : k == 1 ? -(int)bwd[2 * c + 1] : 0;
-            const int p1x = 2 * cx - floor_div(num * vx + den / 2, den), p1y = 2 * cy - floor_div(num * vy + den / 2, den);
-            const int q1x = p1x + (X & 1) - pad_x, q1y = p1y + (Y & 1) - pad_y, q2x = q1x + vx, q2y = q1y + vy;
+            const bbme::Hypothesis h = bbme::hypothesis(fwd, bwd, cw, cx, cy, sel[(size_t)cy * cw + cx], num, den);
+            const int q1x = h.p1x + (X & 1) - pad_x, q1y = h.p1y + (Y & 1) - pad_y, q2x = q1x + h.vx, q2y = q1y + h.vy;
             for (int ch = 0; ch < 3; ++ch)
                 out[((size_t)y * width + x) * 3 + ch] =
                     (uint8_t)(((den - num) * texel(bgr1, q1x, q1y, ch) + num * texel(bgr2, q2x, q2y, ch) + den / 2) / den);
@@ -851,8 +892,7 @@ int bbme_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int pa
     return BBME_OK;
 }
 
-// The BGR temporal filter rule of include/bbme.h, cell by cell of the padded view, in the header's own words (the mirror of
-// k_temporal_filter_bgr).
+// The BGR temporal filter rule: bbme::temporal_filter with three channels, the frame inside its padded view.
 int bbme_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height, int pad_x,
                                   int pad_y, const int16_t *to_prev, const int16_t *to_next, int thr, const int *window, uint8_t *out,
                                   uint8_t *weights, unsigned long long *stats4)
@@ -868,62 +908,9 @@ int bbme_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur, const
     const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y;
     if ((W0 & 1) || (H0 & 1)) return bbme::fail(BBME_ERR_INVALID, "%s: the padded view %dx%d is not a plane of 2x2 cells", what, W0, H0);
     if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
-    const int cw = W0 / 2, ch = H0 / 2;
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
-        return bbme::fail(BBME_ERR_INVALID, "%s: window not inside the %dx%d cells", what, cw, ch);
-    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
-    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
-    // channel k of the pixel at the padded position (X, Y): 0 outside the frame
-    const auto texel = [&](const uint8_t *img, int X, int Y, int k) {
-        const int x = X - pad_x, y = Y - pad_y;
-        return x < 0 || y < 0 || x >= width || y >= height ? 0 : (int)img[((size_t)y * width + x) * 3 + k];
-    };
-    const uint8_t *frames[2] = {prev, next};
-    const int16_t *grids[2] = {to_prev, to_next};
-    unsigned long long s[4] = {0, 0, 0, 0};
-    for (int cy = 0; cy < ch; ++cy)
-        for (int cx = 0; cx < cw; ++cx) {
-            const size_t c = (size_t)cy * cw + cx;
-            const int ox = 2 * cx, oy = 2 * cy;
-            int w[2] = {0, 0}, px[2] = {0, 0}, py[2] = {0, 0};
-            for (int k = 0; k < 2; ++k) {
-                if (!frames[k]) continue;
-                px[k] = ox + grids[k][2 * c];
-                py[k] = oy + grids[k][2 * c + 1];
-                if (px[k] < 0 || py[k] < 0 || px[k] > W0 - 2 || py[k] > H0 - 2) continue;
-                int cost = 0;
-                for (int chn = 0; chn < 3; ++chn) {
-                    int cc = 0;
-                    for (int i = 0; i < 2; ++i)
-                        for (int j = 0; j < 2; ++j)
-                            cc += abs(texel(cur, ox + j, oy + i, chn) - texel(frames[k], px[k] + j, py[k] + i, chn));
-                    if (cc > cost) cost = cc;
-                }
-                if (cost < thr) w[k] = 8 * (thr - cost) / thr;
-            }
-            const int S = 8 + w[0] + w[1];
-            unsigned diff = 0;
-            for (int i = 0; i < 2; ++i)
-                for (int j = 0; j < 2; ++j) {
-                    const int x = ox + j - pad_x, y = oy + i - pad_y;
-                    const bool inside = x >= 0 && y >= 0 && x < width && y < height;
-                    for (int chn = 0; chn < 3; ++chn) {
-                        const int cpx = texel(cur, ox + j, oy + i, chn);
-                        int acc = 8 * cpx + S / 2;
-                        for (int k = 0; k < 2; ++k)
-                            if (w[k]) acc += w[k] * texel(frames[k], px[k] + j, py[k] + i, chn);
-                        const int v = acc / S;
-                        if (out && inside) out[((size_t)y * width + x) * 3 + chn] = (uint8_t)v;
-                        diff += (unsigned)abs(v - cpx);
-                    }
-                }
-            if (weights) weights[c] = (uint8_t)(w[0] | w[1] << 4);
-            if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) {
-                s[0] += w[0] > 0; s[1] += w[1] > 0; s[2] += (unsigned)(w[0] + w[1]); s[3] += diff;
-            }
-        }
-    if (stats4) memcpy(stats4, s, sizeof s);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, W0 / 2, H0 / 2, what, "cells")) return rc;
+    bbme::temporal_filter(prev, cur, next, 3, width, height, pad_x, pad_y, to_prev, to_next, thr, win, out, weights, stats4);
     return BBME_OK;
 }
 
@@ -952,11 +939,8 @@ int bbme_subpel_host(const uint8_t *image1, const uint8_t *image2, int width, in
     if (width > 8188 || height > 8188)
         return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: %dx%d is beyond 8188 (quarter-pel vectors would not fit 16 bits)", what, width, height);
     const int cw = width / 2, ch = height / 2;
-    if (window && (window[0] < 0 || window[1] < 0 || window[2] < 1 || window[3] < 1 ||
-                   (long long)window[0] + window[2] > cw || (long long)window[1] + window[3] > ch))
-        return bbme::fail(BBME_ERR_INVALID, "%s: window not inside the %dx%d cells", what, cw, ch);
-    const int wx0 = window ? window[0] : 0, wy0 = window ? window[1] : 0;
-    const int wx1 = window ? window[0] + window[2] : cw, wy1 = window ? window[1] + window[3] : ch;
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cw, ch, what, "cells")) return rc;
     const auto sat16 = [](int v) { return (int16_t)(v < -32768 ? -32768 : v > 32767 ? 32767 : v); };
     static const int order[8][2] = {{-1, -1}, {0, -1}, {1, -1}, {-1, 0}, {1, 0}, {-1, 1}, {0, 1}, {1, 1}};
     unsigned long long s[4] = {0, 0, 0, 0};
@@ -992,7 +976,7 @@ int bbme_subpel_host(const uint8_t *image1, const uint8_t *image2, int width, in
                         if (k < best) { best = k; qx = c0x + step * d[0]; qy = c0y + step * d[1]; }
                     }
                 }
-                if (cx >= wx0 && cx < wx1 && cy >= wy0 && cy < wy1) {
+                if (win.contains(cx, cy)) {
                     ++s[0]; s[1] += qx != 0 || qy != 0; s[2] += (unsigned)cost0; s[3] += (unsigned)best;
                 }
             }

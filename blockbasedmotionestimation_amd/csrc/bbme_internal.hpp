@@ -57,7 +57,5 @@ void cells_color(const int16_t *cells, int cells_w, int width, int height, int p
 int ppm_write_bgr(const char *filename, int width, int height, const uint8_t *bgr);
 void subsample_div4(const float *flow_padded, int padded_width, int padded_height,
                     int pad_x, int pad_y, float *out, int out_width);
-void motion_compensate(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *grid, int grid_block,
-                       int block, int fill, const int window[4], uint8_t *out, unsigned long long stats[4]);
 
 }  // namespace bbme

@@ -254,6 +254,56 @@ def shard_frames(n_frames, rank, world_size):
     return (first, first + count) if count else None
 
 
+def _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect, bidirectional=False, upsample=1):
+    """The loop of every video driver: the len(frames) - 1 consecutive pairs on chain contexts (MFChain) that follow
+    plan_frame_segments -- in_flight // batch contexts, each walking a contiguous segment of the video.  A context's first
+    round sets count + 1 frames, every later round rolls its last frame to slot 0 (MFChain.advance) and sets `count`; a short
+    round is padded by repeating its last frame (the padded pairs are not read).  Every round enqueues estimate_async, or
+    estimate_bidirectional_async with `bidirectional`, and collect(mf, first, count) reads the products of its pairs
+    first .. first + count - 1 from the context's pairs 0 .. count - 1 (a read waits for that context's stream only).
+    COLLECT BEFORE ADVANCE: the roll and the next estimate overwrite the planes and grids that collect reads, so a round is
+    collected before its context advances, and the rounds still in flight at the end in slot order.  Speculation is switched
+    off when several pairs are in flight (they fill the chip already); every context is closed, also when a read raises."""
+    from .motion_framework import MFChain
+    n_pairs = len(frames) - 1
+    per = max(1, min(batch, in_flight, n_pairs))
+    n_slots = max(1, in_flight // per)
+    rounds = plan_frame_segments(n_pairs, n_slots, per)
+    n_ctx = 1 + max(r[0] for r in rounds)
+    chains = [None] * n_ctx
+    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
+
+    def drain(slot):
+        first, count = pending[slot]
+        pending[slot] = None
+        collect(chains[slot], first, count)
+
+    try:
+        for slot, first, count, carry in rounds:
+            run = frames[first + 1:first + count + 1]
+            run = run + [run[-1]] * (per - count)
+            if not carry:
+                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device,
+                                       upsample=upsample)
+                if n_ctx * per > 1:
+                    chains[slot].set_speculation(False)
+            else:
+                drain(slot)
+                chains[slot].advance(run)
+            if bidirectional:
+                chains[slot].estimate_bidirectional_async()
+            else:
+                chains[slot].estimate_async()
+            pending[slot] = (first, count)
+        for slot in range(n_ctx):
+            if pending[slot]:
+                drain(slot)
+    finally:
+        for mf in chains:
+            if mf is not None:
+                mf.close()
+
+
 def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_flight=4, batch=2, upsample=1, subpel=False):
     """The len(frames) - 1 consecutive pairs of a video on ONE GPU: the unpadded (H, W, 2) float32 fields in order, the same
     as estimate_pairs_pipelined(list(zip(frames, frames[1:])), ...), but on chain contexts (MFChain) that follow
@@ -262,25 +312,15 @@ def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_f
     repeating its last frame (the padded pairs are not read).  upsample=4: original frames, fields of the up-sampled size.
     subpel=True: instead of the fields, every pair's cells refined to quarter-pel on its level-0 planes (MF.subpel_cells), the
     padded (CH, CW, 2) int16 grids in quarter pixels (of the up-sampled frame with upsample=4)."""
-    from .motion_framework import MFChain
     frames = list(frames)
     n_pairs = len(frames) - 1
     if n_pairs < 1:
         return []
     if device is None:
         device = local_device()
-    per = max(1, min(batch, in_flight, n_pairs))
-    n_slots = max(1, in_flight // per)
-    rounds = plan_frame_segments(n_pairs, n_slots, per)
-    n_ctx = 1 + max(r[0] for r in rounds)
-    chains = [None] * n_ctx
     out = [None] * n_pairs
-    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
 
-    def collect(slot):
-        first, count = pending[slot]
-        pending[slot] = None
-        mf = chains[slot]
+    def collect(mf, first, count):
         h, w = mf.orig_height, mf.orig_width
         for p in range(count):
             if subpel:
@@ -289,27 +329,7 @@ def estimate_frames_pipelined(frames, search_size, block_size, device=None, in_f
             flow = mf.get_pair_flow(p)                     # waits for this context's stream only
             out[first + p] = np.ascontiguousarray(flow[mf.padding_y:mf.padding_y + h, mf.padding_x:mf.padding_x + w])
 
-    try:
-        for slot, first, count, carry in rounds:
-            run = frames[first + 1:first + count + 1]
-            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
-            if not carry:
-                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device,
-                                       upsample=upsample)
-                if n_ctx * per > 1:
-                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
-            else:
-                collect(slot)
-                chains[slot].advance(run)
-            chains[slot].estimate_async()
-            pending[slot] = (first, count)
-        for slot in range(n_ctx):
-            if pending[slot]:
-                collect(slot)
-    finally:
-        for mf in chains:
-            if mf is not None:
-                mf.close()
+    _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect, upsample=upsample)
     return out
 
 
@@ -320,25 +340,15 @@ def estimate_frames_bidirectional(frames, search_size, block_size, device=None, 
     Returns one tuple per pair: (forward (H, W, 2) float32, backward (H, W, 2) float32 -- the unpadded fields, the backward
     one expanded on the host from its cells --, forward mask, backward mask -- uint8 consistency classes at tolerance `tol`
     over the cells whose top-left pixel lies in the unpadded frame, MF.default_cell_window)."""
-    from .motion_framework import MFChain
     frames = list(frames)
     n_pairs = len(frames) - 1
     if n_pairs < 1:
         return []
     if device is None:
         device = local_device()
-    per = max(1, min(batch, in_flight, n_pairs))
-    n_slots = max(1, in_flight // per)
-    rounds = plan_frame_segments(n_pairs, n_slots, per)
-    n_ctx = 1 + max(r[0] for r in rounds)
-    chains = [None] * n_ctx
     out = [None] * n_pairs
-    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
 
-    def collect(slot):
-        first, count = pending[slot]
-        pending[slot] = None
-        mf = chains[slot]
+    def collect(mf, first, count):
         h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
         cx0, cy0, cw, ch = mf.default_cell_window()
         for p in range(count):
@@ -348,27 +358,7 @@ def estimate_frames_bidirectional(frames, search_size, block_size, device=None, 
             out[first + p] = (np.ascontiguousarray(fwd[py:py + h, px:px + w]), np.ascontiguousarray(bwd[py:py + h, px:px + w]),
                               masks[0], masks[1])
 
-    try:
-        for slot, first, count, carry in rounds:
-            run = frames[first + 1:first + count + 1]
-            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
-            if not carry:
-                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device,
-                                       upsample=upsample)
-                if n_ctx * per > 1:
-                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
-            else:
-                collect(slot)
-                chains[slot].advance(run)
-            chains[slot].estimate_bidirectional_async()
-            pending[slot] = (first, count)
-        for slot in range(n_ctx):
-            if pending[slot]:
-                collect(slot)
-    finally:
-        for mf in chains:
-            if mf is not None:
-                mf.close()
+    _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect, bidirectional=True, upsample=upsample)
     return out
 
 
@@ -381,7 +371,6 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
     Colour video: (H, W, 3) frames in B,G,R order give (H, W, 3) frames on the same plan -- the luma planes are made on the
     GPU from the colour frames (the luma rule), the fields are the luma's, and the frames in between come from the stored
     colour by the BGR interpolation rule (MF.interpolate_run_bgr); still every frame is set once."""
-    from .motion_framework import MFChain
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     bgr = bool(frames) and frames[0].ndim == 3
     factor = int(factor)
@@ -392,18 +381,9 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
         return frames
     if device is None:
         device = local_device()
-    per = max(1, min(batch, in_flight, n_pairs))
-    n_slots = max(1, in_flight // per)
-    rounds = plan_frame_segments(n_pairs, n_slots, per)
-    n_ctx = 1 + max(r[0] for r in rounds)
-    chains = [None] * n_ctx
     between = [None] * n_pairs
-    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
 
-    def collect(slot):
-        first, count = pending[slot]
-        pending[slot] = None
-        mf = chains[slot]
+    def collect(mf, first, count):
         h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
         for p in range(count):
             if bgr:
@@ -412,26 +392,7 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
             run = mf.interpolate_run(factor, pair=p)       # waits for this context's stream only
             between[first + p] = [np.ascontiguousarray(f[py:py + h, px:px + w]) for f in run]
 
-    try:
-        for slot, first, count, carry in rounds:
-            run = frames[first + 1:first + count + 1]
-            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
-            if not carry:
-                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device)
-                if n_ctx * per > 1:
-                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
-            else:
-                collect(slot)                              # reads the planes the roll is about to replace
-                chains[slot].advance(run)
-            chains[slot].estimate_bidirectional_async()
-            pending[slot] = (first, count)
-        for slot in range(n_ctx):
-            if pending[slot]:
-                collect(slot)
-    finally:
-        for mf in chains:
-            if mf is not None:
-                mf.close()
+    _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect, bidirectional=True)
     out = []
     for p in range(n_pairs):
         out.append(frames[p])
@@ -455,7 +416,6 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
     MF.cells_temporal_filter_device from the copies and its own buffers.  No plane or grid goes through the host.  In colour
     the same plan, rounds and copies, of the stored colour frames in the planes' place (MFChain.temporal_filter_run_bgr,
     MF.frame_bgr_tensor, MF.cells_temporal_filter_bgr_device)."""
-    from .motion_framework import MFChain
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     n_pairs = len(frames) - 1
     if n_pairs < 1:
@@ -465,13 +425,7 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
     import torch
     strength = int(strength)
     bgr = frames[0].ndim == 3
-    per = max(1, min(batch, in_flight, n_pairs))
-    n_slots = max(1, in_flight // per)
-    rounds = plan_frame_segments(n_pairs, n_slots, per)
-    n_ctx = 1 + max(r[0] for r in rounds)
-    chains = [None] * n_ctx
     out = [None] * len(frames)
-    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
     before, after = {}, {}                                 # frame -> copies of (previous plane, grid into it) / (frame, next plane, grid)
 
     def boundary(mf, g, prev, to_prev, cur, nxt, to_next):
@@ -488,10 +442,7 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
         h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
         out[g] = np.ascontiguousarray(plane[py:py + h, px:px + w])
 
-    def collect(slot):
-        first, count = pending[slot]
-        pending[slot] = None
-        mf = chains[slot]
+    def collect(mf, first, count):
         frame_tensor = mf.frame_bgr_tensor if bgr else mf.frame_plane_tensor
         lo = 0 if first == 0 else 1                        # the video's first frame has no previous one anywhere: the chain's own slot 0
         if count > lo:
@@ -519,26 +470,7 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
                 before[last] = tuple(t.clone() for t in half)
             torch.cuda.current_stream().synchronize()      # the copies are taken before the roll and the next estimate overwrite them
 
-    try:
-        for slot, first, count, carry in rounds:
-            run = frames[first + 1:first + count + 1]
-            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
-            if not carry:
-                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device)
-                if n_ctx * per > 1:
-                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
-            else:
-                collect(slot)                              # reads the planes the roll is about to replace
-                chains[slot].advance(run)
-            chains[slot].estimate_bidirectional_async()
-            pending[slot] = (first, count)
-        for slot in range(n_ctx):
-            if pending[slot]:
-                collect(slot)
-    finally:
-        for mf in chains:
-            if mf is not None:
-                mf.close()
+    _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect, bidirectional=True)
     return out
 
 
@@ -548,50 +480,21 @@ def colorize_frames(frames, search_size, block_size, maxmotion=-1.0, scale=1, in
     max u, min v, max v)).  maxmotion > 0 normalises every picture by the same radius; otherwise each by its own.  Runs on the
     chain plan of estimate_frames_pipelined (same contexts, rounds and padding of a short round): every frame is set once, a
     round's ranges come from one launch (MFBatch.flow_ranges_all) and only the images' bytes are downloaded."""
-    from .motion_framework import MFChain
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     n_pairs = len(frames) - 1
     if n_pairs < 1:
         return np.empty((0, 0, 0, 3), np.uint8), np.empty((0, 5), np.float32)
     if device is None:
         device = local_device()
-    per = max(1, min(batch, in_flight, n_pairs))
-    n_slots = max(1, in_flight // per)
-    rounds = plan_frame_segments(n_pairs, n_slots, per)
-    n_ctx = 1 + max(r[0] for r in rounds)
-    chains = [None] * n_ctx
     images = [None] * n_pairs
     ranges = np.empty((n_pairs, 5), np.float32)
-    pending = [None] * n_ctx                               # per context: (first_pair, count) of the round in flight
 
-    def collect(slot):
-        first, count = pending[slot]
-        pending[slot] = None
-        mf = chains[slot]
+    def collect(mf, first, count):
         ranges[first:first + count] = mf.flow_ranges_all("forward", scale)[:count]      # waits for this context's stream only
         for p in range(count):
             images[first + p] = mf.get_pair_flow_color(p, scale, maxmotion)
 
-    try:
-        for slot, first, count, carry in rounds:
-            run = frames[first + 1:first + count + 1]
-            run = run + [run[-1]] * (per - count)          # a short round: padded, not read
-            if not carry:
-                chains[slot] = MFChain([frames[first]] + run, search_size, block_size, len(block_size), device=device)
-                if n_ctx * per > 1:
-                    chains[slot].set_speculation(False)    # the other pairs in flight fill the chip already
-            else:
-                collect(slot)
-                chains[slot].advance(run)
-            chains[slot].estimate_async()
-            pending[slot] = (first, count)
-        for slot in range(n_ctx):
-            if pending[slot]:
-                collect(slot)
-    finally:
-        for mf in chains:
-            if mf is not None:
-                mf.close()
+    _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect)
     return np.stack(images), ranges
 
 

@@ -1,6 +1,43 @@
 """Shared helpers of the parity tests: drive the product (HIP, through the C-ABI) and the
 oracle (CPU restatement) through the reference's level schedule stage by stage."""
 import numpy as np
+import pytest
+
+
+# ---- small helpers the GPU test modules share -------------------------------------------------------------------------------
+def _stats_of(keys):
+    """-> _stats(d): a statistics dict's values in the order of `keys` (every product's test module binds its own STAT_KEYS)."""
+    def _stats(d):
+        return tuple(d[k] for k in keys)
+    return _stats
+
+
+def _odd_window(mf):
+    cx0, cy0, cw, ch = mf.default_cell_window()
+    return (cx0 + 3, cy0 + 1, cw - 8, ch - 5)
+
+
+def _status(bbme, call):
+    with pytest.raises(bbme.BbmeError) as e:
+        call()
+    return e.value.status
+
+
+def _cuda(a):
+    import torch
+    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
+
+
+def _embed(plane, H0, W0, fill=0):
+    out = np.full((H0, W0), fill, plane.dtype)
+    out[:plane.shape[0], :plane.shape[1]] = plane
+    return out
+
+
+def _write_pgm(path, img):
+    h, w = img.shape
+    with open(path, "wb") as f:
+        f.write(b"P5\n%d %d\n255\n" % (w, h) + img.tobytes())
 
 
 def oracle_schedule(omf, levels, on_stage=None):

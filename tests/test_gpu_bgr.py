@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import _status
 from test_bgr_cpu import SHAPES, colour_pair, luma_planes, np_bgr_to_gray, np_interpolate_bgr
 from test_interpolation_cpu import random_grids
 
@@ -274,12 +275,6 @@ def test_direction_backward_exchanges_the_colour_frames_too(bbme):
     assert np.array_equal(mf.interpolate_bgr(1, 2), np_interpolate_bgr(I1, I2, c1, c2, mf.get_cells(), mf.get_backward_cells(), 1, 2, px, py))
     mf.close()
     swapped.close()
-
-
-def _status(bbme, call):
-    with pytest.raises(bbme.BbmeError) as e:
-        call()
-    return e.value.status
 
 
 def test_a_grey_setter_withdraws_the_stored_colour(bbme):

@@ -9,8 +9,10 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import assert_stages_equal, gpu_schedule, oracle_schedule
+from helpers import _odd_window, _stats_of, _write_pgm, assert_stages_equal, gpu_schedule, oracle_schedule
 from test_consistency_cpu import (GENERATORS, STAT_KEYS, TOLS, np_cells_consistency, windows_of)
+
+_stats = _stats_of(STAT_KEYS)
 
 pytestmark = pytest.mark.gpu
 
@@ -74,15 +76,6 @@ def _blocks(B):
     while b <= B:
         yield b
         b *= 2
-
-
-def _stats(d):
-    return tuple(d[k] for k in STAT_KEYS)
-
-
-def _odd_window(mf):
-    cx0, cy0, cw, ch = mf.default_cell_window()
-    return (cx0 + 3, cy0 + 1, cw - 8, ch - 5)
 
 
 def _results(mf, levels, blocks):
@@ -574,12 +567,6 @@ def test_consistency_calls_change_no_state_and_refuse_bad_arguments(bbme):
     assert e.value.status == inv
     _assert_same(dict(flow=mf.get_flow(), back=mf.get_backward_cells()), dict(flow=before["flow"], back=before["back"]), "errors")
     mf.close()
-
-
-def _write_pgm(path, img):
-    h, w = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (w, h) + img.tobytes())
 
 
 def test_cli_writes_the_backward_field_and_the_occlusion_mask(bbme, tmp_path):

@@ -589,3 +589,87 @@ def test_a_batch_of_64_pairs_set_last_pair_first(bbme):
         assert np.array_equal(got, mf.get_cells()), "pair %d" % p
         mf.close()
     _capi.check(lib.bbme_destroy(ctx))
+
+
+# ---- one staging area per context serves every host getter, in any order -----------------------------------------------------
+# name -> the getter on pair 1 of a bidirectional batch; in the order of the bytes they stage (96 x 72 frames, 128 x 128 planes)
+_STAGED_GETTERS = [
+    ("sub4", lambda mf: mf.get_pair_subsampled_flow(1, 4)),                     # 3 456 bytes
+    ("mask", lambda mf: mf.consistency("backward", 1, pair=1)),                 # 4 096
+    ("mc_level1", lambda mf: mf.get_pair_motion_compensated(1, level=1, block=4, fill=9)),
+    ("mc_level0", lambda mf: mf.get_pair_motion_compensated(1, level=0, block=2, fill=9)),      # 16 384
+    ("interpolated", lambda mf: mf.get_pair_interpolated(1, 1, 3)),
+    ("filtered", lambda mf: mf.get_frame_filtered(1, 0, 64)),
+    ("subpel_cells", lambda mf: mf.get_pair_subpel_cells(1)),
+    ("colour", lambda mf: (mf.get_pair_flow_color(1, 1), np.array(mf.last_color_range, np.float32))),      # 20 736 + the ranges
+    ("interpolated_bgr", lambda mf: mf.interpolate_bgr(1, 3, pair=1)),
+    ("filtered_bgr", lambda mf: mf.get_frame_filtered_bgr(1, 0, 64)),
+    ("sub1", lambda mf: mf.get_pair_subsampled_flow(1, 1)),                     # 55 296
+    ("subpel_flow", lambda mf: mf.get_pair_subpel_flow(1)),                     # 55 296 + 16 384 of cells behind them
+]
+_staged_cache = {}
+
+
+def _staged_batch(bbme):
+    from test_gpu_bgr import VIDEO_PARAMS, colour_video
+    frames = [np.ascontiguousarray(f[:72, :96]) for f in colour_video(bbme)[:3]]
+    mf = bbme.MFBatch([(frames[0], frames[1]), (frames[1], frames[2])], *VIDEO_PARAMS)
+    mf.estimate_bidirectional_async()
+    return mf
+
+
+def _staged_x4_batch(bbme):
+    video = bbme.synth_video(48, 36, 3, 77, max_motion=2)
+    mf = bbme.MFBatch([(video[0], video[1]), (video[1], video[2])], [30, 30], [16, 16], upsample=4)
+    mf.estimate_bidirectional_async()
+    return mf
+
+
+def _staged_reference(bbme):
+    """Every getter's result as the FIRST call on a fresh context (its staging area still empty); made once, never changed."""
+    if not _staged_cache:
+        for name, get in _STAGED_GETTERS:
+            mf = _staged_batch(bbme)
+            _staged_cache[name] = get(mf)
+            mf.close()
+        for name, get in (("x4_subpel_flow", lambda mf: mf.get_pair_subpel_flow(1)),
+                          ("x4_subpel_cells", lambda mf: mf.get_pair_subpel_cells(1))):
+            mf = _staged_x4_batch(bbme)
+            _staged_cache[name] = get(mf)
+            mf.close()
+    return _staged_cache
+
+
+def _same_bytes(got, exp):
+    got, exp = (x if isinstance(x, tuple) else (x,) for x in (got, exp))
+    return len(got) == len(exp) and all(g.dtype == e.dtype and g.shape == e.shape and g.tobytes() == e.tobytes() for g, e in zip(got, exp))
+
+
+@pytest.mark.parametrize("order", ["ascending", "descending", "subpel_flow_first"])
+def test_one_staging_area_serves_every_host_getter_in_any_order(bbme, order):
+    ref = _staged_reference(bbme)
+    getters = {"ascending": _STAGED_GETTERS, "descending": _STAGED_GETTERS[::-1],
+               "subpel_flow_first": _STAGED_GETTERS[-1:] + _STAGED_GETTERS[:-1]}[order]
+    mf = _staged_batch(bbme)
+    try:
+        for name, get in getters + getters[:2]:                      # and the first two again, behind everything else
+            assert _same_bytes(get(mf), ref[name]), "%s order: %s differs from a fresh context's" % (order, name)
+    finally:
+        mf.close()
+    assert ref["sub4"].shape == (18, 24, 2) and ref["subpel_flow"].shape == (72, 96, 2) and ref["colour"][1].shape == (5,)
+    assert np.abs(ref["subpel_flow"]).max() > 0 and len(np.unique(ref["colour"][0])) > 8      # results, not blank buffers
+
+
+def test_subpel_field_and_cells_share_the_area_on_an_upsampling_context(bbme):
+    """upsample=4: the field (48 x 36 x 2 floats) is not the size of the cells it is expanded from (the x4 planes' 2x2 cells),
+    so the cells' region does not start where a cells-only download puts them."""
+    ref = _staged_reference(bbme)
+    mf = _staged_x4_batch(bbme)
+    try:
+        assert ref["x4_subpel_flow"].shape == (36, 48, 2) and ref["x4_subpel_cells"].shape == mf.cells_shape + (2,)
+        assert ref["x4_subpel_flow"].nbytes != ref["x4_subpel_cells"].nbytes
+        for name, get in (("x4_subpel_flow", mf.get_pair_subpel_flow), ("x4_subpel_cells", mf.get_pair_subpel_cells),
+                          ("x4_subpel_flow", mf.get_pair_subpel_flow)):
+            assert _same_bytes(get(1), ref[name]), name
+    finally:
+        mf.close()

@@ -21,9 +21,9 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import _write_pgm
 from test_flow_color_cpu import (EXTREME_MAXMOTIONS, all_vectors_grid, assert_within_atan2_cap, axes_grid, full_range_grid,
                                  np_color_cells, subsampled_field)
-from test_gpu_bidirectional import _write_pgm
 
 pytestmark = pytest.mark.gpu
 

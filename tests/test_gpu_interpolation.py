@@ -9,23 +9,17 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_bidirectional import CASES, _frames, _write_pgm
+from helpers import _odd_window, _stats_of, _write_pgm
+from test_gpu_bidirectional import CASES, _frames
 from test_interpolation_cpu import (DIVISION_DENS, STAT_KEYS, extreme_grids, np_interpolate, oracle_grids, ramp_expected,
                                     ramp_pair, random_grids)
+
+_stats = _stats_of(STAT_KEYS)
 
 pytestmark = pytest.mark.gpu
 
 VIDEO = (200, 136, 4, 77, 6)                               # synth_video(width, height, frames, seed, max_motion=...)
 VIDEO_PARAMS = ([30, 30, 30], [16, 16, 16])
-
-
-def _stats(d):
-    return tuple(d[k] for k in STAT_KEYS)
-
-
-def _odd_window(mf):
-    cx0, cy0, cw, ch = mf.default_cell_window()
-    return (cx0 + 3, cy0 + 1, cw - 8, ch - 5)
 
 
 def _device_interpolate(mf, f, b, num0, count, den, window=None, pitch_extra=0, stream=None, want=("out", "sel", "stats")):

@@ -9,7 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import oracle_schedule
+from helpers import _write_pgm, oracle_schedule
 from test_motion_compensation_cpu import block_mvs_from_grid, np_draw_mvimage, np_stats
 
 pytestmark = pytest.mark.gpu
@@ -344,12 +344,6 @@ def test_errors_and_no_state_change(bbme):
     assert np.array_equal(mf.draw_MVimage(), mc) and mf.compensation_error() == err
     assert np.array_equal(mf.calcMotionBlockMatching(), flow)
     mf.close()
-
-
-def _write_pgm(path, img):
-    h, w = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (w, h) + img.tobytes())
 
 
 def test_cli_writes_the_compensated_frame(bbme, tmp_path):

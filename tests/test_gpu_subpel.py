@@ -8,19 +8,12 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_bidirectional import _write_pgm
+from helpers import _cuda, _stats_of, _write_pgm
 from test_subpel_cpu import STAT_KEYS, boundary_grid, cells_to_field, extreme_grid
 
+_stats = _stats_of(STAT_KEYS)
+
 pytestmark = pytest.mark.gpu
-
-
-def _stats(d):
-    return tuple(d[k] for k in STAT_KEYS)
-
-
-def _cuda(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _host(bbme, I1, I2, G, window=None):

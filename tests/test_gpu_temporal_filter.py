@@ -10,29 +10,18 @@ import subprocess
 import numpy as np
 import pytest
 
-from test_gpu_bidirectional import CASES, _frames, _write_pgm
+from helpers import _cuda, _embed, _odd_window, _stats_of, _write_pgm
+from test_gpu_bidirectional import CASES, _frames
 from test_interpolation_cpu import extreme_grids, oracle_grids, random_grids
 from test_temporal_filter_cpu import (S23_THR, STAT_KEYS, THRS, np_temporal_filter, s23_table_planes, s_table_check, s_table_planes,
                                       thr_table_expected, thr_table_planes)
+
+_stats = _stats_of(STAT_KEYS)
 
 pytestmark = pytest.mark.gpu
 
 VIDEO = (200, 136, 4, 77, 6)                               # synth_video(width, height, frames, seed, max_motion=...)
 VIDEO_PARAMS = ([30, 30, 30], [16, 16, 16])
-
-
-def _stats(d):
-    return tuple(d[k] for k in STAT_KEYS)
-
-
-def _odd_window(mf):
-    cx0, cy0, cw, ch = mf.default_cell_window()
-    return (cx0 + 3, cy0 + 1, cw - 8, ch - 5)
-
-
-def _cuda(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _device_filter(mf, Cur, P, GP, N, GN, thr, window=None, pitch_extra=0, stream=None, want=("out", "map", "stats")):
@@ -144,12 +133,6 @@ def table_context(bbme):
     assert (mf.padded_width, mf.padded_height) == (132, 100)
     yield mf
     mf.close()
-
-
-def _embed(plane, H0, W0, fill=0):
-    out = np.full((H0, W0), fill, plane.dtype)
-    out[:plane.shape[0], :plane.shape[1]] = plane
-    return out
 
 
 @pytest.mark.parametrize("thr", THRS)

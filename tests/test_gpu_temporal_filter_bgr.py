@@ -11,6 +11,7 @@ import subprocess
 import numpy as np
 import pytest
 
+from helpers import _cuda, _embed, _stats_of, _status
 from test_bgr_cpu import SHAPES, np_bgr_to_gray
 from test_gpu_bgr import VIDEO, VIDEO_PARAMS, _write_ppm, colour_video
 from test_interpolation_cpu import extreme_grids, odd_windows, random_grids
@@ -18,18 +19,11 @@ from test_temporal_filter_bgr_cpu import RULE_THRS, in_channel, near_colour_trip
 from test_temporal_filter_cpu import (S23_THR, STAT_KEYS, THRS, neighbour_sets, s23_table_planes, s_table_check, s_table_planes,
                                       thr_table_expected, thr_table_planes)
 
+_stats = _stats_of(STAT_KEYS)
+
 pytestmark = pytest.mark.gpu
 
 _cache = {}
-
-
-def _stats(d):
-    return tuple(d[k] for k in STAT_KEYS)
-
-
-def _cuda(a):
-    import torch
-    return None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
 def _pitched_tensor(frame, extra):
@@ -137,12 +131,6 @@ def table_context(bbme):
     assert (mf.padded_width, mf.padded_height, mf.padding_x, mf.padding_y) == (132, 100, 0, 0)
     yield mf
     mf.close()
-
-
-def _embed(plane, H0, W0):
-    out = np.zeros((H0, W0), plane.dtype)
-    out[:plane.shape[0], :plane.shape[1]] = plane
-    return out
 
 
 @pytest.mark.parametrize("k", [0, 1, 2])
@@ -263,12 +251,6 @@ def test_chain_filters_every_slot_and_batch_one_side(bbme):
             exp += [_video_rule(video, fields, p, 64, np_win, side="next")[2], _video_rule(video, fields, p + 1, 64, np_win, side="prev")[2]]
         assert [_stats(s) for s in batch.temporal_filter_bgr_stats(64, w)] == exp, w
     batch.close()
-
-
-def _status(bbme, call):
-    with pytest.raises(bbme.BbmeError) as e:
-        call()
-    return e.value.status
 
 
 def test_colour_filter_needs_fields_and_stored_colour(bbme):

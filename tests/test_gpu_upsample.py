@@ -13,7 +13,7 @@ import subprocess
 import numpy as np
 import pytest
 
-from helpers import HARD_CONTENTS, hard_content
+from helpers import HARD_CONTENTS, _write_pgm, hard_content
 
 pytestmark = pytest.mark.gpu
 
@@ -293,12 +293,6 @@ def test_x4_errors(bbme):
     assert e.value.status == _capi.ERR_INVALID
     assert L.bbme_get_subsampled_flow_host(mf._ctx, 0, 4, out.ctypes.data) == _capi.OK
     mf.close()
-
-
-def _write_pgm(path, img):
-    h, w = img.shape
-    with open(path, "wb") as f:
-        f.write(b"P5\n%d %d\n255\n" % (w, h) + img.tobytes())
 
 
 def test_cli_output_equals_host_pipeline(bbme, venus, venus_flo, tmp_path):
