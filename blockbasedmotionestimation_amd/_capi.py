@@ -183,6 +183,7 @@ SIGNATURES = {
     "bbme_stage_get_mvs": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
     "bbme_stage_set_mvs": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
     "bbme_stage_expand": (C.c_int, [_ctx]),
+    "bbme_fixup_counts": (C.c_int, [_ctx, C.c_int, _P(C.c_uint), C.c_int]),
     "bbme_last_sweep_passes": (C.c_int, [_ctx, _P(C.c_int)]),
     "bbme_sweep_stats": (C.c_int, [_ctx, _P(C.c_uint)]),
     "bbme_set_profiling": (C.c_int, [_ctx, C.c_int]),

@@ -118,13 +118,16 @@ struct Level {
     size_t frame_step = 0;                        // bytes from a pair's image 1 to its image 2: on a chain one plane_stride
     // MV grids.  small[]: grids at the level's own block size B (the search writes small[0]; the two sweeps at B go
     // small[0] -> small[1] -> small[0], which then stays untouched until the level's next search: the speculative search
-    // of the next finer level predicts from it).  big[]: grids at b < B (capacity (H/2)*(W/2)), ping-pong.
+    // of the next finer level predicts from it).  big[]: grids at b < B (capacity (H/2)*(W/2)), ping-pong; zeroed at creation,
+    // since a speculative search may read them before any sweep has written them (newest_coarse_grid, bbme_kernels.hpp).
     DevBuf<mv_t> small[2];
     DevBuf<mv_t> big[2];
     mv_t *cur_grid = nullptr;                     // the grid that holds the current field
     int cur_block = 0;                            // its block size (0 = nothing yet)
     DevBuf<mv_t> pred;                            // per block: the coarse MV a speculative search started from
     DevBuf<uint32_t> fix_list, fix_count;         // blocks to search again after a speculative search
+    // as the coarse side of a speculative search: the sweeps behind the fork that are complete (RegArgs::publish; 64 bytes per pair)
+    DevBuf<uint32_t> publish;
     mv_t *final_grid() const { return block == 2 ? small[0] : big[1]; }   // where two sweeps per block size leave the 2x2 cells
     DevBuf<uint32_t> spiral;                      // rank -> packed (dx, dy)
     int ncand = 0;
@@ -194,6 +197,14 @@ struct Tuning {
         return ((size_t)(160 - 40) * 1024 / per_cu) / 256 * 256;
     }
     double spec_min_absdiffs = 8e9;               // levels with less search work are not speculated; BBME_SPEC_MIN_GABS
+    // where a speculative search's block takes its prediction from (newest_coarse_grid): 1 = the newest grid of the coarser level
+    // that is complete when the block starts; 0 = the grid at the fork, every block (A/B runs); 2 = test setting: the LAST grid
+    // of the table whatever is complete, so that blocks read grids that are unwritten, mid-write or of another geometry
+    int spec_late = 1;                            // BBME_SPEC_LATE
+    // the sweep at B the speculative search is forked behind: the first (with late predictions the blocks no longer depend on the
+    // grid at the fork; cfg4 1.547 -> 1.514 ms, cfg3 1.460 / 1.463: profiles/r18_late_prediction.txt) or, =0, the second.  Without
+    // late predictions (BBME_SPEC_LATE=0) always the second: behind the first, cfg3 loses 2 %
+    bool spec_fork_first = true;                  // BBME_SPEC_FORK_FIRST
 };
 
 const struct {
@@ -219,6 +230,8 @@ const struct {
          if (const char *comma = strchr(e, ',')) t.spec_per_cu_l0 = std::max(1, std::min(32, atoi(comma + 1)));
      }},
     {"BBME_SPEC_MIN_GABS", [](const char *e, Tuning &t) { t.spec_min_absdiffs = atof(e) * 1e9; }},
+    {"BBME_SPEC_LATE", [](const char *e, Tuning &t) { t.spec_late = std::max(0, std::min(2, atoi(e))); }},
+    {"BBME_SPEC_FORK_FIRST", [](const char *e, Tuning &t) { t.spec_fork_first = atoi(e) != 0; }},
     {"BBME_GENERIC_SEARCH", [](const char *e, Tuning &t) { t.force_generic_search = atoi(e) != 0; }},
     {"BBME_LOCAL_ROUNDS", [](const char *e, Tuning &t) { t.local_rounds = std::max(1, atoi(e)); }},
     {"BBME_WIDE_THRESHOLD", [](const char *e, Tuning &t) { t.wide_threshold = std::max(4, atoi(e)); }},
@@ -291,6 +304,9 @@ struct bbme_ctx {
     // FORWARD's graph always speculates; BACKWARD's only while the context has no FORWARD graph, and capturing FORWARD drops a
     // forked BACKWARD graph (captured again, unforked, on its next use).  Tuning::fork_both: both forked (measurements).
     bool graph_forked[2] = {false, false};
+    // bit l: level l's search is speculative in the launch sequence of that direction (enqueue_pyramid), and in the last
+    // estimate (bbme_fixup_counts)
+    uint32_t spec_levels[2] = {0, 0}, last_spec_levels = 0;
     const uint8_t *plane1(const Level &L) const { return direction ? L.img2 : L.img1.get(); }
     const uint8_t *plane2(const Level &L) const { return direction ? L.img1.get() : L.img2; }
     // bbme_estimate_bidirectional: level 0's final grid of the backward half, every pair (bwd_stride words apart), and whether
@@ -516,7 +532,8 @@ int with_block(int b, F &&f)
 
 // Where the search of `level` takes its predictions from (copyMVs, :828-843), by mode:
 //   plain / fix-up : the coarser level's final 2x2-cell grid (it must have been regularised down to 2x2);
-//   speculative    : the coarser level's grid as its two sweeps at its own block size left it (Level::small[0]).
+//   speculative    : the coarser level's grid as the sweeps at its own block size have left it when the search is forked
+//                    (Level::small[0] behind the second of them); the fast kernel's blocks may take a newer one (set_late_grids).
 template <class Args>
 int set_prediction_source(bbme_ctx *c, int level, int mode, Args &a)
 {
@@ -529,9 +546,9 @@ int set_prediction_source(bbme_ctx *c, int level, int mode, Args &a)
     Level &C = c->lv[level + 1];
     a.coarse_block = C.block;
     if (mode == kSearchSpeculative) {
-        if (C.cur_block != C.block || C.cur_grid != C.small[0])
-            return bbme::fail(BBME_ERR_STATE, "level %d is not at the end of the sweeps at its own block size", level + 1);
-        a.coarse = C.small[0];
+        if (C.cur_block != C.block || (C.cur_grid != C.small[0] && C.cur_grid != C.small[1]))
+            return bbme::fail(BBME_ERR_STATE, "level %d is not behind a sweep at its own block size", level + 1);
+        a.coarse = C.cur_grid;
         a.coarse_cell_shift = 0;
         while ((1 << a.coarse_cell_shift) < C.block) ++a.coarse_cell_shift;
     } else {
@@ -543,6 +560,19 @@ int set_prediction_source(bbme_ctx *c, int level, int mode, Args &a)
     a.coarse_cols = C.width >> a.coarse_cell_shift;
     a.s_coarse = C.grid_stride(a.coarse);
     return BBME_OK;
+}
+
+// FastSearchArgs::late of the speculative launch of `level`: the coarser level's grids in the order the sweeps behind the fork
+// leave them (entry 0 is a.coarse, set_prediction_source), and the word those sweeps publish their number in (enqueue_pyramid).
+void set_late_grids(bbme_ctx *c, int level, FastSearchArgs &a)
+{
+    a.late_word = nullptr; a.late_n = 0; a.late_force = 0;
+    if (a.mode != kSearchSpeculative || !a.coarse || c->tune.spec_late == 0) return;
+    const Level &C = c->lv[level + 1];
+    a.late_n = fill_coarse_grids(a.late, C.width, C.block, a.coarse == C.small[1], C.small[0], C.small[1], C.small_stride,
+                                 C.big[0], C.big[1], C.big_stride);
+    a.late_word = C.publish;
+    a.late_force = c->tune.spec_late == 2;
 }
 
 // Level::tasks2 ..: the plan whose rounds have 128 strips, for two waves per macroblock
@@ -569,6 +599,7 @@ int launch_search_fast(bbme_ctx *c, int level, int mode, hipStream_t stream, siz
         a.stage_rpp = 64u / nch;
     }
     if (int rc = set_prediction_source(c, level, mode, a)) return rc;
+    set_late_grids(c, level, a);
     a.out = L.small[0];
     a.cols = L.width / L.block;
     a.pitch_dw = L.fast_pitch_dw;
@@ -713,7 +744,8 @@ void launch_sweep_t(RegArgs a, uint8_t *const (&flags)[2], int relax_steps, bool
     else hipLaunchKernelGGL((k_reg_solve<BS, 16>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
 }
 
-int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false)
+// `publish`: the word the sweep's solver stores `publish_value` in when the sweep is complete (enqueue_pyramid), or nullptr
+int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false, uint32_t *publish = nullptr, uint32_t publish_value = 0)
 {
     Level &L = c->lv[level];
     if (mult < 1) return bbme::fail(BBME_ERR_INVALID, "lambda multiplier %d", mult);
@@ -751,6 +783,7 @@ int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false)
     a.counters = c->counters;
     a.stats = stats ? 1 : 0;
     a.share = c->tune.solve_share ? 1 : 0;
+    a.publish = publish; a.publish_value = publish_value;
     // the SAD memo: sweeps at b >= 8 whose pass 1 runs in the chain form (it is what fills the slots); the first sweep at a
     // (level, block size) finds nothing in it and rewrites every slot
     const long long nblk_memo = (long long)a.rows * a.cols;
@@ -811,9 +844,12 @@ bool worth_speculating(const bbme_ctx *c, int level)
 }
 
 // The level loop of MF::calcMotionBlockMatching (:115-206).  With `speculate`, the search of level l-1 is started on a
-// second stream as soon as level l has finished the two sweeps at its own block size, and runs beside the level's
-// remaining sweeps (which are latency-bound and leave most of the chip idle); when the level is final, a fix-up launch
+// second stream as soon as level l has finished the first sweep at its own block size (Tuning::spec_fork_first), and runs
+// beside the level's remaining sweeps (which are latency-bound and leave most of the chip idle); when the level is final, a fix-up launch
 // searches again the blocks whose prediction those sweeps changed (search_prediction, bbme_kernels.hpp).
+// The sweep in front of the fork publishes 0 in the level's word and every later sweep of the level its number, 1, 2, ...
+// (RegArgs::publish): the speculative search's blocks choose their prediction source by it (newest_coarse_grid).  The 0 is
+// stored before the fork in every replay, so no search sees the count of the step before.
 int enqueue_pyramid(bbme_ctx *c, bool speculate)
 {
     const int nl = (int)c->lv.size();
@@ -825,21 +861,37 @@ int enqueue_pyramid(bbme_ctx *c, bool speculate)
     }
     bool speculated = false;
     c->memo_block = 0;                                  // a captured launch sequence must not depend on what ran before it
+    c->spec_levels[c->direction] = 0;
     for (int l = nl - 1; l >= 0; --l) {
         if (speculated) {
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
             if (int rc = launch_search(c, l, kSearchFixup)) return rc;
         } else if (int rc = launch_search(c, l)) return rc;
         speculated = false;
-        for (int b = c->lv[l].block; b > 1; b >>= 1) {            // while (block_size > 1) :141
-            for (int mult = 1; mult <= 2; ++mult)                  // lambda_multiplier = l + 1 :145
-                if (int rc = launch_sweep(c, l, b, mult)) return rc;
-            if (speculate && l > 0 && b == c->lv[l].block && b > 2 && worth_speculating(c, l - 1)) {
-                HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-                HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-                if (int rc = launch_search(c, l - 1, kSearchSpeculative, c->side_stream, c->tune.spec_lds_for(c->lv[l].block, l - 1))) return rc;
-                HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
-                speculated = true;
+        Level &L = c->lv[l];
+        const bool fork_here = speculate && l > 0 && L.block > 2 && worth_speculating(c, l - 1);
+        const int fork_mult = c->tune.spec_fork_first && c->tune.spec_late ? 1 : 2;     // the sweep at B the search of level l - 1 is forked behind
+        uint32_t *const word = fork_here && c->tune.spec_late ? L.publish.get() : nullptr;
+        uint32_t behind_fork = 0;                                  // sweeps of the level enqueued behind the fork
+        CoarseGrid table[kMaxCoarseGrids];                         // what set_late_grids hands the search: checked against the sweeps
+        const int table_n = fill_coarse_grids(table, L.width, L.block, fork_mult == 1, L.small[0], L.small[1], L.small_stride,
+                                              L.big[0], L.big[1], L.big_stride);
+        for (int b = L.block; b > 1; b >>= 1) {                    // while (block_size > 1) :141
+            for (int mult = 1; mult <= 2; ++mult) {                // lambda_multiplier = l + 1 :145
+                const bool counts = speculated || (b == L.block && mult == fork_mult);
+                if (int rc = launch_sweep(c, l, b, mult, false, counts ? word : nullptr, behind_fork)) return rc;
+                if (counts && word && ((int)behind_fork >= table_n || L.cur_grid != table[behind_fork].grid || L.cur_block != 1 << table[behind_fork].cell_shift))
+                    return bbme::fail(BBME_ERR_STATE, "level %d: sweep %u behind the fork is not entry %u of the coarse grid table", l, behind_fork, behind_fork);
+                if (speculated) ++behind_fork;
+                if (fork_here && b == L.block && mult == fork_mult) {
+                    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+                    HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
+                    if (int rc = launch_search(c, l - 1, kSearchSpeculative, c->side_stream, c->tune.spec_lds_for(L.block, l - 1))) return rc;
+                    HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
+                    speculated = true;
+                    behind_fork = 1;
+                    c->spec_levels[c->direction] |= 1u << (l - 1);
+                }
             }
         }
     }
@@ -981,8 +1033,9 @@ static int create_context(const bbme_params *params, int width, int height, int 
             if (int rc = grid->alloc(P * own_blocks, what)) return rc;
         if (int rc = L.fix_list.alloc(P * own_blocks, what)) return rc;
         if (int rc = L.fix_count.alloc_zero(P * 64 / sizeof(uint32_t), what)) return rc;    // 64 bytes per pair
-        if (int rc = L.big[0].alloc(P * cells, what)) return rc;
-        if (int rc = L.big[1].alloc(P * cells, what)) return rc;
+        if (int rc = L.publish.alloc_zero(P * 64 / sizeof(uint32_t), what)) return rc;
+        if (int rc = L.big[0].alloc_zero(P * cells, what)) return rc;
+        if (int rc = L.big[1].alloc_zero(P * cells, what)) return rc;
         if (int rc = L.spiral.upload(packed, what)) return rc;
         // the speculative search of this level pads its workgroups to this much LDS (launch_search's lds_floor)
         const size_t spec_floor = l + 1 < nl ? c->tune.spec_lds_for(params->block_size[l + 1], l) : 0;
@@ -1542,8 +1595,14 @@ int bbme_get_level_planes_host(bbme_ctx *c, int level, uint8_t *image1, uint8_t 
 // bbme_estimate in the context's current direction (one captured graph per direction)
 static int run_pyramid(bbme_ctx *c)
 {
+    c->last_spec_levels = 0;
     if (c->profiling) { const int rc = profiled_pyramid(c); c->memo_block = 0; return rc; }
-    if (!c->tune.use_graph) { const int rc = enqueue_pyramid(c, c->tune.speculate); c->memo_block = 0; return rc; }
+    if (!c->tune.use_graph) {
+        const int rc = enqueue_pyramid(c, c->tune.speculate);
+        c->memo_block = 0;
+        c->last_spec_levels = c->spec_levels[c->direction];
+        return rc;
+    }
     hipGraphExec_t &exec = c->graph_exec[c->direction];
     if (!exec) {
         // the launch sequence is fixed (no host decisions inside), so capture it once
@@ -1572,6 +1631,7 @@ static int run_pyramid(bbme_ctx *c)
         for (Level &L : c->lv) { L.cur_grid = L.final_grid(); L.cur_block = 2; }
     }
     HIP_TRY(hipGraphLaunch(exec, c->stream));
+    c->last_spec_levels = c->spec_levels[c->direction];
     // after a pyramid the memo describes level 0 at its last memoised block size; a later stage call starts afresh
     c->memo_block = 0;
     return BBME_OK;
@@ -3113,6 +3173,20 @@ int bbme_last_sweep_passes(bbme_ctx *c, int *passes)
     passes[0] = (int)host[3];
     passes[1] = (int)host[4];
     if (host[5]) return bbme::fail(BBME_ERR_STATE, "a regulariser sweep hit its pass cap without converging");
+    return BBME_OK;
+}
+
+int bbme_fixup_counts(bbme_ctx *c, int pair, unsigned *counts, int n)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (!counts || n < 0) return bbme::fail(BBME_ERR_INVALID, "null output");
+    if (pair < 0 || pair >= c->batch) return bbme::fail(BBME_ERR_INVALID, "pair %d of %d", pair, c->batch);
+    HIP_TRY(hipSetDevice(c->device));
+    for (int l = 0; l < n; ++l) counts[l] = 0;
+    for (int l = 0; l < n && l < (int)c->lv.size(); ++l)
+        if (c->last_spec_levels >> l & 1u)
+            HIP_TRY(hipMemcpyAsync(&counts[l], c->lv[l].fix_count.get() + (size_t)pair * 16, sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
     return BBME_OK;
 }
 

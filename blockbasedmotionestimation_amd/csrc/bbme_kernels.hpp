@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "spec_grids.hpp"
+
 namespace bbme {
 
 typedef uint32_t mv_t;   // packed int16 (dx, dy)
@@ -75,12 +77,14 @@ __device__ __forceinline__ void shift_pair(SearchArgs &a, uint32_t p)
 // copyMVs (:828-843) as the search kernels see it: the MV of the coarse block covering pixel (i, j) of this level.
 // A block's search result depends on its prediction alone, which is what makes the search of level l speculable:
 //   kSearchSpeculative  runs beside the late sweeps of level l+1 (second stream), predicting from the grid as the two
-//                       sweeps at B_{l+1} left it, and records the coarse MV it used;
+//                       sweeps at B_{l+1} left it -- or from a newer one (newest_coarse_grid) -- and records the coarse MV it used;
 //   kSearchFixup        after level l+1 is final: a block whose recorded MV equals the final one (the top-left 2x2 cell
 //                       of the coarse block, which is all copyMVs reads) keeps its result, the others are searched again.
 // Either way every block ends with the result of a search from the final prediction: bit-exact by construction.
 enum { kSearchPlain = 0, kSearchSpeculative = 1, kSearchFixup = 2 };
-template <class Args>
+// LIVE: the grid may be written while this launch runs (newest_coarse_grid): one lane of the (one-wave) workgroup reads the cell
+// once, past the caches another XCD's sweep does not reach, and the wave goes on with that value.
+template <bool LIVE = false, class Args>
 __device__ __forceinline__ bool search_prediction(const Args &a, int i, int j, uint32_t bid, mv_t &m)
 {
     m = 0;
@@ -88,7 +92,12 @@ __device__ __forceinline__ bool search_prediction(const Args &a, int i, int j, u
         const int lg = 31 - __builtin_clz((unsigned)a.coarse_block);      // block sizes are powers of two (validate_params): no division
         const int ci = (i >> (lg + 1)) << lg;                              // (i / (2 B_{l+1})) * B_{l+1}, i >= 0
         const int cj = (j >> (lg + 1)) << lg;
-        m = a.coarse[(size_t)(ci >> a.coarse_cell_shift) * a.coarse_cols + (cj >> a.coarse_cell_shift)];
+        const mv_t *cell = a.coarse + (size_t)(ci >> a.coarse_cell_shift) * a.coarse_cols + (cj >> a.coarse_cell_shift);
+        if constexpr (LIVE) {
+            if (threadIdx.x == 0) m = __hip_atomic_load(cell, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            m = (mv_t)__builtin_amdgcn_readfirstlane((int)m);
+        } else
+            m = *cell;
     }
     if (a.mode == kSearchFixup && a.pred[bid] == m) return false;       // searched from this prediction already
     if (a.mode == kSearchSpeculative && threadIdx.x == 0) a.pred[bid] = m;
@@ -260,6 +269,12 @@ struct FastSearchArgs {
     int mode;
     mv_t *pred;
     uint32_t *fix_count;        // length of the fix-up list (zeroed by the speculative launch)
+    // speculative launch only (newest_coarse_grid): the coarser level's grids in the order its sweeps leave them (late[0] is
+    // `coarse`), the word in which its solver publishes how many of them are complete, and the test setting that takes the last
+    // entry whatever the word says.  late_n <= 1: every block predicts from `coarse`.
+    const uint32_t *late_word;
+    int late_n, late_force;
+    CoarseGrid late[kMaxCoarseGrids];
     mv_t *out;
     int cols;
     int pitch_dw;               // LDS window pitch in dwords (odd)
@@ -273,6 +288,38 @@ __device__ __forceinline__ void shift_pair(FastSearchArgs &a, uint32_t p)
     if (a.coarse) a.coarse += (size_t)p * a.s_coarse;
     a.pred += (size_t)p * a.s_pred; a.out += (size_t)p * a.s_out;
     a.fix_count += (size_t)p * 16u;
+    if (a.late_word) a.late_word += (size_t)p * 16u;
+}
+
+// A speculative search's block picks its prediction source when it STARTS: the newest grid of the coarser level that is
+// complete by then.  The level's solver stores k in late_word (release, agent scope) once the k-th sweep behind the fork is
+// done (RegArgs::publish; the sweep in front of the fork stores 0, so a replay never sees the previous step's count), one lane
+// reads the word once and the wave takes late[min(k, late_n - 1)].  No wait and no second look: whatever the block reads,
+// k_fixup_list compares the recorded MV with the final one and k_search_list searches the block again if they differ, so the
+// level ends as the search from the final prediction either way.  Why ANY outcome of the two reads is harmless:
+//   - an MV is one aligned dword: a load beside a store sees the old or the new value, never a mixture;
+//   - late[k] indexes inside its buffer whatever the buffer holds at that moment: small[0] holds (H/B)(W/B) cells and is read
+//     at that geometry only; big[] are sized for the level's finest grid, (H/2)(W/2) cells, and an entry of cell size 2^s
+//     reads below (H >> s)(W >> s) (fill_coarse_grids; tests/cpp/spec_grids_test.cpp).  They are zeroed at creation, so a grid
+//     no sweep has written yet reads as zero vectors;
+//   - whatever a grid buffer holds is an MV of this level or zero, and search_block_fast takes any MV: a prediction whose block
+//     leaves the image gives the zero vector (:304-310), every other window is staged with its bounds checked;
+//   - so a stale grid, one that a later sweep is rewriting (big[] ping-pong: entry k's buffer is written again by sweep
+//     k + 2, at half the cell size) or a word that lags can only put more blocks on the fix-up list.
+// The fix-up's comparison is the only correctness gate, and it is the one the search had before.
+// (`table`: the kernel's argument itself, which nothing writes -- the entry is then a scalar load at a run-time offset of the
+// argument segment; taken from the kernel's working copy `a` the table would live in scratch)
+__device__ __forceinline__ void newest_coarse_grid(FastSearchArgs &a, const FastSearchArgs &table, uint32_t pair)
+{
+    uint32_t k = 0;
+    if (threadIdx.x == 0) k = __hip_atomic_load(a.late_word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    k = (uint32_t)__builtin_amdgcn_readfirstlane((int)k);
+    const uint32_t last = (uint32_t)a.late_n - 1u;
+    k = a.late_force ? last : min(k, last);
+    const CoarseGrid g = table.late[k];
+    a.coarse = g.grid + (size_t)pair * g.stride;
+    a.coarse_cols = g.cols;
+    a.coarse_cell_shift = g.cell_shift;
 }
 
 // bid / cols without the (floating-point reciprocal) division sequence: one scalar multiply for a uniform bid
@@ -699,9 +746,10 @@ __device__ __forceinline__ void search_block_fast(const FastSearchArgs &a, uint3
 }
 
 template <int B, int W>
-__global__ __launch_bounds__(64 * W, (W == 1 && B <= 16 ? 5 : 1)) void k_search_fast(FastSearchArgs a)
+__global__ __launch_bounds__(64 * W, (W == 1 && B <= 16 ? 5 : 1)) void k_search_fast(const FastSearchArgs args)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t smem[];
+    FastSearchArgs a = args;
     shift_pair(a, blockIdx.y);
     // Workgroups are dealt round-robin over the 8 XCDs, each with a private L2.  Give every XCD a
     // contiguous eighth of the raster so that neighbouring macroblocks -- whose windows overlap by
@@ -712,7 +760,13 @@ __global__ __launch_bounds__(64 * W, (W == 1 && B <= 16 ? 5 : 1)) void k_search_
     if (bid >= (uint32_t)a.nblocks) return;
     mv_t m;                                                 // copyMVs (:828-843)
     const uint32_t brow = block_row(a, bid);
-    if (!search_prediction(a, (int)brow * B, (int)(bid - brow * (uint32_t)a.cols) * B, bid, m)) return;
+    const int i = (int)brow * B, j = (int)(bid - brow * (uint32_t)a.cols) * B;
+    bool live = false;
+    if constexpr (W == 1) live = a.mode == kSearchSpeculative && a.late_n > 1;     // (a speculative launch has one wave per block)
+    if (live) {
+        newest_coarse_grid(a, args, blockIdx.y);
+        (void)search_prediction<true>(a, i, j, bid, m);
+    } else if (!search_prediction(a, i, j, bid, m)) return;
     search_block_fast<B, W>(a, bid, m, smem);
 }
 
@@ -811,6 +865,10 @@ struct RegArgs {
     int lazy;                   // k_reg_pass1_strip, when a relaxation launch follows: blocks that need their images are not evaluated
                                 // but flagged (estimate = old value meanwhile) -- the relaxation's first round evaluates them, densely
     int share;                  // solver: a wave whose queue holds more than a round takes hands the surplus to idle waves of its workgroup
+    // the solver's last workgroup stores publish_value here when the sweep is complete (nullptr: nothing is stored): the
+    // speculative search beside the level's late sweeps picks its prediction source by it (newest_coarse_grid)
+    uint32_t *publish;          // pair 0's word, the others 16 words apart (not shifted by shift_pair: read once, in the solver's epilogue)
+    uint32_t publish_value;
     int stats;                  // 1: the solver's waves add their counts to counters[4], [7..12] -- stage calls only: several hundred
                                 // waves adding to the same few words is a queue at the memory side that the pyramid need not stand in
     // batch (blockIdx.y = pair): element strides from pair to pair of the per-pair buffers; counters: 64 words
@@ -2086,6 +2144,12 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
     __syncthreads();
     if (s_ticket != gridDim.x - 1) return;
     drain_lists<BS>(a, threadIdx.x, (int)blockDim.x);
+    if (a.publish) {                                          // the sweep is complete: every workgroup's stores were drained before its ticket
+        BBME_DRAIN();
+        __syncthreads();
+        if (threadIdx.x == 0)
+            __hip_atomic_store(a.publish + (size_t)blockIdx.y * 16u, a.publish_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+    }
 }
 
 // =======================================================================================

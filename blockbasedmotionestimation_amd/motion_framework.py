@@ -924,6 +924,13 @@ class MF:
     def stage_expand(self):
         _capi.check(self._lib.bbme_stage_expand(self._ctx))
 
+    def fixup_counts(self, pair=0):
+        """Blocks per level that the last estimate searched again behind a speculative search (bbme_fixup_counts): 0 for a level
+        whose search was not speculative.  Waits for the estimate."""
+        v = (C.c_uint * self.num_levels)()
+        _capi.check(self._lib.bbme_fixup_counts(self._ctx, pair, v, self.num_levels))
+        return list(v)
+
     def last_sweep_passes(self):
         v = (C.c_int * 2)()
         _capi.check(self._lib.bbme_last_sweep_passes(self._ctx, v))

@@ -242,8 +242,8 @@ int bbme_set_search_mode(bbme_ctx *ctx, int mode);
 enum { BBME_REG_EXACT = 0, BBME_REG_JACOBI = 1 };
 int bbme_set_regularizer_mode(bbme_ctx *ctx, int mode);
 /* Scheduling option (default on; BBME_SPECULATE=0 turns the default off): bbme_estimate starts the search of every level
- * but the coarsest on a second stream beside the coarser level's late regulariser sweeps, predicting from that level's grid
- * as it stands, and afterwards searches again the blocks whose prediction those sweeps changed.  Same field, bit for bit;
+ * but the coarsest on a second stream beside the coarser level's late regulariser sweeps, every block predicting from that
+ * level's newest complete grid when the block starts, and afterwards searches again the blocks whose prediction those sweeps changed.  Same field, bit for bit;
  * shorter single pairs (the late sweeps leave most of the chip idle).  Turn it off when several contexts keep the chip
  * busy anyway (sequences with pairs in flight). */
 int bbme_set_speculation(bbme_ctx *ctx, int enabled);
@@ -799,6 +799,10 @@ int bbme_stage_expand(bbme_ctx *ctx);
  * sweeps run through bbme_stage_regularize (hundreds of waves adding to the same words is a
  * queue at the memory side that bbme_estimate does not stand in); [3] and [5] always. */
 int bbme_sweep_stats(bbme_ctx *ctx, unsigned *stats16);
+/* Blocks per level that the last bbme_estimate searched again behind a speculative search (diagnostic; bbme_set_speculation):
+ * counts[l] for the levels l < n of pair `pair`, 0 for a level whose search was not speculative (the coarsest, levels below the
+ * speculation threshold or searched by the generic kernel, a profiled pass, speculation off).  Waits for the ctx stream. */
+int bbme_fixup_counts(bbme_ctx *ctx, int pair, unsigned *counts, int n);
 /* Fix-up passes the last sweep needed after its first full pass (diagnostic). */
 int bbme_last_sweep_passes(bbme_ctx *ctx, int *passes);
 
