@@ -15,6 +15,7 @@
 
 #include "bbme_internal.hpp"
 #include "bbme_kernels.hpp"
+#include "launch_plan.hpp"
 
 using namespace bbme;
 
@@ -108,8 +109,8 @@ struct DevEvent {
     operator hipEvent_t() const { return ev; }
 };
 
-struct Level {
-    int width = 0, height = 0, block = 0, search = 0, range = 0;
+struct Level : PlanLevel {                        // width, height, block, range and what the search plans give (launch_plan.hpp)
+    int search = 0;
     // Every padded plane of the level (pitch == width), one plane_stride apart, in ONE allocation.  A pair or batch context: the
     // image-1 planes of its pairs, then, from frame_step on, their image-2 planes.  A chain context: its pairs + 1 frame slots.
     // Either way pair p reads img1 + p * plane_stride and img2 + p * plane_stride, and the slack behind every plane is zero.
@@ -132,9 +133,7 @@ struct Level {
     DevBuf<uint32_t> spiral;                      // rank -> packed (dx, dy)
     int ncand = 0;
     int pitch_dw = 0;
-    size_t lds_bytes = 0;
-    // fast search kernel (block 8 / 16)
-    bool fast = false;
+    // fast search kernel (block 8 / 16 / 32)
     DevBuf<uint16_t> rank_of;
     int rank_pitch = 0;
     DevBuf<uint32_t> tasks, rounds;
@@ -142,119 +141,14 @@ struct Level {
     DevBuf<uint32_t> tasks2, rounds2;                 // the plan for two waves per macroblock (levels of few blocks)
     int nrounds2 = 0;
     DevBuf<uint2> lane_ranks, lane_ranks2;            // per plan: the ranks of every lane's candidates (FastSearchArgs::lane_ranks)
-    bool split_pays = false;                          // the two-wave plan is at least 20 % shorter per wave
-    int fast_pitch_dw = 0;
-    size_t fast_lds_bytes = 0;
     // batch: every per-pair buffer holds ctx->batch copies, pair p at p * stride elements (multiples of 64 elements)
     uint32_t plane_stride = 0;                        // img1 / img2, bytes (frame_step and every product with it: size_t)
     uint32_t small_stride = 0;                        // small[], pred, fix_list: words
     uint32_t big_stride = 0;                          // big[]: words
     uint32_t grid_stride(const mv_t *g) const { return (g == small[0] || g == small[1]) ? small_stride : big_stride; }
+    mv_t *grid(GridId g) const { return g == kSmall0 ? small[0] : g == kSmall1 ? small[1] : g == kBig0 ? big[0] : big[1]; }
+    GridId grid_id(const mv_t *g) const { return g == small[0] ? kSmall0 : g == small[1] ? kSmall1 : g == big[0] ? kBig0 : kBig1; }
 };
-
-// Everything the environment tunes, with its default.  Read once per context, at creation (read_tuning): never through
-// statics, so two contexts of a process may differ and a test may set a knob between them.
-struct Tuning {
-    int relax_steps = -1;                         // k_reg_iter launches per sweep; -1 = by grid size (BBME_RELAX_STEPS overrides)
-    bool split_forced = false;                    // threshold given in the environment: split whatever the plans' lengths (tests)
-    long long scan_fine_max = 140000;             // grids of at most this many blocks: scan segments of 4 flags (BBME_SCAN_FINE_MAX)
-    long long pass1_lanes_max = 140000;           // grids of at most this many blocks: pass 1 in the chain form (BBME_PASS1_LANES_MAX)
-    bool list_split = true;                       // two waves per listed block in the fix-up search of small levels; BBME_LIST_SPLIT
-    bool pass1_lazy = true;                       // pass 1 leaves its evaluations to a relaxation launch that follows it; BBME_PASS1_LAZY
-    int pass1_strip = -1;                         // the strip form of pass 1 at b <= 4 (k_reg_pass1_strip): -1 = batched contexts only; BBME_PASS1_STRIP
-    int split_blocks = 10000;                     // levels of at most this many macroblocks: two waves per block (BBME_SEARCH_SPLIT_BLOCKS)
-    int round_cap = 0;                            // > 0: test knob, the regulariser's waves give up after this many rounds
-    bool use_memo = true;                         // BBME_MEMO
-    int memo_min_block = 16;                      // sweeps at smaller blocks run without it (8: measured slower); BBME_MEMO_MIN_B
-    bool memo_forward = false;                    // BBME_MEMO_FORWARD (measured slower: off)
-    int local_rounds = 8;                         // k_reg_iter: heavy rounds of a tile per launch; BBME_LOCAL_ROUNDS
-    int wide_threshold = 16;                      // solver: queue length above which a round takes the throughput form; BBME_WIDE_THRESHOLD
-    int solve_waves = 4;                          // waves per solver workgroup (1, 2 or 4); BBME_SOLVE_WAVES
-    bool solve_share = true;                      // k_reg_solve: idle waves of a workgroup take a sibling's surplus; BBME_SOLVE_SHARE=0
-    int solve_wgs = 256;                          // most workgroups of k_reg_solve (4 independent waves each); r04: 256 measured 1.5 % ahead of 128 (one wave per SIMD)
-    int xcd_remap = 1;                            // XCD-aware block order in k_search_fast; BBME_XCD_REMAP
-    bool loose_plan = false;                      // the round-2 search plan without rim rounds; BBME_LOOSE_PLAN (set at all = on)
-    long long relax_min_blocks = 300000;          // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (launch_sweep)
-    int relax_max_b = 2, relax_s1 = 1, relax_s2 = 0;
-    bool force_generic_search = false;            // BBME_GENERIC_SEARCH=1: use k_search_generic everywhere
-    bool use_graph = true;                        // BBME_NO_GRAPH=1: eager launches
-    bool speculate = true;                        // overlap every level's search with the coarser level's late sweeps; BBME_SPECULATE
-    bool fork_both = false;                       // BBME_SPECULATE_BOTH_GRAPHS=1: both directions' graphs forked (bbme_ctx::graph_forked)
-    // a speculative search may keep at most this many of its (one-wave) workgroups on a CU: the rest of the CU's wave
-    // slots, registers and LDS (40 KB) stay free for the regulariser kernels it runs beside
-    // (r04, on the faster solver.  Behind a level of 16 x 16 blocks -- three late block sizes to hide the search behind -- 6-7 is
-    // best: cfg3 1.614 / 1.585 / 1.591 / 1.626 ms at 8 / 6 / 7 / 5.  Behind a level of 8 x 8 blocks the sweeps are over long
-    // before the search is, and any cap only delays it: cfg4 1.80 / 1.72 / 1.67 / 1.62 ms at 6 / 8 / 10 / 24 = uncapped.)
-    int spec_per_cu = 0;                          // BBME_SPEC_WGS_PER_CU; 0 = by the coarser level's block size (spec_lds_for)
-    int spec_per_cu_l0 = 0;                       // second value of BBME_SPEC_WGS_PER_CU="other,level0": the level-0 launch's own cap
-    // LDS per workgroup of a speculative search launch beside the late sweeps of `coarser_block`-sized level: the occupancy cap
-    size_t spec_lds_for(int coarser_block, int level = 1) const
-    {
-        // (r04: 7, not 6, since the level-0 search -- not the level-1 sweeps beside it, shorter now -- is what the level waits for:
-        //  cfg3 1.494 -> 1.470 ms; 8 and more cost the sweeps more than the search gains)
-        int per_cu = spec_per_cu > 0 ? spec_per_cu : (coarser_block >= 16 ? 7 : 24);
-        if (level == 0 && spec_per_cu_l0 > 0) per_cu = spec_per_cu_l0;
-        return ((size_t)(160 - 40) * 1024 / per_cu) / 256 * 256;
-    }
-    double spec_min_absdiffs = 8e9;               // levels with less search work are not speculated; BBME_SPEC_MIN_GABS
-    // where a speculative search's block takes its prediction from (newest_coarse_grid): 1 = the newest grid of the coarser level
-    // that is complete when the block starts; 0 = the grid at the fork, every block (A/B runs); 2 = test setting: the LAST grid
-    // of the table whatever is complete, so that blocks read grids that are unwritten, mid-write or of another geometry
-    int spec_late = 1;                            // BBME_SPEC_LATE
-    // the sweep at B the speculative search is forked behind: the first (with late predictions the blocks no longer depend on the
-    // grid at the fork; cfg4 1.547 -> 1.514 ms, cfg3 1.460 / 1.463: profiles/r18_late_prediction.txt) or, =0, the second.  Without
-    // late predictions (BBME_SPEC_LATE=0) always the second: behind the first, cfg3 loses 2 %
-    bool spec_fork_first = true;                  // BBME_SPEC_FORK_FIRST
-};
-
-const struct {
-    const char *name;
-    void (*parse)(const char *value, Tuning &t);  // the field(s) the variable sets, with its clamp
-} kKnobs[] = {
-    {"BBME_SOLVE_SHARE", [](const char *e, Tuning &t) { t.solve_share = atoi(e) != 0; }},
-    {"BBME_SOLVE_WGS", [](const char *e, Tuning &t) { t.solve_wgs = std::max(1, std::min(8192, atoi(e))); }},
-    {"BBME_RELAX_STEPS", [](const char *e, Tuning &t) { t.relax_steps = std::max(0, std::min(64, atoi(e))); }},
-    {"BBME_SOLVE_WAVES", [](const char *e, Tuning &t) { const int v = atoi(e); t.solve_waves = v <= 1 ? 1 : (v == 2 ? 2 : 4); }},
-    {"BBME_TEST_ROUND_CAP", [](const char *e, Tuning &t) { t.round_cap = std::max(0, atoi(e)); }},
-    {"BBME_PASS1_LANES_MAX", [](const char *e, Tuning &t) { t.pass1_lanes_max = atoll(e); }},
-    {"BBME_SCAN_FINE_MAX", [](const char *e, Tuning &t) { t.scan_fine_max = atoll(e); }},
-    {"BBME_PASS1_STRIP", [](const char *e, Tuning &t) { t.pass1_strip = atoi(e) != 0 ? 1 : 0; }},
-    {"BBME_LIST_SPLIT", [](const char *e, Tuning &t) { t.list_split = atoi(e) != 0; }},
-    {"BBME_PASS1_LAZY", [](const char *e, Tuning &t) { t.pass1_lazy = atoi(e) != 0; }},
-    {"BBME_SEARCH_SPLIT_BLOCKS", [](const char *e, Tuning &t) { t.split_blocks = std::max(0, atoi(e)); t.split_forced = true; }},
-    {"BBME_NO_GRAPH", [](const char *e, Tuning &t) { t.use_graph = atoi(e) == 0; }},
-    {"BBME_SPECULATE", [](const char *e, Tuning &t) { t.speculate = atoi(e) != 0; }},
-    {"BBME_SPECULATE_BOTH_GRAPHS", [](const char *e, Tuning &t) { t.fork_both = atoi(e) != 0; }},
-    {"BBME_SPEC_WGS_PER_CU", [](const char *e, Tuning &t) {                                   // "n" or "n,n0"
-         t.spec_per_cu = std::max(1, std::min(32, atoi(e)));
-         if (const char *comma = strchr(e, ',')) t.spec_per_cu_l0 = std::max(1, std::min(32, atoi(comma + 1)));
-     }},
-    {"BBME_SPEC_MIN_GABS", [](const char *e, Tuning &t) { t.spec_min_absdiffs = atof(e) * 1e9; }},
-    {"BBME_SPEC_LATE", [](const char *e, Tuning &t) { t.spec_late = std::max(0, std::min(2, atoi(e))); }},
-    {"BBME_SPEC_FORK_FIRST", [](const char *e, Tuning &t) { t.spec_fork_first = atoi(e) != 0; }},
-    {"BBME_GENERIC_SEARCH", [](const char *e, Tuning &t) { t.force_generic_search = atoi(e) != 0; }},
-    {"BBME_LOCAL_ROUNDS", [](const char *e, Tuning &t) { t.local_rounds = std::max(1, atoi(e)); }},
-    {"BBME_WIDE_THRESHOLD", [](const char *e, Tuning &t) { t.wide_threshold = std::max(4, atoi(e)); }},
-    {"BBME_MEMO", [](const char *e, Tuning &t) { t.use_memo = atoi(e) != 0; }},
-    {"BBME_MEMO_FORWARD", [](const char *e, Tuning &t) { t.memo_forward = atoi(e) != 0; }},
-    {"BBME_MEMO_MIN_B", [](const char *e, Tuning &t) { t.memo_min_block = std::max(8, atoi(e)); }},
-    {"BBME_XCD_REMAP", [](const char *e, Tuning &t) { t.xcd_remap = atoi(e) != 0; }},
-    {"BBME_LOOSE_PLAN", [](const char *, Tuning &t) { t.loose_plan = true; }},                // presence, whatever the value
-    {"BBME_RELAX_RULE", [](const char *e, Tuning &t) {                                        // leading fields; the rest keep their defaults
-         sscanf(e, "%lld,%d,%d,%d", &t.relax_min_blocks, &t.relax_max_b, &t.relax_s1, &t.relax_s2);
-     }},
-};
-
-Tuning read_tuning(int pairs)
-{
-    Tuning t;
-    // a batched context is throughput-bound (every launch carries several pairs): the chain form of pass 1, which trades
-    // instructions for latency, only pays on its small grids (24 pairs as 4 x 6: 53.7 -> 55.0 Mblocks/s)
-    if (pairs > 1) t.pass1_lanes_max = 40000;
-    for (const auto &k : kKnobs)
-        if (const char *e = getenv(k.name)) k.parse(e, t);
-    return t;
-}
 
 }  // namespace
 
@@ -562,17 +456,31 @@ int set_prediction_source(bbme_ctx *c, int level, int mode, Args &a)
     return BBME_OK;
 }
 
+// What the launch plan decides from (launch_plan.hpp): the levels' numbers, the context's modes and its knobs
+PlanInputs plan_inputs(const bbme_ctx *c)
+{
+    PlanInputs in;
+    in.lv.assign(c->lv.begin(), c->lv.end());
+    in.pairs = c->batch;
+    in.jacobi = c->jacobi; in.raster_search = c->raster_search; in.relax = c->relax;
+    in.tune = c->tune;
+    in.memo_blocks = c->memo_blocks;
+    return in;
+}
+
+static_assert(kPredictPlain == kSearchPlain && kPredictSpeculative == kSearchSpeculative && kPredictFixup == kSearchFixup, "prediction modes");
+
 // FastSearchArgs::late of the speculative launch of `level`: the coarser level's grids in the order the sweeps behind the fork
 // leave them (entry 0 is a.coarse, set_prediction_source), and the word those sweeps publish their number in (enqueue_pyramid).
-void set_late_grids(bbme_ctx *c, int level, FastSearchArgs &a)
+void set_late_grids(bbme_ctx *c, const SearchLaunch &s, FastSearchArgs &a)
 {
     a.late_word = nullptr; a.late_n = 0; a.late_force = 0;
-    if (a.mode != kSearchSpeculative || !a.coarse || c->tune.spec_late == 0) return;
-    const Level &C = c->lv[level + 1];
+    if (!s.late) return;
+    const Level &C = c->lv[s.level + 1];
     a.late_n = fill_coarse_grids(a.late, C.width, C.block, a.coarse == C.small[1], C.small[0], C.small[1], C.small_stride,
                                  C.big[0], C.big[1], C.big_stride);
     a.late_word = C.publish;
-    a.late_force = c->tune.spec_late == 2;
+    a.late_force = s.late_force;
 }
 
 // Level::tasks2 ..: the plan whose rounds have 128 strips, for two waves per macroblock
@@ -582,11 +490,9 @@ void use_two_wave_plan(FastSearchArgs &a, const Level &L)
     a.stage_rpp = 128u / ((uint32_t)(L.fast_pitch_dw + 3) / 4);
 }
 
-// `lds_floor`: dynamic LDS to ask for at least -- the speculative launch pads its workgroups so that only
-// ctx::spec_wgs_per_cu of them fit a CU and the regulariser's kernels beside it still find wave slots, registers and LDS.
-int launch_search_fast(bbme_ctx *c, int level, int mode, hipStream_t stream, size_t lds_floor)
+int launch_search_fast(bbme_ctx *c, const SearchLaunch &s, hipStream_t stream)
 {
-    Level &L = c->lv[level];
+    Level &L = c->lv[s.level];
     FastSearchArgs a{};
     a.image1 = c->plane1(L); a.image2 = c->plane2(L);
     a.width = L.width; a.height = L.height;
@@ -598,177 +504,119 @@ int launch_search_fast(bbme_ctx *c, int level, int mode, hipStream_t stream, siz
         a.stage_magic = (65536u + nch - 1) / nch;
         a.stage_rpp = 64u / nch;
     }
-    if (int rc = set_prediction_source(c, level, mode, a)) return rc;
-    set_late_grids(c, level, a);
+    if (int rc = set_prediction_source(c, s.level, s.mode, a)) return rc;
+    set_late_grids(c, s, a);
     a.out = L.small[0];
     a.cols = L.width / L.block;
     a.pitch_dw = L.fast_pitch_dw;
-    const int nblocks = (L.width / L.block) * (L.height / L.block);
+    const int nblocks = L.blocks_at(L.block);
     a.nblocks = nblocks;
     a.cols_magic = (uint64_t)nblocks * (uint64_t)a.cols < (1ull << 32) ? (uint32_t)(((1ull << 32) + (uint64_t)a.cols - 1) / (uint64_t)a.cols) : 0u;
     a.xcd_remap = c->tune.xcd_remap;
-    int grid = c->tune.xcd_remap ? ((nblocks + 7) / 8) * 8 : nblocks;
-    const size_t lds = std::max(L.fast_lds_bytes, lds_floor);
     a.fix_count = L.fix_count;
     a.s_fix_list = L.small_stride;
     const unsigned P = (unsigned)c->batch;
-    // a level with fewer macroblocks than the chip has SIMDs: one wave per block leaves most SIMDs idle and every busy one
-    // with a single wave, so the launch lasts as long as one block does -- two waves share each block then
-    const bool split = L.tasks2 && nblocks <= c->tune.split_blocks && (L.split_pays || c->tune.split_forced);
-    bool two_waves = mode == kSearchPlain && split;
-    const bool list = mode == kSearchFixup && a.coarse;
+    const bool list = s.kernel == SearchKernel::List;
     if (list) {
-        // list the blocks whose prediction changed, then search those (k_fixup_list, k_search_list)
-        a.mode = kSearchPlain;
-        hipLaunchKernelGGL(k_fixup_list, dim3((nblocks + 255) / 256, P), dim3(256), 0, stream, a, L.block, L.fix_count.get(), L.fix_list.get());
-        grid = std::max(64, nblocks / 4);
-        // two waves per listed block on the levels that are searched with two waves per block anyway (r04): the list is ONE
-        // generation of waves, and on a level of 8 160 blocks (~1 200 listed) halves fill the chip where wholes leave three SIMDs
-        // in four idle -- 30.4 -> 24.8 us.  Level 0 (~5 000 listed) stays with one wave per block: at two, the 123 registers of
-        // the 128-lane form allow four waves per SIMD, 10 000 halves are two and a half generations, 58.8 -> 65.8 us.
-        two_waves = c->tune.list_split && split;
+        a.mode = kSearchPlain;                               // k_search_list searches what k_fixup_list has compared and listed
+        hipLaunchKernelGGL(k_fixup_list, dim3(s.list_grid, P), dim3(256), 0, stream, a, L.block, L.fix_count.get(), L.fix_list.get());
     }
-    if (two_waves) use_two_wave_plan(a, L);
+    if (s.waves == 2) use_two_wave_plan(a, L);
     // the one launch site: the listed blocks (k_search_list) or the whole level (k_search_fast), W waves per block
     return with_block<8, 16, 32>(L.block, [&](auto B) {
         auto launch = [&](auto W) {
             constexpr int kB = decltype(B)::value, kW = decltype(W)::value;
-            if (list) hipLaunchKernelGGL((k_search_list<kB, kW>), dim3(grid, P), dim3(64 * kW), lds, stream, a, L.fix_count.get(), L.fix_list.get());
-            else hipLaunchKernelGGL((k_search_fast<kB, kW>), dim3(grid, P), dim3(64 * kW), lds, stream, a);
+            if (list) hipLaunchKernelGGL((k_search_list<kB, kW>), dim3(s.grid, P), dim3(64 * kW), s.lds, stream, a, L.fix_count.get(), L.fix_list.get());
+            else hipLaunchKernelGGL((k_search_fast<kB, kW>), dim3(s.grid, P), dim3(64 * kW), s.lds, stream, a);
         };
-        if (two_waves) launch(std::integral_constant<int, 2>{});
+        if (s.waves == 2) launch(std::integral_constant<int, 2>{});
         else launch(std::integral_constant<int, 1>{});
         HIP_TRY(hipGetLastError());
         return (int)BBME_OK;
     });
 }
 
-int launch_search(bbme_ctx *c, int level, int mode = kSearchPlain, hipStream_t stream = nullptr, size_t lds_floor = 0)
+int launch_search(bbme_ctx *c, const SearchLaunch &s)
 {
-    Level &L = c->lv[level];
-    if (!stream) stream = c->stream;
+    Level &L = c->lv[s.level];
+    const hipStream_t stream = s.side_stream ? c->side_stream : c->stream;
     int rc;
-    if (L.fast && !c->tune.force_generic_search && !c->raster_search) {
-        rc = launch_search_fast(c, level, mode, stream, lds_floor);
+    if (s.kernel != SearchKernel::Generic) {
+        rc = launch_search_fast(c, s, stream);
     } else {
         SearchArgs a{};
         a.image1 = c->plane1(L); a.image2 = c->plane2(L);
         a.width = L.width; a.height = L.height;
         a.range = L.range; a.ncand = L.ncand; a.spiral = L.spiral;
         a.raster = c->raster_search ? 1 : 0;
-        if ((rc = set_prediction_source(c, level, mode, a))) return rc;
+        if ((rc = set_prediction_source(c, s.level, s.mode, a))) return rc;
         a.out = L.small[0];
         a.cols = L.width / L.block;
         a.pitch_dw = L.pitch_dw;
-        const int nblocks = (L.width / L.block) * (L.height / L.block);
-        const size_t lds = std::max(L.lds_bytes, lds_floor);
         rc = with_block<2, 4, 8, 16, 32, 64>(L.block, [&](auto B) {
-            hipLaunchKernelGGL(k_search_generic<B()>, dim3(nblocks, c->batch), dim3(64), lds, stream, a);
+            hipLaunchKernelGGL(k_search_generic<B()>, dim3(s.grid, c->batch), dim3(64), s.lds, stream, a);
             HIP_TRY(hipGetLastError());
             return (int)BBME_OK;
         });
     }
-    if (rc == BBME_OK && mode != kSearchSpeculative) { L.cur_grid = L.small[0]; L.cur_block = L.block; }
+    if (rc == BBME_OK && s.mode != kSearchSpeculative) { L.cur_grid = L.small[0]; L.cur_block = L.block; }
     return rc;
 }
 
 template <int BS>
-void launch_sweep_t(RegArgs a, uint8_t *const (&flags)[2], int relax_steps, bool jacobi, const Tuning &t, unsigned P, hipStream_t s)
+void launch_sweep_t(RegArgs a, const SweepLaunch &s, uint8_t *const (&flags)[2], unsigned P, hipStream_t st)
 {
-    const int solve_waves = t.solve_waves;
-    constexpr int LPB = RegCfg<BS>::LPB;
-    const long long blocks = (long long)a.rows * a.cols;
-    const int grid1 = (int)((blocks * LPB + 255) / 256);
-    // a multiple of 8 workgroups: one share per XCD (k_reg_solve's bands)
-    const int grid2 = (int)((std::min<long long>(t.solve_wgs, (blocks + 63) / 64) + 7) / 8 * 8);
     // pass 1 marks flags[0]; relaxation step i consumes flags[i & 1] and marks the other; the solver
     // consumes what the last step marked.  Every flag is zero again afterwards.
-    // grids up to ~130 000 blocks: the chain form of pass 1 (a third of the instructions per wave; 16 lanes per block fill the
-    // chip from ~32 000 blocks on, and it still wins up to four times that: 1.815 -> 1.78 ms per cfg3 pair; slower from 500 000)
-    auto pass1 = [&]() {
-        if constexpr (BS >= 8) {
-            if (a.memo) {                                  // (launch_sweep hands a memo only to sweeps whose pass 1 has the chain form)
-                hipLaunchKernelGGL((k_reg_pass1_lanes<BS, true>), dim3((unsigned)((blocks * 16 + 255) / 256), P), dim3(256), 0, s, a);
-                return;
-            }
-        }
-        if (BS <= 16 && blocks <= t.pass1_lanes_max)               // (b >= 32: a lane would walk 32+ rows -- 13 against 6 us at b = 32)
-            hipLaunchKernelGGL(k_reg_pass1_lanes<BS>, dim3((unsigned)((blocks * 16 + 255) / 256), P), dim3(256), 0, s, a);
-        else {
-            if constexpr (BS <= 4) {
-                // the large grids of small blocks in a BATCHED context: strips of four blocks per lane, the blocks that need their
-                // images listed per wave and worked off densely.  A third fewer vector instructions per pair -- which a batch,
-                // throughput-bound, turns into time (24 pairs as 4 x 6: 60.0 -> 62.3 Mblocks/s) -- in a quarter of the waves, each of
-                // which now walks its list pass after pass -- which a single pair, latency-bound, pays for (level 0, b = 4: 15.8 ->
-                // 53 us; 1.563 -> 1.657 ms per step).  BBME_PASS1_STRIP=0 / 1 forces it off / on.
-                // ... and, for any context, the sweeps with a relaxation launch behind pass 1: the strip test alone (level 0: 5.1 us at
-                // b = 4, 6.5 at b = 2, against 15.5 / 18.4 for the whole of k_reg_pass1), the blocks that need their images flagged for
-                // the relaxation's first round (RegArgs::lazy)
-                a.lazy = (t.pass1_lazy && relax_steps > 0 && a.flag_next != nullptr) ? 1 : 0;
-                const bool strip_form = a.lazy || (t.pass1_strip < 0 ? P > 1 : t.pass1_strip != 0);
-                if (strip_form && a.cols % 4 == 0 && a.cols >= 12) {
-                    hipLaunchKernelGGL(k_reg_pass1_strip<BS>, dim3((unsigned)((blocks / 4 + 255) / 256), P), dim3(256), 0, s, a);
-                    return;
-                }
-            }
-            a.lazy = 0;
-            hipLaunchKernelGGL(k_reg_pass1<BS>, dim3(grid1, P), dim3(256), 0, s, a);
-        }
-    };
-    if (jacobi) {
-        // opt-in, NOT the reference's field: every block against the field as the previous sweep left it, and no more
-        a.flag_cur = nullptr; a.flag_next = nullptr;
-        pass1();
-        return;
+    a.flag_cur = nullptr; a.flag_next = s.solve ? flags[0] : nullptr;
+    a.lazy = s.lazy ? 1 : 0;
+    const dim3 grid1(s.pass1_grid, P);
+    switch (s.pass1) {
+    case Pass1::ChainMemo:
+        if constexpr (BS >= 8) hipLaunchKernelGGL((k_reg_pass1_lanes<BS, true>), grid1, dim3(256), 0, st, a);
+        break;
+    case Pass1::Chain: hipLaunchKernelGGL(k_reg_pass1_lanes<BS>, grid1, dim3(256), 0, st, a); break;
+    case Pass1::Strip:
+        if constexpr (BS <= 4) hipLaunchKernelGGL(k_reg_pass1_strip<BS>, grid1, dim3(256), 0, st, a);
+        break;
+    case Pass1::Plain: hipLaunchKernelGGL(k_reg_pass1<BS>, grid1, dim3(256), 0, st, a); break;
     }
-    a.flag_cur = nullptr; a.flag_next = flags[0];
-    pass1();
+    if (!s.solve) return;
     int cur = 0;
-    for (int i = 0; i < relax_steps; ++i, cur ^= 1) {
+    for (int i = 0; i < s.relax_steps; ++i, cur ^= 1) {
         a.flag_cur = flags[cur]; a.flag_next = flags[cur ^ 1];
-        constexpr int T = RegIter<BS>::T;
-        const unsigned tiles = (unsigned)(((a.cols + T - 1) / T) * ((a.rows + T - 1) / T));
-        hipLaunchKernelGGL(k_reg_iter<BS>, dim3(tiles, P), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_reg_iter<BS>, dim3(s.relax_tiles, P), dim3(256), 0, st, a);
     }
     a.flag_cur = flags[cur]; a.flag_next = nullptr;
-    // small grids: scan segments of 4 flags, so that the stale blocks of a row are dealt to four times as many waves
     a.memo_init = 0;                                       // pass 1 has written every slot
-    if constexpr (BS >= 8) {
-        if (a.memo) {
-            if (blocks <= t.scan_fine_max) hipLaunchKernelGGL((k_reg_solve<BS, 4, true>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
-            else hipLaunchKernelGGL((k_reg_solve<BS, 16, true>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
-            return;
+    const dim3 grid2(s.solve_grid, P), waves(64 * s.solve_waves);
+    auto solve = [&](auto SEG) {
+        if constexpr (BS >= 8) {
+            if (s.memo) { hipLaunchKernelGGL((k_reg_solve<BS, SEG(), true>), grid2, waves, 0, st, a); return; }
         }
-    }
-    if (blocks <= t.scan_fine_max) hipLaunchKernelGGL((k_reg_solve<BS, 4>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
-    else hipLaunchKernelGGL((k_reg_solve<BS, 16>), dim3(grid2, P), dim3(64 * solve_waves), 0, s, a);
+        hipLaunchKernelGGL((k_reg_solve<BS, SEG()>), grid2, waves, 0, st, a);
+    };
+    if (s.solve_segment == 4) solve(std::integral_constant<int, 4>{});
+    else solve(std::integral_constant<int, 16>{});
 }
 
-// `publish`: the word the sweep's solver stores `publish_value` in when the sweep is complete (enqueue_pyramid), or nullptr
-int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false, uint32_t *publish = nullptr, uint32_t publish_value = 0)
+// One sweep on the level's current grid, which must be the one the entry was planned on
+int launch_sweep(bbme_ctx *c, const SweepLaunch &s, bool stats = false)
 {
+    const int level = s.level, b = s.block;
     Level &L = c->lv[level];
-    if (mult < 1) return bbme::fail(BBME_ERR_INVALID, "lambda multiplier %d", mult);
-    if (b < 2 || b > L.block || (b & (b - 1)))
-        return bbme::fail(BBME_ERR_INVALID, "block %d is not a power of two in 2..%d", b, L.block);
+    if (L.cur_block != b << s.old_shift || L.cur_grid != L.grid(s.from))
+        return bbme::fail(BBME_ERR_STATE, "level %d grid is at block size %d, cannot sweep at %d",
+                          level, L.cur_block, b);
     RegArgs a{};
-    if (L.cur_block == b) a.old_shift = 0;
-    else if (L.cur_block == 2 * b) a.old_shift = 1;
-    else return bbme::fail(BBME_ERR_STATE, "level %d grid is at block size %d, cannot sweep at %d",
-                           level, L.cur_block, b);
+    a.old_shift = s.old_shift;
     a.image1 = c->plane1(L); a.image2 = c->plane2(L);
     a.width = L.width; a.height = L.height;
     a.rows = L.height / b; a.cols = L.width / b;
     a.old_grid = L.cur_grid;
     a.old_cols = a.cols >> a.old_shift;
-    // sweeps at the level's own block size ping-pong in small[], the others in big[] (see Level)
-    const DevBuf<mv_t> *pool = (b == L.block) ? L.small : L.big;
-    a.est = (L.cur_grid == pool[0]) ? pool[1] : pool[0];
-    // lambda = (float)(B/2), doubled at every halving (motion_framework.cpp:73,95,151); times
-    // (float)lambda_multiplier as at :607
-    float lambda = (float)(L.block / 2);
-    for (int s = L.block; s > b; s >>= 1) lambda = lambda * 2;
-    a.lambda_mult = lambda * (float)mult;
+    a.est = L.grid(s.to);
+    a.lambda_mult = s.lambda_mult;
     a.list0 = c->list[0]; a.list1 = c->list[1];
     a.own = c->own;
     a.own_pitch = c->own_pitch;
@@ -776,41 +624,21 @@ int launch_sweep(bbme_ctx *c, int level, int b, int mult, bool stats = false, ui
     a.s_list = c->list_stride; a.s_own = c->own_stride; a.s_flag = (uint32_t)c->flag_bytes;
     a.local_rounds = c->tune.local_rounds;
     a.wide_threshold = (uint32_t)c->tune.wide_threshold;
-    // every round of a wave either empties part of its queue or follows a real change, and a change can only travel
-    // along the raster dependency chain (< 2 * rows + cols blocks): the cap is an exit every wave reaches even if
-    // that reasoning were wrong; hitting it raises counters[5] and the result is refused (BBME_ERR_STATE)
-    a.round_cap = c->tune.round_cap > 0 ? (uint32_t)c->tune.round_cap : 64u * (uint32_t)(2 * a.rows + a.cols + 16);
+    a.round_cap = s.round_cap;
     a.counters = c->counters;
     a.stats = stats ? 1 : 0;
     a.share = c->tune.solve_share ? 1 : 0;
-    a.publish = publish; a.publish_value = publish_value;
-    // the SAD memo: sweeps at b >= 8 whose pass 1 runs in the chain form (it is what fills the slots); the first sweep at a
-    // (level, block size) finds nothing in it and rewrites every slot
-    const long long nblk_memo = (long long)a.rows * a.cols;
-    if (c->tune.use_memo && c->memo && !c->jacobi && b >= c->tune.memo_min_block && nblk_memo <= c->tune.pass1_lanes_max && (size_t)nblk_memo <= c->memo_blocks &&
-        L.width <= 8192 && L.height <= 8192) {             // (group_sads packs a vector into 2 x 14 bits)
+    a.publish = s.publish >= 0 ? L.publish.get() : nullptr; a.publish_value = s.publish >= 0 ? (uint32_t)s.publish : 0u;
+    if (s.memo) {
         a.memo = c->memo;
         a.s_memo = c->memo_stride;
         a.memo_init = !(c->memo_level == level && c->memo_block == b);
         a.memo_forward = c->tune.memo_forward ? 1 : 0;
         c->memo_level = level; c->memo_block = b;
     }
-    // relaxation launches (k_reg_iter, 8 local rounds per tile): one more launch (>= 5 us), which only the sweeps with
-    // heavy first generations repay -- measured on cfg3 / cfg4 / cfg2: large grids of small blocks, one launch per sweep
-    const long long nblk = (long long)a.rows * a.cols;
-    int steps = c->tune.relax_steps;
-    if (steps < 0) {
-        // BBME_RELAX_RULE="min_blocks,max_b,steps_first,steps_second" (Tuning)
-        // (r03: no relaxation launch in front of the second sweep at a block size -- it changes little, and the launch cost more
-        // than it took off the solver: 1.760 -> 1.735 ms per cfg3 pair; r04: nor at 4 x 4 -- with the memo-less solver of this
-        // round the chain form takes those sweeps' first generations faster than a 40 us launch does: cfg3 1.566 -> 1.547 ms,
-        // cfg4 1.605 -> 1.585 ms, interleaved medians of 5 / 4 runs; and, once the solver's waves shared their queues, only on
-        // grids of >= 300 000 blocks: cfg3 1.523 -> 1.496, cfg2 0.699 -> 0.680, cfg4 1.611 -> 1.603, reference literals 1.336 -> 1.331)
-        steps = (c->relax && nblk >= c->tune.relax_min_blocks && b <= c->tune.relax_max_b) ? (mult == 1 ? c->tune.relax_s1 : c->tune.relax_s2) : 0;
-    }
     uint8_t *const flags[2] = {c->flags[0], c->flags[1]};
     if (int rc = with_block<2, 4, 8, 16, 32, 64>(b, [&](auto B) {
-            launch_sweep_t<B()>(a, flags, steps, c->jacobi, c->tune, (unsigned)c->batch, c->stream);
+            launch_sweep_t<B()>(a, s, flags, (unsigned)c->batch, c->stream);
             HIP_TRY(hipGetLastError());
             return (int)BBME_OK;
         })) return rc;
@@ -831,100 +659,83 @@ int launch_expand(bbme_ctx *c)
     return BBME_OK;
 }
 
-// A speculative search pays its fork, its fix-up launches and the stretch it puts on the sweeps beside it only when the
-// search it hides is long: levels below ~8 G abs-diffs (~90 us) are searched in line (measured: cfg2, cfg1 and the reference's
-// literals lose 3-12 % when every level is speculated; cfg3 / cfg4 gain 8-10 % from their two largest levels).
-bool worth_speculating(const bbme_ctx *c, int level)
+// Enqueues plan_pyramid's steps (launch_plan.hpp) on the context's streams.  `section(kind, level)` is called behind every search
+// (kind 0), behind the last sweep of every level (1) and behind the expansion (2): the profiled path marks its events there.
+// `spec_levels`: the levels whose search the sequence speculates (bbme_ctx::spec_levels).
+template <class Section>
+int walk_pyramid(bbme_ctx *c, bool speculate, uint32_t *spec_levels, Section &&section)
 {
-    if (c->jacobi) return false;                     // Jacobi sweeps are too short to hide a search behind
-    const Level &L = c->lv[level];
-    const double side = 2.0 * L.range + 1.0;
-    const double absdiffs = (double)(L.width / L.block) * (L.height / L.block) * side * side * L.block * L.block;
-    return absdiffs >= c->tune.spec_min_absdiffs;
-}
-
-// The level loop of MF::calcMotionBlockMatching (:115-206).  With `speculate`, the search of level l-1 is started on a
-// second stream as soon as level l has finished the first sweep at its own block size (Tuning::spec_fork_first), and runs
-// beside the level's remaining sweeps (which are latency-bound and leave most of the chip idle); when the level is final, a fix-up launch
-// searches again the blocks whose prediction those sweeps changed (search_prediction, bbme_kernels.hpp).
-// The sweep in front of the fork publishes 0 in the level's word and every later sweep of the level its number, 1, 2, ...
-// (RegArgs::publish): the speculative search's blocks choose their prediction source by it (newest_coarse_grid).  The 0 is
-// stored before the fork in every replay, so no search sees the count of the step before.
-int enqueue_pyramid(bbme_ctx *c, bool speculate)
-{
-    const int nl = (int)c->lv.size();
-    if (speculate && nl > 1 && !c->side_stream) {       // only contexts that speculate hold a second stream (hardware queue)
+    const PlanInputs in = plan_inputs(c);
+    const PyramidPlan plan = plan_pyramid(in, speculate);
+    if (speculate && in.lv.size() > 1 && !c->side_stream) {   // only contexts that speculate hold a second stream (hardware queue)
         // lowest dispatch priority: the regulariser's workgroups on the main stream go first whenever both have some ready
         int lo = 0, hi = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&lo, &hi));
         HIP_TRY(hipStreamCreateWithPriority(&c->side_stream, hipStreamNonBlocking, lo));
     }
-    bool speculated = false;
     c->memo_block = 0;                                  // a captured launch sequence must not depend on what ran before it
-    c->spec_levels[c->direction] = 0;
-    for (int l = nl - 1; l >= 0; --l) {
-        if (speculated) {
+    *spec_levels = plan.spec_levels;
+    for (size_t i = 0; i < plan.steps.size(); ++i) {
+        const Step &s = plan.steps[i];
+        Level &L = c->lv[s.level];
+        switch (s.kind) {
+        case Step::JoinFixup:
             HIP_TRY(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            if (int rc = launch_search(c, l, kSearchFixup)) return rc;
-        } else if (int rc = launch_search(c, l)) return rc;
-        speculated = false;
-        Level &L = c->lv[l];
-        const bool fork_here = speculate && l > 0 && L.block > 2 && worth_speculating(c, l - 1);
-        const int fork_mult = c->tune.spec_fork_first && c->tune.spec_late ? 1 : 2;     // the sweep at B the search of level l - 1 is forked behind
-        uint32_t *const word = fork_here && c->tune.spec_late ? L.publish.get() : nullptr;
-        uint32_t behind_fork = 0;                                  // sweeps of the level enqueued behind the fork
-        CoarseGrid table[kMaxCoarseGrids];                         // what set_late_grids hands the search: checked against the sweeps
-        const int table_n = fill_coarse_grids(table, L.width, L.block, fork_mult == 1, L.small[0], L.small[1], L.small_stride,
-                                              L.big[0], L.big[1], L.big_stride);
-        for (int b = L.block; b > 1; b >>= 1) {                    // while (block_size > 1) :141
-            for (int mult = 1; mult <= 2; ++mult) {                // lambda_multiplier = l + 1 :145
-                const bool counts = speculated || (b == L.block && mult == fork_mult);
-                if (int rc = launch_sweep(c, l, b, mult, false, counts ? word : nullptr, behind_fork)) return rc;
-                if (counts && word && ((int)behind_fork >= table_n || L.cur_grid != table[behind_fork].grid || L.cur_block != 1 << table[behind_fork].cell_shift))
-                    return bbme::fail(BBME_ERR_STATE, "level %d: sweep %u behind the fork is not entry %u of the coarse grid table", l, behind_fork, behind_fork);
-                if (speculated) ++behind_fork;
-                if (fork_here && b == L.block && mult == fork_mult) {
-                    HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
-                    HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
-                    if (int rc = launch_search(c, l - 1, kSearchSpeculative, c->side_stream, c->tune.spec_lds_for(L.block, l - 1))) return rc;
-                    HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
-                    speculated = true;
-                    behind_fork = 1;
-                    c->spec_levels[c->direction] |= 1u << (l - 1);
-                }
+            [[fallthrough]];
+        case Step::Search:
+            if (int rc = launch_search(c, s.search)) return rc;
+            if (int rc = section(0, s.level)) return rc;
+            break;
+        case Step::ForkSearch:
+            HIP_TRY(hipEventRecord(c->ev_fork, c->stream));
+            HIP_TRY(hipStreamWaitEvent(c->side_stream, c->ev_fork, 0));
+            if (int rc = launch_search(c, s.search)) return rc;
+            HIP_TRY(hipEventRecord(c->ev_join, c->side_stream));
+            break;
+        case Step::Sweep: {
+            const SweepLaunch &w = s.sweep;
+            if (int rc = launch_sweep(c, w)) return rc;
+            if (w.publish >= 0) {                       // what set_late_grids hands the search: checked against the sweeps
+                CoarseGrid table[kMaxCoarseGrids];
+                const int n = fill_coarse_grids(table, L.width, L.block, fork_mult(c->tune) == 1, L.small[0], L.small[1], L.small_stride,
+                                                L.big[0], L.big[1], L.big_stride);
+                if (w.publish >= n || L.cur_grid != table[w.publish].grid || L.cur_block != 1 << table[w.publish].cell_shift)
+                    return bbme::fail(BBME_ERR_STATE, "level %d: sweep %u behind the fork is not entry %u of the coarse grid table", s.level, (unsigned)w.publish, (unsigned)w.publish);
             }
+            if (plan.steps[i + 1].kind != Step::Sweep && plan.steps[i + 1].kind != Step::ForkSearch)
+                if (int rc = section(1, s.level)) return rc;
+            break;
+        }
+        case Step::Expand:
+            if (int rc = launch_expand(c)) return rc;
+            if (int rc = section(2, 0)) return rc;
+            break;
         }
     }
-    return launch_expand(c);
+    return BBME_OK;
+}
+
+int enqueue_pyramid(bbme_ctx *c, bool speculate)
+{
+    return walk_pyramid(c, speculate, &c->spec_levels[c->direction], [](int, int) { return (int)BBME_OK; });
 }
 
 int profiled_pyramid(bbme_ctx *c)
 {
-    // eager launches with events between sections (rank-0 diagnostics; not the timed bench path)
+    // eager launches, speculation off, with events between sections (rank-0 diagnostics; not the timed bench path)
     std::vector<DevEvent> ev;
-    auto mark = [&]() -> int {
+    std::vector<int> kind;   // 0 search, 1 reg, 2 expand ; section i lies between ev[i] and ev[i+1]
+    std::vector<int> lvl;
+    auto mark = [&](int k, int l) -> int {
         ev.emplace_back();
         HIP_TRY(hipEventCreate(&ev.back().ev));
         HIP_TRY(hipEventRecord(ev.back(), c->stream));
+        if (k >= 0) { kind.push_back(k); lvl.push_back(l); }
         return BBME_OK;
     };
-    std::vector<int> kind;   // 0 search, 1 reg, 2 expand ; section i lies between ev[i] and ev[i+1]
-    std::vector<int> lvl;
-    if (int rc = mark()) return rc;
-    c->memo_block = 0;
-    for (int l = (int)c->lv.size() - 1; l >= 0; --l) {
-        if (int rc = launch_search(c, l)) return rc;
-        if (int rc = mark()) return rc;
-        kind.push_back(0); lvl.push_back(l);
-        for (int b = c->lv[l].block; b > 1; b >>= 1)
-            for (int mult = 1; mult <= 2; ++mult)
-                if (int rc = launch_sweep(c, l, b, mult)) return rc;
-        if (int rc = mark()) return rc;
-        kind.push_back(1); lvl.push_back(l);
-    }
-    if (int rc = launch_expand(c)) return rc;
-    if (int rc = mark()) return rc;
-    kind.push_back(2); lvl.push_back(0);
+    if (int rc = mark(-1, 0)) return rc;
+    uint32_t none = 0;
+    if (int rc = walk_pyramid(c, false, &none, mark)) return rc;
     HIP_TRY(hipStreamSynchronize(c->stream));
     c->t_search = c->t_reg = c->t_expand = c->t_search0 = 0;
     for (size_t i = 0; i < kind.size(); ++i) {
@@ -1007,15 +818,10 @@ static int create_context(const bbme_params *params, int width, int height, int 
         snprintf(what_plan, sizeof what_plan, "search plan of level %d", l);
         L.width = g.padded_width >> l; L.height = g.padded_height >> l;
         L.block = params->block_size[l]; L.search = params->search_size[l];
-        // the memo serves the sweeps at b >= memo_min_block whose grid the chain-form pass 1 takes: room for the largest of them
-        for (int b = c->tune.memo_min_block; b <= L.block; b <<= 1) {
-            const size_t nb = (size_t)(L.width / b) * (L.height / b);
-            if ((long long)nb <= c->tune.pass1_lanes_max) { c->memo_blocks = std::max(c->memo_blocks, nb); break; }
-        }
         SpiralTable sp = build_spiral(L.search, L.block);
         L.range = sp.range; L.ncand = (int)sp.dx.size();
-        L.pitch_dw = (L.block + 2 * L.range) / 4 + 2;
-        L.lds_bytes = ((size_t)(L.block + 2 * L.range) * L.pitch_dw + (size_t)L.block * L.block / 4) * 4;
+        L.pitch_dw = generic_pitch_dw(L.block, L.range);
+        L.lds_bytes = generic_lds_bytes(L.block, L.range);
         const size_t plane = round64((size_t)L.width * L.height + 64) + 192;   // slack: row_sad may touch 3 bytes past the end
         const size_t cells = round64((size_t)(L.width / 2) * (L.height / 2));
         const size_t own_blocks = round64((size_t)(L.width / L.block) * (L.height / L.block));
@@ -1037,9 +843,9 @@ static int create_context(const bbme_params *params, int width, int height, int 
         if (int rc = L.big[0].alloc_zero(P * cells, what)) return rc;
         if (int rc = L.big[1].alloc_zero(P * cells, what)) return rc;
         if (int rc = L.spiral.upload(packed, what)) return rc;
-        // the speculative search of this level pads its workgroups to this much LDS (launch_search's lds_floor)
-        const size_t spec_floor = l + 1 < nl ? c->tune.spec_lds_for(params->block_size[l + 1], l) : 0;
-        if (!((L.block == 8 || L.block == 16 || L.block == 32) && L.range <= 63)) {
+        // a speculative search of this level runs beside the sweeps of the next coarser one and pads its workgroups (search_lds_bytes)
+        const int coarser_block = l + 1 < nl ? params->block_size[l + 1] : 0;
+        if (!fast_kernel_serves(L.block, L.range)) {
             // the generic kernel (block 4 / 64, or a range beyond the strip kernel's packed keys): its window may need more LDS
             // than a kernel gets by default (raise_lds_limit below)
             if (L.lds_bytes > 160 * 1024)
@@ -1052,12 +858,9 @@ static int create_context(const bbme_params *params, int width, int height, int 
             L.rank_pitch = sp.rank_pitch;
             L.nrounds = (int)plan.rounds.size();
             L.fast_pitch_dw = plan.pitch_dw;
-            // the window (+ for B <= 16 a copy of the block, 16-byte aligned, for the rim rounds of the tight plan)
-            L.fast_lds_bytes = (((size_t)(L.block + 2 * L.range) * plan.pitch_dw + 3) & ~(size_t)3) * 4 + (size_t)L.block * L.block;
-            // only the speculative launch adds a floor, and it is the one-wave k_search_fast (launch_search_fast); the others stay
-            // at fast_lds_bytes (< 26 KB)
+            L.fast_lds_bytes = fast_lds_bytes(L.block, L.range, plan.pitch_dw);
             if (int rc = with_block<8, 16, 32>(L.block, [&](auto B) {
-                    return raise_lds_limit(device, reinterpret_cast<const void *>(&k_search_fast<B(), 1>), std::max(L.fast_lds_bytes, spec_floor));
+                    return raise_lds_limit(device, reinterpret_cast<const void *>(&k_search_fast<B(), 1>), search_lds_bytes(c->tune, L, true, l, coarser_block));
                 })) return rc;
             // the device copy of a plan's round codes carries, for strip rounds, where the round's rank entries start in
             // lane_ranks (<< 16, in rows of T entries); lane_ranks itself: per strip round and lane the S entries of 4 ranks
@@ -1096,22 +899,16 @@ static int create_context(const bbme_params *params, int width, int height, int 
             // shorter strips, so that the 128 lanes of two waves have a full round of them
             SearchPlan plan2 = plan_search(L.range, L.block, 8, 128, c->tune.loose_plan);
             L.nrounds2 = (int)plan2.rounds.size();
-            // a round of strips of S rows walks S + B - 1 window rows: the split only pays where it shortens a wave's walk
-            // (+-32 at B <= 16: 0.6x; +-16: the square is too small to fill 128 lanes with tall strips, 0.94-1.0x -- measured slower)
-            auto walk = [&](const SearchPlan &p) {
-                int w = 0;
-                for (uint32_t code : p.rounds) w += (code >> 8) ? L.block / 4 : (int)(code & 0xffu) + L.block - 1;   // rim rounds are short
-                return w;
-            };
-            L.split_pays = 5 * walk(plan2) <= 4 * walk(plan);
+            L.split_pays = split_shortens_walk(plan.rounds, plan2.rounds, L.block);
             if (plan2.pitch_dw != plan.pitch_dw) return bbme::fail(BBME_ERR_STATE, "search plans disagree on the window pitch");
             if (int rc = upload_plan(plan2, 128, L.tasks2, L.rounds2, L.lane_ranks2)) return rc;
         }
         // k_search_generic serves the levels above, and every level in raster mode or under BBME_GENERIC_SEARCH
         if (int rc = with_block<2, 4, 8, 16, 32, 64>(L.block, [&](auto B) {
-                return raise_lds_limit(device, reinterpret_cast<const void *>(&k_search_generic<B()>), std::max(L.lds_bytes, spec_floor));
+                return raise_lds_limit(device, reinterpret_cast<const void *>(&k_search_generic<B()>), search_lds_bytes(c->tune, L, false, l, coarser_block));
             })) return rc;
     }
+    c->memo_blocks = memo_room(c->tune, std::vector<PlanLevel>(c->lv.begin(), c->lv.end()));
     // pitch = 33 (mod 64) words: consecutive blocks land 132 bytes (mod 256) apart
     c->own_pitch = (uint32_t)(((max_blocks + 31) / 32 + 63) / 64 * 64 + 33);
     const size_t bit_words = (size_t)c->own_pitch * 32;
@@ -1126,7 +923,7 @@ static int create_context(const bbme_params *params, int width, int height, int 
     if (int rc = c->flags[1].alloc_zero(P * c->flag_bytes, work)) return rc;
     if (int rc = c->own.alloc_zero(P * bit_words, work)) return rc;
     if (int rc = c->counters.alloc_zero(P * 64, work)) return rc;
-    if (c->tune.use_memo && c->memo_blocks) {
+    if (c->memo_blocks) {
         c->memo_stride = (uint32_t)round64(c->memo_blocks << kMemoSlotShift);
         // every slot starts as "nothing known" (the MV half of the word is what counts: 0x80008000 is never a motion vector)
         if (int rc = c->memo.alloc(P * c->memo_stride, "the SAD memo")) return rc;
@@ -3094,7 +2891,7 @@ int bbme_stage_search(bbme_ctx *c, int level)
     HIP_TRY(hipSetDevice(c->device));
     c->memo_block = 0;             // a stage sequence at a level starts here: the planes may have been refilled in place since
     c->fields_valid = false;
-    return launch_search(c, level);
+    return launch_search(c, plan_search_launch(plan_inputs(c), level, kPredictPlain));
 }
 
 int bbme_stage_regularize(bbme_ctx *c, int level, int block, int mult)
@@ -3104,7 +2901,12 @@ int bbme_stage_regularize(bbme_ctx *c, int level, int block, int mult)
     if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "no frames set");
     HIP_TRY(hipSetDevice(c->device));
     c->fields_valid = false;
-    return launch_sweep(c, level, block, mult, true);       // with the solver's counters (bbme_sweep_stats)
+    Level &L = c->lv[level];
+    if (mult < 1) return bbme::fail(BBME_ERR_INVALID, "lambda multiplier %d", mult);
+    if (block < 2 || block > L.block || (block & (block - 1)))
+        return bbme::fail(BBME_ERR_INVALID, "block %d is not a power of two in 2..%d", block, L.block);
+    // on the grid the level holds, with the solver's counters (bbme_sweep_stats)
+    return launch_sweep(c, plan_sweep(plan_inputs(c), level, block, mult, L.grid_id(L.cur_grid), L.cur_block), true);
 }
 
 int bbme_stage_get_mvs(bbme_ctx *c, int level, int block, int16_t *mvs)

@@ -311,6 +311,38 @@ LIMIT_REG_FORMS = {
 }
 
 
+# the knobs README's table calls result-neutral (test_gpu_context_state.test_result_neutral_knobs; test_launch_plan_cpu checks that
+# every geometry's launch plan has the form the knob is about): name, environment of the context, then per geometry
+# (w, h, search, block, content kind); each geometry chosen so that the knob's path runs
+KNOB_CASES = [
+    # the two-wave fix-up list: speculation on, levels of <= 10 000 blocks where the 128-lane plan pays (+-32 at B <= 16)
+    ("list_split", {"BBME_LIST_SPLIT": "0", "BBME_SPEC_MIN_GABS": "0"}, [(512, 384, [80, 80, 80], [16, 16, 16], 1),
+                                                                       (384, 256, [72, 72], [8, 8], 0),
+                                                                       (512, 384, [96, 96], [32, 32], 3)]),
+    # pass 1 evaluates itself instead of flagging for the relaxation launch that BBME_RELAX_STEPS forces into every sweep
+    # (pass 1 is lazy in the strip form only, which a single pair takes where the grid is too large for the chain form: the 2 x 2
+    # grid of 1024 x 576, 147 456 blocks in 512 columns.  The two smaller geometries never reach it: test_launch_plan_cpu.KNOWN_MISSES)
+    ("pass1_eager", {"BBME_PASS1_LAZY": "0", "BBME_RELAX_STEPS": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 4),
+                                                                       (256, 192, [12, 12], [4, 4], 2),
+                                                                       (1024, 576, [24, 24], [8, 8], 0)]),
+    # natural block order in the strip kernel, on levels whose block counts are not multiples of 8 (the XCD-aware order pads
+    # the grid to one): 22 x 14 and 11 x 7, 46 x 26 and 23 x 13 blocks
+    ("xcd_natural", {"BBME_XCD_REMAP": "0"}, [(352, 224, [48, 40], [16, 16], 1),
+                                              (360, 200, [30, 30], [8, 8], 0)]),
+    # the loose plan differs from the tight one for even ranges at B <= 16 (R = 32 here); R = 7, 45, 63 check it elsewhere;
+    # shifted noise moves by an odd amount
+    ("loose_plan_r32", {"BBME_LOOSE_PLAN": "1"}, [(384, 256, [80, 72], [16, 8], 1), (384, 256, [80, 72], [16, 8], 0)]),
+    ("loose_plan_r7_r45_r63", {"BBME_LOOSE_PLAN": "1"}, [(384, 256, [30, 106], [16, 16], 1), (512, 384, [158, 72], [32, 8], 1)]),
+    # relaxation launches on every grid, two steps in front of both sweeps
+    ("relax_rule", {"BBME_RELAX_RULE": "0,64,2,2"}, [(352, 256, [48, 40, 40], [16, 16, 8], 0),
+                                                     (256, 192, [40, 40], [8, 8], 4)]),
+    ("local_rounds_1", {"BBME_LOCAL_ROUNDS": "1", "BBME_RELAX_STEPS": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 4),
+                                                                             (256, 192, [40, 40], [8, 8], 1)]),
+    ("local_rounds_32", {"BBME_LOCAL_ROUNDS": "32", "BBME_RELAX_STEPS": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 4),
+                                                                               (256, 192, [40, 40], [8, 8], 1)]),
+    ("no_graph", {"BBME_NO_GRAPH": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 0), (320, 240, [24, 24, 160], [4, 8, 16], 3)]),
+]
+
 # ---- grids injected with stage_set_mvs: energies beyond 2^24, the SAD memo's 8192 guard, vectors at int16's bounds ----
 def inside_field(rows, cols, b, w, h, rng):
     """A (rows, cols, 2) int16 grid of uniformly random vectors that keep every block's own candidate inside the w x h plane."""

@@ -8,7 +8,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
-from helpers import gpu_schedule, oracle_schedule
+from helpers import KNOB_CASES, gpu_schedule, oracle_schedule
 
 pytestmark = pytest.mark.gpu
 
@@ -330,34 +330,6 @@ def test_speculative_search_lds_floor(bbme, oracle, monkeypatch, geom, per_cu):
 
 
 # ---- E. the knobs the README calls result-neutral --------------------------------------------------------------------------
-# (w, h, search, block, content kind); each geometry chosen so that the knob's path runs
-KNOB_CASES = [
-    # the two-wave fix-up list: speculation on, levels of <= 10 000 blocks where the 128-lane plan pays (+-32 at B <= 16)
-    ("list_split", {"BBME_LIST_SPLIT": "0", "BBME_SPEC_MIN_GABS": "0"}, [(512, 384, [80, 80, 80], [16, 16, 16], 1),
-                                                                       (384, 256, [72, 72], [8, 8], 0),
-                                                                       (512, 384, [96, 96], [32, 32], 3)]),
-    # pass 1 evaluates itself instead of flagging for the relaxation launch that BBME_RELAX_STEPS forces into every sweep
-    ("pass1_eager", {"BBME_PASS1_LAZY": "0", "BBME_RELAX_STEPS": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 4),
-                                                                       (256, 192, [12, 12], [4, 4], 2)]),
-    # natural block order in the strip kernel, on levels whose block counts are not multiples of 8 (the XCD-aware order pads
-    # the grid to one): 22 x 14 and 11 x 7, 46 x 26 and 23 x 13 blocks
-    ("xcd_natural", {"BBME_XCD_REMAP": "0"}, [(352, 224, [48, 40], [16, 16], 1),
-                                              (360, 200, [30, 30], [8, 8], 0)]),
-    # the loose plan differs from the tight one for even ranges at B <= 16 (R = 32 here); R = 7, 45, 63 check it elsewhere;
-    # shifted noise moves by an odd amount
-    ("loose_plan_r32", {"BBME_LOOSE_PLAN": "1"}, [(384, 256, [80, 72], [16, 8], 1), (384, 256, [80, 72], [16, 8], 0)]),
-    ("loose_plan_r7_r45_r63", {"BBME_LOOSE_PLAN": "1"}, [(384, 256, [30, 106], [16, 16], 1), (512, 384, [158, 72], [32, 8], 1)]),
-    # relaxation launches on every grid, two steps in front of both sweeps
-    ("relax_rule", {"BBME_RELAX_RULE": "0,64,2,2"}, [(352, 256, [48, 40, 40], [16, 16, 8], 0),
-                                                     (256, 192, [40, 40], [8, 8], 4)]),
-    ("local_rounds_1", {"BBME_LOCAL_ROUNDS": "1", "BBME_RELAX_STEPS": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 4),
-                                                                             (256, 192, [40, 40], [8, 8], 1)]),
-    ("local_rounds_32", {"BBME_LOCAL_ROUNDS": "32", "BBME_RELAX_STEPS": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 4),
-                                                                               (256, 192, [40, 40], [8, 8], 1)]),
-    ("no_graph", {"BBME_NO_GRAPH": "1"}, [(352, 256, [48, 40, 40], [16, 16, 8], 0), (320, 240, [24, 24, 160], [4, 8, 16], 3)]),
-]
-
-
 @pytest.mark.parametrize("name,env,cases", KNOB_CASES, ids=[k[0] for k in KNOB_CASES])
 def test_result_neutral_knobs(bbme, oracle, monkeypatch, name, env, cases):
     """Every knob of README's table "changes no result": a context created under it returns the oracle's field, twice (the
