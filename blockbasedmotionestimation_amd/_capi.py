@@ -199,6 +199,10 @@ SIGNATURES = {
     "bbme_wait_for_stream": (C.c_int, [_ctx, C.c_void_p]),
     "bbme_calibrate_read": (C.c_int, [C.c_int, C.c_uint, C.c_int]),
     "bbme_selftest_isa": (C.c_int, [C.c_int, _P(C.c_int)]),
+    # test hooks (BBME_TEST_GUARD / BBME_TEST_POISON)
+    "bbme_test_guard_check": (C.c_int, [_P(C.c_ulonglong), _P(C.c_ulonglong), C.c_char_p, C.c_int]),
+    "bbme_test_guard_reset": (C.c_int, []),
+    "bbme_test_guard_find": (C.c_int, [C.c_char_p, C.c_int, _P(C.c_void_p)]),
 }
 
 _lib = None

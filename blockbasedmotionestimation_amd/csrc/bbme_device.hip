@@ -10,10 +10,12 @@
 #include <map>
 #include <memory>
 #include <mutex>
+#include <string>
 #include <type_traits>
 #include <vector>
 
 #include "bbme_internal.hpp"
+#include "guard_layout.hpp"
 #include "bbme_kernels.hpp"
 #include "launch_plan.hpp"
 
@@ -29,52 +31,144 @@ using namespace bbme;
 
 namespace {
 
+// TEST HOOKS of the device allocations (guard_layout.hpp; include/bbme.h, "test hooks").  Both knobs are read at every allocation
+// -- allocations are rare and the steady state makes none --, so a test can set them for one context.  With neither set the
+// allocation path is what it was: one hipMalloc of the caller's bytes, nothing registered, nothing filled.
+// BBME_TEST_GUARD: every allocation gets a guard band on either side; the registry below knows every live one, and a band is
+// scanned by bbme_test_guard_check and when its buffer is freed or replaced, where damage goes into a sticky record.
+// BBME_TEST_POISON: a fresh DATA buffer (Fill::poison) is filled with kPoisonByte.
+enum class Fill {
+    none,       // index lists, whose valid length is a counter's (an address derived from poison must not be possible), and probes
+    poison      // data: grids, planes' upload buffer, colour store, staging, statistics partials, scratch
+};
+
+struct GuardRegistry {
+    struct Entry { uint8_t *base; size_t payload; int device; std::string what; };
+    std::mutex mu;
+    std::vector<Entry> live;
+    unsigned long long sticky = 0;                // damaged bands of buffers that are gone
+    std::string sticky_first;
+};
+GuardRegistry &guard_registry() { static GuardRegistry r; return r; }
+
+// Downloads and scans the two bands of `e`; appends to *violations and, while it is empty, describes the first damage in *first.
+void guard_scan(const GuardRegistry::Entry &e, unsigned long long *violations, std::string *first)
+{
+    std::vector<uint8_t> band(kGuardBytes);
+    for (int back = 0; back < 2; ++back) {
+        const uint8_t *src = e.base + (back ? kGuardBytes + e.payload : 0);
+        char text[256];
+        if (hipMemcpy(band.data(), src, kGuardBytes, hipMemcpyDeviceToHost) != hipSuccess) {
+            snprintf(text, sizeof text, "%s: the %s guard could not be read", e.what.c_str(), back ? "back" : "front");
+        } else {
+            const GuardDamage d = scan_guard(band.data(), kGuardBytes, back != 0);
+            if (!d.count) continue;
+            snprintf(text, sizeof text, "%s (%zu bytes): %s guard, offset %zu from the payload's edge holds 0x%02x (%zu damaged bytes, the "
+                     "farthest at offset %zu)", e.what.c_str(), e.payload, back ? "back" : "front", d.first, (unsigned)d.first_byte,
+                     d.count, d.last);
+        }
+        ++*violations;
+        if (first->empty()) *first = text;
+    }
+}
+
+void guard_register(uint8_t *base, size_t payload, const char *what)
+{
+    int device = 0;
+    (void)hipGetDevice(&device);
+    GuardRegistry &r = guard_registry();
+    std::lock_guard<std::mutex> lock(r.mu);
+    r.live.push_back({base, payload, device, what});
+}
+
+// A guarded buffer goes (freed, or replaced by ensure): whatever wrote near it has finished after the synchronisation
+void guard_release(uint8_t *base)
+{
+    GuardRegistry &r = guard_registry();
+    std::lock_guard<std::mutex> lock(r.mu);
+    for (size_t i = 0; i < r.live.size(); ++i)
+        if (r.live[i].base == base) {
+            (void)hipDeviceSynchronize();
+            guard_scan(r.live[i], &r.sticky, &r.sticky_first);
+            r.live.erase(r.live.begin() + (long)i);
+            return;
+        }
+}
+
 // Owning handles of device memory and of events: whoever holds one releases it, so an early return leaks nothing.
 // DevBuf is move-only, its sizes are in elements of T; every size expression and its slack stays with the caller (they are
-// contracts with the kernels).  Errors are the library's codes: "allocating <what>: <HIP's text>".
+// contracts with the kernels).  Errors are the library's codes: "allocating <what>: <HIP's text>".  The caller says what kind
+// of buffer it is (Fill); alloc_zero and upload fill their own part.
 template <class T>
 class DevBuf {
 public:
     DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : p_(o.p_), bytes_(o.bytes_) { o.p_ = nullptr; o.bytes_ = 0; }
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), bytes_(o.bytes_), guarded_(o.guarded_) { o.p_ = nullptr; o.bytes_ = 0; o.guarded_ = false; }
     DevBuf(const DevBuf &) = delete;
     DevBuf &operator=(const DevBuf &) = delete;
-    ~DevBuf() { if (p_) (void)hipFree(p_); }
+    ~DevBuf() { release(); }
     T *get() const { return p_; }
     operator T *() const { return p_; }
     size_t size() const { return bytes_ / sizeof(T); }
-    int alloc(size_t n, const char *what) { return alloc_bytes(n * sizeof(T), what); }
+    int alloc(size_t n, const char *what, Fill fill) { return alloc_bytes(n * sizeof(T), what, fill, 0); }
     int alloc_zero(size_t n, const char *what)
     {
-        if (int rc = alloc(n, what)) return rc;
+        if (int rc = alloc(n, what, Fill::none)) return rc;
         return check(hipMemset(p_, 0, bytes_), what);
     }
-    // the vector's bytes, and `slack_bytes` behind them that a kernel may load (and mask) but that hold nothing
+    // the vector's bytes, and `slack_bytes` behind them that a kernel may load (and mask) but that hold nothing (poisoned in a test)
     template <class U>
     int upload(const std::vector<U> &v, const char *what, size_t slack_bytes = 0)
     {
-        if (int rc = alloc_bytes(v.size() * sizeof(U) + slack_bytes, what)) return rc;
+        if (int rc = alloc_bytes(v.size() * sizeof(U) + slack_bytes, what, Fill::poison, v.size() * sizeof(U))) return rc;
         return check(hipMemcpy(p_, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice), what);
     }
     // scratch: allocated on first use, replaced when more is asked for (the caller orders that against whoever reads it)
-    int ensure(size_t n, const char *what) { return n * sizeof(T) <= bytes_ ? BBME_OK : alloc(n, what); }
+    int ensure(size_t n, const char *what, Fill fill) { return n * sizeof(T) <= bytes_ ? BBME_OK : alloc(n, what, fill); }
 
 private:
     static int check(hipError_t e, const char *what)
     {
         return e == hipSuccess ? BBME_OK : bbme::fail(BBME_ERR_HIP, "allocating %s: %s", what, hipGetErrorString(e));
     }
-    int alloc_bytes(size_t bytes, const char *what)
+    uint8_t *base() const { return reinterpret_cast<uint8_t *>(p_) - (guarded_ ? kGuardBytes : 0); }
+    void release()
     {
-        if (p_) (void)hipFree(p_);
+        if (!p_) return;
+        if (guarded_) guard_release(base());
+        (void)hipFree(base());
         p_ = nullptr;
         bytes_ = 0;
-        if (int rc = check(hipMalloc(&p_, bytes), what)) { p_ = nullptr; return rc; }
+        guarded_ = false;
+    }
+    // `poison_from`: the first payload byte that Fill::poison covers (upload overwrites what lies in front of it)
+    int alloc_bytes(size_t bytes, const char *what, Fill fill, size_t poison_from)
+    {
+        release();
+        const bool guarded = test_knob_on(getenv("BBME_TEST_GUARD"));
+        const bool poison = fill == Fill::poison && test_knob_on(getenv("BBME_TEST_POISON")) && poison_from < bytes;
+        const GuardLayout g = guard_layout(bytes, guarded);
+        void *raw = nullptr;
+        if (int rc = check(hipMalloc(&raw, g.total()), what)) return rc;
+        uint8_t *b = static_cast<uint8_t *>(raw);
+        if (guarded || poison) {
+            // the fills run on the null stream, which the context's streams do not wait for: finished before anything is enqueued
+            hipError_t e = hipSuccess;
+            if (guarded) e = hipMemset(b, kGuardByte, g.front);
+            if (guarded && e == hipSuccess) e = hipMemset(b + g.back_offset(), kGuardByte, g.back);
+            if (poison && e == hipSuccess) e = hipMemset(b + g.payload_offset() + poison_from, kPoisonByte, bytes - poison_from);
+            if (e == hipSuccess) e = hipDeviceSynchronize();
+            if (e != hipSuccess) { (void)hipFree(raw); return check(e, what); }
+        }
+        if (guarded) guard_register(b, bytes, what);
+        p_ = reinterpret_cast<T *>(b + g.payload_offset());
         bytes_ = bytes;
+        guarded_ = guarded;
         return BBME_OK;
     }
     T *p_ = nullptr;
     size_t bytes_ = 0;
+    bool guarded_ = false;
 };
 
 // Statistics scratch of a gather stage (k_motion_compensate .. k_temporal_filter_bgr): `slots` result quadruples (one per pair or
@@ -85,7 +179,7 @@ struct StatsScratch {
     void layout(int slots, long long groups, int all) { slots_ = slots; groups_ = groups; all_ = all; }
     size_t words(int caller) const { return (size_t)4 * (slots_ + groups_ * (all_ + caller)); }
     size_t size() const { return buf_.size(); }
-    int ensure(int caller, const char *what) { return buf_.ensure(words(caller), what); }
+    int ensure(int caller, const char *what) { return buf_.ensure(words(caller), what, Fill::poison); }
     int ensure(int slots, long long groups, int all, int caller, const char *what)
     {
         layout(slots, groups, all);
@@ -222,7 +316,7 @@ struct bbme_ctx {
     {
         if (n * sizeof(T) > staging.size()) {
             HIP_TRY(hipSetDevice(device));
-            if (int rc = staging.ensure(n * sizeof(T), what)) return rc;
+            if (int rc = staging.ensure(n * sizeof(T), what, Fill::poison)) return rc;
         }
         *p = reinterpret_cast<T *>(staging.get());
         return BBME_OK;
@@ -836,8 +930,8 @@ static int create_context(const bbme_params *params, int width, int height, int 
         if (int rc = L.img1.alloc_zero(chain ? (P + 1) * plane : L.frame_step + P * plane, what)) return rc;
         L.img2 = L.img1 + L.frame_step;
         for (DevBuf<mv_t> *grid : {&L.small[0], &L.small[1], &L.pred})
-            if (int rc = grid->alloc(P * own_blocks, what)) return rc;
-        if (int rc = L.fix_list.alloc(P * own_blocks, what)) return rc;
+            if (int rc = grid->alloc(P * own_blocks, what, Fill::poison)) return rc;
+        if (int rc = L.fix_list.alloc(P * own_blocks, what, Fill::none)) return rc;
         if (int rc = L.fix_count.alloc_zero(P * 64 / sizeof(uint32_t), what)) return rc;    // 64 bytes per pair
         if (int rc = L.publish.alloc_zero(P * 64 / sizeof(uint32_t), what)) return rc;
         if (int rc = L.big[0].alloc_zero(P * cells, what)) return rc;
@@ -917,8 +1011,8 @@ static int create_context(const bbme_params *params, int width, int height, int 
     c->list_stride = (uint32_t)max_blocks; c->own_stride = (uint32_t)bit_words;
     const char *work = "work buffers";
     if (int rc = c->flow.alloc_zero(P * c->flow_stride, work)) return rc;
-    if (int rc = c->list[0].alloc(P * max_blocks, work)) return rc;
-    if (int rc = c->list[1].alloc(P * max_blocks, work)) return rc;
+    if (int rc = c->list[0].alloc(P * max_blocks, work, Fill::none)) return rc;
+    if (int rc = c->list[1].alloc(P * max_blocks, work, Fill::none)) return rc;
     if (int rc = c->flags[0].alloc_zero(P * c->flag_bytes, work)) return rc;
     if (int rc = c->flags[1].alloc_zero(P * c->flag_bytes, work)) return rc;
     if (int rc = c->own.alloc_zero(P * bit_words, work)) return rc;
@@ -926,7 +1020,7 @@ static int create_context(const bbme_params *params, int width, int height, int 
     if (c->memo_blocks) {
         c->memo_stride = (uint32_t)round64(c->memo_blocks << kMemoSlotShift);
         // every slot starts as "nothing known" (the MV half of the word is what counts: 0x80008000 is never a motion vector)
-        if (int rc = c->memo.alloc(P * c->memo_stride, "the SAD memo")) return rc;
+        if (int rc = c->memo.alloc(P * c->memo_stride, "the SAD memo", Fill::poison)) return rc;
         err = hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(c->memo.get()), (int)kMemoNoMv, P * c->memo_stride * 2);
         if (err != hipSuccess) return bbme::fail(BBME_ERR_HIP, "allocating the SAD memo: %s", hipGetErrorString(err));
     }
@@ -1152,7 +1246,7 @@ int bgr_store(bbme_ctx *c)
 {
     if (c->bgr.get()) return BBME_OK;
     c->bgr_stride = ((size_t)3 * c->geom.width * c->geom.height + 255) / 256 * 256;
-    return c->bgr.alloc(c->bgr_stride * (size_t)c->frames(), "the colour store");
+    return c->bgr.alloc(c->bgr_stride * (size_t)c->frames(), "the colour store", Fill::poison);
 }
 
 // A device setter: frames in HBM.  B,G,R frames are kept (copied into the colour store).
@@ -1181,7 +1275,7 @@ int set_frames_host(bbme_ctx *c, bool by_slot, int first, int count, const uint8
     const Geometry &g = c->geom;
     const int scale = fmt == kGreyX4 ? 4 : 1;
     const size_t row = (size_t)(fmt == kBgr ? 3 : 1) * (g.width / scale), rows = (size_t)(g.height / scale);
-    if (int rc = fmt == kBgr ? bgr_store(c) : c->raw.ensure(c->raw_stride * (size_t)c->frames(), "the upload buffer")) return rc;
+    if (int rc = fmt == kBgr ? bgr_store(c) : c->raw.ensure(c->raw_stride * (size_t)c->frames(), "the upload buffer", Fill::poison)) return rc;
     FrameRun run{};
     for (int i = 0; i < count; ++i) {
         uint8_t *d = fmt == kBgr ? c->bgr + (size_t)set.slot(i) * c->bgr_stride : c->raw + (size_t)set.slot(i) * c->raw_stride;
@@ -1477,7 +1571,7 @@ int bbme_estimate_bidirectional(bbme_ctx *c)
     HIP_TRY(hipSetDevice(c->device));
     const Level &L0 = c->lv[0];
     const uint32_t stride = L0.grid_stride(L0.final_grid());
-    if (int rc = c->bwd_cells.ensure((size_t)stride * c->batch, "the backward cells")) return rc;
+    if (int rc = c->bwd_cells.ensure((size_t)stride * c->batch, "the backward cells", Fill::poison)) return rc;
     c->bwd_stride = stride;
     // backward pyramid, its final grid of every pair into the backward cells, forward pyramid: all on the ctx stream, in order
     switch_direction(c, BBME_DIR_BACKWARD);
@@ -1598,7 +1692,7 @@ int bbme_calculate_mse_device(bbme_ctx *c, const float *d_gtruth, int gt_width, 
     const long long n = (long long)gt_width * gt_height;
     const int groups = (int)std::min<long long>(kMaxGroups, (n + 255) / 256);
     static_assert(sizeof(double) == sizeof(unsigned long long), "sums and counts share the scratch");
-    if (int rc = c->epe_scratch.ensure(2 * kMaxGroups, "the EPE scratch")) return rc;
+    if (int rc = c->epe_scratch.ensure(2 * kMaxGroups, "the EPE scratch", Fill::poison)) return rc;
     double *d_sum = c->epe_scratch;
     unsigned long long *d_cnt = reinterpret_cast<unsigned long long *>(d_sum + kMaxGroups);
     hipLaunchKernelGGL(k_epe, dim3(groups), dim3(256), 0, c->stream, L.cur_grid, L.width / 2,
@@ -2038,7 +2132,7 @@ static const float *color_floats(const bbme_ctx *c)
 
 static int color_scratch(bbme_ctx *c)
 {
-    return c->color_range.ensure((size_t)kColorSlots * (kColorKeyCopies * kColorKeyStride + 5), "the colour ranges");
+    return c->color_range.ensure((size_t)kColorSlots * (kColorKeyCopies * kColorKeyStride + 5), "the colour ranges", Fill::poison);
 }
 
 int bbme_cells_color_device(bbme_ctx *c, const int16_t *d_cells, int scale, float maxmotion, uint8_t *d_bgr, int out_pitch_bytes,
@@ -3026,7 +3120,7 @@ int bbme_probe_rates(int device, double *gops)
     if (!gops) return bbme::fail(BBME_ERR_INVALID, "null output");
     if (int rc = probe_device(device)) return rc;
     DevBuf<uint32_t> out;
-    if (int rc = out.alloc(16, kProbe)) return rc;
+    if (int rc = out.alloc(16, kProbe, Fill::none)) return rc;
     const int iters = 4096, grid = 256 * 8;          // 8 workgroups of 4 waves per CU: 8 waves per SIMD
     void (*const kernels[4])(uint32_t *, int, uint32_t) = {k_probe_rate<0>, k_probe_rate<1>, k_probe_rate<2>, k_probe_rate<5>};
     for (int which = 0; which < 4; ++which) {
@@ -3043,7 +3137,7 @@ int bbme_probe_search_loops(int device, double *tabs2)
     if (!tabs2) return bbme::fail(BBME_ERR_INVALID, "null output");
     if (int rc = probe_device(device)) return rc;
     DevBuf<uint32_t> out;
-    if (int rc = out.alloc(16, kProbe)) return rc;
+    if (int rc = out.alloc(16, kProbe, Fill::none)) return rc;
     const int passes = 128, grid = 32768;
     for (int which = 0; which < 2; ++which) {
         float ms = 0;
@@ -3069,7 +3163,7 @@ int bbme_probe_latency(int device, unsigned long long *out9)
     DevBuf<uint32_t> buf;
     DevBuf<unsigned long long> out;
     if (int rc = buf.upload(host, kProbe)) return rc;
-    if (int rc = out.alloc(9, kProbe)) return rc;
+    if (int rc = out.alloc(9, kProbe, Fill::none)) return rc;
     for (int rep = 0; rep < 2; ++rep) hipLaunchKernelGGL(k_probe_latency, dim3(1), dim3(64), 0, 0, buf.get(), nwords, out.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out9, out, 9 * 8, hipMemcpyDeviceToHost));
@@ -3083,7 +3177,7 @@ int bbme_probe_xcd(int device, int *xcds_seen, int *violations)
     const int n = 4096;
     std::vector<uint32_t> host(n);
     DevBuf<uint32_t> d;
-    if (int rc = d.alloc(n, kProbe)) return rc;
+    if (int rc = d.alloc(n, kProbe, Fill::none)) return rc;
     hipLaunchKernelGGL(k_probe_xcc, dim3(n), dim3(64), 0, 0, d.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(host.data(), d, n * 4, hipMemcpyDeviceToHost));
@@ -3103,8 +3197,8 @@ int bbme_calibrate_read(int device, unsigned mbytes, int repeats)
     if (mbytes == 0 || mbytes > 16384 || repeats < 1) return bbme::fail(BBME_ERR_INVALID, "bbme_calibrate_read: bad size");
     const size_t bytes = (size_t)mbytes << 20, n = bytes / 4;
     DevBuf<uint32_t> buf, out;
-    if (int rc = buf.alloc(n, kProbe)) return rc;
-    if (int rc = out.alloc(16, kProbe)) return rc;
+    if (int rc = buf.alloc(n, kProbe, Fill::none)) return rc;
+    if (int rc = out.alloc(16, kProbe, Fill::none)) return rc;
     HIP_TRY(hipMemset(buf, 1, bytes));
     HIP_TRY(hipDeviceSynchronize());
     for (int i = 0; i < repeats; ++i)
@@ -3130,8 +3224,8 @@ int bbme_selftest_isa(int device, int *mismatches)
     if (int rc = db.upload(b, kProbe)) return rc;
     if (int rc = dc.upload(cc, kProbe)) return rc;
     for (DevBuf<uint32_t> *d : {&dsad, &dal, &ds16})
-        if (int rc = d->alloc(n, kProbe)) return rc;
-    if (int rc = dqs.alloc(n, kProbe)) return rc;
+        if (int rc = d->alloc(n, kProbe, Fill::none)) return rc;
+    if (int rc = dqs.alloc(n, kProbe, Fill::none)) return rc;
     hipLaunchKernelGGL(k_probe_sad, dim3(n / 256), dim3(256), 0, 0, da.get(), db.get(), dc.get(), dsad.get(), dqs.get(), dal.get(), ds16.get(), n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(sad.data(), dsad, n * 4, hipMemcpyDeviceToHost));
@@ -3148,7 +3242,7 @@ int bbme_selftest_isa(int device, int *mismatches)
         DevBuf<uint8_t> dp;
         DevBuf<uint32_t> dout;
         if (int rc = dp.upload(bytes, kProbe)) return rc;
-        if (int rc = dout.alloc(got.size(), kProbe)) return rc;
+        if (int rc = dout.alloc(got.size(), kProbe, Fill::none)) return rc;
         hipLaunchKernelGGL(k_probe_unaligned, dim3(m / 256), dim3(256), 0, 0, dp.get(), dout.get(), m);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipMemcpy(got.data(), dout, got.size() * 4, hipMemcpyDeviceToHost));
@@ -3182,6 +3276,58 @@ int bbme_selftest_isa(int device, int *mismatches)
         if (e16 != s16[i]) ++mismatches[3];
     }
     return BBME_OK;
+}
+
+// ---- test hooks: the guard bands of BBME_TEST_GUARD (DevBuf, guard_layout.hpp) ---------------------------------------------
+int bbme_test_guard_check(unsigned long long *live, unsigned long long *violations, char *first, int first_len)
+{
+    if (!live || !violations || first_len < 0 || (first_len > 0 && !first))
+        return bbme::fail(BBME_ERR_INVALID, "bbme_test_guard_check: bad arguments");
+    GuardRegistry &r = guard_registry();
+    std::lock_guard<std::mutex> lock(r.mu);
+    int before = 0;
+    const bool have_device = hipGetDevice(&before) == hipSuccess;
+    unsigned long long found = r.sticky;
+    std::string text = r.sticky_first;
+    int synced = -1;
+    for (const GuardRegistry::Entry &e : r.live) {
+        if (e.device != synced) {                            // whatever any stream of that device still runs has finished
+            HIP_TRY(hipSetDevice(e.device));
+            HIP_TRY(hipDeviceSynchronize());
+            synced = e.device;
+        }
+        guard_scan(e, &found, &text);
+    }
+    if (have_device && synced >= 0) (void)hipSetDevice(before);
+    *live = r.live.size();
+    *violations = found;
+    if (first_len > 0) snprintf(first, (size_t)first_len, "%s", text.c_str());
+    return BBME_OK;
+}
+
+int bbme_test_guard_reset(void)
+{
+    GuardRegistry &r = guard_registry();
+    std::lock_guard<std::mutex> lock(r.mu);
+    r.sticky = 0;
+    r.sticky_first.clear();
+    return BBME_OK;
+}
+
+int bbme_test_guard_find(const char *what, int back, void **guard_address)
+{
+    if (!what || !guard_address) return bbme::fail(BBME_ERR_INVALID, "bbme_test_guard_find: null argument");
+    *guard_address = nullptr;
+    if (!test_knob_on(getenv("BBME_TEST_GUARD")))
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "bbme_test_guard_find: BBME_TEST_GUARD is not set");
+    GuardRegistry &r = guard_registry();
+    std::lock_guard<std::mutex> lock(r.mu);
+    for (const GuardRegistry::Entry &e : r.live)
+        if (e.what == what) {
+            *guard_address = e.base + (back ? kGuardBytes + e.payload : 0);
+            return BBME_OK;
+        }
+    return bbme::fail(BBME_ERR_INVALID, "bbme_test_guard_find: no live guarded buffer \"%s\"", what);
 }
 
 }  // extern "C"

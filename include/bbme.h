@@ -845,6 +845,32 @@ int bbme_calibrate_read(int device, unsigned mbytes, int repeats);
  * mismatches[0..4] receive the number of disagreements per item, in that order. */
 int bbme_selftest_isa(int device, int *mismatches);
 
+/* ---- test hooks ------------------------------------------------------------------------------------------------------------
+ * Two environment variables, read at every device allocation (allocations are rare; an estimate makes none):
+ *   BBME_TEST_GUARD=1   every device allocation of n bytes becomes [4096 guard bytes][n bytes][4096 guard bytes], the guards
+ *                       filled with one byte pattern (0xA5).  The library registers every live guarded allocation and scans a
+ *                       buffer's guards when it is freed or replaced; damage found then is remembered until the reset below.
+ *   BBME_TEST_POISON=1  a fresh data buffer -- grids, upload buffer, colour store, staging area, statistics partials, scratch,
+ *                       the slack behind an uploaded table -- is filled with a second pattern (0xC7) instead of being left as
+ *                       the allocator returned it.  Zeroed buffers stay zero; index lists, whose valid length is a counter's,
+ *                       are left alone.
+ * With neither set the library allocates exactly as it does without these hooks.
+ *
+ * bbme_test_guard_check waits for every device that holds a guarded allocation, downloads and scans every live guard and adds
+ * the remembered damage of buffers that are gone.  live = guarded allocations alive in this process, violations = damaged guard
+ * bands (two per allocation at most).  first (first_len bytes, may be 0): the first damaged band as "<what> (<n> bytes): back
+ * guard, offset 5 from the payload's edge holds 0x00 (...)" -- the buffer's text as in the library's allocation errors, front or
+ * back, the offset of the nearest damaged byte counted from the payload's edge (0 touches the payload), and the byte found;
+ * empty when nothing is damaged. */
+int bbme_test_guard_check(unsigned long long *live, unsigned long long *violations, char *first, int first_len);
+/* Forgets the remembered damage of buffers that are gone (live buffers are scanned afresh by every check). */
+int bbme_test_guard_reset(void);
+/* The first byte of the front (back = 0) or back (back = 1) guard band of the oldest live guarded allocation whose text is `what`
+ * ("work buffers": the flow field): 4096 bytes of the library's own allocation, so that a test can damage one and see the check
+ * fail.  The byte at offset k from the payload's edge is byte k of a back band and byte 4095 - k of a front band.
+ * BBME_ERR_UNSUPPORTED when BBME_TEST_GUARD is unset, BBME_ERR_INVALID when there is no such allocation. */
+int bbme_test_guard_find(const char *what, int back, void **guard_address);
+
 #ifdef __cplusplus
 }
 #endif
