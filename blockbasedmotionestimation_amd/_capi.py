@@ -155,6 +155,13 @@ SIGNATURES = {
     "bbme_get_subpel_cells_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
     "bbme_subpel_stats": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_get_subpel_flow_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_subpel_compensate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]),
+    "bbme_cells_subpel_compensate_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                                      C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_subpel_compensate_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_get_subpel_compensated_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_subpel_compensation_error": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_frame_plane_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
     "bbme_cells_color_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_flow_color_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

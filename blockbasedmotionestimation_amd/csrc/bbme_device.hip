@@ -338,6 +338,10 @@ struct bbme_ctx {
     StatsScratch tf_bgr_stats;                    // the same of bbme_temporal_filter_bgr_stats and bbme_cells_temporal_filter_bgr_device
     int src_scale = 1;                            // 4 after a setter of frames to up-sample (bbme_set_frames_*_x4, scale 4 of a chain), else 1
     StatsScratch sp_stats;                        // bbme_subpel_stats (every pair) and bbme_cells_subpel_device (one pair)
+    DevBuf<mv_t> sc_q4;                           // the quarter-pel cells the context's own sub-pel compensation reads: a packed
+                                                  // grid per pair, allocated at first use (enqueue_own_sc)
+    StatsScratch sc_stats;                        // bbme_subpel_compensation_error (every pair) and
+                                                  // bbme_cells_subpel_compensate_device (one pair)
 };
 
 namespace {
@@ -1739,7 +1743,7 @@ int bbme_subsampled_flow_device(bbme_ctx *c, int pair, int scale, float *d_out, 
 
 }  // extern "C": the stages from here on share templates, which need C++ linkage; their entry points have C linkage from bbme.h
 
-// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter) ----
+// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter, K11) ----
 // Every stage is one launch in which a lane takes runs of 4 units (pixels or cells) along a row, over (workgroups, pairs, phases
 // or frames), with optional statistics: the kernel's partials, then k_mc_reduce.  One run split, one launch path, one scratch
 // layout, one pair of output checks and one pair of download helpers serve all of them.
@@ -2960,6 +2964,141 @@ int bbme_get_subpel_flow_host(bbme_ctx *c, int pair, int which, float *flow)
                            c->geom.pad_x, c->geom.pad_y, scale, d, ow, oh);
         HIP_TRY(hipGetLastError());
         return (int)BBME_OK;
+    });
+}
+
+// ---- motion compensation along a quarter-pel grid (the SUBPEL COMPENSATION RULE of include/bbme.h; K11 k_subpel_compensate) -------
+
+static long long sc_groups(const bbme_ctx *c) { return cell_groups(c, kScRunsPerLane); }
+
+// result words of every pair, partials of a launch over every pair, then those of a caller's launch: one size per context
+static int sc_scratch(bbme_ctx *c)
+{
+    return c->sc_stats.ensure(BBME_MAX_BATCH, sc_groups(c), c->batch, 1, "the subpel compensation statistics");
+}
+
+static int check_fill(int fill, const char *what)
+{
+    if (fill < 0 || fill > 255) return bbme::fail(BBME_ERR_INVALID, "%s: fill %d outside 0..255", what, fill);
+    return BBME_OK;
+}
+
+// k_subpel_compensate over `pairs` pairs (planes s_plane bytes, grids s_q4 words apart): the frame into d_out (one pair only)
+// and / or, with d_stats, the statistics over `window` in pixels
+static int enqueue_sc(bbme_ctx *c, const uint8_t *img1, const uint8_t *img2, size_t s_plane, const mv_t *q4, int q4_pitch, size_t s_q4,
+                      int pairs, int fill, const int *window, uint8_t *d_out, int out_pitch, unsigned long long *partial,
+                      unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    ScArgs a{};
+    a.img1 = img1; a.img2 = img2; a.q4 = q4; a.out = d_out;
+    a.s_plane = s_plane; a.s_q4 = s_q4;
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2;
+    a.q4_pitch = q4_pitch; a.fill = fill; a.out_pitch = out_pitch;
+    set_window(a, window, L.width, L.height);
+    set_runs(a, L.width / 2, L.height / 2);
+    return launch_gather(k_subpel_compensate, a, sc_groups(c), pairs, 1, partial, d_stats, stream);
+}
+
+// The context's own: the cells of `which` of `pairs` pairs from pair0 on refined into the context's quarter-pel buffer (one packed
+// grid per pair, allocated here at first use), then compensated from it
+static int enqueue_own_sc(bbme_ctx *c, int pair0, int pairs, int which, int fill, const int *window, uint8_t *d_out, int out_pitch,
+                          unsigned long long *d_stats, hipStream_t stream, const char *what)
+{
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+    const Level &L = c->lv[0];
+    const int cw = L.width / 2;
+    const size_t cells = (size_t)cw * (L.height / 2), s_plane = L.plane_stride;
+    if (int rc = c->sc_q4.ensure(cells * c->batch, "the quarter-pel cells of the compensation", Fill::poison)) return rc;
+    i1 += pair0 * s_plane; i2 += pair0 * s_plane;
+    mv_t *q4 = c->sc_q4 + pair0 * cells;
+    if (int rc = enqueue_sp(c, i1, i2, s_plane, grid + (size_t)pair0 * s_grid, s_grid, pairs, nullptr, q4, cw, cells, nullptr, nullptr,
+                            stream))
+        return rc;
+    return enqueue_sc(c, i1, i2, s_plane, q4, cw, cells, pairs, fill, window, d_out, out_pitch, c->sc_stats.partials_all(), d_stats,
+                      stream);
+}
+
+int bbme_cells_subpel_compensate_device(bbme_ctx *c, const uint8_t *d_image1, const uint8_t *d_image2, const int16_t *d_q4,
+                                        int q4_pitch_cells, int fill, const int *window, uint8_t *d_out, int out_pitch,
+                                        unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_subpel_compensate_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_image2 || !d_q4 || (!d_out && !d_stats4) || (d_stats4 && !d_image1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_fill(fill, what)) return rc;
+    if (int rc = check_window(window, L.width, L.height, what, 0)) return rc;
+    if (q4_pitch_cells < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch_cells, L.width / 2);
+    if (d_out && out_pitch < L.width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < width %d", what, out_pitch, L.width);
+    if (d_out && overlaps_input(d_out, out_pitch, {d_image1, d_image2}, L.width, L.width, L.height))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input plane", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = sc_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_sc(c, d_image1, d_image2, 0, reinterpret_cast<const mv_t *>(d_q4), q4_pitch_cells, 0, 1, fill, window, d_out, out_pitch,
+                      c->sc_stats.partials_caller(), d_stats4, stream);
+}
+
+// what bbme_subpel_compensate_device and bbme_get_subpel_compensated_host check alike.  Touches no device.
+static int check_sc_own(const bbme_ctx *c, int pair, int which, int fill, const void *out, const char *what)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (int rc = check_fill(fill, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    return check_sp(c, nullptr, what);
+}
+
+int bbme_subpel_compensate_device(bbme_ctx *c, int pair, int which, int fill, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    const char *what = "bbme_subpel_compensate_device";
+    if (int rc = check_sc_own(c, pair, which, fill, d_out, what)) return rc;
+    if (out_pitch < c->lv[0].width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < width %d", what, out_pitch, c->lv[0].width);
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;       // the state, before anything is enqueued
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_sc(c, pair, 1, which, fill, nullptr, d_out, out_pitch, nullptr, stream, what);
+}
+
+int bbme_get_subpel_compensated_host(bbme_ctx *c, int pair, int which, int fill, uint8_t *out)
+{
+    const char *what = "bbme_get_subpel_compensated_host";
+    if (int rc = check_sc_own(c, pair, which, fill, out, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[0];
+    return download_staged(c, (size_t)L.width * L.height, "the quarter-pel compensated plane", out, [&](uint8_t *d) {
+        return enqueue_own_sc(c, pair, 1, which, fill, nullptr, d, L.width, nullptr, c->stream, what);
+    });
+}
+
+int bbme_subpel_compensation_error(bbme_ctx *c, int which, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_subpel_compensation_error";
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (int rc = check_sp(c, nullptr, what)) return rc;
+    if (int rc = check_window(window, c->lv[0].width, c->lv[0].height, what, 0)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = sc_scratch(c)) return rc;
+    return download_stats(c, c->sc_stats, c->batch, stats, [&] {
+        return enqueue_own_sc(c, 0, c->batch, which, 0, window, nullptr, 0, c->sc_stats.results(), c->stream, what);
     });
 }
 

@@ -986,6 +986,50 @@ int bbme_subpel_host(const uint8_t *image1, const uint8_t *image2, int width, in
     return BBME_OK;
 }
 
+// The SUBPEL COMPENSATION RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_subpel_compensate).  A
+// tap of weight 0 is not read: it may lie outside the plane.
+int bbme_subpel_compensate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *q4, int fill,
+                                const int *window, uint8_t *out, unsigned long long *stats4)
+{
+    const char *what = "bbme_subpel_compensate_host";
+    if (!image2 || !q4 || (!out && !stats4) || (stats4 && !image1)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
+    if (fill < 0 || fill > 255) return bbme::fail(BBME_ERR_INVALID, "%s: fill %d outside 0..255", what, fill);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, width, height, what, "plane")) return rc;
+    const int cw = width / 2, ch = height / 2;
+    unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const int16_t *q = q4 + 2 * ((size_t)cy * cw + cx);
+            const int ox = 2 * cx, oy = 2 * cy;
+            const int ix = q[0] >> 2, iy = q[1] >> 2, fx = q[0] & 3, fy = q[1] & 3;
+            const int sx = ox + ix, sy = oy + iy;
+            const bool ok = 0 <= sx && sx + 2 + (fx != 0) <= width && 0 <= sy && sy + 2 + (fy != 0) <= height;
+            for (int k = 0; k < 2; ++k)
+                for (int j = 0; j < 2; ++j) {
+                    int v = fill;
+                    if (ok) {
+                        const auto tap = [&](int weight, int dx, int dy) {
+                            return weight ? weight * image2[(size_t)(sy + k + dy) * width + sx + j + dx] : 0;
+                        };
+                        v = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+                    }
+                    const size_t at = (size_t)(oy + k) * width + ox + j;
+                    if (out) out[at] = (uint8_t)v;
+                    if (!stats4 || !win.contains(ox + j, oy + k)) continue;
+                    if (!ok) { ++skipped; continue; }
+                    const int d = v - image1[at];
+                    sse += (unsigned long long)(d * d);
+                    sad += (unsigned long long)(d < 0 ? -d : d);
+                    ++pixels;
+                }
+        }
+    if (stats4) { stats4[0] = sse; stats4[1] = sad; stats4[2] = pixels; stats4[3] = skipped; }
+    return BBME_OK;
+}
+
 int bbme_spiral_host(int search_size, int block_size, int16_t *dx, int16_t *dy, int capacity, int *count)
 {
     if (!count) return bbme::fail(BBME_ERR_INVALID, "bbme_spiral_host: null count");

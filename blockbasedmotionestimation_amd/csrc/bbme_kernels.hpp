@@ -2937,7 +2937,7 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
-// k_temporal_filter and K9b k_temporal_filter_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_temporal_filter, K9b k_temporal_filter_bgr and K11 k_subpel_compensate.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window.
 // =======================================================================================
@@ -3951,6 +3951,141 @@ __global__ __launch_bounds__(256) void k_subsample_q4(const mv_t *cells, int cel
     const mv_t m = cells[(size_t)((pad_y + scale * y) >> 1) * cell_cols + ((pad_x + scale * x) >> 1)];
     const float s = (float)(4 * scale);
     *reinterpret_cast<float2 *>(out + 2 * (size_t)t) = make_float2((float)mv_x(m) / s, (float)mv_y(m) / s);
+}
+
+// =======================================================================================
+// K11.  Motion compensation along a quarter-pel grid, fused with the residual statistics against I1 (the SUBPEL COMPENSATION RULE
+// of include/bbme.h): cell (cx, cy) with origin o and (qx, qy) = Q[cy][cx] takes its 2 x 2 pixels as the SUBPEL RULE's bilinear
+// samples of I2 at s = o + (qx >> 2, qy >> 2) with the fractions f = (qx & 3, qy & 3); a cell one of whose taps of non-zero weight
+// would leave the plane is skipped and gets `fill`.  It is k_motion_compensate's sibling in the gather family: the shared split of
+// runs of 4 cells of one cell row (gather_index / gather_split), Q by load_mv4, blockIdx.y = pair.
+// Loads.  A cell needs 2 + (fx != 0) bytes of 2 + (fy != 0) rows of I2 at an arbitrary byte address.  The third row and the third
+// column are addressed at offset 1 + (f != 0): where the fraction is 0 they fold onto the second (their weight is 0 then), so no
+// address leaves the plane that the rule does not name.  A row's bytes are one unaligned dword when the four bytes from s.x on lie
+// in the row (s.x + 4 <= W0: all but cells at the right edge), else an unaligned u16 and a byte: three loads a cell, where widening
+// every load to a dword could touch the byte behind a caller's plane.  The sample is the separable form: the horizontal sums of the
+// three rows, then the vertical sums with the single rounding.
+// Stores.  A run is 8 bytes in each of two pixel rows: one 8-byte store when the run is whole and the address 8-byte aligned
+// (a caller's rows need not be), bytes otherwise.  I1 is read -- 8 bytes a row, or a cell at a time on a cut run -- only for cell
+// rows that meet the window.
+// Statistics over the window [wx0, wx1) x [wy0, wy1) in PIXELS: sse, sad and pixels over the compensated cells' window pixels,
+// skipped over the others'.  A lane sums at most kScRunsPerLane runs of 16 pixels in 32 bits, and a wave's sum stays below 2^32:
+// 64 * kScRunsPerLane * 16 * 255^2 = 133 171 200 (store_partial4, frame = pair).
+// =======================================================================================
+struct ScArgs {
+    const uint8_t *img1, *img2;           // packed width x height planes; img1 may be null without statistics
+    const mv_t *q4;                       // quarter-pel vectors: cw entries per row, rows q4_pitch cells apart
+    uint8_t *out;                         // compensated plane (rows out_pitch bytes apart), or null
+    unsigned long long *partial;          // per pair and workgroup {sse, sad, pixels, skipped}; or null (no statistics)
+    size_t s_plane, s_q4;                 // from pair to pair: bytes, words
+    int width, height, cw, q4_pitch, fill, out_pitch;
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kScRunsPerLane = 2;
+
+// bytes s.x, s.x + 1 and s.x + 1 + x1 of a row of I2 (p = the row's byte s.x) in bits 0-7, 8-15 and 16-23
+__device__ __forceinline__ uint32_t sc_row(const uint8_t *p, bool wide, int x1)
+{
+    if (wide) {
+        const uint32_t v = reinterpret_cast<const ua_u32 *>(p)->v;
+        return x1 ? v & 0x00ffffffu : (v & 0xffffu) | ((v & 0xff00u) << 8);
+    }
+    return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)p[1 + x1] << 16;
+}
+
+__global__ __launch_bounds__(256) void k_subpel_compensate(ScArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const uint8_t *I2 = a.img2 + pair * a.s_plane;
+    const mv_t *Q = a.q4 + pair * a.s_q4;
+    const int W = a.width, H = a.height, CW = a.cw;
+    uint32_t sse = 0, sad = 0, npix = 0, nskip = 0;
+#pragma unroll
+    for (int r = 0; r < kScRunsPerLane; ++r) {
+        const long long i = gather_index<kScRunsPerLane>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        const int oy = 2 * cy;
+        uint32_t q[4];
+        load_mv4(Q + (size_t)cy * a.q4_pitch + x0, n, q);
+        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ok = 0;  // the two pixel rows of the run; bit j: cell x0 + j was compensated
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int qx = mv_x(q[j]), qy = mv_y(q[j]);
+            const int fx = qx & 3, fy = qy & 3, x1 = fx != 0, y1 = fy != 0;
+            const int sx = 2 * (x0 + j) + (qx >> 2), sy = oy + (qy >> 2);
+            uint32_t px = (uint32_t)a.fill * 0x01010101u;     // the cell: its upper pixels in bits 0-15, its lower ones in 16-31
+            if (sx >= 0 && sx + 2 + x1 <= W && sy >= 0 && sy + 2 + y1 <= H) {
+                const uint8_t *p = I2 + (size_t)sy * W + sx;
+                const bool wide = sx + 4 <= W;
+                const uint32_t t0 = sc_row(p, wide, x1), t1 = sc_row(p + W, wide, x1), t2 = sc_row(p + (size_t)(1 + y1) * W, wide, x1);
+                const uint32_t wx = (uint32_t)fx, wy = (uint32_t)fy;
+                uint32_t h[3][2];                             // (4 - fx) P0 + fx P1 of the three rows' two pixels, <= 1020
+                h[0][0] = (4u - wx) * (t0 & 0xffu) + wx * ((t0 >> 8) & 0xffu); h[0][1] = (4u - wx) * ((t0 >> 8) & 0xffu) + wx * (t0 >> 16);
+                h[1][0] = (4u - wx) * (t1 & 0xffu) + wx * ((t1 >> 8) & 0xffu); h[1][1] = (4u - wx) * ((t1 >> 8) & 0xffu) + wx * (t1 >> 16);
+                h[2][0] = (4u - wx) * (t2 & 0xffu) + wx * ((t2 >> 8) & 0xffu); h[2][1] = (4u - wx) * ((t2 >> 8) & 0xffu) + wx * (t2 >> 16);
+                px = 0;
+#pragma unroll
+                for (int k = 0; k < 2; ++k)
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) px |= (((4u - wy) * h[k][m] + wy * h[k + 1][m] + 8u) >> 4) << (16 * k + 8 * m);
+                ok |= 1u << j;
+            }
+            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
+            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+        }
+        if (a.out) {
+            uint8_t *o = a.out + (size_t)oy * a.out_pitch + 2 * x0;
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                const uint32_t *row = yy ? row1 : row0;
+                uint8_t *d = o + (size_t)yy * a.out_pitch;
+                if (n == 4 && ((uintptr_t)d & 7u) == 0) *reinterpret_cast<uint2 *>(d) = make_uint2(row[0], row[1]);
+                else for (int x = 0; x < 2 * n; ++x) d[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+            }
+        }
+        if (a.partial && oy + 1 >= a.wy0 && oy < a.wy1) {
+            const uint8_t *r1 = a.img1 + pair * a.s_plane + (size_t)oy * W + 2 * x0;
+            uint32_t ref0[2] = {0, 0}, ref1[2] = {0, 0};
+            if (n == 4) {
+                const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(r1), u = *reinterpret_cast<const ua_u32x2 *>(r1 + W);
+                ref0[0] = t.v[0]; ref0[1] = t.v[1]; ref1[0] = u.v[0]; ref1[1] = u.v[1];
+            } else {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    if (j >= n) break;
+                    ref0[j >> 1] |= (uint32_t)reinterpret_cast<const ua_u16 *>(r1 + 2 * j)->v << (16 * (j & 1));
+                    ref1[j >> 1] |= (uint32_t)reinterpret_cast<const ua_u16 *>(r1 + W + 2 * j)->v << (16 * (j & 1));
+                }
+            }
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                if (oy + yy < a.wy0 || oy + yy >= a.wy1) continue;
+                const uint32_t *row = yy ? row1 : row0, *ref = yy ? ref1 : ref0;
+#pragma unroll
+                for (int x = 0; x < 8; ++x) {
+                    const int X = 2 * x0 + x;
+                    if (x >= 2 * n || X < a.wx0 || X >= a.wx1) continue;
+                    if ((ok >> (x >> 1)) & 1u) {
+                        const int d = (int)((row[x >> 2] >> (8 * (x & 3))) & 0xffu) - (int)((ref[x >> 2] >> (8 * (x & 3))) & 0xffu);
+                        sse += (uint32_t)(d * d);
+                        sad += (uint32_t)abs(d);
+                        ++npix;
+                    } else {
+                        ++nskip;
+                    }
+                }
+            }
+        }
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, pair, part, sse, sad, npix, nskip);
 }
 
 }  // namespace bbme

@@ -3,6 +3,7 @@
 //   bbme_cli frame10.pgm|.ppm frame11.pgm|.ppm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
 //            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T] [--subpel sub.flo]
+//            [--mc-subpel mcq.pgm]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -26,6 +27,8 @@
 // --subpel writes the estimated field refined to quarter-pel on the planes the estimate ran on (the subpel rule of include/bbme.h),
 // through the same writer as --out, and with --gt prints its EPE too: with --no-upsample sub-pixel vectors at the frames' own
 // resolution, a sixteenth of the pixels of the reference's pipeline; without it sixteenths of a pixel of the frames read.
+// --mc-subpel writes --mc's frame made along those quarter-pel vectors instead (the subpel compensation rule of include/bbme.h:
+// bilinear quarter-pel samples of frame 2), the same unpadded crop, and prints the PSNR of both predictions against frame 1.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -76,7 +79,7 @@ static bool read_pnm(const char *path, bbme::Image8 &img, bbme::ImageBGR &bgr, b
 int main(int argc, char **argv)
 {
     const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
-               *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr;
+               *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr, *mc_subpel = nullptr;
     int factor = 2, strength = 64;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
@@ -87,6 +90,7 @@ int main(int argc, char **argv)
         else if (a == "--out") out = next();
         else if (a == "--color") color = next();
         else if (a == "--mc") mc = next();
+        else if (a == "--mc-subpel") mc_subpel = next();
         else if (a == "--backward") backward = next();
         else if (a == "--occlusion") occlusion = next();
         else if (a == "--interpolate") interpolate = next();
@@ -109,7 +113,7 @@ int main(int argc, char **argv)
         fprintf(stderr, "usage: bbme_cli frame1.pgm|.ppm frame2.pgm|.ppm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
-                        "[--denoise PREFIX --strength T] [--subpel sub.flo]\n"
+                        "[--denoise PREFIX --strength T] [--subpel sub.flo] [--mc-subpel mcq.pgm]\n"
                         "--denoise writes PREFIX_1.pgm and PREFIX_2.pgm (on .ppm frames their luma) and, on .ppm frames, the "
                         "filtered colour frames PREFIX_1.ppm and PREFIX_2.ppm; it needs --no-upsample\n");
         return 2;
@@ -173,6 +177,15 @@ int main(int argc, char **argv)
             bbme::check(bbme_pgm_write(mc, img.cols - 2 * px, img.rows - 2 * py, img.cols, img.data.data() + (size_t)py * img.cols + px));
             const bbme::CompensationError e = motion_pair.compensationError(0, 2);
             printf("MC PSNR is %.9g dB over %llu pixels (%llu skipped)\n", e.psnr(), e.pixels, e.skipped);
+        }
+        if (mc_subpel) {
+            const bbme::Image8 img = motion_pair.drawMVimageSubpel(false, 0);
+            const int px = motion_pair.padding_x, py = motion_pair.padding_y;
+            bbme::check(bbme_pgm_write(mc_subpel, img.cols - 2 * px, img.rows - 2 * py, img.cols,
+                                       img.data.data() + (size_t)py * img.cols + px));
+            const bbme::CompensationError e = motion_pair.compensationError(0, 2), q = motion_pair.compensationErrorSubpel();
+            printf("Quarter-pel MC PSNR is %.9g dB (integer vectors: %.9g dB) over %llu pixels (%llu skipped)\n", q.psnr(), e.psnr(),
+                   q.pixels, q.skipped);
         }
         if (backward) {
             // the subsampled getter reads the context's current field: estimate in direction BACKWARD, then back to FORWARD

@@ -217,6 +217,29 @@ public:
         e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3];
         return e;
     }
+    // drawMVimage(0, 2) along the cells refined to quarter-pel (the SUBPEL COMPENSATION RULE of include/bbme.h): the padded level-0
+    // plane; backward = image 2 predicted from image 1 along the backward cells of estimateBidirectional.
+    bbme::Image8 drawMVimageSubpel(bool backward = false, int fill = 0)
+    {
+        int w = 0, h = 0;
+        bbme::check(bbme_level_geometry(ctx_, 0, &w, &h, nullptr, nullptr));
+        bbme::Image8 img(h, w);
+        bbme::check(bbme_get_subpel_compensated_host(ctx_, 0, backward ? 1 : 0, fill, img.data.data()));
+        return img;
+    }
+    // The residual statistics of that frame against the image it predicts over window {x0, y0, w, h} in pixels; nullptr = the
+    // unpadded frame.
+    bbme::CompensationError compensationErrorSubpel(bool backward = false, const int *window = nullptr)
+    {
+        int w = 0, h = 0;
+        bbme::check(bbme_level_geometry(ctx_, 0, &w, &h, nullptr, nullptr));
+        const int unpadded[4] = {padding_x, padding_y, w - 2 * padding_x, h - 2 * padding_y};
+        unsigned long long s[4] = {0, 0, 0, 0};
+        bbme::check(bbme_subpel_compensation_error(ctx_, backward ? 1 : 0, window ? window : unpadded, s));
+        bbme::CompensationError e;
+        e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3];
+        return e;
+    }
     // Direction of the context (include/bbme.h): backward = every estimate and result as if image1 and image2 were exchanged.
     void setDirection(bool backward) { bbme::check(bbme_set_direction(ctx_, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD)); }
     bool direction() const

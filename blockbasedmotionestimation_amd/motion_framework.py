@@ -320,13 +320,7 @@ class MF:
         pairs = getattr(self, "batch", 1)
         s = (C.c_ulonglong * (4 * pairs))()
         _capi.check(self._lib.bbme_compensation_error(self._ctx, level, block, win, s))
-        out = []
-        for p in range(pairs):
-            sse, sad, pixels, skipped = s[4 * p:4 * p + 4]
-            mse = sse / pixels if pixels else math.nan
-            psnr = math.nan if not pixels else math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * pixels / sse)
-            out.append(dict(sse=sse, sad=sad, pixels=pixels, skipped=skipped, mse=mse, psnr=psnr))
-        return out
+        return [_residual_dict(s[4 * p:4 * p + 4]) for p in range(pairs)]
 
     def compensation_error(self, level=0, block=2, window=None):
         """Residual statistics of draw_MVimage(level, block) against image1 over window (x0, y0, w, h) of the level plane:
@@ -507,6 +501,66 @@ class MF:
             self._ctx, C.c_void_p(i1.data_ptr()), C.c_void_p(i2.data_ptr()), C.c_void_p(cells.data_ptr()), win,
             C.c_void_p(out.data_ptr() if out is not None else 0), out.stride(0) // 2 if out is not None else 0,
             C.c_void_p(stats.data_ptr() if stats is not None else 0), C.c_void_p(stream or 0)))
+        return out, stats
+
+    # -- motion compensation along the quarter-pel cells (the SUBPEL COMPENSATION RULE of include/bbme.h) ---------------------------
+    def _get_subpel_compensated(self, pair, which, fill, out, what):
+        out = _host_out(out, (self.padded_height, self.padded_width), np.uint8, what)
+        _capi.check(self._lib.bbme_get_subpel_compensated_host(self._ctx, pair, _which(which), fill, out.ctypes.data))
+        return out
+
+    def draw_MVimage_subpel(self, which="forward", fill=0, out=None):
+        """draw_MVimage(0, 2) along the cells refined to quarter-pel (subpel_cells(which)): the padded (H_pad, W_pad) uint8 plane,
+        every 2x2 cell the bilinear quarter-pel samples of the other image where its vector points, cells whose samples leave
+        the plane set to `fill`.  which="forward": image 1 predicted from image 2; "backward": image 2 from image 1 along the
+        backward cells, after estimate_bidirectional_async().  An upsample=4 context compensates its 4x planes."""
+        return self._get_subpel_compensated(0, which, fill, out, "draw_MVimage_subpel")
+
+    def _subpel_compensation_stats(self, which, window):
+        if window is None:
+            window = (self.padding_x, self.padding_y, self.orig_width, self.orig_height)
+        pairs = getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_subpel_compensation_error(self._ctx, _which(which), _window(window), s))
+        return [_residual_dict(s[4 * p:4 * p + 4]) for p in range(pairs)]
+
+    def compensation_error_subpel(self, which="forward", window=None):
+        """Residual statistics of draw_MVimage_subpel(which) against the image it predicts (image 1 for "forward", image 2 for
+        "backward") over window (x0, y0, w, h) in pixels of the padded plane: the dict of compensation_error.  Default window:
+        the unpadded frame."""
+        return self._subpel_compensation_stats(which, window)[0]
+
+    def cells_compensate_subpel_device(self, i1, i2, q4, out=None, stats=None, fill=0, window=None, stream=None):
+        """The subpel compensation rule on any planes and any quarter-pel grid in HBM: i1 (None without stats), i2 contiguous
+        uint8 CUDA tensors (H_pad, W_pad); q4 an int16 CUDA tensor (CH, CW, 2) whose rows may be further apart than CW cells
+        (what cells_subpel_device wrote); out a uint8 CUDA tensor (H_pad, W_pad) with unit column stride whose rows may be
+        further apart than W_pad, at any byte address; stats an int64 or uint64 CUDA tensor of 4 (sse, sad, pixels, skipped)
+        over window (x0, y0, w, h) in pixels (None = the whole plane).  On the given HIP stream handle (default: the
+        context's), ordered behind the context's stream; no host wait.  Needs no frames and no estimate."""
+        import torch
+        what = "cells_compensate_subpel_device"
+        ch, cw = self.cells_shape
+        for t in (i2,) if i1 is None and stats is None else (i1, i2):
+            if t is None or not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (2 * ch, 2 * cw) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: planes must be contiguous uint8 CUDA tensors of shape (%d, %d)"
+                                      % (what, 2 * ch, 2 * cw))
+        if not (q4.is_cuda and q4.dtype == torch.int16 and tuple(q4.shape) == (ch, cw, 2) and q4.stride(2) == 1
+                and q4.stride(1) == 2 and q4.stride(0) >= 2 * cw and q4.stride(0) % 2 == 0 and q4.data_ptr() % 4 == 0):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: q4 must be an int16 CUDA tensor of shape (%d, %d, 2) with packed cells "
+                                  "and rows a whole number of cells apart" % (what, ch, cw))
+        if out is None and stats is None:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: neither out nor stats" % what)
+        if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (2 * ch, 2 * cw)
+                                    and out.stride(1) == 1 and out.stride(0) >= 2 * cw):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape (%d, %d) with unit column stride"
+                                  % (what, 2 * ch, 2 * cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 4" % what)
+        self._behind_torch(i1, i2, q4, out, stats)
+        _capi.check(self._lib.bbme_cells_subpel_compensate_device(
+            self._ctx, _ptr(i1), _ptr(i2), _ptr(q4), q4.stride(0) // 2, int(fill), _window(window), _ptr(out),
+            out.stride(0) if out is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
         return out, stats
 
     # -- colour coding of the field: Flow::MotionToColor on the GPU, from the cells (the colour rule of include/bbme.h) ----------
@@ -1041,6 +1095,14 @@ class MFBatch(MF):
         """MF.subpel_stats of every pair, from one launch -> list of dicts."""
         return self._subpel_stats(which, window)
 
+    def get_pair_motion_compensated_subpel(self, pair, which="forward", fill=0, out=None):
+        """MF.draw_MVimage_subpel of one pair."""
+        return self._get_subpel_compensated(pair, which, fill, out, "get_pair_motion_compensated_subpel")
+
+    def compensation_errors_subpel(self, which="forward", window=None):
+        """MF.compensation_error_subpel of every pair, in order, from one refinement and one compensation launch."""
+        return self._subpel_compensation_stats(which, window)
+
     def consistency_stats_all(self, which="forward", tol=1, window=None):
         """MF.consistency_stats of every pair, in order, from one launch."""
         return self._consistency_stats(which, tol, window)
@@ -1246,6 +1308,33 @@ def subpel_cells(image1, image2, cells, window=None):
     _capi.check(_capi.lib().bbme_subpel_host(image1.ctypes.data, image2.ctypes.data, w, h, cells.ctypes.data, _window(window),
                                              out.ctypes.data, s))
     return out, dict(zip(_SUBPEL_STATS, list(s)))
+
+
+def _residual_dict(s):
+    """dict(sse, sad, pixels, skipped, mse, psnr) of the four residual statistics of a compensation rule."""
+    sse, sad, pixels, skipped = s
+    mse = sse / pixels if pixels else math.nan
+    psnr = math.nan if not pixels else math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * pixels / sse)
+    return dict(sse=sse, sad=sad, pixels=pixels, skipped=skipped, mse=mse, psnr=psnr)
+
+
+def compensate_cells_subpel(image1, image2, q4, fill=0, window=None):
+    """The subpel compensation rule of include/bbme.h on the CPU (bbme_subpel_compensate_host): image1, image2 uint8 (H, W)
+    planes (both even), q4 an int16 (H / 2, W / 2, 2) grid of quarter-pel vectors on image1 into image2 (subpel_cells' output)
+    -> (compensated plane (H, W) uint8, dict(sse, sad, pixels, skipped, mse, psnr) against image1 over window (x0, y0, w, h)
+    in pixels, None = the whole plane)."""
+    image1 = np.ascontiguousarray(image1, np.uint8)
+    image2 = np.ascontiguousarray(image2, np.uint8)
+    q4 = np.ascontiguousarray(q4, np.int16)
+    if image1.ndim != 2 or image1.shape != image2.shape or q4.shape != (image1.shape[0] // 2, image1.shape[1] // 2, 2):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "compensate_cells_subpel: two uint8 planes of one shape (H, W) and an int16 grid "
+                                                 "(H / 2, W / 2, 2)")
+    h, w = image1.shape
+    out = np.empty((h, w), np.uint8)
+    s = (C.c_ulonglong * 4)()
+    _capi.check(_capi.lib().bbme_subpel_compensate_host(image1.ctypes.data, image2.ctypes.data, w, h, q4.ctypes.data, int(fill),
+                                                        _window(window), out.ctypes.data, s))
+    return out, _residual_dict(list(s))
 
 
 def cells_consistency(a, b, tol=1, window=None):

@@ -736,8 +736,8 @@ int bbme_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, un
  * q != (0, 0), the sum of cost(0, 0) over the valid cells and the sum of best over the valid cells.  The statistics do not need
  * the grid to be written.
  * A context made for up-sampled frames (bbme_set_frames_*_x4) refines its 4x planes: the result is then 1/16 pel of the source.
- * A colour context refines on its luma planes.  Nothing that takes a cell grid (compensation, interpolation, the temporal
- * filters) reads quarter-pel vectors: their rules are integer.
+ * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE below reads quarter-pel vectors; the other rules
+ * that take a cell grid (integer compensation, interpolation, the temporal filters) do not: they are integer.
  * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, q4_pitch_cells < CW, a
  * window as for the consistency rule, a d_q4 of bbme_cells_subpel_device that overlaps its input grid, an odd width or height on
  * the host call; BBME_ERR_UNSUPPORTED beyond 8188; BBME_ERR_STATE when frames are unset or a chain slot is unset, for which = 0
@@ -771,6 +771,58 @@ int bbme_subpel_device(bbme_ctx *ctx, int pair, int which, int16_t *d_q4, int q4
 int bbme_get_subpel_cells_host(bbme_ctx *ctx, int pair, int which, int16_t *q4);
 int bbme_subpel_stats(bbme_ctx *ctx, int which, const int *window, unsigned long long *stats);
 int bbme_get_subpel_flow_host(bbme_ctx *ctx, int pair, int which, float *flow);
+
+/* SUBPEL COMPENSATION RULE (this project's own; MF::draw_MVimage, motion_framework.cpp:887-905, knows integer vectors only): the
+ * motion-compensated prediction along a quarter-pel grid, and its residual statistics.  Inputs: two packed planes I1 and I2 of
+ * W0 x H0 bytes (I1 for the statistics only) and a quarter-pel grid Q of CH x CW int16 pairs, CH = H0 / 2, CW = W0 / 2, holding
+ * vectors as the bbme_subpel_* calls write them, "4 v + q"; any int16 values are allowed.  All arithmetic is in 32-bit integers;
+ * >> of a negative number is the arithmetic shift.
+ * Cell.  For cell (cx, cy): o = (2 cx, 2 cy), (qx, qy) = Q[cy][cx], i = (qx >> 2, qy >> 2), f = (qx & 3, qy & 3), s = o + i.
+ * The cell is COMPENSATED when 0 <= s.x, s.x + 2 + (fx != 0) <= W0, 0 <= s.y and s.y + 2 + (fy != 0) <= H0; otherwise it is
+ * SKIPPED and its four pixels get `fill` (0..255).
+ * Sample.  A compensated cell's pixels are MC[o + (j, k)] = sample(s + (j, k), f) for 0 <= j, k < 2: with P00, P10, P01, P11 the
+ * pixels of I2 at s + (j, k) + (0, 0), (1, 0), (0, 1), (1, 1),
+ *   sample = ((4 - fx) (4 - fy) P00 + fx (4 - fy) P10 + (4 - fx) fy P01 + fx fy P11 + 8) >> 4.
+ * This is the SUBPEL RULE's sample, exactly separable as there (the horizontal sums first, then the vertical one with the single
+ * rounding).  A tap whose weight is 0 is not part of the sample, and the validity test is exactly "every tap of non-zero weight
+ * lies in the plane": no byte outside the W0 x H0 plane is read.
+ * Statistics: the four of the compensation rule, over a window {x0, y0, w, h} in PIXELS of the plane (NULL = the whole plane) --
+ * the window of bbme_compensation_error, not the cell window of bbme_subpel_stats.  sse = sum (MC - I1)^2 and sad = sum |MC - I1|
+ * over the window pixels of compensated cells, pixels = their count, skipped = the count of window pixels of skipped cells.  All
+ * four are exact 64-bit integers and do not depend on `fill`.  A window may cut cells: each pixel counts on its own.
+ * Property.  With Q = 4 G for an integer grid G, the frame and the statistics are those of the compensation rule at level 0 with
+ * block 2 and grid_block 2, bit for bit.
+ * A context made for up-sampled frames compensates its 4x planes, a colour context its luma planes.
+ * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, a fill outside
+ * 0..255, a window not inside the plane, q4_pitch_cells < CW, out_pitch < W0, a d_out of bbme_cells_subpel_compensate_device
+ * that overlaps an input plane, an odd width or height on the host call; for the context's own calls BBME_ERR_UNSUPPORTED beyond
+ * 8188 and BBME_ERR_STATE exactly as bbme_subpel_device.  None of the device calls changes context state (grids, memo, flow,
+ * cells, backward cells, captured graphs, colour store); their scratch buffers are the context's own and independent of the
+ * other getters'.  Outputs must not overlap inputs.  All work on single, batched and chain contexts.
+ * bbme_subpel_compensate_host: the rule on the CPU, no GPU, on packed width x height planes (both even) and a packed
+ * (height / 2) x (width / 2) grid; image1 may be NULL without statistics; out (packed) and stats4 each may be NULL, not both.
+ * bbme_cells_subpel_compensate_device: ANY packed planes and ANY quarter-pel grid in HBM of the context's level-0 geometry, grid
+ * rows q4_pitch_cells int16 pairs apart (bbme_subpel_device's strided output can be fed straight in); no frames set and no
+ * estimate needed; d_image1 may be null without d_stats4; d_out (rows out_pitch bytes apart) and d_stats4 each may be null, not
+ * both; on hip_stream (NULL = the ctx stream; another stream is first ordered behind it); no host wait.  It has no size limit of
+ * its own (s is computed in 32 bits from any int16).  Launches with d_stats4 share one scratch buffer per context: the caller
+ * orders those it issues on different streams.
+ * bbme_subpel_compensate_device: the context's own: the cells of `pair` are refined (bbme_subpel_device's `which`) into a
+ * quarter-pel buffer of the context's, allocated at first use, then compensated from it: which = 0 predicts image 1 from image 2
+ * along the current cells (in direction BACKWARD the planes exchange as for every plane-reading call), which = 1 predicts image 2
+ * from image 1 along the backward cells of bbme_estimate_bidirectional.  On a chain context the planes are slots pair and
+ * pair + 1.  The caller orders calls for the same pair that it issues on different streams.
+ * bbme_get_subpel_compensated_host: the same; synchronises; the packed padded W0 x H0 plane.
+ * bbme_subpel_compensation_error: EVERY pair of the context, stats[4 p + k], from one refinement launch and one compensation
+ * launch over all pairs; synchronises.  The statistics are against image 1 for which = 0 and against image 2 for which = 1. */
+int bbme_subpel_compensate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *q4, int fill,
+                                const int *window, uint8_t *out, unsigned long long *stats4);
+int bbme_cells_subpel_compensate_device(bbme_ctx *ctx, const uint8_t *d_image1, const uint8_t *d_image2, const int16_t *d_q4,
+                                        int q4_pitch_cells, int fill, const int *window, uint8_t *d_out, int out_pitch,
+                                        unsigned long long *d_stats4, void *hip_stream);
+int bbme_subpel_compensate_device(bbme_ctx *ctx, int pair, int which, int fill, uint8_t *d_out, int out_pitch, void *hip_stream);
+int bbme_get_subpel_compensated_host(bbme_ctx *ctx, int pair, int which, int fill, uint8_t *out);
+int bbme_subpel_compensation_error(bbme_ctx *ctx, int which, const int *window, unsigned long long *stats);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
