@@ -342,6 +342,11 @@ struct bbme_ctx {
                                                   // grid per pair, allocated at first use (enqueue_own_sc)
     StatsScratch sc_stats;                        // bbme_subpel_compensation_error (every pair) and
                                                   // bbme_cells_subpel_compensate_device (one pair)
+    DevBuf<mv_t> si_q4;                           // the quarter-pel cells the context's own sub-pel interpolation reads: the packed
+                                                  // forward grids of every pair, then their backward grids, allocated at first use
+                                                  // (enqueue_own_si)
+    StatsScratch si_stats;                        // bbme_subpel_interpolation_stats (every pair) and
+                                                  // bbme_cells_subpel_interpolate_device (one pair, `count` phases)
 };
 
 namespace {
@@ -1743,7 +1748,7 @@ int bbme_subsampled_flow_device(bbme_ctx *c, int pair, int scale, float *d_out, 
 
 }  // extern "C": the stages from here on share templates, which need C++ linkage; their entry points have C linkage from bbme.h
 
-// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter, K11) ----
+// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter, K11, K12) ----
 // Every stage is one launch in which a lane takes runs of 4 units (pixels or cells) along a row, over (workgroups, pairs, phases
 // or frames), with optional statistics: the kernel's partials, then k_mc_reduce.  One run split, one launch path, one scratch
 // layout, one pair of output checks and one pair of download helpers serve all of them.
@@ -2225,14 +2230,18 @@ static int check_ip(const bbme_ctx *c, int num0, int count, int den, const int *
 
 // partials of a launch over every pair, then those of a one-pair launch of `count` phases; grown, behind both streams, when a
 // launch of more phases comes
-static int ip_scratch(bbme_ctx *c, int count, hipStream_t stream)
+static int phase_scratch(bbme_ctx *c, StatsScratch &s, long long groups, int count, hipStream_t stream, const char *what)
 {
-    StatsScratch &s = c->ip_stats;
-    s.layout(BBME_MAX_BATCH, cell_groups(c, kIpRunsPerLane), c->batch);
+    s.layout(BBME_MAX_BATCH, groups, c->batch);
     if (s.words(count) <= s.size()) return BBME_OK;
     HIP_TRY(hipStreamSynchronize(c->stream));             // the old buffer may still be being read
     if (stream != c->stream) HIP_TRY(hipStreamSynchronize(stream));
-    return s.ensure(count, "the interpolation statistics");
+    return s.ensure(count, what);
+}
+
+static int ip_scratch(bbme_ctx *c, int count, hipStream_t stream)
+{
+    return phase_scratch(c, c->ip_stats, cell_groups(c, kIpRunsPerLane), count, stream, "the interpolation statistics");
 }
 
 // what IpArgs and IpBgrArgs share: the planes of `pair0`, the two grids, the output frames, the phases and their division
@@ -3099,6 +3108,130 @@ int bbme_subpel_compensation_error(bbme_ctx *c, int which, const int *window, un
     if (int rc = sc_scratch(c)) return rc;
     return download_stats(c, c->sc_stats, c->batch, stats, [&] {
         return enqueue_own_sc(c, 0, c->batch, which, 0, window, nullptr, 0, c->sc_stats.results(), c->stream, what);
+    });
+}
+
+// ---- interpolation at quarter-pel positions (the SUBPEL INTERPOLATION RULE of include/bbme.h; K12 k_subpel_interpolate) ----------
+
+// as ip_scratch, of the context's own buffer for this rule
+static int si_scratch(bbme_ctx *c, int count, hipStream_t stream)
+{
+    return phase_scratch(c, c->si_stats, cell_groups(c, kSiRunsPerLane), count, stream, "the subpel interpolation statistics");
+}
+
+// k_subpel_interpolate over `pairs` pairs from `pair0` on (grids s_q4 words apart) and `count` phases from num0 on: frames and maps
+// (one pair only) and / or, with d_stats, the statistics
+static int enqueue_si(bbme_ctx *c, int pair0, int pairs, const mv_t *d_qf, const mv_t *d_qb, int q4_pitch, size_t s_q4, int num0,
+                      int count, int den, const int *window, uint8_t *d_out, int out_pitch, size_t out_stride, uint8_t *d_sel,
+                      int sel_pitch, size_t sel_stride, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    SiArgs a{};
+    a.img1 = c->plane1(L) + (size_t)pair0 * L.plane_stride;
+    a.img2 = c->plane2(L) + (size_t)pair0 * L.plane_stride;
+    a.qf = d_qf; a.qb = d_qb; a.q4_pitch = q4_pitch;
+    a.s_plane = L.plane_stride; a.s_q4 = s_q4;
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    a.sel = d_sel; a.sel_pitch = sel_pitch; a.sel_stride = sel_stride;
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2;
+    a.num0 = num0; a.den = den;
+    a.magic = (uint32_t)((1ull << 32) / (unsigned)den + 1ull);
+    set_window(a, window, a.cw, L.height / 2);
+    set_runs(a, a.cw, L.height / 2);
+    return launch_gather(k_subpel_interpolate, a, cell_groups(c, kSiRunsPerLane), pairs, count, partial, d_stats, stream);
+}
+
+int bbme_cells_subpel_interpolate_device(bbme_ctx *c, int pair, const int16_t *d_qf, const int16_t *d_qb, int q4_pitch_cells,
+                                         int num0, int count, int den, const int *window, uint8_t *d_out, int out_pitch,
+                                         size_t out_stride, uint8_t *d_sel, int sel_pitch, size_t sel_stride,
+                                         unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_subpel_interpolate_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_qf || (!d_out && !d_sel && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_ip(c, num0, count, den, window, what)) return rc;
+    if (q4_pitch_cells < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch_cells, L.width / 2);
+    if (d_out) if (int rc = check_frames(count, out_pitch, out_stride, L.width, L.height, what, "output")) return rc;
+    if (d_sel) if (int rc = check_frames(count, sel_pitch, sel_stride, L.width / 2, L.height / 2, what, "selection map")) return rc;
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream = hip_stream ? static_cast<hipStream_t>(hip_stream) : c->stream;
+    if (d_stats4) if (int rc = si_scratch(c, count, stream)) return rc;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_si(c, pair, 1, reinterpret_cast<const mv_t *>(d_qf), reinterpret_cast<const mv_t *>(d_qb), q4_pitch_cells, 0, num0,
+                      count, den, window, d_out, out_pitch, out_stride, d_sel, sel_pitch, sel_stride, c->si_stats.partials_caller(),
+                      d_stats4, stream);
+}
+
+// The context's own: the forward and the backward cells of `pairs` pairs from pair0 on refined into the context's quarter-pel
+// buffer (the packed forward grids of every pair, then the backward ones; allocated here at first use), then interpolated from it
+static int enqueue_own_si(bbme_ctx *c, int pair0, int pairs, int num0, int count, int den, const int *window, uint8_t *d_out,
+                          int out_pitch, size_t out_stride, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream,
+                          const char *what)
+{
+    const Level &L = c->lv[0];
+    const int cw = L.width / 2;
+    const size_t cells = (size_t)cw * (L.height / 2), s_plane = L.plane_stride;
+    if (int rc = c->si_q4.ensure(2 * cells * c->batch, "the quarter-pel cells of the interpolation", Fill::poison)) return rc;
+    mv_t *q4[2] = {c->si_q4 + pair0 * cells, c->si_q4 + ((size_t)c->batch + pair0) * cells};
+    for (int which = 0; which < 2; ++which) {
+        const uint8_t *i1, *i2;
+        const mv_t *grid;
+        uint32_t s_grid;
+        if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+        if (int rc = enqueue_sp(c, i1 + pair0 * s_plane, i2 + pair0 * s_plane, s_plane, grid + (size_t)pair0 * s_grid, s_grid, pairs,
+                                nullptr, q4[which], cw, cells, nullptr, nullptr, stream))
+            return rc;
+    }
+    return enqueue_si(c, pair0, pairs, q4[0], q4[1], cw, cells, num0, count, den, window, d_out, out_pitch, out_stride, nullptr, 0, 0,
+                      partial, d_stats, stream);
+}
+
+// what the three calls on the context's own two fields share.  Touches no device.
+static int check_si_own(const bbme_ctx *c, int num0, int count, int den, const int *window, const void *out, const char *what)
+{
+    if (int rc = check_ip_ctx(c, num0, count, den, window, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_sp(c, nullptr, what)) return rc;
+    return check_fields_state(c, what);
+}
+
+int bbme_subpel_interpolate_device(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
+                                   void *hip_stream)
+{
+    const char *what = "bbme_subpel_interpolate_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (d_out) if (int rc = check_frames(count, out_pitch, out_stride, c->lv[0].width, c->lv[0].height, what, "output")) return rc;
+    if (int rc = check_si_own(c, num0, count, den, nullptr, d_out, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_si(c, pair, 1, num0, count, den, nullptr, d_out, out_pitch, out_stride, nullptr, nullptr, stream, what);
+}
+
+int bbme_get_subpel_interpolated_host(bbme_ctx *c, int pair, int num, int den, uint8_t *out)
+{
+    const char *what = "bbme_get_subpel_interpolated_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_si_own(c, num, 1, den, nullptr, out, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[0];
+    return download_staged(c, (size_t)L.width * L.height, "the quarter-pel interpolated frame", out, [&](uint8_t *d) {
+        return enqueue_own_si(c, pair, 1, num, 1, den, nullptr, d, L.width, 0, nullptr, nullptr, c->stream, what);
+    });
+}
+
+int bbme_subpel_interpolation_stats(bbme_ctx *c, int num, int den, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_subpel_interpolation_stats";
+    if (int rc = check_si_own(c, num, 1, den, window, stats, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = si_scratch(c, 1, c->stream)) return rc;
+    return download_stats(c, c->si_stats, c->batch, stats, [&] {
+        return enqueue_own_si(c, 0, c->batch, num, 1, den, window, nullptr, 0, 0, c->si_stats.partials_all(), c->si_stats.results(),
+                              c->stream, what);
     });
 }
 

@@ -1030,6 +1030,64 @@ int bbme_subpel_compensate_host(const uint8_t *image1, const uint8_t *image2, in
     return BBME_OK;
 }
 
+// The SUBPEL INTERPOLATION RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_subpel_interpolate).
+// A tap of weight 0 is not read: it may lie outside the plane.
+int bbme_subpel_interpolate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *qf,
+                                 const int16_t *qb, int num, int den, const int *window, uint8_t *out, uint8_t *sel,
+                                 unsigned long long *stats4)
+{
+    const char *what = "bbme_subpel_interpolate_host";
+    if (!image1 || !image2 || !qf || (!out && !sel && !stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
+    if (den < 2 || den > 256 || num < 1 || num >= den)
+        return bbme::fail(BBME_ERR_INVALID, "%s: phase %d / %d (2 <= den <= 256, 0 < num < den)", what, num, den);
+    const int cw = width / 2, ch = height / 2;
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cw, ch, what, "cells")) return rc;
+    const auto floor_div = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+    // the four rounded samples of the cell at quarter-pel position (px, py) of `img`; false when a tap of non-zero weight leaves it
+    const auto cell = [&](const uint8_t *img, int px, int py, int (&s)[4]) {
+        const int ix = px >> 2, iy = py >> 2, fx = px & 3, fy = py & 3;
+        if (ix < 0 || ix + 2 + (fx != 0) > width || iy < 0 || iy + 2 + (fy != 0) > height) return false;
+        for (int r = 0; r < 2; ++r)
+            for (int j = 0; j < 2; ++j) {
+                const auto tap = [&](int weight, int dx, int dy) {
+                    return weight ? weight * img[(size_t)(iy + r + dy) * width + ix + j + dx] : 0;
+                };
+                s[2 * r + j] = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+            }
+        return true;
+    };
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            int best = -1, best_cost = 0, b1[4] = {0, 0, 0, 0}, b2[4] = {0, 0, 0, 0};
+            for (int k = 0; k < 3; ++k) {
+                if (k == 1 && !qb) continue;
+                const int vx = k == 0 ? qf[2 * c] : k == 1 ? -(int)qb[2 * c] : 0, vy = k == 0 ? qf[2 * c + 1] : k == 1 ? -(int)qb[2 * c + 1] : 0;
+                const int p1x = 8 * cx - floor_div(num * vx + den / 2, den), p1y = 8 * cy - floor_div(num * vy + den / 2, den);
+                int s1[4], s2[4];
+                if (!cell(image1, p1x, p1y, s1) || !cell(image2, p1x + vx, p1y + vy, s2)) continue;
+                int cost = 0;
+                for (int q = 0; q < 4; ++q) cost += abs(s1[q] - s2[q]);
+                if (best < 0 || cost < best_cost) {
+                    best = k; best_cost = cost;
+                    memcpy(b1, s1, sizeof b1); memcpy(b2, s2, sizeof b2);
+                }
+            }
+            if (out)
+                for (int r = 0; r < 2; ++r)
+                    for (int j = 0; j < 2; ++j)
+                        out[(size_t)(2 * cy + r) * width + 2 * cx + j] = (uint8_t)(((den - num) * b1[2 * r + j] + num * b2[2 * r + j] + den / 2) / den);
+            if (sel) sel[c] = (uint8_t)best;
+            if (win.contains(cx, cy)) { ++s[best]; s[3] += (unsigned)best_cost; }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 int bbme_spiral_host(int search_size, int block_size, int16_t *dx, int16_t *dy, int capacity, int *count)
 {
     if (!count) return bbme::fail(BBME_ERR_INVALID, "bbme_spiral_host: null count");

@@ -2937,7 +2937,7 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
-// k_temporal_filter, K9b k_temporal_filter_bgr and K11 k_subpel_compensate.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate and K12 k_subpel_interpolate.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window.
 // =======================================================================================
@@ -4086,6 +4086,172 @@ __global__ __launch_bounds__(256) void k_subpel_compensate(ScArgs a)
     if (!a.partial) return;
     __shared__ uint32_t part[4][4];
     store_partial4(a.partial, pair, part, sse, sad, npix, nskip);
+}
+
+// =======================================================================================
+// K12.  Motion-compensated interpolation at phase num / den at QUARTER-PEL positions (the SUBPEL INTERPOLATION RULE of
+// include/bbme.h): output cell (cx, cy) with origin o tries v = QF[cy][cx], v = -QB[cy][cx] (when QB is given) and v = 0, all in
+// quarter pels; a hypothesis samples the 2x2 cell of I1 at P1 = 4 o - round(num v / den) and the one of I2 at P2 = P1 + v as the
+// SUBPEL RULE's bilinear samples, is valid when every tap of non-zero weight of both lies in the plane, and costs the SAD of the
+// ROUNDED samples; the cheapest valid one (the earliest of equals) is blended, ((den - num) S1 + num S2 + den / 2) / den.  It is
+// k_interpolate's and k_subpel_compensate's sibling in the gather family: the shared split of runs of 4 cells of one cell row
+// (gather_index / gather_split), QF and QB by load_mv4 (rows q4_pitch cells apart), blockIdx.y = pair (planes s_plane bytes, grids
+// s_q4 words apart), blockIdx.z = phase num0 + z (frames out_stride, maps sel_stride bytes apart), so that every phase but the
+// first finds planes and grids in L2.  `out` and `sel` only with one pair per launch.
+// Loads.  A moved cell needs 2 + (fx != 0) bytes of 2 + (fy != 0) rows of its plane at an arbitrary byte address: K11's
+// addressing (si_cell through sc_row: the third row and the third column at offset 1 + (f != 0), folding onto the second where the
+// weight is 0; one unaligned dword a row where its four bytes lie in the row, a u16 and a byte at the right edge), three loads a
+// cell and plane, six a hypothesis, and none of them leaves the plane.  The zero hypothesis keeps k_interpolate's loads: one
+// 8-byte load per plane row and run, u16 pairs on a cut run.
+// Arithmetic.  The horizontal sums of the three rows, then the vertical sums with the single rounding; the four samples packed
+// into one dword per cell as ip_cell packs pixels, so that v_sad_u8 gives the cost in one instruction.  The cost is taken on the
+// rounded samples because those are what the blend mixes: it is the SAD of the two cells the output is made of, 0..1020, as in
+// k_interpolate, and with all fractions 0 it is k_interpolate's cost.
+// Divisions by den are k_interpolate's multiply-shifts by magic = floor(2^32 / den) + 1, exact below 2^24 (e <= 256): the blend's
+// numerators stay below 255 * 256 + 128, and |num v| <= (den - 1) 32768 for every int16 v, -(-32768) = 32768 included, so the
+// shifts' num v + den / 2 + 32768 den lies in [32768, 511 * 32768 + 128], below 2^24.  Positions are 32-bit: |P| < 2^17.
+// Stores as k_interpolate: two dwords a row where the row is dword-aligned and the run whole, bytes otherwise; the map by
+// store_bytes4.  Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells that selected k = 0, 1, 2 and the sum of the
+// selected costs; a lane holds at most 4 kSiRunsPerLane cells of cost <= 1020 (store_partial4, frame = (phase, pair)).
+// =======================================================================================
+struct SiArgs {
+    const uint8_t *img1, *img2;           // level-0 padded (luma) planes, pitch = width
+    const mv_t *qf, *qb;                  // quarter-pel grids: cw entries per row, rows q4_pitch cells apart; qb may be null
+    uint8_t *out;                         // frames (rows out_pitch, phases out_stride bytes apart), or null
+    uint8_t *sel;                         // one byte k per cell (rows sel_pitch, phases sel_stride bytes apart), or null
+    unsigned long long *partial;          // per (phase, pair) and workgroup {k = 0, k = 1, k = 2, cost}; or null
+    size_t out_stride, sel_stride;
+    size_t s_plane, s_q4;                 // from pair to pair: bytes, words
+    int width, height, cw, q4_pitch, num0, den, out_pitch, sel_pitch;
+    uint32_t magic;                       // floor(2^32 / den) + 1
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * height / 2
+};
+
+constexpr int kSiRunsPerLane = 2;
+
+// The 2x2 cell of the SUBPEL RULE's samples of a plane at integer position (ix, iy) with the fractions (fx, fy), every tap of
+// non-zero weight inside the plane: row iy's two samples in the low half, row iy + 1's in the high half (as ip_cell)
+__device__ __forceinline__ uint32_t si_cell(const uint8_t *img, int W, int ix, int iy, int fx, int fy)
+{
+    const int x1 = fx != 0, y1 = fy != 0;
+    const uint8_t *p = img + (size_t)iy * W + ix;
+    const bool wide = ix + 4 <= W;
+    const uint32_t t0 = sc_row(p, wide, x1), t1 = sc_row(p + W, wide, x1), t2 = sc_row(p + (size_t)(1 + y1) * W, wide, x1);
+    const uint32_t wx = (uint32_t)fx, wy = (uint32_t)fy;
+    uint32_t h[3][2];                                         // (4 - fx) P0 + fx P1 of the three rows' two pixels, <= 1020
+    h[0][0] = (4u - wx) * (t0 & 0xffu) + wx * ((t0 >> 8) & 0xffu); h[0][1] = (4u - wx) * ((t0 >> 8) & 0xffu) + wx * (t0 >> 16);
+    h[1][0] = (4u - wx) * (t1 & 0xffu) + wx * ((t1 >> 8) & 0xffu); h[1][1] = (4u - wx) * ((t1 >> 8) & 0xffu) + wx * (t1 >> 16);
+    h[2][0] = (4u - wx) * (t2 & 0xffu) + wx * ((t2 >> 8) & 0xffu); h[2][1] = (4u - wx) * ((t2 >> 8) & 0xffu) + wx * (t2 >> 16);
+    uint32_t px = 0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) px |= (((4u - wy) * h[k][m] + wy * h[k + 1][m] + 8u) >> 4) << (16 * k + 8 * m);
+    return px;
+}
+
+// every tap of non-zero weight of the cell at quarter-pel position p (one axis) lies in a plane of `size`
+__device__ __forceinline__ bool si_inside(int p, int size)
+{
+    const int i = p >> 2;
+    return i >= 0 && i + 2 + ((p & 3) != 0) <= size;
+}
+
+__global__ __launch_bounds__(256) void k_subpel_interpolate(SiArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const uint8_t *img1 = a.img1 + pair * a.s_plane, *img2 = a.img2 + pair * a.s_plane;
+    const mv_t *QF = a.qf + pair * a.s_q4, *QB = a.qb ? a.qb + pair * a.s_q4 : nullptr;
+    const int W = a.width, H = a.height, CW = a.cw, den = a.den, num = a.num0 + (int)blockIdx.z, half = den >> 1;
+    const uint32_t magic = a.magic, w1 = (uint32_t)(den - num), w2 = (uint32_t)num;
+    const int bias = 32768 * den;
+    uint32_t n0 = 0, n1 = 0, n2 = 0, csum = 0;
+#pragma unroll
+    for (int r = 0; r < kSiRunsPerLane; ++r) {
+        const long long i = gather_index<kSiRunsPerLane>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        const int oy = 2 * cy;
+        uint32_t qf[4], qb[4] = {0, 0, 0, 0}, z1[4], z2[4];
+        load_mv4(QF + (size_t)cy * a.q4_pitch + x0, n, qf);
+        if (QB) load_mv4(QB + (size_t)cy * a.q4_pitch + x0, n, qb);
+        const size_t o0 = (size_t)oy * W + 2 * x0;
+        if (n == 4) {                                         // the zero hypothesis' cells: 8 bytes of each plane row
+            const ua_u32x2 t1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0), u1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0 + W);
+            const ua_u32x2 t2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0), u2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0 + W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int sh = 16 * (j & 1);
+                z1[j] = ((t1.v[j >> 1] >> sh) & 0xffffu) | ((u1.v[j >> 1] >> sh) << 16);
+                z2[j] = ((t2.v[j >> 1] >> sh) & 0xffffu) | ((u2.v[j >> 1] >> sh) << 16);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                z1[j] = z2[j] = 0;
+                if (j >= n) continue;
+                z1[j] = ip_cell(img1, W, 2 * (x0 + j), oy);
+                z2[j] = ip_cell(img2, W, 2 * (x0 + j), oy);
+            }
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ks = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox4 = 8 * (x0 + j), oy4 = 8 * cy;       // 4 o
+            uint32_t c1 = 0, c2 = 0, k = 2u, cost = ~0u;      // nothing selected yet
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+                if (h == 1 && !QB) break;
+                const int vx = h ? -mv_x(qb[j]) : mv_x(qf[j]), vy = h ? -mv_y(qb[j]) : mv_y(qf[j]);
+                const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
+                const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
+                const int p1x = ox4 - sx, p1y = oy4 - sy, p2x = p1x + vx, p2y = p1y + vy;
+                if (!si_inside(p1x, W) || !si_inside(p2x, W) || !si_inside(p1y, H) || !si_inside(p2y, H)) continue;
+                const uint32_t q1 = si_cell(img1, W, p1x >> 2, p1y >> 2, p1x & 3, p1y & 3);
+                const uint32_t q2 = si_cell(img2, W, p2x >> 2, p2y >> 2, p2x & 3, p2y & 3);
+                const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
+                if (c < cost) { c1 = q1; c2 = q2; k = (uint32_t)h; cost = c; }     // strictly cheaper: the earliest of equals stays
+            }
+            const uint32_t cz = __builtin_amdgcn_sad_u8(z1[j], z2[j], 0u);
+            if (cz < cost) { c1 = z1[j]; c2 = z2[j]; k = 2u; cost = cz; }
+            uint32_t px = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t v = __umulhi(w1 * ((c1 >> (8 * q)) & 0xffu) + w2 * ((c2 >> (8 * q)) & 0xffu) + (uint32_t)half, magic);
+                px |= v << (8 * q);
+            }
+            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
+            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            ks |= k << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                n0 += k == 0u; n1 += k == 1u; n2 += k == 2u;
+                csum += cost;
+            }
+        }
+        if (a.out) {
+            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                const uint32_t *row = y ? row1 : row0;
+                uint8_t *q = o + (size_t)y * a.out_pitch;
+                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
+                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
+                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
+                } else {
+                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+                }
+            }
+        }
+        if (a.sel) store_bytes4(a.sel + blockIdx.z * a.sel_stride + (size_t)cy * a.sel_pitch + x0, n, ks);
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, (size_t)blockIdx.z * gridDim.y + pair, part, n0, n1, n2, csum);
 }
 
 }  // namespace bbme

@@ -3,7 +3,7 @@
 //   bbme_cli frame10.pgm|.ppm frame11.pgm|.ppm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
 //            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T] [--subpel sub.flo]
-//            [--mc-subpel mcq.pgm]
+//            [--mc-subpel mcq.pgm] [--interpolate-subpel PREFIX --factor N]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -29,6 +29,9 @@
 // resolution, a sixteenth of the pixels of the reference's pipeline; without it sixteenths of a pixel of the frames read.
 // --mc-subpel writes --mc's frame made along those quarter-pel vectors instead (the subpel compensation rule of include/bbme.h:
 // bilinear quarter-pel samples of frame 2), the same unpadded crop, and prints the PSNR of both predictions against frame 1.
+// --interpolate-subpel PREFIX --factor N writes --interpolate's frames made at quarter-pel positions instead (the subpel
+// interpolation rule of include/bbme.h: both fields refined to quarter-pel, every cell placed and sampled at its quarter-pel
+// position of the phase), as PREFIX_k.pgm, the same unpadded crop; on colour frames the frames of their luma.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -79,7 +82,8 @@ static bool read_pnm(const char *path, bbme::Image8 &img, bbme::ImageBGR &bgr, b
 int main(int argc, char **argv)
 {
     const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
-               *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr, *mc_subpel = nullptr;
+               *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr, *mc_subpel = nullptr,
+               *interpolate_subpel = nullptr;
     int factor = 2, strength = 64;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
@@ -94,6 +98,7 @@ int main(int argc, char **argv)
         else if (a == "--backward") backward = next();
         else if (a == "--occlusion") occlusion = next();
         else if (a == "--interpolate") interpolate = next();
+        else if (a == "--interpolate-subpel") interpolate_subpel = next();
         else if (a == "--backward-color") backward_color = next();
         else if (a == "--denoise") denoise = next();
         else if (a == "--subpel") subpel = next();
@@ -108,12 +113,13 @@ int main(int argc, char **argv)
         else if (!f2) f2 = argv[i];
         else { fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
     }
-    if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || (interpolate && (factor < 2 || factor > 256)) ||
+    if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || ((interpolate || interpolate_subpel) && (factor < 2 || factor > 256)) ||
         (denoise && (strength < 1 || strength > 1021))) {
         fprintf(stderr, "usage: bbme_cli frame1.pgm|.ppm frame2.pgm|.ppm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
-                        "[--denoise PREFIX --strength T] [--subpel sub.flo] [--mc-subpel mcq.pgm]\n"
+                        "[--denoise PREFIX --strength T] [--subpel sub.flo] [--mc-subpel mcq.pgm] "
+                        "[--interpolate-subpel PREFIX --factor N]\n"
                         "--denoise writes PREFIX_1.pgm and PREFIX_2.pgm (on .ppm frames their luma) and, on .ppm frames, the "
                         "filtered colour frames PREFIX_1.ppm and PREFIX_2.ppm; it needs --no-upsample\n");
         return 2;
@@ -215,6 +221,16 @@ int main(int argc, char **argv)
                 }
                 const bbme::Image8 img = motion_pair.interpolate(k, factor);
                 const std::string name = std::string(interpolate) + "_" + std::to_string(k) + ".pgm";
+                bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
+                                           img.data.data() + (size_t)py * img.cols + px));
+            }
+        }
+        if (interpolate_subpel) {
+            motion_pair.estimateBidirectional();
+            const int px = motion_pair.padding_x, py = motion_pair.padding_y;
+            for (int k = 1; k < factor; ++k) {
+                const bbme::Image8 img = motion_pair.interpolateSubpel(k, factor);
+                const std::string name = std::string(interpolate_subpel) + "_" + std::to_string(k) + ".pgm";
                 bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
                                            img.data.data() + (size_t)py * img.cols + px));
             }

@@ -299,6 +299,14 @@ public:
         bbme::check(bbme_get_interpolated_host(ctx_, 0, num, den, img.data.data()));
         return img;
     }
+    // The same frame at quarter-pel positions (the subpel interpolation rule of include/bbme.h): both fields refined to quarter-pel,
+    // every cell placed and sampled at its quarter-pel position of the phase; on an MF made of colour frames, of the luma planes.
+    bbme::Image8 interpolateSubpel(int num = 1, int den = 2)
+    {
+        bbme::Image8 img(padded_height, padded_width);
+        bbme::check(bbme_get_subpel_interpolated_host(ctx_, 0, num, den, img.data.data()));
+        return img;
+    }
     // Frame `which` (0 = image1, 1 = image2) averaged with the other frame, motion-aligned, where their 2x2 cells match better
     // than `strength` (the temporal filter rule of include/bbme.h) after estimateBidirectional(): the padded plane.
     bbme::Image8 temporalFilter(int strength, int which = 0)

@@ -638,19 +638,21 @@ class MF:
         """What interpolation and the temporal filter write: the padded grey plane or, in colour, the unpadded B,G,R frame."""
         return (self.orig_height, self.orig_width, 3) if bgr else (self.padded_height, self.padded_width)
 
-    def _get_interpolated(self, pair, num, den, out, what, bgr=False):
+    def _get_interpolated(self, pair, num, den, out, what, bgr=False, subpel=False):
         out = _host_out(out, self._out_shape(bgr), np.uint8, what)
-        get = self._lib.bbme_get_interpolated_bgr_host if bgr else self._lib.bbme_get_interpolated_host
+        get = (self._lib.bbme_get_interpolated_bgr_host if bgr else self._lib.bbme_get_subpel_interpolated_host if subpel
+               else self._lib.bbme_get_interpolated_host)
         _capi.check(get(self._ctx, pair, int(num), int(den), out.ctypes.data))
         return out
 
-    def _interpolate_run(self, den, pair, what, bgr):
+    def _interpolate_run(self, den, pair, what, bgr, subpel=False):
         import torch
         den = int(den)
         if not 2 <= den <= 256:
             raise _capi.BbmeError(_capi.ERR_INVALID, "%s %d outside 2..256" % (what, den))
         frames = torch.empty((den - 1,) + self._out_shape(bgr), dtype=torch.uint8, device="cuda:%d" % self.device)
-        run = self._lib.bbme_interpolate_bgr_device if bgr else self._lib.bbme_interpolate_device
+        run = (self._lib.bbme_interpolate_bgr_device if bgr else self._lib.bbme_subpel_interpolate_device if subpel
+               else self._lib.bbme_interpolate_device)
         _capi.check(run(self._ctx, pair, 1, den - 1, den, _ptr(frames), frames.stride(1), frames.stride(0), None))
         self.synchronize()
         return frames.cpu().numpy()
@@ -712,11 +714,12 @@ class MF:
         _capi.check(self._lib.bbme_bgr_frames_device_pair(self._ctx, pair, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def _interpolation_stats(self, num, den, window):
+    def _interpolation_stats(self, num, den, window, subpel=False):
         win = self._stats_window(window)
         pairs = getattr(self, "batch", 1)
         s = (C.c_ulonglong * (4 * pairs))()
-        _capi.check(self._lib.bbme_interpolation_stats(self._ctx, int(num), int(den), win, s))
+        stats = self._lib.bbme_subpel_interpolation_stats if subpel else self._lib.bbme_interpolation_stats
+        _capi.check(stats(self._ctx, int(num), int(den), win, s))
         return [dict(zip(INTERPOLATION_STAT_KEYS, s[4 * p:4 * p + 4])) for p in range(pairs)]
 
     def interpolation_stats(self, num=1, den=2, window=None):
@@ -755,6 +758,60 @@ class MF:
             _ptr(out), out.stride(1) if out is not None else 0, max(out.stride(0), 0) if out is not None else 0,
             _ptr(sel), sel.stride(1) if sel is not None else 0, max(sel.stride(0), 0) if sel is not None else 0,
             _ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+        return out, sel, stats
+
+    # -- interpolation at quarter-pel positions (the SUBPEL INTERPOLATION RULE of include/bbme.h) ------------------------------
+    def interpolate_subpel(self, num=1, den=2, pair=0, out=None):
+        """interpolate() at quarter-pel positions: both fields refined to quarter-pel (subpel_cells("forward") and
+        ("backward")), every 2x2 cell placed at its quarter-pel position of the phase and sampled bilinearly from both frames
+        -> the padded (H_pad, W_pad) uint8 plane.  A block that moves an odd number of pixels lands where it belongs at
+        phase 1 / 2.  An upsample=4 context interpolates its 4x planes, a colour context its luma planes."""
+        return self._get_interpolated(pair, num, den, out, "interpolate_subpel", subpel=True)
+
+    def interpolate_run_subpel(self, den, pair=0):
+        """All den - 1 phases of interpolate_subpel from two refinement launches and one interpolation launch ->
+        (den - 1, H_pad, W_pad) uint8."""
+        return self._interpolate_run(den, pair, "interpolate_run_subpel: den", False, subpel=True)
+
+    def interpolation_stats_subpel(self, num=1, den=2, window=None):
+        """interpolation_stats of interpolate_subpel's frame: dict(forward, backward, zero, cost), the costs on the rounded
+        quarter-pel samples."""
+        return self._interpolation_stats(num, den, window, subpel=True)[0]
+
+    def cells_interpolate_subpel_device(self, qf, qb=None, num0=1, count=1, den=2, pair=0, out=None, sel=None, stats=None,
+                                        window=None, stream=None):
+        """The subpel interpolation rule on the context's planes of `pair` and any two quarter-pel grids in HBM: qf, qb (may be
+        None) int16 CUDA tensors (CH, CW, 2) with packed cells whose rows may be further apart than CW cells (what
+        cells_subpel_device wrote), both with the same row pitch; out, sel and stats as in cells_interpolate_device.  On the
+        given HIP stream handle (default: the context's), ordered behind the context's stream; no host wait.  Needs frames,
+        but no estimate."""
+        import torch
+        what = "cells_interpolate_subpel_device"
+        ch, cw = self.cells_shape
+        count = int(count)
+        for t in (qf, qb):
+            if t is qb and qb is None:
+                continue
+            if t is None or not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.stride(2) == 1
+                                 and t.stride(1) == 2 and t.stride(0) >= 2 * cw and t.stride(0) % 2 == 0 and t.data_ptr() % 4 == 0
+                                 and t.stride(0) == qf.stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: grids must be int16 CUDA tensors of shape (%d, %d, 2) with packed "
+                                      "cells and rows a common whole number of cells apart" % (what, ch, cw))
+        for t, shape, name in ((out, (count, self.padded_height, self.padded_width), "out"), (sel, (count, ch, cw), "sel")):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == shape and t.stride(2) == 1):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: %s must be a uint8 CUDA tensor of shape %s with unit column stride"
+                                      % (what, name, shape))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and tuple(stats.shape) == (count, 4)
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of shape (%d, 4)"
+                                  % (what, count))
+        win = _window(window)
+        self._behind_torch(qf, qb, out, sel, stats)
+        _capi.check(self._lib.bbme_cells_subpel_interpolate_device(
+            self._ctx, pair, _ptr(qf), _ptr(qb), qf.stride(0) // 2, int(num0), count, int(den), win,
+            _ptr(out), out.stride(1) if out is not None else 0, max(out.stride(0), 0) if out is not None else 0,
+            _ptr(sel), sel.stride(1) if sel is not None else 0, max(sel.stride(0), 0) if sel is not None else 0,
+            _ptr(stats), C.c_void_p(stream or 0)))
         return out, sel, stats
 
     # -- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rule of include/bbme.h) ------
@@ -1124,6 +1181,14 @@ class MFBatch(MF):
         """MF.interpolation_stats of every pair, in order, from one launch."""
         return self._interpolation_stats(num, den, window)
 
+    def get_pair_interpolated_subpel(self, pair, num=1, den=2, out=None):
+        """MF.interpolate_subpel of one pair."""
+        return self._get_interpolated(pair, num, den, out, "get_pair_interpolated_subpel", subpel=True)
+
+    def interpolation_stats_subpel_all(self, num=1, den=2, window=None):
+        """MF.interpolation_stats_subpel of every pair, in order, from two refinement launches and one interpolation launch."""
+        return self._interpolation_stats(num, den, window, subpel=True)
+
     def get_frame_filtered(self, pair, which, strength, out=None):
         """MF.temporal_filter of frame `which` of one pair."""
         return self._get_temporal_filtered(pair, which, strength, out, "get_frame_filtered")
@@ -1369,27 +1434,39 @@ def color_cells(cells, width, height, pad_x=0, pad_y=0, scale=1, maxmotion=-1.0)
     return out, tuple(rng)
 
 
-def interpolate_cells(image1, image2, fwd, bwd=None, num=1, den=2, window=None):
-    """The interpolation rule of include/bbme.h on the CPU (bbme_interpolate_host): image1, image2 uint8 (H, W) planes of even
-    size, fwd and bwd (may be None) int16 (H / 2, W / 2, 2) cell grids -> (frame (H, W) uint8, selection (H / 2, W / 2) uint8,
-    dict(forward, backward, zero, cost) over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+def _interpolate_cells(what, host, image1, image2, fwd, bwd, num, den, window):
+    """interpolate_cells and interpolate_cells_subpel: `host` names the C call, `what` the caller in the errors."""
     image1 = np.ascontiguousarray(image1, np.uint8)
     image2 = np.ascontiguousarray(image2, np.uint8)
     fwd = np.ascontiguousarray(fwd, np.int16)
     bwd = None if bwd is None else np.ascontiguousarray(bwd, np.int16)
     if image1.ndim != 2 or image1.shape != image2.shape:
-        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells: two uint8 planes of one shape (H, W)")
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: two uint8 planes of one shape (H, W)" % what)
     h, w = image1.shape
     if fwd.shape != (h // 2, w // 2, 2) or (bwd is not None and bwd.shape != fwd.shape):
-        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells: int16 grids of shape (H / 2, W / 2, 2)")
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: int16 grids of shape (H / 2, W / 2, 2)" % what)
     out = np.empty((h, w), np.uint8)
     sel = np.empty((h // 2, w // 2), np.uint8)
     s = (C.c_ulonglong * 4)()
     win = _window(window)
-    _capi.check(_capi.lib().bbme_interpolate_host(image1.ctypes.data, image2.ctypes.data, w, h, fwd.ctypes.data,
-                                                  None if bwd is None else bwd.ctypes.data, int(num), int(den), win,
-                                                  out.ctypes.data, sel.ctypes.data, s))
+    _capi.check(getattr(_capi.lib(), host)(image1.ctypes.data, image2.ctypes.data, w, h, fwd.ctypes.data,
+                                           None if bwd is None else bwd.ctypes.data, int(num), int(den), win,
+                                           out.ctypes.data, sel.ctypes.data, s))
     return out, sel, dict(zip(INTERPOLATION_STAT_KEYS, list(s)))
+
+
+def interpolate_cells(image1, image2, fwd, bwd=None, num=1, den=2, window=None):
+    """The interpolation rule of include/bbme.h on the CPU (bbme_interpolate_host): image1, image2 uint8 (H, W) planes of even
+    size, fwd and bwd (may be None) int16 (H / 2, W / 2, 2) cell grids -> (frame (H, W) uint8, selection (H / 2, W / 2) uint8,
+    dict(forward, backward, zero, cost) over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    return _interpolate_cells("interpolate_cells", "bbme_interpolate_host", image1, image2, fwd, bwd, num, den, window)
+
+
+def interpolate_cells_subpel(image1, image2, qf, qb=None, num=1, den=2, window=None):
+    """The subpel interpolation rule of include/bbme.h on the CPU (bbme_subpel_interpolate_host): interpolate_cells with qf and
+    qb (may be None) int16 (H / 2, W / 2, 2) grids of QUARTER-PEL vectors (subpel_cells' output), every cell sampled
+    bilinearly at its quarter-pel position -> the same three results."""
+    return _interpolate_cells("interpolate_cells_subpel", "bbme_subpel_interpolate_host", image1, image2, qf, qb, num, den, window)
 
 
 def _temporal_filter_cells(what, cur, prev, next, to_prev, to_next, strength, window, bgr=False, pad_x=0, pad_y=0):

@@ -362,7 +362,7 @@ def estimate_frames_bidirectional(frames, search_size, block_size, device=None, 
     return out
 
 
-def interpolate_frames(frames, search_size, block_size, factor, device=None, in_flight=4, batch=2):
+def interpolate_frames(frames, search_size, block_size, factor, device=None, in_flight=4, batch=2, subpel=False):
     """Frame-rate up-conversion of a video on ONE GPU: every original frame, and factor - 1 interpolated frames (phases k /
     factor, the interpolation rule of include/bbme.h) between each consecutive two -> factor * (len(frames) - 1) + 1 uint8
     (H, W) frames, the interpolated ones the unpadded windows of the padded result.  Runs on the chain plan of
@@ -370,12 +370,17 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
     of a pair come from the same planes, and the factor - 1 frames of a pair from one launch (MF.interpolate_run).
     Colour video: (H, W, 3) frames in B,G,R order give (H, W, 3) frames on the same plan -- the luma planes are made on the
     GPU from the colour frames (the luma rule), the fields are the luma's, and the frames in between come from the stored
-    colour by the BGR interpolation rule (MF.interpolate_run_bgr); still every frame is set once."""
+    colour by the BGR interpolation rule (MF.interpolate_run_bgr); still every frame is set once.
+    subpel=True: the frames in between come from the subpel interpolation rule on the same plan (MF.interpolate_run_subpel:
+    both fields refined to quarter-pel, the cells placed and sampled at quarter-pel positions).  Grey video only: colour output
+    keeps the integer rule, and colour frames with subpel=True are a ValueError."""
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     bgr = bool(frames) and frames[0].ndim == 3
     factor = int(factor)
     if not 2 <= factor <= 256:
         raise ValueError("interpolate_frames: factor %d outside 2..256" % factor)
+    if bgr and subpel:
+        raise ValueError("interpolate_frames: subpel=True takes grey frames; colour output keeps the integer rule")
     n_pairs = len(frames) - 1
     if n_pairs < 1:
         return frames
@@ -389,7 +394,7 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
             if bgr:
                 between[first + p] = list(mf.interpolate_run_bgr(factor, pair=p))
                 continue
-            run = mf.interpolate_run(factor, pair=p)       # waits for this context's stream only
+            run = mf.interpolate_run_subpel(factor, pair=p) if subpel else mf.interpolate_run(factor, pair=p)      # waits for this context's stream only
             between[first + p] = [np.ascontiguousarray(f[py:py + h, px:px + w]) for f in run]
 
     _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect, bidirectional=True)

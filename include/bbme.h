@@ -736,8 +736,9 @@ int bbme_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, un
  * q != (0, 0), the sum of cost(0, 0) over the valid cells and the sum of best over the valid cells.  The statistics do not need
  * the grid to be written.
  * A context made for up-sampled frames (bbme_set_frames_*_x4) refines its 4x planes: the result is then 1/16 pel of the source.
- * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE below reads quarter-pel vectors; the other rules
- * that take a cell grid (integer compensation, interpolation, the temporal filters) do not: they are integer.
+ * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE and the SUBPEL INTERPOLATION RULE below read
+ * quarter-pel vectors; the other rules that take a cell grid (integer compensation, integer and colour interpolation, the
+ * temporal filters) do not: they are integer.
  * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, q4_pitch_cells < CW, a
  * window as for the consistency rule, a d_q4 of bbme_cells_subpel_device that overlaps its input grid, an odd width or height on
  * the host call; BBME_ERR_UNSUPPORTED beyond 8188; BBME_ERR_STATE when frames are unset or a chain slot is unset, for which = 0
@@ -823,6 +824,74 @@ int bbme_cells_subpel_compensate_device(bbme_ctx *ctx, const uint8_t *d_image1, 
 int bbme_subpel_compensate_device(bbme_ctx *ctx, int pair, int which, int fill, uint8_t *d_out, int out_pitch, void *hip_stream);
 int bbme_get_subpel_compensated_host(bbme_ctx *ctx, int pair, int which, int fill, uint8_t *out);
 int bbme_subpel_compensation_error(bbme_ctx *ctx, int which, const int *window, unsigned long long *stats);
+
+/* SUBPEL INTERPOLATION RULE (this project's own): the frame at phase num / den between frame 1 (phase 0) and frame 2 (phase 1) of
+ * a pair, motion-compensated from both fields at QUARTER-PEL positions.  It is the INTERPOLATION RULE with every position in
+ * quarter pels and every cell sampled as in the SUBPEL COMPENSATION RULE: the integer rule places a cell at origin - round(num v /
+ * den) in whole pixels, so a block that moves 1 px per frame cannot be put at phase 1 / 2; this one can.
+ * Inputs: the level-0 padded planes I1 and I2 (W0 x H0 bytes), a quarter-pel grid QF on frame 1 (forward) and, optionally, a
+ * quarter-pel grid QB on frame 2 (backward), CH x CW int16 pairs each (CH = H0 / 2, CW = W0 / 2) holding vectors as the
+ * bbme_subpel_* calls write them, "4 v + q"; any int16 values are allowed; and the phase, 2 <= den <= 256 and 0 < num < den.  All
+ * arithmetic is in 32-bit integers; >> of a negative number is the arithmetic shift; den / 2 is the integer half; floor_div rounds
+ * towards minus infinity.
+ * Output cell (cx, cy) with origin o = (2 cx, 2 cy) has up to three hypotheses, in this order, all in QUARTER pels:
+ *   k = 0: v = QF[cy][cx];   k = 1: v = -QB[cy][cx] (absent without QB);   k = 2: v = (0, 0).
+ * For a hypothesis v = (vx, vy): the shift s = (floor_div(num vx + den / 2, den), floor_div(num vy + den / 2, den)),
+ * P1 = 4 o - s and P2 = P1 + v (so P2 - P1 = v exactly).
+ * Samples.  For a quarter-pel position P: i = (P.x >> 2, P.y >> 2), f = (P.x & 3, P.y & 3), and the cell's four pixels are
+ * S[j, r] = sample(i + (j, r), f) for 0 <= j, r < 2: with P00, P10, P01, P11 the plane's pixels at i + (j, r) + (0, 0), (1, 0),
+ * (0, 1), (1, 1),
+ *   sample = ((4 - fx) (4 - fy) P00 + fx (4 - fy) P10 + (4 - fx) fy P01 + fx fy P11 + 8) >> 4.
+ * This is the SUBPEL RULE's sample, exactly separable as there (the horizontal sums first, then the vertical one with the single
+ * rounding).  S1 samples I1 at P1, S2 samples I2 at P2.  A tap whose weight is 0 is not part of the sample.
+ * Validity.  A hypothesis is valid when every tap of non-zero weight of both cells lies in the plane: for each of P1 and P2,
+ * 0 <= i.x, i.x + 2 + (fx != 0) <= W0, 0 <= i.y and i.y + 2 + (fy != 0) <= H0 (k = 2 always is).  No byte outside the W0 x H0
+ * planes is read.
+ * Its cost is the sum over the four pixels of |S1 - S2| on the ROUNDED samples, 0..1020.  The valid hypothesis of the smallest
+ * cost is selected; of equal costs the earliest.  With its S1 and S2, out[oy + r][ox + j] = ((den - num) S1[j, r] + num S2[j, r]
+ * + den / 2) / den for 0 <= j, r < 2.
+ * The selection map holds one byte k per cell.  The statistics over a window {cx0, cy0, cw, ch} IN CELLS (NULL = all cells) are
+ * four exact 64-bit integers: cells that selected k = 0, k = 1, k = 2, and the sum of the selected costs.
+ * One call makes `count` consecutive phases num0 .. num0 + count - 1 of one den in ONE launch (the phase is a grid dimension;
+ * planes and grids come from L2 for all but the first): frame q at d_out + q out_stride, its map at d_sel + q sel_stride, its
+ * statistics at d_stats4[4 q ..].
+ * Properties.  (1) Integer cases reproduce the INTERPOLATION RULE: with QF = 4 F and QB = 4 B for integer grids F and B, if den
+ * divides num v componentwise for every hypothesis v of every cell, the frame, the map and the statistics are those of the
+ * INTERPOLATION RULE on F and B, bit for bit (every fraction is 0 then).  (2) With both grids zero the result is the in-place
+ * blend of the INTERPOLATION RULE on zero grids.  (3) The grid call has no size limit of its own: |num v| <= (den - 1) 32768 for
+ * every int16 v, -(-32768) included, so num v + den / 2 + 32768 den stays below 2^24, where the multiply-shift by
+ * floor(2^32 / den) + 1 is the exact quotient, and P1 and P2 are computed in 32 bits from any int16.
+ * A context made for up-sampled frames (bbme_set_frames_*_x4) interpolates its 4x planes, a colour context its luma planes (there
+ * is no quarter-pel form of the BGR INTERPOLATION RULE).
+ * Errors: those of the INTERPOLATION RULE's calls, and q4_pitch_cells < CW; for the three calls on the context's own fields
+ * BBME_ERR_STATE exactly as bbme_interpolate_device and BBME_ERR_UNSUPPORTED beyond 8188 as bbme_subpel_device.  None of these
+ * calls changes context state; their scratch buffers are the context's own and independent of the other getters'.  All work on
+ * single, batched and chain contexts; in direction BACKWARD the two planes exchange, as for every plane-reading call.
+ * bbme_subpel_interpolate_host: the rule on the CPU, no GPU, on packed width x height planes (both even) and packed
+ * (height / 2) x (width / 2) grids (qb may be NULL); out, sel (packed) and stats4 each may be NULL, not all three.
+ * bbme_cells_subpel_interpolate_device: the context's planes of `pair` and ANY two quarter-pel grids in HBM of its cell geometry,
+ * rows of both q4_pitch_cells int16 pairs apart (bbme_subpel_device's strided output can be fed straight in; d_qb may be null);
+ * d_out, d_sel and d_stats4 each may be null, not all three; on hip_stream (NULL = the ctx stream; another stream is first ordered
+ * behind it); no host wait; needs no valid pair of fields.  Launches with d_stats4 share one scratch buffer per context: the
+ * caller orders those it issues on different streams.
+ * bbme_subpel_interpolate_device: the context's own, frames only: the forward cells (bbme_subpel_device's which = 0) and the kept
+ * backward cells (which = 1) of `pair` are refined into a quarter-pel buffer of the context's (two packed grids per pair, allocated
+ * at first use, not the compensation's), then interpolated from it.  The caller orders calls for the same pair that it issues on
+ * different streams.
+ * bbme_get_subpel_interpolated_host: one phase of the same; synchronises; packed W0 x H0 bytes.
+ * bbme_subpel_interpolation_stats: EVERY pair, stats[4 p + k], from two refinement launches and one interpolation launch over all
+ * pairs; synchronises. */
+int bbme_subpel_interpolate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *qf,
+                                 const int16_t *qb, int num, int den, const int *window, uint8_t *out, uint8_t *sel,
+                                 unsigned long long *stats4);
+int bbme_cells_subpel_interpolate_device(bbme_ctx *ctx, int pair, const int16_t *d_qf, const int16_t *d_qb, int q4_pitch_cells,
+                                         int num0, int count, int den, const int *window, uint8_t *d_out, int out_pitch,
+                                         size_t out_stride, uint8_t *d_sel, int sel_pitch, size_t sel_stride,
+                                         unsigned long long *d_stats4, void *hip_stream);
+int bbme_subpel_interpolate_device(bbme_ctx *ctx, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch,
+                                   size_t out_stride, void *hip_stream);
+int bbme_get_subpel_interpolated_host(bbme_ctx *ctx, int pair, int num, int den, uint8_t *out);
+int bbme_subpel_interpolation_stats(bbme_ctx *ctx, int num, int den, const int *window, unsigned long long *stats);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
