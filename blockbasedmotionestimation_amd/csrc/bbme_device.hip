@@ -693,11 +693,16 @@ void launch_sweep_t(RegArgs a, const SweepLaunch &s, uint8_t *const (&flags)[2],
     a.flag_cur = flags[cur]; a.flag_next = nullptr;
     a.memo_init = 0;                                       // pass 1 has written every slot
     const dim3 grid2(s.solve_grid, P), waves(64 * s.solve_waves);
+    a.flood = s.flood;
     auto solve = [&](auto SEG) {
+        auto launch = [&](auto MEMO) {
+            if (s.flood > 0) hipLaunchKernelGGL((k_reg_solve<BS, SEG(), MEMO(), true>), grid2, waves, 0, st, a);
+            else hipLaunchKernelGGL((k_reg_solve<BS, SEG(), MEMO()>), grid2, waves, 0, st, a);
+        };
         if constexpr (BS >= 8) {
-            if (s.memo) { hipLaunchKernelGGL((k_reg_solve<BS, SEG(), true>), grid2, waves, 0, st, a); return; }
+            if (s.memo) { launch(std::true_type{}); return; }
         }
-        hipLaunchKernelGGL((k_reg_solve<BS, SEG()>), grid2, waves, 0, st, a);
+        launch(std::false_type{});
     };
     if (s.solve_segment == 4) solve(std::integral_constant<int, 4>{});
     else solve(std::integral_constant<int, 16>{});

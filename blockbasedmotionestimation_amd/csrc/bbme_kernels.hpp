@@ -873,6 +873,8 @@ struct RegArgs {
                                 // waves adding to the same few words is a queue at the memory side that the pyramid need not stand in
     // batch (blockIdx.y = pair): element strides from pair to pair of the per-pair buffers; counters: 64 words
     uint32_t s_plane, s_old, s_est, s_list, s_own, s_flag, s_memo;
+    int flood;                  // k_reg_solve<.., true>: blocks a flood claims ahead of itself (1..3); counters[15] (with `stats`): how
+                                // many speculative evaluations counted
 };
 __device__ __forceinline__ void shift_pair(RegArgs &a, uint32_t p)
 {
@@ -1868,7 +1870,21 @@ __device__ __attribute__((noinline)) uint32_t solver_wait_idle(uint32_t *mail, u
 // s belongs to wave s mod W of that XCD, so that a cluster of stale blocks is spread over many waves
 // instead of queueing up behind one, and a wave looks at 64 of its segments -- 1024 flags -- per memory
 // trip: a sweep that left nothing stale costs two trips at 2 M blocks, not 127.
-template <int BS, int SEG = 16, bool MEMO = false>
+//
+// FLOOD (k_reg_solve<.., true>; never part of the other instantiations' instruction stream): the chain rounds speculate along floods.
+// Nine of ten changes that a neighbour's change triggers adopt that neighbour's new value, so a block that has just taken
+// the value of one of its updated inputs L, UL, U, UR claims, besides its four dependants, up to RegArgs::flood further
+// blocks along that direction and queues them, marked, right behind the dependant that leads them.  A marked entry that
+// is popped into the 16-lane group behind its predecessor is evaluated in the SAME round, with the predecessor's estimate
+// replaced in registers by the value the flood is expected to leave there; the evaluation counts if the predecessor's
+// evaluation counted and gave exactly that value, and then the predecessor does not claim the block again.  The block
+// was claimed before the round, so its other inputs were loaded after its claim, and the estimate it was given is the one
+// the same wave stores before any of the round's claims and releases go out: a kept evaluation is an ordinary owned
+// evaluation, and "work-list state" holds as it stands.  Any other outcome leaves the entry where it was, owned and queued,
+// for an ordinary evaluation.  Marked entries exist in the LDS queues and mailboxes only; the overflow list holds plain indices.
+constexpr uint32_t kFloodEntry = 0x80000000u;   // queue entry: claimed on speculation, behind its predecessor along a flood
+
+template <int BS, int SEG = 16, bool MEMO = false, bool FLOOD = false>
 __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
 {
     static_assert(SEG == 16 || SEG == 4, "flags per scan segment");
@@ -1930,9 +1946,14 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
             if (flag) q[(tail + (uint32_t)__popcll(m & lt_mask)) % QCAP] = v;
             tail = __builtin_amdgcn_readfirstlane(tail + total);
         } else if (flag) {                                  // stays QUEUED; drained in the epilogue
+            if constexpr (FLOOD) v &= ~kFloodEntry;
             __hip_atomic_store(&ovf_list[atomicAdd(ovf_count, 1u)], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
+    // FLOOD: blocks a flood may claim ahead of itself -- a round has four groups, the dependant that leads them takes one; the
+    // direction is told from the distance of two entries, which needs a grid at least four blocks wide
+    const uint32_t flood_depth = FLOOD && a.cols >= 4 ? min((uint32_t)a.flood, (uint32_t)(NBL - 1)) : 0u;
+    uint32_t kept = 0;                                     // speculative evaluations that counted (bbme_sweep_stats [15])
 
     const LaneGeom lgeom = lanes_geometry(a, lane & 15, BBME_NEW_MASK);      // chain form: lane k of a group = candidate k
     MemoStats mstats;
@@ -2012,12 +2033,128 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
             if (prof) prof_s.ph[6]++;
             BBME_PHASE(prof, -1);
 #endif
+            if constexpr (FLOOD) {
+                if (!wide) {
+                    // ---- a chain round that speculates along floods (see the kernel's head) ----
+                    const int g = lane >> 4, sub = lane & 15;
+                    const uint32_t cnt = min((uint32_t)NBL, tail - head);
+                    backlog += (tail - head > cnt) ? 1u : 0u;
+                    const bool active = (uint32_t)g < cnt;
+                    const uint32_t e = active ? q[(head + g) % QCAP] : 0u;    // owned since it was claimed
+                    head = __builtin_amdgcn_readfirstlane(head + cnt);
+                    const uint32_t x = e & ~kFloodEntry;
+                    const int r = (int)(x / a.cols), c = (int)(x % a.cols);
+                    const uint32_t cols = (uint32_t)a.cols;
+                    const bool leader = active && sub == 0;
+                    // links: a marked entry whose predecessor along R, DR, D or DL sits in the group before it reads that block as
+                    // its candidate kd = L, UL, U or UR (every steering value wave-uniform: one readlane per group)
+                    const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)e, 0), e1 = (uint32_t)__builtin_amdgcn_readlane((int)e, 16),
+                                   e2 = (uint32_t)__builtin_amdgcn_readlane((int)e, 32);
+                    const uint32_t dist = x - ((g == 1 ? e0 : g == 2 ? e1 : e2) & ~kFloodEntry);
+                    uint32_t kd = 0;
+                    if (active && g >= 1 && (e & kFloodEntry))
+                        kd = (dist == 1u && c >= 1) ? 1u : (dist == cols + 1u && c >= 1) ? 4u : dist == cols ? 6u
+                             : (dist == cols - 1u && (uint32_t)c + 1u < cols) ? 5u : 0u;
+                    const uint32_t k1 = (uint32_t)__builtin_amdgcn_readlane((int)kd, 16), k2 = (uint32_t)__builtin_amdgcn_readlane((int)kd, 32),
+                                   k3 = (uint32_t)__builtin_amdgcn_readlane((int)kd, 48);
+                    // the candidates' trip, as eval_block_lanes
+                    const LaneCand lc = lanes_candidate(a, lgeom, r, c);
+                    uint32_t slot = 0;
+                    uint2 memo = make_uint2(kMemoNoMv, 0u);
+                    mv_t prev = 0, mv = 0;
+                    if (active) {
+                        if constexpr (MEMO) {
+                            slot = (x << kMemoSlotShift) | (uint32_t)(sub < 9 ? sub : 0);
+                            if (!a.memo_init) memo = memo_load<true>(a, slot);
+                        }
+                        if (leader) prev = load_est<true>(a.est + x);
+                        mv = load_est<true>(lc.src);
+                    }
+                    BBME_PHASE(prof, 0);
+                    // A run of linked groups expects the value that its first, unlinked group read from the flood's direction:
+                    // h1, h2, h3 = what group 1, 2, 3 is given in place of its predecessor's estimate
+                    const uint32_t v0 = (uint32_t)__builtin_amdgcn_readlane((int)mv, (int)k1), v1 = (uint32_t)__builtin_amdgcn_readlane((int)mv, (int)(16u + k2)),
+                                   v2 = (uint32_t)__builtin_amdgcn_readlane((int)mv, (int)(32u + k3));
+                    const uint32_t h1 = v0, h2 = k1 ? h1 : v1, h3 = k2 ? h2 : v2;
+                    if (kd != 0u && (uint32_t)sub == kd) mv = g == 1 ? h1 : g == 2 ? h2 : h3;
+                    mv_t res = 0;
+                    if (active) {
+                        const mv_t own = dpp_row<0x150>(mv);
+                        if (!__ballot(lc.present && mv != own)) {
+                            if constexpr (MEMO) {
+                                if (a.memo_init && sub < 9) memo_store(a, slot, kMemoNoMv, 0u);
+                            }
+                            res = own;
+                        } else {
+                            res = lanes_score<BS, MEMO, true>(a, r, c, sub, lc.present, mv, prof, memo, slot, MEMO ? &mstats : nullptr);
+                        }
+                    }
+                    // an evaluation counts if the group is not linked, or if its predecessor's counted and gave what was expected
+                    const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)res, 0), r1 = (uint32_t)__builtin_amdgcn_readlane((int)res, 16),
+                                   r2 = (uint32_t)__builtin_amdgcn_readlane((int)res, 32);
+                    const bool ok1 = !k1 || r0 == h1, ok2 = !k2 || (ok1 && r1 == h2), ok3 = !k3 || (ok2 && r2 == h3);
+                    const bool valid = g == 0 || (g == 1 ? ok1 : g == 2 ? ok2 : ok3);
+                    const bool changed = leader && valid && res != prev;
+                    if (changed) __hip_atomic_store(a.est + x, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    evaluated += cnt;
+                    if (a.stats) kept += (uint32_t)__popcll(__ballot(leader && kd != 0u && valid));
+                    if (__ballot(changed)) BBME_DRAIN();                       // the stores have completed
+                    BBME_PHASE(prof, 3);
+                    // release, and the claims: lanes 0..3 one dependant each, as in the plain round -- but not the block that was
+                    // evaluated behind this one in this very round (nk: the next group's link) -- and, where the block took the
+                    // value of an updated input (fk: the first of L, UL, U, UR that holds it) while the queue is short, lanes 4.. the
+                    // blocks 2, 3, .. steps along that direction
+                    uint32_t wasx = 0;
+                    if (leader && valid) wasx = own_release(a, x);
+                    const bool g_changed = dpp_row<0x150>((uint32_t)changed) != 0;
+                    const uint32_t nk = g == 0 ? k1 : g == 1 ? k2 : g == 2 ? k3 : 0u;
+                    const uint32_t took = (uint32_t)(__ballot(active && lc.present && mv == res) >> (lane & 48)) & 0xffffu;
+                    const uint32_t fk = (took & 2u) ? 1u : (took & 16u) ? 4u : (took & 64u) ? 6u : (took & 32u) ? 5u : 0u;
+                    const bool grow = g_changed && nk == 0u && fk != 0u && tail - head < (uint32_t)NBL;
+                    // candidate L, UL, U, UR is read by the dependant R, DR, D, DL: lane 0, 1, 2, 3
+                    const int nd = nk == 1u ? 0 : nk == 4u ? 1 : nk == 6u ? 2 : 3, fd = fk == 1u ? 0 : fk == 4u ? 1 : fk == 6u ? 2 : 3;
+                    const bool ahead = grow && sub >= 4 && (uint32_t)sub < 4u + flood_depth;
+                    const int d = sub < 4 ? sub : fd, steps = sub < 4 ? 1 : sub - 2;
+                    const int tr = r + steps * (d != 0), tc = c + steps * (d < 2 ? 1 : 2 - d);   // (0,+1) (+1,+1) (+1,0) (+1,-1)
+                    const bool want = g_changed && (sub < 4 ? !(nk != 0u && sub == nd) : ahead) && tr < a.rows && tc >= 0 && tc < a.cols;
+                    const uint32_t tx = (uint32_t)tr * cols + (uint32_t)tc;
+                    uint32_t was = 1;
+                    if (want) was = own_claim(a, tx);
+                    BBME_PHASE(prof, 4);
+                    // the flood's next blocks, and the entries whose evaluation did not count, go to the FRONT of the queue, in
+                    // order: the next round takes them side by side; the other dependants go to its end
+                    const bool won = want && was == 0u;
+                    const bool requeue = leader && !valid;
+                    const bool front = requeue || (won && grow && (sub >= 4 || sub == fd));
+                    const uint32_t fval = requeue ? e : sub >= 4 ? tx | kFloodEntry : tx;
+                    const unsigned long long fm = __ballot(front);
+                    const uint32_t nf = (uint32_t)__popcll(fm);
+                    if (nf != 0u) {
+                        if (tail - head + nf <= QCAP) {
+                            if (front) q[(head - nf + (uint32_t)__popcll(fm & lt_mask)) % QCAP] = fval;
+                            head = __builtin_amdgcn_readfirstlane(head - nf);
+                        } else {
+                            enqueue(front, fval);
+                        }
+                    }
+                    enqueue(won && !front, tx);
+                    if (__ballot(leader && wasx >= 2)) {                    // an input changed while we held x: take it again
+                        bool again = false;
+                        if (leader && wasx >= 2) again = own_claim(a, x) == 0;
+                        enqueue(again, x);
+                    }
+                    if (wasx >= 0x80000000u) a.counters[5] = 1;            // counter close to overflow: report
+                    BBME_PHASE(prof, 5);
+                    continue;
+                }
+            }
             const int gl = wide ? LPBW : 16;                             // lanes per block this round
             const int g = lane / gl, sub = lane % gl;
             const uint32_t cnt = min((uint32_t)(wide ? NBW : NBL), tail - head);
             backlog += (tail - head > cnt) ? 1u : 0u;
             const bool active = (uint32_t)g < cnt;
-            const uint32_t x = active ? q[(head + g) % QCAP] : 0u;      // owned since it was claimed
+            uint32_t x = active ? q[(head + g) % QCAP] : 0u;            // owned since it was claimed
+            if constexpr (FLOOD) x &= ~kFloodEntry;                     // (a throughput round takes a marked entry as any other)
             head = __builtin_amdgcn_readfirstlane(head + cnt);
             const bool leader = active && sub == 0;
             bool changed = false;
@@ -2125,6 +2262,7 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
         atomicAdd(&a.counters[4], evaluated); atomicMax(&a.counters[7], rounds); atomicAdd(&a.counters[8], rounds);
 #ifndef BBME_PHASE_PROFILE
         atomicMax(&a.counters[13], rounds << 16 | min(backlog, 0xffffu)); atomicAdd(&a.counters[14], backlog);
+        if constexpr (FLOOD) { if (kept) atomicAdd(&a.counters[15], kept); }
 #endif
     }
 #ifndef BBME_PHASE_PROFILE

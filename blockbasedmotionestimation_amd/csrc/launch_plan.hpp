@@ -33,6 +33,15 @@ struct Tuning {
     int wide_threshold = 16;                      // solver: queue length above which a round takes the throughput form; BBME_WIDE_THRESHOLD
     int solve_waves = 4;                          // waves per solver workgroup (1, 2 or 4); BBME_SOLVE_WAVES
     bool solve_share = true;                      // k_reg_solve: idle waves of a workgroup take a sibling's surplus; BBME_SOLVE_SHARE=0
+    // k_reg_solve<.., true> (the chain rounds speculate along floods) on sweeps at b >= flood_min_b whose grid has at least
+    // flood_min_blocks blocks; a flood claims flood_depth blocks ahead of itself (0: never).  BBME_FLOOD_RULE="min_b,min_blocks,depth".
+    // The wave-level model (tests/cpp/flood_model.cpp) on cfg3, rounds of the busiest wave at depth 2: 37 + 64 -> 17 + 27 at level 0,
+    // b = 8 (130 560 blocks; measured 38 + 64 -> 18 + 23), 23 + 18 -> 14 + 11 at level 1 (32 640; measured 23 + 18 -> 15 + 13); depth 1
+    // leaves 57 / 29, depth 3 46 / 33; grids of 8 160 blocks and fewer stay within a round, b <= 4 needs more rounds with it.  A
+    // speculating round costs 2.5 us against 1.8, so only the deepest chains pay: level 0, b = 8 -67 us per pyramid, level 1, b = 8
+    // (-3 / +6 us) and level 0, b = 16 (+6 / +2 us) do not -- hence 100 000 blocks (profiles/r22_flood_speculation.txt)
+    int flood_min_b = 8, flood_depth = 2;
+    long long flood_min_blocks = 100000;
     int solve_wgs = 256;                          // most workgroups of k_reg_solve (4 independent waves each); r04: 256 measured 1.5 % ahead of 128 (one wave per SIMD)
     int xcd_remap = 1;                            // XCD-aware block order in k_search_fast; BBME_XCD_REMAP
     bool loose_plan = false;                      // the round-2 search plan without rim rounds; BBME_LOOSE_PLAN (set at all = on)
@@ -105,6 +114,10 @@ inline const Knob kKnobs[] = {
     {"BBME_LOOSE_PLAN", [](const char *, Tuning &t) { t.loose_plan = true; }},                // presence, whatever the value
     {"BBME_RELAX_RULE", [](const char *e, Tuning &t) {                                        // leading fields; the rest keep their defaults
          sscanf(e, "%lld,%d,%d,%d", &t.relax_min_blocks, &t.relax_max_b, &t.relax_s1, &t.relax_s2);
+     }},
+    {"BBME_FLOOD_RULE", [](const char *e, Tuning &t) {                                        // leading fields, as above
+         sscanf(e, "%d,%lld,%d", &t.flood_min_b, &t.flood_min_blocks, &t.flood_depth);
+         t.flood_depth = std::max(0, std::min(3, t.flood_depth));
      }},
 };
 
@@ -247,6 +260,7 @@ struct SweepLaunch {
     bool solve = true;                            // (Jacobi sweeps end with pass 1)
     int solve_segment = 4;                        // k_reg_solve<b, 4 or 16, memo>
     int solve_grid = 0, solve_waves = 0;
+    int flood = 0;                                // > 0: k_reg_solve<.., true> (same launch geometry), RegArgs::flood
     bool memo = false;
     int publish = -1;                             // the value the solver stores in the level's word when the sweep is complete, or none
 };
@@ -347,6 +361,7 @@ inline SweepLaunch plan_sweep(const PlanInputs &in, int level, int b, int mult, 
     // a multiple of 8 workgroups: one share per XCD (k_reg_solve's bands)
     s.solve_grid = (int)((std::min<long long>(t.solve_wgs, (blocks + 63) / 64) + 7) / 8 * 8);
     s.solve_waves = t.solve_waves;
+    s.flood = (b >= t.flood_min_b && blocks >= t.flood_min_blocks) ? t.flood_depth : 0;   // BBME_FLOOD_RULE (Tuning)
     return s;
 }
 
