@@ -918,7 +918,7 @@ static int create_context(const bbme_params *params, int width, int height, int 
     if ((err = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming)) != hipSuccess ||
         (err = hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming)) != hipSuccess)
         return bbme::fail(BBME_ERR_HIP, "creating the side stream: %s", hipGetErrorString(err));
-    size_t max_blocks = 0;
+    size_t max_blocks = 0, max_plane = 0;
     for (int l = 0; l < nl; ++l) {
         Level &L = c->lv[l];
         char what[48], what_plan[48];                      // "allocating level 2: out of memory"
@@ -933,6 +933,7 @@ static int create_context(const bbme_params *params, int width, int height, int 
         const size_t plane = round64((size_t)L.width * L.height + 64) + 192;   // slack: row_sad may touch 3 bytes past the end
         const size_t cells = round64((size_t)(L.width / 2) * (L.height / 2));
         const size_t own_blocks = round64((size_t)(L.width / L.block) * (L.height / L.block));
+        max_plane = std::max(max_plane, plane);             // (before the stride's cast: what s_plane is set from)
         L.plane_stride = (uint32_t)plane; L.small_stride = (uint32_t)own_blocks; L.big_stride = (uint32_t)cells;
         max_blocks = std::max(max_blocks, cells);
         std::vector<uint32_t> packed(sp.dx.size());
@@ -1023,6 +1024,15 @@ static int create_context(const bbme_params *params, int width, int height, int 
     c->flag_bytes = (max_blocks + 2047) / 2048 * 2048 + 2048;             // whole 16-flag segments (k_reg_solve), zero beyond the grid
     c->flow_stride = (size_t)g.padded_width * g.padded_height * 2;        // floats
     c->list_stride = (uint32_t)max_blocks; c->own_stride = (uint32_t)bit_words;
+    // k_reg_solve addresses a pair's planes, grids, ownership words and flags with 32-bit byte offsets on the pair's 64-bit base
+    // and multiplies rows by pitches in 24 bits (SolverArgs): every one of those buffers must end below 4 GiB per pair, every
+    // dimension lie below 2^23 and the ownership map's pitch below 2^24
+    {
+        const size_t most = std::max(std::max(max_plane, max_blocks * sizeof(mv_t)), std::max(bit_words * sizeof(uint32_t), c->flag_bytes));
+        if (most >= (1ull << 32) || c->lv[0].width >= (1 << 23) || c->lv[0].height >= (1 << 23) || c->own_pitch >= (1u << 24))
+            return bbme::fail(BBME_ERR_UNSUPPORTED, "a %d x %d frame needs a per-pair buffer of %zu bytes: the solver's offsets are 32-bit",
+                              c->lv[0].width, c->lv[0].height, most);
+    }
     const char *work = "work buffers";
     if (int rc = c->flow.alloc_zero(P * c->flow_stride, work)) return rc;
     if (int rc = c->list[0].alloc(P * max_blocks, work, Fill::none)) return rc;

@@ -13,6 +13,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "spec_grids.hpp"
 
 namespace bbme {
@@ -888,6 +890,14 @@ __device__ __forceinline__ void shift_pair(RegArgs &a, uint32_t p)
     a.counters += (size_t)p * 64u;
 }
 
+// The solver's copy of the arguments (k_reg_solve, "HOT AND COLD ARGUMENTS"): the same fields, and a promise -- checked where the
+// context is created -- that every per-pair buffer ends below 4 GiB and every dimension below 2^23.  The helpers a chain round
+// inlines take it as a licence to index grids, ownership words and image rows with 32-bit offsets on the pair's 64-bit base (the
+// scalar-base form of a global access, 24-bit multiplies); given a RegArgs they are, instruction for instruction, what they were.
+// (The memo needs no such form: memo_load / memo_store go through a buffer descriptor, whose offsets are 32-bit already.)
+struct SolverArgs : RegArgs {};
+template <class A> constexpr bool kOffsets32 = std::is_same<A, SolverArgs>::value;
+
 template <int BS> struct RegCfg {
     static constexpr int LPB = BS >= 4 ? (BS > 64 ? 64 : BS) : 1;   // lanes per block
     static constexpr int ROWS_PER_LANE = BS / LPB;                  // 2 for BS == 2, else 1
@@ -1115,13 +1125,15 @@ __device__ __forceinline__ LaneGeom lanes_geometry(const RegArgs &a, int k16, ui
     lg.shift = is_new ? 0 : a.old_shift;
     return lg;
 }
-__device__ __forceinline__ LaneCand lanes_candidate(const RegArgs &a, const LaneGeom &lg, int r, int c)
+template <class A>
+__device__ __forceinline__ LaneCand lanes_candidate(const A &a, const LaneGeom &lg, int r, int c)
 {
     const int rr = r + lg.drow, cc = c + lg.dcol;
     LaneCand lc;
     lc.present = lg.cand && (uint32_t)rr < (uint32_t)a.rows && (uint32_t)cc < (uint32_t)a.cols;
     const int rs = min(max(rr, 0), a.rows - 1), cs = min(max(cc, 0), a.cols - 1);
-    lc.src = lg.base + (size_t)((rs >> lg.shift) * lg.pitch + (cs >> lg.shift));
+    if constexpr (kOffsets32<A>) lc.src = lg.base + (uint32_t)(__mul24(rs >> lg.shift, lg.pitch) + (cs >> lg.shift));
+    else lc.src = lg.base + (size_t)((rs >> lg.shift) * lg.pitch + (cs >> lg.shift));
     return lc;
 }
 __device__ __forceinline__ LaneCand lanes_candidate(const RegArgs &a, int r, int c, int k16, uint32_t use_new)
@@ -1280,13 +1292,33 @@ __device__ __forceinline__ void forward_sads(const RegArgs &a, int r, int c, int
 
 // SAD of this lane's candidate, every row walked by the lane itself (no memo): the rows are independent loads, issued
 // back to back
-template <int BS>
-__device__ __forceinline__ uint32_t lane_sad(const RegArgs &a, int bx, int by, int x2, int y2)
+template <int BS, class A>
+__device__ __forceinline__ uint32_t lane_sad(const A &a, int bx, int by, int x2, int y2)
 {
     constexpr int NW = BS >= 4 ? BS / 4 : 1;
     struct __attribute__((packed, aligned(1))) row_t { uint32_t v[NW]; };
     constexpr uint32_t kMask = BS >= 4 ? 0xffffffffu : 0x0000ffffu;
     uint32_t sad0 = 0, sad1 = 0;                              // two chains: v_sad_u8 results feed the next one
+    if constexpr (kOffsets32<A> && BS <= 16) {
+        // every row at a 32-bit offset from the plane's (scalar) base: one 32-bit add a row
+        const uint32_t w = (uint32_t)a.width;
+        uint32_t o1 = __umul24((uint32_t)by, w) + (uint32_t)bx, o2 = __umul24((uint32_t)y2, w) + (uint32_t)x2;
+        row_t u[BS], v[BS];
+#pragma unroll
+        for (int i = 0; i < BS; ++i) {
+            u[i] = *reinterpret_cast<const row_t *>(a.image1 + o1);
+            v[i] = *reinterpret_cast<const row_t *>(a.image2 + o2);
+            o1 += w; o2 += w;
+        }
+#pragma unroll
+        for (int i = 0; i < BS; ++i)
+#pragma unroll
+            for (int q = 0; q < NW; ++q) {
+                if ((i + q) & 1) sad1 = __builtin_amdgcn_sad_u8(u[i].v[q] & kMask, v[i].v[q] & kMask, sad1);
+                else sad0 = __builtin_amdgcn_sad_u8(u[i].v[q] & kMask, v[i].v[q] & kMask, sad0);
+            }
+        return sad0 + sad1;
+    }
     const uint8_t *p1 = a.image1 + (size_t)by * a.width + bx;
     const uint8_t *p2 = a.image2 + (size_t)y2 * a.width + x2;
     // b <= 16: every row in flight at once.  b >= 32: eight rows at a time -- 2 x 32 rows of 8+ dwords do not fit the 256
@@ -1313,8 +1345,8 @@ __device__ __forceinline__ uint32_t lane_sad(const RegArgs &a, int bx, int by, i
 
 // Second half: lane k16 of the group holds candidate k16's MV `mv`; every lane of the group returns the winner.
 // MEMO: `memo` is what the lane's slot held (slot k16; lanes 9..15 shadow slot 0) and `slot` where it lives.
-template <int BS, bool MEMO = false, bool COHERENT = false, bool GROUP = ((COHERENT && BS >= 16) || BS >= 32)>
-__device__ __forceinline__ mv_t lanes_score(const RegArgs &a, int r, int c, int k16, bool present, mv_t mv,
+template <int BS, bool MEMO = false, bool COHERENT = false, bool GROUP = ((COHERENT && BS >= 16) || BS >= 32), class A>
+__device__ __forceinline__ mv_t lanes_score(const A &a, int r, int c, int k16, bool present, mv_t mv,
                                             PhaseProf *prof = nullptr, uint2 memo = make_uint2(0, 0),
                                             uint32_t slot = 0, MemoStats *stats = nullptr)
 {
@@ -1394,8 +1426,8 @@ __device__ __forceinline__ mv_t lanes_score(const RegArgs &a, int r, int c, int 
     return winner;
 }
 
-template <int BS, bool COHERENT, bool MEMO = false>
-__device__ __forceinline__ mv_t eval_block_lanes(const RegArgs &a, int r, int c, int k16, uint32_t use_new,
+template <int BS, bool COHERENT, bool MEMO = false, class A>
+__device__ __forceinline__ mv_t eval_block_lanes(const A &a, int r, int c, int k16, uint32_t use_new,
                                                  PhaseProf *prof = nullptr, const LaneGeom *lg = nullptr, MemoStats *stats = nullptr)
 {
     const LaneCand lc = lg ? lanes_candidate(a, *lg, r, c) : lanes_candidate(a, r, c, k16, use_new);
@@ -1439,13 +1471,23 @@ __device__ __forceinline__ mv_t eval_block_lanes(const RegArgs &a, int r, int c,
 // (mod 256) apart: different cache lines on different L2 channels, instead of 32 atomics queueing
 // on one line.
 __device__ __forceinline__ uint32_t own_slot(const RegArgs &a, uint32_t x) { return (x & 31u) * a.own_pitch + (x >> 5); }
-__device__ __forceinline__ uint32_t own_claim(const RegArgs &a, uint32_t x)    // returns the old counter
+template <class A>
+__device__ __forceinline__ uint32_t *own_word(const A &a, uint32_t x)
 {
-    return atomicAdd(&a.own[own_slot(a, x)], 1u);
+    if constexpr (kOffsets32<A>)
+        return reinterpret_cast<uint32_t *>(reinterpret_cast<char *>(a.own) + ((__umul24(x & 31u, a.own_pitch) + (x >> 5)) << 2));
+    else
+        return &a.own[own_slot(a, x)];
 }
-__device__ __forceinline__ uint32_t own_release(const RegArgs &a, uint32_t x)  // returns the old counter
+template <class A>
+__device__ __forceinline__ uint32_t own_claim(const A &a, uint32_t x)    // returns the old counter
 {
-    return atomicExch(&a.own[own_slot(a, x)], 0u);
+    return atomicAdd(own_word(a, x), 1u);
+}
+template <class A>
+__device__ __forceinline__ uint32_t own_release(const A &a, uint32_t x)  // returns the old counter
+{
+    return atomicExch(own_word(a, x), 0u);
 }
 #define BBME_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
@@ -1828,6 +1870,32 @@ __device__ __forceinline__ void drain_lists(const RegArgs &a, int t, int nthread
     }
 }
 
+// HOT AND COLD ARGUMENTS (k_reg_solve).  A round reads the images, the two grids, the ownership words, the memo, the geometry,
+// lambda and its own switches, a scan step the flag map: those are copied once, with the pair's shift applied, into the SolverArgs
+// the helpers are given (solver_hot_args) and live in scalar registers.  Everything else -- the overflow lists, the counters, the publish word, the switches of the epilogue -- is read
+// from the kernel-argument segment where it is used (BBME_SOLVER_COLD): a scalar load on a path that is not a round's, instead of a
+// register (or a spill slot in a VGPR lane, reloaded inside the rounds) for the whole launch.  The loads are written against the
+// segment's pointer and not against the parameter: the compiler gathers a parameter's loads at the kernel's entry, these it leaves
+// where they stand.  (Hiding the pointer behind an empty asm statement is no way to pin them: the statement's result counts as
+// divergent, and the round loop's control flow -- head, tail, the branches -- turns into vector code.)
+// THE SEGMENT'S POINTER IS TAKEN IN THE KERNEL'S OWN BODY AND HANDED DOWN (SolverKernarg): __builtin_amdgcn_kernarg_segment_ptr()
+// is the segment only inside a kernel -- in a function that the inliner leaves out of line (solver_wait_idle is one) the backend
+// lowers it to a null pointer, without a word.  So no helper calls the builtin: whoever needs a cold argument is given the pointer,
+// which is right inlined or not.  The other condition is stated where k_reg_solve takes the pointer: the kernel's only parameter
+// is the RegArgs, so the segment begins with it.
+typedef const __attribute__((address_space(4))) char *SolverKernarg;
+template <class T>
+__device__ __forceinline__ T solver_cold_arg(SolverKernarg kp, size_t offset)
+{
+    return *reinterpret_cast<const __attribute__((address_space(4))) T *>(kp + offset);
+}
+#define BBME_SOLVER_COLD(kp, field) solver_cold_arg<decltype(RegArgs::field)>(kp, offsetof(RegArgs, field))
+__device__ __forceinline__ uint32_t *solver_counters(SolverKernarg kp) { return BBME_SOLVER_COLD(kp, counters) + (size_t)blockIdx.y * 64u; }
+__device__ __forceinline__ uint32_t *solver_overflow_list(SolverKernarg kp)
+{
+    return BBME_SOLVER_COLD(kp, list0) + (size_t)blockIdx.y * BBME_SOLVER_COLD(kp, s_list);
+}
+
 // k_reg_solve, a wave with nothing left: announce it, wait for a sibling's surplus (returns how many blocks arrived in the wave's
 // mailbox) or for the last wave to fall idle (returns 0).  Kept out of line: inlined, its spin loop sits inside the solver's round loop
 // as far as the register allocator is concerned and costs the rounds 30 scalar spills.
@@ -1884,8 +1952,32 @@ __device__ __attribute__((noinline)) uint32_t solver_wait_idle(uint32_t *mail, u
 // for an ordinary evaluation.  Marked entries exist in the LDS queues and mailboxes only; the overflow list holds plain indices.
 constexpr uint32_t kFloodEntry = 0x80000000u;   // queue entry: claimed on speculation, behind its predecessor along a flood
 
+__device__ __forceinline__ SolverArgs solver_hot_args(const RegArgs &k, uint32_t p)
+{
+    SolverArgs a{};
+    a.image1 = k.image1 + (size_t)p * k.s_plane; a.image2 = k.image2 + (size_t)p * k.s_plane;
+    a.width = k.width; a.height = k.height; a.rows = k.rows; a.cols = k.cols;
+    a.old_grid = k.old_grid + (size_t)p * k.s_old; a.old_shift = k.old_shift; a.old_cols = k.old_cols;
+    a.est = k.est + (size_t)p * k.s_est;
+    a.lambda_mult = k.lambda_mult;
+    a.own = k.own + (size_t)p * k.s_own; a.own_pitch = k.own_pitch;
+    a.flag_cur = k.flag_cur + (size_t)p * k.s_flag;                 // (the scan steps: never null in a solver launch)
+    a.wide_threshold = k.wide_threshold; a.round_cap = k.round_cap; a.share = k.share;
+    a.memo = k.memo ? k.memo + (size_t)p * k.s_memo : nullptr; a.memo_init = k.memo_init; a.memo_forward = k.memo_forward;
+    return a;
+}
+// the epilogue's safety net runs on the whole set (drain_lists): the hot ones and the lists and counters
+__device__ __forceinline__ RegArgs solver_all_args(const SolverArgs &hot, SolverKernarg kp)
+{
+    RegArgs a = hot;
+    const uint32_t s_list = BBME_SOLVER_COLD(kp, s_list);
+    a.list0 = BBME_SOLVER_COLD(kp, list0) + (size_t)blockIdx.y * s_list; a.list1 = BBME_SOLVER_COLD(kp, list1) + (size_t)blockIdx.y * s_list;
+    a.counters = solver_counters(kp);
+    return a;
+}
+
 template <int BS, int SEG = 16, bool MEMO = false, bool FLOOD = false>
-__global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
+__global__ __launch_bounds__(256) void k_reg_solve(const RegArgs args)
 {
     static_assert(SEG == 16 || SEG == 4, "flags per scan segment");
     // two forms of a round: WIDE (eval_block: LPBW lanes per block, 64/LPBW blocks per round) when
@@ -1907,23 +1999,37 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
     __shared__ uint32_t s_idle, s_done;                    // bit w: wave w has nothing to do and may be handed blocks; all waves idle
     __shared__ uint32_t s_ticket;
     __builtin_amdgcn_s_setprio(2);
-    shift_pair(a, blockIdx.y);
+    // (the segment begins with the kernel's first parameter, and the RegArgs is its only one)
+    const SolverKernarg kp = (SolverKernarg)__builtin_amdgcn_kernarg_segment_ptr();
+    const SolverArgs a = solver_hot_args(args, blockIdx.y);   // what the rounds read; the rest: BBME_SOLVER_COLD where it is used
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));      // (uniform, and the compiler is told so: it steers branches)
     uint32_t *q = qmem[wave];
-    if (SHARE && a.share && blockDim.x > 64) {             // (uniform over the launch)
-        if (threadIdx.x < MAXW) s_mail[threadIdx.x][0] = 0;
-        if (threadIdx.x == 0) { s_idle = 0; s_done = 0; }
-        __syncthreads();
-    }
     const uint32_t nblocks = (uint32_t)a.rows * a.cols;
     const uint32_t xcd = blockIdx.x & 7u;                  // the launch has a multiple of 8 workgroups
     const uint32_t wpw = blockDim.x >> 6;                  // waves per workgroup (1, 2 or 4)
     const uint32_t wx = (blockIdx.x >> 3) * wpw + wave, Wx = (gridDim.x >> 3) * wpw;
     const uint32_t nseg = (nblocks + (uint32_t)SEG - 1u) / (uint32_t)SEG, band = (nseg + 7u) / 8u;
     const uint32_t seg_begin = min(xcd * band, nseg), seg_end = min(seg_begin + band, nseg);
-    uint32_t *ovf_list = a.list0;
-    uint32_t *ovf_count = &a.counters[1];
+    // The first scan step's flags are asked for before anything else: the mailboxes with their barrier, the lanes' geometry and the
+    // rest of the set-up below run while that trip is under way (most launches of a pyramid find nothing in it, and it is all they do)
+    auto load_flags = [&](uint32_t sg) {
+        uint4 f = make_uint4(0, 0, 0, 0);
+        const uint8_t *fp = a.flag_cur + (size_t)sg * SEG;                                 // the map is padded to whole 16-flag segments
+        if (sg < seg_end) {
+            if constexpr (SEG == 16) f = *reinterpret_cast<const uint4 *>(fp);
+            else f.x = *reinterpret_cast<const uint32_t *>(fp);
+        }
+        return f;
+    };
+    uint4 f_first = make_uint4(0, 0, 0, 0);
+    if (seg_begin + wx < seg_end) f_first = load_flags(seg_begin + (uint32_t)lane * Wx + wx);
+    if (SHARE && a.share && blockDim.x > 64) {             // (uniform over the launch)
+        if (threadIdx.x < MAXW) s_mail[threadIdx.x][0] = 0;
+        if (threadIdx.x == 0) { s_idle = 0; s_done = 0; }
+        __syncthreads();
+    }
+    auto est_at = [&](uint32_t x) { return reinterpret_cast<mv_t *>(reinterpret_cast<char *>(a.est) + (x << 2)); };   // (32-bit offset, scalar base)
     uint32_t head = 0, tail = 0;                  // wave-uniform, free-running
     uint32_t evaluated = 0, rounds = 0, backlog = 0;       // backlog: rounds that left queued blocks waiting
 #ifdef BBME_PHASE_PROFILE
@@ -1947,12 +2053,13 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
             tail = __builtin_amdgcn_readfirstlane(tail + total);
         } else if (flag) {                                  // stays QUEUED; drained in the epilogue
             if constexpr (FLOOD) v &= ~kFloodEntry;
+            uint32_t *ovf_list = solver_overflow_list(kp), *ovf_count = solver_counters(kp) + 1;
             __hip_atomic_store(&ovf_list[atomicAdd(ovf_count, 1u)], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     };
     // FLOOD: blocks a flood may claim ahead of itself -- a round has four groups, the dependant that leads them takes one; the
     // direction is told from the distance of two entries, which needs a grid at least four blocks wide
-    const uint32_t flood_depth = FLOOD && a.cols >= 4 ? min((uint32_t)a.flood, (uint32_t)(NBL - 1)) : 0u;
+    const uint32_t flood_depth = FLOOD && a.cols >= 4 ? min((uint32_t)args.flood, (uint32_t)(NBL - 1)) : 0u;
     uint32_t kept = 0;                                     // speculative evaluations that counted (bbme_sweep_stats [15])
 
     const LaneGeom lgeom = lanes_geometry(a, lane & 15, BBME_NEW_MASK);      // chain form: lane k of a group = candidate k
@@ -1965,14 +2072,10 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
         if (head == tail) {
             if (seg_begin + k * 64u * Wx + wx < seg_end) {
                 const uint32_t sg = seg_begin + (k * 64u + (uint32_t)lane) * Wx + wx;
-                ++k;
                 // SEG = 4 on small grids: a cluster of stale blocks in a row is dealt to four times as many waves
-                uint4 f = make_uint4(0, 0, 0, 0);
-                uint8_t *fp = a.flag_cur + (size_t)sg * SEG;                               // the map is padded to whole 16-flag segments
-                if (sg < seg_end) {
-                    if constexpr (SEG == 16) f = *reinterpret_cast<uint4 *>(fp);
-                    else f.x = *reinterpret_cast<uint32_t *>(fp);
-                }
+                const uint4 f = k == 0 ? f_first : load_flags(sg);
+                uint8_t *fp = a.flag_cur + (size_t)sg * SEG;
+                ++k;
                 const bool any = (f.x | f.y | f.z | f.w) != 0;
                 if (__ballot(any)) {
                     if (any) {
@@ -1998,7 +2101,7 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
             if (!SHARE || !a.share || wpw == 1) break;
             // (every value that steers the loop is made wave-uniform by hand: a function's result, an LDS load are divergent to the
             // compiler, and one divergent exit turns the whole loop's control flow -- head, tail, the branches -- into vector code)
-            const uint32_t got = __builtin_amdgcn_readfirstlane(solver_wait_idle(&s_mail[wave][0], &s_idle, &s_done, (uint32_t)wave, wpw, &a.counters[5]));
+            const uint32_t got = __builtin_amdgcn_readfirstlane(solver_wait_idle(&s_mail[wave][0], &s_idle, &s_done, (uint32_t)wave, wpw, solver_counters(kp) + 5));
             if (!got) break;
             // the donor cleared this wave's idle bit before it wrote the mailbox: the blocks are this wave's now (owned since claimed)
             if ((uint32_t)lane < got) q[(tail + (uint32_t)lane) % QCAP] = s_mail[wave][1 + lane];
@@ -2007,7 +2110,7 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
             continue;
         }
         while (head != tail) {
-            if (++rounds > round_cap) { if (lane == 0) a.counters[5] = 1; head = tail; continue; }
+            if (++rounds > round_cap) { if (lane == 0) solver_counters(kp)[5] = 1; head = tail; continue; }
             const bool wide = NBW > NBL && tail - head > a.wide_threshold;   // wave-uniform
             if (__builtin_expect(SHARE && a.share && wpw > 1 && tail - head > (uint32_t)(wide ? NBW : NBL), 0)) {
                 // more queued than this round takes: deal the surplus to the idle siblings (at most MAILCAP each)
@@ -2046,6 +2149,19 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
                     const int r = (int)(x / a.cols), c = (int)(x % a.cols);
                     const uint32_t cols = (uint32_t)a.cols;
                     const bool leader = active && sub == 0;
+                    // the candidates' trip, as eval_block_lanes: asked for first -- no load needs the links, which are worked out under it
+                    const LaneCand lc = lanes_candidate(a, lgeom, r, c);
+                    uint32_t slot = 0;
+                    uint2 memo = make_uint2(kMemoNoMv, 0u);
+                    mv_t prev = 0, mv = 0;
+                    if (active) {
+                        if constexpr (MEMO) {
+                            slot = (x << kMemoSlotShift) | (uint32_t)(sub < 9 ? sub : 0);
+                            if (!a.memo_init) memo = memo_load<true>(a, slot);
+                        }
+                        if (leader) prev = load_est<true>(est_at(x));
+                        mv = load_est<true>(lc.src);
+                    }
                     // links: a marked entry whose predecessor along R, DR, D or DL sits in the group before it reads that block as
                     // its candidate kd = L, UL, U or UR (every steering value wave-uniform: one readlane per group)
                     const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)e, 0), e1 = (uint32_t)__builtin_amdgcn_readlane((int)e, 16),
@@ -2057,19 +2173,6 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
                              : (dist == cols - 1u && (uint32_t)c + 1u < cols) ? 5u : 0u;
                     const uint32_t k1 = (uint32_t)__builtin_amdgcn_readlane((int)kd, 16), k2 = (uint32_t)__builtin_amdgcn_readlane((int)kd, 32),
                                    k3 = (uint32_t)__builtin_amdgcn_readlane((int)kd, 48);
-                    // the candidates' trip, as eval_block_lanes
-                    const LaneCand lc = lanes_candidate(a, lgeom, r, c);
-                    uint32_t slot = 0;
-                    uint2 memo = make_uint2(kMemoNoMv, 0u);
-                    mv_t prev = 0, mv = 0;
-                    if (active) {
-                        if constexpr (MEMO) {
-                            slot = (x << kMemoSlotShift) | (uint32_t)(sub < 9 ? sub : 0);
-                            if (!a.memo_init) memo = memo_load<true>(a, slot);
-                        }
-                        if (leader) prev = load_est<true>(a.est + x);
-                        mv = load_est<true>(lc.src);
-                    }
                     BBME_PHASE(prof, 0);
                     // A run of linked groups expects the value that its first, unlinked group read from the flood's direction:
                     // h1, h2, h3 = what group 1, 2, 3 is given in place of its predecessor's estimate
@@ -2095,9 +2198,9 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
                     const bool ok1 = !k1 || r0 == h1, ok2 = !k2 || (ok1 && r1 == h2), ok3 = !k3 || (ok2 && r2 == h3);
                     const bool valid = g == 0 || (g == 1 ? ok1 : g == 2 ? ok2 : ok3);
                     const bool changed = leader && valid && res != prev;
-                    if (changed) __hip_atomic_store(a.est + x, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (changed) __hip_atomic_store(est_at(x), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     evaluated += cnt;
-                    if (a.stats) kept += (uint32_t)__popcll(__ballot(leader && kd != 0u && valid));
+                    kept += (uint32_t)__popcll(__ballot(leader && kd != 0u && valid));   // (counted whether asked for or not: a test of RegArgs::stats costs as much)
                     if (__ballot(changed)) BBME_DRAIN();                       // the stores have completed
                     BBME_PHASE(prof, 3);
                     // release, and the claims: lanes 0..3 one dependant each, as in the plain round -- but not the block that was
@@ -2143,7 +2246,7 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
                         if (leader && wasx >= 2) again = own_claim(a, x) == 0;
                         enqueue(again, x);
                     }
-                    if (wasx >= 0x80000000u) a.counters[5] = 1;            // counter close to overflow: report
+                    if (wasx >= 0x80000000u) solver_counters(kp)[5] = 1;            // counter close to overflow: report
                     BBME_PHASE(prof, 5);
                     continue;
                 }
@@ -2162,12 +2265,12 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
             if (active) {
                 r = (int)(x / a.cols); c = (int)(x % a.cols);
                 mv_t prev = 0;
-                if (leader) prev = load_est<true>(a.est + x);          // issued with the candidate loads
+                if (leader) prev = load_est<true>(est_at(x));          // issued with the candidate loads
                 mv_t res;
                 if (wide) res = eval_block<BS, true>(a, r, c, sub, BBME_NEW_MASK);
                 else res = eval_block_lanes<BS, true, MEMO>(a, r, c, sub, BBME_NEW_MASK, prof, &lgeom, MEMO ? &mstats : nullptr);
                 changed = leader && res != prev;
-                if (changed) __hip_atomic_store(a.est + x, res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (changed) __hip_atomic_store(est_at(x), res, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 if constexpr (MEMO) {
                     // the dependants' SADs of the new value, while the store drains
                     if (!wide && a.memo_forward) {
@@ -2201,7 +2304,7 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
                     if (leader && wasx >= 2) again = own_claim(a, x) == 0;
                     enqueue(again, x);
                 }
-                if (wasx >= 0x80000000u) a.counters[5] = 1;            // counter close to overflow: report
+                if (wasx >= 0x80000000u) solver_counters(kp)[5] = 1;            // counter close to overflow: report
                 BBME_PHASE(prof, 5);                                    // enqueue + re-claim
                 continue;
             }
@@ -2250,43 +2353,43 @@ __global__ __launch_bounds__(256) void k_reg_solve(RegArgs a)
                 if (leader && wasx >= 2) again = own_claim(a, x) == 0;
                 enqueue(again, x);
             }
-            if (wasx >= 0x80000000u) a.counters[5] = 1;                // counter close to overflow: report
+            if (wasx >= 0x80000000u) solver_counters(kp)[5] = 1;                // counter close to overflow: report
             BBME_PHASE(prof, 5);                                        // enqueue + re-claim
         }
     }
 #ifdef BBME_PHASE_PROFILE
     if (lane == 0 && prof_s.ph[6])
-        for (int i = 0; i < 7; ++i) atomicAdd(&a.counters[9 + i], prof_s.ph[i]);
+        for (int i = 0; i < 7; ++i) atomicAdd(&solver_counters(kp)[9 + i], prof_s.ph[i]);
 #endif
-    if (a.stats && lane == 0 && evaluated) {
-        atomicAdd(&a.counters[4], evaluated); atomicMax(&a.counters[7], rounds); atomicAdd(&a.counters[8], rounds);
+    if (BBME_SOLVER_COLD(kp, stats) && lane == 0 && evaluated) {
+        uint32_t *counters = solver_counters(kp);
+        atomicAdd(&counters[4], evaluated); atomicMax(&counters[7], rounds); atomicAdd(&counters[8], rounds);
 #ifndef BBME_PHASE_PROFILE
-        atomicMax(&a.counters[13], rounds << 16 | min(backlog, 0xffffu)); atomicAdd(&a.counters[14], backlog);
-        if constexpr (FLOOD) { if (kept) atomicAdd(&a.counters[15], kept); }
-#endif
-    }
-#ifndef BBME_PHASE_PROFILE
-    if constexpr (MEMO) {
-        if (a.stats && lane == 0 && mstats.lookups) {
-            atomicAdd(&a.counters[9], mstats.lookups); atomicAdd(&a.counters[10], mstats.misses);
-            atomicAdd(&a.counters[11], mstats.passes); atomicAdd(&a.counters[12], mstats.forwards);
+        atomicMax(&counters[13], rounds << 16 | min(backlog, 0xffffu)); atomicAdd(&counters[14], backlog);
+        if constexpr (FLOOD) { if (kept) atomicAdd(&counters[15], kept); }
+        if constexpr (MEMO) {
+            if (mstats.lookups) {
+                atomicAdd(&counters[9], mstats.lookups); atomicAdd(&counters[10], mstats.misses);
+                atomicAdd(&counters[11], mstats.passes); atomicAdd(&counters[12], mstats.forwards);
+            }
         }
-    }
 #endif
+    }
 
     // epilogue: the workgroup that takes the last ticket knows every other one has finished (their
     // stores were drained before they took theirs) and empties the overflow list, if there is one
     BBME_DRAIN();
     __syncthreads();
-    if (threadIdx.x == 0) s_ticket = atomicAdd(&a.counters[6], 1u);
+    if (threadIdx.x == 0) s_ticket = atomicAdd(&solver_counters(kp)[6], 1u);
     __syncthreads();
     if (s_ticket != gridDim.x - 1) return;
-    drain_lists<BS>(a, threadIdx.x, (int)blockDim.x);
-    if (a.publish) {                                          // the sweep is complete: every workgroup's stores were drained before its ticket
+    drain_lists<BS>(solver_all_args(a, kp), threadIdx.x, (int)blockDim.x);
+    uint32_t *publish = BBME_SOLVER_COLD(kp, publish);
+    if (publish) {                                            // the sweep is complete: every workgroup's stores were drained before its ticket
         BBME_DRAIN();
         __syncthreads();
         if (threadIdx.x == 0)
-            __hip_atomic_store(a.publish + (size_t)blockIdx.y * 16u, a.publish_value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(publish + (size_t)blockIdx.y * 16u, BBME_SOLVER_COLD(kp, publish_value), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
