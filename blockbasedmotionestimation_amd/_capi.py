@@ -170,6 +170,14 @@ SIGNATURES = {
     "bbme_subpel_interpolate_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "bbme_get_subpel_interpolated_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_subpel_interpolation_stats": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_subpel_interpolate_bgr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                                   C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_cells_subpel_interpolate_bgr_device": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                           C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t,
+                                                           C.c_void_p]),
+    "bbme_subpel_interpolate_bgr_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t,
+                                                     C.c_void_p]),
+    "bbme_get_subpel_interpolated_bgr_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "bbme_frame_plane_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
     "bbme_cells_color_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_flow_color_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -1763,7 +1763,7 @@ int bbme_subsampled_flow_device(bbme_ctx *c, int pair, int scale, float *d_out, 
 
 }  // extern "C": the stages from here on share templates, which need C++ linkage; their entry points have C linkage from bbme.h
 
-// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter, K11, K12) ----
+// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter, K11, K12, K12b) ----
 // Every stage is one launch in which a lane takes runs of 4 units (pixels or cells) along a row, over (workgroups, pairs, phases
 // or frames), with optional statistics: the kernel's partials, then k_mc_reduce.  One run split, one launch path, one scratch
 // layout, one pair of output checks and one pair of download helpers serve all of them.
@@ -3180,17 +3180,18 @@ int bbme_cells_subpel_interpolate_device(bbme_ctx *c, int pair, const int16_t *d
                       d_stats4, stream);
 }
 
-// The context's own: the forward and the backward cells of `pairs` pairs from pair0 on refined into the context's quarter-pel
-// buffer (the packed forward grids of every pair, then the backward ones; allocated here at first use), then interpolated from it
-static int enqueue_own_si(bbme_ctx *c, int pair0, int pairs, int num0, int count, int den, const int *window, uint8_t *d_out,
-                          int out_pitch, size_t out_stride, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream,
-                          const char *what)
+// The context's own two fields of `pairs` pairs from pair0 on refined into the context's quarter-pel buffer (the packed forward
+// grids of every pair, then the backward ones; allocated here at first use): q4[0] and q4[1] are pair0's, later pairs' `*cells`
+// words on, rows *cw cells apart.  Shared by the grey and the colour interpolation.
+static int refine_own_si(bbme_ctx *c, int pair0, int pairs, hipStream_t stream, const char *what, mv_t *(&q4)[2], int *cw_out,
+                         size_t *cells_out)
 {
     const Level &L = c->lv[0];
     const int cw = L.width / 2;
     const size_t cells = (size_t)cw * (L.height / 2), s_plane = L.plane_stride;
     if (int rc = c->si_q4.ensure(2 * cells * c->batch, "the quarter-pel cells of the interpolation", Fill::poison)) return rc;
-    mv_t *q4[2] = {c->si_q4 + pair0 * cells, c->si_q4 + ((size_t)c->batch + pair0) * cells};
+    q4[0] = c->si_q4 + pair0 * cells;
+    q4[1] = c->si_q4 + ((size_t)c->batch + pair0) * cells;
     for (int which = 0; which < 2; ++which) {
         const uint8_t *i1, *i2;
         const mv_t *grid;
@@ -3200,6 +3201,20 @@ static int enqueue_own_si(bbme_ctx *c, int pair0, int pairs, int num0, int count
                                 nullptr, q4[which], cw, cells, nullptr, nullptr, stream))
             return rc;
     }
+    *cw_out = cw;
+    *cells_out = cells;
+    return BBME_OK;
+}
+
+// The context's own: both fields refined (refine_own_si), then interpolated from the quarter-pel buffer
+static int enqueue_own_si(bbme_ctx *c, int pair0, int pairs, int num0, int count, int den, const int *window, uint8_t *d_out,
+                          int out_pitch, size_t out_stride, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream,
+                          const char *what)
+{
+    mv_t *q4[2];
+    int cw;
+    size_t cells;
+    if (int rc = refine_own_si(c, pair0, pairs, stream, what, q4, &cw, &cells)) return rc;
     return enqueue_si(c, pair0, pairs, q4[0], q4[1], cw, cells, num0, count, den, window, d_out, out_pitch, out_stride, nullptr, 0, 0,
                       partial, d_stats, stream);
 }
@@ -3247,6 +3262,108 @@ int bbme_subpel_interpolation_stats(bbme_ctx *c, int num, int den, const int *wi
     return download_stats(c, c->si_stats, c->batch, stats, [&] {
         return enqueue_own_si(c, 0, c->batch, num, 1, den, window, nullptr, 0, 0, c->si_stats.partials_all(), c->si_stats.results(),
                               c->stream, what);
+    });
+}
+
+// ---- colour frames at quarter-pel positions (the BGR SUBPEL INTERPOLATION RULE of include/bbme.h; K12b k_subpel_interpolate_bgr) ----
+
+// k_subpel_interpolate_bgr over `count` phases from num0 on, one pair; bgr1 / bgr2 already in the direction's order.  No
+// statistics, no map: its own launch.
+static int enqueue_si_bgr(bbme_ctx *c, int pair, const mv_t *d_qf, const mv_t *d_qb, int q4_pitch, const uint8_t *bgr1,
+                          const uint8_t *bgr2, int bgr_pitch, int num0, int count, int den, uint8_t *d_out, int out_pitch,
+                          size_t out_stride, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    const Geometry &g = c->geom;
+    SiBgrArgs a{};
+    a.img1 = c->plane1(L) + (size_t)pair * L.plane_stride;
+    a.img2 = c->plane2(L) + (size_t)pair * L.plane_stride;
+    a.qf = d_qf; a.qb = d_qb; a.q4_pitch = q4_pitch;
+    a.bgr1 = bgr1; a.bgr2 = bgr2; a.bgr_pitch = bgr_pitch;
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2;
+    a.fw = g.width; a.fh = g.height; a.pad_x = g.pad_x; a.pad_y = g.pad_y;
+    a.num0 = num0; a.den = den;
+    a.magic = (uint32_t)((1ull << 32) / (unsigned)den + 1ull);
+    set_runs(a, a.cw, L.height / 2);
+    hipLaunchKernelGGL(k_subpel_interpolate_bgr<kSiRunsPerLane>, dim3((unsigned)cell_groups(c, kSiRunsPerLane), 1, (unsigned)count), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+int bbme_cells_subpel_interpolate_bgr_device(bbme_ctx *c, int pair, const int16_t *d_qf, const int16_t *d_qb, int q4_pitch_cells,
+                                             const uint8_t *d_bgr1, const uint8_t *d_bgr2, int bgr_pitch, int num0, int count,
+                                             int den, uint8_t *d_out, int out_pitch, size_t out_stride, void *hip_stream)
+{
+    const char *what = "bbme_cells_subpel_interpolate_bgr_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (!d_qf) return bbme::fail(BBME_ERR_INVALID, "%s: null forward grid", what);
+    if (int rc = check_ip_bgr(c, num0, count, den, d_out, out_pitch, out_stride, what)) return rc;
+    if (q4_pitch_cells < c->lv[0].width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch_cells, c->lv[0].width / 2);
+    if ((d_bgr1 == nullptr) != (d_bgr2 == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: one colour frame without the other (both, or neither for the stored colour)", what);
+    if (d_bgr1 && (long long)bgr_pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, bgr_pitch, c->geom.width);
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    const uint8_t *bgr1 = c->direction ? d_bgr2 : d_bgr1, *bgr2 = c->direction ? d_bgr1 : d_bgr2;
+    if (!d_bgr1) {
+        if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
+        bgr_pitch = 3 * c->geom.width;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_si_bgr(c, pair, reinterpret_cast<const mv_t *>(d_qf), reinterpret_cast<const mv_t *>(d_qb), q4_pitch_cells, bgr1, bgr2,
+                          bgr_pitch, num0, count, den, d_out, out_pitch, out_stride, stream);
+}
+
+// what the two calls on the context's own two fields and stored colour share; before anything is enqueued.  Touches no device.
+static int check_si_bgr_own(const bbme_ctx *c, int pair, int num0, int count, int den, const uint8_t *d_out, int out_pitch,
+                            size_t out_stride, const char *what)
+{
+    if (int rc = check_ip_bgr(c, num0, count, den, d_out, out_pitch, out_stride, what)) return rc;
+    if (int rc = check_sp(c, nullptr, what)) return rc;
+    if (int rc = check_fields_state(c, what)) return rc;
+    const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
+    return stored_bgr(c, pair, what, &bgr1, &bgr2);
+}
+
+// the context's own two fields of `pair` refined (refine_own_si) and its stored colour, on `stream`
+static int enqueue_own_si_bgr(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch, size_t out_stride,
+                              hipStream_t stream, const char *what)
+{
+    const uint8_t *bgr1 = nullptr, *bgr2 = nullptr;
+    if (int rc = stored_bgr(c, pair, what, &bgr1, &bgr2)) return rc;
+    mv_t *q4[2];
+    int cw;
+    size_t cells;
+    if (int rc = refine_own_si(c, pair, 1, stream, what, q4, &cw, &cells)) return rc;
+    return enqueue_si_bgr(c, pair, q4[0], q4[1], cw, bgr1, bgr2, 3 * c->geom.width, num0, count, den, d_out, out_pitch, out_stride,
+                          stream);
+}
+
+int bbme_subpel_interpolate_bgr_device(bbme_ctx *c, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch,
+                                       size_t out_stride, void *hip_stream)
+{
+    const char *what = "bbme_subpel_interpolate_bgr_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_si_bgr_own(c, pair, num0, count, den, d_out, out_pitch, out_stride, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_si_bgr(c, pair, num0, count, den, d_out, out_pitch, out_stride, stream, what);
+}
+
+int bbme_get_subpel_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int den, uint8_t *out)
+{
+    const char *what = "bbme_get_subpel_interpolated_bgr_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_si_bgr_own(c, pair, num, 1, den, out, 3 * c->geom.width, 0, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    return download_staged(c, (size_t)3 * c->geom.width * c->geom.height, "the quarter-pel interpolated colour frame", out,
+                           [&](uint8_t *d) {
+        return enqueue_own_si_bgr(c, pair, num, 1, den, d, 3 * c->geom.width, 0, c->stream, what);
     });
 }
 

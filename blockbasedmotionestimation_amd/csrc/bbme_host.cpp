@@ -1088,6 +1088,50 @@ int bbme_subpel_interpolate_host(const uint8_t *image1, const uint8_t *image2, i
     return BBME_OK;
 }
 
+// The BGR SUBPEL INTERPOLATION RULE of include/bbme.h: the selection of bbme_subpel_interpolate_host on the luma planes (its map
+// tells which hypothesis; P1 and P2 follow from it), then every pixel of the two colour frames sampled bilinearly at P1 and P2 and
+// blended (the mirror of k_subpel_interpolate_bgr).  A tap of weight 0 or outside the frame is not read.
+int bbme_subpel_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int padded_w, int padded_h, const uint8_t *bgr1,
+                                     const uint8_t *bgr2, int width, int height, int pad_x, int pad_y, const int16_t *qf,
+                                     const int16_t *qb, int num, int den, uint8_t *out)
+{
+    const char *what = "bbme_subpel_interpolate_bgr_host";
+    if (!luma1 || !luma2 || !bgr1 || !bgr2 || !qf || !out) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 1 || height < 1 || pad_x < 0 || pad_y < 0 || (long long)width + 2LL * pad_x != padded_w ||
+        (long long)height + 2LL * pad_y != padded_h)
+        return bbme::fail(BBME_ERR_INVALID, "%s: the %dx%d frame with padding (%d, %d) is not the %dx%d plane", what, width, height,
+                          pad_x, pad_y, padded_w, padded_h);
+    const int cw = padded_w / 2;
+    std::vector<uint8_t> sel((size_t)cw * (padded_h / 2) + 1);
+    if (int rc = bbme_subpel_interpolate_host(luma1, luma2, padded_w, padded_h, qf, qb, num, den, nullptr, nullptr, sel.data(), nullptr))
+        return rc;                                            // odd planes and bad phases are refused there
+    const auto floor_div = [](int a, int b) { return a >= 0 ? a / b : -((-a + b - 1) / b); };
+    // channel ch of the frame's pixel sampled at integer position (tx, ty) with the fractions (fx, fy)
+    const auto sample = [&](const uint8_t *img, int tx, int ty, int fx, int fy, int ch) {
+        const auto tap = [&](int weight, int x, int y) {
+            return !weight || x < 0 || y < 0 || x >= width || y >= height ? 0 : weight * (int)img[((size_t)y * width + x) * 3 + ch];
+        };
+        return (tap((4 - fx) * (4 - fy), tx, ty) + tap(fx * (4 - fy), tx + 1, ty) + tap((4 - fx) * fy, tx, ty + 1) +
+                tap(fx * fy, tx + 1, ty + 1) + 8) >> 4;
+    };
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const int X = x + pad_x, Y = y + pad_y, cx = X >> 1, cy = Y >> 1;
+            const size_t c = (size_t)cy * cw + cx;
+            const int k = sel[c];
+            const int vx = k == 0 ? qf[2 * c] : k == 1 ? -(int)qb[2 * c] : 0, vy = k == 0 ? qf[2 * c + 1] : k == 1 ? -(int)qb[2 * c + 1] : 0;
+            const int p1x = 8 * cx - floor_div(num * vx + den / 2, den), p1y = 8 * cy - floor_div(num * vy + den / 2, den);
+            const int p2x = p1x + vx, p2y = p1y + vy;
+            const int t1x = (p1x >> 2) + (X & 1) - pad_x, t1y = (p1y >> 2) + (Y & 1) - pad_y;
+            const int t2x = (p2x >> 2) + (X & 1) - pad_x, t2y = (p2y >> 2) + (Y & 1) - pad_y;
+            for (int ch = 0; ch < 3; ++ch)
+                out[((size_t)y * width + x) * 3 + ch] =
+                    (uint8_t)(((den - num) * sample(bgr1, t1x, t1y, p1x & 3, p1y & 3, ch) +
+                               num * sample(bgr2, t2x, t2y, p2x & 3, p2y & 3, ch) + den / 2) / den);
+        }
+    return BBME_OK;
+}
+
 int bbme_spiral_host(int search_size, int block_size, int16_t *dx, int16_t *dy, int capacity, int *count)
 {
     if (!count) return bbme::fail(BBME_ERR_INVALID, "bbme_spiral_host: null count");

@@ -3178,7 +3178,7 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
-// k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate and K12 k_subpel_interpolate.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate and K12b k_subpel_interpolate_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window.
 // =======================================================================================
@@ -4493,6 +4493,209 @@ __global__ __launch_bounds__(256) void k_subpel_interpolate(SiArgs a)
     if (!a.partial) return;
     __shared__ uint32_t part[4][4];
     store_partial4(a.partial, (size_t)blockIdx.z * gridDim.y + pair, part, n0, n1, n2, csum);
+}
+
+// =======================================================================================
+// K12b.  The BGR SUBPEL INTERPOLATION RULE of include/bbme.h: k_subpel_interpolate's selection on the LUMA planes (si_select: the
+// same loads through si_cell, the same multiply-shifts by `magic`, validity by si_inside and v_sad_u8 on the packed rounded samples),
+// then both B,G,R frames sampled bilinearly at the selected P1 and P2 and blended, written as the unpadded frame.  The sibling of
+// k_subpel_interpolate and of k_interpolate_bgr in the gather family: the shared split of runs of 4 cells of one cell row
+// (gather_index / gather_split), QF and QB by load_mv4, blockIdx.z = phase num0 + z, so that every phase but the first finds planes,
+// grids and colour in L2 as far as they fit; one pair per launch.
+// Colour loads.  A cell's 2x2 output pixels need, per frame, 2 + (fx != 0) pixels of 2 + (fy != 0) rows from t = (P >> 2) -
+// (pad_x, pad_y) on: up to 3 rows of 9 contiguous bytes (bgr_three).  Where those pixels lie inside the frame's row they arrive as
+// unaligned dwords (a dword and a u16 for two pixels; two dwords and a byte for three); at the frame's edges pixel by pixel in
+// single bytes, a pixel outside reading 0 without a load.  A row or a column of weight 0 is not loaded, and no byte outside the
+// colour frames is read.
+// Arithmetic.  Separable as the rule allows: the horizontal sums (4 - fx) T0 + fx T1 <= 1020 of the rows, then the vertical sum
+// with the single rounding.  B and R share a word in 16-bit lanes (T & 0xff00ff; the sums stay below 4088 < 2^16), G has its own.
+// The blend divides by den with k_interpolate's multiply-shift: numerators below 255 * 256 + 128.
+// Stores are k_interpolate_bgr's: a run's row of 24 bytes as six dwords where the run is whole, inside the frame and its row
+// address dword-aligned; bytes otherwise (an odd pad_x, a caller's odd pitch, a cut run, the frame's edges -- with an odd padding
+// cells straddle the frame and only their pixels inside are written).  Runs wholly outside the frame load nothing.
+// A template over the runs per lane (instantiated with kSiRunsPerLane): template kernels are emitted behind the plain ones in the
+// order of their first use, so this one lies behind every kernel of the estimate in the code object.  As a plain kernel it lay
+// behind k_subpel_interpolate, and every k_search_* and k_reg_* kernel lay 77 056 bytes further on than before.
+// =======================================================================================
+struct SiBgrArgs {
+    const uint8_t *img1, *img2;           // level-0 padded luma planes, pitch = width
+    const mv_t *qf, *qb;                  // quarter-pel grids: cw entries per row, rows q4_pitch cells apart; qb may be null
+    const uint8_t *bgr1, *bgr2;           // the fw x fh colour frames, rows bgr_pitch bytes apart
+    uint8_t *out;                         // the fw x fh B,G,R frames (rows out_pitch, phases out_stride bytes apart)
+    size_t out_stride;
+    int width, height, cw, q4_pitch, num0, den, out_pitch;
+    int fw, fh, pad_x, pad_y, bgr_pitch;
+    uint32_t magic;                       // floor(2^32 / den) + 1
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * height / 2
+};
+
+// What the cell with the quarter-pel origin (ox4, oy4) = 4 o selects: hypothesis k and its cost, P1 and v (P2 = P1 + v).  It is
+// k_subpel_interpolate's selection, statement by statement; z1 and z2 are the cells of the zero hypothesis.  (k_subpel_interpolate
+// keeps its written-out text: taken through this helper its registers and size stay but its instructions change, and that kernel
+// was not measured again.)
+struct SiPick { uint32_t k, cost; int p1x, p1y, vx, vy; };
+
+__device__ __forceinline__ SiPick si_select(const uint8_t *img1, const uint8_t *img2, int W, int H, int ox4, int oy4, uint32_t qf,
+                                            uint32_t qb, bool has_b, uint32_t z1, uint32_t z2, int num, int half, int bias,
+                                            uint32_t magic)
+{
+    SiPick s{2u, ~0u, ox4, oy4, 0, 0};                        // nothing selected yet
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h == 1 && !has_b) break;
+        const int vx = h ? -mv_x(qb) : mv_x(qf), vy = h ? -mv_y(qb) : mv_y(qf);
+        const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
+        const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
+        const int p1x = ox4 - sx, p1y = oy4 - sy, p2x = p1x + vx, p2y = p1y + vy;
+        if (!si_inside(p1x, W) || !si_inside(p2x, W) || !si_inside(p1y, H) || !si_inside(p2y, H)) continue;
+        const uint32_t q1 = si_cell(img1, W, p1x >> 2, p1y >> 2, p1x & 3, p1y & 3);
+        const uint32_t q2 = si_cell(img2, W, p2x >> 2, p2y >> 2, p2x & 3, p2y & 3);
+        const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
+        if (c < s.cost) s = SiPick{(uint32_t)h, c, p1x, p1y, vx, vy};          // strictly cheaper: the earliest of equals stays
+    }
+    const uint32_t cz = __builtin_amdgcn_sad_u8(z1, z2, 0u);
+    if (cz < s.cost) s = SiPick{2u, cz, ox4, oy4, 0, 0};
+    return s;
+}
+
+// Pixels x, x + 1 and, with x1, x + 2 of row y of a colour frame, each as B | G << 8 | R << 16; a pixel outside the frame is 0,
+// and without x1 the third is 0 and not read
+__device__ __forceinline__ void bgr_three(const uint8_t *img, int pitch, int fw, int fh, int x, int y, int x1, uint32_t (&p)[3])
+{
+    p[0] = p[1] = p[2] = 0;
+    if (y < 0 || y >= fh || x + 1 + x1 < 0 || x >= fw) return;
+    const uint8_t *row = img + (size_t)y * pitch;
+    if (x >= 0 && x + 2 + x1 <= fw) {                         // bytes 3 x .. 3 x + 5 + 3 x1 lie in the row
+        const uint8_t *q = row + 3 * x;
+        const uint32_t d0 = reinterpret_cast<const ua_u32 *>(q)->v;
+        p[0] = d0 & 0xffffffu;
+        if (x1) {
+            const uint32_t d1 = reinterpret_cast<const ua_u32 *>(q + 4)->v;
+            p[1] = (d0 >> 24) | (d1 & 0xffffu) << 8;
+            p[2] = (d1 >> 16) | (uint32_t)q[8] << 16;
+        } else {
+            p[1] = (d0 >> 24) | (uint32_t)reinterpret_cast<const ua_u16 *>(q + 4)->v << 8;
+        }
+        return;
+    }
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int px = x + m;
+        if (m >= 2 + x1 || px < 0 || px >= fw) continue;
+        const uint8_t *q = row + 3 * px;
+        p[m] = (uint32_t)q[0] | (uint32_t)q[1] << 8 | (uint32_t)q[2] << 16;
+    }
+}
+
+// The 2x2 pixels of a colour frame sampled at the integer position (tx, ty) (frame coordinates) with the fractions (fx, fy):
+// e[r][m] holds B in bits 0-7 and R in bits 16-23, g[r][m] holds G
+__device__ __forceinline__ void si_bgr_cell(const uint8_t *img, int pitch, int fw, int fh, int tx, int ty, int fx, int fy,
+                                            uint32_t (&e)[2][2], uint32_t (&g)[2][2])
+{
+    const int x1 = fx != 0, y1 = fy != 0;
+    const uint32_t wx = (uint32_t)fx, wy = (uint32_t)fy;
+    uint32_t he[3][2], hg[3][2];                              // the horizontal sums of the three rows' two pixels, <= 1020 a lane
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        uint32_t p[3] = {0, 0, 0};
+        if (k < 2 + y1) bgr_three(img, pitch, fw, fh, tx, ty + k, x1, p);
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            he[k][m] = (4u - wx) * (p[m] & 0xff00ffu) + wx * (p[m + 1] & 0xff00ffu);
+            hg[k][m] = (4u - wx) * ((p[m] >> 8) & 0xffu) + wx * ((p[m + 1] >> 8) & 0xffu);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            e[r][m] = (((4u - wy) * he[r][m] + wy * he[r + 1][m] + 0x00080008u) >> 4) & 0x00ff00ffu;
+            g[r][m] = ((4u - wy) * hg[r][m] + wy * hg[r + 1][m] + 8u) >> 4;
+        }
+}
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_subpel_interpolate_bgr(SiBgrArgs a)
+{
+    const mv_t *QF = a.qf, *QB = a.qb;
+    const int W = a.width, H = a.height, CW = a.cw, den = a.den, num = a.num0 + (int)blockIdx.z, half = den >> 1;
+    const uint32_t magic = a.magic, w1 = (uint32_t)(den - num), w2 = (uint32_t)num;
+    const int bias = 32768 * den;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        const int oy = 2 * cy;
+        const int ry = oy - a.pad_y, rx = 2 * x0 - a.pad_x;   // the run's first pixel in frame coordinates
+        if (ry + 1 < 0 || ry >= a.fh || rx + 2 * n <= 0 || rx >= a.fw) continue;      // no pixel of the run is in the frame
+        uint32_t qf[4], qb[4] = {0, 0, 0, 0}, z1[4], z2[4];
+        load_mv4(QF + (size_t)cy * a.q4_pitch + x0, n, qf);
+        if (QB) load_mv4(QB + (size_t)cy * a.q4_pitch + x0, n, qb);
+        const size_t o0 = (size_t)oy * W + 2 * x0;
+        if (n == 4) {                                         // the zero hypothesis' cells: 8 bytes of each plane row
+            const ua_u32x2 t1 = *reinterpret_cast<const ua_u32x2 *>(a.img1 + o0), u1 = *reinterpret_cast<const ua_u32x2 *>(a.img1 + o0 + W);
+            const ua_u32x2 t2 = *reinterpret_cast<const ua_u32x2 *>(a.img2 + o0), u2 = *reinterpret_cast<const ua_u32x2 *>(a.img2 + o0 + W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int sh = 16 * (j & 1);
+                z1[j] = ((t1.v[j >> 1] >> sh) & 0xffffu) | ((u1.v[j >> 1] >> sh) << 16);
+                z2[j] = ((t2.v[j >> 1] >> sh) & 0xffffu) | ((u2.v[j >> 1] >> sh) << 16);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                z1[j] = z2[j] = 0;
+                if (j >= n) continue;
+                z1[j] = ip_cell(a.img1, W, 2 * (x0 + j), oy);
+                z2[j] = ip_cell(a.img2, W, 2 * (x0 + j), oy);
+            }
+        }
+        uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows, 24 bytes each
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const SiPick s = si_select(a.img1, a.img2, W, H, 8 * (x0 + j), 8 * cy, qf[j], qb[j], QB != nullptr, z1[j], z2[j], num, half,
+                                       bias, magic);
+            const int p2x = s.p1x + s.vx, p2y = s.p1y + s.vy;
+            uint32_t e1[2][2], g1[2][2], e2[2][2], g2[2][2];
+            si_bgr_cell(a.bgr1, a.bgr_pitch, a.fw, a.fh, (s.p1x >> 2) - a.pad_x, (s.p1y >> 2) - a.pad_y, s.p1x & 3, s.p1y & 3, e1, g1);
+            si_bgr_cell(a.bgr2, a.bgr_pitch, a.fw, a.fh, (p2x >> 2) - a.pad_x, (p2y >> 2) - a.pad_y, p2x & 3, p2y & 3, e2, g2);
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                uint64_t px = 0;
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const uint32_t vb = __umulhi(w1 * (e1[y][m] & 0xffu) + w2 * (e2[y][m] & 0xffu) + (uint32_t)half, magic);
+                    const uint32_t vg = __umulhi(w1 * g1[y][m] + w2 * g2[y][m] + (uint32_t)half, magic);
+                    const uint32_t vr = __umulhi(w1 * (e1[y][m] >> 16) + w2 * (e2[y][m] >> 16) + (uint32_t)half, magic);
+                    px |= (uint64_t)(vb | vg << 8 | vr << 16) << (24 * m);
+                }
+                const int bit = 48 * j;                       // the cell's six bytes go to bytes 6 j .. 6 j + 5 of the row
+                rows[y][bit >> 6] |= px << (bit & 63);
+                if ((bit & 63) > 16) rows[y][(bit >> 6) + 1] |= px >> (64 - (bit & 63));
+            }
+        }
+#pragma unroll
+        for (int y = 0; y < 2; ++y) {
+            if (ry + y < 0 || ry + y >= a.fh) continue;
+            uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(ry + y) * a.out_pitch + (ptrdiff_t)3 * rx;
+            if (n == 4 && rx >= 0 && rx + 8 <= a.fw && ((uintptr_t)q & 3u) == 0) {
+                uint32_t *o = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+                for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[y][d >> 1] >> (32 * (d & 1)));
+            } else {
+#pragma unroll
+                for (int p = 0; p < 8; ++p) {
+                    if (p >= 2 * n || rx + p < 0 || rx + p >= a.fw) continue;
+#pragma unroll
+                    for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[y][k >> 3] >> (8 * (k & 7)));
+                }
+            }
+        }
+    }
 }
 
 }  // namespace bbme

@@ -31,7 +31,8 @@
 // bilinear quarter-pel samples of frame 2), the same unpadded crop, and prints the PSNR of both predictions against frame 1.
 // --interpolate-subpel PREFIX --factor N writes --interpolate's frames made at quarter-pel positions instead (the subpel
 // interpolation rule of include/bbme.h: both fields refined to quarter-pel, every cell placed and sampled at its quarter-pel
-// position of the phase), as PREFIX_k.pgm, the same unpadded crop; on colour frames the frames of their luma.
+// position of the phase), as PREFIX_k.pgm, the same unpadded crop; on colour frames the frames of their luma and, with
+// --no-upsample (which keeps the colour), additionally PREFIX_k.ppm, colour frames by the BGR subpel interpolation rule.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -233,6 +234,11 @@ int main(int argc, char **argv)
                 const std::string name = std::string(interpolate_subpel) + "_" + std::to_string(k) + ".pgm";
                 bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
                                            img.data.data() + (size_t)py * img.cols + px));
+                if (colour && !upsample) {
+                    const bbme::ImageBGR bgr = motion_pair.interpolateSubpelBGR(k, factor);
+                    const std::string ppm = std::string(interpolate_subpel) + "_" + std::to_string(k) + ".ppm";
+                    bbme::check(bbme_ppm_write_bgr(ppm.c_str(), bgr.cols, bgr.rows, bgr.data.data()));
+                }
             }
         }
         if (denoise) {

@@ -322,6 +322,14 @@ public:
         bbme::check(bbme_get_interpolated_bgr_host(ctx_, 0, num, den, img.data.data()));
         return img;
     }
+    // interpolateSubpel in colour (the BGR subpel interpolation rule of include/bbme.h), for an MF made of colour frames: the
+    // quarter-pel selection on the luma planes, both colour frames sampled at the quarter-pel positions; the UNPADDED frame.
+    bbme::ImageBGR interpolateSubpelBGR(int num = 1, int den = 2)
+    {
+        bbme::ImageBGR img(padded_height - 2 * padding_y, padded_width - 2 * padding_x);
+        bbme::check(bbme_get_subpel_interpolated_bgr_host(ctx_, 0, num, den, img.data.data()));
+        return img;
+    }
     // temporalFilter in colour (the BGR temporal filter rule of include/bbme.h), for an MF made of colour frames: the stored
     // B,G,R frame `which` averaged with the other one where their 2x2 cells match better than `strength` in every channel;
     // the UNPADDED frame.

@@ -640,8 +640,8 @@ class MF:
 
     def _get_interpolated(self, pair, num, den, out, what, bgr=False, subpel=False):
         out = _host_out(out, self._out_shape(bgr), np.uint8, what)
-        get = (self._lib.bbme_get_interpolated_bgr_host if bgr else self._lib.bbme_get_subpel_interpolated_host if subpel
-               else self._lib.bbme_get_interpolated_host)
+        get = ((self._lib.bbme_get_subpel_interpolated_bgr_host if subpel else self._lib.bbme_get_interpolated_bgr_host) if bgr
+               else self._lib.bbme_get_subpel_interpolated_host if subpel else self._lib.bbme_get_interpolated_host)
         _capi.check(get(self._ctx, pair, int(num), int(den), out.ctypes.data))
         return out
 
@@ -651,8 +651,8 @@ class MF:
         if not 2 <= den <= 256:
             raise _capi.BbmeError(_capi.ERR_INVALID, "%s %d outside 2..256" % (what, den))
         frames = torch.empty((den - 1,) + self._out_shape(bgr), dtype=torch.uint8, device="cuda:%d" % self.device)
-        run = (self._lib.bbme_interpolate_bgr_device if bgr else self._lib.bbme_subpel_interpolate_device if subpel
-               else self._lib.bbme_interpolate_device)
+        run = ((self._lib.bbme_subpel_interpolate_bgr_device if subpel else self._lib.bbme_interpolate_bgr_device) if bgr
+               else self._lib.bbme_subpel_interpolate_device if subpel else self._lib.bbme_interpolate_device)
         _capi.check(run(self._ctx, pair, 1, den - 1, den, _ptr(frames), frames.stride(1), frames.stride(0), None))
         self.synchronize()
         return frames.cpu().numpy()
@@ -813,6 +813,54 @@ class MF:
             _ptr(sel), sel.stride(1) if sel is not None else 0, max(sel.stride(0), 0) if sel is not None else 0,
             _ptr(stats), C.c_void_p(stream or 0)))
         return out, sel, stats
+
+    # -- colour frames at quarter-pel positions (the BGR SUBPEL INTERPOLATION RULE of include/bbme.h) --------------------------
+    def interpolate_subpel_bgr(self, num=1, den=2, pair=0, out=None):
+        """interpolate_subpel() in colour: its selection, made on the luma planes at quarter-pel positions, applied to the B,G,R
+        frames the context was fed, every pixel sampled bilinearly at its quarter-pel position in both -> the UNPADDED (H, W, 3)
+        uint8 frame.  BbmeError (ERR_STATE) when a frame of the pair was set grey."""
+        return self._get_interpolated(pair, num, den, out, "interpolate_subpel_bgr", bgr=True, subpel=True)
+
+    def interpolate_run_subpel_bgr(self, factor, pair=0):
+        """All factor - 1 phases of interpolate_subpel_bgr from two refinement launches and one interpolation launch ->
+        (factor - 1, H, W, 3) uint8."""
+        return self._interpolate_run(factor, pair, "interpolate_run_subpel_bgr: factor", True, subpel=True)
+
+    def cells_interpolate_subpel_bgr_device(self, qf, qb=None, bgr1=None, bgr2=None, num0=1, count=1, den=2, pair=0, out=None,
+                                            stream=None):
+        """The BGR subpel interpolation rule on the context's luma planes of `pair` and any two quarter-pel grids in HBM (as
+        cells_interpolate_subpel_device: rows may be further apart than CW cells, both with the same row pitch): bgr1, bgr2
+        uint8 CUDA tensors (H, W, 3) with packed pixels and a common row pitch, or both None for the colour the context stored;
+        phases num0 .. num0 + count - 1 of den in one launch into out, a uint8 CUDA tensor (count, H, W, 3) with packed pixels
+        whose rows and frames may be further apart than packed (any alignment).  On the given HIP stream handle (default: the
+        context's), ordered behind the context's stream; no host wait.  Needs frames, but no estimate."""
+        import torch
+        what = "cells_interpolate_subpel_bgr_device"
+        ch, cw = self.cells_shape
+        h, w = self.orig_height, self.orig_width
+        count = int(count)
+        for t in (qf, qb):
+            if t is qb and qb is None:
+                continue
+            if t is None or not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.stride(2) == 1
+                                 and t.stride(1) == 2 and t.stride(0) >= 2 * cw and t.stride(0) % 2 == 0 and t.data_ptr() % 4 == 0
+                                 and t.stride(0) == qf.stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: grids must be int16 CUDA tensors of shape (%d, %d, 2) with packed "
+                                      "cells and rows a common whole number of cells apart" % (what, ch, cw))
+        for t in (bgr1, bgr2):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and _packed_pixels(t)
+                                      and (bgr1 is None or t.stride(0) == bgr1.stride(0))):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: colour frames must be uint8 CUDA tensors of shape (%d, %d, 3) with "
+                                      "packed pixels and a common row pitch" % (what, h, w))
+        if out is None or not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (count, h, w, 3)
+                               and out.stride(3) == 1 and out.stride(2) == 3):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape (%d, %d, %d, 3) with packed "
+                                  "pixels" % (what, count, h, w))
+        self._behind_torch(qf, qb, bgr1, bgr2, out)
+        _capi.check(self._lib.bbme_cells_subpel_interpolate_bgr_device(
+            self._ctx, pair, _ptr(qf), _ptr(qb), qf.stride(0) // 2, _ptr(bgr1), _ptr(bgr2), bgr1.stride(0) if bgr1 is not None else 0,
+            int(num0), count, int(den), _ptr(out), out.stride(1), max(out.stride(0), 0), C.c_void_p(stream or 0)))
+        return out
 
     # -- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rule of include/bbme.h) ------
     def _get_temporal_filtered(self, pair, which, strength, out, what, bgr=False):
@@ -1185,6 +1233,10 @@ class MFBatch(MF):
         """MF.interpolate_subpel of one pair."""
         return self._get_interpolated(pair, num, den, out, "get_pair_interpolated_subpel", subpel=True)
 
+    def get_pair_interpolated_subpel_bgr(self, pair, num=1, den=2, out=None):
+        """MF.interpolate_subpel_bgr of one pair."""
+        return self._get_interpolated(pair, num, den, out, "get_pair_interpolated_subpel_bgr", bgr=True, subpel=True)
+
     def interpolation_stats_subpel_all(self, num=1, den=2, window=None):
         """MF.interpolation_stats_subpel of every pair, in order, from two refinement launches and one interpolation launch."""
         return self._interpolation_stats(num, den, window, subpel=True)
@@ -1535,10 +1587,8 @@ def bgr_to_gray(frame):
     return out
 
 
-def interpolate_cells_bgr(luma1, luma2, bgr1, bgr2, fwd, bwd=None, num=1, den=2, pad_x=0, pad_y=0):
-    """The BGR interpolation rule of include/bbme.h on the CPU (bbme_interpolate_bgr_host): luma1, luma2 the padded uint8
-    (H0, W0) luma planes, bgr1, bgr2 the uint8 (H, W, 3) colour frames whose lumas they hold at (pad_x, pad_y) (H0 = H + 2 pad_y,
-    W0 = W + 2 pad_x), fwd and bwd (may be None) int16 (H0 / 2, W0 / 2, 2) cell grids -> the unpadded (H, W, 3) uint8 frame."""
+def _interpolate_cells_bgr(what, host, luma1, luma2, bgr1, bgr2, fwd, bwd, num, den, pad_x, pad_y):
+    """interpolate_cells_bgr and interpolate_cells_subpel_bgr: `host` names the C call, `what` the caller in the errors."""
     luma1 = np.ascontiguousarray(luma1, np.uint8)
     luma2 = np.ascontiguousarray(luma2, np.uint8)
     bgr1 = np.ascontiguousarray(bgr1, np.uint8)
@@ -1546,16 +1596,32 @@ def interpolate_cells_bgr(luma1, luma2, bgr1, bgr2, fwd, bwd=None, num=1, den=2,
     fwd = np.ascontiguousarray(fwd, np.int16)
     bwd = None if bwd is None else np.ascontiguousarray(bwd, np.int16)
     if luma1.ndim != 2 or luma1.shape != luma2.shape or bgr1.ndim != 3 or bgr1.shape[2] != 3 or bgr1.shape != bgr2.shape:
-        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells_bgr: two uint8 planes (H0, W0) and two uint8 frames (H, W, 3)")
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: two uint8 planes (H0, W0) and two uint8 frames (H, W, 3)" % what)
     h0, w0 = luma1.shape
     h, w = bgr1.shape[:2]
     if fwd.shape != (h0 // 2, w0 // 2, 2) or (bwd is not None and bwd.shape != fwd.shape):
-        raise _capi.BbmeError(_capi.ERR_INVALID, "interpolate_cells_bgr: int16 grids of shape (H0 / 2, W0 / 2, 2)")
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: int16 grids of shape (H0 / 2, W0 / 2, 2)" % what)
     out = np.empty((h, w, 3), np.uint8)
-    _capi.check(_capi.lib().bbme_interpolate_bgr_host(luma1.ctypes.data, luma2.ctypes.data, w0, h0, bgr1.ctypes.data, bgr2.ctypes.data,
-                                                      w, h, int(pad_x), int(pad_y), fwd.ctypes.data,
-                                                      None if bwd is None else bwd.ctypes.data, int(num), int(den), out.ctypes.data))
+    _capi.check(getattr(_capi.lib(), host)(luma1.ctypes.data, luma2.ctypes.data, w0, h0, bgr1.ctypes.data, bgr2.ctypes.data,
+                                           w, h, int(pad_x), int(pad_y), fwd.ctypes.data,
+                                           None if bwd is None else bwd.ctypes.data, int(num), int(den), out.ctypes.data))
     return out
+
+
+def interpolate_cells_bgr(luma1, luma2, bgr1, bgr2, fwd, bwd=None, num=1, den=2, pad_x=0, pad_y=0):
+    """The BGR interpolation rule of include/bbme.h on the CPU (bbme_interpolate_bgr_host): luma1, luma2 the padded uint8
+    (H0, W0) luma planes, bgr1, bgr2 the uint8 (H, W, 3) colour frames whose lumas they hold at (pad_x, pad_y) (H0 = H + 2 pad_y,
+    W0 = W + 2 pad_x), fwd and bwd (may be None) int16 (H0 / 2, W0 / 2, 2) cell grids -> the unpadded (H, W, 3) uint8 frame."""
+    return _interpolate_cells_bgr("interpolate_cells_bgr", "bbme_interpolate_bgr_host", luma1, luma2, bgr1, bgr2, fwd, bwd, num, den,
+                                  pad_x, pad_y)
+
+
+def interpolate_cells_subpel_bgr(luma1, luma2, bgr1, bgr2, qf, qb=None, num=1, den=2, pad_x=0, pad_y=0):
+    """The BGR subpel interpolation rule of include/bbme.h on the CPU (bbme_subpel_interpolate_bgr_host): interpolate_cells_bgr
+    with qf and qb (may be None) int16 (H0 / 2, W0 / 2, 2) grids of QUARTER-PEL vectors (subpel_cells' output), every pixel of
+    both colour frames sampled bilinearly at its quarter-pel position -> the unpadded (H, W, 3) uint8 frame."""
+    return _interpolate_cells_bgr("interpolate_cells_subpel_bgr", "bbme_subpel_interpolate_bgr_host", luma1, luma2, bgr1, bgr2, qf, qb,
+                                  num, den, pad_x, pad_y)
 
 
 def plan_padding(width, height, search_size, block_size):

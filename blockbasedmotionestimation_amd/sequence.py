@@ -362,7 +362,7 @@ def estimate_frames_bidirectional(frames, search_size, block_size, device=None, 
     return out
 
 
-def interpolate_frames(frames, search_size, block_size, factor, device=None, in_flight=4, batch=2, subpel=False):
+def interpolate_frames(frames, search_size, block_size, factor, device=None, in_flight=4, batch=2, subpel_bgr=False, subpel=False):
     """Frame-rate up-conversion of a video on ONE GPU: every original frame, and factor - 1 interpolated frames (phases k /
     factor, the interpolation rule of include/bbme.h) between each consecutive two -> factor * (len(frames) - 1) + 1 uint8
     (H, W) frames, the interpolated ones the unpadded windows of the padded result.  Runs on the chain plan of
@@ -372,8 +372,12 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
     GPU from the colour frames (the luma rule), the fields are the luma's, and the frames in between come from the stored
     colour by the BGR interpolation rule (MF.interpolate_run_bgr); still every frame is set once.
     subpel=True: the frames in between come from the subpel interpolation rule on the same plan (MF.interpolate_run_subpel:
-    both fields refined to quarter-pel, the cells placed and sampled at quarter-pel positions).  Grey video only: colour output
-    keeps the integer rule, and colour frames with subpel=True are a ValueError."""
+    both fields refined to quarter-pel, the cells placed and sampled at quarter-pel positions).  Grey video only: colour frames
+    with subpel=True are a ValueError.
+    subpel_bgr=True is the way to get quarter-pel colour: the colour frames in between come from the BGR subpel interpolation
+    rule on the same plan (MF.interpolate_run_subpel_bgr: the quarter-pel selection on the luma planes, both stored colour frames
+    sampled bilinearly at the quarter-pel positions); still every frame is set once.  Colour video only: grey frames with
+    subpel_bgr=True are a ValueError."""
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
     bgr = bool(frames) and frames[0].ndim == 3
     factor = int(factor)
@@ -381,6 +385,8 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
         raise ValueError("interpolate_frames: factor %d outside 2..256" % factor)
     if bgr and subpel:
         raise ValueError("interpolate_frames: subpel=True takes grey frames; colour output keeps the integer rule")
+    if subpel_bgr and frames and not bgr:
+        raise ValueError("interpolate_frames: subpel_bgr=True takes colour frames (H, W, 3); grey frames take subpel=True")
     n_pairs = len(frames) - 1
     if n_pairs < 1:
         return frames
@@ -392,7 +398,8 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
         h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
         for p in range(count):
             if bgr:
-                between[first + p] = list(mf.interpolate_run_bgr(factor, pair=p))
+                between[first + p] = list(mf.interpolate_run_subpel_bgr(factor, pair=p) if subpel_bgr
+                                          else mf.interpolate_run_bgr(factor, pair=p))
                 continue
             run = mf.interpolate_run_subpel(factor, pair=p) if subpel else mf.interpolate_run(factor, pair=p)      # waits for this context's stream only
             between[first + p] = [np.ascontiguousarray(f[py:py + h, px:px + w]) for f in run]

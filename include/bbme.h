@@ -736,9 +736,9 @@ int bbme_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, un
  * q != (0, 0), the sum of cost(0, 0) over the valid cells and the sum of best over the valid cells.  The statistics do not need
  * the grid to be written.
  * A context made for up-sampled frames (bbme_set_frames_*_x4) refines its 4x planes: the result is then 1/16 pel of the source.
- * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE and the SUBPEL INTERPOLATION RULE below read
- * quarter-pel vectors; the other rules that take a cell grid (integer compensation, integer and colour interpolation, the
- * temporal filters) do not: they are integer.
+ * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE, the SUBPEL INTERPOLATION RULE and the BGR SUBPEL
+ * INTERPOLATION RULE below read quarter-pel vectors; the other rules that take a cell grid (integer compensation, the INTERPOLATION
+ * RULE and the BGR INTERPOLATION RULE, the temporal filters) do not: they are integer.
  * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, q4_pitch_cells < CW, a
  * window as for the consistency rule, a d_q4 of bbme_cells_subpel_device that overlaps its input grid, an odd width or height on
  * the host call; BBME_ERR_UNSUPPORTED beyond 8188; BBME_ERR_STATE when frames are unset or a chain slot is unset, for which = 0
@@ -861,8 +861,8 @@ int bbme_subpel_compensation_error(bbme_ctx *ctx, int which, const int *window, 
  * blend of the INTERPOLATION RULE on zero grids.  (3) The grid call has no size limit of its own: |num v| <= (den - 1) 32768 for
  * every int16 v, -(-32768) included, so num v + den / 2 + 32768 den stays below 2^24, where the multiply-shift by
  * floor(2^32 / den) + 1 is the exact quotient, and P1 and P2 are computed in 32 bits from any int16.
- * A context made for up-sampled frames (bbme_set_frames_*_x4) interpolates its 4x planes, a colour context its luma planes (there
- * is no quarter-pel form of the BGR INTERPOLATION RULE).
+ * A context made for up-sampled frames (bbme_set_frames_*_x4) interpolates its 4x planes, a colour context its luma planes (the
+ * BGR SUBPEL INTERPOLATION RULE below makes the colour frame).
  * Errors: those of the INTERPOLATION RULE's calls, and q4_pitch_cells < CW; for the three calls on the context's own fields
  * BBME_ERR_STATE exactly as bbme_interpolate_device and BBME_ERR_UNSUPPORTED beyond 8188 as bbme_subpel_device.  None of these
  * calls changes context state; their scratch buffers are the context's own and independent of the other getters'.  All work on
@@ -892,6 +892,57 @@ int bbme_subpel_interpolate_device(bbme_ctx *ctx, int pair, int num0, int count,
                                    size_t out_stride, void *hip_stream);
 int bbme_get_subpel_interpolated_host(bbme_ctx *ctx, int pair, int num, int den, uint8_t *out);
 int bbme_subpel_interpolation_stats(bbme_ctx *ctx, int num, int den, const int *window, unsigned long long *stats);
+
+/* BGR SUBPEL INTERPOLATION RULE (this project's own): the colour frame at phase num / den at QUARTER-PEL positions; the SUBPEL
+ * INTERPOLATION RULE's selection with the BGR INTERPOLATION RULE's output.
+ * Inputs: those of the SUBPEL INTERPOLATION RULE -- the level-0 padded LUMA planes I1, I2 (W0 x H0), the quarter-pel grids QF and,
+ * optionally, QB, the phase num / den -- and those the BGR INTERPOLATION RULE adds: the two colour frames C1, C2 (W x H pixels of
+ * B,G,R) whose lumas the planes hold at (pad_x, pad_y): W0 = W + 2 pad_x, H0 = H + 2 pad_y.
+ * Selection is EXACTLY the SUBPEL INTERPOLATION RULE's, on the luma planes, in padded quarter-pel coordinates: hypotheses, their
+ * order, the shift s, P1, P2, validity, the cost on the rounded luma samples and ties are unchanged, so the selection map and the
+ * statistics of a colour frame are those bbme_cells_subpel_interpolate_device returns; the colour calls make neither.
+ * The output is the UNPADDED W x H B,G,R frame.  Output pixel (x, y) has the padded position (X, Y) = (x + pad_x, y + pad_y) and
+ * belongs to cell (X >> 1, Y >> 1) at offset (j, r) = (X & 1, Y & 1).  With that cell's selected P1 and P2, for P in {P1, P2}:
+ *     t = (P.x >> 2, P.y >> 2) + (j, r) - (pad_x, pad_y)   (frame coordinates),   f = (P.x & 3, P.y & 3),
+ * and for every channel, with T00, T10, T01, T11 the frame's pixels at t + (0, 0), (1, 0), (0, 1), (1, 1),
+ *     sample = ((4 - fx) (4 - fy) T00 + fx (4 - fy) T10 + (4 - fx) fy T01 + fx fy T11 + 8) >> 4.
+ * A tap outside [0, W) x [0, H) reads 0 in every channel: the zero border the luma planes have (a selected hypothesis is valid, so
+ * such a tap lies in that border).  A tap of weight 0 is not read; no byte outside the colour frames is ever read.  With S1 the
+ * sample of C1 at P1 and S2 the one of C2 at P2,
+ *     out[y][x][c] = ((den - num) S1 + num S2 + den / 2) / den.
+ * pad_x and pad_y may be odd: cells then straddle the frame's edge and only their pixels inside the frame are written.
+ * Properties.  (1) On frames with B = G = R every channel of the result is the unpadded window of the grey SUBPEL INTERPOLATION
+ * RULE's result, bit for bit.  (2) With QF = 4 F and QB = 4 B for integer grids F and B, if den divides num v componentwise for
+ * every hypothesis v of every cell, the result is the BGR INTERPOLATION RULE's on F and B, bit for bit.  (3) With both grids zero
+ * the result is the in-place blend of the two colour frames.
+ * `count` consecutive phases come from one launch, frame q at d_out + q out_stride, rows out_pitch bytes apart (any alignment).
+ * Errors: the union of bbme_cells_interpolate_bgr_device's and bbme_cells_subpel_interpolate_device's: BBME_ERR_INVALID for a null
+ * context or required pointer, pair, den, num0, count, q4_pitch_cells < CW, bgr_pitch < 3 W, out_pitch < 3 W, a stride below one
+ * frame when count > 1, exactly one of d_bgr1 / d_bgr2 null; BBME_ERR_STATE when frames are unset, when stored colour is asked for
+ * and either frame of the pair has none, and for the two context-level calls without a valid pair of fields;
+ * BBME_ERR_UNSUPPORTED beyond 8188 for the two context-level calls (as bbme_subpel_device).  None of these calls changes context
+ * state.  All work on single, batched and chain contexts; in direction BACKWARD the two colour frames exchange together with the
+ * two planes (callers' frames too).
+ * bbme_subpel_interpolate_bgr_host: the rule on the CPU, no GPU: packed padded_w x padded_h luma planes (both even), packed
+ * width x height colour frames, packed (padded_h / 2) x (padded_w / 2) quarter-pel grids (qb may be NULL), out packed 3 width x
+ * height; BBME_ERR_INVALID unless padded_w = width + 2 pad_x and padded_h = height + 2 pad_y with pads >= 0.
+ * bbme_cells_subpel_interpolate_bgr_device: the context's planes of `pair`, ANY two quarter-pel grids in HBM of its cell geometry,
+ * rows of both q4_pitch_cells int16 pairs apart (d_qb may be null), and either the stored colour (d_bgr1 = d_bgr2 = null) or a
+ * caller's two frames in HBM, rows bgr_pitch bytes apart; on hip_stream (NULL = the ctx stream; another stream is first ordered
+ * behind it); no host wait; needs no valid pair of fields.
+ * bbme_subpel_interpolate_bgr_device: the context's own: both fields of `pair` refined into the context's quarter-pel buffer
+ * exactly as bbme_subpel_interpolate_device does, then one launch on the stored colour.  The caller orders calls for the same pair
+ * that it issues on different streams.
+ * bbme_get_subpel_interpolated_bgr_host: one phase of the same; synchronises; packed rows of 3 W bytes. */
+int bbme_subpel_interpolate_bgr_host(const uint8_t *luma1, const uint8_t *luma2, int padded_w, int padded_h, const uint8_t *bgr1,
+                                     const uint8_t *bgr2, int width, int height, int pad_x, int pad_y, const int16_t *qf,
+                                     const int16_t *qb, int num, int den, uint8_t *out);
+int bbme_cells_subpel_interpolate_bgr_device(bbme_ctx *ctx, int pair, const int16_t *d_qf, const int16_t *d_qb, int q4_pitch_cells,
+                                             const uint8_t *d_bgr1, const uint8_t *d_bgr2, int bgr_pitch, int num0, int count,
+                                             int den, uint8_t *d_out, int out_pitch, size_t out_stride, void *hip_stream);
+int bbme_subpel_interpolate_bgr_device(bbme_ctx *ctx, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch,
+                                       size_t out_stride, void *hip_stream);
+int bbme_get_subpel_interpolated_bgr_host(bbme_ctx *ctx, int pair, int num, int den, uint8_t *out);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
