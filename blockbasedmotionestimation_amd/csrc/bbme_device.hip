@@ -347,6 +347,11 @@ struct bbme_ctx {
                                                   // (enqueue_own_si)
     StatsScratch si_stats;                        // bbme_subpel_interpolation_stats (every pair) and
                                                   // bbme_cells_subpel_interpolate_device (one pair, `count` phases)
+    DevBuf<mv_t> tfs_q4;                          // the quarter-pel cells the context's own sub-pel temporal filter reads: the packed
+                                                  // forward grids of every pair, then their backward grids, allocated at first use
+                                                  // (TfSubpel::prepare)
+    StatsScratch tfs_stats;                       // bbme_subpel_temporal_filter_stats (every frame) and
+                                                  // bbme_cells_subpel_temporal_filter_device (one)
 };
 
 namespace {
@@ -2493,7 +2498,8 @@ int bbme_get_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int den, uint
 }
 
 // ---- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rules of include/bbme.h) --------------
-// Written once over a flavour: TfGrey filters the level-0 planes (k_temporal_filter), TfBgr the B,G,R frames (k_temporal_filter_bgr).
+// Written once over a flavour: TfGrey filters the level-0 planes (k_temporal_filter), TfBgr the B,G,R frames (k_temporal_filter_bgr),
+// TfSubpel (further down, behind the refinement it needs) the level-0 planes along quarter-pel grids (k_subpel_temporal_filter).
 
 constexpr int kTfMaxFrames = 2 * BBME_MAX_BATCH;          // a batch holds 2 batch frames, a chain batch + 1
 
@@ -2518,8 +2524,17 @@ static int check_tf_bgr_frame_colour(const bbme_ctx *c, int pair, int which, con
 
 // A flavour names the argument type and kernel, the size of a frame (`rows` rows of row_bytes), the statistics scratch, what the
 // arguments hold beyond TfArgs, and the context's own frames: their base, s_pair bytes from pair to pair and s_frame from a frame
-// to its next neighbour.  What only colour checks hangs on `bgr` in the bodies below.
-struct TfGrey {
+// to its next neighbour.  What only colour checks hangs on `bgr` in the bodies below, the pitch of a caller's quarter-pel grids on
+// `subpel`.  check_own is what the context-level calls check beyond the integer filter's; prepare runs on the stream before a
+// launch on the context's own frames (pairs pair0 .. along y, frames first .. along z) and may replace the grids in the arguments.
+struct TfNoPrepare {
+    static constexpr bool subpel = false;
+    static int check_own(const bbme_ctx *, const char *) { return BBME_OK; }
+    template <class Args>
+    static int prepare(bbme_ctx *, Args &, int, int, int, int, hipStream_t, const char *) { return BBME_OK; }
+};
+
+struct TfGrey : TfNoPrepare {
     using Args = TfArgs;
     static constexpr bool bgr = false;
     static constexpr const char *input = "plane", *staging_what = "the filtered frame", *stats_what = "the temporal filter statistics";
@@ -2537,7 +2552,7 @@ struct TfGrey {
     }
 };
 
-struct TfBgr {
+struct TfBgr : TfNoPrepare {
     using Args = TfBgrArgs;
     static constexpr bool bgr = true;
     static constexpr const char *input = "frame", *staging_what = "the filtered colour frame",
@@ -2657,11 +2672,13 @@ static typename F::Args tf_own_frames(const bbme_ctx *c, int thr, const int *win
 template <class F>
 static int tf_cells(bbme_ctx *c, const char *what, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next, int in_pitch,
                     const int16_t *d_to_prev, const int16_t *d_to_next, int thr, const int *window, uint8_t *d_out, int out_pitch,
-                    uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4, void *hip_stream)
+                    uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4, void *hip_stream, int q4_pitch = 0)
 {
     if (int rc = check_ctx(c)) return rc;
     const Level &L = c->lv[0];
     if (!d_cur || (!d_out && !d_weights && !d_stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (F::subpel && q4_pitch < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch, L.width / 2);
     if ((d_prev == nullptr) != (d_to_prev == nullptr) || (d_next == nullptr) != (d_to_next == nullptr))
         return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its %s and its grid", what, F::input);
     if (!d_prev && !d_next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
@@ -2680,6 +2697,7 @@ static int tf_cells(bbme_ctx *c, const char *what, const uint8_t *d_prev, const 
     typename F::Args a = tf_args<F>(c, thr, window);
     a.cur = d_cur; a.prev = d_prev; a.next = d_next;
     if constexpr (F::bgr) a.bgr_pitch = in_pitch;
+    if constexpr (F::subpel) a.q4_pitch = q4_pitch;
     a.gp = reinterpret_cast<const mv_t *>(d_to_prev); a.gn = reinterpret_cast<const mv_t *>(d_to_next);
     a.first_prev = a.last_next = 1;
     a.out = d_out; a.out_pitch = out_pitch;
@@ -2689,9 +2707,11 @@ static int tf_cells(bbme_ctx *c, const char *what, const uint8_t *d_prev, const 
 
 // frame `which` of `pair` of the context's own, into d_out on `stream`
 template <class F>
-static int enqueue_own_tf(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, hipStream_t stream)
+static int enqueue_own_tf(bbme_ctx *c, const char *what, int pair, int which, int thr, uint8_t *d_out, int out_pitch, hipStream_t stream)
 {
-    typename F::Args a = c->chain ? tf_own_frames<F>(c, thr, nullptr, 0, pair + which, 1) : tf_own_frames<F>(c, thr, nullptr, pair, which, 1);
+    const int pair0 = c->chain ? 0 : pair, first = c->chain ? pair + which : which;
+    typename F::Args a = tf_own_frames<F>(c, thr, nullptr, pair0, first, 1);
+    if (int rc = F::prepare(c, a, pair0, 1, first, 1, stream, what)) return rc;
     a.out = d_out; a.out_pitch = out_pitch;
     return enqueue_tf<F>(c, a, 1, 1, nullptr, nullptr, stream);
 }
@@ -2706,6 +2726,7 @@ static int check_tf_frame(const bbme_ctx *c, int pair, int which, int thr, const
     if (int rc = check_tf(c, thr, nullptr, what)) return rc;
     if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
     if (out_pitch) if (int rc = check_tf_out<F>(c, 1, *out_pitch, 0, what)) return rc;
+    if (int rc = F::check_own(c, what)) return rc;
     if (int rc = check_fields_state(c, what)) return rc;
     return F::bgr ? check_tf_bgr_frame_colour(c, pair, which, what) : BBME_OK;
 }
@@ -2717,7 +2738,7 @@ static int tf_device(bbme_ctx *c, const char *what, int pair, int which, int thr
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t stream;
     if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
-    return enqueue_own_tf<F>(c, pair, which, thr, d_out, out_pitch, stream);
+    return enqueue_own_tf<F>(c, what, pair, which, thr, d_out, out_pitch, stream);
 }
 
 template <class F>
@@ -2730,12 +2751,14 @@ static int tf_chain(bbme_ctx *c, const char *what, int first, int count, int thr
     if (int rc = check_tf(c, thr, nullptr, what)) return rc;
     if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
     if (int rc = check_tf_out<F>(c, count, out_pitch, out_stride, what)) return rc;
+    if (int rc = F::check_own(c, what)) return rc;
     if (int rc = check_fields_state(c, what)) return rc;
     if (F::bgr) if (int rc = check_tf_bgr_colour(c, first - 1, first + count, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     hipStream_t stream;
     if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
     typename F::Args a = tf_own_frames<F>(c, thr, nullptr, 0, first, count);
+    if (int rc = F::prepare(c, a, 0, 1, first, count, stream, what)) return rc;
     a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
     return enqueue_tf<F>(c, a, 1, count, nullptr, nullptr, stream);
 }
@@ -2746,7 +2769,7 @@ static int tf_host(bbme_ctx *c, const char *what, int pair, int which, int thr, 
     if (int rc = check_tf_frame<F>(c, pair, which, thr, out, nullptr, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
     return download_staged(c, (size_t)F::row_bytes(c) * F::rows(c), F::staging_what, out, [&](uint8_t *d) {
-        return enqueue_own_tf<F>(c, pair, which, thr, d, F::row_bytes(c), c->stream);
+        return enqueue_own_tf<F>(c, what, pair, which, thr, d, F::row_bytes(c), c->stream);
     });
 }
 
@@ -2756,6 +2779,7 @@ static int tf_stats(bbme_ctx *c, const char *what, int thr, const int *window, u
     if (int rc = check_ctx(c)) return rc;
     if (int rc = check_tf(c, thr, window, what)) return rc;
     if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = F::check_own(c, what)) return rc;
     if (int rc = check_fields_state(c, what)) return rc;
     if (F::bgr) if (int rc = check_tf_bgr_colour(c, 0, c->frames() - 1, what)) return rc;
     HIP_TRY(hipSetDevice(c->device));
@@ -2764,6 +2788,7 @@ static int tf_stats(bbme_ctx *c, const char *what, int thr, const int *window, u
     const int pairs = c->chain ? 1 : c->batch, count = c->chain ? c->batch + 1 : 2;
     typename F::Args a = tf_own_frames<F>(c, thr, window, 0, 0, count);
     return download_stats(c, F::stats(c), c->frames(), stats, [&] {
+        if (int rc = F::prepare(c, a, 0, pairs, 0, count, c->stream, what)) return rc;
         return enqueue_tf<F>(c, a, pairs, count, F::stats(c).partials_all(), F::stats(c).results(), c->stream);
     });
 }
@@ -3365,6 +3390,83 @@ int bbme_get_subpel_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int de
                            [&](uint8_t *d) {
         return enqueue_own_si_bgr(c, pair, num, 1, den, d, 3 * c->geom.width, 0, c->stream, what);
     });
+}
+
+// ---- temporal filter along quarter-pel grids (the SUBPEL TEMPORAL FILTER RULE of include/bbme.h; K13 k_subpel_temporal_filter) ----
+// The third flavour of the temporal filter's one path (tf_cells .. tf_stats above): the grey flavour's planes and frames, the
+// grids quarter-pel.  On the context's own frames the integer cells a launch reads are refined first (prepare).
+struct TfSubpel : TfGrey {
+    using Args = TfSpArgs;
+    static constexpr bool subpel = true;
+    static constexpr const char *staging_what = "the quarter-pel filtered frame", *stats_what = "the subpel temporal filter statistics";
+    static auto kernel() { return k_subpel_temporal_filter<kTfRunsPerLane>; }
+    static StatsScratch &stats(bbme_ctx *c) { return c->tfs_stats; }
+    static void geometry(const bbme_ctx *c, TfSpArgs &a) { a.q4_pitch = c->lv[0].width / 2; }
+    static int check_own(const bbme_ctx *c, const char *what) { return check_sp(c, nullptr, what); }
+    // The forward cells of every pair the launch reads as a grid into a next frame and the backward cells of every pair it reads
+    // as a grid into a previous one, each set refined by one k_subpel_refine launch into the context's quarter-pel buffer (the
+    // packed forward grids of every pair, then the backward ones); then the arguments' grids are those, addressed as tf_own_fill
+    // addresses the integer ones.
+    static int prepare(bbme_ctx *c, TfSpArgs &a, int pair0, int pairs, int first, int count, hipStream_t stream, const char *what)
+    {
+        const Level &L = c->lv[0];
+        const int cw = L.width / 2, last = first + count - 1;
+        const long long cells = (long long)cw * (L.height / 2);
+        const size_t s_plane = L.plane_stride;
+        if (int rc = c->tfs_q4.ensure(2 * (size_t)cells * c->batch, "the quarter-pel cells of the temporal filter", Fill::poison)) return rc;
+        mv_t *q4[2] = {c->tfs_q4.get(), c->tfs_q4 + (size_t)c->batch * cells};
+        // chain: slot s reads forward pair s (s < batch) and backward pair s - 1 (s > 0); pair or batch: image 1 forward, image 2 backward
+        const int p0[2] = {c->chain ? first : pair0, c->chain ? std::max(first, 1) - 1 : pair0};
+        const int n[2] = {c->chain ? std::min(last, c->batch - 1) - p0[0] + 1 : (first == 0 ? pairs : 0),
+                          c->chain ? last - 1 - p0[1] + 1 : (last >= 1 ? pairs : 0)};
+        for (int which = 0; which < 2; ++which) {
+            if (n[which] < 1) continue;
+            const uint8_t *i1, *i2;
+            const mv_t *grid;
+            uint32_t s_grid;
+            if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+            if (int rc = enqueue_sp(c, i1 + p0[which] * s_plane, i2 + p0[which] * s_plane, s_plane, grid + (size_t)p0[which] * s_grid, s_grid,
+                                    n[which], nullptr, q4[which] + (size_t)p0[which] * cells, cw, (size_t)cells, nullptr, nullptr, stream))
+                return rc;
+        }
+        const uintptr_t f = reinterpret_cast<uintptr_t>(q4[0]), b = reinterpret_cast<uintptr_t>(q4[1]);
+        const long long prev_pair = c->chain ? first - 1 : pair0, next_pair = c->chain ? first : pair0;
+        a.gp = reinterpret_cast<const mv_t *>(b + prev_pair * cells * (long long)sizeof(mv_t));
+        a.gn = reinterpret_cast<const mv_t *>(f + next_pair * cells * (long long)sizeof(mv_t));
+        a.gp_y = a.gn_y = c->chain ? 0 : cells;
+        a.gp_z = a.gn_z = c->chain ? cells : 0;
+        return BBME_OK;
+    }
+};
+
+int bbme_cells_subpel_temporal_filter_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                             const int16_t *d_q_to_prev, const int16_t *d_q_to_next, int q4_pitch_cells, int thr,
+                                             const int *window, uint8_t *d_out, int out_pitch, uint8_t *d_weights, int weights_pitch,
+                                             unsigned long long *d_stats4, void *hip_stream)
+{
+    return tf_cells<TfSubpel>(c, "bbme_cells_subpel_temporal_filter_device", d_prev, d_cur, d_next, c ? c->lv[0].width : 0, d_q_to_prev,
+                              d_q_to_next, thr, window, d_out, out_pitch, d_weights, weights_pitch, d_stats4, hip_stream, q4_pitch_cells);
+}
+
+int bbme_subpel_temporal_filter_device(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    return tf_device<TfSubpel>(c, "bbme_subpel_temporal_filter_device", pair, which, thr, d_out, out_pitch, hip_stream);
+}
+
+int bbme_subpel_temporal_filter_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
+                                             void *hip_stream)
+{
+    return tf_chain<TfSubpel>(c, "bbme_subpel_temporal_filter_chain_device", first, count, thr, d_out, out_pitch, out_stride, hip_stream);
+}
+
+int bbme_get_subpel_temporal_filtered_host(bbme_ctx *c, int pair, int which, int thr, uint8_t *out)
+{
+    return tf_host<TfSubpel>(c, "bbme_get_subpel_temporal_filtered_host", pair, which, thr, out);
+}
+
+int bbme_subpel_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
+{
+    return tf_stats<TfSubpel>(c, "bbme_subpel_temporal_filter_stats", thr, window, stats);
 }
 
 extern "C" {

@@ -1088,6 +1088,63 @@ int bbme_subpel_interpolate_host(const uint8_t *image1, const uint8_t *image2, i
     return BBME_OK;
 }
 
+// The SUBPEL TEMPORAL FILTER RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of
+// k_subpel_temporal_filter).  A tap of weight 0 is not read: it may lie outside the plane.
+int bbme_subpel_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height,
+                                     const int16_t *q_to_prev, const int16_t *q_to_next, int thr, const int *window, uint8_t *out,
+                                     uint8_t *weights, unsigned long long *stats4)
+{
+    const char *what = "bbme_subpel_temporal_filter_host";
+    if (!cur || (!out && !weights && !stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if ((prev == nullptr) != (q_to_prev == nullptr) || (next == nullptr) != (q_to_next == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its plane and its grid", what);
+    if (!prev && !next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    const int cw = width / 2, ch = height / 2;
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cw, ch, what, "cells")) return rc;
+    const uint8_t *frames[2] = {prev, next};
+    const int16_t *grids[2] = {q_to_prev, q_to_next};
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            int w[2] = {0, 0}, x[2][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}};           // the weights; the rounded samples X'[j, k] at [2 k + j]
+            for (int n = 0; n < 2; ++n) {
+                if (!frames[n]) continue;
+                const int qx = grids[n][2 * c], qy = grids[n][2 * c + 1];
+                const int fx = qx & 3, fy = qy & 3, sx = ox + (qx >> 2), sy = oy + (qy >> 2);
+                if (sx < 0 || sx + 2 + (fx != 0) > width || sy < 0 || sy + 2 + (fy != 0) > height) continue;
+                int cost = 0;
+                for (int k = 0; k < 2; ++k)
+                    for (int j = 0; j < 2; ++j) {
+                        const auto tap = [&](int weight, int dx, int dy) {
+                            return weight ? weight * frames[n][(size_t)(sy + k + dy) * width + sx + j + dx] : 0;
+                        };
+                        x[n][2 * k + j] = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+                        cost += abs((int)cur[(size_t)(oy + k) * width + ox + j] - x[n][2 * k + j]);
+                    }
+                if (cost < thr) w[n] = 8 * (thr - cost) / thr;
+            }
+            const int S = 8 + w[0] + w[1];
+            unsigned diff = 0;
+            for (int k = 0; k < 2; ++k)
+                for (int j = 0; j < 2; ++j) {
+                    const size_t at = (size_t)(oy + k) * width + ox + j;
+                    const int v = (8 * cur[at] + w[0] * x[0][2 * k + j] + w[1] * x[1][2 * k + j] + S / 2) / S;
+                    if (out) out[at] = (uint8_t)v;
+                    diff += (unsigned)abs(v - (int)cur[at]);
+                }
+            if (weights) weights[c] = (uint8_t)(w[0] | w[1] << 4);
+            if (win.contains(cx, cy)) { s[0] += w[0] > 0; s[1] += w[1] > 0; s[2] += (unsigned)(w[0] + w[1]); s[3] += diff; }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 // The BGR SUBPEL INTERPOLATION RULE of include/bbme.h: the selection of bbme_subpel_interpolate_host on the luma planes (its map
 // tells which hypothesis; P1 and P2 follow from it), then every pixel of the two colour frames sampled bilinearly at P1 and P2 and
 // blended (the mirror of k_subpel_interpolate_bgr).  A tap of weight 0 or outside the frame is not read.

@@ -3178,7 +3178,8 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
-// k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate and K12b k_subpel_interpolate_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate, K12b k_subpel_interpolate_bgr and K13
+// k_subpel_temporal_filter.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window.
 // =======================================================================================
@@ -4696,6 +4697,131 @@ __global__ __launch_bounds__(256) void k_subpel_interpolate_bgr(SiBgrArgs a)
             }
         }
     }
+}
+
+// =======================================================================================
+// K13.  Motion-compensated temporal filter along QUARTER-PEL grids (the SUBPEL TEMPORAL FILTER RULE of include/bbme.h): K9 with
+// each neighbour's cell taken as K11 and K12 take theirs.  Output cell (cx, cy) with origin o reads, for each present neighbour X
+// with grid Q on C, (qx, qy) = Q[cy][cx], s = o + (qx >> 2, qy >> 2), f = (qx & 3, qy & 3); the neighbour is valid when every tap of
+// non-zero weight lies in the plane, its cell is the SUBPEL RULE's four rounded bilinear samples (si_cell: the separable form over
+// sc_row, whose third row and third column fold onto the second where the fraction is 0, so that a tap of weight 0 is never
+// addressed), packed into one dword so that v_sad_u8 against C's cell gives the cost, and the weight, the blend, the map and the
+// statistics are K9's from there on.
+// Layout is K9's: the shared split of runs of 4 cells (gather_index / gather_split), QP and QN by load_mv4 (rows q4_pitch cells
+// apart), C as one 8-byte load per plane row, blockIdx.y = batch pair, blockIdx.z = the frame of a run, the five inputs addressed
+// base + y s_y + z s_z with the first / last neighbour flags, the two pixel rows stored as two dwords each (bytes where a caller's
+// row is not dword-aligned or the run is cut), the weight bytes by store_bytes4.
+// Both divisions are K9's multiply-shifts with K9's magics and bounds: the cost of four rounded samples is still <= 1020 and the
+// blend's numerator still <= 255 * 24 + 12, the samples being bytes.
+// Statistics: K9's four counters in 32 bits per lane (at most 4 RPL cells of at most 1020 each), through shuffles to one partial
+// per workgroup (store_partial4, frame = y gridDim.z + z), then k_mc_reduce: no atomics.
+// A template, as K12b: a template's code lies behind the estimate's template kernels in the code object, a plain kernel's before.
+// =======================================================================================
+struct TfSpArgs : TfArgs {                // gp / gn: quarter-pel vectors
+    int q4_pitch;                         // cells from row to row of both grids
+};
+
+// One neighbour of the cell c with origin (ox, oy): its weight, and its cell of rounded samples in *q when the weight is not 0
+__device__ __forceinline__ uint32_t stf_weight(const uint8_t *X, int W, int H, int ox, int oy, mv_t g, uint32_t c, uint32_t thr,
+                                               uint32_t magic_thr, uint32_t *q)
+{
+    const int qx = mv_x(g), qy = mv_y(g);
+    const int fx = qx & 3, fy = qy & 3;
+    const int sx = ox + (qx >> 2), sy = oy + (qy >> 2);
+    *q = 0;
+    if (sx < 0 || sy < 0 || sx + 2 + (fx != 0) > W || sy + 2 + (fy != 0) > H) return 0u;
+    const uint32_t x = si_cell(X, W, sx, sy, fx, fy);
+    const uint32_t cost = __builtin_amdgcn_sad_u8(c, x, 0u);
+    if (cost >= thr) return 0u;
+    *q = x;
+    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
+}
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_subpel_temporal_filter(TfSpArgs a)
+{
+    __shared__ uint32_t magic_s[17];
+    if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
+    __syncthreads();
+    const long long y = blockIdx.y, z = blockIdx.z;
+    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
+    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
+    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
+    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
+    const mv_t *QP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *QN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    const int W = a.width, H = a.height, CW = a.cw;
+    const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
+    uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        const int oy = 2 * cy;
+        const size_t g0 = (size_t)cy * a.q4_pitch + x0, o0 = (size_t)oy * W + 2 * x0;
+        uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
+        if (has_p) load_mv4(QP + g0, n, gp);
+        if (has_n) load_mv4(QN + g0, n, gn);
+        if (n == 4) {
+            const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(C + o0), u = *reinterpret_cast<const ua_u32x2 *>(C + o0 + W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int sh = 16 * (j & 1);
+                c[j] = ((t.v[j >> 1] >> sh) & 0xffffu) | ((u.v[j >> 1] >> sh) << 16);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= n) continue;
+                c[j] = ip_cell(C, W, 2 * (x0 + j), oy);
+            }
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ws = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox = 2 * (x0 + j);
+            uint32_t qp = 0, qn = 0;
+            const uint32_t wp = has_p ? stf_weight(P, W, H, ox, oy, gp[j], c[j], thr, magic_thr, &qp) : 0u;
+            const uint32_t wn = has_n ? stf_weight(N, W, H, ox, oy, gn[j], c[j], thr, magic_thr, &qn) : 0u;
+            const uint32_t S = 8u + wp + wn, m = magic_s[wp + wn], half = S >> 1;
+            uint32_t px = 0;
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const uint32_t v = __umulhi(8u * ((c[j] >> (8 * q)) & 0xffu) + wp * ((qp >> (8 * q)) & 0xffu) +
+                                            wn * ((qn >> (8 * q)) & 0xffu) + half, m);
+                px |= v << (8 * q);
+            }
+            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
+            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            ws |= (wp | wn << 4) << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                np += wp != 0u; nn += wn != 0u;
+                wsum += wp + wn;
+                dsum += __builtin_amdgcn_sad_u8(px, c[j], 0u);
+            }
+        }
+        if (a.out) {
+            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                const uint32_t *row = yy ? row1 : row0;
+                uint8_t *q = o + (size_t)yy * a.out_pitch;
+                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
+                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
+                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
+                } else {
+                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+                }
+            }
+        }
+        if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
 }
 
 }  // namespace bbme

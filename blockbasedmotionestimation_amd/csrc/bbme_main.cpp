@@ -3,7 +3,7 @@
 //   bbme_cli frame10.pgm|.ppm frame11.pgm|.ppm [--gt flow10.flo] [--out flow.flo] [--color flow.ppm] [--levels N]
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
 //            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T] [--subpel sub.flo]
-//            [--mc-subpel mcq.pgm] [--interpolate-subpel PREFIX --factor N]
+//            [--mc-subpel mcq.pgm] [--interpolate-subpel PREFIX --factor N] [--denoise-subpel PREFIX --strength T]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -33,6 +33,10 @@
 // interpolation rule of include/bbme.h: both fields refined to quarter-pel, every cell placed and sampled at its quarter-pel
 // position of the phase), as PREFIX_k.pgm, the same unpadded crop; on colour frames the frames of their luma and, with
 // --no-upsample (which keeps the colour), additionally PREFIX_k.ppm, colour frames by the BGR subpel interpolation rule.
+// --denoise-subpel PREFIX --strength T writes --denoise's grey frames made along quarter-pel vectors instead (the subpel temporal
+// filter rule of include/bbme.h: the field into the other frame refined to quarter-pel, its 2x2 cells sampled bilinearly), as
+// PREFIX_1.pgm and PREFIX_2.pgm, the unpadded frames MF sees: with --no-upsample the frames read (on colour frames their luma),
+// without it their 4x planes.  It writes no colour frames: the BGR temporal filter rule is integer.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -84,7 +88,7 @@ int main(int argc, char **argv)
 {
     const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
                *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr, *mc_subpel = nullptr,
-               *interpolate_subpel = nullptr;
+               *interpolate_subpel = nullptr, *denoise_subpel = nullptr;
     int factor = 2, strength = 64;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
@@ -102,6 +106,7 @@ int main(int argc, char **argv)
         else if (a == "--interpolate-subpel") interpolate_subpel = next();
         else if (a == "--backward-color") backward_color = next();
         else if (a == "--denoise") denoise = next();
+        else if (a == "--denoise-subpel") denoise_subpel = next();
         else if (a == "--subpel") subpel = next();
         else if (a == "--strength") strength = atoi(next());
         else if (a == "--factor") factor = atoi(next());
@@ -115,12 +120,12 @@ int main(int argc, char **argv)
         else { fprintf(stderr, "unexpected argument %s\n", argv[i]); return 2; }
     }
     if (!f1 || !f2 || levels < 1 || levels > BBME_MAX_LEVELS || ((interpolate || interpolate_subpel) && (factor < 2 || factor > 256)) ||
-        (denoise && (strength < 1 || strength > 1021))) {
+        ((denoise || denoise_subpel) && (strength < 1 || strength > 1021))) {
         fprintf(stderr, "usage: bbme_cli frame1.pgm|.ppm frame2.pgm|.ppm [--gt gt.flo] [--out flow.flo] [--color flow.ppm] "
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
                         "[--denoise PREFIX --strength T] [--subpel sub.flo] [--mc-subpel mcq.pgm] "
-                        "[--interpolate-subpel PREFIX --factor N]\n"
+                        "[--interpolate-subpel PREFIX --factor N] [--denoise-subpel PREFIX --strength T]\n"
                         "--denoise writes PREFIX_1.pgm and PREFIX_2.pgm (on .ppm frames their luma) and, on .ppm frames, the "
                         "filtered colour frames PREFIX_1.ppm and PREFIX_2.ppm; it needs --no-upsample\n");
         return 2;
@@ -254,6 +259,16 @@ int main(int argc, char **argv)
                     const std::string ppm = std::string(denoise) + "_" + std::to_string(which + 1) + ".ppm";
                     bbme::check(bbme_ppm_write_bgr(ppm.c_str(), bgr.cols, bgr.rows, bgr.data.data()));
                 }
+            }
+        }
+        if (denoise_subpel) {
+            motion_pair.estimateBidirectional();
+            const int px = motion_pair.padding_x, py = motion_pair.padding_y;
+            for (int which = 0; which < 2; ++which) {
+                const bbme::Image8 img = motion_pair.temporalFilterSubpel(strength, which);
+                const std::string name = std::string(denoise_subpel) + "_" + std::to_string(which + 1) + ".pgm";
+                bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
+                                           img.data.data() + (size_t)py * img.cols + px));
             }
         }
         if (backward_color) {

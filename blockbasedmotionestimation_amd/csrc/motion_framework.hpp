@@ -315,6 +315,14 @@ public:
         bbme::check(bbme_get_temporal_filtered_host(ctx_, 0, which, strength, img.data.data()));
         return img;
     }
+    // temporalFilter() along quarter-pel vectors (the subpel temporal filter rule of include/bbme.h): the cells the frame's
+    // neighbour hangs on are refined and its 2x2 cells sampled bilinearly: the padded plane.
+    bbme::Image8 temporalFilterSubpel(int strength, int which = 0)
+    {
+        bbme::Image8 img(padded_height, padded_width);
+        bbme::check(bbme_get_subpel_temporal_filtered_host(ctx_, 0, which, strength, img.data.data()));
+        return img;
+    }
     // The same frame in colour (the BGR interpolation rule of include/bbme.h), for an MF made of colour frames: the UNPADDED frame.
     bbme::ImageBGR interpolateBGR(int num = 1, int den = 2)
     {

@@ -736,9 +736,10 @@ int bbme_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, un
  * q != (0, 0), the sum of cost(0, 0) over the valid cells and the sum of best over the valid cells.  The statistics do not need
  * the grid to be written.
  * A context made for up-sampled frames (bbme_set_frames_*_x4) refines its 4x planes: the result is then 1/16 pel of the source.
- * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE, the SUBPEL INTERPOLATION RULE and the BGR SUBPEL
- * INTERPOLATION RULE below read quarter-pel vectors; the other rules that take a cell grid (integer compensation, the INTERPOLATION
- * RULE and the BGR INTERPOLATION RULE, the temporal filters) do not: they are integer.
+ * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE, the SUBPEL INTERPOLATION RULE, the BGR SUBPEL
+ * INTERPOLATION RULE and the SUBPEL TEMPORAL FILTER RULE below read quarter-pel vectors; the other rules that take a cell grid
+ * (integer compensation, the INTERPOLATION RULE and the BGR INTERPOLATION RULE, the TEMPORAL FILTER RULE and the BGR TEMPORAL
+ * FILTER RULE) do not: they are integer.
  * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, q4_pitch_cells < CW, a
  * window as for the consistency rule, a d_q4 of bbme_cells_subpel_device that overlaps its input grid, an odd width or height on
  * the host call; BBME_ERR_UNSUPPORTED beyond 8188; BBME_ERR_STATE when frames are unset or a chain slot is unset, for which = 0
@@ -943,6 +944,61 @@ int bbme_cells_subpel_interpolate_bgr_device(bbme_ctx *ctx, int pair, const int1
 int bbme_subpel_interpolate_bgr_device(bbme_ctx *ctx, int pair, int num0, int count, int den, uint8_t *d_out, int out_pitch,
                                        size_t out_stride, void *hip_stream);
 int bbme_get_subpel_interpolated_bgr_host(bbme_ctx *ctx, int pair, int num, int den, uint8_t *out);
+
+/* SUBPEL TEMPORAL FILTER RULE (this project's own): the TEMPORAL FILTER RULE with each neighbour's cell taken at a QUARTER-PEL
+ * position, as in the SUBPEL COMPENSATION RULE.  Inputs: those of the TEMPORAL FILTER RULE -- the plane C, optionally P and / or N
+ * (packed W0 x H0 bytes), a strength thr, 1 <= thr <= 1021 -- except that the two grids QP (on C, into P) and QN (on C, into N) hold
+ * quarter-pel vectors, CH x CW int16 (qx, qy) pairs as bbme_subpel_* writes them; any int16 is allowed.  All arithmetic is in 32-bit
+ * integers, `>>` of a negative number is the arithmetic shift, every division the floor division of non-negative numbers.
+ * For output cell (cx, cy) with origin o = (2 cx, 2 cy) and each present neighbour X with grid Q:
+ *   (qx, qy) = Q[cy][cx], i = (qx >> 2, qy >> 2), f = (qx & 3, qy & 3), s = o + i;
+ *   the neighbour is valid when 0 <= s.x, s.x + 2 + (fx != 0) <= W0, 0 <= s.y and s.y + 2 + (fy != 0) <= H0: every tap of non-zero
+ *   weight lies in the plane.  A tap of weight 0 is not read; no byte outside W0 x H0 is read;
+ *   X'[j, k] = sample(s + (j, k), f) for 0 <= j, k < 2, the SUBPEL RULE's sample with its single rounding, (... + 8) >> 4;
+ *   cost = sum over the four ROUNDED samples of |C[o + (j, k)] - X'[j, k]|, 0..1020;
+ *   w = 8 (thr - cost) / thr if the neighbour is valid and cost < thr, else 0.
+ * With S = 8 + wP + wN (8..24),
+ *   out[o + (j, k)] = (8 C[o + (j, k)] + wP P'[j, k] + wN N'[j, k] + S / 2) / S.
+ * The weight map (wP | wN << 4, one byte per cell) and the four statistics over a window in cells (cells with wP > 0, cells with
+ * wN > 0, the sum of wP + wN, the sum of |out - C|) are the TEMPORAL FILTER RULE's.
+ * Properties.  (1) With QP = 4 GP and QN = 4 GN for integer grids the frame, the map and the statistics are the TEMPORAL FILTER
+ * RULE's on GP and GN, bit for bit (the validity test reduces to 0 <= p <= W0 - 2 / H0 - 2).  (2) With equal planes and zero grids
+ * the frame is unchanged and every present weight is 8.  (3) The grid call has no size limit of its own: s is computed in 32 bits
+ * from any int16.
+ * On a context with its own fields the grid into the previous frame is the BACKWARD cells of the pair the frame is image 2 of and
+ * the grid into the next frame the FORWARD cells of the pair it is image 1 of, each refined by the SUBPEL RULE (K10) into
+ * quarter-pel buffers of the context's own, allocated at first use.  A context made for up-sampled frames filters its 4x planes; a
+ * colour context its luma planes.  The BGR TEMPORAL FILTER RULE stays integer.
+ * Errors: those of the TEMPORAL FILTER RULE's calls, plus BBME_ERR_INVALID for q4_pitch_cells < CW and BBME_ERR_UNSUPPORTED beyond
+ * W0 or H0 8188 for the four context-level calls (as bbme_subpel_device); BBME_ERR_STATE for those without a valid pair of
+ * fields; BBME_ERR_UNSUPPORTED for bbme_subpel_temporal_filter_chain_device off a chain.  None of these calls changes context
+ * state (grids, memo, flow, cells, backward cells, captured graphs, colour store); the statistics scratch and the quarter-pel
+ * buffers are their own.  The caller orders context-level calls that it issues on different streams.
+ * bbme_subpel_temporal_filter_host: the rule on the CPU, no GPU, on packed width x height planes (both even) and packed
+ * (height / 2) x (width / 2) quarter-pel grids; out, weights (packed) and stats4 each may be NULL, not all three.
+ * bbme_cells_subpel_temporal_filter_device: ANY three packed planes and ANY two quarter-pel grids in HBM of the context's level-0 /
+ * cell geometry, rows of both grids q4_pitch_cells int16 pairs apart (bbme_subpel_device's output goes straight in); otherwise as
+ * bbme_cells_temporal_filter_device; no host wait.
+ * bbme_subpel_temporal_filter_device: frame `which` of `pair` with the neighbours bbme_temporal_filter_device gives it: the
+ * integer grids it needs refined (one K10 launch each), then one filter launch.
+ * bbme_subpel_temporal_filter_chain_device: chain contexts only; at most two refinement launches (the forward cells of all pairs
+ * the run needs, the backward cells of all pairs it needs), then ONE filter launch for slots first .. first + count - 1, frame q
+ * at d_out + q out_stride.
+ * bbme_get_subpel_temporal_filtered_host: one frame as bbme_subpel_temporal_filter_device; synchronises; packed W0 x H0 bytes.
+ * bbme_subpel_temporal_filter_stats: EVERY frame of the context from one filter launch; synchronises; laid out as
+ * bbme_temporal_filter_stats. */
+int bbme_subpel_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height,
+                                     const int16_t *q_to_prev, const int16_t *q_to_next, int thr, const int *window, uint8_t *out,
+                                     uint8_t *weights, unsigned long long *stats4);
+int bbme_cells_subpel_temporal_filter_device(bbme_ctx *ctx, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                             const int16_t *d_q_to_prev, const int16_t *d_q_to_next, int q4_pitch_cells, int thr,
+                                             const int *window, uint8_t *d_out, int out_pitch, uint8_t *d_weights, int weights_pitch,
+                                             unsigned long long *d_stats4, void *hip_stream);
+int bbme_subpel_temporal_filter_device(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream);
+int bbme_subpel_temporal_filter_chain_device(bbme_ctx *ctx, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                             size_t out_stride, void *hip_stream);
+int bbme_get_subpel_temporal_filtered_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
+int bbme_subpel_temporal_filter_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
