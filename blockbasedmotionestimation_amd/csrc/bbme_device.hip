@@ -347,11 +347,14 @@ struct bbme_ctx {
                                                   // (enqueue_own_si)
     StatsScratch si_stats;                        // bbme_subpel_interpolation_stats (every pair) and
                                                   // bbme_cells_subpel_interpolate_device (one pair, `count` phases)
-    DevBuf<mv_t> tfs_q4;                          // the quarter-pel cells the context's own sub-pel temporal filter reads: the packed
-                                                  // forward grids of every pair, then their backward grids, allocated at first use
+    DevBuf<mv_t> tfs_q4;                          // the quarter-pel cells the context's own sub-pel temporal filters read, grey and
+                                                  // colour (both refine the same cells on the same luma planes): the packed forward
+                                                  // grids of every pair, then their backward grids, allocated at first use
                                                   // (TfSubpel::prepare)
     StatsScratch tfs_stats;                       // bbme_subpel_temporal_filter_stats (every frame) and
                                                   // bbme_cells_subpel_temporal_filter_device (one)
+    StatsScratch tfsb_stats;                      // bbme_subpel_temporal_filter_bgr_stats (every frame) and
+                                                  // bbme_cells_subpel_temporal_filter_bgr_device (one)
 };
 
 namespace {
@@ -2499,7 +2502,8 @@ int bbme_get_interpolated_bgr_host(bbme_ctx *c, int pair, int num, int den, uint
 
 // ---- motion-compensated temporal filter of a frame with its neighbours (the temporal filter rules of include/bbme.h) --------------
 // Written once over a flavour: TfGrey filters the level-0 planes (k_temporal_filter), TfBgr the B,G,R frames (k_temporal_filter_bgr),
-// TfSubpel (further down, behind the refinement it needs) the level-0 planes along quarter-pel grids (k_subpel_temporal_filter).
+// TfSubpel (further down, behind the refinement it needs) the level-0 planes along quarter-pel grids (k_subpel_temporal_filter),
+// TfSubpelBgr (beside it) the B,G,R frames along quarter-pel grids (k_subpel_temporal_filter_bgr).
 
 constexpr int kTfMaxFrames = 2 * BBME_MAX_BATCH;          // a batch holds 2 batch frames, a chain batch + 1
 
@@ -3407,7 +3411,8 @@ struct TfSubpel : TfGrey {
     // as a grid into a previous one, each set refined by one k_subpel_refine launch into the context's quarter-pel buffer (the
     // packed forward grids of every pair, then the backward ones); then the arguments' grids are those, addressed as tf_own_fill
     // addresses the integer ones.
-    static int prepare(bbme_ctx *c, TfSpArgs &a, int pair0, int pairs, int first, int count, hipStream_t stream, const char *what)
+    template <class Args>
+    static int prepare(bbme_ctx *c, Args &a, int pair0, int pairs, int first, int count, hipStream_t stream, const char *what)
     {
         const Level &L = c->lv[0];
         const int cw = L.width / 2, last = first + count - 1;
@@ -3467,6 +3472,55 @@ int bbme_get_subpel_temporal_filtered_host(bbme_ctx *c, int pair, int which, int
 int bbme_subpel_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
 {
     return tf_stats<TfSubpel>(c, "bbme_subpel_temporal_filter_stats", thr, window, stats);
+}
+
+// ---- the same on the B,G,R frames (the BGR SUBPEL TEMPORAL FILTER RULE of include/bbme.h; K13b k_subpel_temporal_filter_bgr) ----
+// The fourth flavour: the colour flavour's frames, colour checks and output checks, the quarter-pel flavour's refusals and
+// refinement.  The cells are refined on the LUMA planes, into the quarter-pel buffer the grey flavour uses (the same cells of the
+// same planes give the same vectors); the filter launch then reads only colour.
+struct TfSubpelBgr : TfBgr {
+    using Args = TfSpBgrArgs;
+    static constexpr bool subpel = true;
+    static constexpr const char *staging_what = "the quarter-pel filtered colour frame",
+                                *stats_what = "the colour subpel temporal filter statistics";
+    static auto kernel() { return k_subpel_temporal_filter_bgr<kTfRunsPerLane>; }
+    static StatsScratch &stats(bbme_ctx *c) { return c->tfsb_stats; }
+    static void geometry(const bbme_ctx *c, TfSpBgrArgs &a) { TfBgr::geometry(c, a); a.q4_pitch = c->lv[0].width / 2; }
+    static int check_own(const bbme_ctx *c, const char *what) { return check_sp(c, nullptr, what); }
+    static int prepare(bbme_ctx *c, TfSpBgrArgs &a, int pair0, int pairs, int first, int count, hipStream_t stream, const char *what)
+    {
+        return TfSubpel::prepare(c, a, pair0, pairs, first, count, stream, what);
+    }
+};
+
+int bbme_cells_subpel_temporal_filter_bgr_device(bbme_ctx *c, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                                 int bgr_pitch, const int16_t *d_q_to_prev, const int16_t *d_q_to_next, int q4_pitch_cells,
+                                                 int thr, const int *window, uint8_t *d_out, int out_pitch, uint8_t *d_weights,
+                                                 int weights_pitch, unsigned long long *d_stats4, void *hip_stream)
+{
+    return tf_cells<TfSubpelBgr>(c, "bbme_cells_subpel_temporal_filter_bgr_device", d_prev, d_cur, d_next, bgr_pitch, d_q_to_prev,
+                                 d_q_to_next, thr, window, d_out, out_pitch, d_weights, weights_pitch, d_stats4, hip_stream, q4_pitch_cells);
+}
+
+int bbme_subpel_temporal_filter_bgr_device(bbme_ctx *c, int pair, int which, int thr, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    return tf_device<TfSubpelBgr>(c, "bbme_subpel_temporal_filter_bgr_device", pair, which, thr, d_out, out_pitch, hip_stream);
+}
+
+int bbme_subpel_temporal_filter_bgr_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                                 size_t out_stride, void *hip_stream)
+{
+    return tf_chain<TfSubpelBgr>(c, "bbme_subpel_temporal_filter_bgr_chain_device", first, count, thr, d_out, out_pitch, out_stride, hip_stream);
+}
+
+int bbme_get_subpel_temporal_filtered_bgr_host(bbme_ctx *c, int pair, int which, int thr, uint8_t *out)
+{
+    return tf_host<TfSubpelBgr>(c, "bbme_get_subpel_temporal_filtered_bgr_host", pair, which, thr, out);
+}
+
+int bbme_subpel_temporal_filter_bgr_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
+{
+    return tf_stats<TfSubpelBgr>(c, "bbme_subpel_temporal_filter_bgr_stats", thr, window, stats);
 }
 
 extern "C" {

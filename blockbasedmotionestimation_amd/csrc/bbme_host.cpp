@@ -1145,6 +1145,79 @@ int bbme_subpel_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, co
     return BBME_OK;
 }
 
+// The BGR SUBPEL TEMPORAL FILTER RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of
+// k_subpel_temporal_filter_bgr).  A tap of weight 0 or outside the frame is not read.
+int bbme_subpel_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height, int pad_x,
+                                         int pad_y, const int16_t *q_to_prev, const int16_t *q_to_next, int thr, const int *window,
+                                         uint8_t *out, uint8_t *weights, unsigned long long *stats4)
+{
+    const char *what = "bbme_subpel_temporal_filter_bgr_host";
+    if (!cur || (!out && !weights && !stats4)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if ((prev == nullptr) != (q_to_prev == nullptr) || (next == nullptr) != (q_to_next == nullptr))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its frame and its grid", what);
+    if (!prev && !next) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (width < 1 || height < 1 || pad_x < 0 || pad_y < 0 || (long long)width + 2LL * pad_x > INT32_MAX ||
+        (long long)height + 2LL * pad_y > INT32_MAX)
+        return bbme::fail(BBME_ERR_INVALID, "%s: bad frame %dx%d with padding (%d, %d)", what, width, height, pad_x, pad_y);
+    const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y;
+    if ((W0 & 1) || (H0 & 1)) return bbme::fail(BBME_ERR_INVALID, "%s: the padded view %dx%d is not a plane of 2x2 cells", what, W0, H0);
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    const int cw = W0 / 2, ch = H0 / 2;
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cw, ch, what, "cells")) return rc;
+    const uint8_t *frames[2] = {prev, next};
+    const int16_t *grids[2] = {q_to_prev, q_to_next};
+    // channel k of the pixel at the padded position (X, Y) of a frame: 0 outside the frame
+    const auto at = [&](const uint8_t *img, int X, int Y, int k) {
+        const int x = X - pad_x, y = Y - pad_y;
+        return x < 0 || y < 0 || x >= width || y >= height ? 0 : (int)img[((size_t)y * width + x) * 3 + k];
+    };
+    unsigned long long s[4] = {0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            int w[2] = {0, 0}, x[2][4][3] = {};                // the weights; channel k of the rounded sample X'[j, i] at [2 i + j][k]
+            for (int n = 0; n < 2; ++n) {
+                if (!frames[n]) continue;
+                const int qx = grids[n][2 * c], qy = grids[n][2 * c + 1];
+                const int fx = qx & 3, fy = qy & 3, sx = ox + (qx >> 2), sy = oy + (qy >> 2);
+                if (sx < 0 || sx + 2 + (fx != 0) > W0 || sy < 0 || sy + 2 + (fy != 0) > H0) continue;
+                int cost = 0;
+                for (int k = 0; k < 3; ++k) {
+                    int cost_k = 0;
+                    for (int i = 0; i < 2; ++i)
+                        for (int j = 0; j < 2; ++j) {
+                            const auto tap = [&](int weight, int dx, int dy) {
+                                return weight ? weight * at(frames[n], sx + j + dx, sy + i + dy, k) : 0;
+                            };
+                            x[n][2 * i + j][k] = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+                            cost_k += abs(at(cur, ox + j, oy + i, k) - x[n][2 * i + j][k]);
+                        }
+                    cost = std::max(cost, cost_k);
+                }
+                if (cost < thr) w[n] = 8 * (thr - cost) / thr;
+            }
+            const int S = 8 + w[0] + w[1];
+            unsigned diff = 0;
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j) {
+                    const int fxp = ox + j - pad_x, fyp = oy + i - pad_y;
+                    const bool inside = fxp >= 0 && fyp >= 0 && fxp < width && fyp < height;
+                    for (int k = 0; k < 3; ++k) {
+                        const int cv = at(cur, ox + j, oy + i, k);
+                        const int v = (8 * cv + w[0] * x[0][2 * i + j][k] + w[1] * x[1][2 * i + j][k] + S / 2) / S;
+                        if (out && inside) out[((size_t)fyp * width + fxp) * 3 + k] = (uint8_t)v;
+                        diff += (unsigned)abs(v - cv);
+                    }
+                }
+            if (weights) weights[c] = (uint8_t)(w[0] | w[1] << 4);
+            if (win.contains(cx, cy)) { s[0] += w[0] > 0; s[1] += w[1] > 0; s[2] += (unsigned)(w[0] + w[1]); s[3] += diff; }
+        }
+    if (stats4) memcpy(stats4, s, sizeof s);
+    return BBME_OK;
+}
+
 // The BGR SUBPEL INTERPOLATION RULE of include/bbme.h: the selection of bbme_subpel_interpolate_host on the luma planes (its map
 // tells which hypothesis; P1 and P2 follow from it), then every pixel of the two colour frames sampled bilinearly at P1 and P2 and
 // blended (the mirror of k_subpel_interpolate_bgr).  A tap of weight 0 or outside the frame is not read.

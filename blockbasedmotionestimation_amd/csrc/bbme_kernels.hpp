@@ -3178,8 +3178,8 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
-// k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate, K12b k_subpel_interpolate_bgr and K13
-// k_subpel_temporal_filter.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate, K12b k_subpel_interpolate_bgr, K13
+// k_subpel_temporal_filter and K13b k_subpel_temporal_filter_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window.
 // =======================================================================================
@@ -4814,6 +4814,163 @@ __global__ __launch_bounds__(256) void k_subpel_temporal_filter(TfSpArgs a)
                     reinterpret_cast<uint32_t *>(q)[1] = row[1];
                 } else {
                     for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+                }
+            }
+        }
+        if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
+}
+
+// =======================================================================================
+// K13b.  The BGR SUBPEL TEMPORAL FILTER RULE of include/bbme.h: K9b with each neighbour's cell taken at a QUARTER-PEL position of
+// the zero-padded view of the colour frames, as K13 takes it on a plane.  Output cell (cx, cy) with origin o reads, for each present
+// neighbour X with grid Q on C, (qx, qy) = Q[cy][cx], s = o + (qx >> 2, qy >> 2), f = (qx & 3, qy & 3); the neighbour is valid when
+// every tap of non-zero weight lies in the padded view (K13's test); its cell is the four rounded bilinear samples of each channel
+// (si_bgr_cell, K12b's: up to three frame rows of nine bytes at an arbitrary byte address, a pixel outside the frame 0, the third
+// row and the third column folded away where the fraction is 0 so that a tap of weight 0 is never addressed), repacked into K9b's
+// layout of a cell row -- the dword B0 G0 R0 B1 and the u16 G1 R1 -- so that bgr_cell_cost gives the largest per-channel SAD on
+// the ROUNDED samples, and the weight, the blend, the output rows, the map and the statistics are K9b's from there on.
+// Layout is K9b's: the shared split of runs of 4 cells, the run's own rows as three unaligned 8-byte loads where the run is whole
+// and inside the frame (bgr_two otherwise), the straddling-edge stores; QP and QN by load_mv4, rows q4_pitch cells apart, as K13
+// reads them; blockIdx.y = batch pair, blockIdx.z = the frame of a run.
+// Both divisions are K9's multiply-shifts with K9's bounds: the samples are bytes, so the cost is still <= 1020 and the blend's
+// numerator still <= 255 * 24 + 12.  Statistics as K9b (at most 3060 a cell), same partial layout: no atomics.
+// A template, as K12b and K13: a template's code lies behind the estimate's template kernels in the code object.
+// =======================================================================================
+struct TfSpBgrArgs : TfBgrArgs {          // gp / gn: quarter-pel vectors
+    int q4_pitch;                         // cells from row to row of both grids
+};
+
+// One neighbour of the cell (c0, c1: its two rows of 6 bytes) with origin (ox, oy) on the padded view: its weight, and its two
+// rows of rounded samples in q[] when the weight is not 0
+__device__ __forceinline__ uint32_t stf_bgr_weight(const uint8_t *X, const TfSpBgrArgs &a, int ox, int oy, mv_t g, uint64_t c0, uint64_t c1,
+                                                   uint32_t thr, uint32_t magic_thr, uint64_t *q)
+{
+    const int qx = mv_x(g), qy = mv_y(g);
+    const int fx = qx & 3, fy = qy & 3;
+    const int sx = ox + (qx >> 2), sy = oy + (qy >> 2);
+    q[0] = q[1] = 0;
+    if (sx < 0 || sy < 0 || sx + 2 + (fx != 0) > a.width || sy + 2 + (fy != 0) > a.height) return 0u;
+    uint32_t e[2][2], gr[2][2];
+    si_bgr_cell(X, a.bgr_pitch, a.fw, a.fh, sx - a.pad_x, sy - a.pad_y, fx, fy, e, gr);
+    uint32_t lo[2], hi[2];                                    // B0 G0 R0 B1; G1 R1
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        lo[r] = (e[r][0] & 0xffu) | gr[r][0] << 8 | (e[r][0] & 0xff0000u) | e[r][1] << 24;
+        hi[r] = gr[r][1] | (e[r][1] >> 16) << 8;
+    }
+    const uint32_t cost = bgr_cell_cost((uint32_t)c0, (uint32_t)c1, (uint32_t)(c0 >> 32) | (uint32_t)(c1 >> 32) << 16,
+                                        lo[0], lo[1], hi[0] | hi[1] << 16);
+    if (cost >= thr) return 0u;
+    q[0] = (uint64_t)lo[0] | (uint64_t)hi[0] << 32; q[1] = (uint64_t)lo[1] | (uint64_t)hi[1] << 32;
+    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
+}
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_subpel_temporal_filter_bgr(TfSpBgrArgs a)
+{
+    __shared__ uint32_t magic_s[17];
+    if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
+    __syncthreads();
+    const long long y = blockIdx.y, z = blockIdx.z;
+    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
+    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
+    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
+    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
+    const mv_t *QP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *QN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    const int CW = a.cw;
+    const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
+    uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        const int oy = 2 * cy;
+        const int fy = oy - a.pad_y, fx = 2 * x0 - a.pad_x;    // the run's first pixel in frame coordinates
+        if (fy + 1 < 0 || fy >= a.fh || fx + 2 * n <= 0 || fx >= a.fw) {      // no pixel of the run is in the frame
+            if (!a.partial && !a.wmap) continue;
+        }
+        const size_t g0 = (size_t)cy * a.q4_pitch + x0;
+        uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0};
+        if (has_p) load_mv4(QP + g0, n, gp);
+        if (has_n) load_mv4(QN + g0, n, gn);
+        const bool whole = n == 4 && fx >= 0 && fx + 8 <= a.fw;      // the run's 8 pixels lie inside a frame row
+        uint64_t crow[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's own two rows, 24 bytes each
+        if (whole) {
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                if (fy + yy < 0 || fy + yy >= a.fh) continue;
+                const uint8_t *q = C + (size_t)(fy + yy) * a.bgr_pitch + (size_t)3 * fx;
+#pragma unroll
+                for (int d = 0; d < 3; ++d) crow[yy][d] = reinterpret_cast<const ua_u64 *>(q)[d].v;
+            }
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows
+        uint32_t ws = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox = 2 * (x0 + j);
+            const int bit = 48 * j, wd = bit >> 6, sh = bit & 63;      // the cell's six bytes are bytes 6 j .. 6 j + 5 of a row
+            uint64_t c[2];
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                if (whole) {
+                    uint64_t v = crow[yy][wd] >> sh;
+                    if (sh > 16) v |= crow[yy][wd + 1] << (64 - sh);
+                    c[yy] = v & 0xffffffffffffull;
+                } else {
+                    c[yy] = bgr_two(C, a.bgr_pitch, a.fw, a.fh, fx + 2 * j, fy + yy);
+                }
+            }
+            uint64_t qp[2] = {0, 0}, qn[2] = {0, 0};
+            const uint32_t wp = has_p ? stf_bgr_weight(P, a, ox, oy, gp[j], c[0], c[1], thr, magic_thr, qp) : 0u;
+            const uint32_t wn = has_n ? stf_bgr_weight(N, a, ox, oy, gn[j], c[0], c[1], thr, magic_thr, qn) : 0u;
+            const uint32_t S = 8u + wp + wn, m = magic_s[wp + wn], half = S >> 1;
+            uint32_t diff = 0;
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                uint64_t px = 0;
+#pragma unroll
+                for (int q = 0; q < 6; ++q) {
+                    const uint32_t v = __umulhi(8u * ((uint32_t)(c[yy] >> (8 * q)) & 0xffu) + wp * ((uint32_t)(qp[yy] >> (8 * q)) & 0xffu) +
+                                                wn * ((uint32_t)(qn[yy] >> (8 * q)) & 0xffu) + half, m);
+                    px |= (uint64_t)v << (8 * q);
+                }
+                rows[yy][wd] |= px << sh;
+                if (sh > 16) rows[yy][wd + 1] |= px >> (64 - sh);
+                diff = __builtin_amdgcn_sad_u8((uint32_t)px, (uint32_t)c[yy], diff);
+                diff = __builtin_amdgcn_sad_u8((uint32_t)(px >> 32), (uint32_t)(c[yy] >> 32), diff);
+            }
+            ws |= (wp | wn << 4) << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                np += wp != 0u; nn += wn != 0u;
+                wsum += wp + wn;
+                dsum += diff;
+            }
+        }
+        if (a.out) {
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                if (fy + yy < 0 || fy + yy >= a.fh) continue;
+                uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(fy + yy) * a.out_pitch + (ptrdiff_t)3 * fx;
+                if (whole && ((uintptr_t)q & 3u) == 0) {
+                    uint32_t *o = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+                    for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[yy][d >> 1] >> (32 * (d & 1)));
+                } else {
+#pragma unroll
+                    for (int p = 0; p < 8; ++p) {
+                        if (p >= 2 * n || fx + p < 0 || fx + p >= a.fw) continue;
+#pragma unroll
+                        for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[yy][k >> 3] >> (8 * (k & 7)));
+                    }
                 }
             }
         }

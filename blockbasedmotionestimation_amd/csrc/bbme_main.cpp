@@ -36,7 +36,8 @@
 // --denoise-subpel PREFIX --strength T writes --denoise's grey frames made along quarter-pel vectors instead (the subpel temporal
 // filter rule of include/bbme.h: the field into the other frame refined to quarter-pel, its 2x2 cells sampled bilinearly), as
 // PREFIX_1.pgm and PREFIX_2.pgm, the unpadded frames MF sees: with --no-upsample the frames read (on colour frames their luma),
-// without it their 4x planes.  It writes no colour frames: the BGR temporal filter rule is integer.
+// without it their 4x planes.  On colour frames with --no-upsample (which keeps the colour) additionally PREFIX_1.ppm and
+// PREFIX_2.ppm, the colour frames by the BGR subpel temporal filter rule, as --denoise writes its own.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -269,6 +270,11 @@ int main(int argc, char **argv)
                 const std::string name = std::string(denoise_subpel) + "_" + std::to_string(which + 1) + ".pgm";
                 bbme::check(bbme_pgm_write(name.c_str(), img.cols - 2 * px, img.rows - 2 * py, img.cols,
                                            img.data.data() + (size_t)py * img.cols + px));
+                if (colour && !upsample) {             // the colour frame itself, by the BGR subpel temporal filter rule
+                    const bbme::ImageBGR bgr = motion_pair.temporalFilterSubpelBgr(strength, which);
+                    const std::string ppm = std::string(denoise_subpel) + "_" + std::to_string(which + 1) + ".ppm";
+                    bbme::check(bbme_ppm_write_bgr(ppm.c_str(), bgr.cols, bgr.rows, bgr.data.data()));
+                }
             }
         }
         if (backward_color) {

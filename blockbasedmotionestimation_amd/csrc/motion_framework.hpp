@@ -347,6 +347,14 @@ public:
         bbme::check(bbme_get_temporal_filtered_bgr_host(ctx_, 0, which, strength, img.data.data()));
         return img;
     }
+    // temporalFilterBgr() along quarter-pel vectors (the BGR subpel temporal filter rule of include/bbme.h): the cells the frame's
+    // neighbour hangs on are refined on the luma planes and its 2x2 colour cells sampled bilinearly; the UNPADDED frame.
+    bbme::ImageBGR temporalFilterSubpelBgr(int strength, int which = 0)
+    {
+        bbme::ImageBGR img(padded_height - 2 * padding_y, padded_width - 2 * padding_x);
+        bbme::check(bbme_get_subpel_temporal_filtered_bgr_host(ctx_, 0, which, strength, img.data.data()));
+        return img;
+    }
     // Its statistics over window {cx0, cy0, cw, ch} in cells; nullptr = unpaddedCells.
     bbme::InterpolationStats interpolationStats(int num = 1, int den = 2, const int *window = nullptr)
     {

@@ -867,7 +867,7 @@ class MF:
         out = _host_out(out, self._out_shape(bgr), np.uint8, what)
         get = self._lib.bbme_get_temporal_filtered_bgr_host if bgr else self._lib.bbme_get_temporal_filtered_host
         if subpel:
-            get = self._lib.bbme_get_subpel_temporal_filtered_host
+            get = self._lib.bbme_get_subpel_temporal_filtered_bgr_host if bgr else self._lib.bbme_get_subpel_temporal_filtered_host
         _capi.check(get(self._ctx, pair, int(which), int(strength), out.ctypes.data))
         return out
 
@@ -876,7 +876,7 @@ class MF:
         s = (C.c_ulonglong * (4 * frames))()
         stats = self._lib.bbme_temporal_filter_bgr_stats if bgr else self._lib.bbme_temporal_filter_stats
         if subpel:
-            stats = self._lib.bbme_subpel_temporal_filter_stats
+            stats = self._lib.bbme_subpel_temporal_filter_bgr_stats if bgr else self._lib.bbme_subpel_temporal_filter_stats
         _capi.check(stats(self._ctx, int(strength), self._stats_window(window), s))
         return [dict(zip(TEMPORAL_STAT_KEYS, s[4 * f:4 * f + 4])) for f in range(frames)]
 
@@ -1032,6 +1032,59 @@ class MF:
             self._ctx, _ptr(prev), _ptr(cur), _ptr(next), cur.stride(0) if cur is not None else 0, _ptr(to_prev), _ptr(to_next),
             int(strength), win, _ptr(out), out.stride(0) if out is not None else 0, _ptr(weights),
             weights.stride(0) if weights is not None else 0, _ptr(stats), C.c_void_p(hip_stream_handle or 0)))
+        return out, weights, stats
+
+    # -- the colour frames along quarter-pel grids (the BGR SUBPEL TEMPORAL FILTER RULE of include/bbme.h) ----------------------
+    def temporal_filter_subpel_bgr(self, strength, which=0, pair=0, out=None):
+        """temporal_filter_bgr() at quarter-pel positions: the integer cells the frame's neighbours hang on are refined on the
+        luma planes (subpel_cells) and each neighbour's 2x2 cell of the stored B,G,R frame is sampled bilinearly at its
+        quarter-pel position; cost (the largest per-channel SAD of the rounded samples), weight and blend are
+        temporal_filter_bgr()'s -> the UNPADDED (H, W, 3) uint8 frame."""
+        return self._get_temporal_filtered(pair, which, strength, out, "temporal_filter_subpel_bgr", bgr=True, subpel=True)
+
+    def temporal_filter_subpel_bgr_stats(self, strength, window=None):
+        """temporal_filter_bgr_stats() of temporal_filter_subpel_bgr's frames: one dict(prev_cells, next_cells, weight, change)
+        per frame of the context, from at most two refinement launches and one filter launch."""
+        return self._temporal_filter_stats(strength, window, True, subpel=True)
+
+    def cells_temporal_filter_subpel_bgr_device(self, cur, prev=None, next=None, q_to_prev=None, q_to_next=None, strength=64, out=None,
+                                                weights=None, stats=None, window=None, stream=None):
+        """The BGR subpel temporal filter rule on any three colour frames and any two quarter-pel grids in HBM: frames, out,
+        weights and stats as in cells_temporal_filter_bgr_device; q_to_prev, q_to_next int16 CUDA tensors (CH, CW, 2) on cur with
+        packed cells whose rows may be further apart than CW cells (what cells_subpel_device wrote, or a strided view), both
+        with the same row pitch.  On the given HIP stream handle (default: the context's), ordered behind the context's stream;
+        no host wait.  Needs neither frames nor an estimate."""
+        import torch
+        what = "cells_temporal_filter_subpel_bgr_device"
+        ch, cw = self.cells_shape
+        h, w = self.orig_height, self.orig_width
+        for t in (cur, prev, next):
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and _packed_pixels(t)
+                                      and cur is not None and t.stride(0) == cur.stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: colour frames must be uint8 CUDA tensors of shape (%d, %d, 3) with "
+                                      "packed pixels and a common row pitch" % (what, h, w))
+        grids = [t for t in (q_to_prev, q_to_next) if t is not None]
+        for t in grids:
+            if not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.stride(2) == 1 and t.stride(1) == 2
+                    and t.stride(0) >= 2 * cw and t.stride(0) % 2 == 0 and t.data_ptr() % 4 == 0 and t.stride(0) == grids[0].stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: grids must be int16 CUDA tensors of shape (%d, %d, 2) with packed "
+                                      "cells and rows a common whole number of cells apart" % (what, ch, cw))
+        if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3) and _packed_pixels(out)):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape (%d, %d, 3) with packed pixels"
+                                  % (what, h, w))
+        if weights is not None and not (weights.is_cuda and weights.dtype == torch.uint8 and tuple(weights.shape) == (ch, cw)
+                                        and weights.stride(1) == 1):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: weights must be a uint8 CUDA tensor of shape (%d, %d) with unit column "
+                                  "stride" % (what, ch, cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 4" % what)
+        win = _window(window)
+        self._behind_torch(cur, prev, next, q_to_prev, q_to_next, out, weights, stats)
+        _capi.check(self._lib.bbme_cells_subpel_temporal_filter_bgr_device(
+            self._ctx, _ptr(prev), _ptr(cur), _ptr(next), cur.stride(0) if cur is not None else 0, _ptr(q_to_prev), _ptr(q_to_next),
+            grids[0].stride(0) // 2 if grids else cw, int(strength), win, _ptr(out), out.stride(0) if out is not None else 0,
+            _ptr(weights), weights.stride(0) if weights is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
         return out, weights, stats
 
     def frame_bgr_tensor(self, pair=0, which=0):
@@ -1305,6 +1358,10 @@ class MFBatch(MF):
         """MF.temporal_filter_subpel of frame `which` of one pair."""
         return self._get_temporal_filtered(pair, which, strength, out, "get_frame_filtered_subpel", subpel=True)
 
+    def get_frame_filtered_subpel_bgr(self, pair, which, strength, out=None):
+        """MF.temporal_filter_subpel_bgr of frame `which` of one pair."""
+        return self._get_temporal_filtered(pair, which, strength, out, "get_frame_filtered_subpel_bgr", bgr=True, subpel=True)
+
     def compensation_errors(self, level=0, block=2, window=None):
         """MF.compensation_error of every pair, in order, from one launch."""
         return self._compensation_stats(level, block, window)
@@ -1406,7 +1463,7 @@ class MFChain(MFBatch):
         self._behind_torch(frames)
         run = self._lib.bbme_temporal_filter_bgr_chain_device if bgr else self._lib.bbme_temporal_filter_chain_device
         if subpel:
-            run = self._lib.bbme_subpel_temporal_filter_chain_device
+            run = self._lib.bbme_subpel_temporal_filter_bgr_chain_device if bgr else self._lib.bbme_subpel_temporal_filter_chain_device
         _capi.check(run(self._ctx, first, count, int(strength), _ptr(frames), frames.stride(1), frames.stride(0), None))
         self.synchronize()
         return frames.cpu().numpy()
@@ -1420,6 +1477,11 @@ class MFChain(MFBatch):
         """temporal_filter_run() at quarter-pel positions (MF.temporal_filter_subpel): at most two refinement launches for the
         cells the run reads, then one filter launch -> (count, H_pad, W_pad) uint8."""
         return self._temporal_filter_run(strength, first, count, "temporal_filter_run_subpel", False, subpel=True)
+
+    def temporal_filter_run_subpel_bgr(self, strength, first=0, count=None):
+        """temporal_filter_run_bgr() at quarter-pel positions (MF.temporal_filter_subpel_bgr): at most two refinement launches on
+        the luma planes for the cells the run reads, then one filter launch -> (count, H, W, 3) uint8, unpadded."""
+        return self._temporal_filter_run(strength, first, count, "temporal_filter_run_subpel_bgr", True, subpel=True)
 
     def temporal_filter_run_bgr(self, strength, first=0, count=None):
         """temporal_filter_run() in colour: the stored B,G,R frames of slots first .. first + count - 1 (default: to the last)
@@ -1586,8 +1648,9 @@ def interpolate_cells_subpel(image1, image2, qf, qb=None, num=1, den=2, window=N
 
 def _temporal_filter_cells(what, cur, prev, next, to_prev, to_next, strength, window, bgr=False, pad_x=0, pad_y=0, subpel=False):
     """temporal_filter_cells (grey planes: they are their own padded view, so no padding and nothing to check about it), with
-    subpel temporal_filter_cells_subpel (the same planes, the grids quarter-pel) and, with bgr, temporal_filter_cells_bgr (colour
-    frames inside a view padded by pad_x, pad_y); `what` names the caller in the errors."""
+    subpel temporal_filter_cells_subpel (the same planes, the grids quarter-pel), with bgr temporal_filter_cells_bgr (colour
+    frames inside a view padded by pad_x, pad_y) and with both temporal_filter_cells_subpel_bgr; `what` names the caller in the
+    errors."""
     shapes = "uint8 frames of one shape (H, W, 3)" if bgr else "uint8 planes of one shape (H, W)"
     grid_shapes = "int16 grids of shape (H0 / 2, W0 / 2, 2)" if bgr else "int16 grids of shape (H / 2, W / 2, 2)"
     cur = np.ascontiguousarray(cur, np.uint8)
@@ -1614,7 +1677,7 @@ def _temporal_filter_cells(what, cur, prev, next, to_prev, to_next, strength, wi
     size = (w, h, pad_x, pad_y) if bgr else (w, h)
     run = _capi.lib().bbme_temporal_filter_bgr_host if bgr else _capi.lib().bbme_temporal_filter_host
     if subpel:
-        run = _capi.lib().bbme_subpel_temporal_filter_host
+        run = _capi.lib().bbme_subpel_temporal_filter_bgr_host if bgr else _capi.lib().bbme_subpel_temporal_filter_host
     _capi.check(run(_ptr(frames[0]), cur.ctypes.data, _ptr(frames[1]), *size, _ptr(grids[0]), _ptr(grids[1]), int(strength),
                     _window(window), out.ctypes.data, wmap.ctypes.data, s))
     return out, wmap, dict(zip(TEMPORAL_STAT_KEYS, list(s)))
@@ -1643,6 +1706,16 @@ def temporal_filter_cells_bgr(cur, prev=None, next=None, to_prev=None, to_next=N
     cells)."""
     return _temporal_filter_cells("temporal_filter_cells_bgr", cur, prev, next, to_prev, to_next, strength, window, bgr=True,
                                   pad_x=pad_x, pad_y=pad_y)
+
+
+def temporal_filter_cells_subpel_bgr(cur, prev=None, next=None, q_to_prev=None, q_to_next=None, strength=64, pad_x=0, pad_y=0,
+                                     window=None):
+    """The BGR subpel temporal filter rule of include/bbme.h on the CPU (bbme_subpel_temporal_filter_bgr_host):
+    temporal_filter_cells_bgr with q_to_prev, q_to_next int16 (H0 / 2, W0 / 2, 2) QUARTER-PEL grids on cur (what subpel_cells returns
+    on the padded luma planes; any int16), each neighbour's 2x2 cell sampled bilinearly at its quarter-pel position of the
+    zero-padded view -> the same three results."""
+    return _temporal_filter_cells("temporal_filter_cells_subpel_bgr", cur, prev, next, q_to_prev, q_to_next, strength, window, bgr=True,
+                                  pad_x=pad_x, pad_y=pad_y, subpel=True)
 
 
 def bgr_to_gray(frame):

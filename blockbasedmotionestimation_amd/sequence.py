@@ -415,7 +415,7 @@ def interpolate_frames(frames, search_size, block_size, factor, device=None, in_
     return out
 
 
-def denoise_frames(frames, search_size, block_size, strength, device=None, in_flight=4, batch=2, subpel=False):
+def denoise_frames(frames, search_size, block_size, strength, device=None, in_flight=4, batch=2, subpel=False, subpel_bgr=False):
     """Motion-compensated temporal denoising of a video on ONE GPU (the temporal filter rule of include/bbme.h): every
     frame averaged with its two motion-aligned neighbours wherever their 2x2 cells match better than `strength` -> len(frames)
     unpadded uint8 (H, W) frames.  A COLOUR video, (H, W, 3) frames in B,G,R order, gives (H, W, 3) frames by the BGR temporal
@@ -433,11 +433,17 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
     With subpel (grey video only) the SUBPEL TEMPORAL FILTER RULE: the same plan, every grid refined to quarter pels before it is
     used (MFChain.temporal_filter_run_subpel; at a boundary MF.cells_subpel_device makes the copy of a grid, so the copies hold
     quarter-pel grids, and MF.cells_temporal_filter_subpel_device filters).  A colour video with subpel is BbmeError
-    (ERR_UNSUPPORTED): the BGR temporal filter rule is integer."""
+    (ERR_UNSUPPORTED): the BGR temporal filter rule is integer.
+    With subpel_bgr (colour video only; grey frames are a ValueError) the BGR SUBPEL TEMPORAL FILTER RULE: the colour plan, every
+    grid refined to quarter pels on the LUMA planes before it is used (MFChain.temporal_filter_run_subpel_bgr; at a boundary
+    MF.cells_subpel_device on MF.frame_plane_tensor makes the copy of a grid before the planes are overwritten, so the copies hold
+    the colour frames and quarter-pel grids, and MF.cells_temporal_filter_subpel_bgr_device filters)."""
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if subpel_bgr and frames and frames[0].ndim != 3:
+        raise ValueError("denoise_frames: subpel_bgr=True needs a colour video, (H, W, 3) frames in B,G,R order")
     if subpel and frames and frames[0].ndim == 3:
         raise _capi.BbmeError(_capi.ERR_UNSUPPORTED, "denoise_frames: subpel=True on a colour video: the BGR temporal filter rule, "
-                              "the colour rule, is integer; there is no quarter-pel colour filter")
+                              "the colour rule, is integer; the quarter-pel colour filter is subpel_bgr=True")
     n_pairs = len(frames) - 1
     if n_pairs < 1:
         return frames
@@ -452,7 +458,8 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
     def boundary(mf, g, prev, to_prev, cur, nxt, to_next):
         flt = torch.empty_like(cur)
         cells_filter = mf.cells_temporal_filter_subpel_device if subpel else mf.cells_temporal_filter_device
-        (mf.cells_temporal_filter_bgr_device if bgr else cells_filter)(cur, prev, nxt, to_prev, to_next, strength, out=flt)
+        bgr_filter = mf.cells_temporal_filter_subpel_bgr_device if subpel_bgr else mf.cells_temporal_filter_bgr_device
+        (bgr_filter if bgr else cells_filter)(cur, prev, nxt, to_prev, to_next, strength, out=flt)
         mf.synchronize()
         keep(mf, g, flt.cpu().numpy())
 
@@ -464,10 +471,11 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
         out[g] = np.ascontiguousarray(plane[py:py + h, px:px + w])
 
     def grid(mf, cur, other, cells):
-        """The grid on `cur` into `other` as the filter reads it: with subpel a fresh quarter-pel grid, refined on the GPU"""
-        if not subpel:
+        """The grid on frame `cur` = (pair, which) into frame `other` as the filter reads it: with subpel or subpel_bgr a fresh
+        quarter-pel grid, refined on the GPU on the level-0 planes (in colour: the luma planes)"""
+        if not (subpel or subpel_bgr):
             return cells
-        q4 = mf.cells_subpel_device(cur, other, cells, out=torch.empty_like(cells))[0]
+        q4 = mf.cells_subpel_device(mf.frame_plane_tensor(*cur), mf.frame_plane_tensor(*other), cells, out=torch.empty_like(cells))[0]
         mf.synchronize()                                   # refined on the context's stream: the copy and another context read it from theirs
         return q4
 
@@ -476,6 +484,8 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
         lo = 0 if first == 0 else 1                        # the video's first frame has no previous one anywhere: the chain's own slot 0
         if count > lo:
             run = mf.temporal_filter_run_bgr if bgr else mf.temporal_filter_run_subpel if subpel else mf.temporal_filter_run
+            if subpel_bgr:
+                run = mf.temporal_filter_run_subpel_bgr
             for q, plane in enumerate(run(strength, lo, count - lo)):      # waits for this context's stream only
                 keep(mf, first + lo + q, plane)
         else:
@@ -483,7 +493,7 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
         with torch.cuda.device(device):
             # the round's first frame: its next half is here
             if first > 0:
-                half = (frame_tensor(0, 0), frame_tensor(0, 1), grid(mf, frame_tensor(0, 0), frame_tensor(0, 1), mf.cells_tensor(0)))
+                half = (frame_tensor(0, 0), frame_tensor(0, 1), grid(mf, (0, 0), (0, 1), mf.cells_tensor(0)))
                 if first in before:
                     boundary(mf, first, *before.pop(first), *half)
                 else:
@@ -491,7 +501,7 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
             # the round's last frame: its previous half is here
             last = first + count
             half = (frame_tensor(count - 1, 0),
-                    grid(mf, frame_tensor(count - 1, 1), frame_tensor(count - 1, 0), mf.backward_cells_tensor(count - 1)))
+                    grid(mf, (count - 1, 1), (count - 1, 0), mf.backward_cells_tensor(count - 1)))
             if last == n_pairs:
                 boundary(mf, last, *half, frame_tensor(count - 1, 1), None, None)
             elif last in after:

@@ -737,7 +737,8 @@ int bbme_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, un
  * the grid to be written.
  * A context made for up-sampled frames (bbme_set_frames_*_x4) refines its 4x planes: the result is then 1/16 pel of the source.
  * A colour context refines on its luma planes.  The SUBPEL COMPENSATION RULE, the SUBPEL INTERPOLATION RULE, the BGR SUBPEL
- * INTERPOLATION RULE and the SUBPEL TEMPORAL FILTER RULE below read quarter-pel vectors; the other rules that take a cell grid
+ * INTERPOLATION RULE, the SUBPEL TEMPORAL FILTER RULE and the BGR SUBPEL TEMPORAL FILTER RULE below read quarter-pel vectors; the
+ * other rules that take a cell grid
  * (integer compensation, the INTERPOLATION RULE and the BGR INTERPOLATION RULE, the TEMPORAL FILTER RULE and the BGR TEMPORAL
  * FILTER RULE) do not: they are integer.
  * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, q4_pitch_cells < CW, a
@@ -999,6 +1000,76 @@ int bbme_subpel_temporal_filter_chain_device(bbme_ctx *ctx, int first, int count
                                              size_t out_stride, void *hip_stream);
 int bbme_get_subpel_temporal_filtered_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
 int bbme_subpel_temporal_filter_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
+
+/* BGR SUBPEL TEMPORAL FILTER RULE (this project's own): the BGR TEMPORAL FILTER RULE with each neighbour's cell taken at a
+ * QUARTER-PEL position, the position taken exactly as the SUBPEL TEMPORAL FILTER RULE takes it, but on the zero-padded view of the
+ * colour frames.  Inputs: those of the BGR TEMPORAL FILTER RULE -- the W x H B,G,R frame C, optionally P and / or N, the paddings
+ * pad_x, pad_y >= 0 with W0 = W + 2 pad_x and H0 = H + 2 pad_y both even, a strength thr, 1 <= thr <= 1021 -- except that the two
+ * grids QP (on C, into P) and QN (on C, into N) hold quarter-pel vectors, CH x CW int16 (qx, qy) pairs as bbme_subpel_* writes
+ * them; any int16 is allowed.  All arithmetic is in 32-bit integers, `>>` of a negative number is the arithmetic shift, every
+ * division the floor division of non-negative numbers.
+ * For cell (cx, cy) with origin o = (2 cx, 2 cy) in the padded view and each present neighbour X with grid Q:
+ *   (qx, qy) = Q[cy][cx], i = (qx >> 2, qy >> 2), f = (qx & 3, qy & 3), s = o + i;
+ *   the neighbour is valid when 0 <= s.x, s.x + 2 + (fx != 0) <= W0, 0 <= s.y and s.y + 2 + (fy != 0) <= H0: the grey subpel
+ *   filter's validity, on the padded view;
+ *   X'[j, k][c] = ((4 - fx)(4 - fy) T00 + fx (4 - fy) T10 + (4 - fx) fy T01 + fx fy T11 + 8) >> 4 for 0 <= j, k < 2 and every channel
+ *   c, T.. the taps at the padded positions s + (j, k) + {(0, 0), (1, 0), (0, 1), (1, 1)}.  A tap at the padded position (X, Y) is
+ *   frame pixel (X - pad_x, Y - pad_y), and 0 in every channel outside [0, W) x [0, H).  A tap of weight 0 is not read; no byte
+ *   outside the frames is ever read;
+ *   cost_c = sum over the four ROUNDED samples of |C[o + (j, k)][c] - X'[j, k][c]|;
+ *   cost = max(cost_B, cost_G, cost_R), 0..1020;
+ *   w = 8 (thr - cost) / thr if the neighbour is valid and cost < thr, else 0.
+ * With S = 8 + wP + wN (8..24), every channel of every pixel of the cell is
+ *   out[o + (j, k)] = (8 C[o + (j, k)] + wP P'[j, k] + wN N'[j, k] + S / 2) / S.
+ * The output is the UNPADDED W x H frame: with an odd padding cells straddle the frame's edge and only their pixels inside the
+ * frame are written.  The weight map (wP | wN << 4, one byte per cell of the padded view) and the four statistics over a window in
+ * cells are the BGR TEMPORAL FILTER RULE's: the fourth is the sum of |out - C| over three channels, on the padded view.
+ * Properties.  (1) On frames with B = G = R every channel is the unpadded window of the SUBPEL TEMPORAL FILTER RULE's result on the
+ * zero-padded plane; the map and the first three statistics are equal and the fourth is three times the grey one.  (2) With
+ * QP = 4 GP and QN = 4 GN for integer grids the frame, the map and the statistics are the BGR TEMPORAL FILTER RULE's on GP and GN,
+ * bit for bit.  (3) With equal frames and zero grids the frame is unchanged and every present weight is 8.  (4) The grid call has
+ * no size limit of its own: s is computed in 32 bits from any int16.
+ * WHAT IT BUYS.  PSNR gain in dB of the filtered middle frame over the noisy one, worst channel, interior only, one independent
+ * texture per channel, over two sizes and three noise levels (tests/test_subpel_temporal_filter_bgr_cpu.py holds these):
+ *     motion per frame (quarter pels)     BGR rule, two- / one-sided        this rule, two- / one-sided
+ *     whole pixels                        +4.3..+4.7 / +2.7..+2.8           the same frames
+ *     half pixels                         +2.1..+4.5 / +0.3..+2.4           +5.2..+6.7 / +3.6..+4.2
+ *     odd quarter pels                    +4.0..+4.6 / +1.4..+2.7           +5.3..+6.2 / +3.5..+3.9
+ * On a context with its own fields the grids are those the SUBPEL TEMPORAL FILTER RULE's context calls use: the backward cells of
+ * the pair the frame is image 2 of and the forward cells of the pair it is image 1 of, each refined by the SUBPEL RULE (K10) on the
+ * LUMA planes into the context's quarter-pel buffers; the filter then reads only the stored colour (the COLOUR STORE above).
+ * Errors: the union of both families'.  BBME_ERR_INVALID for bgr_pitch or out_pitch < 3 W, an out_stride below one frame when
+ * count > 1, q4_pitch_cells < CW, thr outside 1..1021, a bad window, an output that overlaps an input frame; BBME_ERR_STATE without
+ * a valid pair of fields or when a frame the call reads has no stored colour; BBME_ERR_UNSUPPORTED beyond W0 or H0 8188 for the
+ * four context-level calls and for bbme_subpel_temporal_filter_bgr_chain_device off a chain.  None of these calls changes context
+ * state (grids, memo, flow, cells, backward cells, captured graphs, colour store); the statistics scratch is their own, the
+ * quarter-pel buffers are those of the grey calls (the same cells of the same planes: the same vectors).
+ * bbme_subpel_temporal_filter_bgr_host: the rule on the CPU, no GPU: bbme_temporal_filter_bgr_host's arguments, the grids
+ * quarter-pel.
+ * bbme_cells_subpel_temporal_filter_bgr_device: ANY three colour frames in HBM with one common pitch bgr_pitch >= 3 W and ANY two
+ * quarter-pel grids of the context's cell geometry, rows of both grids q4_pitch_cells int16 pairs apart; otherwise as
+ * bbme_cells_temporal_filter_bgr_device; no host wait.
+ * bbme_subpel_temporal_filter_bgr_device: frame `which` of `pair`: the integer grids it needs refined (one K10 launch each), then
+ * one filter launch.
+ * bbme_subpel_temporal_filter_bgr_chain_device: chain contexts only; at most two refinement launches, then ONE filter launch for
+ * slots first .. first + count - 1, frame q at d_out + q out_stride.
+ * bbme_get_subpel_temporal_filtered_bgr_host: one frame as bbme_subpel_temporal_filter_bgr_device; synchronises; packed rows of
+ * 3 W bytes.
+ * bbme_subpel_temporal_filter_bgr_stats: EVERY frame of the context from one filter launch; synchronises; laid out as
+ * bbme_temporal_filter_stats. */
+int bbme_subpel_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height, int pad_x,
+                                         int pad_y, const int16_t *q_to_prev, const int16_t *q_to_next, int thr, const int *window,
+                                         uint8_t *out, uint8_t *weights, unsigned long long *stats4);
+int bbme_cells_subpel_temporal_filter_bgr_device(bbme_ctx *ctx, const uint8_t *d_prev, const uint8_t *d_cur, const uint8_t *d_next,
+                                                 int bgr_pitch, const int16_t *d_q_to_prev, const int16_t *d_q_to_next,
+                                                 int q4_pitch_cells, int thr, const int *window, uint8_t *d_out, int out_pitch,
+                                                 uint8_t *d_weights, int weights_pitch, unsigned long long *d_stats4, void *hip_stream);
+int bbme_subpel_temporal_filter_bgr_device(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *d_out, int out_pitch,
+                                           void *hip_stream);
+int bbme_subpel_temporal_filter_bgr_chain_device(bbme_ctx *ctx, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                                 size_t out_stride, void *hip_stream);
+int bbme_get_subpel_temporal_filtered_bgr_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
+int bbme_subpel_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
