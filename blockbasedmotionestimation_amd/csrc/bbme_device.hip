@@ -355,6 +355,12 @@ struct bbme_ctx {
                                                   // bbme_cells_subpel_temporal_filter_device (one)
     StatsScratch tfsb_stats;                      // bbme_subpel_temporal_filter_bgr_stats (every frame) and
                                                   // bbme_cells_subpel_temporal_filter_bgr_device (one)
+    StatsScratch cmp_stats;                       // bbme_cells_compose_device: one result quadruple and one launch's partials
+    DevBuf<mv_t> wide_cells, wide_q4;             // a chain's wide temporal filter: the composed integer cells into slot f + 2 of
+                                                  // every slot f, then those into slot f - 2, packed; and the same refined to
+                                                  // quarter pels.  Allocated at first use (wide_prepare)
+    StatsScratch wide_stats;                      // bbme_wide_temporal_filter_stats (two quadruples per slot) and
+                                                  // bbme_cells_wide_temporal_filter_device (two more)
 };
 
 namespace {
@@ -1771,7 +1777,7 @@ int bbme_subsampled_flow_device(bbme_ctx *c, int pair, int scale, float *d_out, 
 
 }  // extern "C": the stages from here on share templates, which need C++ linkage; their entry points have C linkage from bbme.h
 
-// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter, K11, K12, K12b) ----
+// ---- what the gather stages share (bbme_kernels.hpp: compensation, K6 consistency, K7 / K7b interpolation, K9 / K9b temporal filter, K11 .. K15) ----
 // Every stage is one launch in which a lane takes runs of 4 units (pixels or cells) along a row, over (workgroups, pairs, phases
 // or frames), with optional statistics: the kernel's partials, then k_mc_reduce.  One run split, one launch path, one scratch
 // layout, one pair of output checks and one pair of download helpers serve all of them.
@@ -3521,6 +3527,271 @@ int bbme_get_subpel_temporal_filtered_bgr_host(bbme_ctx *c, int pair, int which,
 int bbme_subpel_temporal_filter_bgr_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
 {
     return tf_stats<TfSubpelBgr>(c, "bbme_subpel_temporal_filter_bgr_stats", thr, window, stats);
+}
+
+// ---- composition of two cell grids (the CELL COMPOSITION RULE of include/bbme.h; K14 k_compose_cells) ----------------------------
+
+// k_compose_cells over `count` frames (blockIdx.z) and, with d_results, k_mc_reduce of its partials into d_results[4 z ..]
+static int enqueue_cmp(bbme_ctx *c, CmpArgs &a, int count, const int *window, unsigned long long *partial,
+                       unsigned long long *d_results, hipStream_t stream)
+{
+    a.cw = c->lv[0].width / 2; a.ch = c->lv[0].height / 2;
+    set_window(a, window, a.cw, a.ch);
+    set_runs(a, a.cw, a.ch);
+    return launch_gather(k_compose_cells<kCmpRunsPerLane>, a, cell_groups(c, kCmpRunsPerLane), 1, count, partial, d_results, stream);
+}
+
+int bbme_cells_compose_device(bbme_ctx *c, const int16_t *d_a, int a_pitch_cells, const int16_t *d_b, int b_pitch_cells, int unit_shift,
+                              const int *window, int16_t *d_out, int out_pitch_cells, unsigned long long *d_stats2, void *hip_stream)
+{
+    const char *what = "bbme_cells_compose_device";
+    if (int rc = check_ctx(c)) return rc;
+    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
+    if (!d_a || !d_b || (!d_out && !d_stats2)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (a_pitch_cells < cw || b_pitch_cells < cw || (d_out && out_pitch_cells < cw))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a grid pitch < %d cells per row", what, cw);
+    if (unit_shift != 0 && unit_shift != 2) return bbme::fail(BBME_ERR_INVALID, "%s: unit shift %d (0 or 2)", what, unit_shift);
+    if (int rc = check_window(window, cw, ch, what, -1)) return rc;
+    const uint8_t *o = reinterpret_cast<const uint8_t *>(d_out);
+    if (d_out && (overlaps_input(o, out_pitch_cells * 4, {reinterpret_cast<const uint8_t *>(d_a)}, a_pitch_cells * 4, cw * 4, ch) ||
+                  overlaps_input(o, out_pitch_cells * 4, {reinterpret_cast<const uint8_t *>(d_b)}, b_pitch_cells * 4, cw * 4, ch)))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input grid", what);
+    HIP_TRY(hipSetDevice(c->device));
+    // one result quadruple, then one launch's partials: one size per context
+    if (d_stats2) if (int rc = c->cmp_stats.ensure(1, cell_groups(c, kCmpRunsPerLane), 0, 1, "the composition statistics")) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    CmpArgs a{};
+    a.a = reinterpret_cast<const mv_t *>(d_a); a.b = reinterpret_cast<const mv_t *>(d_b); a.out = reinterpret_cast<mv_t *>(d_out);
+    a.a_pitch = a_pitch_cells; a.b_pitch = b_pitch_cells; a.out_pitch = out_pitch_cells; a.ushift = unit_shift;
+    if (int rc = enqueue_cmp(c, a, 1, window, c->cmp_stats.partials_caller(), d_stats2 ? c->cmp_stats.results() : nullptr, stream)) return rc;
+    if (d_stats2)      // the first two words of the quadruple
+        HIP_TRY(hipMemcpyAsync(d_stats2, c->cmp_stats.results(), 2 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
+    return BBME_OK;
+}
+
+// The chain's own: for slots lo .. lo + n - 1 the integer grid into slot + 2 (side > 0: the forward cells of pair slot, then those
+// of pair slot + 1) or into slot - 2 (the backward cells of pair slot - 1, then those of pair slot - 2), one launch
+static int enqueue_cmp_chain(bbme_ctx *c, int lo, int n, int side, mv_t *d_out, int out_pitch, size_t out_stride, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    CmpArgs a{};
+    if (side > 0) {
+        a.a_z = a.b_z = L.grid_stride(L.final_grid());
+        a.a = L.final_grid() + lo * a.a_z; a.b = a.a + a.a_z;
+    } else {
+        a.a_z = a.b_z = c->bwd_stride;
+        a.a = c->bwd_cells.get() + (lo - 1) * a.a_z; a.b = a.a - a.a_z;
+    }
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    a.a_pitch = a.b_pitch = L.width / 2;
+    return enqueue_cmp(c, a, n, nullptr, nullptr, nullptr, stream);
+}
+
+int bbme_compose_chain_device(bbme_ctx *c, int first, int count, int side, int16_t *d_out, int out_pitch_cells, size_t out_stride_cells,
+                              void *hip_stream)
+{
+    const char *what = "bbme_compose_chain_device";
+    if (int rc = chain_context_only(c, what)) return rc;
+    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
+    if (side != 1 && side != -1) return bbme::fail(BBME_ERR_INVALID, "%s: side %d (+1 or -1)", what, side);
+    const int lo = side > 0 ? 0 : 2, hi = side > 0 ? c->batch - 2 : c->batch;
+    if (count < 1 || first < lo || (long long)first + count - 1 > hi)
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside %d .. %d, the slots with a slot two %s", what,
+                          first, first, count, lo, hi, side > 0 ? "on" : "back");
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (out_pitch_cells < cw) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < %d cells per row", what, out_pitch_cells, cw);
+    if (count > 1 && out_stride_cells < (size_t)out_pitch_cells * ch)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output stride %zu < one grid of %d rows of %d cells", what, out_stride_cells, ch,
+                          out_pitch_cells);
+    if (int rc = check_fields_state(c, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_cmp_chain(c, first, count, side, reinterpret_cast<mv_t *>(d_out), out_pitch_cells, out_stride_cells, stream);
+}
+
+// ---- temporal filter over two frames on each side (the WIDE TEMPORAL FILTER RULE of include/bbme.h; K15 k_wide_temporal_filter) ----
+// A path of its own beside the temporal filter's flavours: four neighbours, six statistics and chain contexts only.
+
+// Statistics scratch: two result quadruples per slot ({w_k > 0}, {weights, |out - C|, 0, 0}), two more for a caller's launch,
+// then the partials of a launch over every slot and those of a caller's: one size per context
+static int wide_scratch(bbme_ctx *c)
+{
+    return c->wide_stats.ensure(2 * kTfMaxFrames + 2, tf_groups(c), 2 * c->frames(), 2, "the wide temporal filter statistics");
+}
+
+static unsigned long long *wide_results_caller(bbme_ctx *c) { return c->wide_stats.results() + (size_t)4 * 2 * kTfMaxFrames; }
+
+static WtfArgs wide_args(const bbme_ctx *c, int thr, const int *window)
+{
+    const Level &L = c->lv[0];
+    WtfArgs a{};
+    a.width = L.width; a.height = L.height; a.cw = L.width / 2; a.ch = L.height / 2;
+    a.thr = thr;
+    a.magic_thr = thr > 1 ? (uint32_t)((1ull << 32) / (unsigned)thr + 1ull) : 0u;      // thr = 1: the kernel does not divide
+    for (int S = 8; S <= 40; ++S) a.magic_s[S - 8] = (uint32_t)((1ull << 32) / (unsigned)S + 1ull);
+    a.q4_pitch = a.cw;
+    set_window(a, window, a.cw, a.ch);
+    set_runs(a, a.cw, a.ch);
+    return a;
+}
+
+// k_wide_temporal_filter over `count` frames and, with d_results, k_mc_reduce of its partials into d_results[8 z ..]
+static int enqueue_wide(bbme_ctx *c, WtfArgs &a, int count, unsigned long long *partial, unsigned long long *d_results, hipStream_t stream)
+{
+    const long long groups = tf_groups(c);
+    a.partial = d_results ? partial : nullptr;
+    hipLaunchKernelGGL(k_wide_temporal_filter<kTfRunsPerLane>, dim3((unsigned)groups, 1u, (unsigned)count), dim3(256), 0, stream, a);
+    if (d_results) hipLaunchKernelGGL(k_mc_reduce, dim3(2u * (unsigned)count), dim3(256), 0, stream, a.partial, (int)groups, d_results);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+int bbme_cells_wide_temporal_filter_device(bbme_ctx *c, const uint8_t *const d_planes[4], const uint8_t *d_cur,
+                                           const int16_t *const d_grids[4], int q4_pitch_cells, int thr, const int *window, uint8_t *d_out,
+                                           int out_pitch, uint16_t *d_weights, int weights_pitch, unsigned long long *d_stats6,
+                                           void *hip_stream)
+{
+    const char *what = "bbme_cells_wide_temporal_filter_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_planes || !d_grids || !d_cur || (!d_out && !d_weights && !d_stats6)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (q4_pitch_cells < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch_cells, L.width / 2);
+    bool any = false;
+    for (int k = 0; k < 4; ++k) {
+        if ((d_planes[k] == nullptr) != (d_grids[k] == nullptr))
+            return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its plane and its grid", what);
+        any = any || d_planes[k];
+    }
+    if (!any) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if (d_out) if (int rc = check_frames(1, out_pitch, 0, L.width, L.height, what, "output")) return rc;
+    if (d_weights && weights_pitch < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: weight map pitch %d < %d cells per row", what, weights_pitch, L.width / 2);
+    if (d_out && overlaps_input(d_out, out_pitch, {d_cur, d_planes[0], d_planes[1], d_planes[2], d_planes[3]}, L.width, L.width, L.height))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input plane", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats6) if (int rc = wide_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    WtfArgs a = wide_args(c, thr, window);
+    a.cur = d_cur;
+    for (int k = 0; k < 4; ++k) { a.x[k] = d_planes[k]; a.g[k] = reinterpret_cast<const mv_t *>(d_grids[k]); }
+    a.q4_pitch = q4_pitch_cells;
+    a.first_prev = a.last_next = 2;
+    a.out = d_out; a.out_pitch = out_pitch;
+    a.wmap = d_weights; a.wmap_pitch = weights_pitch;
+    if (int rc = enqueue_wide(c, a, 1, c->wide_stats.partials_caller(), d_stats6 ? wide_results_caller(c) : nullptr, stream)) return rc;
+    if (d_stats6)      // the first six words of the two quadruples
+        HIP_TRY(hipMemcpyAsync(d_stats6, wide_results_caller(c), 6 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
+    return BBME_OK;
+}
+
+// The chain's slots first .. first + count - 1 as the kernel addresses them, every grid a launch reads made on `stream` first:
+// the +-1 grids are the subpel temporal filter's, refined into its buffer by its own prepare (at most two K10 launches); the +-2
+// grids are composed (one K14 launch a side) into wide_cells and refined against (slot, slot +- 2) into wide_q4 (one K10 launch a
+// side).  Both buffers hold, packed, the grids into slot f - 2 of every slot f, then those into slot f + 2.
+static int wide_prepare(bbme_ctx *c, WtfArgs &a, int first, int count, hipStream_t stream, const char *what)
+{
+    const Level &L = c->lv[0];
+    const int cw = L.width / 2, slots = c->batch + 1, last = first + count - 1;
+    const long long cells = (long long)cw * (L.height / 2), s_plane = L.plane_stride;
+    TfSpArgs adj{};
+    if (int rc = TfSubpel::prepare(c, adj, 0, 1, first, count, stream, what)) return rc;
+    if (int rc = c->wide_cells.ensure(2 * (size_t)cells * slots, "the composed cells of the wide temporal filter", Fill::poison)) return rc;
+    if (int rc = c->wide_q4.ensure(2 * (size_t)cells * slots, "the quarter-pel cells of the wide temporal filter", Fill::poison)) return rc;
+    const uintptr_t cur = reinterpret_cast<uintptr_t>(L.img1.get()) + first * s_plane;
+    a.cur = reinterpret_cast<const uint8_t *>(cur);
+    a.plane_z = s_plane; a.g_z = cells;
+    a.first_prev = std::min(first, 2); a.last_next = std::min(slots - 1 - last, 2);
+    a.g[0] = adj.gp; a.g[1] = adj.gn;
+    for (int k = 0; k < 4; ++k) {
+        const long long step = (k & 1 ? 1 : -1) * (1 + (k >> 1));                    // slots from C to the neighbour
+        a.x[k] = reinterpret_cast<const uint8_t *>(cur + step * s_plane);            // never read where the chain has no such slot
+    }
+    for (int side = 0; side < 2; ++side) {                                           // 0: into slot - 2 (P2), 1: into slot + 2 (N2)
+        const int lo = side ? first : std::max(first, 2), hi = side ? std::min(last, slots - 3) : last;
+        mv_t *cmp = c->wide_cells.get() + (size_t)side * slots * cells, *q4 = c->wide_q4.get() + (size_t)side * slots * cells;
+        if (hi >= lo) {
+            const uint8_t *i1 = L.img1.get() + (size_t)lo * s_plane, *i2 = L.img1.get() + (size_t)(lo + (side ? 2 : -2)) * s_plane;
+            if (int rc = enqueue_cmp_chain(c, lo, hi - lo + 1, side ? 1 : -1, cmp + (size_t)lo * cells, cw, (size_t)cells, stream)) return rc;
+            if (int rc = enqueue_sp(c, i1, i2, (size_t)s_plane, cmp + (size_t)lo * cells, (size_t)cells, hi - lo + 1, nullptr,
+                                    q4 + (size_t)lo * cells, cw, (size_t)cells, nullptr, nullptr, stream))
+                return rc;
+        }
+        a.g[2 + side] = q4 + (size_t)first * cells;
+    }
+    return BBME_OK;
+}
+
+// what the context-level calls of the wide filter share: a chain, the strength and window, 8188, the context's state
+static int check_wide_own(const bbme_ctx *c, int thr, const int *window, const char *what)
+{
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if (int rc = check_sp(c, nullptr, what)) return rc;
+    return check_fields_state(c, what);
+}
+
+static int enqueue_own_wide(bbme_ctx *c, const char *what, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
+                            hipStream_t stream)
+{
+    WtfArgs a = wide_args(c, thr, nullptr);
+    if (int rc = wide_prepare(c, a, first, count, stream, what)) return rc;
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    return enqueue_wide(c, a, count, nullptr, nullptr, stream);
+}
+
+int bbme_wide_temporal_filter_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch, size_t out_stride,
+                                           void *hip_stream)
+{
+    const char *what = "bbme_wide_temporal_filter_chain_device";
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (first < 0 || count < 1 || (long long)first + count > c->batch + 1)
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside 0 .. %d", what, first, first, count, c->batch);
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_frames(count, out_pitch, out_stride, c->lv[0].width, c->lv[0].height, what, "output")) return rc;
+    if (int rc = check_wide_own(c, thr, nullptr, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_wide(c, what, first, count, thr, d_out, out_pitch, out_stride, stream);
+}
+
+int bbme_get_wide_temporal_filtered_host(bbme_ctx *c, int slot, int thr, uint8_t *out)
+{
+    const char *what = "bbme_get_wide_temporal_filtered_host";
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (slot < 0 || slot > c->batch) return bbme::fail(BBME_ERR_INVALID, "%s: slot %d is not inside 0 .. %d", what, slot, c->batch);
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_wide_own(c, thr, nullptr, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int w = c->lv[0].width;
+    return download_staged(c, (size_t)w * c->lv[0].height, "the wide filtered frame", out, [&](uint8_t *d) {
+        return enqueue_own_wide(c, what, slot, 1, thr, d, w, 0, c->stream);
+    });
+}
+
+int bbme_wide_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_wide_temporal_filter_stats";
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_wide_own(c, thr, window, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = wide_scratch(c)) return rc;
+    const int slots = c->batch + 1;
+    std::vector<unsigned long long> s((size_t)8 * slots);
+    WtfArgs a = wide_args(c, thr, window);
+    if (int rc = download_stats(c, c->wide_stats, 2 * slots, s.data(), [&] {
+            if (int rc = wide_prepare(c, a, 0, slots, c->stream, what)) return rc;
+            return enqueue_wide(c, a, slots, c->wide_stats.partials_all(), c->wide_stats.results(), c->stream);
+        }))
+        return rc;
+    for (int f = 0; f < slots; ++f)
+        for (int k = 0; k < 6; ++k) stats[6 * f + k] = s[8 * f + k];
+    return BBME_OK;
 }
 
 extern "C" {

@@ -1218,6 +1218,109 @@ int bbme_subpel_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur
     return BBME_OK;
 }
 
+// The CELL COMPOSITION RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_compose_cells).
+int bbme_compose_host(const int16_t *a, int a_pitch_cells, const int16_t *b, int b_pitch_cells, int cells_w, int cells_h,
+                      int unit_shift, const int *window, int16_t *out, int out_pitch_cells, unsigned long long *stats2)
+{
+    const char *what = "bbme_compose_host";
+    if (!a || !b || (!out && !stats2)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (cells_w < 1 || cells_h < 1) return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d cells", what, cells_w, cells_h);
+    if (a_pitch_cells < cells_w || b_pitch_cells < cells_w || (out && out_pitch_cells < cells_w))
+        return bbme::fail(BBME_ERR_INVALID, "%s: a grid pitch < %d cells per row", what, cells_w);
+    if (unit_shift != 0 && unit_shift != 2) return bbme::fail(BBME_ERR_INVALID, "%s: unit shift %d (0 or 2)", what, unit_shift);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cells_w, cells_h, what, "cells")) return rc;
+    const int u = unit_shift;
+    const auto sat16 = [](int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; };
+    unsigned long long s[2] = {0, 0};
+    for (int cy = 0; cy < cells_h; ++cy)
+        for (int cx = 0; cx < cells_w; ++cx) {
+            const size_t i = (size_t)cy * a_pitch_cells + cx;
+            const int ax = a[2 * i], ay = a[2 * i + 1];
+            const int tx = (2 * cx) * (1 << u) + ax, ty = (2 * cy) * (1 << u) + ay;
+            // floor division by 2^(u + 1): the arithmetic shift of the rule, without shifting a negative number here
+            const int d = 1 << (u + 1);
+            const auto floor_div = [d](int v) { return v >= 0 ? v / d : -((-v + d - 1) / d); };
+            const int px = floor_div(tx + (1 << u)), py = floor_div(ty + (1 << u));
+            const int qx = std::min(std::max(px, 0), cells_w - 1), qy = std::min(std::max(py, 0), cells_h - 1);
+            const size_t j = (size_t)qy * b_pitch_cells + qx;
+            const int sx = ax + b[2 * j], sy = ay + b[2 * j + 1];
+            const int rx = sat16(sx), ry = sat16(sy);
+            if (out) {
+                const size_t o = (size_t)cy * out_pitch_cells + cx;
+                out[2 * o] = (int16_t)rx; out[2 * o + 1] = (int16_t)ry;
+            }
+            if (win.contains(cx, cy)) { s[0] += qx != px || qy != py; s[1] += rx != sx || ry != sy; }
+        }
+    if (stats2) memcpy(stats2, s, sizeof s);
+    return BBME_OK;
+}
+
+// The WIDE TEMPORAL FILTER RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of
+// k_wide_temporal_filter): bbme_subpel_temporal_filter_host's neighbour, up to four times.  A tap of weight 0 is not read.
+int bbme_wide_temporal_filter_host(const uint8_t *const planes[4], const uint8_t *cur, int width, int height,
+                                   const int16_t *const grids[4], int q4_pitch_cells, int thr, const int *window, uint8_t *out,
+                                   uint16_t *weights, unsigned long long *stats6)
+{
+    const char *what = "bbme_wide_temporal_filter_host";
+    if (!planes || !grids || !cur || (!out && !weights && !stats6)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    bool any = false;
+    for (int n = 0; n < 4; ++n) {
+        if ((planes[n] == nullptr) != (grids[n] == nullptr))
+            return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its plane and its grid", what);
+        any = any || planes[n];
+    }
+    if (!any) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    const int cw = width / 2, ch = height / 2;
+    if (q4_pitch_cells < cw) return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch_cells, cw);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cw, ch, what, "cells")) return rc;
+    unsigned long long s[6] = {0, 0, 0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx, g = (size_t)cy * q4_pitch_cells + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            int w[4] = {0, 0, 0, 0}, x[4][4] = {};                               // the weights; the rounded samples X'[j, k] at [2 k + j]
+            for (int n = 0; n < 4; ++n) {
+                if (!planes[n]) continue;
+                const int qx = grids[n][2 * g], qy = grids[n][2 * g + 1];
+                const int fx = qx & 3, fy = qy & 3, sx = ox + (qx >> 2), sy = oy + (qy >> 2);
+                if (sx < 0 || sx + 2 + (fx != 0) > width || sy < 0 || sy + 2 + (fy != 0) > height) continue;
+                int cost = 0;
+                for (int k = 0; k < 2; ++k)
+                    for (int j = 0; j < 2; ++j) {
+                        const auto tap = [&](int weight, int dx, int dy) {
+                            return weight ? weight * planes[n][(size_t)(sy + k + dy) * width + sx + j + dx] : 0;
+                        };
+                        x[n][2 * k + j] = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+                        cost += abs((int)cur[(size_t)(oy + k) * width + ox + j] - x[n][2 * k + j]);
+                    }
+                if (cost < thr) w[n] = 8 * (thr - cost) / thr;
+            }
+            const int S = 8 + w[0] + w[1] + w[2] + w[3];
+            unsigned diff = 0;
+            for (int k = 0; k < 2; ++k)
+                for (int j = 0; j < 2; ++j) {
+                    const size_t at = (size_t)(oy + k) * width + ox + j;
+                    int num = 8 * cur[at] + S / 2;
+                    for (int n = 0; n < 4; ++n) num += w[n] * x[n][2 * k + j];
+                    const int v = num / S;
+                    if (out) out[at] = (uint8_t)v;
+                    diff += (unsigned)abs(v - (int)cur[at]);
+                }
+            if (weights) weights[c] = (uint16_t)(w[0] | w[1] << 4 | w[2] << 8 | w[3] << 12);
+            if (win.contains(cx, cy)) {
+                for (int n = 0; n < 4; ++n) { s[n] += w[n] > 0; s[4] += (unsigned)w[n]; }
+                s[5] += diff;
+            }
+        }
+    if (stats6) memcpy(stats6, s, sizeof s);
+    return BBME_OK;
+}
+
 // The BGR SUBPEL INTERPOLATION RULE of include/bbme.h: the selection of bbme_subpel_interpolate_host on the luma planes (its map
 // tells which hypothesis; P1 and P2 follow from it), then every pixel of the two colour frames sampled bilinearly at P1 and P2 and
 // blended (the mirror of k_subpel_interpolate_bgr).  A tap of weight 0 or outside the frame is not read.

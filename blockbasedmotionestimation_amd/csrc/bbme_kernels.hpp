@@ -3179,9 +3179,10 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
 // k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate, K12b k_subpel_interpolate_bgr, K13
-// k_subpel_temporal_filter and K13b k_subpel_temporal_filter_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_subpel_temporal_filter, K13b k_subpel_temporal_filter_bgr, K14 k_compose_cells and K15 k_wide_temporal_filter.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
-// runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window.
+// runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window (K14
+// two of them, K15 six: two quadruples).
 // =======================================================================================
 
 // Run split: run r (0 .. RPL - 1) of this lane is run gather_index<RPL>(r) of the plane's runs -- past the last one the lane is
@@ -4979,6 +4980,221 @@ __global__ __launch_bounds__(256) void k_subpel_temporal_filter_bgr(TfSpBgrArgs 
     if (!a.partial) return;
     __shared__ uint32_t part[4][4];
     store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
+}
+
+// =======================================================================================
+// K14.  Composition of two cell grids (the CELL COMPOSITION RULE of include/bbme.h): cell (cx, cy) of A with vector a lands at
+// t = ((2 cx, 2 cy) << u) + a, looks up B at the cell c' whose origin is nearest (ties upward, clamped into the grid) and gets
+// sat16(a + B[c']).  Layout is K6's and K9's: the shared split of runs of 4 cells (gather_index / gather_split), A by load_mv4
+// (rows a_pitch cells apart), B as one dword gather per cell (rows b_pitch apart), the four results as one 16-byte store where the
+// run is whole and its address 16-byte aligned (a caller's rows need not be), word by word otherwise.  blockIdx.z = the frame of a
+// run: A, B and the output each base + z stride (words), so that one launch composes every slot of a chain; blockIdx.y is 1 (the
+// composition exists on chains only, which have one row of pairs).
+// No index leaves the grid for any int16: |t| <= 2^16 + 2^15 in 32 bits, c' is clamped before it is used.
+// Statistics over the window in cells: cells whose c' was clamped, cells that saturated; a lane holds at most 4 RPL of each
+// (store_partial4 with two idle words, frame = z, then k_mc_reduce: no atomics).
+// A template, as K12b: a template's code lies behind the estimate's template kernels in the code object, a plain kernel's before.
+// =======================================================================================
+struct CmpArgs {
+    const mv_t *a, *b;                    // cw entries per row, rows a_pitch / b_pitch cells apart
+    mv_t *out;                            // rows out_pitch cells apart, or null
+    unsigned long long *partial;          // per frame and workgroup {clamped, saturated, 0, 0}; or null
+    long long a_z, b_z;                   // words from frame to frame
+    size_t out_stride;                    // words from frame to frame
+    int cw, ch, a_pitch, b_pitch, out_pitch, ushift;
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kCmpRunsPerLane = 2;
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_compose_cells(CmpArgs a)
+{
+    const long long z = blockIdx.z;
+    const mv_t *A = a.a + z * a.a_z, *B = a.b + z * a.b_z;
+    const int CW = a.cw, CH = a.ch, u = a.ushift, half = 1 << u;
+    uint32_t nclamp = 0, nsat = 0;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        uint32_t m[4], o[4] = {0, 0, 0, 0};
+        load_mv4(A + (size_t)cy * a.a_pitch + x0, n, m);
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ax = mv_x(m[j]), ay = mv_y(m[j]);
+            const int px = (((2 * (x0 + j)) << u) + ax + half) >> (u + 1), py = (((2 * cy) << u) + ay + half) >> (u + 1);
+            const int qx = min(max(px, 0), CW - 1), qy = min(max(py, 0), CH - 1);
+            const mv_t e = B[(size_t)qy * a.b_pitch + qx];
+            const int sx = ax + mv_x(e), sy = ay + mv_y(e);
+            const int rx = min(max(sx, -32768), 32767), ry = min(max(sy, -32768), 32767);
+            o[j] = mv_pack(rx, ry);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                nclamp += (qx != px) | (qy != py);
+                nsat += (rx != sx) | (ry != sy);
+            }
+        }
+        if (a.out) {
+            mv_t *dst = a.out + blockIdx.z * a.out_stride + (size_t)cy * a.out_pitch + x0;
+            if (n == 4 && ((uintptr_t)dst & 15u) == 0) *reinterpret_cast<uint4 *>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+            else for (int j = 0; j < n; ++j) dst[j] = o[j];
+        }
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, blockIdx.z, part, nclamp, nsat, 0u, 0u);
+}
+
+// =======================================================================================
+// K15.  Motion-compensated temporal filter over TWO frames on each side (the WIDE TEMPORAL FILTER RULE of include/bbme.h): K13
+// with up to four neighbours, k = 0 .. 3 = P1, N1, P2, N2, each a plane x[k] with a quarter-pel grid g[k] on C.  Each neighbour's
+// validity, samples, cost and weight are K13's (stf_weight, si_cell), independent of the others; S = 8 + sum w_k (8..40) and
+// out = (8 C + sum w_k X'_k + S / 2) / S.
+// Layout is K13's: the shared split of runs of 4 cells (gather_index / gather_split), the grids by load_mv4 (rows q4_pitch cells
+// apart), C as one 8-byte load per plane row, the two pixel rows stored as two dwords each (bytes where a caller's row is not
+// dword-aligned or the run is cut).  The weight map is one uint16 per cell, w_k << 4 k: one aligned 8-byte store where the run is
+// whole and its address 8-byte aligned, uint16 by uint16 otherwise.
+// blockIdx.z = the frame of a run; every plane is addressed base + z plane_z (bytes) and every grid base + z g_z (words).  Frame z
+// of a run of gridDim.z has min(2, z + first_prev) previous and min(2, gridDim.z - 1 - z + last_next) next neighbours: P1 / N1
+// are read when that is >= 1, P2 / N2 when it is 2, and only where x[k] is not null.  One launch so serves the slots of a chain
+// (first_prev, last_next = how many slots the chain has before the first and after the last frame of the run, at most 2) as well
+// as a caller's single frame (both 2: the null pointers alone decide).
+// The division by thr is K9's; the one by S is K9's multiply-shift with magic = floor(2^32 / S) + 1 = (2^32 + e) / S, 0 < e <= S:
+// umulhi(n, magic) = floor(n / S) for n e < 2^32, and here n <= 255 * 40 + 20 = 10220, e <= 40.  The 33 magics of S = 8..40 come
+// with the arguments and are read from LDS.
+// Statistics: six counters in 32 bits per lane (at most 4 RPL cells: a count each, a weight sum <= 32, a change <= 1020), through
+// shuffles to two partial quadruples per workgroup (store_partial4, frames 2 z and 2 z + 1: {w_0 > 0, .. w_3 > 0} and {weights,
+// |out - C|, 0, 0}), then k_mc_reduce over 2 gridDim.z quadruples: no atomics.
+// A template, as K12b and K13.
+// =======================================================================================
+struct WtfArgs {
+    const uint8_t *cur;                   // level-0 padded plane, pitch = width
+    const uint8_t *x[4];                  // P1, N1, P2, N2; null = no such neighbour at all
+    const mv_t *g[4];                     // their quarter-pel grids on C: cw entries per row, rows q4_pitch cells apart
+    uint8_t *out;                         // frames (rows out_pitch, frames out_stride bytes apart), or null
+    uint16_t *wmap;                       // one uint16 per cell (rows wmap_pitch uint16 apart; one-frame launches only), or null
+    unsigned long long *partial;          // per frame and workgroup, two quadruples; or null
+    long long plane_z, g_z;               // from frame to frame: bytes, words
+    size_t out_stride;
+    int width, height, cw, ch, thr, out_pitch, wmap_pitch, q4_pitch;
+    int first_prev, last_next;            // 0..2
+    uint32_t magic_thr;                   // floor(2^32 / thr) + 1; not used at thr = 1
+    uint32_t magic_s[33];                 // floor(2^32 / S) + 1 for S = 8..40
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
+{
+    __shared__ uint32_t magic_s[33];
+    if (threadIdx.x < 33) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
+    __syncthreads();
+    const long long z = blockIdx.z;
+    const int prevs = min(2, (int)blockIdx.z + a.first_prev), nexts = min(2, (int)(gridDim.z - 1 - blockIdx.z) + a.last_next);
+    const uint8_t *C = a.cur + z * a.plane_z;
+    const uint8_t *X[4];
+    const mv_t *Q[4];
+    bool has[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        has[k] = a.x[k] && ((k & 1) ? nexts : prevs) > (k >> 1);
+        X[k] = has[k] ? a.x[k] + z * a.plane_z : nullptr;
+        Q[k] = has[k] ? a.g[k] + z * a.g_z : nullptr;
+    }
+    const int W = a.width, H = a.height, CW = a.cw;
+    const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
+    uint32_t cnt[4] = {0, 0, 0, 0}, wsum = 0, dsum = 0;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        const int oy = 2 * cy;
+        const size_t g0 = (size_t)cy * a.q4_pitch + x0, o0 = (size_t)oy * W + 2 * x0;
+        uint32_t g[4][4] = {}, c[4] = {0, 0, 0, 0};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (has[k]) load_mv4(Q[k] + g0, n, g[k]);
+        if (n == 4) {
+            const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(C + o0), v = *reinterpret_cast<const ua_u32x2 *>(C + o0 + W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int sh = 16 * (j & 1);
+                c[j] = ((t.v[j >> 1] >> sh) & 0xffffu) | ((v.v[j >> 1] >> sh) << 16);
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= n) continue;
+                c[j] = ip_cell(C, W, 2 * (x0 + j), oy);
+            }
+        }
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ws[2] = {0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox = 2 * (x0 + j);
+            uint32_t w[4], q[4], wt = 0, wm = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                q[k] = 0;
+                w[k] = has[k] ? stf_weight(X[k], W, H, ox, oy, g[k][j], c[j], thr, magic_thr, &q[k]) : 0u;
+                wt += w[k];
+                wm |= w[k] << (4 * k);
+            }
+            const uint32_t S = 8u + wt, m = magic_s[wt], half = S >> 1;
+            uint32_t px = 0;
+#pragma unroll
+            for (int p = 0; p < 4; ++p) {
+                uint32_t num = 8u * ((c[j] >> (8 * p)) & 0xffu) + half;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) num += w[k] * ((q[k] >> (8 * p)) & 0xffu);
+                px |= __umulhi(num, m) << (8 * p);
+            }
+            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
+            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            ws[j >> 1] |= wm << (16 * (j & 1));
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) cnt[k] += w[k] != 0u;
+                wsum += wt;
+                dsum += __builtin_amdgcn_sad_u8(px, c[j], 0u);
+            }
+        }
+        if (a.out) {
+            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                const uint32_t *row = yy ? row1 : row0;
+                uint8_t *d = o + (size_t)yy * a.out_pitch;
+                if (n == 4 && ((uintptr_t)d & 3u) == 0) {
+                    reinterpret_cast<uint32_t *>(d)[0] = row[0];
+                    reinterpret_cast<uint32_t *>(d)[1] = row[1];
+                } else {
+                    for (int x = 0; x < 2 * n; ++x) d[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+                }
+            }
+        }
+        if (a.wmap) {
+            uint16_t *d = a.wmap + (size_t)cy * a.wmap_pitch + x0;
+            if (n == 4 && ((uintptr_t)d & 7u) == 0) *reinterpret_cast<uint2 *>(d) = make_uint2(ws[0], ws[1]);
+            else for (int j = 0; j < n; ++j) d[j] = (uint16_t)(ws[j >> 1] >> (16 * (j & 1)));
+        }
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[2][4][4];
+    store_partial4(a.partial, 2 * (size_t)blockIdx.z, part[0], cnt[0], cnt[1], cnt[2], cnt[3]);
+    store_partial4(a.partial, 2 * (size_t)blockIdx.z + 1, part[1], wsum, dsum, 0u, 0u);
 }
 
 }  // namespace bbme

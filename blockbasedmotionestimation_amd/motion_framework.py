@@ -24,6 +24,9 @@ from . import _capi
 DIR_FORWARD, DIR_BACKWARD = 0, 1                           # bbme_set_direction, `which` of the consistency calls
 FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE = 0, 1, 2      # classes of a consistency mask
 INTERPOLATION_STAT_KEYS = ("forward", "backward", "zero", "cost")      # the hypothesis a cell selected (0, 1, 2), their SADs
+# cells with w_k > 0 for P1, N1, P2, N2, sum of all weights, sum |out - C|
+WIDE_STAT_KEYS = ("prev1_cells", "next1_cells", "prev2_cells", "next2_cells", "weight", "change")
+COMPOSE_STAT_KEYS = ("clamped", "saturated")    # cells whose target cell was clamped into the grid, cells that saturated
 TEMPORAL_STAT_KEYS = ("prev_cells", "next_cells", "weight", "change")  # cells with wP > 0, with wN > 0, sum of weights, sum |out - C|
 
 
@@ -38,6 +41,11 @@ def _ptr(t):
     if t is None:
         return C.c_void_p(0)
     return C.c_void_p(t.data_ptr() if hasattr(t, "data_ptr") else t.ctypes.data)
+
+
+def _ptr4(items):
+    """Four addresses as the pointer array of a C entry point (the wide temporal filter's planes and grids); None is null."""
+    return (C.c_void_p * 4)(*[_ptr(t).value for t in items])
 
 
 def _window(window):
@@ -1087,6 +1095,74 @@ class MF:
             _ptr(weights), weights.stride(0) if weights is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
         return out, weights, stats
 
+    # -- two frames on each side (the CELL COMPOSITION RULE and the WIDE TEMPORAL FILTER RULE of include/bbme.h) ----------------
+    def _check_grid_tensor(self, t, what, name):
+        """An int16 CUDA tensor (CH, CW, 2) of packed cells whose rows lie a whole number of cells apart -> that pitch in cells"""
+        import torch
+        ch, cw = self.cells_shape
+        if not (t.is_cuda and t.dtype == torch.int16 and tuple(t.shape) == (ch, cw, 2) and t.stride(2) == 1 and t.stride(1) == 2
+                and t.stride(0) >= 2 * cw and t.stride(0) % 2 == 0 and t.data_ptr() % 4 == 0):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: %s must be an int16 CUDA tensor of shape (%d, %d, 2) with packed cells and "
+                                  "rows a whole number of cells apart" % (what, name, ch, cw))
+        return t.stride(0) // 2
+
+    def cells_compose_device(self, a, b, unit_shift=0, out=None, stats=None, window=None, stream=None):
+        """The cell composition rule on any two grids in HBM: a (on X into Y) and b (on Y into Z) int16 CUDA tensors (CH, CW, 2),
+        strided row views welcome; unit_shift 0 for pixels, 2 for quarter pels.  out: an int16 tensor of that shape that overlaps
+        neither input, stats: an int64 or uint64 tensor of 2 (clamped, saturated over `window`), each optional, not both.  On
+        the given HIP stream handle (default: the context's), ordered behind the context's stream; no host wait.  Needs neither
+        frames nor an estimate."""
+        import torch
+        what = "cells_compose_device"
+        pa, pb = self._check_grid_tensor(a, what, "a"), self._check_grid_tensor(b, what, "b")
+        po = self._check_grid_tensor(out, what, "out") if out is not None else 0
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 2
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 2" % what)
+        self._behind_torch(a, b, out, stats)
+        _capi.check(self._lib.bbme_cells_compose_device(self._ctx, _ptr(a), pa, _ptr(b), pb, int(unit_shift), _window(window), _ptr(out),
+                                                        po, _ptr(stats), C.c_void_p(stream or 0)))
+        return out, stats
+
+    def cells_temporal_filter_wide_device(self, cur, planes, grids, strength=64, out=None, weights=None, stats=None, window=None,
+                                          stream=None):
+        """The wide temporal filter rule on any planes and quarter-pel grids in HBM: cur a contiguous uint8 CUDA tensor
+        (H_pad, W_pad); planes and grids sequences of four, P1, N1, P2, N2, None = absent: planes as cur, grids int16 (CH, CW, 2)
+        on cur with one common row pitch (strided row views welcome).  out uint8 (H_pad, W_pad), weights int16 or uint16 (CH, CW)
+        holding w_k << 4 k, both with unit column stride, stats an int64 or uint64 tensor of 6, each optional, not all three.  On
+        the given HIP stream handle (default: the context's), ordered behind the context's stream; no host wait.  Needs neither
+        frames nor an estimate."""
+        import torch
+        what = "cells_temporal_filter_wide_device"
+        ch, cw = self.cells_shape
+        h, w = self.padded_height, self.padded_width
+        planes, grids = list(planes), list(grids)
+        if len(planes) != 4 or len(grids) != 4:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: planes and grids are sequences of four (None = absent)" % what)
+        for t in [cur] + planes:
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: planes must be contiguous uint8 CUDA tensors of shape (%d, %d)"
+                                      % (what, h, w))
+        pitches = {self._check_grid_tensor(t, what, "a grid") for t in grids if t is not None}
+        if len(pitches) > 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: the grids' rows must lie a common number of cells apart" % what)
+        if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w) and out.stride(1) == 1):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape (%d, %d) with unit column stride"
+                                  % (what, h, w))
+        if weights is not None and not (weights.is_cuda and weights.dtype in (torch.int16, torch.uint16) and tuple(weights.shape) == (ch, cw)
+                                        and weights.stride(1) == 1):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: weights must be an int16 or uint16 CUDA tensor of shape (%d, %d) with unit "
+                                  "column stride" % (what, ch, cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 6
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 6" % what)
+        self._behind_torch(cur, *planes, *grids, out, weights, stats)
+        _capi.check(self._lib.bbme_cells_wide_temporal_filter_device(
+            self._ctx, _ptr4(planes), _ptr(cur), _ptr4(grids), pitches.pop() if pitches else cw, int(strength), _window(window),
+            _ptr(out), out.stride(0) if out is not None else 0, _ptr(weights), weights.stride(0) if weights is not None else 0,
+            _ptr(stats), C.c_void_p(stream or 0)))
+        return out, weights, stats
+
     def frame_bgr_tensor(self, pair=0, which=0):
         """The stored colour frame `which` of `pair` in HBM (bbme_bgr_frames_device_pair) as a (H, W, 3) uint8 torch view; on an
         MFChain slot pair + which.  BbmeError (ERR_STATE) unless both frames of the pair have colour.  Read it only."""
@@ -1488,6 +1564,50 @@ class MFChain(MFBatch):
         filtered from one launch -> (count, H, W, 3) uint8, unpadded."""
         return self._temporal_filter_run(strength, first, count, "temporal_filter_run_bgr", True)
 
+    # -- two frames on each side (the CELL COMPOSITION RULE and the WIDE TEMPORAL FILTER RULE of include/bbme.h) ----------------
+    def composed_cells(self, f, side):
+        """The integer grid on slot f into slot f + 2 (side = +1: the forward cells of pair f composed with those of pair f + 1)
+        or into slot f - 2 (side = -1: the backward cells of pair f - 1 with those of pair f - 2), after
+        estimate_bidirectional_async -> (CH, CW, 2) int16."""
+        import torch
+        ch, cw = self.cells_shape
+        out = torch.empty((ch, cw, 2), dtype=torch.int16, device="cuda:%d" % self.device)
+        self._behind_torch(out)
+        _capi.check(self._lib.bbme_compose_chain_device(self._ctx, int(f), 1, int(side), _ptr(out), cw, 0, None))
+        self.synchronize()
+        return out.cpu().numpy()
+
+    def temporal_filter_run_wide(self, strength, first=0, count=None):
+        """Slots first .. first + count - 1 (default: to the last) filtered over two frames on each side, as far as the chain
+        has them (the wide temporal filter rule): the grids into slots f +- 1 are temporal_filter_run_subpel's, those into slots
+        f +- 2 composed_cells refined against the real frame pair; one filter launch -> (count, H_pad, W_pad) uint8."""
+        import torch
+        first = int(first)
+        count = self.batch + 1 - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.batch + 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_run_wide: slots %d .. %d of a chain of %d"
+                                  % (first, first + count - 1, self.batch + 1))
+        frames = torch.empty((count,) + self._out_shape(False), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._behind_torch(frames)
+        _capi.check(self._lib.bbme_wide_temporal_filter_chain_device(self._ctx, first, count, int(strength), _ptr(frames),
+                                                                     frames.stride(1), frames.stride(0), None))
+        self.synchronize()
+        return frames.cpu().numpy()
+
+    def get_frame_filtered_wide(self, f, strength, out=None):
+        """Slot f alone as temporal_filter_run_wide filters it -> the padded (H_pad, W_pad) uint8 plane."""
+        out = _host_out(out, self._out_shape(False), np.uint8, "get_frame_filtered_wide")
+        _capi.check(self._lib.bbme_get_wide_temporal_filtered_host(self._ctx, int(f), int(strength), out.ctypes.data))
+        return out
+
+    def temporal_filter_wide_stats(self, strength, window=None):
+        """One dict(prev1_cells, next1_cells, prev2_cells, next2_cells, weight, change) per slot of the chain over `window` in
+        cells, from one filter launch."""
+        slots = self.batch + 1
+        s = (C.c_ulonglong * (6 * slots))()
+        _capi.check(self._lib.bbme_wide_temporal_filter_stats(self._ctx, int(strength), self._stats_window(window), s))
+        return [dict(zip(WIDE_STAT_KEYS, s[6 * f:6 * f + 6])) for f in range(slots)]
+
     def get_slot_plane(self, level, slot):
         """The padded plane of frame slot `slot` at `level` (bbme_get_chain_plane_host) -> (level height, level width) uint8."""
         w, h, _, _ = self.level_geometry(level)
@@ -1696,6 +1816,62 @@ def temporal_filter_cells_subpel(cur, prev=None, next=None, q_to_prev=None, q_to
     q_to_prev, q_to_next int16 (H / 2, W / 2, 2) QUARTER-PEL grids on cur (what subpel_cells returns; any int16), each neighbour's
     2x2 cell sampled bilinearly at its quarter-pel position -> the same three results."""
     return _temporal_filter_cells("temporal_filter_cells_subpel", cur, prev, next, q_to_prev, q_to_next, strength, window, subpel=True)
+
+
+def _grid_rows(grid, shape, what):
+    """An int16 (CH, CW, 2) grid as the host rules read it -> (array, row pitch in cells): a view whose cells are packed and whose
+    rows lie a whole number of cells apart stays as it is, anything else is copied packed."""
+    grid = np.asarray(grid)
+    if grid.shape != shape:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: int16 grids of shape %s" % (what, shape))
+    if not (grid.dtype == np.int16 and grid.strides[1:] == (4, 2) and grid.strides[0] % 4 == 0 and grid.strides[0] >= 4 * shape[1]):
+        grid = np.ascontiguousarray(grid, np.int16)
+    return grid, grid.strides[0] // 4
+
+
+def compose_cells(a, b, unit_shift=0, window=None):
+    """The cell composition rule of include/bbme.h on the CPU (bbme_compose_host): a (on frame X into Y) and b (on Y into Z) int16
+    (CH, CW, 2) grids, strided row views welcome, unit_shift 0 for pixels or 2 for quarter pels -> (the grid on X into Z
+    (CH, CW, 2) int16, dict(clamped, saturated) over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    what = "compose_cells"
+    shape = np.shape(a)
+    if len(shape) != 3 or shape[2] != 2 or shape[0] < 1 or shape[1] < 1:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: int16 grids of one shape (CH, CW, 2)" % what)
+    a, pa = _grid_rows(a, shape, what)
+    b, pb = _grid_rows(b, shape, what)
+    out = np.empty(shape, np.int16)
+    s = (C.c_ulonglong * 2)()
+    _capi.check(_capi.lib().bbme_compose_host(a.ctypes.data, pa, b.ctypes.data, pb, shape[1], shape[0], int(unit_shift), _window(window),
+                                              out.ctypes.data, shape[1], s))
+    return out, dict(zip(COMPOSE_STAT_KEYS, list(s)))
+
+
+def temporal_filter_cells_wide(cur, planes, grids, strength=64, window=None):
+    """The wide temporal filter rule of include/bbme.h on the CPU (bbme_wide_temporal_filter_host): cur a uint8 (H, W) plane of even
+    size; planes and grids sequences of four, P1, N1, P2, N2, None = absent: uint8 (H, W) planes and int16 (H / 2, W / 2, 2)
+    QUARTER-PEL grids on cur (strided row views of one common pitch stay as they are) -> (frame (H, W) uint8, weights
+    (H / 2, W / 2) uint16 holding w_k << 4 k, dict(prev1_cells, next1_cells, prev2_cells, next2_cells, weight, change) over
+    window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    what = "temporal_filter_cells_wide"
+    cur = np.ascontiguousarray(cur, np.uint8)
+    planes, grids = list(planes), list(grids)
+    if cur.ndim != 2 or len(planes) != 4 or len(grids) != 4:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: a uint8 (H, W) plane, four planes and four grids (None = absent)" % what)
+    h, w = cur.shape
+    planes = [None if p is None else np.ascontiguousarray(p, np.uint8) for p in planes]
+    if any(p is not None and p.shape != cur.shape for p in planes):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: uint8 planes of one shape (H, W)" % what)
+    rows = [None if g is None else _grid_rows(g, (h // 2, w // 2, 2), what) for g in grids]
+    if len({r[1] for r in rows if r is not None}) > 1:                 # no common pitch: packed copies have one
+        rows = [None if r is None else (np.ascontiguousarray(r[0]), w // 2) for r in rows]
+    grids = [None if r is None else r[0] for r in rows]
+    pitch = next((r[1] for r in rows if r is not None), w // 2)
+    out = np.empty(cur.shape, np.uint8)
+    wmap = np.empty((h // 2, w // 2), np.uint16)
+    s = (C.c_ulonglong * 6)()
+    _capi.check(_capi.lib().bbme_wide_temporal_filter_host(_ptr4(planes), cur.ctypes.data, w, h, _ptr4(grids), pitch, int(strength),
+                                                           _window(window), out.ctypes.data, wmap.ctypes.data, s))
+    return out, wmap, dict(zip(WIDE_STAT_KEYS, list(s)))
 
 
 def temporal_filter_cells_bgr(cur, prev=None, next=None, to_prev=None, to_next=None, strength=64, pad_x=0, pad_y=0, window=None):

@@ -514,6 +514,51 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
     return out
 
 
+def denoise_frames_wide(frames, search_size, block_size, strength, device=None, window=8):
+    """Motion-compensated temporal denoising of a grey video on ONE GPU over TWO frames on each side (the wide temporal filter rule
+    of include/bbme.h): every frame averaged with up to four motion-aligned neighbours, along quarter-pel vectors, wherever their
+    2x2 cells match better than `strength` -> len(frames) unpadded uint8 (H, W) frames.  The video is cut into runs of `window`
+    output frames a .. a + window - 1.  Each run gets a bidirectional chain estimate of its own over its frames plus two on
+    either side, where the video has them (MFChain over frames a - 2 .. a + window + 1), and one MFChain.temporal_filter_run_wide
+    over its output slots: every frame is therefore filtered from every neighbour that exists, the frames at a run's ends
+    included, and a run needs nothing from another.  The price: the four pairs of a run that lie outside its own frames -- (a - 2,
+    a - 1), (a - 1, a), (a + window - 1, a + window) and (a + window, a + window + 1) -- are estimated by the neighbouring run
+    as well, so a video of many runs costs window + 3 pair estimates per window frames.  Runs of one length share a context.
+    A colour video is BbmeError (ERR_UNSUPPORTED): the rule is grey.  denoise_frames is the filter over one frame on each side."""
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if frames and frames[0].ndim == 3:
+        raise _capi.BbmeError(_capi.ERR_UNSUPPORTED, "denoise_frames_wide: a colour video: the wide temporal filter rule is grey")
+    window = int(window)
+    if window < 1:
+        raise ValueError("denoise_frames_wide: window must be at least 1")
+    n = len(frames)
+    if n < 2:
+        return frames
+    if device is None:
+        device = local_device()
+    from .motion_framework import MFChain
+    out = [None] * n
+    chains = {}                                            # frames of a chain -> its context
+    try:
+        for a in range(0, n, window):
+            b = min(a + window, n)
+            lo, hi = max(a - 2, 0), min(b + 2, n)
+            run = frames[lo:hi]
+            mf = chains.get(len(run))
+            if mf is None:
+                mf = chains[len(run)] = MFChain(run, search_size, block_size, device=device)
+            else:
+                mf.set_frame_run(0, run)
+            mf.estimate_bidirectional_async()
+            h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
+            for q, plane in enumerate(mf.temporal_filter_run_wide(int(strength), a - lo, b - a)):
+                out[a + q] = np.ascontiguousarray(plane[py:py + h, px:px + w])
+    finally:
+        for mf in chains.values():
+            mf.close()
+    return out
+
+
 def colorize_frames(frames, search_size, block_size, maxmotion=-1.0, scale=1, in_flight=4, batch=2, device=None):
     """The colour-coded forward field of the len(frames) - 1 consecutive pairs of a video on ONE GPU (the colour rule of
     include/bbme.h at subsampling `scale`): -> ((P, oh, ow, 3) uint8 B,G,R images, (P, 5) float32 ranges (max radius, min u,

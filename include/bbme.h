@@ -1071,6 +1071,84 @@ int bbme_subpel_temporal_filter_bgr_chain_device(bbme_ctx *ctx, int first, int c
 int bbme_get_subpel_temporal_filtered_bgr_host(bbme_ctx *ctx, int pair, int which, int thr, uint8_t *out);
 int bbme_subpel_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 
+/* CELL COMPOSITION RULE (this project's own): the field from frame X into frame Z, two frames on, from the field of X into Y and
+ * the field of Y into Z.  Inputs: grid A on X into Y and grid B on Y into Z, both CH x CW int16 (x, y) pairs, rows a_pitch_cells
+ * and b_pitch_cells pairs apart; a unit shift u, 0 (the vectors are pixels) or 2 (quarter pels).  Any int16 is allowed.  All
+ * arithmetic is in 32-bit integers, `>>` of a negative number is the arithmetic shift.
+ * For cell (cx, cy) with a = A[cy][cx]:
+ *   t  = ((2 cx, 2 cy) << u) + a                                   where the cell's origin lands in Y, in the vectors' unit;
+ *   c' = ((t.x + (1 << u)) >> (u + 1), (t.y + (1 << u)) >> (u + 1)) the cell of Y whose origin is nearest, ties upward;
+ *   c' is clamped to 0 .. CW - 1 and 0 .. CH - 1: no index leaves the grid;
+ *   out[cy][cx] = sat16(a + B[c']), each component saturated to -32768 .. 32767.
+ * Two statistics over a window in cells: cells whose c' was clamped (in either coordinate), cells that saturated (in either
+ * component).
+ * Properties.  (1) B = 0 gives A; A = 0 gives B.  (2) With u = 2, A = 4 GA and B = 4 GB the result is 4 x the result of u = 0 on GA
+ * and GB wherever neither saturates (c' is the same cell).  (3) Any int16 is legal.
+ * The composed grid is an INTEGER guess of a distance-2 field: the WIDE TEMPORAL FILTER RULE's context calls refine it by the
+ * SUBPEL RULE against the real frame pair before they use it.
+ * Errors: BBME_ERR_INVALID for a null context or required pointer, a pitch < CW, u not 0 or 2, a window as for the consistency
+ * rule, an output that overlaps an input, slots or a side without a composition; BBME_ERR_UNSUPPORTED for
+ * bbme_compose_chain_device off a chain; BBME_ERR_STATE for it without frames and a valid bidirectional estimate.  None of these
+ * calls changes context state; the statistics scratch is their own.
+ * bbme_compose_host: the rule on the CPU, no GPU; out (rows out_pitch_cells pairs apart) and stats2 each may be NULL, not both.
+ * bbme_cells_compose_device: ANY two grids in HBM of the context's cell geometry, on hip_stream (NULL = the context's), ordered
+ * behind the context's stream; no host wait.  d_out must not overlap d_a or d_b.
+ * bbme_compose_chain_device: chain contexts only, after bbme_estimate_bidirectional; ONE launch, the frame a grid dimension, for
+ * slots first .. first + count - 1, slot first + q at d_out + q out_stride_cells pairs.  side = +1: for slot f the grid into slot
+ * f + 2, compose(forward cells of pair f, forward cells of pair f + 1), u = 0; every slot must be <= the last slot - 2.
+ * side = -1: the grid into slot f - 2, compose(backward cells of pair f - 1, backward cells of pair f - 2); every slot >= 2. */
+int bbme_compose_host(const int16_t *a, int a_pitch_cells, const int16_t *b, int b_pitch_cells, int cells_w, int cells_h,
+                      int unit_shift, const int *window, int16_t *out, int out_pitch_cells, unsigned long long *stats2);
+int bbme_cells_compose_device(bbme_ctx *ctx, const int16_t *d_a, int a_pitch_cells, const int16_t *d_b, int b_pitch_cells,
+                              int unit_shift, const int *window, int16_t *d_out, int out_pitch_cells, unsigned long long *d_stats2,
+                              void *hip_stream);
+int bbme_compose_chain_device(bbme_ctx *ctx, int first, int count, int side, int16_t *d_out, int out_pitch_cells,
+                              size_t out_stride_cells, void *hip_stream);
+
+/* WIDE TEMPORAL FILTER RULE (this project's own): the SUBPEL TEMPORAL FILTER RULE with up to FOUR neighbours, two frames on each
+ * side.  Neighbour k = 0 .. 3 is P1 (the previous frame), N1 (the next), P2 (two back), N2 (two on): a packed W0 x H0 plane X_k
+ * and a quarter-pel grid Q_k on C into X_k (CH x CW int16 pairs, rows q4_pitch_cells pairs apart, one pitch for all; any int16).
+ * A neighbour is present when both its plane and its grid are given; at least one must be present.  Grey planes only.
+ * Each neighbour's validity, rounded samples X'_k, cost and weight w_k (0..8) are exactly the SUBPEL TEMPORAL FILTER RULE's, each
+ * independent of the other neighbours.  With S = 8 + sum of w_k (8..40),
+ *   out[o + (j, k)] = (8 C[o + (j, k)] + sum over k of w_k X'_k[j, k] + S / 2) / S         the numerator is at most 10220.
+ * The weight map is one uint16 per cell, w_0 | w_1 << 4 | w_2 << 8 | w_3 << 12.  Six statistics over a window in cells: cells
+ * with w_k > 0 for k = 0 .. 3, the sum of all weights, the sum of |out - C|.
+ * Properties.  (1) With neighbours 2 and 3 absent the frame, the low byte of the map and statistics 0, 1, 4, 5 are the SUBPEL
+ * TEMPORAL FILTER RULE's, bit for bit; with 4 x integer grids therefore the TEMPORAL FILTER RULE's.  (2) Equal planes and zero
+ * grids leave the frame unchanged, every present weight 8.  (3) Exchanging two neighbours' (plane, grid) exchanges their nibbles
+ * and their counters and nothing else.
+ * On a CHAIN context with its own fields slot f uses, as far as the chain has them, slots f - 1 and f + 1 with the grids the
+ * SUBPEL TEMPORAL FILTER RULE's calls use, and slots f - 2 and f + 2 with the grids of bbme_compose_chain_device; every grid is
+ * refined by the SUBPEL RULE (K10) against (slot f, slot f +- k) into quarter-pel buffers of the context's own, allocated at first
+ * use.  A colour context filters its luma planes.
+ * Errors: those of the SUBPEL TEMPORAL FILTER RULE's calls: BBME_ERR_INVALID for a null context or required pointer, a neighbour
+ * with only one of plane and grid, no neighbour, thr outside 1..1021, a pitch too small, a window, an output that overlaps an
+ * input plane, slots outside the chain; BBME_ERR_UNSUPPORTED for the four context-level calls off a chain or beyond W0 or H0
+ * 8188; BBME_ERR_STATE for those without frames and a valid bidirectional estimate.  None of these calls changes context state;
+ * the statistics scratch and the quarter-pel buffers are their own (the +-1 grids share the subpel temporal filter's buffer).
+ * The caller orders context-level calls that it issues on different streams.
+ * bbme_wide_temporal_filter_host: the rule on the CPU, no GPU; planes[k] / grids[k] NULL = absent; out, weights (packed, CW per
+ * row) and stats6 each may be NULL, not all three.
+ * bbme_cells_wide_temporal_filter_device: ANY planes and grids in HBM of the context's level-0 / cell geometry; d_out rows
+ * out_pitch bytes apart, d_weights rows weights_pitch uint16 apart; d_out, d_weights, d_stats6 each optional, not all three; on
+ * hip_stream (NULL = the context's), no host wait.
+ * bbme_wide_temporal_filter_chain_device: the composition, then the refinement launches, then ONE filter launch for slots first ..
+ * first + count - 1, frame q at d_out + q out_stride.
+ * bbme_get_wide_temporal_filtered_host: one slot as the chain call; synchronises; packed W0 x H0 bytes.
+ * bbme_wide_temporal_filter_stats: EVERY slot of the chain from one filter launch, stats[6 f + k]; synchronises. */
+int bbme_wide_temporal_filter_host(const uint8_t *const planes[4], const uint8_t *cur, int width, int height,
+                                   const int16_t *const grids[4], int q4_pitch_cells, int thr, const int *window, uint8_t *out,
+                                   uint16_t *weights, unsigned long long *stats6);
+int bbme_cells_wide_temporal_filter_device(bbme_ctx *ctx, const uint8_t *const d_planes[4], const uint8_t *d_cur,
+                                           const int16_t *const d_grids[4], int q4_pitch_cells, int thr, const int *window,
+                                           uint8_t *d_out, int out_pitch, uint16_t *d_weights, int weights_pitch,
+                                           unsigned long long *d_stats6, void *hip_stream);
+int bbme_wide_temporal_filter_chain_device(bbme_ctx *ctx, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                           size_t out_stride, void *hip_stream);
+int bbme_get_wide_temporal_filtered_host(bbme_ctx *ctx, int slot, int thr, uint8_t *out);
+int bbme_wide_temporal_filter_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
+
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
 /* copyMVs (:828-843) + calcLevelBM (:226-244) of one level.  Leaves that level's MV
