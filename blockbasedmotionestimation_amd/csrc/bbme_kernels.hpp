@@ -3182,7 +3182,17 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 // k_subpel_temporal_filter, K13b k_subpel_temporal_filter_bgr, K14 k_compose_cells and K15 k_wide_temporal_filter.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window (K14
-// two of them, K15 six: two quadruples).
+// two of them, K15 six: two quadruples).  The pieces, each written once below and used by every kernel that has the step:
+//   gather_index / gather_split   the run split
+//   load_mv4                      a run's four grid words
+//   load_cells4                   a run's own four 2x2 cells of a plane (ip_cell's packing)
+//   rows_put / store_rows2        a run's two grey pixel rows: a cell into them, the rows to memory
+//   bgr_load_rows / bgr_row_get / bgr_row_put / bgr_store_rows
+//                                 a run's two colour rows of 24 bytes: the run's own rows, a cell out of a row, a cell into a
+//                                 row, the rows to the unpadded frame
+//   store_bytes4                  one map byte per unit
+//   store_partial4                the statistics tail
+//   tf_frame / tf_cost_weight     the temporal filters' neighbour head and weight tail
 // =======================================================================================
 
 // Run split: run r (0 .. RPL - 1) of this lane is run gather_index<RPL>(r) of the plane's runs -- past the last one the lane is
@@ -3222,6 +3232,175 @@ __device__ __forceinline__ void store_bytes4(uint8_t *o, int n, uint32_t v)
 {
     if (n == 4 && ((uintptr_t)o & 3u) == 0) *reinterpret_cast<uint32_t *>(o) = v;
     else for (int j = 0; j < n; ++j) o[j] = (uint8_t)(v >> (8 * j));
+}
+
+// the 2x2 cell at (x, y) of a plane as one dword: row y in the low half, row y + 1 in the high half
+__device__ __forceinline__ uint32_t ip_cell(const uint8_t *img, int W, int x, int y)
+{
+    const uint8_t *p = img + (size_t)y * W + x;
+    return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)reinterpret_cast<const ua_u16 *>(p + W)->v << 16;
+}
+
+// bytes s.x, s.x + 1 and s.x + 1 + x1 of a row of I2 (p = the row's byte s.x) in bits 0-7, 8-15 and 16-23
+__device__ __forceinline__ uint32_t sc_row(const uint8_t *p, bool wide, int x1)
+{
+    if (wide) {
+        const uint32_t v = reinterpret_cast<const ua_u32 *>(p)->v;
+        return x1 ? v & 0x00ffffffu : (v & 0xffffu) | ((v & 0xff00u) << 8);
+    }
+    return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)p[1 + x1] << 16;
+}
+
+// The 2x2 cell of the SUBPEL RULE's samples of a plane at integer position (ix, iy) with the fractions (fx, fy), every tap of
+// non-zero weight inside the plane: row iy's two samples in the low half, row iy + 1's in the high half (as ip_cell)
+__device__ __forceinline__ uint32_t si_cell(const uint8_t *img, int W, int ix, int iy, int fx, int fy)
+{
+    const int x1 = fx != 0, y1 = fy != 0;
+    const uint8_t *p = img + (size_t)iy * W + ix;
+    const bool wide = ix + 4 <= W;
+    const uint32_t t0 = sc_row(p, wide, x1), t1 = sc_row(p + W, wide, x1), t2 = sc_row(p + (size_t)(1 + y1) * W, wide, x1);
+    const uint32_t wx = (uint32_t)fx, wy = (uint32_t)fy;
+    uint32_t h[3][2];                                         // (4 - fx) P0 + fx P1 of the three rows' two pixels, <= 1020
+    h[0][0] = (4u - wx) * (t0 & 0xffu) + wx * ((t0 >> 8) & 0xffu); h[0][1] = (4u - wx) * ((t0 >> 8) & 0xffu) + wx * (t0 >> 16);
+    h[1][0] = (4u - wx) * (t1 & 0xffu) + wx * ((t1 >> 8) & 0xffu); h[1][1] = (4u - wx) * ((t1 >> 8) & 0xffu) + wx * (t1 >> 16);
+    h[2][0] = (4u - wx) * (t2 & 0xffu) + wx * ((t2 >> 8) & 0xffu); h[2][1] = (4u - wx) * ((t2 >> 8) & 0xffu) + wx * (t2 >> 16);
+    uint32_t px = 0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) px |= (((4u - wy) * h[k][m] + wy * h[k + 1][m] + 8u) >> 4) << (16 * k + 8 * m);
+    return px;
+}
+
+// A run's own four cells of a plane, cells x0 .. x0 + 3 of the cell row whose upper pixel row is oy, each as ip_cell packs it: one
+// unaligned 8-byte load per pixel row when the run is whole, ip_cell for each of the n cells otherwise (the others 0).
+__device__ __forceinline__ void load_cells4(const uint8_t *img, int W, int oy, int x0, int n, uint32_t (&c)[4])
+{
+    if (n == 4) {
+        const uint8_t *p = img + (size_t)oy * W + 2 * x0;
+        const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(p), u = *reinterpret_cast<const ua_u32x2 *>(p + W);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int sh = 16 * (j & 1);
+            c[j] = ((t.v[j >> 1] >> sh) & 0xffffu) | ((u.v[j >> 1] >> sh) << 16);
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) c[j] = j < n ? ip_cell(img, W, 2 * (x0 + j), oy) : 0u;
+    }
+}
+
+// A run's two grey pixel rows, 8 bytes each in two dwords.  rows_put: cell j (ip_cell's packing) into them.  store_rows2: the
+// rows to o and o + pitch, each as two dwords when the run is whole and the row's address dword-aligned (a caller's rows need not
+// be), its 2 n bytes one by one otherwise.
+__device__ __forceinline__ void rows_put(uint32_t (&rows)[2][2], int j, uint32_t px)
+{
+    rows[0][j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
+    rows[1][j >> 1] |= (px >> 16) << (16 * (j & 1));
+}
+
+__device__ __forceinline__ void store_rows2(uint8_t *o, int pitch, int n, const uint32_t (&rows)[2][2])
+{
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+        const uint32_t *row = rows[y];
+        uint8_t *q = o + (size_t)y * pitch;
+        if (n == 4 && ((uintptr_t)q & 3u) == 0) {
+            reinterpret_cast<uint32_t *>(q)[0] = row[0];
+            reinterpret_cast<uint32_t *>(q)[1] = row[1];
+        } else {
+            for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
+        }
+    }
+}
+
+// A run's two colour rows: 8 pixels = 24 bytes a row in three 64-bit words, cell j's six bytes B,G,R,B,G,R at bytes 6 j .. 6 j + 5
+// (bit 48 j: cells 1 and 2 span two words).  The run starts at pixel (fx, fy) of the fw x fh frame and is `whole` when it has four
+// cells and its 8 pixels lie inside a frame row; with an odd padding cells straddle the frame's edge.
+__device__ __forceinline__ bool bgr_run_whole(int n, int fx, int fw) { return n == 4 && fx >= 0 && fx + 8 <= fw; }
+
+// a whole run's own rows, three unaligned 8-byte loads each (a row outside the frame stays as it is)
+__device__ __forceinline__ void bgr_load_rows(const uint8_t *img, int pitch, int fh, int fx, int fy, uint64_t (&rows)[2][3])
+{
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+        if (fy + y < 0 || fy + y >= fh) continue;
+        const uint8_t *q = img + (size_t)(fy + y) * pitch + (size_t)3 * fx;
+#pragma unroll
+        for (int d = 0; d < 3; ++d) rows[y][d] = reinterpret_cast<const ua_u64 *>(q)[d].v;
+    }
+}
+
+// cell j's six bytes of a row, from bit 0 up
+__device__ __forceinline__ uint64_t bgr_row_get(const uint64_t (&row)[3], int j)
+{
+    const int bit = 48 * j, wd = bit >> 6, sh = bit & 63;
+    uint64_t v = row[wd] >> sh;
+    if (sh > 16) v |= row[wd + 1] << (64 - sh);
+    return v & 0xffffffffffffull;
+}
+
+// six bytes into cell j's place of a row that holds 0 there
+__device__ __forceinline__ void bgr_row_put(uint64_t (&row)[3], int j, uint64_t px)
+{
+    const int bit = 48 * j, wd = bit >> 6, sh = bit & 63;
+    row[wd] |= px << sh;
+    if (sh > 16) row[wd + 1] |= px >> (64 - sh);
+}
+
+// The rows to the unpadded frame (rows `pitch` bytes apart): six dwords a row when the run is whole and the row's address
+// dword-aligned (an odd pad_x or a caller's odd pitch breaks that), otherwise byte by byte the pixels of the run's n cells that lie
+// inside the frame.  Rows outside the frame are not written.  `whole` is bgr_run_whole's answer: the
+// filters hold it for their loads, and found again in here it costs K9b a VGPR (57 against the parent's 56).
+__device__ __forceinline__ void bgr_store_rows(uint8_t *frame, int pitch, int fw, int fh, int fx, int fy, int n, bool whole,
+                                               const uint64_t (&rows)[2][3])
+{
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+        if (fy + y < 0 || fy + y >= fh) continue;
+        uint8_t *q = frame + (size_t)(fy + y) * pitch + (ptrdiff_t)3 * fx;
+        if (whole && ((uintptr_t)q & 3u) == 0) {
+            uint32_t *o = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+            for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[y][d >> 1] >> (32 * (d & 1)));
+        } else {
+#pragma unroll
+            for (int p = 0; p < 8; ++p) {
+                if (p >= 2 * n || fx + p < 0 || fx + p >= fw) continue;
+#pragma unroll
+                for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[y][k >> 3] >> (8 * (k & 7)));
+            }
+        }
+    }
+}
+
+// The temporal filters' head: frame (y, z) = blockIdx.y / z of a launch reads every input at base + y s_y + z s_z (bytes for
+// planes, words for grids).  Along z the first frame has its previous neighbour only with first_prev and the last its next one only
+// with last_next, so that one launch serves the frames of a chain (z = slot) as well as the 2 frames of every pair of a batch
+// (z = which).  A neighbour that is absent has null pointers.
+struct TfFrame { const uint8_t *C, *P, *N; const mv_t *GP, *GN; bool has_p, has_n; };
+
+template <class Args>
+__device__ __forceinline__ TfFrame tf_frame(const Args &a)
+{
+    const long long y = blockIdx.y, z = blockIdx.z;
+    TfFrame f;
+    f.C = a.cur + y * a.cur_y + z * a.cur_z;
+    f.has_p = a.prev && (z > 0 || a.first_prev);
+    f.has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
+    f.P = f.has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
+    f.N = f.has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
+    f.GP = f.has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr;
+    f.GN = f.has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    return f;
+}
+
+// The temporal filters' weight tail: w = 8 (thr - cost) / thr for a cost below thr, 0 otherwise.  The division is a multiply-shift
+// (see K9); cost 0 is weight 8 at every thr and all that passes at thr = 1, which has no 32-bit magic, so it is answered without it.
+__device__ __forceinline__ uint32_t tf_cost_weight(uint32_t cost, uint32_t thr, uint32_t magic_thr)
+{
+    if (cost >= thr) return 0u;
+    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;
 }
 
 // Statistics tail: the lane's four counters summed over its wave, the four waves' sums over the workgroup through `part`, and
@@ -3483,10 +3662,10 @@ __global__ __launch_bounds__(256) void k_fb_consistency(FbArgs a)
 // the 2x2 cell of I1 at p1 = origin - round(num v / den) and the one of I2 at p2 = p1 + v, is valid when both lie inside the
 // plane, and costs their SAD; the cheapest valid one (the earliest of equals) is blended, ((den - num) I1 + num I2 +
 // den / 2) / den.  A memory-bound gather: a lane takes a run of 4 consecutive cells of one cell row (fewer at the row's
-// end), so that F and B arrive as one 16-byte load each and the zero hypothesis as one 8-byte load per plane row; the moved
-// cells are unaligned u16 loads, two per cell and plane, packed into one dword per cell so that v_sad_u8 gives the cost in
-// one instruction.  A lane writes its 8 pixels of each of the two output rows as two dwords (bytes where a caller's row is
-// not dword-aligned or the run is cut by the row's end) and its selections as one dword.
+// end), so that F and B arrive as one 16-byte load each and the zero hypothesis as one 8-byte load per plane row
+// (load_cells4's text, kept in ip_load_run); the moved cells are unaligned u16 loads, two per cell and plane, packed into one dword per cell (ip_cell) so
+// that v_sad_u8 gives the cost in one instruction.  A lane writes its two output rows by store_rows2 and its selections as one
+// dword.
 // Divisions by den are multiply-shifts: with magic = floor(2^32 / den) + 1 = (2^32 + e) / den, 0 < e <= den,
 // umulhi(n, magic) = floor(n / den) for every n with n e < 2^32.  The blend's numerators stay below 255 * 256 + 128 and the
 // shifts', moved to n >= 0 by 32768 den (|num v| < 32768 den), below 2^24, and e <= 256.
@@ -3521,20 +3700,13 @@ struct IpArgs : IpCommon {
 
 constexpr int kIpRunsPerLane = 2;
 
-// the 2x2 cell at (x, y) of a plane as one dword: row y in the low half, row y + 1 in the high half
-__device__ __forceinline__ uint32_t ip_cell(const uint8_t *img, int W, int x, int y)
-{
-    const uint8_t *p = img + (size_t)y * W + x;
-    return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)reinterpret_cast<const ua_u16 *>(p + W)->v << 16;
-}
-
 // One run of a cell row, cells x0 .. x0 + n - 1 (n = 1..4) of row cy: the grids' entries and the cells of the zero hypothesis
 struct IpRun { uint32_t f[4], b[4], z1[4], z2[4]; };
 
 __device__ __forceinline__ IpRun ip_load_run(const uint8_t *img1, const uint8_t *img2, const mv_t *F, const mv_t *B, int W, int CW,
                                              int cy, int x0, int n)
 {
-    IpRun r;
+    IpRun r;                                                  // load_cells4's text, written out: through it K7b takes 43 VGPRs, not 42
     const int oy = 2 * cy;
     const size_t g0 = (size_t)cy * CW + x0, o0 = (size_t)oy * W + 2 * x0;
 #pragma unroll
@@ -3612,7 +3784,7 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
         const int oy = 2 * cy;
         const IpRun run = ip_load_run(img1, img2, F, B, W, CW, cy, x0, n);
         const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
-        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ks = 0;
+        uint32_t rows[2][2] = {{0, 0}, {0, 0}}, ks = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n) break;
@@ -3626,28 +3798,14 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
                 const uint32_t v = __umulhi(w1 * ((c1 >> (8 * q)) & 0xffu) + w2 * ((c2 >> (8 * q)) & 0xffu) + (uint32_t)half, magic);
                 px |= v << (8 * q);
             }
-            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
-            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            rows_put(rows, j, px);
             ks |= k << (8 * j);
             if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
                 n0 += k == 0u; n1 += k == 1u; n2 += k == 2u;
                 csum += cost;
             }
         }
-        if (a.out) {
-            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
-#pragma unroll
-            for (int y = 0; y < 2; ++y) {
-                const uint32_t *row = y ? row1 : row0;
-                uint8_t *q = o + (size_t)y * a.out_pitch;
-                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
-                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
-                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
-                } else {
-                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
-                }
-            }
-        }
+        if (a.out) store_rows2(a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0, a.out_pitch, n, rows);
         if (a.sel) store_bytes4(a.sel + blockIdx.z * a.sel_stride + (size_t)cy * a.sel_pitch + x0, n, ks);
     }
     if (!a.partial) return;
@@ -3675,9 +3833,7 @@ __global__ __launch_bounds__(256) void k_interpolate(IpArgs a)
 // first finds planes, grids and colour in L2 -- and the same kind of kernel, a memory-bound gather with three times the pixel
 // bytes: per cell and frame two rows of two pixels, 6 contiguous bytes each, as one unaligned dword and one u16 load where both
 // pixels lie inside the frame, by bytes (0 outside) where they straddle its edge.  A run's output row is 8 pixels = 24 bytes,
-// collected in three 64-bit words: six dword stores when the run is whole, wholly inside the frame and its row address
-// dword-aligned; bytes otherwise (an odd pad_x, a caller's odd pitch, a cut run, the frame's edges -- with an odd padding
-// cells straddle the frame and only their pixels inside are written).  Runs wholly outside the frame load nothing.
+// collected by bgr_row_put and stored by bgr_store_rows.  Runs wholly outside the frame load nothing.
 // =======================================================================================
 struct IpBgrArgs : IpCommon {           // out: the fw x fh B,G,R frames
     const uint8_t *bgr1, *bgr2;           // the fw x fh colour frames, rows bgr_pitch bytes apart
@@ -3730,28 +3886,10 @@ __global__ __launch_bounds__(256) void k_interpolate_bgr(IpBgrArgs a)
                                                 (uint32_t)half, magic);
                     px |= (uint64_t)v << (8 * q);
                 }
-                const int bit = 48 * j;                       // the cell's six bytes go to bytes 6 j .. 6 j + 5 of the row
-                rows[y][bit >> 6] |= px << (bit & 63);
-                if ((bit & 63) > 16) rows[y][(bit >> 6) + 1] |= px >> (64 - (bit & 63));
+                bgr_row_put(rows[y], j, px);
             }
         }
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            if (fy + y < 0 || fy + y >= a.fh) continue;
-            uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(fy + y) * a.out_pitch + (ptrdiff_t)3 * fx;
-            if (n == 4 && fx >= 0 && fx + 8 <= a.fw && ((uintptr_t)q & 3u) == 0) {
-                uint32_t *o = reinterpret_cast<uint32_t *>(q);
-#pragma unroll
-                for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[y][d >> 1] >> (32 * (d & 1)));
-            } else {
-#pragma unroll
-                for (int p = 0; p < 8; ++p) {
-                    if (p >= 2 * n || fx + p < 0 || fx + p >= a.fw) continue;
-#pragma unroll
-                    for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[y][k >> 3] >> (8 * (k & 7)));
-                }
-            }
-        }
+        bgr_store_rows(a.out + blockIdx.z * a.out_stride, a.out_pitch, a.fw, a.fh, fx, fy, n, bgr_run_whole(n, fx, a.fw), rows);
     }
 }
 
@@ -3759,22 +3897,23 @@ __global__ __launch_bounds__(256) void k_interpolate_bgr(IpBgrArgs a)
 // K9.  Motion-compensated temporal filter of a frame C with its previous frame P and / or its next frame N (the TEMPORAL FILTER
 // RULE of include/bbme.h): output cell (cx, cy) with origin o reads, for each present neighbour X with grid G on C, the 2x2 cell
 // of X at p = o + G[cy][cx]; inside the plane and with cost = SAD(C cell, X cell) < thr it gets the weight w = 8 (thr - cost) /
-// thr (0..8), otherwise 0, and out = (8 C + wP P + wN N + S / 2) / S with S = 8 + wP + wN.  The shared split of runs of 4 cells
-// (gather_index / gather_split): GP and GN arrive by load_mv4 and C as one 8-byte load per plane row; each moved cell is two unaligned u16 loads packed into one
-// dword (ip_cell), so that v_sad_u8 gives the cost -- and, on the finished cell, |out - C| -- in one instruction.  A lane writes
-// its 8 pixels of each of the two output rows as two dwords (bytes where a caller's row is not dword-aligned or the run is cut
-// by the row's end) and its four weight bytes wP | wN << 4 by store_bytes4.
+// thr (0..8), otherwise 0, and out = (8 C + wP P + wN N + S / 2) / S with S = 8 + wP + wN.
+// K9 and K13 are one body, tf_body<SUBPEL, RPL>: K13 differs in how a neighbour's cell is taken (tf_weight<SUBPEL>) and in the
+// row pitch of its grids.  The shared split of runs of 4 cells (gather_index / gather_split): GP and GN arrive by load_mv4 and C by
+// load_cells4; each moved cell is one dword (ip_cell: two unaligned u16 loads; si_cell: rounded samples), so that v_sad_u8 gives
+// the cost -- and, on the finished cell, |out - C| -- in one instruction.  A lane writes its two output rows by store_rows2 and its
+// four weight bytes wP | wN << 4 by store_bytes4.
 // Both divisions are multiply-shifts by k_interpolate's argument: with magic = floor(2^32 / d) + 1 = (2^32 + e) / d, 0 < e <= d,
-// umulhi(n, magic) = floor(n / d) for every n with n e < 2^32.  By thr: n = 8 (thr - cost) <= 8 * 1021 and e <= 1021, n e < 2^23
-// (thr = 1 has no 32-bit magic, 2^32 + 1: there only cost 0 passes, and cost 0 is answered without the division).
-// By S: n <= 255 * 24 + 12 and e <= 24, n e < 2^18; S is the lane's own, so the 17 magics of S = 8..24 come with the arguments
-// and are read from LDS.
-// blockIdx.y = batch pair, blockIdx.z = the frame of a run: each of the five inputs is addressed as base + y s_y + z s_z (bytes for
-// planes, words for grids), frames lie out_stride bytes apart along z and need gridDim.y = 1; the map only with one frame per launch.  Along z the
-// first frame has its previous neighbour only with first_prev and the last its next one only with last_next, so that one launch
-// serves the frames of a chain (z = slot) as well as the 2 frames of every pair of a batch (z = which).  Statistics over the window
-// [wx0, wx1) x [wy0, wy1) in cells: cells with wP > 0, cells with wN > 0, the sum of wP + wN and the sum of |out - C| over the
-// cells' pixels; a lane holds at most 4 kTfRunsPerLane cells of at most 1020 each (store_partial4, frame = y gridDim.z + z).
+// umulhi(n, magic) = floor(n / d) for every n with n e < 2^32.  By thr (tf_cost_weight): n = 8 (thr - cost) <= 8 * 1021 and
+// e <= 1021, n e < 2^23 (thr = 1 has no 32-bit magic, 2^32 + 1: there only cost 0 passes, and cost 0 is answered without the
+// division).  By S: n <= 255 * 24 + 12 and e <= 24, n e < 2^18; S is the lane's own, so the 17 magics of S = 8..24 come with the
+// arguments and are read from LDS.  The bounds hold for every sampling: a cell is four bytes, rounded samples included, so the
+// cost is at most 1020 and the blend's numerator at most 255 * 24 + 12.
+// blockIdx.y = batch pair, blockIdx.z = the frame of a run (tf_frame); frames lie out_stride bytes apart along z and need
+// gridDim.y = 1; the map only with one frame per launch.  Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells with
+// wP > 0, cells with wN > 0, the sum of wP + wN and the sum of |out - C| over the cells' pixels; a lane holds at most 4 RPL cells
+// of at most 1020 each (store_partial4, frame = y gridDim.z + z, then k_mc_reduce: no atomics).
+// __shared__ arrays are the kernels' and come in as arguments: inside the body they would be module-level LDS variables.
 // =======================================================================================
 struct TfArgs {
     const uint8_t *cur, *prev, *next;     // level-0 padded planes, pitch = width; prev / next null = no such neighbour at all
@@ -3796,68 +3935,56 @@ struct TfArgs {
 
 constexpr int kTfRunsPerLane = 2;
 
-// One neighbour of the cell c with origin (ox, oy): its weight, and its cell in *q when the weight is not 0
+// One neighbour of the cell c with origin (ox, oy): its weight, and its cell in *q when the weight is not 0.  g is in pixels and
+// the cell ip_cell's; with SUBPEL g is in quarter pels, the cell lies at o + (g >> 2) with the fractions g & 3, is valid when
+// every tap of non-zero weight lies in the plane, and holds the SUBPEL RULE's four rounded bilinear samples (si_cell, which never
+// addresses a tap of weight 0).
+template <bool SUBPEL>
 __device__ __forceinline__ uint32_t tf_weight(const uint8_t *X, int W, int H, int ox, int oy, mv_t g, uint32_t c, uint32_t thr,
                                               uint32_t magic_thr, uint32_t *q)
 {
-    const int px = ox + mv_x(g), py = oy + mv_y(g);
+    const int gx = mv_x(g), gy = mv_y(g);
+    const int fx = SUBPEL ? gx & 3 : 0, fy = SUBPEL ? gy & 3 : 0;
+    const int sx = ox + (SUBPEL ? gx >> 2 : gx), sy = oy + (SUBPEL ? gy >> 2 : gy);
     *q = 0;
-    if (px < 0 || py < 0 || px > W - 2 || py > H - 2) return 0u;
-    const uint32_t x = ip_cell(X, W, px, py);
+    if (sx < 0 || sy < 0 || sx + 2 + (fx != 0) > W || sy + 2 + (fy != 0) > H) return 0u;
+    uint32_t x;
+    if constexpr (SUBPEL) x = si_cell(X, W, sx, sy, fx, fy);
+    else x = ip_cell(X, W, sx, sy);
     const uint32_t cost = __builtin_amdgcn_sad_u8(c, x, 0u);
-    if (cost >= thr) return 0u;
-    *q = x;
-    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
+    if (cost < thr) *q = x;
+    return tf_cost_weight(cost, thr, magic_thr);
 }
 
-__global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
+// K9's and K13's body: g_pitch = cells from row to row of both grids
+template <bool SUBPEL, int RPL>
+__device__ __forceinline__ void tf_body(const TfArgs &a, int g_pitch, const uint32_t (&magic_s)[17], uint32_t (&part)[4][4])
 {
-    __shared__ uint32_t magic_s[17];
-    if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
-    __syncthreads();
-    const long long y = blockIdx.y, z = blockIdx.z;
-    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
-    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
-    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
-    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
-    const mv_t *GP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *GN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    const TfFrame f = tf_frame(a);
     const int W = a.width, H = a.height, CW = a.cw;
     const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
     uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
 #pragma unroll
-    for (int r = 0; r < kTfRunsPerLane; ++r) {
-        const long long i = gather_index<kTfRunsPerLane>(r);
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
         if (i >= a.runs) break;
         int cy, x0, n;                                        // n cells of the run lie inside the row
         gather_split(i, a.runs_per_row, CW, cy, x0, n);
         const int oy = 2 * cy;
-        const size_t g0 = (size_t)cy * CW + x0, o0 = (size_t)oy * W + 2 * x0;
-        uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
-        if (has_p) load_mv4(GP + g0, n, gp);
-        if (has_n) load_mv4(GN + g0, n, gn);
-        if (n == 4) {
-            const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(C + o0), u = *reinterpret_cast<const ua_u32x2 *>(C + o0 + W);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int sh = 16 * (j & 1);
-                c[j] = ((t.v[j >> 1] >> sh) & 0xffffu) | ((u.v[j >> 1] >> sh) << 16);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (j >= n) continue;
-                c[j] = ip_cell(C, W, 2 * (x0 + j), oy);
-            }
-        }
+        const size_t g0 = (size_t)cy * g_pitch + x0;
+        uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0}, c[4];
+        if (f.has_p) load_mv4(f.GP + g0, n, gp);
+        if (f.has_n) load_mv4(f.GN + g0, n, gn);
+        load_cells4(f.C, W, oy, x0, n, c);
         const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
-        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ws = 0;
+        uint32_t rows[2][2] = {{0, 0}, {0, 0}}, ws = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n) break;
             const int ox = 2 * (x0 + j);
             uint32_t qp = 0, qn = 0;
-            const uint32_t wp = has_p ? tf_weight(P, W, H, ox, oy, gp[j], c[j], thr, magic_thr, &qp) : 0u;
-            const uint32_t wn = has_n ? tf_weight(N, W, H, ox, oy, gn[j], c[j], thr, magic_thr, &qn) : 0u;
+            const uint32_t wp = f.has_p ? tf_weight<SUBPEL>(f.P, W, H, ox, oy, gp[j], c[j], thr, magic_thr, &qp) : 0u;
+            const uint32_t wn = f.has_n ? tf_weight<SUBPEL>(f.N, W, H, ox, oy, gn[j], c[j], thr, magic_thr, &qn) : 0u;
             const uint32_t S = 8u + wp + wn, m = magic_s[wp + wn], half = S >> 1;
             uint32_t px = 0;
 #pragma unroll
@@ -3866,8 +3993,7 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
                                             wn * ((qn >> (8 * q)) & 0xffu) + half, m);
                 px |= v << (8 * q);
             }
-            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
-            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            rows_put(rows, j, px);
             ws |= (wp | wn << 4) << (8 * j);
             if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
                 np += wp != 0u; nn += wn != 0u;
@@ -3875,25 +4001,19 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
                 dsum += __builtin_amdgcn_sad_u8(px, c[j], 0u);
             }
         }
-        if (a.out) {
-            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                const uint32_t *row = yy ? row1 : row0;
-                uint8_t *q = o + (size_t)yy * a.out_pitch;
-                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
-                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
-                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
-                } else {
-                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
-                }
-            }
-        }
+        if (a.out) store_rows2(a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0, a.out_pitch, n, rows);
         if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
     }
     if (!a.partial) return;
-    __shared__ uint32_t part[4][4];
     store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
+}
+
+__global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
+{
+    __shared__ uint32_t magic_s[17], part[4][4];
+    if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
+    __syncthreads();
+    tf_body<false, kTfRunsPerLane>(a, a.cw, magic_s, part);
 }
 
 // =======================================================================================
@@ -3912,6 +4032,8 @@ __global__ __launch_bounds__(256) void k_temporal_filter(TfArgs a)
 // A cell row of a frame is the dword B0 G0 R0 B1 and the u16 G1 R1: the two u16 of a cell share a dword, and the per-channel SADs
 // are v_sad_u8 on channel-masked dwords (B: 2, G and R: 3 each).  The divisions are K9's multiply-shifts with K9's bounds.
 // Statistics as K9 (|out - C| over the cells' four pixels and three channels, at most 3060 a cell), same partial layout.
+// K9b and K13b are made of the shared pieces (tf_frame, tf_cost_weight, the colour row helpers) but keep a kernel loop each: as
+// one body, made as tf_body is, K9b measured up to 3.8 % and K13b up to 1.2 % above the parent (profiles/r28_gather_pieces.txt).
 // =======================================================================================
 // TfArgs, with cur / prev / next and out the fw x fh B,G,R frames (rows bgr_pitch and out_pitch bytes apart) and width x height the
 // padded view, and the frame's place inside that view
@@ -3943,9 +4065,8 @@ __device__ __forceinline__ uint32_t tf_bgr_weight(const uint8_t *X, const TfBgrA
     const uint64_t x1 = bgr_two(X, a.bgr_pitch, a.fw, a.fh, px - a.pad_x, py - a.pad_y + 1);
     const uint32_t cost = bgr_cell_cost((uint32_t)c0, (uint32_t)c1, (uint32_t)(c0 >> 32) | (uint32_t)(c1 >> 32) << 16,
                                         (uint32_t)x0, (uint32_t)x1, (uint32_t)(x0 >> 32) | (uint32_t)(x1 >> 32) << 16);
-    if (cost >= thr) return 0u;
-    q[0] = x0; q[1] = x1;
-    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
+    if (cost < thr) { q[0] = x0; q[1] = x1; }
+    return tf_cost_weight(cost, thr, magic_thr);
 }
 
 __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
@@ -3953,12 +4074,10 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
     __shared__ uint32_t magic_s[17];
     if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
     __syncthreads();
-    const long long y = blockIdx.y, z = blockIdx.z;
-    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
-    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
-    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
-    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
-    const mv_t *GP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *GN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    const TfFrame f = tf_frame(a);
+    const uint8_t *C = f.C, *P = f.P, *N = f.N;
+    const bool has_p = f.has_p, has_n = f.has_n;
+    const mv_t *GP = f.GP, *GN = f.GN;
     const int CW = a.cw;
     const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
     uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
@@ -3977,17 +4096,9 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
         uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0};
         if (has_p) load_mv4(GP + g0, n, gp);
         if (has_n) load_mv4(GN + g0, n, gn);
-        const bool whole = n == 4 && fx >= 0 && fx + 8 <= a.fw;      // the run's 8 pixels lie inside a frame row
+        const bool whole = bgr_run_whole(n, fx, a.fw);        // the run's 8 pixels lie inside a frame row
         uint64_t crow[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's own two rows, 24 bytes each
-        if (whole) {
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                if (fy + yy < 0 || fy + yy >= a.fh) continue;
-                const uint8_t *q = C + (size_t)(fy + yy) * a.bgr_pitch + (size_t)3 * fx;
-#pragma unroll
-                for (int d = 0; d < 3; ++d) crow[yy][d] = reinterpret_cast<const ua_u64 *>(q)[d].v;
-            }
-        }
+        if (whole) bgr_load_rows(C, a.bgr_pitch, a.fh, fx, fy, crow);
         const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
         uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows
         uint32_t ws = 0;
@@ -3995,18 +4106,10 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
         for (int j = 0; j < 4; ++j) {
             if (j >= n) break;
             const int ox = 2 * (x0 + j);
-            const int bit = 48 * j, wd = bit >> 6, sh = bit & 63;      // the cell's six bytes are bytes 6 j .. 6 j + 5 of a row
             uint64_t c[2];
 #pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                if (whole) {
-                    uint64_t v = crow[yy][wd] >> sh;
-                    if (sh > 16) v |= crow[yy][wd + 1] << (64 - sh);
-                    c[yy] = v & 0xffffffffffffull;
-                } else {
-                    c[yy] = bgr_two(C, a.bgr_pitch, a.fw, a.fh, fx + 2 * j, fy + yy);
-                }
-            }
+            for (int yy = 0; yy < 2; ++yy)
+                c[yy] = whole ? bgr_row_get(crow[yy], j) : bgr_two(C, a.bgr_pitch, a.fw, a.fh, fx + 2 * j, fy + yy);
             uint64_t qp[2] = {0, 0}, qn[2] = {0, 0};
             const uint32_t wp = has_p ? tf_bgr_weight(P, a, ox, oy, gp[j], c[0], c[1], thr, magic_thr, qp) : 0u;
             const uint32_t wn = has_n ? tf_bgr_weight(N, a, ox, oy, gn[j], c[0], c[1], thr, magic_thr, qn) : 0u;
@@ -4021,8 +4124,7 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
                                                 wn * ((uint32_t)(qn[yy] >> (8 * q)) & 0xffu) + half, m);
                     px |= (uint64_t)v << (8 * q);
                 }
-                rows[yy][wd] |= px << sh;
-                if (sh > 16) rows[yy][wd + 1] |= px >> (64 - sh);
+                bgr_row_put(rows[yy], j, px);
                 diff = __builtin_amdgcn_sad_u8((uint32_t)px, (uint32_t)c[yy], diff);
                 diff = __builtin_amdgcn_sad_u8((uint32_t)(px >> 32), (uint32_t)(c[yy] >> 32), diff);
             }
@@ -4033,25 +4135,7 @@ __global__ __launch_bounds__(256) void k_temporal_filter_bgr(TfBgrArgs a)
                 dsum += diff;
             }
         }
-        if (a.out) {
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                if (fy + yy < 0 || fy + yy >= a.fh) continue;
-                uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(fy + yy) * a.out_pitch + (ptrdiff_t)3 * fx;
-                if (whole && ((uintptr_t)q & 3u) == 0) {
-                    uint32_t *o = reinterpret_cast<uint32_t *>(q);
-#pragma unroll
-                    for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[yy][d >> 1] >> (32 * (d & 1)));
-                } else {
-#pragma unroll
-                    for (int p = 0; p < 8; ++p) {
-                        if (p >= 2 * n || fx + p < 0 || fx + p >= a.fw) continue;
-#pragma unroll
-                        for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[yy][k >> 3] >> (8 * (k & 7)));
-                    }
-                }
-            }
-        }
+        if (a.out) bgr_store_rows(a.out + blockIdx.z * a.out_stride, a.out_pitch, a.fw, a.fh, fx, fy, n, whole, rows);
         if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
     }
     if (!a.partial) return;
@@ -4229,16 +4313,6 @@ struct ScArgs {
 
 constexpr int kScRunsPerLane = 2;
 
-// bytes s.x, s.x + 1 and s.x + 1 + x1 of a row of I2 (p = the row's byte s.x) in bits 0-7, 8-15 and 16-23
-__device__ __forceinline__ uint32_t sc_row(const uint8_t *p, bool wide, int x1)
-{
-    if (wide) {
-        const uint32_t v = reinterpret_cast<const ua_u32 *>(p)->v;
-        return x1 ? v & 0x00ffffffu : (v & 0xffffu) | ((v & 0xff00u) << 8);
-    }
-    return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)p[1 + x1] << 16;
-}
-
 __global__ __launch_bounds__(256) void k_subpel_compensate(ScArgs a)
 {
     const size_t pair = blockIdx.y;
@@ -4344,8 +4418,8 @@ __global__ __launch_bounds__(256) void k_subpel_compensate(ScArgs a)
 // Loads.  A moved cell needs 2 + (fx != 0) bytes of 2 + (fy != 0) rows of its plane at an arbitrary byte address: K11's
 // addressing (si_cell through sc_row: the third row and the third column at offset 1 + (f != 0), folding onto the second where the
 // weight is 0; one unaligned dword a row where its four bytes lie in the row, a u16 and a byte at the right edge), three loads a
-// cell and plane, six a hypothesis, and none of them leaves the plane.  The zero hypothesis keeps k_interpolate's loads: one
-// 8-byte load per plane row and run, u16 pairs on a cut run.
+// cell and plane, six a hypothesis, and none of them leaves the plane.  The zero hypothesis keeps k_interpolate's loads
+// (load_cells4).
 // Arithmetic.  The horizontal sums of the three rows, then the vertical sums with the single rounding; the four samples packed
 // into one dword per cell as ip_cell packs pixels, so that v_sad_u8 gives the cost in one instruction.  The cost is taken on the
 // rounded samples because those are what the blend mixes: it is the SAD of the two cells the output is made of, 0..1020, as in
@@ -4353,8 +4427,8 @@ __global__ __launch_bounds__(256) void k_subpel_compensate(ScArgs a)
 // Divisions by den are k_interpolate's multiply-shifts by magic = floor(2^32 / den) + 1, exact below 2^24 (e <= 256): the blend's
 // numerators stay below 255 * 256 + 128, and |num v| <= (den - 1) 32768 for every int16 v, -(-32768) = 32768 included, so the
 // shifts' num v + den / 2 + 32768 den lies in [32768, 511 * 32768 + 128], below 2^24.  Positions are 32-bit: |P| < 2^17.
-// Stores as k_interpolate: two dwords a row where the row is dword-aligned and the run whole, bytes otherwise; the map by
-// store_bytes4.  Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells that selected k = 0, 1, 2 and the sum of the
+// Stores as k_interpolate: the rows by store_rows2, the map by store_bytes4.  The selection is si_select, which
+// k_subpel_interpolate_bgr shares.  Statistics over the window [wx0, wx1) x [wy0, wy1) in cells: cells that selected k = 0, 1, 2 and the sum of the
 // selected costs; a lane holds at most 4 kSiRunsPerLane cells of cost <= 1020 (store_partial4, frame = (phase, pair)).
 // =======================================================================================
 struct SiArgs {
@@ -4374,32 +4448,39 @@ struct SiArgs {
 
 constexpr int kSiRunsPerLane = 2;
 
-// The 2x2 cell of the SUBPEL RULE's samples of a plane at integer position (ix, iy) with the fractions (fx, fy), every tap of
-// non-zero weight inside the plane: row iy's two samples in the low half, row iy + 1's in the high half (as ip_cell)
-__device__ __forceinline__ uint32_t si_cell(const uint8_t *img, int W, int ix, int iy, int fx, int fy)
-{
-    const int x1 = fx != 0, y1 = fy != 0;
-    const uint8_t *p = img + (size_t)iy * W + ix;
-    const bool wide = ix + 4 <= W;
-    const uint32_t t0 = sc_row(p, wide, x1), t1 = sc_row(p + W, wide, x1), t2 = sc_row(p + (size_t)(1 + y1) * W, wide, x1);
-    const uint32_t wx = (uint32_t)fx, wy = (uint32_t)fy;
-    uint32_t h[3][2];                                         // (4 - fx) P0 + fx P1 of the three rows' two pixels, <= 1020
-    h[0][0] = (4u - wx) * (t0 & 0xffu) + wx * ((t0 >> 8) & 0xffu); h[0][1] = (4u - wx) * ((t0 >> 8) & 0xffu) + wx * (t0 >> 16);
-    h[1][0] = (4u - wx) * (t1 & 0xffu) + wx * ((t1 >> 8) & 0xffu); h[1][1] = (4u - wx) * ((t1 >> 8) & 0xffu) + wx * (t1 >> 16);
-    h[2][0] = (4u - wx) * (t2 & 0xffu) + wx * ((t2 >> 8) & 0xffu); h[2][1] = (4u - wx) * ((t2 >> 8) & 0xffu) + wx * (t2 >> 16);
-    uint32_t px = 0;
-#pragma unroll
-    for (int k = 0; k < 2; ++k)
-#pragma unroll
-        for (int m = 0; m < 2; ++m) px |= (((4u - wy) * h[k][m] + wy * h[k + 1][m] + 8u) >> 4) << (16 * k + 8 * m);
-    return px;
-}
-
 // every tap of non-zero weight of the cell at quarter-pel position p (one axis) lies in a plane of `size`
 __device__ __forceinline__ bool si_inside(int p, int size)
 {
     const int i = p >> 2;
     return i >= 0 && i + 2 + ((p & 3) != 0) <= size;
+}
+
+// What the cell with the quarter-pel origin (ox4, oy4) = 4 o selects: hypothesis k and its cost, its two cells of rounded samples
+// c1 (of I1 at P1) and c2 (of I2 at P2 = P1 + v), P1 and v; z1 and z2 are the cells of the zero hypothesis.  Shared by
+// k_subpel_interpolate, which blends the cells, and k_subpel_interpolate_bgr, which samples colour at P1 and P2.
+struct SiPick { uint32_t c1, c2, k, cost; int p1x, p1y, vx, vy; };
+
+__device__ __forceinline__ SiPick si_select(const uint8_t *img1, const uint8_t *img2, int W, int H, int ox4, int oy4, uint32_t qf,
+                                            uint32_t qb, bool has_b, uint32_t z1, uint32_t z2, int num, int half, int bias,
+                                            uint32_t magic)
+{
+    SiPick s{0u, 0u, 2u, ~0u, ox4, oy4, 0, 0};                // nothing selected yet
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (h == 1 && !has_b) break;
+        const int vx = h ? -mv_x(qb) : mv_x(qf), vy = h ? -mv_y(qb) : mv_y(qf);
+        const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
+        const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
+        const int p1x = ox4 - sx, p1y = oy4 - sy, p2x = p1x + vx, p2y = p1y + vy;
+        if (!si_inside(p1x, W) || !si_inside(p2x, W) || !si_inside(p1y, H) || !si_inside(p2y, H)) continue;
+        const uint32_t q1 = si_cell(img1, W, p1x >> 2, p1y >> 2, p1x & 3, p1y & 3);
+        const uint32_t q2 = si_cell(img2, W, p2x >> 2, p2y >> 2, p2x & 3, p2y & 3);
+        const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
+        if (c < s.cost) s = SiPick{q1, q2, (uint32_t)h, c, p1x, p1y, vx, vy};      // strictly cheaper: the earliest of equals stays
+    }
+    const uint32_t cz = __builtin_amdgcn_sad_u8(z1, z2, 0u);
+    if (cz < s.cost) s = SiPick{z1, z2, 2u, cz, ox4, oy4, 0, 0};
+    return s;
 }
 
 __global__ __launch_bounds__(256) void k_subpel_interpolate(SiArgs a)
@@ -4421,75 +4502,30 @@ __global__ __launch_bounds__(256) void k_subpel_interpolate(SiArgs a)
         uint32_t qf[4], qb[4] = {0, 0, 0, 0}, z1[4], z2[4];
         load_mv4(QF + (size_t)cy * a.q4_pitch + x0, n, qf);
         if (QB) load_mv4(QB + (size_t)cy * a.q4_pitch + x0, n, qb);
-        const size_t o0 = (size_t)oy * W + 2 * x0;
-        if (n == 4) {                                         // the zero hypothesis' cells: 8 bytes of each plane row
-            const ua_u32x2 t1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0), u1 = *reinterpret_cast<const ua_u32x2 *>(img1 + o0 + W);
-            const ua_u32x2 t2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0), u2 = *reinterpret_cast<const ua_u32x2 *>(img2 + o0 + W);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int sh = 16 * (j & 1);
-                z1[j] = ((t1.v[j >> 1] >> sh) & 0xffffu) | ((u1.v[j >> 1] >> sh) << 16);
-                z2[j] = ((t2.v[j >> 1] >> sh) & 0xffffu) | ((u2.v[j >> 1] >> sh) << 16);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                z1[j] = z2[j] = 0;
-                if (j >= n) continue;
-                z1[j] = ip_cell(img1, W, 2 * (x0 + j), oy);
-                z2[j] = ip_cell(img2, W, 2 * (x0 + j), oy);
-            }
-        }
+        load_cells4(img1, W, oy, x0, n, z1);                  // the zero hypothesis' cells
+        load_cells4(img2, W, oy, x0, n, z2);
         const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
-        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ks = 0;
+        uint32_t rows[2][2] = {{0, 0}, {0, 0}}, ks = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n) break;
-            const int ox4 = 8 * (x0 + j), oy4 = 8 * cy;       // 4 o
-            uint32_t c1 = 0, c2 = 0, k = 2u, cost = ~0u;      // nothing selected yet
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                if (h == 1 && !QB) break;
-                const int vx = h ? -mv_x(qb[j]) : mv_x(qf[j]), vy = h ? -mv_y(qb[j]) : mv_y(qf[j]);
-                const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
-                const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
-                const int p1x = ox4 - sx, p1y = oy4 - sy, p2x = p1x + vx, p2y = p1y + vy;
-                if (!si_inside(p1x, W) || !si_inside(p2x, W) || !si_inside(p1y, H) || !si_inside(p2y, H)) continue;
-                const uint32_t q1 = si_cell(img1, W, p1x >> 2, p1y >> 2, p1x & 3, p1y & 3);
-                const uint32_t q2 = si_cell(img2, W, p2x >> 2, p2y >> 2, p2x & 3, p2y & 3);
-                const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
-                if (c < cost) { c1 = q1; c2 = q2; k = (uint32_t)h; cost = c; }     // strictly cheaper: the earliest of equals stays
-            }
-            const uint32_t cz = __builtin_amdgcn_sad_u8(z1[j], z2[j], 0u);
-            if (cz < cost) { c1 = z1[j]; c2 = z2[j]; k = 2u; cost = cz; }
+            const SiPick s = si_select(img1, img2, W, H, 8 * (x0 + j), 8 * cy, qf[j], qb[j], QB != nullptr, z1[j], z2[j], num, half,
+                                       bias, magic);
+            const uint32_t c1 = s.c1, c2 = s.c2, k = s.k, cost = s.cost;
             uint32_t px = 0;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const uint32_t v = __umulhi(w1 * ((c1 >> (8 * q)) & 0xffu) + w2 * ((c2 >> (8 * q)) & 0xffu) + (uint32_t)half, magic);
                 px |= v << (8 * q);
             }
-            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
-            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            rows_put(rows, j, px);
             ks |= k << (8 * j);
             if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
                 n0 += k == 0u; n1 += k == 1u; n2 += k == 2u;
                 csum += cost;
             }
         }
-        if (a.out) {
-            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
-#pragma unroll
-            for (int y = 0; y < 2; ++y) {
-                const uint32_t *row = y ? row1 : row0;
-                uint8_t *q = o + (size_t)y * a.out_pitch;
-                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
-                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
-                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
-                } else {
-                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
-                }
-            }
-        }
+        if (a.out) store_rows2(a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0, a.out_pitch, n, rows);
         if (a.sel) store_bytes4(a.sel + blockIdx.z * a.sel_stride + (size_t)cy * a.sel_pitch + x0, n, ks);
     }
     if (!a.partial) return;
@@ -4512,9 +4548,7 @@ __global__ __launch_bounds__(256) void k_subpel_interpolate(SiArgs a)
 // Arithmetic.  Separable as the rule allows: the horizontal sums (4 - fx) T0 + fx T1 <= 1020 of the rows, then the vertical sum
 // with the single rounding.  B and R share a word in 16-bit lanes (T & 0xff00ff; the sums stay below 4088 < 2^16), G has its own.
 // The blend divides by den with k_interpolate's multiply-shift: numerators below 255 * 256 + 128.
-// Stores are k_interpolate_bgr's: a run's row of 24 bytes as six dwords where the run is whole, inside the frame and its row
-// address dword-aligned; bytes otherwise (an odd pad_x, a caller's odd pitch, a cut run, the frame's edges -- with an odd padding
-// cells straddle the frame and only their pixels inside are written).  Runs wholly outside the frame load nothing.
+// Stores are k_interpolate_bgr's (bgr_row_put, bgr_store_rows).  Runs wholly outside the frame load nothing.
 // A template over the runs per lane (instantiated with kSiRunsPerLane): template kernels are emitted behind the plain ones in the
 // order of their first use, so this one lies behind every kernel of the estimate in the code object.  As a plain kernel it lay
 // behind k_subpel_interpolate, and every k_search_* and k_reg_* kernel lay 77 056 bytes further on than before.
@@ -4531,35 +4565,6 @@ struct SiBgrArgs {
     int runs_per_row;                     // ceil(cw / 4)
     long long runs;                       // runs_per_row * height / 2
 };
-
-// What the cell with the quarter-pel origin (ox4, oy4) = 4 o selects: hypothesis k and its cost, P1 and v (P2 = P1 + v).  It is
-// k_subpel_interpolate's selection, statement by statement; z1 and z2 are the cells of the zero hypothesis.  (k_subpel_interpolate
-// keeps its written-out text: taken through this helper its registers and size stay but its instructions change, and that kernel
-// was not measured again.)
-struct SiPick { uint32_t k, cost; int p1x, p1y, vx, vy; };
-
-__device__ __forceinline__ SiPick si_select(const uint8_t *img1, const uint8_t *img2, int W, int H, int ox4, int oy4, uint32_t qf,
-                                            uint32_t qb, bool has_b, uint32_t z1, uint32_t z2, int num, int half, int bias,
-                                            uint32_t magic)
-{
-    SiPick s{2u, ~0u, ox4, oy4, 0, 0};                        // nothing selected yet
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (h == 1 && !has_b) break;
-        const int vx = h ? -mv_x(qb) : mv_x(qf), vy = h ? -mv_y(qb) : mv_y(qf);
-        const int sx = (int)__umulhi((uint32_t)(num * vx + half + bias), magic) - 32768;
-        const int sy = (int)__umulhi((uint32_t)(num * vy + half + bias), magic) - 32768;
-        const int p1x = ox4 - sx, p1y = oy4 - sy, p2x = p1x + vx, p2y = p1y + vy;
-        if (!si_inside(p1x, W) || !si_inside(p2x, W) || !si_inside(p1y, H) || !si_inside(p2y, H)) continue;
-        const uint32_t q1 = si_cell(img1, W, p1x >> 2, p1y >> 2, p1x & 3, p1y & 3);
-        const uint32_t q2 = si_cell(img2, W, p2x >> 2, p2y >> 2, p2x & 3, p2y & 3);
-        const uint32_t c = __builtin_amdgcn_sad_u8(q1, q2, 0u);
-        if (c < s.cost) s = SiPick{(uint32_t)h, c, p1x, p1y, vx, vy};          // strictly cheaper: the earliest of equals stays
-    }
-    const uint32_t cz = __builtin_amdgcn_sad_u8(z1, z2, 0u);
-    if (cz < s.cost) s = SiPick{2u, cz, ox4, oy4, 0, 0};
-    return s;
-}
 
 // Pixels x, x + 1 and, with x1, x + 2 of row y of a colour frame, each as B | G << 8 | R << 16; a pixel outside the frame is 0,
 // and without x1 the third is 0 and not read
@@ -4636,25 +4641,8 @@ __global__ __launch_bounds__(256) void k_subpel_interpolate_bgr(SiBgrArgs a)
         uint32_t qf[4], qb[4] = {0, 0, 0, 0}, z1[4], z2[4];
         load_mv4(QF + (size_t)cy * a.q4_pitch + x0, n, qf);
         if (QB) load_mv4(QB + (size_t)cy * a.q4_pitch + x0, n, qb);
-        const size_t o0 = (size_t)oy * W + 2 * x0;
-        if (n == 4) {                                         // the zero hypothesis' cells: 8 bytes of each plane row
-            const ua_u32x2 t1 = *reinterpret_cast<const ua_u32x2 *>(a.img1 + o0), u1 = *reinterpret_cast<const ua_u32x2 *>(a.img1 + o0 + W);
-            const ua_u32x2 t2 = *reinterpret_cast<const ua_u32x2 *>(a.img2 + o0), u2 = *reinterpret_cast<const ua_u32x2 *>(a.img2 + o0 + W);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int sh = 16 * (j & 1);
-                z1[j] = ((t1.v[j >> 1] >> sh) & 0xffffu) | ((u1.v[j >> 1] >> sh) << 16);
-                z2[j] = ((t2.v[j >> 1] >> sh) & 0xffffu) | ((u2.v[j >> 1] >> sh) << 16);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                z1[j] = z2[j] = 0;
-                if (j >= n) continue;
-                z1[j] = ip_cell(a.img1, W, 2 * (x0 + j), oy);
-                z2[j] = ip_cell(a.img2, W, 2 * (x0 + j), oy);
-            }
-        }
+        load_cells4(a.img1, W, oy, x0, n, z1);                // the zero hypothesis' cells
+        load_cells4(a.img2, W, oy, x0, n, z2);
         uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows, 24 bytes each
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -4675,154 +4663,32 @@ __global__ __launch_bounds__(256) void k_subpel_interpolate_bgr(SiBgrArgs a)
                     const uint32_t vr = __umulhi(w1 * (e1[y][m] >> 16) + w2 * (e2[y][m] >> 16) + (uint32_t)half, magic);
                     px |= (uint64_t)(vb | vg << 8 | vr << 16) << (24 * m);
                 }
-                const int bit = 48 * j;                       // the cell's six bytes go to bytes 6 j .. 6 j + 5 of the row
-                rows[y][bit >> 6] |= px << (bit & 63);
-                if ((bit & 63) > 16) rows[y][(bit >> 6) + 1] |= px >> (64 - (bit & 63));
+                bgr_row_put(rows[y], j, px);
             }
         }
-#pragma unroll
-        for (int y = 0; y < 2; ++y) {
-            if (ry + y < 0 || ry + y >= a.fh) continue;
-            uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(ry + y) * a.out_pitch + (ptrdiff_t)3 * rx;
-            if (n == 4 && rx >= 0 && rx + 8 <= a.fw && ((uintptr_t)q & 3u) == 0) {
-                uint32_t *o = reinterpret_cast<uint32_t *>(q);
-#pragma unroll
-                for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[y][d >> 1] >> (32 * (d & 1)));
-            } else {
-#pragma unroll
-                for (int p = 0; p < 8; ++p) {
-                    if (p >= 2 * n || rx + p < 0 || rx + p >= a.fw) continue;
-#pragma unroll
-                    for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[y][k >> 3] >> (8 * (k & 7)));
-                }
-            }
-        }
+        bgr_store_rows(a.out + blockIdx.z * a.out_stride, a.out_pitch, a.fw, a.fh, rx, ry, n, bgr_run_whole(n, rx, a.fw), rows);
     }
 }
 
 // =======================================================================================
 // K13.  Motion-compensated temporal filter along QUARTER-PEL grids (the SUBPEL TEMPORAL FILTER RULE of include/bbme.h): K9 with
-// each neighbour's cell taken as K11 and K12 take theirs.  Output cell (cx, cy) with origin o reads, for each present neighbour X
-// with grid Q on C, (qx, qy) = Q[cy][cx], s = o + (qx >> 2, qy >> 2), f = (qx & 3, qy & 3); the neighbour is valid when every tap of
-// non-zero weight lies in the plane, its cell is the SUBPEL RULE's four rounded bilinear samples (si_cell: the separable form over
-// sc_row, whose third row and third column fold onto the second where the fraction is 0, so that a tap of weight 0 is never
-// addressed), packed into one dword so that v_sad_u8 against C's cell gives the cost, and the weight, the blend, the map and the
-// statistics are K9's from there on.
-// Layout is K9's: the shared split of runs of 4 cells (gather_index / gather_split), QP and QN by load_mv4 (rows q4_pitch cells
-// apart), C as one 8-byte load per plane row, blockIdx.y = batch pair, blockIdx.z = the frame of a run, the five inputs addressed
-// base + y s_y + z s_z with the first / last neighbour flags, the two pixel rows stored as two dwords each (bytes where a caller's
-// row is not dword-aligned or the run is cut), the weight bytes by store_bytes4.
-// Both divisions are K9's multiply-shifts with K9's magics and bounds: the cost of four rounded samples is still <= 1020 and the
-// blend's numerator still <= 255 * 24 + 12, the samples being bytes.
-// Statistics: K9's four counters in 32 bits per lane (at most 4 RPL cells of at most 1020 each), through shuffles to one partial
-// per workgroup (store_partial4, frame = y gridDim.z + z), then k_mc_reduce: no atomics.
+// each neighbour's cell taken as K11 and K12 take theirs.  For each present neighbour X with grid Q on C, (qx, qy) = Q[cy][cx],
+// s = o + (qx >> 2, qy >> 2), f = (qx & 3, qy & 3); the neighbour is valid when every tap of non-zero weight lies in the plane, and
+// its cell is the SUBPEL RULE's four rounded bilinear samples (tf_weight<true>).  Everything else -- layout, weight, blend, map,
+// statistics and the divisions' bounds -- is tf_body's, with K9; the grids' rows lie q4_pitch cells apart.
 // A template, as K12b: a template's code lies behind the estimate's template kernels in the code object, a plain kernel's before.
 // =======================================================================================
 struct TfSpArgs : TfArgs {                // gp / gn: quarter-pel vectors
     int q4_pitch;                         // cells from row to row of both grids
 };
 
-// One neighbour of the cell c with origin (ox, oy): its weight, and its cell of rounded samples in *q when the weight is not 0
-__device__ __forceinline__ uint32_t stf_weight(const uint8_t *X, int W, int H, int ox, int oy, mv_t g, uint32_t c, uint32_t thr,
-                                               uint32_t magic_thr, uint32_t *q)
-{
-    const int qx = mv_x(g), qy = mv_y(g);
-    const int fx = qx & 3, fy = qy & 3;
-    const int sx = ox + (qx >> 2), sy = oy + (qy >> 2);
-    *q = 0;
-    if (sx < 0 || sy < 0 || sx + 2 + (fx != 0) > W || sy + 2 + (fy != 0) > H) return 0u;
-    const uint32_t x = si_cell(X, W, sx, sy, fx, fy);
-    const uint32_t cost = __builtin_amdgcn_sad_u8(c, x, 0u);
-    if (cost >= thr) return 0u;
-    *q = x;
-    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
-}
-
 template <int RPL>
 __global__ __launch_bounds__(256) void k_subpel_temporal_filter(TfSpArgs a)
 {
-    __shared__ uint32_t magic_s[17];
+    __shared__ uint32_t magic_s[17], part[4][4];
     if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
     __syncthreads();
-    const long long y = blockIdx.y, z = blockIdx.z;
-    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
-    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
-    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
-    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
-    const mv_t *QP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *QN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
-    const int W = a.width, H = a.height, CW = a.cw;
-    const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
-    uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
-#pragma unroll
-    for (int r = 0; r < RPL; ++r) {
-        const long long i = gather_index<RPL>(r);
-        if (i >= a.runs) break;
-        int cy, x0, n;                                        // n cells of the run lie inside the row
-        gather_split(i, a.runs_per_row, CW, cy, x0, n);
-        const int oy = 2 * cy;
-        const size_t g0 = (size_t)cy * a.q4_pitch + x0, o0 = (size_t)oy * W + 2 * x0;
-        uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0}, c[4] = {0, 0, 0, 0};
-        if (has_p) load_mv4(QP + g0, n, gp);
-        if (has_n) load_mv4(QN + g0, n, gn);
-        if (n == 4) {
-            const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(C + o0), u = *reinterpret_cast<const ua_u32x2 *>(C + o0 + W);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int sh = 16 * (j & 1);
-                c[j] = ((t.v[j >> 1] >> sh) & 0xffffu) | ((u.v[j >> 1] >> sh) << 16);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (j >= n) continue;
-                c[j] = ip_cell(C, W, 2 * (x0 + j), oy);
-            }
-        }
-        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
-        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ws = 0;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (j >= n) break;
-            const int ox = 2 * (x0 + j);
-            uint32_t qp = 0, qn = 0;
-            const uint32_t wp = has_p ? stf_weight(P, W, H, ox, oy, gp[j], c[j], thr, magic_thr, &qp) : 0u;
-            const uint32_t wn = has_n ? stf_weight(N, W, H, ox, oy, gn[j], c[j], thr, magic_thr, &qn) : 0u;
-            const uint32_t S = 8u + wp + wn, m = magic_s[wp + wn], half = S >> 1;
-            uint32_t px = 0;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const uint32_t v = __umulhi(8u * ((c[j] >> (8 * q)) & 0xffu) + wp * ((qp >> (8 * q)) & 0xffu) +
-                                            wn * ((qn >> (8 * q)) & 0xffu) + half, m);
-                px |= v << (8 * q);
-            }
-            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
-            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
-            ws |= (wp | wn << 4) << (8 * j);
-            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
-                np += wp != 0u; nn += wn != 0u;
-                wsum += wp + wn;
-                dsum += __builtin_amdgcn_sad_u8(px, c[j], 0u);
-            }
-        }
-        if (a.out) {
-            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                const uint32_t *row = yy ? row1 : row0;
-                uint8_t *q = o + (size_t)yy * a.out_pitch;
-                if (n == 4 && ((uintptr_t)q & 3u) == 0) {
-                    reinterpret_cast<uint32_t *>(q)[0] = row[0];
-                    reinterpret_cast<uint32_t *>(q)[1] = row[1];
-                } else {
-                    for (int x = 0; x < 2 * n; ++x) q[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
-                }
-            }
-        }
-        if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
-    }
-    if (!a.partial) return;
-    __shared__ uint32_t part[4][4];
-    store_partial4(a.partial, (size_t)blockIdx.y * gridDim.z + blockIdx.z, part, np, nn, wsum, dsum);
+    tf_body<true, RPL>(a, a.q4_pitch, magic_s, part);
 }
 
 // =======================================================================================
@@ -4865,9 +4731,8 @@ __device__ __forceinline__ uint32_t stf_bgr_weight(const uint8_t *X, const TfSpB
     }
     const uint32_t cost = bgr_cell_cost((uint32_t)c0, (uint32_t)c1, (uint32_t)(c0 >> 32) | (uint32_t)(c1 >> 32) << 16,
                                         lo[0], lo[1], hi[0] | hi[1] << 16);
-    if (cost >= thr) return 0u;
-    q[0] = (uint64_t)lo[0] | (uint64_t)hi[0] << 32; q[1] = (uint64_t)lo[1] | (uint64_t)hi[1] << 32;
-    return cost ? __umulhi(8u * (thr - cost), magic_thr) : 8u;    // cost 0 is weight 8 at every thr, and all that passes at thr = 1
+    if (cost < thr) { q[0] = (uint64_t)lo[0] | (uint64_t)hi[0] << 32; q[1] = (uint64_t)lo[1] | (uint64_t)hi[1] << 32; }
+    return tf_cost_weight(cost, thr, magic_thr);
 }
 
 template <int RPL>
@@ -4876,12 +4741,10 @@ __global__ __launch_bounds__(256) void k_subpel_temporal_filter_bgr(TfSpBgrArgs 
     __shared__ uint32_t magic_s[17];
     if (threadIdx.x < 17) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
     __syncthreads();
-    const long long y = blockIdx.y, z = blockIdx.z;
-    const uint8_t *C = a.cur + y * a.cur_y + z * a.cur_z;
-    const bool has_p = a.prev && (z > 0 || a.first_prev), has_n = a.next && (z + 1 < (long long)gridDim.z || a.last_next);
-    const uint8_t *P = has_p ? a.prev + y * a.prev_y + z * a.prev_z : nullptr;
-    const uint8_t *N = has_n ? a.next + y * a.next_y + z * a.next_z : nullptr;
-    const mv_t *QP = has_p ? a.gp + y * a.gp_y + z * a.gp_z : nullptr, *QN = has_n ? a.gn + y * a.gn_y + z * a.gn_z : nullptr;
+    const TfFrame f = tf_frame(a);
+    const uint8_t *C = f.C, *P = f.P, *N = f.N;
+    const bool has_p = f.has_p, has_n = f.has_n;
+    const mv_t *QP = f.GP, *QN = f.GN;
     const int CW = a.cw;
     const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
     uint32_t np = 0, nn = 0, wsum = 0, dsum = 0;
@@ -4900,17 +4763,9 @@ __global__ __launch_bounds__(256) void k_subpel_temporal_filter_bgr(TfSpBgrArgs 
         uint32_t gp[4] = {0, 0, 0, 0}, gn[4] = {0, 0, 0, 0};
         if (has_p) load_mv4(QP + g0, n, gp);
         if (has_n) load_mv4(QN + g0, n, gn);
-        const bool whole = n == 4 && fx >= 0 && fx + 8 <= a.fw;      // the run's 8 pixels lie inside a frame row
+        const bool whole = bgr_run_whole(n, fx, a.fw);        // the run's 8 pixels lie inside a frame row
         uint64_t crow[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's own two rows, 24 bytes each
-        if (whole) {
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                if (fy + yy < 0 || fy + yy >= a.fh) continue;
-                const uint8_t *q = C + (size_t)(fy + yy) * a.bgr_pitch + (size_t)3 * fx;
-#pragma unroll
-                for (int d = 0; d < 3; ++d) crow[yy][d] = reinterpret_cast<const ua_u64 *>(q)[d].v;
-            }
-        }
+        if (whole) bgr_load_rows(C, a.bgr_pitch, a.fh, fx, fy, crow);
         const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
         uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows
         uint32_t ws = 0;
@@ -4918,18 +4773,10 @@ __global__ __launch_bounds__(256) void k_subpel_temporal_filter_bgr(TfSpBgrArgs 
         for (int j = 0; j < 4; ++j) {
             if (j >= n) break;
             const int ox = 2 * (x0 + j);
-            const int bit = 48 * j, wd = bit >> 6, sh = bit & 63;      // the cell's six bytes are bytes 6 j .. 6 j + 5 of a row
             uint64_t c[2];
 #pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                if (whole) {
-                    uint64_t v = crow[yy][wd] >> sh;
-                    if (sh > 16) v |= crow[yy][wd + 1] << (64 - sh);
-                    c[yy] = v & 0xffffffffffffull;
-                } else {
-                    c[yy] = bgr_two(C, a.bgr_pitch, a.fw, a.fh, fx + 2 * j, fy + yy);
-                }
-            }
+            for (int yy = 0; yy < 2; ++yy)
+                c[yy] = whole ? bgr_row_get(crow[yy], j) : bgr_two(C, a.bgr_pitch, a.fw, a.fh, fx + 2 * j, fy + yy);
             uint64_t qp[2] = {0, 0}, qn[2] = {0, 0};
             const uint32_t wp = has_p ? stf_bgr_weight(P, a, ox, oy, gp[j], c[0], c[1], thr, magic_thr, qp) : 0u;
             const uint32_t wn = has_n ? stf_bgr_weight(N, a, ox, oy, gn[j], c[0], c[1], thr, magic_thr, qn) : 0u;
@@ -4944,8 +4791,7 @@ __global__ __launch_bounds__(256) void k_subpel_temporal_filter_bgr(TfSpBgrArgs 
                                                 wn * ((uint32_t)(qn[yy] >> (8 * q)) & 0xffu) + half, m);
                     px |= (uint64_t)v << (8 * q);
                 }
-                rows[yy][wd] |= px << sh;
-                if (sh > 16) rows[yy][wd + 1] |= px >> (64 - sh);
+                bgr_row_put(rows[yy], j, px);
                 diff = __builtin_amdgcn_sad_u8((uint32_t)px, (uint32_t)c[yy], diff);
                 diff = __builtin_amdgcn_sad_u8((uint32_t)(px >> 32), (uint32_t)(c[yy] >> 32), diff);
             }
@@ -4956,25 +4802,7 @@ __global__ __launch_bounds__(256) void k_subpel_temporal_filter_bgr(TfSpBgrArgs 
                 dsum += diff;
             }
         }
-        if (a.out) {
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                if (fy + yy < 0 || fy + yy >= a.fh) continue;
-                uint8_t *q = a.out + blockIdx.z * a.out_stride + (size_t)(fy + yy) * a.out_pitch + (ptrdiff_t)3 * fx;
-                if (whole && ((uintptr_t)q & 3u) == 0) {
-                    uint32_t *o = reinterpret_cast<uint32_t *>(q);
-#pragma unroll
-                    for (int d = 0; d < 6; ++d) o[d] = (uint32_t)(rows[yy][d >> 1] >> (32 * (d & 1)));
-                } else {
-#pragma unroll
-                    for (int p = 0; p < 8; ++p) {
-                        if (p >= 2 * n || fx + p < 0 || fx + p >= a.fw) continue;
-#pragma unroll
-                        for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[yy][k >> 3] >> (8 * (k & 7)));
-                    }
-                }
-            }
-        }
+        if (a.out) bgr_store_rows(a.out + blockIdx.z * a.out_stride, a.out_pitch, a.fw, a.fh, fx, fy, n, whole, rows);
         if (a.wmap) store_bytes4(a.wmap + (size_t)cy * a.wmap_pitch + x0, n, ws);
     }
     if (!a.partial) return;
@@ -5054,12 +4882,13 @@ __global__ __launch_bounds__(256) void k_compose_cells(CmpArgs a)
 // =======================================================================================
 // K15.  Motion-compensated temporal filter over TWO frames on each side (the WIDE TEMPORAL FILTER RULE of include/bbme.h): K13
 // with up to four neighbours, k = 0 .. 3 = P1, N1, P2, N2, each a plane x[k] with a quarter-pel grid g[k] on C.  Each neighbour's
-// validity, samples, cost and weight are K13's (stf_weight, si_cell), independent of the others; S = 8 + sum w_k (8..40) and
+// validity, samples, cost and weight are K13's (tf_weight<true>), independent of the others; S = 8 + sum w_k (8..40) and
 // out = (8 C + sum w_k X'_k + S / 2) / S.
-// Layout is K13's: the shared split of runs of 4 cells (gather_index / gather_split), the grids by load_mv4 (rows q4_pitch cells
-// apart), C as one 8-byte load per plane row, the two pixel rows stored as two dwords each (bytes where a caller's row is not
-// dword-aligned or the run is cut).  The weight map is one uint16 per cell, w_k << 4 k: one aligned 8-byte store where the run is
-// whole and its address 8-byte aligned, uint16 by uint16 otherwise.
+// Layout is K13's and made of the same pieces (gather_index / gather_split, load_mv4 with rows q4_pitch cells apart, load_cells4,
+// rows_put / store_rows2), but the kernel keeps a loop of its own over its neighbours and is not tf_body: head, map, magics and
+// statistics all differ with the neighbour count.  The weight map is one uint16 per cell, w_k << 4 k: one aligned 8-byte store
+// where the run is whole and its address 8-byte aligned, uint16 by uint16 otherwise; it is stored before the rows (in the other
+// order the compiler spills 34 SGPRs to lanes instead of 8).
 // blockIdx.z = the frame of a run; every plane is addressed base + z plane_z (bytes) and every grid base + z g_z (words).  Frame z
 // of a run of gridDim.z has min(2, z + first_prev) previous and min(2, gridDim.z - 1 - z + last_next) next neighbours: P1 / N1
 // are read when that is >= 1, P2 / N2 when it is 2, and only where x[k] is not null.  One launch so serves the slots of a chain
@@ -5119,27 +4948,14 @@ __global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
         int cy, x0, n;                                        // n cells of the run lie inside the row
         gather_split(i, a.runs_per_row, CW, cy, x0, n);
         const int oy = 2 * cy;
-        const size_t g0 = (size_t)cy * a.q4_pitch + x0, o0 = (size_t)oy * W + 2 * x0;
-        uint32_t g[4][4] = {}, c[4] = {0, 0, 0, 0};
+        const size_t g0 = (size_t)cy * a.q4_pitch + x0;
+        uint32_t g[4][4] = {}, c[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (has[k]) load_mv4(Q[k] + g0, n, g[k]);
-        if (n == 4) {
-            const ua_u32x2 t = *reinterpret_cast<const ua_u32x2 *>(C + o0), v = *reinterpret_cast<const ua_u32x2 *>(C + o0 + W);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int sh = 16 * (j & 1);
-                c[j] = ((t.v[j >> 1] >> sh) & 0xffffu) | ((v.v[j >> 1] >> sh) << 16);
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                if (j >= n) continue;
-                c[j] = ip_cell(C, W, 2 * (x0 + j), oy);
-            }
-        }
+        load_cells4(C, W, oy, x0, n, c);
         const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
-        uint32_t row0[2] = {0, 0}, row1[2] = {0, 0}, ws[2] = {0, 0};
+        uint32_t rows[2][2] = {{0, 0}, {0, 0}}, ws[2] = {0, 0};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (j >= n) break;
@@ -5148,7 +4964,7 @@ __global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 q[k] = 0;
-                w[k] = has[k] ? stf_weight(X[k], W, H, ox, oy, g[k][j], c[j], thr, magic_thr, &q[k]) : 0u;
+                w[k] = has[k] ? tf_weight<true>(X[k], W, H, ox, oy, g[k][j], c[j], thr, magic_thr, &q[k]) : 0u;
                 wt += w[k];
                 wm |= w[k] << (4 * k);
             }
@@ -5161,8 +4977,7 @@ __global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
                 for (int k = 0; k < 4; ++k) num += w[k] * ((q[k] >> (8 * p)) & 0xffu);
                 px |= __umulhi(num, m) << (8 * p);
             }
-            row0[j >> 1] |= (px & 0xffffu) << (16 * (j & 1));
-            row1[j >> 1] |= (px >> 16) << (16 * (j & 1));
+            rows_put(rows, j, px);
             ws[j >> 1] |= wm << (16 * (j & 1));
             if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
 #pragma unroll
@@ -5171,25 +4986,12 @@ __global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
                 dsum += __builtin_amdgcn_sad_u8(px, c[j], 0u);
             }
         }
-        if (a.out) {
-            uint8_t *o = a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0;
-#pragma unroll
-            for (int yy = 0; yy < 2; ++yy) {
-                const uint32_t *row = yy ? row1 : row0;
-                uint8_t *d = o + (size_t)yy * a.out_pitch;
-                if (n == 4 && ((uintptr_t)d & 3u) == 0) {
-                    reinterpret_cast<uint32_t *>(d)[0] = row[0];
-                    reinterpret_cast<uint32_t *>(d)[1] = row[1];
-                } else {
-                    for (int x = 0; x < 2 * n; ++x) d[x] = (uint8_t)(row[x >> 2] >> (8 * (x & 3)));
-                }
-            }
-        }
         if (a.wmap) {
             uint16_t *d = a.wmap + (size_t)cy * a.wmap_pitch + x0;
             if (n == 4 && ((uintptr_t)d & 7u) == 0) *reinterpret_cast<uint2 *>(d) = make_uint2(ws[0], ws[1]);
             else for (int j = 0; j < n; ++j) d[j] = (uint16_t)(ws[j >> 1] >> (16 * (j & 1)));
         }
+        if (a.out) store_rows2(a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0, a.out_pitch, n, rows);
     }
     if (!a.partial) return;
     __shared__ uint32_t part[2][4][4];
