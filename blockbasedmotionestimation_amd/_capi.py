@@ -209,6 +209,25 @@ SIGNATURES = {
     "bbme_subpel_interpolate_bgr_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t,
                                                      C.c_void_p]),
     "bbme_get_subpel_interpolated_bgr_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_vector_histogram_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_global_moments_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "bbme_global_motion_solve_host": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_global_motion_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_cells_vector_histogram_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_cells_global_moments_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p,
+                                                   C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_global_motion": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                     C.c_void_p]),
+    "bbme_get_global_motion_map_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]),
+    "bbme_global_compensate_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p, C.c_void_p]),
+    "bbme_cells_global_compensate_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                                      C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_global_compensate_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_get_global_compensated_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_global_compensation_error": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_frame_plane_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
     "bbme_cells_color_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_flow_color_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

@@ -361,6 +361,15 @@ struct bbme_ctx {
                                                   // quarter pels.  Allocated at first use (wide_prepare)
     StatsScratch wide_stats;                      // bbme_wide_temporal_filter_stats (two quadruples per slot) and
                                                   // bbme_cells_wide_temporal_filter_device (two more)
+    // GLOBAL MOTION RULE, all allocated at first use
+    DevBuf<unsigned long long> gm_words;          // sixteen result words per pair (BBME_MAX_BATCH of them), then K17's partials of a
+                                                  // launch over every pair, then those of a caller's launch (gm_scratch)
+    DevBuf<uint32_t> gm_hist;                     // bbme_global_motion: the two histograms of every pair
+    DevBuf<int32_t> gm_models;                    // the device table of models, six words per pair
+    DevBuf<mv_t> gm_q4;                           // with subpel = 1: the refined cells of every pair, packed
+    DevBuf<uint8_t> gm_mask;                      // with mask_tol >= 0: the consistency mask of every pair, packed
+    StatsScratch gc_stats;                        // bbme_global_compensation_error (every pair) and
+                                                  // bbme_cells_global_compensate_device (one pair)
 };
 
 namespace {
@@ -3792,6 +3801,374 @@ int bbme_wide_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, uns
     for (int f = 0; f < slots; ++f)
         for (int k = 0; k < 6; ++k) stats[6 * f + k] = s[8 * f + k];
     return BBME_OK;
+}
+
+// ---- global motion and global compensation (the GLOBAL MOTION RULE and the GLOBAL COMPENSATION RULE of include/bbme.h; K16 k_vector_histogram,
+// K17 k_global_moments, K18 k_global_compensate) ------------------------------------------------------------------------------
+
+// a grid and, optionally, its exclusion mask, of `pairs` pairs s_cells words / s_excl bytes apart
+struct GmGrid {
+    const mv_t *cells = nullptr;
+    size_t s_cells = 0;
+    int pitch = 0;
+    const uint8_t *excl = nullptr;
+    size_t s_excl = 0;
+    int excl_pitch = 0;
+};
+
+static long long vh_groups(const bbme_ctx *c) { return std::min<long long>(cell_groups(c, 1), kVhMaxGroups); }
+static long long gm_groups(const bbme_ctx *c) { return cell_groups(c, kGmRunsPerLane); }
+static long long gc_groups(const bbme_ctx *c) { return gather_groups(c->lv[0].width, c->lv[0].height, kGcRunsPerLane); }
+
+// gm_words: sixteen result words of every pair, K17's partials of a launch over every pair, then those of a caller's launch
+static int gm_scratch(bbme_ctx *c)
+{
+    return c->gm_words.ensure((size_t)16 * (BBME_MAX_BATCH + gm_groups(c) * (c->batch + 1)), "the global motion moments", Fill::poison);
+}
+static unsigned long long *gm_partials_all(const bbme_ctx *c) { return c->gm_words + (size_t)16 * BBME_MAX_BATCH; }
+static unsigned long long *gm_partials_caller(const bbme_ctx *c) { return gm_partials_all(c) + (size_t)16 * gm_groups(c) * c->batch; }
+
+static int gc_scratch(bbme_ctx *c)
+{
+    return c->gc_stats.ensure(BBME_MAX_BATCH, gc_groups(c), c->batch, 1, "the global compensation statistics");
+}
+
+// geometry and a window in cells.  Touches no device.
+static int check_gm(const bbme_ctx *c, const int *window, const char *what)
+{
+    const Level &L = c->lv[0];
+    if (L.width > 8188 || L.height > 8188)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: a %dx%d plane is beyond 8188 (the moments would not stay exact)", what, L.width, L.height);
+    return check_window(window, L.width / 2, L.height / 2, what, -1);
+}
+
+static int check_gm_tol(long long tol_q16, const char *what)
+{
+    if (tol_q16 < 0 || tol_q16 > (1LL << 40)) return bbme::fail(BBME_ERR_INVALID, "%s: tolerance %lld outside 0..2^40", what, tol_q16);
+    return BBME_OK;
+}
+
+// a caller's grid and mask.  Touches no device.
+static int check_gm_cells(const bbme_ctx *c, const int16_t *d_cells, int cells_pitch_cells, const uint8_t *d_exclude, int exclude_pitch,
+                          const char *what, GmGrid *g)
+{
+    const int cw = c->lv[0].width / 2;
+    if (!d_cells) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (cells_pitch_cells < cw) return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, cells_pitch_cells, cw);
+    if (d_exclude && exclude_pitch < cw)
+        return bbme::fail(BBME_ERR_INVALID, "%s: exclusion mask pitch %d < %d cells per row", what, exclude_pitch, cw);
+    g->cells = reinterpret_cast<const mv_t *>(d_cells); g->pitch = cells_pitch_cells;
+    g->excl = d_exclude; g->excl_pitch = exclude_pitch;
+    return BBME_OK;
+}
+
+// the table zeroed, then k_vector_histogram over `pairs` pairs into it (2 BBME_GM_BINS words per pair)
+static int enqueue_vh(bbme_ctx *c, const GmGrid &g, int pairs, const int *window, uint32_t *d_hist, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    VhArgs a{};
+    a.cells = g.cells; a.s_cells = g.s_cells; a.pitch = g.pitch;
+    a.excl = g.excl; a.s_excl = g.s_excl; a.excl_pitch = g.excl_pitch;
+    a.hist = d_hist; a.cw = L.width / 2;
+    set_window(a, window, L.width / 2, L.height / 2);
+    set_runs(a, L.width / 2, L.height / 2);
+    HIP_TRY(hipMemsetAsync(d_hist, 0, (size_t)pairs * 2 * BBME_GM_BINS * sizeof(uint32_t), stream));
+    hipLaunchKernelGGL(k_vector_histogram<BBME_GM_BINS>, dim3((unsigned)vh_groups(c), (unsigned)pairs), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+// k_global_moments over `pairs` pairs under the models of the device table d_models (six words per pair) or, without one, under
+// `model`: the map (rows map_pitch, pairs s_map bytes apart) and / or, with d_words, the sixteen words of every pair
+static int enqueue_gm(bbme_ctx *c, const GmGrid &g, int pairs, const int32_t *d_models, const int32_t *model, long long tol_q16,
+                      const int *window, uint8_t *d_map, int map_pitch, size_t s_map, unsigned long long *partial,
+                      unsigned long long *d_words, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    GmArgs a{};
+    a.cells = g.cells; a.s_cells = g.s_cells; a.pitch = g.pitch;
+    a.excl = g.excl; a.s_excl = g.s_excl; a.excl_pitch = g.excl_pitch;
+    a.map = d_map; a.map_pitch = map_pitch; a.s_map = s_map;
+    a.partial = d_words ? partial : nullptr;
+    a.models = d_models;
+    if (model) std::copy(model, model + 6, a.model);
+    a.tol = tol_q16;
+    a.cw = L.width / 2; a.ch = L.height / 2;
+    set_window(a, window, a.cw, a.ch);
+    set_runs(a, a.cw, a.ch);
+    const long long groups = gm_groups(c);
+    hipLaunchKernelGGL(k_global_moments<kGmRunsPerLane>, dim3((unsigned)groups, (unsigned)pairs), dim3(256), 0, stream, a);
+    if (d_words) hipLaunchKernelGGL(k_reduce_words<16>, dim3((unsigned)pairs), dim3(256), 0, stream, a.partial, (int)groups, d_words);
+    HIP_TRY(hipGetLastError());
+    return BBME_OK;
+}
+
+// k_global_compensate over `pairs` pairs (planes s_plane bytes apart), models as for enqueue_gm: the frame into d_out (one pair
+// only) and / or, with d_stats, the statistics over `window` in pixels
+static int enqueue_gc(bbme_ctx *c, const uint8_t *img1, const uint8_t *img2, size_t s_plane, int pairs, const int32_t *d_models,
+                      const int32_t *model, int unit, int fill, const int *window, uint8_t *d_out, int out_pitch,
+                      unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    GcArgs a{};
+    a.img1 = img1; a.img2 = img2; a.out = d_out; a.s_plane = s_plane;
+    a.models = d_models;
+    if (model) std::copy(model, model + 6, a.model);
+    a.width = L.width; a.height = L.height; a.mul = 4 / unit; a.fill = fill; a.out_pitch = out_pitch;
+    set_window(a, window, L.width, L.height);
+    set_runs(a, L.width, L.height);
+    return launch_gather(k_global_compensate<kGcRunsPerLane>, a, gc_groups(c), pairs, 1, partial, d_stats, stream);
+}
+
+int bbme_cells_vector_histogram_device(bbme_ctx *c, const int16_t *d_cells, int cells_pitch_cells, const uint8_t *d_exclude,
+                                       int exclude_pitch, const int *window, uint32_t *d_hist, void *hip_stream)
+{
+    const char *what = "bbme_cells_vector_histogram_device";
+    if (int rc = check_ctx(c)) return rc;
+    GmGrid g;
+    if (int rc = check_gm_cells(c, d_cells, cells_pitch_cells, d_exclude, exclude_pitch, what, &g)) return rc;
+    if (!d_hist) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_gm(c, window, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_vh(c, g, 1, window, d_hist, stream);
+}
+
+int bbme_cells_global_moments_device(bbme_ctx *c, const int16_t *d_cells, int cells_pitch_cells, const uint8_t *d_exclude,
+                                     int exclude_pitch, const int32_t *model, long long tol_q16, const int *window, uint8_t *d_map,
+                                     int map_pitch, long long *d_words16, void *hip_stream)
+{
+    const char *what = "bbme_cells_global_moments_device";
+    if (int rc = check_ctx(c)) return rc;
+    GmGrid g;
+    if (int rc = check_gm_cells(c, d_cells, cells_pitch_cells, d_exclude, exclude_pitch, what, &g)) return rc;
+    if (!model || (!d_map && !d_words16)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_gm_tol(tol_q16, what)) return rc;
+    if (int rc = check_gm(c, window, what)) return rc;
+    if (d_map && map_pitch < c->lv[0].width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: map pitch %d < %d cells per row", what, map_pitch, c->lv[0].width / 2);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_words16) if (int rc = gm_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_gm(c, g, 1, nullptr, model, tol_q16, window, d_map, map_pitch, 0, d_words16 ? gm_partials_caller(c) : nullptr,
+                      reinterpret_cast<unsigned long long *>(d_words16), stream);
+}
+
+// What bbme_global_motion and bbme_get_global_motion_map_host check alike: the arguments, then the state.  Touches no device.
+static int check_gm_own(const bbme_ctx *c, int which, int subpel, int mask_tol, long long tol_q16, const int *window, const char *what)
+{
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (subpel != 0 && subpel != 1) return bbme::fail(BBME_ERR_INVALID, "%s: subpel = %d (0 or 1)", what, subpel);
+    if (int rc = check_gm_tol(tol_q16, what)) return rc;
+    if (int rc = check_gm(c, window, what)) return rc;
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+    if (mask_tol >= 0 && !c->fields_valid) return bbme::fail(BBME_ERR_STATE, "%s: no valid bidirectional estimate for the mask", what);
+    return BBME_OK;
+}
+
+// The cells the context's own calls fit, of `pairs` pairs from pair0 on: the cells of `which`, refined into gm_q4 with subpel,
+// and with mask_tol >= 0 their consistency mask in gm_mask -- both made on `stream` first.  After check_gm_own.
+static int gm_prepare(bbme_ctx *c, int pair0, int pairs, int which, int subpel, int mask_tol, hipStream_t stream, const char *what,
+                      GmGrid *g)
+{
+    const Level &L = c->lv[0];
+    const int cw = L.width / 2;
+    const size_t cells = (size_t)cw * (L.height / 2), s_plane = L.plane_stride;
+    const uint8_t *i1, *i2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+    g->cells = grid + (size_t)pair0 * s_grid; g->s_cells = s_grid; g->pitch = cw;
+    if (subpel) {
+        if (int rc = c->gm_q4.ensure(cells * c->batch, "the quarter-pel cells of the global motion", Fill::poison)) return rc;
+        mv_t *q4 = c->gm_q4 + pair0 * cells;
+        if (int rc = enqueue_sp(c, i1 + pair0 * s_plane, i2 + pair0 * s_plane, s_plane, g->cells, s_grid, pairs, nullptr, q4, cw, cells,
+                                nullptr, nullptr, stream))
+            return rc;
+        g->cells = q4; g->s_cells = cells;
+    }
+    if (mask_tol >= 0) {
+        if (int rc = c->gm_mask.ensure(cells * c->batch, "the consistency mask of the global motion", Fill::poison)) return rc;
+        const uint32_t s_f = L.grid_stride(L.final_grid()), s_b = c->bwd_stride;
+        const mv_t *f = L.final_grid() + (size_t)pair0 * s_f, *b = c->bwd_cells + (size_t)pair0 * s_b;
+        FbArgs a{};
+        a.a = which ? b : f; a.s_a = which ? s_b : s_f;
+        a.b = which ? f : b; a.s_b = which ? s_f : s_b;
+        a.mask = c->gm_mask + pair0 * cells; a.mask_pitch = cw; a.s_mask = cells;
+        a.cw = cw; a.ch = L.height / 2; a.tol = mask_tol;
+        set_window(a, nullptr, a.cw, a.ch);
+        set_runs(a, a.cw, a.ch);
+        if (int rc = launch_gather(k_fb_consistency, a, cell_groups(c, kFbRunsPerLane), pairs, 1, nullptr, nullptr, stream)) return rc;
+        g->excl = a.mask; g->s_excl = cells; g->excl_pitch = cw;
+    }
+    return BBME_OK;
+}
+
+int bbme_global_motion(bbme_ctx *c, int which, int subpel, int kind, long long tol_q16, int iterations, int mask_tol, const int *window,
+                       int32_t *models, long long *words)
+{
+    const char *what = "bbme_global_motion";
+    if (int rc = check_gm_own(c, which, subpel, mask_tol, tol_q16, window, what)) return rc;
+    if (kind != BBME_GM_TRANSLATION && kind != BBME_GM_AFFINE) return bbme::fail(BBME_ERR_INVALID, "%s: kind = %d (0 or 1)", what, kind);
+    if (iterations < 0 || iterations > 8) return bbme::fail(BBME_ERR_INVALID, "%s: %d iterations (0..8)", what, iterations);
+    if (!models || !words) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    HIP_TRY(hipSetDevice(c->device));
+    const int P = c->batch;
+    if (int rc = gm_scratch(c)) return rc;
+    if (int rc = c->gm_hist.ensure((size_t)P * 2 * BBME_GM_BINS, "the global motion histograms", Fill::poison)) return rc;
+    if (int rc = c->gm_models.ensure((size_t)6 * BBME_MAX_BATCH, "the global motion models", Fill::poison)) return rc;
+    GmGrid g;
+    if (int rc = gm_prepare(c, 0, P, which, subpel, mask_tol, c->stream, what, &g)) return rc;
+    // step 1: the histograms of every pair, 16 KB each, and their medians
+    std::vector<uint32_t> hist((size_t)P * 2 * BBME_GM_BINS);
+    if (int rc = enqueue_vh(c, g, P, window, c->gm_hist, c->stream)) return rc;
+    HIP_TRY(hipMemcpyAsync(hist.data(), c->gm_hist, hist.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    if (int rc = check_converged(c)) return rc;
+    std::vector<uint8_t> done((size_t)P, 0);
+    for (int p = 0; p < P; ++p) {
+        const uint32_t *h = hist.data() + (size_t)p * 2 * BBME_GM_BINS;
+        unsigned long long n = 0;
+        for (int b = 0; b < BBME_GM_BINS; ++b) n += h[b];
+        int32_t *m = models + 6 * p;
+        std::fill(m, m + 6, 0);
+        m[0] = bbme::global_median(h, n) * 65536;
+        m[3] = bbme::global_median(h + BBME_GM_BINS, n) * 65536;
+        done[p] = n == 0;
+    }
+    // steps 2 .. : a moments pass over every pair under the table of models, 128 bytes per pair down, the solve on the host; a pair
+    // that is done (no cell, or no inlier) keeps its model and its words of these passes are not read.  The last pass is the result.
+    for (int it = 0; it <= iterations; ++it) {
+        const bool last = it == iterations || std::find(done.begin(), done.end(), 0) == done.end();
+        HIP_TRY(hipMemcpyAsync(c->gm_models, models, (size_t)6 * P * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        if (int rc = enqueue_gm(c, g, P, c->gm_models, nullptr, tol_q16, window, nullptr, 0, 0, gm_partials_all(c), c->gm_words, c->stream))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(words, c->gm_words, (size_t)16 * P * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        if (last) break;
+        for (int p = 0; p < P; ++p) {
+            if (done[p]) continue;
+            if (words[16 * p] == 0) { done[p] = 1; continue; }
+            if (int rc = bbme_global_motion_solve_host(words + 16 * p, kind, models + 6 * p)) return rc;
+        }
+    }
+    return BBME_OK;
+}
+
+int bbme_get_global_motion_map_host(bbme_ctx *c, int pair, int which, int subpel, int mask_tol, const int32_t *model, long long tol_q16,
+                                    uint8_t *map)
+{
+    const char *what = "bbme_get_global_motion_map_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_gm_own(c, which, subpel, mask_tol, tol_q16, nullptr, what)) return rc;
+    if (!model || !map) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    HIP_TRY(hipSetDevice(c->device));
+    const int cw = c->lv[0].width / 2, ch = c->lv[0].height / 2;
+    return download_staged(c, (size_t)cw * ch, "the global motion map", map, [&](uint8_t *d) {
+        GmGrid g;
+        if (int rc = gm_prepare(c, pair, 1, which, subpel, mask_tol, c->stream, what, &g)) return rc;
+        return enqueue_gm(c, g, 1, nullptr, model, tol_q16, nullptr, d, cw, 0, nullptr, nullptr, c->stream);
+    });
+}
+
+// unit, fill and a window in pixels.  Touches no device.
+static int check_gc(const bbme_ctx *c, const int32_t *model, int unit, int fill, const int *window, const char *what)
+{
+    const Level &L = c->lv[0];
+    if (!model) return bbme::fail(BBME_ERR_INVALID, "%s: null model", what);
+    if (unit != 1 && unit != 4) return bbme::fail(BBME_ERR_INVALID, "%s: unit %d (1 or 4)", what, unit);
+    if (int rc = check_fill(fill, what)) return rc;
+    if (L.width > 8188 || L.height > 8188)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: a %dx%d plane is beyond 8188", what, L.width, L.height);
+    return check_window(window, L.width, L.height, what, 0);
+}
+
+int bbme_cells_global_compensate_device(bbme_ctx *c, const uint8_t *d_image1, const uint8_t *d_image2, const int32_t *model, int unit,
+                                        int fill, const int *window, uint8_t *d_out, int out_pitch, unsigned long long *d_stats4,
+                                        void *hip_stream)
+{
+    const char *what = "bbme_cells_global_compensate_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_image2 || (!d_out && !d_stats4) || (d_stats4 && !d_image1)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_gc(c, model, unit, fill, window, what)) return rc;
+    if (d_out && out_pitch < L.width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < width %d", what, out_pitch, L.width);
+    if (d_out && overlaps_input(d_out, out_pitch, {d_image1, d_image2}, L.width, L.width, L.height))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input plane", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = gc_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_gc(c, d_image1, d_image2, 0, 1, nullptr, model, unit, fill, window, d_out, out_pitch, c->gc_stats.partials_caller(),
+                      d_stats4, stream);
+}
+
+// the context's own planes of `which`, as sp_source names them: 0 predicts image 1 from image 2 of the context's direction, 1
+// image 2 from image 1 (the planes the backward cells lie on)
+static int gc_source(const bbme_ctx *c, int which, const char *what, const uint8_t **img1, const uint8_t **img2)
+{
+    const Level &L = c->lv[0];
+    if (int rc = check_which(which, what)) return rc;
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    *img1 = which ? L.img2 : c->plane1(L);
+    *img2 = which ? L.img1.get() : c->plane2(L);
+    return BBME_OK;
+}
+
+int bbme_global_compensate_device(bbme_ctx *c, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *d_out,
+                                  int out_pitch, void *hip_stream)
+{
+    const char *what = "bbme_global_compensate_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_gc(c, model, unit, fill, nullptr, what)) return rc;
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (out_pitch < c->lv[0].width) return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < width %d", what, out_pitch, c->lv[0].width);
+    const uint8_t *i1, *i2;
+    if (int rc = gc_source(c, which, what, &i1, &i2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    const size_t at = (size_t)pair * c->lv[0].plane_stride;
+    return enqueue_gc(c, i1 + at, i2 + at, 0, 1, nullptr, model, unit, fill, nullptr, d_out, out_pitch, nullptr, nullptr, stream);
+}
+
+int bbme_get_global_compensated_host(bbme_ctx *c, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *out)
+{
+    const char *what = "bbme_get_global_compensated_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_gc(c, model, unit, fill, nullptr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const uint8_t *i1, *i2;
+    if (int rc = gc_source(c, which, what, &i1, &i2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const Level &L = c->lv[0];
+    const size_t at = (size_t)pair * L.plane_stride;
+    return download_staged(c, (size_t)L.width * L.height, "the globally compensated plane", out, [&](uint8_t *d) {
+        return enqueue_gc(c, i1 + at, i2 + at, 0, 1, nullptr, model, unit, fill, nullptr, d, L.width, nullptr, nullptr, c->stream);
+    });
+}
+
+int bbme_global_compensation_error(bbme_ctx *c, int which, const int32_t *models, int unit, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_global_compensation_error";
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_gc(c, models, unit, 0, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const uint8_t *i1, *i2;
+    if (int rc = gc_source(c, which, what, &i1, &i2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = gc_scratch(c)) return rc;
+    if (int rc = c->gm_models.ensure((size_t)6 * BBME_MAX_BATCH, "the global motion models", Fill::poison)) return rc;
+    return download_stats(c, c->gc_stats, c->batch, stats, [&] {
+        HIP_TRY(hipMemcpyAsync(c->gm_models, models, (size_t)6 * c->batch * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        return enqueue_gc(c, i1, i2, c->lv[0].plane_stride, c->batch, c->gm_models, nullptr, unit, 0, window, nullptr, 0,
+                          c->gc_stats.partials_all(), c->gc_stats.results(), c->stream);
+    });
 }
 
 extern "C" {

@@ -1030,6 +1030,190 @@ int bbme_subpel_compensate_host(const uint8_t *image1, const uint8_t *image2, in
     return BBME_OK;
 }
 
+// ---- the GLOBAL MOTION RULE and the GLOBAL COMPENSATION RULE of include/bbme.h, in the header's own words (the mirrors of
+// k_vector_histogram, k_global_moments and k_global_compensate) ---------------------------------------------------------------
+
+// what the four calls on a grid check alike
+static int gm_check_grid(const int16_t *cells, int cells_w, int cells_h, const uint8_t *exclude, int exclude_pitch, const char *what)
+{
+    if (!cells) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (cells_w < 1 || cells_h < 1) return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d cells", what, cells_w, cells_h);
+    if (cells_w > 4094 || cells_h > 4094)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: %dx%d cells are beyond a plane of 8188", what, cells_w, cells_h);
+    if (exclude && exclude_pitch < cells_w)
+        return bbme::fail(BBME_ERR_INVALID, "%s: exclusion mask pitch %d < %d cells per row", what, exclude_pitch, cells_w);
+    return BBME_OK;
+}
+
+static int gm_check_fit(int kind, long long tol_q16, int iterations, const char *what)
+{
+    if (kind != BBME_GM_TRANSLATION && kind != BBME_GM_AFFINE) return bbme::fail(BBME_ERR_INVALID, "%s: kind = %d (0 or 1)", what, kind);
+    if (tol_q16 < 0 || tol_q16 > (1LL << 40)) return bbme::fail(BBME_ERR_INVALID, "%s: tolerance %lld outside 0..2^40", what, tol_q16);
+    if (iterations < 0 || iterations > 8) return bbme::fail(BBME_ERR_INVALID, "%s: %d iterations (0..8)", what, iterations);
+    return BBME_OK;
+}
+
+int bbme_vector_histogram_host(const int16_t *cells, int cells_w, int cells_h, const uint8_t *exclude, int exclude_pitch,
+                               const int *window, uint32_t *hist)
+{
+    const char *what = "bbme_vector_histogram_host";
+    if (int rc = gm_check_grid(cells, cells_w, cells_h, exclude, exclude_pitch, what)) return rc;
+    if (!hist) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cells_w, cells_h, what, "cells")) return rc;
+    memset(hist, 0, 2 * BBME_GM_BINS * sizeof(uint32_t));
+    for (int cy = win.y0; cy < win.y1; ++cy)
+        for (int cx = win.x0; cx < win.x1; ++cx) {
+            if (exclude && exclude[(size_t)cy * exclude_pitch + cx]) continue;
+            const int16_t *v = cells + 2 * ((size_t)cy * cells_w + cx);
+            for (int k = 0; k < 2; ++k) ++hist[k * BBME_GM_BINS + (v[k] < -1024 ? -1024 : v[k] > 1023 ? 1023 : v[k]) + 1024];
+        }
+    return BBME_OK;
+}
+
+int bbme_global_moments_host(const int16_t *cells, int cells_w, int cells_h, const uint8_t *exclude, int exclude_pitch,
+                             const int32_t *model, long long tol_q16, const int *window, uint8_t *map, long long *words16)
+{
+    const char *what = "bbme_global_moments_host";
+    if (int rc = gm_check_grid(cells, cells_w, cells_h, exclude, exclude_pitch, what)) return rc;
+    if (!model || (!map && !words16)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = gm_check_fit(BBME_GM_TRANSLATION, tol_q16, 0, what)) return rc;
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cells_w, cells_h, what, "cells")) return rc;
+    unsigned long long s[16] = {};                            // two's-complement sums: no signed overflow whatever word 3 does
+    for (int cy = 0; cy < cells_h; ++cy)
+        for (int cx = 0; cx < cells_w; ++cx) {
+            const size_t i = (size_t)cy * cells_w + cx;
+            const long long X = 4LL * cx + 2 - 2LL * cells_w, Y = 4LL * cy + 2 - 2LL * cells_h, dx = cells[2 * i], dy = cells[2 * i + 1];
+            int cls = BBME_GM_EXCLUDED;
+            long long r = 0;
+            if (!exclude || !exclude[(size_t)cy * exclude_pitch + cx]) {
+                const long long pu = model[0] + model[1] * X + model[2] * Y, pv = model[3] + model[4] * X + model[5] * Y;
+                r = llabs(dx * 65536 - pu) + llabs(dy * 65536 - pv);
+                cls = r <= tol_q16 ? BBME_GM_INLIER : BBME_GM_OUTLIER;
+            }
+            if (map) map[i] = (uint8_t)cls;
+            if (!win.contains(cx, cy)) continue;
+            ++s[cls];
+            if (cls != BBME_GM_INLIER) continue;
+            const long long t[13] = {r, X, Y, X * X, X * Y, Y * Y, dx, dy, X * dx, Y * dx, X * dy, Y * dy, dx * dx + dy * dy};
+            for (int k = 0; k < 13; ++k) s[3 + k] += (unsigned long long)t[k];
+        }
+    if (words16) memcpy(words16, s, sizeof s);
+    return BBME_OK;
+}
+
+// llrint(v * 65536), half to even (the default rounding mode), saturated to int32
+static int32_t gm_q16(double v)
+{
+    const double q = v * 65536.0;
+    if (!(q > -2147483648.0)) return INT32_MIN;               // NaN too
+    if (q >= 2147483647.0) return INT32_MAX;
+    return (int32_t)llrint(q);
+}
+
+#if defined(__clang__)
+#define BBME_NO_FP_CONTRACT
+#elif defined(__GNUC__)
+#define BBME_NO_FP_CONTRACT __attribute__((optimize("fp-contract=off")))
+#else
+#define BBME_NO_FP_CONTRACT
+#endif
+
+BBME_NO_FP_CONTRACT int bbme_global_motion_solve_host(const long long *w, int kind, int32_t *model)
+{
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+    const char *what = "bbme_global_motion_solve_host";
+    if (!w || !model) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = gm_check_fit(kind, 0, 0, what)) return rc;
+    for (int k = 0; k < 6; ++k) model[k] = 0;
+    if (w[0] <= 0) return BBME_OK;
+    const double n = (double)w[0], sx = (double)w[4], sy = (double)w[5], su = (double)w[9], sv = (double)w[10];
+    const double xm = sx / n, ym = sy / n, um = su / n, vm = sv / n;
+    model[0] = gm_q16(um);
+    model[3] = gm_q16(vm);
+    if (kind != BBME_GM_AFFINE || w[0] < 3) return BBME_OK;
+    const double Sxx = (double)w[6] - sx * xm, Sxy = (double)w[7] - sx * ym, Syy = (double)w[8] - sy * ym;
+    const double D = Sxx * Syy - Sxy * Sxy;
+    if (!(Sxx > 0.0 && Syy > 0.0 && D > Sxx * Syy / 1048576.0)) return BBME_OK;
+    const double Sxu = (double)w[11] - sx * um, Syu = (double)w[12] - sy * um, Sxv = (double)w[13] - sx * vm, Syv = (double)w[14] - sy * vm;
+    const double a1 = (Sxu * Syy - Syu * Sxy) / D, a2 = (Syu * Sxx - Sxu * Sxy) / D, a0 = um - a1 * xm - a2 * ym;
+    const double b1 = (Sxv * Syy - Syv * Sxy) / D, b2 = (Syv * Sxx - Sxv * Sxy) / D, b0 = vm - b1 * xm - b2 * ym;
+    model[0] = gm_q16(a0); model[1] = gm_q16(a1); model[2] = gm_q16(a2);
+    model[3] = gm_q16(b0); model[4] = gm_q16(b1); model[5] = gm_q16(b2);
+    return BBME_OK;
+}
+
+int bbme_global_motion_host(const int16_t *cells, int cells_w, int cells_h, const uint8_t *exclude, int exclude_pitch, int kind,
+                            long long tol_q16, int iterations, const int *window, int32_t *model, long long *words16, uint8_t *map)
+{
+    const char *what = "bbme_global_motion_host";
+    if (int rc = gm_check_grid(cells, cells_w, cells_h, exclude, exclude_pitch, what)) return rc;
+    if (!model) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = gm_check_fit(kind, tol_q16, iterations, what)) return rc;
+    std::vector<uint32_t> hist(2 * BBME_GM_BINS);
+    if (int rc = bbme_vector_histogram_host(cells, cells_w, cells_h, exclude, exclude_pitch, window, hist.data())) return rc;
+    unsigned long long n = 0;
+    for (int b = 0; b < BBME_GM_BINS; ++b) n += hist[b];
+    for (int k = 0; k < 6; ++k) model[k] = 0;
+    long long w[16];
+    if (n) {
+        model[0] = bbme::global_median(hist.data(), n) * 65536;
+        model[3] = bbme::global_median(hist.data() + BBME_GM_BINS, n) * 65536;
+        for (int it = 0; it < iterations; ++it) {
+            if (int rc = bbme_global_moments_host(cells, cells_w, cells_h, exclude, exclude_pitch, model, tol_q16, window, nullptr, w)) return rc;
+            if (w[0] == 0) break;
+            if (int rc = bbme_global_motion_solve_host(w, kind, model)) return rc;
+        }
+    }
+    if (!map && !words16) return BBME_OK;
+    return bbme_global_moments_host(cells, cells_w, cells_h, exclude, exclude_pitch, model, tol_q16, window, map, words16);
+}
+
+int bbme_global_compensate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int32_t *model, int unit,
+                                int fill, const int *window, uint8_t *out, unsigned long long *stats4)
+{
+    const char *what = "bbme_global_compensate_host";
+    if (!image2 || !model || (!out && !stats4) || (stats4 && !image1)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 2 || height < 2 || (width & 1) || (height & 1))
+        return bbme::fail(BBME_ERR_INVALID, "%s: %dx%d is not a plane of 2x2 cells", what, width, height);
+    if (width > 8188 || height > 8188) return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: %dx%d is beyond 8188", what, width, height);
+    if (unit != 1 && unit != 4) return bbme::fail(BBME_ERR_INVALID, "%s: unit %d (1 or 4)", what, unit);
+    if (fill < 0 || fill > 255) return bbme::fail(BBME_ERR_INVALID, "%s: fill %d outside 0..255", what, fill);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, width, height, what, "plane")) return rc;
+    const long long mul = 4 / unit;
+    unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const long long X = 2LL * x + 1 - width, Y = 2LL * y + 1 - height;
+            const long long pu = model[0] + model[1] * X + model[2] * Y, pv = model[3] + model[4] * X + model[5] * Y;
+            const long long qx = (pu * mul + 32768) >> 16, qy = (pv * mul + 32768) >> 16;
+            const int fx = (int)(qx & 3), fy = (int)(qy & 3);
+            const long long sx = x + (qx >> 2), sy = y + (qy >> 2);
+            const bool ok = 0 <= sx && sx + 1 + (fx != 0) <= width && 0 <= sy && sy + 1 + (fy != 0) <= height;
+            int v = fill;
+            if (ok) {
+                const auto tap = [&](int weight, int dx, int dy) {
+                    return weight ? weight * image2[(size_t)(sy + dy) * width + (size_t)(sx + dx)] : 0;
+                };
+                v = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+            }
+            const size_t at = (size_t)y * width + x;
+            if (out) out[at] = (uint8_t)v;
+            if (!stats4 || !win.contains(x, y)) continue;
+            if (!ok) { ++skipped; continue; }
+            const int d = v - image1[at];
+            sse += (unsigned long long)(d * d);
+            sad += (unsigned long long)(d < 0 ? -d : d);
+            ++pixels;
+        }
+    if (stats4) { stats4[0] = sse; stats4[1] = sad; stats4[2] = pixels; stats4[3] = skipped; }
+    return BBME_OK;
+}
+
 // The SUBPEL INTERPOLATION RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_subpel_interpolate).
 // A tap of weight 0 is not read: it may lie outside the plane.
 int bbme_subpel_interpolate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *qf,

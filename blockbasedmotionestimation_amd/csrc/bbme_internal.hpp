@@ -58,4 +58,16 @@ int ppm_write_bgr(const char *filename, int width, int height, const uint8_t *bg
 void subsample_div4(const float *flow_padded, int padded_width, int padded_height,
                     int pad_x, int pad_y, float *out, int out_width);
 
+// ---- GLOBAL MOTION RULE (include/bbme.h) ----------------------------------------------
+// The median of one histogram of BBME_GM_BINS bins with n entries: the smallest bin whose cumulative count reaches (n + 1) >> 1,
+// minus 1024; 0 for n = 0.  One text for the CPU route and for the host half of the GPU route.
+inline int global_median(const uint32_t *hist, unsigned long long n)
+{
+    if (!n) return 0;
+    unsigned long long cum = 0;
+    for (int b = 0; b < BBME_GM_BINS; ++b)
+        if ((cum += hist[b]) >= ((n + 1) >> 1)) return b - BBME_GM_BINS / 2;
+    return BBME_GM_BINS / 2 - 1;
+}
+
 }  // namespace bbme

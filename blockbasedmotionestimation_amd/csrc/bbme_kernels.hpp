@@ -4999,4 +4999,307 @@ __global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
     store_partial4(a.partial, 2 * (size_t)blockIdx.z + 1, part[1], wsum, dsum, 0u, 0u);
 }
 
+// =======================================================================================
+// K16 .. K18.  The GLOBAL MOTION RULE and the GLOBAL COMPENSATION RULE of include/bbme.h.  They are templates so that they lie
+// behind the estimate's template kernels in the code object, as K12b does.
+// =======================================================================================
+
+// One exclusion byte per unit of a run, bit j of the result set when unit x0 + j is excluded: one dword when the run is whole and
+// its address dword-aligned (a caller's rows need not be), bytes otherwise.
+__device__ __forceinline__ uint32_t gm_excluded4(const uint8_t *e, int n)
+{
+    uint32_t bits = 0;
+    if (n == 4 && ((uintptr_t)e & 3u) == 0) {
+        const uint32_t v = *reinterpret_cast<const uint32_t *>(e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bits |= ((v >> (8 * j)) & 0xffu) ? 1u << j : 0u;
+    } else {
+        for (int j = 0; j < n; ++j) bits |= e[j] ? 1u << j : 0u;
+    }
+    return bits;
+}
+
+// The sixteen-word sibling of store_partial4, for sums that need 64 bits in the lane already: the lane's sixteen 64-bit sums over
+// its wave, the four waves' over the workgroup through `part`, stored as the partial of (frame, workgroup) at word
+// 16 (frame gridDim.x + blockIdx.x), for k_reduce_words to add up.  All adds are modulo 2^64.
+__device__ __forceinline__ void store_partial16(unsigned long long *partial, size_t frame, unsigned long long (&part)[4][16],
+                                                unsigned long long (&s)[16])
+{
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        unsigned long long v = s[k];
+        for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+        if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6][k] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 16)
+        partial[16 * (frame * gridDim.x + blockIdx.x) + threadIdx.x] =
+            part[0][threadIdx.x] + part[1][threadIdx.x] + part[2][threadIdx.x] + part[3][threadIdx.x];
+}
+
+// k_mc_reduce's sibling for partials of WORDS (a power of two <= 256) words: one workgroup per pair (blockIdx.x), lane t adds
+// word t % WORDS of every (256 / WORDS)-th workgroup's partial, then the slices are added through LDS.
+template <int WORDS>
+__global__ __launch_bounds__(256) void k_reduce_words(const unsigned long long *partial, int groups, unsigned long long *out)
+{
+    constexpr int kSlices = 256 / WORDS;
+    const unsigned long long *p = partial + (size_t)WORDS * groups * blockIdx.x;
+    const int k = threadIdx.x % WORDS, slice = threadIdx.x / WORDS;
+    unsigned long long s = 0;
+    for (int g = slice; g < groups; g += kSlices) s += p[(size_t)WORDS * g + k];
+    __shared__ unsigned long long red[256];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    if ((int)threadIdx.x < WORDS) {
+        unsigned long long t = 0;
+        for (int q = 0; q < kSlices; ++q) t += red[q * WORDS + threadIdx.x];
+        out[(size_t)WORDS * blockIdx.x + threadIdx.x] = t;
+    }
+}
+
+// K16.  The histogram part: over the window's cells that the exclusion mask does not exclude, the counts of clamp(dx) and of
+// clamp(dy) in BINS bins each.  A bounded number of workgroups (gridDim.x <= kVhMaxGroups) stride over the runs of 4 cells, so the
+// flush traffic does not grow with the frame; each fills one histogram pair in LDS (2 BINS words = 16 KB) with LDS atomics and
+// then adds its non-zero bins to the pair's table in memory (blockIdx.y = pair), which the host zeroes in front of the launch.
+// Integer adds commute: the counts are exact whatever the order.
+// Contention.  A regularised field is mostly uniform, and 64 lanes adding to one LDS word serialise.  vh_add therefore
+// aggregates inside the wave first: the lowest lane still to do broadcasts its bin, the lanes with the same bin are counted by a
+// ballot and leave, and that lane adds the count once.  A uniform run costs one LDS add per wave and component; 64 distinct
+// bins cost 64 turns of the loop.  The loop runs in wave-uniform control flow (every lane of the wave takes part, `on` says
+// whether it has a value), so ballot and shuffle see whole waves.
+struct VhArgs {
+    const mv_t *cells;                    // cw entries per row, rows `pitch` cells apart
+    const uint8_t *excl;                  // one byte per cell, rows excl_pitch bytes apart, non-zero = excluded; or null
+    uint32_t *hist;                       // per pair 2 BINS words, zero before the launch
+    size_t s_cells, s_excl;               // from pair to pair: words, bytes
+    int cw, pitch, excl_pitch;
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kVhMaxGroups = 256;                      // one per compute unit of an MI355X
+
+__device__ __forceinline__ void vh_add(uint32_t *h, bool on, uint32_t bin)
+{
+    unsigned long long todo = __ballot(on);
+    while (todo) {
+        const int leader = __ffsll((unsigned long long)todo) - 1;
+        const uint32_t b = (uint32_t)__shfl((int)bin, leader);
+        const unsigned long long same = __ballot(on && bin == b);
+        if ((int)(threadIdx.x & 63) == leader) atomicAdd(&h[b], (uint32_t)__popcll(same));
+        todo &= ~same;
+    }
+}
+
+template <int BINS>
+__global__ __launch_bounds__(256) void k_vector_histogram(VhArgs a)
+{
+    __shared__ uint32_t h[2 * BINS];
+    for (int b = threadIdx.x; b < 2 * BINS; b += 256) h[b] = 0;
+    __syncthreads();
+    const size_t pair = blockIdx.y;
+    const mv_t *Q = a.cells + pair * a.s_cells;
+    const uint8_t *E = a.excl ? a.excl + pair * a.s_excl : nullptr;
+    for (long long base = (long long)blockIdx.x * 256; base < a.runs; base += (long long)gridDim.x * 256) {
+        const long long i = base + threadIdx.x;
+        int cy = 0, x0 = 0, n = 0;
+        uint32_t m[4] = {0, 0, 0, 0}, e = 0;
+        if (i < a.runs) {
+            gather_split(i, a.runs_per_row, a.cw, cy, x0, n);
+            if (cy < a.wy0 || cy >= a.wy1 || x0 + n <= a.wx0 || x0 >= a.wx1) {
+                n = 0;                                        // no cell of the run lies in the window: nothing is loaded
+            } else {
+                load_mv4(Q + (size_t)cy * a.pitch + x0, n, m);
+                if (E) e = gm_excluded4(E + (size_t)cy * a.excl_pitch + x0, n);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const bool on = j < n && x0 + j >= a.wx0 && x0 + j < a.wx1 && !((e >> j) & 1u);
+            vh_add(h, on, (uint32_t)(min(max(mv_x(m[j]), -BINS / 2), BINS / 2 - 1) + BINS / 2));
+            vh_add(h + BINS, on, (uint32_t)(min(max(mv_y(m[j]), -BINS / 2), BINS / 2 - 1) + BINS / 2));
+        }
+    }
+    __syncthreads();
+    uint32_t *out = a.hist + pair * (size_t)(2 * BINS);
+    for (int b = threadIdx.x; b < 2 * BINS; b += 256) {
+        const uint32_t v = h[b];
+        if (v) atomicAdd(&out[b], v);
+    }
+}
+
+// K17.  The moments part: every cell's class under a model and a tolerance, the class map and the sixteen words over the window.
+// It has k_fb_consistency's shape: a lane takes runs of 4 consecutive cells of one row (2 at a row's end when CW = 2 mod 4), the
+// grid arrives as one 16-byte load (load_mv4), the exclusion bytes as one dword where aligned, the map leaves as one dword
+// (store_bytes4); blockIdx.y = pair, with the pair's model from a device table (`models`, six words per pair) or, without one,
+// from the arguments.  pu and pv advance along the run by 4 m1 and 4 m4 in 64 bits.
+// Sums.  One product is up to 2^28 and r up to 2^47, so a lane's sums are 64-bit from the first add, and so are the wave's and
+// the workgroup's (store_partial16); k_reduce_words<16> adds the workgroups' partials.  All sums are modulo 2^64, as the rule's.
+struct GmArgs {
+    const mv_t *cells;                    // cw entries per row, rows `pitch` cells apart
+    const uint8_t *excl;                  // one byte per cell, rows excl_pitch bytes apart, non-zero = excluded; or null
+    uint8_t *map;                         // one class byte per cell, rows map_pitch bytes apart; or null
+    unsigned long long *partial;          // per pair and workgroup the sixteen words; or null (no statistics)
+    const int32_t *models;                // six words per pair; or null: `model` for every pair
+    int32_t model[6];
+    long long tol;
+    size_t s_cells, s_excl, s_map;        // from pair to pair: words, bytes, bytes
+    int cw, ch, pitch, excl_pitch, map_pitch;
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kGmRunsPerLane = 4;
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_global_moments(GmArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const mv_t *Q = a.cells + pair * a.s_cells;
+    const uint8_t *E = a.excl ? a.excl + pair * a.s_excl : nullptr;
+    long long m[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) m[k] = a.models ? a.models[6 * pair + k] : a.model[k];
+    const int CW = a.cw;
+    unsigned long long s[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row (4, or 2 at the row's end)
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        uint32_t q[4];
+        load_mv4(Q + (size_t)cy * a.pitch + x0, n, q);
+        const uint32_t e = E ? gm_excluded4(E + (size_t)cy * a.excl_pitch + x0, n) : 0u;
+        const long long Y = 4LL * cy + 2 - 2LL * a.ch;
+        long long X = 4LL * x0 + 2 - 2LL * CW, pu = m[0] + m[1] * X + m[2] * Y, pv = m[3] + m[4] * X + m[5] * Y;
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint32_t cls = 0;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const long long dx = mv_x(q[j]), dy = mv_y(q[j]);
+            uint32_t c = 2u;
+            long long res = 0;
+            if (!((e >> j) & 1u)) {
+                const long long ru = dx * 65536 - pu, rv = dy * 65536 - pv;
+                res = (ru < 0 ? -ru : ru) + (rv < 0 ? -rv : rv);
+                c = res > a.tol ? 1u : 0u;
+            }
+            cls |= c << (8 * j);
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+                s[0] += c == 0u; s[1] += c == 1u; s[2] += c == 2u;
+                if (c == 0u) {
+                    s[3] += (unsigned long long)res;
+                    s[4] += (unsigned long long)X; s[5] += (unsigned long long)Y;
+                    s[6] += (unsigned long long)(X * X); s[7] += (unsigned long long)(X * Y); s[8] += (unsigned long long)(Y * Y);
+                    s[9] += (unsigned long long)dx; s[10] += (unsigned long long)dy;
+                    s[11] += (unsigned long long)(X * dx); s[12] += (unsigned long long)(Y * dx);
+                    s[13] += (unsigned long long)(X * dy); s[14] += (unsigned long long)(Y * dy);
+                    s[15] += (unsigned long long)(dx * dx + dy * dy);
+                }
+            }
+            X += 4; pu += 4 * m[1]; pv += 4 * m[4];
+        }
+        if (a.map) store_bytes4(a.map + pair * a.s_map + (size_t)cy * a.map_pitch + x0, n, cls);
+    }
+    if (!a.partial) return;
+    __shared__ unsigned long long part[4][16];
+    store_partial16(a.partial, pair, part, s);
+}
+
+// K18.  The GLOBAL COMPENSATION RULE: pixel (x, y) takes the SUBPEL RULE's sample of I2 at s = (x, y) + (q >> 2) with the
+// fractions q & 3, q = (d (4 / unit) + 32768) >> 16 the model's displacement there in quarter pels; a pixel one of whose taps of
+// non-zero weight would leave the plane gets `fill`.  It is k_motion_compensate's sibling: a lane takes runs of 4 pixels of one
+// row, the model advances along the run by 2 m1 and 2 m4 per pixel in 64 bits, the run leaves as one dword (store_bytes4) and I1
+// is read, as a dword, only for rows that meet the window; blockIdx.y = pair, the model as in K17.
+// Loads.  Neighbouring pixels of a zooming or rotating model need not be neighbours in I2, and a single pixel's second column
+// and row exist only where the fraction is not 0: sc_row and si_cell read byte s.x + 1 and row s.y + 1 whatever the fraction --
+// right for a 2x2 cell, whose second pixel lies there, but one byte or one row past the plane for a lone pixel on its last column
+// or row.  So the four taps are byte loads at offsets x1 = (fx != 0) and y1 W: where a fraction is 0 its tap folds onto the
+// first (weight 0), and no address leaves the plane that the rule does not name.  The sample is the separable form.
+// Statistics over the window [wx0, wx1) x [wy0, wy1) in PIXELS: sse, sad, pixels over the compensated pixels, skipped over the
+// others.  A lane sums at most 4 RPL pixels in 32 bits and a wave's sum stays below 2^32: 64 * 4 RPL * 255^2 (store_partial4,
+// frame = pair; k_mc_reduce).
+struct GcArgs {
+    const uint8_t *img1, *img2;           // packed width x height planes; img1 may be null without statistics
+    uint8_t *out;                         // compensated plane (rows out_pitch bytes apart), or null
+    unsigned long long *partial;          // per pair and workgroup {sse, sad, pixels, skipped}; or null (no statistics)
+    const int32_t *models;                // six words per pair; or null: `model` for every pair
+    int32_t model[6];
+    size_t s_plane;                       // bytes from pair to pair
+    int width, height, mul, fill, out_pitch;      // mul = 4 / unit
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(width / 4)
+    long long runs;                       // runs_per_row * height
+};
+
+constexpr int kGcRunsPerLane = 4;
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_global_compensate(GcArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const uint8_t *I2 = a.img2 + pair * a.s_plane;
+    long long m[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) m[k] = a.models ? a.models[6 * pair + k] : a.model[k];
+    const int W = a.width, H = a.height;
+    const long long mul = a.mul;
+    uint32_t sse = 0, sad = 0, npix = 0, nskip = 0;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int y, x0, n;                                         // n pixels of the run lie inside the row
+        gather_split(i, a.runs_per_row, W, y, x0, n);
+        const long long X = 2LL * x0 + 1 - W, Y = 2LL * y + 1 - H;
+        long long pu = m[0] + m[1] * X + m[2] * Y, pv = m[3] + m[4] * X + m[5] * Y;
+        uint32_t mc = 0, ok = 0;                              // sampled bytes; bit j: pixel x0 + j was compensated
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const long long qx = (pu * mul + 32768) >> 16, qy = (pv * mul + 32768) >> 16;
+            const uint32_t fx = (uint32_t)(qx & 3), fy = (uint32_t)(qy & 3);
+            const int x1 = fx != 0, y1 = fy != 0;
+            const long long sx = x0 + j + (qx >> 2), sy = y + (qy >> 2);
+            if (sx >= 0 && sx + 1 + x1 <= W && sy >= 0 && sy + 1 + y1 <= H) {
+                const uint8_t *p = I2 + (size_t)sy * W + (size_t)sx, *p1 = p + (size_t)y1 * W;
+                const uint32_t h0 = (4u - fx) * p[0] + fx * p[x1], h1 = (4u - fx) * p1[0] + fx * p1[x1];
+                mc |= (((4u - fy) * h0 + fy * h1 + 8u) >> 4) << (8 * j);
+                ok |= 1u << j;
+            }
+            pu += 2 * m[1]; pv += 2 * m[4];
+        }
+        if (a.out) {
+            uint32_t keep = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) keep |= ((ok >> j) & 1u) ? 0xffu << (8 * j) : 0u;
+            store_bytes4(a.out + (size_t)y * a.out_pitch + x0, n, (mc & keep) | ((uint32_t)a.fill * 0x01010101u & ~keep));
+        }
+        if (a.partial && y >= a.wy0 && y < a.wy1) {
+            const uint8_t *r1 = a.img1 + pair * a.s_plane + (size_t)y * W + x0;
+            uint32_t ref = 0;
+            if (n == 4) ref = reinterpret_cast<const ua_u32 *>(r1)->v;
+            else for (int j = 0; j < n; ++j) ref |= (uint32_t)r1[j] << (8 * j);
+            for (int j = 0; j < n; ++j) {
+                if (x0 + j < a.wx0 || x0 + j >= a.wx1) continue;
+                if ((ok >> j) & 1u) {
+                    const int d = (int)((mc >> (8 * j)) & 0xffu) - (int)((ref >> (8 * j)) & 0xffu);
+                    sse += (uint32_t)(d * d);
+                    sad += (uint32_t)abs(d);
+                    ++npix;
+                } else {
+                    ++nskip;
+                }
+            }
+        }
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, pair, part, sse, sad, npix, nskip);
+}
+
 }  // namespace bbme

@@ -4,6 +4,7 @@
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
 //            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T] [--subpel sub.flo]
 //            [--mc-subpel mcq.pgm] [--interpolate-subpel PREFIX --factor N] [--denoise-subpel PREFIX --strength T]
+//            [--global-motion [--gm-out gm.pgm]]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -38,6 +39,10 @@
 // PREFIX_1.pgm and PREFIX_2.pgm, the unpadded frames MF sees: with --no-upsample the frames read (on colour frames their luma),
 // without it their 4x planes.  On colour frames with --no-upsample (which keeps the colour) additionally PREFIX_1.ppm and
 // PREFIX_2.ppm, the colour frames by the BGR subpel temporal filter rule, as --denoise writes its own.
+// --global-motion prints the dominant motion of the pair (the global motion rule of include/bbme.h: an affine model fitted to the
+// estimated cells of the unpadded frame, tolerance one pixel, three iterations) as six numbers in pixels and pixels per pixel, the
+// cells that follow it, that do not and that were excluded, and the PSNR of the prediction of frame 1 from frame 2 along the model
+// alone (the global compensation rule) beside the block field's; --gm-out writes that prediction, the same unpadded crop as --mc.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -89,7 +94,8 @@ int main(int argc, char **argv)
 {
     const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
                *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr, *mc_subpel = nullptr,
-               *interpolate_subpel = nullptr, *denoise_subpel = nullptr;
+               *interpolate_subpel = nullptr, *denoise_subpel = nullptr, *gm_out = nullptr;
+    bool global_motion = false;
     int factor = 2, strength = 64;
     int levels = 4, block = 32, search = 64, device = 0;
     bool upsample = true;
@@ -109,6 +115,8 @@ int main(int argc, char **argv)
         else if (a == "--denoise") denoise = next();
         else if (a == "--denoise-subpel") denoise_subpel = next();
         else if (a == "--subpel") subpel = next();
+        else if (a == "--global-motion") global_motion = true;
+        else if (a == "--gm-out") gm_out = next();
         else if (a == "--strength") strength = atoi(next());
         else if (a == "--factor") factor = atoi(next());
         else if (a == "--levels") levels = atoi(next());
@@ -126,13 +134,18 @@ int main(int argc, char **argv)
                         "[--levels N] [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] "
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
                         "[--denoise PREFIX --strength T] [--subpel sub.flo] [--mc-subpel mcq.pgm] "
-                        "[--interpolate-subpel PREFIX --factor N] [--denoise-subpel PREFIX --strength T]\n"
+                        "[--interpolate-subpel PREFIX --factor N] [--denoise-subpel PREFIX --strength T] "
+                        "[--global-motion [--gm-out gm.pgm]]\n"
                         "--denoise writes PREFIX_1.pgm and PREFIX_2.pgm (on .ppm frames their luma) and, on .ppm frames, the "
                         "filtered colour frames PREFIX_1.ppm and PREFIX_2.ppm; it needs --no-upsample\n");
         return 2;
     }
     if (denoise && upsample) {
         fprintf(stderr, "--denoise needs --no-upsample\n");
+        return 2;
+    }
+    if (gm_out && !global_motion) {
+        fprintf(stderr, "--gm-out needs --global-motion\n");
         return 2;
     }
     try {
@@ -182,6 +195,24 @@ int main(int argc, char **argv)
                 bbme::ImageFlow gtruth;
                 file.ReadFlowFile(gtruth, gt);
                 printf("Calculated MSE after quarter-pel refinement is %.9g\n", file.CalculateMSE(gtruth, refined));
+            }
+        }
+        if (global_motion) {                           // before anything below replaces the forward field
+            const MF::GlobalMotion g = motion_pair.globalMotion(BBME_GM_AFFINE, 65536, 3);
+            const int W = motion_pair.padded_width, H = motion_pair.padded_height;
+            // the model at the plane centre, and its slopes per pixel (two half pixels)
+            printf("Global motion: u = %.6g %+.6g x %+.6g y, v = %.6g %+.6g x %+.6g y (pixels, x and y from the centre of the %dx%d "
+                   "plane)\n", g.model[0] / 65536.0, g.model[1] / 32768.0, g.model[2] / 32768.0, g.model[3] / 65536.0,
+                   g.model[4] / 32768.0, g.model[5] / 32768.0, W, H);
+            printf("Global motion cells: %lld follow it, %lld do not, %lld excluded\n", g.words[0], g.words[1], g.words[2]);
+            const bbme::CompensationError e = motion_pair.compensationError(0, 2), q = motion_pair.compensationErrorGlobal(g.model, 1);
+            printf("Global MC PSNR is %.9g dB (block field: %.9g dB) over %llu pixels (%llu skipped)\n", q.psnr(), e.psnr(), q.pixels,
+                   q.skipped);
+            if (gm_out) {
+                const bbme::Image8 img = motion_pair.drawMVimageGlobal(g.model, 1, false, 0);
+                const int px = motion_pair.padding_x, py = motion_pair.padding_y;
+                bbme::check(bbme_pgm_write(gm_out, img.cols - 2 * px, img.rows - 2 * py, img.cols,
+                                           img.data.data() + (size_t)py * img.cols + px));
             }
         }
         if (mc) {

@@ -240,6 +240,43 @@ public:
         e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3];
         return e;
     }
+    // The dominant motion of the current cells (the GLOBAL MOTION RULE of include/bbme.h) over the cells of the unpadded frame:
+    // six Q16 integers in pixels (unit 1) over half pixels from the plane centre, and the sixteen words of the last moments pass
+    // (words[0..2]: inliers, outliers, excluded).  tol_q16: the L1 tolerance in Q16 pixels.
+    struct GlobalMotion { int32_t model[6]; long long words[16]; };
+    GlobalMotion globalMotion(int kind = BBME_GM_AFFINE, long long tol_q16 = 65536, int iterations = 3, bool backward = false)
+    {
+        int win[4];
+        unpaddedCells(win);
+        GlobalMotion g{};
+        bbme::check(bbme_global_motion(ctx_, backward ? 1 : 0, 0, kind, tol_q16, iterations, -1, win, g.model, g.words));
+        return g;
+    }
+    // The class map of the current cells under that model: one byte (BBME_GM_*) per cell.
+    bbme::Image8 globalMotionMap(const int32_t model[6], long long tol_q16 = 65536, bool backward = false)
+    {
+        bbme::Image8 map(padded_height / 2, padded_width / 2);
+        bbme::check(bbme_get_global_motion_map_host(ctx_, 0, backward ? 1 : 0, 0, -1, model, tol_q16, map.data.data()));
+        return map;
+    }
+    // The padded level-0 plane compensated for the model's motion alone (the GLOBAL COMPENSATION RULE of include/bbme.h), and its
+    // residual statistics against the image it predicts over window {x0, y0, w, h} in pixels; nullptr = the unpadded frame.
+    bbme::Image8 drawMVimageGlobal(const int32_t model[6], int unit = 1, bool backward = false, int fill = 0)
+    {
+        bbme::Image8 img(padded_height, padded_width);
+        bbme::check(bbme_get_global_compensated_host(ctx_, 0, backward ? 1 : 0, model, unit, fill, img.data.data()));
+        return img;
+    }
+    bbme::CompensationError compensationErrorGlobal(const int32_t model[6], int unit = 1, bool backward = false,
+                                                    const int *window = nullptr)
+    {
+        const int unpadded[4] = {padding_x, padding_y, padded_width - 2 * padding_x, padded_height - 2 * padding_y};
+        unsigned long long s[4] = {0, 0, 0, 0};
+        bbme::check(bbme_global_compensation_error(ctx_, backward ? 1 : 0, model, unit, window ? window : unpadded, s));
+        bbme::CompensationError e;
+        e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3];
+        return e;
+    }
     // Direction of the context (include/bbme.h): backward = every estimate and result as if image1 and image2 were exchanged.
     void setDirection(bool backward) { bbme::check(bbme_set_direction(ctx_, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD)); }
     bool direction() const

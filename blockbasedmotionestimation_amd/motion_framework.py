@@ -571,6 +571,152 @@ class MF:
             out.stride(0) if out is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
         return out, stats
 
+    # -- global motion and global compensation (the GLOBAL MOTION RULE and the GLOBAL COMPENSATION RULE of include/bbme.h) ----------
+    def _global_motion(self, which, subpel, kind, tol, iterations, mask_tol, window):
+        """Every pair's estimate from one launch per step -> list of dicts without the map."""
+        pairs = getattr(self, "batch", 1)
+        unit = 4 if subpel else 1
+        models = np.zeros((pairs, 6), np.int32)
+        words = np.zeros((pairs, 16), np.int64)
+        _capi.check(self._lib.bbme_global_motion(self._ctx, _which(which), int(bool(subpel)), _gm_kind(kind), _gm_tol(tol, unit),
+                                                 int(iterations), -1 if mask_tol is None else int(mask_tol), self._stats_window(window),
+                                                 models.ctypes.data, words.ctypes.data))
+        return [_gm_dict(models[p], words[p], unit) for p in range(pairs)]
+
+    def _global_motion_map(self, pair, which, subpel, mask_tol, model, tol, out, what):
+        out = _host_out(out, self.cells_shape, np.uint8, what)
+        model = _gm_model(model, what)
+        _capi.check(self._lib.bbme_get_global_motion_map_host(self._ctx, pair, _which(which), int(bool(subpel)),
+                                                              -1 if mask_tol is None else int(mask_tol), model.ctypes.data,
+                                                              _gm_tol(tol, 4 if subpel else 1), out.ctypes.data))
+        return out
+
+    def global_motion(self, which="forward", subpel=False, kind="affine", tol=1.0, iterations=3, mask_tol=None, window=None):
+        """The dominant motion of the context's cells (the global motion rule): dict(model, unit, translation, statistics, map).
+        model: six int32 in Q16 (m0..m2 for u, m3..m5 for v) in grid units of 1 / unit pixel over half pixels from the plane
+        centre; translation: (m0, m3) in pixels; statistics: dict(inliers, outliers, excluded, residual, ...) of the last
+        moments pass; map: (CH, CW) uint8, 0 a cell that follows the model within `tol` pixels (L1), 1 one that does not, 2 an
+        excluded one.  which: the forward (current) or the backward cells; subpel: refine them to quarter-pel first (unit 4);
+        kind: "translation" or "affine"; mask_tol: exclude the cells that consistency(which, mask_tol) does not call consistent
+        (needs estimate_bidirectional_async()); window (cx0, cy0, cw, ch) in cells, default default_cell_window(), "all" every
+        cell.  Synchronises at every step."""
+        d = self._global_motion(which, subpel, kind, tol, iterations, mask_tol, window)[0]
+        d["map"] = self._global_motion_map(0, which, subpel, mask_tol, d["model"], tol, None, "global_motion")
+        return d
+
+    def _get_global_compensated(self, pair, which, model, unit, fill, out, what):
+        out = _host_out(out, (self.padded_height, self.padded_width), np.uint8, what)
+        model = _gm_model(model, what)
+        _capi.check(self._lib.bbme_get_global_compensated_host(self._ctx, pair, _which(which), model.ctypes.data, int(unit), int(fill),
+                                                               out.ctypes.data))
+        return out
+
+    def draw_MVimage_global(self, model, unit=1, which="forward", fill=0, out=None):
+        """The padded (H_pad, W_pad) uint8 plane compensated for the model's motion alone (the global compensation rule): every
+        pixel the bilinear quarter-pel sample of the other image where the model points, `fill` where a tap leaves the plane.
+        which="forward": image 1 predicted from image 2; "backward": image 2 from image 1.  Needs frames, no estimate."""
+        return self._get_global_compensated(0, which, model, unit, fill, out, "draw_MVimage_global")
+
+    def _global_compensation_stats(self, which, models, unit, window):
+        if window is None:
+            window = (self.padding_x, self.padding_y, self.orig_width, self.orig_height)
+        pairs = getattr(self, "batch", 1)
+        models = np.ascontiguousarray(models, np.int32).reshape(-1)
+        if models.size != 6 * pairs:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "compensation_error_global: six int32 per pair (%d pairs)" % pairs)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_global_compensation_error(self._ctx, _which(which), models.ctypes.data, int(unit), _window(window), s))
+        return [_residual_dict(s[4 * p:4 * p + 4]) for p in range(pairs)]
+
+    def compensation_error_global(self, model, unit=1, which="forward", window=None):
+        """Residual statistics of draw_MVimage_global against the image it predicts over window (x0, y0, w, h) in pixels of the
+        padded plane: the dict of compensation_error.  Default window: the unpadded frame."""
+        return self._global_compensation_stats(which, model, unit, window)[0]
+
+    def _check_gm_grid_tensors(self, cells, exclude, what):
+        import torch
+        ch, cw = self.cells_shape
+        if not (cells.is_cuda and cells.dtype == torch.int16 and tuple(cells.shape) == (ch, cw, 2) and cells.stride(2) == 1
+                and cells.stride(1) == 2 and cells.stride(0) >= 2 * cw and cells.stride(0) % 2 == 0 and cells.data_ptr() % 4 == 0):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: cells must be an int16 CUDA tensor of shape (%d, %d, 2) with packed cells "
+                                  "and rows a whole number of cells apart" % (what, ch, cw))
+        if exclude is not None and not (exclude.is_cuda and exclude.dtype == torch.uint8 and tuple(exclude.shape) == (ch, cw)
+                                        and exclude.stride(1) == 1 and exclude.stride(0) >= cw):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: exclude must be a uint8 CUDA tensor of shape (%d, %d) with unit column "
+                                  "stride" % (what, ch, cw))
+
+    def cells_vector_histogram_device(self, cells, hist, exclude=None, window=None, stream=None):
+        """The histogram part of the global motion rule on any grid in HBM: cells an int16 CUDA tensor (CH, CW, 2) whose rows may
+        be further apart than CW cells, exclude a uint8 CUDA tensor (CH, CW) with unit column stride (non-zero = excluded) or
+        None, hist a contiguous int32 or uint32 CUDA tensor of 2 x 2048 (zeroed and filled), window (cx0, cy0, cw, ch) in
+        cells (None = all).  On the given HIP stream handle (default: the context's), ordered behind the context's stream; no
+        host wait.  Needs no estimate."""
+        import torch
+        what = "cells_vector_histogram_device"
+        self._check_gm_grid_tensors(cells, exclude, what)
+        if not (hist.is_cuda and hist.dtype in (torch.int32, torch.uint32) and hist.numel() == 4096 and hist.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: hist must be a contiguous int32 or uint32 CUDA tensor of 4096" % what)
+        self._behind_torch(cells, exclude, hist)
+        _capi.check(self._lib.bbme_cells_vector_histogram_device(
+            self._ctx, _ptr(cells), cells.stride(0) // 2, _ptr(exclude), exclude.stride(0) if exclude is not None else 0,
+            _window(window), _ptr(hist), C.c_void_p(stream or 0)))
+        return hist
+
+    def cells_global_moments_device(self, cells, model, tol_q16, exclude=None, map=None, words=None, window=None, stream=None):
+        """The moments part of the global motion rule on any grid in HBM: cells and exclude as for
+        cells_vector_histogram_device, model six int32 (host), tol_q16 the tolerance in Q16 grid units; map a uint8 CUDA tensor
+        (CH, CW) with unit column stride whose rows may be further apart than CW; words a contiguous int64 CUDA tensor of 16.
+        Same stream rules; no host wait."""
+        import torch
+        what = "cells_global_moments_device"
+        ch, cw = self.cells_shape
+        self._check_gm_grid_tensors(cells, exclude, what)
+        if map is None and words is None:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: neither map nor words" % what)
+        if map is not None and not (map.is_cuda and map.dtype == torch.uint8 and tuple(map.shape) == (ch, cw) and map.stride(1) == 1
+                                    and map.stride(0) >= cw):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: map must be a uint8 CUDA tensor of shape (%d, %d) with unit column stride"
+                                  % (what, ch, cw))
+        if words is not None and not (words.is_cuda and words.dtype in (torch.int64, torch.uint64) and words.numel() == 16
+                                      and words.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: words must be a contiguous int64 CUDA tensor of 16" % what)
+        model = _gm_model(model, what)
+        self._behind_torch(cells, exclude, map, words)
+        _capi.check(self._lib.bbme_cells_global_moments_device(
+            self._ctx, _ptr(cells), cells.stride(0) // 2, _ptr(exclude), exclude.stride(0) if exclude is not None else 0,
+            model.ctypes.data, int(tol_q16), _window(window), _ptr(map), map.stride(0) if map is not None else 0, _ptr(words),
+            C.c_void_p(stream or 0)))
+        return map, words
+
+    def cells_global_compensate_device(self, i1, i2, model, unit=1, out=None, stats=None, fill=0, window=None, stream=None):
+        """The global compensation rule on any planes in HBM: i1 (None without stats), i2 contiguous uint8 CUDA tensors
+        (H_pad, W_pad); model six int32 (host) in grid units of 1 / unit pixel; out a uint8 CUDA tensor (H_pad, W_pad) with unit
+        column stride whose rows may be further apart than W_pad; stats an int64 or uint64 CUDA tensor of 4 (sse, sad, pixels,
+        skipped) over window (x0, y0, w, h) in pixels (None = the whole plane).  Same stream rules; no host wait.  Needs no
+        frames and no estimate."""
+        import torch
+        what = "cells_global_compensate_device"
+        ch, cw = self.cells_shape
+        for t in (i2,) if i1 is None and stats is None else (i1, i2):
+            if t is None or not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (2 * ch, 2 * cw) and t.is_contiguous()):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: planes must be contiguous uint8 CUDA tensors of shape (%d, %d)"
+                                      % (what, 2 * ch, 2 * cw))
+        if out is None and stats is None:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: neither out nor stats" % what)
+        if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (2 * ch, 2 * cw)
+                                    and out.stride(1) == 1 and out.stride(0) >= 2 * cw):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape (%d, %d) with unit column stride"
+                                  % (what, 2 * ch, 2 * cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 4" % what)
+        model = _gm_model(model, what)
+        self._behind_torch(i1, i2, out, stats)
+        _capi.check(self._lib.bbme_cells_global_compensate_device(
+            self._ctx, _ptr(i1), _ptr(i2), model.ctypes.data, int(unit), int(fill), _window(window), _ptr(out),
+            out.stride(0) if out is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
+        return out, stats
+
     # -- colour coding of the field: Flow::MotionToColor on the GPU, from the cells (the colour rule of include/bbme.h) ----------
     def color_shape(self, scale=None):
         """(rows, cols, 3) of the colour image: the subsampled field's size; scale defaults to upsample."""
@@ -1389,6 +1535,24 @@ class MFBatch(MF):
         """MF.compensation_error_subpel of every pair, in order, from one refinement and one compensation launch."""
         return self._subpel_compensation_stats(which, window)
 
+    def global_motion_all(self, which="forward", subpel=False, kind="affine", tol=1.0, iterations=3, mask_tol=None, window=None,
+                          maps=False):
+        """MF.global_motion of every pair, in order, from one launch per step -> list of dicts; maps=True adds each pair's map
+        (one more launch and download per pair)."""
+        out = self._global_motion(which, subpel, kind, tol, iterations, mask_tol, window)
+        if maps:
+            for p, d in enumerate(out):
+                d["map"] = self._global_motion_map(p, which, subpel, mask_tol, d["model"], tol, None, "global_motion_all")
+        return out
+
+    def get_pair_global_compensated(self, pair, model, unit=1, which="forward", fill=0, out=None):
+        """MF.draw_MVimage_global of one pair."""
+        return self._get_global_compensated(pair, which, model, unit, fill, out, "get_pair_global_compensated")
+
+    def compensation_errors_global(self, models, unit=1, which="forward", window=None):
+        """MF.compensation_error_global of every pair under its own model (models: (pairs, 6) int32), from one launch."""
+        return self._global_compensation_stats(which, models, unit, window)
+
     def consistency_stats_all(self, which="forward", tol=1, window=None):
         """MF.consistency_stats of every pair, in order, from one launch."""
         return self._consistency_stats(which, tol, window)
@@ -1697,6 +1861,119 @@ def compensate_cells_subpel(image1, image2, q4, fill=0, window=None):
     _capi.check(_capi.lib().bbme_subpel_compensate_host(image1.ctypes.data, image2.ctypes.data, w, h, q4.ctypes.data, int(fill),
                                                         _window(window), out.ctypes.data, s))
     return out, _residual_dict(list(s))
+
+
+GM_TRANSLATION, GM_AFFINE = 0, 1                          # `kind` of the global motion rule
+GM_INLIER, GM_OUTLIER, GM_EXCLUDED = 0, 1, 2             # classes of a global motion map
+GM_BINS = 2048
+GM_STAT_KEYS = ("inliers", "outliers", "excluded", "residual", "sum_x", "sum_y", "sum_xx", "sum_xy", "sum_yy", "sum_dx", "sum_dy",
+                "sum_x_dx", "sum_y_dx", "sum_x_dy", "sum_y_dy", "sum_sq")
+
+
+def _gm_kind(kind):
+    if kind in ("translation", GM_TRANSLATION):
+        return GM_TRANSLATION
+    if kind in ("affine", GM_AFFINE):
+        return GM_AFFINE
+    raise _capi.BbmeError(_capi.ERR_INVALID, "kind must be 'translation' or 'affine', not %r" % (kind,))
+
+
+def _gm_tol(tol, unit):
+    """A tolerance in pixels as Q16 grid units of 1 / unit pixel."""
+    return int(round(float(tol) * unit * 65536.0))
+
+
+def _gm_model(model, what):
+    model = np.ascontiguousarray(model, np.int32).reshape(-1)
+    if model.size != 6:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: a model is six int32" % what)
+    return model
+
+
+def _gm_dict(model, words, unit):
+    model = np.array(model, np.int32)
+    return dict(model=model, unit=unit, translation=(model[0] / 65536.0 / unit, model[3] / 65536.0 / unit),
+                statistics=dict(zip(GM_STAT_KEYS, [int(v) for v in words])))
+
+
+def _gm_grid(cells, exclude, what):
+    """(cells, exclude, exclude pitch, cw, ch) of a grid and its optional exclusion mask, whose rows may be strided."""
+    cells = np.ascontiguousarray(cells, np.int16)
+    if cells.ndim != 3 or cells.shape[2] != 2:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: an int16 grid (CH, CW, 2)" % what)
+    ch, cw = cells.shape[:2]
+    pitch = 0
+    if exclude is not None:
+        exclude = np.asarray(exclude, np.uint8)
+        if exclude.shape != (ch, cw) or exclude.strides[1] != 1 or exclude.strides[0] < cw:
+            exclude = np.ascontiguousarray(exclude)
+        if exclude.shape != (ch, cw):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: exclude must be a uint8 array (%d, %d)" % (what, ch, cw))
+        pitch = exclude.strides[0]
+    return cells, exclude, pitch, cw, ch
+
+
+def vector_histogram_cells(cells, exclude=None, window=None):
+    """The histogram part of the global motion rule on the CPU (bbme_vector_histogram_host): cells an int16 (CH, CW, 2) grid,
+    exclude a uint8 (CH, CW) mask (non-zero = excluded) or None -> (2, 2048) uint32, row 0 for dx, row 1 for dy, over window
+    (cx0, cy0, cw, ch) in cells, None = all cells."""
+    cells, exclude, pitch, cw, ch = _gm_grid(cells, exclude, "vector_histogram_cells")
+    hist = np.empty((2, GM_BINS), np.uint32)
+    _capi.check(_capi.lib().bbme_vector_histogram_host(cells.ctypes.data, cw, ch, _ptr(exclude), pitch, _window(window), hist.ctypes.data))
+    return hist
+
+
+def global_moments_cells(cells, model, tol_q16, exclude=None, window=None):
+    """The moments part of the global motion rule on the CPU (bbme_global_moments_host) -> (map (CH, CW) uint8, words (16,)
+    int64): model six int32 in Q16, tol_q16 the tolerance in Q16 grid units."""
+    cells, exclude, pitch, cw, ch = _gm_grid(cells, exclude, "global_moments_cells")
+    model = _gm_model(model, "global_moments_cells")
+    gmap = np.empty((ch, cw), np.uint8)
+    words = np.empty(16, np.int64)
+    _capi.check(_capi.lib().bbme_global_moments_host(cells.ctypes.data, cw, ch, _ptr(exclude), pitch, model.ctypes.data, int(tol_q16),
+                                                     _window(window), gmap.ctypes.data, words.ctypes.data))
+    return gmap, words
+
+
+def solve_global_motion(words, kind="affine"):
+    """The solve part of the global motion rule (bbme_global_motion_solve_host): sixteen int64 words -> six int32 in Q16."""
+    words = np.ascontiguousarray(words, np.int64).reshape(-1)
+    if words.size != 16:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "solve_global_motion: sixteen int64 words")
+    model = np.empty(6, np.int32)
+    _capi.check(_capi.lib().bbme_global_motion_solve_host(words.ctypes.data, _gm_kind(kind), model.ctypes.data))
+    return model
+
+
+def global_motion_cells(cells, kind="affine", tol_q16=65536, iterations=3, exclude=None, window=None):
+    """The whole estimate of the global motion rule on the CPU (bbme_global_motion_host) -> (model (6,) int32, words (16,)
+    int64, map (CH, CW) uint8)."""
+    cells, exclude, pitch, cw, ch = _gm_grid(cells, exclude, "global_motion_cells")
+    model = np.empty(6, np.int32)
+    words = np.empty(16, np.int64)
+    gmap = np.empty((ch, cw), np.uint8)
+    _capi.check(_capi.lib().bbme_global_motion_host(cells.ctypes.data, cw, ch, _ptr(exclude), pitch, _gm_kind(kind), int(tol_q16),
+                                                    int(iterations), _window(window), model.ctypes.data, words.ctypes.data,
+                                                    gmap.ctypes.data))
+    return model, words, gmap
+
+
+def global_compensate(image1, image2, model, unit=1, fill=0, window=None):
+    """The global compensation rule on the CPU (bbme_global_compensate_host): image1 (None without statistics), image2 uint8
+    (H, W) planes (both even), model six int32 in Q16 grid units of 1 / unit pixel -> (compensated plane (H, W) uint8,
+    dict(sse, sad, pixels, skipped, mse, psnr) against image1 over window (x0, y0, w, h) in pixels, or None without image1)."""
+    image2 = np.ascontiguousarray(image2, np.uint8)
+    if image1 is not None:
+        image1 = np.ascontiguousarray(image1, np.uint8)
+    if image2.ndim != 2 or (image1 is not None and image1.shape != image2.shape):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "global_compensate: uint8 planes of one shape (H, W)")
+    model = _gm_model(model, "global_compensate")
+    h, w = image2.shape
+    out = np.empty((h, w), np.uint8)
+    s = (C.c_ulonglong * 4)() if image1 is not None else None
+    _capi.check(_capi.lib().bbme_global_compensate_host(_ptr(image1), image2.ctypes.data, w, h, model.ctypes.data, int(unit), int(fill),
+                                                        _window(window), out.ctypes.data, s))
+    return out, (_residual_dict(list(s)) if s is not None else None)
 
 
 def cells_consistency(a, b, tol=1, window=None):

@@ -559,6 +559,89 @@ def denoise_frames_wide(frames, search_size, block_size, strength, device=None, 
     return out
 
 
+def compose_global_models(models, unit=1):
+    """Per-pair models of the global motion rule (six Q16 int32 each, grid units of 1 / unit pixel over half pixels from the plane
+    centre) -> the cumulative motions (len(models) + 1, 6) float64, pixels and pixels per half pixel: row f is the displacement
+    that takes a position of frame 0 to where frame 0's content lies in frame f (row 0 is zero).  Pair p's model is the map
+    T_p(P) = P + 2 d_p(P) on half-pixel positions P; the cumulative map is T_{f-1} o ... o T_0, composed in double."""
+    cum = np.zeros((len(models) + 1, 6), np.float64)
+    A, t = np.eye(2), np.zeros(2)                          # half-pixel position in frame f = A P + t
+    for f, m in enumerate(models):
+        m = np.asarray(m, np.float64) / 65536.0 / unit
+        Ap, tp = np.eye(2) + 2.0 * np.array([[m[1], m[2]], [m[4], m[5]]]), 2.0 * np.array([m[0], m[3]])
+        A, t = Ap @ A, Ap @ t + tp
+        D = (A - np.eye(2)) / 2.0
+        cum[f + 1] = (t[0] / 2.0, D[0, 0], D[0, 1], t[1] / 2.0, D[1, 0], D[1, 1])
+    return cum
+
+
+def stabilization_corrections(models, radius=None, unit=1):
+    """The correction of every frame as six Q16 int32 in pixels (unit 1 of the global compensation rule), (len(models) + 1, 6):
+    radius=None locks every frame to frame 0 -- the correction is the cumulative motion --; an integer radius subtracts the
+    moving average of the cumulative motions over the frames f - radius .. f + radius, the window clipped at the video's ends.
+    In double, then rint(value * 65536) (half to even)."""
+    cum = compose_global_models(models, unit)
+    n = len(cum)
+    corr = cum.copy()
+    if radius is not None:
+        r = int(radius)
+        if r < 0:
+            raise ValueError("stabilization_corrections: radius must be None or at least 0")
+        for f in range(n):
+            corr[f] = cum[f] - cum[max(0, f - r):min(n, f + r + 1)].mean(axis=0)
+    return np.clip(np.rint(corr * 65536.0), -2.0 ** 31, 2.0 ** 31 - 1).astype(np.int32)
+
+
+def stabilize_frames(frames, search_size, block_size, radius=None, kind="translation", tol=1.0, iterations=3, fill=0, device=None,
+                     in_flight=4, batch=2):
+    """Stabilisation of a grey video on ONE GPU from the dominant motion of its consecutive pairs (the global motion rule and the
+    global compensation rule of include/bbme.h) -> (frames, models, corrections): len(frames) unpadded uint8 (H, W) frames, the
+    per-pair models (P, 6) int32 (unit 1: pixels over half pixels from the plane centre) and the per-frame corrections
+    (P + 1, 6) int32 each frame was warped by (stabilization_corrections).  The pairs are estimated on chain contexts
+    (estimate_frames_pipelined's plan: every frame is set once), every pair's model comes from MFChain.global_motion_all, and a
+    copy of every frame's padded level-0 plane stays in HBM; the models are composed and smoothed on the host in double; then
+    every plane is warped by the global compensation kernel (MF.cells_global_compensate_device, no image 1) and the unpadded
+    frame cut out of it.  A pixel whose source lies in the padding takes the padding's zero, one whose source lies outside the
+    padded plane takes `fill`.  radius=None locks every frame to frame 0; an integer radius follows the smoothed path.  A colour
+    video is BbmeError (ERR_UNSUPPORTED): the warp is grey."""
+    import torch
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    if frames and frames[0].ndim == 3:
+        raise _capi.BbmeError(_capi.ERR_UNSUPPORTED, "stabilize_frames: a colour video: the global compensation rule is grey")
+    n = len(frames)
+    if n < 2:
+        return frames, np.zeros((0, 6), np.int32), np.zeros((n, 6), np.int32)
+    if device is None:
+        device = local_device()
+    models = np.zeros((n - 1, 6), np.int32)
+    planes = [None] * n
+
+    def collect(mf, first, count):
+        got = mf.global_motion_all(kind=kind, tol=tol, iterations=iterations)         # waits for this context's stream
+        for p in range(count):
+            models[first + p] = got[p]["model"]
+            for which in (0, 1):
+                if planes[first + p + which] is None:
+                    planes[first + p + which] = mf.frame_plane_tensor(p, which).clone()
+        torch.cuda.synchronize(device)                                                # the copies, before the planes roll
+
+    _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect)
+    corrections = stabilization_corrections(models, radius)
+    from .motion_framework import MF
+    out = [None] * n
+    mf = MF(frames[0], frames[0], search_size, block_size, len(block_size), device=device)
+    try:
+        h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
+        warped = torch.empty((mf.padded_height, mf.padded_width), dtype=torch.uint8, device=planes[0].device)
+        for f in range(n):
+            mf.cells_global_compensate_device(None, planes[f], corrections[f], unit=1, out=warped, fill=fill)
+            mf.synchronize()
+            out[f] = np.ascontiguousarray(warped.cpu().numpy()[py:py + h, px:px + w])
+    finally:
+        mf.close()
+    return out, models, corrections
+
+
 def colorize_frames(frames, search_size, block_size, maxmotion=-1.0, scale=1, in_flight=4, batch=2, device=None):
     """The colour-coded forward field of the len(frames) - 1 consecutive pairs of a video on ONE GPU (the colour rule of
     include/bbme.h at subsampling `scale`): -> ((P, oh, ow, 3) uint8 B,G,R images, (P, 5) float32 ranges (max radius, min u,

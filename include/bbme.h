@@ -1149,6 +1149,113 @@ int bbme_wide_temporal_filter_chain_device(bbme_ctx *ctx, int first, int count, 
 int bbme_get_wide_temporal_filtered_host(bbme_ctx *ctx, int slot, int thr, uint8_t *out);
 int bbme_wide_temporal_filter_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 
+/* GLOBAL MOTION RULE (this project's own; the reference has no parametric motion): the dominant motion of a cell grid as a
+ * translation or an affine model, and the cells that follow it.  Inputs: a grid Q of CH x CW int16 (dx, dy), CH = H0 / 2,
+ * CW = W0 / 2, in GRID UNITS of 1 / unit pixel (unit = 1: integer cells; unit = 4: quarter-pel cells "4 v + q"); optionally an
+ * exclusion mask E, one byte per cell (rows exclude_pitch bytes apart), non-zero = excluded -- a consistency mask can be fed as it
+ * is --; a window {cx0, cy0, cw, ch} IN CELLS (NULL = all cells).  Any int16 values are allowed.
+ * Coordinates are HALF PIXELS FROM THE PLANE CENTRE, so that all of them are integers: cell (cx, cy) lies at X = 4 cx + 2 - W0,
+ * Y = 4 cy + 2 - H0, pixel (x, y) at X = 2 x + 1 - W0, Y = 2 y + 1 - H0; they stay plane-centred whatever the window is.
+ * A MODEL is six int32 in Q16, m0..m2 for u and m3..m5 for v: pu = m0 + m1 X + m2 Y and pv = m3 + m4 X + m5 Y in 64-bit
+ * integers; m0 and m3 are in grid units, the slopes in grid units per half pixel.
+ * Histogram part.  Over the window's cells that E does not exclude, two histograms of BBME_GM_BINS = 2048 uint32 bins, hist[b] for
+ * dx and hist[2048 + b] for dy, bin(v) = clamp(v, -1024, 1023) + 1024.  n = the sum of one histogram; the MEDIAN of a component is
+ * the smallest bin whose cumulative count is >= (n + 1) >> 1, minus 1024, and 0 when n = 0.
+ * Moments part, under a model and a tolerance tol_q16 (0 .. 2^40).  A cell is class BBME_GM_EXCLUDED if E excludes it; otherwise
+ * r = |(dx << 16) - pu| + |(dy << 16) - pv| in 64 bits and the class is BBME_GM_INLIER if r <= tol_q16, else BBME_GM_OUTLIER.  The
+ * map is one class byte per cell, for EVERY cell of the grid.  The sixteen words, over the WINDOW's cells, are 64-bit integers:
+ *   [0] n0, [1] n1, [2] n2 (cells per class), [3] the sum of r over the inliers, and over the inliers [4] sum X, [5] sum Y,
+ *   [6] sum XX, [7] sum XY, [8] sum YY, [9] sum dx, [10] sum dy, [11] sum X dx, [12] sum Y dx, [13] sum X dy, [14] sum Y dy,
+ *   [15] sum (dx^2 + dy^2).
+ * They are exact two's-complement sums (|X|, |Y| < 2^13, a product below 2^28, r below 2^47; up to 2^24 cells), word 3 as long as
+ * n0 tol_q16 < 2^63; beyond that it is the sum modulo 2^64.  Hence BBME_ERR_UNSUPPORTED for W0 or H0 > 8188.
+ * Solve part (host code, one function for the GPU route and the CPU route, so both get the same model from the same words).
+ * Translation: m0 = [9] / n0, m3 = [10] / n0, slopes 0.  Affine: least squares of dx and of dy on (1, X, Y) over the inliers, in
+ * double from the centred scatter: with n = n0, xm = [4] / n, ym = [5] / n, Sxx = [6] - [4] xm, Sxy = [7] - [4] ym,
+ * Syy = [8] - [5] ym, Sxu = [11] - [4] um (um = [9] / n) and likewise Syu, Sxv, Syv, D = Sxx Syy - Sxy Sxy:
+ * a1 = (Sxu Syy - Syu Sxy) / D, a2 = (Syu Sxx - Sxu Sxy) / D, a0 = um - a1 xm - a2 ym (Cramer's rule), no fused multiply-add.
+ * The affine model is used only if n0 >= 3, Sxx > 0, Syy > 0 and D > Sxx Syy / 2^20; otherwise the translation is.  Each parameter
+ * is llrint(value * 65536) (half to even) saturated to int32.  n0 = 0 gives the zero model.  Every moment stays below 2^53.
+ * Estimate.  iterations in 0..8.  The histogram; n = 0: the model is zero.  Otherwise model = (median_x << 16, 0, 0,
+ * median_y << 16, 0, 0).  Then `iterations` times: moments(model, tol_q16); stop if n0 = 0; model = solve(kind).  A last moments
+ * pass under the final model gives the sixteen words and the map.
+ * Limit: the start is the component-wise median.  When independently moving cells outnumber, in one component's histogram, the
+ * spread of a strongly zooming or rotating background, the median starts on them and the fit can stay there (README.md).
+ * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, `kind` not one of the
+ * two, tol_q16 outside 0..2^40, iterations outside 0..8, unit not 1 or 4, a pitch < CW, a window as for the consistency rule;
+ * BBME_ERR_UNSUPPORTED beyond 8188; BBME_ERR_STATE for the context's own calls exactly as bbme_subpel_device (frames, cells of
+ * `which`) and, with mask_tol >= 0, as bbme_consistency_stats (a valid pair of fields).  None of these calls changes context state
+ * (grids, memo, flow, cells, backward cells, captured graphs, colour store); their scratch buffers are the context's own and
+ * independent of the other getters'.  All work on single, batched and chain contexts and in direction BACKWARD.
+ * bbme_vector_histogram_host / bbme_global_moments_host / bbme_global_motion_solve_host / bbme_global_motion_host: the parts and
+ * the whole estimate on the CPU, no GPU, on a packed cells_h x cells_w grid; exclude may be NULL; map (packed) and words16 each
+ * may be NULL, not both (bbme_global_motion_host: model is required, words16 and map are optional).
+ * bbme_cells_vector_histogram_device: ANY grid in HBM of the context's cell geometry, rows cells_pitch_cells int16 pairs apart;
+ * d_hist (4096 uint32) is zeroed and filled on hip_stream (NULL = the ctx stream; another stream is first ordered behind it); no
+ * host wait; needs no estimate and no scratch.
+ * bbme_cells_global_moments_device: the same for the moments; d_map (rows map_pitch bytes apart) and d_words16 each may be null,
+ * not both.  Launches with d_words16 share one scratch buffer per context: the caller orders those it issues on different streams.
+ * bbme_global_motion: the estimate of EVERY pair of the context, one launch per step over all pairs with a device table of
+ * models; models[6 p + k], words[16 p + k].  which = 0: the current level-0 cells, which = 1: the backward cells; subpel = 1
+ * refines them first as bbme_subpel_device does and the grid unit is 4, else 1; mask_tol >= 0 excludes the cells that the
+ * CONSISTENCY RULE of (which, mask_tol) does not call consistent, mask_tol < 0 excludes none.  It SYNCHRONISES AT EVERY STEP: the
+ * 16 KB of counts per pair come down once and 128 bytes per pair after each moments pass, the solve runs on the host.
+ * bbme_get_global_motion_map_host: the class map of `pair` under `model` for the same selection of cells; synchronises; packed
+ * CH x CW bytes. */
+enum { BBME_GM_TRANSLATION = 0, BBME_GM_AFFINE = 1 };
+enum { BBME_GM_INLIER = 0, BBME_GM_OUTLIER = 1, BBME_GM_EXCLUDED = 2 };
+enum { BBME_GM_BINS = 2048 };
+int bbme_vector_histogram_host(const int16_t *cells, int cells_w, int cells_h, const uint8_t *exclude, int exclude_pitch,
+                               const int *window, uint32_t *hist);
+int bbme_global_moments_host(const int16_t *cells, int cells_w, int cells_h, const uint8_t *exclude, int exclude_pitch,
+                             const int32_t *model, long long tol_q16, const int *window, uint8_t *map, long long *words16);
+int bbme_global_motion_solve_host(const long long *words16, int kind, int32_t *model);
+int bbme_global_motion_host(const int16_t *cells, int cells_w, int cells_h, const uint8_t *exclude, int exclude_pitch, int kind,
+                            long long tol_q16, int iterations, const int *window, int32_t *model, long long *words16, uint8_t *map);
+int bbme_cells_vector_histogram_device(bbme_ctx *ctx, const int16_t *d_cells, int cells_pitch_cells, const uint8_t *d_exclude,
+                                       int exclude_pitch, const int *window, uint32_t *d_hist, void *hip_stream);
+int bbme_cells_global_moments_device(bbme_ctx *ctx, const int16_t *d_cells, int cells_pitch_cells, const uint8_t *d_exclude,
+                                     int exclude_pitch, const int32_t *model, long long tol_q16, const int *window, uint8_t *d_map,
+                                     int map_pitch, long long *d_words16, void *hip_stream);
+int bbme_global_motion(bbme_ctx *ctx, int which, int subpel, int kind, long long tol_q16, int iterations, int mask_tol,
+                       const int *window, int32_t *models, long long *words);
+int bbme_get_global_motion_map_host(bbme_ctx *ctx, int pair, int which, int subpel, int mask_tol, const int32_t *model,
+                                    long long tol_q16, uint8_t *map);
+
+/* GLOBAL COMPENSATION RULE (this project's own): the frame compensated for a model's motion alone, pixel by pixel, and its
+ * residual statistics.  Inputs: two packed planes I1 and I2 of W0 x H0 bytes (I1 for the statistics only), a model of the GLOBAL
+ * MOTION RULE and its grid unit (1 or 4).  For pixel (x, y) with its X, Y of that rule: d = (pu, pv);
+ * q = (d (4 / unit) + 32768) >> 16, the arithmetic shift in 64 bits: the displacement in quarter pels; i = q >> 2, f = q & 3,
+ * s = (x, y) + i.  The pixel is COMPENSATED when every tap of non-zero weight lies in the plane: 0 <= s.x, s.x + 1 + (fx != 0) <= W0,
+ * 0 <= s.y and s.y + 1 + (fy != 0) <= H0; it is then the SUBPEL RULE's sample of I2 at s with the fractions f.  Otherwise it gets
+ * `fill` (0..255) and counts as skipped.  No byte outside the plane is read.
+ * Statistics: the four of the SUBPEL COMPENSATION RULE -- sse, sad, pixels, skipped against I1 over a window {x0, y0, w, h} in
+ * PIXELS (NULL = the whole plane) --, exact and independent of `fill`.
+ * Property.  With a whole-pixel translation model (m0 = tx unit << 16, m3 = ty unit << 16, slopes 0), out[y][x] =
+ * I2[y + ty][x + tx] wherever that lies in the plane.
+ * Errors: as for the SUBPEL COMPENSATION RULE's calls, with unit not 1 or 4 BBME_ERR_INVALID; the context's own calls need frames
+ * only (BBME_ERR_STATE without; no estimate).  No call changes context state.
+ * bbme_global_compensate_host: the rule on the CPU, no GPU, on packed width x height planes (both even); image1 may be NULL without
+ * statistics; out (packed) and stats4 each may be NULL, not both.
+ * bbme_cells_global_compensate_device: ANY packed planes in HBM of the context's level-0 geometry; d_image1 may be null without
+ * d_stats4; d_out (rows out_pitch bytes apart) and d_stats4 each may be null, not both; on hip_stream as above; no host wait.
+ * Launches with d_stats4 share one scratch buffer per context: the caller orders those it issues on different streams.
+ * bbme_global_compensate_device: the context's own planes of `pair`: which = 0 predicts image 1 from image 2 (in direction BACKWARD
+ * the planes exchange as for every plane-reading call), which = 1 image 2 from image 1.  On a chain the planes are slots pair and
+ * pair + 1.  A colour context compensates its luma planes.
+ * bbme_get_global_compensated_host: the same; synchronises; the packed padded W0 x H0 plane.
+ * bbme_global_compensation_error: EVERY pair from one launch under its own model, models[6 p + k], stats[4 p + k]; synchronises. */
+int bbme_global_compensate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int32_t *model, int unit,
+                                int fill, const int *window, uint8_t *out, unsigned long long *stats4);
+int bbme_cells_global_compensate_device(bbme_ctx *ctx, const uint8_t *d_image1, const uint8_t *d_image2, const int32_t *model, int unit,
+                                        int fill, const int *window, uint8_t *d_out, int out_pitch, unsigned long long *d_stats4,
+                                        void *hip_stream);
+int bbme_global_compensate_device(bbme_ctx *ctx, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *d_out,
+                                  int out_pitch, void *hip_stream);
+int bbme_get_global_compensated_host(bbme_ctx *ctx, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *out);
+int bbme_global_compensation_error(bbme_ctx *ctx, int which, const int32_t *models, int unit, const int *window,
+                                   unsigned long long *stats);
+
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
 /* copyMVs (:828-843) + calcLevelBM (:226-244) of one level.  Leaves that level's MV
