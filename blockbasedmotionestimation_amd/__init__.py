@@ -10,7 +10,7 @@ from .motion_framework import (MF, MFBatch, MFChain, plan_padding, pad_zero, pyr
                                temporal_filter_cells_bgr, subpel_cells, compensate_cells_subpel, interpolate_cells_subpel,
                                interpolate_cells_subpel_bgr, temporal_filter_cells_subpel, temporal_filter_cells_subpel_bgr,
                                compose_cells, temporal_filter_cells_wide, vector_histogram_cells, global_moments_cells,
-                               solve_global_motion, global_motion_cells, global_compensate,
+                               solve_global_motion, global_motion_cells, global_compensate, global_compensate_bgr,
                                DIR_FORWARD, DIR_BACKWARD, FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE)
 from .rw_flow import Flow, FlowWriter, subsample_div4  # noqa: F401
 from .synth import synth_pair, synth_video, warp_pair_from_flow  # noqa: F401
@@ -21,4 +21,4 @@ __all__ = ["MF", "MFBatch", "MFChain", "Flow", "FlowWriter", "BbmeError", "plan_
            "temporal_filter_cells", "temporal_filter_cells_bgr", "subpel_cells", "compensate_cells_subpel",
            "interpolate_cells_subpel", "interpolate_cells_subpel_bgr", "temporal_filter_cells_subpel",
            "temporal_filter_cells_subpel_bgr", "compose_cells", "temporal_filter_cells_wide", "vector_histogram_cells",
-           "global_moments_cells", "solve_global_motion", "global_motion_cells", "global_compensate"]
+           "global_moments_cells", "solve_global_motion", "global_motion_cells", "global_compensate", "global_compensate_bgr"]

@@ -370,6 +370,11 @@ struct bbme_ctx {
     DevBuf<uint8_t> gm_mask;                      // with mask_tol >= 0: the consistency mask of every pair, packed
     StatsScratch gc_stats;                        // bbme_global_compensation_error (every pair) and
                                                   // bbme_cells_global_compensate_device (one pair)
+    // BGR GLOBAL COMPENSATION RULE, allocated at first use and at one size, so neither is replaced under a launch that reads it
+    StatsScratch gcb_stats;                       // bbme_global_compensation_error_bgr (every pair) and
+                                                  // bbme_cells_global_compensate_bgr_device (BBME_GC_MAX_FRAMES frames)
+    DevBuf<int32_t> gcb_models;                   // the device tables of models, six words per frame: every pair's of the context's own
+                                                  // calls (BBME_MAX_BATCH), then a caller's run (BBME_GC_MAX_FRAMES)
 };
 
 namespace {
@@ -4168,6 +4173,159 @@ int bbme_global_compensation_error(bbme_ctx *c, int which, const int32_t *models
         HIP_TRY(hipMemcpyAsync(c->gm_models, models, (size_t)6 * c->batch * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         return enqueue_gc(c, i1, i2, c->lv[0].plane_stride, c->batch, c->gm_models, nullptr, unit, 0, window, nullptr, 0,
                           c->gc_stats.partials_all(), c->gc_stats.results(), c->stream);
+    });
+}
+
+// ---- the same on the B,G,R frames (the BGR GLOBAL COMPENSATION RULE of include/bbme.h; K18b k_global_compensate_bgr) ----------
+
+static long long gcb_groups(const bbme_ctx *c) { return gather_groups(c->geom.width, c->geom.height, kGcBgrRunsPerLane); }
+
+// result words of every pair, partials of a launch over every pair, then those of a caller's longest run: one size per context
+static int gcb_scratch(bbme_ctx *c)
+{
+    return c->gcb_stats.ensure(BBME_MAX_BATCH, gcb_groups(c), c->batch, BBME_GC_MAX_FRAMES, "the colour global compensation statistics");
+}
+
+static int gcb_tables(bbme_ctx *c)
+{
+    return c->gcb_models.ensure((size_t)6 * (BBME_MAX_BATCH + BBME_GC_MAX_FRAMES), "the colour global compensation models", Fill::poison);
+}
+static int32_t *gcb_table_caller(const bbme_ctx *c) { return c->gcb_models + (size_t)6 * BBME_MAX_BATCH; }
+
+// unit, fill, the padded plane's limit and a window in pixels of the FRAME.  Touches no device.
+static int check_gcb(const bbme_ctx *c, const int32_t *model, int unit, int fill, const int *window, const char *what)
+{
+    const Level &L = c->lv[0];
+    if (!model) return bbme::fail(BBME_ERR_INVALID, "%s: null model", what);
+    if (unit != 1 && unit != 4) return bbme::fail(BBME_ERR_INVALID, "%s: unit %d (1 or 4)", what, unit);
+    if (int rc = check_fill(fill, what)) return rc;
+    if (L.width > 8188 || L.height > 8188)
+        return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: a %dx%d plane is beyond 8188", what, L.width, L.height);
+    if (!window || (window[0] >= 0 && window[1] >= 0 && window[2] >= 1 && window[3] >= 1 &&
+                    (long long)window[0] + window[2] <= c->geom.width && (long long)window[1] + window[3] <= c->geom.height))
+        return BBME_OK;
+    return bbme::fail(BBME_ERR_INVALID, "%s: window (%d, %d, %d, %d) is not inside the %dx%d frame", what, window[0], window[1],
+                      window[2], window[3], c->geom.width, c->geom.height);
+}
+
+// k_global_compensate_bgr over `count` frames (frame_stride bytes apart in both inputs, out_stride in the output) under the models
+// of the device table d_models (six words per frame) or, without one, under `model`: the frames into d_out and / or, with
+// d_stats, the statistics of every frame over `window` in frame pixels
+static int enqueue_gcb(bbme_ctx *c, const uint8_t *bgr1, const uint8_t *bgr2, int bgr_pitch, size_t frame_stride, int count,
+                       const int32_t *d_models, const int32_t *model, int unit, int fill, const int *window, uint8_t *d_out,
+                       int out_pitch, size_t out_stride, unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
+{
+    GcBgrArgs a{};
+    a.bgr1 = bgr1; a.bgr2 = bgr2; a.out = d_out;
+    a.models = d_models;
+    if (model) std::copy(model, model + 6, a.model);
+    a.frame_stride = frame_stride; a.out_stride = out_stride;
+    a.fw = c->geom.width; a.fh = c->geom.height; a.pad_x = c->geom.pad_x; a.pad_y = c->geom.pad_y;
+    a.bgr_pitch = bgr_pitch; a.out_pitch = out_pitch; a.mul = 4 / unit; a.fill = fill;
+    set_window(a, window, a.fw, a.fh);
+    set_runs(a, a.fw, a.fh);
+    return launch_gather(k_global_compensate_bgr<kGcBgrRunsPerLane>, a, gcb_groups(c), count, 1, partial, d_stats, stream);
+}
+
+int bbme_cells_global_compensate_bgr_device(bbme_ctx *c, const uint8_t *d_bgr1, const uint8_t *d_bgr2, int bgr_pitch, size_t frame_stride,
+                                            int count, const int32_t *models, int unit, int fill, const int *window, uint8_t *d_out,
+                                            int out_pitch, size_t out_stride, unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_global_compensate_bgr_device";
+    if (int rc = check_ctx(c)) return rc;
+    const int fw = c->geom.width, fh = c->geom.height;
+    if (!d_bgr2 || (!d_out && !d_stats4) || (d_stats4 && !d_bgr1)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (count < 1 || count > BBME_GC_MAX_FRAMES)
+        return bbme::fail(BBME_ERR_INVALID, "%s: %d frames (1..%d)", what, count, (int)BBME_GC_MAX_FRAMES);
+    if (int rc = check_gcb(c, models, unit, fill, window, what)) return rc;
+    if (int rc = check_frames(count, bgr_pitch, frame_stride, 3 * fw, fh, what, "colour")) return rc;
+    if (d_out) if (int rc = check_bgr_frames(c, count, out_pitch, out_stride, what)) return rc;
+    if (d_out) {                                            // the run of output frames against each run of input frames
+        const uintptr_t o0 = reinterpret_cast<uintptr_t>(d_out),
+                        o1 = o0 + (size_t)(count - 1) * out_stride + (size_t)out_pitch * (fh - 1) + (size_t)3 * fw;
+        for (const uint8_t *in : {d_bgr1, d_bgr2}) {
+            const uintptr_t i0 = reinterpret_cast<uintptr_t>(in),
+                            i1 = i0 + (size_t)(count - 1) * frame_stride + (size_t)bgr_pitch * (fh - 1) + (size_t)3 * fw;
+            if (in && o0 < i1 && i0 < o1) return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input frame", what);
+        }
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = gcb_scratch(c)) return rc;
+    if (count > 1) if (int rc = gcb_tables(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    const int32_t *table = nullptr;
+    if (count > 1) {                                        // one frame: its model travels in the arguments
+        HIP_TRY(hipMemcpyAsync(gcb_table_caller(c), models, (size_t)6 * count * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+        table = gcb_table_caller(c);
+    }
+    return enqueue_gcb(c, d_bgr1, d_bgr2, bgr_pitch, frame_stride, count, table, table ? nullptr : models, unit, fill, window, d_out,
+                       out_pitch, out_stride, d_stats4 ? c->gcb_stats.partials_caller() : nullptr, d_stats4, stream);
+}
+
+// The stored colour of `which`, pairs bgr_stride bytes apart, as gc_source names the planes: 0 predicts frame 1 from frame 2 of
+// the context's direction, 1 frame 2 from frame 1 as they were set.  Pairs pair0 .. pair0 + pairs - 1 need their colour.
+static int gcb_source(const bbme_ctx *c, int which, int pair0, int pairs, const char *what, const uint8_t **bgr1, const uint8_t **bgr2)
+{
+    if (int rc = check_which(which, what)) return rc;
+    if (!c->frames_set()) return bbme::fail(BBME_ERR_STATE, "%s: no frames set", what);
+    const int w1 = which ? 1 : c->direction ? 1 : 0, w2 = 1 - w1;
+    for (int p = pair0; p < pair0 + pairs; ++p)
+        if (!c->bgr.get() || !c->bgr_set[c->slot(p, 0)] || !c->bgr_set[c->slot(p, 1)])
+            return bbme::fail(BBME_ERR_STATE, "%s: pair %d has no stored colour (set both frames with a *_bgr setter)", what, p);
+    *bgr1 = c->bgr + (size_t)c->slot(pair0, w1) * c->bgr_stride;
+    *bgr2 = c->bgr + (size_t)c->slot(pair0, w2) * c->bgr_stride;
+    return BBME_OK;
+}
+
+int bbme_global_compensate_bgr_device(bbme_ctx *c, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *d_out,
+                                      int out_pitch, void *hip_stream)
+{
+    const char *what = "bbme_global_compensate_bgr_device";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_gcb(c, model, unit, fill, nullptr, what)) return rc;
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_bgr_frames(c, 1, out_pitch, 0, what)) return rc;
+    const uint8_t *b1, *b2;
+    if (int rc = gcb_source(c, which, pair, 1, what, &b1, &b2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_gcb(c, b1, b2, 3 * c->geom.width, 0, 1, nullptr, model, unit, fill, nullptr, d_out, out_pitch, 0, nullptr, nullptr,
+                       stream);
+}
+
+int bbme_get_global_compensated_bgr_host(bbme_ctx *c, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *out)
+{
+    const char *what = "bbme_get_global_compensated_bgr_host";
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_gcb(c, model, unit, fill, nullptr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const uint8_t *b1, *b2;
+    if (int rc = gcb_source(c, which, pair, 1, what, &b1, &b2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int row = 3 * c->geom.width;
+    return download_staged(c, (size_t)row * c->geom.height, "the globally compensated colour frame", out, [&](uint8_t *d) {
+        return enqueue_gcb(c, b1, b2, row, 0, 1, nullptr, model, unit, fill, nullptr, d, row, 0, nullptr, nullptr, c->stream);
+    });
+}
+
+int bbme_global_compensation_error_bgr(bbme_ctx *c, int which, const int32_t *models, int unit, const int *window,
+                                       unsigned long long *stats)
+{
+    const char *what = "bbme_global_compensation_error_bgr";
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_gcb(c, models, unit, 0, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    const uint8_t *b1, *b2;
+    if (int rc = gcb_source(c, which, 0, c->batch, what, &b1, &b2)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = gcb_scratch(c)) return rc;
+    if (int rc = gcb_tables(c)) return rc;
+    return download_stats(c, c->gcb_stats, c->batch, stats, [&] {
+        HIP_TRY(hipMemcpyAsync(c->gcb_models, models, (size_t)6 * c->batch * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        return enqueue_gcb(c, b1, b2, 3 * c->geom.width, c->bgr_stride, c->batch, c->gcb_models, nullptr, unit, 0, window, nullptr, 0, 0,
+                           c->gcb_stats.partials_all(), c->gcb_stats.results(), c->stream);
     });
 }
 

@@ -1214,6 +1214,63 @@ int bbme_global_compensate_host(const uint8_t *image1, const uint8_t *image2, in
     return BBME_OK;
 }
 
+// The BGR GLOBAL COMPENSATION RULE of include/bbme.h in the header's own words (the mirror of k_global_compensate_bgr): the grey
+// rule on the zero-padded view of a colour frame, in frame coordinates.  A tap outside the frame is the padding's 0 and is not
+// read; neither is a tap of weight 0.
+int bbme_global_compensate_bgr_host(const uint8_t *bgr1, const uint8_t *bgr2, int width, int height, int bgr_pitch, int pad_x, int pad_y,
+                                    const int32_t *model, int unit, int fill, const int *window, uint8_t *out, int out_pitch,
+                                    unsigned long long *stats4)
+{
+    const char *what = "bbme_global_compensate_bgr_host";
+    if (!bgr2 || !model || (!out && !stats4) || (stats4 && !bgr1)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 1 || height < 1 || pad_x < 0 || pad_y < 0 || (long long)width + 2LL * pad_x > INT32_MAX ||
+        (long long)height + 2LL * pad_y > INT32_MAX)
+        return bbme::fail(BBME_ERR_INVALID, "%s: bad frame %dx%d with padding (%d, %d)", what, width, height, pad_x, pad_y);
+    const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y;
+    if ((W0 & 1) || (H0 & 1)) return bbme::fail(BBME_ERR_INVALID, "%s: the padded view %dx%d is not a plane of 2x2 cells", what, W0, H0);
+    if (W0 > 8188 || H0 > 8188) return bbme::fail(BBME_ERR_UNSUPPORTED, "%s: the padded view %dx%d is beyond 8188", what, W0, H0);
+    if (unit != 1 && unit != 4) return bbme::fail(BBME_ERR_INVALID, "%s: unit %d (1 or 4)", what, unit);
+    if (fill < 0 || fill > 255) return bbme::fail(BBME_ERR_INVALID, "%s: fill %d outside 0..255", what, fill);
+    if ((long long)bgr_pitch < 3LL * width) return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, bgr_pitch, width);
+    if (out && (long long)out_pitch < 3LL * width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x frame width %d", what, out_pitch, width);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, width, height, what, "frame")) return rc;
+    const long long mul = 4 / unit;
+    unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
+    for (int y = 0; y < height; ++y)
+        for (int x = 0; x < width; ++x) {
+            const long long X = 2LL * x + 1 - width, Y = 2LL * y + 1 - height;      // = 2 (x + pad_x) + 1 - W0, 2 (y + pad_y) + 1 - H0
+            const long long pu = model[0] + model[1] * X + model[2] * Y, pv = model[3] + model[4] * X + model[5] * Y;
+            const long long qx = (pu * mul + 32768) >> 16, qy = (pv * mul + 32768) >> 16;
+            const int fx = (int)(qx & 3), fy = (int)(qy & 3);
+            const long long sx = x + (qx >> 2), sy = y + (qy >> 2);                  // frame coordinates: the padded plane's less the pads
+            const bool ok = -pad_x <= sx && sx + 1 + (fx != 0) <= (long long)width + pad_x && -pad_y <= sy &&
+                            sy + 1 + (fy != 0) <= (long long)height + pad_y;
+            const size_t at = (size_t)y * bgr_pitch + (size_t)3 * x;
+            for (int c = 0; c < 3; ++c) {
+                int v = fill;
+                if (ok) {
+                    const auto tap = [&](int weight, int dx, int dy) {
+                        const long long tx = sx + dx, ty = sy + dy;
+                        if (!weight || tx < 0 || tx >= width || ty < 0 || ty >= height) return 0;
+                        return weight * bgr2[(size_t)ty * bgr_pitch + (size_t)3 * tx + c];
+                    };
+                    v = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+                }
+                if (out) out[(size_t)y * out_pitch + (size_t)3 * x + c] = (uint8_t)v;
+                if (!stats4 || !ok || !win.contains(x, y)) continue;
+                const int d = v - bgr1[at + c];
+                sse += (unsigned long long)(d * d);
+                sad += (unsigned long long)(d < 0 ? -d : d);
+            }
+            if (!stats4 || !win.contains(x, y)) continue;
+            if (ok) ++pixels; else ++skipped;
+        }
+    if (stats4) { stats4[0] = sse; stats4[1] = sad; stats4[2] = pixels; stats4[3] = skipped; }
+    return BBME_OK;
+}
+
 // The SUBPEL INTERPOLATION RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_subpel_interpolate).
 // A tap of weight 0 is not read: it may lie outside the plane.
 int bbme_subpel_interpolate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *qf,

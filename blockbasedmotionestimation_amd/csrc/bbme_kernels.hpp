@@ -3190,6 +3190,7 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 //   bgr_load_rows / bgr_row_get / bgr_row_put / bgr_store_rows
 //                                 a run's two colour rows of 24 bytes: the run's own rows, a cell out of a row, a cell into a
 //                                 row, the rows to the unpadded frame
+//   bgr_run_put / bgr_store_run   a one-row run of 4 colour pixels = 12 bytes: a pixel into it, the run to the unpadded frame
 //   store_bytes4                  one map byte per unit
 //   store_partial4                the statistics tail
 //   tf_frame / tf_cost_weight     the temporal filters' neighbour head and weight tail
@@ -3371,6 +3372,30 @@ __device__ __forceinline__ void bgr_store_rows(uint8_t *frame, int pitch, int fw
                 for (int k = 3 * p; k < 3 * p + 3; ++k) q[k] = (uint8_t)(rows[y][k >> 3] >> (8 * (k & 7)));
             }
         }
+    }
+}
+
+// A one-row run of 4 colour pixels: 12 bytes in three dwords, pixel j's B,G,R at bytes 3 j .. 3 j + 2 (bit 24 j: pixels 1 and 2
+// span two dwords).  bgr_run_put: three bytes into pixel j's place of a run that holds 0 there.  bgr_store_run: the run's n
+// pixels to q, three dwords when the run is whole and q dword-aligned (an odd pitch or a caller's odd base breaks that), byte
+// by byte otherwise.
+__device__ __forceinline__ void bgr_run_put(uint32_t (&run)[3], int j, uint32_t px)
+{
+    const int bit = 24 * j, wd = bit >> 5, sh = bit & 31;
+    run[wd] |= px << sh;
+    if (sh > 8) run[wd + 1] |= px >> (32 - sh);
+}
+
+__device__ __forceinline__ void bgr_store_run(uint8_t *q, int n, const uint32_t (&run)[3])
+{
+    if (n == 4 && ((uintptr_t)q & 3u) == 0) {
+        uint32_t *o = reinterpret_cast<uint32_t *>(q);
+#pragma unroll
+        for (int d = 0; d < 3; ++d) o[d] = run[d];
+    } else {
+#pragma unroll
+        for (int k = 0; k < 12; ++k)
+            if (k < 3 * n) q[k] = (uint8_t)(run[k >> 2] >> (8 * (k & 3)));
     }
 }
 
@@ -5000,7 +5025,7 @@ __global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
 }
 
 // =======================================================================================
-// K16 .. K18.  The GLOBAL MOTION RULE and the GLOBAL COMPENSATION RULE of include/bbme.h.  They are templates so that they lie
+// K16 .. K18b.  The GLOBAL MOTION RULE, the GLOBAL COMPENSATION RULE and its BGR form of include/bbme.h.  They are templates so that they lie
 // behind the estimate's template kernels in the code object, as K12b does.
 // =======================================================================================
 
@@ -5300,6 +5325,139 @@ __global__ __launch_bounds__(256) void k_global_compensate(GcArgs a)
     if (!a.partial) return;
     __shared__ uint32_t part[4][4];
     store_partial4(a.partial, pair, part, sse, sad, npix, nskip);
+}
+
+// K18b.  The BGR GLOBAL COMPENSATION RULE: K18 on the zero-padded view of a colour frame, written as the unpadded frame.  Output
+// pixel (x, y) of the fw x fh frame has the X, Y of the frame's own centre (the padded plane's are the same numbers), q, i and f
+// are K18's, and s = (x, y) + i in FRAME coordinates: the pixel is compensated when s lies in [-pad_x, fw + pad_x - 1 - (fx != 0)]
+// x [-pad_y, fh + pad_y - 1 - (fy != 0)], the padded plane, and a tap outside [0, fw) x [0, fh) is the padding's 0.  Same split as
+// K18 -- a lane takes runs of 4 pixels of one frame row, the model advances by 2 m1 and 2 m4 per pixel in 64 bits --;
+// blockIdx.y = FRAME of a run of frames frame_stride bytes apart in both inputs and out_stride in the output, the frame's model
+// from a device table (`models`, six words per frame) or, without one, `model` for all of them.
+// Loads.  The two taps of a row are six adjacent bytes, one unaligned dword and one u16 where both lie in the frame (gcb_row);
+// where they straddle the frame's edge the one inside is a u16 and a byte, and a tap outside is 0 without a load.  The second
+// column is loaded only where fx != 0 and the second row only where fy != 0, so no tap of weight 0 is read and no address
+// leaves the frame's fw x fh pixels: a lone pixel is 3 bytes, never a dword that would reach into the next pixel or past the row.
+// Stores: the run's 12 bytes by bgr_run_put / bgr_store_run.  Frame 1's run arrives as three unaligned dwords, for rows that meet
+// the window only.
+// Statistics over the window [wx0, wx1) x [wy0, wy1) in FRAME pixels: sse and sad over the three channels of the compensated
+// pixels, pixels and skipped in pixels.  Bound: a lane sums at most 4 RPL pixels of three channels, 4 * 4 * 3 * 255^2 = 3 121 200 at
+// RPL = 4, and a wave 64 times that, 64 * 4 RPL * 3 * 255^2 = 199 756 800 < 2^32 (up to RPL = 86); the workgroup's sums are 64-bit
+// (store_partial4, frame = blockIdx.y; k_mc_reduce).
+struct GcBgrArgs {
+    const uint8_t *bgr1, *bgr2;           // fw x fh colour frames, rows bgr_pitch bytes apart; bgr1 may be null without statistics
+    uint8_t *out;                         // compensated frames (rows out_pitch, frames out_stride bytes apart), or null
+    unsigned long long *partial;          // per frame and workgroup {sse, sad, pixels, skipped}; or null (no statistics)
+    const int32_t *models;                // six words per frame; or null: `model` for every frame
+    int32_t model[6];
+    size_t frame_stride, out_stride;      // bytes from frame to frame: inputs, output
+    int fw, fh, pad_x, pad_y, bgr_pitch, out_pitch, mul, fill;      // mul = 4 / unit
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(fw / 4)
+    long long runs;                       // runs_per_row * fh
+};
+
+constexpr int kGcBgrRunsPerLane = 4;
+
+// pixel (x, y) of a colour frame as three bytes B,G,R from bit 0 up
+__device__ __forceinline__ uint32_t gcb_pixel(const uint8_t *p)
+{
+    return (uint32_t)reinterpret_cast<const ua_u16 *>(p)->v | (uint32_t)p[2] << 16;
+}
+
+// Pixel (x, y) of a colour frame in bits 0-23 and, with x1, pixel (x + 1, y) in bits 24-47; a pixel outside the frame is 0 and is
+// not loaded, and without x1 the second one is not looked at.
+__device__ __forceinline__ uint64_t gcb_row(const uint8_t *img, int pitch, int fw, int fh, int x, int y, int x1)
+{
+    if (y < 0 || y >= fh) return 0;
+    const uint8_t *row = img + (size_t)y * pitch;
+    const bool in0 = x >= 0 && x < fw, in1 = x1 && x + 1 >= 0 && x + 1 < fw;
+    if (in0 && in1)
+        return (uint64_t)reinterpret_cast<const ua_u32 *>(row + 3 * x)->v | (uint64_t)reinterpret_cast<const ua_u16 *>(row + 3 * x + 4)->v << 32;
+    if (in0) return gcb_pixel(row + 3 * x);
+    if (in1) return (uint64_t)gcb_pixel(row + 3 * (x + 1)) << 24;
+    return 0;
+}
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_global_compensate_bgr(GcBgrArgs a)
+{
+    const size_t frame = blockIdx.y;
+    const uint8_t *C2 = a.bgr2 + frame * a.frame_stride;
+    long long m[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) m[k] = a.models ? a.models[6 * frame + k] : a.model[k];
+    const int FW = a.fw, FH = a.fh;
+    const long long mul = a.mul;
+    uint32_t sse = 0, sad = 0, npix = 0, nskip = 0;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int y, x0, n;                                         // n pixels of the run lie inside the frame row
+        gather_split(i, a.runs_per_row, FW, y, x0, n);
+        const long long X = 2LL * x0 + 1 - FW, Y = 2LL * y + 1 - FH;
+        long long pu = m[0] + m[1] * X + m[2] * Y, pv = m[3] + m[4] * X + m[5] * Y;
+        uint32_t run[3] = {0, 0, 0}, ok = 0;                  // the sampled pixels; bit j: pixel x0 + j was compensated
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const long long qx = (pu * mul + 32768) >> 16, qy = (pv * mul + 32768) >> 16;
+            const uint32_t fx = (uint32_t)(qx & 3), fy = (uint32_t)(qy & 3);
+            const int x1 = fx != 0, y1 = fy != 0;
+            const long long sx = x0 + j + (qx >> 2), sy = y + (qy >> 2);
+            if (sx >= -a.pad_x && sx + 1 + x1 <= (long long)FW + a.pad_x && sy >= -a.pad_y && sy + 1 + y1 <= (long long)FH + a.pad_y) {
+                const uint64_t t0 = gcb_row(C2, a.bgr_pitch, FW, FH, (int)sx, (int)sy, x1);
+                const uint64_t t1 = y1 ? gcb_row(C2, a.bgr_pitch, FW, FH, (int)sx, (int)sy + 1, x1) : 0;
+                uint32_t px = 0;
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const uint32_t h0 = (4u - fx) * ((uint32_t)(t0 >> (8 * c)) & 0xffu) + fx * ((uint32_t)(t0 >> (24 + 8 * c)) & 0xffu);
+                    const uint32_t h1 = (4u - fx) * ((uint32_t)(t1 >> (8 * c)) & 0xffu) + fx * ((uint32_t)(t1 >> (24 + 8 * c)) & 0xffu);
+                    px |= (((4u - fy) * h0 + fy * h1 + 8u) >> 4) << (8 * c);
+                }
+                bgr_run_put(run, j, px);
+                ok |= 1u << j;
+            }
+            pu += 2 * m[1]; pv += 2 * m[4];
+        }
+        if (a.partial && y >= a.wy0 && y < a.wy1) {
+            const uint8_t *r1 = a.bgr1 + frame * a.frame_stride + (size_t)y * a.bgr_pitch + (size_t)3 * x0;
+            uint32_t ref[3] = {0, 0, 0};
+            if (n == 4) {
+#pragma unroll
+                for (int d = 0; d < 3; ++d) ref[d] = reinterpret_cast<const ua_u32 *>(r1)[d].v;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 9; ++k)
+                    if (k < 3 * n) ref[k >> 2] |= (uint32_t)r1[k] << (8 * (k & 3));
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                if (j >= n || x0 + j < a.wx0 || x0 + j >= a.wx1) continue;
+                if ((ok >> j) & 1u) {
+#pragma unroll
+                    for (int k = 3 * j; k < 3 * j + 3; ++k) {
+                        const int d = (int)((run[k >> 2] >> (8 * (k & 3))) & 0xffu) - (int)((ref[k >> 2] >> (8 * (k & 3))) & 0xffu);
+                        sse += (uint32_t)(d * d);
+                        sad += (uint32_t)abs(d);
+                    }
+                    ++npix;
+                } else {
+                    ++nskip;
+                }
+            }
+        }
+        if (a.out) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (j < n && !((ok >> j) & 1u)) bgr_run_put(run, j, (uint32_t)a.fill * 0x010101u);
+            bgr_store_run(a.out + frame * a.out_stride + (size_t)y * a.out_pitch + (size_t)3 * x0, n, run);
+        }
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, frame, part, sse, sad, npix, nskip);
 }
 
 }  // namespace bbme

@@ -4,7 +4,7 @@
 //            [--block B] [--search S] [--no-upsample] [--device D] [--mc mc.pgm] [--backward back.flo] [--occlusion occ.pgm]
 //            [--interpolate PREFIX --factor N] [--backward-color back.ppm] [--denoise PREFIX --strength T] [--subpel sub.flo]
 //            [--mc-subpel mcq.pgm] [--interpolate-subpel PREFIX --factor N] [--denoise-subpel PREFIX --strength T]
-//            [--global-motion [--gm-out gm.pgm]]
+//            [--global-motion [--gm-out gm.pgm] [--gm-out-bgr gm.ppm]]
 //
 // Sequence of main_class.cpp: read two grey frames (:24,26; binary PGM here, the image has no
 // libpng), 4x bilinear up-sampling (:32-33) and MF::MF (:45) on the GPU from the original frames,
@@ -43,6 +43,8 @@
 // estimated cells of the unpadded frame, tolerance one pixel, three iterations) as six numbers in pixels and pixels per pixel, the
 // cells that follow it, that do not and that were excluded, and the PSNR of the prediction of frame 1 from frame 2 along the model
 // alone (the global compensation rule) beside the block field's; --gm-out writes that prediction, the same unpadded crop as --mc.
+// --gm-out-bgr, on .ppm frames with --no-upsample (which keeps the colour), writes the colour prediction (the BGR global
+// compensation rule) and prints its PSNR over the three channels.
 // Colour frames: binary PPM (P6, maxval 255) is accepted wherever PGM is (both frames of one kind).  Everything above is then
 // computed from their luma (the luma rule of include/bbme.h) as for grey frames -- with --no-upsample the conversion runs on the
 // GPU from the colour frames, otherwise on the host in front of the x4 up-sampling -- and --interpolate writes PREFIX_k.ppm,
@@ -94,7 +96,7 @@ int main(int argc, char **argv)
 {
     const char *f1 = nullptr, *f2 = nullptr, *gt = nullptr, *out = nullptr, *color = nullptr, *mc = nullptr, *backward = nullptr, *occlusion = nullptr, *interpolate = nullptr,
                *backward_color = nullptr, *denoise = nullptr, *subpel = nullptr, *mc_subpel = nullptr,
-               *interpolate_subpel = nullptr, *denoise_subpel = nullptr, *gm_out = nullptr;
+               *interpolate_subpel = nullptr, *denoise_subpel = nullptr, *gm_out = nullptr, *gm_out_bgr = nullptr;
     bool global_motion = false;
     int factor = 2, strength = 64;
     int levels = 4, block = 32, search = 64, device = 0;
@@ -117,6 +119,7 @@ int main(int argc, char **argv)
         else if (a == "--subpel") subpel = next();
         else if (a == "--global-motion") global_motion = true;
         else if (a == "--gm-out") gm_out = next();
+        else if (a == "--gm-out-bgr") gm_out_bgr = next();
         else if (a == "--strength") strength = atoi(next());
         else if (a == "--factor") factor = atoi(next());
         else if (a == "--levels") levels = atoi(next());
@@ -135,7 +138,7 @@ int main(int argc, char **argv)
                         "[--occlusion occ.pgm] [--interpolate PREFIX --factor N] [--backward-color back.ppm] "
                         "[--denoise PREFIX --strength T] [--subpel sub.flo] [--mc-subpel mcq.pgm] "
                         "[--interpolate-subpel PREFIX --factor N] [--denoise-subpel PREFIX --strength T] "
-                        "[--global-motion [--gm-out gm.pgm]]\n"
+                        "[--global-motion [--gm-out gm.pgm] [--gm-out-bgr gm.ppm]]\n"
                         "--denoise writes PREFIX_1.pgm and PREFIX_2.pgm (on .ppm frames their luma) and, on .ppm frames, the "
                         "filtered colour frames PREFIX_1.ppm and PREFIX_2.ppm; it needs --no-upsample\n");
         return 2;
@@ -146,6 +149,10 @@ int main(int argc, char **argv)
     }
     if (gm_out && !global_motion) {
         fprintf(stderr, "--gm-out needs --global-motion\n");
+        return 2;
+    }
+    if (gm_out_bgr && (!global_motion || upsample)) {
+        fprintf(stderr, "--gm-out-bgr needs --global-motion and --no-upsample\n");
         return 2;
     }
     try {
@@ -162,6 +169,10 @@ int main(int argc, char **argv)
         }
         if (colour && upsample && interpolate) {
             fprintf(stderr, "--interpolate on colour frames needs --no-upsample\n");
+            return 2;
+        }
+        if (gm_out_bgr && !colour) {
+            fprintf(stderr, "--gm-out-bgr needs colour frames (.ppm)\n");
             return 2;
         }
         if (colour && upsample) { image1 = bbme::bgr_to_gray(bgr1); image2 = bbme::bgr_to_gray(bgr2); }
@@ -213,6 +224,12 @@ int main(int argc, char **argv)
                 const int px = motion_pair.padding_x, py = motion_pair.padding_y;
                 bbme::check(bbme_pgm_write(gm_out, img.cols - 2 * px, img.rows - 2 * py, img.cols,
                                            img.data.data() + (size_t)py * img.cols + px));
+            }
+            if (gm_out_bgr) {
+                const bbme::ImageBGR img = motion_pair.drawMVimageGlobalBGR(g.model, 1, false, 0);
+                bbme::check(bbme_ppm_write_bgr(gm_out_bgr, img.cols, img.rows, img.data.data()));
+                const bbme::CompensationError c = motion_pair.compensationErrorGlobalBGR(g.model, 1);
+                printf("Global MC colour PSNR is %.9g dB over %llu pixels (%llu skipped)\n", c.psnr(), c.pixels, c.skipped);
             }
         }
         if (mc) {

@@ -72,13 +72,14 @@ struct ImageBGR {
 // residual statistics of a motion-compensated frame (bbme_compensation_error)
 struct CompensationError {
     unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
-    double mse() const { return pixels ? (double)sse / (double)pixels : std::numeric_limits<double>::quiet_NaN(); }
-    // 10 log10(255^2 pixels / sse); infinite for a perfect prediction, NaN when no pixel was compensated
+    int channels = 1;                                   // samples per pixel that sse and sad are summed over (3 for a colour rule)
+    double mse() const { return pixels ? (double)sse / ((double)channels * (double)pixels) : std::numeric_limits<double>::quiet_NaN(); }
+    // 10 log10(255^2 channels pixels / sse); infinite for a perfect prediction, NaN when no pixel was compensated
     double psnr() const
     {
         if (!pixels) return std::numeric_limits<double>::quiet_NaN();
         if (!sse) return std::numeric_limits<double>::infinity();
-        return 10.0 * std::log10(255.0 * 255.0 * (double)pixels / (double)sse);
+        return 10.0 * std::log10(255.0 * 255.0 * (double)channels * (double)pixels / (double)sse);
     }
 };
 
@@ -275,6 +276,24 @@ public:
         bbme::check(bbme_global_compensation_error(ctx_, backward ? 1 : 0, model, unit, window ? window : unpadded, s));
         bbme::CompensationError e;
         e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3];
+        return e;
+    }
+    // The same in colour (the BGR GLOBAL COMPENSATION RULE of include/bbme.h), for frames set as B,G,R: the UNPADDED frame sampled
+    // from the stored colour of the other image, and its statistics over window {x0, y0, w, h} in pixels of the frame (nullptr =
+    // the whole frame), sse and sad summed over the three channels.
+    bbme::ImageBGR drawMVimageGlobalBGR(const int32_t model[6], int unit = 1, bool backward = false, int fill = 0)
+    {
+        bbme::ImageBGR img(padded_height - 2 * padding_y, padded_width - 2 * padding_x);
+        bbme::check(bbme_get_global_compensated_bgr_host(ctx_, 0, backward ? 1 : 0, model, unit, fill, img.data.data()));
+        return img;
+    }
+    bbme::CompensationError compensationErrorGlobalBGR(const int32_t model[6], int unit = 1, bool backward = false,
+                                                       const int *window = nullptr)
+    {
+        unsigned long long s[4] = {0, 0, 0, 0};
+        bbme::check(bbme_global_compensation_error_bgr(ctx_, backward ? 1 : 0, model, unit, window, s));
+        bbme::CompensationError e;
+        e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3]; e.channels = 3;
         return e;
     }
     // Direction of the context (include/bbme.h): backward = every estimate and result as if image1 and image2 were exchanged.

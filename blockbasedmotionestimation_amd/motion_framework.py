@@ -717,6 +717,77 @@ class MF:
             out.stride(0) if out is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
         return out, stats
 
+    # -- the same on the B,G,R frames (the BGR GLOBAL COMPENSATION RULE of include/bbme.h): needs frames set as (H, W, 3) ---------
+    def _get_global_compensated_bgr(self, pair, which, model, unit, fill, out, what):
+        out = _host_out(out, (self.orig_height, self.orig_width, 3), np.uint8, what)
+        model = _gm_model(model, what)
+        _capi.check(self._lib.bbme_get_global_compensated_bgr_host(self._ctx, pair, _which(which), model.ctypes.data, int(unit),
+                                                                   int(fill), out.ctypes.data))
+        return out
+
+    def draw_MVimage_global_bgr(self, model, unit=1, which="forward", fill=0, out=None):
+        """draw_MVimage_global in colour: the UNPADDED (H, W, 3) uint8 frame compensated for the model's motion alone (the BGR
+        global compensation rule), sampled from the stored B,G,R frame of the other image; a source in the padding reads its
+        zero, one outside the padded plane gives `fill`.  BbmeError (ERR_STATE) when a frame of the pair was set grey."""
+        return self._get_global_compensated_bgr(0, which, model, unit, fill, out, "draw_MVimage_global_bgr")
+
+    def _global_compensation_stats_bgr(self, which, models, unit, window):
+        pairs = getattr(self, "batch", 1)
+        models = np.ascontiguousarray(models, np.int32).reshape(-1)
+        if models.size != 6 * pairs:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "compensation_error_global_bgr: six int32 per pair (%d pairs)" % pairs)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_global_compensation_error_bgr(self._ctx, _which(which), models.ctypes.data, int(unit),
+                                                                 _window(window), s))
+        return [_residual_dict(s[4 * p:4 * p + 4], 3) for p in range(pairs)]
+
+    def compensation_error_global_bgr(self, model, unit=1, which="forward", window=None):
+        """Residual statistics of draw_MVimage_global_bgr against the colour frame it predicts over window (x0, y0, w, h) in
+        pixels of the FRAME (None = the whole frame): the dict of compensation_error_global with sse and sad summed over the three
+        channels and mse = sse / (3 pixels)."""
+        return self._global_compensation_stats_bgr(which, model, unit, window)[0]
+
+    def cells_global_compensate_bgr_device(self, bgr1, bgr2, models, unit=1, out=None, stats=None, fill=0, window=None, stream=None):
+        """The BGR global compensation rule on any colour frames in HBM, a run of them from ONE launch: bgr1 (None without stats)
+        and bgr2 uint8 CUDA tensors (H, W, 3) or (N, H, W, 3), N <= GC_MAX_FRAMES, with packed pixels, a common row pitch and a
+        common frame stride; models (6,) or (N, 6) int32 on the host, frame k under models[k]; out a uint8 CUDA tensor of the same
+        shape with packed pixels whose rows and frames may be further apart; stats an int64 or uint64 CUDA tensor of 4 N (sse,
+        sad, pixels, skipped per frame) over window (x0, y0, w, h) in frame pixels (None = the whole frame).  On the given HIP
+        stream handle (default: the context's), ordered behind the context's stream; no host wait.  Needs no frames and no
+        estimate."""
+        import torch
+        what = "cells_global_compensate_bgr_device"
+        h, w = self.orig_height, self.orig_width
+        if bgr2 is None or bgr2.dim() not in (3, 4):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: bgr2 must be a uint8 CUDA tensor (H, W, 3) or (N, H, W, 3)" % what)
+        run = bgr2.dim() == 4
+        count = bgr2.shape[0] if run else 1
+        shape = ((count,) if run else ()) + (h, w, 3)
+
+        def frames_ok(t):
+            return t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == shape and _packed_pixels(t[0] if run else t)
+
+        for t in (bgr2,) if bgr1 is None and stats is None else (bgr1, bgr2):
+            if t is None or not (frames_ok(t) and t.stride(-3) == bgr2.stride(-3) and (not run or t.stride(0) == bgr2.stride(0))):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: colour frames must be uint8 CUDA tensors of shape %s with packed pixels, "
+                                      "a common row pitch and a common frame stride" % (what, shape))
+        if out is None and stats is None:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: neither out nor stats" % what)
+        if out is not None and not frames_ok(out):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape %s with packed pixels" % (what, shape))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4 * count
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of %d" % (what, 4 * count))
+        models = np.ascontiguousarray(models, np.int32).reshape(-1)
+        if models.size != 6 * count:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: six int32 per frame (%d frames)" % (what, count))
+        self._behind_torch(bgr1, bgr2, out, stats)
+        _capi.check(self._lib.bbme_cells_global_compensate_bgr_device(
+            self._ctx, _ptr(bgr1), _ptr(bgr2), bgr2.stride(-3), bgr2.stride(0) if run else 0, count, models.ctypes.data, int(unit),
+            int(fill), _window(window), _ptr(out), out.stride(-3) if out is not None else 0,
+            out.stride(0) if out is not None and run else 0, _ptr(stats), C.c_void_p(stream or 0)))
+        return out, stats
+
     # -- colour coding of the field: Flow::MotionToColor on the GPU, from the cells (the colour rule of include/bbme.h) ----------
     def color_shape(self, scale=None):
         """(rows, cols, 3) of the colour image: the subsampled field's size; scale defaults to upsample."""
@@ -1553,6 +1624,14 @@ class MFBatch(MF):
         """MF.compensation_error_global of every pair under its own model (models: (pairs, 6) int32), from one launch."""
         return self._global_compensation_stats(which, models, unit, window)
 
+    def get_pair_global_compensated_bgr(self, pair, model, unit=1, which="forward", fill=0, out=None):
+        """MF.draw_MVimage_global_bgr of one pair."""
+        return self._get_global_compensated_bgr(pair, which, model, unit, fill, out, "get_pair_global_compensated_bgr")
+
+    def compensation_errors_global_bgr(self, models, unit=1, which="forward", window=None):
+        """MF.compensation_error_global_bgr of every pair under its own model (models: (pairs, 6) int32), from one launch."""
+        return self._global_compensation_stats_bgr(which, models, unit, window)
+
     def consistency_stats_all(self, which="forward", tol=1, window=None):
         """MF.consistency_stats of every pair, in order, from one launch."""
         return self._consistency_stats(which, tol, window)
@@ -1836,11 +1915,12 @@ def subpel_cells(image1, image2, cells, window=None):
     return out, dict(zip(_SUBPEL_STATS, list(s)))
 
 
-def _residual_dict(s):
-    """dict(sse, sad, pixels, skipped, mse, psnr) of the four residual statistics of a compensation rule."""
+def _residual_dict(s, channels=1):
+    """dict(sse, sad, pixels, skipped, mse, psnr) of the four residual statistics of a compensation rule; sse is summed over
+    `channels` samples per pixel."""
     sse, sad, pixels, skipped = s
-    mse = sse / pixels if pixels else math.nan
-    psnr = math.nan if not pixels else math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * pixels / sse)
+    mse = sse / (channels * pixels) if pixels else math.nan
+    psnr = math.nan if not pixels else math.inf if sse == 0 else 10.0 * math.log10(255.0 ** 2 * channels * pixels / sse)
     return dict(sse=sse, sad=sad, pixels=pixels, skipped=skipped, mse=mse, psnr=psnr)
 
 
@@ -1974,6 +2054,38 @@ def global_compensate(image1, image2, model, unit=1, fill=0, window=None):
     _capi.check(_capi.lib().bbme_global_compensate_host(_ptr(image1), image2.ctypes.data, w, h, model.ctypes.data, int(unit), int(fill),
                                                         _window(window), out.ctypes.data, s))
     return out, (_residual_dict(list(s)) if s is not None else None)
+
+
+GC_MAX_FRAMES = 32                                        # frames of one cells_global_compensate_bgr_device launch
+
+
+def global_compensate_bgr(c1, c2, model, unit=1, fill=0, pad_x=0, pad_y=0, window=None):
+    """The BGR global compensation rule on the CPU (bbme_global_compensate_bgr_host): c1 (None without statistics), c2 uint8
+    (H, W, 3) frames with packed pixels whose rows may be further apart than 3 W bytes (both with the same pitch), model six
+    int32 in Q16 grid units of 1 / unit pixel, (pad_x, pad_y) the zero padding of the view the rule works on -> (compensated
+    frame (H, W, 3) uint8, dict(sse, sad, pixels, skipped, mse, psnr) against c1 over window (x0, y0, w, h) in frame pixels, or
+    None without c1); sse and sad are summed over the three channels, mse = sse / (3 pixels)."""
+    def frame(a):
+        a = np.asarray(a, np.uint8)
+        if a.ndim == 3 and a.shape[2] == 3 and a.strides[2] == 1 and a.strides[1] == 3 and a.strides[0] >= 3 * a.shape[1]:
+            return a
+        return np.ascontiguousarray(a)
+
+    c2 = frame(c2)
+    if c1 is not None:
+        c1 = frame(c1)
+        if c1.strides[0] != c2.strides[0]:
+            c1, c2 = np.ascontiguousarray(c1), np.ascontiguousarray(c2)
+    if c2.ndim != 3 or c2.shape[2] != 3 or (c1 is not None and c1.shape != c2.shape):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "global_compensate_bgr: uint8 frames of one shape (H, W, 3)")
+    model = _gm_model(model, "global_compensate_bgr")
+    h, w = c2.shape[:2]
+    out = np.empty((h, w, 3), np.uint8)
+    s = (C.c_ulonglong * 4)() if c1 is not None else None
+    _capi.check(_capi.lib().bbme_global_compensate_bgr_host(_ptr(c1), c2.ctypes.data, w, h, c2.strides[0], int(pad_x), int(pad_y),
+                                                            model.ctypes.data, int(unit), int(fill), _window(window), out.ctypes.data,
+                                                            3 * w, s))
+    return out, (_residual_dict(list(s), 3) if s is not None else None)
 
 
 def cells_consistency(a, b, tol=1, window=None):

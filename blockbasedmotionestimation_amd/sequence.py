@@ -594,49 +594,74 @@ def stabilization_corrections(models, radius=None, unit=1):
 
 def stabilize_frames(frames, search_size, block_size, radius=None, kind="translation", tol=1.0, iterations=3, fill=0, device=None,
                      in_flight=4, batch=2):
-    """Stabilisation of a grey video on ONE GPU from the dominant motion of its consecutive pairs (the global motion rule and the
-    global compensation rule of include/bbme.h) -> (frames, models, corrections): len(frames) unpadded uint8 (H, W) frames, the
-    per-pair models (P, 6) int32 (unit 1: pixels over half pixels from the plane centre) and the per-frame corrections
-    (P + 1, 6) int32 each frame was warped by (stabilization_corrections).  The pairs are estimated on chain contexts
-    (estimate_frames_pipelined's plan: every frame is set once), every pair's model comes from MFChain.global_motion_all, and a
-    copy of every frame's padded level-0 plane stays in HBM; the models are composed and smoothed on the host in double; then
-    every plane is warped by the global compensation kernel (MF.cells_global_compensate_device, no image 1) and the unpadded
-    frame cut out of it.  A pixel whose source lies in the padding takes the padding's zero, one whose source lies outside the
-    padded plane takes `fill`.  radius=None locks every frame to frame 0; an integer radius follows the smoothed path.  A colour
-    video is BbmeError (ERR_UNSUPPORTED): the warp is grey."""
+    """Stabilisation of a grey or a colour video on ONE GPU from the dominant motion of its consecutive pairs (the global motion
+    rule and the global compensation rule of include/bbme.h, for colour its BGR form) -> (frames, models, corrections):
+    len(frames) unpadded uint8 frames, (H, W) or (H, W, 3) as they came, the per-pair models (P, 6) int32 (unit 1: pixels over
+    half pixels from the plane centre) and the per-frame corrections (P + 1, 6) int32 each frame was warped by
+    (stabilization_corrections).  The pairs are estimated on chain contexts (estimate_frames_pipelined's plan: every frame is set
+    once) and every pair's model comes from MFChain.global_motion_all; the models are composed and smoothed on the host in double.
+    A pixel whose source lies in the padding takes the padding's zero, one whose source lies outside the padded plane takes
+    `fill`.  radius=None locks every frame to frame 0; an integer radius follows the smoothed path.
+    Grey video: a copy of every frame's padded level-0 plane stays in HBM, every plane is warped by the global compensation kernel
+    (MF.cells_global_compensate_device, no image 1) and the unpadded frame cut out of it.
+    Colour video, (H, W, 3) frames in B,G,R order: the chains are fed the colour frames, so the models are those of the grey call
+    on bgr_to_gray(video); a copy of every frame's stored colour (MF.frame_bgr_tensor) stays in HBM and no plane copy is kept;
+    the frames are warped in runs of up to in_flight * batch (at most GC_MAX_FRAMES) by MF.cells_global_compensate_bgr_device,
+    each run one launch under its frames' own corrections and one download."""
     import torch
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if frames and frames[0].ndim == 3:
-        raise _capi.BbmeError(_capi.ERR_UNSUPPORTED, "stabilize_frames: a colour video: the global compensation rule is grey")
+    bgr = bool(frames) and frames[0].ndim == 3
     n = len(frames)
     if n < 2:
         return frames, np.zeros((0, 6), np.int32), np.zeros((n, 6), np.int32)
     if device is None:
         device = local_device()
     models = np.zeros((n - 1, 6), np.int32)
-    planes = [None] * n
+    planes = [None] * n                                    # grey: every frame's padded plane
+    store = []                                             # colour: one (n, H, W, 3) tensor of every frame's stored colour
+    have = [False] * n
 
     def collect(mf, first, count):
         got = mf.global_motion_all(kind=kind, tol=tol, iterations=iterations)         # waits for this context's stream
         for p in range(count):
             models[first + p] = got[p]["model"]
             for which in (0, 1):
-                if planes[first + p + which] is None:
-                    planes[first + p + which] = mf.frame_plane_tensor(p, which).clone()
+                f = first + p + which
+                if have[f]:
+                    continue
+                have[f] = True
+                if bgr:
+                    src = mf.frame_bgr_tensor(p, which)
+                    if not store:
+                        store.append(torch.empty((n,) + tuple(src.shape), dtype=torch.uint8, device=src.device))
+                    store[0][f].copy_(src)
+                else:
+                    planes[f] = mf.frame_plane_tensor(p, which).clone()
         torch.cuda.synchronize(device)                                                # the copies, before the planes roll
 
     _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect)
     corrections = stabilization_corrections(models, radius)
-    from .motion_framework import MF
+    from .motion_framework import MF, GC_MAX_FRAMES
     out = [None] * n
     mf = MF(frames[0], frames[0], search_size, block_size, len(block_size), device=device)
     try:
         h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
-        warped = torch.empty((mf.padded_height, mf.padded_width), dtype=torch.uint8, device=planes[0].device)
-        for f in range(n):
-            mf.cells_global_compensate_device(None, planes[f], corrections[f], unit=1, out=warped, fill=fill)
-            mf.synchronize()
-            out[f] = np.ascontiguousarray(warped.cpu().numpy()[py:py + h, px:px + w])
+        if bgr:
+            run = max(1, min(int(in_flight) * int(batch), GC_MAX_FRAMES, n))
+            warped = torch.empty((run, h, w, 3), dtype=torch.uint8, device=store[0].device)
+            for f0 in range(0, n, run):
+                k = min(run, n - f0)
+                mf.cells_global_compensate_bgr_device(None, store[0][f0:f0 + k], corrections[f0:f0 + k], unit=1, out=warped[:k], fill=fill)
+                mf.synchronize()
+                host = warped[:k].cpu().numpy()
+                for i in range(k):
+                    out[f0 + i] = np.ascontiguousarray(host[i])
+        else:
+            warped = torch.empty((mf.padded_height, mf.padded_width), dtype=torch.uint8, device=planes[0].device)
+            for f in range(n):
+                mf.cells_global_compensate_device(None, planes[f], corrections[f], unit=1, out=warped, fill=fill)
+                mf.synchronize()
+                out[f] = np.ascontiguousarray(warped.cpu().numpy()[py:py + h, px:px + w])
     finally:
         mf.close()
     return out, models, corrections

@@ -1256,6 +1256,56 @@ int bbme_get_global_compensated_host(bbme_ctx *ctx, int pair, int which, const i
 int bbme_global_compensation_error(bbme_ctx *ctx, int which, const int32_t *models, int unit, const int *window,
                                    unsigned long long *stats);
 
+/* BGR GLOBAL COMPENSATION RULE (this project's own): the GLOBAL COMPENSATION RULE applied to the zero-padded view of a colour
+ * frame; it writes the unpadded frame, as every other BGR rule does.  Inputs: two colour frames C1 and C2, each W x H pixels of
+ * B,G,R with rows bgr_pitch >= 3 W bytes apart (C1 for the statistics only); pad_x and pad_y, with W0 = W + 2 pad_x and
+ * H0 = H + 2 pad_y (both even, as every padded plane is); a model of the GLOBAL MOTION RULE and its unit (1 or 4); fill (0..255).
+ * Output pixel (x, y) of the frame lies at padded position (x + pad_x, y + pad_y); its X, Y are 2 (x + pad_x) + 1 - W0 and
+ * 2 (y + pad_y) + 1 - H0, which equal 2 x + 1 - W and 2 y + 1 - H: THE MODEL DOES NOT DEPEND ON THE PADDING.  q, i and f are exactly
+ * as in the grey rule, in 64 bits; s = (x + pad_x, y + pad_y) + i.  The pixel is COMPENSATED under the grey rule's condition on the
+ * padded plane W0 x H0; every channel c is then the SUBPEL RULE's sample, with its single rounding (... + 8) >> 4, of channel c at
+ * s with the fractions f, where a tap whose frame coordinates lie outside [0, W) x [0, H) reads 0 -- the zero border of the luma
+ * planes -- and a tap of weight 0 is never read.  A pixel that is not compensated gets `fill` in all three channels and counts as
+ * skipped.  No byte outside the frames' W x H pixels is read.
+ * Statistics: four words {sse, sad, pixels, skipped} against C1 over a window {x0, y0, w, h} in FRAME pixels (NULL = the whole
+ * frame): sse and sad are summed over the three channels, pixels and skipped count pixels (the mirrors derive
+ * mse = sse / (3 pixels) and psnr from it); exact and independent of `fill`.
+ * Properties.  On B = G = R frames every channel of the output is the unpadded crop of the grey rule's output on pad_zero(grey),
+ * sse and sad are three times the grey statistics over the same window, pixels and skipped are equal.  With pads of 0 each channel
+ * is the grey rule on that channel.  With a whole-pixel translation model, out[y][x] = C2[y + ty][x + tx] wherever that lies in
+ * the padded view (0 in its border).  The identity model returns C2.
+ * Errors: as for the grey rule's calls, the window inside the frame; in addition BBME_ERR_INVALID for bgr_pitch or out_pitch < 3 W,
+ * for a frame_stride or out_stride below one frame when count > 1, and for count outside 1..BBME_GC_MAX_FRAMES; BBME_ERR_STATE
+ * when stored colour is asked for and a frame has none (a grey setter withdraws it); BBME_ERR_UNSUPPORTED for W0 or H0 > 8188.  No
+ * call changes context state.  All work on single, batched and chain contexts.
+ * bbme_global_compensate_bgr_host: the rule on the CPU, no GPU; bgr1 may be NULL without statistics; out (rows out_pitch bytes
+ * apart) and stats4 each may be NULL, not both.
+ * bbme_cells_global_compensate_bgr_device: ANY colour frames in HBM of the context's frame size and a common bgr_pitch: `count`
+ * frames (1..BBME_GC_MAX_FRAMES), frame_stride bytes apart in both inputs, from ONE launch; models holds 6 count int32 ON THE HOST,
+ * frame k under models[6 k ..] (for count > 1 they are copied to a device table on hip_stream, as bbme_global_compensation_error
+ * copies its own); d_bgr1 may be null without d_stats4; d_out (rows out_pitch, frames out_stride bytes apart) and d_stats4
+ * (4 count words, frame k at 4 k) each may be null, not both; the output must not overlap an input.  On hip_stream (NULL = the ctx
+ * stream; another stream is first ordered behind it); no host wait.  Launches with d_stats4 share one scratch buffer per context and
+ * launches with count > 1 one table: the caller orders those it issues on different streams.
+ * bbme_global_compensate_bgr_device: the stored colour of `pair` (the COLOUR STORE): which = 0 predicts frame 1 from frame 2 (in
+ * direction BACKWARD the frames exchange, as the planes of bbme_global_compensate_device do), which = 1 frame 2 from frame 1.  On a
+ * chain the frames are slots pair and pair + 1.
+ * bbme_get_global_compensated_bgr_host: the same; synchronises; packed rows of 3 W bytes.
+ * bbme_global_compensation_error_bgr: EVERY pair from one launch under its own model, models[6 p + k], stats[4 p + k]; every pair
+ * needs its stored colour; synchronises. */
+enum { BBME_GC_MAX_FRAMES = 32 };
+int bbme_global_compensate_bgr_host(const uint8_t *bgr1, const uint8_t *bgr2, int width, int height, int bgr_pitch, int pad_x, int pad_y,
+                                    const int32_t *model, int unit, int fill, const int *window, uint8_t *out, int out_pitch,
+                                    unsigned long long *stats4);
+int bbme_cells_global_compensate_bgr_device(bbme_ctx *ctx, const uint8_t *d_bgr1, const uint8_t *d_bgr2, int bgr_pitch, size_t frame_stride,
+                                            int count, const int32_t *models, int unit, int fill, const int *window, uint8_t *d_out,
+                                            int out_pitch, size_t out_stride, unsigned long long *d_stats4, void *hip_stream);
+int bbme_global_compensate_bgr_device(bbme_ctx *ctx, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *d_out,
+                                      int out_pitch, void *hip_stream);
+int bbme_get_global_compensated_bgr_host(bbme_ctx *ctx, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *out);
+int bbme_global_compensation_error_bgr(bbme_ctx *ctx, int which, const int32_t *models, int unit, const int *window,
+                                       unsigned long long *stats);
+
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
 /* copyMVs (:828-843) + calcLevelBM (:226-244) of one level.  Leaves that level's MV
