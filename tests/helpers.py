@@ -907,3 +907,70 @@ def scale_cell_windows(pad_x, pad_y, w, h):
     x0, y0 = -(-pad_x // 2), -(-pad_y // 2)
     x1, y1 = -(-(pad_x + w) // 2), -(-(pad_y + h) // 2)
     return (x0, y0, x1 - x0, y1 - y0), (x0 + 3, y0 + 1, x1 - x0 - 8, y1 - y0 - 5)
+
+
+# ---- global motion and global compensation at scale (tests/test_global_motion_scale_cpu.py proves what the shapes and the content
+# ---- do, tests/test_gpu_scale.py runs K16, K17, K18 and K18b on them) ----------------------------------------------------------
+GM_WIDE = dict(w=8186, h=130, search=[12], block=[4])        # pads to 8188 x 132, pad (1, 1): 4094 x 66 cells, the rule's widest
+GM_TALL = dict(w=130, h=8186, search=[12], block=[4])        # pads to 132 x 8188: 66 x 4094 cells, the rule's tallest
+GM_SHAPES = {"G1": SCALE_G1, "WIDE": GM_WIDE, "TALL": GM_TALL}
+GM_PADDED = {"G1": (2060, 1040), "WIDE": (8188, 132), "TALL": (132, 8188)}
+GM_TOL = 3 << 16
+
+
+def gm_trips(w0, h0, max_groups):
+    """(runs, workgroups, trips, runs of the last trip) of k_vector_histogram: min(ceil(runs / 256), max_groups) workgroups stride
+    over the runs of 4 cells, 256 runs per workgroup and trip (vh_groups, csrc/bbme_device.hip)."""
+    runs = (w0 // 2 + 3) // 4 * (h0 // 2)
+    groups = min((runs + 255) // 256, max_groups)
+    trips = (runs + groups * 256 - 1) // (groups * 256)
+    return runs, groups, trips, runs - (trips - 1) * groups * 256
+
+
+def gm_cell_window(cw, ch):
+    """A window in cells that starts and ends inside runs of 4"""
+    return (1, 1, cw - 3, ch - 2)
+
+
+def gm_plane_window(w0, h0):
+    """A window in pixels, odd on every side"""
+    return (3, 1, w0 - 8, h0 - 4)
+
+
+def gm_scale_grid(ch, cw, seed=SCALE_SEED):
+    """The grid of the moments tests -> (grid, model, mask): a zooming and rotating field in quarter pels plus noise of +-2, a
+    quarter of the cells overwritten from extreme_grid; the field's true model rounded to Q16; an exclusion mask of 30 %.  Under
+    GM_TOL about a third of the cells each is an inlier, an outlier and excluded."""
+    from test_global_motion_cpu import affine_cells, extreme_grid, random_mask
+    g, true = affine_cells(ch, cw, 4, 3.25, -1.5, 0.001, -0.0007)
+    rng = np.random.default_rng(seed + 4)
+    g += rng.integers(-2, 3, size=g.shape).astype(np.int16)
+    pick = rng.random((ch, cw)) < 0.25
+    g[pick] = extreme_grid(ch, cw, seed + 5)[pick]
+    model = tuple(int(v) for v in np.rint(true * 65536))
+    return g, model, random_mask(ch, cw, seed + 6)
+
+
+def gm_histogram_grids(ch, cw):
+    """(name, grid) of the histogram tests and their exclusion mask"""
+    from test_global_motion_cpu import extreme_grid, random_grid, random_mask, uniform_grid
+    return (("uniform", uniform_grid(ch, cw)), ("random", random_grid(ch, cw, 1)), ("extreme", extreme_grid(ch, cw, 2))), \
+        random_mask(ch, cw, 3)
+
+
+def gm_scale_planes(h0, w0, seed=SCALE_SEED):
+    """Two unrelated padded planes of random bytes"""
+    rng = np.random.default_rng(seed + 7)
+    return rng.integers(0, 256, (h0, w0), dtype=np.uint8), rng.integers(0, 256, (h0, w0), dtype=np.uint8)
+
+
+GM_BGR_MODELS = (((20000, 2621, -700, -9000, 700, 2621), (3 << 16, 0, 0, -(2 << 16), 0, 0), (16384 + 3000, 300, 0, -8192, 0, -200)), 1)
+
+
+def gm_scale_bgr_case(h, w, seed=SCALE_SEED):
+    """Three pairs of unrelated colour frames, the three models they are warped under from one launch (and the unit), an odd frame
+    window"""
+    rng = np.random.default_rng(seed + 8)
+    c1 = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(3)]
+    c2 = [rng.integers(0, 256, (h, w, 3), dtype=np.uint8) for _ in range(3)]
+    return c1, c2, GM_BGR_MODELS[0], GM_BGR_MODELS[1], (1, 2, w - 5, h - 3)

@@ -1,7 +1,8 @@
 """K18b k_global_compensate_bgr against the host rule of the BGR GLOBAL COMPENSATION RULE (bbme_global_compensate_bgr_host, which
 tests/test_global_compensation_bgr_cpu.py holds against numpy), bit for bit: caller's frames at odd pitches and the stored
 colour, every output pitch and the byte path, runs of frames from one launch, a caller's stream; B = G = R contexts against the
-grey calls; single, batched and chain contexts; refusals and state; the guard bands; sequence.stabilize_frames on a colour
+grey calls; single, batched and chain contexts; refusals and state, planes beyond 8188 among them; a run of GC_MAX_FRAMES = 32
+frames from one launch; the guard bands; sequence.stabilize_frames on a colour
 video; bbme_cli --gm-out-bgr.  No tolerance appears."""
 import hashlib
 import os
@@ -168,6 +169,52 @@ def test_stored_colour_runs_of_frames_and_a_callers_stream(bbme, geometry):
                 assert st[k] == st1[0] == tuple(host[k][1][s] for s in STAT_KEYS), (unit, k, kw)
         got, none = _warp(mf, None, f2, models, unit, 3, None, want=("out",), in_extra=1, stream=stream)
         assert all(np.array_equal(got[k], host[k][0]) for k in range(3))
+    mf.close()
+
+
+def test_a_run_of_32_frames_from_one_launch(bbme):
+    """BBME_GC_MAX_FRAMES = 32 frames as blockIdx.y of one launch: 32 models in the caller's table, 32 statistics quadruples, the
+    frames 5 bytes further apart than their rows need; 33 are refused"""
+    w, h = 50, 38
+    f1, f2 = _frames(w, h, 32, seed=3), _frames(w, h, 32, seed=4)
+    mf = bbme.MF(f1[0], f2[0], [12], [4])
+    px, py = mf.padding_x, mf.padding_y
+    assert (mf.padded_width, mf.padded_height, px, py) == (52, 40, 1, 1)
+    models = [(40000 * (k - 16), 40 * k, -25 * (k % 7), -30000 * (k % 11) + 90000, 30 * (k % 5), -45 * k) for k in range(32)]
+    assert len(set(models)) == 32
+    window = (1, 2, w - 5, h - 3)
+    for unit in (1, 4):
+        models = [tuple(unit * v + (unit == 4) for v in m) for m in models]               # the same motion in quarter pels, nearly
+        host = [bbme.global_compensate_bgr(f1[k], f2[k], models[k], unit, 3, px, py, window) for k in range(32)]
+        assert len({h_[1]["sse"] for h_ in host}) == 32 and len({h_[0].tobytes() for h_ in host}) == 32
+        assert sum(h_[1]["skipped"] > 0 for h_ in host) >= 8
+        got, st = _warp(mf, f1, f2, models, unit, 3, window, in_extra=1, out_extra=5, out_offset=1)      # (_warp checks the gaps)
+        for k in range(32):
+            assert np.array_equal(got[k], host[k][0]), (unit, k)
+            assert st[k] == tuple(host[k][1][s] for s in STAT_KEYS), (unit, k, st[k], host[k][1])
+    assert _status(bbme, lambda: _warp(mf, f1 + f1[:1], f2 + f2[:1], models + models[:1], 4, 3, window)) == -1
+    mf.close()
+
+
+def test_planes_beyond_8188_are_refused_and_nothing_is_written(bbme):
+    """Frames of 8190 x 130 pad to 8192 x 132: ERR_UNSUPPORTED before anything is launched"""
+    import torch
+    from blockbasedmotionestimation_amd import _capi
+    w, h = 8190, 130
+    z = np.zeros((h, w, 3), np.uint8)
+    mf = bbme.MF(z, z, [12], [4])
+    assert (mf.padded_width, mf.padded_height) == (8192, 132)
+    t = torch.zeros((h, w, 3), dtype=torch.uint8, device="cuda")
+    out = torch.full((h, w, 3), PATTERN, dtype=torch.uint8, device="cuda")
+    st = torch.full((4,), -7, dtype=torch.int64, device="cuda")
+    calls = (lambda: mf.cells_global_compensate_bgr_device(t, t, EDGE_MODEL[0], 1, out, st),
+             lambda: mf.draw_MVimage_global_bgr(EDGE_MODEL[0]),
+             lambda: mf.compensation_error_global_bgr(EDGE_MODEL[0]))
+    for k, call in enumerate(calls):
+        assert _status(bbme, call) == _capi.ERR_UNSUPPORTED == -8, k
+    mf.synchronize()
+    torch.cuda.synchronize()
+    assert (out == PATTERN).all() and (st == -7).all()
     mf.close()
 
 

@@ -1,7 +1,8 @@
 """K16 k_vector_histogram, K17 k_global_moments and K18 k_global_compensate against the numpy restatements of the GLOBAL MOTION
 RULE and the GLOBAL COMPENSATION RULE (tests/test_global_motion_cpu.py), bit for bit, on injected grids and planes; the context's
 own estimate against the CPU route on the downloaded cells and mask, on every kind of context; the context-level compensation;
-refusals and state; the guard bands; sequence.stabilize_frames."""
+refusals and state, the refusal of planes beyond 8188 among them; the deepest batch; up-sampled and colour contexts; the guard
+bands; sequence.stabilize_frames.  (The kernels at 2 Mpixel and at the rule's largest planes: tests/test_gpu_scale.py.)"""
 import hashlib
 import os
 import subprocess
@@ -337,6 +338,115 @@ def test_batch_and_chain_equal_single_contexts(bbme):
             assert np.array_equal(ctx.get_pair_global_compensated(p, models[p], 1, "backward", 5), single[p]["frame"]), p
         assert all(np.array_equal(ctx.get_pair_cells(p), cells[p]) for p in range(3))
         ctx.close()
+
+
+def test_planes_beyond_8188_are_refused_and_nothing_is_written(bbme):
+    """8190 x 130 pads to 8192 x 132: every device call of the rule and the context's own estimate answer ERR_UNSUPPORTED before
+    anything is launched"""
+    import torch
+    from blockbasedmotionestimation_amd import _capi
+    z = np.zeros((130, 8190), np.uint8)
+    mf = bbme.MF(z, z, [12], [4])
+    assert (mf.padded_width, mf.padded_height) == (8192, 132)
+    CH, CW = mf.cells_shape
+    cells = torch.zeros((CH, CW, 2), dtype=torch.int16, device="cuda")
+    hist = torch.full((2, BINS), 12345, dtype=torch.int32, device="cuda")
+    words = torch.full((16,), -7, dtype=torch.int64, device="cuda")
+    tmap = torch.full((CH, CW), PATTERN, dtype=torch.uint8, device="cuda")
+    plane = torch.zeros((2 * CH, 2 * CW), dtype=torch.uint8, device="cuda")
+    out = torch.full((2 * CH, 2 * CW), PATTERN, dtype=torch.uint8, device="cuda")
+    st = torch.full((4,), -7, dtype=torch.int64, device="cuda")
+    calls = (lambda: mf.cells_vector_histogram_device(cells, hist),
+             lambda: mf.cells_global_moments_device(cells, MODELS[1], 65536, map=tmap, words=words),
+             lambda: mf.cells_global_compensate_device(plane, plane, COMP_MODELS[0][0], 1, out, st),
+             lambda: mf.global_motion(),
+             lambda: mf.draw_MVimage_global(COMP_MODELS[0][0]),
+             lambda: mf.compensation_error_global(COMP_MODELS[0][0]))
+    for k, call in enumerate(calls):
+        with pytest.raises(bbme.BbmeError) as e:
+            call()
+        assert e.value.status == _capi.ERR_UNSUPPORTED == -8, k
+    mf.synchronize()
+    torch.cuda.synchronize()
+    assert (hist == 12345).all() and (words == -7).all() and (tmap == PATTERN).all() and (out == PATTERN).all() and (st == -7).all()
+    mf.close()
+
+
+def test_deepest_batch_equals_the_cpu_route_for_every_pair(bbme):
+    """BBME_MAX_BATCH = 64 pairs behind every launch of the estimate (blockIdx.y of K16, K17 and K18, 64 rows of the model table)"""
+    w, h, search, block = 72, 56, [12, 12], [8, 8]
+    base = [bbme.synth_pair(w, h, 7300 + i, max_motion=2 + i % 4)[:2] for i in range(16)]
+    pairs = []
+    for k in range(64):                                        # sixteen distinct pairs and the same pairs rolled: distinct content
+        f1, f2 = base[k % 16]
+        sh = (2 * (k // 16), 3 * (k // 16))
+        pairs.append((np.ascontiguousarray(np.roll(f1, sh, (0, 1))), np.ascontiguousarray(np.roll(f2, sh, (0, 1)))))
+    mb = bbme.MFBatch(pairs, search, block)
+    assert mb.batch == 64
+    mb.estimate_bidirectional_async()
+    kw = VARIANTS[3]
+    got = mb.global_motion_all(maps=True, **kw)
+    assert len(got) == 64
+    models = np.stack([_assert_equals_cpu_route(bbme, mb, p, got[p], **kw) for p in range(64)])
+    assert not np.array_equal(models[0], models[63]) and len({tuple(m) for m in models}) >= 16
+    win = (mb.padding_x, mb.padding_y, mb.orig_width, mb.orig_height)
+    errs = mb.compensation_errors_global(models, 4, "backward")
+    for p in range(64):
+        I1, I2 = (mb.frame_plane_tensor(p, which).cpu().numpy() for which in (0, 1))
+        assert _stats(errs[p]) == np_global_compensate(I2, I1, models[p], 4, 0, win)[1], p
+    mb.close()
+
+
+def _check_own_estimate(bbme, mf, variants):
+    """global_motion, draw_MVimage_global and compensation_error_global of a context against the CPU route on its downloaded
+    cells and planes"""
+    mf.estimate_bidirectional_async()
+    I1, I2 = mf.get_level_planes(0)
+    win = (mf.padding_x, mf.padding_y, mf.orig_width, mf.orig_height)
+    models = []
+    for kw in variants:
+        got = mf.global_motion(**kw)
+        model = _assert_equals_cpu_route(bbme, mf, 0, got, **kw)
+        which, unit = kw["which"], 4 if kw.get("subpel") else 1
+        a, b = (I1, I2) if which == "forward" else (I2, I1)
+        exp = np_global_compensate(a, b, model, unit, 9, win)
+        assert np.array_equal(mf.draw_MVimage_global(model, unit, which, 9), exp[0]), kw
+        assert _stats(mf.compensation_error_global(model, unit, which)) == exp[1], kw
+        assert exp[1][2] > 0
+        models.append(model)
+    return models
+
+
+def test_own_estimate_on_an_upsampled_context(bbme):
+    f1, f2, _ = bbme.synth_pair(50, 34, 250, max_motion=2)
+    mf = bbme.MF(f1, f2, [20, 20], [8, 8], upsample=4)
+    assert (mf.orig_width, mf.orig_height, mf.source_width) == (200, 136, 50)
+    I1, _ = mf.get_level_planes(0)
+    py, px = mf.padding_y, mf.padding_x
+    assert np.array_equal(I1[py:py + 136, px:px + 200], bbme.resize_x4(f1))           # the planes are the up-sampled frames
+    models = _check_own_estimate(bbme, mf, (VARIANTS[0], VARIANTS[3], VARIANTS[5]))
+    assert any(m.any() for m in models)
+    mf.close()
+
+
+def test_own_estimate_on_a_colour_context_keeps_its_colour(bbme):
+    w, h = 200, 120
+    f1, f2, _ = bbme.synth_pair(w, h, 251, max_motion=5)
+    rng = np.random.default_rng(252)
+    tint = rng.integers(0, 64, (h, w, 3)).astype(np.int64)
+    c1 = np.clip(f1[:, :, None].astype(np.int64) + tint - 32, 0, 255).astype(np.uint8)
+    c2 = np.clip(f2[:, :, None].astype(np.int64) + tint - 32, 0, 255).astype(np.uint8)
+    mf = bbme.MF(c1, c2, [20, 20], [8, 8])
+    py, px = mf.padding_y, mf.padding_x
+    I1, _ = mf.get_level_planes(0)
+    assert np.array_equal(I1[py:py + h, px:px + w], bbme.bgr_to_gray(c1))               # the planes are the luma of the colour
+    models = _check_own_estimate(bbme, mf, (VARIANTS[0], VARIANTS[3], VARIANTS[5]))
+    assert any(m.any() for m in models)
+    # the stored colour is still there, and still the frames that were set
+    frame = mf.draw_MVimage_global_bgr(models[0], 1, "forward", 9)
+    assert np.array_equal(frame, bbme.global_compensate_bgr(None, c2, models[0], 1, 9, px, py)[0])
+    assert np.array_equal(mf.frame_bgr_tensor(0, 0).cpu().numpy(), c1)
+    mf.close()
 
 
 # ---- guard bands ---------------------------------------------------------------------------------------------------------------

@@ -3,15 +3,21 @@ statistics kernel leaves more than 256 partials per pair, so that lanes of k_mc_
 launch is partly filled, every cell row ends inside a lane's run and both paddings are odd (tests/test_scale_cpu.py recomputes all
 of that from the kernels' constants and proves the content non-trivial).  Injected planes and grids on single contexts; every pair
 of a batch and every frame of a chain from one launch, on fields read back from the context, so that nothing here depends on what
-the estimate found.  Every comparison is exact, against the numpy restatements of include/bbme.h's rules in tests/test_*_cpu.py."""
+the estimate found.  Global motion and global compensation (K16, K17, K18, K18b) on injected grids and planes at that shape and at
+the rule's widest and tallest plane, 8188 (section d; tests/test_global_motion_scale_cpu.py is its CPU side).  Every comparison is
+exact, against the numpy restatements of include/bbme.h's rules in tests/test_*_cpu.py."""
 import numpy as np
 import pytest
 
 import helpers as H
 from test_bgr_cpu import np_interpolate_bgr
 from test_consistency_cpu import STAT_KEYS as FB_KEYS, leaving_grids, np_cells_consistency
+from test_global_compensation_bgr_cpu import np_global_compensate_bgr
+from test_global_motion_cpu import COMP_MODELS, MODELS, np_global_compensate, np_histogram, np_moments
 from test_gpu_bgr import _device_bgr
 from test_gpu_bidirectional import _device_consistency
+from test_gpu_global_compensation_bgr import _warp
+from test_gpu_global_motion import _compensate, _hist, _moments
 from test_gpu_interpolation import _device_interpolate
 from test_gpu_temporal_filter import _device_filter
 from test_interpolation_cpu import STAT_KEYS as IP_KEYS, np_interpolate
@@ -257,3 +263,125 @@ def test_chain_temporal_filter_of_every_slot(chain1):
     run = chain.temporal_filter_run(thr)
     for s in range(3):
         assert np.array_equal(run[s], want[s][0]), s
+
+
+# ---- d. global motion and global compensation at G1 and at the rule's widest and tallest plane ----------------------------------
+def _bare_context(bbme, g, name):
+    z = np.zeros((g["h"], g["w"]), np.uint8)
+    mf = bbme.MF(z, z, g["search"], g["block"])                    # frames set, no estimate: the device calls need neither
+    assert (mf.padded_width, mf.padded_height, mf.padding_x, mf.padding_y) == H.GM_PADDED[name] + (1, 1)
+    return mf
+
+
+@pytest.fixture(scope="module")
+def gm_wide(bbme):
+    mf = _bare_context(bbme, H.GM_WIDE, "WIDE")
+    yield mf
+    mf.close()
+
+
+@pytest.fixture(scope="module")
+def gm_tall(bbme):
+    mf = _bare_context(bbme, H.GM_TALL, "TALL")
+    yield mf
+    mf.close()
+
+
+@pytest.fixture
+def gm_context(request):
+    """(name, context) of SCALE_G1, GM_WIDE or GM_TALL"""
+    if request.param == "G1":
+        return "G1", request.getfixturevalue("g1")["mf"]
+    return request.param, request.getfixturevalue({"WIDE": "gm_wide", "TALL": "gm_tall"}[request.param])
+
+
+GM_NAMES = ("G1", "WIDE", "TALL")
+
+
+@pytest.mark.parametrize("gm_context", GM_NAMES, indirect=True)
+def test_vector_histogram_strides_over_the_runs(gm_context):
+    """K16 where its 256 workgroups take a second and a third trip through the runs and the last trip ends inside a workgroup"""
+    name, mf = gm_context
+    CH, CW = mf.cells_shape
+    grids, mask = H.gm_histogram_grids(CH, CW)
+    window = H.gm_cell_window(CW, CH)
+    for gname, g in grids:
+        exp = np_histogram(g)
+        assert np.array_equal(_hist(mf, g), exp), (name, gname)
+        if gname == "uniform":
+            assert exp.max() == CH * CW > 2 ** 17
+        got = _hist(mf, g, mask, window, q_extra=5, e_extra=3, twice=True)            # twice: the call zeroes the table
+        assert np.array_equal(got, np_histogram(g, mask, window)), (name, gname, "mask and window")
+
+
+@pytest.mark.parametrize("gm_context", GM_NAMES, indirect=True)
+def test_global_moments_sum_beyond_32_bits_over_more_than_16_workgroups(gm_context):
+    """K17 where words 6..8 pass 2^40 and words 11..14 pass 2^31 (GM_WIDE, GM_TALL) and k_reduce_words<16> takes up to nine
+    trips with an uneven last one"""
+    import torch
+    name, mf = gm_context
+    CH, CW = mf.cells_shape
+    g, true, mask = H.gm_scale_grid(CH, CW)
+    window = H.gm_cell_window(CW, CH)
+    side = torch.cuda.Stream()
+    for k, (model, tol) in enumerate(((true, H.GM_TOL), (MODELS[3], 2 ** 40), (MODELS[4], 2 ** 40))):
+        exp = np_moments(g, model, tol, mask, window)
+        got = _moments(mf, g, model, tol, mask, window, map_offset=1 + k, map_extra=2, q_extra=k, e_extra=3,
+                       stream=side if k == 1 else None)
+        assert np.array_equal(got[0], exp[0]), (name, model, np.argwhere(got[0] != exp[0])[:4])
+        assert np.array_equal(got[1], exp[1]), (name, model, got[1], exp[1])
+        assert exp[1][0] > 0 and exp[1][1] > 0 and exp[1][2] > 0
+    exp = np_moments(g, true, H.GM_TOL)
+    got = _moments(mf, g, true, H.GM_TOL, want=("words",))
+    assert got[0] is None and np.array_equal(got[1], exp[1]), (name, "words alone", got[1], exp[1])
+    got = _moments(mf, g, true, H.GM_TOL, want=("map",), map_offset=3, map_extra=8)
+    assert got[1] is None and np.array_equal(got[0], exp[0]), (name, "map alone")
+
+
+@pytest.mark.parametrize("gm_context", GM_NAMES, indirect=True)
+def test_global_compensation_sums_beyond_32_bits_over_more_than_256_workgroups(gm_context):
+    """K18 where its partials take k_mc_reduce's lanes into a second trip and sse passes 2^32"""
+    name, mf = gm_context
+    W0, H0 = mf.padded_width, mf.padded_height
+    I1, I2 = H.gm_scale_planes(H0, W0)
+    odd = H.gm_plane_window(W0, H0)
+    beyond = 0
+    for k, (model, unit) in enumerate(COMP_MODELS[:4]):
+        fill, win = (0, 7, 255)[k % 3], (None, odd)[k % 2]
+        exp = np_global_compensate(I1, I2, model, unit, fill, win)
+        frame, st = _compensate(mf, I1, I2, model, unit, fill, win, out_offset=1 + k % 3, out_extra=(3, 0, 8)[k % 3])
+        assert np.array_equal(frame, exp[0]), (name, model, unit, np.argwhere(frame != exp[0])[:4])
+        assert st == exp[1], (name, model, unit, win, st, exp[1])
+        beyond += exp[1][0] > 2 ** 32
+        if k == 2:
+            assert min(exp[1][2], exp[1][3]) >= (win[2] * win[3] if win else W0 * H0) // 4           # compensates and skips in bulk
+        if k == 1:                                             # the statistics alone over the other window, the frame alone
+            other = np_global_compensate(I1, I2, model, unit, fill, None)
+            assert _compensate(mf, I1, I2, model, unit, fill, None, want=("stats",)) == (None, other[1])
+            frame, st = _compensate(mf, None, I2, model, unit, fill, want=("out",), out_offset=5)
+            assert st is None and np.array_equal(frame, other[0])
+    assert beyond >= 3
+    for unit, (tx, ty) in ((1, (3, -2)), (4, (-5, 7))):            # the whole-pixel property
+        frame, _ = _compensate(mf, None, I2, (tx * unit << 16, 0, 0, ty * unit << 16, 0, 0), unit, 77, want=("out",))
+        exp = np.full((H0, W0), 77, np.uint8)
+        exp[max(0, -ty):H0 - max(0, ty), max(0, -tx):W0 - max(0, tx)] = I2[max(0, ty):H0 - max(0, -ty), max(0, tx):W0 - max(0, -tx)]
+        assert np.array_equal(frame, exp), (name, unit, tx, ty)
+    # the largest sums: every pixel differs by 255
+    _, st = _compensate(mf, np.zeros_like(I1), np.full_like(I1, 255), (0,) * 6, 1, want=("stats",))
+    assert st == (255 * 255 * W0 * H0, 255 * W0 * H0, W0 * H0, 0) and st[0] > 2 ** 32
+
+
+@pytest.mark.parametrize("gm_context", GM_NAMES[:2], indirect=True)
+def test_colour_global_compensation_of_three_frames_from_one_launch(gm_context):
+    """K18b on colour frames of 2058 x 1038 and 8186 x 130: three frames under three models from one launch, 523 and 260 partials
+    per frame"""
+    name, mf = gm_context
+    h, w = mf.orig_height, mf.orig_width
+    c1, c2, models, unit, window = H.gm_scale_bgr_case(h, w)
+    got, st = _warp(mf, c1, c2, models, unit, 3, window, in_extra=1, out_extra=5, out_offset=1)
+    for k in range(3):
+        exp = np_global_compensate_bgr(c1[k], c2[k], models[k], unit, 3, mf.padding_x, mf.padding_y, window)
+        assert np.array_equal(got[k], exp[0]), (name, k, np.argwhere(got[k] != exp[0])[:4])
+        assert st[k] == exp[1], (name, k, st[k], exp[1])
+        assert exp[1][0] > 2 ** 32
+    assert H.stats_differ_pairwise(st, words=(0, 1)), st
