@@ -9,7 +9,8 @@ from .motion_framework import (MF, MFBatch, MFChain, plan_padding, pad_zero, pyr
                                interpolate_cells, color_cells, bgr_to_gray, interpolate_cells_bgr, temporal_filter_cells,
                                temporal_filter_cells_bgr, subpel_cells, compensate_cells_subpel, interpolate_cells_subpel,
                                interpolate_cells_subpel_bgr, temporal_filter_cells_subpel, temporal_filter_cells_subpel_bgr,
-                               compose_cells, temporal_filter_cells_wide, vector_histogram_cells, global_moments_cells,
+                               compose_cells, temporal_filter_cells_wide, temporal_filter_cells_wide_bgr, vector_histogram_cells,
+                               global_moments_cells,
                                solve_global_motion, global_motion_cells, global_compensate, global_compensate_bgr,
                                DIR_FORWARD, DIR_BACKWARD, FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE)
 from .rw_flow import Flow, FlowWriter, subsample_div4  # noqa: F401
@@ -20,5 +21,6 @@ __all__ = ["MF", "MFBatch", "MFChain", "Flow", "FlowWriter", "BbmeError", "plan_
            "FB_CONSISTENT", "FB_INCONSISTENT", "FB_OUTSIDE", "interpolate_cells", "color_cells", "bgr_to_gray", "interpolate_cells_bgr",
            "temporal_filter_cells", "temporal_filter_cells_bgr", "subpel_cells", "compensate_cells_subpel",
            "interpolate_cells_subpel", "interpolate_cells_subpel_bgr", "temporal_filter_cells_subpel",
-           "temporal_filter_cells_subpel_bgr", "compose_cells", "temporal_filter_cells_wide", "vector_histogram_cells",
+           "temporal_filter_cells_subpel_bgr", "compose_cells", "temporal_filter_cells_wide", "temporal_filter_cells_wide_bgr",
+           "vector_histogram_cells",
            "global_moments_cells", "solve_global_motion", "global_motion_cells", "global_compensate", "global_compensate_bgr"]

@@ -170,6 +170,14 @@ SIGNATURES = {
     "bbme_wide_temporal_filter_chain_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
     "bbme_get_wide_temporal_filtered_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
     "bbme_wide_temporal_filter_stats": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_wide_temporal_filter_bgr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                                     C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bbme_cells_wide_temporal_filter_bgr_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                             C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p,
+                                                             C.c_void_p]),
+    "bbme_wide_temporal_filter_bgr_chain_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_size_t, C.c_void_p]),
+    "bbme_get_wide_temporal_filtered_bgr_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_wide_temporal_filter_bgr_stats": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_temporal_filter_bgr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                                 C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bbme_cells_temporal_filter_bgr_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,

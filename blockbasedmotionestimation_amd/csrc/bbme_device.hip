@@ -361,6 +361,8 @@ struct bbme_ctx {
                                                   // quarter pels.  Allocated at first use (wide_prepare)
     StatsScratch wide_stats;                      // bbme_wide_temporal_filter_stats (two quadruples per slot) and
                                                   // bbme_cells_wide_temporal_filter_device (two more)
+    StatsScratch wide_bgr_stats;                  // the same of bbme_wide_temporal_filter_bgr_stats and
+                                                  // bbme_cells_wide_temporal_filter_bgr_device
     // GLOBAL MOTION RULE, all allocated at first use
     DevBuf<unsigned long long> gm_words;          // sixteen result words per pair (BBME_MAX_BATCH of them), then K17's partials of a
                                                   // launch over every pair, then those of a caller's launch (gm_scratch)
@@ -3630,12 +3632,15 @@ int bbme_compose_chain_device(bbme_ctx *c, int first, int count, int side, int16
 
 // Statistics scratch: two result quadruples per slot ({w_k > 0}, {weights, |out - C|, 0, 0}), two more for a caller's launch,
 // then the partials of a launch over every slot and those of a caller's: one size per context
-static int wide_scratch(bbme_ctx *c)
+static int wide_scratch(bbme_ctx *c, StatsScratch &s, const char *what = "the wide temporal filter statistics")
 {
-    return c->wide_stats.ensure(2 * kTfMaxFrames + 2, tf_groups(c), 2 * c->frames(), 2, "the wide temporal filter statistics");
+    return s.ensure(2 * kTfMaxFrames + 2, tf_groups(c), 2 * c->frames(), 2, what);
 }
 
-static unsigned long long *wide_results_caller(bbme_ctx *c) { return c->wide_stats.results() + (size_t)4 * 2 * kTfMaxFrames; }
+static int wide_scratch(bbme_ctx *c) { return wide_scratch(c, c->wide_stats); }
+
+static unsigned long long *wide_results_caller(StatsScratch &s) { return s.results() + (size_t)4 * 2 * kTfMaxFrames; }
+static unsigned long long *wide_results_caller(bbme_ctx *c) { return wide_results_caller(c->wide_stats); }
 
 static WtfArgs wide_args(const bbme_ctx *c, int thr, const int *window)
 {
@@ -3651,12 +3656,17 @@ static WtfArgs wide_args(const bbme_ctx *c, int thr, const int *window)
     return a;
 }
 
-// k_wide_temporal_filter over `count` frames and, with d_results, k_mc_reduce of its partials into d_results[8 z ..]
-static int enqueue_wide(bbme_ctx *c, WtfArgs &a, int count, unsigned long long *partial, unsigned long long *d_results, hipStream_t stream)
+static auto wide_kernel(const WtfArgs &) { return k_wide_temporal_filter<kTfRunsPerLane>; }
+static auto wide_kernel(const WtfBgrArgs &) { return k_wide_temporal_filter_bgr<kTfRunsPerLane>; }
+
+// k_wide_temporal_filter (WtfArgs) or k_wide_temporal_filter_bgr (WtfBgrArgs) over `count` frames and, with d_results, k_mc_reduce
+// of its partials into d_results[8 z ..]
+template <class Args>
+static int enqueue_wide(bbme_ctx *c, Args &a, int count, unsigned long long *partial, unsigned long long *d_results, hipStream_t stream)
 {
     const long long groups = tf_groups(c);
     a.partial = d_results ? partial : nullptr;
-    hipLaunchKernelGGL(k_wide_temporal_filter<kTfRunsPerLane>, dim3((unsigned)groups, 1u, (unsigned)count), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(wide_kernel(a), dim3((unsigned)groups, 1u, (unsigned)count), dim3(256), 0, stream, a);
     if (d_results) hipLaunchKernelGGL(k_mc_reduce, dim3(2u * (unsigned)count), dim3(256), 0, stream, a.partial, (int)groups, d_results);
     HIP_TRY(hipGetLastError());
     return BBME_OK;
@@ -3801,6 +3811,151 @@ int bbme_wide_temporal_filter_stats(bbme_ctx *c, int thr, const int *window, uns
     if (int rc = download_stats(c, c->wide_stats, 2 * slots, s.data(), [&] {
             if (int rc = wide_prepare(c, a, 0, slots, c->stream, what)) return rc;
             return enqueue_wide(c, a, slots, c->wide_stats.partials_all(), c->wide_stats.results(), c->stream);
+        }))
+        return rc;
+    for (int f = 0; f < slots; ++f)
+        for (int k = 0; k < 6; ++k) stats[6 * f + k] = s[8 * f + k];
+    return BBME_OK;
+}
+
+// ---- the same on the B,G,R frames (the BGR WIDE TEMPORAL FILTER RULE of include/bbme.h; K15b k_wide_temporal_filter_bgr) ---------
+// The wide path's arguments, grids and launch (wide_args, wide_prepare, enqueue_wide) with the colour flavour's frames, colour
+// checks and output checks.  The grids are made on the LUMA planes into the buffers the grey wide calls use (the same cells of the
+// same planes give the same vectors); the filter launch then reads only colour.
+
+static WtfBgrArgs wide_bgr_args(const bbme_ctx *c, int thr, const int *window)
+{
+    WtfBgrArgs a{};
+    static_cast<WtfArgs &>(a) = wide_args(c, thr, window);
+    a.fw = c->geom.width; a.fh = c->geom.height; a.pad_x = c->geom.pad_x; a.pad_y = c->geom.pad_y;
+    a.bgr_pitch = 3 * c->geom.width;
+    return a;
+}
+
+int bbme_cells_wide_temporal_filter_bgr_device(bbme_ctx *c, const uint8_t *const d_frames[4], const uint8_t *d_cur, int bgr_pitch,
+                                               const int16_t *const d_grids[4], int q4_pitch_cells, int thr, const int *window,
+                                               uint8_t *d_out, int out_pitch, uint16_t *d_weights, int weights_pitch,
+                                               unsigned long long *d_stats6, void *hip_stream)
+{
+    const char *what = "bbme_cells_wide_temporal_filter_bgr_device";
+    if (int rc = check_ctx(c)) return rc;
+    const Level &L = c->lv[0];
+    if (!d_frames || !d_grids || !d_cur || (!d_out && !d_weights && !d_stats6)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (q4_pitch_cells < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch_cells, L.width / 2);
+    bool any = false;
+    for (int k = 0; k < 4; ++k) {
+        if ((d_frames[k] == nullptr) != (d_grids[k] == nullptr))
+            return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its frame and its grid", what);
+        any = any || d_frames[k];
+    }
+    if (!any) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (int rc = check_tf(c, thr, window, what)) return rc;
+    if ((long long)bgr_pitch < 3LL * c->geom.width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, bgr_pitch, c->geom.width);
+    if (d_out) if (int rc = check_bgr_frames(c, 1, out_pitch, 0, what)) return rc;
+    if (d_weights && weights_pitch < L.width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: weight map pitch %d < %d cells per row", what, weights_pitch, L.width / 2);
+    if (d_out && overlaps_input(d_out, out_pitch, {d_cur, d_frames[0], d_frames[1], d_frames[2], d_frames[3]}, bgr_pitch,
+                                3 * c->geom.width, c->geom.height))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input frame", what);
+    HIP_TRY(hipSetDevice(c->device));
+    StatsScratch &scratch = c->wide_bgr_stats;
+    if (d_stats6) if (int rc = wide_scratch(c, scratch, "the colour wide temporal filter statistics")) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    WtfBgrArgs a = wide_bgr_args(c, thr, window);
+    a.cur = d_cur; a.bgr_pitch = bgr_pitch;
+    for (int k = 0; k < 4; ++k) { a.x[k] = d_frames[k]; a.g[k] = reinterpret_cast<const mv_t *>(d_grids[k]); }
+    a.q4_pitch = q4_pitch_cells;
+    a.first_prev = a.last_next = 2;
+    a.out = d_out; a.out_pitch = out_pitch;
+    a.wmap = d_weights; a.wmap_pitch = weights_pitch;
+    if (int rc = enqueue_wide(c, a, 1, scratch.partials_caller(), d_stats6 ? wide_results_caller(scratch) : nullptr, stream)) return rc;
+    if (d_stats6)      // the first six words of the two quadruples
+        HIP_TRY(hipMemcpyAsync(d_stats6, wide_results_caller(scratch), 6 * sizeof(unsigned long long), hipMemcpyDeviceToDevice, stream));
+    return BBME_OK;
+}
+
+// wide_prepare's grids for slots first .. first + count - 1, then the frames those slots have in the colour store (slots
+// bgr_stride bytes apart, in 64 bits: a deep chain's store exceeds 4 GB).  A base the launch never dereferences is address
+// arithmetic only.
+static int wide_bgr_prepare(bbme_ctx *c, WtfBgrArgs &a, int first, int count, hipStream_t stream, const char *what)
+{
+    if (int rc = wide_prepare(c, a, first, count, stream, what)) return rc;
+    const long long s_slot = (long long)c->bgr_stride;
+    const uintptr_t cur = reinterpret_cast<uintptr_t>(c->bgr.get()) + first * s_slot;
+    a.cur = reinterpret_cast<const uint8_t *>(cur);
+    a.plane_z = s_slot;
+    for (int k = 0; k < 4; ++k) {
+        const long long step = (k & 1 ? 1 : -1) * (1 + (k >> 1));                    // slots from C to the neighbour
+        a.x[k] = reinterpret_cast<const uint8_t *>(cur + step * s_slot);
+    }
+    return BBME_OK;
+}
+
+// what the context-level calls of the colour wide filter share: check_wide_own, and stored colour in every slot that the slots
+// first .. first + count - 1 read
+static int check_wide_bgr_own(const bbme_ctx *c, int first, int count, int thr, const int *window, const char *what)
+{
+    if (int rc = check_wide_own(c, thr, window, what)) return rc;
+    return check_tf_bgr_colour(c, first - 2, first + count + 1, what);
+}
+
+static int enqueue_own_wide_bgr(bbme_ctx *c, const char *what, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                size_t out_stride, hipStream_t stream)
+{
+    WtfBgrArgs a = wide_bgr_args(c, thr, nullptr);
+    if (int rc = wide_bgr_prepare(c, a, first, count, stream, what)) return rc;
+    a.out = d_out; a.out_pitch = out_pitch; a.out_stride = out_stride;
+    return enqueue_wide(c, a, count, nullptr, nullptr, stream);
+}
+
+int bbme_wide_temporal_filter_bgr_chain_device(bbme_ctx *c, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                               size_t out_stride, void *hip_stream)
+{
+    const char *what = "bbme_wide_temporal_filter_bgr_chain_device";
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (first < 0 || count < 1 || (long long)first + count > c->batch + 1)
+        return bbme::fail(BBME_ERR_INVALID, "%s: slots %d .. %d + %d - 1 are not inside 0 .. %d", what, first, first, count, c->batch);
+    if (!d_out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_bgr_frames(c, count, out_pitch, out_stride, what)) return rc;
+    if (int rc = check_wide_bgr_own(c, first, count, thr, nullptr, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_wide_bgr(c, what, first, count, thr, d_out, out_pitch, out_stride, stream);
+}
+
+int bbme_get_wide_temporal_filtered_bgr_host(bbme_ctx *c, int slot, int thr, uint8_t *out)
+{
+    const char *what = "bbme_get_wide_temporal_filtered_bgr_host";
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (slot < 0 || slot > c->batch) return bbme::fail(BBME_ERR_INVALID, "%s: slot %d is not inside 0 .. %d", what, slot, c->batch);
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_wide_bgr_own(c, slot, 1, thr, nullptr, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int row = 3 * c->geom.width;
+    return download_staged(c, (size_t)row * c->geom.height, "the wide filtered colour frame", out, [&](uint8_t *d) {
+        return enqueue_own_wide_bgr(c, what, slot, 1, thr, d, row, 0, c->stream);
+    });
+}
+
+int bbme_wide_temporal_filter_bgr_stats(bbme_ctx *c, int thr, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_wide_temporal_filter_bgr_stats";
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = chain_context_only(c, what)) return rc;
+    if (int rc = check_wide_bgr_own(c, 0, c->batch + 1, thr, window, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    StatsScratch &scratch = c->wide_bgr_stats;
+    if (int rc = wide_scratch(c, scratch, "the colour wide temporal filter statistics")) return rc;
+    const int slots = c->batch + 1;
+    std::vector<unsigned long long> s((size_t)8 * slots);
+    WtfBgrArgs a = wide_bgr_args(c, thr, window);
+    if (int rc = download_stats(c, scratch, 2 * slots, s.data(), [&] {
+            if (int rc = wide_bgr_prepare(c, a, 0, slots, c->stream, what)) return rc;
+            return enqueue_wide(c, a, slots, scratch.partials_all(), scratch.results(), c->stream);
         }))
         return rc;
     for (int f = 0; f < slots; ++f)

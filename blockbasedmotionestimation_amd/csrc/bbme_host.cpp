@@ -1386,6 +1386,34 @@ int bbme_subpel_temporal_filter_host(const uint8_t *prev, const uint8_t *cur, co
     return BBME_OK;
 }
 
+// What the BGR SUBPEL TEMPORAL FILTER RULE and the BGR WIDE TEMPORAL FILTER RULE say of ONE neighbour `frame` of the cell with origin
+// (ox, oy) on the padded view of `cur` (both packed width x height B,G,R frames) and the quarter-pel vector (qx, qy): its weight,
+// and channel k of the rounded sample X'[j, i] in x[2 i + j][k].  A tap of weight 0 or outside the frame is not read.
+static int bgr_subpel_neighbour(const uint8_t *frame, const uint8_t *cur, int width, int height, int pad_x, int pad_y, int ox, int oy,
+                                int qx, int qy, int thr, int (&x)[4][3])
+{
+    const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y;
+    // channel k of the pixel at the padded position (X, Y) of a frame: 0 outside the frame
+    const auto at = [&](const uint8_t *img, int X, int Y, int k) {
+        const int px = X - pad_x, py = Y - pad_y;
+        return px < 0 || py < 0 || px >= width || py >= height ? 0 : (int)img[((size_t)py * width + px) * 3 + k];
+    };
+    const int fx = qx & 3, fy = qy & 3, sx = ox + (qx >> 2), sy = oy + (qy >> 2);
+    if (sx < 0 || sx + 2 + (fx != 0) > W0 || sy < 0 || sy + 2 + (fy != 0) > H0) return 0;
+    int cost = 0;
+    for (int k = 0; k < 3; ++k) {
+        int cost_k = 0;
+        for (int i = 0; i < 2; ++i)
+            for (int j = 0; j < 2; ++j) {
+                const auto tap = [&](int weight, int dx, int dy) { return weight ? weight * at(frame, sx + j + dx, sy + i + dy, k) : 0; };
+                x[2 * i + j][k] = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+                cost_k += abs(at(cur, ox + j, oy + i, k) - x[2 * i + j][k]);
+            }
+        cost = std::max(cost, cost_k);
+    }
+    return cost < thr ? 8 * (thr - cost) / thr : 0;
+}
+
 // The BGR SUBPEL TEMPORAL FILTER RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of
 // k_subpel_temporal_filter_bgr).  A tap of weight 0 or outside the frame is not read.
 int bbme_subpel_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur, const uint8_t *next, int width, int height, int pad_x,
@@ -1419,26 +1447,9 @@ int bbme_subpel_temporal_filter_bgr_host(const uint8_t *prev, const uint8_t *cur
             const size_t c = (size_t)cy * cw + cx;
             const int ox = 2 * cx, oy = 2 * cy;
             int w[2] = {0, 0}, x[2][4][3] = {};                // the weights; channel k of the rounded sample X'[j, i] at [2 i + j][k]
-            for (int n = 0; n < 2; ++n) {
-                if (!frames[n]) continue;
-                const int qx = grids[n][2 * c], qy = grids[n][2 * c + 1];
-                const int fx = qx & 3, fy = qy & 3, sx = ox + (qx >> 2), sy = oy + (qy >> 2);
-                if (sx < 0 || sx + 2 + (fx != 0) > W0 || sy < 0 || sy + 2 + (fy != 0) > H0) continue;
-                int cost = 0;
-                for (int k = 0; k < 3; ++k) {
-                    int cost_k = 0;
-                    for (int i = 0; i < 2; ++i)
-                        for (int j = 0; j < 2; ++j) {
-                            const auto tap = [&](int weight, int dx, int dy) {
-                                return weight ? weight * at(frames[n], sx + j + dx, sy + i + dy, k) : 0;
-                            };
-                            x[n][2 * i + j][k] = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
-                            cost_k += abs(at(cur, ox + j, oy + i, k) - x[n][2 * i + j][k]);
-                        }
-                    cost = std::max(cost, cost_k);
-                }
-                if (cost < thr) w[n] = 8 * (thr - cost) / thr;
-            }
+            for (int n = 0; n < 2; ++n)
+                if (frames[n])
+                    w[n] = bgr_subpel_neighbour(frames[n], cur, width, height, pad_x, pad_y, ox, oy, grids[n][2 * c], grids[n][2 * c + 1], thr, x[n]);
             const int S = 8 + w[0] + w[1];
             unsigned diff = 0;
             for (int i = 0; i < 2; ++i)
@@ -1551,6 +1562,66 @@ int bbme_wide_temporal_filter_host(const uint8_t *const planes[4], const uint8_t
                     const int v = num / S;
                     if (out) out[at] = (uint8_t)v;
                     diff += (unsigned)abs(v - (int)cur[at]);
+                }
+            if (weights) weights[c] = (uint16_t)(w[0] | w[1] << 4 | w[2] << 8 | w[3] << 12);
+            if (win.contains(cx, cy)) {
+                for (int n = 0; n < 4; ++n) { s[n] += w[n] > 0; s[4] += (unsigned)w[n]; }
+                s[5] += diff;
+            }
+        }
+    if (stats6) memcpy(stats6, s, sizeof s);
+    return BBME_OK;
+}
+
+// The BGR WIDE TEMPORAL FILTER RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of
+// k_wide_temporal_filter_bgr): bbme_subpel_temporal_filter_bgr_host's neighbour, up to four times, in bbme_wide_temporal_filter_host's
+// blend, map and statistics.
+int bbme_wide_temporal_filter_bgr_host(const uint8_t *const frames[4], const uint8_t *cur, int width, int height, int pad_x, int pad_y,
+                                       const int16_t *const grids[4], int q4_pitch_cells, int thr, const int *window, uint8_t *out,
+                                       uint16_t *weights, unsigned long long *stats6)
+{
+    const char *what = "bbme_wide_temporal_filter_bgr_host";
+    if (!frames || !grids || !cur || (!out && !weights && !stats6)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    bool any = false;
+    for (int n = 0; n < 4; ++n) {
+        if ((frames[n] == nullptr) != (grids[n] == nullptr))
+            return bbme::fail(BBME_ERR_INVALID, "%s: a neighbour needs both its frame and its grid", what);
+        any = any || frames[n];
+    }
+    if (!any) return bbme::fail(BBME_ERR_INVALID, "%s: no neighbour", what);
+    if (width < 1 || height < 1 || pad_x < 0 || pad_y < 0 || (long long)width + 2LL * pad_x > INT32_MAX ||
+        (long long)height + 2LL * pad_y > INT32_MAX)
+        return bbme::fail(BBME_ERR_INVALID, "%s: bad frame %dx%d with padding (%d, %d)", what, width, height, pad_x, pad_y);
+    const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y;
+    if ((W0 & 1) || (H0 & 1)) return bbme::fail(BBME_ERR_INVALID, "%s: the padded view %dx%d is not a plane of 2x2 cells", what, W0, H0);
+    if (thr < 1 || thr > 1021) return bbme::fail(BBME_ERR_INVALID, "%s: strength %d outside 1..1021", what, thr);
+    const int cw = W0 / 2, ch = H0 / 2;
+    if (q4_pitch_cells < cw) return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, q4_pitch_cells, cw);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, cw, ch, what, "cells")) return rc;
+    unsigned long long s[6] = {0, 0, 0, 0, 0, 0};
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const size_t c = (size_t)cy * cw + cx, g = (size_t)cy * q4_pitch_cells + cx;
+            const int ox = 2 * cx, oy = 2 * cy;
+            int w[4] = {0, 0, 0, 0}, x[4][4][3] = {};           // the weights; channel k of the rounded sample X'_n[j, i] at [n][2 i + j][k]
+            for (int n = 0; n < 4; ++n)
+                if (frames[n])
+                    w[n] = bgr_subpel_neighbour(frames[n], cur, width, height, pad_x, pad_y, ox, oy, grids[n][2 * g], grids[n][2 * g + 1], thr, x[n]);
+            const int S = 8 + w[0] + w[1] + w[2] + w[3];
+            unsigned diff = 0;
+            for (int i = 0; i < 2; ++i)
+                for (int j = 0; j < 2; ++j) {
+                    const int fxp = ox + j - pad_x, fyp = oy + i - pad_y;
+                    const bool inside = fxp >= 0 && fyp >= 0 && fxp < width && fyp < height;
+                    for (int k = 0; k < 3; ++k) {
+                        const int cv = inside ? (int)cur[((size_t)fyp * width + fxp) * 3 + k] : 0;
+                        int num = 8 * cv + S / 2;
+                        for (int n = 0; n < 4; ++n) num += w[n] * x[n][2 * i + j][k];
+                        const int v = num / S;
+                        if (out && inside) out[((size_t)fyp * width + fxp) * 3 + k] = (uint8_t)v;
+                        diff += (unsigned)abs(v - cv);
+                    }
                 }
             if (weights) weights[c] = (uint16_t)(w[0] | w[1] << 4 | w[2] << 8 | w[3] << 12);
             if (win.contains(cx, cy)) {

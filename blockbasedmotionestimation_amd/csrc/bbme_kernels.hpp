@@ -3179,7 +3179,8 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
 // k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate, K12b k_subpel_interpolate_bgr, K13
-// k_subpel_temporal_filter, K13b k_subpel_temporal_filter_bgr, K14 k_compose_cells and K15 k_wide_temporal_filter.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_subpel_temporal_filter, K13b k_subpel_temporal_filter_bgr, K14 k_compose_cells, K15 k_wide_temporal_filter and K15b
+// k_wide_temporal_filter_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window (K14
 // two of them, K15 six: two quadruples).  The pieces, each written once below and used by every kernel that has the step:
@@ -5017,6 +5018,169 @@ __global__ __launch_bounds__(256) void k_wide_temporal_filter(WtfArgs a)
             else for (int j = 0; j < n; ++j) d[j] = (uint16_t)(ws[j >> 1] >> (16 * (j & 1)));
         }
         if (a.out) store_rows2(a.out + blockIdx.z * a.out_stride + (size_t)oy * a.out_pitch + 2 * x0, a.out_pitch, n, rows);
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[2][4][4];
+    store_partial4(a.partial, 2 * (size_t)blockIdx.z, part[0], cnt[0], cnt[1], cnt[2], cnt[3]);
+    store_partial4(a.partial, 2 * (size_t)blockIdx.z + 1, part[1], wsum, dsum, 0u, 0u);
+}
+
+// =======================================================================================
+// K15b.  The BGR WIDE TEMPORAL FILTER RULE of include/bbme.h: K15 on B,G,R frames, each neighbour's cell taken as K13b takes it.
+// Neighbours k = 0 .. 3 = P1, N1, P2, N2, each a colour frame x[k] with a quarter-pel grid g[k] on C; for each present one
+// (qx, qy) = Q[cy][cx], s = o + (qx >> 2, qy >> 2), f = (qx & 3, qy & 3), valid when every tap of non-zero weight lies in the padded
+// view; its cell is the four rounded bilinear samples of each channel (si_bgr_cell: a pixel outside the frame 0, a tap of weight 0
+// never addressed), its cost the largest per-channel SAD on the rounded samples (bgr_cell_cost on K9b's cell-row layout) and its
+// weight tf_cost_weight's, as stf_bgr_weight does all three.
+// The samples are not held until S is known: the numerators 8 C + sum w_k X'_k do not depend on S, so each neighbour's w_k X'_k is
+// added into the cell's numerators as the neighbour is done.  They stay in si_bgr_cell's layout, B in bits 0-15 and R in bits
+// 16-31 of one dword (each at most 255 * 40 = 10200: no carry from B into R) and G in a dword of its own, so a neighbour costs 8
+// multiply-adds a cell and the cell holds 8 dwords whatever the neighbour count; S / 2 is added when S is known.
+// Layout is K13b's and K15's, made of the same pieces: the shared split of runs of 4 cells (gather_index / gather_split), the grids
+// by load_mv4 with rows q4_pitch cells apart, the run's own rows by bgr_load_rows where the run is whole and inside the frame
+// (bgr_two cell by cell otherwise), the output rows by bgr_row_put and bgr_store_rows, K15's uint16 map store (before the rows).  A
+// run with no pixel in the frame is skipped before any load unless the map or the statistics are asked for.
+// blockIdx.z = the frame of a run; every colour frame is addressed base + z plane_z (bytes: the colour store's slot stride) and
+// every grid base + z g_z (words); first_prev / last_next decide which neighbours a slot has, as in K15.
+// The divisions are K15's with K15's bounds: by thr as K9; by S, n <= 255 * 40 + 20 = 10220 and e <= 40, the 33 magics of
+// S = 8..40 come with the arguments and are read from LDS.
+// Statistics as K15: six counters in 32 bits per lane (at most 4 RPL cells: a count each, a weight sum <= 32, a change <= 3060),
+// two partial quadruples per workgroup (store_partial4, frames 2 z and 2 z + 1), then k_mc_reduce: no atomics.
+// A template, as K12b, K13b and K15: a template's code lies behind the estimate's template kernels in the code object.
+// =======================================================================================
+// WtfArgs with cur / x[] and out the fw x fh B,G,R frames (rows bgr_pitch and out_pitch bytes apart), width x height the padded
+// view, and the frame's place inside that view
+struct WtfBgrArgs : WtfArgs {
+    int fw, fh, pad_x, pad_y, bgr_pitch;
+};
+
+// One neighbour of the cell (c0, c1: its two rows of 6 bytes) with origin (ox, oy) on the padded view: its weight w, and w times
+// its rounded samples added into the cell's numerators (ne: B and R, ng: G; [row][pixel])
+__device__ __forceinline__ uint32_t wtf_bgr_add(const uint8_t *X, const WtfBgrArgs &a, int ox, int oy, mv_t g, uint64_t c0, uint64_t c1,
+                                                uint32_t thr, uint32_t magic_thr, uint32_t (&ne)[2][2], uint32_t (&ng)[2][2])
+{
+    const int qx = mv_x(g), qy = mv_y(g);
+    const int fx = qx & 3, fy = qy & 3;
+    const int sx = ox + (qx >> 2), sy = oy + (qy >> 2);
+    if (sx < 0 || sy < 0 || sx + 2 + (fx != 0) > a.width || sy + 2 + (fy != 0) > a.height) return 0u;
+    uint32_t e[2][2], gr[2][2];
+    si_bgr_cell(X, a.bgr_pitch, a.fw, a.fh, sx - a.pad_x, sy - a.pad_y, fx, fy, e, gr);
+    uint32_t lo[2], hi[2];                                    // B0 G0 R0 B1; G1 R1
+#pragma unroll
+    for (int r = 0; r < 2; ++r) {
+        lo[r] = (e[r][0] & 0xffu) | gr[r][0] << 8 | (e[r][0] & 0xff0000u) | e[r][1] << 24;
+        hi[r] = gr[r][1] | (e[r][1] >> 16) << 8;
+    }
+    const uint32_t cost = bgr_cell_cost((uint32_t)c0, (uint32_t)c1, (uint32_t)(c0 >> 32) | (uint32_t)(c1 >> 32) << 16,
+                                        lo[0], lo[1], hi[0] | hi[1] << 16);
+    const uint32_t w = tf_cost_weight(cost, thr, magic_thr);
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int m = 0; m < 2; ++m) {
+            ne[r][m] += w * e[r][m];
+            ng[r][m] += w * gr[r][m];
+        }
+    return w;
+}
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_wide_temporal_filter_bgr(WtfBgrArgs a)
+{
+    __shared__ uint32_t magic_s[33];
+    if (threadIdx.x < 33) magic_s[threadIdx.x] = a.magic_s[threadIdx.x];
+    __syncthreads();
+    const long long z = blockIdx.z;
+    const int prevs = min(2, (int)blockIdx.z + a.first_prev), nexts = min(2, (int)(gridDim.z - 1 - blockIdx.z) + a.last_next);
+    const uint8_t *C = a.cur + z * a.plane_z;
+    const uint8_t *X[4];
+    const mv_t *Q[4];
+    bool has[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        has[k] = a.x[k] && ((k & 1) ? nexts : prevs) > (k >> 1);
+        X[k] = has[k] ? a.x[k] + z * a.plane_z : nullptr;
+        Q[k] = has[k] ? a.g[k] + z * a.g_z : nullptr;
+    }
+    const int CW = a.cw;
+    const uint32_t thr = (uint32_t)a.thr, magic_thr = a.magic_thr;
+    uint32_t cnt[4] = {0, 0, 0, 0}, wsum = 0, dsum = 0;
+    // the loop over the lane's runs stays a loop: one run is four cells of four neighbours, 16 inlined si_bgr_cell, and the
+    // compiler declines to unroll it further
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, CW, cy, x0, n);
+        const int oy = 2 * cy;
+        const int fy = oy - a.pad_y, fx = 2 * x0 - a.pad_x;    // the run's first pixel in frame coordinates
+        if (fy + 1 < 0 || fy >= a.fh || fx + 2 * n <= 0 || fx >= a.fw) {      // no pixel of the run is in the frame
+            if (!a.partial && !a.wmap) continue;
+        }
+        const size_t g0 = (size_t)cy * a.q4_pitch + x0;
+        uint32_t g[4][4] = {};
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (has[k]) load_mv4(Q[k] + g0, n, g[k]);
+        const bool whole = bgr_run_whole(n, fx, a.fw);        // the run's 8 pixels lie inside a frame row
+        uint64_t crow[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's own two rows, 24 bytes each
+        if (whole) bgr_load_rows(C, a.bgr_pitch, a.fh, fx, fy, crow);
+        const bool in_rows = a.partial && cy >= a.wy0 && cy < a.wy1;
+        uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows
+        uint32_t ws[2] = {0, 0};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int ox = 2 * (x0 + j);
+            uint64_t c[2];
+            uint32_t ne[2][2], ng[2][2];                      // the numerators 8 C + sum w_k X'_k
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                c[yy] = whole ? bgr_row_get(crow[yy], j) : bgr_two(C, a.bgr_pitch, a.fw, a.fh, fx + 2 * j, fy + yy);
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const uint32_t p = (uint32_t)(c[yy] >> (24 * m));
+                    ne[yy][m] = 8u * (p & 0xff00ffu);
+                    ng[yy][m] = 8u * ((p >> 8) & 0xffu);
+                }
+            }
+            uint32_t w[4], wt = 0, wm = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                w[k] = has[k] ? wtf_bgr_add(X[k], a, ox, oy, g[k][j], c[0], c[1], thr, magic_thr, ne, ng) : 0u;
+                wt += w[k];
+                wm |= w[k] << (4 * k);
+            }
+            const uint32_t S = 8u + wt, mg = magic_s[wt], half = S >> 1;
+            uint32_t diff = 0;
+#pragma unroll
+            for (int yy = 0; yy < 2; ++yy) {
+                uint64_t px = 0;
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const uint32_t vb = __umulhi((ne[yy][m] & 0xffffu) + half, mg);
+                    const uint32_t vg = __umulhi(ng[yy][m] + half, mg);
+                    const uint32_t vr = __umulhi((ne[yy][m] >> 16) + half, mg);
+                    px |= (uint64_t)(vb | vg << 8 | vr << 16) << (24 * m);
+                }
+                bgr_row_put(rows[yy], j, px);
+                diff = __builtin_amdgcn_sad_u8((uint32_t)px, (uint32_t)c[yy], diff);
+                diff = __builtin_amdgcn_sad_u8((uint32_t)(px >> 32), (uint32_t)(c[yy] >> 32), diff);
+            }
+            ws[j >> 1] |= wm << (16 * (j & 1));
+            if (in_rows && x0 + j >= a.wx0 && x0 + j < a.wx1) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) cnt[k] += w[k] != 0u;
+                wsum += wt;
+                dsum += diff;
+            }
+        }
+        if (a.wmap) {
+            uint16_t *d = a.wmap + (size_t)cy * a.wmap_pitch + x0;
+            if (n == 4 && ((uintptr_t)d & 7u) == 0) *reinterpret_cast<uint2 *>(d) = make_uint2(ws[0], ws[1]);
+            else for (int j = 0; j < n; ++j) d[j] = (uint16_t)(ws[j >> 1] >> (16 * (j & 1)));
+        }
+        if (a.out) bgr_store_rows(a.out + blockIdx.z * a.out_stride, a.out_pitch, a.fw, a.fh, fx, fy, n, whole, rows);
     }
     if (!a.partial) return;
     __shared__ uint32_t part[2][4][4];

@@ -1380,6 +1380,46 @@ class MF:
             _ptr(stats), C.c_void_p(stream or 0)))
         return out, weights, stats
 
+    def cells_temporal_filter_wide_bgr_device(self, cur, frames, grids, strength=64, out=None, weights=None, stats=None, window=None,
+                                              stream=None):
+        """The BGR wide temporal filter rule on any colour frames and quarter-pel grids in HBM: cur a uint8 CUDA tensor (H, W, 3)
+        with packed pixels (rows may be further apart than 3 W); frames and grids sequences of four, P1, N1, P2, N2, None =
+        absent: frames as cur with its row pitch, grids int16 (CH, CW, 2) on cur with one common row pitch (strided row views
+        welcome).  out uint8 (H, W, 3) with packed pixels, weights int16 or uint16 (CH, CW) holding w_k << 4 k with unit column
+        stride, stats an int64 or uint64 tensor of 6, each optional, not all three.  On the given HIP stream handle (default: the
+        context's), ordered behind the context's stream; no host wait.  Needs neither frames nor an estimate."""
+        import torch
+        what = "cells_temporal_filter_wide_bgr_device"
+        ch, cw = self.cells_shape
+        h, w = self.orig_height, self.orig_width
+        frames, grids = list(frames), list(grids)
+        if len(frames) != 4 or len(grids) != 4:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: frames and grids are sequences of four (None = absent)" % what)
+        for t in [cur] + frames:
+            if t is not None and not (t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == (h, w, 3) and _packed_pixels(t)
+                                      and cur is not None and t.stride(0) == cur.stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: colour frames must be uint8 CUDA tensors of shape (%d, %d, 3) with "
+                                      "packed pixels and a common row pitch" % (what, h, w))
+        pitches = {self._check_grid_tensor(t, what, "a grid") for t in grids if t is not None}
+        if len(pitches) > 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: the grids' rows must lie a common number of cells apart" % what)
+        if out is not None and not (out.is_cuda and out.dtype == torch.uint8 and tuple(out.shape) == (h, w, 3) and _packed_pixels(out)):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape (%d, %d, 3) with packed pixels"
+                                  % (what, h, w))
+        if weights is not None and not (weights.is_cuda and weights.dtype in (torch.int16, torch.uint16) and tuple(weights.shape) == (ch, cw)
+                                        and weights.stride(1) == 1):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: weights must be an int16 or uint16 CUDA tensor of shape (%d, %d) with unit "
+                                  "column stride" % (what, ch, cw))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 6
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 6" % what)
+        self._behind_torch(cur, *frames, *grids, out, weights, stats)
+        _capi.check(self._lib.bbme_cells_wide_temporal_filter_bgr_device(
+            self._ctx, _ptr4(frames), _ptr(cur), cur.stride(0) if cur is not None else 0, _ptr4(grids),
+            pitches.pop() if pitches else cw, int(strength), _window(window), _ptr(out), out.stride(0) if out is not None else 0,
+            _ptr(weights), weights.stride(0) if weights is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
+        return out, weights, stats
+
     def frame_bgr_tensor(self, pair=0, which=0):
         """The stored colour frame `which` of `pair` in HBM (bbme_bgr_frames_device_pair) as a (H, W, 3) uint8 torch view; on an
         MFChain slot pair + which.  BbmeError (ERR_STATE) unless both frames of the pair have colour.  Read it only."""
@@ -1851,6 +1891,36 @@ class MFChain(MFBatch):
         _capi.check(self._lib.bbme_wide_temporal_filter_stats(self._ctx, int(strength), self._stats_window(window), s))
         return [dict(zip(WIDE_STAT_KEYS, s[6 * f:6 * f + 6])) for f in range(slots)]
 
+    def temporal_filter_run_wide_bgr(self, strength, first=0, count=None):
+        """temporal_filter_run_wide() in colour (the BGR wide temporal filter rule): the same grids, made on the luma planes, then
+        one filter launch on the stored B,G,R frames -> (count, H, W, 3) uint8, unpadded."""
+        import torch
+        first = int(first)
+        count = self.batch + 1 - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > self.batch + 1:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "temporal_filter_run_wide_bgr: slots %d .. %d of a chain of %d"
+                                  % (first, first + count - 1, self.batch + 1))
+        frames = torch.empty((count,) + self._out_shape(True), dtype=torch.uint8, device="cuda:%d" % self.device)
+        self._behind_torch(frames)
+        _capi.check(self._lib.bbme_wide_temporal_filter_bgr_chain_device(self._ctx, first, count, int(strength), _ptr(frames),
+                                                                         frames.stride(1), frames.stride(0), None))
+        self.synchronize()
+        return frames.cpu().numpy()
+
+    def get_frame_filtered_wide_bgr(self, f, strength, out=None):
+        """Slot f alone as temporal_filter_run_wide_bgr filters it -> the (H, W, 3) uint8 frame."""
+        out = _host_out(out, self._out_shape(True), np.uint8, "get_frame_filtered_wide_bgr")
+        _capi.check(self._lib.bbme_get_wide_temporal_filtered_bgr_host(self._ctx, int(f), int(strength), out.ctypes.data))
+        return out
+
+    def temporal_filter_wide_bgr_stats(self, strength, window=None):
+        """temporal_filter_wide_stats() of the colour filter: one dict per slot of the chain over `window` in cells, from one
+        filter launch; change is summed over three channels."""
+        slots = self.batch + 1
+        s = (C.c_ulonglong * (6 * slots))()
+        _capi.check(self._lib.bbme_wide_temporal_filter_bgr_stats(self._ctx, int(strength), self._stats_window(window), s))
+        return [dict(zip(WIDE_STAT_KEYS, s[6 * f:6 * f + 6])) for f in range(slots)]
+
     def get_slot_plane(self, level, slot):
         """The padded plane of frame slot `slot` at `level` (bbme_get_chain_plane_host) -> (level height, level width) uint8."""
         w, h, _, _ = self.level_geometry(level)
@@ -2260,6 +2330,38 @@ def temporal_filter_cells_wide(cur, planes, grids, strength=64, window=None):
     s = (C.c_ulonglong * 6)()
     _capi.check(_capi.lib().bbme_wide_temporal_filter_host(_ptr4(planes), cur.ctypes.data, w, h, _ptr4(grids), pitch, int(strength),
                                                            _window(window), out.ctypes.data, wmap.ctypes.data, s))
+    return out, wmap, dict(zip(WIDE_STAT_KEYS, list(s)))
+
+
+def temporal_filter_cells_wide_bgr(cur, frames, grids, strength=64, pad_x=0, pad_y=0, window=None):
+    """The BGR wide temporal filter rule of include/bbme.h on the CPU (bbme_wide_temporal_filter_bgr_host): cur a uint8 (H, W, 3)
+    colour frame, read as if zero-padded by (pad_x, pad_y) to an even H0 x W0; frames and grids sequences of four, P1, N1, P2, N2,
+    None = absent: uint8 (H, W, 3) frames and int16 (H0 / 2, W0 / 2, 2) QUARTER-PEL grids on cur (strided row views of one common
+    pitch stay as they are) -> (frame (H, W, 3) uint8, weights (H0 / 2, W0 / 2) uint16 holding w_k << 4 k, dict(prev1_cells,
+    next1_cells, prev2_cells, next2_cells, weight, change) over window (cx0, cy0, cw, ch) in cells, None = all cells)."""
+    what = "temporal_filter_cells_wide_bgr"
+    cur = np.ascontiguousarray(cur, np.uint8)
+    frames, grids = list(frames), list(grids)
+    if cur.ndim != 3 or cur.shape[2] != 3 or len(frames) != 4 or len(grids) != 4:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: a uint8 (H, W, 3) frame, four frames and four grids (None = absent)" % what)
+    h, w = cur.shape[:2]
+    pad_x, pad_y = int(pad_x), int(pad_y)
+    frames = [None if p is None else np.ascontiguousarray(p, np.uint8) for p in frames]
+    if any(p is not None and p.shape != cur.shape for p in frames):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: uint8 frames of one shape (H, W, 3)" % what)
+    if pad_x < 0 or pad_y < 0 or (w + 2 * pad_x) % 2 or (h + 2 * pad_y) % 2:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "%s: paddings (%d, %d) do not give an even padded view" % (what, pad_x, pad_y))
+    ch, cw = (h + 2 * pad_y) // 2, (w + 2 * pad_x) // 2
+    rows = [None if g is None else _grid_rows(g, (ch, cw, 2), what) for g in grids]
+    if len({r[1] for r in rows if r is not None}) > 1:                 # no common pitch: packed copies have one
+        rows = [None if r is None else (np.ascontiguousarray(r[0]), cw) for r in rows]
+    grids = [None if r is None else r[0] for r in rows]
+    pitch = next((r[1] for r in rows if r is not None), cw)
+    out = np.empty(cur.shape, np.uint8)
+    wmap = np.empty((ch, cw), np.uint16)
+    s = (C.c_ulonglong * 6)()
+    _capi.check(_capi.lib().bbme_wide_temporal_filter_bgr_host(_ptr4(frames), cur.ctypes.data, w, h, pad_x, pad_y, _ptr4(grids), pitch,
+                                                               int(strength), _window(window), out.ctypes.data, wmap.ctypes.data, s))
     return out, wmap, dict(zip(WIDE_STAT_KEYS, list(s)))
 
 

@@ -514,7 +514,7 @@ def denoise_frames(frames, search_size, block_size, strength, device=None, in_fl
     return out
 
 
-def denoise_frames_wide(frames, search_size, block_size, strength, device=None, window=8):
+def denoise_frames_wide(frames, search_size, block_size, strength, device=None, window=8, bgr=False):
     """Motion-compensated temporal denoising of a grey video on ONE GPU over TWO frames on each side (the wide temporal filter rule
     of include/bbme.h): every frame averaged with up to four motion-aligned neighbours, along quarter-pel vectors, wherever their
     2x2 cells match better than `strength` -> len(frames) unpadded uint8 (H, W) frames.  The video is cut into runs of `window`
@@ -524,9 +524,14 @@ def denoise_frames_wide(frames, search_size, block_size, strength, device=None, 
     included, and a run needs nothing from another.  The price: the four pairs of a run that lie outside its own frames -- (a - 2,
     a - 1), (a - 1, a), (a + window - 1, a + window) and (a + window, a + window + 1) -- are estimated by the neighbouring run
     as well, so a video of many runs costs window + 3 pair estimates per window frames.  Runs of one length share a context.
-    A colour video is BbmeError (ERR_UNSUPPORTED): the rule is grey.  denoise_frames is the filter over one frame on each side."""
+    Without bgr a colour video is BbmeError (ERR_UNSUPPORTED): the rule is grey.  bgr=True takes a colour video only, (H, W, 3)
+    frames in B,G,R order (grey frames are a ValueError), and follows the same run plan with the BGR wide temporal filter rule:
+    the chains are fed the colour frames, estimate and refine on their luma planes, and one MFChain.temporal_filter_run_wide_bgr
+    per run filters the stored colour -> (H, W, 3) frames.  denoise_frames is the filter over one frame on each side."""
     frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
-    if frames and frames[0].ndim == 3:
+    if bgr and frames and frames[0].ndim != 3:
+        raise ValueError("denoise_frames_wide: bgr=True needs a colour video, (H, W, 3) frames in B,G,R order")
+    if not bgr and frames and frames[0].ndim == 3:
         raise _capi.BbmeError(_capi.ERR_UNSUPPORTED, "denoise_frames_wide: a colour video: the wide temporal filter rule is grey")
     window = int(window)
     if window < 1:
@@ -551,6 +556,10 @@ def denoise_frames_wide(frames, search_size, block_size, strength, device=None, 
                 mf.set_frame_run(0, run)
             mf.estimate_bidirectional_async()
             h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
+            if bgr:                                        # the colour call writes the unpadded frame
+                for q, frame in enumerate(mf.temporal_filter_run_wide_bgr(int(strength), a - lo, b - a)):
+                    out[a + q] = np.ascontiguousarray(frame)
+                continue
             for q, plane in enumerate(mf.temporal_filter_run_wide(int(strength), a - lo, b - a)):
                 out[a + q] = np.ascontiguousarray(plane[py:py + h, px:px + w])
     finally:

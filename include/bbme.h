@@ -1149,6 +1149,65 @@ int bbme_wide_temporal_filter_chain_device(bbme_ctx *ctx, int first, int count, 
 int bbme_get_wide_temporal_filtered_host(bbme_ctx *ctx, int slot, int thr, uint8_t *out);
 int bbme_wide_temporal_filter_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
 
+/* BGR WIDE TEMPORAL FILTER RULE (this project's own): the WIDE TEMPORAL FILTER RULE with each neighbour taken as the BGR SUBPEL
+ * TEMPORAL FILTER RULE takes it.  Inputs: the W x H B,G,R frame C; the paddings pad_x, pad_y >= 0 with W0 = W + 2 pad_x and
+ * H0 = H + 2 pad_y both even; up to four neighbours k = 0 .. 3 = P1, N1, P2, N2, each a colour frame X_k (one common pitch) and a
+ * quarter-pel grid Q_k on C into X_k (CH x CW int16 pairs, rows q4_pitch_cells pairs apart, one pitch for all; any int16); a
+ * strength thr, 1 <= thr <= 1021.  A neighbour is present when both its frame and its grid are given; at least one must be.
+ * Per neighbour, each independent of the others, exactly the BGR SUBPEL TEMPORAL FILTER RULE's: the validity of s = o + (q >> 2)
+ * with f = q & 3 on the padded view; the per-channel bilinear samples X'_k[j, i][c] with the single rounding (... + 8) >> 4, a tap
+ * outside the frame 0 in every channel and a tap of weight 0 never read; cost = max(cost_B, cost_G, cost_R) on the ROUNDED samples;
+ * w_k = 8 (thr - cost) / thr when the neighbour is valid and cost < thr, else 0.
+ * With S = 8 + sum of w_k (8..40), every channel of every pixel of the cell is
+ *   out[o + (j, i)] = (8 C[o + (j, i)] + sum over k of w_k X'_k[j, i] + S / 2) / S         the numerator is at most 10220.
+ * The output is the UNPADDED W x H frame: cells that straddle the frame's edge write only their pixels inside the frame.  The
+ * weight map is the WIDE rule's, one uint16 per cell of the padded view, w_0 | w_1 << 4 | w_2 << 8 | w_3 << 12.  Six statistics
+ * over a window in cells: cells with w_k > 0 for k = 0 .. 3, the sum of all weights, the sum of |out - C| over three channels on
+ * the padded view.
+ * Properties.  (1) On frames with B = G = R every channel is the unpadded window of the WIDE TEMPORAL FILTER RULE's result on the
+ * zero-padded plane; the map and statistics 0 .. 4 are equal and the sixth is three times the grey one.  (2) With neighbours 2 and
+ * 3 absent the frame, the low byte of the map and statistics 0, 1, 4, 5 are the BGR SUBPEL TEMPORAL FILTER RULE's, bit for bit;
+ * with 4 x integer grids therefore the BGR TEMPORAL FILTER RULE's.  (3) Equal frames and zero grids leave the frame unchanged,
+ * every present weight 8.  (4) Exchanging two neighbours' (frame, grid) exchanges their nibbles and their counters and nothing
+ * else.  (5) Any int16 is legal: s is computed in 32 bits, and no byte outside the frames is ever read.
+ * WHAT IT BUYS.  PSNR gain in dB of the filtered middle frame of five over the noisy one, worst channel, interior only, one
+ * independent texture per channel, true quarter-pel grids, over two sizes and three noise levels
+ * (tests/test_wide_temporal_filter_bgr_cpu.py holds these and the floors 1.0 / 1.0 dB, for the tiles 0.6 / 0.4 dB):
+ *     motion per frame (quarter pels)       two-sided +-1    two-sided +-2    one-sided +1     one-sided +1, +2
+ *     (4, 0), (8, -8)                       +4.28..+4.51     +6.40..+6.79     +2.61..+2.83     +4.28..+4.60
+ *     (2, 2), (6, -2), (10, 6), (14, -10)   +5.24..+6.68     +7.10..+8.12     +3.59..+4.20     +5.02..+5.59
+ *     (1, 3), (5, -7)                       +5.29..+6.21     +6.87..+9.30     +3.44..+3.87     +5.30..+6.40
+ *     2x2 tiles of four motions             +4.94..+6.34     +6.67..+7.43     +3.01..+3.88     +4.01..+4.76
+ * On a CHAIN context with its own fields the grids are those the WIDE TEMPORAL FILTER RULE's context calls use -- the +-1 grids of
+ * the subpel temporal filter, the +-2 grids composed, all refined by the SUBPEL RULE (K10) on the LUMA planes into the buffers the
+ * grey wide calls use -- and ONE filter launch then reads only the stored colour (the COLOUR STORE above).
+ * Errors: the union of the wide calls' and the BGR subpel calls'.  BBME_ERR_INVALID for a null context or required pointer,
+ * bgr_pitch or out_pitch < 3 W, an out_stride below one frame when count > 1, q4_pitch_cells or weights_pitch < CW, a neighbour
+ * with only one of frame and grid, no neighbour, thr outside 1..1021, a bad window, an output that overlaps an input frame, slots
+ * outside the chain; BBME_ERR_UNSUPPORTED for the three context-level calls off a chain or beyond W0 or H0 8188; BBME_ERR_STATE
+ * for those without frames and a valid bidirectional estimate, or when a slot the call reads has no stored colour.  None of these
+ * calls changes context state; the statistics scratch is their own, the quarter-pel buffers are those of the grey wide calls.
+ * bbme_wide_temporal_filter_bgr_host: the rule on the CPU, no GPU; packed frames of 3 W bytes a row; frames[k] / grids[k] NULL =
+ * absent; out (packed), weights (packed, CW per row) and stats6 each may be NULL, not all three.
+ * bbme_cells_wide_temporal_filter_bgr_device: ANY colour frames in HBM with one common pitch bgr_pitch >= 3 W and ANY grids of the
+ * context's cell geometry; d_out rows out_pitch bytes apart, d_weights rows weights_pitch uint16 apart; d_out, d_weights,
+ * d_stats6 each optional, not all three; on hip_stream (NULL = the context's), ordered behind the context's stream; no host wait.
+ * bbme_wide_temporal_filter_bgr_chain_device: the composition and refinement launches of the grey chain call, then ONE filter
+ * launch for slots first .. first + count - 1, frame q at d_out + q out_stride.
+ * bbme_get_wide_temporal_filtered_bgr_host: one slot as the chain call; synchronises; packed rows of 3 W bytes.
+ * bbme_wide_temporal_filter_bgr_stats: EVERY slot of the chain from one filter launch, stats[6 f + k]; synchronises. */
+int bbme_wide_temporal_filter_bgr_host(const uint8_t *const frames[4], const uint8_t *cur, int width, int height, int pad_x, int pad_y,
+                                       const int16_t *const grids[4], int q4_pitch_cells, int thr, const int *window, uint8_t *out,
+                                       uint16_t *weights, unsigned long long *stats6);
+int bbme_cells_wide_temporal_filter_bgr_device(bbme_ctx *ctx, const uint8_t *const d_frames[4], const uint8_t *d_cur, int bgr_pitch,
+                                               const int16_t *const d_grids[4], int q4_pitch_cells, int thr, const int *window,
+                                               uint8_t *d_out, int out_pitch, uint16_t *d_weights, int weights_pitch,
+                                               unsigned long long *d_stats6, void *hip_stream);
+int bbme_wide_temporal_filter_bgr_chain_device(bbme_ctx *ctx, int first, int count, int thr, uint8_t *d_out, int out_pitch,
+                                               size_t out_stride, void *hip_stream);
+int bbme_get_wide_temporal_filtered_bgr_host(bbme_ctx *ctx, int slot, int thr, uint8_t *out);
+int bbme_wide_temporal_filter_bgr_stats(bbme_ctx *ctx, int thr, const int *window, unsigned long long *stats);
+
 /* GLOBAL MOTION RULE (this project's own; the reference has no parametric motion): the dominant motion of a cell grid as a
  * translation or an affine model, and the cells that follow it.  Inputs: a grid Q of CH x CW int16 (dx, dy), CH = H0 / 2,
  * CW = W0 / 2, in GRID UNITS of 1 / unit pixel (unit = 1: integer cells; unit = 4: quarter-pel cells "4 v + q"); optionally an
