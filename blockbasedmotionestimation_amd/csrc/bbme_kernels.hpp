@@ -896,7 +896,19 @@ __device__ __forceinline__ void shift_pair(RegArgs &a, uint32_t p)
 // scalar-base form of a global access, 24-bit multiplies); given a RegArgs they are, instruction for instruction, what they were.
 // (The memo needs no such form: memo_load / memo_store go through a buffer descriptor, whose offsets are 32-bit already.)
 struct SolverArgs : RegArgs {};
-template <class A> constexpr bool kOffsets32 = std::is_same<A, SolverArgs>::value;
+// Pass 1's copy (pass1_hot_args): the same promise, and the fields pass 1 reads -- the pair's shift is applied to those alone.
+// It reaches further than the solver's: eval_block, score_block and mark_dependants, which the solver's throughput rounds
+// call as they always did, take the 32-bit form for a Pass1Args only (kPass1Args).
+struct Pass1Args : RegArgs {};
+template <class A> constexpr bool kPass1Args = std::is_same<A, Pass1Args>::value;
+template <class A> constexpr bool kOffsets32 = std::is_same<A, SolverArgs>::value || kPass1Args<A>;
+// element at a 32-bit byte offset from a (scalar) 64-bit base: the scalar-base form of a global access
+template <class T>
+__device__ __forceinline__ T *at32(T *base, uint32_t bytes)
+{
+    using byte_t = typename std::conditional<std::is_const<T>::value, const char, char>::type;
+    return reinterpret_cast<T *>(reinterpret_cast<byte_t *>(base) + bytes);
+}
 
 template <int BS> struct RegCfg {
     static constexpr int LPB = BS >= 4 ? (BS > 64 ? 64 : BS) : 1;   // lanes per block
@@ -924,8 +936,8 @@ __device__ __forceinline__ mv_t load_est(const mv_t *p)
 // that exist in the grid.  Every image row of every candidate is loaded in ONE memory trip: loads are
 // unconditional -- out-of-image candidates read a clamped, harmless address and are masked afterwards
 // -- because a load inside a divergent `if` costs its own round trip.
-template <int BS, bool DEDUP = false>
-__device__ __forceinline__ mv_t score_block(const RegArgs &a, const mv_t (&cand)[9], uint32_t present,
+template <int BS, bool DEDUP = false, class A = RegArgs>
+__device__ __forceinline__ mv_t score_block(const A &a, const mv_t (&cand)[9], uint32_t present,
                                             int bx, int by, int sub)
 {
 #pragma clang fp contract(off)
@@ -942,7 +954,10 @@ __device__ __forceinline__ mv_t score_block(const RegArgs &a, const mv_t (&cand)
     row_t win[9][RPL];
 #pragma unroll
     for (int i = 0; i < RPL; ++i)
-        cur[i] = *reinterpret_cast<const row_t *>(a.image1 + (size_t)(by + sub + i * LPB) * a.width + bx);
+        if constexpr (kPass1Args<A>)   // (rows and widths below 2^23, planes below 4 GiB: see Pass1Args)
+            cur[i] = *reinterpret_cast<const row_t *>(at32(a.image1, __umul24((uint32_t)(by + sub + i * LPB), (uint32_t)a.width) + (uint32_t)bx));
+        else
+            cur[i] = *reinterpret_cast<const row_t *>(a.image1 + (size_t)(by + sub + i * LPB) * a.width + bx);
     // DEDUP (throughput kernels): neighbouring blocks mostly carry the same MV, so a candidate whose
     // MV already occurred earlier in the list re-uses that candidate's SAD instead of gathering the same
     // image rows again.  first[k] = index of the first present candidate with the same MV.
@@ -965,8 +980,12 @@ __device__ __forceinline__ mv_t score_block(const RegArgs &a, const mv_t (&cand)
         else { x2 = bx; y2 = by; }                          // harmless address; result is discarded
         if (!DEDUP || first[k] == k) {
 #pragma unroll
-            for (int i = 0; i < RPL; ++i)
-                win[k][i] = *reinterpret_cast<const row_t *>(a.image2 + (size_t)(y2 + sub + i * LPB) * a.width + x2);
+            for (int i = 0; i < RPL; ++i) {
+                if constexpr (kPass1Args<A>)   // (x2, y2 lie inside the image here)
+                    win[k][i] = *reinterpret_cast<const row_t *>(at32(a.image2, __umul24((uint32_t)(y2 + sub + i * LPB), (uint32_t)a.width) + (uint32_t)x2));
+                else
+                    win[k][i] = *reinterpret_cast<const row_t *>(a.image2 + (size_t)(y2 + sub + i * LPB) * a.width + x2);
+            }
         } else {                                            // duplicate: loads skipped under the exec mask
 #pragma unroll
             for (int i = 0; i < RPL; ++i)
@@ -1047,9 +1066,9 @@ __device__ __forceinline__ mv_t score_block(const RegArgs &a, const mv_t (&cand)
 }
 
 // Evaluate block (r, c) with its candidates read from global memory (one trip for all nine):
-// use_new = bit mask of the candidates read from `est` instead of `old_grid`.
-template <int BS, bool COHERENT, bool DEDUP = false>
-__device__ __forceinline__ mv_t eval_block(const RegArgs &a, int r, int c, int sub, uint32_t use_new)
+// use_new = bit mask of the candidates read from `est` instead of `old_grid`.  `own`, if given, takes candidate 0 as it was loaded.
+template <int BS, bool COHERENT, bool DEDUP = false, class A = RegArgs>
+__device__ __forceinline__ mv_t eval_block(const A &a, int r, int c, int sub, uint32_t use_new, mv_t *own = nullptr)
 {
     mv_t cand[9];
     uint32_t present = 0;
@@ -1058,11 +1077,19 @@ __device__ __forceinline__ mv_t eval_block(const RegArgs &a, int r, int c, int s
         const int rr = r + kNbRow[k], cc = c + kNbCol[k];
         if (rr >= 0 && rr < a.rows && cc >= 0 && cc < a.cols) present |= 1u << k;
         const int rs = min(max(rr, 0), a.rows - 1), cs = min(max(cc, 0), a.cols - 1);
-        if ((use_new >> k) & 1u)
-            cand[k] = load_est<COHERENT>(a.est + (size_t)rs * a.cols + cs);
-        else
-            cand[k] = a.old_grid[(size_t)(rs >> a.old_shift) * a.old_cols + (cs >> a.old_shift)];
+        if constexpr (kPass1Args<A>) {
+            if ((use_new >> k) & 1u)
+                cand[k] = load_est<COHERENT>(at32(a.est, (__umul24((uint32_t)rs, (uint32_t)a.cols) + (uint32_t)cs) << 2));
+            else
+                cand[k] = *at32(a.old_grid, (__umul24((uint32_t)(rs >> a.old_shift), (uint32_t)a.old_cols) + (uint32_t)(cs >> a.old_shift)) << 2);
+        } else {
+            if ((use_new >> k) & 1u)
+                cand[k] = load_est<COHERENT>(a.est + (size_t)rs * a.cols + cs);
+            else
+                cand[k] = a.old_grid[(size_t)(rs >> a.old_shift) * a.old_cols + (cs >> a.old_shift)];
+        }
     }
+    if (own) *own = cand[0];
     // All candidates equal (the common case inside a moving region): they have the same SAD and the same smoothness
     // (or all lie outside the image: FLT_MAX), so the first one -- the block's own old MV -- stays (:648-660).
     // No image row is touched; whole waves leave here where the field is locally constant.
@@ -1150,6 +1177,20 @@ __device__ __forceinline__ LaneCand lanes_candidate(const RegArgs &a, int r, int
     // already-updated inputs come from `est`, the others from `old_grid`, all through the coherent path
     lc.src = ((use_new >> k) & 1u) ? a.est + (size_t)rs * a.cols + cs
                                    : a.old_grid + (size_t)(rs >> a.old_shift) * a.old_cols + (cs >> a.old_shift);
+    return lc;
+}
+
+// pass 1's form: every candidate comes from the old grid (use_new = 0), at a 32-bit byte offset from its base
+__device__ __forceinline__ LaneCand lanes_candidate(const Pass1Args &a, int r, int c, int k16, uint32_t)
+{
+    constexpr uint32_t kRowCode = 1u | 1u << 2 | 1u << 4 | 2u << 6 | 0u << 8 | 0u << 10 | 0u << 12 | 2u << 14 | 2u << 16;
+    constexpr uint32_t kColCode = 1u | 0u << 2 | 2u << 4 | 2u << 6 | 0u << 8 | 2u << 10 | 1u << 12 | 1u << 14 | 0u << 16;
+    const int k = k16 < 9 ? k16 : 0;
+    const int rr = r + (int)((kRowCode >> (2 * k)) & 3u) - 1, cc = c + (int)((kColCode >> (2 * k)) & 3u) - 1;
+    LaneCand lc;
+    lc.present = k16 < 9 && (uint32_t)rr < (uint32_t)a.rows && (uint32_t)cc < (uint32_t)a.cols;
+    const int rs = min(max(rr, 0), a.rows - 1), cs = min(max(cc, 0), a.cols - 1);
+    lc.src = at32(a.old_grid, (__umul24((uint32_t)(rs >> a.old_shift), (uint32_t)a.old_cols) + (uint32_t)(cs >> a.old_shift)) << 2);
     return lc;
 }
 
@@ -1428,7 +1469,8 @@ __device__ __forceinline__ mv_t lanes_score(const A &a, int r, int c, int k16, b
 
 template <int BS, bool COHERENT, bool MEMO = false, class A>
 __device__ __forceinline__ mv_t eval_block_lanes(const A &a, int r, int c, int k16, uint32_t use_new,
-                                                 PhaseProf *prof = nullptr, const LaneGeom *lg = nullptr, MemoStats *stats = nullptr)
+                                                 PhaseProf *prof = nullptr, const LaneGeom *lg = nullptr, MemoStats *stats = nullptr,
+                                                 mv_t *own_out = nullptr)
 {
     const LaneCand lc = lg ? lanes_candidate(a, *lg, r, c) : lanes_candidate(a, r, c, k16, use_new);
     uint32_t slot = 0;                                        // the lane's memo word (index into RegArgs::memo)
@@ -1443,6 +1485,7 @@ __device__ __forceinline__ mv_t eval_block_lanes(const A &a, int r, int c, int k
     // every block of the round has nine equal candidates (behind a flood that has passed): equal SADs, equal smoothness, the
     // first one -- the block's own MV -- stays (:648-660), as in eval_block; no image row is touched
     const mv_t own = dpp_row<0x150>(mv);
+    if (own_out) *own_out = own;                              // candidate 0 as the group's first lane loaded it
     if (!__ballot(lc.present && mv != own)) {
         if constexpr (MEMO) {
             if (a.memo_init && k16 < 9) memo_store(a, slot, kMemoNoMv, 0u);   // nothing known yet
@@ -1492,29 +1535,75 @@ __device__ __forceinline__ uint32_t own_release(const A &a, uint32_t x)  // retu
 #define BBME_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
 
 // block (r, c) has a new estimate: its dependants R, DR, D, DL must be looked at again (idempotent byte stores)
-__device__ __forceinline__ void mark_dependants(const RegArgs &a, uint8_t *flags, int r, int c)
+template <class A>
+__device__ __forceinline__ void mark_dependants(const A &a, uint8_t *flags, int r, int c)
 {
     const int dr[4] = {0, 1, 1, 1}, dc[4] = {1, 1, 0, -1};
 #pragma unroll
     for (int d = 0; d < 4; ++d) {
         const int rr = r + dr[d], cc = c + dc[d];
-        if (rr < a.rows && cc >= 0 && cc < a.cols) flags[(size_t)rr * a.cols + cc] = 1;
+        if (rr < a.rows && cc >= 0 && cc < a.cols) {
+            if constexpr (kPass1Args<A>) *at32(flags, __umul24((uint32_t)rr, (uint32_t)a.cols) + (uint32_t)cc) = 1;
+            else flags[(size_t)rr * a.cols + cc] = 1;
+        }
     }
 }
 
+// PASS 1'S HEAD (the three kernels below).  A pass-1 launch on a small grid lasts as long as one wave's way to its first and
+// last memory trip, and one on a large grid of small blocks as long as 32 waves a SIMD take to issue theirs, so what stands in front
+// of the candidates' load is the launch.  Hence: thread, block, row and column in 32 bits (the context promises every dimension
+// below 2^23 and every per-pair buffer below 4 GiB, see Pass1Args; the block index is formed per group, blockIdx.x * groups + group, and
+// stays below blocks + 256), one unsigned 32-bit division by `cols`; every grid, flag and image access at a 32-bit byte offset from
+// the pair's base; the pair's shift on the pointers pass 1 reads and no others; what the straight path reads asked for in one
+// group of scalar loads at entry (pass1_pin: it pins the VALUES -- the kernel-argument pointer stays the compiler's); the counters
+// zeroed behind the evaluation, not in front of it; and the block's old value taken from the candidates' trip, where it is
+// candidate 0, instead of from a load of its own behind the estimate's store.
+__device__ __forceinline__ Pass1Args pass1_hot_args(const RegArgs &k, uint32_t p)
+{
+    Pass1Args a{};
+    a.image1 = k.image1 + (size_t)p * k.s_plane; a.image2 = k.image2 + (size_t)p * k.s_plane;
+    a.width = k.width; a.height = k.height; a.rows = k.rows; a.cols = k.cols;
+    a.old_grid = k.old_grid + (size_t)p * k.s_old; a.old_shift = k.old_shift; a.old_cols = k.old_cols;
+    a.est = k.est + (size_t)p * k.s_est;
+    a.lambda_mult = k.lambda_mult;
+    // (the strides are read whether or not the pointer is null: a load under the test would be a second wait)
+    uint8_t *const flag_next = k.flag_next + (size_t)p * k.s_flag;
+    a.flag_next = k.flag_next ? flag_next : nullptr;                              // no map: the Jacobi fast mode
+    unsigned long long *const memo = k.memo + (size_t)p * k.s_memo;
+    a.memo = k.memo ? memo : nullptr; a.memo_init = k.memo_init;
+    a.lazy = k.lazy;
+    return a;
+}
+// everything the straight path reads is in scalar registers from here on: the loads stand together at the kernel's entry.
+// (Not in the strip form: it lives at the SGPR limit, the pinned values were spilled at once and its first load moved back;
+// without the pin the compiler groups its loads by itself.)
+template <bool MEMO = false>
+__device__ __forceinline__ void pass1_pin(const Pass1Args &a)
+{
+    asm volatile("" :: "s"(a.image1), "s"(a.image2), "s"(a.width), "s"(a.height), "s"(a.rows), "s"(a.cols), "s"(a.old_grid),
+                 "s"(a.old_shift), "s"(a.old_cols), "s"(a.est), "s"(a.lambda_mult), "s"(a.flag_next));
+    if constexpr (MEMO) asm volatile("" :: "s"(a.memo), "s"(a.memo_init));
+}
+// the solver's counters (nothing else touches them before this sweep's solver launch): the launch's first 16 threads, [5] stays
+__device__ __forceinline__ void pass1_zero_counters(const RegArgs &k)
+{
+    if (blockIdx.x == 0 && threadIdx.x < 16 && threadIdx.x != 5) k.counters[(size_t)blockIdx.y * 64u + threadIdx.x] = 0;
+}
+
 template <int BS>
-__global__ __launch_bounds__(256) void k_reg_pass1(RegArgs a)
+__global__ __launch_bounds__(256) void k_reg_pass1(const RegArgs args)
 {
     constexpr int LPB = RegCfg<BS>::LPB;
     __builtin_amdgcn_s_setprio(2);                 // latency-bound: ahead of a speculative search sharing the SIMD
-    shift_pair(a, blockIdx.y);
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    // the solver's counters (nothing else touches them before this sweep's solver launch)
-    if (t < 16 && t != 5) a.counters[t] = 0;
-    const long long g = t / LPB;
-    const int sub = (int)(t % LPB);
-    if (g >= (long long)a.rows * a.cols) return;   // whole groups drop out together (LPB | 256)
-    const int r = (int)(g / a.cols), c = (int)(g % a.cols);
+    const Pass1Args a = pass1_hot_args(args, blockIdx.y);
+    pass1_pin(a);
+    const uint32_t g = blockIdx.x * (256u / LPB) + threadIdx.x / LPB;
+    const int sub = (int)(threadIdx.x % LPB);
+    if (g >= (uint32_t)a.rows * (uint32_t)a.cols) {  // whole groups drop out together (LPB | 256)
+        pass1_zero_counters(args);                 // (a grid of fewer than 16 blocks)
+        return;
+    }
+    const int r = (int)(g / (uint32_t)a.cols), c = (int)(g - (uint32_t)r * (uint32_t)a.cols);
     mv_t res, old;
     if (r >= 1 && r + 1 < a.rows && c >= 1 && c + 1 < a.cols) {
         // away from the border all nine candidates exist and come from the old grid: three 12-byte loads (or, when the old
@@ -1522,17 +1611,18 @@ __global__ __launch_bounds__(256) void k_reg_pass1(RegArgs a)
         mv_t cand[9];
         if (a.old_shift == 0) {
             struct __attribute__((packed, aligned(1))) tri_t { uint32_t v[3]; };
-            const mv_t *p = a.old_grid + (size_t)(r - 1) * a.old_cols + (c - 1);
+            const uint32_t pitch = (uint32_t)a.old_cols << 2, o = (__umul24((uint32_t)(r - 1), (uint32_t)a.old_cols) + (uint32_t)(c - 1)) << 2;
             tri_t row[3];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) row[i] = *reinterpret_cast<const tri_t *>(p + (size_t)i * a.old_cols);
+            for (int i = 0; i < 3; ++i) row[i] = *reinterpret_cast<const tri_t *>(at32(a.old_grid, o + (uint32_t)i * pitch));
 #pragma unroll
             for (int k = 0; k < 9; ++k) cand[k] = row[1 + kNbRow[k]].v[1 + kNbCol[k]];
         } else {
             struct __attribute__((packed, aligned(1))) duo_t { uint32_t v[2]; };
             const int pr0 = (r - 1) >> 1, pc0 = (c - 1) >> 1;                // (r + 1) >> 1 == pr0 + 1, (c + 1) >> 1 == pc0 + 1
-            const mv_t *p = a.old_grid + (size_t)pr0 * a.old_cols + pc0;
-            const duo_t w0 = *reinterpret_cast<const duo_t *>(p), w1 = *reinterpret_cast<const duo_t *>(p + a.old_cols);
+            const uint32_t o = (__umul24((uint32_t)pr0, (uint32_t)a.old_cols) + (uint32_t)pc0) << 2;
+            const duo_t w0 = *reinterpret_cast<const duo_t *>(at32(a.old_grid, o));
+            const duo_t w1 = *reinterpret_cast<const duo_t *>(at32(a.old_grid, o + ((uint32_t)a.old_cols << 2)));
             const int ro = r & 1, co = c & 1;                                 // odd row: rows r-1, r in parent row pr0, r+1 in pr0 + 1
 #pragma unroll
             for (int k = 0; k < 9; ++k) {
@@ -1549,14 +1639,14 @@ __global__ __launch_bounds__(256) void k_reg_pass1(RegArgs a)
         for (int k = 1; k < 9; ++k) uniform &= cand[k] == cand[0];
         res = uniform ? cand[0] : score_block<BS, true>(a, cand, 0x1ffu, c * BS, r * BS, sub);
     } else {
-        res = eval_block<BS, false, true>(a, r, c, sub, 0u);
-        old = a.old_grid[(size_t)(r >> a.old_shift) * a.old_cols + (c >> a.old_shift)];
+        res = eval_block<BS, false, true>(a, r, c, sub, 0u, &old);            // (candidate 0 is the block's old value)
     }
     if (sub == 0) {
-        a.est[g] = res;
+        *at32(a.est, g << 2) = res;
         // the blocks that read this one as an already-updated input assumed the old value
         if (a.flag_next && res != old) mark_dependants(a, a.flag_next, r, c);     // no map: the Jacobi fast mode stops here
     }
+    pass1_zero_counters(args);
 }
 
 // Pass 1 on the large grids of small blocks (b = 2, 4; hundreds of thousands to millions of blocks), r04.  Measured with the image
@@ -1567,15 +1657,14 @@ __global__ __launch_bounds__(256) void k_reg_pass1(RegArgs a)
 // were found: the wave lists them (ballots, no barrier) and works the list off densely, 64 / LPB blocks per pass -- blocks that need
 // their images come in clusters (motion boundaries), so one dense pass replaces what were several sparse ones.
 template <int BS>
-__global__ __launch_bounds__(256) void k_reg_pass1_strip(RegArgs a)
+__global__ __launch_bounds__(256) void k_reg_pass1_strip(const RegArgs args)
 {
     constexpr int LPB = RegCfg<BS>::LPB;                       // 1 (b = 2) or 4 (b = 4): lanes per block on the image path
     static_assert(BS == 2 || BS == 4, "small blocks");
     __shared__ uint32_t s_list[4][256];                       // per wave: the blocks of its 64 strips that need their images
     __builtin_amdgcn_s_setprio(2);
-    shift_pair(a, blockIdx.y);
+    const Pass1Args a = pass1_hot_args(args, blockIdx.y);
     const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-    if (t < 16 && t != 5) a.counters[t] = 0;                  // as k_reg_pass1
     const int lane = (int)(threadIdx.x & 63u);
     uint32_t *list = s_list[threadIdx.x >> 6];
     const uint32_t spr = (uint32_t)a.cols >> 2;                // strips per row (the host takes this form only when 4 | cols)
@@ -1590,10 +1679,10 @@ __global__ __launch_bounds__(256) void k_reg_pass1_strip(RegArgs a)
         need = 0;
         if (a.old_shift == 0) {
             struct __attribute__((packed, aligned(1))) hex_t { uint32_t v[6]; };
-            const mv_t *p = a.old_grid + (size_t)(r - 1) * a.old_cols + (c0 - 1);
+            const uint32_t pitch = (uint32_t)a.old_cols << 2, o = (__umul24((uint32_t)(r - 1), (uint32_t)a.old_cols) + (uint32_t)(c0 - 1)) << 2;
             hex_t row[3];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) row[i] = *reinterpret_cast<const hex_t *>(p + (size_t)i * a.old_cols);
+            for (int i = 0; i < 3; ++i) row[i] = *reinterpret_cast<const hex_t *>(at32(a.old_grid, o + (uint32_t)i * pitch));
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 own[j] = row[1].v[j + 1];
@@ -1609,8 +1698,9 @@ __global__ __launch_bounds__(256) void k_reg_pass1_strip(RegArgs a)
             // in parent rows (r - 1) >> 1 and that + 1
             struct __attribute__((packed, aligned(1))) quad_t { uint32_t v[4]; };
             const int pr0 = (r - 1) >> 1, pc0 = (c0 >> 1) - 1;
-            const mv_t *p = a.old_grid + (size_t)pr0 * a.old_cols + pc0;
-            const quad_t w0 = *reinterpret_cast<const quad_t *>(p), w1 = *reinterpret_cast<const quad_t *>(p + a.old_cols);
+            const uint32_t o = (__umul24((uint32_t)pr0, (uint32_t)a.old_cols) + (uint32_t)pc0) << 2;
+            const quad_t w0 = *reinterpret_cast<const quad_t *>(at32(a.old_grid, o));
+            const quad_t w1 = *reinterpret_cast<const quad_t *>(at32(a.old_grid, o + ((uint32_t)a.old_cols << 2)));
             const bool mid_hi = !(r & 1);                                     // row r itself: parent row pr0 (r odd) or pr0 + 1 (r even)
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -1629,8 +1719,9 @@ __global__ __launch_bounds__(256) void k_reg_pass1_strip(RegArgs a)
         }
         // nine equal candidates: the block keeps its vector (:648-660); the others get theirs below, this is their old value meanwhile
         struct __attribute__((aligned(16))) out_t { uint32_t v[4]; };
-        *reinterpret_cast<out_t *>(a.est + cell0) = out_t{{own[0], own[1], own[2], own[3]}};
+        *reinterpret_cast<out_t *>(at32(a.est, cell0 << 2)) = out_t{{own[0], own[1], own[2], own[3]}};
     }
+    pass1_zero_counters(args);                                // as k_reg_pass1: behind the strip test
     if (a.lazy) {
         // a relaxation launch follows: it evaluates flagged blocks tile by tile with every lane busy, so the blocks that need their
         // images are handed to it as they are -- old value as the estimate, flag set.  The field the sweep converges to is the same:
@@ -1641,8 +1732,10 @@ __global__ __launch_bounds__(256) void k_reg_pass1_strip(RegArgs a)
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if ((need >> j) & 1u) {
-                    if (!interior) a.est[cell0 + j] = a.old_grid[(size_t)(r >> a.old_shift) * a.old_cols + ((c0 + j) >> a.old_shift)];
-                    a.flag_next[cell0 + j] = 1;
+                    if (!interior)
+                        *at32(a.est, (cell0 + j) << 2) =
+                            *at32(a.old_grid, (__umul24((uint32_t)(r >> a.old_shift), (uint32_t)a.old_cols) + (uint32_t)((c0 + j) >> a.old_shift)) << 2);
+                    *at32(a.flag_next, cell0 + j) = 1;
                 }
         }
         return;
@@ -1664,10 +1757,10 @@ __global__ __launch_bounds__(256) void k_reg_pass1_strip(RegArgs a)
         if (idx < total) {                                     // whole groups
             const uint32_t cell = list[idx];
             const int rr = (int)(cell / (uint32_t)a.cols), cc = (int)(cell - (uint32_t)rr * (uint32_t)a.cols);
-            const mv_t res = eval_block<BS, false, true>(a, rr, cc, sub, 0u);
+            mv_t old;                                          // candidate 0 of the evaluation
+            const mv_t res = eval_block<BS, false, true>(a, rr, cc, sub, 0u, &old);
             if (sub == 0) {
-                const mv_t old = a.old_grid[(size_t)(rr >> a.old_shift) * a.old_cols + (cc >> a.old_shift)];
-                a.est[cell] = res;
+                *at32(a.est, cell << 2) = res;
                 if (a.flag_next && res != old) mark_dependants(a, a.flag_next, rr, cc);
             }
         }
@@ -1684,22 +1777,22 @@ __global__ __launch_bounds__(256) void k_reg_pass1_strip(RegArgs a)
 // Pass 1 in the chain form (16 lanes per block, lane k = candidate k), for grids too small to fill the chip: there the launch
 // lasts as long as one wave's instruction stream does, and the chain form's is a third as long as eval_block's.
 template <int BS, bool MEMO = false>
-__global__ __launch_bounds__(256) void k_reg_pass1_lanes(RegArgs a)
+__global__ __launch_bounds__(256) void k_reg_pass1_lanes(const RegArgs args)
 {
     __builtin_amdgcn_s_setprio(2);
-    shift_pair(a, blockIdx.y);
-    const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (t < 16 && t != 5) a.counters[t] = 0;                  // as k_reg_pass1
-    const long long g = t >> 4;
-    const int k16 = (int)(t & 15);
-    if (g >= (long long)a.rows * a.cols) return;              // whole groups drop out together
-    const int r = (int)(g / a.cols), c = (int)(g % a.cols);
-    const mv_t res = eval_block_lanes<BS, false, MEMO>(a, r, c, k16, 0u);
+    const Pass1Args a = pass1_hot_args(args, blockIdx.y);
+    pass1_pin<MEMO>(a);
+    const uint32_t g = blockIdx.x * 16u + (threadIdx.x >> 4);
+    const int k16 = (int)(threadIdx.x & 15u);
+    if (g >= (uint32_t)a.rows * (uint32_t)a.cols) return;     // whole groups drop out together (never the launch's first: it zeroes the counters)
+    const int r = (int)(g / (uint32_t)a.cols), c = (int)(g - (uint32_t)r * (uint32_t)a.cols);
+    mv_t old;                                                  // candidate 0 as the group's first lane loaded it
+    const mv_t res = eval_block_lanes<BS, false, MEMO>(a, r, c, k16, 0u, nullptr, nullptr, nullptr, &old);
     if (k16 == 0) {
-        a.est[g] = res;
-        const mv_t old = a.old_grid[(size_t)(r >> a.old_shift) * a.old_cols + (c >> a.old_shift)];
+        *at32(a.est, g << 2) = res;
         if (a.flag_next && res != old) mark_dependants(a, a.flag_next, r, c);
     }
+    pass1_zero_counters(args);                                // as k_reg_pass1
 }
 
 // This is asynchronous fixed-point iteration: any number of rounds or launches, followed by k_reg_solve, ends at
