@@ -12,6 +12,7 @@ from .motion_framework import (MF, MFBatch, MFChain, plan_padding, pad_zero, pyr
                                compose_cells, temporal_filter_cells_wide, temporal_filter_cells_wide_bgr, vector_histogram_cells,
                                global_moments_cells,
                                solve_global_motion, global_motion_cells, global_compensate, global_compensate_bgr,
+                               compensate_cells_bgr,
                                DIR_FORWARD, DIR_BACKWARD, FB_CONSISTENT, FB_INCONSISTENT, FB_OUTSIDE)
 from .rw_flow import Flow, FlowWriter, subsample_div4  # noqa: F401
 from .synth import synth_pair, synth_video, warp_pair_from_flow  # noqa: F401
@@ -23,4 +24,5 @@ __all__ = ["MF", "MFBatch", "MFChain", "Flow", "FlowWriter", "BbmeError", "plan_
            "interpolate_cells_subpel", "interpolate_cells_subpel_bgr", "temporal_filter_cells_subpel",
            "temporal_filter_cells_subpel_bgr", "compose_cells", "temporal_filter_cells_wide", "temporal_filter_cells_wide_bgr",
            "vector_histogram_cells",
-           "global_moments_cells", "solve_global_motion", "global_motion_cells", "global_compensate", "global_compensate_bgr"]
+           "global_moments_cells", "solve_global_motion", "global_motion_cells", "global_compensate", "global_compensate_bgr",
+           "compensate_cells_bgr"]

@@ -243,6 +243,13 @@ SIGNATURES = {
     "bbme_global_compensate_bgr_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "bbme_get_global_compensated_bgr_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "bbme_global_compensation_error_bgr": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_compensate_bgr_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_cells_compensate_bgr_device": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "bbme_compensate_bgr_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "bbme_get_compensated_bgr_host": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "bbme_compensation_error_bgr": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_frame_plane_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _P(C.c_void_p)]),
     "bbme_cells_color_device": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "bbme_flow_color_device": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

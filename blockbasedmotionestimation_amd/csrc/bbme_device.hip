@@ -377,6 +377,8 @@ struct bbme_ctx {
                                                   // bbme_cells_global_compensate_bgr_device (BBME_GC_MAX_FRAMES frames)
     DevBuf<int32_t> gcb_models;                   // the device tables of models, six words per frame: every pair's of the context's own
                                                   // calls (BBME_MAX_BATCH), then a caller's run (BBME_GC_MAX_FRAMES)
+    StatsScratch cb_stats;                        // bbme_compensation_error_bgr (every pair) and bbme_cells_compensate_bgr_device
+                                                  // (one pair)
 };
 
 namespace {
@@ -4481,6 +4483,156 @@ int bbme_global_compensation_error_bgr(bbme_ctx *c, int which, const int32_t *mo
         HIP_TRY(hipMemcpyAsync(c->gcb_models, models, (size_t)6 * c->batch * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         return enqueue_gcb(c, b1, b2, 3 * c->geom.width, c->bgr_stride, c->batch, c->gcb_models, nullptr, unit, 0, window, nullptr, 0, 0,
                            c->gcb_stats.partials_all(), c->gcb_stats.results(), c->stream);
+    });
+}
+
+// ---- motion compensation of the B,G,R frames along a cell grid (the BGR COMPENSATION RULE of include/bbme.h; K11b k_compensate_bgr) ----
+
+static long long cb_groups(const bbme_ctx *c) { return cell_groups(c, kCbRunsPerLane); }
+
+// result words of every pair, partials of a launch over every pair, then those of a caller's launch: one size per context
+static int cb_scratch(bbme_ctx *c)
+{
+    return c->cb_stats.ensure(BBME_MAX_BATCH, cb_groups(c), c->batch, 1, "the colour compensation statistics");
+}
+
+// unit, fill and a window in pixels of the FRAME.  Touches no device.
+static int check_cb(const bbme_ctx *c, int unit, int fill, const int *window, const char *what)
+{
+    if (unit != 1 && unit != 4) return bbme::fail(BBME_ERR_INVALID, "%s: unit %d (1 or 4)", what, unit);
+    if (int rc = check_fill(fill, what)) return rc;
+    if (!window || (window[0] >= 0 && window[1] >= 0 && window[2] >= 1 && window[3] >= 1 &&
+                    (long long)window[0] + window[2] <= c->geom.width && (long long)window[1] + window[3] <= c->geom.height))
+        return BBME_OK;
+    return bbme::fail(BBME_ERR_INVALID, "%s: window (%d, %d, %d, %d) is not inside the %dx%d frame", what, window[0], window[1],
+                      window[2], window[3], c->geom.width, c->geom.height);
+}
+
+// k_compensate_bgr over `pairs` pairs (colour frames frame_stride bytes, grids s_grid words apart): the frame into d_out (one pair
+// only) and / or, with d_stats, the statistics over `window` in frame pixels
+static int enqueue_cb(bbme_ctx *c, const uint8_t *bgr1, const uint8_t *bgr2, int bgr_pitch, size_t frame_stride, const mv_t *grid,
+                      int grid_pitch, size_t s_grid, int pairs, int unit, int fill, const int *window, uint8_t *d_out, int out_pitch,
+                      unsigned long long *partial, unsigned long long *d_stats, hipStream_t stream)
+{
+    const Level &L = c->lv[0];
+    CbArgs a{};
+    a.bgr1 = bgr1; a.bgr2 = bgr2; a.grid = grid; a.out = d_out;
+    a.frame_stride = frame_stride; a.s_grid = s_grid;
+    a.fw = c->geom.width; a.fh = c->geom.height; a.pad_x = c->geom.pad_x; a.pad_y = c->geom.pad_y;
+    a.cw = L.width / 2; a.grid_pitch = grid_pitch; a.bgr_pitch = bgr_pitch; a.out_pitch = out_pitch;
+    a.mul = 4 / unit; a.fill = fill;
+    set_window(a, window, a.fw, a.fh);
+    set_runs(a, L.width / 2, L.height / 2);
+    return launch_gather(k_compensate_bgr<kCbRunsPerLane>, a, cb_groups(c), pairs, 1, partial, d_stats, stream);
+}
+
+int bbme_cells_compensate_bgr_device(bbme_ctx *c, const uint8_t *d_bgr1, const uint8_t *d_bgr2, int bgr_pitch, const int16_t *d_grid,
+                                     int pitch_cells, int unit, int fill, const int *window, uint8_t *d_out, int out_pitch,
+                                     unsigned long long *d_stats4, void *hip_stream)
+{
+    const char *what = "bbme_cells_compensate_bgr_device";
+    if (int rc = check_ctx(c)) return rc;
+    const int fw = c->geom.width, fh = c->geom.height;
+    if (!d_bgr2 || !d_grid || (!d_out && !d_stats4) || (d_stats4 && !d_bgr1)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (int rc = check_cb(c, unit, fill, window, what)) return rc;
+    if (int rc = check_frames(1, bgr_pitch, 0, 3 * fw, fh, what, "colour")) return rc;
+    if (pitch_cells < c->lv[0].width / 2)
+        return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, pitch_cells, c->lv[0].width / 2);
+    if (d_out) if (int rc = check_bgr_frames(c, 1, out_pitch, 0, what)) return rc;
+    if (d_out && (overlaps_input(d_out, out_pitch, {d_bgr1, d_bgr2}, bgr_pitch, 3 * fw, fh)))
+        return bbme::fail(BBME_ERR_INVALID, "%s: the output overlaps an input frame", what);
+    HIP_TRY(hipSetDevice(c->device));
+    if (d_stats4) if (int rc = cb_scratch(c)) return rc;
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_cb(c, d_bgr1, d_bgr2, bgr_pitch, 0, reinterpret_cast<const mv_t *>(d_grid), pitch_cells, 0, 1, unit, fill, window,
+                      d_out, out_pitch, c->cb_stats.partials_caller(), d_stats4, stream);
+}
+
+// The state the context's own calls need, before anything is enqueued: planes and cells as bbme_subpel_device's `which` names them,
+// and the stored colour of pairs pair0 .. pair0 + pairs - 1.  Touches no device.
+static int cb_state(const bbme_ctx *c, int which, int pair0, int pairs, const char *what)
+{
+    const uint8_t *p1, *p2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &p1, &p2, &grid, &s_grid)) return rc;
+    return gcb_source(c, which, pair0, pairs, what, &p1, &p2);
+}
+
+// The context's own: the integer cells of `which` of `pairs` pairs from pair0 on (unit 1) or, with unit 4, those cells refined on
+// the luma planes into the context's quarter-pel buffer as enqueue_own_sc refines them, then the stored colour compensated along them
+static int enqueue_own_cb(bbme_ctx *c, int pair0, int pairs, int which, int unit, int fill, const int *window, uint8_t *d_out,
+                          int out_pitch, unsigned long long *d_stats, hipStream_t stream, const char *what)
+{
+    const uint8_t *i1, *i2, *b1, *b2;
+    const mv_t *grid;
+    uint32_t s_grid;
+    if (int rc = sp_source(c, which, what, &i1, &i2, &grid, &s_grid)) return rc;
+    if (int rc = gcb_source(c, which, pair0, pairs, what, &b1, &b2)) return rc;
+    const Level &L = c->lv[0];
+    const int cw = L.width / 2;
+    const size_t cells = (size_t)cw * (L.height / 2), s_plane = L.plane_stride;
+    grid += (size_t)pair0 * s_grid;
+    size_t s_cells = s_grid;
+    if (unit == 4) {
+        if (int rc = c->sc_q4.ensure(cells * c->batch, "the quarter-pel cells of the compensation", Fill::poison)) return rc;
+        mv_t *q4 = c->sc_q4 + pair0 * cells;
+        if (int rc = enqueue_sp(c, i1 + pair0 * s_plane, i2 + pair0 * s_plane, s_plane, grid, s_grid, pairs, nullptr, q4, cw, cells, nullptr,
+                                nullptr, stream))
+            return rc;
+        grid = q4; s_cells = cells;
+    }
+    return enqueue_cb(c, b1, b2, 3 * c->geom.width, c->bgr_stride, grid, cw, s_cells, pairs, unit, fill, window, d_out, out_pitch,
+                      c->cb_stats.partials_all(), d_stats, stream);
+}
+
+// what bbme_compensate_bgr_device and bbme_get_compensated_bgr_host check alike.  Touches no device.
+static int check_cb_own(const bbme_ctx *c, int pair, int which, int unit, int fill, const void *out, const char *what)
+{
+    if (int rc = check_pair(c, pair)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (int rc = check_cb(c, unit, fill, nullptr, what)) return rc;
+    if (!out) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_sp(c, nullptr, what)) return rc;
+    return cb_state(c, which, pair, 1, what);
+}
+
+int bbme_compensate_bgr_device(bbme_ctx *c, int pair, int which, int unit, int fill, uint8_t *d_out, int out_pitch, void *hip_stream)
+{
+    const char *what = "bbme_compensate_bgr_device";
+    if (int rc = check_cb_own(c, pair, which, unit, fill, d_out, what)) return rc;
+    if (int rc = check_bgr_frames(c, 1, out_pitch, 0, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    hipStream_t stream;
+    if (int rc = stream_behind_ctx(c, hip_stream, &stream)) return rc;
+    return enqueue_own_cb(c, pair, 1, which, unit, fill, nullptr, d_out, out_pitch, nullptr, stream, what);
+}
+
+int bbme_get_compensated_bgr_host(bbme_ctx *c, int pair, int which, int unit, int fill, uint8_t *out)
+{
+    const char *what = "bbme_get_compensated_bgr_host";
+    if (int rc = check_cb_own(c, pair, which, unit, fill, out, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    const int row = 3 * c->geom.width;
+    return download_staged(c, (size_t)row * c->geom.height, "the compensated colour frame", out, [&](uint8_t *d) {
+        return enqueue_own_cb(c, pair, 1, which, unit, fill, nullptr, d, row, nullptr, c->stream, what);
+    });
+}
+
+int bbme_compensation_error_bgr(bbme_ctx *c, int which, int unit, const int *window, unsigned long long *stats)
+{
+    const char *what = "bbme_compensation_error_bgr";
+    if (int rc = check_ctx(c)) return rc;
+    if (int rc = check_which(which, what)) return rc;
+    if (int rc = check_cb(c, unit, 0, window, what)) return rc;
+    if (!stats) return bbme::fail(BBME_ERR_INVALID, "%s: null output", what);
+    if (int rc = check_sp(c, nullptr, what)) return rc;
+    if (int rc = cb_state(c, which, 0, c->batch, what)) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    if (int rc = cb_scratch(c)) return rc;
+    return download_stats(c, c->cb_stats, c->batch, stats, [&] {
+        return enqueue_own_cb(c, 0, c->batch, which, unit, 0, window, nullptr, 0, c->cb_stats.results(), c->stream, what);
     });
 }
 

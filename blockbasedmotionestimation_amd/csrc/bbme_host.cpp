@@ -1271,6 +1271,67 @@ int bbme_global_compensate_bgr_host(const uint8_t *bgr1, const uint8_t *bgr2, in
     return BBME_OK;
 }
 
+// The BGR COMPENSATION RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_compensate_bgr): the SUBPEL
+// COMPENSATION RULE on the zero-padded view of a colour frame, in frame coordinates.  A tap outside the frame is the padding's 0
+// and is not read; neither is a tap of weight 0.
+int bbme_compensate_bgr_host(const uint8_t *bgr1, const uint8_t *bgr2, int width, int height, int bgr_pitch, int pad_x, int pad_y,
+                             const int16_t *grid, int pitch_cells, int unit, int fill, const int *window, uint8_t *out, int out_pitch,
+                             unsigned long long *stats4)
+{
+    const char *what = "bbme_compensate_bgr_host";
+    if (!bgr2 || !grid || (!out && !stats4) || (stats4 && !bgr1)) return bbme::fail(BBME_ERR_INVALID, "%s: null pointer", what);
+    if (width < 1 || height < 1 || pad_x < 0 || pad_y < 0 || (long long)width + 2LL * pad_x > INT32_MAX ||
+        (long long)height + 2LL * pad_y > INT32_MAX)
+        return bbme::fail(BBME_ERR_INVALID, "%s: bad frame %dx%d with padding (%d, %d)", what, width, height, pad_x, pad_y);
+    const int W0 = width + 2 * pad_x, H0 = height + 2 * pad_y;
+    if ((W0 & 1) || (H0 & 1)) return bbme::fail(BBME_ERR_INVALID, "%s: the padded view %dx%d is not a plane of 2x2 cells", what, W0, H0);
+    if (unit != 1 && unit != 4) return bbme::fail(BBME_ERR_INVALID, "%s: unit %d (1 or 4)", what, unit);
+    if (fill < 0 || fill > 255) return bbme::fail(BBME_ERR_INVALID, "%s: fill %d outside 0..255", what, fill);
+    if ((long long)bgr_pitch < 3LL * width) return bbme::fail(BBME_ERR_INVALID, "%s: colour pitch %d < 3 x frame width %d", what, bgr_pitch, width);
+    if (out && (long long)out_pitch < 3LL * width)
+        return bbme::fail(BBME_ERR_INVALID, "%s: output pitch %d < 3 x frame width %d", what, out_pitch, width);
+    const int cw = W0 / 2, ch = H0 / 2;
+    if (pitch_cells < cw) return bbme::fail(BBME_ERR_INVALID, "%s: grid pitch %d < %d cells per row", what, pitch_cells, cw);
+    bbme::CellWindow win;
+    if (int rc = win.set(window, width, height, what, "frame")) return rc;
+    const int mul = 4 / unit;
+    unsigned long long sse = 0, sad = 0, pixels = 0, skipped = 0;
+    for (int cy = 0; cy < ch; ++cy)
+        for (int cx = 0; cx < cw; ++cx) {
+            const int16_t *g = grid + 2 * ((size_t)cy * pitch_cells + cx);
+            const int qx = mul * g[0], qy = mul * g[1];                              // 32 bits: 4 G need not fit int16
+            const int fx = qx & 3, fy = qy & 3;
+            const long long sx = 2LL * cx + (qx >> 2), sy = 2LL * cy + (qy >> 2);    // the padded plane's coordinates
+            const bool ok = 0 <= sx && sx + 2 + (fx != 0) <= W0 && 0 <= sy && sy + 2 + (fy != 0) <= H0;
+            for (int k = 0; k < 2; ++k)
+                for (int j = 0; j < 2; ++j) {
+                    const int x = 2 * cx + j - pad_x, y = 2 * cy + k - pad_y;        // the pixel in frame coordinates
+                    if (x < 0 || x >= width || y < 0 || y >= height) continue;
+                    const bool in = stats4 && win.contains(x, y);
+                    for (int c = 0; c < 3; ++c) {
+                        int v = fill;
+                        if (ok) {
+                            const auto tap = [&](int weight, int dx, int dy) {
+                                const long long tx = sx + j + dx - pad_x, ty = sy + k + dy - pad_y;
+                                if (!weight || tx < 0 || tx >= width || ty < 0 || ty >= height) return 0;
+                                return weight * bgr2[(size_t)ty * bgr_pitch + (size_t)3 * tx + c];
+                            };
+                            v = (tap((4 - fx) * (4 - fy), 0, 0) + tap(fx * (4 - fy), 1, 0) + tap((4 - fx) * fy, 0, 1) + tap(fx * fy, 1, 1) + 8) >> 4;
+                        }
+                        if (out) out[(size_t)y * out_pitch + (size_t)3 * x + c] = (uint8_t)v;
+                        if (!in || !ok) continue;
+                        const int d = v - bgr1[(size_t)y * bgr_pitch + (size_t)3 * x + c];
+                        sse += (unsigned long long)(d * d);
+                        sad += (unsigned long long)(d < 0 ? -d : d);
+                    }
+                    if (!in) continue;
+                    if (ok) ++pixels; else ++skipped;
+                }
+        }
+    if (stats4) { stats4[0] = sse; stats4[1] = sad; stats4[2] = pixels; stats4[3] = skipped; }
+    return BBME_OK;
+}
+
 // The SUBPEL INTERPOLATION RULE of include/bbme.h, cell by cell, in the header's own words (the mirror of k_subpel_interpolate).
 // A tap of weight 0 is not read: it may lie outside the plane.
 int bbme_subpel_interpolate_host(const uint8_t *image1, const uint8_t *image2, int width, int height, const int16_t *qf,

@@ -3272,8 +3272,8 @@ __global__ void k_probe_sad(const uint32_t *a, const uint32_t *b, const uint32_t
 // =======================================================================================
 // What the gather kernels share: k_motion_compensate, K6 k_fb_consistency, K7 k_interpolate, K7b k_interpolate_bgr, K9
 // k_temporal_filter, K9b k_temporal_filter_bgr, K11 k_subpel_compensate, K12 k_subpel_interpolate, K12b k_subpel_interpolate_bgr, K13
-// k_subpel_temporal_filter, K13b k_subpel_temporal_filter_bgr, K14 k_compose_cells, K15 k_wide_temporal_filter and K15b
-// k_wide_temporal_filter_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
+// k_subpel_temporal_filter, K13b k_subpel_temporal_filter_bgr, K14 k_compose_cells, K15 k_wide_temporal_filter, K15b
+// k_wide_temporal_filter_bgr and K11b k_compensate_bgr.  Each is a memory-bound gather in which a lane takes up to k*RunsPerLane runs of 4
 // consecutive units (pixels or 2x2 cells) of one row, blockIdx.x counting workgroups of 256 lanes over the runs_per_row x rows
 // runs of a plane and blockIdx.y / z pairs, phases or frames; each has optional statistics of four counters over a window (K14
 // two of them, K15 six: two quadruples).  The pieces, each written once below and used by every kernel that has the step:
@@ -5715,6 +5715,117 @@ __global__ __launch_bounds__(256) void k_global_compensate_bgr(GcBgrArgs a)
     if (!a.partial) return;
     __shared__ uint32_t part[4][4];
     store_partial4(a.partial, frame, part, sse, sad, npix, nskip);
+}
+
+// =======================================================================================
+// K11b.  The BGR COMPENSATION RULE of include/bbme.h: K11 on the zero-padded view of a colour frame, written as the unpadded frame.
+// Cell (cx, cy) of the padded W0 x H0 plane with origin o = (2 cx, 2 cy) and (qx, qy) = mul * G[cy][cx] in 32 bits (mul = 4 / unit:
+// 4 for a grid of integer cells, whose 4 G need not fit int16, 1 for a quarter-pel grid) has s = o + (qx >> 2, qy >> 2) and
+// f = (qx & 3, qy & 3); it is compensated under K11's condition on the padded plane and its pixels that lie inside the fw x fh
+// frame, at o + (j, k) - (pad_x, pad_y), take in every channel the SUBPEL RULE's sample, a tap outside the frame being the padding's
+// 0; a skipped cell's get `fill`.  K11's layout from the shared pieces: runs of 4 cells of one cell row (gather_index /
+// gather_split), G by load_mv4 with rows grid_pitch cells apart, blockIdx.y = pair (colour frames frame_stride bytes, grids s_grid
+// words apart).  A run with no pixel in the frame loads nothing.
+// Loads.  The cell is K12b's si_bgr_cell at s - pad: up to three frame rows of nine bytes at an arbitrary byte address, unaligned
+// dwords where the pixels lie inside the row, single bytes at the frame's edges, a pixel outside 0 without a load and a row or
+// column of weight 0 not loaded: no byte outside the frame's fw x fh pixels is read.  Stores are K7b's (bgr_row_put /
+// bgr_store_rows: six dwords a row where the run is whole and the row's address dword-aligned, bytes otherwise, nothing outside the
+// frame).  Frame 1's rows arrive by bgr_load_rows where the run is whole and by bgr_two cell by cell otherwise, only for cell rows
+// that meet the window.
+// Statistics over the window [wx0, wx1) x [wy0, wy1) in FRAME pixels: sse and sad over the three channels of the compensated
+// cells' window pixels, pixels and skipped in pixels.  Bound: a lane sums at most RPL runs of 16 pixels of three channels in 32
+// bits, RPL * 16 * 3 * 255^2 = RPL * 3 121 200, and a wave 64 times that, RPL * 199 756 800, which stays below 2^32 up to RPL = 21;
+// RPL = kCbRunsPerLane = 2 (K11's): 399 513 600.  The workgroup's sums are 64-bit (store_partial4, frame = pair; k_mc_reduce): no
+// atomics.  A template, as K12b: its code lies behind the estimate's template kernels in the code object.
+// =======================================================================================
+struct CbArgs {
+    const uint8_t *bgr1, *bgr2;           // fw x fh colour frames, rows bgr_pitch bytes apart; bgr1 may be null without statistics
+    const mv_t *grid;                     // cw entries per row, rows grid_pitch cells apart
+    uint8_t *out;                         // the compensated fw x fh frame (rows out_pitch bytes apart; one pair only), or null
+    unsigned long long *partial;          // per pair and workgroup {sse, sad, pixels, skipped}; or null (no statistics)
+    size_t frame_stride, s_grid;          // from pair to pair: bytes, words
+    int fw, fh, pad_x, pad_y, cw, grid_pitch, bgr_pitch, out_pitch, mul, fill;      // mul = 4 / unit
+    int wx0, wy0, wx1, wy1;
+    int runs_per_row;                     // ceil(cw / 4)
+    long long runs;                       // runs_per_row * ch
+};
+
+constexpr int kCbRunsPerLane = 2;
+
+template <int RPL>
+__global__ __launch_bounds__(256) void k_compensate_bgr(CbArgs a)
+{
+    const size_t pair = blockIdx.y;
+    const uint8_t *C2 = a.bgr2 + pair * a.frame_stride;
+    const mv_t *G = a.grid + pair * a.s_grid;
+    const int FW = a.fw, FH = a.fh, W0 = FW + 2 * a.pad_x, H0 = FH + 2 * a.pad_y;
+    const uint64_t fill6 = (uint64_t)a.fill * 0x010101010101ull;
+    uint32_t sse = 0, sad = 0, npix = 0, nskip = 0;
+#pragma unroll
+    for (int r = 0; r < RPL; ++r) {
+        const long long i = gather_index<RPL>(r);
+        if (i >= a.runs) break;
+        int cy, x0, n;                                        // n cells of the run lie inside the row
+        gather_split(i, a.runs_per_row, a.cw, cy, x0, n);
+        const int oy = 2 * cy;
+        const int ry = oy - a.pad_y, rx = 2 * x0 - a.pad_x;   // the run's first pixel in frame coordinates
+        if (ry + 1 < 0 || ry >= FH || rx + 2 * n <= 0 || rx >= FW) continue;          // no pixel of the run is in the frame
+        uint32_t g[4];
+        load_mv4(G + (size_t)cy * a.grid_pitch + x0, n, g);
+        const bool whole = bgr_run_whole(n, rx, FW);
+        const bool stat = a.partial && ry + 1 >= a.wy0 && ry < a.wy1;
+        uint64_t ref[2][3] = {{0, 0, 0}, {0, 0, 0}};          // frame 1's two rows of a whole run
+        if (stat && whole) bgr_load_rows(a.bgr1 + pair * a.frame_stride, a.bgr_pitch, FH, rx, ry, ref);
+        uint64_t rows[2][3] = {{0, 0, 0}, {0, 0, 0}};         // the run's two output rows, 24 bytes each
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (j >= n) break;
+            const int qx = a.mul * mv_x(g[j]), qy = a.mul * mv_y(g[j]);
+            const int fx = qx & 3, fy = qy & 3;
+            const int sx = 2 * (x0 + j) + (qx >> 2), sy = oy + (qy >> 2);
+            const bool ok = sx >= 0 && sx + 2 + (fx != 0) <= W0 && sy >= 0 && sy + 2 + (fy != 0) <= H0;
+            uint64_t px[2] = {fill6, fill6};                  // the cell's two rows, six bytes each
+            if (ok) {
+                uint32_t e[2][2], gr[2][2];
+                si_bgr_cell(C2, a.bgr_pitch, FW, FH, sx - a.pad_x, sy - a.pad_y, fx, fy, e, gr);
+#pragma unroll
+                for (int y = 0; y < 2; ++y) {
+                    px[y] = 0;
+#pragma unroll
+                    for (int m = 0; m < 2; ++m) px[y] |= (uint64_t)(e[y][m] | gr[y][m] << 8) << (24 * m);
+                }
+            }
+#pragma unroll
+            for (int y = 0; y < 2; ++y) bgr_row_put(rows[y], j, px[y]);
+            if (!stat) continue;
+#pragma unroll
+            for (int y = 0; y < 2; ++y) {
+                if (ry + y < a.wy0 || ry + y >= a.wy1) continue;
+                const uint64_t c1 = whole ? bgr_row_get(ref[y], j)
+                                          : bgr_two(a.bgr1 + pair * a.frame_stride, a.bgr_pitch, FW, FH, rx + 2 * j, ry + y);
+#pragma unroll
+                for (int m = 0; m < 2; ++m) {
+                    const int X = rx + 2 * j + m;
+                    if (X < a.wx0 || X >= a.wx1) continue;
+                    if (ok) {
+#pragma unroll
+                        for (int k = 3 * m; k < 3 * m + 3; ++k) {
+                            const int d = (int)((px[y] >> (8 * k)) & 0xffu) - (int)((c1 >> (8 * k)) & 0xffu);
+                            sse += (uint32_t)(d * d);
+                            sad += (uint32_t)abs(d);
+                        }
+                        ++npix;
+                    } else {
+                        ++nskip;
+                    }
+                }
+            }
+        }
+        if (a.out) bgr_store_rows(a.out, a.out_pitch, FW, FH, rx, ry, n, whole, rows);
+    }
+    if (!a.partial) return;
+    __shared__ uint32_t part[4][4];
+    store_partial4(a.partial, pair, part, sse, sad, npix, nskip);
 }
 
 }  // namespace bbme

@@ -30,6 +30,9 @@
 // resolution, a sixteenth of the pixels of the reference's pipeline; without it sixteenths of a pixel of the frames read.
 // --mc-subpel writes --mc's frame made along those quarter-pel vectors instead (the subpel compensation rule of include/bbme.h:
 // bilinear quarter-pel samples of frame 2), the same unpadded crop, and prints the PSNR of both predictions against frame 1.
+// On colour frames with --no-upsample (which keeps the colour) --mc and --mc-subpel also write the colour prediction (the BGR
+// compensation rule of include/bbme.h along the integer and along the quarter-pel cells) beside the luma's, under the same name
+// with .ppm in place of .pgm, and print its PSNR over the three channels next to the luma's.
 // --interpolate-subpel PREFIX --factor N writes --interpolate's frames made at quarter-pel positions instead (the subpel
 // interpolation rule of include/bbme.h: both fields refined to quarter-pel, every cell placed and sampled at its quarter-pel
 // position of the phase), as PREFIX_k.pgm, the same unpadded crop; on colour frames the frames of their luma and, with
@@ -90,6 +93,14 @@ static bool read_pnm(const char *path, bbme::Image8 &img, bbme::ImageBGR &bgr, b
     }
     fclose(f);
     return ok;
+}
+
+// the colour file that goes beside a grey one: the same name with .ppm in place of .pgm (or behind a name without it)
+static std::string ppm_beside(const char *pgm)
+{
+    std::string name(pgm);
+    if (name.size() >= 4 && name.compare(name.size() - 4, 4, ".pgm") == 0) name.resize(name.size() - 4);
+    return name + ".ppm";
 }
 
 int main(int argc, char **argv)
@@ -238,6 +249,12 @@ int main(int argc, char **argv)
             bbme::check(bbme_pgm_write(mc, img.cols - 2 * px, img.rows - 2 * py, img.cols, img.data.data() + (size_t)py * img.cols + px));
             const bbme::CompensationError e = motion_pair.compensationError(0, 2);
             printf("MC PSNR is %.9g dB over %llu pixels (%llu skipped)\n", e.psnr(), e.pixels, e.skipped);
+            if (colour && !upsample) {                 // the colour frame itself, by the BGR compensation rule along the integer cells
+                const bbme::ImageBGR bgr = motion_pair.drawMVimageBGR(false, 0);
+                bbme::check(bbme_ppm_write_bgr(ppm_beside(mc).c_str(), bgr.cols, bgr.rows, bgr.data.data()));
+                const bbme::CompensationError c = motion_pair.compensationErrorBGR(1);
+                printf("MC colour PSNR is %.9g dB over %llu pixels (%llu skipped)\n", c.psnr(), c.pixels, c.skipped);
+            }
         }
         if (mc_subpel) {
             const bbme::Image8 img = motion_pair.drawMVimageSubpel(false, 0);
@@ -247,6 +264,13 @@ int main(int argc, char **argv)
             const bbme::CompensationError e = motion_pair.compensationError(0, 2), q = motion_pair.compensationErrorSubpel();
             printf("Quarter-pel MC PSNR is %.9g dB (integer vectors: %.9g dB) over %llu pixels (%llu skipped)\n", q.psnr(), e.psnr(),
                    q.pixels, q.skipped);
+            if (colour && !upsample) {                 // the colour frame itself, by the BGR compensation rule along the quarter-pel cells
+                const bbme::ImageBGR bgr = motion_pair.drawMVimageSubpelBGR(false, 0);
+                bbme::check(bbme_ppm_write_bgr(ppm_beside(mc_subpel).c_str(), bgr.cols, bgr.rows, bgr.data.data()));
+                const bbme::CompensationError c1 = motion_pair.compensationErrorBGR(1), c4 = motion_pair.compensationErrorBGR(4);
+                printf("Quarter-pel MC colour PSNR is %.9g dB (integer vectors: %.9g dB) over %llu pixels (%llu skipped)\n", c4.psnr(),
+                       c1.psnr(), c4.pixels, c4.skipped);
+            }
         }
         if (backward) {
             // the subsampled getter reads the context's current field: estimate in direction BACKWARD, then back to FORWARD

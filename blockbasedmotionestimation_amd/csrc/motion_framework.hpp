@@ -296,6 +296,22 @@ public:
         e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3]; e.channels = 3;
         return e;
     }
+    // drawMVimage(0, 2) and drawMVimageSubpel in colour (the BGR COMPENSATION RULE of include/bbme.h, unit 1 and unit 4), for frames
+    // set as B,G,R: the UNPADDED frame, every cell sampled from the stored colour of the other image along the integer cells or
+    // along the cells refined to quarter pels on the luma planes; backward = frame 2 predicted from frame 1 along the backward cells
+    // of estimateBidirectional.
+    bbme::ImageBGR drawMVimageBGR(bool backward = false, int fill = 0) { return compensatedBGR(1, backward, fill); }
+    bbme::ImageBGR drawMVimageSubpelBGR(bool backward = false, int fill = 0) { return compensatedBGR(4, backward, fill); }
+    // The residual statistics of those frames (unit 1 or 4) against the colour frame they predict over window {x0, y0, w, h} in
+    // pixels of the frame (nullptr = the whole frame), sse and sad summed over the three channels.
+    bbme::CompensationError compensationErrorBGR(int unit, bool backward = false, const int *window = nullptr)
+    {
+        unsigned long long s[4] = {0, 0, 0, 0};
+        bbme::check(bbme_compensation_error_bgr(ctx_, backward ? 1 : 0, unit, window, s));
+        bbme::CompensationError e;
+        e.sse = s[0]; e.sad = s[1]; e.pixels = s[2]; e.skipped = s[3]; e.channels = 3;
+        return e;
+    }
     // Direction of the context (include/bbme.h): backward = every estimate and result as if image1 and image2 were exchanged.
     void setDirection(bool backward) { bbme::check(bbme_set_direction(ctx_, backward ? BBME_DIR_BACKWARD : BBME_DIR_FORWARD)); }
     bool direction() const
@@ -457,6 +473,12 @@ private:
         }
         bbme::check(bbme_create(&p, width, height, device, &ctx_));
         bbme::check(bbme_get_geometry(ctx_, &padded_width, &padded_height, &padding_x, &padding_y));
+    }
+    bbme::ImageBGR compensatedBGR(int unit, bool backward, int fill)
+    {
+        bbme::ImageBGR img(padded_height - 2 * padding_y, padded_width - 2 * padding_x);
+        bbme::check(bbme_get_compensated_bgr_host(ctx_, 0, backward ? 1 : 0, unit, fill, img.data.data()));
+        return img;
     }
 #ifdef BBME_WITH_OPENCV
     static bbme::Image8 from_mat(const cv::Mat &m)

@@ -788,6 +788,79 @@ class MF:
             out.stride(0) if out is not None and run else 0, _ptr(stats), C.c_void_p(stream or 0)))
         return out, stats
 
+    # -- motion compensation of the B,G,R frames along the cells (the BGR COMPENSATION RULE of include/bbme.h): needs frames set as
+    # (H, W, 3); unit 1 = the integer cells, unit 4 = the cells refined to quarter pels on the luma planes ------------------------
+    def _get_compensated_bgr(self, pair, which, unit, fill, out, what):
+        out = _host_out(out, (self.orig_height, self.orig_width, 3), np.uint8, what)
+        _capi.check(self._lib.bbme_get_compensated_bgr_host(self._ctx, pair, _which(which), int(unit), int(fill), out.ctypes.data))
+        return out
+
+    def draw_MVimage_bgr(self, which="forward", fill=0, out=None):
+        """draw_MVimage(0, 2) in colour: the UNPADDED (H, W, 3) uint8 frame, every 2x2 cell of the padded plane copied from the
+        stored B,G,R frame of the other image where its integer vector points (the BGR compensation rule, unit 1); a source in
+        the padding reads its zero, a cell whose source leaves the padded plane gives `fill`.  which="forward": frame 1 predicted
+        from frame 2; "backward": frame 2 from frame 1 along the backward cells, after estimate_bidirectional_async().
+        BbmeError (ERR_STATE) when a frame of the pair was set grey."""
+        return self._get_compensated_bgr(0, which, 1, fill, out, "draw_MVimage_bgr")
+
+    def draw_MVimage_subpel_bgr(self, which="forward", fill=0, out=None):
+        """draw_MVimage_subpel in colour: as draw_MVimage_bgr along the cells refined to quarter pels on the luma planes
+        (subpel_cells(which)), every channel sampled bilinearly (the BGR compensation rule, unit 4)."""
+        return self._get_compensated_bgr(0, which, 4, fill, out, "draw_MVimage_subpel_bgr")
+
+    def _compensation_stats_bgr(self, which, unit, window):
+        pairs = getattr(self, "batch", 1)
+        s = (C.c_ulonglong * (4 * pairs))()
+        _capi.check(self._lib.bbme_compensation_error_bgr(self._ctx, _which(which), int(unit), _window(window), s))
+        return [_residual_dict(s[4 * p:4 * p + 4], 3) for p in range(pairs)]
+
+    def compensation_error_bgr(self, which="forward", window=None):
+        """Residual statistics of draw_MVimage_bgr(which) against the colour frame it predicts over window (x0, y0, w, h) in
+        pixels of the FRAME (None = the whole frame): the dict of compensation_error_global_bgr, sse and sad summed over the
+        three channels and mse = sse / (3 pixels)."""
+        return self._compensation_stats_bgr(which, 1, window)[0]
+
+    def compensation_error_subpel_bgr(self, which="forward", window=None):
+        """The same of draw_MVimage_subpel_bgr(which)."""
+        return self._compensation_stats_bgr(which, 4, window)[0]
+
+    def cells_compensate_bgr_device(self, bgr1, bgr2, grid, unit, out=None, stats=None, fill=0, window=None, stream=None):
+        """The BGR compensation rule on any colour frames and any grid in HBM: bgr1 (None without stats) and bgr2 uint8 CUDA
+        tensors (H, W, 3) with packed pixels and a common row pitch; grid an int16 CUDA tensor (CH, CW, 2) whose rows may be
+        further apart than CW cells, integer cells with unit=1 or quarter-pel vectors with unit=4 (what cells_subpel_device
+        wrote); out a uint8 CUDA tensor (H, W, 3) with packed pixels whose rows may be further apart, at any byte address; stats
+        an int64 or uint64 CUDA tensor of 4 (sse, sad, pixels, skipped) over window (x0, y0, w, h) in frame pixels (None = the
+        whole frame).  On the given HIP stream handle (default: the context's), ordered behind the context's stream; no host
+        wait.  Needs no frames and no estimate."""
+        import torch
+        what = "cells_compensate_bgr_device"
+        shape = (self.orig_height, self.orig_width, 3)
+        ch, cw = self.cells_shape
+
+        def frame_ok(t):
+            return t.is_cuda and t.dtype == torch.uint8 and tuple(t.shape) == shape and _packed_pixels(t)
+
+        for t in (bgr2,) if bgr1 is None and stats is None else (bgr1, bgr2):
+            if t is None or not (frame_ok(t) and t.stride(0) == bgr2.stride(0)):
+                raise _capi.BbmeError(_capi.ERR_INVALID, "%s: colour frames must be uint8 CUDA tensors of shape %s with packed pixels "
+                                      "and a common row pitch" % (what, shape))
+        if not (grid.is_cuda and grid.dtype == torch.int16 and tuple(grid.shape) == (ch, cw, 2) and grid.stride(2) == 1
+                and grid.stride(1) == 2 and grid.stride(0) >= 2 * cw and grid.stride(0) % 2 == 0 and grid.data_ptr() % 4 == 0):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: grid must be an int16 CUDA tensor of shape (%d, %d, 2) with packed cells "
+                                  "and rows a whole number of cells apart" % (what, ch, cw))
+        if out is None and stats is None:
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: neither out nor stats" % what)
+        if out is not None and not frame_ok(out):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: out must be a uint8 CUDA tensor of shape %s with packed pixels" % (what, shape))
+        if stats is not None and not (stats.is_cuda and stats.dtype in (torch.int64, torch.uint64) and stats.numel() == 4
+                                      and stats.is_contiguous()):
+            raise _capi.BbmeError(_capi.ERR_INVALID, "%s: stats must be a contiguous int64 or uint64 CUDA tensor of 4" % what)
+        self._behind_torch(bgr1, bgr2, grid, out, stats)
+        _capi.check(self._lib.bbme_cells_compensate_bgr_device(
+            self._ctx, _ptr(bgr1), _ptr(bgr2), bgr2.stride(0), _ptr(grid), grid.stride(0) // 2, int(unit), int(fill), _window(window),
+            _ptr(out), out.stride(0) if out is not None else 0, _ptr(stats), C.c_void_p(stream or 0)))
+        return out, stats
+
     # -- colour coding of the field: Flow::MotionToColor on the GPU, from the cells (the colour rule of include/bbme.h) ----------
     def color_shape(self, scale=None):
         """(rows, cols, 3) of the colour image: the subsampled field's size; scale defaults to upsample."""
@@ -1672,6 +1745,15 @@ class MFBatch(MF):
         """MF.compensation_error_global_bgr of every pair under its own model (models: (pairs, 6) int32), from one launch."""
         return self._global_compensation_stats_bgr(which, models, unit, window)
 
+    def get_pair_motion_compensated_bgr(self, pair, unit=4, which="forward", fill=0, out=None):
+        """MF.draw_MVimage_subpel_bgr (unit=4) or MF.draw_MVimage_bgr (unit=1) of one pair."""
+        return self._get_compensated_bgr(pair, which, unit, fill, out, "get_pair_motion_compensated_bgr")
+
+    def compensation_errors_bgr(self, unit=4, which="forward", window=None):
+        """MF.compensation_error_subpel_bgr (unit=4) or MF.compensation_error_bgr (unit=1) of every pair, in order, from one
+        refinement launch (unit 4 only) and one compensation launch."""
+        return self._compensation_stats_bgr(which, unit, window)
+
     def consistency_stats_all(self, which="forward", tol=1, window=None):
         """MF.consistency_stats of every pair, in order, from one launch."""
         return self._consistency_stats(which, tol, window)
@@ -2155,6 +2237,43 @@ def global_compensate_bgr(c1, c2, model, unit=1, fill=0, pad_x=0, pad_y=0, windo
     _capi.check(_capi.lib().bbme_global_compensate_bgr_host(_ptr(c1), c2.ctypes.data, w, h, c2.strides[0], int(pad_x), int(pad_y),
                                                             model.ctypes.data, int(unit), int(fill), _window(window), out.ctypes.data,
                                                             3 * w, s))
+    return out, (_residual_dict(list(s), 3) if s is not None else None)
+
+
+def compensate_cells_bgr(c1, c2, grid, unit, fill=0, pad_x=0, pad_y=0, window=None):
+    """The BGR compensation rule on the CPU (bbme_compensate_bgr_host): c1 (None without statistics), c2 uint8 (H, W, 3) frames
+    with packed pixels whose rows may be further apart than 3 W bytes (both with the same pitch); grid an int16
+    ((H + 2 pad_y) / 2, (W + 2 pad_x) / 2, 2) grid of the zero-padded view's cells, whose rows may be further apart, holding
+    integer cells (unit=1) or quarter-pel vectors (unit=4) -> (compensated frame (H, W, 3) uint8, dict(sse, sad, pixels, skipped,
+    mse, psnr) against c1 over window (x0, y0, w, h) in frame pixels, or None without c1); sse and sad are summed over the three
+    channels, mse = sse / (3 pixels)."""
+    def frame(a):
+        a = np.asarray(a, np.uint8)
+        if a.ndim == 3 and a.shape[2] == 3 and a.strides[2] == 1 and a.strides[1] == 3 and a.strides[0] >= 3 * a.shape[1]:
+            return a
+        return np.ascontiguousarray(a)
+
+    c2 = frame(c2)
+    if c1 is not None:
+        c1 = frame(c1)
+        if c1.strides[0] != c2.strides[0]:
+            c1, c2 = np.ascontiguousarray(c1), np.ascontiguousarray(c2)
+    if c2.ndim != 3 or c2.shape[2] != 3 or (c1 is not None and c1.shape != c2.shape):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "compensate_cells_bgr: uint8 frames of one shape (H, W, 3)")
+    h, w = c2.shape[:2]
+    grid = np.asarray(grid, np.int16)
+    if grid.ndim != 3 or grid.shape[2] != 2:
+        raise _capi.BbmeError(_capi.ERR_INVALID, "compensate_cells_bgr: an int16 grid (CH, CW, 2)")
+    if not (grid.strides[2] == 2 and grid.strides[1] == 4 and grid.strides[0] >= 4 * grid.shape[1] and grid.strides[0] % 4 == 0):
+        grid = np.ascontiguousarray(grid)
+    if (2 * grid.shape[0], 2 * grid.shape[1]) != (h + 2 * int(pad_y), w + 2 * int(pad_x)):
+        raise _capi.BbmeError(_capi.ERR_INVALID, "compensate_cells_bgr: a grid of %s cells does not cover the %dx%d frame padded by "
+                              "(%d, %d)" % (grid.shape[:2], w, h, pad_x, pad_y))
+    out = np.empty((h, w, 3), np.uint8)
+    s = (C.c_ulonglong * 4)() if c1 is not None else None
+    _capi.check(_capi.lib().bbme_compensate_bgr_host(_ptr(c1), c2.ctypes.data, w, h, c2.strides[0], int(pad_x), int(pad_y),
+                                                     grid.ctypes.data, grid.strides[0] // 4, int(unit), int(fill), _window(window),
+                                                     out.ctypes.data, 3 * w, s))
     return out, (_residual_dict(list(s), 3) if s is not None else None)
 
 

@@ -676,6 +676,46 @@ def stabilize_frames(frames, search_size, block_size, radius=None, kind="transla
     return out, models, corrections
 
 
+def predict_frames(frames, search_size, block_size, subpel=True, in_flight=4, batch=2, device=None):
+    """The motion-compensated prediction of every frame of a video from the next one, and its residual, on ONE GPU ->
+    (predictions, stats): for every consecutive pair (f_k, f_k+1) the prediction of f_k from f_k+1 along the pair's field, an
+    unpadded uint8 frame shaped as the frames came, and stats (P, 4) uint64, row k = (sse, sad, pixels, skipped) of that
+    prediction against f_k over the unpadded frame.  On the chain plan of estimate_frames_pipelined (every frame is set once);
+    a round's statistics come from one launch over its pairs.  subpel=True predicts along the cells refined to quarter pels on
+    the level-0 (luma) planes, subpel=False along the integer cells.
+    Grey video: the unpadded crop of MF.draw_MVimage_subpel / draw_MVimage(0, 2) and the statistics of
+    compensation_errors_subpel / compensation_errors over the unpadded frame.
+    Colour video, (H, W, 3) frames in B,G,R order: the chains are fed the colour frames, so the fields are those of the grey
+    call on bgr_to_gray(video); predictions and statistics are the BGR compensation rule's on the stored colour
+    (get_pair_motion_compensated_bgr, compensation_errors_bgr), sse and sad summed over the three channels."""
+    frames = [np.ascontiguousarray(f, np.uint8) for f in frames]
+    n_pairs = len(frames) - 1
+    if n_pairs < 1:
+        return [], np.zeros((0, 4), np.uint64)
+    bgr = frames[0].ndim == 3
+    if device is None:
+        device = local_device()
+    out = [None] * n_pairs
+    stats = np.zeros((n_pairs, 4), np.uint64)
+
+    def collect(mf, first, count):
+        h, w, py, px = mf.orig_height, mf.orig_width, mf.padding_y, mf.padding_x
+        if bgr:
+            errors = mf.compensation_errors_bgr(unit=4 if subpel else 1)              # waits for this context's stream only
+        else:
+            errors = mf.compensation_errors_subpel() if subpel else mf.compensation_errors(0, 2)
+        for p in range(count):
+            if bgr:
+                out[first + p] = mf.get_pair_motion_compensated_bgr(p, unit=4 if subpel else 1)
+            else:
+                plane = mf.get_pair_motion_compensated_subpel(p) if subpel else mf.get_pair_motion_compensated(p, 0, 2)
+                out[first + p] = np.ascontiguousarray(plane[py:py + h, px:px + w])
+            stats[first + p] = [errors[p][k] for k in ("sse", "sad", "pixels", "skipped")]
+
+    _walk_chains(frames, search_size, block_size, device, in_flight, batch, collect)
+    return out, stats
+
+
 def colorize_frames(frames, search_size, block_size, maxmotion=-1.0, scale=1, in_flight=4, batch=2, device=None):
     """The colour-coded forward field of the len(frames) - 1 consecutive pairs of a video on ONE GPU (the colour rule of
     include/bbme.h at subsampling `scale`): -> ((P, oh, ow, 3) uint8 B,G,R images, (P, 5) float32 ranges (max radius, min u,

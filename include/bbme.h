@@ -795,7 +795,8 @@ int bbme_get_subpel_flow_host(bbme_ctx *ctx, int pair, int which, float *flow);
  * four are exact 64-bit integers and do not depend on `fill`.  A window may cut cells: each pixel counts on its own.
  * Property.  With Q = 4 G for an integer grid G, the frame and the statistics are those of the compensation rule at level 0 with
  * block 2 and grid_block 2, bit for bit.
- * A context made for up-sampled frames compensates its 4x planes, a colour context its luma planes.
+ * A context made for up-sampled frames compensates its 4x planes, a colour context its luma planes (its colour frames: the BGR
+ * COMPENSATION RULE below).
  * Errors: BBME_ERR_INVALID for a null context or required pointer, a pair out of range, `which` not 0 or 1, a fill outside
  * 0..255, a window not inside the plane, q4_pitch_cells < CW, out_pitch < W0, a d_out of bbme_cells_subpel_compensate_device
  * that overlaps an input plane, an odd width or height on the host call; for the context's own calls BBME_ERR_UNSUPPORTED beyond
@@ -1364,6 +1365,65 @@ int bbme_global_compensate_bgr_device(bbme_ctx *ctx, int pair, int which, const 
 int bbme_get_global_compensated_bgr_host(bbme_ctx *ctx, int pair, int which, const int32_t *model, int unit, int fill, uint8_t *out);
 int bbme_global_compensation_error_bgr(bbme_ctx *ctx, int which, const int32_t *models, int unit, const int *window,
                                        unsigned long long *stats);
+
+/* BGR COMPENSATION RULE (this project's own; MF::draw_MVimage, motion_framework.cpp:887-905, is grey): the SUBPEL COMPENSATION RULE
+ * applied to the zero-padded view of a colour frame; it writes the unpadded frame, as every other BGR rule does.  It is the colour
+ * form of per-cell motion compensation, along integer cells or along quarter-pel cells.
+ * Inputs: two colour frames C1 and C2, each W x H pixels of B,G,R with rows bgr_pitch >= 3 W bytes apart (C1 for the statistics
+ * only); pad_x and pad_y, with W0 = W + 2 pad_x and H0 = H + 2 pad_y (both even, as every padded plane is); a grid of CH x CW int16
+ * pairs, CH = H0 / 2, CW = W0 / 2, rows pitch_cells >= CW pairs apart; unit (1 or 4); fill (0..255).  With unit 4 the grid holds
+ * quarter-pel vectors as the bbme_subpel_* calls write them, (qx, qy) = Q[cy][cx].  With unit 1 it holds integer cells G and
+ * (qx, qy) = 4 G[cy][cx] computed in 32 bits: any int16 is allowed and 4 G need not fit int16, which is why the unit exists.
+ * Cell.  For cell (cx, cy) of the padded plane, o, i, f and s are exactly those of the SUBPEL COMPENSATION RULE, and the cell is
+ * COMPENSATED under that rule's condition on the W0 x H0 plane: 0 <= s.x, s.x + 2 + (fx != 0) <= W0, 0 <= s.y and
+ * s.y + 2 + (fy != 0) <= H0.
+ * Pixels.  Each of the cell's four pixels lies at frame coordinates o + (j, k) - (pad_x, pad_y); a pixel inside [0, W) x [0, H) is
+ * written and the others are not: with an odd pad a cell straddles the frame's edge.  A compensated cell's pixel takes, in every
+ * channel, the SUBPEL RULE's sample of that channel at s + (j, k) with the fractions f and the single rounding (... + 8) >> 4, where
+ * a tap whose frame coordinates lie outside the frame reads 0 -- the zero border of the luma planes -- and a tap of weight 0 is
+ * never read.  A skipped cell's pixels get `fill` in all three channels.  No byte outside the frames' W x H pixels is read and no
+ * byte outside the output's W x H pixels is written.
+ * Statistics: four words {sse, sad, pixels, skipped} against C1 over a window {x0, y0, w, h} in FRAME pixels (NULL = the whole
+ * frame): sse and sad are summed over the three channels of the window pixels of compensated cells, pixels counts those pixels and
+ * skipped the window pixels of skipped cells (the mirrors derive mse = sse / (3 pixels) and psnr from it, as for the BGR GLOBAL
+ * COMPENSATION RULE); all four are exact 64-bit integers and do not depend on `fill`.
+ * Properties.  On B = G = R frames every channel of the output is the unpadded crop of bbme_subpel_compensate_host on
+ * pad_zero(grey) and, with unit 1, of the integer compensation rule at level 0 with block 2 and grid_block 2; sse and sad are three
+ * times the grey figures over the same window, pixels and skipped are equal.  With pads of 0 each channel is the grey rule on that
+ * channel.  Unit 1 on G equals unit 4 on 4 G wherever 4 G fits int16.  A zero grid returns C2, and its statistics are the plain
+ * frame difference.
+ * Errors: as the SUBPEL COMPENSATION RULE's and the BGR GLOBAL COMPENSATION RULE's: BBME_ERR_INVALID for a null context or required
+ * pointer, a pair out of range, `which` not 0 or 1, unit not 1 or 4, a fill outside 0..255, bgr_pitch or out_pitch < 3 W,
+ * pitch_cells < CW, a window not inside the frame, an odd W0 or H0 on the host call, a d_out of bbme_cells_compensate_bgr_device
+ * that overlaps an input frame; BBME_ERR_STATE where stored colour is asked for and a frame has none (a grey setter withdraws it),
+ * and exactly as bbme_subpel_device for the cells (either unit); for the context's own calls BBME_ERR_UNSUPPORTED beyond 8188.  No
+ * call changes context state (grids, memo, flow, cells, backward cells, captured graphs, colour store).  All work on single, batched
+ * and chain contexts.
+ * bbme_compensate_bgr_host: the rule on the CPU, no GPU; bgr1 may be NULL without stats4; out (rows out_pitch bytes apart) and
+ * stats4 each may be NULL, not both.  It has no size limit of its own.
+ * bbme_cells_compensate_bgr_device: ANY colour frames of the context's frame size (a common bgr_pitch) and ANY grid in HBM of the
+ * context's cell geometry, grid rows pitch_cells int16 pairs apart (bbme_subpel_device's strided output can be fed straight in);
+ * no frames set and no estimate needed; d_bgr1 may be null without d_stats4; d_out and d_stats4 each may be null, not both.  On
+ * hip_stream (NULL = the ctx stream; another stream is first ordered behind it); no host wait.  Launches with d_stats4 share one
+ * scratch buffer per context: the caller orders those it issues on different streams.
+ * bbme_compensate_bgr_device: the stored colour of `pair` (the COLOUR STORE).  With unit 4 the cells of `pair` are refined on the
+ * LUMA planes (bbme_subpel_device's `which`) into the quarter-pel buffer bbme_subpel_compensate_device uses, then the colour is
+ * compensated from it; with unit 1 the integer cells are read as they are and no refinement is launched.  which = 0 predicts
+ * frame 1 from frame 2 along the current cells (in direction BACKWARD the frames exchange, as in
+ * bbme_global_compensate_bgr_device), which = 1 frame 2 from frame 1 along the backward cells of bbme_estimate_bidirectional.  On a
+ * chain the frames are slots pair and pair + 1.  The caller orders calls for the same pair that it issues on different streams.
+ * bbme_get_compensated_bgr_host: the same; synchronises; packed rows of 3 W bytes.
+ * bbme_compensation_error_bgr: EVERY pair of the context, stats[4 p + k], from at most one refinement launch (unit 4; none with
+ * unit 1) and one compensation launch over all pairs; every pair needs its stored colour; synchronises. */
+int bbme_compensate_bgr_host(const uint8_t *bgr1, const uint8_t *bgr2, int width, int height, int bgr_pitch, int pad_x, int pad_y,
+                             const int16_t *grid, int pitch_cells, int unit, int fill, const int *window, uint8_t *out, int out_pitch,
+                             unsigned long long *stats4);
+int bbme_cells_compensate_bgr_device(bbme_ctx *ctx, const uint8_t *d_bgr1, const uint8_t *d_bgr2, int bgr_pitch, const int16_t *d_grid,
+                                     int pitch_cells, int unit, int fill, const int *window, uint8_t *d_out, int out_pitch,
+                                     unsigned long long *d_stats4, void *hip_stream);
+int bbme_compensate_bgr_device(bbme_ctx *ctx, int pair, int which, int unit, int fill, uint8_t *d_out, int out_pitch, void *hip_stream);
+int bbme_get_compensated_bgr_host(bbme_ctx *ctx, int pair, int which, int unit, int fill, uint8_t *out);
+int bbme_compensation_error_bgr(bbme_ctx *ctx, int which, int unit, const int *window, unsigned long long *stats);
 
 /* ---- single stages, for parity tests against the reference's private methods (single-pair contexts only) -------- */
 
